@@ -1,12 +1,18 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: Whitted render of the reference scene at 1920x1080, depth 8.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A "step" is one frame: every rank renders its interleaved row band of the frame with the HIP kernel
 (homework-18-graphics-raytracer_amd/csrc/rt_pwf.hip by default, through the C ABI) and, for N > 1, the bands
 are gathered to rank 0 over RCCL.  Rays = World::cast evaluations (primary + shadow + reflection +
 refraction casts), counted by the kernel itself.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the headline.  --full adds everything else the line can
+carry, after the headline's timed region: the CPU oracle's baseline and its bit-for-bit check of the frame, two frames
+in flight, the depth-of-field and scatter passes, sharded_finish, share_timing and large_scene (each still subject to
+its --no-* switch).  --dump-outputs DIR writes what the last timed step computed (rank 0's assembled frame and the
+casts per frame) as DIR/*.npy.
 
 For N > 1 the driver launches this file under `python -m torch.distributed.run`; when started plainly
 with --gpus N > 1 it starts that launcher itself as a child process.
@@ -50,7 +56,48 @@ def parse_args():
                    help="N > 1 only: frames a rank renders at once, one per stream (dist.FramePipeline in_flight); 0 = 4, each launch on a quarter of the "
                         "device (a share of the frame leaves the GPU mostly idle: profiles/r04_frames_in_flight.txt); 1 = one after the other")
     p.add_argument("--no-extras", action="store_true", help="skip the sharded_finish, share_timing and large_scene objects (after everything else)")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="after the headline, also run the CPU baseline (with its bit-for-bit check), the pipelined, stochastic and scatter "
+                        "passes and the extras; without it a run does only what the headline needs")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's outputs (frame.npy float32, casts_per_frame.npy float64) to DIR")
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    if not args.full:
+        args.no_cpu_baseline = args.no_pipelined = args.no_stochastic = args.no_extras = True
+    return args
+
+
+DUMP_MAX_BYTES = 60_000_000  # every file of --dump-outputs together stays below 64 MB
+
+
+def dump_outputs(directory, frame, casts_per_frame):
+    """The timed path's outputs of its last step: the frame (rows, cols, 3) float32 as rank 0 holds it, and the casts per frame.
+    A frame too large for the budget is written as a fixed sample of its pixels (seed 0, in pixel order) with their indices."""
+    import numpy as np
+
+    out = Path(directory)
+    out.mkdir(parents=True, exist_ok=True)
+    img = np.ascontiguousarray(frame.detach().cpu().numpy(), dtype=np.float32)
+    if img.nbytes <= DUMP_MAX_BYTES:
+        np.save(out / "frame.npy", img)
+    else:
+        pixels = img.reshape(-1, 3)
+        n = DUMP_MAX_BYTES // (3 * 4 + 8)
+        idx = np.sort(np.random.default_rng(0).choice(pixels.shape[0], size=n, replace=False))
+        np.save(out / "frame_sample.npy", pixels[idx])
+        np.save(out / "frame_sample_pixel_index.npy", idx.astype(np.float64))
+    np.save(out / "casts_per_frame.npy", np.array([casts_per_frame], dtype=np.float64))
+
+
+def built_and_current(entry) -> bool:
+    """True when make has nothing to do in the directories build() makes (`make -q` only reads the tree).  A library that is
+    being built reads as out of date: its objects are newer than it until it is renamed into place."""
+    for directory in (entry.PKG / "csrc", entry.ROOT / "oracle"):
+        if subprocess.run(["make", "-q", "-C", str(directory)], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL).returncode != 0:
+            return False
+    return True
 
 
 def relaunch_under_torchrun(args) -> int:
@@ -450,9 +497,11 @@ def main() -> int:
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    # every rank, before anything imports the package or touches the GPU: the makes run under a file lock, so one rank builds (a
-    # no-op when the in-tree libraries are current) and the others wait for it instead of loading a library that is being linked
-    __graft_entry__.build()
+    # every rank, before anything imports the package or touches the GPU: when make has something to do, build() runs the makes
+    # under a file lock, so one rank builds and the others wait for it instead of loading a library that is being linked.  When
+    # everything is current nothing is written: a tree built beforehand may be read-only to the user who benchmarks it
+    if not built_and_current(__graft_entry__):
+        __graft_entry__.build()
     import torch
     import torch.distributed as dist
 
@@ -565,6 +614,8 @@ def main() -> int:
     elapsed_max, kernel_ms_max = float(t[0].item()), float(t[1].item())
     casts_all_steps = int(total_casts.item())
     casts_per_frame = casts_all_steps // max(1, args.steps)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, full, casts_per_frame)
 
     if rank == 0:
         ms_per_step = elapsed_max * 1e3 / args.steps
