@@ -8,6 +8,7 @@ reference's host-side names on top of them:
     World / ObjectProxy            src/main.rs:130-178, 700-728
     Camera                         src/main.rs:43-49
     render (the Whitted par_iter)  src/main.rs:1087-1104
+    cast_rays (World::cast)        src/main.rs:180-326, on caller-supplied rays
     post_process / write_to_file   src/main.rs:748-776
 
 PyTorch is used only for device memory, streams and torch.distributed.
@@ -25,7 +26,7 @@ from ._capi import Camera, Frame, Light, Material, RtError, SceneDesc, Sphere, T
 
 __all__ = [
     "World", "ObjectProxy", "Scene", "Camera", "Frame", "Material", "Light", "RtError", "reference_world",
-    "reference_camera", "render_whitted", "render_whitted_numpy", "Rng", "render_distributed", "render_distributed_numpy", "set_option", "options", "post_process_device", "encode_srgb8_device", "post_process", "encode_srgb8", "write_to_file",
+    "reference_camera", "render_whitted", "render_whitted_numpy", "make_rays", "cast_rays", "Hits", "camera_rays", "cast_rays_numpy", "Rng", "render_distributed", "render_distributed_numpy", "set_option", "options", "post_process_device", "encode_srgb8_device", "post_process", "encode_srgb8", "write_to_file",
     "DEFAULT_OBJ",
 ]
 
@@ -191,6 +192,140 @@ def render_whitted_numpy(scene: Scene, camera: Camera, frame: Frame):
         _capi.amd_lib().rt_render_whitted_host(scene._h, C.byref(camera), C.byref(frame), img.ctypes.data_as(C.c_void_p), C.byref(casts))
     )
     return img, int(casts.value)
+
+
+# ---- ray queries: World::cast on caller-supplied rays (include/rt_amd.h rt_cast_rays) ----
+
+FRONT, BACK, BOTH = 0, 1, 2  # FaceDirection, main.rs:52-57
+SPHERE, TRIANGLE = 0, 1      # PrimitiveIndex, primitives.rs:31-34
+HIT_NONE = -1                # RT_HIT_NONE seen as int32: the cast returned None
+RAY_DTYPE = np.dtype([("origin", "<f4", 3), ("direction", "<f4", 3), ("face_direction", "<u4"), ("has_exclude", "<u4"),
+                      ("exclude_kind", "<u4"), ("exclude_index", "<u4"), ("exclude_face", "<u4")])  # rt_ray, 44 bytes
+HIT_DTYPE = np.dtype([("kind", "<u4"), ("index", "<u4"), ("object_index", "<u4"), ("position", "<f4", 3), ("normal", "<f4", 3),
+                      ("uv", "<f4", 2), ("face_direction", "<u4"), ("distance", "<f4")])  # rt_hit, 52 bytes
+
+
+def make_rays(origins, directions, face=FRONT, exclude_kind=None, exclude_index=None, exclude_face=BOTH):
+    """Pack rays into an (N, 11) int32 CUDA tensor of rt_ray records, on the device.
+
+    origins, directions: (N, 3) float32 CUDA tensors (directions are used as given: cast does not normalise them).
+    face, exclude_face: FRONT / BACK / BOTH, scalars or (N,) tensors.
+    exclude_kind, exclude_index: both None (no exclusion), or scalars / (N,) tensors: SPHERE or TRIANGLE and the index in that
+    array; a negative kind means no exclusion for that ray, and an index beyond its array excludes nothing (as in the reference)."""
+    import torch
+
+    for name, t in (("origins", origins), ("directions", directions)):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.shape[1] == 3):
+            raise ValueError(f"{name} must be an (N, 3) float32 CUDA tensor")
+    n = origins.shape[0]
+    if directions.shape[0] != n:
+        raise ValueError("origins and directions differ in length")
+    dev = origins.device
+
+    def column(v, name):
+        if torch.is_tensor(v):
+            if v.shape != (n,):
+                raise ValueError(f"{name} must be a scalar or an (N,) tensor")
+            return v.to(device=dev, dtype=torch.int64)
+        return torch.full((n,), int(v), dtype=torch.int64, device=dev)
+
+    rays = torch.zeros((n, 11), dtype=torch.int32, device=dev)
+    rays[:, 0:3] = origins.view(torch.int32)
+    rays[:, 3:6] = directions.view(torch.int32)
+    rays[:, 6] = column(face, "face").to(torch.int32)
+    if (exclude_kind is None) != (exclude_index is None):
+        raise ValueError("exclude_kind and exclude_index go together")
+    if exclude_kind is not None:
+        kind = column(exclude_kind, "exclude_kind")
+        some = kind >= 0
+        rays[:, 7] = some.to(torch.int32)
+        rays[:, 8] = torch.where(some, kind, torch.zeros_like(kind)).to(torch.int32)
+        rays[:, 9] = torch.where(some, column(exclude_index, "exclude_index"), torch.zeros_like(kind)).to(torch.int32)
+        rays[:, 10] = torch.where(some, column(exclude_face, "exclude_face"), torch.zeros_like(kind)).to(torch.int32)
+    return rays
+
+
+def _records(t, words, name):
+    import torch
+
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.dim() == 2 and t.shape[1] == words):
+        raise ValueError(f"{name} must be a contiguous (N, {words}) int32 CUDA tensor")
+
+
+def cast_rays(scene: Scene, rays, out=None, stream=None):
+    """World::cast (src/main.rs:180-326) for every ray of an (N, 11) int32 CUDA tensor of rt_ray records (make_rays, camera_rays):
+    returns ``out``, an (N, 13) int32 CUDA tensor of rt_hit records (allocated if None; Hits names its fields), bit-identical to the
+    reference's cast.  Stream-ordered on ``stream`` (default: torch's current stream)."""
+    import torch
+
+    _records(rays, 11, "rays")
+    n = rays.shape[0]
+    if out is None:
+        out = torch.empty((n, 13), dtype=torch.int32, device=rays.device)
+    _records(out, 13, "out")
+    if out.shape[0] != n:
+        raise ValueError("out must have one record per ray")
+    s = stream if stream is not None else torch.cuda.current_stream()
+    _capi.check(_capi.amd_lib().rt_cast_rays(scene._h, C.c_void_p(rays.data_ptr()), n, C.c_void_p(out.data_ptr()), C.c_void_p(s.cuda_stream)))
+    return out
+
+
+class Hits:
+    """Named views of an (N, 13) int32 tensor of rt_hit records (what cast_rays returns), on the same storage."""
+
+    def __init__(self, records):
+        import torch
+
+        if not (torch.is_tensor(records) and records.dtype == torch.int32 and records.dim() == 2 and records.shape[1] == 13):
+            raise ValueError("expected an (N, 13) int32 tensor of rt_hit records")
+        self.records = records
+        self.kind = records[:, 0]               # SPHERE, TRIANGLE or HIT_NONE
+        self.index = records[:, 1]              # in the sphere or the triangle array
+        self.object_index = records[:, 2]
+        self.position = records[:, 3:6].view(torch.float32)
+        self.normal = records[:, 6:9].view(torch.float32)
+        self.uv = records[:, 9:11].view(torch.float32)
+        self.face = records[:, 11]              # FRONT or BACK
+        self.distance = records[:, 12].view(torch.float32)
+
+    @property
+    def hit(self):
+        """bool mask: the cast returned Some."""
+        return self.kind != HIT_NONE
+
+    def __len__(self):
+        return self.records.shape[0]
+
+
+def camera_rays(camera: Camera, frame: Frame, out=None, stream=None):
+    """The primary rays Camera::shoot(clip(x, y)) of a frame or tile (src/main.rs:83-99, 1093-1096), as an (rows * cols, 11) int32 CUDA
+    tensor of rt_ray records in the tile's compact row order — the rays the Whitted pass casts first, bit for bit."""
+    import torch
+
+    n = frame.rows * frame.cols
+    if out is None:
+        out = torch.empty((n, 11), dtype=torch.int32, device="cuda")
+    _records(out, 11, "out")
+    if out.shape[0] != n:
+        raise ValueError("out must have rows * cols records")
+    s = stream if stream is not None else torch.cuda.current_stream()
+    _capi.check(_capi.amd_lib().rt_camera_rays(C.byref(camera), C.byref(frame), C.c_void_p(out.data_ptr()), C.c_void_p(s.cuda_stream)))
+    return out
+
+
+def cast_rays_numpy(scene: Scene, rays_np) -> np.ndarray:
+    """Host-buffer convenience (rt_cast_rays_host, synchronous): rays as a RAY_DTYPE structured array or an (N, 11) array of 4-byte
+    words; returns the hits as a HIT_DTYPE structured array."""
+    a = np.asarray(rays_np)
+    if a.dtype == RAY_DTYPE:
+        a = np.ascontiguousarray(a).reshape(-1)
+    elif a.ndim == 2 and a.shape[1] == 11 and a.dtype.itemsize == 4:
+        a = np.ascontiguousarray(a).view(RAY_DTYPE).reshape(-1)
+    else:
+        raise ValueError("expected a RAY_DTYPE array or an (N, 11) array of 4-byte words")
+    hits = np.zeros(a.shape[0], dtype=HIT_DTYPE)
+    _capi.check(_capi.amd_lib().rt_cast_rays_host(scene._h, a.ctypes.data_as(C.c_void_p), a.shape[0], hits.ctypes.data_as(C.c_void_p)))
+    return hits
 
 
 class Rng:

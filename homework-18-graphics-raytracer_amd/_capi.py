@@ -119,6 +119,26 @@ class Frame(C.Structure):
         return (self.y1 - self.y0 + self.y_step - 1) // self.y_step
 
 
+class Ray(C.Structure):  # main.rs:69-81 Ray + Option<Exclusion>, flattened (rt_ray)
+    _fields_ = [
+        ("origin", C.c_float * 3), ("direction", C.c_float * 3), ("face_direction", C.c_uint32),
+        ("has_exclude", C.c_uint32), ("exclude_kind", C.c_uint32), ("exclude_index", C.c_uint32),
+        ("exclude_face", C.c_uint32),
+    ]
+
+
+class Hit(C.Structure):  # main.rs:139-147 Hit, flattened (rt_hit)
+    _fields_ = [
+        ("kind", C.c_uint32), ("index", C.c_uint32), ("object_index", C.c_uint32), ("position", C.c_float * 3),
+        ("normal", C.c_float * 3), ("uv", C.c_float * 2), ("face_direction", C.c_uint32), ("distance", C.c_float),
+    ]
+
+
+RT_HIT_NONE = 0xFFFFFFFF
+RAY_WORDS = C.sizeof(Ray) // 4  # 11
+HIT_WORDS = C.sizeof(Hit) // 4  # 13
+
+
 # every symbol include/rt_amd.h declares (checked by tests/test_capi_symbols.py)
 DEFAULT_VARIANT = 18  # RT_VARIANT_PWF | RT_VARIANT_STATIC (csrc/rt_kernels.h)
 
@@ -142,6 +162,7 @@ AMD_SYMBOLS = [
     "rt_scene_create", "rt_scene_destroy", "rt_render_whitted", "rt_render_whitted_host", "rt_set_option", "rt_set_variant",
     "rt_get_variant", "rt_set_wavefront_budget", "rt_set_distributed_split", "rt_profile_enable", "rt_profile_read", "rt_profile_read_distributed", "rt_math_eval_host", "rt_math_eval_device", "rt_scene_describe_nodes", "rt_rng_state_words", "rt_rng_create",
     "rt_rng_destroy", "rt_rng_download", "rt_render_distributed", "rt_render_distributed_host", "rt_multi_create", "rt_multi_destroy", "rt_multi_render_whitted_host", "rt_multi_render_distributed_host", "rt_multi_render_whitted", "rt_multi_render_distributed", "rt_post_process_device", "rt_post_keys_device", "rt_post_hist_device", "rt_post_pick_device", "rt_post_scale_device", "rt_post_release", "rt_encode_srgb8_device", "rt_accumulate_device", "rt_accumulator_resolve_device",
+    "rt_cast_rays", "rt_cast_rays_host", "rt_camera_rays",
 ]
 HOST_SYMBOLS = [
     "rt_world_new", "rt_world_free", "rt_world_push_object", "rt_world_push_triangle", "rt_world_push_sphere",
@@ -251,6 +272,9 @@ def amd_lib() -> C.CDLL:
         lib.rt_profile_read.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_uint)]
         lib.rt_math_eval_host.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
         lib.rt_math_eval_device.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        lib.rt_cast_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        lib.rt_cast_rays_host.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.rt_camera_rays.argtypes = [C.POINTER(Camera), C.POINTER(Frame), C.c_void_p, C.c_void_p]
         lib.rt_scene_describe_nodes.argtypes = [C.POINTER(SceneDesc), C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32)]
         _amd = lib
     return _amd

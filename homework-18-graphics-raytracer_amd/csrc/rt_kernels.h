@@ -104,6 +104,7 @@ enum Option : int {
     OPT_BFS_WALK_TRIANGLES, /* scenes of at least this many triangles are walked breadth-first by the wavefront kernel (0: never); read by rt_scene_create */
     OPT_WF_SHARE,           /* n > 1: a launch of the persistent wavefront kernel takes 1/n of the workgroups the device holds — a caller with n frames in flight on n streams runs them side by side instead of one behind the other's tail */
     OPT_DIAG_BFS_CAP,       /* test hook: that walk's record lists hold this many records at most (default: RT_BFS_ITEMS_CAP / RT_BFS_JOBS_CAP): a wave-cast that needs more takes the wave-uniform walk */
+    OPT_QUERY_WAVE_UNIFORM, /* 1: rt_cast_rays sends every wave through cast_asm (the wave-uniform walk) instead of cast_pairs / cast_bfs */
     OPT_COUNT
 };
 long long option(Option id, long long unset);
@@ -221,6 +222,16 @@ hipError_t launch_encode_srgb8(const float *rgb, size_t n_values, unsigned char 
 hipError_t launch_accumulate(const float *samples, const unsigned char *valid, uint32_t n_epochs, size_t n_pixels, float *sum, float *weight,
                              hipStream_t stream);
 hipError_t launch_accumulator_resolve(const float *sum, const float *weight, size_t n_pixels, float *rgb, hipStream_t stream);
+
+/* ray queries (rt_query.hip): World::cast on caller-supplied rays, Camera::shoot of a frame's pixels.  The rays of a batch are
+ * unrelated, so a wave of 64 of them takes the pair-wise cast (wave_uniform: cast_asm for every wave); a scene with bfs_walk takes
+ * the breadth-first walk when bfs_scratch is set (per wave of its grid, as in PwParams: two level lists of items_cap records and a
+ * job list of jobs_cap records), on bfs_groups workgroups of RT_QUERY_BFS_WAVES waves */
+#define RT_QUERY_BFS_WAVES 8u
+hipError_t launch_cast_rays(const KernelScene &sc, const rt_ray *rays, rt_hit *hits, uint32_t n_rays, bool wave_uniform, hipStream_t stream);
+hipError_t launch_cast_rays_bfs(const KernelScene &sc, const rt_ray *rays, rt_hit *hits, uint32_t n_rays, uint32_t *bfs_scratch,
+                                uint32_t items_cap, uint32_t jobs_cap, uint32_t bfs_groups, hipStream_t stream);
+hipError_t launch_camera_rays(const KernelFrame &fr, rt_ray *rays, hipStream_t stream);
 
 /* diagnostics: evaluate rt_detmath on the device (op codes = rt_math_op) */
 hipError_t launch_math_eval(int op, const float *d_x, const float *d_y, float *d_out, size_t n, hipStream_t stream);

@@ -206,6 +206,48 @@ int rt_render_whitted(const rt_scene *scene, const rt_camera *camera, const rt_f
 int rt_render_whitted_host(const rt_scene *scene, const rt_camera *camera, const rt_frame *frame,
                            float *h_rgb, unsigned long long *h_ray_count);
 
+/* ---- ray queries: World::cast on caller-supplied rays ------------------------------
+
+ * World::cast (src/main.rs:180-326) for a batch of unrelated rays: "what does this ray hit?" — picking, visibility between two
+ * points, a depth / normal / object-id buffer, rays of a camera model the library does not have.  Every result is bit-identical
+ * to the reference's cast of that ray, NaN distances included. */
+
+/* main.rs:69-81 Ray + Option<Exclusion>, flattened */
+typedef struct rt_ray {
+    float origin[3];
+    float direction[3];      /* used as given: not normalised (the reference does not normalise in cast) */
+    uint32_t face_direction; /* 0 Front, 1 Back, 2 Both (main.rs:52-57); a value above 2 is read as Both */
+    uint32_t has_exclude;    /* 0: None; anything else: Some */
+    uint32_t exclude_kind;   /* 0 Sphere, 1 Triangle (PrimitiveIndex, primitives.rs:31-34); any other kind excludes nothing */
+    uint32_t exclude_index;  /* index into the scene's sphere or triangle array; beyond that array it excludes nothing, as in the
+                              * reference, where PrimitiveIndex equality simply never holds */
+    uint32_t exclude_face;   /* 0 Front, 1 Back, 2 Both; a value above 2 is read as Both */
+} rt_ray;                    /* 44 bytes */
+
+/* main.rs:139-147 Hit, flattened */
+#define RT_HIT_NONE 0xffffffffu
+typedef struct rt_hit {
+    uint32_t kind;           /* 0 Sphere, 1 Triangle, RT_HIT_NONE: cast returned None (every other field 0) */
+    uint32_t index, object_index; /* the primitive's index in its array (sphere or triangle), its Object's index */
+    float position[3], normal[3], uv[2]; /* a sphere hit always carries its uv (main.rs:310-313) */
+    uint32_t face_direction; /* 0 Front, 1 Back */
+    float distance;
+} rt_hit;                    /* 52 bytes */
+
+/* For every ray d_rays[i], d_hits[i] = World::cast(ray) (device pointers, n_rays records each).  Stream-ordered and asynchronous
+ * on hip_stream (NULL = default stream).  n_rays == 0 launches nothing; n_rays >= 2^32 is RT_ERR_UNSUPPORTED (checked first).
+ * Graph capture: on a scene below the breadth-first switch (RT_AMD_BFS_WALK_TRIANGLES) the call uses no workspace and may be
+ * captured at once.  A scene walked breadth-first keeps record lists in the per-(scene, stream) workspace, shared with
+ * rt_render_whitted: make one uncaptured call on the stream first (with at least as many rays); a call captured before that
+ * uses the pair-wise kernel, which gives the same results more slowly. */
+int rt_cast_rays(const rt_scene *scene, const rt_ray *d_rays, size_t n_rays, rt_hit *d_hits, void *hip_stream);
+/* Same, with host buffers: allocates, launches, copies back and synchronises. */
+int rt_cast_rays_host(const rt_scene *scene, const rt_ray *h_rays, size_t n_rays, rt_hit *h_hits);
+/* The primary rays Camera::shoot(clip(x, y)) (main.rs:83-99, 1093-1096) of every pixel of a frame or tile, in the tile's compact
+ * row order (as the render output): d_rays[row * (x1 - x0) + (x - x0)], rt_frame_pixels(frame) records.  Face Front, no
+ * exclusion; each ray is bit for bit the primary ray the Whitted pass casts.  frame->max_depth is not used.  Stream-ordered. */
+int rt_camera_rays(const rt_camera *camera, const rt_frame *frame, rt_ray *d_rays, void *hip_stream);
+
 /* ---- distributed (stochastic / depth-of-field) pass ----------------------------
 
  * Replaces the par_iter_mut closure at src/main.rs:1131-1156 and the per-pixel RNG construction at
@@ -328,7 +370,8 @@ int rt_accumulator_resolve_device(const float *d_sum, const float *d_weight, siz
  * named like the environment variable that seeds it — RT_AMD_DIST_PIPELINE, RT_AMD_DIST_WS_MB, RT_AMD_RNG_LOOKAHEAD,
  * RT_AMD_RNG_OVERLAP, RT_AMD_DIST_BY_COST, RT_AMD_DIST_OWN_FIRST, RT_AMD_DIST_PREP_FIRST, RT_AMD_DIST_SPLIT, RT_AMD_DIST_STATIC,
  * RT_AMD_DIST_CHAIN_WAVES, RT_AMD_SHADE_TILE, RT_AMD_SHADE_SORT, RT_AMD_DIAG_WS_REFUSE,
- * RT_AMD_MULTI_FORCE_STAGE, RT_AMD_BFS_WALK_TRIANGLES (read by rt_scene_create), RT_AMD_WF_SHARE, RT_AMD_DIAG_BFS_CAP (INTEGRATION.md says what each does).  The environment is read ONCE per process, at the first use;
+ * RT_AMD_MULTI_FORCE_STAGE, RT_AMD_BFS_WALK_TRIANGLES (read by rt_scene_create), RT_AMD_WF_SHARE, RT_AMD_DIAG_BFS_CAP,
+ * RT_AMD_QUERY_WAVE_UNIFORM (INTEGRATION.md says what each does).  The environment is read ONCE per process, at the first use;
  * after that only this call changes a switch: value = decimal integer, NULL or "" = unset (the library's own choice).  Render
  * calls read the switches without locks: set them between calls, not during one. */
 int rt_set_option(const char *name, const char *value);
