@@ -27,12 +27,10 @@ extern "C" void rt_diag_set_timeline(void *device_ptr) { g_diag_timeline = stati
                                               * ahead at 9 244 triangles, 2.1-2.3x at 36 892, 8-17x at 147 484; at 2 332 it loses (1.2x on flat meshes, 2x
                                               * on spherized ones) */
 #endif
-/* the switches of rt_kernels.h `Option`: name (also the environment variable that seeds it), whether it has a value, the value */
-static const char *const OPT_NAMES[rt::OPT_COUNT] = {
-    "RT_AMD_RNG_LOOKAHEAD", "RT_AMD_RNG_OVERLAP", "RT_AMD_DIST_PIPELINE", "RT_AMD_DIST_BY_COST", "RT_AMD_DIST_OWN_FIRST", "RT_AMD_DIST_PREP_FIRST",
-    "RT_AMD_DIST_WS_MB", "RT_AMD_DIAG_WS_REFUSE", "RT_AMD_DIST_STATIC", "RT_AMD_DIST_CHAIN_WAVES", "RT_AMD_SHADE_TILE", "RT_AMD_SHADE_SORT",
-    "RT_AMD_MULTI_FORCE_STAGE", "RT_AMD_DIST_SPLIT", "RT_AMD_BFS_WALK_TRIANGLES", "RT_AMD_WF_SHARE", "RT_AMD_DIAG_BFS_CAP",
-    "RT_AMD_QUERY_WAVE_UNIFORM"};
+/* the switches of rt_kernels.h RT_OPTIONS: name (also the environment variable that seeds it), whether it has a value, the value */
+#define RT_OPTION_NAME(id, name) name,
+static const char *const OPT_NAMES[rt::OPT_COUNT] = {RT_OPTIONS(RT_OPTION_NAME)};
+#undef RT_OPTION_NAME
 static std::atomic<int> g_opt_set[rt::OPT_COUNT];
 static std::atomic<long long> g_opt_val[rt::OPT_COUNT];
 static std::once_flag g_opt_once;

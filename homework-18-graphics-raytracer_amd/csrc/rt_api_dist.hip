@@ -230,9 +230,8 @@ int rt_render_distributed(const rt_scene *scene, const rt_camera *camera, const 
     if (scene->ks.bfs_walk != 0u) split = 0; /* a scene beyond the caches: the one-kernel organisation has the breadth-first walk (below) */
     const size_t n_pixels = (size_t)kf.cols * kf.rows;
     if (n_pixels == 0 || n_epochs == 0) return RT_OK;
-    /* the switches (rt_kernels.h Option; rt_set_option or, once per process, the environment) */
+    /* the switches (rt_kernels.h RT_OPTIONS; rt_set_option or, once per process, the environment) */
     const bool lookahead = rt::option(rt::OPT_RNG_LOOKAHEAD, 1) != 0; /* 0 leaves every IsaacCore::generate to the render kernels */
-    const bool overlap = rt::option(rt::OPT_RNG_OVERLAP, 1) != 0;     /* 0 runs the look-ahead in line, before each chain kernel */
     rt_scene *mut = const_cast<rt_scene *>(scene);
     if (split && kf.max_depth <= 254) {
         /* chain / shade / unwind kernels over batches of epochs (rt_distributed.hip "the split pass"); a batch is as
@@ -346,7 +345,7 @@ int rt_render_distributed(const rt_scene *scene, const rt_camera *camera, const 
             if (e == hipSuccess) e = rt::launch_dist_chain(scene->ks, kf, dp, dist_waves, stream);
             if (e == hipSuccess && prof_chain) e = hipEventRecord(pe[3], stream);
             /* from here on this batch does not touch the RNG records: the look-ahead for the next one, on its own stream */
-            if (e == hipSuccess && lookahead && overlap) e = lookahead_after_chain(rng);
+            if (e == hipSuccess && lookahead) e = lookahead_after_chain(rng);
             if (n_buf == 2u) {
                 if (e == hipSuccess) e = hipEventRecord(rng->ev_tail[b], stream); /* first: the chain kernel has written workspace b ... */
                 if (e == hipSuccess) e = hipStreamWaitEvent(rng->tail, rng->ev_tail[b], 0);
@@ -381,38 +380,35 @@ one_kernel:
     dp.n_epochs = n_epochs;
     dp.epoch0 = 0;
     dp.sp_hdr = nullptr; dp.sp_req = nullptr; dp.sp_shade = nullptr; dp.sp_frame = nullptr; dp.sp_slots = 0;
-    {
-        if (rt::option(rt::OPT_DIST_STATIC, 0) != 1) { /* 1 (A/B): one 64-pixel chunk per wave instead of persistent lanes */
-            std::lock_guard<std::mutex> lock(mut->ws_mutex);
-            Workspace &ws = mut->workspaces[stream];
-            RT_HIP(ensure_counters(ws));
-            dp.work_queue = ws.d_counters;
-            if (scene->ks.bfs_walk != 0u) { /* the breadth-first walk's lists, one set per wave of the grid (shared with the Whitted path of this stream) */
-                const uint32_t waves = rt::dist_bfs_waves(rng->compute_units);
-                const size_t words = (size_t)waves * rt::pwf_bfs_scratch_words_per_wave();
-                if (ws.bfs_words < words) {
-                    if (ws.d_bfs) (void)hipFree(ws.d_bfs);
-                    ws.d_bfs = nullptr;
-                    ws.bfs_words = 0;
-                    if (hipMalloc(reinterpret_cast<void **>(&ws.d_bfs), words * sizeof(uint32_t)) != hipSuccess) { (void)hipGetLastError(); ws.d_bfs = nullptr; }
-                    else ws.bfs_words = words;
+    { /* persistent lanes: the grid's waves take 64-pixel chunks off the stream's chunk counter */
+        std::lock_guard<std::mutex> lock(mut->ws_mutex);
+        Workspace &ws = mut->workspaces[stream];
+        RT_HIP(ensure_counters(ws));
+        dp.work_queue = ws.d_counters;
+        if (scene->ks.bfs_walk != 0u) { /* the breadth-first walk's lists, one set per wave of the grid (shared with the Whitted path of this stream) */
+            const uint32_t waves = rt::dist_bfs_waves(rng->compute_units);
+            const size_t words = (size_t)waves * rt::pwf_bfs_scratch_words_per_wave();
+            if (ws.bfs_words < words) {
+                if (ws.d_bfs) (void)hipFree(ws.d_bfs);
+                ws.d_bfs = nullptr;
+                ws.bfs_words = 0;
+                if (hipMalloc(reinterpret_cast<void **>(&ws.d_bfs), words * sizeof(uint32_t)) != hipSuccess) { (void)hipGetLastError(); ws.d_bfs = nullptr; }
+                else ws.bfs_words = words;
+            }
+            if (ws.d_bfs != nullptr) { /* (no room: the wave-uniform walk renders the same samples) */
+                dp.bfs_scratch = ws.d_bfs;
+                dp.bfs_items_cap = RT_BFS_ITEMS_CAP;
+                dp.bfs_jobs_cap = RT_BFS_JOBS_CAP;
+                const long long cap = rt::option(rt::OPT_DIAG_BFS_CAP, 0);
+                if (cap > 0) {
+                    dp.bfs_items_cap = (uint32_t)std::min<long long>(cap, RT_BFS_ITEMS_CAP);
+                    dp.bfs_jobs_cap = (uint32_t)std::min<long long>(cap, RT_BFS_JOBS_CAP);
                 }
-                if (ws.d_bfs != nullptr) { /* (no room: the wave-uniform walk renders the same samples) */
-                    dp.bfs_scratch = ws.d_bfs;
-                    dp.bfs_items_cap = RT_BFS_ITEMS_CAP;
-                    dp.bfs_jobs_cap = RT_BFS_JOBS_CAP;
-                    const long long cap = rt::option(rt::OPT_DIAG_BFS_CAP, 0);
-                    if (cap > 0) {
-                        dp.bfs_items_cap = (uint32_t)std::min<long long>(cap, RT_BFS_ITEMS_CAP);
-                        dp.bfs_jobs_cap = (uint32_t)std::min<long long>(cap, RT_BFS_JOBS_CAP);
-                    }
-                    if (dist_waves > waves) dist_waves = waves;
-                }
+                if (dist_waves > waves) dist_waves = waves;
             }
         }
     }
-    hipError_t e = hipSuccess;
-    if (dp.work_queue) e = hipMemsetAsync(dp.work_queue, 0, sizeof(uint32_t), stream);
+    hipError_t e = hipMemsetAsync(dp.work_queue, 0, sizeof(uint32_t), stream);
     if (e == hipSuccess && lookahead && !rng->ahead) e = rt::launch_rng_prepare(rng->d_states, (uint32_t)n_pixels, rng->d_list, rng->compute_units, stream);
     rng->ahead = false;
     if (e == hipSuccess) e = rt::launch_distributed(scene->ks, kf, dp, dist_waves, stream);

@@ -69,10 +69,8 @@ int layout_scene(const rt_scene_desc *desc, SceneLayout &layout) {
                 const double a = fabs((double)desc->triangles[i].vertices[v].position[k]);
                 if (a > scene_extent) scene_extent = a; /* NaN never compares greater */
             }
-    const bool filter_off = getenv("RT_AMD_NO_SPHERE_FILTER") != nullptr; /* A/B switch; results are the same either way */
-    const char *frac_env = getenv("RT_AMD_FILTER_MAX_FRAC");
     /* a triangle as large as the scene rejects next to nothing: not worth its ten instructions */
-    const double max_frac = (frac_env && *frac_env) ? atof(frac_env) : 0.5;
+    const double max_frac = 0.5;
     for (uint32_t i = 0; i < desc->n_triangles; ++i) {
         rt::DevTri &t = tris[i];
         t.bq = std::numeric_limits<float>::infinity();
@@ -84,7 +82,7 @@ int layout_scene(const rt_scene_desc *desc, SceneLayout &layout) {
                 P[v][k] = (double)desc->triangles[i].vertices[v].position[k];
                 finite = finite && std::isfinite(P[v][k]);
             }
-        if (!finite || filter_off || !(scene_extent <= 1e10)) continue;
+        if (!finite || !(scene_extent <= 1e10)) continue;
         auto sub = [](const double *a, const double *b, double *o) { for (int k = 0; k < 3; ++k) o[k] = a[k] - b[k]; };
         auto dotd = [](const double *a, const double *b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; };
         double ab[3], ac[3], bc[3];
@@ -134,10 +132,7 @@ int layout_scene(const rt_scene_desc *desc, SceneLayout &layout) {
     std::vector<rt::DevSegment> &segments = layout.segments;
     segments.clear();
     {
-        const bool clusters_off = filter_off || getenv("RT_AMD_NO_CLUSTERS") != nullptr; /* A/B switch; results are the same either way */
-        const bool flat_only = getenv("RT_AMD_NO_HIERARCHY") != nullptr; /* A/B: one cluster per object run, explicit normals only (round 1) */
-        uint32_t single_leaf_max = 64u; /* A/B: objects up to this many triangles stay one leaf */
-        if (const char *v = getenv("RT_AMD_SINGLE_LEAF_MAX")) { if (*v) single_leaf_max = (uint32_t)atoi(v); }
+        const uint32_t single_leaf_max = 64u; /* objects up to this many triangles stay one leaf */
         /* A plain run may only grow the leaf before it if that leaf is not inside a subtree that is already closed: an inner
          * node's skip_to jumps over everything emitted below it, so triangles appended to a leaf in there would be skipped with
          * it.  merge_barrier = the number of nodes no later run may be merged into (moved whenever a subtree or a tree ends). */
@@ -197,7 +192,6 @@ int layout_scene(const rt_scene_desc *desc, SceneLayout &layout) {
                 }
             }
             if (explicit_ok && g->n_normals != 0u) return true;
-            if (flat_only) return false;
             /* More than 8 plane directions: a CONE.  Axis a (unit), half-angle theta >= the angle between a and every face normal
              * or its negative.  For a unit direction d and a unit normal n within theta of +-a:
              *     |n.d| >= |a.d| cos(theta) - sin(theta),
@@ -267,17 +261,16 @@ int layout_scene(const rt_scene_desc *desc, SceneLayout &layout) {
         for (uint32_t i = 0; i < desc->n_triangles;) {
             uint32_t j = i;
             while (j < desc->n_triangles && desc->triangles[j].object_index == desc->triangles[i].object_index) ++j;
-            bool ok = !clusters_off && j - i >= 8u;
+            bool ok = j - i >= 8u;
             for (uint32_t k = i; ok && k < j; ++k) ok = std::isfinite(tris[k].bq); /* every triangle qualifies for its own rejection */
             if (!ok) {
                 push_plain(i, j - i);
-            } else if (flat_only || j - i <= single_leaf_max) {
+            } else if (j - i <= single_leaf_max) {
                 /* a small object is ONE leaf (the reference scene's dodecahedron: 36 triangles, 6 plane directions — one test per
                  * cast decides it; as a tree of three leaves it cost the bench frame 3 %) */
                 rt::DevSegment g;
                 memset(&g, 0, sizeof g);
                 if (node_stats(i, j, &g)) { g.first = i; g.count = j - i; g.skip_to = (uint32_t)segments.size() + 1u; segments.push_back(g); }
-                else if (flat_only) push_plain(i, j - i);
                 else Emit::go(0u, (j - i + RT_LEAF_TRIANGLES - 1u) / RT_LEAF_TRIANGLES, i, j, segments, node_stats, push_plain, &merge_barrier);
             } else {
                 const uint32_t n_leaves = (j - i + RT_LEAF_TRIANGLES - 1u) / RT_LEAF_TRIANGLES;
@@ -290,31 +283,28 @@ int layout_scene(const rt_scene_desc *desc, SceneLayout &layout) {
          * directions): a ray that needs one nearly always needs the other, and a leaf is a bounding-sphere test, a set of plane
          * directions and — pair-wise — a set-up of its own.  A leaf is any run of consecutive triangles that all qualify for their own
          * rejection, so nothing else changes.  Only leaves with the same ancestors are joined (no subtree ends between them). */
-        if (!clusters_off && getenv("RT_AMD_NO_LEAF_MERGE") == nullptr) {
-            for (size_t k = 0; k + 1u < segments.size();) {
-                const rt::DevSegment a = segments[k], b = segments[k + 1u];
-                bool ok = a.count != 0u && b.count != 0u && a.n_normals != 0u && b.n_normals != 0u && a.n_normals != RT_SEGMENT_CONE &&
-                          b.n_normals != RT_SEGMENT_CONE && a.first + a.count == b.first && a.count + b.count <= 64u;
-                for (size_t j = 0; ok && j < k; ++j) ok = !(segments[j].count == 0u && segments[j].skip_to == k + 1u);
-                rt::DevSegment g;
-                memset(&g, 0, sizeof g);
-                ok = ok && node_stats(a.first, b.first + b.count, &g) && g.n_normals != RT_SEGMENT_CONE &&
-                     g.r2_hi <= 1.15f * std::max(a.r2_hi, b.r2_hi);
-                if (!ok) { ++k; continue; }
-                g.first = a.first;
-                g.count = a.count + b.count;
-                g.skip_to = (uint32_t)k + 1u;
-                segments[k] = g;
-                segments.erase(segments.begin() + (ptrdiff_t)k + 1);
-                for (rt::DevSegment &n : segments)
-                    if (n.skip_to > k + 1u) n.skip_to -= 1u;
-                /* and again from the same node: it may take the next one too */
-            }
+        for (size_t k = 0; k + 1u < segments.size();) {
+            const rt::DevSegment a = segments[k], b = segments[k + 1u];
+            bool ok = a.count != 0u && b.count != 0u && a.n_normals != 0u && b.n_normals != 0u && a.n_normals != RT_SEGMENT_CONE &&
+                      b.n_normals != RT_SEGMENT_CONE && a.first + a.count == b.first && a.count + b.count <= 64u;
+            for (size_t j = 0; ok && j < k; ++j) ok = !(segments[j].count == 0u && segments[j].skip_to == k + 1u);
+            rt::DevSegment g;
+            memset(&g, 0, sizeof g);
+            ok = ok && node_stats(a.first, b.first + b.count, &g) && g.n_normals != RT_SEGMENT_CONE &&
+                 g.r2_hi <= 1.15f * std::max(a.r2_hi, b.r2_hi);
+            if (!ok) { ++k; continue; }
+            g.first = a.first;
+            g.count = a.count + b.count;
+            g.skip_to = (uint32_t)k + 1u;
+            segments[k] = g;
+            segments.erase(segments.begin() + (ptrdiff_t)k + 1);
+            for (rt::DevSegment &n : segments)
+                if (n.skip_to > k + 1u) n.skip_to -= 1u;
+            /* and again from the same node: it may take the next one too */
         }
         /* clustered leaves: how their triangles are dealt to the lanes of a pair-wise pass (rt_device_scene.h RT_SEG_PAIR_*) */
-        const bool pairs_off = getenv("RT_AMD_NO_PAIRS") != nullptr; /* A/B switch; results are the same either way */
         for (rt::DevSegment &g : segments) {
-            if (g.count == 0u || g.n_normals == 0u || pairs_off || g.count > 64u) continue;
+            if (g.count == 0u || g.n_normals == 0u || g.count > 64u) continue;
             uint32_t best_k = 0u, best_ck = 0u, best_r = 0u;
             double best_fill = 0.0;
             for (uint32_t K = 1u; K <= 8u; ++K) {
@@ -333,8 +323,7 @@ int layout_scene(const rt_scene_desc *desc, SceneLayout &layout) {
     }
     /* triangles on their predecessor's plane (rt_device_scene.h RT_TRI_FOLLOWS): same segment; n and d equal bit for bit, or
      * (WEAK) equal up to the signs of zero components */
-    if (getenv("RT_AMD_NO_PLANE_SHARING") == nullptr && desc->n_materials <= RT_TRI_OBJ_MASK) { /* A/B switch; results are the same either way */
-        const bool weak_ok = getenv("RT_AMD_NO_WEAK_PLANE_SHARING") == nullptr;
+    if (desc->n_materials <= RT_TRI_OBJ_MASK) {
         /* any two consecutive triangles of one object: a call of the loop covers consecutive records and treats its first triangle
          * as a leader whatever its flag says, so a pair may straddle leaves */
         for (uint32_t i = 1u; i < desc->n_triangles; ++i) {
@@ -349,7 +338,7 @@ int layout_scene(const rt_scene_desc *desc, SceneLayout &layout) {
                     weak = weak && (same_bits || (a[k] == 0.0f && b[k] == 0.0f));
                 }
                 if (exact) tris[i].obj |= RT_TRI_FOLLOWS;
-                else if (weak && weak_ok) tris[i].obj |= RT_TRI_FOLLOWS | RT_TRI_FOLLOWS_WEAK;
+                else if (weak) tris[i].obj |= RT_TRI_FOLLOWS | RT_TRI_FOLLOWS_WEAK;
             }
         }
     }

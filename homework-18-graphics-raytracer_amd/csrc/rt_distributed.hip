@@ -480,7 +480,7 @@ __global__ __launch_bounds__(64, BFS ? RT_DIST_BFS_WAVES : RT_DIST_MIN_WAVES) vo
      * nothing is lost by mixing pixels in a wave, and every lane stays busy until the tile runs dry.  Pixels are
      * handed out as in the Whitted kernel: 64-slot chunks from a global counter (one atomic per chunk per wave),
      * slots inside a chunk by ballot + prefix count.  dp.work_queue == nullptr selects the static assignment
-     * (wave w = chunk w), kept for A/B. */
+     * (wave w = chunk w); no host path selects it any more (rt_api_dist.hip always passes the chunk counter). */
     const bool persistent = dp.work_queue != nullptr;
     uint32_t q_next = 0u, q_end = 0u;
     bool exhausted = false;
@@ -890,12 +890,9 @@ uint32_t dist_bfs_waves(uint32_t compute_units) { return compute_units * 4u * (u
  * Same operations on the same values as the fused kernel, so samples, flags, RNG states and cast counts are
  * bit-identical to it and to the oracle (tests/test_gpu_distributed_parity.py runs both). */
 
-/* The shade kernel keeps the wave-uniform cast: pair-wise (RT_DIST_SHADE_PAIRS) it is slower, 5.97 against 5.15 ms per 8-epoch batch —
- * its shadow rays need the clusters less sparsely (half of the leaf visits have 8 lanes or more, a quarter 34 or more, against 7 and
- * 25 in the chain kernel) and the 19 KB of PairLds per workgroup cost it two of its six waves per SIMD (profiles/r03p7_*). */
-#if !defined(RT_DIST_SHADE_PAIRS) && !defined(RT_DIST_SHADE_NO_PAIRS)
-#define RT_DIST_SHADE_NO_PAIRS
-#endif
+/* The shade kernel keeps the wave-uniform cast: pair-wise it was slower, 5.97 against 5.15 ms per 8-epoch batch — its shadow rays
+ * need the clusters less sparsely (half of the leaf visits have 8 lanes or more, a quarter 34 or more, against 7 and 25 in the chain
+ * kernel) and the 19 KB of PairLds per workgroup cost it two of its six waves per SIMD (profiles/r03p7_*). */
 #ifndef RT_DIST_CHAIN_MIN_WAVES
 #define RT_DIST_CHAIN_MIN_WAVES 5 /* 96 VGPRs, no more scratch than at 4 (112); 3 / 4 / 5: 709 / 853 / 868 Msamples/s */
 #endif
@@ -928,25 +925,16 @@ __global__ __launch_bounds__(64, RT_DIST_CHAIN_MIN_WAVES) void dist_chain_kernel
      * would cost the fifth. */
     union ChainLds {
         uint32_t stage[RNG_LDS_SLOTS * 256u];
-#ifndef RT_DIST_NO_PAIRS
         PairLds pairs;
-#endif
     };
     __shared__ __attribute__((aligned(16))) ChainLds chain_lds;
-    uint32_t *const rng_stage = chain_lds.stage;
-#ifndef RT_DIST_NO_PAIRS
     static_assert(sizeof(PairLds) <= sizeof(chain_lds.stage), "PairLds must fit the staging area");
     PairLds *const pair_lds = &chain_lds.pairs;
-#endif
     Rng rng;
     rng.rec = rng.st = dp.rng_states;
     rng.index = 256u;
     rng.flags = 0u;
-#ifdef RT_DIST_NO_STAGE /* A/B */
-    rng.lds = nullptr;
-#else
-    rng.lds = rng_stage;
-#endif
+    rng.lds = chain_lds.stage;
     uint32_t phase = DP_DONE;
     uint32_t epoch = 0u;
     Ray req;
@@ -1047,13 +1035,6 @@ __global__ __launch_bounds__(64, RT_DIST_CHAIN_MIN_WAVES) void dist_chain_kernel
         if (phase == DP_START) start_epoch();
 
         CastResult cr;
-#ifdef RT_DIST_NO_PAIRS /* A/B: every leaf wave-uniformly (round 2) */
-        cr.prim = -1;
-        cr.t = 0.0f;
-        cr.bf = 0u;
-        cr.a0 = cr.a1 = cr.a2 = 0.0f;
-        if (phase != DP_DONE) cr = cast_asm(sc, req);
-#else
 #ifdef RT_DIAG_PAIR_TIME
         RT_STEP_TICK(9)
         cr = cast_pairs(sc, req, phase != DP_DONE, pair_lds, diag_dt);
@@ -1063,7 +1044,6 @@ __global__ __launch_bounds__(64, RT_DIST_CHAIN_MIN_WAVES) void dist_chain_kernel
         diag_tick = __builtin_readcyclecounter();
 #else
         cr = cast_pairs(sc, req, phase != DP_DONE, pair_lds); /* all lanes: the idle ones help with the others' pairs */
-#endif
 #endif
         if (phase == DP_DONE) continue;
         casts += 1u;
@@ -1131,10 +1111,6 @@ extern "C" int rt_diag_read_shade_time(unsigned long long *out8, int reset) {
 #endif
 __global__ __launch_bounds__(RT_DIST_SHADE_THREADS, RT_DIST_SHADE_MIN_WAVES) void dist_shade_kernel(const KernelScene sc, const DistParams dp, const size_t n_samples, const uint32_t tile, const uint32_t list_cap, const uint32_t sort) {
     extern __shared__ uint32_t shade_lds[];
-#ifndef RT_DIST_SHADE_NO_PAIRS
-    __shared__ PairLdsSlim pair_lds_all[RT_DIST_SHADE_THREADS / 64u];
-    PairLdsSlim *const pair_lds = &pair_lds_all[threadIdx.x >> 6];
-#endif
     uint32_t *const bucket_start = shade_lds + 1u, *const bucket_cursor = bucket_start + DIST_SHADE_BUCKETS;
     uint32_t *const unsorted = shade_lds + DIST_SHADE_HDR;       /* slot << 24 | bucket << 16 | sample - tile0 */
     uint32_t *const shade_list = unsorted + list_cap;            /* the same, bucket by bucket */
@@ -1191,9 +1167,6 @@ __global__ __launch_bounds__(RT_DIST_SHADE_THREADS, RT_DIST_SHADE_MIN_WAVES) voi
     __syncthreads();
     uint32_t casts = 0u;
     RT_SHADE_TICK(0)
-#if defined(RT_AB_SHADE_STUB) && RT_AB_SHADE_STUB == 3
-    if (shade_list[0] != 0xffffffffu) return;
-#endif
     for (uint32_t first = (threadIdx.x >> 6) * 64u; first < total; first += blockDim.x) {
         const bool active = first + lane < total;
         V3 pos = v3(0.0f, 0.0f, 0.0f), normal = v3(0.0f, 0.0f, 1.0f), view = v3(0.0f, 0.0f, 1.0f);
@@ -1214,28 +1187,12 @@ __global__ __launch_bounds__(RT_DIST_SHADE_THREADS, RT_DIST_SHADE_MIN_WAVES) voi
         const V3 adj_n = adjust_normal(m.normal, normal); /* main.rs:410 */
         V3 sum = v3(0.0f, 0.0f, 0.0f);
         RT_SHADE_TICK(1)
-#if defined(RT_AB_SHADE_STUB) && RT_AB_SHADE_STUB == 2
-        sum = adj_n + m.diffuse;
-        for (uint32_t light_i = 0; light_i < 0u; ++light_i) {
-#else
         for (uint32_t light_i = 0; light_i < sc.n_lights; ++light_i) { /* wave-uniform */
-#endif
             const auto &L = uniform_ref(sc.lights + light_i);
             /* does the light ask for a shadow cast (main.rs:413-433)?  light_asks answers without a spot light's acos wherever the
              * angle is clear of the cone's edge (rt_shade.h); the light's colour — a spot light's powf — waits for the lit lanes */
             V3 l_direction = v3(0.0f, 0.0f, 0.0f);
-#ifdef RT_SHADE_NO_LIGHT_ASKS /* A/B (round 3): the light evaluated in full for every active lane */
-            DirLight dl0;
-            dl0.direction = dl0.color = v3(0.0f, 0.0f, 0.0f);
-            bool need = false;
-            if (active && approximate_into_directional(L, pos, &dl0)) {
-                const float cosine = -dot(dl0.direction, adj_n);
-                need = !(cosine <= 0.0f);
-            }
-            l_direction = dl0.direction;
-#else
             const bool need = light_asks(L, uniform_ref(sc.light_aux + light_i), pos, adj_n, &l_direction) && active;
-#endif
             RT_SHADE_TICK(2)
             if (__builtin_amdgcn_ballot_w64(need) == 0ull) continue;
             Ray req;
@@ -1243,24 +1200,15 @@ __global__ __launch_bounds__(RT_DIST_SHADE_THREADS, RT_DIST_SHADE_MIN_WAVES) voi
             req.d = -l_direction;
             req.mode = FACE_BACK;
             req.excl = pack_excl(prim, FACE_BACK);
-#ifdef RT_DIST_SHADE_NO_PAIRS /* A/B */
             CastResult cr;
             cr.prim = -1;
             cr.t = 0.0f;
             cr.bf = 0u;
             cr.a0 = cr.a1 = cr.a2 = 0.0f;
-#if !defined(RT_AB_SHADE_STUB) || RT_AB_SHADE_STUB != 1 /* attribution builds (profiles/r04_shade_attribution.txt): 1 no cast, 2 no light loop, 3 the lists only */
             if (need) cr = cast_asm(sc, req);
-#endif
 #ifdef RT_DIAG_PAIR_TIME
             RT_SHADE_TICK(3)
             sdt[6] += 1ull;
-#endif
-#elif defined(RT_DIAG_PAIR_TIME)
-            unsigned long long diag_dt[9];
-            const CastResult cr = cast_pairs(sc, req, need, pair_lds, diag_dt);
-#else
-            const CastResult cr = cast_pairs(sc, req, need, pair_lds); /* all lanes: those without a shadow ray help with the others' pairs */
 #endif
             if (need) {
                 casts += 1u;
@@ -1399,10 +1347,7 @@ size_t distributed_split_bytes_per_sample(int32_t max_depth) {
  * different streams: the chain kernel (dp.work_queue zeroed) ... */
 /* the waves the chain kernel's grid has at most: as many as are resident together */
 uint32_t dist_chain_waves(uint32_t resident_waves) {
-    uint32_t chain_waves = resident_waves / 3u * (uint32_t)RT_DIST_CHAIN_MIN_WAVES; /* resident_waves is sized for 3 per SIMD */
-    const uint32_t per_simd = (uint32_t)option(OPT_DIST_CHAIN_WAVES, 0); /* A/B: waves per SIMD of the chain kernel's grid */
-    if (per_simd >= 1u && per_simd <= (uint32_t)RT_DIST_CHAIN_MIN_WAVES) chain_waves = resident_waves / 3u * per_simd;
-    return chain_waves;
+    return resident_waves / 3u * (uint32_t)RT_DIST_CHAIN_MIN_WAVES; /* resident_waves is sized for 3 per SIMD */
 }
 
 hipError_t launch_dist_chain(const KernelScene &sc, const KernelFrame &fr, const DistParams &dp, uint32_t resident_waves, hipStream_t stream) {
@@ -1425,10 +1370,7 @@ hipError_t launch_dist_shade_unwind(const KernelScene &sc, const KernelFrame &fr
     if (ev != nullptr) (void)hipEventRecord(ev[0], stream); /* profiling: [0, 1] around the shade kernel, [2, 3] around the unwind */
     {
         uint32_t tile = 256u; /* samples per workgroup (18 KB of LDS at depth 8: six workgroups per CU); the two lists must fit 48 KB */
-        uint32_t sort = 1u;
-        /* A/B knobs (profiles/README.md) */
-        { const uint32_t t = (uint32_t)option(OPT_SHADE_TILE, 0); if (t >= 32u && t <= 4096u) tile = t; }
-        sort = option(OPT_SHADE_SORT, 1) != 0 ? 1u : 0u;
+        const uint32_t sort = 1u; /* the bucket sort by facing lights (profiles/README.md) */
         while (tile > 32u && (DIST_SHADE_HDR + 2u * (size_t)tile * slots) * sizeof(uint32_t) > 49152u) tile >>= 1;
         const size_t shade_tiles = (n_samples + tile - 1u) / tile;
         const uint32_t list_cap = tile * slots;

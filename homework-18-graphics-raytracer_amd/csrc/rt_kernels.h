@@ -84,29 +84,26 @@ struct KernelQueues {
     const uint32_t *run_if;        /* when set: the kernel is a no-op unless *run_if != 0 (the persistent-wavefront path's overflow fallback) */
 };
 
-/* Process-wide switches — A/B knobs and test hooks (include/rt_amd.h rt_set_option).  Each is an integer that starts from the
+/* Process-wide switches — settings and test hooks (include/rt_amd.h rt_set_option).  Each is an integer that starts from the
  * environment variable of its name, read ONCE per process at the first use of any of them, and can be changed at run time through
- * rt_set_option; option() returns `unset` while it has no value.  (Defined in rt_api.hip; OPT_NAMES there is in this order.) */
-enum Option : int {
-    OPT_RNG_LOOKAHEAD,     /* 0: every IsaacCore::generate is left to the render kernels */
-    OPT_RNG_OVERLAP,       /* 0: the look-ahead runs in line, before each chain kernel */
-    OPT_DIST_PIPELINE,     /* 0: one workspace, a batch's kernels in line */
-    OPT_DIST_BY_COST,      /* the chain kernel's pixels grouped by cost: 0 never, 1 always (unset: by the share's size) */
-    OPT_DIST_OWN_FIRST,    /* a wave's first chunk its own: 0 / 1 (unset: by the share's size) */
-    OPT_DIST_PREP_FIRST,   /* 0: the shade kernel and the look-ahead start together */
-    OPT_DIST_WS_MB,        /* cap of the split pass's workspace(s), MiB */
-    OPT_DIAG_WS_REFUSE,    /* test hook: pretend the first n workspace allocations fail */
-    OPT_DIST_STATIC,       /* 1: the one-kernel organisation with one 64-pixel chunk per wave */
-    OPT_DIST_CHAIN_WAVES,  /* waves per SIMD of the chain kernel's grid */
-    OPT_SHADE_TILE, OPT_SHADE_SORT, /* the per-request shade kernel: samples per workgroup; 0: no bucket sort */
-    OPT_MULTI_FORCE_STAGE, /* test hook: rt_multi_* stage every band as if it lived on another device */
-    OPT_DIST_SPLIT,        /* 0: the one-kernel organisation (rt_set_distributed_split has the last word) */
-    OPT_BFS_WALK_TRIANGLES, /* scenes of at least this many triangles are walked breadth-first by the wavefront kernel (0: never); read by rt_scene_create */
-    OPT_WF_SHARE,           /* n > 1: a launch of the persistent wavefront kernel takes 1/n of the workgroups the device holds — a caller with n frames in flight on n streams runs them side by side instead of one behind the other's tail */
-    OPT_DIAG_BFS_CAP,       /* test hook: that walk's record lists hold this many records at most (default: RT_BFS_ITEMS_CAP / RT_BFS_JOBS_CAP): a wave-cast that needs more takes the wave-uniform walk */
-    OPT_QUERY_WAVE_UNIFORM, /* 1: rt_cast_rays sends every wave through cast_asm (the wave-uniform walk) instead of cast_pairs / cast_bfs */
-    OPT_COUNT
-};
+ * rt_set_option; option() returns `unset` while it has no value (defined in rt_api.hip).  One entry per switch: enum id, name. */
+#define RT_OPTIONS(X) \
+    X(OPT_RNG_LOOKAHEAD, "RT_AMD_RNG_LOOKAHEAD")           /* 0: every IsaacCore::generate is left to the render kernels */ \
+    X(OPT_DIST_PIPELINE, "RT_AMD_DIST_PIPELINE")           /* 0: one workspace, a batch's kernels in line */ \
+    X(OPT_DIST_BY_COST, "RT_AMD_DIST_BY_COST")             /* the chain kernel's pixels grouped by cost: 0 never, 1 always (unset: by the share's size) */ \
+    X(OPT_DIST_OWN_FIRST, "RT_AMD_DIST_OWN_FIRST")         /* a wave's first chunk its own: 0 / 1 (unset: by the share's size) */ \
+    X(OPT_DIST_PREP_FIRST, "RT_AMD_DIST_PREP_FIRST")       /* 0: the shade kernel and the look-ahead start together */ \
+    X(OPT_DIST_WS_MB, "RT_AMD_DIST_WS_MB")                 /* cap of the split pass's workspace(s), MiB */ \
+    X(OPT_DIAG_WS_REFUSE, "RT_AMD_DIAG_WS_REFUSE")         /* test hook: pretend the first n workspace allocations fail */ \
+    X(OPT_MULTI_FORCE_STAGE, "RT_AMD_MULTI_FORCE_STAGE")   /* test hook: rt_multi_* stage every band as if it lived on another device */ \
+    X(OPT_DIST_SPLIT, "RT_AMD_DIST_SPLIT")                 /* 0: the one-kernel organisation (rt_set_distributed_split has the last word) */ \
+    X(OPT_BFS_WALK_TRIANGLES, "RT_AMD_BFS_WALK_TRIANGLES") /* scenes of at least this many triangles are walked breadth-first by the wavefront kernel (0: never); read by rt_scene_create */ \
+    X(OPT_WF_SHARE, "RT_AMD_WF_SHARE")                     /* n > 1: a launch of the persistent wavefront kernel takes 1/n of the workgroups the device holds — a caller with n frames in flight on n streams runs them side by side instead of one behind the other's tail */ \
+    X(OPT_DIAG_BFS_CAP, "RT_AMD_DIAG_BFS_CAP")             /* test hook: that walk's record lists hold this many records at most (default: RT_BFS_ITEMS_CAP / RT_BFS_JOBS_CAP): a wave-cast that needs more takes the wave-uniform walk */ \
+    X(OPT_QUERY_WAVE_UNIFORM, "RT_AMD_QUERY_WAVE_UNIFORM") /* 1: rt_cast_rays sends every wave through cast_asm (the wave-uniform walk) instead of cast_pairs / cast_bfs */
+#define RT_OPTION_ID(id, name) id,
+enum Option : int { RT_OPTIONS(RT_OPTION_ID) OPT_COUNT };
+#undef RT_OPTION_ID
 long long option(Option id, long long unset);
 
 void set_main_kernel_events(hipEvent_t start, hipEvent_t stop); /* profiling hook, see rt_profile_* */
@@ -162,7 +159,7 @@ struct DistParams {
     float *samples;                /* n_epochs*pixels*3 raw samples; may be null */
     unsigned char *valid;          /* n_epochs*pixels filter flags; may be null */
     unsigned long long *ray_count; /* may be null */
-    uint32_t *work_queue;          /* zeroed chunk counter: persistent lanes; null: one chunk per wave */
+    uint32_t *work_queue;          /* zeroed chunk counter: persistent lanes; null: one chunk per wave (no host path passes null) */
     /* split pass (launch_distributed_split): the chain kernel records, per sample of the batch, what the shade and
      * unwind kernels need; all arrays are slot-major ([slot][sample]) so that neighbouring lanes read neighbouring records */
     uint32_t epoch0;               /* first epoch of this batch within the call (indexes samples/valid) */

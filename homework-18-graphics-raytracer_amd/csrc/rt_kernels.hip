@@ -169,11 +169,7 @@ __device__ __forceinline__ void whitted_body(const KernelScene &sc, const Kernel
         const unsigned long long diag_ca = __builtin_amdgcn_s_memtime();
 #endif
         if (phase != PH_DONE) {
-#ifdef RT_CAST_COMPILER /* the compiler-generated loop of the first builds, for A/B */
-            cr = cast<USE_LDS>(sc, lds_tris, req);
-#else
             cr = USE_LDS ? cast<USE_LDS>(sc, lds_tris, req) : cast_asm(sc, req);
-#endif
             casts += 1u;
         }
 #ifdef RT_DIAG_TIMELINE

@@ -411,11 +411,7 @@ __global__ __launch_bounds__(PA_THREADS, BFS ? 2 : PA_MIN_WAVES) void pwf_kernel
                              * frame the counter sat on the path of every tile started (profiles/r03_ab11.txt: 1.003 -> 0.939 ms per frame,
                              * a 1/8 share 0.419 -> 0.336 ms). */
                             const uint32_t share = n_tiles / gridDim.x;
-#ifdef PA_STATIC_EIGHTHS /* A/B: a fixed fraction */
-                            const uint32_t own = (uint32_t)(((unsigned long long)share * PA_STATIC_EIGHTHS) >> 3);
-#else
                             const uint32_t own = share / 2u > (share < 8u ? share : 8u) ? share / 2u : (share < 8u ? share : 8u);
-#endif
                             uint32_t k;
                             const uint32_t mine = own != 0u && lds_load(&S.static_next) < own ? atomicAdd(&S.static_next, 1u) : own;
                             if (mine < own) k = blockIdx.x + gridDim.x * mine;
@@ -947,11 +943,7 @@ __global__ __launch_bounds__(PA_THREADS, BFS ? 2 : PA_MIN_WAVES) void pwf_kernel
             }
         }
         const bool listed = f_start[64] <= f_cap;
-#ifdef PA_DIAG_NO_LEVELS /* timing experiment: the wrong image */
-        for (uint32_t left = max_depth; left < max_depth; ++left) {
-#else
         for (uint32_t left = 1u; left < max_depth; ++left) {
-#endif
             if (listed) {
                 const uint32_t end = f_start[left + 1u];
                 for (uint32_t i = f_start[left] + threadIdx.x; i < end; i += PA_THREADS) fold_node(f_list[i]);
@@ -976,11 +968,7 @@ __global__ __launch_bounds__(PA_THREADS, BFS ? 2 : PA_MIN_WAVES) void pwf_kernel
         /* the roots, by tile: a wave takes four tiles at a time so that their dependent loads (record, then children)
          * overlap */
         const uint32_t n_started = S.tile_list_count;
-#ifdef PA_DIAG_NO_ROOTS /* timing experiment: no image */
-        for (uint32_t e0 = n_started; e0 < n_started; e0 += PA_WAVES * 4u) {
-#else
         for (uint32_t e0 = threadIdx.x >> 6; e0 < n_started; e0 += PA_WAVES * 4u) {
-#endif
             uint32_t id[4], slot[4], tile_of[4];
             uint4 ra[4], rb[4];
             bool live[4];

@@ -65,13 +65,8 @@ __host__ __device__ __forceinline__ bool pa_ready_packed(uint32_t node_cap, uint
     return ((node_cap + 63u) / 64u + 2u * (ring_cap / 64u)) * 4u > PA_READY_UNPACKED_LIMIT;
 }
 __device__ __forceinline__ uint32_t pa_ready_shift(uint32_t idx) { return (idx & 1u) << 4; }
-/* the queue helpers: inlined at every site (46 % of pwf_kernel's instructions); -DPA_OUTLINE makes them functions (A/B:
- * profiles/r04_ab6.txt) */
-#ifdef PA_OUTLINE
-#define PA_HELPER __device__ __noinline__
-#else
+/* the queue helpers: inlined at every site (46 % of pwf_kernel's instructions; as functions they were slower, profiles/r04_ab6.txt) */
 #define PA_HELPER __device__ __forceinline__
-#endif
 struct PaQueue {
     uint32_t alloc; /* next position to reserve */
     uint32_t taken; /* next PAGE to claim */

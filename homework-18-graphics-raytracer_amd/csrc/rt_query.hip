@@ -63,11 +63,6 @@ __device__ __forceinline__ void store_hit(const Scene &sc, const Ray &ray, const
 #ifndef RT_QUERY_MIN_WAVES
 #define RT_QUERY_MIN_WAVES 6
 #endif
-#ifdef RT_QUERY_PAIR_LDS_FULL /* A/B: the leaf's plane records staged in LDS too */
-typedef PairLds QueryPairLds;
-#else
-typedef PairLdsSlim QueryPairLds;
-#endif
 template <bool WAVE_UNIFORM>
 __global__ __launch_bounds__(RT_QUERY_THREADS, RT_QUERY_MIN_WAVES) void cast_rays_kernel(const KernelScene sc, const rt_ray *__restrict__ rays,
                                                                                         rt_hit *__restrict__ hits, const uint32_t n_rays) {
@@ -91,7 +86,7 @@ __global__ __launch_bounds__(RT_QUERY_THREADS, RT_QUERY_MIN_WAVES) void cast_ray
     if constexpr (WAVE_UNIFORM) {
         if (active) cr = cast_asm(sc, ray);
     } else {
-        __shared__ QueryPairLds pair_lds_all[RT_QUERY_THREADS / 64];
+        __shared__ PairLdsSlim pair_lds_all[RT_QUERY_THREADS / 64];
         cr = cast_pairs(sc, ray, active, &pair_lds_all[threadIdx.x >> 6]); /* all 64 lanes: those past the end help */
     }
     if (active) store_hit(sc, ray, cr, hits + i);

@@ -117,9 +117,6 @@ RT_HD V3 get_diffuse(const Mat &m, V3 normal, V3 light_direction) {
  * 935): outside the highlight the power underflows, and a wave none of whose lanes is inside one skips the binary64
  * evaluation altogether.  Same bits as evaluating it (tests: GPU == oracle, which always evaluates). */
 RT_HD bool pow_underflows_to_zero(float x, float y) {
-#ifdef RT_NO_POW_SHORTCUT /* A/B */
-    return false;
-#endif
     return x >= 0.0f && x < 1.0f && y > 0.0f && y <= 3.0e38f && (x == 0.0f || y * (x - 1.0f) < -111.0f);
 }
 

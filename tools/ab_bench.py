@@ -8,7 +8,6 @@ Each tag is homework-18-graphics-raytracer_amd/variants/librt_amd_<tag>.so (make
 """
 import argparse
 import ctypes as C
-import os
 import statistics
 import sys
 import time
@@ -33,20 +32,15 @@ ap.add_argument("--variant", type=int, default=18)
 ap.add_argument("--world", type=int, default=1, help="render only rank 0's interleaved row band of this many ranks (a multi-GPU share)")
 args = ap.parse_args()
 
-ENV_KNOBS = ("RT_AMD_NO_SPHERE_FILTER", "RT_AMD_FILTER_MAX_FRAC", "RT_AMD_NO_CLUSTERS", "RT_AMD_PWF_RING", "RT_AMD_NO_PLANE_SHARING", "RT_AMD_NO_WEAK_PLANE_SHARING")
 world = rt.reference_world()
 cam = rt.reference_camera()
 desc = world.desc()
 frame = rt.Frame.full(args.width, args.height, args.depth) if args.world == 1 else rt.Frame.rows_of_rank(args.width, args.height, args.depth, 0, args.world)
 libs = {}
 for tag in args.tags.split(","):
-    parts = tag.split(":")  # "name", "name:variant" or "name:variant:ENV=value[;ENV=value]"
+    parts = tag.split(":")  # "name" or "name:variant"
     name, var = parts[0], (parts[1] if len(parts) > 1 else "")
     evict = None
-    env = dict(kv.split("=", 1) for kv in parts[2].split(";")) if len(parts) == 3 else {}
-    for k in ENV_KNOBS:
-        os.environ.pop(k, None)
-    os.environ.update(env)  # read by rt_scene_create (and, for some, at every render call: see run())
     path = _capi.PKG_DIR / ("librt_amd.so" if name == "main" else f"variants/librt_amd_{name}.so")
     lib = C.CDLL(str(path))
     lib.rt_last_error.restype = C.c_char_p
@@ -55,7 +49,7 @@ for tag in args.tags.split(","):
     lib_variant = int(var) if var else args.variant
     h = C.c_void_p()
     assert lib.rt_scene_create(C.byref(desc), C.byref(h)) == 0, lib.rt_last_error()
-    libs[tag] = (lib, h, lib_variant, evict, env)
+    libs[tag] = (lib, h, lib_variant, evict)
 
 out = torch.empty((frame.rows, frame.cols, 3), dtype=torch.float32, device="cuda")
 cnt = torch.zeros(1, dtype=torch.int64, device="cuda")
@@ -63,10 +57,7 @@ stream = torch.cuda.current_stream().cuda_stream
 
 
 def run(tag, n):
-    lib, h, lib_variant, evict, env = libs[tag]
-    for k in ENV_KNOBS:
-        os.environ.pop(k, None)
-    os.environ.update(env)
+    lib, h, lib_variant, evict = libs[tag]
     lib.rt_set_variant(lib_variant)
     for _ in range(n):
         rc = lib.rt_render_whitted(h, C.byref(cam), C.byref(frame), C.c_void_p(out.data_ptr()), C.c_void_p(cnt.data_ptr()), C.c_void_p(stream))
