@@ -9,6 +9,7 @@ reference's host-side names on top of them:
     Camera                         src/main.rs:43-49
     render (the Whitted par_iter)  src/main.rs:1087-1104
     cast_rays (World::cast)        src/main.rs:180-326, on caller-supplied rays
+    trace_rays (World::ray_trace)  src/main.rs:466-519, on caller-supplied rays
     post_process / write_to_file   src/main.rs:748-776
 
 PyTorch is used only for device memory, streams and torch.distributed.
@@ -26,7 +27,7 @@ from ._capi import Camera, Frame, Light, Material, RtError, SceneDesc, Sphere, T
 
 __all__ = [
     "World", "ObjectProxy", "Scene", "Camera", "Frame", "Material", "Light", "RtError", "reference_world",
-    "reference_camera", "render_whitted", "render_whitted_numpy", "make_rays", "cast_rays", "Hits", "camera_rays", "cast_rays_numpy", "Rng", "render_distributed", "render_distributed_numpy", "set_option", "options", "post_process_device", "encode_srgb8_device", "post_process", "encode_srgb8", "write_to_file",
+    "reference_camera", "render_whitted", "render_whitted_numpy", "make_rays", "cast_rays", "Hits", "camera_rays", "cast_rays_numpy", "trace_rays", "trace_rays_numpy", "Rng", "render_distributed", "render_distributed_numpy", "set_option", "options", "post_process_device", "encode_srgb8_device", "post_process", "encode_srgb8", "write_to_file",
     "DEFAULT_OBJ",
 ]
 
@@ -326,6 +327,50 @@ def cast_rays_numpy(scene: Scene, rays_np) -> np.ndarray:
     hits = np.zeros(a.shape[0], dtype=HIT_DTYPE)
     _capi.check(_capi.amd_lib().rt_cast_rays_host(scene._h, a.ctypes.data_as(C.c_void_p), a.shape[0], hits.ctypes.data_as(C.c_void_p)))
     return hits
+
+
+# ---- radiance queries: World::ray_trace on caller-supplied rays (include/rt_amd.h rt_trace_rays) ----
+
+def trace_rays(scene: Scene, rays, max_depth: int, contribution: float = 1.0, out=None, ray_count=None, stream=None):
+    """ray_trace (src/main.rs:466-519) for every ray of an (N, 11) int32 CUDA tensor of rt_ray records (make_rays, camera_rays), with
+    TraceState { depth: max_depth, contribution }: returns ``out``, an (N, 3) float32 CUDA tensor (allocated if None) holding
+    ray_trace's own value bit for bit — not ``0.0 + value`` as a frame stores it, so ``trace_rays(camera_rays(f)) + 0.0`` is the frame.
+    ``ray_count``: a 1-element int64 CUDA tensor that the World::cast count is added to.  Stream-ordered on ``stream`` (default:
+    torch's current stream).  Rays that travel together should be neighbours: a wave takes 64 consecutive rays."""
+    import torch
+
+    _records(rays, 11, "rays")
+    n = rays.shape[0]
+    if out is None:
+        out = torch.empty((n, 3), dtype=torch.float32, device=rays.device)
+    if not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (n, 3)):
+        raise ValueError("out must be a contiguous (N, 3) float32 CUDA tensor")
+    cnt_ptr = None
+    if ray_count is not None:
+        if not (ray_count.is_cuda and ray_count.dtype == torch.int64 and ray_count.numel() == 1):
+            raise ValueError("ray_count must be a 1-element int64 CUDA tensor")
+        cnt_ptr = C.c_void_p(ray_count.data_ptr())
+    s = stream if stream is not None else torch.cuda.current_stream()
+    _capi.check(_capi.amd_lib().rt_trace_rays(scene._h, C.c_void_p(rays.data_ptr()), n, int(max_depth), float(contribution),
+                                              C.c_void_p(out.data_ptr()), cnt_ptr, C.c_void_p(s.cuda_stream)))
+    return out
+
+
+def trace_rays_numpy(scene: Scene, rays_np, max_depth: int, contribution: float = 1.0):
+    """Host-buffer convenience (rt_trace_rays_host, synchronous): rays as a RAY_DTYPE structured array or an (N, 11) array of 4-byte
+    words; returns (rgb[N, 3] float32, casts)."""
+    a = np.asarray(rays_np)
+    if a.dtype == RAY_DTYPE:
+        a = np.ascontiguousarray(a).reshape(-1)
+    elif a.ndim == 2 and a.shape[1] == 11 and a.dtype.itemsize == 4:
+        a = np.ascontiguousarray(a).view(RAY_DTYPE).reshape(-1)
+    else:
+        raise ValueError("expected a RAY_DTYPE array or an (N, 11) array of 4-byte words")
+    rgb = np.zeros((a.shape[0], 3), dtype=np.float32)
+    casts = C.c_ulonglong(0)
+    _capi.check(_capi.amd_lib().rt_trace_rays_host(scene._h, a.ctypes.data_as(C.c_void_p), a.shape[0], int(max_depth), float(contribution),
+                                                   rgb.ctypes.data_as(C.c_void_p), C.byref(casts)))
+    return rgb, int(casts.value)
 
 
 class Rng:

@@ -378,14 +378,36 @@ int make_kernel_frame(const rt_camera *camera, const rt_frame *frame, rt::Kernel
     return RT_OK;
 }
 
-extern "C" {
-int rt_render_whitted(const rt_scene *scene, const rt_camera *camera, const rt_frame *frame, float *d_rgb,
-                      unsigned long long *d_ray_count, void *hip_stream) {
-    if (!scene || !d_rgb) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_whitted: null argument");
-    rt::KernelFrame kf;
-    int rc = make_kernel_frame(camera, frame, &kf);
-    if (rc != RT_OK) return rc;
-    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+/* A ray batch is rendered in bands of at most this many rays per launch, whichever path it takes: slot indices stay far from what
+ * 32 bits hold (pw_slot_to_pixel's cols << 3 wraps at 2^29). */
+#define RT_TRACE_BAND_RAYS (1u << 26)
+
+/* The Whitted render behind rt_render_whitted and rt_trace_rays: kf is a camera frame (make_kernel_frame) or a ray batch (one row of
+ * rays whose first record is d_rays; rt_kernels.h frame_set_rays).  The per-(scene, stream) arenas, the bands, the profiling events
+ * and the launches; `who` names the entry point in error messages. */
+static int render_whitted_frame(const rt_scene *scene, const rt::KernelFrame &kf, const rt_ray *d_rays, float *d_rgb,
+                                unsigned long long *d_ray_count, hipStream_t stream, const char *who) {
+    const bool rays = rt::frame_is_rays(kf);
+    /* Bands: runs of whole 8-row tile bands of a camera frame, runs of whole 64-ray tiles of a ray batch (its one row).  Band k of
+     * band_units: its frame description and where its output starts. */
+    const uint32_t units = rays ? kf.cols : kf.rows;
+    /* The band loops below count in 64 bits: a batch may hold up to 2^32 - 1 rays, and the start of the band after the last one
+     * (a multiple of the band length, up to units + band length - 1) need not fit 32 bits.  Each band itself is at most
+     * RT_TRACE_BAND_RAYS rays (a batch) or a frame of fewer than 2^32 pixels (frame_fits), so everything inside a launch is 32-bit. */
+    auto band_of = [&](uint64_t first, uint32_t band_units, rt::KernelFrame *band, float **band_rgb) {
+        const uint32_t u0 = (uint32_t)first; /* < units */
+        *band = kf;
+        const uint32_t len = units - u0 < band_units ? units - u0 : band_units;
+        if (rays) {
+            band->cols = len;
+            rt::frame_set_rays(band, d_rays + u0, rt::frame_root_contribution(kf));
+            *band_rgb = d_rgb + (size_t)u0 * 3u;
+        } else {
+            band->y0 = kf.y0 + u0 * kf.y_step;
+            band->rows = len;
+            *band_rgb = d_rgb + (size_t)u0 * kf.cols * 3u;
+        }
+    };
     int variant = current_variant();
     /* the persistent-wavefront path packs the ray's face mode and the depth left next to a 21-bit primitive id */
     if ((variant & RT_VARIANT_PWF) && (uint64_t)scene->ks.n_triangles + scene->ks.n_spheres >= (1ull << 21)) variant &= ~RT_VARIANT_PWF;
@@ -393,7 +415,7 @@ int rt_render_whitted(const rt_scene *scene, const rt_camera *camera, const rt_f
     const int wf_budget = current_wf_budget();
     rt::PwParams pw;
     memset(&pw, 0, sizeof pw);
-    uint32_t pw_groups = 0, pw_band_rows = 0, pw_parity = 0;
+    uint32_t pw_groups = 0, pw_band_units = 0, pw_parity = 0;
     bool pw_init = true;
     rt::KernelQueues qs;
     memset(&qs, 0, sizeof qs);
@@ -416,15 +438,17 @@ int rt_render_whitted(const rt_scene *scene, const rt_camera *camera, const rt_f
                 if (groups > cap) groups = cap;
             }
             if (groups < 1) groups = 1;
-            const uint64_t max_pixels = (ring_max - 1024u) * groups / (uint64_t)wf_budget;
-            pw_band_rows = kf.rows;
+            uint64_t max_pixels = (ring_max - 1024u) * groups / (uint64_t)wf_budget;
+            if (rays && max_pixels > RT_TRACE_BAND_RAYS) max_pixels = RT_TRACE_BAND_RAYS;
+            pw_band_units = units;
             if (pixels > max_pixels) {
                 const uint64_t n_bands = (pixels + max_pixels - 1) / max_pixels;
-                uint64_t rows = (kf.rows + n_bands - 1) / n_bands;
-                rows = (rows + 7u) & ~7ull; /* whole 8-row tile bands */
-                pw_band_rows = (uint32_t)(rows < kf.rows ? rows : kf.rows);
+                const uint64_t grain = rays ? 64u : 8u; /* whole tiles: 64-ray runs, 8-row tile bands */
+                uint64_t len = (units + n_bands - 1) / n_bands;
+                len = (len + grain - 1u) & ~(grain - 1u);
+                pw_band_units = (uint32_t)(len < units ? len : units);
             }
-            const uint64_t band_pixels = (uint64_t)kf.cols * pw_band_rows;
+            const uint64_t band_pixels = rays ? (uint64_t)pw_band_units : (uint64_t)kf.cols * pw_band_units;
             const uint64_t want = (band_pixels * (uint64_t)wf_budget + groups - 1) / groups; /* nodes per arena */
             /* tiles are handed out dynamically, so a workgroup may end up with several times the average: arenas have a
              * floor of 8192 ring slots (1.5 MB) however small the frame (budgets below 4 waive it: tests of the fallback) */
@@ -490,7 +514,7 @@ int rt_render_whitted(const rt_scene *scene, const rt_camera *camera, const rt_f
                 hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
                 if (hipStreamIsCapturing(stream, &capturing) != hipSuccess) (void)hipGetLastError();
                 if (capturing != hipStreamCaptureStatusNone) ws.pw_always_prepare = true;
-                if (pw_band_rows >= kf.rows && !ws.pw_always_prepare) { /* one launch: does it find its block zeroed and its frame description in place? */
+                if (pw_band_units >= units && !ws.pw_always_prepare) { /* one launch: does it find its block zeroed and its frame description in place? */
                     rt::KernelFrame want_frame = kf;
                     want_frame.n_chunks = (kf.cols * kf.rows + 63u) / 64u; /* as launch_pwf fills it in */
                     pw_init = !ws.pw_ready || memcmp(&ws.pw_frame, &want_frame, sizeof want_frame) != 0;
@@ -529,11 +553,10 @@ int rt_render_whitted(const rt_scene *scene, const rt_camera *camera, const rt_f
         pw.global = blocks + pw_parity * PW_G_BLOCK_WORDS;
         pw.global_next = blocks + (pw_parity ^ 1u) * PW_G_BLOCK_WORDS;
         qs.run_if = pw.global + PW_G_OVERFLOW;
-        for (uint32_t r0 = 0; e == hipSuccess && r0 < kf.rows; r0 += pw_band_rows) {
-            rt::KernelFrame band = kf;
-            band.y0 = kf.y0 + r0 * kf.y_step;
-            band.rows = kf.rows - r0 < pw_band_rows ? kf.rows - r0 : pw_band_rows;
-            float *band_rgb = d_rgb + (size_t)r0 * kf.cols * 3u;
+        for (uint64_t u0 = 0; e == hipSuccess && u0 < units; u0 += pw_band_units) {
+            rt::KernelFrame band;
+            float *band_rgb;
+            band_of(u0, pw_band_units, &band, &band_rgb);
             {   /* a stride near the golden section of the tile count scatters consecutive tile fetches over the image */
                 auto gcd = [](uint64_t a, uint64_t b) { while (b) { const uint64_t t = a % b; a = b; b = t; } return a; };
                 const uint64_t tiles = ((uint64_t)band.cols * band.rows + 63u) / 64u;
@@ -542,7 +565,7 @@ int rt_render_whitted(const rt_scene *scene, const rt_camera *camera, const rt_f
                 while (gcd(stride, tiles) != 1) stride += 1;
                 pw.tile_stride = (uint32_t)stride;
             }
-            const bool first = r0 == 0, last = r0 + pw_band_rows >= kf.rows;
+            const bool first = u0 == 0, last = u0 + pw_band_units >= units;
             e = rt::launch_pwf(scene->ks, band, band_rgb, pw, pw_groups, stream, pw_init, first, last);
             if (e == hipSuccess) {
                 rt::mute_main_kernel_events(true); /* the event pair brackets the persistent kernel(s), not the fallback */
@@ -554,12 +577,93 @@ int rt_render_whitted(const rt_scene *scene, const rt_camera *camera, const rt_f
             rt_scene *mut = const_cast<rt_scene *>(scene);
             std::lock_guard<std::mutex> lock(mut->ws_mutex);
             mut->workspaces[stream].pw_ready = false; /* whatever state the blocks are in: the next launch prepares its own */
-            return fail_hip("rt_render_whitted: launch", e);
+            return fail_hip((std::string(who) + ": launch").c_str(), e);
         }
         return RT_OK;
     }
-    e = rt::launch_whitted(scene->ks, kf, d_rgb, d_ray_count, qs, stream, variant);
-    if (e != hipSuccess) return fail_hip("rt_render_whitted: launch", e);
+    /* the per-pixel kernel: a camera frame in one launch, a ray batch in bands of RT_TRACE_BAND_RAYS (one event pair around them all) */
+    const uint32_t band_units = rays && units > RT_TRACE_BAND_RAYS ? RT_TRACE_BAND_RAYS : units;
+    const bool several = band_units < units;
+    if (several) {
+        rt::record_main_kernel_event(0, stream);
+        rt::mute_main_kernel_events(true);
+    }
+    for (uint64_t u0 = 0; e == hipSuccess && u0 < units; u0 += band_units) {
+        rt::KernelFrame band;
+        float *band_rgb;
+        band_of(u0, band_units, &band, &band_rgb);
+        e = rt::launch_whitted(scene->ks, band, band_rgb, d_ray_count, qs, stream, variant);
+    }
+    if (several) {
+        rt::mute_main_kernel_events(false);
+        if (e == hipSuccess) rt::record_main_kernel_event(1, stream);
+    }
+    if (e != hipSuccess) return fail_hip((std::string(who) + ": launch").c_str(), e);
+    return RT_OK;
+}
+
+extern "C" {
+int rt_render_whitted(const rt_scene *scene, const rt_camera *camera, const rt_frame *frame, float *d_rgb,
+                      unsigned long long *d_ray_count, void *hip_stream) {
+    if (!scene || !d_rgb) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_whitted: null argument");
+    rt::KernelFrame kf;
+    int rc = make_kernel_frame(camera, frame, &kf);
+    if (rc != RT_OK) return rc;
+    return render_whitted_frame(scene, kf, nullptr, d_rgb, d_ray_count, static_cast<hipStream_t>(hip_stream), "rt_render_whitted");
+}
+
+int rt_trace_rays(const rt_scene *scene, const rt_ray *d_rays, size_t n_rays, int32_t max_depth, float contribution, float *d_rgb,
+                  unsigned long long *d_ray_count, void *hip_stream) {
+    if ((uint64_t)n_rays >= (1ull << 32)) return fail(RT_ERR_UNSUPPORTED, "rt_trace_rays: 2^32 rays or more (checked first; trace them in several calls)");
+    if (!scene) return fail(RT_ERR_INVALID_ARGUMENT, "rt_trace_rays: null scene");
+    if (n_rays == 0) return RT_OK;
+    if (!d_rays || !d_rgb) return fail(RT_ERR_INVALID_ARGUMENT, "rt_trace_rays: null ray or rgb pointer");
+    if (max_depth > RT_MAX_DEPTH) return fail(RT_ERR_UNSUPPORTED, "rt_trace_rays: max_depth above RT_MAX_DEPTH");
+    /* max_depth < 0 renders as 0, as in rt_render_whitted (TraceState.depth is tested with `depth <= 0`, main.rs:488) */
+    rt::KernelFrame kf;
+    memset(&kf, 0, sizeof kf);
+    kf.cols = (uint32_t)n_rays;
+    kf.rows = 1u;
+    kf.max_depth = max_depth;
+    rt::frame_set_rays(&kf, d_rays, contribution);
+    return render_whitted_frame(scene, kf, d_rays, d_rgb, d_ray_count, static_cast<hipStream_t>(hip_stream), "rt_trace_rays");
+}
+
+int rt_trace_rays_host(const rt_scene *scene, const rt_ray *h_rays, size_t n_rays, int32_t max_depth, float contribution, float *h_rgb,
+                       unsigned long long *h_ray_count) {
+    if ((uint64_t)n_rays >= (1ull << 32)) return fail(RT_ERR_UNSUPPORTED, "rt_trace_rays_host: 2^32 rays or more (checked first; trace them in several calls)");
+    if (!scene) return fail(RT_ERR_INVALID_ARGUMENT, "rt_trace_rays_host: null scene");
+    if (n_rays == 0) {
+        if (h_ray_count) *h_ray_count = 0;
+        return RT_OK;
+    }
+    if (!h_rays || !h_rgb) return fail(RT_ERR_INVALID_ARGUMENT, "rt_trace_rays_host: null ray or rgb pointer");
+    if (max_depth > RT_MAX_DEPTH) return fail(RT_ERR_UNSUPPORTED, "rt_trace_rays_host: max_depth above RT_MAX_DEPTH");
+    const size_t rgb_bytes = n_rays * 3 * sizeof(float);
+    rt_ray *d_rays = nullptr;
+    float *d_rgb = nullptr;
+    unsigned long long *d_cnt = nullptr;
+    RT_HIP(hipMalloc(reinterpret_cast<void **>(&d_rays), n_rays * sizeof(rt_ray)));
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(&d_rgb), rgb_bytes);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_cnt), sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemset(d_cnt, 0, sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemcpy(d_rays, h_rays, n_rays * sizeof(rt_ray), hipMemcpyHostToDevice);
+    int rc = RT_OK;
+    if (e == hipSuccess) {
+        rc = rt_trace_rays(scene, d_rays, n_rays, max_depth, contribution, d_rgb, d_cnt, nullptr);
+        if (rc == RT_OK) {
+            e = hipDeviceSynchronize();
+            if (e == hipSuccess) e = hipMemcpy(h_rgb, d_rgb, rgb_bytes, hipMemcpyDeviceToHost);
+            unsigned long long cnt = 0;
+            if (e == hipSuccess) e = hipMemcpy(&cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost);
+            if (e == hipSuccess && h_ray_count) *h_ray_count = cnt;
+        }
+    }
+    (void)hipFree(d_rays);
+    if (d_rgb) (void)hipFree(d_rgb);
+    if (d_cnt) (void)hipFree(d_cnt);
+    if (rc != RT_OK) return rc;
+    if (e != hipSuccess) return fail_hip("rt_trace_rays_host", e);
     return RT_OK;
 }
 

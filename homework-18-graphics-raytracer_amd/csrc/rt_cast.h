@@ -41,6 +41,25 @@ struct Ray {
     uint32_t excl; /* packed exclusion */
 };
 
+/* an ABI record (include/rt_amd.h rt_ray) as the kernels' Ray: rt_query.hip's ray queries and the roots of a ray batch (rt_trace_rays).
+ * The scene's sizes are at most 2^29 - 1 primitives together (rt_scene_create), so a packed primitive id always fits */
+__device__ __forceinline__ Ray ray_from_abi(const rt_ray *__restrict__ r, uint32_t n_triangles, uint32_t n_spheres) {
+    Ray q;
+    q.o = v3(r->origin[0], r->origin[1], r->origin[2]);
+    q.d = v3(r->direction[0], r->direction[1], r->direction[2]);
+    const uint32_t mode = r->face_direction;
+    q.mode = mode > FACE_BOTH ? FACE_BOTH : mode; /* (main.rs:185-186 test Front and Back; anything else culls nothing) */
+    q.excl = 0u;
+    if (r->has_exclude != 0u) {
+        const uint32_t kind = r->exclude_kind, index = r->exclude_index;
+        const uint32_t face = r->exclude_face > FACE_BOTH ? FACE_BOTH : r->exclude_face;
+        /* an index beyond its array never equals a PrimitiveIndex of the scene (main.rs:190-200, 315-319): no exclusion */
+        if (kind == 1u && index < n_triangles) q.excl = pack_excl(index, face);
+        else if (kind == 0u && index < n_spheres) q.excl = pack_excl(n_triangles + index, face);
+    }
+    return q;
+}
+
 struct CastResult {
     float t;       /* travel distance of the nearest hit */
     int32_t prim;  /* -1 = miss */

@@ -7,6 +7,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 
 #include "../../include/rt_amd.h"
 #include "rt_device_scene.h"
@@ -78,6 +79,28 @@ struct KernelFrame {
     float cam_origin_focus[3]; /* center + normalize(normalize(toward)) * near: shoot_focus normalises twice (main.rs:119) */
 };
 
+/* A ray batch (rt_trace_rays) is rendered as a frame of ONE row whose roots are read from rt_ray records instead of shot from the
+ * camera: cols = the band's rays, rows = 1, so slot i of a tile hand-out is ray i (pw_slot_to_pixel is the identity on one row) and
+ * so is the output index.  Its description has y_step 0 (a camera frame has y_step >= 1), and the camera's fields, unused, carry
+ * the batch: cam_origin[0] / [1] the address of the band's first record (low / high word), cam_origin[2] the roots' contribution.
+ * (The struct keeps its size and layout: it is a by-value argument of the per-pixel kernel, whose camera instantiations are to
+ * compile as before.)  The kernels take the roots from there when instantiated with RAYS = true. */
+__host__ __device__ inline bool frame_is_rays(const KernelFrame &fr) { return fr.y_step == 0u; }
+inline void frame_set_rays(KernelFrame *fr, const rt_ray *rays, float contribution) {
+    const uint64_t a = (uint64_t)(uintptr_t)rays;
+    const uint32_t lo = (uint32_t)a, hi = (uint32_t)(a >> 32);
+    fr->y_step = 0u;
+    memcpy(&fr->cam_origin[0], &lo, sizeof lo);
+    memcpy(&fr->cam_origin[1], &hi, sizeof hi);
+    fr->cam_origin[2] = contribution;
+}
+template <class F> /* KernelFrame, by value or in the constant address space */
+__device__ __forceinline__ const rt_ray *frame_rays(const F &fr) {
+    return reinterpret_cast<const rt_ray *>((uintptr_t)__float_as_uint(fr.cam_origin[0]) | ((uintptr_t)__float_as_uint(fr.cam_origin[1]) << 32));
+}
+template <class F>
+__host__ __device__ __forceinline__ float frame_root_contribution(const F &fr) { return fr.cam_origin[2]; }
+
 /* what a launch of the per-pixel kernel is told besides the scene and the frame */
 struct KernelQueues {
     unsigned long long *timeline;  /* diagnostic builds (RT_DIAG_TIMELINE): 4 u64 per wave, else unused */
@@ -112,6 +135,9 @@ void mute_main_kernel_events(bool muted);                        /* launches in 
 
 hipError_t launch_whitted(const KernelScene &sc, const KernelFrame &fr, float *out, unsigned long long *ray_count,
                           const KernelQueues &qs, hipStream_t stream, int variant);
+/* the launch of whitted_kernel<MAXD, USE_LDS, true> for a ray batch (rt_kernels_rays.hip; called by launch_whitted) */
+hipError_t launch_tiles_rays(int maxd, const KernelScene &sc, const KernelFrame &fr, float *out, unsigned long long *ray_count,
+                             const KernelQueues &qs, uint32_t waves, hipStream_t stream, bool use_lds);
 
 /* persistent workgroup-local wavefronts (rt_pwf.hip) */
 #define PW_G_TILE 0u       /* next tile of the frame */
@@ -149,6 +175,9 @@ size_t pwf_arena_bytes(uint32_t node_cap, uint32_t ring_cap);
  * both as this one needs them */
 hipError_t launch_pwf(const KernelScene &sc, KernelFrame fr, float *out, const PwParams &pp, uint32_t workgroups, hipStream_t stream,
                       bool init, bool first_band, bool last_band);
+/* the launch of pwf_kernel<PACKED, BFS, true> for a ray batch (rt_pwf_rays.hip; called by launch_pwf) */
+void launch_pwf_rays(const KernelScene &sc, const PwParams &pp, float *out, uint32_t workgroups, size_t lds, hipStream_t stream, bool packed,
+                     bool bfs);
 
 /* distributed pass (rt_distributed.hip) */
 struct DistParams {

@@ -66,7 +66,9 @@ struct Frame {
  * them in a second pass, a cost probe with most-expensive-first dispatch, and cooperative workgroups whose four waves split
  * every tile's triangle loop; all bit-identical, all slower or equal — numbers in profiles/README.md — and removed in round 2
  * when the persistent wavefront kernel of rt_pwf.hip had long been the default and this kernel its fallback.) */
-template <int MAXD, bool USE_LDS>
+/* RAYS: the roots are a ray batch's (rt_trace_rays; rt_kernels.h frame_is_rays): read from rt_ray records, with the batch's
+ * contribution and ray_trace's entry check, and their values written as ray_trace returns them */
+template <int MAXD, bool USE_LDS, bool RAYS>
 __device__ __forceinline__ void whitted_body(const KernelScene &sc, const KernelFrame &fr, float *__restrict__ out,
                                              unsigned long long *__restrict__ ray_count, const KernelQueues &qs, const DevTri *lds_tris,
                                              const uint32_t wave) {
@@ -126,7 +128,20 @@ __device__ __forceinline__ void whitted_body(const KernelScene &sc, const Kernel
         while (need != 0ull && q_next != q_end) {
             const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(need >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)need, 0u));
             const uint32_t avail = q_end - q_next;
-            if (phase == PH_DONE && rank < avail) {
+            if (RAYS && phase == PH_DONE && rank < avail) {
+                /* TraceState { depth: max_depth, contribution } on the caller's ray; the frame's one row makes slot = ray index */
+                const uint32_t slot = q_next + rank;
+                out_index = slot;
+                req = ray_from_abi(frame_rays(fr) + slot, sc.n_triangles, sc.n_spheres);
+                contribution = frame_root_contribution(fr);
+                sp = 0;
+                if (contribution < THRESHOLD) { /* ray_trace's entry check (main.rs:469): black, no cast; the lane takes the next ray */
+                    float *px = out + (size_t)slot * 3u;
+                    px[0] = px[1] = px[2] = 0.0f;
+                } else {
+                    phase = PH_NODE;
+                }
+            } else if (!RAYS && phase == PH_DONE && rank < avail) {
                 const uint32_t slot = q_next + rank;
                 const uint32_t band = slot / band_slots;
                 const uint32_t r = slot - band * band_slots;
@@ -377,11 +392,16 @@ __device__ __forceinline__ void whitted_body(const KernelScene &sc, const Kernel
                     break;
                 } else { /* GO_RETURN: unwind finished activations */
                     if (sp == 0) {
-                        /* img[at] = img[at] + photon on a zeroed image (main.rs:1107) */
                         float *px = out + (size_t)out_index * 3u;
-                        px[0] = 0.0f + value.x;
-                        px[1] = 0.0f + value.y;
-                        px[2] = 0.0f + value.z;
+                        if (RAYS) { /* ray_trace's own value, -0.0 and NaN as they are */
+                            px[0] = value.x;
+                            px[1] = value.y;
+                            px[2] = value.z;
+                        } else { /* img[at] = img[at] + photon on a zeroed image (main.rs:1107) */
+                            px[0] = 0.0f + value.x;
+                            px[1] = 0.0f + value.y;
+                            px[2] = 0.0f + value.z;
+                        }
                         phase = PH_DONE;
                         break;
                     }
@@ -428,7 +448,7 @@ __device__ __forceinline__ void whitted_body(const KernelScene &sc, const Kernel
     }
 }
 
-template <int MAXD, bool USE_LDS>
+template <int MAXD, bool USE_LDS, bool RAYS = false>
 __global__ RT_LAUNCH_BOUNDS void whitted_kernel(const KernelScene sc, const KernelFrame fr, float *__restrict__ out,
                                                 unsigned long long *__restrict__ ray_count, const KernelQueues qs) {
     if (qs.run_if != nullptr && *qs.run_if == 0u) return; /* fallback launch that is not needed */
@@ -448,7 +468,7 @@ __global__ RT_LAUNCH_BOUNDS void whitted_kernel(const KernelScene sc, const Kern
      * tiles a grid apart */
     const uint32_t n_waves = gridDim.x * (blockDim.x >> 6);
     for (uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6; wave < fr.n_chunks; wave += n_waves)
-        whitted_body<MAXD, USE_LDS>(sc, fr, out, ray_count, qs, lds_tris, wave);
+        whitted_body<MAXD, USE_LDS, RAYS>(sc, fr, out, ray_count, qs, lds_tris, wave);
 }
 
 } /* namespace rt */
@@ -457,19 +477,33 @@ __global__ RT_LAUNCH_BOUNDS void whitted_kernel(const KernelScene sc, const Kern
 
 namespace rt {
 
-template <int MAXD>
-static hipError_t launch_tiles(const KernelScene &sc, const KernelFrame &fr, float *out, unsigned long long *ray_count,
-                               const KernelQueues &qs, uint32_t waves, hipStream_t stream, bool use_lds) {
+template <int MAXD, bool RAYS>
+static hipError_t launch_tiles_of(const KernelScene &sc, const KernelFrame &fr, float *out, unsigned long long *ray_count,
+                                  const KernelQueues &qs, uint32_t waves, hipStream_t stream, bool use_lds) {
     if (waves == 0u) return hipSuccess;
     const uint32_t waves_per_block = RT_BLOCK_THREADS / 64;
     const uint32_t blocks = (waves + waves_per_block - 1) / waves_per_block;
     if (use_lds) {
         const size_t lds = (size_t)sc.n_triangles * sizeof(DevTri);
-        hipLaunchKernelGGL((whitted_kernel<MAXD, true>), dim3(blocks), dim3(RT_BLOCK_THREADS), lds, stream, sc, fr, out, ray_count, qs);
+        hipLaunchKernelGGL((whitted_kernel<MAXD, true, RAYS>), dim3(blocks), dim3(RT_BLOCK_THREADS), lds, stream, sc, fr, out, ray_count, qs);
     } else {
-        hipLaunchKernelGGL((whitted_kernel<MAXD, false>), dim3(blocks), dim3(RT_BLOCK_THREADS), 0, stream, sc, fr, out, ray_count, qs);
+        hipLaunchKernelGGL((whitted_kernel<MAXD, false, RAYS>), dim3(blocks), dim3(RT_BLOCK_THREADS), 0, stream, sc, fr, out, ray_count, qs);
     }
     return hipGetLastError();
+}
+
+} /* namespace rt */
+
+/* The ray-batch instantiations (RAYS = true) are compiled from this file once more, in rt_kernels_rays.hip, which takes nothing
+ * below: the camera instantiations' code object stays as it was without them. */
+#ifndef RT_KERNELS_RAYS_TU
+namespace rt {
+
+template <int MAXD>
+static hipError_t launch_tiles(const KernelScene &sc, const KernelFrame &fr, float *out, unsigned long long *ray_count,
+                               const KernelQueues &qs, uint32_t waves, hipStream_t stream, bool use_lds) {
+    if (frame_is_rays(fr)) return launch_tiles_rays(MAXD, sc, fr, out, ray_count, qs, waves, stream, use_lds);
+    return launch_tiles_of<MAXD, false>(sc, fr, out, ray_count, qs, waves, stream, use_lds);
 }
 
 /* optional HIP events recorded on the launch stream right around the dominant (render) kernel of a call */
@@ -557,3 +591,4 @@ void math_eval_host(int op, const float *x, const float *y, float *out, size_t n
 #ifdef RT_DIAG_STAGES
 RT_DIAG_STAGE_READER(rt_diag_read_stages_kernels)
 #endif
+#endif /* RT_KERNELS_RAYS_TU */

@@ -221,8 +221,10 @@ __device__ unsigned long long pa_phase_stats[32];
  * by-value argument its 25 dwords would sit in SGPRs across the intersection loop, which needs those itself */
 /* PACKED: the arena queues' page counters two to a word (rt_pwf_common.h): frames of several megapixels.
  * BFS: the intersection loop as a breadth-first walk of the node tree, ray by ray (rt_cast_bfs.h cast_bfs): scenes beyond the caches
- * (KernelScene::bfs_walk); 20 KB more LDS per workgroup for the waves' ray tables */
-template <bool PACKED, bool BFS = false>
+ * (KernelScene::bfs_walk); 20 KB more LDS per workgroup for the waves' ray tables
+ * RAYS: the roots are a ray batch's (rt_trace_rays; rt_kernels.h frame_is_rays): read from rt_ray records, with the batch's
+ * contribution and ray_trace's entry check, and their values written as ray_trace returns them */
+template <bool PACKED, bool BFS = false, bool RAYS = false>
 __global__ __launch_bounds__(PA_THREADS, BFS ? 2 : PA_MIN_WAVES) void pwf_kernel(const KernelScene sc, const PwParams pp, float *__restrict__ out) {
     BfsLds *bfs_lds = nullptr;
     BfsScratch bfs_ws = {nullptr, nullptr, nullptr, 0u, 0u};
@@ -523,7 +525,12 @@ __global__ __launch_bounds__(PA_THREADS, BFS ? 2 : PA_MIN_WAVES) void pwf_kernel
             if (lane == 0u) { tile_list[entry * 2u] = tile; tile_list[entry * 2u + 1u] = first_id; }
             id = first_id + lane;
             depth = (uint32_t)(fr.max_depth > 0 ? fr.max_depth : 0);
-            if (active) {
+            if constexpr (RAYS) {
+                /* TraceState { depth: max_depth, contribution } on the caller's ray; the frame's one row makes slot = ray index */
+                contribution = frame_root_contribution(fr);
+                if (active) req = ray_from_abi(frame_rays(fr) + (tile * 64u + lane), sc.n_triangles, sc.n_spheres);
+                do_cast = active && !(contribution < THRESHOLD); /* ray_trace's entry check (main.rs:469): black, no cast — a miss's value */
+            } else if (active) {
                 uint32_t row, col;
                 pw_slot_to_pixel(fr, tile * 64u + lane, &row, &col);
                 /* Camera::shoot (main.rs:84-99), per-frame basis hoisted to the host */
@@ -1023,11 +1030,16 @@ __global__ __launch_bounds__(PA_THREADS, BFS ? 2 : PA_MIN_WAVES) void pwf_kernel
                 }
                 uint32_t row, col;
                 pw_slot_to_pixel(fr, slot[j], &row, &col);
-                /* img[at] = img[at] + photon on a zeroed image (main.rs:1107) */
                 float *px = out + ((size_t)row * fr.cols + col) * 3u;
-                px[0] = 0.0f + value.x;
-                px[1] = 0.0f + value.y;
-                px[2] = 0.0f + value.z;
+                if constexpr (RAYS) { /* ray_trace's own value, -0.0 and NaN as they are */
+                    px[0] = value.x;
+                    px[1] = value.y;
+                    px[2] = value.z;
+                } else { /* img[at] = img[at] + photon on a zeroed image (main.rs:1107) */
+                    px[0] = 0.0f + value.x;
+                    px[1] = 0.0f + value.y;
+                    px[2] = 0.0f + value.z;
+                }
             }
         }
         if (threadIdx.x == 0u && n_started != 0u) atomicAdd(pp.global + PW_G_TILES_DONE, n_started);
@@ -1087,6 +1099,23 @@ __global__ __launch_bounds__(PA_THREADS, BFS ? 2 : PA_MIN_WAVES) void pwf_kernel
     }
 }
 
+template <bool RAYS>
+static void launch_pwf_kernel(const KernelScene &sc, const PwParams &pp, float *out, uint32_t workgroups, size_t lds, hipStream_t stream, bool packed,
+                              bool bfs) {
+    if (bfs) {
+        if (packed) hipLaunchKernelGGL((pwf_kernel<true, true, RAYS>), dim3(workgroups), dim3(PA_THREADS), lds, stream, sc, pp, out);
+        else hipLaunchKernelGGL((pwf_kernel<false, true, RAYS>), dim3(workgroups), dim3(PA_THREADS), lds, stream, sc, pp, out);
+    } else if (packed) hipLaunchKernelGGL((pwf_kernel<true, false, RAYS>), dim3(workgroups), dim3(PA_THREADS), lds, stream, sc, pp, out);
+    else hipLaunchKernelGGL((pwf_kernel<false, false, RAYS>), dim3(workgroups), dim3(PA_THREADS), lds, stream, sc, pp, out);
+}
+
+} /* namespace rt */
+
+/* The ray-batch instantiations (RAYS = true) are compiled from this file once more, in rt_pwf_rays.hip, which takes nothing below:
+ * the camera instantiations' code object stays as it was without them. */
+#ifndef RT_PWF_RAYS_TU
+namespace rt {
+
 static size_t pwf_dynamic_lds(uint32_t node_cap, uint32_t ring_cap) {
     const bool packed = pa_ready_packed(node_cap, ring_cap);
     return (size_t)(PA_READY_WORDS((node_cap + 63u) / 64u, packed) + 2u * PA_READY_WORDS(ring_cap / 64u, packed)) * sizeof(uint32_t);
@@ -1144,11 +1173,8 @@ hipError_t launch_pwf(const KernelScene &sc, KernelFrame fr, float *out, const P
     if (first_band) record_main_kernel_event(0, stream); /* the pair brackets all bands of a call (one, up to ~8 Mpixel) */
     const size_t lds = pwf_dynamic_lds(pp.node_cap, pp.ring_cap);
     const bool packed = pa_ready_packed(pp.node_cap, pp.ring_cap);
-    if (sc.bfs_walk != 0u && pp.bfs_scratch != nullptr) {
-        if (packed) hipLaunchKernelGGL((pwf_kernel<true, true>), dim3(workgroups), dim3(PA_THREADS), lds, stream, sc, pp, out);
-        else hipLaunchKernelGGL((pwf_kernel<false, true>), dim3(workgroups), dim3(PA_THREADS), lds, stream, sc, pp, out);
-    } else if (packed) hipLaunchKernelGGL((pwf_kernel<true, false>), dim3(workgroups), dim3(PA_THREADS), lds, stream, sc, pp, out);
-    else hipLaunchKernelGGL((pwf_kernel<false, false>), dim3(workgroups), dim3(PA_THREADS), lds, stream, sc, pp, out);
+    if (frame_is_rays(fr)) launch_pwf_rays(sc, pp, out, workgroups, lds, stream, packed, sc.bfs_walk != 0u && pp.bfs_scratch != nullptr);
+    else launch_pwf_kernel<false>(sc, pp, out, workgroups, lds, stream, packed, sc.bfs_walk != 0u && pp.bfs_scratch != nullptr);
     if (last_band) record_main_kernel_event(1, stream);
     return hipGetLastError();
 }
@@ -1164,3 +1190,4 @@ RT_DIAG_NEED_READER(rt_diag_read_need_pwf)
 #ifdef RT_DIAG_BFS
 RT_DIAG_BFS_READER(rt_diag_read_bfs)
 #endif
+#endif /* RT_PWF_RAYS_TU */

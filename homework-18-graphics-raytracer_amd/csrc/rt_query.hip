@@ -15,24 +15,6 @@
 
 namespace rt {
 
-/* the scene's sizes are at most 2^29 - 1 primitives together (rt_scene_create), so a packed primitive id always fits */
-__device__ __forceinline__ Ray ray_from_abi(const rt_ray *__restrict__ r, uint32_t n_triangles, uint32_t n_spheres) {
-    Ray q;
-    q.o = v3(r->origin[0], r->origin[1], r->origin[2]);
-    q.d = v3(r->direction[0], r->direction[1], r->direction[2]);
-    const uint32_t mode = r->face_direction;
-    q.mode = mode > FACE_BOTH ? FACE_BOTH : mode; /* (main.rs:185-186 test Front and Back; anything else culls nothing) */
-    q.excl = 0u;
-    if (r->has_exclude != 0u) {
-        const uint32_t kind = r->exclude_kind, index = r->exclude_index;
-        const uint32_t face = r->exclude_face > FACE_BOTH ? FACE_BOTH : r->exclude_face;
-        /* an index beyond its array never equals a PrimitiveIndex of the scene (main.rs:190-200, 315-319): no exclusion */
-        if (kind == 1u && index < n_triangles) q.excl = pack_excl(index, face);
-        else if (kind == 0u && index < n_spheres) q.excl = pack_excl(n_triangles + index, face);
-    }
-    return q;
-}
-
 /* the Hit of main.rs:139-147 as the ABI record; a miss is RT_HIT_NONE with every other field 0 */
 template <class Scene>
 __device__ __forceinline__ void store_hit(const Scene &sc, const Ray &ray, const CastResult &cr, rt_hit *__restrict__ out) {

@@ -248,6 +248,36 @@ int rt_cast_rays_host(const rt_scene *scene, const rt_ray *h_rays, size_t n_rays
  * exclusion; each ray is bit for bit the primary ray the Whitted pass casts.  frame->max_depth is not used.  Stream-ordered. */
 int rt_camera_rays(const rt_camera *camera, const rt_frame *frame, rt_ray *d_rays, void *hip_stream);
 
+/* ---- radiance queries: ray_trace on caller-supplied rays ------------------------------
+
+ * ray_trace (src/main.rs:466-519) for every ray: d_rgb[3*i + c] = ray_trace(world, d_rays[i], TraceState { depth: max_depth,
+ * contribution }) — the Whitted render with the caller's rays as its roots: a camera model the library does not have (a 360-degree,
+ * fisheye, orthographic or stereo view), a re-render of chosen pixels, the secondary rays of the caller's own integrator.
+ * Device pointers (n_rays records, 3 * n_rays floats); stream-ordered and asynchronous on hip_stream (NULL = default stream).
+ *   value        ray_trace's own return value, bit for bit, NaN included.  It is NOT `0.0 + value` as a frame stores it
+ *                (main.rs:1107; rt_render_whitted), so a -0.0 channel stays -0.0: rt_trace_rays(rt_camera_rays(frame)) + 0.0f
+ *                equals rt_render_whitted(frame) bit for bit.
+ *   d_rays       rt_ray records read exactly as rt_cast_rays reads them: a face value above 2 is Both, an exclusion whose index is
+ *                outside its array excludes nothing, the direction is used as given.
+ *   max_depth    as rt_frame.max_depth: negative renders like 0, above RT_MAX_DEPTH is RT_ERR_UNSUPPORTED.
+ *   contribution the roots' TraceState.contribution, ray_trace's entry check included (below THRESHOLD = 0.001: black, no cast,
+ *                main.rs:469).  Any float, NaN included (it passes the check and no child or shade is wanted: black, one cast).
+ *   d_ray_count  NULL or one u64 device word: the call's World::cast count is ADDED to it (the sum over the rays of what the
+ *                recursion of each casts).
+ * Checked before any device work, in this order: n_rays >= 2^32 is RT_ERR_UNSUPPORTED; a null scene RT_ERR_INVALID_ARGUMENT;
+ * n_rays == 0 is RT_OK and launches nothing; a null ray or rgb pointer RT_ERR_INVALID_ARGUMENT; then max_depth.
+ * Workspace and graph capture as rt_render_whitted: the call shares the per-(scene, stream) workspace, and may be captured after
+ * one uncaptured call on that stream.  rt_profile_enable / rt_profile_read bracket its render kernel(s) as rt_render_whitted's.
+ * Speed depends on the ORDER of the rays: the kernels cast 64 consecutive rays per wave, wave-uniformly, so rays that travel
+ * together should be neighbours (rt_camera_rays' row order makes 64x1 strips; an 8x8-tile order is what rt_render_whitted uses;
+ * DESIGN.md §3.8).  Not covered: the depth-of-field pass, per-ray cast counts. */
+int rt_trace_rays(const rt_scene *scene, const rt_ray *d_rays, size_t n_rays, int32_t max_depth, float contribution,
+                  float *d_rgb, unsigned long long *d_ray_count, void *hip_stream);
+/* Same, with host buffers: allocates, launches, copies back and synchronises.  *h_ray_count is overwritten with the cast count
+ * of this call (may be NULL).  Without a device it fails with a status and writes nothing into h_rgb. */
+int rt_trace_rays_host(const rt_scene *scene, const rt_ray *h_rays, size_t n_rays, int32_t max_depth, float contribution,
+                       float *h_rgb, unsigned long long *h_ray_count);
+
 /* ---- distributed (stochastic / depth-of-field) pass ----------------------------
 
  * Replaces the par_iter_mut closure at src/main.rs:1131-1156 and the per-pixel RNG construction at

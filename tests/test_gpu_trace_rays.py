@@ -1,0 +1,484 @@
+"""Radiance queries on the device (include/rt_amd.h rt_trace_rays): ray_trace (src/main.rs:466-519) on caller-supplied rays.  Every
+channel equals the oracle's orc_ray_trace bit for bit (NaN equal to NaN, -0.0 not equal to +0.0) and the cast counts add up to the
+oracle's; a frame's camera rays give the frame (after + 0.0) and its cast count.  Each case runs on the persistent wavefront kernel
+(variant 18) and on the per-pixel kernel (variant 2)."""
+import contextlib
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import homework_18_graphics_raytracer_amd as rt
+from homework_18_graphics_raytracer_amd import _capi
+import _oracle
+import _scenes
+from test_gpu_ray_query import _tessellated, bounds, random_rays
+
+pytestmark = pytest.mark.gpu
+PATHS = [18, 2]
+HEADLINE_CASTS = 17756787  # World::cast evaluations of the 1920x1080 depth-8 frame (test_gpu_wavefront.py)
+
+
+def _torch():
+    import torch
+
+    torch.cuda.set_device(0)
+    return torch
+
+
+@contextlib.contextmanager
+def variant(v, budget=None):
+    lib = _capi.amd_lib()
+    _capi.check(lib.rt_set_variant(v))
+    if budget is not None:
+        _capi.check(lib.rt_set_wavefront_budget(budget))
+    try:
+        yield
+    finally:
+        _capi.check(lib.rt_set_variant(_capi.DEFAULT_VARIANT))
+        _capi.check(lib.rt_set_wavefront_budget(6))
+
+
+_oracle_cache = {}
+
+
+def oracle_trace(desc, rays_t, depth, contribution, key=None):
+    """orc_ray_trace of every ray record of an (N, 11) int32 tensor: ((N, 3) float32, summed cast count); cached under `key`"""
+    ck = None if key is None else (key, depth, np.float32(contribution).tobytes())
+    if ck in _oracle_cache:
+        return _oracle_cache[ck]
+    rays = np.ascontiguousarray(rays_t.cpu().numpy()).view(np.uint32).reshape(-1, 11).copy()
+    n = rays.shape[0]
+    orays = (_oracle.OrcRay * n).from_buffer(rays)
+    rgb = np.zeros((n, 3), dtype=np.float32)
+    buf = (C.c_float * 3)()
+    casts = C.c_uint64(0)
+    total = 0
+    lib = _oracle.lib()
+    for i in range(n):
+        lib.orc_ray_trace(C.byref(desc), C.byref(orays[i]), int(depth), float(contribution), buf, C.byref(casts))
+        rgb[i] = np.frombuffer(buf, dtype=np.float32)
+        total += casts.value
+    if ck is not None:
+        _oracle_cache[ck] = (rgb, total)
+    return rgb, total
+
+
+def trace(scene, rays, depth, contribution=1.0, **kw):
+    torch = _torch()
+    count = torch.zeros(1, dtype=torch.int64, device="cuda")
+    out = rt.trace_rays(scene, rays, depth, contribution, ray_count=count, **kw)
+    torch.cuda.synchronize()
+    return out.cpu().numpy(), int(count.item())
+
+
+def assert_same(got, want, what=""):
+    g, w = np.asarray(got, dtype=np.float32).reshape(-1, 3), np.asarray(want, dtype=np.float32).reshape(-1, 3)
+    same = (g.view(np.uint32) == w.view(np.uint32)) | (np.isnan(g) & np.isnan(w))
+    bad = np.argwhere(~same)
+    assert same.all(), f"{what}: {len(bad)} channels differ, first {bad[:3].tolist()}: got {g[bad[0][0]]} want {w[bad[0][0]]}"
+
+
+def check(scene, desc, rays, depth, contribution=1.0, key=None, what=""):
+    got, casts = trace(scene, rays, depth, contribution)
+    want, wcasts = oracle_trace(desc, rays, depth, contribution, key)
+    assert_same(got, want, f"{what} depth {depth} contribution {contribution}")
+    assert casts == wcasts, f"{what} depth {depth} contribution {contribution}: {casts} casts, oracle {wcasts}"
+    return got, casts
+
+
+@pytest.fixture(scope="module")
+def ref():
+    world = rt.reference_world()
+    desc = world.desc()
+    centre, radius = bounds(desc)
+    return world, desc, rt.Scene(world), rt.reference_camera(), random_rays(41, 10007, desc, centre, radius)
+
+
+def tile_order(cols, rows):
+    """position k of the Whitted kernels' slot order (8-row bands, column-major inside a band: 8x8 tiles) -> row-order index"""
+    s = np.arange(cols * rows, dtype=np.int64)
+    band = s // (cols * 8)
+    r = s - band * cols * 8
+    band_rows = np.minimum(8, rows - band * 8)
+    col = r // band_rows
+    return (band * 8 + (r - col * band_rows)) * cols + col
+
+
+# ---- 1. the camera's rays give the frame ----
+
+FRAMES = {"256x256d1": rt.Frame.full(256, 256, 1), "320x240d5": rt.Frame.full(320, 240, 5), "1080p_d8": rt.Frame.full(1920, 1080, 8),
+          "tile_step3": rt.Frame(320, 240, 5, 17, 3, 300, 239, 3)}
+
+
+@pytest.mark.parametrize("v", PATHS)
+@pytest.mark.parametrize("name", list(FRAMES))
+def test_camera_rays_give_the_frame(ref, name, v):
+    torch = _torch()
+    world, desc, scene, cam, _ = ref
+    frame = FRAMES[name]
+    with variant(v):
+        count = torch.zeros(1, dtype=torch.int64, device="cuda")
+        want = rt.render_whitted(scene, cam, frame, ray_count=count)
+        got, casts = trace(scene, rt.camera_rays(cam, frame), frame.max_depth)
+    assert_same(got + np.float32(0.0), want.cpu().numpy(), name)
+    assert casts == int(count.item())
+    if name == "1080p_d8":
+        assert casts == HEADLINE_CASTS
+
+
+@pytest.mark.parametrize("v", PATHS)
+def test_tile_ordered_rays_give_the_frame(ref, v):
+    torch = _torch()
+    world, desc, scene, cam, _ = ref
+    for frame in (rt.Frame.full(320, 240, 5), rt.Frame.full(203, 97, 8)):  # a ragged last band too
+        perm = torch.from_numpy(tile_order(frame.cols, frame.rows)).cuda()
+        with variant(v):
+            count = torch.zeros(1, dtype=torch.int64, device="cuda")
+            want = rt.render_whitted(scene, cam, frame, ray_count=count)
+            rays = rt.camera_rays(cam, frame)[perm].contiguous()
+            got_t, casts = trace(scene, rays, frame.max_depth)
+        got = np.empty_like(got_t)
+        got[perm.cpu().numpy()] = got_t
+        assert_same(got + np.float32(0.0), want.cpu().numpy(), f"{frame.cols}x{frame.rows} tile order")
+        assert casts == int(count.item())
+
+
+# ---- 2. odd rays against the oracle ----
+
+@pytest.mark.parametrize("v", PATHS)
+def test_random_rays_against_the_oracle(ref, v):
+    world, desc, scene, cam, rays = ref
+    with variant(v):
+        got, _ = check(scene, desc, rays, 5, key="ref10k", what="random rays")
+        check(scene, desc, rays, 8, 0.37, key="ref10k", what="random rays")
+    assert (got != 0.0).any(axis=1).sum() > 1000  # the mix lights something
+
+
+@pytest.mark.parametrize("v", PATHS)
+def test_depths_and_contributions(ref, v):
+    world, desc, scene, cam, rays = ref
+    sub = rays[:1500].contiguous()
+    with variant(v):
+        for depth in (-1, 0, 1, 5, 8, 32):
+            check(scene, desc, sub, depth, key="ref1500", what="depth")
+        for c in (1.0, 0.37, 0.0011, 0.001, 0.0009, 0.0, float("nan")):
+            got, casts = check(scene, desc, sub, 5, c, key="ref1500", what="contribution")
+            if c < 0.001:  # ray_trace's entry check: black, no cast
+                assert casts == 0 and (got.view(np.uint32) == 0).all()
+            elif c != c:  # NaN passes the check and nothing below it: one cast per ray
+                assert casts == sub.shape[0]
+            else:  # THRESHOLD itself passes
+                assert casts >= sub.shape[0]
+
+
+def edge_rays(desc):
+    """rays in an axis-aligned triangle's plane (NaN distances), on sphere surfaces looking out, zero / tiny / huge / infinite / NaN
+    directions from ordinary, infinite and NaN origins, face values above 2"""
+    torch = _torch()
+    g = np.random.default_rng(5)
+    o, d, face = [], [], []
+    for i in range(desc.n_triangles):
+        p = np.array([v.position for v in desc.triangles[i].vertices], dtype=np.float32)
+        for k in range(3):
+            if p[0, k] == p[1, k] == p[2, k]:
+                c = p.mean(axis=0)
+                for j in range(3):
+                    along = np.zeros(3, np.float32)
+                    along[(k + 1 + j % 2) % 3] = 1.0 if j < 2 else -0.5
+                    along[(k + 2 - j % 2) % 3] = 0.25 * j
+                    origin = c - 3.0 * along
+                    origin[k] = p[0, k]
+                    o.append(origin)
+                    d.append(along)
+                    face.append(j % 3)
+    for i in range(desc.n_spheres):
+        s = desc.spheres[i]
+        for k in range(4):
+            u = g.normal(size=3)
+            u /= np.linalg.norm(u)
+            o.append(np.asarray(s.center) + u * s.radius)
+            d.append(u if k % 2 else -u)
+            face.append([1, 2][k % 2])
+    specials = [(0.0, 0.0, 0.0), (0.0, 0.0, -1e-30), (0.0, 0.0, -1e30), (3.0, -7.0, 11.0), (np.inf, 0.0, 0.0), (0.0, -np.inf, 0.0),
+                (np.nan, 0.0, -1.0), (0.1, 0.2, np.nan), (np.inf, np.inf, -np.inf)]
+    for k, dd in enumerate(specials):
+        for origin in ((0.0, 1.0, 3.0), (0.5, 0.5, 0.5), (np.inf, 0.0, 0.0), (np.nan, 1.0, 1.0)):
+            o.append(origin)
+            d.append(dd)
+            face.append(k % 3)
+    face = np.asarray(face)
+    face[::7] = 3 + face[::7]
+    return rt.make_rays(torch.tensor(np.asarray(o, np.float32), device="cuda"), torch.tensor(np.asarray(d, np.float32), device="cuda"),
+                        torch.tensor(face, device="cuda"))
+
+
+@pytest.mark.parametrize("v", PATHS)
+def test_edge_rays(ref, v):
+    world, desc, scene, cam, _ = ref
+    rays = edge_rays(desc)
+    with variant(v):
+        for depth, c in ((5, 1.0), (8, 0.37), (0, 1.0)):
+            got, _ = check(scene, desc, rays, depth, c, key="edge", what="edge rays")
+            # in-plane and NaN rays give NaN radiance (25-29 of the 136 rays in the oracle), compared above as NaN = NaN
+            assert np.isnan(got).any(axis=1).sum() >= 20, f"depth {depth}: only {np.isnan(got).any(axis=1).sum()} NaN rays"
+
+
+def negative_zero_world():
+    """a scene where ray_trace returns -0.0 (and 0.0 + value would be +0.0): a sphere with transparency 2 and shiness 0.5, so that the
+    shade and reflection coefficients are negative and their black terms -0.0, and opaque_decay 0, so that the refraction term is a
+    negative radiance times +0.0 = -0.0; behind it a wall with a negative diffuse colour, lit from the side"""
+    from homework_18_graphics_raytracer_amd._capi import Light, Material
+
+    def mat(diffuse, shiness, transparency, decay):
+        m = Material()
+        m.diffuse_fn = m.normal_fn = 0
+        m.normal = (0.0, 0.0, 1.0)
+        m.diffuse_color = diffuse
+        m.specular_color = (0.2, 0.2, 0.2)
+        m.shiness, m.smoothness, m.transparency, m.refraction_index, m.opaque_decay = shiness, 0.2, transparency, 1.0, decay
+        return m
+
+    w = rt.World()
+    glass = w.push_object(mat((0.5, 0.5, 0.5), 0.5, 2.0, 0.0))
+    wall = w.push_object(mat((-0.5, -0.25, -0.75), 0.0, 0.0, 1.0))
+    glass.push_sphere((0.0, 0.0, 0.0), 0.5)
+    wall.push_square([(-3, -3, -2), (3, -3, -2), (3, 3, -2), (-3, 3, -2)], [(0, 0), (1, 0), (1, 1), (0, 1)])
+    light = Light()
+    light.kind, light.has_origin, light.origin, light.color = 2, 1, (2.5, 0.0, 0.0), (1.0, 1.0, 1.0)
+    w.push_light(light)
+    return w
+
+
+@pytest.mark.parametrize("v", PATHS)
+def test_negative_zero_is_kept(v):
+    """the value is ray_trace's own, not 0.0 + value: the -0.0 channels the oracle returns come back as -0.0"""
+    torch = _torch()
+    world = negative_zero_world()
+    desc = world.desc()
+    scene = rt.Scene(world)
+    g = np.linspace(-0.7, 0.7, 48, dtype=np.float32)
+    xy = np.stack(np.meshgrid(g, g), axis=-1).reshape(-1, 2)
+    origins = np.concatenate([xy, np.full((xy.shape[0], 1), 2.0, np.float32)], axis=1)
+    dirs = np.tile(np.array([[0.0, 0.0, -1.0]], np.float32), (xy.shape[0], 1))
+    rays = rt.make_rays(torch.tensor(origins, device="cuda"), torch.tensor(dirs, device="cuda"))
+    with variant(v):
+        got, _ = check(scene, desc, rays, 5, key="negzero", what="negative zero")
+    want, _ = oracle_trace(desc, rays, 5, 1.0, key="negzero")
+    neg = (want == 0.0) & np.signbit(want)
+    assert neg.any(axis=1).sum() > 100, "the scene no longer produces -0.0"
+    assert (np.signbit(got) == np.signbit(want)).all()
+
+
+@pytest.mark.parametrize("v", PATHS)
+@pytest.mark.parametrize("make", ["random", "clustered", "squares"])
+def test_other_scenes(make, v):
+    world = {"random": lambda: _scenes.random_world(1, 40, 3), "clustered": lambda: _scenes.clustered_world(3, n_boxes=4),
+             "squares": lambda: _scenes.squares_world(8)}[make]()
+    desc = world.desc()
+    scene = rt.Scene(world)
+    centre, radius = bounds(desc)
+    rays = random_rays(100, 2000, desc, centre, radius)
+    with variant(v):
+        check(scene, desc, rays, 5, key=f"scene-{make}", what=make)
+
+
+# ---- 3. a camera the library does not have ----
+
+@pytest.mark.parametrize("v", PATHS)
+def test_equirectangular_panorama(ref, v):
+    torch = _torch()
+    world, desc, scene, cam, _ = ref
+    W, H = 512, 256
+    x = (torch.arange(W, device="cuda", dtype=torch.float32) + 0.5) / W * (2.0 * np.pi) - np.pi
+    y = np.pi / 2 - (torch.arange(H, device="cuda", dtype=torch.float32) + 0.5) / H * np.pi
+    theta, phi = x[None, :].expand(H, W), y[:, None].expand(H, W)
+    dirs = torch.stack([torch.cos(phi) * torch.sin(theta), torch.sin(phi), -torch.cos(phi) * torch.cos(theta)], dim=-1).reshape(-1, 3).contiguous()
+    origins = torch.tensor([0.0, 0.25, 0.0], device="cuda").expand(W * H, 3).contiguous()
+    rays = rt.make_rays(origins, dirs)
+    with variant(v):
+        img, _ = trace(scene, rays, 5)
+        pick = torch.from_numpy(np.random.default_rng(7).choice(W * H, 2000, replace=False)).cuda()
+        sample = rays[pick].contiguous()
+        got, _ = check(scene, desc, sample, 5, key="panorama", what="panorama sample")
+    assert_same(img[pick.cpu().numpy()], got, "panorama vs its sample")
+    hit = rt.Hits(rt.cast_rays(scene, rays)).hit.reshape(H, W).cpu().numpy()
+    lit = (img.reshape(H, W, 3) != 0.0).any(axis=2)
+    for q in range(4):
+        assert hit[:, q * W // 4:(q + 1) * W // 4].any() and lit[:, q * W // 4:(q + 1) * W // 4].any(), f"quarter {q}"
+
+
+# ---- 4. fallback and size paths ----
+
+def pwf_tiles_written(run, n):
+    """run() with the wavefront kernel's per-tile record switched on (rt_diag_set_tile_cost): how many of the batch's ceil(n / 64)
+    tiles it folded and wrote itself.  All of them: no arena overflowed and the trailing per-pixel launch had nothing to do"""
+    torch = _torch()
+    lib = _capi.amd_lib()
+    tiles = (n + 63) // 64
+    cost = torch.full((tiles,), -1, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    lib.rt_diag_set_tile_cost(C.c_void_p(cost.data_ptr()))
+    try:
+        run()
+        torch.cuda.synchronize()
+    finally:
+        lib.rt_diag_set_tile_cost(None)
+    return int((cost != -1).sum().item()), tiles
+
+
+def test_variant_18_renders_batches_in_the_wavefront_kernel(ref):
+    """the results of both kernels are the same, so parity alone cannot tell which one ran: the wavefront kernel must finish an
+    ordinary batch itself, every tile of it"""
+    world, desc, scene, cam, rays = ref
+    camera = rt.camera_rays(cam, rt.Frame.full(640, 360, 8))
+    with variant(18):
+        for name, batch, depth in (("random", rays, 8), ("camera", camera, 8)):
+            done, tiles = pwf_tiles_written(lambda: trace(scene, batch, depth), batch.shape[0])
+            assert done == tiles, f"{name}: the wavefront kernel finished {done} of {tiles} tiles"
+
+
+def test_batch_that_overflows_the_arenas_is_finished_by_the_per_pixel_kernel(ref):
+    """budget 1 on the 1080p camera rays: about 42 tiles per workgroup against arenas of 1 024 nodes, so the wavefront kernel gives up
+    on some tiles and the trailing per-pixel launch renders the batch — the image and the cast count are still the frame's"""
+    torch = _torch()
+    world, desc, scene, cam, _ = ref
+    frame = rt.Frame.full(1920, 1080, 8)
+    count = torch.zeros(1, dtype=torch.int64, device="cuda")
+    want = rt.render_whitted(scene, cam, frame, ray_count=count).cpu().numpy()
+    rays = rt.camera_rays(cam, frame)
+    with variant(18, 1):
+        result = {}
+        done, tiles = pwf_tiles_written(lambda: result.update(out=trace(scene, rays, 8)), rays.shape[0])
+    assert done < tiles, f"budget 1 should overflow the arenas ({done} of {tiles} tiles finished by the wavefront kernel)"
+    got, casts = result["out"]
+    assert_same(got + np.float32(0.0), want, "overflowed batch")
+    assert casts == int(count.item()) == HEADLINE_CASTS
+
+@pytest.mark.parametrize("budget", [1, 3])
+def test_small_budgets_on_a_small_batch(ref, budget):
+    """the smallest arenas (budgets below 4 waive the arena floor) on a batch of one tile per workgroup; the overflow itself is
+    test_batch_that_overflows_the_arenas_is_finished_by_the_per_pixel_kernel"""
+    world, desc, scene, cam, rays = ref
+    with variant(18, budget):
+        check(scene, desc, rays[:4096].contiguous(), 8, key="ref4096", what=f"budget {budget}")
+
+
+def test_no_memory_for_the_arenas(ref):
+    world, desc, _, cam, rays = ref
+    rt.set_option("RT_AMD_DIAG_WS_REFUSE", "1")
+    try:
+        check(rt.Scene(world), desc, rays[:4096].contiguous(), 8, key="ref4096", what="no arena memory")
+    finally:
+        rt.set_option("RT_AMD_DIAG_WS_REFUSE", None)
+
+
+def test_batch_split_into_ray_bands(ref):
+    """a large budget makes the arenas too small for the batch: several launches of whole 64-ray runs, the last one ragged"""
+    torch = _torch()
+    world, desc, scene, cam, _ = ref
+    frame = rt.Frame.full(317, 313, 5)  # 99 221 rays: not a multiple of 64
+    with variant(18, 2048):
+        count = torch.zeros(1, dtype=torch.int64, device="cuda")
+        want = rt.render_whitted(scene, cam, frame, ray_count=count)
+        got, casts = trace(scene, rt.camera_rays(cam, frame), frame.max_depth)
+    assert_same(got + np.float32(0.0), want.cpu().numpy(), "bands")
+    assert casts == int(count.item())
+
+
+@pytest.mark.parametrize("v", PATHS)
+@pytest.mark.parametrize("cap", [0, 96])
+def test_breadth_first_scene(tmp_path, cap, v):
+    world = _tessellated(tmp_path, 2, True)
+    desc = world.desc()
+    opts = {"RT_AMD_BFS_WALK_TRIANGLES": 1}
+    if cap:
+        opts["RT_AMD_DIAG_BFS_CAP"] = cap
+    with rt.options(**opts):
+        scene = rt.Scene(world)
+        centre, radius = bounds(desc)
+        with variant(v):
+            check(scene, desc, random_rays(51, 3000, desc, centre, radius), 5, key="bfs", what=f"bfs cap {cap}")
+
+
+# ---- 5. stream state ----
+
+def test_frames_and_batches_alternate_on_one_stream(ref):
+    torch = _torch()
+    world, desc, scene, cam, rays = ref
+    fa = rt.Frame.full(256, 160, 8)
+    wa, ca = _oracle.render_whitted(desc, cam, fa)
+    x = rays[:4099].contiguous()
+    y = rays[4099:8198].contiguous()  # same n, another buffer
+    wx, cx = oracle_trace(desc, x, 8, 1.0, key="x4099")
+    wy, cy = oracle_trace(desc, y, 8, 1.0, key="y4099")
+    stream = torch.cuda.Stream()
+    count = torch.zeros(1, dtype=torch.int64, device="cuda")
+    with torch.cuda.stream(stream):
+        for step, (kind, want, wcasts) in enumerate([("A", wa, ca), ("X", wx, cx), ("Y", wy, cy), ("A", wa, ca), ("Y", wy, cy)]):
+            count.zero_()
+            if kind == "A":
+                got = rt.render_whitted(scene, cam, fa, ray_count=count, stream=stream)
+            else:
+                got = rt.trace_rays(scene, x if kind == "X" else y, 8, ray_count=count, stream=stream)
+            stream.synchronize()
+            assert_same(got.cpu().numpy(), want, f"step {step} ({kind})")
+            assert int(count.item()) == wcasts, f"step {step} ({kind})"
+
+
+def test_two_streams_at_once(ref):
+    torch = _torch()
+    world, desc, scene, cam, rays = ref
+    x, y = rays[:4099].contiguous(), rays[4099:8198].contiguous()
+    sa, sb = torch.cuda.Stream(), torch.cuda.Stream()
+    torch.cuda.synchronize()
+    with torch.cuda.stream(sa):
+        ox = rt.trace_rays(scene, x, 8, stream=sa)
+    with torch.cuda.stream(sb):
+        oy = rt.trace_rays(scene, y, 8, stream=sb)
+    torch.cuda.synchronize()
+    assert_same(ox.cpu().numpy(), oracle_trace(desc, x, 8, 1.0, key="x4099")[0], "stream a")
+    assert_same(oy.cpu().numpy(), oracle_trace(desc, y, 8, 1.0, key="y4099")[0], "stream b")
+
+
+def test_captured_call_replays_on_new_rays(ref):
+    torch = _torch()
+    world, desc, scene, cam, _ = ref
+    centre, radius = bounds(desc)
+    rays = random_rays(61, 1000, desc, centre, radius)
+    fresh = random_rays(62, 1000, desc, centre, radius)
+    out = torch.empty((1000, 3), dtype=torch.float32, device="cuda")
+    count = torch.zeros(1, dtype=torch.int64, device="cuda")
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        rt.trace_rays(scene, rays, 5, out=out, stream=s)  # warm-up, uncaptured
+    s.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, stream=s):
+        rt.trace_rays(scene, rays, 5, out=out, ray_count=count, stream=torch.cuda.current_stream())
+    rays.copy_(fresh)
+    out.fill_(7.0)
+    count.zero_()
+    graph.replay()
+    torch.cuda.synchronize()
+    want, wcasts = oracle_trace(desc, fresh, 5, 1.0)
+    assert_same(out.cpu().numpy(), want, "replay")
+    assert int(count.item()) == wcasts
+
+
+def test_empty_batch_leaves_the_output_alone(ref):
+    torch = _torch()
+    world, desc, scene, cam, rays = ref
+    empty = torch.empty((0, 11), dtype=torch.int32, device="cuda")
+    assert tuple(rt.trace_rays(scene, empty, 5).shape) == (0, 3)
+    sentinel = torch.full((4, 3), 99.0, dtype=torch.float32, device="cuda")
+    lib = _capi.amd_lib()
+    assert lib.rt_trace_rays(scene._h, C.c_void_p(rays.data_ptr()), 0, 5, 1.0, C.c_void_p(sentinel.data_ptr()), None, None) == 0
+    torch.cuda.synchronize()
+    assert (sentinel.cpu().numpy() == 99.0).all()
+    # the host call on a small batch, for completeness
+    rgb, casts = rt.trace_rays_numpy(scene, rays[:64].cpu().numpy(), 5)
+    want, wcasts = oracle_trace(desc, rays[:64], 5, 1.0)
+    assert_same(rgb, want, "host call")
+    assert casts == wcasts
