@@ -10,6 +10,7 @@ reference's host-side names on top of them:
     render (the Whitted par_iter)  src/main.rs:1087-1104
     cast_rays (World::cast)        src/main.rs:180-326, on caller-supplied rays
     trace_rays (World::ray_trace)  src/main.rs:466-519, on caller-supplied rays
+    trace_rays_distributed         src/main.rs:521-614 (distributed_ray_trace), on caller-supplied rays
     post_process / write_to_file   src/main.rs:748-776
 
 PyTorch is used only for device memory, streams and torch.distributed.
@@ -27,7 +28,7 @@ from ._capi import Camera, Frame, Light, Material, RtError, SceneDesc, Sphere, T
 
 __all__ = [
     "World", "ObjectProxy", "Scene", "Camera", "Frame", "Material", "Light", "RtError", "reference_world",
-    "reference_camera", "render_whitted", "render_whitted_numpy", "make_rays", "cast_rays", "Hits", "camera_rays", "cast_rays_numpy", "trace_rays", "trace_rays_numpy", "Rng", "render_distributed", "render_distributed_numpy", "set_option", "options", "post_process_device", "encode_srgb8_device", "post_process", "encode_srgb8", "write_to_file",
+    "reference_camera", "render_whitted", "render_whitted_numpy", "make_rays", "cast_rays", "Hits", "camera_rays", "cast_rays_numpy", "trace_rays", "trace_rays_numpy", "Rng", "focus_rays", "trace_rays_distributed", "trace_rays_distributed_numpy", "render_distributed", "render_distributed_numpy", "set_option", "options", "post_process_device", "encode_srgb8_device", "post_process", "encode_srgb8", "write_to_file",
     "DEFAULT_OBJ",
 ]
 
@@ -378,14 +379,37 @@ class Rng:
 
     def __init__(self, frame: Frame):
         self.frame = frame
+        self.count = frame.rows * frame.cols
         self._h = C.c_void_p()
         _capi.check(_capi.amd_lib().rt_rng_create(C.byref(frame), C.byref(self._h)))
 
+    @classmethod
+    def seeded(cls, seeds) -> "Rng":
+        """Generators that belong to no frame (rt_rng_create_seeded): generator i is IsaacRng::new_from_u64(seeds[i]); ``seeds`` is a
+        sequence or array of integers below 2^64.  Rng(frame) is the case seeds[p] = y * 2^33 + x in the tile's row order."""
+        a = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64).reshape(-1))
+        self = cls.__new__(cls)
+        self.frame = None
+        self.count = int(a.shape[0])
+        self._h = C.c_void_p()
+        _capi.check(_capi.amd_lib().rt_rng_create_seeded(a.ctypes.data_as(C.c_void_p), self.count, C.byref(self._h)))
+        return self
+
     def download(self) -> np.ndarray:
         words = _capi.amd_lib().rt_rng_state_words()
-        st = np.empty((self.frame.rows * self.frame.cols, words), dtype=np.uint32)
+        st = np.empty((self.count, words), dtype=np.uint32)
         _capi.check(_capi.amd_lib().rt_rng_download(self._h, st.ctypes.data_as(C.c_void_p)))
         return st
+
+    def upload(self, states) -> None:
+        """The inverse of download (rt_rng_upload): (count, rt_rng_state_words) uint32 records in the reference's layout; the next call
+        continues exactly from them.  Synchronises."""
+        words = _capi.amd_lib().rt_rng_state_words()
+        a = np.asarray(states)
+        if not (a.dtype == np.uint32 and a.shape == (self.count, words)):
+            raise ValueError(f"expected a ({self.count}, {words}) uint32 array")
+        a = np.ascontiguousarray(a)
+        _capi.check(_capi.amd_lib().rt_rng_upload(self._h, a.ctypes.data_as(C.c_void_p)))
 
     def close(self) -> None:
         h, self._h = getattr(self, "_h", None), None
@@ -422,6 +446,69 @@ def render_distributed(scene: Scene, camera: Camera, frame: Frame, rng: Rng, n_e
                                               int(n_epochs), ptr(accum), ptr(samples), ptr(valid), ptr(ray_count), C.c_void_p(s.cuda_stream))
     )
     return accum if accum is not None else samples
+
+
+def focus_rays(camera: Camera, frame: Frame, rng: Rng, focus: float = 3.0, blur: float = 0.04, out=None, stream=None):
+    """Camera::shoot_focus (src/main.rs:101-127) of every pixel of a frame or tile as an (rows * cols, 11) int32 CUDA tensor of rt_ray
+    records in compact row order (rt_focus_rays): the two lens draws come from the pixel's generator in ``rng`` (the frame's Rng, or a
+    seeded one of as many generators), which advances — bit for bit the ray render_distributed casts first in that epoch."""
+    import torch
+
+    n = frame.rows * frame.cols
+    if out is None:
+        out = torch.empty((n, 11), dtype=torch.int32, device="cuda")
+    _records(out, 11, "out")
+    if out.shape[0] != n:
+        raise ValueError("out must have rows * cols records")
+    s = stream if stream is not None else torch.cuda.current_stream()
+    _capi.check(_capi.amd_lib().rt_focus_rays(C.byref(camera), C.byref(frame), float(focus), float(blur), rng._h, C.c_void_p(out.data_ptr()),
+                                              C.c_void_p(s.cuda_stream)))
+    return out
+
+
+def trace_rays_distributed(scene: Scene, rays, max_depth: int, rng: Rng, n_epochs: int = 1, accum=None, samples=None, valid=None,
+                           ray_count=None, stream=None):
+    """`n_epochs` samples of distributed_ray_trace (src/main.rs:521-614) per ray of an (N, 11) int32 CUDA tensor of rt_ray records, ray i
+    on generator i of ``rng`` (N generators: Rng.seeded, or a frame's Rng of N pixels), whose stream continues (rt_trace_rays_distributed).
+
+    accum   (N, 3) f32 CUDA tensor or None: the samples that pass the filter of main.rs:1157-1160 are added in epoch order.
+    samples (n_epochs, N, 3) f32 / valid (n_epochs, N) u8 CUDA tensors or None: raw samples + filter flags.
+    ray_count: a 1-element int64 CUDA tensor that the World::cast count is added to.  At least one of accum / samples.
+    """
+    import torch
+
+    def ptr(t):
+        return None if t is None else C.c_void_p(t.data_ptr())
+
+    _records(rays, 11, "rays")
+    n = rays.shape[0]
+    for t, shape, dt in ((accum, (n, 3), torch.float32), (samples, (n_epochs, n, 3), torch.float32), (valid, (n_epochs, n), torch.uint8)):
+        if t is not None and not (torch.is_tensor(t) and t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape):
+            raise ValueError(f"expected a contiguous CUDA {dt} tensor of shape {shape}")
+    if ray_count is not None and not (ray_count.is_cuda and ray_count.dtype == torch.int64 and ray_count.numel() == 1):
+        raise ValueError("ray_count must be a 1-element int64 CUDA tensor")
+    s = stream if stream is not None else torch.cuda.current_stream()
+    _capi.check(_capi.amd_lib().rt_trace_rays_distributed(scene._h, C.c_void_p(rays.data_ptr()), n, int(max_depth), rng._h, int(n_epochs),
+                                                          ptr(accum), ptr(samples), ptr(valid), ptr(ray_count), C.c_void_p(s.cuda_stream)))
+    return accum if accum is not None else samples
+
+
+def trace_rays_distributed_numpy(scene: Scene, rays_np, max_depth: int, rng: Rng, n_epochs: int, img: np.ndarray) -> int:
+    """Host-buffer convenience (rt_trace_rays_distributed_host, synchronous): rays as a RAY_DTYPE structured array or an (N, 11) array
+    of 4-byte words; `n_epochs` samples per ray are added into ``img`` ((N, 3) f32, in place).  Returns the cast count."""
+    a = np.asarray(rays_np)
+    if a.dtype == RAY_DTYPE:
+        a = np.ascontiguousarray(a).reshape(-1)
+    elif a.ndim == 2 and a.shape[1] == 11 and a.dtype.itemsize == 4:
+        a = np.ascontiguousarray(a).view(RAY_DTYPE).reshape(-1)
+    else:
+        raise ValueError("expected a RAY_DTYPE array or an (N, 11) array of 4-byte words")
+    if not (isinstance(img, np.ndarray) and img.dtype == np.float32 and img.flags.c_contiguous and img.shape == (a.shape[0], 3)):
+        raise ValueError("expected a contiguous (N, 3) float32 array")
+    casts = C.c_ulonglong(0)
+    _capi.check(_capi.amd_lib().rt_trace_rays_distributed_host(scene._h, a.ctypes.data_as(C.c_void_p), a.shape[0], int(max_depth), rng._h,
+                                                               int(n_epochs), img.ctypes.data_as(C.c_void_p), C.byref(casts)))
+    return int(casts.value)
 
 
 def render_distributed_numpy(scene: Scene, camera: Camera, frame: Frame, rng: Rng, n_epochs: int, img: np.ndarray,

@@ -1,7 +1,9 @@
 /*
  * rt_api_dist.hip — the depth-of-field pass behind the C ABI (main.rs:1117-1167): the per-pixel generators (rt_rng_*) and
  * rt_render_distributed — how many epochs make a batch, the workspace(s) a call runs through, and which stream each of a batch's
- * kernels (look-ahead, chain, shade, unwind; rt_distributed.hip) is put on.
+ * kernels (look-ahead, chain, shade, unwind; rt_distributed.hip) is put on.  The same pass on caller-supplied rays
+ * (rt_trace_rays_distributed: one body, render_distributed_frame, serves both), generators that belong to no frame
+ * (rt_rng_create_seeded, rt_rng_upload) and the lens as a ray source (rt_focus_rays).
  */
 #include "rt_api_internal.h"
 
@@ -83,23 +85,20 @@ struct rt_rng {
     uint32_t *d_pix;
     bool order_valid[2];
     hipStream_t main_stream; /* of the call in progress (for the after-chain hook) */
+    uint32_t *la_states;     /* ... and the records that call (or band of a ray batch) works on */
+    uint32_t la_count;
+    /* the tile the generators were seeded for (rt_rng_create); seeded ones (rt_rng_create_seeded) belong to no frame: one row of
+     * `cols` records with y_step 0, which no frame has (frame_ok) */
     uint32_t cols, rows, x0, y0, y_step;
 };
 
-int rt_rng_state_words(void) { return (int)RT_RNG_STATE_WORDS; }
+static size_t rng_count(const rt_rng *r) { return (size_t)r->cols * r->rows; }
 
-int rt_rng_create(const rt_frame *frame, rt_rng **out_rng) {
-    if (!out_rng) return fail(RT_ERR_INVALID_ARGUMENT, "rt_rng_create: null argument");
-    *out_rng = nullptr;
-    if (!frame_ok(frame)) return fail(RT_ERR_INVALID_ARGUMENT, "rt_rng_create: bad frame");
-    if (!frame_fits(frame)) return fail(RT_ERR_UNSUPPORTED, "rt_rng_create: tile of 2^32 pixels or more");
+static rt_rng *rng_new(uint32_t cols, uint32_t rows, uint32_t x0, uint32_t y0, uint32_t y_step) {
     rt_rng *r = new (std::nothrow) rt_rng();
-    if (!r) return fail(RT_ERR_OUT_OF_MEMORY, "rt_rng_create: host allocation failed");
-    r->cols = frame->x1 - frame->x0;
-    r->rows = rt_frame_rows(frame);
-    r->x0 = frame->x0;
-    r->y0 = frame->y0;
-    r->y_step = frame->y_step;
+    if (!r) return nullptr;
+    r->cols = cols; r->rows = rows; r->x0 = x0; r->y0 = y0; r->y_step = y_step;
+    r->device = -1;
     r->d_states = nullptr;
     r->d_list = nullptr;
     r->compute_units = 256;
@@ -111,22 +110,55 @@ int rt_rng_create(const rt_frame *frame, rt_rng **out_rng) {
     r->order_valid[0] = r->order_valid[1] = false;
     r->ahead = false;
     r->main_stream = nullptr;
-    const size_t bytes = (size_t)r->cols * r->rows * RT_RNG_DEVICE_WORDS * sizeof(uint32_t);
+    r->la_states = nullptr;
+    r->la_count = 0;
+    return r;
+}
+
+/* the records (unseeded), the scratch arrays, the streams and the events */
+static hipError_t rng_device_init(rt_rng *r) {
+    const size_t n = rng_count(r);
+    const size_t bytes = n * RT_RNG_DEVICE_WORDS * sizeof(uint32_t);
     hipError_t e = hipGetDevice(&r->device);
     if (e == hipSuccess) {
         int cus = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, r->device) == hipSuccess && cus > 0) r->compute_units = (uint32_t)cus;
     }
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&r->d_states), bytes);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&r->d_list), ((size_t)r->cols * r->rows + 1u) * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&r->d_pix), ((size_t)r->cols * r->rows * 3u + 512u) * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMemset(r->d_pix, 0, ((size_t)r->cols * r->rows * 3u + 512u) * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&r->d_list), (n + 1u) * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&r->d_pix), (n * 3u + 512u) * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemset(r->d_pix, 0, (n * 3u + 512u) * sizeof(uint32_t));
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&r->aux, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&r->ev_chain, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&r->ev_prepared, hipEventDisableTiming);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&r->tail, hipStreamNonBlocking); /* (at the lowest stream priority: no different, 1 226 against 1 229 Msamples/s) */
     if (e == hipSuccess) e = hipEventCreateWithFlags(&r->ev_tail[0], hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&r->ev_tail[1], hipEventDisableTiming);
+    return e;
+}
+
+static void rng_free(rt_rng *r) {
+    if (r->d_states) (void)hipFree(r->d_states);
+    if (r->d_list) (void)hipFree(r->d_list);
+    if (r->d_pix) (void)hipFree(r->d_pix);
+    if (r->ev_chain) (void)hipEventDestroy(r->ev_chain);
+    if (r->ev_prepared) (void)hipEventDestroy(r->ev_prepared);
+    if (r->aux) (void)hipStreamDestroy(r->aux);
+    for (int b = 0; b < 2; ++b) if (r->ev_tail[b]) (void)hipEventDestroy(r->ev_tail[b]);
+    if (r->tail) (void)hipStreamDestroy(r->tail);
+    delete r;
+}
+
+int rt_rng_state_words(void) { return (int)RT_RNG_STATE_WORDS; }
+
+int rt_rng_create(const rt_frame *frame, rt_rng **out_rng) {
+    if (!out_rng) return fail(RT_ERR_INVALID_ARGUMENT, "rt_rng_create: null argument");
+    *out_rng = nullptr;
+    if (!frame_ok(frame)) return fail(RT_ERR_INVALID_ARGUMENT, "rt_rng_create: bad frame");
+    if (!frame_fits(frame)) return fail(RT_ERR_UNSUPPORTED, "rt_rng_create: tile of 2^32 pixels or more");
+    rt_rng *r = rng_new(frame->x1 - frame->x0, rt_frame_rows(frame), frame->x0, frame->y0, frame->y_step);
+    if (!r) return fail(RT_ERR_OUT_OF_MEMORY, "rt_rng_create: host allocation failed");
+    hipError_t e = rng_device_init(r);
     if (e == hipSuccess) {
         rt::KernelFrame kf;
         memset(&kf, 0, sizeof kf);
@@ -135,16 +167,35 @@ int rt_rng_create(const rt_frame *frame, rt_rng **out_rng) {
     }
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) {
-        if (r->d_states) (void)hipFree(r->d_states);
-        if (r->d_list) (void)hipFree(r->d_list);
-        if (r->d_pix) (void)hipFree(r->d_pix);
-        if (r->ev_chain) (void)hipEventDestroy(r->ev_chain);
-        if (r->ev_prepared) (void)hipEventDestroy(r->ev_prepared);
-        if (r->aux) (void)hipStreamDestroy(r->aux);
-        for (int b = 0; b < 2; ++b) if (r->ev_tail[b]) (void)hipEventDestroy(r->ev_tail[b]);
-        if (r->tail) (void)hipStreamDestroy(r->tail);
-        delete r;
+        rng_free(r);
         return fail_hip("rt_rng_create", e);
+    }
+    *out_rng = r;
+    return RT_OK;
+}
+
+int rt_rng_create_seeded(const uint64_t *h_seeds, size_t n, rt_rng **out_rng) {
+    if ((uint64_t)n >= (1ull << 32)) return fail(RT_ERR_UNSUPPORTED, "rt_rng_create_seeded: 2^32 generators or more (checked first)");
+    if (!out_rng) return fail(RT_ERR_INVALID_ARGUMENT, "rt_rng_create_seeded: null argument");
+    *out_rng = nullptr;
+    if (n != 0 && !h_seeds) return fail(RT_ERR_INVALID_ARGUMENT, "rt_rng_create_seeded: null seed pointer");
+    rt_rng *r = rng_new((uint32_t)n, 1u, 0u, 0u, 0u);
+    if (!r) return fail(RT_ERR_OUT_OF_MEMORY, "rt_rng_create_seeded: host allocation failed");
+    if (n == 0) { /* a valid empty object: nothing on the device, nothing ever launched for it */
+        *out_rng = r;
+        return RT_OK;
+    }
+    static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "the seed kernel reads 64-bit words");
+    unsigned long long *d_seeds = nullptr;
+    hipError_t e = rng_device_init(r);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_seeds), n * sizeof(uint64_t));
+    if (e == hipSuccess) e = hipMemcpy(d_seeds, h_seeds, n * sizeof(uint64_t), hipMemcpyHostToDevice); /* the one upload */
+    if (e == hipSuccess) e = rt::launch_rng_seed_from(r->d_states, d_seeds, (uint32_t)n, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (d_seeds) (void)hipFree(d_seeds);
+    if (e != hipSuccess) {
+        rng_free(r);
+        return fail_hip("rt_rng_create_seeded", e);
     }
     *out_rng = r;
     return RT_OK;
@@ -183,6 +234,25 @@ int rt_rng_download(const rt_rng *rng, uint32_t *h_states) {
     return RT_OK;
 }
 
+int rt_rng_upload(rt_rng *rng, const uint32_t *h_states) {
+    if (!rng || !h_states) return fail(RT_ERR_INVALID_ARGUMENT, "rt_rng_upload: null argument");
+    const size_t bytes = rng_count(rng) * RT_RNG_STATE_WORDS * sizeof(uint32_t);
+    if (bytes == 0) return RT_OK;
+    RT_HIP(hipDeviceSynchronize()); /* whatever still reads or writes the records (a look-ahead on the aux stream) has finished */
+    uint32_t *d_tmp = nullptr;
+    RT_HIP(hipMalloc(reinterpret_cast<void **>(&d_tmp), bytes));
+    hipError_t e = hipMemcpy(d_tmp, h_states, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = rt::launch_rng_import(rng->d_states, (uint32_t)rng_count(rng), d_tmp, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    (void)hipFree(d_tmp);
+    if (e != hipSuccess) return fail_hip("rt_rng_upload", e);
+    /* every record now has its block in bank 0 and none prepared: the next call's look-ahead finds that out by itself once it is
+     * not told otherwise; and what the pixels cost under the old streams says nothing about the new ones */
+    rng->ahead = false;
+    rng->order_valid[0] = rng->order_valid[1] = false;
+    return RT_OK;
+}
+
 /* after the chain kernel of a batch: look-ahead for the next batch on the aux stream */
 static hipError_t lookahead_after_chain(void *ctx) {
     rt_rng *rng = static_cast<rt_rng *>(ctx);
@@ -191,45 +261,40 @@ static hipError_t lookahead_after_chain(void *ctx) {
     hipEvent_t pe[2];
     const bool prof = dist_profile_pairs(DK_PREPARE, 1, pe);
     if (e == hipSuccess && prof) e = hipEventRecord(pe[0], rng->aux);
-    if (e == hipSuccess) e = rt::launch_rng_prepare(rng->d_states, rng->cols * rng->rows, rng->d_list, rng->compute_units, rng->aux);
+    if (e == hipSuccess) e = rt::launch_rng_prepare(rng->la_states, rng->la_count, rng->d_list, rng->compute_units, rng->aux);
     if (e == hipSuccess && prof) e = hipEventRecord(pe[1], rng->aux);
     if (e == hipSuccess) e = hipEventRecord(rng->ev_prepared, rng->aux);
     if (e == hipSuccess) rng->ahead = true;
     return e;
 }
 
-int rt_render_distributed(const rt_scene *scene, const rt_camera *camera, const rt_frame *frame, float focus, float blur,
-                          rt_rng *rng, uint32_t n_epochs, float *d_accum, float *d_samples, unsigned char *d_valid,
-                          unsigned long long *d_ray_count, void *hip_stream) {
-    if (!scene || !rng) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_distributed: null argument");
-    if (!d_accum && !d_samples) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_distributed: need d_accum or d_samples");
-    rt::KernelFrame kf;
-    int rc = make_kernel_frame(camera, frame, &kf);
-    if (rc != RT_OK) return rc;
-    if (kf.cols != rng->cols || kf.rows != rng->rows || kf.x0 != rng->x0 || kf.y0 != rng->y0 || kf.y_step != rng->y_step)
-        return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_distributed: the RNG was created for a different tile");
-    rt::DistParams dp;
-    dp.rng_states = rng->d_states;
-    dp.n_epochs = n_epochs;
-    dp.focus = focus;
-    dp.blur = blur;
-    dp.accum = d_accum;
-    dp.samples = d_samples;
-    dp.valid = d_valid;
-    dp.ray_count = d_ray_count;
+} /* extern "C" */
+
+/* The pass behind rt_render_distributed and rt_trace_rays_distributed: kf is a camera frame (make_kernel_frame) or a band of a ray
+ * batch (one row of rays, rt_kernels.h frame_set_rays / frame_set_sample_stride); dp comes with what differs between the two — the
+ * band's generator records, n_epochs, focus and blur, the outputs — and `first` is the band's first generator within rng (0 for a
+ * frame).  Batches of epochs, the two workspaces in turn, the look-ahead on the aux stream, the fall to the one-kernel organisation,
+ * the profiling events and every RT_AMD_DIST_* switch; `who` names the entry point in error messages. */
+static int render_distributed_frame(const rt_scene *scene, const rt::KernelFrame &kf, rt_rng *rng, size_t first, rt::DistParams dp,
+                                    hipStream_t stream, const char *who) {
+    const uint32_t n_epochs = dp.n_epochs;
     dp.work_queue = nullptr;
     dp.pixel_order = nullptr;
     dp.pixel_cost = nullptr;
     dp.own_first_chunk = 0u;
     dp.bfs_scratch = nullptr;
     dp.bfs_items_cap = dp.bfs_jobs_cap = 0u;
-    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    dp.epoch0 = 0u;
+    const std::string launch_failed = std::string(who) + ": launch";
     uint32_t dist_waves = scene->resident_waves;
     int split = g_dist_split.load();
     if (split < 0) split = rt::option(rt::OPT_DIST_SPLIT, RT_DIST_SPLIT_DEFAULT) != 0 ? 1 : 0;
     if (scene->ks.bfs_walk != 0u) split = 0; /* a scene beyond the caches: the one-kernel organisation has the breadth-first walk (below) */
     const size_t n_pixels = (size_t)kf.cols * kf.rows;
     if (n_pixels == 0 || n_epochs == 0) return RT_OK;
+    const bool whole = first == 0 && n_pixels == rng_count(rng); /* not a band of a larger batch: the cost order covers what is launched */
+    rng->la_states = dp.rng_states;
+    rng->la_count = (uint32_t)n_pixels;
     /* the switches (rt_kernels.h RT_OPTIONS; rt_set_option or, once per process, the environment) */
     const bool lookahead = rt::option(rt::OPT_RNG_LOOKAHEAD, 1) != 0; /* 0 leaves every IsaacCore::generate to the render kernels */
     rt_scene *mut = const_cast<rt_scene *>(scene);
@@ -246,7 +311,7 @@ int rt_render_distributed(const rt_scene *scene, const rt_camera *camera, const 
         /* the chain kernel's pixels grouped by cost when a lane gets two of them at most (rt_kernels.h DistParams::pixel_order);
          * A/B: RT_AMD_DIST_BY_COST=0 never, =1 always */
         const bool small_share = (n_pixels + 63u) / 64u <= 2u * (size_t)rt::dist_chain_waves(dist_waves);
-        const bool by_cost = rt::option(rt::OPT_DIST_BY_COST, small_share ? 1 : 0) != 0;
+        const bool by_cost = whole && rt::option(rt::OPT_DIST_BY_COST, small_share ? 1 : 0) != 0;
         dp.own_first_chunk = rt::option(rt::OPT_DIST_OWN_FIRST, small_share ? 1 : 0) != 0 ? 1u : 0u; /* rt_kernels.h */
         const bool prep_first = rt::option(rt::OPT_DIST_PREP_FIRST, 1) != 0; /* 0: shade kernel and look-ahead start together */
         const size_t cap = (size_t)std::max<long long>(0, rt::option(rt::OPT_DIST_WS_MB, pipeline ? 32768 : 16384)) << 20;
@@ -328,7 +393,7 @@ int rt_render_distributed(const rt_scene *scene, const rt_camera *camera, const 
             if (e == hipSuccess && lookahead && !rng->ahead) {
                 const bool prof = dist_profile_pairs(DK_PREPARE, 1, pe);
                 if (prof) e = hipEventRecord(pe[0], stream);
-                if (e == hipSuccess) e = rt::launch_rng_prepare(rng->d_states, (uint32_t)n_pixels, rng->d_list, rng->compute_units, stream);
+                if (e == hipSuccess) e = rt::launch_rng_prepare(dp.rng_states, (uint32_t)n_pixels, rng->d_list, rng->compute_units, stream);
                 if (e == hipSuccess && prof) e = hipEventRecord(pe[1], stream);
             }
             rng->ahead = false; /* the chain kernel uses blocks up */
@@ -338,7 +403,7 @@ int rt_render_distributed(const rt_scene *scene, const rt_camera *camera, const 
             rng->main_stream = stream;
             /* the pixels in the order of what they cost in the batch that used this workspace last (two batches ago in a pipelined
              * call, the last one else): rt_kernels.h DistParams::pixel_order */
-            uint32_t *const pix_cost = rng->d_pix, *const pix_order = rng->d_pix + (size_t)(1u + b) * n_pixels, *const pix_scratch = rng->d_pix + 3u * n_pixels;
+            uint32_t *const pix_cost = rng->d_pix, *const pix_order = rng->d_pix + (size_t)(1u + b) * n_pixels, *const pix_scratch = rng->d_pix + 3u * n_pixels; /* (by_cost: the whole rng, so n_pixels is its count) */
             dp.pixel_cost = by_cost ? pix_cost : nullptr;
             dp.pixel_order = by_cost && rng->order_valid[b] ? pix_order : nullptr;
             if (e == hipSuccess && prof_chain) e = hipEventRecord(pe[2], stream);
@@ -373,7 +438,7 @@ int rt_render_distributed(const rt_scene *scene, const rt_camera *camera, const 
         /* everything the call started is behind the caller's stream again */
         for (uint32_t b = 0; b < 2u; ++b)
             if (tail_used[b]) { const hipError_t e2 = hipStreamWaitEvent(stream, rng->ev_tail[b], 0); if (e == hipSuccess) e = e2; }
-        if (e != hipSuccess) return fail_hip("rt_render_distributed: launch", e);
+        if (e != hipSuccess) return fail_hip(launch_failed.c_str(), e);
         return RT_OK;
     }
 one_kernel:
@@ -409,10 +474,149 @@ one_kernel:
         }
     }
     hipError_t e = hipMemsetAsync(dp.work_queue, 0, sizeof(uint32_t), stream);
-    if (e == hipSuccess && lookahead && !rng->ahead) e = rt::launch_rng_prepare(rng->d_states, (uint32_t)n_pixels, rng->d_list, rng->compute_units, stream);
+    if (e == hipSuccess && lookahead && !rng->ahead) e = rt::launch_rng_prepare(dp.rng_states, (uint32_t)n_pixels, rng->d_list, rng->compute_units, stream);
     rng->ahead = false;
     if (e == hipSuccess) e = rt::launch_distributed(scene->ks, kf, dp, dist_waves, stream);
-    if (e != hipSuccess) return fail_hip("rt_render_distributed: launch", e);
+    if (e != hipSuccess) return fail_hip(launch_failed.c_str(), e);
+    return RT_OK;
+}
+
+/* A ray batch runs in bands of at most this many rays per launch set, whole 64-ray chunks (as RT_TRACE_BAND_RAYS of rt_trace_rays):
+ * slot and sample indices inside a launch stay far from what 32 bits hold.  A band works on its own stretch of the generator
+ * records, the accumulator and the [epoch][ray] outputs. */
+#define RT_DIST_BAND_RAYS (1u << 26)
+
+static int trace_rays_distributed_checks(const char *who, const rt_scene *scene, const void *rays, size_t n_rays, int32_t max_depth,
+                                         const rt_rng *rng, uint32_t n_epochs, const void *accum, const void *samples, bool host, bool *nothing) {
+    const std::string w(who);
+    *nothing = false;
+    if ((uint64_t)n_rays >= (1ull << 32)) return fail(RT_ERR_UNSUPPORTED, w + ": 2^32 rays or more (checked first; trace them in several calls)");
+    if (!scene) return fail(RT_ERR_INVALID_ARGUMENT, w + ": null scene");
+    if (!rng) return fail(RT_ERR_INVALID_ARGUMENT, w + ": null rng");
+    if (n_rays != rng_count(rng)) return fail(RT_ERR_INVALID_ARGUMENT, w + ": the RNG holds a different number of generators than there are rays");
+    if (n_rays == 0 || n_epochs == 0) { *nothing = true; return RT_OK; }
+    if (!rays) return fail(RT_ERR_INVALID_ARGUMENT, w + ": null ray pointer");
+    if (host ? !accum : (!accum && !samples)) return fail(RT_ERR_INVALID_ARGUMENT, w + (host ? ": null accum pointer" : ": need d_accum or d_samples"));
+    if (max_depth > RT_MAX_DEPTH) return fail(RT_ERR_UNSUPPORTED, w + ": max_depth above RT_MAX_DEPTH");
+    return RT_OK;
+}
+
+extern "C" {
+
+int rt_render_distributed(const rt_scene *scene, const rt_camera *camera, const rt_frame *frame, float focus, float blur,
+                          rt_rng *rng, uint32_t n_epochs, float *d_accum, float *d_samples, unsigned char *d_valid,
+                          unsigned long long *d_ray_count, void *hip_stream) {
+    if (!scene || !rng) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_distributed: null argument");
+    if (!d_accum && !d_samples) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_distributed: need d_accum or d_samples");
+    rt::KernelFrame kf;
+    int rc = make_kernel_frame(camera, frame, &kf);
+    if (rc != RT_OK) return rc;
+    if (kf.cols != rng->cols || kf.rows != rng->rows || kf.x0 != rng->x0 || kf.y0 != rng->y0 || kf.y_step != rng->y_step)
+        return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_distributed: the RNG was created for a different tile");
+    rt::DistParams dp;
+    memset(&dp, 0, sizeof dp);
+    dp.rng_states = rng->d_states;
+    dp.n_epochs = n_epochs;
+    dp.focus = focus;
+    dp.blur = blur;
+    dp.accum = d_accum;
+    dp.samples = d_samples;
+    dp.valid = d_valid;
+    dp.ray_count = d_ray_count;
+    return render_distributed_frame(scene, kf, rng, 0, dp, static_cast<hipStream_t>(hip_stream), "rt_render_distributed");
+}
+
+int rt_trace_rays_distributed(const rt_scene *scene, const rt_ray *d_rays, size_t n_rays, int32_t max_depth, rt_rng *rng, uint32_t n_epochs,
+                              float *d_accum, float *d_samples, unsigned char *d_valid, unsigned long long *d_ray_count, void *hip_stream) {
+    bool nothing = false;
+    const int rc0 = trace_rays_distributed_checks("rt_trace_rays_distributed", scene, d_rays, n_rays, max_depth, rng, n_epochs, d_accum, d_samples, false, &nothing);
+    if (rc0 != RT_OK || nothing) return rc0;
+    /* max_depth < 0 renders as 0, as in rt_render_distributed (distributed_ray_trace tests `depth <= 0`, main.rs:524) */
+    const uint32_t n = (uint32_t)n_rays;
+    uint64_t band = RT_DIST_BAND_RAYS;
+    {
+        const long long hook = rt::option(rt::OPT_DIAG_DIST_BAND_RAYS, 0); /* test hook: shorter bands */
+        if (hook > 0 && (uint64_t)hook < band) band = ((uint64_t)hook + 63u) & ~(uint64_t)63u;
+    }
+    const bool ahead0 = rng->ahead; /* the records of the bands still to come are as the call found them */
+    for (uint64_t u0 = 0; u0 < n; u0 += band) {
+        const uint32_t len = (uint32_t)std::min<uint64_t>(band, n - u0);
+        rt::KernelFrame kf;
+        memset(&kf, 0, sizeof kf);
+        kf.cols = len;
+        kf.rows = 1u;
+        kf.max_depth = max_depth;
+        rt::frame_set_rays(&kf, d_rays + u0, 0.0f);
+        rt::frame_set_sample_stride(&kf, n);
+        rt::DistParams dp;
+        memset(&dp, 0, sizeof dp);
+        dp.rng_states = rng->d_states + (size_t)u0 * RT_RNG_DEVICE_WORDS;
+        dp.n_epochs = n_epochs;
+        dp.accum = d_accum ? d_accum + (size_t)u0 * 3u : nullptr;
+        dp.samples = d_samples ? d_samples + (size_t)u0 * 3u : nullptr;
+        dp.valid = d_valid ? d_valid + (size_t)u0 : nullptr;
+        dp.ray_count = d_ray_count;
+        rng->ahead = ahead0;
+        const int rc = render_distributed_frame(scene, kf, rng, (size_t)u0, dp, static_cast<hipStream_t>(hip_stream), "rt_trace_rays_distributed");
+        if (rc != RT_OK) { rng->ahead = false; return rc; }
+    }
+    return RT_OK;
+}
+
+int rt_trace_rays_distributed_host(const rt_scene *scene, const rt_ray *h_rays, size_t n_rays, int32_t max_depth, rt_rng *rng, uint32_t n_epochs,
+                                   float *h_accum, unsigned long long *h_ray_count) {
+    bool nothing = false;
+    const int rc0 = trace_rays_distributed_checks("rt_trace_rays_distributed_host", scene, h_rays, n_rays, max_depth, rng, n_epochs, h_accum, nullptr, true, &nothing);
+    if (rc0 != RT_OK) return rc0;
+    if (nothing) {
+        if (h_ray_count) *h_ray_count = 0;
+        return RT_OK;
+    }
+    const size_t bytes = n_rays * 3 * sizeof(float);
+    rt_ray *d_rays = nullptr;
+    float *d_accum = nullptr;
+    unsigned long long *d_cnt = nullptr;
+    RT_HIP(hipMalloc(reinterpret_cast<void **>(&d_rays), n_rays * sizeof(rt_ray)));
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(&d_accum), bytes);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_cnt), sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemset(d_cnt, 0, sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemcpy(d_rays, h_rays, n_rays * sizeof(rt_ray), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_accum, h_accum, bytes, hipMemcpyHostToDevice); /* continues from the caller's sums */
+    int rc = RT_OK;
+    if (e == hipSuccess) {
+        rc = rt_trace_rays_distributed(scene, d_rays, n_rays, max_depth, rng, n_epochs, d_accum, nullptr, nullptr, d_cnt, nullptr);
+        if (rc == RT_OK) {
+            e = hipDeviceSynchronize();
+            if (e == hipSuccess) e = hipMemcpy(h_accum, d_accum, bytes, hipMemcpyDeviceToHost);
+            unsigned long long cnt = 0;
+            if (e == hipSuccess) e = hipMemcpy(&cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost);
+            if (e == hipSuccess && h_ray_count) *h_ray_count = cnt;
+        }
+    }
+    (void)hipFree(d_rays);
+    if (d_accum) (void)hipFree(d_accum);
+    if (d_cnt) (void)hipFree(d_cnt);
+    if (rc != RT_OK) return rc;
+    if (e != hipSuccess) return fail_hip("rt_trace_rays_distributed_host", e);
+    return RT_OK;
+}
+
+int rt_focus_rays(const rt_camera *camera, const rt_frame *frame, float focus, float blur, rt_rng *rng, rt_ray *d_rays, void *hip_stream) {
+    if (!camera || !frame || !rng) return fail(RT_ERR_INVALID_ARGUMENT, "rt_focus_rays: null argument");
+    if (!frame_ok(frame)) return fail(RT_ERR_INVALID_ARGUMENT, "rt_focus_rays: bad frame (need 0 <= x0 < x1 <= width, 0 <= y0 < y1 <= height, y_step >= 1)");
+    if (!d_rays) return fail(RT_ERR_INVALID_ARGUMENT, "rt_focus_rays: null ray pointer");
+    rt_frame f = *frame;
+    f.max_depth = 0; /* not used here */
+    rt::KernelFrame kf;
+    const int rc = make_kernel_frame(camera, &f, &kf); /* refuses a tile of 2^32 pixels or more */
+    if (rc != RT_OK) return rc;
+    const bool same_tile = kf.cols == rng->cols && kf.rows == rng->rows && kf.x0 == rng->x0 && kf.y0 == rng->y0 && kf.y_step == rng->y_step;
+    const bool seeded_same_count = rng->y_step == 0u && (size_t)kf.cols * kf.rows == rng_count(rng);
+    if (!same_tile && !seeded_same_count)
+        return fail(RT_ERR_INVALID_ARGUMENT, "rt_focus_rays: the RNG was created for a different tile (or, seeded, holds a different number of generators)");
+    const hipError_t e = rt::launch_focus_rays(kf, focus, blur, rng->d_states, d_rays, static_cast<hipStream_t>(hip_stream));
+    if (e != hipSuccess) return fail_hip("rt_focus_rays: launch", e);
+    rng->ahead = false; /* a generator may have moved on to its prepared block: the next call looks */
     return RT_OK;
 }
 

@@ -293,6 +293,9 @@ __device__ __forceinline__ void standard_normal_x2(Rng &r, double *n0, double *n
     *n1 = standard_normal(r);
 }
 
+/* RT_DIST_RAYS_TU: this file is compiled once more by rt_distributed_rays.hip, which takes the device functions and the two kernel
+ * templates (for their RAYS = true instantiations) and none of the plain kernels and launchers between the guards */
+#ifndef RT_DIST_RAYS_TU
 __global__ __launch_bounds__(256) void rng_seed_kernel(uint32_t *states, uint32_t cols, uint32_t rows, uint32_t x0, uint32_t y0, uint32_t y_step) {
     const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= cols * rows) return;
@@ -432,6 +435,7 @@ hipError_t launch_rng_export(const uint32_t *states, uint32_t n_pixels, uint32_t
     hipLaunchKernelGGL(rng_export_kernel, dim3(4096), dim3(256), 0, stream, states, n_pixels, out);
     return hipGetLastError();
 }
+#endif /* RT_DIST_RAYS_TU */
 
 /* ---- the kernel ------------------------------------------------------------------------------- */
 
@@ -457,7 +461,11 @@ struct DFrame {
 /* BFS: the casts as a breadth-first walk of the node tree (rt_cast_bfs.h cast_bfs), for scenes beyond the caches (KernelScene::bfs_walk):
  * 256 VGPRs, two waves per SIMD, 5 KB of LDS and a set of record lists per wave */
 #define RT_DIST_BFS_WAVES 2
-template <int MAXD, bool BFS = false>
+/* RAYS: the roots are a ray batch's (rt_trace_rays_distributed; rt_kernels.h frame_is_rays): slot i of the one-row frame is ray i,
+ * start_epoch reads its rt_ray record instead of shooting through the lens — no draws, no clip coordinates — and samples / flags
+ * are indexed with the call's ray count (frame_sample_stride), which a band of a larger batch does not have as its own.
+ * Instantiated in rt_distributed_rays.hip. */
+template <int MAXD, bool BFS = false, bool RAYS = false>
 __global__ __launch_bounds__(64, BFS ? RT_DIST_BFS_WAVES : RT_DIST_MIN_WAVES) void distributed_kernel(const KernelScene sc, const KernelFrame fr, const DistParams dp) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
@@ -495,7 +503,7 @@ __global__ __launch_bounds__(64, BFS ? RT_DIST_BFS_WAVES : RT_DIST_MIN_WAVES) vo
     const V3 cam_y = v3(fr.cam_y[0], fr.cam_y[1], fr.cam_y[2]);
     const V3 cam_t = v3(fr.cam_toward[0], fr.cam_toward[1], fr.cam_toward[2]);
     const V3 cam_o = v3(fr.cam_origin_focus[0], fr.cam_origin_focus[1], fr.cam_origin_focus[2]);
-    const size_t n_pixels = total_slots;
+    const size_t n_pixels = RAYS ? (size_t)frame_sample_stride(fr) : (size_t)total_slots;
 
     Rng rng;
     rng.rec = rng.st = dp.rng_states;
@@ -532,6 +540,12 @@ __global__ __launch_bounds__(64, BFS ? RT_DIST_BFS_WAVES : RT_DIST_MIN_WAVES) vo
 
     /* Camera::shoot_focus for the next epoch of this pixel (main.rs:101-127) */
     auto start_epoch = [&]() {
+        if constexpr (RAYS) { /* the caller's ray, the same in every epoch */
+            req = ray_from_abi(frame_rays(fr) + out_index, sc.n_triangles, sc.n_spheres);
+            sp = 0;
+            phase = DP_PRIMARY;
+            return;
+        }
         const V3 direction = normalize(clip_x * cam_x + clip_y * cam_y + cam_t);
         const float xoffset = (float)(0.0 + (double)dp.blur * standard_normal(rng)); /* Normal::new(0.0, blur as f64) */
         const float yoffset = (float)(0.0 + (double)dp.blur * standard_normal(rng));
@@ -563,6 +577,9 @@ __global__ __launch_bounds__(64, BFS ? RT_DIST_BFS_WAVES : RT_DIST_MIN_WAVES) vo
             if (phase == DP_DONE && rank < avail) {
                 /* same slot -> pixel mapping as the Whitted kernel: 8-row bands, column-major inside a band */
                 const uint32_t slot = q_next + rank;
+                if constexpr (RAYS) {
+                    out_index = slot;
+                } else {
                 const uint32_t band = slot / band_slots;
                 const uint32_t r = slot - band * band_slots;
                 const uint32_t rows_left = fr.rows - (band << 3);
@@ -573,6 +590,7 @@ __global__ __launch_bounds__(64, BFS ? RT_DIST_BFS_WAVES : RT_DIST_MIN_WAVES) vo
                 const uint32_t x = fr.x0 + col, y = fr.y0 + row * fr.y_step;
                 clip_y = (fr.half_height - (float)y) / fr.height_f; /* main.rs:1134-1135 */
                 clip_x = ((float)x - fr.half_width) / fr.height_f;
+                }
                 rng_open(rng, dp.rng_states + (size_t)out_index * RNG_WORDS);
                 accum = v3(0.0f, 0.0f, 0.0f);
                 if (dp.accum != nullptr) accum = v3(dp.accum[(size_t)out_index * 3u], dp.accum[(size_t)out_index * 3u + 1u], dp.accum[(size_t)out_index * 3u + 2u]);
@@ -852,24 +870,31 @@ __global__ __launch_bounds__(64, BFS ? RT_DIST_BFS_WAVES : RT_DIST_MIN_WAVES) vo
     }
 }
 
-hipError_t launch_distributed(const KernelScene &sc, const KernelFrame &fr, const DistParams &dp, uint32_t resident_waves, hipStream_t stream) {
+template <bool RAYS>
+static hipError_t launch_distributed_of(const KernelScene &sc, const KernelFrame &fr, const DistParams &dp, uint32_t resident_waves, hipStream_t stream) {
     const uint32_t total = fr.cols * fr.rows;
     uint32_t waves = (total + 63u) / 64u;
     if (waves == 0u) return hipSuccess;
     if (dp.work_queue != nullptr && waves > resident_waves) waves = resident_waves; /* persistent lanes: fill the chip once */
     if (sc.bfs_walk != 0u && dp.bfs_scratch != nullptr && dp.work_queue != nullptr) { /* (the caller sized resident_waves by dist_bfs_waves) */
-        if (fr.max_depth <= 8) hipLaunchKernelGGL((distributed_kernel<9, true>), dim3(waves), dim3(64), 0, stream, sc, fr, dp);
-        else hipLaunchKernelGGL((distributed_kernel<RT_MAX_DEPTH + 1, true>), dim3(waves), dim3(64), 0, stream, sc, fr, dp);
+        if (fr.max_depth <= 8) hipLaunchKernelGGL((distributed_kernel<9, true, RAYS>), dim3(waves), dim3(64), 0, stream, sc, fr, dp);
+        else hipLaunchKernelGGL((distributed_kernel<RT_MAX_DEPTH + 1, true, RAYS>), dim3(waves), dim3(64), 0, stream, sc, fr, dp);
         return hipGetLastError();
     }
     if (fr.max_depth <= 8) {
-        hipLaunchKernelGGL((distributed_kernel<9>), dim3(waves), dim3(64), 0, stream, sc, fr, dp);
+        hipLaunchKernelGGL((distributed_kernel<9, false, RAYS>), dim3(waves), dim3(64), 0, stream, sc, fr, dp);
     } else {
-        hipLaunchKernelGGL((distributed_kernel<RT_MAX_DEPTH + 1>), dim3(waves), dim3(64), 0, stream, sc, fr, dp);
+        hipLaunchKernelGGL((distributed_kernel<RT_MAX_DEPTH + 1, false, RAYS>), dim3(waves), dim3(64), 0, stream, sc, fr, dp);
     }
     return hipGetLastError();
 }
+#ifndef RT_DIST_RAYS_TU
+hipError_t launch_distributed(const KernelScene &sc, const KernelFrame &fr, const DistParams &dp, uint32_t resident_waves, hipStream_t stream) {
+    if (frame_is_rays(fr)) return launch_distributed_rays(sc, fr, dp, resident_waves, stream); /* rt_distributed_rays.hip */
+    return launch_distributed_of<false>(sc, fr, dp, resident_waves, stream);
+}
 uint32_t dist_bfs_waves(uint32_t compute_units) { return compute_units * 4u * (uint32_t)RT_DIST_BFS_WAVES; }
+#endif /* RT_DIST_RAYS_TU */
 
 
 /* ---- the split pass ----------------------------------------------------------------------------------------------
@@ -900,7 +925,8 @@ uint32_t dist_bfs_waves(uint32_t compute_units) { return compute_units * 4u * (u
 __device__ __forceinline__ uint32_t dfu(float x) { return __float_as_uint(x); }
 __device__ __forceinline__ float duf(uint32_t x) { return __uint_as_float(x); }
 
-template <int DUMMY>
+/* RAYS: as in distributed_kernel — the batch's rays are the roots (instantiated in rt_distributed_rays.hip) */
+template <int DUMMY, bool RAYS = false>
 __global__ __launch_bounds__(64, RT_DIST_CHAIN_MIN_WAVES) void dist_chain_kernel(const KernelScene sc, const KernelFrame fr, const DistParams dp) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t total_slots = fr.cols * fr.rows;
@@ -956,6 +982,12 @@ __global__ __launch_bounds__(64, RT_DIST_CHAIN_MIN_WAVES) void dist_chain_kernel
     int32_t retry = 0;
 
     auto start_epoch = [&]() { /* Camera::shoot_focus (main.rs:101-127) */
+        if constexpr (RAYS) { /* the caller's ray, the same in every epoch */
+            req = ray_from_abi(frame_rays(fr) + out_index, sc.n_triangles, sc.n_spheres);
+            sp = 0;
+            phase = DP_PRIMARY;
+            return;
+        }
         const V3 direction = normalize(clip_x * cam_x + clip_y * cam_y + cam_t);
         double nx, ny;
         standard_normal_x2(rng, &nx, &ny);
@@ -1004,8 +1036,10 @@ __global__ __launch_bounds__(64, RT_DIST_CHAIN_MIN_WAVES) void dist_chain_kernel
             const uint32_t avail = q_end - q_next;
             if (phase == DP_DONE && rank < avail) {
                 const uint32_t slot = q_next + rank;
-                uint32_t row, col;
-                if (DUMMY != 0) { /* instantiation 1: the pixels grouped by cost (rt_kernels.h); its own, so that instantiation 0 does not carry it */
+                uint32_t row = 0u, col = 0u;
+                if constexpr (RAYS) { /* one row: slot i is ray i */
+                    out_index = DUMMY != 0 ? dp.pixel_order[slot] : slot;
+                } else if (DUMMY != 0) { /* instantiation 1: the pixels grouped by cost (rt_kernels.h); its own, so that instantiation 0 does not carry it */
                     out_index = dp.pixel_order[slot];
                     row = out_index / fr.cols;
                     col = out_index - row * fr.cols;
@@ -1018,9 +1052,11 @@ __global__ __launch_bounds__(64, RT_DIST_CHAIN_MIN_WAVES) void dist_chain_kernel
                     row = (band << 3) + (r - col * band_rows);
                     out_index = row * fr.cols + col;
                 }
-                const uint32_t x = fr.x0 + col, y = fr.y0 + row * fr.y_step;
-                clip_y = (fr.half_height - (float)y) / fr.height_f;
-                clip_x = ((float)x - fr.half_width) / fr.height_f;
+                if constexpr (!RAYS) {
+                    const uint32_t x = fr.x0 + col, y = fr.y0 + row * fr.y_step;
+                    clip_y = (fr.half_height - (float)y) / fr.height_f;
+                    clip_x = ((float)x - fr.half_width) / fr.height_f;
+                }
                 rng_open(rng, dp.rng_states + (size_t)out_index * RNG_WORDS);
                 epoch = 0u;
                 phase = DP_START;
@@ -1082,6 +1118,7 @@ __global__ __launch_bounds__(64, RT_DIST_CHAIN_MIN_WAVES) void dist_chain_kernel
  * coherent chunks, the organisation of the Whitted path.  It lost to the persistent lanes above twice: 2.35 against 2.28 ms per epoch
  * in round 2, 1 015 against 1 136 Msamples/s in round 3 with the pair-wise cast in both (profiles/README.md), and is gone.) */
 
+#ifndef RT_DIST_RAYS_TU
 /* get_shade (main.rs:407-464) for every request of the batch.  The request arrays are sparse — slot k of a sample is in
  * use only if its chain got that far (90 % at slot 0, a few per cent at slot 8) — so a workgroup first lists the live
  * (slot, sample) pairs of its `tile` samples in LDS and its waves then work through the list 64 at a time with
@@ -1349,16 +1386,24 @@ size_t distributed_split_bytes_per_sample(int32_t max_depth) {
 uint32_t dist_chain_waves(uint32_t resident_waves) {
     return resident_waves / 3u * (uint32_t)RT_DIST_CHAIN_MIN_WAVES; /* resident_waves is sized for 3 per SIMD */
 }
+#endif /* RT_DIST_RAYS_TU */
 
-hipError_t launch_dist_chain(const KernelScene &sc, const KernelFrame &fr, const DistParams &dp, uint32_t resident_waves, hipStream_t stream) {
+template <bool RAYS>
+static hipError_t launch_dist_chain_of(const KernelScene &sc, const KernelFrame &fr, const DistParams &dp, uint32_t resident_waves, hipStream_t stream) {
     const uint32_t total = fr.cols * fr.rows;
     if (total == 0u || dp.n_epochs == 0u) return hipSuccess;
     uint32_t waves = (total + 63u) / 64u;
     const uint32_t chain_waves = dist_chain_waves(resident_waves);
     if (waves > chain_waves) waves = chain_waves;
-    if (dp.pixel_order != nullptr) hipLaunchKernelGGL((dist_chain_kernel<1>), dim3(waves), dim3(64), 0, stream, sc, fr, dp);
-    else hipLaunchKernelGGL((dist_chain_kernel<0>), dim3(waves), dim3(64), 0, stream, sc, fr, dp);
+    if (dp.pixel_order != nullptr) hipLaunchKernelGGL((dist_chain_kernel<1, RAYS>), dim3(waves), dim3(64), 0, stream, sc, fr, dp);
+    else hipLaunchKernelGGL((dist_chain_kernel<0, RAYS>), dim3(waves), dim3(64), 0, stream, sc, fr, dp);
     return hipGetLastError();
+}
+
+#ifndef RT_DIST_RAYS_TU
+hipError_t launch_dist_chain(const KernelScene &sc, const KernelFrame &fr, const DistParams &dp, uint32_t resident_waves, hipStream_t stream) {
+    if (frame_is_rays(fr)) return launch_dist_chain_rays(sc, fr, dp, resident_waves, stream); /* rt_distributed_rays.hip */
+    return launch_dist_chain_of<false>(sc, fr, dp, resident_waves, stream);
 }
 
 /* ... and what only reads its records: the shade kernel and the unwind */
@@ -1380,12 +1425,17 @@ hipError_t launch_dist_shade_unwind(const KernelScene &sc, const KernelFrame &fr
     if (ev != nullptr) { (void)hipEventRecord(ev[1], stream); (void)hipEventRecord(ev[2], stream); }
     size_t blocks = ((size_t)total + 255u) / 256u;
     if (blocks > 4096u) blocks = 4096u;
-    hipLaunchKernelGGL(dist_unwind_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, dp, (size_t)total, (size_t)total);
+    /* samples and flags are indexed with the CALL's count: a band of a ray batch is a part of it (frame_sample_stride) */
+    hipLaunchKernelGGL(dist_unwind_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, dp, (size_t)total,
+                       frame_is_rays(fr) ? (size_t)frame_sample_stride(fr) : (size_t)total);
     if (ev != nullptr) (void)hipEventRecord(ev[3], stream);
     return hipGetLastError();
 }
 
+#endif /* RT_DIST_RAYS_TU */
+
 } /* namespace rt */
+#ifndef RT_DIST_RAYS_TU
 #ifdef RT_DIAG_NEED
 RT_DIAG_NEED_READER(rt_diag_read_need_dist)
 #endif
@@ -1434,3 +1484,4 @@ extern "C" int rt_diag_prepare_time(uint32_t n_records, uint32_t reps, uint32_t 
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 #endif
+#endif /* RT_DIST_RAYS_TU */

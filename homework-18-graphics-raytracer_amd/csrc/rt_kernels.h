@@ -100,6 +100,11 @@ __device__ __forceinline__ const rt_ray *frame_rays(const F &fr) {
 }
 template <class F>
 __host__ __device__ __forceinline__ float frame_root_contribution(const F &fr) { return fr.cam_origin[2]; }
+/* The stochastic pass on a ray batch (rt_trace_rays_distributed) describes a band the same way — one row, y_step 0, the band's first
+ * record in cam_origin[0] / [1] — and x0, which a row of rays has no use for, carries the CALL's ray count: its samples and flags
+ * are laid out [epoch][ray of the call], and the band's pointers start at the band's first ray. */
+inline void frame_set_sample_stride(KernelFrame *fr, uint32_t call_rays) { fr->x0 = call_rays; }
+__host__ __device__ __forceinline__ uint32_t frame_sample_stride(const KernelFrame &fr) { return fr.x0; }
 
 /* what a launch of the per-pixel kernel is told besides the scene and the frame */
 struct KernelQueues {
@@ -123,6 +128,7 @@ struct KernelQueues {
     X(OPT_BFS_WALK_TRIANGLES, "RT_AMD_BFS_WALK_TRIANGLES") /* scenes of at least this many triangles are walked breadth-first by the wavefront kernel (0: never); read by rt_scene_create */ \
     X(OPT_WF_SHARE, "RT_AMD_WF_SHARE")                     /* n > 1: a launch of the persistent wavefront kernel takes 1/n of the workgroups the device holds — a caller with n frames in flight on n streams runs them side by side instead of one behind the other's tail */ \
     X(OPT_DIAG_BFS_CAP, "RT_AMD_DIAG_BFS_CAP")             /* test hook: that walk's record lists hold this many records at most (default: RT_BFS_ITEMS_CAP / RT_BFS_JOBS_CAP): a wave-cast that needs more takes the wave-uniform walk */ \
+    X(OPT_DIAG_DIST_BAND_RAYS, "RT_AMD_DIAG_DIST_BAND_RAYS") /* test hook: rt_trace_rays_distributed launches at most this many rays at a time, rounded up to whole 64-ray chunks (default: 2^26) */ \
     X(OPT_QUERY_WAVE_UNIFORM, "RT_AMD_QUERY_WAVE_UNIFORM") /* 1: rt_cast_rays sends every wave through cast_asm (the wave-uniform walk) instead of cast_pairs / cast_bfs */
 #define RT_OPTION_ID(id, name) id,
 enum Option : int { RT_OPTIONS(RT_OPTION_ID) OPT_COUNT };
@@ -224,6 +230,16 @@ hipError_t launch_rng_seed(uint32_t *states, const KernelFrame &fr, hipStream_t 
 /* look-ahead: generate the next block of every pixel that has none prepared; list = n_pixels + 1 words of scratch */
 hipError_t launch_rng_prepare(uint32_t *states, uint32_t n_pixels, uint32_t *list, uint32_t compute_units, hipStream_t stream);
 hipError_t launch_rng_export(const uint32_t *states, uint32_t n_pixels, uint32_t *out, hipStream_t stream);
+/* rt_distributed_rays.hip: generators that belong to no frame — record i seeded with seeds[i] (device memory); the inverse of
+ * launch_rng_export (records in the reference's layout -> bank 0 of the device records, nothing prepared); and Camera::shoot_focus of
+ * every pixel of a frame in compact row order, drawing from the pixel's record */
+hipError_t launch_rng_seed_from(uint32_t *states, const unsigned long long *seeds, uint32_t n, hipStream_t stream);
+hipError_t launch_rng_import(uint32_t *states, uint32_t n, const uint32_t *in, hipStream_t stream);
+hipError_t launch_focus_rays(const KernelFrame &fr, float focus, float blur, uint32_t *states, rt_ray *rays, hipStream_t stream);
+/* the launches of distributed_kernel<MAXD, BFS, true> and dist_chain_kernel<ORDER, true> for a ray batch (rt_distributed_rays.hip;
+ * called by launch_distributed / launch_dist_chain when frame_is_rays) */
+hipError_t launch_distributed_rays(const KernelScene &sc, const KernelFrame &fr, const DistParams &dp, uint32_t resident_waves, hipStream_t stream);
+hipError_t launch_dist_chain_rays(const KernelScene &sc, const KernelFrame &fr, const DistParams &dp, uint32_t resident_waves, hipStream_t stream);
 hipError_t launch_distributed(const KernelScene &sc, const KernelFrame &fr, const DistParams &dp, uint32_t resident_waves, hipStream_t stream);
 uint32_t dist_bfs_waves(uint32_t compute_units); /* the grid of launch_distributed, at most, when dp.bfs_scratch is set: one list set per wave */
 /* the split pass, one batch of dp.n_epochs epochs: the chain kernel (all random draws; dp.work_queue zeroed), and — once it has

@@ -270,7 +270,7 @@ int rt_camera_rays(const rt_camera *camera, const rt_frame *frame, rt_ray *d_ray
  * one uncaptured call on that stream.  rt_profile_enable / rt_profile_read bracket its render kernel(s) as rt_render_whitted's.
  * Speed depends on the ORDER of the rays: the kernels cast 64 consecutive rays per wave, wave-uniformly, so rays that travel
  * together should be neighbours (rt_camera_rays' row order makes 64x1 strips; an 8x8-tile order is what rt_render_whitted uses;
- * DESIGN.md §3.8).  Not covered: the depth-of-field pass, per-ray cast counts. */
+ * DESIGN.md §3.8).  The stochastic integrator on caller rays is rt_trace_rays_distributed, below.  Not covered: per-ray cast counts. */
 int rt_trace_rays(const rt_scene *scene, const rt_ray *d_rays, size_t n_rays, int32_t max_depth, float contribution,
                   float *d_rgb, unsigned long long *d_ray_count, void *hip_stream);
 /* Same, with host buffers: allocates, launches, copies back and synchronises.  *h_ray_count is overwritten with the cast count
@@ -294,6 +294,18 @@ int rt_rng_create(const rt_frame *frame, rt_rng **out_rng);
 int rt_rng_destroy(rt_rng *rng);
 /* Copy the states to the host (rt_frame_pixels * rt_rng_state_words u32) — for tests. */
 int rt_rng_download(const rt_rng *rng, uint32_t *h_states);
+/* Generators that belong to no frame: n of them, generator i = IsaacRng::new_from_u64(h_seeds[i]) (host memory, uploaded once; the
+ * seeding runs on the device).  rt_rng_create(frame) is the special case h_seeds[p] = y * 2^33 + x in the tile's row order
+ * (main.rs:1119).  n >= 2^32 is RT_ERR_UNSUPPORTED (checked first); n == 0 gives a valid empty object, made without a device.
+ * An rt_rng made either way serves wherever its count matches: a seeded one of n generators rt_trace_rays_distributed on n rays
+ * and rt_focus_rays on a tile of n pixels; a frame's one the same, its generators in the tile's row order.  rt_render_distributed
+ * alone wants the tile the generators were created for: a seeded rt_rng has none and is refused (RT_ERR_INVALID_ARGUMENT). */
+int rt_rng_create_seeded(const uint64_t *h_seeds, size_t n, rt_rng **out_rng);
+/* The inverse of rt_rng_download: rt_rng_state_words() u32 per generator in the reference's record layout (mem[256], a, b, c,
+ * results[256], index), host memory.  The next render call continues exactly from those records (the device's second bank and the
+ * look-ahead start afresh; so does the grouping of the pixels by cost, which only orders work).  Synchronises the device, as
+ * rt_rng_download does.  Download + upload checkpoint and restore the streams. */
+int rt_rng_upload(rt_rng *rng, const uint32_t *h_states);
 
 /* n_epochs passes over the tile.  Per pixel and epoch: shoot_focus(focus, blur) (main.rs:1144-1149,
  * reference literals 3.0 / 0.04) -> cast -> distributed_ray_trace(depth = max_depth).
@@ -315,6 +327,47 @@ int rt_render_distributed(const rt_scene *scene, const rt_camera *camera, const 
  * World::cast count of this call (may be NULL).  Synchronises. */
 int rt_render_distributed_host(const rt_scene *scene, const rt_camera *camera, const rt_frame *frame, float focus, float blur,
                                rt_rng *rng, uint32_t n_epochs, float *h_accum, unsigned long long *h_ray_count);
+
+/* ---- stochastic radiance queries: distributed_ray_trace on caller-supplied rays ------------------------------
+
+ * The body of the closure at main.rs:1150-1155 with the caller's ray in place of shoot_focus's — per ray i and epoch e, in epoch
+ * order, on generator i of rng:
+ *     sample = match world.cast(&d_rays[i]) { Some(hit) => distributed_ray_trace(state { depth: max_depth, rng_i }, &hit), None => black }
+ * (distributed_ray_trace: src/main.rs:521-614) — the stochastic scatter pass for a camera or lens model the library does not have,
+ * a list of chosen pixels to resample, the secondary rays of the caller's own integrator.  Bit for bit the reference's samples,
+ * flags, generator records and cast counts.
+ *   d_rays       n_rays rt_ray records (device), read exactly as rt_cast_rays and rt_trace_rays read them: a face value above 2 is
+ *                Both, an exclusion whose index is outside its array excludes nothing, the direction is used as given.  The ray is
+ *                the same in every epoch; a fresh lens sample per epoch is rt_focus_rays + this call with n_epochs = 1.
+ *   max_depth    as rt_frame.max_depth: negative renders like 0, above RT_MAX_DEPTH is RT_ERR_UNSUPPORTED.
+ *   rng          n_rays generators (rt_rng_create_seeded, or a frame's of rt_frame_pixels == n_rays); generator i serves ray i and
+ *                its stream continues from epoch to epoch and from call to call.
+ *   d_accum      n_rays*3 floats or NULL; d_samples n_epochs*n_rays*3 floats or NULL, indexed [epoch][ray]; d_valid n_epochs*n_rays
+ *                bytes or NULL; d_ray_count one u64 or NULL: all as in rt_render_distributed — the filter of main.rs:1157-1160 applies
+ *                and surviving samples are ADDED to d_accum in epoch order.  Every epoch casts (and counts) its primary ray; a miss is
+ *                black, which the filter rejects (0.0 is not is_normal), as in the reference.
+ * Checked before any device work, in this order: n_rays >= 2^32 is RT_ERR_UNSUPPORTED; a null scene, then a null rng,
+ * RT_ERR_INVALID_ARGUMENT; n_rays different from the rng's count RT_ERR_INVALID_ARGUMENT; n_rays == 0 or n_epochs == 0 is RT_OK and
+ * launches nothing; a null ray pointer RT_ERR_INVALID_ARGUMENT; neither d_accum nor d_samples RT_ERR_INVALID_ARGUMENT; then max_depth.
+ * The launcher is rt_render_distributed's: both organisations (rt_set_distributed_split) with the same bits, batches of epochs, the
+ * two workspaces, the look-ahead, rt_profile_read_distributed and every RT_AMD_DIST_* switch; a batch of more than 2^26 rays runs
+ * in bands of whole 64-ray chunks.  Stream-ordered and asynchronous on hip_stream as rt_render_distributed is.  Graph capture is
+ * supported by neither of the two: a call forks onto streams the rt_rng owns, keeps host-side look-ahead state per call and may
+ * allocate its workspace.  A wave takes 64 consecutive rays: rays that travel together should be neighbours. */
+int rt_trace_rays_distributed(const rt_scene *scene, const rt_ray *d_rays, size_t n_rays, int32_t max_depth, rt_rng *rng, uint32_t n_epochs,
+                              float *d_accum, float *d_samples, unsigned char *d_valid, unsigned long long *d_ray_count, void *hip_stream);
+/* Same, with host rays and a host image: h_accum (n_rays*3 floats, required) is uploaded, added to as above and copied back;
+ * *h_ray_count is overwritten with the cast count of this call (may be NULL).  Synchronises.  Without a device it fails with a
+ * status and writes nothing. */
+int rt_trace_rays_distributed_host(const rt_scene *scene, const rt_ray *h_rays, size_t n_rays, int32_t max_depth, rt_rng *rng,
+                                   uint32_t n_epochs, float *h_accum, unsigned long long *h_ray_count);
+/* The library's lens as a ray source: for every pixel of the tile, in compact row order as rt_camera_rays, d_rays[p] =
+ * Camera::shoot_focus(clip(x, y), state, focus, blur) (main.rs:101-127), the two Normal(0, blur) values drawn from that pixel's
+ * generator, which advances.  rng: the frame's, or a seeded one of rt_frame_pixels generators.  Face Front, no exclusion; the ray is
+ * bit for bit the one rt_render_distributed casts first, so one rt_focus_rays + rt_trace_rays_distributed(n_epochs = 1) IS one epoch
+ * of rt_render_distributed — and the caller may transform, reorder, subset or replace the rays in between.  frame->max_depth is
+ * not used.  Stream-ordered on hip_stream. */
+int rt_focus_rays(const rt_camera *camera, const rt_frame *frame, float focus, float blur, rt_rng *rng, rt_ray *d_rays, void *hip_stream);
 
 /* ---- several GPUs from one process (SURVEY §8e without Python or MPI) -------------------
  * Image rows are interleaved over the entries of `devices` exactly as homework-18-graphics-raytracer_amd/dist.py interleaves
@@ -400,7 +453,7 @@ int rt_accumulator_resolve_device(const float *d_sum, const float *d_weight, siz
  * named like the environment variable that seeds it — RT_AMD_DIST_PIPELINE, RT_AMD_DIST_WS_MB, RT_AMD_RNG_LOOKAHEAD,
  * RT_AMD_DIST_BY_COST, RT_AMD_DIST_OWN_FIRST, RT_AMD_DIST_PREP_FIRST, RT_AMD_DIST_SPLIT, RT_AMD_DIAG_WS_REFUSE,
  * RT_AMD_MULTI_FORCE_STAGE, RT_AMD_BFS_WALK_TRIANGLES (read by rt_scene_create), RT_AMD_WF_SHARE, RT_AMD_DIAG_BFS_CAP,
- * RT_AMD_QUERY_WAVE_UNIFORM (INTEGRATION.md says what each does); any other name is RT_ERR_INVALID_ARGUMENT.  The environment is read ONCE per process, at the first use;
+ * RT_AMD_DIAG_DIST_BAND_RAYS, RT_AMD_QUERY_WAVE_UNIFORM (INTEGRATION.md says what each does); any other name is RT_ERR_INVALID_ARGUMENT.  The environment is read ONCE per process, at the first use;
  * after that only this call changes a switch: value = decimal integer, NULL or "" = unset (the library's own choice).  Render
  * calls read the switches without locks: set them between calls, not during one. */
 int rt_set_option(const char *name, const char *value);
