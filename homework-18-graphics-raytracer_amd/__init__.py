@@ -11,6 +11,7 @@ reference's host-side names on top of them:
     cast_rays (World::cast)        src/main.rs:180-326, on caller-supplied rays
     trace_rays (World::ray_trace)  src/main.rs:466-519, on caller-supplied rays
     trace_rays_distributed         src/main.rs:521-614 (distributed_ray_trace), on caller-supplied rays
+    shade_hits / reflect_rays / refract_rays   src/main.rs:407-464, 328-341, 343-405 (get_shade, get_reflect, get_refract), on caller-supplied hits
     post_process / write_to_file   src/main.rs:748-776
 
 PyTorch is used only for device memory, streams and torch.distributed.
@@ -28,7 +29,7 @@ from ._capi import Camera, Frame, Light, Material, RtError, SceneDesc, Sphere, T
 
 __all__ = [
     "World", "ObjectProxy", "Scene", "Camera", "Frame", "Material", "Light", "RtError", "reference_world",
-    "reference_camera", "render_whitted", "render_whitted_numpy", "make_rays", "cast_rays", "Hits", "camera_rays", "cast_rays_numpy", "trace_rays", "trace_rays_numpy", "Rng", "focus_rays", "trace_rays_distributed", "trace_rays_distributed_numpy", "render_distributed", "render_distributed_numpy", "set_option", "options", "post_process_device", "encode_srgb8_device", "post_process", "encode_srgb8", "write_to_file",
+    "reference_camera", "render_whitted", "render_whitted_numpy", "make_rays", "cast_rays", "Hits", "camera_rays", "cast_rays_numpy", "trace_rays", "trace_rays_numpy", "shade_hits", "reflect_rays", "refract_rays", "Refractions", "ESCAPED", "INFINITE", "TRAPPED", "HIT_NONE", "shade_hits_numpy", "refract_rays_numpy", "Rng", "focus_rays", "trace_rays_distributed", "trace_rays_distributed_numpy", "render_distributed", "render_distributed_numpy", "set_option", "options", "post_process_device", "encode_srgb8_device", "post_process", "encode_srgb8", "write_to_file",
     "DEFAULT_OBJ",
 ]
 
@@ -372,6 +373,142 @@ def trace_rays_numpy(scene: Scene, rays_np, max_depth: int, contribution: float 
     _capi.check(_capi.amd_lib().rt_trace_rays_host(scene._h, a.ctypes.data_as(C.c_void_p), a.shape[0], int(max_depth), float(contribution),
                                                    rgb.ctypes.data_as(C.c_void_p), C.byref(casts)))
     return rgb, int(casts.value)
+
+
+# ---- hit queries: get_shade / get_reflect / get_refract on caller-supplied hits (include/rt_amd.h rt_shade_hits) ----
+
+ESCAPED, INFINITE, TRAPPED = 0, 1, 2  # Refraction, main.rs:149-158 (HIT_NONE: the record was no hit)
+
+
+def _hit_records(hits):
+    records = hits.records if isinstance(hits, Hits) else hits
+    _records(records, 13, "hits")
+    return records
+
+
+def _hits_and_rays(hits, rays):
+    records = _hit_records(hits)
+    _records(rays, 11, "rays")
+    if rays.shape[0] != records.shape[0]:
+        raise ValueError("hits and rays must have one record each per hit: rays[i] is the ray that produced hits[i]")
+    return records, records.shape[0]
+
+
+def _count_ptr(ray_count):
+    if ray_count is None:
+        return None
+    import torch
+
+    if not (torch.is_tensor(ray_count) and ray_count.is_cuda and ray_count.dtype == torch.int64 and ray_count.numel() == 1):
+        raise ValueError("ray_count must be a 1-element int64 CUDA tensor")
+    return C.c_void_p(ray_count.data_ptr())
+
+
+def shade_hits(scene: Scene, hits, rays, out=None, ray_count=None, stream=None):
+    """get_shade (src/main.rs:407-464) for every hit: ``hits`` is a Hits or its (N, 13) int32 CUDA record tensor (what cast_rays
+    returns), ``rays`` the (N, 11) rt_ray records that produced them (Hit.ray).  Returns ``out``, an (N, 3) float32 CUDA tensor
+    (allocated if None) with get_shade's value bit for bit; a record that is no hit gives black.  ``ray_count``: a 1-element int64 CUDA
+    tensor that the shadow casts are added to.  Stream-ordered on ``stream`` (default: torch's current stream)."""
+    import torch
+
+    records, n = _hits_and_rays(hits, rays)
+    if out is None:
+        out = torch.empty((n, 3), dtype=torch.float32, device=records.device)
+    if not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (n, 3)):
+        raise ValueError("out must be a contiguous (N, 3) float32 CUDA tensor")
+    s = stream if stream is not None else torch.cuda.current_stream()
+    _capi.check(_capi.amd_lib().rt_shade_hits(scene._h, C.c_void_p(records.data_ptr()), C.c_void_p(rays.data_ptr()), n,
+                                              C.c_void_p(out.data_ptr()), _count_ptr(ray_count), C.c_void_p(s.cuda_stream)))
+    return out
+
+
+def reflect_rays(hits, rays, out=None, stream=None):
+    """get_reflect (src/main.rs:328-341) for every hit: returns ``out``, an (N, 11) int32 CUDA tensor of rt_ray records (allocated if
+    None) that cast_rays / trace_rays take as they are; a record that is no hit gives an all-zero ray.  Needs no scene."""
+    import torch
+
+    records, n = _hits_and_rays(hits, rays)
+    if out is None:
+        out = torch.empty((n, 11), dtype=torch.int32, device=records.device)
+    _records(out, 11, "out")
+    if out.shape[0] != n:
+        raise ValueError("out must have one record per hit")
+    s = stream if stream is not None else torch.cuda.current_stream()
+    _capi.check(_capi.amd_lib().rt_reflect_rays(C.c_void_p(records.data_ptr()), C.c_void_p(rays.data_ptr()), n, C.c_void_p(out.data_ptr()),
+                                                C.c_void_p(s.cuda_stream)))
+    return out
+
+
+class Refractions:
+    """What refract_rays returns: ``kind`` (N,) int32 — ESCAPED, INFINITE, TRAPPED, or HIT_NONE for a record that was no hit —,
+    ``travel`` (N,) float32 (travel_distance where escaped, else 0) and ``rays`` (N, 11) int32 rt_ray records (escape_ray where
+    escaped, else zero words)."""
+
+    def __init__(self, kind, travel, rays):
+        self.kind, self.travel, self.rays = kind, travel, rays
+
+    @property
+    def escaped(self):
+        """bool mask: Refraction::Escaped."""
+        return self.kind == ESCAPED
+
+    def __len__(self):
+        return self.kind.shape[0]
+
+
+def refract_rays(scene: Scene, hits, rays, max_distance: float = 100.0, ray_count=None, stream=None) -> Refractions:
+    """get_refract (src/main.rs:343-405) for every hit, the walk through the glass: 1 to 11 casts each.  Returns a Refractions;
+    ``ray_count``: a 1-element int64 CUDA tensor that those casts are added to."""
+    import torch
+
+    records, n = _hits_and_rays(hits, rays)
+    kind = torch.empty((n,), dtype=torch.int32, device=records.device)
+    travel = torch.empty((n,), dtype=torch.float32, device=records.device)
+    escape = torch.empty((n, 11), dtype=torch.int32, device=records.device)
+    s = stream if stream is not None else torch.cuda.current_stream()
+    _capi.check(_capi.amd_lib().rt_refract_rays(scene._h, C.c_void_p(records.data_ptr()), C.c_void_p(rays.data_ptr()), n, float(max_distance),
+                                                C.c_void_p(kind.data_ptr()), C.c_void_p(travel.data_ptr()), C.c_void_p(escape.data_ptr()),
+                                                _count_ptr(ray_count), C.c_void_p(s.cuda_stream)))
+    return Refractions(kind, travel, escape)
+
+
+def _host_records(a, dtype, words, name):
+    a = np.asarray(a)
+    if a.dtype == dtype:
+        return np.ascontiguousarray(a).reshape(-1)
+    if a.ndim == 2 and a.shape[1] == words and a.dtype.itemsize == 4:
+        return np.ascontiguousarray(a).view(dtype).reshape(-1)
+    raise ValueError(f"{name}: expected a {'HIT' if words == 13 else 'RAY'}_DTYPE array or an (N, {words}) array of 4-byte words")
+
+
+def shade_hits_numpy(scene: Scene, hits_np, rays_np):
+    """Host-buffer convenience (rt_shade_hits_host, synchronous): hits as a HIT_DTYPE array or (N, 13) 4-byte words, rays as a RAY_DTYPE
+    array or (N, 11) words; returns (rgb[N, 3] float32, shadow casts)."""
+    h, r = _host_records(hits_np, HIT_DTYPE, 13, "hits"), _host_records(rays_np, RAY_DTYPE, 11, "rays")
+    if h.shape[0] != r.shape[0]:
+        raise ValueError("hits and rays must have one record each per hit")
+    rgb = np.zeros((h.shape[0], 3), dtype=np.float32)
+    casts = C.c_ulonglong(0)
+    _capi.check(_capi.amd_lib().rt_shade_hits_host(scene._h, h.ctypes.data_as(C.c_void_p), r.ctypes.data_as(C.c_void_p), h.shape[0],
+                                                   rgb.ctypes.data_as(C.c_void_p), C.byref(casts)))
+    return rgb, int(casts.value)
+
+
+def refract_rays_numpy(scene: Scene, hits_np, rays_np, max_distance: float = 100.0):
+    """Host-buffer convenience (rt_refract_rays_host, synchronous): returns (kind[N] int32, travel[N] float32, escape rays as a
+    RAY_DTYPE array, casts)."""
+    h, r = _host_records(hits_np, HIT_DTYPE, 13, "hits"), _host_records(rays_np, RAY_DTYPE, 11, "rays")
+    if h.shape[0] != r.shape[0]:
+        raise ValueError("hits and rays must have one record each per hit")
+    n = h.shape[0]
+    kind = np.zeros(n, dtype=np.int32)
+    travel = np.zeros(n, dtype=np.float32)
+    escape = np.zeros(n, dtype=RAY_DTYPE)
+    casts = C.c_ulonglong(0)
+    _capi.check(_capi.amd_lib().rt_refract_rays_host(scene._h, h.ctypes.data_as(C.c_void_p), r.ctypes.data_as(C.c_void_p), n, float(max_distance),
+                                                     kind.ctypes.data_as(C.c_void_p), travel.ctypes.data_as(C.c_void_p),
+                                                     escape.ctypes.data_as(C.c_void_p), C.byref(casts)))
+    return kind, travel, escape, int(casts.value)
 
 
 class Rng:

@@ -164,6 +164,7 @@ AMD_SYMBOLS = [
     "rt_rng_destroy", "rt_rng_download", "rt_render_distributed", "rt_render_distributed_host", "rt_multi_create", "rt_multi_destroy", "rt_multi_render_whitted_host", "rt_multi_render_distributed_host", "rt_multi_render_whitted", "rt_multi_render_distributed", "rt_post_process_device", "rt_post_keys_device", "rt_post_hist_device", "rt_post_pick_device", "rt_post_scale_device", "rt_post_release", "rt_encode_srgb8_device", "rt_accumulate_device", "rt_accumulator_resolve_device",
     "rt_cast_rays", "rt_cast_rays_host", "rt_camera_rays", "rt_trace_rays", "rt_trace_rays_host",
     "rt_rng_create_seeded", "rt_rng_upload", "rt_trace_rays_distributed", "rt_trace_rays_distributed_host", "rt_focus_rays",
+    "rt_shade_hits", "rt_reflect_rays", "rt_refract_rays", "rt_shade_hits_host", "rt_refract_rays_host",
 ]
 HOST_SYMBOLS = [
     "rt_world_new", "rt_world_free", "rt_world_push_object", "rt_world_push_triangle", "rt_world_push_sphere",
@@ -285,6 +286,13 @@ def amd_lib() -> C.CDLL:
         lib.rt_trace_rays_distributed_host.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p, C.c_uint32, C.c_void_p,
                                                        C.POINTER(C.c_ulonglong)]
         lib.rt_focus_rays.argtypes = [C.POINTER(Camera), C.POINTER(Frame), C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.rt_shade_hits.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.rt_reflect_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        lib.rt_refract_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p]
+        lib.rt_shade_hits_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_ulonglong)]
+        lib.rt_refract_rays_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.POINTER(C.c_ulonglong)]
         lib.rt_scene_describe_nodes.argtypes = [C.POINTER(SceneDesc), C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32)]
         _amd = lib
     return _amd

@@ -8,6 +8,7 @@
  *   rt_api_dist.hip    rt_rng_* and rt_render_distributed: batches, the two workspaces, the streams of a pipelined call
  *   rt_api_multi.hip   rt_multi_*: a device list from one process
  *   rt_api_post.hip    post_process / sRGB / accumulator / rt_math_eval entry points
+ *   rt_api_query.hip   rt_cast_rays / rt_camera_rays and the hit queries rt_shade_hits / rt_reflect_rays / rt_refract_rays
  */
 #ifndef RT_API_INTERNAL_H
 #define RT_API_INTERNAL_H
@@ -115,5 +116,17 @@ struct SceneLayout {
     double scene_extent = 0.0;
 };
 RT_API_HIDDEN int layout_scene(const rt_scene_desc *desc, SceneLayout &layout);
+
+/* The hit queries' kernels (rt_hit_query.hip): get_shade / get_refract / get_reflect on n ABI records, in bands of at most
+ * band_records per launch (a multiple of 64, RT_HITQ_BAND at most).  wave_uniform: the casts go through cast_asm instead of cast_pairs
+ * (same bits). */
+#define RT_HITQ_BAND (1u << 26)
+namespace rt {
+hipError_t launch_shade_hits(const KernelScene &sc, const rt_hit *hits, const rt_ray *incoming, uint32_t n, float *rgb,
+                             unsigned long long *ray_count, bool wave_uniform, uint32_t band_records, hipStream_t stream);
+hipError_t launch_refract_rays(const KernelScene &sc, const rt_hit *hits, const rt_ray *incoming, uint32_t n, float max_distance, uint32_t *kind,
+                               float *travel, rt_ray *escape, unsigned long long *ray_count, bool wave_uniform, uint32_t band_records, hipStream_t stream);
+hipError_t launch_reflect_rays(const rt_hit *hits, const rt_ray *incoming, uint32_t n, rt_ray *out, uint32_t band_records, hipStream_t stream);
+} /* namespace rt */
 
 #endif /* RT_API_INTERNAL_H */

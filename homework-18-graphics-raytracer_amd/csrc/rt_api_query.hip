@@ -1,7 +1,8 @@
 /*
  * rt_api_query.hip — rt_cast_rays / rt_cast_rays_host / rt_camera_rays (include/rt_amd.h "ray queries"): validation, the
- * per-(scene, stream) workspace of a scene walked breadth-first, the launches of rt_query.hip.  No CPU path: without a device
- * every call fails with a status.
+ * per-(scene, stream) workspace of a scene walked breadth-first, the launches of rt_query.hip; and rt_shade_hits / rt_reflect_rays /
+ * rt_refract_rays with their _host forms ("hit queries"): validation and the launches of rt_hit_query.hip, no workspace.  No CPU
+ * path: without a device every call fails with a status.
  */
 #include "rt_api_internal.h"
 
@@ -97,6 +98,138 @@ int rt_camera_rays(const rt_camera *camera, const rt_frame *frame, rt_ray *d_ray
     if (rc != RT_OK) return rc;
     const hipError_t e = rt::launch_camera_rays(kf, d_rays, static_cast<hipStream_t>(hip_stream));
     if (e != hipSuccess) return fail_hip("rt_camera_rays: launch", e);
+    return RT_OK;
+}
+
+/* ---- hit queries (rt_hit_query.hip) ---- */
+
+/* the checks every hit query makes before any device work, in the documented order; *done: nothing to launch */
+static int hit_query_args(const char *who, bool needs_scene, const void *scene, size_t n, bool pointers_ok, const char *pointers, bool *done) {
+    *done = true;
+    if ((uint64_t)n >= (1ull << 32)) return fail(RT_ERR_UNSUPPORTED, std::string(who) + ": 2^32 records or more (checked first; query them in several calls)");
+    if (needs_scene && !scene) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": null scene");
+    if (n == 0) return RT_OK;
+    if (!pointers_ok) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": null " + pointers + " pointer");
+    *done = false;
+    return RT_OK;
+}
+
+/* records per launch: RT_HITQ_BAND, or what the test hook asks for, in whole 64-record chunks */
+static uint32_t hit_query_band() {
+    const long long hook = rt::option(rt::OPT_DIAG_HIT_BAND_RECORDS, 0);
+    if (hook > 0 && hook < (long long)RT_HITQ_BAND) return (uint32_t)((hook + 63) & ~63ll);
+    return RT_HITQ_BAND;
+}
+
+int rt_shade_hits(const rt_scene *scene, const rt_hit *d_hits, const rt_ray *d_incoming, size_t n, float *d_rgb, unsigned long long *d_ray_count,
+                  void *hip_stream) {
+    bool done;
+    const int rc = hit_query_args("rt_shade_hits", true, scene, n, d_hits && d_incoming && d_rgb, "hit, incoming-ray or rgb", &done);
+    if (rc != RT_OK || done) return rc;
+    const bool wave_uniform = rt::option(rt::OPT_QUERY_WAVE_UNIFORM, 0) == 1;
+    const hipError_t e = rt::launch_shade_hits(scene->ks, d_hits, d_incoming, (uint32_t)n, d_rgb, d_ray_count, wave_uniform, hit_query_band(),
+                                               static_cast<hipStream_t>(hip_stream));
+    if (e != hipSuccess) return fail_hip("rt_shade_hits: launch", e);
+    return RT_OK;
+}
+
+int rt_reflect_rays(const rt_hit *d_hits, const rt_ray *d_incoming, size_t n, rt_ray *d_out, void *hip_stream) {
+    bool done;
+    const int rc = hit_query_args("rt_reflect_rays", false, nullptr, n, d_hits && d_incoming && d_out, "hit, incoming-ray or output", &done);
+    if (rc != RT_OK || done) return rc;
+    const hipError_t e = rt::launch_reflect_rays(d_hits, d_incoming, (uint32_t)n, d_out, hit_query_band(), static_cast<hipStream_t>(hip_stream));
+    if (e != hipSuccess) return fail_hip("rt_reflect_rays: launch", e);
+    return RT_OK;
+}
+
+int rt_refract_rays(const rt_scene *scene, const rt_hit *d_hits, const rt_ray *d_incoming, size_t n, float max_distance, uint32_t *d_kind,
+                    float *d_travel, rt_ray *d_escape, unsigned long long *d_ray_count, void *hip_stream) {
+    bool done;
+    const int rc = hit_query_args("rt_refract_rays", true, scene, n, d_hits && d_incoming && d_kind && d_escape, "hit, incoming-ray, kind or escape-ray", &done);
+    if (rc != RT_OK || done) return rc;
+    const bool wave_uniform = rt::option(rt::OPT_QUERY_WAVE_UNIFORM, 0) == 1;
+    const hipError_t e = rt::launch_refract_rays(scene->ks, d_hits, d_incoming, (uint32_t)n, max_distance, d_kind, d_travel, d_escape, d_ray_count,
+                                                 wave_uniform, hit_query_band(), static_cast<hipStream_t>(hip_stream));
+    if (e != hipSuccess) return fail_hip("rt_refract_rays: launch", e);
+    return RT_OK;
+}
+
+/* device copies of the two inputs and a zeroed counter, shared by the _host forms; everything is freed by the destructor */
+namespace {
+struct HitQueryBuffers {
+    rt_hit *d_hits = nullptr;
+    rt_ray *d_incoming = nullptr;
+    unsigned long long *d_cnt = nullptr;
+    std::vector<void *> outs;
+    ~HitQueryBuffers() {
+        if (d_hits) (void)hipFree(d_hits);
+        if (d_incoming) (void)hipFree(d_incoming);
+        if (d_cnt) (void)hipFree(d_cnt);
+        for (void *p : outs) if (p) (void)hipFree(p);
+    }
+    hipError_t upload(const rt_hit *h_hits, const rt_ray *h_incoming, size_t n) {
+        hipError_t e = hipMalloc(reinterpret_cast<void **>(&d_hits), n * sizeof(rt_hit));
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_incoming), n * sizeof(rt_ray));
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_cnt), sizeof(unsigned long long));
+        if (e == hipSuccess) e = hipMemset(d_cnt, 0, sizeof(unsigned long long));
+        if (e == hipSuccess) e = hipMemcpy(d_hits, h_hits, n * sizeof(rt_hit), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(d_incoming, h_incoming, n * sizeof(rt_ray), hipMemcpyHostToDevice);
+        return e;
+    }
+    hipError_t out(void **p, size_t bytes) {
+        const hipError_t e = hipMalloc(p, bytes);
+        if (e == hipSuccess) outs.push_back(*p);
+        return e;
+    }
+};
+} /* namespace */
+
+int rt_shade_hits_host(const rt_scene *scene, const rt_hit *h_hits, const rt_ray *h_incoming, size_t n, float *h_rgb, unsigned long long *h_ray_count) {
+    bool done;
+    int rc = hit_query_args("rt_shade_hits_host", true, scene, n, h_hits && h_incoming && h_rgb, "hit, incoming-ray or rgb", &done);
+    if (rc == RT_OK && done && h_ray_count) *h_ray_count = 0;
+    if (rc != RT_OK || done) return rc;
+    HitQueryBuffers b;
+    float *d_rgb = nullptr;
+    hipError_t e = b.upload(h_hits, h_incoming, n);
+    if (e == hipSuccess) e = b.out(reinterpret_cast<void **>(&d_rgb), n * 3 * sizeof(float));
+    if (e != hipSuccess) return fail_hip("rt_shade_hits_host", e);
+    rc = rt_shade_hits(scene, b.d_hits, b.d_incoming, n, d_rgb, b.d_cnt, nullptr);
+    if (rc != RT_OK) return rc;
+    unsigned long long cnt = 0;
+    e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(&cnt, b.d_cnt, sizeof cnt, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(h_rgb, d_rgb, n * 3 * sizeof(float), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail_hip("rt_shade_hits_host", e);
+    if (h_ray_count) *h_ray_count = cnt;
+    return RT_OK;
+}
+
+int rt_refract_rays_host(const rt_scene *scene, const rt_hit *h_hits, const rt_ray *h_incoming, size_t n, float max_distance, uint32_t *h_kind,
+                         float *h_travel, rt_ray *h_escape, unsigned long long *h_ray_count) {
+    bool done;
+    int rc = hit_query_args("rt_refract_rays_host", true, scene, n, h_hits && h_incoming && h_kind && h_escape, "hit, incoming-ray, kind or escape-ray", &done);
+    if (rc == RT_OK && done && h_ray_count) *h_ray_count = 0;
+    if (rc != RT_OK || done) return rc;
+    HitQueryBuffers b;
+    uint32_t *d_kind = nullptr;
+    float *d_travel = nullptr;
+    rt_ray *d_escape = nullptr;
+    hipError_t e = b.upload(h_hits, h_incoming, n);
+    if (e == hipSuccess) e = b.out(reinterpret_cast<void **>(&d_kind), n * sizeof(uint32_t));
+    if (e == hipSuccess && h_travel) e = b.out(reinterpret_cast<void **>(&d_travel), n * sizeof(float));
+    if (e == hipSuccess) e = b.out(reinterpret_cast<void **>(&d_escape), n * sizeof(rt_ray));
+    if (e != hipSuccess) return fail_hip("rt_refract_rays_host", e);
+    rc = rt_refract_rays(scene, b.d_hits, b.d_incoming, n, max_distance, d_kind, d_travel, d_escape, b.d_cnt, nullptr);
+    if (rc != RT_OK) return rc;
+    unsigned long long cnt = 0;
+    e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(&cnt, b.d_cnt, sizeof cnt, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(h_kind, d_kind, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && h_travel) e = hipMemcpy(h_travel, d_travel, n * sizeof(float), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(h_escape, d_escape, n * sizeof(rt_ray), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail_hip("rt_refract_rays_host", e);
+    if (h_ray_count) *h_ray_count = cnt;
     return RT_OK;
 }
 

@@ -278,6 +278,53 @@ int rt_trace_rays(const rt_scene *scene, const rt_ray *d_rays, size_t n_rays, in
 int rt_trace_rays_host(const rt_scene *scene, const rt_ray *h_rays, size_t n_rays, int32_t max_depth, float contribution,
                        float *h_rgb, unsigned long long *h_ray_count);
 
+/* ---- hit queries: get_shade, get_reflect and get_refract on caller-supplied hits ------------------------------
+
+ * What the reference does with a Hit once it holds one — the three calls ray_trace makes between two casts (main.rs:478-514) — so that
+ * a caller can write the recursion itself, level by level: cast -> shade / reflect / refract -> cast, weighting, stopping, re-sorting
+ * or mixing levels as it likes (INTEGRATION.md shows the loop).  A hit is the rt_hit rt_cast_rays writes; Hit.ray (main.rs:142)
+ * travels beside it as the rt_ray that produced it: entry i of d_incoming belongs to entry i of d_hits.  Device pointers, n records
+ * each; stream-ordered and asynchronous on hip_stream (NULL = default stream); no workspace, so every call may be captured into a
+ * HIP graph at once, as rt_cast_rays below the breadth-first switch.  Every result is the reference's, bit for bit.
+ * Records are the caller's and are validated, never trusted:
+ *   - a hit whose kind is neither 0 nor 1, or (rt_shade_hits, rt_refract_rays) whose object_index >= n_materials, is "no hit": black,
+ *     an all-zero ray, kind RT_HIT_NONE, and no cast; rt_reflect_rays has no scene and tests the kind only;
+ *   - a hit's index outside its primitive array is used as given: it only serves as an exclusion, and as one excludes nothing (the
+ *     rule of rt_ray.exclude_index);
+ *   - a hit's face_direction above 1 is read as Back;
+ *   - incoming rays are read exactly as rt_cast_rays reads them (a face value above 2 is Both); NaN and Inf in positions, normals or
+ *     directions pass through the arithmetic as in the reference.
+ * Checked before any device work, in this order: n >= 2^32 is RT_ERR_UNSUPPORTED; a null scene RT_ERR_INVALID_ARGUMENT (rt_shade_hits,
+ * rt_refract_rays); n == 0 is RT_OK and launches nothing; a null hits, incoming or required output pointer RT_ERR_INVALID_ARGUMENT.
+ * A wave takes 64 consecutive records; a batch of more than 2^26 runs in bands of whole 64-record chunks (any n below 2^32).  The casts are pair-wise
+ * (cast_pairs), or wave-uniform under RT_AMD_QUERY_WAVE_UNIFORM=1, with the same bits (DESIGN.md §3.10 says which is faster when).
+ * A scene walked breadth-first (RT_AMD_BFS_WALK_TRIANGLES) gives the same bits through the same two casts: the breadth-first walk
+ * itself is not used inside these kernels.
+ * Not covered: scatter_hit and weighted_select as queries (they need the generator plumbing of rt_trace_rays_distributed); per-record
+ * cast counts; rt_multi_* variants; the breadth-first walk inside these kernels; the ray of Refraction::Infinite (main.rs:154-156),
+ * which the reference's callers discard. */
+
+/* get_shade(&hit) (main.rs:407-464): d_rgb[3*i + c], bit for bit, NaN and -0.0 included.  d_ray_count: NULL or one u64 device word, the
+ * shadow casts (one per light that faces the bumped normal, main.rs:435) are ADDED. */
+int rt_shade_hits(const rt_scene *scene, const rt_hit *d_hits, const rt_ray *d_incoming, size_t n, float *d_rgb,
+                  unsigned long long *d_ray_count, void *hip_stream);
+/* get_reflect(&hit) (main.rs:328-341): origin = the hit's position, direction normalised as the reference does, face mode = the incoming
+ * ray's, exclusion { hit.kind, hit.index, invert(hit.face_direction) }.  Pure: needs no scene. */
+int rt_reflect_rays(const rt_hit *d_hits, const rt_ray *d_incoming, size_t n, rt_ray *d_out, void *hip_stream);
+/* get_refract(&hit, max_distance) (main.rs:343-405; the reference passes 100.0): 1 to 11 casts per hit.
+ *   d_kind[i]    0 Escaped, 1 Infinite, 2 Trapped (main.rs:149-158), RT_HIT_NONE for a record that is no hit
+ *   d_travel[i]  travel_distance when Escaped, else 0 (may be NULL)
+ *   d_escape[i]  escape_ray when Escaped, else all-zero words; feeds rt_cast_rays / rt_trace_rays as it is
+ *   d_ray_count  NULL or one u64 device word: the casts get_refract made are ADDED. */
+int rt_refract_rays(const rt_scene *scene, const rt_hit *d_hits, const rt_ray *d_incoming, size_t n, float max_distance,
+                    uint32_t *d_kind, float *d_travel, rt_ray *d_escape, unsigned long long *d_ray_count, void *hip_stream);
+/* The same two with host buffers: allocate, launch, copy back and synchronise.  *h_ray_count is overwritten with the cast count of
+ * this call (may be NULL).  Without a device they fail with a status and write nothing. */
+int rt_shade_hits_host(const rt_scene *scene, const rt_hit *h_hits, const rt_ray *h_incoming, size_t n, float *h_rgb,
+                       unsigned long long *h_ray_count);
+int rt_refract_rays_host(const rt_scene *scene, const rt_hit *h_hits, const rt_ray *h_incoming, size_t n, float max_distance,
+                         uint32_t *h_kind, float *h_travel, rt_ray *h_escape, unsigned long long *h_ray_count);
+
 /* ---- distributed (stochastic / depth-of-field) pass ----------------------------
 
  * Replaces the par_iter_mut closure at src/main.rs:1131-1156 and the per-pixel RNG construction at
@@ -453,7 +500,7 @@ int rt_accumulator_resolve_device(const float *d_sum, const float *d_weight, siz
  * named like the environment variable that seeds it — RT_AMD_DIST_PIPELINE, RT_AMD_DIST_WS_MB, RT_AMD_RNG_LOOKAHEAD,
  * RT_AMD_DIST_BY_COST, RT_AMD_DIST_OWN_FIRST, RT_AMD_DIST_PREP_FIRST, RT_AMD_DIST_SPLIT, RT_AMD_DIAG_WS_REFUSE,
  * RT_AMD_MULTI_FORCE_STAGE, RT_AMD_BFS_WALK_TRIANGLES (read by rt_scene_create), RT_AMD_WF_SHARE, RT_AMD_DIAG_BFS_CAP,
- * RT_AMD_DIAG_DIST_BAND_RAYS, RT_AMD_QUERY_WAVE_UNIFORM (INTEGRATION.md says what each does); any other name is RT_ERR_INVALID_ARGUMENT.  The environment is read ONCE per process, at the first use;
+ * RT_AMD_DIAG_DIST_BAND_RAYS, RT_AMD_QUERY_WAVE_UNIFORM, RT_AMD_DIAG_HIT_BAND_RECORDS (INTEGRATION.md says what each does); any other name is RT_ERR_INVALID_ARGUMENT.  The environment is read ONCE per process, at the first use;
  * after that only this call changes a switch: value = decimal integer, NULL or "" = unset (the library's own choice).  Render
  * calls read the switches without locks: set them between calls, not during one. */
 int rt_set_option(const char *name, const char *value);
