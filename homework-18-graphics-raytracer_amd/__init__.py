@@ -29,7 +29,7 @@ from ._capi import Camera, Frame, Light, Material, RtError, SceneDesc, Sphere, T
 
 __all__ = [
     "World", "ObjectProxy", "Scene", "Camera", "Frame", "Material", "Light", "RtError", "reference_world",
-    "reference_camera", "render_whitted", "render_whitted_numpy", "make_rays", "cast_rays", "Hits", "camera_rays", "cast_rays_numpy", "trace_rays", "trace_rays_numpy", "shade_hits", "reflect_rays", "refract_rays", "Refractions", "ESCAPED", "INFINITE", "TRAPPED", "HIT_NONE", "shade_hits_numpy", "refract_rays_numpy", "Rng", "focus_rays", "trace_rays_distributed", "trace_rays_distributed_numpy", "render_distributed", "render_distributed_numpy", "set_option", "options", "post_process_device", "encode_srgb8_device", "post_process", "encode_srgb8", "write_to_file",
+    "reference_camera", "render_whitted", "render_whitted_numpy", "make_rays", "cast_rays", "Hits", "camera_rays", "cast_rays_numpy", "trace_rays", "trace_rays_numpy", "shade_hits", "reflect_rays", "refract_rays", "Refractions", "ESCAPED", "INFINITE", "TRAPPED", "HIT_NONE", "shade_hits_numpy", "refract_rays_numpy", "scatter_hits", "scatter_factors", "Scatters", "DIFFUSE", "REFLECTION", "REFRACTION", "scatter_hits_numpy", "scatter_factors_numpy", "Rng", "focus_rays", "trace_rays_distributed", "trace_rays_distributed_numpy", "render_distributed", "render_distributed_numpy", "set_option", "options", "post_process_device", "encode_srgb8_device", "post_process", "encode_srgb8", "write_to_file",
     "DEFAULT_OBJ",
 ]
 
@@ -646,6 +646,135 @@ def trace_rays_distributed_numpy(scene: Scene, rays_np, max_depth: int, rng: Rng
     _capi.check(_capi.amd_lib().rt_trace_rays_distributed_host(scene._h, a.ctypes.data_as(C.c_void_p), a.shape[0], int(max_depth), rng._h,
                                                                int(n_epochs), img.ctypes.data_as(C.c_void_p), C.byref(casts)))
     return int(casts.value)
+
+
+# ---- scatter queries: weighted_select / scatter_hit on caller-supplied hits (include/rt_amd.h rt_scatter_hits) ----
+
+DIFFUSE, REFLECTION, REFRACTION = 0, 1, 2  # ScatterType, main.rs:533-537 (HIT_NONE: the record was no hit)
+
+
+class Scatters:
+    """What scatter_hits returns: ``type`` (N,) int32 — DIFFUSE, REFLECTION, REFRACTION, or HIT_NONE for a record that was no hit —,
+    ``rays`` (N, 11) int32 rt_ray records (scattered_hit.ray: with the hits they feed reflect_rays / refract_rays / shade_hits as
+    they are) and ``cosine`` (N,) float32 (-hit.normal . new_dir)."""
+
+    def __init__(self, type, rays, cosine):
+        self.type, self.rays, self.cosine = type, rays, cosine
+
+    @property
+    def alive(self):
+        """bool mask: the level goes on — a valid record that does not meet the reference's ``cosine <= 0`` (black).  Spelt as that
+        test's negation, so a NaN cosine counts as alive, as in the reference."""
+        return (self.type != HIT_NONE) & ~(self.cosine <= 0)
+
+    def __len__(self):
+        return self.type.shape[0]
+
+
+def _rng_of(rng):
+    if not isinstance(rng, Rng):
+        raise ValueError("rng must be an Rng")
+    return rng
+
+
+def scatter_hits(scene: Scene, hits, rays, rng: Rng, rng_index=None, stream=None) -> Scatters:
+    """The three draws of one level of distributed_ray_trace (src/main.rs:533-554) for every hit: weighted_select, then scatter_hit,
+    record i on generator ``rng_index[i]`` of ``rng`` — or generator i when ``rng_index`` is None, and then ``rng`` must hold exactly
+    N generators.  ``rng_index``: an (N,) int32 CUDA tensor; an index at or beyond ``rng.count`` (-1, say) makes the record "no hit".
+    A record that is no hit draws nothing: its generator does not move.  Returns a Scatters.  Calls on one Rng must be serialised."""
+    import torch
+
+    records, n = _hits_and_rays(hits, rays)
+    _rng_of(rng)
+    idx_ptr = None
+    if rng_index is not None:
+        if not (torch.is_tensor(rng_index) and rng_index.is_cuda and rng_index.dtype == torch.int32 and rng_index.is_contiguous()
+                and tuple(rng_index.shape) == (n,)):
+            raise ValueError("rng_index must be a contiguous (N,) int32 CUDA tensor")
+        idx_ptr = C.c_void_p(rng_index.data_ptr())
+    elif n != rng.count:
+        raise ValueError("without rng_index the Rng must hold one generator per record")
+    type_ = torch.empty((n,), dtype=torch.int32, device=records.device)
+    out = torch.empty((n, 11), dtype=torch.int32, device=records.device)
+    cosine = torch.empty((n,), dtype=torch.float32, device=records.device)
+    s = stream if stream is not None else torch.cuda.current_stream()
+    _capi.check(_capi.amd_lib().rt_scatter_hits(scene._h, C.c_void_p(records.data_ptr()), C.c_void_p(rays.data_ptr()), n, rng._h, idx_ptr,
+                                                C.c_void_p(type_.data_ptr()), C.c_void_p(out.data_ptr()), C.c_void_p(cosine.data_ptr()),
+                                                C.c_void_p(s.cuda_stream)))
+    return Scatters(type_, out, cosine)
+
+
+def scatter_factors(scene: Scene, hits, rays, types, next_rays, travel, out=None, stream=None):
+    """The factor of one level once its next ray is known (src/main.rs:566-570, 585-589, 605): get_diffuse (DIFFUSE) or get_specular
+    (REFLECTION) of the hit's material towards ``next_rays[i]``'s direction seen from ``-rays[i]``'s, or opaque_decay ** travel[i] in all
+    three channels (REFRACTION); any other type or a record that is no hit gives 0.  ``types``: (N,) int32, ``next_rays``: (N, 11)
+    int32 rt_ray records, ``travel``: (N,) float32, all CUDA.  Returns ``out``, an (N, 3) float32 CUDA tensor (allocated if None)."""
+    import torch
+
+    records, n = _hits_and_rays(hits, rays)
+    if not (torch.is_tensor(types) and types.is_cuda and types.dtype == torch.int32 and types.is_contiguous() and tuple(types.shape) == (n,)):
+        raise ValueError("types must be a contiguous (N,) int32 CUDA tensor")
+    _records(next_rays, 11, "next_rays")
+    if next_rays.shape[0] != n:
+        raise ValueError("next_rays must have one record per hit")
+    if not (torch.is_tensor(travel) and travel.is_cuda and travel.dtype == torch.float32 and travel.is_contiguous()
+            and tuple(travel.shape) == (n,)):
+        raise ValueError("travel must be a contiguous (N,) float32 CUDA tensor")
+    if out is None:
+        out = torch.empty((n, 3), dtype=torch.float32, device=records.device)
+    if not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (n, 3)):
+        raise ValueError("out must be a contiguous (N, 3) float32 CUDA tensor")
+    s = stream if stream is not None else torch.cuda.current_stream()
+    _capi.check(_capi.amd_lib().rt_scatter_factors(scene._h, C.c_void_p(records.data_ptr()), C.c_void_p(rays.data_ptr()),
+                                                   C.c_void_p(types.data_ptr()), C.c_void_p(next_rays.data_ptr()), C.c_void_p(travel.data_ptr()),
+                                                   n, C.c_void_p(out.data_ptr()), C.c_void_p(s.cuda_stream)))
+    return out
+
+
+def _host_column(a, dtype, n, name):
+    a = np.asarray(a)
+    if not (a.dtype.kind in dtype[0] and a.dtype.itemsize == 4 and a.shape == (n,)):
+        raise ValueError(f"{name}: expected an ({n},) array of {dtype[1]}")
+    return np.ascontiguousarray(a)
+
+
+def scatter_hits_numpy(scene: Scene, hits_np, rays_np, rng: Rng, rng_index=None):
+    """Host-buffer convenience (rt_scatter_hits_host, synchronous; the Rng stays on the device): returns (type[N] int32, scattered rays
+    as a RAY_DTYPE array, cosine[N] float32)."""
+    h, r = _host_records(hits_np, HIT_DTYPE, 13, "hits"), _host_records(rays_np, RAY_DTYPE, 11, "rays")
+    if h.shape[0] != r.shape[0]:
+        raise ValueError("hits and rays must have one record each per hit")
+    n = h.shape[0]
+    _rng_of(rng)
+    idx = None
+    if rng_index is not None:
+        idx = _host_column(rng_index, ("iu", "32-bit integers"), n, "rng_index")
+    elif n != rng.count:
+        raise ValueError("without rng_index the Rng must hold one generator per record")
+    type_ = np.zeros(n, dtype=np.int32)
+    out = np.zeros(n, dtype=RAY_DTYPE)
+    cosine = np.zeros(n, dtype=np.float32)
+    _capi.check(_capi.amd_lib().rt_scatter_hits_host(scene._h, h.ctypes.data_as(C.c_void_p), r.ctypes.data_as(C.c_void_p), n, rng._h,
+                                                     None if idx is None else idx.ctypes.data_as(C.c_void_p),
+                                                     type_.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p),
+                                                     cosine.ctypes.data_as(C.c_void_p)))
+    return type_, out, cosine
+
+
+def scatter_factors_numpy(scene: Scene, hits_np, rays_np, types, next_rays_np, travel):
+    """Host-buffer convenience (rt_scatter_factors_host, synchronous): returns rgb[N, 3] float32."""
+    h, r = _host_records(hits_np, HIT_DTYPE, 13, "hits"), _host_records(rays_np, RAY_DTYPE, 11, "rays")
+    nx = _host_records(next_rays_np, RAY_DTYPE, 11, "next_rays")
+    n = h.shape[0]
+    if r.shape[0] != n or nx.shape[0] != n:
+        raise ValueError("hits, rays and next_rays must have one record each per hit")
+    t = _host_column(types, ("iu", "32-bit integers"), n, "types")
+    tr = _host_column(travel, ("f", "float32"), n, "travel")
+    rgb = np.zeros((n, 3), dtype=np.float32)
+    _capi.check(_capi.amd_lib().rt_scatter_factors_host(scene._h, h.ctypes.data_as(C.c_void_p), r.ctypes.data_as(C.c_void_p),
+                                                        t.ctypes.data_as(C.c_void_p), nx.ctypes.data_as(C.c_void_p),
+                                                        tr.ctypes.data_as(C.c_void_p), n, rgb.ctypes.data_as(C.c_void_p)))
+    return rgb
 
 
 def render_distributed_numpy(scene: Scene, camera: Camera, frame: Frame, rng: Rng, n_epochs: int, img: np.ndarray,

@@ -165,6 +165,7 @@ AMD_SYMBOLS = [
     "rt_cast_rays", "rt_cast_rays_host", "rt_camera_rays", "rt_trace_rays", "rt_trace_rays_host",
     "rt_rng_create_seeded", "rt_rng_upload", "rt_trace_rays_distributed", "rt_trace_rays_distributed_host", "rt_focus_rays",
     "rt_shade_hits", "rt_reflect_rays", "rt_refract_rays", "rt_shade_hits_host", "rt_refract_rays_host",
+    "rt_scatter_hits", "rt_scatter_factors", "rt_scatter_hits_host", "rt_scatter_factors_host",
 ]
 HOST_SYMBOLS = [
     "rt_world_new", "rt_world_free", "rt_world_push_object", "rt_world_push_triangle", "rt_world_push_sphere",
@@ -293,6 +294,11 @@ def amd_lib() -> C.CDLL:
         lib.rt_shade_hits_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_ulonglong)]
         lib.rt_refract_rays_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.POINTER(C.c_ulonglong)]
+        lib.rt_scatter_hits.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p]
+        lib.rt_scatter_factors.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        lib.rt_scatter_hits_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.rt_scatter_factors_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         lib.rt_scene_describe_nodes.argtypes = [C.POINTER(SceneDesc), C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32)]
         _amd = lib
     return _amd

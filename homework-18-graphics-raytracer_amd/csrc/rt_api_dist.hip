@@ -270,6 +270,17 @@ static hipError_t lookahead_after_chain(void *ctx) {
 
 } /* extern "C" */
 
+size_t rng_generator_count(const rt_rng *rng) { return rng_count(rng); }
+
+hipError_t rng_begin_draws(rt_rng *rng, bool prepare, hipStream_t stream, uint32_t **d_states) {
+    *d_states = rng->d_states;
+    hipError_t e = hipSuccess;
+    if (prepare && !rng->ahead && rng_count(rng) != 0)
+        e = rt::launch_rng_prepare(rng->d_states, (uint32_t)rng_count(rng), rng->d_list, rng->compute_units, stream);
+    rng->ahead = false; /* a generator may move on to its prepared block */
+    return e;
+}
+
 /* The pass behind rt_render_distributed and rt_trace_rays_distributed: kf is a camera frame (make_kernel_frame) or a band of a ray
  * batch (one row of rays, rt_kernels.h frame_set_rays / frame_set_sample_stride); dp comes with what differs between the two — the
  * band's generator records, n_epochs, focus and blur, the outputs — and `first` is the band's first generator within rng (0 for a

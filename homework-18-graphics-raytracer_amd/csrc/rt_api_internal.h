@@ -8,7 +8,8 @@
  *   rt_api_dist.hip    rt_rng_* and rt_render_distributed: batches, the two workspaces, the streams of a pipelined call
  *   rt_api_multi.hip   rt_multi_*: a device list from one process
  *   rt_api_post.hip    post_process / sRGB / accumulator / rt_math_eval entry points
- *   rt_api_query.hip   rt_cast_rays / rt_camera_rays and the hit queries rt_shade_hits / rt_reflect_rays / rt_refract_rays
+ *   rt_api_query.hip   rt_cast_rays / rt_camera_rays, the hit queries rt_shade_hits / rt_reflect_rays / rt_refract_rays and the scatter
+ *                      queries rt_scatter_hits / rt_scatter_factors
  */
 #ifndef RT_API_INTERNAL_H
 #define RT_API_INTERNAL_H
@@ -127,6 +128,19 @@ hipError_t launch_shade_hits(const KernelScene &sc, const rt_hit *hits, const rt
 hipError_t launch_refract_rays(const KernelScene &sc, const rt_hit *hits, const rt_ray *incoming, uint32_t n, float max_distance, uint32_t *kind,
                                float *travel, rt_ray *escape, unsigned long long *ray_count, bool wave_uniform, uint32_t band_records, hipStream_t stream);
 hipError_t launch_reflect_rays(const rt_hit *hits, const rt_ray *incoming, uint32_t n, rt_ray *out, uint32_t band_records, hipStream_t stream);
+/* The scatter queries' kernels (rt_scatter_query.hip), banded the same way.  states: the n_generators device records of an rt_rng;
+ * record i draws from generator rng_index[i], or i when rng_index is null; a generator index >= n_generators is "no hit". */
+hipError_t launch_scatter_hits(const KernelScene &sc, const rt_hit *hits, const rt_ray *incoming, uint32_t n, uint32_t *states, uint32_t n_generators,
+                               const uint32_t *rng_index, uint32_t *type, rt_ray *scattered, float *cosine, uint32_t band_records, hipStream_t stream);
+hipError_t launch_scatter_factors(const KernelScene &sc, const rt_hit *hits, const rt_ray *incoming, const uint32_t *types, const rt_ray *next,
+                                  const float *travel, uint32_t n, float *rgb, uint32_t band_records, hipStream_t stream);
 } /* namespace rt */
+
+/* What rt_scatter_hits (rt_api_query.hip) needs of an rt_rng (rt_api_dist.hip): how many generators it holds; and, for a call about to
+ * be put on `stream`, its device records — after the look-ahead pass when `prepare` is set and the generators are not known to have
+ * their next block already.  Either way the generators may move on to that block in the call, so the object's look-ahead bookkeeping
+ * is reset: the next call on it looks for itself. */
+RT_API_HIDDEN size_t rng_generator_count(const rt_rng *rng);
+RT_API_HIDDEN hipError_t rng_begin_draws(rt_rng *rng, bool prepare, hipStream_t stream, uint32_t **d_states);
 
 #endif /* RT_API_INTERNAL_H */

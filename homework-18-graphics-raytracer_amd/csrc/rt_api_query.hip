@@ -1,8 +1,9 @@
 /*
  * rt_api_query.hip — rt_cast_rays / rt_cast_rays_host / rt_camera_rays (include/rt_amd.h "ray queries"): validation, the
  * per-(scene, stream) workspace of a scene walked breadth-first, the launches of rt_query.hip; and rt_shade_hits / rt_reflect_rays /
- * rt_refract_rays with their _host forms ("hit queries"): validation and the launches of rt_hit_query.hip, no workspace.  No CPU
- * path: without a device every call fails with a status.
+ * rt_refract_rays with their _host forms ("hit queries"): validation and the launches of rt_hit_query.hip, no workspace; and
+ * rt_scatter_hits / rt_scatter_factors with theirs ("scatter queries", rt_scatter_query.hip).  No CPU path: without a device every
+ * call fails with a status.
  */
 #include "rt_api_internal.h"
 
@@ -230,6 +231,108 @@ int rt_refract_rays_host(const rt_scene *scene, const rt_hit *h_hits, const rt_r
     if (e == hipSuccess) e = hipMemcpy(h_escape, d_escape, n * sizeof(rt_ray), hipMemcpyDeviceToHost);
     if (e != hipSuccess) return fail_hip("rt_refract_rays_host", e);
     if (h_ray_count) *h_ray_count = cnt;
+    return RT_OK;
+}
+
+/* ---- scatter queries (rt_scatter_query.hip) ---- */
+
+#ifndef RT_SCATTER_PREPARE_DEFAULT
+#define RT_SCATTER_PREPARE_DEFAULT 0
+#endif
+
+/* the checks of rt_scatter_hits before any device work, in the documented order; *done: nothing to launch */
+static int scatter_hits_args(const char *who, const rt_scene *scene, const rt_rng *rng, size_t n, bool has_index, bool pointers_ok, bool *done) {
+    const std::string w(who);
+    *done = true;
+    if ((uint64_t)n >= (1ull << 32)) return fail(RT_ERR_UNSUPPORTED, w + ": 2^32 records or more (checked first; query them in several calls)");
+    if (!scene) return fail(RT_ERR_INVALID_ARGUMENT, w + ": null scene");
+    if (!rng) return fail(RT_ERR_INVALID_ARGUMENT, w + ": null rng");
+    if (!has_index && n != rng_generator_count(rng))
+        return fail(RT_ERR_INVALID_ARGUMENT, w + ": without an index array the RNG must hold as many generators as there are records");
+    if (n == 0) return RT_OK;
+    if (!pointers_ok) return fail(RT_ERR_INVALID_ARGUMENT, w + ": null hit, incoming-ray, type or scattered-ray pointer");
+    *done = false;
+    return RT_OK;
+}
+
+int rt_scatter_hits(const rt_scene *scene, const rt_hit *d_hits, const rt_ray *d_incoming, size_t n, rt_rng *rng, const uint32_t *d_rng_index,
+                    uint32_t *d_type, rt_ray *d_scattered, float *d_cosine, void *hip_stream) {
+    bool done;
+    const int rc = scatter_hits_args("rt_scatter_hits", scene, rng, n, d_rng_index != nullptr, d_hits && d_incoming && d_type && d_scattered, &done);
+    if (rc != RT_OK || done) return rc;
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    const bool prepare = rt::option(rt::OPT_SCATTER_PREPARE, RT_SCATTER_PREPARE_DEFAULT) != 0;
+    uint32_t *d_states = nullptr;
+    hipError_t e = rng_begin_draws(rng, prepare, stream, &d_states);
+    if (e == hipSuccess)
+        e = rt::launch_scatter_hits(scene->ks, d_hits, d_incoming, (uint32_t)n, d_states, (uint32_t)rng_generator_count(rng), d_rng_index, d_type,
+                                    d_scattered, d_cosine, hit_query_band(), stream);
+    if (e != hipSuccess) return fail_hip("rt_scatter_hits: launch", e);
+    return RT_OK;
+}
+
+int rt_scatter_factors(const rt_scene *scene, const rt_hit *d_hits, const rt_ray *d_incoming, const uint32_t *d_type, const rt_ray *d_next,
+                       const float *d_travel, size_t n, float *d_rgb, void *hip_stream) {
+    bool done;
+    const int rc = hit_query_args("rt_scatter_factors", true, scene, n, d_hits && d_incoming && d_type && d_next && d_travel && d_rgb,
+                                  "hit, incoming-ray, type, next-ray, travel or rgb", &done);
+    if (rc != RT_OK || done) return rc;
+    const hipError_t e = rt::launch_scatter_factors(scene->ks, d_hits, d_incoming, d_type, d_next, d_travel, (uint32_t)n, d_rgb, hit_query_band(),
+                                                    static_cast<hipStream_t>(hip_stream));
+    if (e != hipSuccess) return fail_hip("rt_scatter_factors: launch", e);
+    return RT_OK;
+}
+
+int rt_scatter_hits_host(const rt_scene *scene, const rt_hit *h_hits, const rt_ray *h_incoming, size_t n, rt_rng *rng, const uint32_t *h_rng_index,
+                         uint32_t *h_type, rt_ray *h_scattered, float *h_cosine) {
+    bool done;
+    int rc = scatter_hits_args("rt_scatter_hits_host", scene, rng, n, h_rng_index != nullptr, h_hits && h_incoming && h_type && h_scattered, &done);
+    if (rc != RT_OK || done) return rc;
+    HitQueryBuffers b;
+    uint32_t *d_index = nullptr, *d_type = nullptr;
+    rt_ray *d_scattered = nullptr;
+    float *d_cosine = nullptr;
+    hipError_t e = b.upload(h_hits, h_incoming, n);
+    if (e == hipSuccess && h_rng_index) e = b.out(reinterpret_cast<void **>(&d_index), n * sizeof(uint32_t));
+    if (e == hipSuccess && h_rng_index) e = hipMemcpy(d_index, h_rng_index, n * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = b.out(reinterpret_cast<void **>(&d_type), n * sizeof(uint32_t));
+    if (e == hipSuccess) e = b.out(reinterpret_cast<void **>(&d_scattered), n * sizeof(rt_ray));
+    if (e == hipSuccess && h_cosine) e = b.out(reinterpret_cast<void **>(&d_cosine), n * sizeof(float));
+    if (e != hipSuccess) return fail_hip("rt_scatter_hits_host", e);
+    rc = rt_scatter_hits(scene, b.d_hits, b.d_incoming, n, rng, d_index, d_type, d_scattered, d_cosine, nullptr);
+    if (rc != RT_OK) return rc;
+    e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(h_type, d_type, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(h_scattered, d_scattered, n * sizeof(rt_ray), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && h_cosine) e = hipMemcpy(h_cosine, d_cosine, n * sizeof(float), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail_hip("rt_scatter_hits_host", e);
+    return RT_OK;
+}
+
+int rt_scatter_factors_host(const rt_scene *scene, const rt_hit *h_hits, const rt_ray *h_incoming, const uint32_t *h_type, const rt_ray *h_next,
+                            const float *h_travel, size_t n, float *h_rgb) {
+    bool done;
+    int rc = hit_query_args("rt_scatter_factors_host", true, scene, n, h_hits && h_incoming && h_type && h_next && h_travel && h_rgb,
+                            "hit, incoming-ray, type, next-ray, travel or rgb", &done);
+    if (rc != RT_OK || done) return rc;
+    HitQueryBuffers b;
+    uint32_t *d_type = nullptr;
+    rt_ray *d_next = nullptr;
+    float *d_travel = nullptr, *d_rgb = nullptr;
+    hipError_t e = b.upload(h_hits, h_incoming, n);
+    if (e == hipSuccess) e = b.out(reinterpret_cast<void **>(&d_type), n * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemcpy(d_type, h_type, n * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = b.out(reinterpret_cast<void **>(&d_next), n * sizeof(rt_ray));
+    if (e == hipSuccess) e = hipMemcpy(d_next, h_next, n * sizeof(rt_ray), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = b.out(reinterpret_cast<void **>(&d_travel), n * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy(d_travel, h_travel, n * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = b.out(reinterpret_cast<void **>(&d_rgb), n * 3 * sizeof(float));
+    if (e != hipSuccess) return fail_hip("rt_scatter_factors_host", e);
+    rc = rt_scatter_factors(scene, b.d_hits, b.d_incoming, d_type, d_next, d_travel, n, d_rgb, nullptr);
+    if (rc != RT_OK) return rc;
+    e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(h_rgb, d_rgb, n * 3 * sizeof(float), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail_hip("rt_scatter_factors_host", e);
     return RT_OK;
 }
 

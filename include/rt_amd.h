@@ -300,8 +300,7 @@ int rt_trace_rays_host(const rt_scene *scene, const rt_ray *h_rays, size_t n_ray
  * (cast_pairs), or wave-uniform under RT_AMD_QUERY_WAVE_UNIFORM=1, with the same bits (DESIGN.md §3.10 says which is faster when).
  * A scene walked breadth-first (RT_AMD_BFS_WALK_TRIANGLES) gives the same bits through the same two casts: the breadth-first walk
  * itself is not used inside these kernels.
- * Not covered: scatter_hit and weighted_select as queries (they need the generator plumbing of rt_trace_rays_distributed); per-record
- * cast counts; rt_multi_* variants; the breadth-first walk inside these kernels; the ray of Refraction::Infinite (main.rs:154-156),
+ * Not covered: per-record cast counts; rt_multi_* variants; the breadth-first walk inside these kernels; the ray of Refraction::Infinite (main.rs:154-156),
  * which the reference's callers discard. */
 
 /* get_shade(&hit) (main.rs:407-464): d_rgb[3*i + c], bit for bit, NaN and -0.0 included.  d_ray_count: NULL or one u64 device word, the
@@ -415,6 +414,66 @@ int rt_trace_rays_distributed_host(const rt_scene *scene, const rt_ray *h_rays, 
  * of rt_render_distributed — and the caller may transform, reorder, subset or replace the rays in between.  frame->max_depth is
  * not used.  Stream-ordered on hip_stream. */
 int rt_focus_rays(const rt_camera *camera, const rt_frame *frame, float focus, float blur, rt_rng *rng, rt_ray *d_rays, void *hip_stream);
+
+/* ---- scatter queries: weighted_select and scatter_hit on caller-supplied hits ------------------------------
+
+ * The three generator draws distributed_ray_trace (main.rs:521-614) makes per level before it calls get_reflect or get_refract, and
+ * the level's factor once the next ray is known — with the hit queries above, everything a caller needs to run the depth-of-field and
+ * scatter integrator one level at a time: cast -> scatter -> reflect / refract -> cast -> shade and factor, with its own stopping
+ * rule, weighting, re-sorting or mix of levels (INTEGRATION.md writes the loop and the fold out).  Every bit, every generator record
+ * and every cast is the reference's.  Records are the hit queries': entry i of d_incoming is Hit.ray of entry i of d_hits; device
+ * pointers; stream-ordered and asynchronous on hip_stream.  The record rules are those of the hit-query block:
+ *   - a hit whose kind is neither 0 nor 1, or whose object_index >= n_materials, is "no hit"; so is (rt_scatter_hits) a record whose
+ *     generator index is at or beyond the rt_rng's count.  A "no hit" record writes type RT_HIT_NONE, an all-zero ray, cosine 0 and a
+ *     black factor — and DRAWS NOTHING: its generator does not move.  That is how a caller masks dead or finished records without
+ *     compacting;
+ *   - a valid record always draws exactly three u32 words, as the reference does, in the order selection, phi, theta.  The depth test
+ *     of main.rs:525 stays with the caller: it makes no draw;
+ *   - incoming rays are read as rt_cast_rays reads them; NaN and Inf pass through the arithmetic; degenerate materials (a NaN weight,
+ *     a weight sum that is not positive, where the reference would panic) give what rt_trace_rays_distributed gives: it is the same code;
+ *   - d_rng_index == NULL means record i draws from generator i; then n must equal the generator count (RT_ERR_INVALID_ARGUMENT).  With
+ *     an index array n is free: a caller may compact or re-sort its records between levels and keep each on its own stream.  Two
+ *     records of one call naming the same generator is the caller's error: their results are unspecified, the call stays memory-safe.
+ * Checked before any device work, in this order: n >= 2^32 is RT_ERR_UNSUPPORTED; a null scene, then (rt_scatter_hits) a null rng,
+ * RT_ERR_INVALID_ARGUMENT; the count mismatch above; n == 0 is RT_OK and launches nothing; a null record pointer or a null required
+ * output pointer RT_ERR_INVALID_ARGUMENT.  A batch of more than 2^26 records runs in bands of whole 64-record chunks
+ * (RT_AMD_DIAG_HIT_BAND_RECORDS shortens them for tests).  rt_scatter_factors uses no workspace and no generator and may be captured
+ * into a HIP graph at once.  rt_scatter_hits mutates an rt_rng: calls on one rt_rng must be serialised by the caller, and a later
+ * rt_trace_rays_distributed, rt_render_distributed, rt_focus_rays or rt_rng_download continues bit-exactly from where it left the
+ * streams.  A generator that runs dry (every 256 words: about every 85 calls) generates its next block inside the kernel;
+ * RT_AMD_SCATTER_PREPARE=1 runs the look-ahead pass ahead of the kernel instead (same bits; DESIGN.md §3.11 has the measurement).
+ * Not covered: rt_multi_* variants; per-record cast counts (these two calls cast nothing); a device-side fold. */
+
+#define RT_SCATTER_DIFFUSE 0u
+#define RT_SCATTER_REFLECTION 1u
+#define RT_SCATTER_REFRACTION 2u
+/* per record i, on generator g = d_rng_index ? d_rng_index[i] : i of rng, in stream order:
+ *   type   = weighted_select(rng_g, [(1-shiness)(1-transparency), shiness(1-transparency), transparency])   main.rs:533-537, 652-666
+ *   s_hit  = scatter_hit(state, hit, type == Diffuse ? -hit.normal : hit.ray.direction,
+ *                        type == Diffuse ? 1.0 : material.smoothness)                                       main.rs:539-554
+ *   d_type[i]      0 Diffuse, 1 Reflection, 2 Refraction; RT_HIT_NONE for a record that is "no hit"
+ *   d_scattered[i] s_hit.ray: the incoming rt_ray with its direction replaced by new_dir (origin, face mode and exclusion copied, as
+ *                  hit.clone() does; a face value above 2 is written as 2, as it was read), so (d_hits[i], d_scattered[i]) IS
+ *                  scattered_hit and feeds rt_reflect_rays / rt_refract_rays / rt_shade_hits as it is
+ *   d_cosine[i]    -hit.normal . new_dir (main.rs:559, 578, 597); the caller tests `cosine <= 0` (may be NULL) */
+int rt_scatter_hits(const rt_scene *scene, const rt_hit *d_hits, const rt_ray *d_incoming, size_t n, rt_rng *rng,
+                    const uint32_t *d_rng_index, uint32_t *d_type, rt_ray *d_scattered, float *d_cosine, void *hip_stream);
+/* the level's factor once the next ray is known (main.rs:566-570, 585-589, 605), d_rgb[3*i + c]:
+ *   type 0: material.get_diffuse (probe { at: hit.at, view: -d_incoming[i].direction, light: d_next[i].direction })
+ *   type 1: material.get_specular(the same probe)
+ *   type 2: opaque_decay.powf(d_travel[i]) in all three channels
+ *   any other type, or a record that is "no hit": 0
+ * d_next: the ray the level cast next (rt_reflect_rays' output, or the escape ray); d_travel: rt_refract_rays' d_travel.  All six
+ * pointers are required; d_next[i] is read for types 0 and 1 only and d_travel[i] for type 2 only. */
+int rt_scatter_factors(const rt_scene *scene, const rt_hit *d_hits, const rt_ray *d_incoming, const uint32_t *d_type,
+                       const rt_ray *d_next, const float *d_travel, size_t n, float *d_rgb, void *hip_stream);
+/* The same two with host records in and out: allocate, launch, copy back and synchronise.  The rng stays a device object, as in
+ * rt_trace_rays_distributed_host; h_rng_index and h_cosine may be NULL as above.  Without a device they fail with a status and write
+ * nothing. */
+int rt_scatter_hits_host(const rt_scene *scene, const rt_hit *h_hits, const rt_ray *h_incoming, size_t n, rt_rng *rng,
+                         const uint32_t *h_rng_index, uint32_t *h_type, rt_ray *h_scattered, float *h_cosine);
+int rt_scatter_factors_host(const rt_scene *scene, const rt_hit *h_hits, const rt_ray *h_incoming, const uint32_t *h_type,
+                            const rt_ray *h_next, const float *h_travel, size_t n, float *h_rgb);
 
 /* ---- several GPUs from one process (SURVEY §8e without Python or MPI) -------------------
  * Image rows are interleaved over the entries of `devices` exactly as homework-18-graphics-raytracer_amd/dist.py interleaves
