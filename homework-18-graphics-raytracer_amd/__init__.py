@@ -12,6 +12,7 @@ reference's host-side names on top of them:
     trace_rays (World::ray_trace)  src/main.rs:466-519, on caller-supplied rays
     trace_rays_distributed         src/main.rs:521-614 (distributed_ray_trace), on caller-supplied rays
     shade_hits / reflect_rays / refract_rays   src/main.rs:407-464, 328-341, 343-405 (get_shade, get_reflect, get_refract), on caller-supplied hits
+    trace_rays_distributed_levels  src/main.rs:521-614 again, one level at a time from the queries and the level-loop calls
     post_process / write_to_file   src/main.rs:748-776
 
 PyTorch is used only for device memory, streams and torch.distributed.
@@ -29,7 +30,7 @@ from ._capi import Camera, Frame, Light, Material, RtError, SceneDesc, Sphere, T
 
 __all__ = [
     "World", "ObjectProxy", "Scene", "Camera", "Frame", "Material", "Light", "RtError", "reference_world",
-    "reference_camera", "render_whitted", "render_whitted_numpy", "make_rays", "cast_rays", "Hits", "camera_rays", "cast_rays_numpy", "trace_rays", "trace_rays_numpy", "shade_hits", "reflect_rays", "refract_rays", "Refractions", "ESCAPED", "INFINITE", "TRAPPED", "HIT_NONE", "shade_hits_numpy", "refract_rays_numpy", "scatter_hits", "scatter_factors", "Scatters", "DIFFUSE", "REFLECTION", "REFRACTION", "scatter_hits_numpy", "scatter_factors_numpy", "Rng", "focus_rays", "trace_rays_distributed", "trace_rays_distributed_numpy", "render_distributed", "render_distributed_numpy", "set_option", "options", "post_process_device", "encode_srgb8_device", "post_process", "encode_srgb8", "write_to_file",
+    "reference_camera", "render_whitted", "render_whitted_numpy", "make_rays", "cast_rays", "Hits", "camera_rays", "cast_rays_numpy", "trace_rays", "trace_rays_numpy", "shade_hits", "reflect_rays", "refract_rays", "Refractions", "ESCAPED", "INFINITE", "TRAPPED", "HIT_NONE", "shade_hits_numpy", "refract_rays_numpy", "scatter_hits", "scatter_factors", "Scatters", "DIFFUSE", "REFLECTION", "REFRACTION", "scatter_hits_numpy", "scatter_factors_numpy", "select_records", "cast_rays_indexed", "level_split", "level_join", "level_close", "level_fold", "level_finish", "trace_rays_distributed_levels", "Rng", "focus_rays", "trace_rays_distributed", "trace_rays_distributed_numpy", "render_distributed", "render_distributed_numpy", "set_option", "options", "post_process_device", "encode_srgb8_device", "post_process", "encode_srgb8", "write_to_file",
     "DEFAULT_OBJ",
 ]
 
@@ -394,6 +395,20 @@ def _hits_and_rays(hits, rays):
     return records, records.shape[0]
 
 
+def _column(t, dtype, n, name):
+    import torch
+
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == (n,)):
+        raise ValueError(f"{name} must be a contiguous ({n},) {dtype} CUDA tensor")
+
+
+def _rgb(t, n, name):
+    import torch
+
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (n, 3)):
+        raise ValueError(f"{name} must be a contiguous ({n}, 3) float32 CUDA tensor")
+
+
 def _count_ptr(ray_count):
     if ray_count is None:
         return None
@@ -456,20 +471,27 @@ class Refractions:
         return self.kind.shape[0]
 
 
-def refract_rays(scene: Scene, hits, rays, max_distance: float = 100.0, ray_count=None, stream=None) -> Refractions:
-    """get_refract (src/main.rs:343-405) for every hit, the walk through the glass: 1 to 11 casts each.  Returns a Refractions;
-    ``ray_count``: a 1-element int64 CUDA tensor that those casts are added to."""
+def refract_rays(scene: Scene, hits, rays, max_distance: float = 100.0, ray_count=None, stream=None, out=None) -> Refractions:
+    """get_refract (src/main.rs:343-405) for every hit, the walk through the glass: 1 to 11 casts each.  Returns a Refractions
+    (``out``, a Refractions of this size to write into, or a new one); ``ray_count``: a 1-element int64 CUDA tensor that those casts
+    are added to."""
     import torch
 
     records, n = _hits_and_rays(hits, rays)
-    kind = torch.empty((n,), dtype=torch.int32, device=records.device)
-    travel = torch.empty((n,), dtype=torch.float32, device=records.device)
-    escape = torch.empty((n, 11), dtype=torch.int32, device=records.device)
+    if out is None:
+        out = Refractions(torch.empty((n,), dtype=torch.int32, device=records.device), torch.empty((n,), dtype=torch.float32, device=records.device),
+                          torch.empty((n, 11), dtype=torch.int32, device=records.device))
+    kind, travel, escape = out.kind, out.travel, out.rays
+    _column(kind, torch.int32, n, "out.kind")
+    _column(travel, torch.float32, n, "out.travel")
+    _records(escape, 11, "out.rays")
+    if escape.shape[0] != n:
+        raise ValueError("out must have one record per hit")
     s = stream if stream is not None else torch.cuda.current_stream()
     _capi.check(_capi.amd_lib().rt_refract_rays(scene._h, C.c_void_p(records.data_ptr()), C.c_void_p(rays.data_ptr()), n, float(max_distance),
                                                 C.c_void_p(kind.data_ptr()), C.c_void_p(travel.data_ptr()), C.c_void_p(escape.data_ptr()),
                                                 _count_ptr(ray_count), C.c_void_p(s.cuda_stream)))
-    return Refractions(kind, travel, escape)
+    return out
 
 
 def _host_records(a, dtype, words, name):
@@ -677,11 +699,12 @@ def _rng_of(rng):
     return rng
 
 
-def scatter_hits(scene: Scene, hits, rays, rng: Rng, rng_index=None, stream=None) -> Scatters:
+def scatter_hits(scene: Scene, hits, rays, rng: Rng, rng_index=None, stream=None, out=None) -> Scatters:
     """The three draws of one level of distributed_ray_trace (src/main.rs:533-554) for every hit: weighted_select, then scatter_hit,
     record i on generator ``rng_index[i]`` of ``rng`` — or generator i when ``rng_index`` is None, and then ``rng`` must hold exactly
     N generators.  ``rng_index``: an (N,) int32 CUDA tensor; an index at or beyond ``rng.count`` (-1, say) makes the record "no hit".
-    A record that is no hit draws nothing: its generator does not move.  Returns a Scatters.  Calls on one Rng must be serialised."""
+    A record that is no hit draws nothing: its generator does not move.  Returns a Scatters (``out``, a Scatters of this size to write
+    into, or a new one).  Calls on one Rng must be serialised."""
     import torch
 
     records, n = _hits_and_rays(hits, rays)
@@ -694,14 +717,19 @@ def scatter_hits(scene: Scene, hits, rays, rng: Rng, rng_index=None, stream=None
         idx_ptr = C.c_void_p(rng_index.data_ptr())
     elif n != rng.count:
         raise ValueError("without rng_index the Rng must hold one generator per record")
-    type_ = torch.empty((n,), dtype=torch.int32, device=records.device)
-    out = torch.empty((n, 11), dtype=torch.int32, device=records.device)
-    cosine = torch.empty((n,), dtype=torch.float32, device=records.device)
+    if out is None:
+        out = Scatters(torch.empty((n,), dtype=torch.int32, device=records.device), torch.empty((n, 11), dtype=torch.int32, device=records.device),
+                       torch.empty((n,), dtype=torch.float32, device=records.device))
+    _column(out.type, torch.int32, n, "out.type")
+    _records(out.rays, 11, "out.rays")
+    if out.rays.shape[0] != n:
+        raise ValueError("out must have one record per hit")
+    _column(out.cosine, torch.float32, n, "out.cosine")
     s = stream if stream is not None else torch.cuda.current_stream()
     _capi.check(_capi.amd_lib().rt_scatter_hits(scene._h, C.c_void_p(records.data_ptr()), C.c_void_p(rays.data_ptr()), n, rng._h, idx_ptr,
-                                                C.c_void_p(type_.data_ptr()), C.c_void_p(out.data_ptr()), C.c_void_p(cosine.data_ptr()),
+                                                C.c_void_p(out.type.data_ptr()), C.c_void_p(out.rays.data_ptr()), C.c_void_p(out.cosine.data_ptr()),
                                                 C.c_void_p(s.cuda_stream)))
-    return Scatters(type_, out, cosine)
+    return out
 
 
 def scatter_factors(scene: Scene, hits, rays, types, next_rays, travel, out=None, stream=None):
@@ -775,6 +803,250 @@ def scatter_factors_numpy(scene: Scene, hits_np, rays_np, types, next_rays_np, t
                                                         t.ctypes.data_as(C.c_void_p), nx.ctypes.data_as(C.c_void_p),
                                                         tr.ctypes.data_as(C.c_void_p), n, rgb.ctypes.data_as(C.c_void_p)))
     return rgb
+
+
+# ---- level loop: select, indexed casts, the glue of one level and the fold (include/rt_amd.h rt_select_records ... rt_level_finish) ----
+
+
+def _stream_ptr(stream):
+    import torch
+
+    s = stream if stream is not None else torch.cuda.current_stream()
+    return C.c_void_p(s.cuda_stream)
+
+
+def _p(t):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def select_records(flags, index=None, count=None, stream=None):
+    """Stable selection on the device (rt_select_records): ``flags`` is an (N,) uint8 CUDA tensor; returns (index, count) — ``index``
+    an (N,) int32 CUDA tensor whose first ``count[0]`` entries are the ascending i with flags[i] != 0 (the rest unspecified), ``count``
+    a 1-element int32 CUDA tensor that stays on the device.  The first call on a stream allocates 4 KB of scratch and must not be
+    captured into a graph.  N == 0 leaves ``count`` as it was."""
+    import torch
+
+    if not (torch.is_tensor(flags) and flags.is_cuda and flags.dtype == torch.uint8 and flags.is_contiguous() and flags.dim() == 1):
+        raise ValueError("flags must be a contiguous (N,) uint8 CUDA tensor")
+    n = flags.shape[0]
+    if index is None:
+        index = torch.empty((n,), dtype=torch.int32, device=flags.device)
+    if count is None:
+        count = torch.empty((1,), dtype=torch.int32, device=flags.device)
+    _column(index, torch.int32, n, "index")
+    _column(count, torch.int32, 1, "count")
+    _capi.check(_capi.amd_lib().rt_select_records(_p(flags), n, _p(index), _p(count), _stream_ptr(stream)))
+    return index, count
+
+
+def cast_rays_indexed(scene: Scene, rays, index, count, out, max_count=None, ray_count=None, stream=None):
+    """World::cast of the rays an index list names (rt_cast_rays_indexed): for j < min(count[0], max_count), out[index[j]] =
+    cast(rays[index[j]]), bit for bit cast_rays' record; records of ``out`` ((N, 13) int32, required) that are not named are not
+    written, an index >= N is skipped.  ``index``: an (M,) int32 CUDA tensor, ``count``: a 1-element int32 CUDA tensor (what
+    select_records returns), ``max_count``: the host's bound on the list's length (default M).  ``ray_count``: a 1-element int64 CUDA
+    tensor that the casts made are added to."""
+    import torch
+
+    _records(rays, 11, "rays")
+    n = rays.shape[0]
+    _records(out, 13, "out")
+    if out.shape[0] != n:
+        raise ValueError("out must have one record per ray")
+    if not (torch.is_tensor(index) and index.is_cuda and index.dtype == torch.int32 and index.is_contiguous() and index.dim() == 1):
+        raise ValueError("index must be a contiguous (M,) int32 CUDA tensor")
+    _column(count, torch.int32, 1, "count")
+    m = index.shape[0] if max_count is None else int(max_count)
+    if not 0 <= m <= index.shape[0]:
+        raise ValueError("max_count must not exceed the length of index")
+    _capi.check(_capi.amd_lib().rt_cast_rays_indexed(scene._h, _p(rays), n, _p(index), _p(count), m, _p(out), _count_ptr(ray_count),
+                                                     _stream_ptr(stream)))
+    return out
+
+
+def level_split(hits, types, cosine, out_reflect=None, out_refract=None, stream=None):
+    """After scatter_hits (rt_level_split): returns (hits_reflect, hits_refract), (N, 13) int32 rt_hit records — hits[i] where the level
+    goes on as a diffuse or reflection scatter, respectively as a refraction, "no hit" elsewhere: the operands of reflect_rays and
+    refract_rays.  ``types``, ``cosine``: Scatters.type and Scatters.cosine."""
+    import torch
+
+    records = _hit_records(hits)
+    n = records.shape[0]
+    _column(types, torch.int32, n, "types")
+    _column(cosine, torch.float32, n, "cosine")
+    if out_reflect is None:
+        out_reflect = torch.empty((n, 13), dtype=torch.int32, device=records.device)
+    if out_refract is None:
+        out_refract = torch.empty((n, 13), dtype=torch.int32, device=records.device)
+    for t in (out_reflect, out_refract):
+        _records(t, 13, "out")
+        if t.shape[0] != n:
+            raise ValueError("out must have one record per hit")
+    _capi.check(_capi.amd_lib().rt_level_split(_p(records), _p(types), _p(cosine), n, _p(out_reflect), _p(out_refract), _stream_ptr(stream)))
+    return out_reflect, out_refract
+
+
+def level_join(types, cosine, reflected, refr_kind, escape, out_rays=None, out_hits=None, out_flags=None, stream=None):
+    """After reflect_rays / refract_rays (rt_level_join): returns (next_rays, next_hits, flags) — the ray each record casts next (the
+    reflected one, or the escape ray of an Escaped refraction; zero words where there is none), the next hits preset to "no hit", and
+    an (N,) uint8 flag where a ray exists: select_records(flags) + cast_rays_indexed(next_rays -> next_hits) follow."""
+    import torch
+
+    _records(reflected, 11, "reflected")
+    n = reflected.shape[0]
+    _records(escape, 11, "escape")
+    if escape.shape[0] != n:
+        raise ValueError("reflected and escape must have one record each per record")
+    _column(types, torch.int32, n, "types")
+    _column(cosine, torch.float32, n, "cosine")
+    _column(refr_kind, torch.int32, n, "refr_kind")
+    if out_rays is None:
+        out_rays = torch.empty((n, 11), dtype=torch.int32, device=reflected.device)
+    if out_hits is None:
+        out_hits = torch.empty((n, 13), dtype=torch.int32, device=reflected.device)
+    if out_flags is None:
+        out_flags = torch.empty((n,), dtype=torch.uint8, device=reflected.device)
+    _records(out_rays, 11, "out_rays")
+    _records(out_hits, 13, "out_hits")
+    if out_rays.shape[0] != n or out_hits.shape[0] != n:
+        raise ValueError("outputs must have one record per record")
+    _column(out_flags, torch.uint8, n, "out_flags")
+    _capi.check(_capi.amd_lib().rt_level_join(_p(types), _p(cosine), _p(reflected), _p(refr_kind), _p(escape), n, _p(out_rays), _p(out_hits),
+                                              _p(out_flags), _stream_ptr(stream)))
+    return out_rays, out_hits, out_flags
+
+
+def level_close(hits, types, cosine, next_hits, out=None, stream=None):
+    """After the indexed cast (rt_level_close): returns (N, 13) int32 rt_hit records — hits[i] where a diffuse or reflection scatter
+    went on and its next cast missed, "no hit" elsewhere: the operand of get_shade(&scattered_hit), shade_hits(out, Scatters.rays)."""
+    import torch
+
+    records = _hit_records(hits)
+    n = records.shape[0]
+    nxt = _hit_records(next_hits)
+    if nxt.shape[0] != n:
+        raise ValueError("next_hits must have one record per hit")
+    _column(types, torch.int32, n, "types")
+    _column(cosine, torch.float32, n, "cosine")
+    if out is None:
+        out = torch.empty((n, 13), dtype=torch.int32, device=records.device)
+    _records(out, 13, "out")
+    if out.shape[0] != n:
+        raise ValueError("out must have one record per hit")
+    _capi.check(_capi.amd_lib().rt_level_close(_p(records), _p(types), _p(cosine), _p(nxt), n, _p(out), _stream_ptr(stream)))
+    return out
+
+
+def level_fold(types, cosine, next_hits, factor, shade_next, shade_missed, value, stream=None):
+    """One step of the unwind (rt_level_fold), from the deepest level back: ``value`` ((N, 3) float32, in place) holds the value of the
+    level below and receives this level's — the mix of main.rs:571 / 590, the sum of main.rs:605, shade_missed or black, in
+    trace_rays_distributed's operation order."""
+    import torch
+
+    nxt = _hit_records(next_hits)
+    n = nxt.shape[0]
+    _column(types, torch.int32, n, "types")
+    _column(cosine, torch.float32, n, "cosine")
+    for t, name in ((factor, "factor"), (shade_next, "shade_next"), (shade_missed, "shade_missed"), (value, "value")):
+        _rgb(t, n, name)
+    _capi.check(_capi.amd_lib().rt_level_fold(_p(types), _p(cosine), _p(nxt), _p(factor), _p(shade_next), _p(shade_missed), n, _p(value),
+                                              _stream_ptr(stream)))
+    return value
+
+
+def level_finish(value, accum=None, valid=None, stream=None):
+    """The sample filter and the accumulation (rt_level_finish, main.rs:1157-1165): valid[i] = all three channels of value[i] are
+    is_normal ((N,) uint8 or None); accum[i] += value[i] where valid ((N, 3) float32 or None).  At least one of the two."""
+    import torch
+
+    if not (torch.is_tensor(value) and value.dim() == 2):
+        raise ValueError("value must be a contiguous (N, 3) float32 CUDA tensor")
+    n = value.shape[0]
+    _rgb(value, n, "value")
+    if accum is not None:
+        _rgb(accum, n, "accum")
+    if valid is not None:
+        _column(valid, torch.uint8, n, "valid")
+    _capi.check(_capi.amd_lib().rt_level_finish(_p(value), n, _p(accum), _p(valid), _stream_ptr(stream)))
+    return accum if accum is not None else valid
+
+
+def trace_rays_distributed_levels(scene: Scene, rays, max_depth: int, rng: Rng, n_epochs: int = 1, accum=None, samples=None, valid=None,
+                                  ray_count=None, stream=None):
+    """trace_rays_distributed — the same arguments, the same samples, flags, accumulated image, cast count and generator records, bit for
+    bit — written one level at a time from the public calls alone: the executable form of the loop in INTEGRATION.md, to be copied and
+    changed (a stopping rule, a weighting, a re-sort between levels).  Every buffer is allocated once, up front; after that the function
+    only enqueues library calls on ``stream``: no tensor arithmetic, nothing read back, no synchronisation.  The cast count is what the
+    calls' device counters add up to; the primary casts go through cast_rays_indexed with an identity list so that they are counted too.
+    (Being a sequence of calls it may not be captured before select_records has run once on the stream.)"""
+    import torch
+
+    _records(rays, 11, "rays")
+    n = rays.shape[0]
+    n_epochs = int(n_epochs)
+    for t, shape, dt in ((accum, (n, 3), torch.float32), (samples, (n_epochs, n, 3), torch.float32), (valid, (n_epochs, n), torch.uint8)):
+        if t is not None and not (torch.is_tensor(t) and t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape):
+            raise ValueError(f"expected a contiguous CUDA {dt} tensor of shape {shape}")
+    _count_ptr(ray_count)
+    _rng_of(rng)
+    if n != rng.count:
+        raise ValueError("the Rng must hold one generator per ray")
+    if accum is None and samples is None:
+        raise ValueError("at least one of accum / samples")
+    if max_depth > _capi.RT_MAX_DEPTH:
+        raise RtError(-5, f"max_depth above RT_MAX_DEPTH ({_capi.RT_MAX_DEPTH})")
+    if n == 0 or n_epochs == 0:
+        return accum if accum is not None else samples
+    depth = max(int(max_depth), 0)
+    dev = rays.device
+    s = stream
+
+    def new(shape, dtype):
+        return torch.empty(shape, dtype=dtype, device=dev)
+
+    # allocated (and the one fill enqueued) with `stream` as torch's current stream: the caching allocator then ties the blocks to it
+    with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+        i32, f32, u8 = torch.int32, torch.float32, torch.uint8
+        # per level: what the fold needs — the scatter (type, cosine, scattered ray), the hits the level ended on, factor and the two shades
+        hits = [new((n, 13), i32) for _ in range(depth + 1)]  # hits[k]: what level k scatters; hits[k + 1]: what its next cast found
+        scat = [Scatters(new((n,), i32), new((n, 11), i32), new((n,), f32)) for _ in range(depth)]
+        factor = [new((n, 3), f32) for _ in range(depth)]
+        shade_next = [new((n, 3), f32) for _ in range(depth)]
+        shade_missed = [new((n, 3), f32) for _ in range(depth)]
+        level_rays = [new((n, 11), i32) for _ in range(2)]  # the rays that produced hits[k], in turn
+        h_reflect, h_refract, h_missed = new((n, 13), i32), new((n, 13), i32), new((n, 13), i32)
+        reflected = new((n, 11), i32)
+        refr = Refractions(new((n,), i32), new((n,), f32), new((n, 11), i32))
+        flags, index, count = new((n,), u8), new((n,), i32), new((1,), i32)
+        identity, n_all = new((n,), i32), new((1,), i32)
+        value = None if samples is not None else new((n, 3), f32)
+        flags.fill_(1)
+    select_records(flags, identity, n_all, stream=s)  # 0 .. n-1 and n: the primary casts as an indexed cast, which counts
+
+    for e in range(n_epochs):
+        cur_rays = rays
+        cast_rays_indexed(scene, cur_rays, identity, n_all, hits[0], ray_count=ray_count, stream=s)  # a miss is written as "no hit"
+        for k in range(depth):
+            sc = scatter_hits(scene, hits[k], cur_rays, rng, stream=s, out=scat[k])  # the level's three draws; "no hit" draws nothing
+            level_split(hits[k], sc.type, sc.cosine, h_reflect, h_refract, stream=s)
+            reflect_rays(h_reflect, sc.rays, out=reflected, stream=s)
+            refract_rays(scene, h_refract, sc.rays, 100.0, ray_count=ray_count, stream=s, out=refr)
+            nxt = level_rays[k & 1]
+            level_join(sc.type, sc.cosine, reflected, refr.kind, refr.rays, nxt, hits[k + 1], flags, stream=s)
+            select_records(flags, index, count, stream=s)
+            cast_rays_indexed(scene, nxt, index, count, hits[k + 1], ray_count=ray_count, stream=s)
+            scatter_factors(scene, hits[k], cur_rays, sc.type, nxt, refr.travel, out=factor[k], stream=s)
+            shade_hits(scene, hits[k + 1], nxt, out=shade_next[k], ray_count=ray_count, stream=s)  # the mix / sum operand
+            level_close(hits[k], sc.type, sc.cosine, hits[k + 1], h_missed, stream=s)
+            shade_hits(scene, h_missed, sc.rays, out=shade_missed[k], ray_count=ray_count, stream=s)  # get_shade(&scattered_hit)
+            cur_rays = nxt
+        v = samples[e] if samples is not None else value
+        shade_hits(scene, hits[depth], cur_rays, out=v, ray_count=ray_count, stream=s)  # depth <= 0: get_shade(&hit), main.rs:524-527
+        for k in reversed(range(depth)):
+            level_fold(scat[k].type, scat[k].cosine, hits[k + 1], factor[k], shade_next[k], shade_missed[k], v, stream=s)
+        if accum is not None or valid is not None:  # samples alone: the folded value is the sample, nothing to filter into
+            level_finish(v, accum, None if valid is None else valid[e], stream=s)
+    return accum if accum is not None else samples
+
 
 
 def render_distributed_numpy(scene: Scene, camera: Camera, frame: Frame, rng: Rng, n_epochs: int, img: np.ndarray,

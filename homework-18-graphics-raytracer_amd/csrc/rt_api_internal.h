@@ -8,8 +8,9 @@
  *   rt_api_dist.hip    rt_rng_* and rt_render_distributed: batches, the two workspaces, the streams of a pipelined call
  *   rt_api_multi.hip   rt_multi_*: a device list from one process
  *   rt_api_post.hip    post_process / sRGB / accumulator / rt_math_eval entry points
- *   rt_api_query.hip   rt_cast_rays / rt_camera_rays, the hit queries rt_shade_hits / rt_reflect_rays / rt_refract_rays and the scatter
- *                      queries rt_scatter_hits / rt_scatter_factors
+ *   rt_api_query.hip   rt_cast_rays / rt_camera_rays, the hit queries rt_shade_hits / rt_reflect_rays / rt_refract_rays, the scatter
+ *                      queries rt_scatter_hits / rt_scatter_factors and the level loop's rt_select_records / rt_cast_rays_indexed /
+ *                      rt_level_*
  */
 #ifndef RT_API_INTERNAL_H
 #define RT_API_INTERNAL_H
@@ -134,7 +135,23 @@ hipError_t launch_scatter_hits(const KernelScene &sc, const rt_hit *hits, const 
                                const uint32_t *rng_index, uint32_t *type, rt_ray *scattered, float *cosine, uint32_t band_records, hipStream_t stream);
 hipError_t launch_scatter_factors(const KernelScene &sc, const rt_hit *hits, const rt_ray *incoming, const uint32_t *types, const rt_ray *next,
                                   const float *travel, uint32_t n, float *rgb, uint32_t band_records, hipStream_t stream);
+/* The level loop's kernels (rt_level_query.hip): the stable selection (totals: RT_SELECT_MAX_GROUPS words of scratch) and the
+ * element-wise glue, fold and filter of one level; none is banded, the record number is counted in 64 bits. */
+hipError_t launch_select_records(const unsigned char *flags, uint32_t n, uint32_t *index, uint32_t *count, uint32_t *totals, hipStream_t stream);
+hipError_t launch_level_split(const rt_hit *hits, const uint32_t *type, const float *cosine, uint32_t n, rt_hit *hits_reflect, rt_hit *hits_refract,
+                              hipStream_t stream);
+hipError_t launch_level_join(const uint32_t *type, const float *cosine, const rt_ray *reflected, const uint32_t *refr_kind, const rt_ray *escape,
+                             uint32_t n, rt_ray *next, rt_hit *next_hits, unsigned char *flags, hipStream_t stream);
+hipError_t launch_level_close(const rt_hit *hits, const uint32_t *type, const float *cosine, const rt_hit *next_hits, uint32_t n, rt_hit *hits_missed,
+                              hipStream_t stream);
+hipError_t launch_level_fold(const uint32_t *type, const float *cosine, const rt_hit *next_hits, const float *factor, const float *shade_next,
+                             const float *shade_missed, uint32_t n, float *value, hipStream_t stream);
+hipError_t launch_level_finish(const float *value, uint32_t n, float *accum, unsigned char *valid, hipStream_t stream);
 } /* namespace rt */
+
+/* rt_select_records (rt_api_query.hip) keeps its block totals per (device, stream); rt_post_release (rt_api_post.hip) frees those of a
+ * device, which it has synchronised */
+RT_API_HIDDEN void select_release(int device);
 
 /* What rt_scatter_hits (rt_api_query.hip) needs of an rt_rng (rt_api_dist.hip): how many generators it holds; and, for a call about to
  * be put on `stream`, its device records — after the look-ahead pass when `prepare` is set and the generators are not known to have

@@ -26,6 +26,7 @@ int rt_post_release(void) {
     int device = 0;
     RT_HIP(hipGetDevice(&device));
     RT_HIP(hipDeviceSynchronize());
+    select_release(device); /* rt_select_records' block totals */
     std::lock_guard<std::mutex> lock(g_post_mutex);
     for (auto it = g_post_ws.begin(); it != g_post_ws.end();) {
         if (it->first.first == device) {

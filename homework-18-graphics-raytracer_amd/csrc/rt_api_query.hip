@@ -9,6 +9,44 @@
 
 static_assert(sizeof(rt_ray) == 44 && sizeof(rt_hit) == 52, "the ABI records are flat u32 / f32 words");
 
+/* The breadth-first walk's record lists for a cast of n rays (or index entries) on `stream`: per wave of the grid, in the workspace
+ * rt_render_whitted keeps them in (sized and grown as there: workgroups x 8 waves x pwf_bfs_scratch_words_per_wave), one workgroup per
+ * CU at most.  false: no room for the lists, or a capture before the first call on this stream (allocation cannot be captured). */
+namespace {
+struct BfsLists {
+    uint32_t *lists = nullptr;
+    uint32_t items_cap = RT_BFS_ITEMS_CAP, jobs_cap = RT_BFS_JOBS_CAP, groups = 0;
+};
+} /* namespace */
+static bool bfs_lists(const rt_scene *scene, hipStream_t stream, uint32_t n, BfsLists *out) {
+    const uint64_t cus = scene->resident_waves / (4u * (uint32_t)RT_MIN_WAVES);
+    uint64_t groups = ((uint64_t)n + 64u * RT_QUERY_BFS_WAVES - 1u) / (64u * RT_QUERY_BFS_WAVES);
+    if (groups > cus) groups = cus;
+    if (groups < 1) groups = 1;
+    static_assert(RT_QUERY_BFS_WAVES == 8u, "the lists are sized per wave of an 8-wave workgroup, as rt_render_whitted sizes them");
+    const size_t words = (size_t)groups * RT_QUERY_BFS_WAVES * rt::pwf_bfs_scratch_words_per_wave();
+    out->groups = (uint32_t)groups;
+    rt_scene *mut = const_cast<rt_scene *>(scene); /* workspaces are the only mutable part of a scene */
+    std::lock_guard<std::mutex> lock(mut->ws_mutex);
+    Workspace &ws = mut->workspaces[stream];
+    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &capturing) != hipSuccess) (void)hipGetLastError();
+    if (ws.bfs_words < words && capturing == hipStreamCaptureStatusNone) { /* allocation cannot be captured */
+        if (ws.d_bfs) (void)hipFree(ws.d_bfs);
+        ws.d_bfs = nullptr;
+        ws.bfs_words = 0;
+        if (hipMalloc(reinterpret_cast<void **>(&ws.d_bfs), words * sizeof(uint32_t)) != hipSuccess) { (void)hipGetLastError(); ws.d_bfs = nullptr; }
+        else ws.bfs_words = words;
+    }
+    if (ws.d_bfs != nullptr && ws.bfs_words >= words) out->lists = ws.d_bfs;
+    const long long cap = rt::option(rt::OPT_DIAG_BFS_CAP, 0); /* test hook: shorter lists (the memory is the same) */
+    if (cap > 0) {
+        out->items_cap = (uint32_t)std::min<long long>(cap, RT_BFS_ITEMS_CAP);
+        out->jobs_cap = (uint32_t)std::min<long long>(cap, RT_BFS_JOBS_CAP);
+    }
+    return out->lists != nullptr;
+}
+
 extern "C" {
 
 int rt_cast_rays(const rt_scene *scene, const rt_ray *d_rays, size_t n_rays, rt_hit *d_hits, void *hip_stream) {
@@ -21,38 +59,9 @@ int rt_cast_rays(const rt_scene *scene, const rt_ray *d_rays, size_t n_rays, rt_
     const bool wave_uniform = rt::option(rt::OPT_QUERY_WAVE_UNIFORM, 0) == 1;
     hipError_t e = hipSuccess;
     if (scene->ks.bfs_walk != 0u && !wave_uniform) {
-        /* the breadth-first walk's record lists: per wave of the grid, in the workspace rt_render_whitted keeps them in (sized and grown
-         * as there: workgroups x 8 waves x pwf_bfs_scratch_words_per_wave), one workgroup per CU at most */
-        const uint64_t cus = scene->resident_waves / (4u * (uint32_t)RT_MIN_WAVES);
-        uint64_t groups = ((uint64_t)n + 64u * RT_QUERY_BFS_WAVES - 1u) / (64u * RT_QUERY_BFS_WAVES);
-        if (groups > cus) groups = cus;
-        if (groups < 1) groups = 1;
-        static_assert(RT_QUERY_BFS_WAVES == 8u, "the lists are sized per wave of an 8-wave workgroup, as rt_render_whitted sizes them");
-        const size_t words = (size_t)groups * RT_QUERY_BFS_WAVES * rt::pwf_bfs_scratch_words_per_wave();
-        uint32_t *lists = nullptr;
-        uint32_t items_cap = RT_BFS_ITEMS_CAP, jobs_cap = RT_BFS_JOBS_CAP;
-        {
-            rt_scene *mut = const_cast<rt_scene *>(scene); /* workspaces are the only mutable part of a scene */
-            std::lock_guard<std::mutex> lock(mut->ws_mutex);
-            Workspace &ws = mut->workspaces[stream];
-            hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-            if (hipStreamIsCapturing(stream, &capturing) != hipSuccess) (void)hipGetLastError();
-            if (ws.bfs_words < words && capturing == hipStreamCaptureStatusNone) { /* allocation cannot be captured */
-                if (ws.d_bfs) (void)hipFree(ws.d_bfs);
-                ws.d_bfs = nullptr;
-                ws.bfs_words = 0;
-                if (hipMalloc(reinterpret_cast<void **>(&ws.d_bfs), words * sizeof(uint32_t)) != hipSuccess) { (void)hipGetLastError(); ws.d_bfs = nullptr; }
-                else ws.bfs_words = words;
-            }
-            if (ws.d_bfs != nullptr && ws.bfs_words >= words) lists = ws.d_bfs;
-            const long long cap = rt::option(rt::OPT_DIAG_BFS_CAP, 0); /* test hook: shorter lists (the memory is the same) */
-            if (cap > 0) {
-                items_cap = (uint32_t)std::min<long long>(cap, RT_BFS_ITEMS_CAP);
-                jobs_cap = (uint32_t)std::min<long long>(cap, RT_BFS_JOBS_CAP);
-            }
-        }
-        if (lists != nullptr) {
-            e = rt::launch_cast_rays_bfs(scene->ks, d_rays, d_hits, n, lists, items_cap, jobs_cap, (uint32_t)groups, stream);
+        BfsLists bl;
+        if (bfs_lists(scene, stream, n, &bl)) {
+            e = rt::launch_cast_rays_bfs(scene->ks, d_rays, d_hits, n, bl.lists, bl.items_cap, bl.jobs_cap, bl.groups, stream);
             if (e != hipSuccess) return fail_hip("rt_cast_rays: launch", e);
             return RT_OK;
         }
@@ -333,6 +342,134 @@ int rt_scatter_factors_host(const rt_scene *scene, const rt_hit *h_hits, const r
     e = hipDeviceSynchronize();
     if (e == hipSuccess) e = hipMemcpy(h_rgb, d_rgb, n * 3 * sizeof(float), hipMemcpyDeviceToHost);
     if (e != hipSuccess) return fail_hip("rt_scatter_factors_host", e);
+    return RT_OK;
+}
+
+/* ---- the level loop (rt_level_query.hip; the indexed casts: rt_query.hip) ---- */
+
+} /* extern "C" */
+
+/* rt_select_records' block totals: RT_SELECT_MAX_GROUPS words per (device, stream), as rt_post_process_device keeps its scratch */
+static std::mutex g_select_mutex;
+static std::map<std::pair<int, hipStream_t>, uint32_t *> g_select_totals;
+
+void select_release(int device) {
+    std::lock_guard<std::mutex> lock(g_select_mutex);
+    for (auto it = g_select_totals.begin(); it != g_select_totals.end();) {
+        if (it->first.first == device) {
+            if (it->second) (void)hipFree(it->second);
+            it = g_select_totals.erase(it);
+        } else {
+            ++it;
+        }
+    }
+}
+
+extern "C" {
+
+int rt_select_records(const unsigned char *d_flags, size_t n, uint32_t *d_index, uint32_t *d_count, void *hip_stream) {
+    bool done;
+    const int rc = hit_query_args("rt_select_records", false, nullptr, n, d_flags && d_index && d_count, "flag, index or count", &done);
+    if (rc != RT_OK || done) return rc;
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    int device = 0;
+    RT_HIP(hipGetDevice(&device));
+    uint32_t *totals = nullptr;
+    {
+        std::lock_guard<std::mutex> lock(g_select_mutex);
+        uint32_t *&slot = g_select_totals[std::make_pair(device, stream)];
+        if (!slot) {
+            hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+            if (hipStreamIsCapturing(stream, &capturing) != hipSuccess) (void)hipGetLastError();
+            if (capturing != hipStreamCaptureStatusNone)
+                return fail(RT_ERR_UNSUPPORTED, "rt_select_records: the first call on a stream allocates its scratch and cannot be captured; call once uncaptured");
+            RT_HIP(hipMalloc(reinterpret_cast<void **>(&slot), RT_SELECT_MAX_GROUPS * sizeof(uint32_t)));
+        }
+        totals = slot;
+    }
+    const hipError_t e = rt::launch_select_records(d_flags, (uint32_t)n, d_index, d_count, totals, stream);
+    if (e != hipSuccess) return fail_hip("rt_select_records: launch", e);
+    return RT_OK;
+}
+
+int rt_cast_rays_indexed(const rt_scene *scene, const rt_ray *d_rays, size_t n, const uint32_t *d_index, const uint32_t *d_count, size_t max_count,
+                         rt_hit *d_hits, unsigned long long *d_ray_count, void *hip_stream) {
+    if ((uint64_t)n >= (1ull << 32) || (uint64_t)max_count >= (1ull << 32))
+        return fail(RT_ERR_UNSUPPORTED, "rt_cast_rays_indexed: 2^32 rays or index entries or more (checked first; cast them in several calls)");
+    if (!scene) return fail(RT_ERR_INVALID_ARGUMENT, "rt_cast_rays_indexed: null scene");
+    if (n == 0 || max_count == 0) return RT_OK;
+    if (!d_rays || !d_index || !d_count || !d_hits) return fail(RT_ERR_INVALID_ARGUMENT, "rt_cast_rays_indexed: null ray, index, count or hit pointer");
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    const bool wave_uniform = rt::option(rt::OPT_QUERY_WAVE_UNIFORM, 0) == 1;
+    hipError_t e = hipSuccess;
+    if (scene->ks.bfs_walk != 0u && !wave_uniform) {
+        BfsLists bl;
+        if (bfs_lists(scene, stream, (uint32_t)max_count, &bl)) {
+            e = rt::launch_cast_rays_indexed_bfs(scene->ks, d_rays, d_hits, (uint32_t)n, d_index, d_count, (uint32_t)max_count, d_ray_count, bl.lists,
+                                                 bl.items_cap, bl.jobs_cap, bl.groups, stream);
+            if (e != hipSuccess) return fail_hip("rt_cast_rays_indexed: launch", e);
+            return RT_OK;
+        }
+        /* no room for the lists (or a capture before the first call on this stream): the pair-wise kernel, exact as well */
+    }
+    e = rt::launch_cast_rays_indexed(scene->ks, d_rays, d_hits, (uint32_t)n, d_index, d_count, (uint32_t)max_count, d_ray_count, wave_uniform, stream);
+    if (e != hipSuccess) return fail_hip("rt_cast_rays_indexed: launch", e);
+    return RT_OK;
+}
+
+int rt_level_split(const rt_hit *d_hits, const uint32_t *d_type, const float *d_cosine, size_t n, rt_hit *d_hits_reflect, rt_hit *d_hits_refract,
+                   void *hip_stream) {
+    bool done;
+    const int rc = hit_query_args("rt_level_split", false, nullptr, n, d_hits && d_type && d_cosine && d_hits_reflect && d_hits_refract,
+                                  "hit, type, cosine or output", &done);
+    if (rc != RT_OK || done) return rc;
+    const hipError_t e = rt::launch_level_split(d_hits, d_type, d_cosine, (uint32_t)n, d_hits_reflect, d_hits_refract, static_cast<hipStream_t>(hip_stream));
+    if (e != hipSuccess) return fail_hip("rt_level_split: launch", e);
+    return RT_OK;
+}
+
+int rt_level_join(const uint32_t *d_type, const float *d_cosine, const rt_ray *d_reflected, const uint32_t *d_refr_kind, const rt_ray *d_escape, size_t n,
+                  rt_ray *d_next, rt_hit *d_next_hits, unsigned char *d_flags, void *hip_stream) {
+    bool done;
+    const int rc = hit_query_args("rt_level_join", false, nullptr, n, d_type && d_cosine && d_reflected && d_refr_kind && d_escape && d_next && d_next_hits && d_flags,
+                                  "type, cosine, reflected-ray, refraction-kind, escape-ray or output", &done);
+    if (rc != RT_OK || done) return rc;
+    const hipError_t e = rt::launch_level_join(d_type, d_cosine, d_reflected, d_refr_kind, d_escape, (uint32_t)n, d_next, d_next_hits, d_flags,
+                                               static_cast<hipStream_t>(hip_stream));
+    if (e != hipSuccess) return fail_hip("rt_level_join: launch", e);
+    return RT_OK;
+}
+
+int rt_level_close(const rt_hit *d_hits, const uint32_t *d_type, const float *d_cosine, const rt_hit *d_next_hits, size_t n, rt_hit *d_hits_missed,
+                   void *hip_stream) {
+    bool done;
+    const int rc = hit_query_args("rt_level_close", false, nullptr, n, d_hits && d_type && d_cosine && d_next_hits && d_hits_missed,
+                                  "hit, type, cosine, next-hit or output", &done);
+    if (rc != RT_OK || done) return rc;
+    const hipError_t e = rt::launch_level_close(d_hits, d_type, d_cosine, d_next_hits, (uint32_t)n, d_hits_missed, static_cast<hipStream_t>(hip_stream));
+    if (e != hipSuccess) return fail_hip("rt_level_close: launch", e);
+    return RT_OK;
+}
+
+int rt_level_fold(const uint32_t *d_type, const float *d_cosine, const rt_hit *d_next_hits, const float *d_factor, const float *d_shade_next,
+                  const float *d_shade_missed, size_t n, float *d_value, void *hip_stream) {
+    bool done;
+    const int rc = hit_query_args("rt_level_fold", false, nullptr, n, d_type && d_cosine && d_next_hits && d_factor && d_shade_next && d_shade_missed && d_value,
+                                  "type, cosine, next-hit, factor, shade or value", &done);
+    if (rc != RT_OK || done) return rc;
+    const hipError_t e = rt::launch_level_fold(d_type, d_cosine, d_next_hits, d_factor, d_shade_next, d_shade_missed, (uint32_t)n, d_value,
+                                               static_cast<hipStream_t>(hip_stream));
+    if (e != hipSuccess) return fail_hip("rt_level_fold: launch", e);
+    return RT_OK;
+}
+
+int rt_level_finish(const float *d_value, size_t n, float *d_accum, unsigned char *d_valid, void *hip_stream) {
+    bool done;
+    const int rc = hit_query_args("rt_level_finish", false, nullptr, n, d_value != nullptr, "value", &done);
+    if (rc != RT_OK || done) return rc;
+    if (!d_accum && !d_valid) return fail(RT_ERR_INVALID_ARGUMENT, "rt_level_finish: neither d_accum nor d_valid");
+    const hipError_t e = rt::launch_level_finish(d_value, (uint32_t)n, d_accum, d_valid, static_cast<hipStream_t>(hip_stream));
+    if (e != hipSuccess) return fail_hip("rt_level_finish: launch", e);
     return RT_OK;
 }
 

@@ -276,6 +276,17 @@ hipError_t launch_cast_rays(const KernelScene &sc, const rt_ray *rays, rt_hit *h
 hipError_t launch_cast_rays_bfs(const KernelScene &sc, const rt_ray *rays, rt_hit *hits, uint32_t n_rays, uint32_t *bfs_scratch,
                                 uint32_t items_cap, uint32_t jobs_cap, uint32_t bfs_groups, hipStream_t stream);
 hipError_t launch_camera_rays(const KernelFrame &fr, rt_ray *rays, hipStream_t stream);
+/* the same casts through an index list: entry j < min(*count, max_count) names ray index[j], whose hit record alone is written; an
+ * entry at or beyond n_rays is skipped; the casts made are added to *ray_count (may be null).  The grid is sized by max_count; waves
+ * beyond the device-side count leave at once */
+hipError_t launch_cast_rays_indexed(const KernelScene &sc, const rt_ray *rays, rt_hit *hits, uint32_t n_rays, const uint32_t *index,
+                                    const uint32_t *count, uint32_t max_count, unsigned long long *ray_count, bool wave_uniform, hipStream_t stream);
+hipError_t launch_cast_rays_indexed_bfs(const KernelScene &sc, const rt_ray *rays, rt_hit *hits, uint32_t n_rays, const uint32_t *index,
+                                        const uint32_t *count, uint32_t max_count, unsigned long long *ray_count, uint32_t *bfs_scratch,
+                                        uint32_t items_cap, uint32_t jobs_cap, uint32_t bfs_groups, hipStream_t stream);
+
+/* the level loop's selection (rt_level_query.hip): at most this many workgroups, one block total each in a scratch of as many words */
+#define RT_SELECT_MAX_GROUPS 1024u
 
 /* diagnostics: evaluate rt_detmath on the device (op codes = rt_math_op) */
 hipError_t launch_math_eval(int op, const float *d_x, const float *d_y, float *d_out, size_t n, hipStream_t stream);

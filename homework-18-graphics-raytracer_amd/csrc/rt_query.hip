@@ -9,6 +9,8 @@
  *                              built for (rt_cast.h) — or, with RT_AMD_QUERY_WAVE_UNIFORM, cast_asm for every wave
  *   rt::cast_rays_bfs_kernel   scenes with KernelScene::bfs_walk: cast_bfs over 64-ray chunks, a grid of resident waves
  *                              taking chunks grid-stride (no atomic counter: nothing to reset, capturable)
+ *   rt::cast_rays_indexed_kernel, rt::cast_rays_indexed_bfs_kernel   the same two with the ray number taken from an index list and
+ *                              the bound from a device-side count (rt_cast_rays_indexed)
  *   rt::camera_rays_kernel     one work-item per pixel of a tile, in its compact row order
  */
 #include "rt_cast.h"
@@ -108,6 +110,88 @@ __global__ __launch_bounds__(RT_QUERY_BFS_WAVES * 64u, 2) void cast_rays_bfs_ker
     }
 }
 
+/* ---- the same casts through an index list (rt_cast_rays_indexed): entry j of the list names the ray, the device-side count bounds j ----
+ * A wave takes 64 consecutive ENTRIES; the hit goes to the record of the ray it names, so records that are not named are not written.
+ * An entry at or beyond n_rays is skipped: its lane only helps, as a lane beyond the count does. */
+
+/* the ray of a lane that has none of its own: it misses everything and only helps */
+__device__ __forceinline__ Ray idle_ray() {
+    Ray ray;
+    ray.o = v3(0.0f, 0.0f, 0.0f);
+    ray.d = v3(0.0f, 0.0f, 1.0f);
+    ray.mode = FACE_FRONT;
+    ray.excl = 0u;
+    return ray;
+}
+
+__device__ __forceinline__ uint32_t indexed_count(const uint32_t *__restrict__ count, uint32_t max_count) {
+    const uint32_t c = *count;
+    return c < max_count ? c : max_count;
+}
+
+template <bool WAVE_UNIFORM>
+__global__ __launch_bounds__(RT_QUERY_THREADS, RT_QUERY_MIN_WAVES) void cast_rays_indexed_kernel(const KernelScene sc, const rt_ray *__restrict__ rays,
+                                                                                                rt_hit *__restrict__ hits, const uint32_t n_rays,
+                                                                                                const uint32_t *__restrict__ index,
+                                                                                                const uint32_t *__restrict__ count, const uint32_t max_count,
+                                                                                                unsigned long long *ray_count) {
+    const uint32_t n_entries = indexed_count(count, max_count);
+    const uint32_t first = blockIdx.x * RT_QUERY_THREADS + (threadIdx.x & ~63u); /* the wave's first entry */
+    if (first >= n_entries) return;                                              /* whole waves only, before LDS is touched */
+    const uint32_t j = first + (threadIdx.x & 63u);
+    const uint32_t i = j < n_entries ? index[j] : 0xffffffffu;
+    const bool active = j < n_entries && i < n_rays;
+    const Ray ray = active ? ray_from_abi(rays + i, sc.n_triangles, sc.n_spheres) : idle_ray();
+    CastResult cr;
+    cr.prim = -1;
+    cr.t = 0.0f;
+    cr.bf = 0u;
+    cr.a0 = cr.a1 = cr.a2 = 0.0f;
+    if constexpr (WAVE_UNIFORM) {
+        if (active) cr = cast_asm(sc, ray);
+    } else {
+        __shared__ PairLdsSlim pair_lds_all[RT_QUERY_THREADS / 64];
+        cr = cast_pairs(sc, ray, active, &pair_lds_all[threadIdx.x >> 6]); /* all 64 lanes: those without a ray help */
+    }
+    if (active) store_hit(sc, ray, cr, hits + i);
+    if (ray_count != nullptr) {
+        const unsigned long long cast = __ballot(active);
+        if ((threadIdx.x & 63u) == 0u && cast != 0ull) atomicAdd(ray_count, (unsigned long long)__popcll(cast));
+    }
+}
+
+__global__ __launch_bounds__(RT_QUERY_BFS_WAVES * 64u, 2) void cast_rays_indexed_bfs_kernel(const KernelScene sc, const rt_ray *__restrict__ rays,
+                                                                                           rt_hit *__restrict__ hits, const uint32_t n_rays,
+                                                                                           const uint32_t *__restrict__ index,
+                                                                                           const uint32_t *__restrict__ count, const uint32_t max_count,
+                                                                                           unsigned long long *ray_count, uint32_t *bfs_scratch,
+                                                                                           const uint32_t items_cap, const uint32_t jobs_cap) {
+    __shared__ BfsLds bfs_lds_all[RT_QUERY_BFS_WAVES];
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = blockIdx.x * RT_QUERY_BFS_WAVES + (threadIdx.x >> 6), n_waves = gridDim.x * RT_QUERY_BFS_WAVES;
+    BfsLds *const bl = &bfs_lds_all[threadIdx.x >> 6];
+    BfsScratch ws;
+    uint2 *const mine = reinterpret_cast<uint2 *>(bfs_scratch) + (size_t)wave * (2u * (size_t)items_cap + jobs_cap);
+    ws.items_a = mine;
+    ws.items_b = mine + items_cap;
+    ws.jobs = mine + 2u * (size_t)items_cap;
+    ws.items_cap = items_cap;
+    ws.jobs_cap = jobs_cap;
+    const uint32_t n_entries = indexed_count(count, max_count);
+    const uint32_t n_chunks = (n_entries >> 6) + ((n_entries & 63u) != 0u ? 1u : 0u);
+    uint32_t casts = 0u;
+    for (uint32_t chunk = wave; chunk < n_chunks; chunk += n_waves) { /* wave-uniform */
+        const uint32_t j = chunk * 64u + lane;
+        const uint32_t i = j < n_entries ? index[j] : 0xffffffffu;
+        const bool active = j < n_entries && i < n_rays;
+        const Ray ray = active ? ray_from_abi(rays + i, sc.n_triangles, sc.n_spheres) : idle_ray();
+        const CastResult cr = cast_bfs(sc, ray, active, bl, ws); /* all lanes: those without a ray help */
+        if (active) store_hit(sc, ray, cr, hits + i);
+        casts += (uint32_t)__popcll(__ballot(active));
+    }
+    if (ray_count != nullptr && lane == 0u && casts != 0u) atomicAdd(ray_count, (unsigned long long)casts);
+}
+
 /* Camera::shoot(clip(x, y)) (main.rs:83-99, 1093-1096) with the per-frame basis of make_kernel_frame: the operations of the
  * Whitted kernels' primary ray (rt_kernels.hip) */
 __device__ __forceinline__ Ray primary_ray(const KernelFrame &fr, uint32_t col, uint32_t row) {
@@ -150,6 +234,28 @@ hipError_t launch_cast_rays_bfs(const KernelScene &sc, const rt_ray *rays, rt_hi
     if (n_rays == 0u || bfs_groups == 0u) return hipSuccess;
     hipLaunchKernelGGL(cast_rays_bfs_kernel, dim3(bfs_groups), dim3(RT_QUERY_BFS_WAVES * 64u), 0, stream, sc, rays, hits, n_rays, bfs_scratch,
                        items_cap, jobs_cap);
+    return hipGetLastError();
+}
+
+hipError_t launch_cast_rays_indexed(const KernelScene &sc, const rt_ray *rays, rt_hit *hits, uint32_t n_rays, const uint32_t *index,
+                                    const uint32_t *count, uint32_t max_count, unsigned long long *ray_count, bool wave_uniform, hipStream_t stream) {
+    if (n_rays == 0u || max_count == 0u) return hipSuccess;
+    const uint32_t groups = (uint32_t)(((uint64_t)max_count + RT_QUERY_THREADS - 1u) / RT_QUERY_THREADS);
+    if (wave_uniform)
+        hipLaunchKernelGGL(cast_rays_indexed_kernel<true>, dim3(groups), dim3(RT_QUERY_THREADS), 0, stream, sc, rays, hits, n_rays, index, count,
+                           max_count, ray_count);
+    else
+        hipLaunchKernelGGL(cast_rays_indexed_kernel<false>, dim3(groups), dim3(RT_QUERY_THREADS), 0, stream, sc, rays, hits, n_rays, index, count,
+                           max_count, ray_count);
+    return hipGetLastError();
+}
+
+hipError_t launch_cast_rays_indexed_bfs(const KernelScene &sc, const rt_ray *rays, rt_hit *hits, uint32_t n_rays, const uint32_t *index,
+                                        const uint32_t *count, uint32_t max_count, unsigned long long *ray_count, uint32_t *bfs_scratch,
+                                        uint32_t items_cap, uint32_t jobs_cap, uint32_t bfs_groups, hipStream_t stream) {
+    if (n_rays == 0u || max_count == 0u || bfs_groups == 0u) return hipSuccess;
+    hipLaunchKernelGGL(cast_rays_indexed_bfs_kernel, dim3(bfs_groups), dim3(RT_QUERY_BFS_WAVES * 64u), 0, stream, sc, rays, hits, n_rays, index, count,
+                       max_count, ray_count, bfs_scratch, items_cap, jobs_cap);
     return hipGetLastError();
 }
 

@@ -442,7 +442,8 @@ int rt_focus_rays(const rt_camera *camera, const rt_frame *frame, float focus, f
  * rt_trace_rays_distributed, rt_render_distributed, rt_focus_rays or rt_rng_download continues bit-exactly from where it left the
  * streams.  A generator that runs dry (every 256 words: about every 85 calls) generates its next block inside the kernel;
  * RT_AMD_SCATTER_PREPARE=1 runs the look-ahead pass ahead of the kernel instead (same bits; DESIGN.md §3.11 has the measurement).
- * Not covered: rt_multi_* variants; per-record cast counts (these two calls cast nothing); a device-side fold. */
+ * Not covered: rt_multi_* variants; per-record cast counts (these two calls cast nothing).  The device-side fold is
+ * rt_level_fold, in the level-loop block below. */
 
 #define RT_SCATTER_DIFFUSE 0u
 #define RT_SCATTER_REFLECTION 1u
@@ -474,6 +475,77 @@ int rt_scatter_hits_host(const rt_scene *scene, const rt_hit *h_hits, const rt_r
                          const uint32_t *h_rng_index, uint32_t *h_type, rt_ray *h_scattered, float *h_cosine);
 int rt_scatter_factors_host(const rt_scene *scene, const rt_hit *h_hits, const rt_ray *h_incoming, const uint32_t *h_type,
                             const rt_ray *h_next, const float *h_travel, size_t n, float *h_rgb);
+
+/* ---- level loop: select, indexed casts, the glue of one level and the fold, on the device ------------------------------
+
+ * What lies BETWEEN two queries when a caller runs distributed_ray_trace (main.rs:521-614) one level at a time: which records still have
+ * a ray, a cast of those alone, the masks of main.rs:556-613 as records the hit queries take, and the unwind — so that one epoch of the
+ * loop is a fixed sequence of stream-ordered calls: the host reads nothing back and does no arithmetic between the primary cast and the
+ * finished sample, and the result is rt_trace_rays_distributed's bit for bit (INTEGRATION.md writes the sequence out).  The primitives
+ * are generic: a caller's own stopping or re-sorting rule uses the same selection and the same indexed cast.
+ * Every pointer is a device pointer; every call is stream-ordered and asynchronous on hip_stream (NULL = default stream).  Records are
+ * the caller's and are validated, never trusted: a type above 2 belongs to no branch (RT_HIT_NONE is the dead record); a next hit whose
+ * kind is neither 0 nor 1 is a miss; an index at or beyond n is skipped.
+ * Checked before any device work, in this order: n >= 2^32 is RT_ERR_UNSUPPORTED (for rt_cast_rays_indexed max_count >= 2^32 as well);
+ * a null scene RT_ERR_INVALID_ARGUMENT (rt_cast_rays_indexed); n == 0 is RT_OK and launches nothing (so rt_select_records leaves *d_count
+ * as it was; for rt_cast_rays_indexed max_count == 0 as well); a null required pointer RT_ERR_INVALID_ARGUMENT.
+ * Any n below 2^32 runs in one launch per kernel (the record number is counted in 64 bits; no bands).
+ * Not covered: a Whitted (tree) fold; rt_multi_* forms; indexed forms of the hit and scatter queries, which already skip "no hit"
+ * records; per-record cast counts. */
+
+/* Stable selection: d_index[0 .. *d_count) receives, ascending, every i with d_flags[i] != 0 (any non-zero byte); *d_count (one u32) is
+ * overwritten with their number and never goes to the host.  d_index has room for n words; entries at and beyond the count are
+ * unspecified.  Records that were neighbours stay neighbours: what keeps the 64 rays of a wave together.  The same flags always give
+ * the same output: two kernels (block totals, then the placement: a workgroup's base is the sum of the totals before it), no ordering by
+ * atomics.  The totals live in a 4 KB scratch per (device, stream), allocated by the first call on that stream — which therefore must not
+ * be captured (RT_ERR_UNSUPPORTED if it is); every later call on the stream may be captured into a HIP graph.  rt_post_release frees
+ * the scratch of the current device. */
+int rt_select_records(const unsigned char *d_flags, size_t n, uint32_t *d_index, uint32_t *d_count, void *hip_stream);
+
+/* World::cast through an index list: for j < min(*d_count, max_count), with k = d_index[j]: d_hits[k] = World::cast(d_rays[k]), bit for
+ * bit what rt_cast_rays writes for that ray, NaN distances included.  Records that are not named are not written; an index >= n is
+ * skipped (nothing is read or cast for it).  d_rays and d_hits hold n records; max_count is the host's upper bound on the list's length
+ * (typically n): it sizes the grid, and waves beyond the device-side count leave at once.  A wave takes 64 consecutive index entries.
+ * An index named twice is cast twice and written twice, with the same bits.  d_ray_count: NULL or one u64, the number of casts actually
+ * made is ADDED.  Routes and graph capture as rt_cast_rays: pair-wise, or wave-uniform under RT_AMD_QUERY_WAVE_UNIFORM=1, no workspace;
+ * a scene walked breadth-first takes the breadth-first walk with the record lists of the per-(scene, stream) workspace (make one
+ * uncaptured call on the stream first, with at least as large a max_count; a call captured before that uses the pair-wise kernel). */
+int rt_cast_rays_indexed(const rt_scene *scene, const rt_ray *d_rays, size_t n, const uint32_t *d_index, const uint32_t *d_count,
+                         size_t max_count, rt_hit *d_hits, unsigned long long *d_ray_count, void *hip_stream);
+
+/* The glue of one level.  With type and cosine as rt_scatter_hits wrote them:
+ *     alive(i) = d_type[i] != RT_HIT_NONE && !(d_cosine[i] <= 0)      (a NaN cosine goes on, as in the reference: main.rs:559, 578, 597)
+ *     dr(i) = alive && d_type[i] <= 1 (Diffuse, Reflection)           fr(i) = alive && d_type[i] == 2 (Refraction)
+ * "no hit" is kind RT_HIT_NONE with every other word 0, as rt_cast_rays writes a miss.  Each call is one element-wise kernel, needs no
+ * workspace and may be captured at once.  All pointers are required unless said otherwise; n records each.
+ *   rt_level_split   after rt_scatter_hits: d_hits_reflect[i] = d_hits[i] where dr, d_hits_refract[i] = d_hits[i] where fr, "no hit"
+ *                    elsewhere — the operands of rt_reflect_rays and rt_refract_rays (with d_scattered as their incoming rays)
+ *   rt_level_join    after those two: d_next[i] = d_reflected[i] where dr, d_escape[i] where fr && d_refr_kind[i] == 0 (Escaped), all-zero
+ *                    words elsewhere; d_flags[i] = 1 exactly where such a ray exists, else 0; d_next_hits[i] is preset to "no hit" for
+ *                    every i — rt_select_records(d_flags) + rt_cast_rays_indexed(d_next -> d_next_hits) then overwrite the records cast
+ *   rt_level_close   after the indexed cast: d_hits_missed[i] = d_hits[i] where dr and d_next_hits[i].kind is neither 0 nor 1, "no hit"
+ *                    elsewhere — the operand of get_shade(&scattered_hit) (main.rs:573, 592; incoming rays: d_scattered)
+ *   rt_level_fold    from the deepest level back, d_value (3 floats per record) holding the value of the level below (at the deepest:
+ *                    rt_shade_hits of the last hits) and receiving this level's, in place:
+ *                        !alive, or a type above 2                black                                       (main.rs:560, 579, 598)
+ *                        type <= 1, next kind 0 or 1              s = value * factor; shade_next + (s - shade_next) * 0.5 per channel
+ *                        type <= 1, otherwise                     shade_missed                                (main.rs:573, 592)
+ *                        type == 2, next kind 0 or 1              (value + shade_next) * factor[0] in all three channels (main.rs:605)
+ *                        type == 2, otherwise                     black                                       (main.rs:607-611)
+ *                    d_factor: rt_scatter_factors; d_shade_next: rt_shade_hits(d_next_hits, d_next); d_shade_missed:
+ *                    rt_shade_hits(d_hits_missed, d_scattered).  Every operation rounds to f32, none is fused: the operations and
+ *                    their order are those of rt_trace_rays_distributed's unwind
+ *   rt_level_finish  main.rs:1157-1165: valid = all three channels of d_value[i] are is_normal; d_valid[i] = valid (one byte; may be NULL);
+ *                    d_accum[3*i + c] += d_value[3*i + c] where valid (may be NULL).  Neither: RT_ERR_INVALID_ARGUMENT */
+int rt_level_split(const rt_hit *d_hits, const uint32_t *d_type, const float *d_cosine, size_t n, rt_hit *d_hits_reflect, rt_hit *d_hits_refract,
+                   void *hip_stream);
+int rt_level_join(const uint32_t *d_type, const float *d_cosine, const rt_ray *d_reflected, const uint32_t *d_refr_kind, const rt_ray *d_escape,
+                  size_t n, rt_ray *d_next, rt_hit *d_next_hits, unsigned char *d_flags, void *hip_stream);
+int rt_level_close(const rt_hit *d_hits, const uint32_t *d_type, const float *d_cosine, const rt_hit *d_next_hits, size_t n, rt_hit *d_hits_missed,
+                   void *hip_stream);
+int rt_level_fold(const uint32_t *d_type, const float *d_cosine, const rt_hit *d_next_hits, const float *d_factor, const float *d_shade_next,
+                  const float *d_shade_missed, size_t n, float *d_value, void *hip_stream);
+int rt_level_finish(const float *d_value, size_t n, float *d_accum, unsigned char *d_valid, void *hip_stream);
 
 /* ---- several GPUs from one process (SURVEY §8e without Python or MPI) -------------------
  * Image rows are interleaved over the entries of `devices` exactly as homework-18-graphics-raytracer_amd/dist.py interleaves
