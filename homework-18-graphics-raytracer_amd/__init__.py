@@ -13,6 +13,7 @@ reference's host-side names on top of them:
     trace_rays_distributed         src/main.rs:521-614 (distributed_ray_trace), on caller-supplied rays
     shade_hits / reflect_rays / refract_rays   src/main.rs:407-464, 328-341, 343-405 (get_shade, get_reflect, get_refract), on caller-supplied hits
     trace_rays_distributed_levels  src/main.rs:521-614 again, one level at a time from the queries and the level-loop calls
+    trace_rays_levels              src/main.rs:466-519 again, one level of the tree at a time from the queries and the tree-loop calls
     post_process / write_to_file   src/main.rs:748-776
 
 PyTorch is used only for device memory, streams and torch.distributed.
@@ -30,7 +31,7 @@ from ._capi import Camera, Frame, Light, Material, RtError, SceneDesc, Sphere, T
 
 __all__ = [
     "World", "ObjectProxy", "Scene", "Camera", "Frame", "Material", "Light", "RtError", "reference_world",
-    "reference_camera", "render_whitted", "render_whitted_numpy", "make_rays", "cast_rays", "Hits", "camera_rays", "cast_rays_numpy", "trace_rays", "trace_rays_numpy", "shade_hits", "reflect_rays", "refract_rays", "Refractions", "ESCAPED", "INFINITE", "TRAPPED", "HIT_NONE", "shade_hits_numpy", "refract_rays_numpy", "scatter_hits", "scatter_factors", "Scatters", "DIFFUSE", "REFLECTION", "REFRACTION", "scatter_hits_numpy", "scatter_factors_numpy", "select_records", "cast_rays_indexed", "level_split", "level_join", "level_close", "level_fold", "level_finish", "trace_rays_distributed_levels", "Rng", "focus_rays", "trace_rays_distributed", "trace_rays_distributed_numpy", "render_distributed", "render_distributed_numpy", "set_option", "options", "post_process_device", "encode_srgb8_device", "post_process", "encode_srgb8", "write_to_file",
+    "reference_camera", "render_whitted", "render_whitted_numpy", "make_rays", "cast_rays", "Hits", "camera_rays", "cast_rays_numpy", "trace_rays", "trace_rays_numpy", "shade_hits", "reflect_rays", "refract_rays", "Refractions", "ESCAPED", "INFINITE", "TRAPPED", "HIT_NONE", "shade_hits_numpy", "refract_rays_numpy", "scatter_hits", "scatter_factors", "Scatters", "DIFFUSE", "REFLECTION", "REFRACTION", "scatter_hits_numpy", "scatter_factors_numpy", "select_records", "cast_rays_indexed", "level_split", "level_join", "level_close", "level_fold", "level_finish", "trace_rays_distributed_levels", "tree_gate", "tree_split", "tree_spawn", "tree_gather", "tree_fold", "trace_rays_levels", "default_level_capacity", "Rng", "focus_rays", "trace_rays_distributed", "trace_rays_distributed_numpy", "render_distributed", "render_distributed_numpy", "set_option", "options", "post_process_device", "encode_srgb8_device", "post_process", "encode_srgb8", "write_to_file",
     "DEFAULT_OBJ",
 ]
 
@@ -1046,6 +1047,301 @@ def trace_rays_distributed_levels(scene: Scene, rays, max_depth: int, rng: Rng, 
         if accum is not None or valid is not None:  # samples alone: the folded value is the sample, nothing to filter into
             level_finish(v, accum, None if valid is None else valid[e], stream=s)
     return accum if accum is not None else samples
+
+
+# ---- tree loop: ray_trace level by level — gate, split, spawn, gather and fold (include/rt_amd.h rt_tree_gate ... rt_tree_fold) ----
+
+
+def _count_word(t, name):
+    import torch
+
+    if t is not None:
+        _column(t, torch.int32, 1, name)
+
+
+def _floats(t, shape, name):
+    import torch
+
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == tuple(shape)):
+        raise ValueError(f"{name} must be a contiguous {tuple(shape)} float32 CUDA tensor")
+
+
+def tree_gate(contribution, count=None, out_flags=None, out_hits=None, stream=None):
+    """The entry check of ray_trace on the roots (rt_tree_gate, main.rs:469): returns (flags, hits) — ``flags`` (N,) uint8, 1 where
+    j < count and not contribution[j] < 0.001 (NaN passes), ``hits`` (N, 13) int32 preset to "no hit": select_records(flags) +
+    cast_rays_indexed(rays -> hits) follow.  ``count``: a 1-element int32 CUDA tensor, or None for N."""
+    import torch
+
+    if not (torch.is_tensor(contribution) and contribution.dim() == 1):
+        raise ValueError("contribution must be a contiguous (N,) float32 CUDA tensor")
+    n = contribution.shape[0]
+    _floats(contribution, (n,), "contribution")
+    _count_word(count, "count")
+    if out_flags is None:
+        out_flags = torch.empty((n,), dtype=torch.uint8, device=contribution.device)
+    if out_hits is None:
+        out_hits = torch.empty((n, 13), dtype=torch.int32, device=contribution.device)
+    _column(out_flags, torch.uint8, n, "out_flags")
+    _records(out_hits, 13, "out_hits")
+    if out_hits.shape[0] != n:
+        raise ValueError("out_hits must have one record per root")
+    _capi.check(_capi.amd_lib().rt_tree_gate(_p(contribution), n, _p(count), _p(out_flags), _p(out_hits), _stream_ptr(stream)))
+    return out_flags, out_hits
+
+
+def tree_split(scene: Scene, hits, contribution, depth_left: int, count=None, out_shade=None, out_reflect=None, out_refract=None,
+               out_weights=None, stream=None):
+    """The weights and threshold gates of main.rs:478-504 (rt_tree_split): returns (hits_shade, hits_reflect, hits_refract, weights) —
+    the level's hits where get_shade, get_reflect and get_refract are wanted ("no hit" elsewhere), the operands of shade_hits,
+    reflect_rays and refract_rays with the level's rays; ``weights`` (N, 4) float32 = (sc, rc, fc, opaque_decay), zeros where the record
+    is not live.  ``depth_left``: TraceState.depth of the level."""
+    import torch
+
+    records = _hit_records(hits)
+    n = records.shape[0]
+    _floats(contribution, (n,), "contribution")
+    _count_word(count, "count")
+    outs = []
+    for t in (out_shade, out_reflect, out_refract):
+        if t is None:
+            t = torch.empty((n, 13), dtype=torch.int32, device=records.device)
+        _records(t, 13, "out")
+        if t.shape[0] != n:
+            raise ValueError("out must have one record per hit")
+        outs.append(t)
+    if out_weights is None:
+        out_weights = torch.empty((n, 4), dtype=torch.float32, device=records.device)
+    _floats(out_weights, (n, 4), "out_weights")
+    _capi.check(_capi.amd_lib().rt_tree_split(scene._h, _p(records), _p(contribution), n, _p(count), int(depth_left), _p(outs[0]), _p(outs[1]),
+                                              _p(outs[2]), _p(out_weights), _stream_ptr(stream)))
+    return outs[0], outs[1], outs[2], out_weights
+
+
+def tree_spawn(hits_reflect, refr_kind, out_flags=None, out_child_values=None, stream=None):
+    """The child candidates of a level (rt_tree_spawn): returns (flags, child_values) — ``flags`` (2N,) uint8, entry 2j the reflection
+    child of record j (hits_reflect[j] is a hit), entry 2j + 1 its refraction child (refr_kind[j] == ESCAPED); ``child_values``
+    (2N, 3) float32, zeroed, which the children's tree_fold overwrites.  select_records(flags) + tree_gather follow."""
+    import torch
+
+    records = _hit_records(hits_reflect)
+    n = records.shape[0]
+    _column(refr_kind, torch.int32, n, "refr_kind")
+    if out_flags is None:
+        out_flags = torch.empty((2 * n,), dtype=torch.uint8, device=records.device)
+    if out_child_values is None:
+        out_child_values = torch.empty((2 * n, 3), dtype=torch.float32, device=records.device)
+    _column(out_flags, torch.uint8, 2 * n, "out_flags")
+    _floats(out_child_values, (2 * n, 3), "out_child_values")
+    _capi.check(_capi.amd_lib().rt_tree_spawn(_p(records), _p(refr_kind), n, _p(out_flags), _p(out_child_values), _stream_ptr(stream)))
+    return out_flags, out_child_values
+
+
+def tree_gather(index, count, reflected, escape, contribution, weights, overflow, max_count=None, out_rays=None, out_contribution=None,
+                out_parent=None, out_count=None, stream=None):
+    """The next level from the selected candidates (rt_tree_gather): returns (rays, contribution, parent, count) of the children —
+    child j comes from candidate c = index[j]: the reflected ray of record c >> 1 when c is even, its escape ray when odd; its
+    contribution is the parent's times rc or fc, its parent slot c.  ``max_count``: the capacity of the child arrays (default: that of
+    ``out_rays``, or 2N); candidates beyond it are dropped and their number is ADDED to ``overflow`` (a 1-element int32 CUDA tensor)."""
+    import torch
+
+    _records(reflected, 11, "reflected")
+    n = reflected.shape[0]
+    _records(escape, 11, "escape")
+    if escape.shape[0] != n:
+        raise ValueError("reflected and escape must have one record each per record")
+    _floats(contribution, (n,), "contribution")
+    _floats(weights, (n, 4), "weights")
+    if not (torch.is_tensor(index) and index.is_cuda and index.dtype == torch.int32 and index.is_contiguous() and index.dim() == 1):
+        raise ValueError("index must be a contiguous (M,) int32 CUDA tensor")
+    _count_word(count, "count")
+    _count_word(overflow, "overflow")
+    if count is None or overflow is None:
+        raise ValueError("count and overflow are required")
+    if max_count is None:
+        max_count = out_rays.shape[0] if out_rays is not None else 2 * n
+    m = int(max_count)
+    if not 0 <= min(m, 2 * n) <= index.shape[0]:
+        raise ValueError("index must hold every candidate that can be kept")
+    dev = reflected.device
+    if out_rays is None:
+        out_rays = torch.empty((m, 11), dtype=torch.int32, device=dev)
+    if out_contribution is None:
+        out_contribution = torch.empty((m,), dtype=torch.float32, device=dev)
+    if out_parent is None:
+        out_parent = torch.empty((m,), dtype=torch.int32, device=dev)
+    if out_count is None:
+        out_count = torch.empty((1,), dtype=torch.int32, device=dev)
+    _records(out_rays, 11, "out_rays")
+    if out_rays.shape[0] < m or out_contribution.shape[0] < m or out_parent.shape[0] < m:
+        raise ValueError("the child arrays must hold max_count records")
+    _floats(out_contribution, out_contribution.shape[:1], "out_contribution")
+    _column(out_parent, torch.int32, out_parent.shape[0], "out_parent")
+    _count_word(out_count, "out_count")
+    if out_count.data_ptr() == count.data_ptr():
+        raise ValueError("out_count must not alias count")
+    _capi.check(_capi.amd_lib().rt_tree_gather(_p(index), _p(count), m, _p(reflected), _p(escape), _p(contribution), _p(weights), n, _p(out_rays),
+                                               _p(out_contribution), _p(out_parent), _p(out_count), _p(overflow), _stream_ptr(stream)))
+    return out_rays, out_contribution, out_parent, out_count
+
+
+def tree_fold(hits, depth_left: int, shade, out, count=None, weights=None, refr_kind=None, travel=None, child_values=None, parent=None,
+              stream=None):
+    """main.rs:516-518 on one level (rt_tree_fold), from the deepest back: the value of every live record j < count — black, the shade
+    (depth_left <= 0) or (shade * sc + reflection * rc) + refraction * fc with the children's values of ``child_values`` — is written
+    to ``out[parent[j]]``, or to ``out[j]`` when ``parent`` is None (the roots).  ``out``: an (M, 3) float32 CUDA tensor, the parent
+    level's child_values or the result; a parent at or beyond M writes nothing."""
+    import torch
+
+    records = _hit_records(hits)
+    n = records.shape[0]
+    _rgb(shade, n, "shade")
+    _count_word(count, "count")
+    if not (torch.is_tensor(out) and out.dim() == 2):
+        raise ValueError("out must be a contiguous (M, 3) float32 CUDA tensor")
+    _rgb(out, out.shape[0], "out")
+    if int(depth_left) > 0 and (weights is None or refr_kind is None or travel is None or child_values is None):
+        raise ValueError("weights, refr_kind, travel and child_values are required when depth_left > 0")
+    if weights is not None:
+        _floats(weights, (n, 4), "weights")
+    if refr_kind is not None:
+        _column(refr_kind, torch.int32, n, "refr_kind")
+    if travel is not None:
+        _column(travel, torch.float32, n, "travel")
+    if child_values is not None:
+        _floats(child_values, (2 * n, 3), "child_values")
+    if parent is not None:
+        _column(parent, torch.int32, n, "parent")
+    _capi.check(_capi.amd_lib().rt_tree_fold(_p(records), _p(count), n, int(depth_left), _p(shade), _p(weights), _p(refr_kind), _p(travel),
+                                             _p(child_values), _p(parent), _p(out), out.shape[0], _stream_ptr(stream)))
+    return out
+
+
+# the default capacity of level L is min(n * 2^L, ceil(LEVEL_CAPACITY_FACTOR * n)): DESIGN.md §3.13 has the measured level shares
+LEVEL_CAPACITY_FACTOR = 1.5
+
+
+def default_level_capacity(n: int, level: int) -> int:
+    """Records trace_rays_levels provides for level ``level`` (0: the roots) of ``n`` rays when no ``level_capacity`` is given."""
+    import math
+
+    return min(n << min(level, 32), int(math.ceil(LEVEL_CAPACITY_FACTOR * n)))
+
+
+def trace_rays_levels(scene: Scene, rays, max_depth: int, contribution=1.0, out=None, ray_count=None, stream=None, level_capacity=None,
+                      check: bool = True, overflow=None, level_counts=None):
+    """trace_rays — the same rays, depth and contribution, the same values and cast count, bit for bit — written one level of the
+    recursion tree at a time from the public calls alone: the executable form of the sequence in INTEGRATION.md, to be copied and changed
+    (a stopping rule, a weighting, a re-sort between levels).  ``contribution``: a float, or an (N,) float32 CUDA tensor of per-ray root
+    contributions.  ``level_capacity``: the records provided for level L >= 1 — an int, a callable L -> int, or None for
+    default_level_capacity; children that do not fit are dropped (their parents see black) and counted into the overflow word.
+    ``check=True`` reads that word once, after the last call, and raises RtError if it is not zero; ``check=False`` reads nothing back
+    and does not synchronise — the form for graph capture.  ``overflow``: a 1-element int32 CUDA tensor the dropped children are ADDED to
+    (one is made and zeroed if None); ``level_counts``: a (max(max_depth, 0) + 1,) int32 CUDA tensor that receives the number of records
+    cast per level.  Every buffer is allocated once, up front; after that the function only enqueues library calls on ``stream``.
+    (Being a sequence of calls it may not be captured before select_records has run once on the stream.)"""
+    import torch
+
+    _records(rays, 11, "rays")
+    n = rays.shape[0]
+    dev = rays.device
+    if out is None:
+        out = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    _rgb(out, n, "out")
+    _count_ptr(ray_count)
+    _count_word(overflow, "overflow")
+    if max_depth > _capi.RT_MAX_DEPTH:
+        raise RtError(-5, f"max_depth above RT_MAX_DEPTH ({_capi.RT_MAX_DEPTH})")
+    depth = max(int(max_depth), 0)
+    if level_counts is not None:
+        _column(level_counts, torch.int32, depth + 1, "level_counts")
+    if torch.is_tensor(contribution):
+        _floats(contribution, (n,), "contribution")
+    if n == 0:
+        return out
+    caps = [n]
+    for level in range(1, depth + 1):
+        if level_capacity is None:
+            cap = default_level_capacity(n, level)
+        elif callable(level_capacity):
+            cap = int(level_capacity(level))
+        else:
+            cap = int(level_capacity)
+        if cap < 0:
+            raise ValueError("level_capacity must not be negative")
+        caps.append(min(cap, 2 * caps[-1]))  # a level cannot hold more than two children per parent record
+    if 2 * max(caps) >= 1 << 32:
+        raise RtError(-5, "a level of 2^31 records or more")
+    top = max(caps)
+    s = stream
+
+    def new(shape, dtype):
+        return torch.empty(shape, dtype=dtype, device=dev)
+
+    # allocated (and the fills enqueued) with `stream` as torch's current stream: the caching allocator then ties the blocks to it
+    with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+        i32, f32, u8 = torch.int32, torch.float32, torch.uint8
+        # per level: what the fold needs
+        hits = [new((c, 13), i32) for c in caps]
+        shade = [new((c, 3), f32) for c in caps]
+        weights = [new((c, 4), f32) for c in caps]
+        refr_kind = [new((c,), i32) for c in caps[:depth]]
+        travel = [new((c,), f32) for c in caps[:depth]]
+        child_values = [new((2 * c, 3), f32) for c in caps[:depth]]
+        parent = [None] + [new((c,), i32) for c in caps[1:]]
+        counts = level_counts if level_counts is not None else new((depth + 1,), i32)
+        count = [counts[k:k + 1] for k in range(depth + 1)]  # count[0]: the roots that passed the gate; the root arrays are full (n)
+        # shared by the levels: the fold needs none of it
+        h_shade, h_reflect, h_refract = new((top, 13), i32), new((top, 13), i32), new((top, 13), i32)
+        reflected, escape = new((top, 11), i32), new((top, 11), i32)
+        level_rays = [None, new((top, 11), i32), new((top, 11), i32)]  # children's rays and contributions, in turn
+        level_contribution = [None, new((top,), f32), new((top,), f32)]
+        flags, index, selected = new((2 * top,), u8), new((2 * top,), i32), new((1,), i32)
+        identity, n_all = new((top,), i32), new((1,), i32)
+        if torch.is_tensor(contribution):
+            root_contribution = contribution
+        else:
+            root_contribution = new((n,), f32)
+            root_contribution.fill_(float(contribution))
+        if overflow is None:
+            overflow = new((1,), i32)
+            overflow.zero_()
+        counts.zero_()  # a level without room is not visited by any kernel: its count stays 0
+        flags[:top].fill_(1)
+    select_records(flags[:top], identity, n_all, stream=s)  # 0 .. top-1: the child levels are cast through it with their own counts
+
+    cur_rays, cur_contribution = rays, root_contribution
+    for k in range(depth + 1):
+        c, left = caps[k], depth - k
+        live = None if k == 0 else count[k]
+        if k == 0:
+            tree_gate(cur_contribution, None, flags[:c], hits[0], stream=s)
+            select_records(flags[:c], index[:c], count[0], stream=s)
+            cast_rays_indexed(scene, cur_rays, index[:c], count[0], hits[0], ray_count=ray_count, stream=s)
+        else:
+            cast_rays_indexed(scene, cur_rays[:c], identity[:c], count[k], hits[k], ray_count=ray_count, stream=s)
+        tree_split(scene, hits[k], cur_contribution[:c], left, live, h_shade[:c], h_reflect[:c], h_refract[:c], weights[k], stream=s)
+        shade_hits(scene, h_shade[:c], cur_rays[:c], out=shade[k], ray_count=ray_count, stream=s)
+        if left > 0:
+            reflect_rays(h_reflect[:c], cur_rays[:c], out=reflected[:c], stream=s)
+            refract_rays(scene, h_refract[:c], cur_rays[:c], 100.0, ray_count=ray_count, stream=s,
+                         out=Refractions(refr_kind[k], travel[k], escape[:c]))
+            tree_spawn(h_reflect[:c], refr_kind[k], flags[:2 * c], child_values[k], stream=s)
+            select_records(flags[:2 * c], index[:2 * c], selected, stream=s)
+            nxt = 1 + (k & 1)
+            tree_gather(index[:2 * c], selected, reflected[:c], escape[:c], cur_contribution[:c], weights[k], overflow, caps[k + 1],
+                        level_rays[nxt], level_contribution[nxt], parent[k + 1], count[k + 1], stream=s)
+            cur_rays, cur_contribution = level_rays[nxt], level_contribution[nxt]
+    for k in reversed(range(depth + 1)):
+        left = depth - k
+        tree_fold(hits[k], left, shade[k], out if k == 0 else child_values[k - 1], None if k == 0 else count[k],
+                  weights[k] if left > 0 else None, refr_kind[k] if left > 0 else None, travel[k] if left > 0 else None,
+                  child_values[k] if left > 0 else None, parent[k], stream=s)
+    if check:
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+            dropped = int(overflow.item())  # the one readback: it waits for the loop
+        if dropped != 0:
+            raise RtError(-5, f"trace_rays_levels: {dropped} child records did not fit their level's capacity (level_capacity)")
+    return out
 
 
 

@@ -11,6 +11,7 @@
  *   rt_api_query.hip   rt_cast_rays / rt_camera_rays, the hit queries rt_shade_hits / rt_reflect_rays / rt_refract_rays, the scatter
  *                      queries rt_scatter_hits / rt_scatter_factors and the level loop's rt_select_records / rt_cast_rays_indexed /
  *                      rt_level_*
+ *   rt_tree_query.hip  the tree loop's rt_tree_*: kernels and entry points in one unit
  */
 #ifndef RT_API_INTERNAL_H
 #define RT_API_INTERNAL_H

@@ -490,8 +490,8 @@ int rt_scatter_factors_host(const rt_scene *scene, const rt_hit *h_hits, const r
  * a null scene RT_ERR_INVALID_ARGUMENT (rt_cast_rays_indexed); n == 0 is RT_OK and launches nothing (so rt_select_records leaves *d_count
  * as it was; for rt_cast_rays_indexed max_count == 0 as well); a null required pointer RT_ERR_INVALID_ARGUMENT.
  * Any n below 2^32 runs in one launch per kernel (the record number is counted in 64 bits; no bands).
- * Not covered: a Whitted (tree) fold; rt_multi_* forms; indexed forms of the hit and scatter queries, which already skip "no hit"
- * records; per-record cast counts. */
+ * Not covered: rt_multi_* forms; indexed forms of the hit and scatter queries, which already skip "no hit" records; per-record cast
+ * counts.  The Whitted recursion, a tree and not a chain, has its own glue and fold in the tree-loop block below. */
 
 /* Stable selection: d_index[0 .. *d_count) receives, ascending, every i with d_flags[i] != 0 (any non-zero byte); *d_count (one u32) is
  * overwritten with their number and never goes to the host.  d_index has room for n words; entries at and beyond the count are
@@ -546,6 +546,82 @@ int rt_level_close(const rt_hit *d_hits, const uint32_t *d_type, const float *d_
 int rt_level_fold(const uint32_t *d_type, const float *d_cosine, const rt_hit *d_next_hits, const float *d_factor, const float *d_shade_next,
                   const float *d_shade_missed, size_t n, float *d_value, void *hip_stream);
 int rt_level_finish(const float *d_value, size_t n, float *d_accum, unsigned char *d_valid, void *hip_stream);
+
+/* ---- tree loop: ray_trace level by level on the device — gate, split, spawn, gather and fold ------------------------------
+
+ * What lies BETWEEN two queries when a caller runs the Whitted integrator ray_trace (main.rs:466-519) one level at a time.  The
+ * stochastic loop above is a chain: one successor per record.  ray_trace is a tree with up to two children per node (the reflected
+ * ray and the escape ray of the refraction), so it needs three things the chain never did: the material weights and threshold gates
+ * of main.rs:480-504 as a query, the compaction of 2n child candidates into the next level with a link to the parent's slot, and a
+ * fold that hands each child's value to that slot.  rt_select_records and rt_cast_rays_indexed are used as they are.  One level is
+ *     [roots] rt_tree_gate -> rt_select_records -> rt_cast_rays_indexed        [children] rt_cast_rays_indexed (identity list, level count)
+ *     rt_tree_split -> rt_shade_hits, rt_reflect_rays, rt_refract_rays(100.0)   (incoming rays: the level's rays)
+ *     rt_tree_spawn -> rt_select_records(2n flags) -> rt_tree_gather            (not at depth_left <= 0)
+ * and, from the deepest level back, rt_tree_fold.  The host reads nothing back and does no arithmetic, and values and cast count are
+ * rt_trace_rays' bit for bit (INTEGRATION.md writes the sequence out; DESIGN.md §3.13 says why the bits are the same).
+ * Rules of the block: every pointer is a device pointer; every call is stream-ordered and asynchronous on hip_stream (NULL = default
+ * stream), is one element-wise kernel with one record per lane, uses no workspace and may be captured into a HIP graph at once.  n is
+ * the CAPACITY of the level's arrays; d_count is one device u32 holding the number of live records (a count above n is read as n), it
+ * never goes to the host, and a NULL d_count means n.  Records at or beyond the count are dead: they are read as "no hit" and written
+ * as "no hit", zero or not at all, as said per call.  Records are the caller's and are validated, never trusted: a hit whose kind is
+ * neither 0 nor 1 is "no hit", and so is (rt_tree_split) one whose object_index >= n_materials.  "no hit" is kind RT_HIT_NONE with
+ * every other word 0.  Checked before any device work, in this order: the limit on n (per call, below) is RT_ERR_UNSUPPORTED; a null
+ * scene RT_ERR_INVALID_ARGUMENT (rt_tree_split); n == 0 is RT_OK and launches nothing; a null required pointer RT_ERR_INVALID_ARGUMENT.
+ * Not covered: rt_multi_* forms; per-record cast counts. */
+
+/* The entry check of main.rs:469 on the roots: d_flags[j] = j < count && !(d_contribution[j] < 0.001f) — a NaN contribution passes, as
+ * in the reference — and d_hits[j] is preset to "no hit" for every j < n; rt_select_records(d_flags) + rt_cast_rays_indexed then cast the
+ * roots that passed.  Child levels need no gate: a child exists only where contribution * weight passed the threshold.
+ * n >= 2^32 is RT_ERR_UNSUPPORTED. */
+int rt_tree_gate(const float *d_contribution, size_t n, const uint32_t *d_count, unsigned char *d_flags, rt_hit *d_hits, void *hip_stream);
+
+/* main.rs:478-504 up to the three calls.  With the hit's material (material.approx(hit.at)), in f32 and in the reference's order:
+ *     sc = (1 - shiness) * (1 - transparency)     rc = shiness * (1 - transparency)     fc = transparency
+ * and c = d_contribution[j], a live record (j < count and a valid hit) copies its hit to
+ *     d_hits_shade[j]    where c * sc >= 0.001f                           the operand of rt_shade_hits
+ *     d_hits_reflect[j]  where depth_left > 0 && c * rc >= 0.001f         the operand of rt_reflect_rays
+ *     d_hits_refract[j]  where depth_left > 0 && c * fc >  0.001f         the operand of rt_refract_rays (strict, main.rs:504)
+ * and everywhere else, for every j < n, the three outputs are "no hit".  d_weights[4*j ..] = (sc, rc, fc, opaque_decay), zeros for a
+ * record that is not live.  depth_left: TraceState.depth of the level, uniform.  n >= 2^32 is RT_ERR_UNSUPPORTED. */
+int rt_tree_split(const rt_scene *scene, const rt_hit *d_hits, const float *d_contribution, size_t n, const uint32_t *d_count, int32_t depth_left,
+                  rt_hit *d_hits_shade, rt_hit *d_hits_reflect, rt_hit *d_hits_refract, float *d_weights, void *hip_stream);
+
+/* The child candidates of a level, two per record: d_flags[2*j] = d_hits_reflect[j] is a hit (the reflection child), d_flags[2*j + 1] =
+ * d_refr_kind[j] == 0 (Escaped: the refraction child); d_child_values (6 floats per record: 3 per candidate) is zeroed — black until the
+ * child's fold overwrites its slot.  rt_select_records(d_flags, 2n) then lists the candidates ascending: siblings stay adjacent and
+ * children stay in their parents' order, which keeps a wave's rays together.  n >= 2^31 is RT_ERR_UNSUPPORTED (2n stays below 2^32). */
+int rt_tree_spawn(const rt_hit *d_hits_reflect, const uint32_t *d_refr_kind, size_t n, unsigned char *d_flags, float *d_child_values,
+                  void *hip_stream);
+
+/* The next level from the selected candidates.  For j < min(*d_count, max_count), with c = d_index[j], p = c >> 1, slot = c & 1:
+ *     d_child_rays[j] = slot ? d_escape[p] : d_reflected[p]
+ *     d_child_contribution[j] = d_contribution[p] * (slot ? fc : rc) of d_weights[4*p ..]    (one f32 multiply: TraceState::nested)
+ *     d_child_parent[j] = c
+ * *d_child_count = min(*d_count, max_count), and the number of candidates that did not fit is ADDED to *d_overflow (one u32): their
+ * parents see a black child and the call stays memory-safe.  max_count is the capacity of the child arrays; n the parents' capacity
+ * (d_index comes from rt_select_records over 2n flags: it holds at least min(max_count, 2n) entries).  An index c >= 2n names no candidate: its record is an all-zero ray with
+ * contribution 0 and parent 0xffffffff, which folds into no slot.  d_child_count must not alias d_count.  Checked first:
+ * n >= 2^31 or max_count >= 2^32 is RT_ERR_UNSUPPORTED.  With max_count == 0 the child arrays may be NULL. */
+int rt_tree_gather(const uint32_t *d_index, const uint32_t *d_count, size_t max_count, const rt_ray *d_reflected, const rt_ray *d_escape,
+                   const float *d_contribution, const float *d_weights, size_t n, rt_ray *d_child_rays, float *d_child_contribution,
+                   uint32_t *d_child_parent, uint32_t *d_child_count, uint32_t *d_overflow, void *hip_stream);
+
+/* main.rs:516-518 on one level, from the deepest back.  For every j < count the value is
+ *     not live (a miss, a gated root)     +0 black                                                       (main.rs:470, 475)
+ *     depth_left <= 0                     d_shade[3*j ..] as rt_shade_hits wrote it, NOT multiplied by sc  (main.rs:488-490)
+ *     otherwise                           (shade * sc + reflection * rc) + refraction * fc               (main.rs:516-518)
+ * with reflection = d_child_values[6*j ..], refraction = d_child_values[6*j + 3 ..] * powf(opaque_decay, d_travel[j]) where
+ * d_refr_kind[j] == 0 and black, without the multiply, elsewhere (main.rs:508-510); the powf is the library's deterministic one
+ * (rt_math_eval_host(RT_MATH_POW)).  Every operation rounds to f32, none is fused, and the association is rt_trace_rays'.  A shade that
+ * was not wanted is black and is still multiplied by sc.  Live is j < count and d_hits[j].kind <= 1 (a hit rt_tree_split rejected for its
+ * object_index has black shade and zero weights: +0 either way).  The value goes to d_out[3*d_parent[j] + c] — d_out being the parent
+ * level's d_child_values, 3 floats per candidate — or, with d_parent == NULL (the roots), to d_out[3*j + c].  n_out is the number of
+ * 3-float slots d_out holds: a parent at or beyond it writes nothing.  Each slot has one writer: no atomics, and the result does not
+ * depend on scheduling.  Dead records write nothing.  d_weights, d_refr_kind, d_travel and d_child_values may be NULL when
+ * depth_left <= 0.  n >= 2^32 is RT_ERR_UNSUPPORTED. */
+int rt_tree_fold(const rt_hit *d_hits, const uint32_t *d_count, size_t n, int32_t depth_left, const float *d_shade, const float *d_weights,
+                 const uint32_t *d_refr_kind, const float *d_travel, const float *d_child_values, const uint32_t *d_parent, float *d_out,
+                 size_t n_out, void *hip_stream);
 
 /* ---- several GPUs from one process (SURVEY §8e without Python or MPI) -------------------
  * Image rows are interleaved over the entries of `devices` exactly as homework-18-graphics-raytracer_amd/dist.py interleaves
