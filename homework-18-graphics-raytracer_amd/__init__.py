@@ -14,6 +14,8 @@ reference's host-side names on top of them:
     shade_hits / reflect_rays / refract_rays   src/main.rs:407-464, 328-341, 343-405 (get_shade, get_reflect, get_refract), on caller-supplied hits
     trace_rays_distributed_levels  src/main.rs:521-614 again, one level at a time from the queries and the level-loop calls
     trace_rays_levels              src/main.rs:466-519 again, one level of the tree at a time from the queries and the tree-loop calls
+    light_rays / light_terms / light_fold      src/main.rs:407-464 (get_shade) opened into the calls between its shadow casts
+    shade_hits_by_light            src/main.rs:407-464 again, light by light from those calls, select_records and cast_rays_indexed
     post_process / write_to_file   src/main.rs:748-776
 
 PyTorch is used only for device memory, streams and torch.distributed.
@@ -31,7 +33,7 @@ from ._capi import Camera, Frame, Light, Material, RtError, SceneDesc, Sphere, T
 
 __all__ = [
     "World", "ObjectProxy", "Scene", "Camera", "Frame", "Material", "Light", "RtError", "reference_world",
-    "reference_camera", "render_whitted", "render_whitted_numpy", "make_rays", "cast_rays", "Hits", "camera_rays", "cast_rays_numpy", "trace_rays", "trace_rays_numpy", "shade_hits", "reflect_rays", "refract_rays", "Refractions", "ESCAPED", "INFINITE", "TRAPPED", "HIT_NONE", "shade_hits_numpy", "refract_rays_numpy", "scatter_hits", "scatter_factors", "Scatters", "DIFFUSE", "REFLECTION", "REFRACTION", "scatter_hits_numpy", "scatter_factors_numpy", "select_records", "cast_rays_indexed", "level_split", "level_join", "level_close", "level_fold", "level_finish", "trace_rays_distributed_levels", "tree_gate", "tree_split", "tree_spawn", "tree_gather", "tree_fold", "trace_rays_levels", "default_level_capacity", "Rng", "focus_rays", "trace_rays_distributed", "trace_rays_distributed_numpy", "render_distributed", "render_distributed_numpy", "set_option", "options", "post_process_device", "encode_srgb8_device", "post_process", "encode_srgb8", "write_to_file",
+    "reference_camera", "render_whitted", "render_whitted_numpy", "make_rays", "cast_rays", "Hits", "camera_rays", "cast_rays_numpy", "trace_rays", "trace_rays_numpy", "shade_hits", "reflect_rays", "refract_rays", "Refractions", "ESCAPED", "INFINITE", "TRAPPED", "HIT_NONE", "shade_hits_numpy", "refract_rays_numpy", "scatter_hits", "scatter_factors", "Scatters", "DIFFUSE", "REFLECTION", "REFRACTION", "scatter_hits_numpy", "scatter_factors_numpy", "select_records", "cast_rays_indexed", "level_split", "level_join", "level_close", "level_fold", "level_finish", "trace_rays_distributed_levels", "tree_gate", "tree_split", "tree_spawn", "tree_gather", "tree_fold", "trace_rays_levels", "default_level_capacity", "light_rays", "light_terms", "light_fold", "shade_hits_by_light", "Rng", "focus_rays", "trace_rays_distributed", "trace_rays_distributed_numpy", "render_distributed", "render_distributed_numpy", "set_option", "options", "post_process_device", "encode_srgb8_device", "post_process", "encode_srgb8", "write_to_file",
     "DEFAULT_OBJ",
 ]
 
@@ -145,6 +147,7 @@ class Scene:
     def __init__(self, world_or_desc):
         desc = world_or_desc.desc() if isinstance(world_or_desc, World) else world_or_desc
         self._desc = desc
+        self.n_lights = int(desc.n_lights)
         self._h = C.c_void_p()
         _capi.check(_capi.amd_lib().rt_scene_create(C.byref(desc), C.byref(self._h)))
 
@@ -1343,6 +1346,144 @@ def trace_rays_levels(scene: Scene, rays, max_depth: int, contribution=1.0, out=
             raise RtError(-5, f"trace_rays_levels: {dropped} child records did not fit their level's capacity (level_capacity)")
     return out
 
+# ---- light queries: get_shade light by light (include/rt_amd.h rt_light_rays, rt_light_terms, rt_light_fold) ----
+
+
+def _light_range(scene: Scene, light_first, light_count):
+    first = int(light_first)
+    count = scene.n_lights - first if light_count is None else int(light_count)
+    if first < 0 or count < 0:
+        raise ValueError("light_first and light_count must not be negative (light_count None: every light from light_first on)")
+    return first, count
+
+
+def light_rays(scene: Scene, hits, rays, light_first: int = 0, light_count=None, out_rays=None, out_asks=None, out_distance=None,
+               distance: bool = False, stream=None):
+    """main.rs:408-433 per hit and light (rt_light_rays): returns (shadow_rays, asks, light_distance) for the lights light_first ..
+    light_first + light_count - 1 (default: every light from light_first on), light-major — entry (l - light_first) * N + i belongs to
+    light l and hit i.  ``asks`` (L*N,) uint8: 1 where get_shade casts a shadow ray; ``shadow_rays`` (L*N, 11) int32: that ray, bit for
+    bit, all-zero words elsewhere — one batch for select_records(asks) + cast_rays_indexed; ``light_distance`` (L*N,) float32, computed
+    when ``distance`` is set or ``out_distance`` given (else None): what the reference compares the occluder's distance against."""
+    import torch
+
+    records, n = _hits_and_rays(hits, rays)
+    first, count = _light_range(scene, light_first, light_count)
+    pairs = count * n
+    dev = records.device
+    if out_rays is None:
+        out_rays = torch.empty((pairs, 11), dtype=torch.int32, device=dev)
+    if out_asks is None:
+        out_asks = torch.empty((pairs,), dtype=torch.uint8, device=dev)
+    if out_distance is None and distance:
+        out_distance = torch.empty((pairs,), dtype=torch.float32, device=dev)
+    _records(out_rays, 11, "out_rays")
+    if out_rays.shape[0] != pairs:
+        raise ValueError("out_rays must have one record per (light, hit) pair")
+    _column(out_asks, torch.uint8, pairs, "out_asks")
+    if out_distance is not None:
+        _column(out_distance, torch.float32, pairs, "out_distance")
+    _capi.check(_capi.amd_lib().rt_light_rays(scene._h, _p(records), _p(rays), n, first, count, _p(out_rays), _p(out_asks), _p(out_distance),
+                                              _stream_ptr(stream)))
+    return out_rays, out_asks, out_distance
+
+
+def light_terms(scene: Scene, hits, rays, asks, shadow_hits, light_first: int = 0, light_count=None, out_lit=None, out_diffuse=None,
+                out_specular=None, stream=None):
+    """main.rs:435-459 per hit and light (rt_light_terms): returns (lit, diffuse, specular), light-major as light_rays' outputs.
+    ``shadow_hits`` (L*N, 13) int32: what a cast of the shadow rays wrote, read only where ``asks`` is set.  ``lit`` (L*N,) uint8: 1
+    where the light asks, is Some and is not occluded; there ``diffuse`` and ``specular`` (L*N, 3) float32 are get_diffuse and
+    get_specular times the light's colour, not yet weighted by shiness; +0 elsewhere."""
+    import torch
+
+    records, n = _hits_and_rays(hits, rays)
+    first, count = _light_range(scene, light_first, light_count)
+    pairs = count * n
+    dev = records.device
+    _column(asks, torch.uint8, pairs, "asks")
+    _records(shadow_hits, 13, "shadow_hits")
+    if shadow_hits.shape[0] != pairs:
+        raise ValueError("shadow_hits must have one record per (light, hit) pair")
+    if out_lit is None:
+        out_lit = torch.empty((pairs,), dtype=torch.uint8, device=dev)
+    if out_diffuse is None:
+        out_diffuse = torch.empty((pairs, 3), dtype=torch.float32, device=dev)
+    if out_specular is None:
+        out_specular = torch.empty((pairs, 3), dtype=torch.float32, device=dev)
+    _column(out_lit, torch.uint8, pairs, "out_lit")
+    _rgb(out_diffuse, pairs, "out_diffuse")
+    _rgb(out_specular, pairs, "out_specular")
+    _capi.check(_capi.amd_lib().rt_light_terms(scene._h, _p(records), _p(rays), n, first, count, _p(asks), _p(shadow_hits), _p(out_lit),
+                                               _p(out_diffuse), _p(out_specular), _stream_ptr(stream)))
+    return out_lit, out_diffuse, out_specular
+
+
+def light_fold(scene: Scene, hits, lit, diffuse, specular, out, stream=None):
+    """main.rs:461 (rt_light_fold): for the L = len(lit) / N lights of ``lit``, ``diffuse`` and ``specular`` in order, where lit:
+    out = (out + diffuse * (1 - shiness)) + specular * shiness, in place on ``out`` ((N, 3) float32, required).  The call ADDS: zero
+    ``out`` before the first range of lights; later ranges continue the sum.  A record that is no hit is not written."""
+    import torch
+
+    records = _hit_records(hits)
+    n = records.shape[0]
+    _rgb(out, n, "out")
+    if not (torch.is_tensor(lit) and lit.dim() == 1):
+        raise ValueError("lit must be a contiguous (L*N,) uint8 CUDA tensor")
+    pairs = lit.shape[0]
+    if pairs % n != 0 if n else pairs != 0:
+        raise ValueError("lit must have one entry per (light, hit) pair")
+    count = pairs // n if n else 0
+    _column(lit, torch.uint8, pairs, "lit")
+    _rgb(diffuse, pairs, "diffuse")
+    _rgb(specular, pairs, "specular")
+    _capi.check(_capi.amd_lib().rt_light_fold(scene._h, _p(records), n, count, _p(lit), _p(diffuse), _p(specular), _p(out), _stream_ptr(stream)))
+    return out
+
+
+def shade_hits_by_light(scene: Scene, hits, rays, out=None, ray_count=None, stream=None, lights_per_pass=None):
+    """shade_hits — the same hits, the same values and cast count, bit for bit — written light by light from the public calls alone:
+    the executable form of the sequence in INTEGRATION.md, to be copied and changed (a subset of lights, a shadow rule of one's own,
+    per-light output).  Zero ``out``; then per range of ``lights_per_pass`` lights (default: all of them — it bounds the memory, about
+    126 B per (hit, light) pair of a pass): light_rays -> select_records(asks) -> cast_rays_indexed(shadow rays -> shadow hits,
+    ray_count) -> light_terms -> light_fold.  Every buffer is allocated once, up front; after that the function only enqueues library
+    calls on ``stream`` and reads nothing back.  The shadow casts take cast_rays_indexed's routes: on a scene walked breadth-first that
+    walk.  (Being a sequence of calls it may not be captured before select_records — and, on such a scene, cast_rays_indexed — has run
+    once on the stream.)"""
+    import torch
+
+    records, n = _hits_and_rays(hits, rays)
+    dev = records.device
+    if out is None:
+        out = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    _rgb(out, n, "out")
+    _count_ptr(ray_count)
+    lights = scene.n_lights
+    per_pass = lights if lights_per_pass is None else int(lights_per_pass)
+    if lights_per_pass is not None and per_pass < 1:
+        raise ValueError("lights_per_pass must be at least 1")
+    per_pass = min(per_pass, lights)
+    if n * per_pass >= 1 << 32:
+        raise RtError(-5, "2^32 (hit, light) pairs or more in one pass (lights_per_pass)")
+    s = stream
+    # allocated (and the fill enqueued) with `stream` as torch's current stream: the caching allocator then ties the blocks to it
+    with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+        out.zero_()  # `sum` starts black (main.rs:411)
+        if n == 0 or lights == 0:
+            return out
+        pairs = per_pass * n
+        shadow_rays = torch.empty((pairs, 11), dtype=torch.int32, device=dev)
+        shadow_hits = torch.empty((pairs, 13), dtype=torch.int32, device=dev)
+        asks, lit = torch.empty((pairs,), dtype=torch.uint8, device=dev), torch.empty((pairs,), dtype=torch.uint8, device=dev)
+        index, count = torch.empty((pairs,), dtype=torch.int32, device=dev), torch.empty((1,), dtype=torch.int32, device=dev)
+        diffuse, specular = torch.empty((pairs, 3), dtype=torch.float32, device=dev), torch.empty((pairs, 3), dtype=torch.float32, device=dev)
+    for first in range(0, lights, per_pass):
+        c = min(per_pass, lights - first)
+        m = c * n
+        light_rays(scene, records, rays, first, c, shadow_rays[:m], asks[:m], stream=s)
+        select_records(asks[:m], index[:m], count, stream=s)
+        cast_rays_indexed(scene, shadow_rays[:m], index[:m], count, shadow_hits[:m], ray_count=ray_count, stream=s)
+        light_terms(scene, records, rays, asks[:m], shadow_hits[:m], first, c, lit[:m], diffuse[:m], specular[:m], stream=s)
+        light_fold(scene, records, lit[:m], diffuse[:m], specular[:m], out, stream=s)
+    return out
 
 
 def render_distributed_numpy(scene: Scene, camera: Camera, frame: Frame, rng: Rng, n_epochs: int, img: np.ndarray,

@@ -12,6 +12,7 @@
  *                      queries rt_scatter_hits / rt_scatter_factors and the level loop's rt_select_records / rt_cast_rays_indexed /
  *                      rt_level_*
  *   rt_tree_query.hip  the tree loop's rt_tree_*: kernels and entry points in one unit
+ *   rt_light_query.hip the light queries' rt_light_*: kernels and entry points in one unit
  */
 #ifndef RT_API_INTERNAL_H
 #define RT_API_INTERNAL_H

@@ -300,8 +300,9 @@ int rt_trace_rays_host(const rt_scene *scene, const rt_ray *h_rays, size_t n_ray
  * (cast_pairs), or wave-uniform under RT_AMD_QUERY_WAVE_UNIFORM=1, with the same bits (DESIGN.md §3.10 says which is faster when).
  * A scene walked breadth-first (RT_AMD_BFS_WALK_TRIANGLES) gives the same bits through the same two casts: the breadth-first walk
  * itself is not used inside these kernels.
- * Not covered: per-record cast counts; rt_multi_* variants; the breadth-first walk inside these kernels; the ray of Refraction::Infinite (main.rs:154-156),
- * which the reference's callers discard. */
+ * Not covered: per-record cast counts; rt_multi_* variants; the breadth-first walk inside these kernels (for get_shade's shadow casts it
+ * comes with the light queries below, whose shadow rays go through rt_cast_rays_indexed); the ray of Refraction::Infinite
+ * (main.rs:154-156), which the reference's callers discard. */
 
 /* get_shade(&hit) (main.rs:407-464): d_rgb[3*i + c], bit for bit, NaN and -0.0 included.  d_ray_count: NULL or one u64 device word, the
  * shadow casts (one per light that faces the bumped normal, main.rs:435) are ADDED. */
@@ -323,6 +324,58 @@ int rt_shade_hits_host(const rt_scene *scene, const rt_hit *h_hits, const rt_ray
                        unsigned long long *h_ray_count);
 int rt_refract_rays_host(const rt_scene *scene, const rt_hit *h_hits, const rt_ray *h_incoming, size_t n, float max_distance,
                          uint32_t *h_kind, float *h_travel, rt_ray *h_escape, unsigned long long *h_ray_count);
+
+/* ---- light queries: get_shade light by light on caller-supplied hits ------------------------------
+
+ * get_shade (main.rs:407-464) opened into the calls between its casts.  rt_shade_hits runs the whole light loop in one kernel, shadow
+ * casts inside, and returns the sum; here the shadow rays are records like every other ray, so that a caller can touch direct
+ * lighting — per-light output, a subset of lights (light linking), a shadow rule of its own (a jittered shadow ray, a shadow that
+ * ignores glass), a re-weighting of diffuse against specular — and so that the shadow casts go through rt_select_records +
+ * rt_cast_rays_indexed, which on a scene walked breadth-first take that walk.  The sequence, per range of lights,
+ *     rt_light_rays -> rt_select_records(d_asks) -> rt_cast_rays_indexed(d_shadow_rays -> d_shadow_hits) -> rt_light_terms -> rt_light_fold
+ * on a zeroed d_rgb gives rt_shade_hits' values and cast count bit for bit (INTEGRATION.md writes it out; DESIGN.md §3.14 says why the
+ * bits are the same).  Records are the hit queries': entry i of d_incoming is Hit.ray of d_hits[i]; every pointer is a device pointer;
+ * every call is stream-ordered and asynchronous on hip_stream (NULL = default stream), is one kernel with one record per lane, uses no
+ * workspace and may be captured into a HIP graph at once.
+ * Per-(light, record) arrays are light-major: entry k = (l - light_first) * n + i, n * light_count entries — one light's plane is
+ * contiguous, and the whole array is one batch of n * light_count records for rt_select_records and rt_cast_rays_indexed.
+ * The record rules are those of the hit-query block: a hit whose kind is neither 0 nor 1, or whose object_index >= n_materials, is "no
+ * hit" — asks 0, an all-zero ray, lit 0, black, nothing cast, and its d_rgb entry is not written; a primitive index outside its array
+ * only ever serves as an exclusion; a face above 1 reads as Back; NaN and Inf pass through the arithmetic.
+ * Checked before any device work, in this order: n >= 2^32, or n * light_count >= 2^32, is RT_ERR_UNSUPPORTED; a null scene
+ * RT_ERR_INVALID_ARGUMENT; n == 0 or light_count == 0 is RT_OK and launches nothing; a null required pointer RT_ERR_INVALID_ARGUMENT; only
+ * then is the scene read: light_first + light_count > n_lights (in 64 bits) is RT_ERR_INVALID_ARGUMENT.
+ * Not covered: _host forms (the calls sit between device calls); rt_multi_* forms; per-record cast counts. */
+
+/* main.rs:408-433 per record and light, with material = approx(hit.at) and normal = adjust_normal(hit.at.normal):
+ *   d_asks[k]            1 where approximate_into_directional is Some and !(cosine <= 0) — a NaN cosine asks, as in the reference —
+ *                        else 0: exactly the pairs rt_shade_hits casts a shadow ray for
+ *   d_shadow_rays[k]     where the light asks, shadow_ray: origin = the hit's position, direction = -light.direction, face Back,
+ *                        exclusion { hit.kind, hit.index, Back } — bit for bit the ray rt_shade_hits casts; elsewhere all-zero words
+ *   d_light_distance[k]  (may be NULL) what main.rs:439 compares against: the distance from the hit to the light's origin, +inf for a
+ *                        directional light without origin, 0 where the light does not ask.  For a caller's own occlusion rule;
+ *                        rt_light_terms does not read it. */
+int rt_light_rays(const rt_scene *scene, const rt_hit *d_hits, const rt_ray *d_incoming, size_t n, uint32_t light_first, uint32_t light_count,
+                  rt_ray *d_shadow_rays, unsigned char *d_asks, float *d_light_distance, void *hip_stream);
+/* main.rs:435-459.  d_shadow_hits[k] — what a cast of d_shadow_rays[k] wrote — is read only where d_asks[k] != 0, so it needs no preset.
+ * The occlusion rule is the reference's: a shadow hit of kind 0 or 1 occludes a light without origin always, and a light with origin
+ * where distance(hit.position, shadow_hit.position) < distance(hit.position, light.origin); any other kind is a miss.
+ *   d_lit[k]             1 where the record is a hit, d_asks[k] != 0, approximate_into_directional is Some and the light is not occluded
+ *   d_diffuse[3k ..], d_specular[3k ..]   there, the locals `diffuse` and `specular` of main.rs:458-459: get_diffuse / get_specular of the
+ *                        probe times light.color, not yet weighted by shiness; elsewhere d_lit[k] = 0 and both are +0
+ * The probe's light_direction is -light.direction of the light itself, not the direction of d_shadow_rays[k]: a caller may have
+ * replaced that ray.  d_asks is the caller's and is not trusted: a flag set where the light would not have asked costs nothing unsafe
+ * (None gives d_lit[k] = 0; a cosine that is not positive makes get_diffuse and get_specular black by their own tests). */
+int rt_light_terms(const rt_scene *scene, const rt_hit *d_hits, const rt_ray *d_incoming, size_t n, uint32_t light_first, uint32_t light_count,
+                   const unsigned char *d_asks, const rt_hit *d_shadow_hits, unsigned char *d_lit, float *d_diffuse, float *d_specular,
+                   void *hip_stream);
+/* main.rs:461: for l = 0 .. light_count - 1 in order, where d_lit[l * n + i]:
+ *     rgb = (rgb + diffuse * (1 - shiness)) + specular * shiness        per channel, in place on d_rgb[3i ..]
+ * with the shiness of the hit's material; every operation rounds to f32 and none is fused.  The call ADDS: the caller zeroes d_rgb
+ * before the first range of lights, as `sum` starts black, and later ranges continue the same sum — a fold over ranges of lights in
+ * order is the fold over all of them.  "No hit" records are not written.  It takes no light_first: it reads the material only. */
+int rt_light_fold(const rt_scene *scene, const rt_hit *d_hits, size_t n, uint32_t light_count, const unsigned char *d_lit, const float *d_diffuse,
+                  const float *d_specular, float *d_rgb, void *hip_stream);
 
 /* ---- distributed (stochastic / depth-of-field) pass ----------------------------
 
