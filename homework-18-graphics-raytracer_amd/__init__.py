@@ -16,6 +16,8 @@ reference's host-side names on top of them:
     trace_rays_levels              src/main.rs:466-519 again, one level of the tree at a time from the queries and the tree-loop calls
     light_rays / light_terms / light_fold      src/main.rs:407-464 (get_shade) opened into the calls between its shadow casts
     shade_hits_by_light            src/main.rs:407-464 again, light by light from those calls, select_records and cast_rays_indexed
+    refract_enter / refract_step   src/main.rs:343-405 (get_refract) opened into the calls between its casts
+    refract_rays_by_bounce         src/main.rs:343-405 again, bounce by bounce from those calls, select_records and cast_rays_indexed
     post_process / write_to_file   src/main.rs:748-776
 
 PyTorch is used only for device memory, streams and torch.distributed.
@@ -33,7 +35,7 @@ from ._capi import Camera, Frame, Light, Material, RtError, SceneDesc, Sphere, T
 
 __all__ = [
     "World", "ObjectProxy", "Scene", "Camera", "Frame", "Material", "Light", "RtError", "reference_world",
-    "reference_camera", "render_whitted", "render_whitted_numpy", "make_rays", "cast_rays", "Hits", "camera_rays", "cast_rays_numpy", "trace_rays", "trace_rays_numpy", "shade_hits", "reflect_rays", "refract_rays", "Refractions", "ESCAPED", "INFINITE", "TRAPPED", "HIT_NONE", "shade_hits_numpy", "refract_rays_numpy", "scatter_hits", "scatter_factors", "Scatters", "DIFFUSE", "REFLECTION", "REFRACTION", "scatter_hits_numpy", "scatter_factors_numpy", "select_records", "cast_rays_indexed", "level_split", "level_join", "level_close", "level_fold", "level_finish", "trace_rays_distributed_levels", "tree_gate", "tree_split", "tree_spawn", "tree_gather", "tree_fold", "trace_rays_levels", "default_level_capacity", "light_rays", "light_terms", "light_fold", "shade_hits_by_light", "Rng", "focus_rays", "trace_rays_distributed", "trace_rays_distributed_numpy", "render_distributed", "render_distributed_numpy", "set_option", "options", "post_process_device", "encode_srgb8_device", "post_process", "encode_srgb8", "write_to_file",
+    "reference_camera", "render_whitted", "render_whitted_numpy", "make_rays", "cast_rays", "Hits", "camera_rays", "cast_rays_numpy", "trace_rays", "trace_rays_numpy", "shade_hits", "reflect_rays", "refract_rays", "Refractions", "ESCAPED", "INFINITE", "TRAPPED", "HIT_NONE", "shade_hits_numpy", "refract_rays_numpy", "scatter_hits", "scatter_factors", "Scatters", "DIFFUSE", "REFLECTION", "REFRACTION", "scatter_hits_numpy", "scatter_factors_numpy", "select_records", "cast_rays_indexed", "level_split", "level_join", "level_close", "level_fold", "level_finish", "trace_rays_distributed_levels", "tree_gate", "tree_split", "tree_spawn", "tree_gather", "tree_fold", "trace_rays_levels", "default_level_capacity", "light_rays", "light_terms", "light_fold", "shade_hits_by_light", "light_workspace", "LightWorkspace", "WALKING", "refract_enter", "refract_step", "refract_rays_by_bounce", "refract_workspace", "RefractWorkspace", "Rng", "focus_rays", "trace_rays_distributed", "trace_rays_distributed_numpy", "render_distributed", "render_distributed_numpy", "set_option", "options", "post_process_device", "encode_srgb8_device", "post_process", "encode_srgb8", "write_to_file",
     "DEFAULT_OBJ",
 ]
 
@@ -975,12 +977,15 @@ def level_finish(value, accum=None, valid=None, stream=None):
 
 
 def trace_rays_distributed_levels(scene: Scene, rays, max_depth: int, rng: Rng, n_epochs: int = 1, accum=None, samples=None, valid=None,
-                                  ray_count=None, stream=None):
+                                  ray_count=None, stream=None, open_casts: bool = False):
     """trace_rays_distributed — the same arguments, the same samples, flags, accumulated image, cast count and generator records, bit for
     bit — written one level at a time from the public calls alone: the executable form of the loop in INTEGRATION.md, to be copied and
     changed (a stopping rule, a weighting, a re-sort between levels).  Every buffer is allocated once, up front; after that the function
     only enqueues library calls on ``stream``: no tensor arithmetic, nothing read back, no synchronisation.  The cast count is what the
     calls' device counters add up to; the primary casts go through cast_rays_indexed with an identity list so that they are counted too.
+    ``open_casts=True`` replaces shade_hits by shade_hits_by_light and refract_rays by refract_rays_by_bounce, each on a workspace made
+    up front: every cast of the loop is then a cast_rays_indexed — on a scene walked breadth-first, that walk — with the same bits and
+    count (the two add a few element-wise fills to what is enqueued).
     (Being a sequence of calls it may not be captured before select_records has run once on the stream.)"""
     import torch
 
@@ -1024,7 +1029,19 @@ def trace_rays_distributed_levels(scene: Scene, rays, max_depth: int, rng: Rng, 
         identity, n_all = new((n,), i32), new((1,), i32)
         value = None if samples is not None else new((n, 3), f32)
         flags.fill_(1)
+        lws = light_workspace(scene, n, dev) if open_casts else None
+        rws = refract_workspace(n, dev) if open_casts and depth > 0 else None
     select_records(flags, identity, n_all, stream=s)  # 0 .. n-1 and n: the primary casts as an indexed cast, which counts
+
+    def shade(level_hits, level_rays, out):  # get_shade, in one kernel or light by light
+        if open_casts:
+            return shade_hits_by_light(scene, level_hits, level_rays, out=out, ray_count=ray_count, stream=s, workspace=lws)
+        return shade_hits(scene, level_hits, level_rays, out=out, ray_count=ray_count, stream=s)
+
+    def refract(level_hits, level_rays, out):  # get_refract(100.0), in one kernel or bounce by bounce
+        if open_casts:
+            return refract_rays_by_bounce(scene, level_hits, level_rays, 100.0, ray_count=ray_count, stream=s, out=out, workspace=rws)
+        return refract_rays(scene, level_hits, level_rays, 100.0, ray_count=ray_count, stream=s, out=out)
 
     for e in range(n_epochs):
         cur_rays = rays
@@ -1033,18 +1050,18 @@ def trace_rays_distributed_levels(scene: Scene, rays, max_depth: int, rng: Rng, 
             sc = scatter_hits(scene, hits[k], cur_rays, rng, stream=s, out=scat[k])  # the level's three draws; "no hit" draws nothing
             level_split(hits[k], sc.type, sc.cosine, h_reflect, h_refract, stream=s)
             reflect_rays(h_reflect, sc.rays, out=reflected, stream=s)
-            refract_rays(scene, h_refract, sc.rays, 100.0, ray_count=ray_count, stream=s, out=refr)
+            refract(h_refract, sc.rays, refr)
             nxt = level_rays[k & 1]
             level_join(sc.type, sc.cosine, reflected, refr.kind, refr.rays, nxt, hits[k + 1], flags, stream=s)
             select_records(flags, index, count, stream=s)
             cast_rays_indexed(scene, nxt, index, count, hits[k + 1], ray_count=ray_count, stream=s)
             scatter_factors(scene, hits[k], cur_rays, sc.type, nxt, refr.travel, out=factor[k], stream=s)
-            shade_hits(scene, hits[k + 1], nxt, out=shade_next[k], ray_count=ray_count, stream=s)  # the mix / sum operand
+            shade(hits[k + 1], nxt, shade_next[k])  # the mix / sum operand
             level_close(hits[k], sc.type, sc.cosine, hits[k + 1], h_missed, stream=s)
-            shade_hits(scene, h_missed, sc.rays, out=shade_missed[k], ray_count=ray_count, stream=s)  # get_shade(&scattered_hit)
+            shade(h_missed, sc.rays, shade_missed[k])  # get_shade(&scattered_hit)
             cur_rays = nxt
         v = samples[e] if samples is not None else value
-        shade_hits(scene, hits[depth], cur_rays, out=v, ray_count=ray_count, stream=s)  # depth <= 0: get_shade(&hit), main.rs:524-527
+        shade(hits[depth], cur_rays, v)  # depth <= 0: get_shade(&hit), main.rs:524-527
         for k in reversed(range(depth)):
             level_fold(scat[k].type, scat[k].cosine, hits[k + 1], factor[k], shade_next[k], shade_missed[k], v, stream=s)
         if accum is not None or valid is not None:  # samples alone: the folded value is the sample, nothing to filter into
@@ -1231,7 +1248,7 @@ def default_level_capacity(n: int, level: int) -> int:
 
 
 def trace_rays_levels(scene: Scene, rays, max_depth: int, contribution=1.0, out=None, ray_count=None, stream=None, level_capacity=None,
-                      check: bool = True, overflow=None, level_counts=None):
+                      check: bool = True, overflow=None, level_counts=None, open_casts: bool = False):
     """trace_rays — the same rays, depth and contribution, the same values and cast count, bit for bit — written one level of the
     recursion tree at a time from the public calls alone: the executable form of the sequence in INTEGRATION.md, to be copied and changed
     (a stopping rule, a weighting, a re-sort between levels).  ``contribution``: a float, or an (N,) float32 CUDA tensor of per-ray root
@@ -1241,6 +1258,9 @@ def trace_rays_levels(scene: Scene, rays, max_depth: int, contribution=1.0, out=
     and does not synchronise — the form for graph capture.  ``overflow``: a 1-element int32 CUDA tensor the dropped children are ADDED to
     (one is made and zeroed if None); ``level_counts``: a (max(max_depth, 0) + 1,) int32 CUDA tensor that receives the number of records
     cast per level.  Every buffer is allocated once, up front; after that the function only enqueues library calls on ``stream``.
+    ``open_casts=True`` replaces shade_hits by shade_hits_by_light and refract_rays by refract_rays_by_bounce, each on a workspace made
+    up front: every cast of the loop is then a cast_rays_indexed — on a scene walked breadth-first, that walk — with the same bits and
+    count (the two add a few element-wise fills to what is enqueued).
     (Being a sequence of calls it may not be captured before select_records has run once on the stream.)"""
     import torch
 
@@ -1310,7 +1330,19 @@ def trace_rays_levels(scene: Scene, rays, max_depth: int, contribution=1.0, out=
             overflow.zero_()
         counts.zero_()  # a level without room is not visited by any kernel: its count stays 0
         flags[:top].fill_(1)
+        lws = light_workspace(scene, top, dev) if open_casts else None
+        rws = refract_workspace(top, dev) if open_casts and depth > 0 else None
     select_records(flags[:top], identity, n_all, stream=s)  # 0 .. top-1: the child levels are cast through it with their own counts
+
+    def shade_level(level_hits, level_rays, out):  # get_shade, in one kernel or light by light
+        if open_casts:
+            return shade_hits_by_light(scene, level_hits, level_rays, out=out, ray_count=ray_count, stream=s, workspace=lws)
+        return shade_hits(scene, level_hits, level_rays, out=out, ray_count=ray_count, stream=s)
+
+    def refract(level_hits, level_rays, out):  # get_refract(100.0), in one kernel or bounce by bounce
+        if open_casts:
+            return refract_rays_by_bounce(scene, level_hits, level_rays, 100.0, ray_count=ray_count, stream=s, out=out, workspace=rws)
+        return refract_rays(scene, level_hits, level_rays, 100.0, ray_count=ray_count, stream=s, out=out)
 
     cur_rays, cur_contribution = rays, root_contribution
     for k in range(depth + 1):
@@ -1323,11 +1355,10 @@ def trace_rays_levels(scene: Scene, rays, max_depth: int, contribution=1.0, out=
         else:
             cast_rays_indexed(scene, cur_rays[:c], identity[:c], count[k], hits[k], ray_count=ray_count, stream=s)
         tree_split(scene, hits[k], cur_contribution[:c], left, live, h_shade[:c], h_reflect[:c], h_refract[:c], weights[k], stream=s)
-        shade_hits(scene, h_shade[:c], cur_rays[:c], out=shade[k], ray_count=ray_count, stream=s)
+        shade_level(h_shade[:c], cur_rays[:c], shade[k])
         if left > 0:
             reflect_rays(h_reflect[:c], cur_rays[:c], out=reflected[:c], stream=s)
-            refract_rays(scene, h_refract[:c], cur_rays[:c], 100.0, ray_count=ray_count, stream=s,
-                         out=Refractions(refr_kind[k], travel[k], escape[:c]))
+            refract(h_refract[:c], cur_rays[:c], Refractions(refr_kind[k], travel[k], escape[:c]))
             tree_spawn(h_reflect[:c], refr_kind[k], flags[:2 * c], child_values[k], stream=s)
             select_records(flags[:2 * c], index[:2 * c], selected, stream=s)
             nxt = 1 + (k & 1)
@@ -1439,7 +1470,31 @@ def light_fold(scene: Scene, hits, lit, diffuse, specular, out, stream=None):
     return out
 
 
-def shade_hits_by_light(scene: Scene, hits, rays, out=None, ray_count=None, stream=None, lights_per_pass=None):
+class LightWorkspace:
+    """The buffers of one pass of shade_hits_by_light, made once by light_workspace so that a caller's loop allocates nothing:
+    ``pairs`` (hit, light) pairs of room."""
+
+    def __init__(self, pairs: int, device):
+        import torch
+
+        self.pairs = int(pairs)
+        i32, f32, u8 = torch.int32, torch.float32, torch.uint8
+        self.shadow_rays = torch.empty((pairs, 11), dtype=i32, device=device)
+        self.shadow_hits = torch.empty((pairs, 13), dtype=i32, device=device)
+        self.asks, self.lit = torch.empty((pairs,), dtype=u8, device=device), torch.empty((pairs,), dtype=u8, device=device)
+        self.index, self.count = torch.empty((pairs,), dtype=i32, device=device), torch.empty((1,), dtype=i32, device=device)
+        self.diffuse, self.specular = torch.empty((pairs, 3), dtype=f32, device=device), torch.empty((pairs, 3), dtype=f32, device=device)
+
+
+def light_workspace(scene: Scene, n: int, device, lights_per_pass=None) -> LightWorkspace:
+    """A LightWorkspace for shade_hits_by_light on up to ``n`` hits of ``scene``, ``lights_per_pass`` lights at a time (default: all)."""
+    per_pass = scene.n_lights if lights_per_pass is None else min(int(lights_per_pass), scene.n_lights)
+    if per_pass < 0 or n < 0:
+        raise ValueError("n and lights_per_pass must not be negative")
+    return LightWorkspace(int(n) * per_pass, device)
+
+
+def shade_hits_by_light(scene: Scene, hits, rays, out=None, ray_count=None, stream=None, lights_per_pass=None, workspace=None):
     """shade_hits — the same hits, the same values and cast count, bit for bit — written light by light from the public calls alone:
     the executable form of the sequence in INTEGRATION.md, to be copied and changed (a subset of lights, a shadow rule of one's own,
     per-light output).  Zero ``out``; then per range of ``lights_per_pass`` lights (default: all of them — it bounds the memory, about
@@ -1470,11 +1525,12 @@ def shade_hits_by_light(scene: Scene, hits, rays, out=None, ray_count=None, stre
         if n == 0 or lights == 0:
             return out
         pairs = per_pass * n
-        shadow_rays = torch.empty((pairs, 11), dtype=torch.int32, device=dev)
-        shadow_hits = torch.empty((pairs, 13), dtype=torch.int32, device=dev)
-        asks, lit = torch.empty((pairs,), dtype=torch.uint8, device=dev), torch.empty((pairs,), dtype=torch.uint8, device=dev)
-        index, count = torch.empty((pairs,), dtype=torch.int32, device=dev), torch.empty((1,), dtype=torch.int32, device=dev)
-        diffuse, specular = torch.empty((pairs, 3), dtype=torch.float32, device=dev), torch.empty((pairs, 3), dtype=torch.float32, device=dev)
+        if workspace is None:
+            workspace = LightWorkspace(pairs, dev)
+        elif not isinstance(workspace, LightWorkspace) or workspace.pairs < pairs:
+            raise ValueError(f"workspace must be a LightWorkspace with room for {pairs} (hit, light) pairs (light_workspace)")
+        shadow_rays, shadow_hits, asks, lit = workspace.shadow_rays, workspace.shadow_hits, workspace.asks, workspace.lit
+        index, count, diffuse, specular = workspace.index, workspace.count, workspace.diffuse, workspace.specular
     for first in range(0, lights, per_pass):
         c = min(per_pass, lights - first)
         m = c * n
@@ -1483,6 +1539,157 @@ def shade_hits_by_light(scene: Scene, hits, rays, out=None, ray_count=None, stre
         cast_rays_indexed(scene, shadow_rays[:m], index[:m], count, shadow_hits[:m], ray_count=ray_count, stream=s)
         light_terms(scene, records, rays, asks[:m], shadow_hits[:m], first, c, lit[:m], diffuse[:m], specular[:m], stream=s)
         light_fold(scene, records, lit[:m], diffuse[:m], specular[:m], out, stream=s)
+    return out
+
+
+# ---- refraction queries: get_refract bounce by bounce (include/rt_amd.h rt_refract_enter, rt_refract_step) ----
+
+WALKING = 3  # RT_REFR_WALKING: the walk through the glass goes on (beside ESCAPED, INFINITE, TRAPPED and HIT_NONE)
+
+
+def refract_enter(scene: Scene, hits, rays, out_rays=None, out_kind=None, out_travel=None, out_casts=None, out_flags=None, stream=None):
+    """main.rs:354-368 per hit (rt_refract_enter): returns (inside_rays, kind, travel, casts, flags), the state of a walk that has cast
+    nothing yet.  ``kind`` (N,) int32: WALKING, TRAPPED where the ray cannot enter, HIT_NONE for a record that is no hit;
+    ``inside_rays`` (N, 11) int32: where walking, ray_inside — bit for bit the ray refract_rays casts first —, all-zero words elsewhere;
+    ``travel`` (N,) float32 zeros, ``casts`` (N,) int32 zeros, ``flags`` (N,) uint8: 1 where walking — the operand of select_records."""
+    import torch
+
+    records, n = _hits_and_rays(hits, rays)
+    dev = records.device
+    if out_rays is None:
+        out_rays = torch.empty((n, 11), dtype=torch.int32, device=dev)
+    if out_kind is None:
+        out_kind = torch.empty((n,), dtype=torch.int32, device=dev)
+    if out_travel is None:
+        out_travel = torch.empty((n,), dtype=torch.float32, device=dev)
+    if out_casts is None:
+        out_casts = torch.empty((n,), dtype=torch.int32, device=dev)
+    if out_flags is None:
+        out_flags = torch.empty((n,), dtype=torch.uint8, device=dev)
+    _records(out_rays, 11, "out_rays")
+    if out_rays.shape[0] != n:
+        raise ValueError("out_rays must have one record per hit")
+    _column(out_kind, torch.int32, n, "out_kind")
+    _column(out_travel, torch.float32, n, "out_travel")
+    _column(out_casts, torch.int32, n, "out_casts")
+    _column(out_flags, torch.uint8, n, "out_flags")
+    _capi.check(_capi.amd_lib().rt_refract_enter(scene._h, _p(records), _p(rays), n, _p(out_rays), _p(out_kind), _p(out_travel), _p(out_casts),
+                                                 _p(out_flags), _stream_ptr(stream)))
+    return out_rays, out_kind, out_travel, out_casts, out_flags
+
+
+def refract_step(scene: Scene, hits, inside_hits, inside_rays, kind, travel, casts, flags, max_distance: float = 100.0, out_escape=None,
+                 stream=None):
+    """main.rs:371-402 for one answered cast (rt_refract_step), in place on the state refract_enter made: ``inside_hits`` (N, 13) int32
+    is what a cast of ``inside_rays`` wrote, read only where ``kind`` is WALKING.  A walking record counts the cast and becomes INFINITE
+    (its ray stays: the one whose cast missed), goes on WALKING with the total-reflection ray and flag 1, becomes ESCAPED with its escape
+    ray in ``out_escape``, or TRAPPED; records that were finished get flag 0 and nothing else.  Returns ``out_escape`` ((N, 11) int32;
+    zeroed and allocated if None — keep ONE across the rounds: a record's entry is written in the round that finishes it)."""
+    import torch
+
+    records = _hit_records(hits)
+    n = records.shape[0]
+    _records(inside_hits, 13, "inside_hits")
+    _records(inside_rays, 11, "inside_rays")
+    if inside_hits.shape[0] != n or inside_rays.shape[0] != n:
+        raise ValueError("inside_hits and inside_rays must have one record per hit")
+    _column(kind, torch.int32, n, "kind")
+    _column(travel, torch.float32, n, "travel")
+    _column(casts, torch.int32, n, "casts")
+    _column(flags, torch.uint8, n, "flags")
+    if out_escape is None:
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+            out_escape = torch.zeros((n, 11), dtype=torch.int32, device=records.device)
+    _records(out_escape, 11, "out_escape")
+    if out_escape.shape[0] != n:
+        raise ValueError("out_escape must have one record per hit")
+    _capi.check(_capi.amd_lib().rt_refract_step(scene._h, _p(records), n, float(max_distance), _p(inside_hits), _p(inside_rays), _p(kind),
+                                                _p(travel), _p(casts), _p(flags), _p(out_escape), _stream_ptr(stream)))
+    return out_escape
+
+
+class RefractWorkspace:
+    """The state and scratch of refract_rays_by_bounce beside its result, made once by refract_workspace so that a caller's loop
+    allocates nothing; ``n`` records of room.  ``rays`` (n, 11): the ray in flight (for an INFINITE record the ray whose cast missed),
+    ``inside_hits`` (n, 13), ``casts`` (n,) int32: the casts answered per record, ``flags`` (n,) uint8, ``index`` / ``count``:
+    select_records' list."""
+
+    def __init__(self, n: int, device):
+        import torch
+
+        self.n = int(n)
+        i32, u8 = torch.int32, torch.uint8
+        self.rays = torch.empty((n, 11), dtype=i32, device=device)
+        self.inside_hits = torch.empty((n, 13), dtype=i32, device=device)
+        self.casts = torch.empty((n,), dtype=i32, device=device)
+        self.flags, self.index, self.count = torch.empty((n,), dtype=u8, device=device), torch.empty((n,), dtype=i32, device=device), torch.empty((1,), dtype=i32, device=device)
+        self._mask = [torch.empty((n,), dtype=torch.bool, device=device) for _ in range(2)]
+
+
+def refract_workspace(n: int, device) -> RefractWorkspace:
+    """A RefractWorkspace for refract_rays_by_bounce on up to ``n`` hits."""
+    if n < 0:
+        raise ValueError("n must not be negative")
+    return RefractWorkspace(n, device)
+
+
+def refract_rays_by_bounce(scene: Scene, hits, rays, max_distance: float = 100.0, ray_count=None, stream=None, out=None, rounds: int = 11,
+                           workspace=None, resume: bool = False) -> Refractions:
+    """refract_rays — the same hits, the same Refractions and cast count, bit for bit — written bounce by bounce from the public calls
+    alone: the executable form of the sequence in INTEGRATION.md, to be copied and changed (a bounce limit, an absorption rule per
+    segment, a stop at the first interior hit).  refract_enter, then ``rounds`` times select_records(flags) -> cast_rays_indexed(inside
+    rays -> inside hits, ray_count) -> refract_step; last, travel is set to 0 where the record ended without escaping, as refract_rays
+    reports it.  Eleven rounds finish every walk (main.rs:378); fewer leave the unfinished records WALKING — a caller's own bounce limit —
+    with their state in ``out`` and ``workspace``, and a later call with ``resume=True`` and the same ``out`` and ``workspace`` goes on
+    from there.  Every buffer is allocated once, up front — or none at all with ``out`` and ``workspace``, a RefractWorkspace
+    (refract_workspace); after that the function only enqueues calls on ``stream`` (the library's, and four element-wise fills for the
+    travel of the records that did not escape) and reads nothing back.  workspace.casts holds the casts per record.  The casts take
+    cast_rays_indexed's routes: on a scene walked breadth-first that walk.  (Being a sequence of calls it may not be captured before
+    select_records — and, on such a scene, cast_rays_indexed — has run once on the stream.)"""
+    import torch
+
+    records, n = _hits_and_rays(hits, rays)
+    dev = records.device
+    rounds = int(rounds)
+    if rounds < 0:
+        raise ValueError("rounds must not be negative")
+    _count_ptr(ray_count)
+    if resume and (out is None or workspace is None):
+        raise ValueError("resume=True continues the walks held in out and workspace: both are required")
+    if workspace is not None and not (isinstance(workspace, RefractWorkspace) and workspace.n >= n):
+        raise ValueError(f"workspace must be a RefractWorkspace with room for {n} records (refract_workspace)")
+    s = stream
+    # allocated (and the fills enqueued) with `stream` as torch's current stream: the caching allocator then ties the blocks to it
+    with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+        if out is None:
+            out = Refractions(torch.empty((n,), dtype=torch.int32, device=dev), torch.empty((n,), dtype=torch.float32, device=dev),
+                              torch.empty((n, 11), dtype=torch.int32, device=dev))
+        kind, travel, escape = out.kind, out.travel, out.rays
+        _column(kind, torch.int32, n, "out.kind")
+        _column(travel, torch.float32, n, "out.travel")
+        _records(escape, 11, "out.rays")
+        if escape.shape[0] != n:
+            raise ValueError("out must have one record per hit")
+        if n == 0:
+            return out
+        if workspace is None:
+            workspace = RefractWorkspace(n, dev)
+        w = workspace
+        w_rays, w_hits, w_casts, w_flags, w_index = w.rays[:n], w.inside_hits[:n], w.casts[:n], w.flags[:n], w.index[:n]
+        if not resume:
+            escape.zero_()  # refract_step writes a record's escape ray in the round that finishes it; refract_enter finishes some itself
+    if not resume:
+        refract_enter(scene, records, rays, w_rays, kind, travel, w_casts, w_flags, stream=s)
+    for _ in range(rounds):
+        select_records(w_flags, w_index, w.count, stream=s)
+        cast_rays_indexed(scene, w_rays, w_index, w.count, w_hits, ray_count=ray_count, stream=s)
+        refract_step(scene, records, w_hits, w_rays, kind, travel, w_casts, w_flags, max_distance, escape, stream=s)
+    with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+        ended, not_walking = w._mask[0][:n], w._mask[1][:n]
+        torch.ne(kind, ESCAPED, out=ended)
+        torch.ne(kind, WALKING, out=not_walking)
+        ended.logical_and_(not_walking)
+        travel.masked_fill_(ended, 0.0)  # travel_distance belongs to Escaped alone (main.rs:402)
     return out
 
 

@@ -13,6 +13,7 @@
  *                      rt_level_*
  *   rt_tree_query.hip  the tree loop's rt_tree_*: kernels and entry points in one unit
  *   rt_light_query.hip the light queries' rt_light_*: kernels and entry points in one unit
+ *   rt_refract_query.hip the refraction queries' rt_refract_enter / rt_refract_step: kernels and entry points in one unit
  */
 #ifndef RT_API_INTERNAL_H
 #define RT_API_INTERNAL_H

@@ -301,8 +301,9 @@ int rt_trace_rays_host(const rt_scene *scene, const rt_ray *h_rays, size_t n_ray
  * A scene walked breadth-first (RT_AMD_BFS_WALK_TRIANGLES) gives the same bits through the same two casts: the breadth-first walk
  * itself is not used inside these kernels.
  * Not covered: per-record cast counts; rt_multi_* variants; the breadth-first walk inside these kernels (for get_shade's shadow casts it
- * comes with the light queries below, whose shadow rays go through rt_cast_rays_indexed); the ray of Refraction::Infinite
- * (main.rs:154-156), which the reference's callers discard. */
+ * comes with the light queries below, for get_refract's casts with the refraction queries after them: both hand their rays to
+ * rt_cast_rays_indexed); the ray of Refraction::Infinite (main.rs:154-156), which the reference's callers discard (the refraction
+ * queries keep it, and count casts per record). */
 
 /* get_shade(&hit) (main.rs:407-464): d_rgb[3*i + c], bit for bit, NaN and -0.0 included.  d_ray_count: NULL or one u64 device word, the
  * shadow casts (one per light that faces the bumped normal, main.rs:435) are ADDED. */
@@ -376,6 +377,69 @@ int rt_light_terms(const rt_scene *scene, const rt_hit *d_hits, const rt_ray *d_
  * order is the fold over all of them.  "No hit" records are not written.  It takes no light_first: it reads the material only. */
 int rt_light_fold(const rt_scene *scene, const rt_hit *d_hits, size_t n, uint32_t light_count, const unsigned char *d_lit, const float *d_diffuse,
                   const float *d_specular, float *d_rgb, void *hip_stream);
+
+/* ---- refraction queries: get_refract bounce by bounce on caller-supplied hits ------------------------------
+
+ * get_refract (main.rs:343-405) opened into the calls between its casts.  rt_refract_rays runs the whole walk through the glass in one
+ * kernel, its 1 to 11 casts inside; here every one of those casts is a record like every other ray, so that a caller can touch the walk
+ * — a bounce limit of its own, an absorption rule per segment, a stop at the first interior hit — and so that the casts go through
+ * rt_select_records + rt_cast_rays_indexed, which on a scene walked breadth-first take that walk.  The sequence
+ *     rt_refract_enter, then eleven times:
+ *     rt_select_records(d_flags) -> rt_cast_rays_indexed(d_rays -> d_inside_hits, d_ray_count) -> rt_refract_step
+ * on a d_escape zeroed once up front gives rt_refract_rays' kind, escape ray and cast count bit for bit, and its travel where the record
+ * escaped (INTEGRATION.md writes it out; DESIGN.md §3.15 says why the bits are the same).  Fewer rounds leave the unfinished records
+ * RT_REFR_WALKING with their state complete: later rounds continue them.  Records are the hit queries': entry i of d_incoming is Hit.ray
+ * of d_hits[i]; every pointer is a device pointer and all are required; every call is stream-ordered and asynchronous on hip_stream
+ * (NULL = default stream), is one kernel with one record per lane (any n below 2^32 in one launch), uses no workspace and may be
+ * captured into a HIP graph at once.
+ * The state of a walk is five caller-owned arrays of n entries, written by rt_refract_enter and advanced by rt_refract_step:
+ *   d_kind[i]    RT_REFR_WALKING while the walk goes on; then 0 Escaped, 1 Infinite, 2 Trapped, or RT_HIT_NONE (no hit), as rt_refract_rays
+ *   d_rays[i]    the ray to cast next while walking; the ray whose cast missed when Infinite (Refraction::Infinite's ray, main.rs:154-156)
+ *   d_travel[i]  the running travel_distance: the sum so far while walking, rt_refract_rays' travel when Escaped.  For Infinite and Trapped
+ *                it stays as computed — rt_refract_rays reports 0 there; a caller that wants that writes it
+ *   d_casts[i]   the casts answered for the record so far, a miss included: the per-record cast count; its sum over the records is what
+ *                rt_cast_rays_indexed added to d_ray_count
+ *   d_flags[i]   1 exactly where d_rays[i] is to be cast next: the operand of rt_select_records
+ * The record rules are those of the hit-query block: a hit whose kind is neither 0 nor 1, or whose object_index >= n_materials, is "no
+ * hit"; a primitive index outside its array only ever serves as an exclusion; a face above 1 reads as Back; NaN and Inf pass through the
+ * arithmetic.  The state is the caller's as well and is validated, never trusted: a d_kind word other than RT_REFR_WALKING is "finished"
+ * whatever it holds; d_casts only enters the test `casts < 10` (10, 2^31 or any other value at or above 10 fails it); nothing is indexed
+ * with a state word; d_rays and d_inside_hits are read as rt_cast_rays reads a ray and as the hit queries read a hit (an inside hit whose
+ * kind is neither 0 nor 1 is a miss; an exclusion index beyond its array excludes nothing).
+ * Checked before any device work, in this order: n >= 2^32 is RT_ERR_UNSUPPORTED; a null scene RT_ERR_INVALID_ARGUMENT; n == 0 is RT_OK
+ * and launches nothing; a null pointer RT_ERR_INVALID_ARGUMENT.
+ * Not covered: _host forms (the calls sit between device calls); rt_multi_* forms. */
+
+#define RT_REFR_WALKING 3u /* beside 0 Escaped, 1 Infinite, 2 Trapped and RT_HIT_NONE */
+
+/* main.rs:354-368 per record, with k = approx(hit.at).refraction_index:
+ *   a record that is "no hit"                     d_kind RT_HIT_NONE, an all-zero d_rays[i], d_flags 0
+ *   refract(hit.normal, hit.ray.direction, k) None  d_kind 2 (Trapped, main.rs:356-358), an all-zero d_rays[i], d_flags 0
+ *   otherwise                                     d_kind RT_REFR_WALKING, d_flags 1 and d_rays[i] = ray_inside: origin = the hit's position,
+ *                                                 direction = refract_in normalised a second time, face Back, exclusion { hit.kind,
+ *                                                 hit.index, Front } — bit for bit the ray rt_refract_rays casts first
+ * and for every record d_travel[i] = +0 and d_casts[i] = 0. */
+int rt_refract_enter(const rt_scene *scene, const rt_hit *d_hits, const rt_ray *d_incoming, size_t n, rt_ray *d_rays, uint32_t *d_kind,
+                     float *d_travel, uint32_t *d_casts, unsigned char *d_flags, void *hip_stream);
+/* main.rs:371-402 for ONE answered cast.  A record whose d_kind[i] is not RT_REFR_WALKING is finished: d_flags[i] = 0 and nothing else is
+ * written (so d_escape[i] of a record rt_refract_enter finished is never written: zero d_escape once, before the first round).  For a
+ * walking record d_inside_hits[i] is what a cast of d_rays[i] wrote (hit_inside); with j = d_casts[i] and k of the material of d_hits[i]:
+ *   d_casts[i] = j + 1
+ *   hit_inside is a miss          d_kind 1 (Infinite); d_rays[i] and d_travel[i] stay as they are
+ *   otherwise                     travel = distance(hit_inside.position, hit.position) when j == 0 (main.rs:375), else
+ *                                 travel = d_travel[i] + distance(origin of d_rays[i], hit_inside.position) (main.rs:385); d_travel[i] = travel;
+ *                                 out = refract(hit_inside.normal, direction of d_rays[i], 1 / k), and then
+ *     out is None && travel <= max_distance && j < 10 (in that order, main.rs:378)
+ *                                 d_rays[i] = get_reflect(&hit_inside): origin hit_inside.position, the reflected direction, face Back,
+ *                                 exclusion { hit_inside.kind, hit_inside.index, invert(hit_inside.face_direction) }; d_flags[i] = 1; the
+ *                                 kind stays RT_REFR_WALKING and d_escape[i] is not written
+ *     out is Some                 d_kind 0 (Escaped); d_escape[i] = escape_ray as rt_refract_rays writes it: origin hit_inside.position,
+ *                                 direction out normalised again, face Front, exclusion { hit_inside.kind, hit_inside.index, Back }
+ *     anything else               d_kind 2 (Trapped)
+ * Where the walk ends without an escape ray (Infinite, Trapped) d_escape[i] is all-zero words; where it ends, d_flags[i] = 0.
+ * max_distance: the reference passes 100.0. */
+int rt_refract_step(const rt_scene *scene, const rt_hit *d_hits, size_t n, float max_distance, const rt_hit *d_inside_hits, rt_ray *d_rays,
+                    uint32_t *d_kind, float *d_travel, uint32_t *d_casts, unsigned char *d_flags, rt_ray *d_escape, void *hip_stream);
 
 /* ---- distributed (stochastic / depth-of-field) pass ----------------------------
 
