@@ -144,7 +144,8 @@ def reference_camera() -> Camera:
 
 
 class Scene:
-    """Device-resident, immutable scene (rt_scene_create / rt_scene_destroy)."""
+    """Device-resident scene (rt_scene_create / rt_scene_destroy).  Its counts, object indices and node tree are fixed; the
+    update_* methods move triangles, spheres and lights and replace materials in place (include/rt_amd.h "scene updates")."""
 
     def __init__(self, world_or_desc):
         desc = world_or_desc.desc() if isinstance(world_or_desc, World) else world_or_desc
@@ -152,6 +153,57 @@ class Scene:
         self.n_lights = int(desc.n_lights)
         self._h = C.c_void_p()
         _capi.check(_capi.amd_lib().rt_scene_create(C.byref(desc), C.byref(self._h)))
+
+    @staticmethod
+    def _device_records(data, record_bytes, name, stream):
+        """``data`` as device memory holding whole records of record_bytes: a contiguous CUDA tensor as it is, a numpy array or
+        ctypes array uploaded first (on ``stream``, default torch's current one).  Returns (tensor, record count, stream)."""
+        import torch
+
+        host = None
+        if torch.is_tensor(data):
+            if not (data.is_cuda and data.is_contiguous()):
+                raise ValueError(f"{name} must be a contiguous CUDA tensor or a numpy array")
+            nbytes = data.numel() * data.element_size()
+        else:
+            host = np.ascontiguousarray(data) if isinstance(data, np.ndarray) else np.frombuffer(data, dtype=np.uint8)
+            nbytes = host.nbytes
+        if nbytes % record_bytes != 0:
+            raise ValueError(f"{name} must hold whole records of {record_bytes} bytes")
+        s = stream if stream is not None else torch.cuda.current_stream()
+        if host is not None:
+            with torch.cuda.stream(s):
+                data = torch.from_numpy(host.reshape(-1).view(np.uint8).copy()).to("cuda")
+            data.record_stream(s)
+        return data, nbytes // record_bytes, s
+
+    def update_vertices(self, first: int, vertices, stream=None) -> None:
+        """rt_scene_update_vertices: triangles first .. first + count - 1 get the 3 * count rt_vertex records (8 floats each: position,
+        normal, uv) of ``vertices`` — a CUDA tensor, or a numpy / ctypes array of Vertex records that is uploaded first — and the node
+        tree is refitted.  Stream-ordered on ``stream`` (default: torch's current stream)."""
+        t, n, s = self._device_records(vertices, 3 * C.sizeof(Vertex), "vertices", stream)
+        _capi.check(_capi.amd_lib().rt_scene_update_vertices(self._h, int(first), n, C.c_void_p(t.data_ptr()), C.c_void_p(s.cuda_stream)))
+
+    def update_spheres(self, first: int, spheres, stream=None) -> None:
+        """rt_scene_update_spheres: spheres first .. get the rt_sphere records (object_index — ignored —, centre, radius: 5 words each)
+        of ``spheres``, a CUDA tensor or a numpy / ctypes array of Sphere records."""
+        t, n, s = self._device_records(spheres, C.sizeof(Sphere), "spheres", stream)
+        _capi.check(_capi.amd_lib().rt_scene_update_spheres(self._h, int(first), n, C.c_void_p(t.data_ptr()), C.c_void_p(s.cuda_stream)))
+
+    def _update_host_records(self, fn, first, records, ctype, stream):
+        import torch
+
+        arr = records if isinstance(records, C.Array) and records._type_ is ctype else (ctype * len(records))(*records)
+        s = stream if stream is not None else torch.cuda.current_stream()
+        _capi.check(fn(self._h, int(first), len(arr), arr, C.c_void_p(s.cuda_stream)))
+
+    def update_lights(self, first: int, lights, stream=None) -> None:
+        """rt_scene_update_lights: lights first .. are replaced by the Light records of ``lights`` (read at the call)."""
+        self._update_host_records(_capi.amd_lib().rt_scene_update_lights, first, lights, Light, stream)
+
+    def update_materials(self, first: int, materials, stream=None) -> None:
+        """rt_scene_update_materials: materials (objects) first .. are replaced by the Material records of ``materials``."""
+        self._update_host_records(_capi.amd_lib().rt_scene_update_materials, first, materials, Material, stream)
 
     def close(self) -> None:
         h, self._h = getattr(self, "_h", None), None

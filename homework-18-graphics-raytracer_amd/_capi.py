@@ -170,6 +170,7 @@ AMD_SYMBOLS = [
     "rt_tree_gate", "rt_tree_split", "rt_tree_spawn", "rt_tree_gather", "rt_tree_fold",
     "rt_light_rays", "rt_light_terms", "rt_light_fold",
     "rt_refract_enter", "rt_refract_step",
+    "rt_scene_update_vertices", "rt_scene_update_spheres", "rt_scene_update_lights", "rt_scene_update_materials",
 ]
 HOST_SYMBOLS = [
     "rt_world_new", "rt_world_free", "rt_world_push_object", "rt_world_push_triangle", "rt_world_push_sphere",
@@ -328,6 +329,10 @@ def amd_lib() -> C.CDLL:
                                          C.c_void_p]
         lib.rt_refract_step.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.rt_scene_update_vertices.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+        lib.rt_scene_update_spheres.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+        lib.rt_scene_update_lights.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(Light), C.c_void_p]
+        lib.rt_scene_update_materials.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(Material), C.c_void_p]
         lib.rt_scene_describe_nodes.argtypes = [C.POINTER(SceneDesc), C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32)]
         _amd = lib
     return _amd

@@ -232,8 +232,8 @@ int rt_scene_create(const rt_scene_desc *desc, rt_scene **out_scene) {
      * k + 1, then each one's skip_to, up to k's own skip_to; the top-level nodes likewise from 0. */
     std::vector<rt::DevSegment> bfs_nodes;
     uint32_t bfs_top = 0u;
+    std::vector<uint32_t> order; /* pre-order index of the node at each level-order position */
     {
-        std::vector<uint32_t> order; /* pre-order index of the node at each level-order position */
         order.reserve(segments.size());
         for (uint32_t k = 0; k < (uint32_t)segments.size(); k = segments[k].skip_to) { order.push_back(k); bfs_top += 1u; }
         bfs_nodes.reserve(segments.size());
@@ -263,17 +263,8 @@ int rt_scene_create(const rt_scene_desc *desc, rt_scene **out_scene) {
     const size_t off_bfs_nodes = off_light_aux + up(desc->n_lights * sizeof(rt::LightAux));
     const size_t off_bfs_soa = off_bfs_nodes + up(bfs_nodes.size() * sizeof(rt::DevSegment));
     const size_t total = off_bfs_soa + up(bfs_soa.size() * sizeof(float)) + 256;
-    /* a spot light's cone edge as a cosine, with margins (rt_shade.h light_asks); anything unusual switches the shortcut off */
     std::vector<rt::LightAux> light_aux(desc->n_lights);
-    for (uint32_t i = 0; i < desc->n_lights; ++i) {
-        light_aux[i].cos_in = std::numeric_limits<float>::infinity();
-        light_aux[i].cos_out = -std::numeric_limits<float>::infinity();
-        const double a = (double)desc->lights[i].angle;
-        if (desc->lights[i].kind == RT_LIGHT_SPOT && a > 1e-3 && a < 3.14) {
-            light_aux[i].cos_in = std::nextafter((float)(cos(a) + 1e-4), std::numeric_limits<float>::infinity());
-            light_aux[i].cos_out = std::nextafter((float)(cos(a) - 1e-4), -std::numeric_limits<float>::infinity());
-        }
-    }
+    for (uint32_t i = 0; i < desc->n_lights; ++i) light_aux[i] = light_aux_of(desc->lights[i]);
 
     std::vector<unsigned char> blob(total, 0);
     if (!tris.empty()) memcpy(&blob[off_tris], tris.data(), tris.size() * sizeof(rt::DevTri));
@@ -289,6 +280,21 @@ int rt_scene_create(const rt_scene_desc *desc, rt_scene **out_scene) {
 
     rt_scene *sc = new (std::nothrow) rt_scene();
     if (!sc) return fail(RT_ERR_OUT_OF_MEMORY, "rt_scene_create: host allocation failed");
+    /* for the scene updates (rt_scene_update.hip): the box, and the triangle range of every node that has a bounding sphere — an inner
+     * node's reaches to the end of the last leaf below it */
+    sc->upd.extent = scene_extent;
+    for (size_t at = 0; at < order.size(); ++at) {
+        const uint32_t k = order[at];
+        const rt::DevSegment &g = segments[k];
+        if (g.n_normals == 0u) continue; /* a plain leaf stays plain */
+        RefitNode n;
+        n.lo = g.first;
+        n.hi = g.first + g.count;
+        for (uint32_t j = k + 1u; g.count == 0u && j < g.skip_to && j < (uint32_t)segments.size(); ++j) n.hi = std::max(n.hi, segments[j].first + segments[j].count);
+        n.seg = k;
+        n.bfs_pos = (uint32_t)at;
+        if (n.hi > n.lo) sc->upd.nodes.push_back(n);
+    }
     sc->d_blob = nullptr;
     hipError_t e = hipGetDevice(&sc->device);
     if (e == hipSuccess) e = hipMalloc(&sc->d_blob, total);
@@ -338,6 +344,9 @@ int rt_scene_destroy(rt_scene *scene) {
         if (kv.second.d_bfs) (void)hipFree(kv.second.d_bfs);
         if (kv.second.d_split) (void)hipFree(kv.second.d_split);
     }
+    if (scene->upd.d_nodes) (void)hipFree(scene->upd.d_nodes);
+    if (scene->upd.h_stage) (void)hipHostFree(scene->upd.h_stage);
+    if (scene->upd.stage_event) (void)hipEventDestroy(scene->upd.stage_event);
     if (scene->d_blob) e = hipFree(scene->d_blob);
     delete scene;
     if (e != hipSuccess) return fail_hip("rt_scene_destroy: hipFree", e);

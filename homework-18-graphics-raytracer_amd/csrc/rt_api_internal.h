@@ -14,6 +14,7 @@
  *   rt_tree_query.hip  the tree loop's rt_tree_*: kernels and entry points in one unit
  *   rt_light_query.hip the light queries' rt_light_*: kernels and entry points in one unit
  *   rt_refract_query.hip the refraction queries' rt_refract_enter / rt_refract_step: kernels and entry points in one unit
+ *   rt_scene_update.hip the scene updates' rt_scene_update_*: kernels and entry points in one unit
  */
 #ifndef RT_API_INTERNAL_H
 #define RT_API_INTERNAL_H
@@ -70,6 +71,40 @@ inline hipError_t ensure_counters(Workspace &ws) {
     return e;
 }
 
+/* What the scene updates (rt_scene_update.hip) need beyond KernelScene.  A node that rt_scene_create built with a bounding sphere — every
+ * inner node, every clustered leaf — is refitted over its unchanged triangle range [lo, hi); leaves that were plain at creation stay
+ * plain and are not listed. */
+struct RefitNode {
+    uint32_t lo, hi;  /* the triangles below the node */
+    uint32_t seg;     /* its index in KernelScene::segments (pre-order) ... */
+    uint32_t bfs_pos; /* ... and in bfs_nodes / bfs_soa (level order) */
+};
+#define RT_REFIT_WAVE_MAX 1024u /* a node of up to this many triangles is refitted by one wave, a larger one by a workgroup */
+struct SceneUpdate {
+    double extent = 0.0;          /* the scene's box at creation: fixed (KernelScene::filter_origin2 travels by value) */
+    std::vector<RefitNode> nodes; /* kept on the host by rt_scene_create, uploaded with the first rt_scene_update_vertices */
+    std::mutex mutex;
+    bool uploaded = false;
+    RefitNode *d_nodes = nullptr; /* n_small nodes for a wave each, then n_large for a workgroup each */
+    uint32_t n_small = 0, n_large = 0;
+    void *h_stage = nullptr;      /* pinned: the light and material records of one call on their way to the device */
+    size_t stage_bytes = 0;
+    hipEvent_t stage_event = nullptr; /* recorded after that call's copies */
+};
+
+/* a spot light's cone edge as a cosine, with margins (rt_shade.h light_asks); anything unusual switches the shortcut off */
+inline rt::LightAux light_aux_of(const rt_light &l) {
+    rt::LightAux aux;
+    aux.cos_in = std::numeric_limits<float>::infinity();
+    aux.cos_out = -std::numeric_limits<float>::infinity();
+    const double a = (double)l.angle;
+    if (l.kind == RT_LIGHT_SPOT && a > 1e-3 && a < 3.14) {
+        aux.cos_in = std::nextafter((float)(cos(a) + 1e-4), std::numeric_limits<float>::infinity());
+        aux.cos_out = std::nextafter((float)(cos(a) - 1e-4), -std::numeric_limits<float>::infinity());
+    }
+    return aux;
+}
+
 struct rt_scene {
     int device;
     void *d_blob; /* one allocation holding every array */
@@ -78,6 +113,7 @@ struct rt_scene {
     uint32_t pwf_workgroups;  /* CUs * resident workgroups of the persistent-wavefront kernel */
     std::mutex ws_mutex;
     std::map<hipStream_t, Workspace> workspaces;
+    SceneUpdate upd;
 };
 
 /* rt_last_error() of the calling thread.  (Thread-local state is reached through functions of the translation unit that defines

@@ -17,7 +17,8 @@
  *
  * Threading (the reference shares `&World` immutably between rayon threads and
  * gives each pixel exclusive `&mut` access to its RNG, main.rs:1096, 1131):
- * an rt_scene is immutable and may be rendered from several host threads at
+ * an rt_scene is changed only by the rt_scene_update_* calls (below: the caller
+ * orders them against renders on other streams) and may be rendered from several host threads at
  * once, each on its own HIP stream (per-(scene, stream) workspaces are created
  * under a lock; the rt_set_* settings are atomics; the profiling hooks keep the
  * event pair of a call in thread-local state).  Calls on ONE stream, and calls
@@ -161,7 +162,7 @@ typedef struct rt_frame {
     uint32_t y_step;         /* >= 1 */
 } rt_frame;
 
-typedef struct rt_scene rt_scene; /* opaque: device-resident, immutable after create */
+typedef struct rt_scene rt_scene; /* opaque: device-resident; changed only by the rt_scene_update_* calls */
 
 /* ---- entry points --------------------------------------------------------- */
 
@@ -739,6 +740,45 @@ int rt_tree_gather(const uint32_t *d_index, const uint32_t *d_count, size_t max_
 int rt_tree_fold(const rt_hit *d_hits, const uint32_t *d_count, size_t n, int32_t depth_left, const float *d_shade, const float *d_weights,
                  const uint32_t *d_refr_kind, const float *d_travel, const float *d_child_values, const uint32_t *d_parent, float *d_out,
                  size_t n_out, void *hip_stream);
+
+/* ---- scene updates: move triangles, spheres and lights in place ------------------------------
+ * An animated sequence changes the world between two frames without rt_scene_destroy + rt_scene_create: the device arrays are
+ * rewritten in place, so the scene's pointers, its per-stream workspaces and every captured graph that names it stay valid.  After
+ * an update every render and query entry point gives, bit for bit, what it gives on a scene freshly created from the updated
+ * description: the values the reference computes per primitive (face normal, plane constant, edges, area, squared radius) are
+ * recomputed on the device in the reference's operation order, and everything the intersection loop only uses to leave work out
+ * (bounding spheres, the node tree's spheres, normals and cones, the plane-sharing bits) is refitted by the rules
+ * rt_scene_create builds it by.
+ *
+ * What never changes: the NUMBER of triangles, spheres, lights and materials, every object_index, and the node tree's topology (which
+ * triangles share a node) — a caller who needs one of them changed re-creates the scene.  The scene's box is the one it was created
+ * with: geometry that moves outside it (a coordinate larger in magnitude than the largest at creation) is rendered correctly but
+ * loses its rejections, and so does every node above it — correct, slower; moving back restores them.  A node whose triangles no
+ * longer qualify (a sliver, a degenerate or non-finite triangle, a normal cone of 60 degrees or more) is always visited until they
+ * do again.  The tree is not re-clustered: after a deformation that scatters the triangles of a node, a fresh rt_scene_create
+ * may render faster.  Not covered: the rt_multi_* forms (their scenes are re-created).
+ *
+ * All four calls are stream-ordered on hip_stream.  The scene's arrays are shared by ALL streams: ordering a render or a query on
+ * another stream after an update (or an update after a render still in flight elsewhere) is the caller's business — an event —
+ * as with any buffer.
+ * Checks, in this order and before any device work: a null scene is RT_ERR_INVALID_ARGUMENT; first + count (in 64 bits) beyond the
+ * array is RT_ERR_INVALID_ARGUMENT; count == 0 is RT_OK and launches nothing; a null data pointer is RT_ERR_INVALID_ARGUMENT.
+ *
+ * rt_scene_update_vertices: d_vertices holds 3 * count rt_vertex records in DEVICE memory, the three vertices of triangles
+ * first .. first + count - 1 (positions, normals and uvs all replace the old ones).  The per-triangle records of the range are
+ * rewritten and the node tree of the WHOLE scene is refitted (whether a node qualifies depends on every triangle below it).  The
+ * first call on a scene allocates (the nodes' triangle ranges go to the device) and cannot be captured into a graph; later calls
+ * allocate nothing and can.
+ * rt_scene_update_spheres: d_spheres holds count rt_sphere records in DEVICE memory; object_index in them is ignored.  Allocates
+ * nothing; can be captured.
+ * rt_scene_update_lights / _materials: count records in HOST memory, validated as rt_scene_create validates them (an unknown kind or
+ * function: RT_ERR_INVALID_ARGUMENT, nothing written), staged in a pinned buffer the scene owns and copied from there on the stream.
+ * The records are read at the call; a call waits for the copies of the call before it; on a stream that is being captured they are
+ * RT_ERR_UNSUPPORTED. */
+int rt_scene_update_vertices(rt_scene *scene, uint32_t first, uint32_t count, const rt_vertex *d_vertices, void *hip_stream);
+int rt_scene_update_spheres(rt_scene *scene, uint32_t first, uint32_t count, const rt_sphere *d_spheres, void *hip_stream);
+int rt_scene_update_lights(rt_scene *scene, uint32_t first, uint32_t count, const rt_light *h_lights, void *hip_stream);
+int rt_scene_update_materials(rt_scene *scene, uint32_t first, uint32_t count, const rt_material *h_materials, void *hip_stream);
 
 /* ---- several GPUs from one process (SURVEY §8e without Python or MPI) -------------------
  * Image rows are interleaved over the entries of `devices` exactly as homework-18-graphics-raytracer_amd/dist.py interleaves
