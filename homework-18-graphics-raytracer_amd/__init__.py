@@ -18,6 +18,8 @@ reference's host-side names on top of them:
     shade_hits_by_light            src/main.rs:407-464 again, light by light from those calls, select_records and cast_rays_indexed
     refract_enter / refract_step   src/main.rs:343-405 (get_refract) opened into the calls between its casts
     refract_rays_by_bounce         src/main.rs:343-405 again, bounce by bounce from those calls, select_records and cast_rays_indexed
+    ray_keys / sort_records / gather_records / scatter_records   the order of a batch: include/rt_amd.h "record ordering"
+    cast_rays_ordered / trace_rays_ordered     cast_rays and trace_rays again, on rays the device put into a coherent order first
     post_process / write_to_file   src/main.rs:748-776
 
 PyTorch is used only for device memory, streams and torch.distributed.
@@ -35,7 +37,7 @@ from ._capi import Camera, Frame, Light, Material, RtError, SceneDesc, Sphere, T
 
 __all__ = [
     "World", "ObjectProxy", "Scene", "Camera", "Frame", "Material", "Light", "RtError", "reference_world",
-    "reference_camera", "render_whitted", "render_whitted_numpy", "make_rays", "cast_rays", "Hits", "camera_rays", "cast_rays_numpy", "trace_rays", "trace_rays_numpy", "shade_hits", "reflect_rays", "refract_rays", "Refractions", "ESCAPED", "INFINITE", "TRAPPED", "HIT_NONE", "shade_hits_numpy", "refract_rays_numpy", "scatter_hits", "scatter_factors", "Scatters", "DIFFUSE", "REFLECTION", "REFRACTION", "scatter_hits_numpy", "scatter_factors_numpy", "select_records", "cast_rays_indexed", "level_split", "level_join", "level_close", "level_fold", "level_finish", "trace_rays_distributed_levels", "tree_gate", "tree_split", "tree_spawn", "tree_gather", "tree_fold", "trace_rays_levels", "default_level_capacity", "light_rays", "light_terms", "light_fold", "shade_hits_by_light", "light_workspace", "LightWorkspace", "WALKING", "refract_enter", "refract_step", "refract_rays_by_bounce", "refract_workspace", "RefractWorkspace", "Rng", "focus_rays", "trace_rays_distributed", "trace_rays_distributed_numpy", "render_distributed", "render_distributed_numpy", "set_option", "options", "post_process_device", "encode_srgb8_device", "post_process", "encode_srgb8", "write_to_file",
+    "reference_camera", "render_whitted", "render_whitted_numpy", "make_rays", "cast_rays", "Hits", "camera_rays", "cast_rays_numpy", "trace_rays", "trace_rays_numpy", "shade_hits", "reflect_rays", "refract_rays", "Refractions", "ESCAPED", "INFINITE", "TRAPPED", "HIT_NONE", "shade_hits_numpy", "refract_rays_numpy", "scatter_hits", "scatter_factors", "Scatters", "DIFFUSE", "REFLECTION", "REFRACTION", "scatter_hits_numpy", "scatter_factors_numpy", "select_records", "cast_rays_indexed", "level_split", "level_join", "level_close", "level_fold", "level_finish", "trace_rays_distributed_levels", "tree_gate", "tree_split", "tree_spawn", "tree_gather", "tree_fold", "trace_rays_levels", "default_level_capacity", "light_rays", "light_terms", "light_fold", "shade_hits_by_light", "light_workspace", "LightWorkspace", "WALKING", "refract_enter", "refract_step", "refract_rays_by_bounce", "refract_workspace", "RefractWorkspace", "ORDER_DIRECTION_MAJOR", "ray_keys", "sort_temp_bytes", "sort_records", "gather_records", "scatter_records", "order_workspace", "OrderWorkspace", "cast_rays_ordered", "trace_rays_ordered", "Rng", "focus_rays", "trace_rays_distributed", "trace_rays_distributed_numpy", "render_distributed", "render_distributed_numpy", "set_option", "options", "post_process_device", "encode_srgb8_device", "post_process", "encode_srgb8", "write_to_file",
     "DEFAULT_OBJ",
 ]
 
@@ -127,6 +129,31 @@ class World:
         _capi.host_lib().rt_world_desc(self._h, C.byref(d))
         d._keepalive = self  # the arrays belong to the world
         return d
+
+    def bounds(self):
+        """(lo, hi), two float32 arrays of 3: the box of the finite vertex positions and of sphere centre -+ radius (non-finite
+        coordinates are left out; an empty world gives zeros).  Host numpy, no device — the box ray_keys measures origins in."""
+        return _desc_bounds(self.desc())
+
+
+def _desc_bounds(desc: SceneDesc):
+    parts = []
+    if desc.n_triangles:
+        words = C.sizeof(Triangle) // 4  # object_index, then 3 vertices of 8 floats: the position leads each
+        tri = np.ctypeslib.as_array(C.cast(desc.triangles, C.POINTER(C.c_float)), shape=(int(desc.n_triangles), words))
+        parts.append(tri[:, 1:].reshape(-1, 3, 8)[:, :, 0:3].reshape(-1, 3))
+    if desc.n_spheres:
+        sph = np.ctypeslib.as_array(C.cast(desc.spheres, C.POINTER(C.c_float)), shape=(int(desc.n_spheres), C.sizeof(Sphere) // 4))
+        parts.append(sph[:, 1:4] - sph[:, 4:5])
+        parts.append(sph[:, 1:4] + sph[:, 4:5])
+    lo, hi = np.zeros(3, dtype=np.float32), np.zeros(3, dtype=np.float32)
+    if parts:
+        pts = np.concatenate(parts).astype(np.float32)
+        for a in range(3):
+            col = pts[:, a][np.isfinite(pts[:, a])]
+            if col.size:
+                lo[a], hi[a] = col.min(), col.max()
+    return lo, hi
 
 
 def reference_world(obj_path: Optional[str] = None) -> World:
@@ -1742,6 +1769,199 @@ def refract_rays_by_bounce(scene: Scene, hits, rays, max_distance: float = 100.0
         torch.ne(kind, WALKING, out=not_walking)
         ended.logical_and_(not_walking)
         travel.masked_fill_(ended, 0.0)  # travel_distance belongs to Escaped alone (main.rs:402)
+    return out
+
+
+# ---- record ordering: coherence keys, a stable sort of an index list, gather and scatter (include/rt_amd.h rt_ray_keys ... rt_scatter_records) ----
+
+ORDER_DIRECTION_MAJOR = 1  # RT_ORDER_DIRECTION_MAJOR: the direction code above the origin code
+
+
+def _words(t, name):
+    """a contiguous CUDA tensor of 4-byte elements, one or two dimensional: (records, words per record)"""
+    import torch
+
+    if not (torch.is_tensor(t) and t.is_cuda and t.is_contiguous() and t.element_size() == 4 and t.dim() in (1, 2)):
+        raise ValueError(f"{name} must be a contiguous CUDA tensor of 4-byte elements, (N,) or (N, words)")
+    return t.shape[0], (1 if t.dim() == 1 else t.shape[1])
+
+
+def _box3(v, name):
+    a = np.asarray(v, dtype=np.float32).reshape(-1)
+    if a.shape != (3,):
+        raise ValueError(f"{name} must hold 3 floats")
+    return (C.c_float * 3)(*a.tolist())
+
+
+def ray_keys(rays, box_lo, box_hi, flags: int = 0, out=None, stream=None):
+    """A 30-bit coherence key per ray (rt_ray_keys): the origin's cell in a 64^3 grid over the box ``box_lo`` .. ``box_hi`` (host
+    values, e.g. World.bounds()) and the direction's cell in a 64^2 grid over the octahedral map, both in Z-order; origin-major, or
+    direction-major with ORDER_DIRECTION_MAJOR.  ``rays``: (N, 11) int32 rt_ray records; returns ``out``, an (N,) int32 CUDA tensor."""
+    import torch
+
+    _records(rays, 11, "rays")
+    n = rays.shape[0]
+    if out is None:
+        out = torch.empty((n,), dtype=torch.int32, device=rays.device)
+    _column(out, torch.int32, n, "out")
+    _capi.check(_capi.amd_lib().rt_ray_keys(_p(rays), n, _box3(box_lo, "box_lo"), _box3(box_hi, "box_hi"), int(flags), _p(out), _stream_ptr(stream)))
+    return out
+
+
+def sort_temp_bytes(n: int) -> int:
+    """The workspace sort_records needs for N records (rt_sort_temp_bytes: host arithmetic)."""
+    return int(_capi.amd_lib().rt_sort_temp_bytes(int(n)))
+
+
+def sort_records(keys, first_bit: int = 0, key_bits: int = 32, index=None, count=None, out=None, temp=None, stream=None):
+    """Stable radix sort of an index list by bits [first_bit, first_bit + key_bits) of ``keys[index]`` (rt_sort_records), ascending,
+    equal keys in input order.  ``keys``: an (N,) int32 CUDA tensor (ray_keys, or any words of the caller's).  ``index``: None for the
+    identity list, or an (N,) int32 CUDA tensor whose first min(count[0], N) entries are the list (``count``: a 1-element int32 CUDA
+    tensor that stays on the device, None for N); an entry >= N sorts last and keeps its value.  Returns ``out`` ((N,) int32, allocated
+    if None, may be ``index`` itself): its first min(count[0], N) entries are the sorted list.  ``temp``: a uint8 CUDA tensor of at
+    least sort_temp_bytes(N) bytes (allocated if None).  Nothing is read back: the call may be captured into a graph."""
+    import torch
+
+    if not (torch.is_tensor(keys) and keys.is_cuda and keys.dtype == torch.int32 and keys.is_contiguous() and keys.dim() == 1):
+        raise ValueError("keys must be a contiguous (N,) int32 CUDA tensor")
+    n = keys.shape[0]
+    if index is not None:
+        _column(index, torch.int32, n, "index")
+    if count is not None:
+        _column(count, torch.int32, 1, "count")
+    if out is None:
+        out = torch.empty((n,), dtype=torch.int32, device=keys.device)
+    _column(out, torch.int32, n, "out")
+    need = sort_temp_bytes(n)
+    if temp is None:
+        temp = torch.empty((need,), dtype=torch.uint8, device=keys.device)
+    if not (torch.is_tensor(temp) and temp.is_cuda and temp.dtype == torch.uint8 and temp.is_contiguous() and temp.dim() == 1):
+        raise ValueError("temp must be a contiguous 1-d uint8 CUDA tensor")
+    _capi.check(_capi.amd_lib().rt_sort_records(_p(keys), n, int(first_bit), int(key_bits), _p(index), _p(count), _p(out), _p(temp), temp.numel(),
+                                                _stream_ptr(stream)))
+    return out
+
+
+def _move_records(src, index, count, out, n_out, max_count):
+    import torch
+
+    n_src, words = _words(src, "src")
+    if not (torch.is_tensor(index) and index.is_cuda and index.dtype == torch.int32 and index.is_contiguous() and index.dim() == 1):
+        raise ValueError("index must be a contiguous (M,) int32 CUDA tensor")
+    if count is not None:
+        _column(count, torch.int32, 1, "count")
+    m = index.shape[0] if max_count is None else int(max_count)
+    if not 0 <= m <= index.shape[0]:
+        raise ValueError("max_count must not exceed the length of index")
+    if out is None:
+        out = torch.zeros((n_out,) + tuple(src.shape[1:]), dtype=src.dtype, device=src.device)
+    if _words(out, "out")[1] != words or out.dtype != src.dtype:
+        raise ValueError("out must hold records of the same words as src")
+    return out, n_src, words, m
+
+
+def gather_records(src, index, count=None, out=None, max_count=None, stream=None):
+    """out[j] = src[index[j]] for j < min(count[0], max_count), all-zero words where index[j] >= N (rt_gather_records).  ``src``: a
+    contiguous CUDA tensor of 4-byte elements, (N,) or (N, words) with 1 to 64 words per record; ``index``: an (M,) int32 CUDA tensor;
+    ``count``: a 1-element int32 CUDA tensor or None (= max_count, default M).  ``out``: (at least max_count, words), allocated if None."""
+    out, n, words, m = _move_records(src, index, count, out, index.shape[0] if max_count is None else int(max_count), max_count)
+    if out.shape[0] < m:
+        raise ValueError("out must hold max_count records")
+    _capi.check(_capi.amd_lib().rt_gather_records(_p(src), 4 * words, n, _p(index), _p(count), m, _p(out), _stream_ptr(stream)))
+    return out
+
+
+def scatter_records(src, index, out, count=None, max_count=None, stream=None):
+    """out[index[j]] = src[j] for j < min(count[0], max_count); an index >= N, the records of ``out`` (required), is skipped
+    (rt_scatter_records).  Records of ``out`` that no entry names are not written; of two entries naming one record either may win."""
+    out, n_src, words, m = _move_records(src, index, count, out, 0, max_count)
+    if n_src < m:
+        raise ValueError("src must hold max_count records")
+    _capi.check(_capi.amd_lib().rt_scatter_records(_p(src), 4 * words, out.shape[0], _p(index), _p(count), m, _p(out), _stream_ptr(stream)))
+    return out
+
+
+class OrderWorkspace:
+    """The buffers of cast_rays_ordered / trace_rays_ordered for up to ``n`` rays, allocated once: keys, the sorted list, its count
+    word (n, written at creation), the sort's workspace and — for trace_rays_ordered — the gathered rays and their values."""
+
+    def __init__(self, n: int, device, trace: bool = False):
+        import torch
+
+        self.n = int(n)
+        self.keys = torch.empty((self.n,), dtype=torch.int32, device=device)
+        self.index = torch.empty((self.n,), dtype=torch.int32, device=device)
+        self.count = torch.full((1,), self.n if self.n < 2 ** 31 else self.n - 2 ** 32, dtype=torch.int32, device=device)
+        self.temp = torch.empty((sort_temp_bytes(self.n),), dtype=torch.uint8, device=device)
+        self.rays = torch.empty((self.n, 11), dtype=torch.int32, device=device) if trace else None
+        self.rgb = torch.empty((self.n, 3), dtype=torch.float32, device=device) if trace else None
+
+
+def order_workspace(n: int, device, trace: bool = False) -> OrderWorkspace:
+    return OrderWorkspace(n, device, trace)
+
+
+def _scene_box(scene: Scene, box):
+    if box is not None:
+        lo, hi = box
+        return lo, hi
+    if getattr(scene, "_bounds", None) is None:
+        scene._bounds = _desc_bounds(scene._desc)  # of the description the scene was created from
+    return scene._bounds
+
+
+def _order_list(scene, rays, box, flags, workspace, trace, stream):
+    n = rays.shape[0]
+    w = workspace if workspace is not None else OrderWorkspace(n, rays.device, trace)
+    if w.n != n or (trace and w.rays is None):
+        raise ValueError("the workspace was made for another number of rays (or without trace=True)")
+    lo, hi = _scene_box(scene, box)
+    ray_keys(rays, lo, hi, flags, out=w.keys, stream=stream)
+    sort_records(w.keys, 0, 30, out=w.index, temp=w.temp, stream=stream)
+    return w
+
+
+def cast_rays_ordered(scene: Scene, rays, box=None, flags: int = 0, out=None, ray_count=None, stream=None, workspace=None):
+    """cast_rays with the waves filled in a coherent order: ray_keys, sort_records, then cast_rays_indexed through the sorted list — a
+    wave takes 64 consecutive list entries, and each hit goes to its ray's own slot, so ``out`` ((N, 13) int32, allocated if None) is
+    cast_rays' record for record, bit for bit.  ``box``: (lo, hi) for the origin cells; None takes the bounds of the description the
+    scene was created from.  ``flags``: 0 or ORDER_DIRECTION_MAJOR.  ``workspace``: order_workspace(N, device), made here if None;
+    after that the function only enqueues library calls."""
+    import torch
+
+    _records(rays, 11, "rays")
+    n = rays.shape[0]
+    if out is None:
+        out = torch.empty((n, 13), dtype=torch.int32, device=rays.device)
+    _records(out, 13, "out")
+    if out.shape[0] != n:
+        raise ValueError("out must have one record per ray")
+    if n == 0:
+        return out
+    w = _order_list(scene, rays, box, flags, workspace, False, stream)
+    cast_rays_indexed(scene, rays, w.index, w.count, out, ray_count=ray_count, stream=stream)
+    return out
+
+
+def trace_rays_ordered(scene: Scene, rays, max_depth: int, contribution: float = 1.0, box=None, flags: int = 0, out=None, ray_count=None,
+                       stream=None, workspace=None):
+    """trace_rays with the waves filled in a coherent order: ray_keys, sort_records, gather_records of the rays, rt_trace_rays on the
+    gathered batch, scatter_records of the values back to the caller's order.  The recursion of a ray does not depend on its
+    neighbours, so ``out`` ((N, 3) float32, allocated if None) and the cast count are trace_rays' bit for bit.  ``workspace``:
+    order_workspace(N, device, trace=True), made here if None."""
+    import torch
+
+    _records(rays, 11, "rays")
+    n = rays.shape[0]
+    if out is None:
+        out = torch.empty((n, 3), dtype=torch.float32, device=rays.device)
+    _rgb(out, n, "out")
+    if n == 0:
+        return out
+    w = _order_list(scene, rays, box, flags, workspace, True, stream)
+    gather_records(rays, w.index, out=w.rays, stream=stream)
+    trace_rays(scene, w.rays, max_depth, contribution, out=w.rgb, ray_count=ray_count, stream=stream)
+    scatter_records(w.rgb, w.index, out, stream=stream)
     return out
 
 

@@ -171,6 +171,7 @@ AMD_SYMBOLS = [
     "rt_light_rays", "rt_light_terms", "rt_light_fold",
     "rt_refract_enter", "rt_refract_step",
     "rt_scene_update_vertices", "rt_scene_update_spheres", "rt_scene_update_lights", "rt_scene_update_materials",
+    "rt_ray_keys", "rt_sort_temp_bytes", "rt_sort_records", "rt_gather_records", "rt_scatter_records",
 ]
 HOST_SYMBOLS = [
     "rt_world_new", "rt_world_free", "rt_world_push_object", "rt_world_push_triangle", "rt_world_push_sphere",
@@ -333,6 +334,13 @@ def amd_lib() -> C.CDLL:
         lib.rt_scene_update_spheres.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
         lib.rt_scene_update_lights.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(Light), C.c_void_p]
         lib.rt_scene_update_materials.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(Material), C.c_void_p]
+        lib.rt_ray_keys.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.c_void_p, C.c_void_p]
+        lib.rt_sort_temp_bytes.argtypes = [C.c_size_t]
+        lib.rt_sort_temp_bytes.restype = C.c_size_t
+        lib.rt_sort_records.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                        C.c_void_p]
+        lib.rt_gather_records.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        lib.rt_scatter_records.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         lib.rt_scene_describe_nodes.argtypes = [C.POINTER(SceneDesc), C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32)]
         _amd = lib
     return _amd

@@ -15,6 +15,7 @@
  *   rt_light_query.hip the light queries' rt_light_*: kernels and entry points in one unit
  *   rt_refract_query.hip the refraction queries' rt_refract_enter / rt_refract_step: kernels and entry points in one unit
  *   rt_scene_update.hip the scene updates' rt_scene_update_*: kernels and entry points in one unit
+ *   rt_order_query.hip the record ordering's rt_ray_keys / rt_sort_records / rt_gather_records / rt_scatter_records: kernels and entry points in one unit
  */
 #ifndef RT_API_INTERNAL_H
 #define RT_API_INTERNAL_H

@@ -741,6 +741,64 @@ int rt_tree_fold(const rt_hit *d_hits, const uint32_t *d_count, size_t n, int32_
                  const uint32_t *d_refr_kind, const float *d_travel, const float *d_child_values, const uint32_t *d_parent, float *d_out,
                  size_t n_out, void *hip_stream);
 
+/* ---- record ordering: coherence keys, a stable sort of an index list, gather and scatter ------------------------------
+ * Every query block above says that a wave takes 64 consecutive records and that rays which travel together should be neighbours, and
+ * leaves the order to the caller.  This block builds such an order on the device: a coherence key per ray, a stable and deterministic
+ * radix sort of an index list by caller keys — the list rt_cast_rays_indexed takes — and a gather and a scatter of fixed-size records
+ * through a list, for the calls that take none (rt_trace_rays, the hit and scatter queries).  INTEGRATION.md writes the two sequences
+ * out; DESIGN.md §3.17 describes the kernels.
+ * Rules of the block: every data pointer is a device pointer unless said otherwise; every call is stream-ordered and asynchronous on
+ * hip_stream (NULL = default stream), allocates nothing and may be captured into a HIP graph at once; records and lists are the
+ * caller's and are validated, never trusted: a list entry at or beyond n names no record.  A device-side count never goes to the host:
+ * grids are sized from the host's bound, and waves beyond the count leave at once.
+ * Checked before any device work, in this order: n >= 2^32 (and max_count >= 2^32) is RT_ERR_UNSUPPORTED; n == 0 (or max_count == 0)
+ * is RT_OK and launches nothing; a null required pointer is RT_ERR_INVALID_ARGUMENT; then the values, each RT_ERR_INVALID_ARGUMENT: the
+ * flags, key_bits == 0 or first_bit + key_bits > 32, record_bytes, temp_bytes, a d_count_in given without d_index_in.
+ * Not covered: rt_multi_* forms; 64-bit keys; sorting inside the render kernels; indexed forms of the hit and scatter queries, since
+ * gather and scatter serve them. */
+
+#define RT_ORDER_DIRECTION_MAJOR 1u /* rt_ray_keys: the direction code above the origin code */
+
+/* A 30-bit coherence key per ray; no scene is read.  box_lo and box_hi are HOST arrays of 3 floats (the scene's bounds, or any box the
+ * caller likes); per axis scale[a] = hi > lo ? 64.0f / (hi - lo) : 0.0f, a NaN giving 0.  Per ray, every operation a single f32 operation
+ * in the order written, nothing fused:
+ *     cell(t)  = 0 if t is NaN or t < 0;  63 if t >= 63;  (uint32)t, truncated, otherwise
+ *     origin   x, y, z = cell((o[a] - lo[a]) * scale[a])
+ *     direction, used as given: s = (|dx| + |dy|) + |dz|, px = dx / s, py = dy / s; if dz < 0.0f (strict: -0.0 and NaN do not fold)
+ *              the pair becomes ((1 - |py|) * sg(px), (1 - |px|) * sg(py)), both from the old values, sg(x) = x >= 0.0f ? 1.0f : -1.0f;
+ *              u = cell((px * 0.5f + 0.5f) * 64.0f), v likewise from py                       (the octahedral map, 64 x 64 cells)
+ *     ocode    bit k of x, y, z at bit 3k, 3k + 1, 3k + 2 (18 bits);  dcode  bit k of u, v at bit 2k, 2k + 1 (12 bits)
+ *     key      (ocode << 12) | dcode, or with RT_ORDER_DIRECTION_MAJOR (dcode << 18) | ocode; bits 30 and 31 are zero
+ * Any other flag bit is RT_ERR_INVALID_ARGUMENT.  Face and exclusion words are not read.  Rays of one origin sort by dcode, a Z-order
+ * over the octahedral map: camera rays come out in tile-like order; rays leaving surfaces sort by where they start. */
+int rt_ray_keys(const rt_ray *d_rays, size_t n, const float box_lo[3], const float box_hi[3], uint32_t flags, uint32_t *d_keys, void *hip_stream);
+
+/* Stable LSD radix sort of an index list by bits [first_bit, first_bit + key_bits) of d_keys[index], ascending; equal keys keep their
+ * input order.  d_keys is any array of n u32: rt_ray_keys' output, or the caller's own (rt_scatter_hits' d_type with key_bits = 2 groups
+ * a level by branch; first_bit = 12, key_bits = 18 orders rt_ray_keys' default key by origin cell alone).
+ * The input list: d_index_in == NULL is the identity list 0 .. n-1 (d_count_in must be NULL too); otherwise d_index_in[0 .. m) with
+ * m = min(*d_count_in, n), a NULL d_count_in meaning n.  d_index_out[0 .. m) receives the permuted list; entries at and beyond m are
+ * unspecified and no more than n words are ever written.  An entry >= n reads no key, sorts behind every valid entry and keeps its
+ * value (rt_cast_rays_indexed and rt_gather_records skip it); entries naming the same record are kept, adjacent, in input order.
+ * d_index_out may alias d_index_in.  The same inputs always give the same output: placement is by ranks — per-tile digit counts, a scan,
+ * in-tile ranks from ballots and LDS; atomics count but never order.  ceil(key_bits / 8) passes of three kernels each.
+ * d_temp: rt_sort_temp_bytes(n) bytes of the caller's, 4-byte aligned, contents unspecified before and after; a smaller temp_bytes is
+ * RT_ERR_INVALID_ARGUMENT.  rt_sort_temp_bytes is host arithmetic, monotone in n, and 0 for n == 0 and for n >= 2^32. */
+size_t rt_sort_temp_bytes(size_t n);
+int rt_sort_records(const uint32_t *d_keys, size_t n, uint32_t first_bit, uint32_t key_bits, const uint32_t *d_index_in, const uint32_t *d_count_in,
+                    uint32_t *d_index_out, void *d_temp, size_t temp_bytes, void *hip_stream);
+
+/* Fixed-size records through a list, as dwords: record_bytes is a multiple of 4 in 4..256 (rt_ray 44, rt_hit 52, rgb 12, a flag word 4)
+ * and the arrays are 4-byte aligned.  Both calls cover j < min(*d_count, max_count), a NULL d_count meaning max_count.
+ *   rt_gather_records    d_dst[j] = d_src[d_index[j]], all-zero words where d_index[j] >= n; d_src holds n records, d_dst max_count
+ *   rt_scatter_records   d_dst[d_index[j]] = d_src[j], an index >= n is skipped; d_src holds max_count records, d_dst n.  Of two entries
+ *                        with the same index either source may win, word by word; the call stays memory-safe
+ * d_src and d_dst must not overlap. */
+int rt_gather_records(const void *d_src, size_t record_bytes, size_t n, const uint32_t *d_index, const uint32_t *d_count, size_t max_count,
+                      void *d_dst, void *hip_stream);
+int rt_scatter_records(const void *d_src, size_t record_bytes, size_t n, const uint32_t *d_index, const uint32_t *d_count, size_t max_count,
+                       void *d_dst, void *hip_stream);
+
 /* ---- scene updates: move triangles, spheres and lights in place ------------------------------
  * An animated sequence changes the world between two frames without rt_scene_destroy + rt_scene_create: the device arrays are
  * rewritten in place, so the scene's pointers, its per-stream workspaces and every captured graph that names it stay valid.  After
