@@ -207,7 +207,7 @@ __global__ void __launch_bounds__(T) refit_nodes(UpdScene sc, const RefitNode *l
     const double radius = sqrt(r2);
     bool ok = bad == 0.0 && isfinite(radius) && radius <= 0.5 * sc.extent && radius >= 1e-3 * sc.extent;
 
-    uint32_t n_normals = 0u;
+    uint32_t n_normals = 0u, n_reps = 0u;
     float cone[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     if (ok) { /* (wave-uniform, and the same in every wave of the workgroup) */
         bool explicit_ok = true;
@@ -234,6 +234,7 @@ __global__ void __launch_bounds__(T) refit_nodes(UpdScene sc, const RefitNode *l
             n_normals += 1u;
         }
         if (!(explicit_ok && n_normals != 0u)) { /* more than 8 plane directions: a cone (rt_api_layout.hip for the derivation of K) */
+            n_reps = n_normals; /* node_stats leaves the representatives it found behind the cone: so does the record here */
             n_normals = 0u;
             const double ml = sqrt(mean[0] * mean[0] + mean[1] * mean[1] + mean[2] * mean[2]);
             ok = ml > 1e-6;
@@ -274,7 +275,7 @@ __global__ void __launch_bounds__(T) refit_nodes(UpdScene sc, const RefitNode *l
         g.r2_hi = r2_hi;
         g.c[0] = c[0]; g.c[1] = c[1]; g.c[2] = c[2];
         for (uint32_t q = 0; q < RT_SEGMENT_NORMALS; ++q) {
-            const bool have = n_normals != RT_SEGMENT_CONE && q < n_normals;
+            const bool have = n_normals != RT_SEGMENT_CONE ? q < n_normals : (q != 0u && q < n_reps);
             g.normals[q][0] = have ? reps[q][0] : (q == 0u ? cone[0] : 0.0f);
             g.normals[q][1] = have ? reps[q][1] : (q == 0u ? cone[1] : 0.0f);
             g.normals[q][2] = have ? reps[q][2] : (q == 0u ? cone[2] : 0.0f);
@@ -440,6 +441,25 @@ int rt_scene_update_materials(rt_scene *scene, uint32_t first, uint32_t count, c
             return fail(RT_ERR_INVALID_ARGUMENT, "rt_scene_update_materials: unknown material function");
     return stage_and_copy(scene, "rt_scene_update_materials", static_cast<hipStream_t>(hip_stream), const_cast<rt_material *>(scene->ks.materials) + first,
                           h_materials, count * sizeof(rt_material), nullptr, nullptr, 0);
+}
+
+/* Diagnostics: the node records as they stand on the device, for tests of the refit (include/rt_amd.h). */
+int rt_diag_scene_nodes(const rt_scene *scene, int which, uint32_t *h_words, size_t cap_words, size_t *n_words) {
+    if (!scene || !n_words || (cap_words && !h_words)) return fail(RT_ERR_INVALID_ARGUMENT, "rt_diag_scene_nodes: null argument");
+    const size_t n_nodes = scene->ks.n_segments;
+    const void *src;
+    size_t bytes;
+    switch (which) {
+    case 0: src = scene->ks.segments; bytes = n_nodes * sizeof(rt::DevSegment); break;
+    case 1: src = scene->ks.bfs_nodes; bytes = n_nodes * sizeof(rt::DevSegment); break;
+    case 2: src = scene->ks.bfs_soa; bytes = (3u * n_nodes + 2u * (size_t)scene->ks.n_triangles) * sizeof(float4); break;
+    default: return fail(RT_ERR_INVALID_ARGUMENT, "rt_diag_scene_nodes: which must be 0 (segments), 1 (bfs_nodes) or 2 (bfs_soa)");
+    }
+    *n_words = bytes / sizeof(uint32_t);
+    if (cap_words < *n_words || bytes == 0u) return RT_OK; /* the size alone */
+    const hipError_t e = hipMemcpy(h_words, src, bytes, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail_hip("rt_diag_scene_nodes: copy", e);
+    return RT_OK;
 }
 
 } /* extern "C" */

@@ -988,6 +988,14 @@ int rt_math_eval_device(int op, const float *h_x, const float *h_y, float *h_out
  * never pair-wise), 0.  Writes at most cap_nodes nodes, always reports the count.  For tests of the builder's invariants. */
 int rt_scene_describe_nodes(const rt_scene_desc *desc, uint32_t *out_words, uint32_t cap_nodes, uint32_t *n_nodes);
 
+/* The node records of a scene as they stand on the device, copied to host memory with a blocking copy: `which` 0 the pre-order
+ * array (csrc/rt_device_scene.h DevSegment, 40 words per node), 1 the same records in level order (an inner node's first / skip_to
+ * name its children there), 2 the 16-byte pieces of the breadth-first walk (per node in level order: first, count, n_normals, r2_hi;
+ * then centre and child count; then the first plane direction or the cone; then two pieces per triangle).  Always reports the
+ * number of 32-bit words in *n_words and copies only when cap_words holds them all.  The caller has synchronised every stream that
+ * updates the scene.  For tests of rt_scene_update_vertices: what it leaves against what rt_scene_create builds. */
+int rt_diag_scene_nodes(const rt_scene *scene, int which, uint32_t *h_words, size_t cap_words, size_t *n_words);
+
 #ifdef __cplusplus
 }
 #endif

@@ -80,23 +80,28 @@ def test_keys_equal_the_numpy_restatement(ref, n):
 BITS = [(0, 1), (0, 8), (0, 9), (7, 10), (12, 18), (0, 30), (0, 32), (31, 1)]
 
 
-def _key_sets(n, g):
+def _key_sets(n, g, only=None):
     four = np.asarray([0x00000000, 0x80000001, 0x3FF00F80, 0xFFFFFFFF], dtype=np.uint32)
-    return {
-        "all equal": np.full(n, 0xA5A5A5A5, dtype=np.uint32),
-        "ascending": (np.arange(n, dtype=np.uint64) * 4099 % (1 << 32)).astype(np.uint32) if n < 1000 else np.sort(g.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32)),
-        "descending": np.sort(g.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32))[::-1].copy(),
-        "random": g.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32),
-        "four values": four[g.integers(0, 4, n)],
+    make = {
+        "all equal": lambda: np.full(n, 0xA5A5A5A5, dtype=np.uint32),
+        "ascending": lambda: (np.arange(n, dtype=np.uint64) * 4099 % (1 << 32)).astype(np.uint32) if n < 1000 else np.sort(g.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32)),
+        "descending": lambda: np.sort(g.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32))[::-1].copy(),
+        "random": lambda: g.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32),
+        "four values": lambda: four[g.integers(0, 4, n)],
     }
+    return {name: fn() for name, fn in make.items() if only is None or name in only}
 
 
 def _expected(keys, n, first, bits, index, m):
     idx = np.asarray(index[:m], dtype=np.uint32).astype(np.int64)
     valid = idx < n
     field = (keys[idx[valid]].astype(np.uint64) >> first) & ((1 << bits) - 1)
-    field = field.astype(np.uint8 if bits <= 8 else np.uint16 if bits <= 16 else np.uint32)
-    return np.concatenate([idx[valid][np.argsort(field, kind="stable")], idx[~valid]]).astype(np.uint32)
+    if bits <= 16 or field.size < (1 << 20):
+        order = np.argsort(field.astype(np.uint8 if bits <= 8 else np.uint16 if bits <= 16 else np.uint32), kind="stable")
+    else:  # the same order from two stable argsorts of 16-bit halves, low then high: numpy sorts those several times faster
+        low = np.argsort((field & 0xFFFF).astype(np.uint16), kind="stable")
+        order = low[np.argsort((field[low] >> 16).astype(np.uint16), kind="stable")]
+    return np.concatenate([idx[valid][order], idx[~valid]]).astype(np.uint32)
 
 
 class _Sorter:
@@ -167,6 +172,54 @@ def test_sort_against_numpy_stable_argsort(n):
                 assert np.array_equal(u32(index_t), index), (what, label, "the input list is only read")
     seen = {lists[(c + c // len(BITS)) % len(lists)][0] for c in range(combo)}
     assert len(seen) == len(lists)
+
+
+LARGE_KEYS = ("random", "four values", "all equal")
+LARGE_BITS = [(0, 8), (0, 9), (0, 32)]
+
+
+@pytest.mark.parametrize("n", list(oq.SORT_LARGE))
+def test_sort_of_more_than_2_to_the_21_entries(n):
+    """capacities at which a tile of sort_scatter_kernel is more than one 2048-entry step (a bucket's position carried from step to step,
+    the waves' counts zeroed again, a ragged last step that ends at a device-side count) and at which the scan takes the whole bucket
+    table — what a 4K frame of rays gets.  Lists rotate over key sets and bit ranges; every one of each is met."""
+    import time
+
+    torch = _torch()
+    t0 = time.perf_counter()
+    tile, tiles = oq.sort_tile(n)
+    assert (tile, tiles) == oq.SORT_LARGE[n]  # a change of the constants fails here instead of moving the test off the path
+    g = np.random.default_rng(n)
+    sorter = _Sorter(n, torch)
+    perm = g.permutation(n).astype(np.uint32)
+    wild = perm.copy()
+    wild[::3] = (n + g.integers(0, 1000, wild[::3].size)).astype(np.uint32)  # the 257th bucket in every step: last, in input order
+    lists = [("identity", None, None, n), ("entries >= n", words(wild), None, n), ("permuted, in place", words(perm), None, n)]
+    if tile > oq.SORT_STEP:
+        m = 5 * tile + oq.SORT_STEP + 5  # ends five entries into the second step of the sixth tile
+        assert m < n and (m % tile) // oq.SORT_STEP == 1 and m % oq.SORT_STEP == 5
+        lists.insert(2, ("count inside a later step", words(perm), words([m]), m))
+    identity = np.arange(n, dtype=np.uint32)
+    combo, seen = 0, set()
+    for name, keys in _key_sets(n, g, only=LARGE_KEYS).items():
+        keys_t = words(keys)
+        for first, bits in LARGE_BITS:
+            label, index_t, count_t, m = lists[(combo + combo // len(lists)) % len(lists)]
+            what = (n, name, first, bits, label)
+            seen |= {name, (first, bits), label}
+            index = identity if index_t is None else u32(index_t).copy()
+            want = _expected(keys, n, first, bits, index, m)
+            in_place = label.endswith("in place")
+            work_t = index_t.clone() if in_place else index_t
+            got = sorter.run(keys_t, first, bits, work_t, count_t, in_place=in_place)
+            assert np.array_equal(got[:m], want), (what, m, np.flatnonzero(got[:m] != want)[:5])
+            if index_t is not None and not in_place:
+                assert np.array_equal(u32(index_t), index), (what, "the input list is only read")
+            if combo == 1:  # once per capacity: the same call again gives the same array
+                assert np.array_equal(sorter.run(keys_t, first, bits, work_t, count_t, in_place=in_place)[:m], got[:m]), (what, "twice")
+            combo += 1
+    assert seen == set(LARGE_KEYS) | set(LARGE_BITS) | {entry[0] for entry in lists}, seen
+    print(f"sort n={n} tile={tile} tiles={tiles}: {combo} sorts against numpy in {time.perf_counter() - t0:.2f} s")
 
 
 def test_sort_keeps_equal_keys_in_input_order_and_groups_a_level_by_branch():
@@ -326,6 +379,24 @@ def test_ordered_casts_equal_cast_rays(ref, batch, which, checked):
         assert np.array_equal(np.sort(u32(workspace.index)), np.arange(n, dtype=np.uint32))  # the list is a permutation
     got = _guarded(lambda: rt.cast_rays_ordered(scene, rays_t, box=((-1, -1, -1), (1, 1, 1))), checked, torch)  # a box and buffers of its own
     assert np.array_equal(u32(got), hits)
+
+
+def test_ordered_casts_of_more_than_2_to_the_21_rays(ref, batch):
+    """a batch whose sort takes tiles of two steps (a 4K frame's worth): the permuted camera rays over and over, then random rays"""
+    torch = _torch()
+    _, desc, scene, _ = ref
+    n = (1 << 21) + 4099
+    assert oq.sort_tile(n) == (4096, 514)
+    rays_t = dev(np.concatenate([np.resize(batch[1][:W * H], (1 << 21, 11)), hq.source_b(desc, 78, 4099)]))
+    assert rays_t.shape[0] == n
+    hits = u32(rt.cast_rays(scene, rays_t))
+    out = torch.full((n, 13), SENTINEL, dtype=torch.int32, device="cuda")
+    workspace = rt.order_workspace(n, "cuda")
+    rt.cast_rays_ordered(scene, rays_t, out=out, workspace=workspace)
+    bad = np.flatnonzero((u32(out) != hits).any(axis=1))
+    assert bad.size == 0, (bad.size, bad[:5])  # bits, NaN distances included
+    assert (hits[:, 0] == 0xFFFFFFFF).sum() > 0 and (hits[:, 0] != 0xFFFFFFFF).sum() > 0
+    assert np.array_equal(np.sort(u32(workspace.index)), np.arange(n, dtype=np.uint32))  # the list is a permutation
 
 
 @pytest.mark.parametrize("checked", [False, True])

@@ -2,7 +2,10 @@
 workspaces exist and are reused) and then updated to B gives, bit for bit, what a scene freshly created from B gives — a 64x48 depth-5
 Whitted frame with its cast count, rt_cast_rays on 20 000 random rays plus rays grazing the moved triangles' bounding spheres (NaN
 distances compared as bits), two depth-of-field epochs at 32x24 with samples, flags, generator records and casts — under the default
-walker and under the breadth-first one.  One Whitted frame per case is also compared with the oracle's render of B."""
+walker and under the breadth-first one.  One Whitted frame per case is also compared with the oracle's render of B.  The node cases
+also read the device's node records back (rt_diag_scene_nodes) and compare them with the fresh scene's word for word: outputs alone
+cannot tell a refit that keeps a node's rejection alive from one that switches every node to "always visit".  A dome of 3200
+triangles reaches the workgroup refit (a node above RT_REFIT_WAVE_MAX = 1024 triangles) and a tree of two inner levels."""
 import ctypes as C
 
 import numpy as np
@@ -71,10 +74,11 @@ def flat(verts):
 BOX, DOME, SQUARE = slice(2, 14), slice(14, 214), slice(214, 216)
 
 
-def dome_triangles(centre=(0.4, 0.2, -0.3), radius=0.9, half_angle=0.6, bulge=1.0):
-    """10 x 10 quads over a spherical cap around +y: 200 triangles whose normals stay within half_angle of the axis"""
+def dome_triangles(centre=(0.4, 0.2, -0.3), radius=0.9, half_angle=0.6, bulge=1.0, grid=10):
+    """grid x grid quads over a spherical cap around +y (10: 200 triangles) whose normals stay within half_angle of the axis; with
+    bulge < 1 the cap is flattened along y and its normals lie closer to the axis"""
     c = np.array(centre)
-    g = np.linspace(-half_angle, half_angle, 11)
+    g = np.linspace(-half_angle, half_angle, grid + 1)
 
     def p(i, j):
         a, b = g[i], g[j]
@@ -82,14 +86,14 @@ def dome_triangles(centre=(0.4, 0.2, -0.3), radius=0.9, half_angle=0.6, bulge=1.
         return c + radius * d / np.linalg.norm(d) if bulge == 1.0 else c + radius * d
 
     tris = []
-    for i in range(10):
-        for j in range(10):
+    for i in range(grid):
+        for j in range(grid):
             q = [p(i, j), p(i, j + 1), p(i + 1, j + 1), p(i + 1, j)]
             tris += [[q[0], q[1], q[2]], [q[0], q[2], q[3]]]
     return np.array(tris)
 
 
-def dome_world():
+def dome_world(**dome_args):
     rng = np.random.default_rng(77)
     w = rt.World()
     w.push_object(_scenes.material(rng, "plain")).push_square([(-4, -0.5, -4), (-4, -0.5, 4), (4, -0.5, 4), (4, -0.5, -4)], [(0, 0), (0, 1), (1, 0), (0, 1)])
@@ -97,7 +101,7 @@ def dome_world():
     for tri in _scenes._box((-1.2, 0.1, 0.6), (0.4, 0.5, 0.3), _scenes._rotation(rng)):
         box.push_flat_triangle(tri, rng.uniform(0, 1, (3, 2)).tolist())
     dome = w.push_object(_scenes.material(rng, "plain"))
-    for tri in dome_triangles():
+    for tri in dome_triangles(**dome_args):
         dome.push_flat_triangle(tri.tolist(), rng.uniform(0, 1, (3, 2)).tolist())
     w.push_object(_scenes.material(rng, "plain")).push_square([(1.0, 0.0, 1.0), (1.0, 0.0, 2.0), (2.0, 0.0, 2.0), (2.0, 0.0, 1.0)], [(0, 0), (0, 1), (1, 1), (1, 0)])
     for _ in range(2):
@@ -120,6 +124,111 @@ def dome():
     assert inner[0, 2] == CONE  # 100 plane directions below it: a cone
     assert (nodes[nodes[:, 0] == DOME.start + 16][:, 2] == 8).all()  # a leaf: 8 quads, each one plane direction — explicit normals
     return w, d, verts
+
+
+# ---- the large world: the same with a dome of 40 x 40 quads — a root above 1024 triangles over inner nodes of 256 over leaves of 16 -----
+
+LARGE_GRID, LARGE_BULGE = 40, 0.8
+LARGE = slice(14, 14 + 2 * LARGE_GRID * LARGE_GRID)
+REFIT_WAVE_MAX = 1024  # csrc/rt_api_internal.h RT_REFIT_WAVE_MAX: a node of more triangles is refitted by refit_nodes<256>
+
+
+def range_ends(nodes):
+    """one past the last triangle below each node of the pre-order array (columns first, count, ..., skip_to as rt_scene_describe_nodes
+    gives them): a leaf's range is [first, first + count), an inner node's runs to the largest end among the nodes before its skip_to
+    (rt_scene_create's rule for the ranges the refit works on)"""
+    end = nodes[:, 0].astype(np.int64) + nodes[:, 1]
+    for k in np.flatnonzero(nodes[:, 1] == 0):
+        end[k] = max(end[k], end[k + 1:nodes[k, 3]].max())
+    return end
+
+
+def large_dome_parts():
+    """(world, description, vertices) of the large world, with its structure asserted: needs no GPU.  With the 10 x 10 dome's plain cap
+    (bulge 1) the corner faces of a 40 x 40 grid at half-angle 0.6 lie 47 degrees off the axis, where the cone's K reaches 1 and
+    rt_scene_create emits no root; flattened to 0.8 the root qualifies."""
+    w = dome_world(grid=LARGE_GRID, bulge=LARGE_BULGE)
+    d = w.desc()
+    obj, verts, _ = arrays_of(d)
+    assert len(obj) == LARGE.stop + 2 and (obj[LARGE] == 2).all() and obj[LARGE.stop] == 3
+    large_dome_structure(nodes_of(d))
+    return w, d, verts
+
+
+def large_dome_structure(nodes, rooted=True):
+    """the tree over the large dome: leaves of 16 below inner nodes of 256 triangles, below (if `rooted`) a root of 3200 that qualifies"""
+    end = range_ends(nodes)
+    inside = (nodes[:, 0] >= LARGE.start) & (end <= LARGE.stop)
+    inner = inside & (nodes[:, 1] == 0)
+    below = end - nodes[:, 0]
+    big = np.flatnonzero(inner & (below > REFIT_WAVE_MAX))
+    assert (big.size >= 1) == rooted, nodes[inner]
+    if rooted:
+        assert nodes[big[0], 0] == LARGE.start and end[big[0]] == LARGE.stop and nodes[big[0], 2] == CONE, nodes[big[0]]
+        nested = [j for j in np.flatnonzero(inner) if big[0] < j < nodes[big[0], 3]]
+        assert len(nested) >= 2 and all(16 < below[j] <= REFIT_WAVE_MAX and nodes[j, 2] == CONE for j in nested), nodes[nested]  # two inner levels
+    leaves = nodes[inside & (nodes[:, 1] != 0)]
+    assert (leaves[:, 1] <= 16).all() and leaves[:, 1].sum() == LARGE.stop - LARGE.start
+    return end
+
+
+@pytest.fixture(scope="module")
+def large_dome():
+    return large_dome_parts()
+
+
+def small_rotation(axis, angle):
+    k = np.asarray(axis, dtype=np.float64) / np.linalg.norm(axis)
+    kx = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
+    return np.eye(3) + np.sin(angle) * kx + (1 - np.cos(angle)) * kx @ kx
+
+
+def large_case(name, va, a):
+    """(description B, the updated triangles, whether a fresh B has A's tree) of the three cases on the large dome; what each is meant
+    to reach is asserted on the description alone, without a GPU"""
+    rows = lambda nodes: nodes[:, [0, 1, 3]]
+    na = nodes_of(a)
+    vb = va.copy()
+    if name == "whole dome moved":  # translated and rotated a little, inside the creation box: every node of the tree, the root's cone turns
+        touched, centre = LARGE, np.array([0.4, 0.2, -0.3])
+        rot = small_rotation((1.0, 0.3, -0.5), 0.12)
+        vb[LARGE] = transformed(va[LARGE], rot, centre - rot @ centre + np.array([0.15, 0.1, -0.2]))
+        assert np.abs(vb[:, :, :3]).max() <= np.abs(va[:, :, :3]).max()
+        nb = nodes_of(desc_with(a, verts=vb))
+        assert np.array_equal(nb, na)
+    elif name == "band nudged":  # 40 leaves under four of the 256-triangle nodes: 8 plane directions each become 16, a cone
+        touched = slice(LARGE.start + 200, LARGE.start + 840)
+        rng = np.random.default_rng(31)
+        vb[touched, :, :3] += rng.normal(0, 0.0005, (touched.stop - touched.start, 3, 3)).astype(np.float32)
+        vb[touched] = flat(vb[touched])
+        nb = nodes_of(desc_with(a, verts=vb))
+        assert np.array_equal(rows(nb), rows(na))
+        changed = np.flatnonzero(nb[:, 2] != na[:, 2])
+        assert len(changed) >= 38 and (na[changed, 2] == 8).all() and (nb[changed, 2] == CONE).all(), (na[changed], nb[changed])
+        assert len({int(np.flatnonzero((na[:k, 1] == 0))[-1]) for k in changed}) >= 3  # ... under different inner nodes
+    elif name == "leaf crumpled":  # each triangle of one leaf turned 69 degrees about its centroid, to alternating sides: no cone holds them
+        touched = slice(LARGE.start + 1600 + 48, LARGE.start + 1600 + 64)
+        for i, t in enumerate(range(touched.start, touched.stop)):
+            rot = small_rotation((1.0, 0.0, 0.0) if i % 4 < 2 else (0.0, 0.0, 1.0), 1.2 if i % 2 else -1.2)
+            centroid = va[t, :, :3].astype(np.float64).mean(axis=0)
+            vb[t:t + 1] = transformed(va[t:t + 1], rot, centroid - rot @ centroid)
+        nb = nodes_of(desc_with(a, verts=vb))
+        ea, eb = large_dome_structure(na), large_dome_structure(nb, rooted=False)
+        key = lambda nodes, end: {(int(n[0]), int(n[1]), int(e)): n for n, e in zip(nodes, end)}
+        ka, kb = key(na, ea), key(nb, eb)
+        gone = sorted(set(ka) - set(kb))
+        # the leaf stays a node of its own, now plain; the root and the inner node above it are gone, every other node is as it was
+        assert kb[(touched.start, 16, touched.stop)][2] == 0 and ka[(touched.start, 16, touched.stop)][2] == 8
+        assert len(gone) == 2 and all(c == 0 and f <= touched.start and touched.stop <= e for f, c, e in gone), gone
+        assert gone[0] == (LARGE.start, 0, LARGE.stop) and set(kb) <= set(ka)
+        assert all((kb[k][2] == ka[k][2]) or k[0] == touched.start for k in kb)
+    else:
+        raise KeyError(name)
+    same_tree = name != "leaf crumpled"
+    return desc_with(a, verts=vb), vb, touched, same_tree
+
+
+LARGE_CASES = ["whole dome moved", "band nudged", "leaf crumpled"]
 
 
 # ---- outputs of a scene ---------------------------------------------------------------------------------------------------------
@@ -179,9 +288,120 @@ def assert_same(got, want, what):
         assert np.array_equal(got[key], want[key]), (what, key)
 
 
-def check_update(desc_a, desc_b, cam, update, moved, seed=1, stream=None, back=False):
+# ---- the node records of a scene ------------------------------------------------------------------------------------------------
+
+INF_BITS = 0x7F800000
+AXIS_STEP = 2.0 ** -23  # one rounding step of a binary32 component of a unit vector, absolute
+K2_RELATIVE = 3e-4
+
+
+def records_of(scene):
+    """rt_diag_scene_nodes: (the pre-order records (N, 40), the level-order records (N, 40), the 16-byte pieces (3 N + 2 T, 4)) as
+    uint32; the scene's stream is synchronised"""
+    lib = _capi.amd_lib()
+    out = []
+    for which in range(3):
+        n = C.c_size_t(0)
+        _capi.check(lib.rt_diag_scene_nodes(scene._h, which, None, 0, C.byref(n)))
+        buf = np.empty(n.value, dtype=np.uint32)
+        _capi.check(lib.rt_diag_scene_nodes(scene._h, which, buf.ctypes.data_as(C.c_void_p), n.value, C.byref(n)))
+        out.append(buf)
+    return out[0].reshape(-1, 40), out[1].reshape(-1, 40), out[2].reshape(-1, 4)
+
+
+def level_order(seg):
+    """the pre-order index of the node at each level-order position (rt_scene_create): the top-level nodes, then every inner node's
+    children one after the other"""
+    count, skip_to, n = seg[:, 1], seg[:, 7], len(seg)
+    order, k = [], 0
+    while k < n:
+        order.append(k)
+        k = int(skip_to[k])
+    at = 0
+    while at < len(order):
+        k = order[at]
+        j = k + 1
+        while count[k] == 0 and j < skip_to[k] and j < n:
+            order.append(j)
+            j = int(skip_to[j])
+        at += 1
+    assert sorted(order) == list(range(n))
+    return np.asarray(order, dtype=np.int64)
+
+
+# per node, the words of its three places side by side: what is fixed at creation, and what a refit derives from the triangles
+STATS_PLACES = (0, 37, 74)  # where the pre-order record's, the level-order record's and the pieces' words start in a row of `stats`
+CONE_COLUMNS = [base + 5 + k for base in (0, 37) for k in range(4)] + [79, 80, 81, 82]  # normals[0][0..3]: the axis and K^2
+
+
+def node_table(rec):
+    seg, bfs, soa = rec
+    n = len(seg)
+    at = np.empty(n, dtype=np.int64)
+    at[level_order(seg)] = np.arange(n)
+    b, p0, p1, p2 = bfs[at], soa[at], soa[n + at], soa[2 * n + at]
+    topo = np.concatenate([seg[:, [0, 1, 7]], b[:, [0, 1, 7]], p0[:, :2], p1[:, 3:]], axis=1)  # first, count, skip_to / children
+    stats = np.concatenate([seg[:, 2:7], seg[:, 8:], b[:, 2:7], b[:, 8:], p0[:, 2:], p1[:, :3], p2], axis=1)
+    assert stats.shape[1] == 83
+    return topo, stats, range_ends(seg[:, [0, 1, 2, 7]]), soa[3 * n:]
+
+
+CONE_FIGURES = {"nodes": 0, "words": 0, "differ": 0, "axis": 0.0, "k2": 0.0}
+
+
+def compare_records(updated, fresh_from, fresh_to, touched, same_tree, what):
+    """the records of `updated` (created as `fresh_from` was, then updated) against those of `fresh_to`, node by node: all words bit for
+    bit but a cone's axis and K^2 — the device adds the normals up in another order than rt_scene_create: a component of the rounded
+    axis moves by one rounding step at most (2^-23 absolute), the half-angle with it by sqrt(3) 2^-23 rad at most, K^2 (K >= 1.01e-3)
+    by 3e-4 relative at most.  Nodes are matched by (first, count, end of range); a node of the updated scene
+      - that is plain in `fresh_from` is never refitted and stays as it is there,
+      - whose counterpart in `fresh_to` qualifies has its words — so it qualifies too,
+      - whose counterpart is a plain leaf, or that has none and lies over a touched triangle, is always visited (n_normals 0, r2_hi +inf),
+      - that has none and lies over no touched triangle has the words of `fresh_from`."""
+    (tu, su, eu, triu), (ta, sa, ea, _), (tb, sb, eb, trib) = (node_table(records_of(s)) for s in (updated, fresh_from, fresh_to))
+    assert np.array_equal(tu, ta), (what, "first, count, skip_to are fixed at creation")
+    assert np.array_equal(triu, trib), (what, "the triangles' planes and bounding spheres")
+    key_b = {(int(t[0]), int(t[1]), int(e)): j for j, (t, e) in enumerate(zip(tb, eb))}
+    if same_tree:
+        assert np.array_equal(ta[:, :3], tb[:, :3]), (what, "the fresh scene has the same tree")
+    cone_cols = np.asarray(CONE_COLUMNS)
+    k2_cols = cone_cols[3::4]
+    for k in range(len(tu)):
+        node = (what, k, tuple(int(x) for x in tu[k, :3]), int(eu[k]))
+        j = key_b.get((int(tu[k, 0]), int(tu[k, 1]), int(eu[k])))
+        if sa[k, 0] == 0:
+            want = sa[k]
+        elif j is not None and sb[j, 0] != 0:
+            want = sb[j]
+            assert (su[k, STATS_PLACES] == want[0]).all(), (node, "qualifies in the fresh scene, so in the updated one", su[k, STATS_PLACES], want[0])
+        elif j is not None or (tu[k, 0] < touched.stop and eu[k] > touched.start):
+            assert (su[k, STATS_PLACES] == 0).all() and (su[k, [p + 1 for p in STATS_PLACES]] == INF_BITS).all(), (node, "always visited", su[k])
+            continue
+        else:
+            want = sa[k]
+        exact = np.ones(83, dtype=bool)
+        if want[0] == CONE:
+            exact[cone_cols] = False
+            got_f, want_f = su[k, cone_cols].view(np.float32).astype(np.float64), want[cone_cols].view(np.float32).astype(np.float64)
+            diff = np.abs(got_f - want_f)
+            is_k2 = np.isin(cone_cols, k2_cols)
+            rel = diff[is_k2] / want_f[is_k2]
+            CONE_FIGURES["nodes"] += 1
+            CONE_FIGURES["words"] += cone_cols.size
+            CONE_FIGURES["differ"] += int((su[k, cone_cols] != want[cone_cols]).sum())
+            CONE_FIGURES["axis"] = max(CONE_FIGURES["axis"], float(diff[~is_k2].max()))
+            CONE_FIGURES["k2"] = max(CONE_FIGURES["k2"], float(rel.max()))
+            assert (diff[~is_k2] <= AXIS_STEP).all() and (rel <= K2_RELATIVE).all(), (node, "cone", got_f, want_f)
+        bad = np.flatnonzero((su[k] != want) & exact)
+        assert bad.size == 0, (node, "columns", bad, su[k, bad], want[bad])
+    print(f"{what}: cone words so far: {CONE_FIGURES['differ']} of {CONE_FIGURES['words']} in {CONE_FIGURES['nodes']} nodes differ, "
+          f"axis by at most {CONE_FIGURES['axis']:.3e} (bound {AXIS_STEP:.3e}), K^2 by at most {CONE_FIGURES['k2']:.3e} relative (bound {K2_RELATIVE:.1e})")
+
+
+def check_update(desc_a, desc_b, cam, update, moved, seed=1, stream=None, back=False, records=None):
     """A rendered, updated to B by `update(scene, stream)`, against a fresh B under both walkers and against the oracle; with `back`,
-    updated to A again by `back(scene, stream)` against a fresh A (what was disqualified qualifies again)."""
+    updated to A again by `back(scene, stream)` against a fresh A (what was disqualified qualifies again).  `records`: (the triangles
+    the update touches, whether a fresh B has A's tree) — then the node records are compared as well (compare_records)."""
     import torch
 
     _, va, _ = arrays_of(desc_a)
@@ -198,9 +418,13 @@ def check_update(desc_a, desc_b, cam, update, moved, seed=1, stream=None, back=F
         assert not (np.array_equal(got["whitted"], before["whitted"]) and np.array_equal(got["hits"], before["hits"])), ("the update shows", opts)
         assert_same(got, outputs(fresh_b, cam, rays, s), ("updated against fresh", opts))
         assert np.array_equal(got["whitted"], want_img.view(np.uint32)) and got["casts"] == want_casts, ("oracle", opts)
+        if records:
+            compare_records(scene, fresh_a, fresh_b, records[0], records[1], ("records, updated against fresh", opts))
         if back:
             back(scene, s)
             again = outputs(scene, cam, rays, s)
+            if records:
+                compare_records(scene, fresh_a, fresh_a, records[0], True, ("records, back against fresh", opts))
             assert_same(again, outputs(fresh_a, cam, rays, s), ("back against fresh", opts))
             assert_same(again, before, ("back against before", opts))
         for sc in (scene, fresh_a, fresh_b):
@@ -256,7 +480,9 @@ def test_node_tree_explicit_normals_and_cone(dome):
     vb[both] = flat(vb[both])
     nodes = nodes_of(desc_with(a, verts=vb))
     assert nodes[nodes[:, 0] == leaf.start][0, 2] == CONE and nodes[nodes[:, 0] == other.start][0, 2] == 1  # what a fresh B has there
-    check_update(a, desc_with(a, verts=vb), _scenes.camera(3), vertex_update(both.start, vb[both]), DOME, seed=2, back=vertex_update(both.start, va[both]))
+    same_tree = np.array_equal(nodes[:, [0, 1, 3]], nodes_of(a)[:, [0, 1, 3]])
+    check_update(a, desc_with(a, verts=vb), _scenes.camera(3), vertex_update(both.start, vb[both]), DOME, seed=2, back=vertex_update(both.start, va[both]),
+                 records=(both, same_tree))
 
 
 def test_node_tree_cone_beyond_60_degrees(dome):
@@ -269,7 +495,20 @@ def test_node_tree_cone_beyond_60_degrees(dome):
     vb[leaf] = flat(vb[leaf])
     nodes = nodes_of(desc_with(a, verts=vb))
     assert not ((nodes[:, 1] == 0) & (nodes[:, 0] == DOME.start)).any()  # a fresh B has no inner node over the dome any more
-    check_update(a, desc_with(a, verts=vb), _scenes.camera(4), vertex_update(leaf.start, vb[leaf]), DOME, seed=3, back=vertex_update(leaf.start, va[leaf]))
+    check_update(a, desc_with(a, verts=vb), _scenes.camera(4), vertex_update(leaf.start, vb[leaf]), DOME, seed=3, back=vertex_update(leaf.start, va[leaf]),
+                 records=(leaf, False))
+
+
+@pytest.mark.parametrize("name", LARGE_CASES)
+def test_large_dome_workgroup_refit_and_two_inner_levels(large_dome, name):
+    """the dome of 3200 triangles: its root is refitted by a workgroup (refit_nodes<256>: the LDS stage of the reductions, loops that wrap,
+    representative rounds across four waves), the nodes below by a wave.  The whole dome moved; a band across four inner nodes nudged
+    (leaves go from explicit normals to a cone); one leaf crumpled beyond 60 degrees (the leaf, its inner node and the root are always
+    visited, and qualify again on the way back) — frames, hits and samples as everywhere, and the node records word for word."""
+    w, a, va = large_dome
+    b, vb, touched, same_tree = large_case(name, va, a)
+    check_update(a, b, _scenes.camera(3), vertex_update(touched.start, vb[touched]), LARGE, seed=8 + LARGE_CASES.index(name),
+                 back=vertex_update(touched.start, va[touched]), records=(touched, same_tree))
 
 
 def test_disqualified_triangles_and_back(dome):

@@ -134,6 +134,37 @@ def test_sort_temp_bytes_is_host_arithmetic():
     assert rt.sort_temp_bytes(4097) == lib.rt_sort_temp_bytes(4097)
 
 
+SORT_STEP, SORT_MAX_TILES, SORT_BUCKETS = 2048, 1024, 257  # csrc/rt_order_query.hip RT_SORT_STEP, RT_SORT_MAX_TILES, RT_SORT_BUCKETS
+
+
+def sort_tile(n):
+    """csrc/rt_order_query.hip sort_tile restated: (entries per tile, tiles) for a list of capacity n"""
+    tile = -(-n // SORT_MAX_TILES)
+    tile = max(-(-tile // SORT_STEP) * SORT_STEP, SORT_STEP)
+    return tile, -(-n // tile)
+
+
+# capacity: (tile, tiles) — the sizes at which the sort takes another path (tests/test_gpu_order_queries.py sorts them)
+SORT_LARGE = {1 << 21: (2048, 1024),            # the full bucket table in the scan; still one step per tile
+              (1 << 21) + 1: (4096, 513),       # two steps; the last tile holds a single entry
+              3 * (1 << 21) + 77: (8192, 769)}  # four steps; a ragged last tile
+
+
+def test_sort_tile_restated_and_the_table_it_needs():
+    lib = _capi.amd_lib()
+    for n, want in SORT_LARGE.items():
+        assert sort_tile(n) == want, (n, sort_tile(n))
+    assert sort_tile((1 << 20) + 37) == (2048, 513) and sort_tile(2_073_600) == (2048, 1013)  # one step: what the suite had before
+    assert sort_tile((1 << 21) + 4099) == (4096, 514)
+    for n in sorted(set(SORT_LARGE) | {1, 2048, 2049, (1 << 21) - 1, (1 << 21) + 4099, (1 << 22) + 1, 1 << 24, (1 << 32) - 1}):
+        tile, tiles = sort_tile(n)
+        assert tile % SORT_STEP == 0 and tiles <= SORT_MAX_TILES and tiles * tile >= n > (tiles - 1) * tile, n
+        # the workspace: two (key field, index) pair buffers of n words each, then 257 words per tile of the bucket table — never
+        # fewer than the tiles the sort launches (the GPU tests put sentinels behind exactly this many bytes)
+        table_words = lib.rt_sort_temp_bytes(n) // 4 - 4 * n
+        assert table_words == min(-(-n // SORT_STEP), SORT_MAX_TILES) * SORT_BUCKETS and table_words >= tiles * SORT_BUCKETS, n
+
+
 def test_ray_keys_arguments_are_checked_before_device_work():
     lib = _capi.amd_lib()
     fake = C.c_void_p(16)  # never dereferenced: every call below is refused on its arguments first, or has nothing to do
