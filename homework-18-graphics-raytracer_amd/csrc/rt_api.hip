@@ -468,7 +468,7 @@ static int render_whitted_frame(const rt_scene *scene, const rt::KernelFrame &kf
              * dynamically, and a workgroup that met expensive ones needs more than the average) */
             pw.node_cap = (uint32_t)(ring - 1024u);
             pw.tile_reserve = 10;
-            pw.arena_stride = (rt::pwf_arena_bytes(pw.node_cap, pw.ring_cap) + 255u) & ~(size_t)255u;
+            pw.arena_stride = (rt::pwf_arena_bytes(pw.node_cap, pw.ring_cap, (uint32_t)(kf.max_depth > 0 ? kf.max_depth : 0)) + 255u) & ~(size_t)255u;
             const size_t need = 512 + (size_t)groups * pw.arena_stride;
             if (need > ws.pwf_bytes) {
                 if (ws.d_pwf) (void)hipFree(ws.d_pwf);

@@ -177,7 +177,10 @@ struct PwParams {
 #define RT_BFS_JOBS_CAP 131072u
 inline size_t pwf_bfs_scratch_words_per_wave() { return 4u * (size_t)RT_BFS_ITEMS_CAP + 2u * (size_t)RT_BFS_JOBS_CAP; }
 int pwf_workgroups_per_cu(uint32_t node_cap, uint32_t ring_cap, bool bfs_walk = false);
-size_t pwf_arena_bytes(uint32_t node_cap, uint32_t ring_cap);
+/* the fold's lists (rt_pwf.hip): regions of node_cap ids, one for every two of the levels 1 .. max_depth - 1 (63 at most: a queued
+ * ray's word has six bits for the depth left) */
+inline uint32_t pwf_fold_list_regions(uint32_t max_depth) { return (max_depth < 64u ? max_depth : 63u) / 2u; }
+size_t pwf_arena_bytes(uint32_t node_cap, uint32_t ring_cap, uint32_t max_depth);
 /* init: zero this launch's block of global words and (re)write the frame description first — needed for a workspace's first
  * launch and whenever the frame description differs from the previous launch's; otherwise the previous launch has left
  * both as this one needs them */

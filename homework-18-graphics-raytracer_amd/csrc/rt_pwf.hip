@@ -21,8 +21,8 @@
  * in the same phase, so the code between casts runs once; an item is a few dozen bytes, so nothing but the cast's own
  * temporaries is live across the intersection loop (80 VGPRs, six waves per SIMD).  When a workgroup's queues are dry
  * it folds its records bottom-up, value = (shade*sc + reflection*rc) + (refraction*decay)*fc (main.rs:516-518) — the
- * nodes that have something below them, listed level by level in LDS first; the others were written complete — and
- * writes its pixels.  Subtrees are pure functions of their rays and every helper (rt_shade.h, rt_cast.h) and the
+ * nodes that have something below them, which the NODE step listed level by level in the arena as it made them; the others
+ * were written complete — and writes its pixels.  Subtrees are pure functions of their rays and every helper (rt_shade.h, rt_cast.h) and the
  * association of the fold are the per-pixel kernel's, so the two paths agree bit for bit with each other and with the
  * oracle (tests/test_gpu_wavefront.py).
  *
@@ -155,6 +155,7 @@ struct PaShared {
     uint32_t gen;             /* bumped whenever items are published */
     uint32_t done;            /* all waves idle at once: the queues are final */
     uint32_t abort;
+    uint32_t fold_count[64];  /* nodes listed for the fold, by level (the depth left: six bits of a queued ray's word) */
 };
 
 /* the five fields of a SHADE item (t: field 0 of its entry, in the arena's ring or in LDS) */
@@ -212,7 +213,8 @@ __device__ __forceinline__ void pa_release_page(uint32_t *released, uint32_t pag
 #ifdef PA_STATS
 /* diagnostic build: wave time by phase (s_memtime ticks, summed over all waves) and chunk / lane counts by item type:
  * [0..3] find work, [4..7] load items, [8..11] the cast, [12..15] after the cast — each by type NODE(0) REFR(1) TILE(2)
- * SHADE(3); [16..19] chunks, [20..23] active lanes; [24] sleep/idle time, [25] fold */
+ * SHADE(3); [16..19] chunks, [20..23] active lanes; [24] sleep/idle time, [25] fold; and the fold's parts per workgroup, in 100 MHz
+ * ticks summed over the workgroups: [26] from the closing barrier to the first level, [27] the levels, [28] the roots, [29] workgroups */
 __device__ unsigned long long pa_phase_stats[32];
 #define PA_TICK() __builtin_readcyclecounter()
 #endif
@@ -258,14 +260,24 @@ __global__ __launch_bounds__(PA_THREADS, BFS ? 2 : PA_MIN_WAVES) void pwf_kernel
     uint32_t *tile_list = reinterpret_cast<uint32_t *>(refr_q + (size_t)pp.ring_cap * 3u); /* (tile, first root node) pairs */
     const uint32_t ring_mask = pp.ring_cap - 1u;
     const uint32_t tile_cap = pp.node_cap / 64u;
-    /* one byte per queued node: the level it is folded at (its depth left) if it has a hit below the depth limit, else 0;
+    /* one byte per node, written for roots only (they are folded by tile): 0xff marks one that is complete as it stands;
      * 16-byte aligned because tile_cap * 8 bytes is a multiple of 16 only for even tile_cap */
-    unsigned char *fold_level = reinterpret_cast<unsigned char *>(((uintptr_t)(tile_list + (size_t)tile_cap * 2u) + 15u) & ~(uintptr_t)15u);
+    unsigned char *root_mark = reinterpret_cast<unsigned char *>(((uintptr_t)(tile_list + (size_t)tile_cap * 2u) + 15u) & ~(uintptr_t)15u);
+    /* The fold's lists: the ids of the nodes that have something below them (roots apart), by the level they are folded at.  Levels
+     * 1 .. max_depth - 1 exist, and two of them share a region of node_cap words, one filling it from the bottom and one from the top:
+     * a node is listed once, so all lists together hold at most node_cap ids and the two never meet — the lists cannot overflow unless
+     * the arena has.  pwf_fold_list_regions is the rule kernel and launcher share. */
+    uint32_t *fold_list = reinterpret_cast<uint32_t *>(root_mark + (((size_t)pp.node_cap + 15u) & ~(size_t)15u));
+    auto fold_slot = [&](uint32_t level, uint32_t i) -> uint32_t * { /* 1 <= level < max_depth, i < node_cap */
+        uint32_t *region = fold_list + (size_t)((level - 1u) >> 1) * pp.node_cap;
+        return region + (((level - 1u) & 1u) != 0u ? pp.node_cap - 1u - i : i);
+    };
     const uint32_t node_pages = (pp.node_cap + 63u) / 64u, ring_pages = pp.ring_cap / 64u;
     uint32_t *ready_n = pa_ready, *ready_s = pa_ready + PA_READY_WORDS(node_pages, PACKED), *ready_f = ready_s + PA_READY_WORDS(ring_pages, PACKED);
     const uint32_t ring_page_mask = ring_pages - 1u;
 
     for (uint32_t i = threadIdx.x; i < PA_READY_WORDS(node_pages, PACKED) + 2u * PA_READY_WORDS(ring_pages, PACKED); i += PA_THREADS) pa_ready[i] = 0u;
+    if (threadIdx.x < 64u) S.fold_count[threadIdx.x] = 0u;
     if (threadIdx.x == 0u) {
         S.n.alloc = S.n.taken = 0u;
         S.f.alloc = S.f.taken = 0u;
@@ -556,10 +568,7 @@ __global__ __launch_bounds__(PA_THREADS, BFS ? 2 : PA_MIN_WAVES) void pwf_kernel
                 }
                 pa_release_page(&S.ln_released, start >> 6, lane);
             } else {
-                id = start + lane;
-                /* a sealed page: the positions after its last item are node ids nobody owns; the fold walks all ids below
-                 * n.alloc, so they must not look like nodes (level 0 is never folded) */
-                if (!active && id < pp.node_cap) fold_level[id] = 0u;
+                id = start + lane; /* (a sealed page: the positions after its last item are node ids nobody owns, and nobody lists) */
                 if (active) a = node_in[pa_entry(id, 2u)], b = node_in[pa_entry(id, 2u) + PA_F(1u)];
             }
             if (active) {
@@ -694,8 +703,8 @@ __global__ __launch_bounds__(PA_THREADS, BFS ? 2 : PA_MIN_WAVES) void pwf_kernel
             const bool bare = active && cr.prim >= 0 && depth > 0u && !below;
             if (active) {
                 if (below) nodes[pa_entry(id, 2u) + PA_F(1u)] = make_uint4(pfu(fc), 0u, rec_cr, rec_cf);
-                /* the level the node is folded at; roots are folded by tile: 0xff marks one that is complete as it stands */
-                fold_level[id] = (unsigned char)(below ? (from_tile ? 0u : depth) : (from_tile ? 0xffu : 0u));
+                /* roots are folded by tile: 0xff marks one that is complete as it stands */
+                if (from_tile) root_mark[id] = (unsigned char)(below ? 0u : 0xffu);
             }
             /* reflection child (get_reflect, main.rs:328-341) */
             if (want_refl && !overflow) {
@@ -719,6 +728,29 @@ __global__ __launch_bounds__(PA_THREADS, BFS ? 2 : PA_MIN_WAVES) void pwf_kernel
             if (refr_in_lds) pa_publish(S.ready_lf, PA_LDS_F_PAGES - 1u, want_refr, k_refr, &S.gen);
             else pa_publish<PACKED>(ready_f, ring_page_mask, want_refr, k_refr, &S.gen);
             if (any_overflow && lane == 0u) { S.abort = 1u; atomicExch(pp.global + PW_G_OVERFLOW, 1u); }
+            /* The fold's list: a node with something below it is appended to the list of its level (the depth left), one LDS atomic
+             * per level present in the chunk — a chunk's nodes are nearly all of one depth — and a plain store of the id.  Here, after the
+             * children are on their way: nothing waits for the list before the workgroup's closing barrier.  `below` is final
+             * now: the REFR steps that later attach the escape child to this record (word 7) and its decay (word 5) change
+             * neither the node's level nor whether it is folded — a node whose ray went into the glass is folded (want_refr) whether
+             * or not anything comes out again.  Roots are folded by tile. */
+            if (!from_tile) {
+                unsigned long long todo = __builtin_amdgcn_ballot_w64(below);
+                while (todo != 0ull) {
+                    const int first = (int)__builtin_ctzll(todo); /* the lowest lane of its level: it reserves for all of them */
+                    const uint32_t l = (uint32_t)__builtin_amdgcn_readlane((int)depth, first);
+                    const bool mine = below && depth == l;
+                    const unsigned long long m = __builtin_amdgcn_ballot_w64(mine);
+                    uint32_t at = 0u;
+                    if ((int)lane == first) at = atomicAdd(&S.fold_count[l & 63u], (uint32_t)__builtin_popcountll(m));
+                    at = (uint32_t)__builtin_amdgcn_readlane((int)at, first) + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+                    if (mine) {
+                        if (at < pp.node_cap) *fold_slot(l, at) = id;
+                        else { S.abort = 1u; atomicExch(pp.global + PW_G_OVERFLOW, 1u); } /* a node is listed once, so this is never reached; were it, the frame falls back */
+                    }
+                    todo &= ~m;
+                }
+            }
             /* get_shade up to its first shadow cast (main.rs:407-433) */
             if (want_shade) {
                 const rt_material &rm = sc.materials[nh.obj];
@@ -888,90 +920,49 @@ __global__ __launch_bounds__(PA_THREADS, BFS ? 2 : PA_MIN_WAVES) void pwf_kernel
     const uint32_t top_first = pp.node_cap - n_top;
     if (!aborted) {
         /* levels 1 .. max_depth-1 (children before parents; level max_depth are the roots, folded by tile below) */
-        auto fold_node = [&](uint32_t id) {
-            const uint4 a = nodes[pa_entry(id, 2u)], b = nodes[pa_entry(id, 2u) + PA_F(1u)];
+        auto fold_value = [&](uint32_t id, const uint4 a, const uint4 b) { /* the record's two fields in registers */
             const float rc = puf(a.w), fc = puf(b.x), decay = puf(b.y);
             V3 reflection = v3(0.0f, 0.0f, 0.0f), refraction = v3(0.0f, 0.0f, 0.0f);
-            if (b.z != PW_NO_CHILD) {
-                const uint4 c = nodes[pa_entry(b.z, 2u)];
-                reflection = v3(puf(c.x), puf(c.y), puf(c.z));
-            }
-            if (b.w != PW_NO_CHILD) {
-                const uint4 c = nodes[pa_entry(b.w, 2u)];
-                refraction = v3(puf(c.x), puf(c.y), puf(c.z)) * decay; /* main.rs:508 */
-            }
+            uint4 cr = make_uint4(0u, 0u, 0u, 0u), cf = cr;
+            if (b.z != PW_NO_CHILD) cr = nodes[pa_entry(b.z, 2u)];
+            if (b.w != PW_NO_CHILD) cf = nodes[pa_entry(b.w, 2u)];
+            if (b.z != PW_NO_CHILD) reflection = v3(puf(cr.x), puf(cr.y), puf(cr.z));
+            if (b.w != PW_NO_CHILD) refraction = v3(puf(cf.x), puf(cf.y), puf(cf.z)) * decay; /* main.rs:508 */
             const V3 value = (v3(puf(a.x), puf(a.y), puf(a.z)) + reflection * rc) + refraction * fc;
             float *rec = reinterpret_cast<float *>(nodes + pa_entry(id, 2u));
             rec[0] = value.x;
             rec[1] = value.y;
             rec[2] = value.z;
         };
-        /* The nodes to fold are listed level by level first — in the LDS that held the SHADE queues, which are empty now — by a
-         * counting sort over the level bytes: two passes over them instead of one per level, and a level's nodes dealt evenly
-         * to the 512 threads, one or two each, all their loads in flight together (the fold is the serial end of a workgroup's
-         * frame: 73 -> ~40 us of a 1.04 ms frame, profiles/r03_ab9.txt).  More nodes than the list holds: the scan per level. */
-        uint32_t *const f_list = reinterpret_cast<uint32_t *>(lds_shade);
-        uint32_t *const f_cursor = reinterpret_cast<uint32_t *>(lds_refr); /* [64]: a level's count, then where its next node goes */
-        uint32_t *const f_start = f_cursor + 64u;                           /* [65] */
-        const uint32_t f_cap = PA_LQ * PA_LDS_PAGES * PA_SHADE_U4 * 64u * 4u;
-        const uint32_t n_all = n_nodes + n_top;
-        static_assert(PA_LDS_F_PAGES * 3u * 64u * 4u >= 129u, "the fold's counters live where the REFR queue was");
-        if (threadIdx.x < 64u) f_cursor[threadIdx.x] = 0u;
-        __syncthreads();
-        for (int pass = 0; pass < 2; ++pass) {
-            for (uint32_t v0 = 0; v0 < n_all; v0 += PA_THREADS) { /* every thread takes part in every trip: wave-wide ballots below */
-                const uint32_t v = v0 + threadIdx.x;
-                const uint32_t id = v < n_nodes ? v : top_first + (v - n_nodes);
-                uint32_t lv = v < n_all ? (uint32_t)fold_level[id] : 0u;
-                if (lv >= max_depth) lv = 0u; /* 0xff: a complete root */
-                unsigned long long todo = __builtin_amdgcn_ballot_w64(lv != 0u);
-                while (todo != 0ull) { /* one LDS atomic per level present in the wave */
-                    const uint32_t l = (uint32_t)__builtin_amdgcn_readlane((int)lv, (int)__builtin_ctzll(todo));
-                    const unsigned long long m = __builtin_amdgcn_ballot_w64(lv == l);
-                    uint32_t base = 0u;
-                    if (lane == (uint32_t)__builtin_ctzll(m)) base = atomicAdd(&f_cursor[l], (uint32_t)__builtin_popcountll(m));
-                    if (pass == 1 && lv == l) {
-                        base = (uint32_t)__builtin_amdgcn_readlane((int)base, (int)__builtin_ctzll(m));
-                        const uint32_t at = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-                        if (at < f_cap) f_list[at] = id;
-                    }
-                    todo &= ~m;
-                }
-            }
-            __syncthreads();
-            if (pass == 0) {
-                if (threadIdx.x == 0u) { /* counts -> starts = cursors */
-                    uint32_t sum = 0u; /* levels 1 .. max_depth - 1 have nodes (max_depth <= 63: six bits of a queued ray's word) */
-                    for (uint32_t l = 0; l <= max_depth && l < 64u; ++l) { const uint32_t c = f_cursor[l]; f_start[l] = sum; f_cursor[l] = sum; sum += c; }
-                    f_start[64] = sum;
-                }
-                __syncthreads();
-                if (f_start[64] > f_cap) break; /* wave-uniform: LDS */
-            }
-        }
-        const bool listed = f_start[64] <= f_cap;
+        auto fold_node = [&](uint32_t id) { fold_value(id, nodes[pa_entry(id, 2u)], nodes[pa_entry(id, 2u) + PA_F(1u)]); };
+        /* The nodes to fold were listed level by level by the NODE steps that made them (fold_slot): a level's nodes are dealt evenly
+         * to the 512 threads, one or two each.  What a thread needs of its first node of a level that does not depend on the levels
+         * below is fetched ahead — the id two levels ahead, the record (shade term, factors, children's ids: final since the main
+         * loop) one level ahead — so that a level costs its children's values, the arithmetic, the store and the barrier.  (Until
+         * round 5 the lists were built here, by a counting sort over one level byte per node: profiles/README.md.) */
+        auto fold_listed = [&](uint32_t level) -> uint32_t { const uint32_t c = S.fold_count[level]; return c < pp.node_cap ? c : pp.node_cap; };
+        auto first_id = [&](uint32_t level) -> uint32_t { /* this thread's first node of a level, if it has one */
+            return level < max_depth && threadIdx.x < fold_listed(level) ? *fold_slot(level, threadIdx.x) : PW_NO_CHILD;
+        };
+#ifdef PA_STATS
+        const unsigned long long st_f0 = __builtin_amdgcn_s_memrealtime();
+#endif
+        uint32_t id0 = first_id(1u), id1 = first_id(2u);
+        uint4 a0 = make_uint4(0u, 0u, 0u, 0u), b0 = a0;
+        if (id0 != PW_NO_CHILD) a0 = nodes[pa_entry(id0, 2u)], b0 = nodes[pa_entry(id0, 2u) + PA_F(1u)];
         for (uint32_t left = 1u; left < max_depth; ++left) {
-            if (listed) {
-                const uint32_t end = f_start[left + 1u];
-                for (uint32_t i = f_start[left] + threadIdx.x; i < end; i += PA_THREADS) fold_node(f_list[i]);
-            } else {
-                for (uint32_t first = threadIdx.x; first < n_all; first += PA_THREADS * 16u) {
-                    uint32_t lv[16];
-#pragma unroll
-                    for (uint32_t k = 0; k < 16u; ++k) {
-                        const uint32_t v = first + k * PA_THREADS;
-                        lv[k] = v < n_all ? (uint32_t)fold_level[v < n_nodes ? v : top_first + (v - n_nodes)] : 0u;
-                    }
-#pragma unroll
-                    for (uint32_t k = 0; k < 16u; ++k) {
-                        if (lv[k] != left) continue;
-                        const uint32_t v = first + k * PA_THREADS;
-                        fold_node(v < n_nodes ? v : top_first + (v - n_nodes));
-                    }
-                }
-            }
+            const uint32_t n = fold_listed(left);
+            const uint32_t id2 = first_id(left + 2u);
+            uint4 a1 = make_uint4(0u, 0u, 0u, 0u), b1 = a1;
+            if (id1 != PW_NO_CHILD) a1 = nodes[pa_entry(id1, 2u)], b1 = nodes[pa_entry(id1, 2u) + PA_F(1u)];
+            if (id0 != PW_NO_CHILD) fold_value(id0, a0, b0);
+            for (uint32_t i = threadIdx.x + PA_THREADS; i < n; i += PA_THREADS) fold_node(*fold_slot(left, i));
             __syncthreads();
+            id0 = id1, a0 = a1, b0 = b1, id1 = id2;
         }
+#ifdef PA_STATS
+        const unsigned long long st_f1 = __builtin_amdgcn_s_memrealtime();
+#endif
         /* the roots, by tile: a wave takes four tiles at a time so that their dependent loads (record, then children)
          * overlap */
         const uint32_t n_started = S.tile_list_count;
@@ -997,7 +988,7 @@ __global__ __launch_bounds__(PA_THREADS, BFS ? 2 : PA_MIN_WAVES) void pwf_kernel
                 if (live[j]) {
                     ra[j] = nodes[pa_entry(id[j], 2u)];
                     rb[j] = make_uint4(0u, 0u, PW_FINAL, PW_NO_CHILD);
-                    if (fold_level[id[j]] != 0xffu) rb[j] = nodes[pa_entry(id[j], 2u) + PA_F(1u)]; /* else complete as it stands: no second field */
+                    if (root_mark[id[j]] != 0xffu) rb[j] = nodes[pa_entry(id[j], 2u) + PA_F(1u)]; /* else complete as it stands: no second field */
                 }
             }
             if (pp.tile_cost != nullptr) { /* what the tile cost, roughly: how many of its pixels recursed */
@@ -1043,6 +1034,15 @@ __global__ __launch_bounds__(PA_THREADS, BFS ? 2 : PA_MIN_WAVES) void pwf_kernel
             }
         }
         if (threadIdx.x == 0u && n_started != 0u) atomicAdd(pp.global + PW_G_TILES_DONE, n_started);
+#ifdef PA_STATS
+        __syncthreads();
+        if (threadIdx.x == 0u) {
+            atomicAdd(&pa_phase_stats[26], st_f0 - st_t2);
+            atomicAdd(&pa_phase_stats[27], st_f1 - st_f0);
+            atomicAdd(&pa_phase_stats[28], __builtin_amdgcn_s_memrealtime() - st_f1);
+            atomicAdd(&pa_phase_stats[29], 1ull);
+        }
+#endif
     }
 #ifdef PA_STATS
     __syncthreads();
@@ -1138,10 +1138,10 @@ __global__ void pwf_init_kernel(uint32_t *global, KernelFrame *frame, const Kern
     if (threadIdx.x == 0u) *frame = fr;
 }
 
-size_t pwf_arena_bytes(uint32_t node_cap, uint32_t ring_cap) {
-    /* node inputs + records, the two rings, the tile list, one "folds at level" byte per node (barrier-free kernel) */
+size_t pwf_arena_bytes(uint32_t node_cap, uint32_t ring_cap, uint32_t max_depth) {
+    /* node inputs + records, the two rings, the tile list, one "complete as it stands" byte per node (read for roots), the fold's lists */
     return ((size_t)node_cap * 4u + (size_t)ring_cap * (3u + PA_SHADE_U4)) * sizeof(uint4) + (size_t)(node_cap / 64u) * 2u * sizeof(uint32_t) +
-           (((size_t)node_cap + 15u) & ~(size_t)15u) + 256u;
+           (((size_t)node_cap + 15u) & ~(size_t)15u) + (size_t)pwf_fold_list_regions(max_depth) * node_cap * sizeof(uint32_t) + 256u;
 }
 
 #ifdef PA_STATS

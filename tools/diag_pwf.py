@@ -54,3 +54,5 @@ for k, n in enumerate(names):
     print(f"  {n:5s} find {ph[k] / total:6.3f}  load {ph[4 + k] / total:6.3f}  cast {ph[8 + k] / total:6.3f}  after {ph[12 + k] / total:6.3f}"
           f"   chunks {ph[16 + k]:8d}  lanes/chunk {ph[20 + k] / chunks:5.1f}  ticks/chunk: load {ph[4 + k] / chunks:7.0f} cast {ph[8 + k] / chunks:7.0f} after {ph[12 + k] / chunks:7.0f}")
 print(f"  idle/sleep {ph[24] / total:6.3f}   fold {ph[25] / total:6.3f}")
+wg = max(1, ph[29])  # the fold's parts, per workgroup (100 MHz ticks), over the two counted frames
+print(f"fold per workgroup, mean: barrier to first level {ph[26] / wg / 100:.1f} us, levels {ph[27] / wg / 100:.1f} us, roots {ph[28] / wg / 100:.1f} us")
