@@ -20,6 +20,8 @@ reference's host-side names on top of them:
     refract_rays_by_bounce         src/main.rs:343-405 again, bounce by bounce from those calls, select_records and cast_rays_indexed
     ray_keys / sort_records / gather_records / scatter_records   the order of a batch: include/rt_amd.h "record ordering"
     cast_rays_ordered / trace_rays_ordered     cast_rays and trace_rays again, on rays the device put into a coherent order first
+    triangle_keys / order_triangles / World.ordered   the order of a mesh: include/rt_amd.h "mesh ordering"
+    unorder_hits / order_rays      triangle indices between an ordered world and the one it was made from
     post_process / write_to_file   src/main.rs:748-776
 
 PyTorch is used only for device memory, streams and torch.distributed.
@@ -37,7 +39,7 @@ from ._capi import Camera, Frame, Light, Material, RtError, SceneDesc, Sphere, T
 
 __all__ = [
     "World", "ObjectProxy", "Scene", "Camera", "Frame", "Material", "Light", "RtError", "reference_world",
-    "reference_camera", "render_whitted", "render_whitted_numpy", "make_rays", "cast_rays", "Hits", "camera_rays", "cast_rays_numpy", "trace_rays", "trace_rays_numpy", "shade_hits", "reflect_rays", "refract_rays", "Refractions", "ESCAPED", "INFINITE", "TRAPPED", "HIT_NONE", "shade_hits_numpy", "refract_rays_numpy", "scatter_hits", "scatter_factors", "Scatters", "DIFFUSE", "REFLECTION", "REFRACTION", "scatter_hits_numpy", "scatter_factors_numpy", "select_records", "cast_rays_indexed", "level_split", "level_join", "level_close", "level_fold", "level_finish", "trace_rays_distributed_levels", "tree_gate", "tree_split", "tree_spawn", "tree_gather", "tree_fold", "trace_rays_levels", "default_level_capacity", "light_rays", "light_terms", "light_fold", "shade_hits_by_light", "light_workspace", "LightWorkspace", "WALKING", "refract_enter", "refract_step", "refract_rays_by_bounce", "refract_workspace", "RefractWorkspace", "ORDER_DIRECTION_MAJOR", "ray_keys", "sort_temp_bytes", "sort_records", "gather_records", "scatter_records", "order_workspace", "OrderWorkspace", "cast_rays_ordered", "trace_rays_ordered", "Rng", "focus_rays", "trace_rays_distributed", "trace_rays_distributed_numpy", "render_distributed", "render_distributed_numpy", "set_option", "options", "post_process_device", "encode_srgb8_device", "post_process", "encode_srgb8", "write_to_file",
+    "reference_camera", "render_whitted", "render_whitted_numpy", "make_rays", "cast_rays", "Hits", "camera_rays", "cast_rays_numpy", "trace_rays", "trace_rays_numpy", "shade_hits", "reflect_rays", "refract_rays", "Refractions", "ESCAPED", "INFINITE", "TRAPPED", "HIT_NONE", "shade_hits_numpy", "refract_rays_numpy", "scatter_hits", "scatter_factors", "Scatters", "DIFFUSE", "REFLECTION", "REFRACTION", "scatter_hits_numpy", "scatter_factors_numpy", "select_records", "cast_rays_indexed", "level_split", "level_join", "level_close", "level_fold", "level_finish", "trace_rays_distributed_levels", "tree_gate", "tree_split", "tree_spawn", "tree_gather", "tree_fold", "trace_rays_levels", "default_level_capacity", "light_rays", "light_terms", "light_fold", "shade_hits_by_light", "light_workspace", "LightWorkspace", "WALKING", "refract_enter", "refract_step", "refract_rays_by_bounce", "refract_workspace", "RefractWorkspace", "ORDER_DIRECTION_MAJOR", "ray_keys", "sort_temp_bytes", "sort_records", "gather_records", "scatter_records", "order_workspace", "OrderWorkspace", "cast_rays_ordered", "trace_rays_ordered", "triangle_keys", "order_triangles_temp_bytes", "order_triangles", "unorder_hits", "order_rays", "Rng", "focus_rays", "trace_rays_distributed", "trace_rays_distributed_numpy", "render_distributed", "render_distributed_numpy", "set_option", "options", "post_process_device", "encode_srgb8_device", "post_process", "encode_srgb8", "write_to_file",
     "DEFAULT_OBJ",
 ]
 
@@ -134,6 +136,33 @@ class World:
         """(lo, hi), two float32 arrays of 3: the box of the finite vertex positions and of sphere centre -+ radius (non-finite
         coordinates are left out; an empty world gives zeros).  Host numpy, no device — the box ray_keys measures origins in."""
         return _desc_bounds(self.desc())
+
+    def ordered(self, box=None):
+        """(World, perm): a new world with this one's triangles grouped by object and, inside an object, in Z-order of their centroids'
+        cells in ``box`` ((lo, hi); None takes bounds()) — the order in which Scene's 16-triangle leaves are patches of the surface
+        (rt_order_triangles_host: include/rt_amd.h "mesh ordering"; needs a device).  Materials, spheres and lights are unchanged.
+        ``perm`` is a numpy uint32 array: perm[j] is this world's index of the new world's triangle j.  The new world is another
+        scene — its casts report its own indices and break ties of equal distance by them: unorder_hits and order_rays map between
+        the two."""
+        d = self.desc()
+        n = int(d.n_triangles)
+        lo, hi = self.bounds() if box is None else box
+        perm = np.zeros(n, dtype=np.uint32)
+        tris = (Triangle * n)()
+        _capi.check(_capi.amd_lib().rt_order_triangles_host(d.triangles, n, _box3(lo, "box lo"), _box3(hi, "box hi"), int(d.n_materials),
+                                                            perm.ctypes.data_as(C.c_void_p), tris))
+        w = World()
+        lib = _capi.host_lib()
+        for i in range(d.n_materials):
+            _capi.check_host(lib.rt_world_push_object(w._h, C.byref(d.materials[i])))
+        for j in range(n):
+            _capi.check_host(lib.rt_world_push_triangle(w._h, tris[j].object_index, tris[j].vertices))
+        for i in range(d.n_spheres):
+            sph = d.spheres[i]
+            _capi.check_host(lib.rt_world_push_sphere(w._h, sph.object_index, sph.center, sph.radius))
+        for i in range(d.n_lights):
+            _capi.check_host(lib.rt_world_push_light(w._h, C.byref(d.lights[i])))
+        return w, perm
 
 
 def _desc_bounds(desc: SceneDesc):
@@ -1963,6 +1992,93 @@ def trace_rays_ordered(scene: Scene, rays, max_depth: int, contribution: float =
     trace_rays(scene, w.rays, max_depth, contribution, out=w.rgb, ray_count=ray_count, stream=stream)
     scatter_records(w.rgb, w.index, out, stream=stream)
     return out
+
+
+# ---- mesh ordering: triangle keys and the permutation that makes the node tree selective (include/rt_amd.h rt_triangle_keys, rt_order_triangles) ----
+
+TRIANGLE_WORDS = C.sizeof(Triangle) // 4  # 25: the object word, then three vertices of eight floats
+
+
+def triangle_keys(triangles, box_lo, box_hi, out=None, objects=None, stream=None):
+    """A 30-bit Z-order key per triangle (rt_triangle_keys): the cell of its centroid in a 1024^3 grid over the box ``box_lo`` ..
+    ``box_hi`` (host values, e.g. World.bounds()).  ``triangles``: (N, 25) int32 rt_triangle records; returns ``out``, an (N,) int32
+    CUDA tensor.  ``objects``: None, or an (N,) int32 CUDA tensor that receives the object indices."""
+    import torch
+
+    _records(triangles, TRIANGLE_WORDS, "triangles")
+    n = triangles.shape[0]
+    if out is None:
+        out = torch.empty((n,), dtype=torch.int32, device=triangles.device)
+    _column(out, torch.int32, n, "out")
+    if objects is not None:
+        _column(objects, torch.int32, n, "objects")
+    _capi.check(_capi.amd_lib().rt_triangle_keys(_p(triangles), n, _box3(box_lo, "box_lo"), _box3(box_hi, "box_hi"), _p(out), _p(objects),
+                                                 _stream_ptr(stream)))
+    return out
+
+
+def order_triangles_temp_bytes(n: int) -> int:
+    """The workspace order_triangles needs for N triangles (rt_order_triangles_temp_bytes: host arithmetic)."""
+    return int(_capi.amd_lib().rt_order_triangles_temp_bytes(int(n)))
+
+
+def order_triangles(triangles, box_lo, box_hi, n_objects: int, out=None, ordered=None, temp=None, stream=None):
+    """The permutation that groups triangles by object and, inside an object, by triangle_keys' Z-order, equal pairs in input order
+    (rt_order_triangles: the keys, two stable sorts and a gather as one call).  ``triangles``: (N, 25) int32 rt_triangle records;
+    ``n_objects``: the world's number of materials.  Returns ``out`` ((N,) int32, allocated if None): out[j] is the old index of the
+    triangle at new position j.  ``ordered``: None, or an (N, 25) int32 CUDA tensor that receives triangles[out].  ``temp``: a uint8
+    CUDA tensor of at least order_triangles_temp_bytes(N) bytes (allocated if None).  Nothing is read back: the call may be captured."""
+    import torch
+
+    _records(triangles, TRIANGLE_WORDS, "triangles")
+    n = triangles.shape[0]
+    if out is None:
+        out = torch.empty((n,), dtype=torch.int32, device=triangles.device)
+    _column(out, torch.int32, n, "out")
+    if ordered is not None:
+        _records(ordered, TRIANGLE_WORDS, "ordered")
+        if ordered.shape[0] != n:
+            raise ValueError("ordered must have one record per triangle")
+    need = order_triangles_temp_bytes(n)
+    if temp is None:
+        temp = torch.empty((need,), dtype=torch.uint8, device=triangles.device)
+    if not (torch.is_tensor(temp) and temp.is_cuda and temp.dtype == torch.uint8 and temp.is_contiguous() and temp.dim() == 1):
+        raise ValueError("temp must be a contiguous 1-d uint8 CUDA tensor")
+    _capi.check(_capi.amd_lib().rt_order_triangles(_p(triangles), n, _box3(box_lo, "box_lo"), _box3(box_hi, "box_hi"), int(n_objects), _p(out),
+                                                   _p(ordered), _p(temp), temp.numel(), _stream_ptr(stream)))
+    return out
+
+
+def _perm(perm):
+    p = np.asarray(perm)
+    if p.ndim != 1 or p.dtype.kind not in "ui":
+        raise ValueError("perm must be a 1-d integer array")
+    return p.astype(np.int64)
+
+
+def unorder_hits(hits_np, perm):
+    """Hits cast on an ordered world (World.ordered) in the numbering of the world it was made from: a copy of ``hits_np`` (HIT_DTYPE
+    or (N, 13) words) in which ``index`` of every triangle hit is perm[index].  Sphere hits and HIT_NONE records are untouched."""
+    h = _host_records(hits_np, HIT_DTYPE, 13, "hits").copy()
+    p = _perm(perm)
+    index = h["index"].astype(np.int64)
+    mine = (h["kind"] == TRIANGLE) & (index < p.size)
+    h["index"][mine] = p[index[mine]].astype(np.uint32)
+    return h
+
+
+def order_rays(rays_np, perm):
+    """Rays meant for a world in the numbering of its ordered form (World.ordered): a copy of ``rays_np`` (RAY_DTYPE or (N, 11) words) in
+    which a triangle ``exclude_index`` i becomes the j with perm[j] == i.  An index outside the array stays as it is (it excludes
+    nothing either way); sphere exclusions and rays without one are untouched."""
+    r = _host_records(rays_np, RAY_DTYPE, 11, "rays").copy()
+    p = _perm(perm)
+    inverse = np.empty(p.size, dtype=np.int64)
+    inverse[p] = np.arange(p.size)
+    index = r["exclude_index"].astype(np.int64)
+    mine = (r["has_exclude"] != 0) & (r["exclude_kind"] == TRIANGLE) & (index < p.size)
+    r["exclude_index"][mine] = inverse[index[mine]].astype(np.uint32)
+    return r
 
 
 def render_distributed_numpy(scene: Scene, camera: Camera, frame: Frame, rng: Rng, n_epochs: int, img: np.ndarray,

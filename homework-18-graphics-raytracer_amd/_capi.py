@@ -172,6 +172,7 @@ AMD_SYMBOLS = [
     "rt_refract_enter", "rt_refract_step",
     "rt_scene_update_vertices", "rt_scene_update_spheres", "rt_scene_update_lights", "rt_scene_update_materials",
     "rt_ray_keys", "rt_sort_temp_bytes", "rt_sort_records", "rt_gather_records", "rt_scatter_records",
+    "rt_triangle_keys", "rt_order_triangles_temp_bytes", "rt_order_triangles", "rt_order_triangles_host",
     "rt_diag_scene_nodes",
 ]
 HOST_SYMBOLS = [
@@ -342,6 +343,12 @@ def amd_lib() -> C.CDLL:
                                         C.c_void_p]
         lib.rt_gather_records.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         lib.rt_scatter_records.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        lib.rt_triangle_keys.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.rt_order_triangles_temp_bytes.argtypes = [C.c_size_t]
+        lib.rt_order_triangles_temp_bytes.restype = C.c_size_t
+        lib.rt_order_triangles.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.rt_order_triangles_host.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.c_void_p, C.c_void_p]
         lib.rt_scene_describe_nodes.argtypes = [C.POINTER(SceneDesc), C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32)]
         lib.rt_diag_scene_nodes.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
         _amd = lib

@@ -16,6 +16,7 @@
  *   rt_refract_query.hip the refraction queries' rt_refract_enter / rt_refract_step: kernels and entry points in one unit
  *   rt_scene_update.hip the scene updates' rt_scene_update_*: kernels and entry points in one unit
  *   rt_order_query.hip the record ordering's rt_ray_keys / rt_sort_records / rt_gather_records / rt_scatter_records: kernels and entry points in one unit
+ *   rt_mesh_order.hip  the mesh ordering's rt_triangle_keys / rt_order_triangles: the key kernel and entry points that call rt_order_query.hip's
  */
 #ifndef RT_API_INTERNAL_H
 #define RT_API_INTERNAL_H

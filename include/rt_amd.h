@@ -799,6 +799,54 @@ int rt_gather_records(const void *d_src, size_t record_bytes, size_t n, const ui
 int rt_scatter_records(const void *d_src, size_t record_bytes, size_t n, const uint32_t *d_index, const uint32_t *d_count, size_t max_count,
                        void *d_dst, void *hip_stream);
 
+/* ---- mesh ordering: triangle keys and the permutation that makes the node tree selective ------------------------------
+ * rt_scene_create builds its node tree over the triangles IN THE ORDER GIVEN: within each run of equal object_index a leaf is 16
+ * consecutive triangles, leaves are grouped 16 by 16, and a node can be skipped only if its bounding sphere is small and its plane
+ * directions are few or lie in a narrow cone.  A mesh whose consecutive triangles are neighbours on the surface (a subdivision that
+ * emits siblings together) gets such nodes; an exporter's face order, a simulation's particle order or a concatenation of parts
+ * does not — every leaf spans the object, nothing is skipped, and the walk is brute force.  This block produces the order: a Z-order
+ * key per triangle and, from the record ordering above, the stable permutation by (object_index, key).
+ * The order is a tool the caller applies, never rt_scene_create behind the caller's back: every entry point reports primitive
+ * indices, and among accepted triangles at equal distance World::cast keeps the later one (main.rs:229-233), so a reordered
+ * description is ANOTHER SCENE.  Each of the two is bit-identical to the reference's cast of its own description; mapped through the
+ * permutation they agree everywhere except at such ties (same distance bits, another triangle).  The permutation is handed back so
+ * that indices can be mapped: hits back through d_perm, a ray's triangle exclusion forward through its inverse.
+ * The same call serves a scene that rt_scene_update_vertices has deformed until its nodes no longer reject: order the moved
+ * description and re-create.  Re-clustering a live scene in place is not covered.
+ * Rules as in the record-ordering block: device pointers unless said otherwise, stream-ordered on hip_stream, no allocation, may be
+ * captured into a HIP graph at once.  Checked before any device work, in this order: n >= 2^32 is RT_ERR_UNSUPPORTED; n == 0 is RT_OK
+ * and launches nothing; a null required pointer is RT_ERR_INVALID_ARGUMENT; then temp_bytes, RT_ERR_INVALID_ARGUMENT.
+ * Not covered: ordering inside rt_scene_create, or original indices kept inside the kernels; spheres; rt_multi_* forms; 64-bit keys. */
+
+/* A 30-bit key per triangle: the cell of its centroid in a 1024^3 grid over the box, in Z-order.  box_lo and box_hi are HOST arrays of
+ * 3 floats (World.bounds, or any box); per axis scale[a] = hi > lo ? 1024.0f / (hi - lo) : 0.0f, a NaN giving 0.  Per triangle with
+ * vertex positions p0, p1, p2, every operation a single f32 operation in the order written, nothing fused:
+ *     c[a]     = ((p0[a] + p1[a]) + p2[a]) / 3.0f
+ *     cell(t)  = 0 if t is NaN or t < 0;  1023 if t >= 1023;  (uint32)t, truncated, otherwise
+ *     x, y, z  = cell((c[a] - lo[a]) * scale[a])
+ *     key      = bit k of x, y, z at bit 3k, 3k + 1, 3k + 2; bits 30 and 31 are zero
+ * NaN, infinite and degenerate triangles get a cell by these rules.  d_objects, which may be NULL, receives d_triangles[i].object_index.
+ * Only the positions and the object word are read (as dwords: an rt_triangle is 100 bytes and 4-byte aligned). */
+int rt_triangle_keys(const rt_triangle *d_triangles, size_t n, const float box_lo[3], const float box_hi[3], uint32_t *d_keys, uint32_t *d_objects,
+                     void *hip_stream);
+
+/* The whole sequence as one call: rt_triangle_keys; rt_sort_records of the identity list by the 30 key bits; a second, stable
+ * rt_sort_records of that list by object_index over max(1, bits of n_objects - 1) bits; and, with d_ordered_or_null given,
+ * rt_gather_records(d_triangles, 100, ...) into it.  d_perm[j] (n words) is the OLD index of the triangle at NEW position j: the list
+ * is grouped by object, ascending, and inside an object it is in Z-order of the centroid cells; equal (object, key) pairs keep their
+ * input order.  The same inputs always give the same words.  d_ordered_or_null (n records) must not overlap d_triangles.
+ * n_objects is the description's n_materials.  An object_index >= n_objects cannot be refused here, since the records are on the
+ * device: such triangles sort by the low bits of their object word, and rt_scene_create rejects the description as it always did.
+ * d_temp: rt_order_triangles_temp_bytes(n) bytes, 4-byte aligned — the keys, the object words and rt_sort_temp_bytes(n) — contents
+ * unspecified before and after; the size is host arithmetic, monotone in n, and 0 for n == 0 and for n >= 2^32. */
+size_t rt_order_triangles_temp_bytes(size_t n);
+int rt_order_triangles(const rt_triangle *d_triangles, size_t n, const float box_lo[3], const float box_hi[3], uint32_t n_objects, uint32_t *d_perm,
+                       rt_triangle *d_ordered_or_null, void *d_temp, size_t temp_bytes, void *hip_stream);
+/* The same on HOST arrays: allocates, copies, runs, synchronises the device and copies back (h_perm: n words; h_ordered_or_null: n
+ * records or NULL).  Without a device it returns the status and writes nothing. */
+int rt_order_triangles_host(const rt_triangle *h_triangles, size_t n, const float lo[3], const float hi[3], uint32_t n_objects, uint32_t *h_perm,
+                            rt_triangle *h_ordered_or_null);
+
 /* ---- scene updates: move triangles, spheres and lights in place ------------------------------
  * An animated sequence changes the world between two frames without rt_scene_destroy + rt_scene_create: the device arrays are
  * rewritten in place, so the scene's pointers, its per-stream workspaces and every captured graph that names it stay valid.  After
@@ -814,7 +862,7 @@ int rt_scatter_records(const void *d_src, size_t record_bytes, size_t n, const u
  * loses its rejections, and so does every node above it — correct, slower; moving back restores them.  A node whose triangles no
  * longer qualify (a sliver, a degenerate or non-finite triangle, a normal cone of 60 degrees or more) is always visited until they
  * do again.  The tree is not re-clustered: after a deformation that scatters the triangles of a node, a fresh rt_scene_create
- * may render faster.  Not covered: the rt_multi_* forms (their scenes are re-created).
+ * of the description put in order again (rt_order_triangles, "mesh ordering" above) may render faster.  Not covered: the rt_multi_* forms (their scenes are re-created).
  *
  * All four calls are stream-ordered on hip_stream.  The scene's arrays are shared by ALL streams: ordering a render or a query on
  * another stream after an update (or an update after a render still in flight elsewhere) is the caller's business — an event —
