@@ -250,8 +250,7 @@ class Scene:
         import torch
 
         arr = records if isinstance(records, C.Array) and records._type_ is ctype else (ctype * len(records))(*records)
-        s = stream if stream is not None else torch.cuda.current_stream()
-        _capi.check(fn(self._h, int(first), len(arr), arr, C.c_void_p(s.cuda_stream)))
+        _capi.check(fn(self._h, int(first), len(arr), arr, _stream_ptr(stream)))
 
     def update_lights(self, first: int, lights, stream=None) -> None:
         """rt_scene_update_lights: lights first .. are replaced by the Light records of ``lights`` (read at the call)."""
@@ -273,6 +272,29 @@ class Scene:
             pass
 
 
+def _stream_ptr(stream):
+    """``stream`` (default: torch's current stream) as the void pointer the C entry points take"""
+    import torch
+
+    s = stream if stream is not None else torch.cuda.current_stream()
+    return C.c_void_p(s.cuda_stream)
+
+
+def _p(t):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _out_tensor(out, shape, dtype, device, name="out"):
+    """``out`` if the caller gave one — it must be a contiguous CUDA tensor of this shape and dtype — or a new one on ``device``"""
+    import torch
+
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if not (torch.is_tensor(out) and out.is_cuda and out.dtype == dtype and out.is_contiguous() and tuple(out.shape) == tuple(shape)):
+        raise ValueError(f"{name} must be a contiguous {tuple(shape)} {dtype} CUDA tensor")
+    return out
+
+
 def render_whitted(scene: Scene, camera: Camera, frame: Frame, out=None, ray_count=None, stream=None):
     """Whitted pass over one tile into device memory (src/main.rs:1090-1104).
 
@@ -287,15 +309,10 @@ def render_whitted(scene: Scene, camera: Camera, frame: Frame, out=None, ray_cou
         out = torch.empty((rows, cols, 3), dtype=torch.float32, device="cuda")
     if not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == rows * cols * 3):
         raise ValueError("out must be a contiguous float32 CUDA tensor with rows*cols*3 elements")
-    cnt_ptr = None
-    if ray_count is not None:
-        if not (ray_count.is_cuda and ray_count.dtype == torch.int64 and ray_count.numel() == 1):
-            raise ValueError("ray_count must be a 1-element int64 CUDA tensor")
-        cnt_ptr = C.c_void_p(ray_count.data_ptr())
-    s = stream if stream is not None else torch.cuda.current_stream()
+    cnt_ptr = _count_ptr(ray_count)
     _capi.check(
         _capi.amd_lib().rt_render_whitted(
-            scene._h, C.byref(camera), C.byref(frame), C.c_void_p(out.data_ptr()), cnt_ptr, C.c_void_p(s.cuda_stream)
+            scene._h, C.byref(camera), C.byref(frame), C.c_void_p(out.data_ptr()), cnt_ptr, _stream_ptr(stream)
         )
     )
     return out
@@ -378,13 +395,8 @@ def cast_rays(scene: Scene, rays, out=None, stream=None):
 
     _records(rays, 11, "rays")
     n = rays.shape[0]
-    if out is None:
-        out = torch.empty((n, 13), dtype=torch.int32, device=rays.device)
-    _records(out, 13, "out")
-    if out.shape[0] != n:
-        raise ValueError("out must have one record per ray")
-    s = stream if stream is not None else torch.cuda.current_stream()
-    _capi.check(_capi.amd_lib().rt_cast_rays(scene._h, C.c_void_p(rays.data_ptr()), n, C.c_void_p(out.data_ptr()), C.c_void_p(s.cuda_stream)))
+    out = _out_tensor(out, (n, 13), torch.int32, rays.device)
+    _capi.check(_capi.amd_lib().rt_cast_rays(scene._h, C.c_void_p(rays.data_ptr()), n, C.c_void_p(out.data_ptr()), _stream_ptr(stream)))
     return out
 
 
@@ -421,26 +433,15 @@ def camera_rays(camera: Camera, frame: Frame, out=None, stream=None):
     import torch
 
     n = frame.rows * frame.cols
-    if out is None:
-        out = torch.empty((n, 11), dtype=torch.int32, device="cuda")
-    _records(out, 11, "out")
-    if out.shape[0] != n:
-        raise ValueError("out must have rows * cols records")
-    s = stream if stream is not None else torch.cuda.current_stream()
-    _capi.check(_capi.amd_lib().rt_camera_rays(C.byref(camera), C.byref(frame), C.c_void_p(out.data_ptr()), C.c_void_p(s.cuda_stream)))
+    out = _out_tensor(out, (n, 11), torch.int32, "cuda")
+    _capi.check(_capi.amd_lib().rt_camera_rays(C.byref(camera), C.byref(frame), C.c_void_p(out.data_ptr()), _stream_ptr(stream)))
     return out
 
 
 def cast_rays_numpy(scene: Scene, rays_np) -> np.ndarray:
     """Host-buffer convenience (rt_cast_rays_host, synchronous): rays as a RAY_DTYPE structured array or an (N, 11) array of 4-byte
     words; returns the hits as a HIT_DTYPE structured array."""
-    a = np.asarray(rays_np)
-    if a.dtype == RAY_DTYPE:
-        a = np.ascontiguousarray(a).reshape(-1)
-    elif a.ndim == 2 and a.shape[1] == 11 and a.dtype.itemsize == 4:
-        a = np.ascontiguousarray(a).view(RAY_DTYPE).reshape(-1)
-    else:
-        raise ValueError("expected a RAY_DTYPE array or an (N, 11) array of 4-byte words")
+    a = _host_records(rays_np, RAY_DTYPE, 11, "rays")
     hits = np.zeros(a.shape[0], dtype=HIT_DTYPE)
     _capi.check(_capi.amd_lib().rt_cast_rays_host(scene._h, a.ctypes.data_as(C.c_void_p), a.shape[0], hits.ctypes.data_as(C.c_void_p)))
     return hits
@@ -458,31 +459,17 @@ def trace_rays(scene: Scene, rays, max_depth: int, contribution: float = 1.0, ou
 
     _records(rays, 11, "rays")
     n = rays.shape[0]
-    if out is None:
-        out = torch.empty((n, 3), dtype=torch.float32, device=rays.device)
-    if not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (n, 3)):
-        raise ValueError("out must be a contiguous (N, 3) float32 CUDA tensor")
-    cnt_ptr = None
-    if ray_count is not None:
-        if not (ray_count.is_cuda and ray_count.dtype == torch.int64 and ray_count.numel() == 1):
-            raise ValueError("ray_count must be a 1-element int64 CUDA tensor")
-        cnt_ptr = C.c_void_p(ray_count.data_ptr())
-    s = stream if stream is not None else torch.cuda.current_stream()
+    out = _out_tensor(out, (n, 3), torch.float32, rays.device)
+    cnt_ptr = _count_ptr(ray_count)
     _capi.check(_capi.amd_lib().rt_trace_rays(scene._h, C.c_void_p(rays.data_ptr()), n, int(max_depth), float(contribution),
-                                              C.c_void_p(out.data_ptr()), cnt_ptr, C.c_void_p(s.cuda_stream)))
+                                              C.c_void_p(out.data_ptr()), cnt_ptr, _stream_ptr(stream)))
     return out
 
 
 def trace_rays_numpy(scene: Scene, rays_np, max_depth: int, contribution: float = 1.0):
     """Host-buffer convenience (rt_trace_rays_host, synchronous): rays as a RAY_DTYPE structured array or an (N, 11) array of 4-byte
     words; returns (rgb[N, 3] float32, casts)."""
-    a = np.asarray(rays_np)
-    if a.dtype == RAY_DTYPE:
-        a = np.ascontiguousarray(a).reshape(-1)
-    elif a.ndim == 2 and a.shape[1] == 11 and a.dtype.itemsize == 4:
-        a = np.ascontiguousarray(a).view(RAY_DTYPE).reshape(-1)
-    else:
-        raise ValueError("expected a RAY_DTYPE array or an (N, 11) array of 4-byte words")
+    a = _host_records(rays_np, RAY_DTYPE, 11, "rays")
     rgb = np.zeros((a.shape[0], 3), dtype=np.float32)
     casts = C.c_ulonglong(0)
     _capi.check(_capi.amd_lib().rt_trace_rays_host(scene._h, a.ctypes.data_as(C.c_void_p), a.shape[0], int(max_depth), float(contribution),
@@ -541,13 +528,9 @@ def shade_hits(scene: Scene, hits, rays, out=None, ray_count=None, stream=None):
     import torch
 
     records, n = _hits_and_rays(hits, rays)
-    if out is None:
-        out = torch.empty((n, 3), dtype=torch.float32, device=records.device)
-    if not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (n, 3)):
-        raise ValueError("out must be a contiguous (N, 3) float32 CUDA tensor")
-    s = stream if stream is not None else torch.cuda.current_stream()
+    out = _out_tensor(out, (n, 3), torch.float32, records.device)
     _capi.check(_capi.amd_lib().rt_shade_hits(scene._h, C.c_void_p(records.data_ptr()), C.c_void_p(rays.data_ptr()), n,
-                                              C.c_void_p(out.data_ptr()), _count_ptr(ray_count), C.c_void_p(s.cuda_stream)))
+                                              C.c_void_p(out.data_ptr()), _count_ptr(ray_count), _stream_ptr(stream)))
     return out
 
 
@@ -557,14 +540,9 @@ def reflect_rays(hits, rays, out=None, stream=None):
     import torch
 
     records, n = _hits_and_rays(hits, rays)
-    if out is None:
-        out = torch.empty((n, 11), dtype=torch.int32, device=records.device)
-    _records(out, 11, "out")
-    if out.shape[0] != n:
-        raise ValueError("out must have one record per hit")
-    s = stream if stream is not None else torch.cuda.current_stream()
+    out = _out_tensor(out, (n, 11), torch.int32, records.device)
     _capi.check(_capi.amd_lib().rt_reflect_rays(C.c_void_p(records.data_ptr()), C.c_void_p(rays.data_ptr()), n, C.c_void_p(out.data_ptr()),
-                                                C.c_void_p(s.cuda_stream)))
+                                                _stream_ptr(stream)))
     return out
 
 
@@ -601,10 +579,9 @@ def refract_rays(scene: Scene, hits, rays, max_distance: float = 100.0, ray_coun
     _records(escape, 11, "out.rays")
     if escape.shape[0] != n:
         raise ValueError("out must have one record per hit")
-    s = stream if stream is not None else torch.cuda.current_stream()
     _capi.check(_capi.amd_lib().rt_refract_rays(scene._h, C.c_void_p(records.data_ptr()), C.c_void_p(rays.data_ptr()), n, float(max_distance),
                                                 C.c_void_p(kind.data_ptr()), C.c_void_p(travel.data_ptr()), C.c_void_p(escape.data_ptr()),
-                                                _count_ptr(ray_count), C.c_void_p(s.cuda_stream)))
+                                                _count_ptr(ray_count), _stream_ptr(stream)))
     return out
 
 
@@ -713,10 +690,9 @@ def render_distributed(scene: Scene, camera: Camera, frame: Frame, rng: Rng, n_e
                          (valid, (n_epochs, rows, cols), torch.uint8)):
         if t is not None and not (t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape):
             raise ValueError(f"expected a contiguous CUDA {dt} tensor of shape {shape}")
-    s = stream if stream is not None else torch.cuda.current_stream()
     _capi.check(
         _capi.amd_lib().rt_render_distributed(scene._h, C.byref(camera), C.byref(frame), float(focus), float(blur), rng._h,
-                                              int(n_epochs), ptr(accum), ptr(samples), ptr(valid), ptr(ray_count), C.c_void_p(s.cuda_stream))
+                                              int(n_epochs), ptr(accum), ptr(samples), ptr(valid), ptr(ray_count), _stream_ptr(stream))
     )
     return accum if accum is not None else samples
 
@@ -728,14 +704,9 @@ def focus_rays(camera: Camera, frame: Frame, rng: Rng, focus: float = 3.0, blur:
     import torch
 
     n = frame.rows * frame.cols
-    if out is None:
-        out = torch.empty((n, 11), dtype=torch.int32, device="cuda")
-    _records(out, 11, "out")
-    if out.shape[0] != n:
-        raise ValueError("out must have rows * cols records")
-    s = stream if stream is not None else torch.cuda.current_stream()
+    out = _out_tensor(out, (n, 11), torch.int32, "cuda")
     _capi.check(_capi.amd_lib().rt_focus_rays(C.byref(camera), C.byref(frame), float(focus), float(blur), rng._h, C.c_void_p(out.data_ptr()),
-                                              C.c_void_p(s.cuda_stream)))
+                                              _stream_ptr(stream)))
     return out
 
 
@@ -760,22 +731,15 @@ def trace_rays_distributed(scene: Scene, rays, max_depth: int, rng: Rng, n_epoch
             raise ValueError(f"expected a contiguous CUDA {dt} tensor of shape {shape}")
     if ray_count is not None and not (ray_count.is_cuda and ray_count.dtype == torch.int64 and ray_count.numel() == 1):
         raise ValueError("ray_count must be a 1-element int64 CUDA tensor")
-    s = stream if stream is not None else torch.cuda.current_stream()
     _capi.check(_capi.amd_lib().rt_trace_rays_distributed(scene._h, C.c_void_p(rays.data_ptr()), n, int(max_depth), rng._h, int(n_epochs),
-                                                          ptr(accum), ptr(samples), ptr(valid), ptr(ray_count), C.c_void_p(s.cuda_stream)))
+                                                          ptr(accum), ptr(samples), ptr(valid), ptr(ray_count), _stream_ptr(stream)))
     return accum if accum is not None else samples
 
 
 def trace_rays_distributed_numpy(scene: Scene, rays_np, max_depth: int, rng: Rng, n_epochs: int, img: np.ndarray) -> int:
     """Host-buffer convenience (rt_trace_rays_distributed_host, synchronous): rays as a RAY_DTYPE structured array or an (N, 11) array
     of 4-byte words; `n_epochs` samples per ray are added into ``img`` ((N, 3) f32, in place).  Returns the cast count."""
-    a = np.asarray(rays_np)
-    if a.dtype == RAY_DTYPE:
-        a = np.ascontiguousarray(a).reshape(-1)
-    elif a.ndim == 2 and a.shape[1] == 11 and a.dtype.itemsize == 4:
-        a = np.ascontiguousarray(a).view(RAY_DTYPE).reshape(-1)
-    else:
-        raise ValueError("expected a RAY_DTYPE array or an (N, 11) array of 4-byte words")
+    a = _host_records(rays_np, RAY_DTYPE, 11, "rays")
     if not (isinstance(img, np.ndarray) and img.dtype == np.float32 and img.flags.c_contiguous and img.shape == (a.shape[0], 3)):
         raise ValueError("expected a contiguous (N, 3) float32 array")
     casts = C.c_ulonglong(0)
@@ -839,10 +803,9 @@ def scatter_hits(scene: Scene, hits, rays, rng: Rng, rng_index=None, stream=None
     if out.rays.shape[0] != n:
         raise ValueError("out must have one record per hit")
     _column(out.cosine, torch.float32, n, "out.cosine")
-    s = stream if stream is not None else torch.cuda.current_stream()
     _capi.check(_capi.amd_lib().rt_scatter_hits(scene._h, C.c_void_p(records.data_ptr()), C.c_void_p(rays.data_ptr()), n, rng._h, idx_ptr,
                                                 C.c_void_p(out.type.data_ptr()), C.c_void_p(out.rays.data_ptr()), C.c_void_p(out.cosine.data_ptr()),
-                                                C.c_void_p(s.cuda_stream)))
+                                                _stream_ptr(stream)))
     return out
 
 
@@ -862,14 +825,10 @@ def scatter_factors(scene: Scene, hits, rays, types, next_rays, travel, out=None
     if not (torch.is_tensor(travel) and travel.is_cuda and travel.dtype == torch.float32 and travel.is_contiguous()
             and tuple(travel.shape) == (n,)):
         raise ValueError("travel must be a contiguous (N,) float32 CUDA tensor")
-    if out is None:
-        out = torch.empty((n, 3), dtype=torch.float32, device=records.device)
-    if not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (n, 3)):
-        raise ValueError("out must be a contiguous (N, 3) float32 CUDA tensor")
-    s = stream if stream is not None else torch.cuda.current_stream()
+    out = _out_tensor(out, (n, 3), torch.float32, records.device)
     _capi.check(_capi.amd_lib().rt_scatter_factors(scene._h, C.c_void_p(records.data_ptr()), C.c_void_p(rays.data_ptr()),
                                                    C.c_void_p(types.data_ptr()), C.c_void_p(next_rays.data_ptr()), C.c_void_p(travel.data_ptr()),
-                                                   n, C.c_void_p(out.data_ptr()), C.c_void_p(s.cuda_stream)))
+                                                   n, C.c_void_p(out.data_ptr()), _stream_ptr(stream)))
     return out
 
 
@@ -920,17 +879,6 @@ def scatter_factors_numpy(scene: Scene, hits_np, rays_np, types, next_rays_np, t
 
 
 # ---- level loop: select, indexed casts, the glue of one level and the fold (include/rt_amd.h rt_select_records ... rt_level_finish) ----
-
-
-def _stream_ptr(stream):
-    import torch
-
-    s = stream if stream is not None else torch.cuda.current_stream()
-    return C.c_void_p(s.cuda_stream)
-
-
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 def select_records(flags, index=None, count=None, stream=None):
@@ -1041,11 +989,7 @@ def level_close(hits, types, cosine, next_hits, out=None, stream=None):
         raise ValueError("next_hits must have one record per hit")
     _column(types, torch.int32, n, "types")
     _column(cosine, torch.float32, n, "cosine")
-    if out is None:
-        out = torch.empty((n, 13), dtype=torch.int32, device=records.device)
-    _records(out, 13, "out")
-    if out.shape[0] != n:
-        raise ValueError("out must have one record per hit")
+    out = _out_tensor(out, (n, 13), torch.int32, records.device)
     _capi.check(_capi.amd_lib().rt_level_close(_p(records), _p(types), _p(cosine), _p(nxt), n, _p(out), _stream_ptr(stream)))
     return out
 
@@ -1375,9 +1319,7 @@ def trace_rays_levels(scene: Scene, rays, max_depth: int, contribution=1.0, out=
     _records(rays, 11, "rays")
     n = rays.shape[0]
     dev = rays.device
-    if out is None:
-        out = torch.empty((n, 3), dtype=torch.float32, device=dev)
-    _rgb(out, n, "out")
+    out = _out_tensor(out, (n, 3), torch.float32, dev)
     _count_ptr(ray_count)
     _count_word(overflow, "overflow")
     if max_depth > _capi.RT_MAX_DEPTH:
@@ -1615,9 +1557,7 @@ def shade_hits_by_light(scene: Scene, hits, rays, out=None, ray_count=None, stre
 
     records, n = _hits_and_rays(hits, rays)
     dev = records.device
-    if out is None:
-        out = torch.empty((n, 3), dtype=torch.float32, device=dev)
-    _rgb(out, n, "out")
+    out = _out_tensor(out, (n, 3), torch.float32, dev)
     _count_ptr(ray_count)
     lights = scene.n_lights
     per_pass = lights if lights_per_pass is None else int(lights_per_pass)
@@ -1960,11 +1900,7 @@ def cast_rays_ordered(scene: Scene, rays, box=None, flags: int = 0, out=None, ra
 
     _records(rays, 11, "rays")
     n = rays.shape[0]
-    if out is None:
-        out = torch.empty((n, 13), dtype=torch.int32, device=rays.device)
-    _records(out, 13, "out")
-    if out.shape[0] != n:
-        raise ValueError("out must have one record per ray")
+    out = _out_tensor(out, (n, 13), torch.int32, rays.device)
     if n == 0:
         return out
     w = _order_list(scene, rays, box, flags, workspace, False, stream)
@@ -1982,9 +1918,7 @@ def trace_rays_ordered(scene: Scene, rays, max_depth: int, contribution: float =
 
     _records(rays, 11, "rays")
     n = rays.shape[0]
-    if out is None:
-        out = torch.empty((n, 3), dtype=torch.float32, device=rays.device)
-    _rgb(out, n, "out")
+    out = _out_tensor(out, (n, 3), torch.float32, rays.device)
     if n == 0:
         return out
     w = _order_list(scene, rays, box, flags, workspace, True, stream)
@@ -2121,9 +2055,8 @@ def post_process_device(img, divisor=None, stream=None):
     import torch
 
     assert img.is_cuda and img.dtype == torch.float32 and img.is_contiguous() and img.shape[-1] == 3
-    s = stream if stream is not None else torch.cuda.current_stream()
     _capi.check(_capi.amd_lib().rt_post_process_device(C.c_void_p(img.data_ptr()), img.numel() // 3,
-                                                      None if divisor is None else C.c_void_p(divisor.data_ptr()), C.c_void_p(s.cuda_stream)))
+                                                      None if divisor is None else C.c_void_p(divisor.data_ptr()), _stream_ptr(stream)))
     return img
 
 
@@ -2134,8 +2067,7 @@ def encode_srgb8_device(img, out=None, stream=None):
     assert img.is_cuda and img.dtype == torch.float32 and img.is_contiguous()
     if out is None:
         out = torch.empty(img.shape, dtype=torch.uint8, device=img.device)
-    s = stream if stream is not None else torch.cuda.current_stream()
-    _capi.check(_capi.amd_lib().rt_encode_srgb8_device(C.c_void_p(img.data_ptr()), img.numel(), C.c_void_p(out.data_ptr()), C.c_void_p(s.cuda_stream)))
+    _capi.check(_capi.amd_lib().rt_encode_srgb8_device(C.c_void_p(img.data_ptr()), img.numel(), C.c_void_p(out.data_ptr()), _stream_ptr(stream)))
     return out
 
 
@@ -2170,10 +2102,9 @@ class PhotonAccumulator:
 
             assert samples.is_cuda and samples.dtype == torch.float32 and samples.is_contiguous()
             assert valid.is_cuda and valid.dtype == torch.uint8 and valid.is_contiguous()
-            s = stream if stream is not None else torch.cuda.current_stream()
             _capi.check(_capi.amd_lib().rt_accumulate_device(C.c_void_p(samples.data_ptr()), C.c_void_p(valid.data_ptr()), n_epochs, n_pixels,
                                                             C.c_void_p(self.sum.data_ptr()), C.c_void_p(self.weight.data_ptr()),
-                                                            C.c_void_p(s.cuda_stream)))
+                                                            _stream_ptr(stream)))
 
     def resolve(self, stream=None):
         """into_rgb_internal: sum / weight, black where nothing was accumulated."""
@@ -2186,9 +2117,8 @@ class PhotonAccumulator:
         import torch
 
         out = torch.empty((self.rows, self.cols, 3), dtype=torch.float32, device=self.device)
-        s = stream if stream is not None else torch.cuda.current_stream()
         _capi.check(_capi.amd_lib().rt_accumulator_resolve_device(C.c_void_p(self.sum.data_ptr()), C.c_void_p(self.weight.data_ptr()), n_pixels,
-                                                                 C.c_void_p(out.data_ptr()), C.c_void_p(s.cuda_stream)))
+                                                                 C.c_void_p(out.data_ptr()), _stream_ptr(stream)))
         return out
 
 

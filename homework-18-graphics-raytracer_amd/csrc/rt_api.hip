@@ -69,6 +69,71 @@ int fail_hip(const char *what, hipError_t e) {
                                                                   : RT_ERR_HIP;
 }
 
+int check_count(const char *who, uint64_t n, const CountLimit &limit) {
+    if (n < (1ull << limit.log2)) return RT_OK;
+    std::string msg = std::string(who) + ": 2^" + std::to_string(limit.log2) + " " + limit.noun + " or more (checked first";
+    if (limit.advice) msg = msg + "; " + limit.advice;
+    return fail(RT_ERR_UNSUPPORTED, msg + ")");
+}
+int check_scene(const char *who, const void *scene) {
+    if (scene) return RT_OK;
+    return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": null scene");
+}
+int check_pointers(const char *who, bool ok, const char *names) {
+    if (ok) return RT_OK;
+    return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": null " + names + " pointer");
+}
+int query_args(const char *who, size_t n, const CountLimit &limit, bool needs_scene, const void *scene, bool pointers_ok, const char *names,
+               bool *done) {
+    *done = true;
+    int rc = check_count(who, n, limit);
+    if (rc == RT_OK && needs_scene) rc = check_scene(who, scene);
+    if (rc != RT_OK || n == 0) return rc;
+    rc = check_pointers(who, pointers_ok, names);
+    *done = rc != RT_OK;
+    return rc;
+}
+
+int launched(const char *who, hipError_t e) {
+    if (e == hipSuccess) return RT_OK;
+    return fail_hip((std::string(who) + ": launch").c_str(), e);
+}
+
+bool stream_capturing(hipStream_t stream) {
+    hipStreamCaptureStatus status = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &status) != hipSuccess) (void)hipGetLastError();
+    return status != hipStreamCaptureStatusNone;
+}
+
+HostRoundTrip::~HostRoundTrip() {
+    for (const Buffer &b : buffers_) (void)hipFree(b.d);
+    if (d_count_) (void)hipFree(d_count_);
+}
+void *HostRoundTrip::add(void *h, size_t bytes, bool wanted, bool upload, bool download) {
+    if (!wanted || e_ != hipSuccess) return nullptr;
+    void *d = nullptr;
+    e_ = hipMalloc(&d, bytes);
+    if (e_ != hipSuccess) return nullptr;
+    buffers_.push_back({d, download ? h : nullptr, bytes});
+    if (upload) e_ = hipMemcpy(d, h, bytes, hipMemcpyHostToDevice);
+    return d;
+}
+unsigned long long *HostRoundTrip::counter() {
+    if (e_ != hipSuccess) return nullptr;
+    e_ = hipMalloc(reinterpret_cast<void **>(&d_count_), sizeof *d_count_);
+    if (e_ == hipSuccess) e_ = hipMemset(d_count_, 0, sizeof *d_count_);
+    return d_count_;
+}
+int HostRoundTrip::finish(unsigned long long *h_count) {
+    if (e_ == hipSuccess) e_ = hipDeviceSynchronize();
+    for (const Buffer &b : buffers_)
+        if (e_ == hipSuccess && b.h) e_ = hipMemcpy(b.h, b.d, b.bytes, hipMemcpyDeviceToHost);
+    unsigned long long count = 0;
+    if (e_ == hipSuccess && d_count_) e_ = hipMemcpy(&count, d_count_, sizeof count, hipMemcpyDeviceToHost);
+    if (e_ != hipSuccess) return failed();
+    if (h_count) *h_count = count;
+    return RT_OK;
+}
 
 /* 2 / 3: the per-pixel kernel with scalar / LDS triangle fetches; 18 / 19: the persistent wavefront kernel (with that as its fallback) */
 static bool variant_ok(int v) { return v == 2 || v == 3 || v == 18 || v == 19; }
@@ -520,9 +585,7 @@ static int render_whitted_frame(const rt_scene *scene, const rt::KernelFrame &kf
             pw.ray_count = d_ray_count;
             pw_groups = (uint32_t)groups;
             if (ws.d_pwf != nullptr) {
-                hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-                if (hipStreamIsCapturing(stream, &capturing) != hipSuccess) (void)hipGetLastError();
-                if (capturing != hipStreamCaptureStatusNone) ws.pw_always_prepare = true;
+                if (stream_capturing(stream)) ws.pw_always_prepare = true;
                 if (pw_band_units >= units && !ws.pw_always_prepare) { /* one launch: does it find its block zeroed and its frame description in place? */
                     rt::KernelFrame want_frame = kf;
                     want_frame.n_chunks = (kf.cols * kf.rows + 63u) / 64u; /* as launch_pwf fills it in */
@@ -586,9 +649,8 @@ static int render_whitted_frame(const rt_scene *scene, const rt::KernelFrame &kf
             rt_scene *mut = const_cast<rt_scene *>(scene);
             std::lock_guard<std::mutex> lock(mut->ws_mutex);
             mut->workspaces[stream].pw_ready = false; /* whatever state the blocks are in: the next launch prepares its own */
-            return fail_hip((std::string(who) + ": launch").c_str(), e);
         }
-        return RT_OK;
+        return launched(who, e);
     }
     /* the per-pixel kernel: a camera frame in one launch, a ray batch in bands of RT_TRACE_BAND_RAYS (one event pair around them all) */
     const uint32_t band_units = rays && units > RT_TRACE_BAND_RAYS ? RT_TRACE_BAND_RAYS : units;
@@ -607,8 +669,7 @@ static int render_whitted_frame(const rt_scene *scene, const rt::KernelFrame &kf
         rt::mute_main_kernel_events(false);
         if (e == hipSuccess) rt::record_main_kernel_event(1, stream);
     }
-    if (e != hipSuccess) return fail_hip((std::string(who) + ": launch").c_str(), e);
-    return RT_OK;
+    return launched(who, e);
 }
 
 extern "C" {
@@ -621,12 +682,13 @@ int rt_render_whitted(const rt_scene *scene, const rt_camera *camera, const rt_f
     return render_whitted_frame(scene, kf, nullptr, d_rgb, d_ray_count, static_cast<hipStream_t>(hip_stream), "rt_render_whitted");
 }
 
+static const CountLimit TRACE_RAYS_LIMIT = {32u, "rays", "trace them in several calls"};
+
 int rt_trace_rays(const rt_scene *scene, const rt_ray *d_rays, size_t n_rays, int32_t max_depth, float contribution, float *d_rgb,
                   unsigned long long *d_ray_count, void *hip_stream) {
-    if ((uint64_t)n_rays >= (1ull << 32)) return fail(RT_ERR_UNSUPPORTED, "rt_trace_rays: 2^32 rays or more (checked first; trace them in several calls)");
-    if (!scene) return fail(RT_ERR_INVALID_ARGUMENT, "rt_trace_rays: null scene");
-    if (n_rays == 0) return RT_OK;
-    if (!d_rays || !d_rgb) return fail(RT_ERR_INVALID_ARGUMENT, "rt_trace_rays: null ray or rgb pointer");
+    bool done;
+    const int rc = query_args("rt_trace_rays", n_rays, TRACE_RAYS_LIMIT, true, scene, d_rays && d_rgb, "ray or rgb", &done);
+    if (rc != RT_OK || done) return rc;
     if (max_depth > RT_MAX_DEPTH) return fail(RT_ERR_UNSUPPORTED, "rt_trace_rays: max_depth above RT_MAX_DEPTH");
     /* max_depth < 0 renders as 0, as in rt_render_whitted (TraceState.depth is tested with `depth <= 0`, main.rs:488) */
     rt::KernelFrame kf;
@@ -640,68 +702,30 @@ int rt_trace_rays(const rt_scene *scene, const rt_ray *d_rays, size_t n_rays, in
 
 int rt_trace_rays_host(const rt_scene *scene, const rt_ray *h_rays, size_t n_rays, int32_t max_depth, float contribution, float *h_rgb,
                        unsigned long long *h_ray_count) {
-    if ((uint64_t)n_rays >= (1ull << 32)) return fail(RT_ERR_UNSUPPORTED, "rt_trace_rays_host: 2^32 rays or more (checked first; trace them in several calls)");
-    if (!scene) return fail(RT_ERR_INVALID_ARGUMENT, "rt_trace_rays_host: null scene");
-    if (n_rays == 0) {
-        if (h_ray_count) *h_ray_count = 0;
-        return RT_OK;
-    }
-    if (!h_rays || !h_rgb) return fail(RT_ERR_INVALID_ARGUMENT, "rt_trace_rays_host: null ray or rgb pointer");
+    bool done;
+    int rc = query_args("rt_trace_rays_host", n_rays, TRACE_RAYS_LIMIT, true, scene, h_rays && h_rgb, "ray or rgb", &done);
+    if (rc == RT_OK && done && h_ray_count) *h_ray_count = 0;
+    if (rc != RT_OK || done) return rc;
     if (max_depth > RT_MAX_DEPTH) return fail(RT_ERR_UNSUPPORTED, "rt_trace_rays_host: max_depth above RT_MAX_DEPTH");
-    const size_t rgb_bytes = n_rays * 3 * sizeof(float);
-    rt_ray *d_rays = nullptr;
-    float *d_rgb = nullptr;
-    unsigned long long *d_cnt = nullptr;
-    RT_HIP(hipMalloc(reinterpret_cast<void **>(&d_rays), n_rays * sizeof(rt_ray)));
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&d_rgb), rgb_bytes);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_cnt), sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemset(d_cnt, 0, sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemcpy(d_rays, h_rays, n_rays * sizeof(rt_ray), hipMemcpyHostToDevice);
-    int rc = RT_OK;
-    if (e == hipSuccess) {
-        rc = rt_trace_rays(scene, d_rays, n_rays, max_depth, contribution, d_rgb, d_cnt, nullptr);
-        if (rc == RT_OK) {
-            e = hipDeviceSynchronize();
-            if (e == hipSuccess) e = hipMemcpy(h_rgb, d_rgb, rgb_bytes, hipMemcpyDeviceToHost);
-            unsigned long long cnt = 0;
-            if (e == hipSuccess) e = hipMemcpy(&cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost);
-            if (e == hipSuccess && h_ray_count) *h_ray_count = cnt;
-        }
-    }
-    (void)hipFree(d_rays);
-    if (d_rgb) (void)hipFree(d_rgb);
-    if (d_cnt) (void)hipFree(d_cnt);
-    if (rc != RT_OK) return rc;
-    if (e != hipSuccess) return fail_hip("rt_trace_rays_host", e);
-    return RT_OK;
+    HostRoundTrip t("rt_trace_rays_host");
+    const rt_ray *d_rays = t.in(h_rays, n_rays * sizeof(rt_ray));
+    float *d_rgb = t.out(h_rgb, n_rays * 3 * sizeof(float));
+    unsigned long long *d_cnt = t.counter();
+    if (!t.ok()) return t.failed();
+    rc = rt_trace_rays(scene, d_rays, n_rays, max_depth, contribution, d_rgb, d_cnt, nullptr);
+    return rc != RT_OK ? rc : t.finish(h_ray_count);
 }
 
 int rt_render_whitted_host(const rt_scene *scene, const rt_camera *camera, const rt_frame *frame, float *h_rgb,
                            unsigned long long *h_ray_count) {
     if (!scene || !h_rgb) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_whitted_host: null argument");
     if (!frame_ok(frame)) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_whitted_host: bad frame");
-    const size_t bytes = (size_t)rt_frame_pixels(frame) * 3 * sizeof(float);
-    float *d_rgb = nullptr;
-    unsigned long long *d_cnt = nullptr;
-    RT_HIP(hipMalloc(reinterpret_cast<void **>(&d_rgb), bytes));
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&d_cnt), sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemset(d_cnt, 0, sizeof(unsigned long long));
-    int rc = RT_OK;
-    if (e == hipSuccess) {
-        rc = rt_render_whitted(scene, camera, frame, d_rgb, d_cnt, nullptr);
-        if (rc == RT_OK) {
-            e = hipDeviceSynchronize();
-            if (e == hipSuccess) e = hipMemcpy(h_rgb, d_rgb, bytes, hipMemcpyDeviceToHost);
-            unsigned long long cnt = 0;
-            if (e == hipSuccess) e = hipMemcpy(&cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost);
-            if (e == hipSuccess && h_ray_count) *h_ray_count = cnt;
-        }
-    }
-    (void)hipFree(d_rgb);
-    if (d_cnt) (void)hipFree(d_cnt);
-    if (rc != RT_OK) return rc;
-    if (e != hipSuccess) return fail_hip("rt_render_whitted_host", e);
-    return RT_OK;
+    HostRoundTrip t("rt_render_whitted_host");
+    float *d_rgb = t.out(h_rgb, (size_t)rt_frame_pixels(frame) * 3 * sizeof(float));
+    unsigned long long *d_cnt = t.counter();
+    if (!t.ok()) return t.failed();
+    const int rc = rt_render_whitted(scene, camera, frame, d_rgb, d_cnt, nullptr);
+    return rc != RT_OK ? rc : t.finish(h_ray_count);
 }
 
 } /* extern "C" */

@@ -175,7 +175,8 @@ int rt_rng_create(const rt_frame *frame, rt_rng **out_rng) {
 }
 
 int rt_rng_create_seeded(const uint64_t *h_seeds, size_t n, rt_rng **out_rng) {
-    if ((uint64_t)n >= (1ull << 32)) return fail(RT_ERR_UNSUPPORTED, "rt_rng_create_seeded: 2^32 generators or more (checked first)");
+    const int rc = check_count("rt_rng_create_seeded", n, {32u, "generators", nullptr});
+    if (rc != RT_OK) return rc;
     if (!out_rng) return fail(RT_ERR_INVALID_ARGUMENT, "rt_rng_create_seeded: null argument");
     *out_rng = nullptr;
     if (n != 0 && !h_seeds) return fail(RT_ERR_INVALID_ARGUMENT, "rt_rng_create_seeded: null seed pointer");
@@ -296,7 +297,6 @@ static int render_distributed_frame(const rt_scene *scene, const rt::KernelFrame
     dp.bfs_scratch = nullptr;
     dp.bfs_items_cap = dp.bfs_jobs_cap = 0u;
     dp.epoch0 = 0u;
-    const std::string launch_failed = std::string(who) + ": launch";
     uint32_t dist_waves = scene->resident_waves;
     int split = g_dist_split.load();
     if (split < 0) split = rt::option(rt::OPT_DIST_SPLIT, RT_DIST_SPLIT_DEFAULT) != 0 ? 1 : 0;
@@ -449,8 +449,7 @@ static int render_distributed_frame(const rt_scene *scene, const rt::KernelFrame
         /* everything the call started is behind the caller's stream again */
         for (uint32_t b = 0; b < 2u; ++b)
             if (tail_used[b]) { const hipError_t e2 = hipStreamWaitEvent(stream, rng->ev_tail[b], 0); if (e == hipSuccess) e = e2; }
-        if (e != hipSuccess) return fail_hip(launch_failed.c_str(), e);
-        return RT_OK;
+        return launched(who, e);
     }
 one_kernel:
     dp.n_epochs = n_epochs;
@@ -488,8 +487,7 @@ one_kernel:
     if (e == hipSuccess && lookahead && !rng->ahead) e = rt::launch_rng_prepare(dp.rng_states, (uint32_t)n_pixels, rng->d_list, rng->compute_units, stream);
     rng->ahead = false;
     if (e == hipSuccess) e = rt::launch_distributed(scene->ks, kf, dp, dist_waves, stream);
-    if (e != hipSuccess) return fail_hip(launch_failed.c_str(), e);
-    return RT_OK;
+    return launched(who, e);
 }
 
 /* A ray batch runs in bands of at most this many rays per launch set, whole 64-ray chunks (as RT_TRACE_BAND_RAYS of rt_trace_rays):
@@ -499,16 +497,18 @@ one_kernel:
 
 static int trace_rays_distributed_checks(const char *who, const rt_scene *scene, const void *rays, size_t n_rays, int32_t max_depth,
                                          const rt_rng *rng, uint32_t n_epochs, const void *accum, const void *samples, bool host, bool *nothing) {
-    const std::string w(who);
     *nothing = false;
-    if ((uint64_t)n_rays >= (1ull << 32)) return fail(RT_ERR_UNSUPPORTED, w + ": 2^32 rays or more (checked first; trace them in several calls)");
-    if (!scene) return fail(RT_ERR_INVALID_ARGUMENT, w + ": null scene");
-    if (!rng) return fail(RT_ERR_INVALID_ARGUMENT, w + ": null rng");
-    if (n_rays != rng_count(rng)) return fail(RT_ERR_INVALID_ARGUMENT, w + ": the RNG holds a different number of generators than there are rays");
+    int rc = check_count(who, n_rays, {32u, "rays", "trace them in several calls"});
+    if (rc == RT_OK) rc = check_scene(who, scene);
+    if (rc != RT_OK) return rc;
+    if (!rng) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": null rng");
+    if (n_rays != rng_count(rng)) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": the RNG holds a different number of generators than there are rays");
     if (n_rays == 0 || n_epochs == 0) { *nothing = true; return RT_OK; }
-    if (!rays) return fail(RT_ERR_INVALID_ARGUMENT, w + ": null ray pointer");
-    if (host ? !accum : (!accum && !samples)) return fail(RT_ERR_INVALID_ARGUMENT, w + (host ? ": null accum pointer" : ": need d_accum or d_samples"));
-    if (max_depth > RT_MAX_DEPTH) return fail(RT_ERR_UNSUPPORTED, w + ": max_depth above RT_MAX_DEPTH");
+    rc = check_pointers(who, rays != nullptr, "ray");
+    if (rc == RT_OK && host) rc = check_pointers(who, accum != nullptr, "accum");
+    if (rc != RT_OK) return rc;
+    if (!host && !accum && !samples) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": need d_accum or d_samples");
+    if (max_depth > RT_MAX_DEPTH) return fail(RT_ERR_UNSUPPORTED, std::string(who) + ": max_depth above RT_MAX_DEPTH");
     return RT_OK;
 }
 
@@ -544,11 +544,7 @@ int rt_trace_rays_distributed(const rt_scene *scene, const rt_ray *d_rays, size_
     if (rc0 != RT_OK || nothing) return rc0;
     /* max_depth < 0 renders as 0, as in rt_render_distributed (distributed_ray_trace tests `depth <= 0`, main.rs:524) */
     const uint32_t n = (uint32_t)n_rays;
-    uint64_t band = RT_DIST_BAND_RAYS;
-    {
-        const long long hook = rt::option(rt::OPT_DIAG_DIST_BAND_RAYS, 0); /* test hook: shorter bands */
-        if (hook > 0 && (uint64_t)hook < band) band = ((uint64_t)hook + 63u) & ~(uint64_t)63u;
-    }
+    const uint64_t band = band_limit(rt::OPT_DIAG_DIST_BAND_RAYS, RT_DIST_BAND_RAYS); /* the option: a test hook, shorter bands */
     const bool ahead0 = rng->ahead; /* the records of the bands still to come are as the call found them */
     for (uint64_t u0 = 0; u0 < n; u0 += band) {
         const uint32_t len = (uint32_t)std::min<uint64_t>(band, n - u0);
@@ -583,33 +579,13 @@ int rt_trace_rays_distributed_host(const rt_scene *scene, const rt_ray *h_rays, 
         if (h_ray_count) *h_ray_count = 0;
         return RT_OK;
     }
-    const size_t bytes = n_rays * 3 * sizeof(float);
-    rt_ray *d_rays = nullptr;
-    float *d_accum = nullptr;
-    unsigned long long *d_cnt = nullptr;
-    RT_HIP(hipMalloc(reinterpret_cast<void **>(&d_rays), n_rays * sizeof(rt_ray)));
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&d_accum), bytes);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_cnt), sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemset(d_cnt, 0, sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemcpy(d_rays, h_rays, n_rays * sizeof(rt_ray), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_accum, h_accum, bytes, hipMemcpyHostToDevice); /* continues from the caller's sums */
-    int rc = RT_OK;
-    if (e == hipSuccess) {
-        rc = rt_trace_rays_distributed(scene, d_rays, n_rays, max_depth, rng, n_epochs, d_accum, nullptr, nullptr, d_cnt, nullptr);
-        if (rc == RT_OK) {
-            e = hipDeviceSynchronize();
-            if (e == hipSuccess) e = hipMemcpy(h_accum, d_accum, bytes, hipMemcpyDeviceToHost);
-            unsigned long long cnt = 0;
-            if (e == hipSuccess) e = hipMemcpy(&cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost);
-            if (e == hipSuccess && h_ray_count) *h_ray_count = cnt;
-        }
-    }
-    (void)hipFree(d_rays);
-    if (d_accum) (void)hipFree(d_accum);
-    if (d_cnt) (void)hipFree(d_cnt);
-    if (rc != RT_OK) return rc;
-    if (e != hipSuccess) return fail_hip("rt_trace_rays_distributed_host", e);
-    return RT_OK;
+    HostRoundTrip t("rt_trace_rays_distributed_host");
+    const rt_ray *d_rays = t.in(h_rays, n_rays * sizeof(rt_ray));
+    float *d_accum = t.inout(h_accum, n_rays * 3 * sizeof(float));
+    unsigned long long *d_cnt = t.counter();
+    if (!t.ok()) return t.failed();
+    const int rc = rt_trace_rays_distributed(scene, d_rays, n_rays, max_depth, rng, n_epochs, d_accum, nullptr, nullptr, d_cnt, nullptr);
+    return rc != RT_OK ? rc : t.finish(h_ray_count);
 }
 
 int rt_focus_rays(const rt_camera *camera, const rt_frame *frame, float focus, float blur, rt_rng *rng, rt_ray *d_rays, void *hip_stream) {
@@ -626,38 +602,20 @@ int rt_focus_rays(const rt_camera *camera, const rt_frame *frame, float focus, f
     if (!same_tile && !seeded_same_count)
         return fail(RT_ERR_INVALID_ARGUMENT, "rt_focus_rays: the RNG was created for a different tile (or, seeded, holds a different number of generators)");
     const hipError_t e = rt::launch_focus_rays(kf, focus, blur, rng->d_states, d_rays, static_cast<hipStream_t>(hip_stream));
-    if (e != hipSuccess) return fail_hip("rt_focus_rays: launch", e);
-    rng->ahead = false; /* a generator may have moved on to its prepared block: the next call looks */
-    return RT_OK;
+    if (e == hipSuccess) rng->ahead = false; /* a generator may have moved on to its prepared block: the next call looks */
+    return launched("rt_focus_rays", e);
 }
 
 int rt_render_distributed_host(const rt_scene *scene, const rt_camera *camera, const rt_frame *frame, float focus, float blur,
                                rt_rng *rng, uint32_t n_epochs, float *h_accum, unsigned long long *h_ray_count) {
     if (!scene || !rng || !h_accum) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_distributed_host: null argument");
     if (!frame_ok(frame)) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_distributed_host: bad frame");
-    const size_t bytes = (size_t)rt_frame_pixels(frame) * 3 * sizeof(float);
-    float *d_accum = nullptr;
-    unsigned long long *d_cnt = nullptr;
-    RT_HIP(hipMalloc(reinterpret_cast<void **>(&d_accum), bytes));
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&d_cnt), sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemset(d_cnt, 0, sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemcpy(d_accum, h_accum, bytes, hipMemcpyHostToDevice); /* img continues from the caller's sums */
-    int rc = RT_OK;
-    if (e == hipSuccess) {
-        rc = rt_render_distributed(scene, camera, frame, focus, blur, rng, n_epochs, d_accum, nullptr, nullptr, d_cnt, nullptr);
-        if (rc == RT_OK) {
-            e = hipDeviceSynchronize();
-            if (e == hipSuccess) e = hipMemcpy(h_accum, d_accum, bytes, hipMemcpyDeviceToHost);
-            unsigned long long cnt = 0;
-            if (e == hipSuccess) e = hipMemcpy(&cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost);
-            if (e == hipSuccess && h_ray_count) *h_ray_count = cnt;
-        }
-    }
-    (void)hipFree(d_accum);
-    if (d_cnt) (void)hipFree(d_cnt);
-    if (rc != RT_OK) return rc;
-    if (e != hipSuccess) return fail_hip("rt_render_distributed_host", e);
-    return RT_OK;
+    HostRoundTrip t("rt_render_distributed_host");
+    float *d_accum = t.inout(h_accum, (size_t)rt_frame_pixels(frame) * 3 * sizeof(float)); /* img continues from the caller's sums */
+    unsigned long long *d_cnt = t.counter();
+    if (!t.ok()) return t.failed();
+    const int rc = rt_render_distributed(scene, camera, frame, focus, blur, rng, n_epochs, d_accum, nullptr, nullptr, d_cnt, nullptr);
+    return rc != RT_OK ? rc : t.finish(h_ray_count);
 }
 
 } /* extern "C" */

@@ -1,11 +1,14 @@
 /*
  * rt_api_internal.h — what the translation units behind include/rt_amd.h share: the scene handle with its per-stream
- * workspaces, the status/error helpers, the frame checks.  Internal (hidden visibility): the library's exports are the
+ * workspaces, the status/error helpers, the frame checks, and the host plumbing every entry point is made of (argument checks, the
+ * launch tail, the band loop, the round trip of a _host form).  Internal (hidden visibility): the library's exports are the
  * extern "C" entry points of include/rt_amd.h and nothing else.
  *
- *   rt_api.hip         errors, settings, profiling, rt_scene_create/destroy, rt_render_whitted (the per-stream arenas)
+ *   rt_api.hip         errors and the shared host plumbing declared below, settings, profiling, rt_scene_create/destroy,
+ *                      rt_render_whitted (the per-stream arenas), rt_trace_rays
  *   rt_api_layout.hip  the device records and the node tree built from the ABI arrays — host only, no HIP call
- *   rt_api_dist.hip    rt_rng_* and rt_render_distributed: batches, the two workspaces, the streams of a pipelined call
+ *   rt_api_dist.hip    rt_rng_*, rt_render_distributed and rt_trace_rays_distributed: batches, the two workspaces, the streams of a
+ *                      pipelined call
  *   rt_api_multi.hip   rt_multi_*: a device list from one process
  *   rt_api_post.hip    post_process / sRGB / accumulator / rt_math_eval entry points
  *   rt_api_query.hip   rt_cast_rays / rt_camera_rays, the hit queries rt_shade_hits / rt_reflect_rays / rt_refract_rays, the scatter
@@ -17,6 +20,7 @@
  *   rt_scene_update.hip the scene updates' rt_scene_update_*: kernels and entry points in one unit
  *   rt_order_query.hip the record ordering's rt_ray_keys / rt_sort_records / rt_gather_records / rt_scatter_records: kernels and entry points in one unit
  *   rt_mesh_order.hip  the mesh ordering's rt_triangle_keys / rt_order_triangles: the key kernel and entry points that call rt_order_query.hip's
+ * The kernel units rt_hit_query.hip and rt_scatter_query.hip include this header for the band loop of their launchers.
  */
 #ifndef RT_API_INTERNAL_H
 #define RT_API_INTERNAL_H
@@ -129,6 +133,83 @@ RT_API_HIDDEN int fail_hip(const char *what, hipError_t e);
         hipError_t e_ = (call);                               \
         if (e_ != hipSuccess) return fail_hip(#call, e_);     \
     } while (0)
+
+/* ---- the host plumbing of an entry point (definitions: rt_api.hip, next to fail / fail_hip) ---- */
+
+/* The argument checks, in the house order: the count limit first, then a null scene (reported even for an empty batch), then "nothing
+ * to do", then the pointers.  Each returns RT_OK or what fail() returned; the text is put together only when a check fails.
+ * A limit reads "<who>: 2^<log2> <noun> or more (checked first; <advice>)"; advice may be null. */
+struct CountLimit {
+    unsigned log2;
+    const char *noun, *advice;
+};
+constexpr CountLimit RECORDS_2_32 = {32u, "records", "query them in several calls"};
+RT_API_HIDDEN int check_count(const char *who, uint64_t n, const CountLimit &limit);
+RT_API_HIDDEN int check_scene(const char *who, const void *scene);
+RT_API_HIDDEN int check_pointers(const char *who, bool ok, const char *names); /* "<who>: null <names> pointer" */
+/* ... and the four of them composed; *done: nothing to launch (a failed check or an empty batch).  An entry point with a check of its
+ * own in between composes the three above itself. */
+RT_API_HIDDEN int query_args(const char *who, size_t n, const CountLimit &limit, bool needs_scene, const void *scene, bool pointers_ok,
+                             const char *names, bool *done);
+
+/* the end of an entry point that launched: RT_OK, or "<who>: launch: <the HIP error>" with its status */
+RT_API_HIDDEN int launched(const char *who, hipError_t e);
+static inline int launched(const char *who) { return launched(who, hipGetLastError()); }
+
+static inline dim3 grid_of(uint64_t n, uint32_t threads) { return dim3((unsigned)((n + threads - 1u) / threads)); }
+
+/* is `stream` being captured into a graph (then nothing may be allocated, and host memory is not read later) */
+RT_API_HIDDEN bool stream_capturing(hipStream_t stream);
+
+/* Bands: no launch takes more than `band` records, a multiple of 64 so that bands are whole 64-record chunks.  band_limit: `limit`, or
+ * what the test hook `hook` asks for, in whole chunks.  for_each_band: launch(off, len) for every band of n records; the start of a
+ * band is counted in 64 bits (n may be anything below 2^32, and the start of the band after the last one need not fit 32 bits). */
+static inline uint64_t round_up_64(uint64_t x) { return (x + 63u) & ~(uint64_t)63u; }
+static inline uint32_t band_limit(rt::Option hook, uint32_t limit) {
+    const long long h = rt::option(hook, 0);
+    return h > 0 && h < (long long)limit ? (uint32_t)round_up_64((uint64_t)h) : limit;
+}
+template <class Launch>
+static inline hipError_t for_each_band(uint32_t n, uint32_t band, Launch launch) {
+    for (uint64_t off = 0u; off < n; off += band) {
+        launch(off, (uint32_t)(n - off < band ? n - off : band));
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+/* The round trip of a _host form: device copies of the caller's arrays, the device form on the null stream, the results back.  A null
+ * host pointer is an optional array the caller left out: nothing is allocated and the device pointer is null.  The first HIP error
+ * sticks: every later step is skipped, ok() is false and failed() reports it under the entry point's name.  finish(): one
+ * hipDeviceSynchronize, the downloads in declaration order, then the counter (*h_count is written last, and only if all went well).
+ * The destructor frees everything, whichever way the call ends. */
+class RT_API_HIDDEN HostRoundTrip {
+public:
+    explicit HostRoundTrip(const char *who) : who_(who) {}
+    ~HostRoundTrip();
+    HostRoundTrip(const HostRoundTrip &) = delete;
+    HostRoundTrip &operator=(const HostRoundTrip &) = delete;
+    template <class T> T *in(const T *h, size_t bytes) { return static_cast<T *>(add(const_cast<T *>(h), bytes, h != nullptr, true, false)); }
+    template <class T> T *out(T *h, size_t bytes) { return static_cast<T *>(add(h, bytes, h != nullptr, false, true)); }
+    template <class T> T *inout(T *h, size_t bytes) { return static_cast<T *>(add(h, bytes, h != nullptr, true, true)); } /* continues from the caller's values */
+    void *scratch(size_t bytes) { return add(nullptr, bytes, true, false, false); }
+    unsigned long long *counter(); /* zeroed */
+    bool ok() const { return e_ == hipSuccess; }
+    int failed() const { return fail_hip(who_, e_); }
+    int finish(unsigned long long *h_count = nullptr);
+
+private:
+    struct Buffer {
+        void *d, *h; /* h: where finish() downloads to, or null */
+        size_t bytes;
+    };
+    void *add(void *h, size_t bytes, bool wanted, bool upload, bool download);
+    const char *who_;
+    hipError_t e_ = hipSuccess;
+    std::vector<Buffer> buffers_;
+    unsigned long long *d_count_ = nullptr;
+};
 
 RT_API_HIDDEN bool frame_ok(const rt_frame *f);
 RT_API_HIDDEN bool frame_fits(const rt_frame *f);

@@ -63,9 +63,7 @@ int rt_post_process_device(float *d_rgb, size_t n_pixels, float *d_divisor, void
     }
     float row[3];
     rt::luma_row(row);
-    hipError_t e = rt::launch_post_process(d_rgb, n_pixels, row, keys, state, d_divisor, stream);
-    if (e != hipSuccess) return fail_hip("rt_post_process_device: launch", e);
-    return RT_OK;
+    return launched("rt_post_process_device", rt::launch_post_process(d_rgb, n_pixels, row, keys, state, d_divisor, stream));
 }
 
 /* the passes of rt_post_process_device one by one, on the caller's device memory (include/rt_amd.h) */
@@ -73,54 +71,40 @@ int rt_post_keys_device(const float *d_rgb, size_t n_pixels, uint32_t *d_keys, u
     if (!d_state || (n_pixels && (!d_rgb || !d_keys))) return fail(RT_ERR_INVALID_ARGUMENT, "rt_post_keys_device: null argument");
     float row[3];
     rt::luma_row(row);
-    const hipError_t e = rt::launch_post_keys(d_rgb, n_pixels, row, d_keys, d_state, static_cast<hipStream_t>(hip_stream));
-    if (e != hipSuccess) return fail_hip("rt_post_keys_device: launch", e);
-    return RT_OK;
+    return launched("rt_post_keys_device", rt::launch_post_keys(d_rgb, n_pixels, row, d_keys, d_state, static_cast<hipStream_t>(hip_stream)));
 }
 
 int rt_post_hist_device(const uint32_t *d_keys, size_t n_pixels, int pass, uint32_t *d_state, void *hip_stream) {
     if (!d_state || (n_pixels && !d_keys)) return fail(RT_ERR_INVALID_ARGUMENT, "rt_post_hist_device: null argument");
     if (pass < 0 || pass > 3) return fail(RT_ERR_INVALID_ARGUMENT, "rt_post_hist_device: pass 0..3");
-    const hipError_t e = rt::launch_post_hist(d_keys, n_pixels, pass, d_state, static_cast<hipStream_t>(hip_stream));
-    if (e != hipSuccess) return fail_hip("rt_post_hist_device: launch", e);
-    return RT_OK;
+    return launched("rt_post_hist_device", rt::launch_post_hist(d_keys, n_pixels, pass, d_state, static_cast<hipStream_t>(hip_stream)));
 }
 
 int rt_post_pick_device(int pass, uint32_t *d_state, void *hip_stream) {
     if (!d_state) return fail(RT_ERR_INVALID_ARGUMENT, "rt_post_pick_device: null argument");
     if (pass < 0 || pass > 3) return fail(RT_ERR_INVALID_ARGUMENT, "rt_post_pick_device: pass 0..3");
-    const hipError_t e = rt::launch_post_pick(pass, d_state, static_cast<hipStream_t>(hip_stream));
-    if (e != hipSuccess) return fail_hip("rt_post_pick_device: launch", e);
-    return RT_OK;
+    return launched("rt_post_pick_device", rt::launch_post_pick(pass, d_state, static_cast<hipStream_t>(hip_stream)));
 }
 
 int rt_post_scale_device(float *d_rgb, size_t n_pixels, const uint32_t *d_state, float *d_divisor, void *hip_stream) {
     if (!d_state || (n_pixels && !d_rgb)) return fail(RT_ERR_INVALID_ARGUMENT, "rt_post_scale_device: null argument");
-    const hipError_t e = rt::launch_post_scale(d_rgb, n_pixels, d_state, d_divisor, static_cast<hipStream_t>(hip_stream));
-    if (e != hipSuccess) return fail_hip("rt_post_scale_device: launch", e);
-    return RT_OK;
+    return launched("rt_post_scale_device", rt::launch_post_scale(d_rgb, n_pixels, d_state, d_divisor, static_cast<hipStream_t>(hip_stream)));
 }
 
 int rt_accumulate_device(const float *d_samples, const unsigned char *d_valid, uint32_t n_epochs, size_t n_pixels, float *d_sum,
                          float *d_weight, void *hip_stream) {
     if (!d_samples || !d_valid || !d_sum || !d_weight) return fail(RT_ERR_INVALID_ARGUMENT, "rt_accumulate_device: null argument");
-    const hipError_t e = rt::launch_accumulate(d_samples, d_valid, n_epochs, n_pixels, d_sum, d_weight, static_cast<hipStream_t>(hip_stream));
-    if (e != hipSuccess) return fail_hip("rt_accumulate_device: launch", e);
-    return RT_OK;
+    return launched("rt_accumulate_device", rt::launch_accumulate(d_samples, d_valid, n_epochs, n_pixels, d_sum, d_weight, static_cast<hipStream_t>(hip_stream)));
 }
 
 int rt_accumulator_resolve_device(const float *d_sum, const float *d_weight, size_t n_pixels, float *d_rgb, void *hip_stream) {
     if (!d_sum || !d_weight || !d_rgb) return fail(RT_ERR_INVALID_ARGUMENT, "rt_accumulator_resolve_device: null argument");
-    const hipError_t e = rt::launch_accumulator_resolve(d_sum, d_weight, n_pixels, d_rgb, static_cast<hipStream_t>(hip_stream));
-    if (e != hipSuccess) return fail_hip("rt_accumulator_resolve_device: launch", e);
-    return RT_OK;
+    return launched("rt_accumulator_resolve_device", rt::launch_accumulator_resolve(d_sum, d_weight, n_pixels, d_rgb, static_cast<hipStream_t>(hip_stream)));
 }
 
 int rt_encode_srgb8_device(const float *d_rgb, size_t n_values, unsigned char *d_out, void *hip_stream) {
     if (!d_rgb || !d_out) return fail(RT_ERR_INVALID_ARGUMENT, "rt_encode_srgb8_device: null argument");
-    hipError_t e = rt::launch_encode_srgb8(d_rgb, n_values, d_out, static_cast<hipStream_t>(hip_stream));
-    if (e != hipSuccess) return fail_hip("rt_encode_srgb8_device: launch", e);
-    return RT_OK;
+    return launched("rt_encode_srgb8_device", rt::launch_encode_srgb8(d_rgb, n_values, d_out, static_cast<hipStream_t>(hip_stream)));
 }
 
 int rt_math_eval_host(int op, const float *x, const float *y, float *out, size_t n) {

@@ -14,6 +14,7 @@
  */
 #include "rt_cast.h"
 #include "rt_hit_abi.h"
+#include "rt_api_internal.h"
 
 namespace rt {
 
@@ -239,53 +240,38 @@ __global__ __launch_bounds__(256) void reflect_rays_kernel(const rt_hit *__restr
     store_ray(out + i, h.g.pos, reflect_dir(h.g.normal, in.d), in.mode, 1u, h.kind, h.index, h.g.bf ? FACE_FRONT : FACE_BACK);
 }
 
-/* No launch takes more than `band` records — RT_HITQ_BAND, or fewer under the test hook RT_AMD_DIAG_HIT_BAND_RECORDS (rt_api_query.hip);
- * a multiple of 64, so that bands are whole 64-record chunks — as RT_TRACE_BAND_RAYS of rt_trace_rays.  The start of a band is
- * counted in 64 bits: n may be anything below 2^32, and the start of the band after the last one need not fit 32 bits. */
+/* No launch takes more than band_records records (rt_api_internal.h for_each_band; RT_HITQ_BAND, or fewer under the test hook
+ * RT_AMD_DIAG_HIT_BAND_RECORDS) — as RT_TRACE_BAND_RAYS of rt_trace_rays. */
 
 hipError_t launch_shade_hits(const KernelScene &sc, const rt_hit *hits, const rt_ray *incoming, uint32_t n, float *rgb,
                              unsigned long long *ray_count, bool wave_uniform, uint32_t band_records, hipStream_t stream) {
-    for (uint64_t off = 0u; off < n; off += band_records) {
-        const uint32_t band = (uint32_t)(n - off < band_records ? n - off : band_records);
-        const uint32_t groups = (band + RT_HITQ_THREADS - 1u) / RT_HITQ_THREADS;
+    return for_each_band(n, band_records, [&](uint64_t off, uint32_t band) {
         if (wave_uniform)
-            hipLaunchKernelGGL(shade_hits_kernel<true>, dim3(groups), dim3(RT_HITQ_THREADS), 0, stream, sc, hits + off, incoming + off,
+            hipLaunchKernelGGL(shade_hits_kernel<true>, grid_of(band, RT_HITQ_THREADS), dim3(RT_HITQ_THREADS), 0, stream, sc, hits + off, incoming + off,
                                rgb + (size_t)off * 3u, ray_count, band);
         else
-            hipLaunchKernelGGL(shade_hits_kernel<false>, dim3(groups), dim3(RT_HITQ_THREADS), 0, stream, sc, hits + off, incoming + off,
+            hipLaunchKernelGGL(shade_hits_kernel<false>, grid_of(band, RT_HITQ_THREADS), dim3(RT_HITQ_THREADS), 0, stream, sc, hits + off, incoming + off,
                                rgb + (size_t)off * 3u, ray_count, band);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    });
 }
 
 hipError_t launch_refract_rays(const KernelScene &sc, const rt_hit *hits, const rt_ray *incoming, uint32_t n, float max_distance, uint32_t *kind,
                                float *travel, rt_ray *escape, unsigned long long *ray_count, bool wave_uniform, uint32_t band_records, hipStream_t stream) {
-    for (uint64_t off = 0u; off < n; off += band_records) {
-        const uint32_t band = (uint32_t)(n - off < band_records ? n - off : band_records);
-        const uint32_t groups = (band + RT_HITQ_THREADS - 1u) / RT_HITQ_THREADS;
+    return for_each_band(n, band_records, [&](uint64_t off, uint32_t band) {
         float *const band_travel = travel != nullptr ? travel + off : nullptr;
         if (wave_uniform)
-            hipLaunchKernelGGL(refract_rays_kernel<true>, dim3(groups), dim3(RT_HITQ_THREADS), 0, stream, sc, hits + off, incoming + off,
+            hipLaunchKernelGGL(refract_rays_kernel<true>, grid_of(band, RT_HITQ_THREADS), dim3(RT_HITQ_THREADS), 0, stream, sc, hits + off, incoming + off,
                                max_distance, kind + off, band_travel, escape + off, ray_count, band);
         else
-            hipLaunchKernelGGL(refract_rays_kernel<false>, dim3(groups), dim3(RT_HITQ_THREADS), 0, stream, sc, hits + off, incoming + off,
+            hipLaunchKernelGGL(refract_rays_kernel<false>, grid_of(band, RT_HITQ_THREADS), dim3(RT_HITQ_THREADS), 0, stream, sc, hits + off, incoming + off,
                                max_distance, kind + off, band_travel, escape + off, ray_count, band);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    });
 }
 
 hipError_t launch_reflect_rays(const rt_hit *hits, const rt_ray *incoming, uint32_t n, rt_ray *out, uint32_t band_records, hipStream_t stream) {
-    for (uint64_t off = 0u; off < n; off += band_records) {
-        const uint32_t band = (uint32_t)(n - off < band_records ? n - off : band_records);
-        hipLaunchKernelGGL(reflect_rays_kernel, dim3((band + 255u) / 256u), dim3(256), 0, stream, hits + off, incoming + off, out + off, band);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    return for_each_band(n, band_records, [&](uint64_t off, uint32_t band) {
+        hipLaunchKernelGGL(reflect_rays_kernel, grid_of(band, 256u), dim3(256), 0, stream, hits + off, incoming + off, out + off, band);
+    });
 }
 
 } /* namespace rt */

@@ -158,8 +158,6 @@ __global__ __launch_bounds__(RT_LIGHT_THREADS) void light_fold_kernel(const Kern
     rgb[i * 3u + 2u] = sum.z;
 }
 
-static inline dim3 light_grid(uint64_t n) { return dim3((unsigned)((n + RT_LIGHT_THREADS - 1u) / RT_LIGHT_THREADS)); }
-
 } /* namespace rt */
 
 /* ---- the C entry points (include/rt_amd.h "light queries") ---- */
@@ -168,17 +166,16 @@ static inline dim3 light_grid(uint64_t n) { return dim3((unsigned)((n + RT_LIGHT
  * range of lights (rt_light_fold reads the material only) */
 static int light_args(const char *who, const rt_scene *scene, size_t n, int64_t light_first, uint32_t light_count, bool pointers_ok,
                       const char *pointers, bool *done) {
-    const std::string w(who);
     *done = true;
-    if ((uint64_t)n >= (1ull << 32)) return fail(RT_ERR_UNSUPPORTED, w + ": 2^32 records or more (checked first; query them in several calls)");
-    if ((uint64_t)n * (uint64_t)light_count >= (1ull << 32))
-        return fail(RT_ERR_UNSUPPORTED, w + ": 2^32 (record, light) pairs or more (checked first; pass the lights in several ranges)");
-    if (!scene) return fail(RT_ERR_INVALID_ARGUMENT, w + ": null scene");
-    if (n == 0 || light_count == 0) return RT_OK;
-    if (!pointers_ok) return fail(RT_ERR_INVALID_ARGUMENT, w + ": null " + pointers + " pointer");
+    int rc = check_count(who, n, RECORDS_2_32);
+    if (rc == RT_OK) rc = check_count(who, (uint64_t)n * (uint64_t)light_count, {32u, "(record, light) pairs", "pass the lights in several ranges"});
+    if (rc == RT_OK) rc = check_scene(who, scene);
+    if (rc != RT_OK || n == 0 || light_count == 0) return rc;
+    rc = check_pointers(who, pointers_ok, pointers);
+    if (rc != RT_OK) return rc;
     if (light_first >= 0 && (uint64_t)light_first + (uint64_t)light_count > (uint64_t)scene->ks.n_lights)
-        return fail(RT_ERR_INVALID_ARGUMENT, w + ": lights " + std::to_string(light_first) + " .. " + std::to_string((uint64_t)light_first + light_count) +
-                                                 " of a scene with " + std::to_string(scene->ks.n_lights));
+        return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": lights " + std::to_string(light_first) + " .. " +
+                                                 std::to_string((uint64_t)light_first + light_count) + " of a scene with " + std::to_string(scene->ks.n_lights));
     *done = false;
     return RT_OK;
 }
@@ -191,11 +188,9 @@ int rt_light_rays(const rt_scene *scene, const rt_hit *d_hits, const rt_ray *d_i
     const int rc = light_args("rt_light_rays", scene, n, light_first, light_count, d_hits && d_incoming && d_shadow_rays && d_asks,
                               "hit, incoming-ray, shadow-ray or flag", &done);
     if (rc != RT_OK || done) return rc;
-    hipLaunchKernelGGL(rt::light_rays_kernel, rt::light_grid(n), dim3(RT_LIGHT_THREADS), 0, static_cast<hipStream_t>(hip_stream), scene->ks, d_hits,
+    hipLaunchKernelGGL(rt::light_rays_kernel, grid_of(n, RT_LIGHT_THREADS), dim3(RT_LIGHT_THREADS), 0, static_cast<hipStream_t>(hip_stream), scene->ks, d_hits,
                        (uint64_t)n, light_first, light_count, d_shadow_rays, d_asks, d_light_distance);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail_hip("rt_light_rays: launch", e);
-    return RT_OK;
+    return launched("rt_light_rays");
 }
 
 int rt_light_terms(const rt_scene *scene, const rt_hit *d_hits, const rt_ray *d_incoming, size_t n, uint32_t light_first, uint32_t light_count,
@@ -206,11 +201,9 @@ int rt_light_terms(const rt_scene *scene, const rt_hit *d_hits, const rt_ray *d_
                               d_hits && d_incoming && d_asks && d_shadow_hits && d_lit && d_diffuse && d_specular,
                               "hit, incoming-ray, flag, shadow-hit, lit, diffuse or specular", &done);
     if (rc != RT_OK || done) return rc;
-    hipLaunchKernelGGL(rt::light_terms_kernel, rt::light_grid(n), dim3(RT_LIGHT_THREADS), 0, static_cast<hipStream_t>(hip_stream), scene->ks, d_hits,
+    hipLaunchKernelGGL(rt::light_terms_kernel, grid_of(n, RT_LIGHT_THREADS), dim3(RT_LIGHT_THREADS), 0, static_cast<hipStream_t>(hip_stream), scene->ks, d_hits,
                        d_incoming, (uint64_t)n, light_first, light_count, d_asks, d_shadow_hits, d_lit, d_diffuse, d_specular);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail_hip("rt_light_terms: launch", e);
-    return RT_OK;
+    return launched("rt_light_terms");
 }
 
 int rt_light_fold(const rt_scene *scene, const rt_hit *d_hits, size_t n, uint32_t light_count, const unsigned char *d_lit, const float *d_diffuse,
@@ -219,11 +212,9 @@ int rt_light_fold(const rt_scene *scene, const rt_hit *d_hits, size_t n, uint32_
     const int rc = light_args("rt_light_fold", scene, n, -1, light_count, d_hits && d_lit && d_diffuse && d_specular && d_rgb,
                               "hit, lit, diffuse, specular or rgb", &done);
     if (rc != RT_OK || done) return rc;
-    hipLaunchKernelGGL(rt::light_fold_kernel, rt::light_grid(n), dim3(RT_LIGHT_THREADS), 0, static_cast<hipStream_t>(hip_stream), scene->ks, d_hits,
+    hipLaunchKernelGGL(rt::light_fold_kernel, grid_of(n, RT_LIGHT_THREADS), dim3(RT_LIGHT_THREADS), 0, static_cast<hipStream_t>(hip_stream), scene->ks, d_hits,
                        (uint64_t)n, light_count, d_lit, d_diffuse, d_specular, d_rgb);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail_hip("rt_light_fold: launch", e);
-    return RT_OK;
+    return launched("rt_light_fold");
 }
 
 } /* extern "C" */

@@ -59,7 +59,7 @@ __global__ __launch_bounds__(RT_MESH_THREADS) void triangle_keys_kernel(const rt
 
 /* ---- the C entry points (include/rt_amd.h "mesh ordering") ---- */
 
-static inline bool mesh_too_many(size_t n) { return (uint64_t)n >= (1ull << 32); }
+static const CountLimit TRIANGLES_2_32 = {32u, "triangles", nullptr};
 
 /* the bits of the second sort: those of the largest object index, one at least */
 static inline uint32_t mesh_object_bits(uint32_t n_objects) {
@@ -72,39 +72,36 @@ extern "C" {
 
 int rt_triangle_keys(const rt_triangle *d_triangles, size_t n, const float box_lo[3], const float box_hi[3], uint32_t *d_keys, uint32_t *d_objects,
                      void *hip_stream) {
-    if (mesh_too_many(n)) return fail(RT_ERR_UNSUPPORTED, "rt_triangle_keys: 2^32 triangles or more (checked first)");
-    if (n == 0) return RT_OK;
-    if (!d_triangles || !box_lo || !box_hi || !d_keys) return fail(RT_ERR_INVALID_ARGUMENT, "rt_triangle_keys: null triangle, box or key pointer");
+    bool done;
+    const int rc = query_args("rt_triangle_keys", n, TRIANGLES_2_32, false, nullptr, d_triangles && box_lo && box_hi && d_keys, "triangle, box or key", &done);
+    if (rc != RT_OK || done) return rc;
     rt::MeshBox box;
     for (int a = 0; a < 3; ++a) {
         box.lo[a] = box_lo[a];
         box.scale[a] = box_hi[a] > box_lo[a] ? 1024.0f / (box_hi[a] - box_lo[a]) : 0.0f; /* a NaN bound compares false: 0 */
     }
-    const unsigned groups = (unsigned)(((uint64_t)n + RT_MESH_THREADS - 1u) / RT_MESH_THREADS);
-    hipLaunchKernelGGL(rt::triangle_keys_kernel, dim3(groups), dim3(RT_MESH_THREADS), 0, static_cast<hipStream_t>(hip_stream), d_triangles, (uint64_t)n, box,
+    hipLaunchKernelGGL(rt::triangle_keys_kernel, grid_of(n, RT_MESH_THREADS), dim3(RT_MESH_THREADS), 0, static_cast<hipStream_t>(hip_stream), d_triangles, (uint64_t)n, box,
                        d_keys, d_objects);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail_hip("rt_triangle_keys: launch", e);
-    return RT_OK;
+    return launched("rt_triangle_keys");
 }
 
 size_t rt_order_triangles_temp_bytes(size_t n) {
-    if (n == 0 || mesh_too_many(n)) return 0;
+    if (n == 0 || (uint64_t)n >= (1ull << 32)) return 0;
     return 2u * n * sizeof(uint32_t) + rt_sort_temp_bytes(n); /* keys, objects, the sort's workspace */
 }
 
 int rt_order_triangles(const rt_triangle *d_triangles, size_t n, const float box_lo[3], const float box_hi[3], uint32_t n_objects, uint32_t *d_perm,
                        rt_triangle *d_ordered_or_null, void *d_temp, size_t temp_bytes, void *hip_stream) {
-    if (mesh_too_many(n)) return fail(RT_ERR_UNSUPPORTED, "rt_order_triangles: 2^32 triangles or more (checked first)");
-    if (n == 0) return RT_OK;
-    if (!d_triangles || !box_lo || !box_hi || !d_perm || !d_temp)
-        return fail(RT_ERR_INVALID_ARGUMENT, "rt_order_triangles: null triangle, box, permutation or workspace pointer");
+    bool done;
+    int rc = query_args("rt_order_triangles", n, TRIANGLES_2_32, false, nullptr, d_triangles && box_lo && box_hi && d_perm && d_temp,
+                        "triangle, box, permutation or workspace", &done);
+    if (rc != RT_OK || done) return rc;
     if (temp_bytes < rt_order_triangles_temp_bytes(n))
         return fail(RT_ERR_INVALID_ARGUMENT, "rt_order_triangles: the workspace is smaller than rt_order_triangles_temp_bytes(n)");
     uint32_t *const keys = static_cast<uint32_t *>(d_temp), *const objects = keys + n;
     void *const sort_temp = objects + n;
     const size_t sort_bytes = rt_sort_temp_bytes(n);
-    int rc = rt_triangle_keys(d_triangles, n, box_lo, box_hi, keys, objects, hip_stream);
+    rc = rt_triangle_keys(d_triangles, n, box_lo, box_hi, keys, objects, hip_stream);
     /* Z-order first, then — stable — the object: equal (object, key) pairs keep their input order.  The second sort's list is the
      * first one's output, in place (rt_sort_records reads its list before it writes one) */
     if (rc == RT_OK) rc = rt_sort_records(keys, n, 0u, 30u, nullptr, nullptr, d_perm, sort_temp, sort_bytes, hip_stream);
@@ -116,34 +113,18 @@ int rt_order_triangles(const rt_triangle *d_triangles, size_t n, const float box
 
 int rt_order_triangles_host(const rt_triangle *h_triangles, size_t n, const float lo[3], const float hi[3], uint32_t n_objects, uint32_t *h_perm,
                             rt_triangle *h_ordered_or_null) {
-    if (mesh_too_many(n)) return fail(RT_ERR_UNSUPPORTED, "rt_order_triangles_host: 2^32 triangles or more (checked first)");
-    if (n == 0) return RT_OK;
-    if (!h_triangles || !lo || !hi || !h_perm) return fail(RT_ERR_INVALID_ARGUMENT, "rt_order_triangles_host: null triangle, box or permutation pointer");
+    bool done;
+    int rc = query_args("rt_order_triangles_host", n, TRIANGLES_2_32, false, nullptr, h_triangles && lo && hi && h_perm, "triangle, box or permutation", &done);
+    if (rc != RT_OK || done) return rc;
     const size_t tri_bytes = n * sizeof(rt_triangle), temp_bytes = rt_order_triangles_temp_bytes(n);
-    rt_triangle *d_triangles = nullptr, *d_ordered = nullptr;
-    uint32_t *d_perm = nullptr;
-    void *d_temp = nullptr;
-    RT_HIP(hipMalloc(reinterpret_cast<void **>(&d_triangles), tri_bytes)); /* no device: the status, nothing written */
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&d_perm), n * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc(&d_temp, temp_bytes);
-    if (e == hipSuccess && h_ordered_or_null) e = hipMalloc(reinterpret_cast<void **>(&d_ordered), tri_bytes);
-    if (e == hipSuccess) e = hipMemcpy(d_triangles, h_triangles, tri_bytes, hipMemcpyHostToDevice);
-    int rc = RT_OK;
-    if (e == hipSuccess) {
-        rc = rt_order_triangles(d_triangles, n, lo, hi, n_objects, d_perm, d_ordered, d_temp, temp_bytes, nullptr);
-        if (rc == RT_OK) {
-            e = hipDeviceSynchronize();
-            if (e == hipSuccess) e = hipMemcpy(h_perm, d_perm, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
-            if (e == hipSuccess && d_ordered) e = hipMemcpy(h_ordered_or_null, d_ordered, tri_bytes, hipMemcpyDeviceToHost);
-        }
-    }
-    (void)hipFree(d_triangles);
-    if (d_perm) (void)hipFree(d_perm);
-    if (d_temp) (void)hipFree(d_temp);
-    if (d_ordered) (void)hipFree(d_ordered);
-    if (rc != RT_OK) return rc;
-    if (e != hipSuccess) return fail_hip("rt_order_triangles_host", e);
-    return RT_OK;
+    HostRoundTrip t("rt_order_triangles_host"); /* no device: the status, nothing written */
+    const rt_triangle *d_triangles = t.in(h_triangles, tri_bytes);
+    uint32_t *d_perm = t.out(h_perm, n * sizeof(uint32_t));
+    void *d_temp = t.scratch(temp_bytes);
+    rt_triangle *d_ordered = t.out(h_ordered_or_null, tri_bytes); /* optional */
+    if (!t.ok()) return t.failed();
+    rc = rt_order_triangles(d_triangles, n, lo, hi, n_objects, d_perm, d_ordered, d_temp, temp_bytes, nullptr);
+    return rc != RT_OK ? rc : t.finish();
 }
 
 } /* extern "C" */

@@ -278,41 +278,38 @@ __global__ __launch_bounds__(RT_ORDER_THREADS) void scatter_records_kernel(const
 
 /* ---- the C entry points (include/rt_amd.h "record ordering") ---- */
 
-static inline bool order_too_many(size_t n) { return (uint64_t)n >= (1ull << 32); }
-
 /* the workspace of rt_sort_records for capacity n: two (key field, index) pair buffers and the bucket table */
 static inline uint64_t sort_temp_bytes(uint64_t n) { return (4u * n + rt::sort_table_words(n)) * sizeof(uint32_t); }
 
 extern "C" {
 
 int rt_ray_keys(const rt_ray *d_rays, size_t n, const float box_lo[3], const float box_hi[3], uint32_t flags, uint32_t *d_keys, void *hip_stream) {
-    if (order_too_many(n)) return fail(RT_ERR_UNSUPPORTED, "rt_ray_keys: 2^32 rays or more (checked first; key them in several calls)");
-    if (n == 0) return RT_OK;
-    if (!d_rays || !box_lo || !box_hi || !d_keys) return fail(RT_ERR_INVALID_ARGUMENT, "rt_ray_keys: null ray, box or key pointer");
+    bool done;
+    const int rc = query_args("rt_ray_keys", n, {32u, "rays", "key them in several calls"}, false, nullptr, d_rays && box_lo && box_hi && d_keys,
+                              "ray, box or key", &done);
+    if (rc != RT_OK || done) return rc;
     if ((flags & ~(uint32_t)RT_ORDER_DIRECTION_MAJOR) != 0u) return fail(RT_ERR_INVALID_ARGUMENT, "rt_ray_keys: unknown flag bit (RT_ORDER_DIRECTION_MAJOR is the only one)");
     rt::OrderBox box;
     for (int a = 0; a < 3; ++a) {
         box.lo[a] = box_lo[a];
         box.scale[a] = box_hi[a] > box_lo[a] ? 64.0f / (box_hi[a] - box_lo[a]) : 0.0f; /* a NaN bound compares false: 0 */
     }
-    const unsigned groups = (unsigned)(((uint64_t)n + RT_ORDER_THREADS - 1u) / RT_ORDER_THREADS);
-    hipLaunchKernelGGL(rt::ray_keys_kernel, dim3(groups), dim3(RT_ORDER_THREADS), 0, static_cast<hipStream_t>(hip_stream), d_rays, (uint64_t)n, box,
+    hipLaunchKernelGGL(rt::ray_keys_kernel, grid_of(n, RT_ORDER_THREADS), dim3(RT_ORDER_THREADS), 0, static_cast<hipStream_t>(hip_stream), d_rays, (uint64_t)n, box,
                        flags & (uint32_t)RT_ORDER_DIRECTION_MAJOR, d_keys);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail_hip("rt_ray_keys: launch", e);
-    return RT_OK;
+    return launched("rt_ray_keys");
 }
 
 size_t rt_sort_temp_bytes(size_t n) {
-    if (n == 0 || order_too_many(n)) return 0;
+    if (n == 0 || (uint64_t)n >= (1ull << 32)) return 0;
     return (size_t)sort_temp_bytes((uint64_t)n);
 }
 
 int rt_sort_records(const uint32_t *d_keys, size_t n, uint32_t first_bit, uint32_t key_bits, const uint32_t *d_index_in, const uint32_t *d_count_in,
                     uint32_t *d_index_out, void *d_temp, size_t temp_bytes, void *hip_stream) {
-    if (order_too_many(n)) return fail(RT_ERR_UNSUPPORTED, "rt_sort_records: 2^32 records or more (checked first; sort them in several calls)");
-    if (n == 0) return RT_OK;
-    if (!d_keys || !d_index_out || !d_temp) return fail(RT_ERR_INVALID_ARGUMENT, "rt_sort_records: null key, output or workspace pointer");
+    bool done;
+    const int rc = query_args("rt_sort_records", n, {32u, "records", "sort them in several calls"}, false, nullptr, d_keys && d_index_out && d_temp,
+                              "key, output or workspace", &done);
+    if (rc != RT_OK || done) return rc;
     if (key_bits == 0u || (uint64_t)first_bit + key_bits > 32u)
         return fail(RT_ERR_INVALID_ARGUMENT, "rt_sort_records: need key_bits >= 1 and first_bit + key_bits <= 32");
     if ((uint64_t)temp_bytes < sort_temp_bytes((uint64_t)n))
@@ -342,22 +339,19 @@ int rt_sort_records(const uint32_t *d_keys, size_t n, uint32_t first_bit, uint32
                            (const uint32_t *)pair_index[cur], (uint64_t)n, d_count_in, tile, tiles, shift, (const uint32_t *)table,
                            last ? (uint32_t *)nullptr : pair_keys[cur ^ 1u], last ? d_index_out : pair_index[cur ^ 1u]);
     }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail_hip("rt_sort_records: launch", e);
-    return RT_OK;
+    return launched("rt_sort_records");
 }
 
 /* the checks the two record movers share, in the documented order; *done: nothing to launch */
 static int move_records_args(const char *who, const void *d_src, size_t record_bytes, size_t n, const uint32_t *d_index, size_t max_count,
                              const void *d_dst, bool *done) {
-    const std::string w(who);
     *done = true;
-    if (order_too_many(n) || order_too_many(max_count))
-        return fail(RT_ERR_UNSUPPORTED, w + ": 2^32 records or index entries or more (checked first; move them in several calls)");
-    if (n == 0 || max_count == 0) return RT_OK;
-    if (!d_src || !d_index || !d_dst) return fail(RT_ERR_INVALID_ARGUMENT, w + ": null source, index or destination pointer");
+    int rc = check_count(who, std::max<uint64_t>(n, max_count), {32u, "records or index entries", "move them in several calls"});
+    if (rc != RT_OK || n == 0 || max_count == 0) return rc;
+    rc = check_pointers(who, d_src && d_index && d_dst, "source, index or destination");
+    if (rc != RT_OK) return rc;
     if (record_bytes < 4 || record_bytes > 256 || (record_bytes & 3u) != 0)
-        return fail(RT_ERR_INVALID_ARGUMENT, w + ": record_bytes must be a multiple of 4 from 4 to 256");
+        return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": record_bytes must be a multiple of 4 from 4 to 256");
     *done = false;
     return RT_OK;
 }
@@ -368,12 +362,9 @@ int rt_gather_records(const void *d_src, size_t record_bytes, size_t n, const ui
     const int rc = move_records_args("rt_gather_records", d_src, record_bytes, n, d_index, max_count, d_dst, &done);
     if (rc != RT_OK || done) return rc;
     const uint32_t words = (uint32_t)(record_bytes / 4);
-    const unsigned groups = (unsigned)(((uint64_t)max_count * words + RT_ORDER_THREADS - 1u) / RT_ORDER_THREADS); /* below 2^30 */
-    hipLaunchKernelGGL(rt::gather_records_kernel, dim3(groups), dim3(RT_ORDER_THREADS), 0, static_cast<hipStream_t>(hip_stream),
+    hipLaunchKernelGGL(rt::gather_records_kernel, grid_of((uint64_t)max_count * words, RT_ORDER_THREADS) /* below 2^30 */, dim3(RT_ORDER_THREADS), 0, static_cast<hipStream_t>(hip_stream),
                        static_cast<const uint32_t *>(d_src), words, (uint64_t)n, d_index, d_count, (uint64_t)max_count, static_cast<uint32_t *>(d_dst));
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail_hip("rt_gather_records: launch", e);
-    return RT_OK;
+    return launched("rt_gather_records");
 }
 
 int rt_scatter_records(const void *d_src, size_t record_bytes, size_t n, const uint32_t *d_index, const uint32_t *d_count, size_t max_count, void *d_dst,
@@ -382,12 +373,9 @@ int rt_scatter_records(const void *d_src, size_t record_bytes, size_t n, const u
     const int rc = move_records_args("rt_scatter_records", d_src, record_bytes, n, d_index, max_count, d_dst, &done);
     if (rc != RT_OK || done) return rc;
     const uint32_t words = (uint32_t)(record_bytes / 4);
-    const unsigned groups = (unsigned)(((uint64_t)max_count * words + RT_ORDER_THREADS - 1u) / RT_ORDER_THREADS);
-    hipLaunchKernelGGL(rt::scatter_records_kernel, dim3(groups), dim3(RT_ORDER_THREADS), 0, static_cast<hipStream_t>(hip_stream),
+    hipLaunchKernelGGL(rt::scatter_records_kernel, grid_of((uint64_t)max_count * words, RT_ORDER_THREADS), dim3(RT_ORDER_THREADS), 0, static_cast<hipStream_t>(hip_stream),
                        static_cast<const uint32_t *>(d_src), words, (uint64_t)n, d_index, d_count, (uint64_t)max_count, static_cast<uint32_t *>(d_dst));
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail_hip("rt_scatter_records: launch", e);
-    return RT_OK;
+    return launched("rt_scatter_records");
 }
 
 } /* extern "C" */

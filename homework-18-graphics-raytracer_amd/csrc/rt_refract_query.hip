@@ -100,50 +100,32 @@ __global__ __launch_bounds__(RT_REFR_THREADS) void refract_step_kernel(const Ker
     flags[i] = 0;
 }
 
-static inline dim3 refract_grid(uint64_t n) { return dim3((unsigned)((n + RT_REFR_THREADS - 1u) / RT_REFR_THREADS)); }
-
 } /* namespace rt */
 
 /* ---- the C entry points (include/rt_amd.h "refraction queries") ---- */
-
-/* the block's checks before any device work, in the documented order; *done: nothing to launch */
-static int refract_args(const char *who, const rt_scene *scene, size_t n, bool pointers_ok, const char *pointers, bool *done) {
-    const std::string w(who);
-    *done = true;
-    if ((uint64_t)n >= (1ull << 32)) return fail(RT_ERR_UNSUPPORTED, w + ": 2^32 records or more (checked first; query them in several calls)");
-    if (!scene) return fail(RT_ERR_INVALID_ARGUMENT, w + ": null scene");
-    if (n == 0) return RT_OK;
-    if (!pointers_ok) return fail(RT_ERR_INVALID_ARGUMENT, w + ": null " + pointers + " pointer");
-    *done = false;
-    return RT_OK;
-}
 
 extern "C" {
 
 int rt_refract_enter(const rt_scene *scene, const rt_hit *d_hits, const rt_ray *d_incoming, size_t n, rt_ray *d_rays, uint32_t *d_kind,
                      float *d_travel, uint32_t *d_casts, unsigned char *d_flags, void *hip_stream) {
     bool done;
-    const int rc = refract_args("rt_refract_enter", scene, n, d_hits && d_incoming && d_rays && d_kind && d_travel && d_casts && d_flags,
+    const int rc = query_args("rt_refract_enter", n, RECORDS_2_32, true, scene, d_hits && d_incoming && d_rays && d_kind && d_travel && d_casts && d_flags,
                                 "hit, incoming-ray, ray, kind, travel, cast-count or flag", &done);
     if (rc != RT_OK || done) return rc;
-    hipLaunchKernelGGL(rt::refract_enter_kernel, rt::refract_grid(n), dim3(RT_REFR_THREADS), 0, static_cast<hipStream_t>(hip_stream), scene->ks,
+    hipLaunchKernelGGL(rt::refract_enter_kernel, grid_of(n, RT_REFR_THREADS), dim3(RT_REFR_THREADS), 0, static_cast<hipStream_t>(hip_stream), scene->ks,
                        d_hits, d_incoming, (uint64_t)n, d_rays, d_kind, d_travel, d_casts, d_flags);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail_hip("rt_refract_enter: launch", e);
-    return RT_OK;
+    return launched("rt_refract_enter");
 }
 
 int rt_refract_step(const rt_scene *scene, const rt_hit *d_hits, size_t n, float max_distance, const rt_hit *d_inside_hits, rt_ray *d_rays,
                     uint32_t *d_kind, float *d_travel, uint32_t *d_casts, unsigned char *d_flags, rt_ray *d_escape, void *hip_stream) {
     bool done;
-    const int rc = refract_args("rt_refract_step", scene, n, d_hits && d_inside_hits && d_rays && d_kind && d_travel && d_casts && d_flags && d_escape,
+    const int rc = query_args("rt_refract_step", n, RECORDS_2_32, true, scene, d_hits && d_inside_hits && d_rays && d_kind && d_travel && d_casts && d_flags && d_escape,
                                 "hit, inside-hit, ray, kind, travel, cast-count, flag or escape-ray", &done);
     if (rc != RT_OK || done) return rc;
-    hipLaunchKernelGGL(rt::refract_step_kernel, rt::refract_grid(n), dim3(RT_REFR_THREADS), 0, static_cast<hipStream_t>(hip_stream), scene->ks,
+    hipLaunchKernelGGL(rt::refract_step_kernel, grid_of(n, RT_REFR_THREADS), dim3(RT_REFR_THREADS), 0, static_cast<hipStream_t>(hip_stream), scene->ks,
                        d_hits, (uint64_t)n, max_distance, d_inside_hits, d_rays, d_kind, d_travel, d_casts, d_flags, d_escape);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail_hip("rt_refract_step: launch", e);
-    return RT_OK;
+    return launched("rt_refract_step");
 }
 
 } /* extern "C" */

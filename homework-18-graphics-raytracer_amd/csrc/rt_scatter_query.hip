@@ -18,6 +18,7 @@
 #define RT_DIST_RAYS_TU
 #include "rt_distributed.hip"
 #include "rt_hit_abi.h"
+#include "rt_api_internal.h"
 
 namespace rt {
 
@@ -107,32 +108,24 @@ __global__ __launch_bounds__(256) void scatter_factors_kernel(const KernelScene 
     rgb[(size_t)i * 3u + 2u] = factor.z;
 }
 
-/* Bands of at most band_records records per launch, whole 64-record chunks, their start counted in 64 bits (as rt_hit_query.hip).
- * Without an index array a band's first generator is the band's first record. */
+/* Bands of at most band_records records per launch (rt_api_internal.h for_each_band, as rt_hit_query.hip).  Without an index array a
+ * band's first generator is the band's first record. */
 
 hipError_t launch_scatter_hits(const KernelScene &sc, const rt_hit *hits, const rt_ray *incoming, uint32_t n, uint32_t *states, uint32_t n_generators,
                                const uint32_t *rng_index, uint32_t *type, rt_ray *scattered, float *cosine, uint32_t band_records, hipStream_t stream) {
-    for (uint64_t off = 0u; off < n; off += band_records) {
-        const uint32_t band = (uint32_t)(n - off < band_records ? n - off : band_records);
-        hipLaunchKernelGGL(scatter_hits_kernel, dim3((band + 255u) / 256u), dim3(256), 0, stream, sc, hits + off, incoming + off, states, n_generators,
+    return for_each_band(n, band_records, [&](uint64_t off, uint32_t band) {
+        hipLaunchKernelGGL(scatter_hits_kernel, grid_of(band, 256u), dim3(256), 0, stream, sc, hits + off, incoming + off, states, n_generators,
                            rng_index != nullptr ? rng_index + off : nullptr, (uint32_t)off, type + off, scattered + off,
                            cosine != nullptr ? cosine + off : nullptr, band);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    });
 }
 
 hipError_t launch_scatter_factors(const KernelScene &sc, const rt_hit *hits, const rt_ray *incoming, const uint32_t *types, const rt_ray *next,
                                   const float *travel, uint32_t n, float *rgb, uint32_t band_records, hipStream_t stream) {
-    for (uint64_t off = 0u; off < n; off += band_records) {
-        const uint32_t band = (uint32_t)(n - off < band_records ? n - off : band_records);
-        hipLaunchKernelGGL(scatter_factors_kernel, dim3((band + 255u) / 256u), dim3(256), 0, stream, sc, hits + off, incoming + off, types + off,
+    return for_each_band(n, band_records, [&](uint64_t off, uint32_t band) {
+        hipLaunchKernelGGL(scatter_factors_kernel, grid_of(band, 256u), dim3(256), 0, stream, sc, hits + off, incoming + off, types + off,
                            next + off, travel + off, rgb + (size_t)off * 3u, band);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    });
 }
 
 } /* namespace rt */

@@ -323,12 +323,6 @@ UpdScene upd_scene(const rt_scene *scene) {
     return u;
 }
 
-bool capturing(hipStream_t stream) {
-    hipStreamCaptureStatus status = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(stream, &status) != hipSuccess) (void)hipGetLastError();
-    return status != hipStreamCaptureStatusNone;
-}
-
 /* the house order of the argument checks, before any device work; 1: nothing to do */
 int check_range(const char *who, uint32_t first, uint32_t count, uint32_t have, const void *data) {
     if ((uint64_t)first + (uint64_t)count > (uint64_t)have) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": first + count is beyond the scene's array");
@@ -341,7 +335,7 @@ int check_range(const char *who, uint32_t first, uint32_t count, uint32_t have, 
  * copies of the call before it. */
 int stage_and_copy(rt_scene *scene, const char *who, hipStream_t stream, void *d_a, const void *h_a, size_t bytes_a, void *d_b, const void *h_b,
                    size_t bytes_b) {
-    if (capturing(stream)) return fail(RT_ERR_UNSUPPORTED, std::string(who) + ": the stream is being captured (the records are read from host memory at the call)");
+    if (stream_capturing(stream)) return fail(RT_ERR_UNSUPPORTED, std::string(who) + ": the stream is being captured (the records are read from host memory at the call)");
     SceneUpdate &u = scene->upd;
     std::lock_guard<std::mutex> lock(u.mutex);
     const size_t need = bytes_a + bytes_b;
@@ -377,7 +371,7 @@ int rt_scene_update_vertices(rt_scene *scene, uint32_t first, uint32_t count, co
     {   /* the node ranges: kept on the host by rt_scene_create, uploaded with the first update (an allocation: not inside a capture) */
         std::lock_guard<std::mutex> lock(u.mutex);
         if (!u.uploaded) {
-            if (capturing(stream)) return fail(RT_ERR_UNSUPPORTED, "rt_scene_update_vertices: the first update of a scene allocates and cannot be captured");
+            if (stream_capturing(stream)) return fail(RT_ERR_UNSUPPORTED, "rt_scene_update_vertices: the first update of a scene allocates and cannot be captured");
             std::vector<RefitNode> small, large;
             for (const RefitNode &n : u.nodes) (n.hi - n.lo > RT_REFIT_WAVE_MAX ? large : small).push_back(n);
             const size_t total = small.size() + large.size();

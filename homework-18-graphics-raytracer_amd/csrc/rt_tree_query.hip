@@ -166,63 +166,44 @@ __global__ __launch_bounds__(RT_TREE_THREADS) void tree_fold_kernel(const rt_hit
     out[slot * 3u + 2u] = value.z;
 }
 
-static inline dim3 tree_grid(uint64_t n) { return dim3((unsigned)((n + RT_TREE_THREADS - 1u) / RT_TREE_THREADS)); }
-
 } /* namespace rt */
 
 /* ---- the C entry points (include/rt_amd.h "tree loop") ---- */
 
-/* the block's checks before any device work, in the documented order; *done: nothing to launch */
-static int tree_args(const char *who, uint64_t limit_log2, size_t n, bool needs_scene, const void *scene, bool pointers_ok, const char *pointers,
-                     bool *done) {
-    const std::string w(who);
-    *done = true;
-    if ((uint64_t)n >= (1ull << limit_log2))
-        return fail(RT_ERR_UNSUPPORTED, w + ": 2^" + std::to_string(limit_log2) + " records or more (checked first; split the level)");
-    if (needs_scene && !scene) return fail(RT_ERR_INVALID_ARGUMENT, w + ": null scene");
-    if (n == 0) return RT_OK;
-    if (!pointers_ok) return fail(RT_ERR_INVALID_ARGUMENT, w + ": null " + pointers + " pointer");
-    *done = false;
-    return RT_OK;
-}
+/* a level of 2^32 (2^31 where a record has two children) records or more is refused: the caller splits it */
+static const CountLimit TREE_2_32 = {32u, "records", "split the level"}, TREE_2_31 = {31u, "records", "split the level"};
 
 extern "C" {
 
 int rt_tree_gate(const float *d_contribution, size_t n, const uint32_t *d_count, unsigned char *d_flags, rt_hit *d_hits, void *hip_stream) {
     bool done;
-    const int rc = tree_args("rt_tree_gate", 32, n, false, nullptr, d_contribution && d_flags && d_hits, "contribution, flag or hit", &done);
+    const int rc = query_args("rt_tree_gate", n, TREE_2_32, false, nullptr, d_contribution && d_flags && d_hits, "contribution, flag or hit", &done);
     if (rc != RT_OK || done) return rc;
-    hipLaunchKernelGGL(rt::tree_gate_kernel, rt::tree_grid(n), dim3(RT_TREE_THREADS), 0, static_cast<hipStream_t>(hip_stream), d_contribution, (uint64_t)n,
+    hipLaunchKernelGGL(rt::tree_gate_kernel, grid_of(n, RT_TREE_THREADS), dim3(RT_TREE_THREADS), 0, static_cast<hipStream_t>(hip_stream), d_contribution, (uint64_t)n,
                        d_count, d_flags, d_hits);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail_hip("rt_tree_gate: launch", e);
-    return RT_OK;
+    return launched("rt_tree_gate");
 }
 
 int rt_tree_split(const rt_scene *scene, const rt_hit *d_hits, const float *d_contribution, size_t n, const uint32_t *d_count, int32_t depth_left,
                   rt_hit *d_hits_shade, rt_hit *d_hits_reflect, rt_hit *d_hits_refract, float *d_weights, void *hip_stream) {
     bool done;
-    const int rc = tree_args("rt_tree_split", 32, n, true, scene, d_hits && d_contribution && d_hits_shade && d_hits_reflect && d_hits_refract && d_weights,
+    const int rc = query_args("rt_tree_split", n, TREE_2_32, true, scene, d_hits && d_contribution && d_hits_shade && d_hits_reflect && d_hits_refract && d_weights,
                              "hit, contribution, output-hit or weight", &done);
     if (rc != RT_OK || done) return rc;
-    hipLaunchKernelGGL(rt::tree_split_kernel, rt::tree_grid(n), dim3(RT_TREE_THREADS), 0, static_cast<hipStream_t>(hip_stream), scene->ks.materials,
+    hipLaunchKernelGGL(rt::tree_split_kernel, grid_of(n, RT_TREE_THREADS), dim3(RT_TREE_THREADS), 0, static_cast<hipStream_t>(hip_stream), scene->ks.materials,
                        scene->ks.n_materials, d_hits, d_contribution, (uint64_t)n, d_count, depth_left, d_hits_shade, d_hits_reflect, d_hits_refract,
                        d_weights);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail_hip("rt_tree_split: launch", e);
-    return RT_OK;
+    return launched("rt_tree_split");
 }
 
 int rt_tree_spawn(const rt_hit *d_hits_reflect, const uint32_t *d_refr_kind, size_t n, unsigned char *d_flags, float *d_child_values, void *hip_stream) {
     bool done;
-    const int rc = tree_args("rt_tree_spawn", 31, n, false, nullptr, d_hits_reflect && d_refr_kind && d_flags && d_child_values,
+    const int rc = query_args("rt_tree_spawn", n, TREE_2_31, false, nullptr, d_hits_reflect && d_refr_kind && d_flags && d_child_values,
                              "reflect-hit, refraction-kind, flag or child-value", &done);
     if (rc != RT_OK || done) return rc;
-    hipLaunchKernelGGL(rt::tree_spawn_kernel, rt::tree_grid(n), dim3(RT_TREE_THREADS), 0, static_cast<hipStream_t>(hip_stream), d_hits_reflect, d_refr_kind,
+    hipLaunchKernelGGL(rt::tree_spawn_kernel, grid_of(n, RT_TREE_THREADS), dim3(RT_TREE_THREADS), 0, static_cast<hipStream_t>(hip_stream), d_hits_reflect, d_refr_kind,
                        (uint64_t)n, d_flags, d_child_values);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail_hip("rt_tree_spawn: launch", e);
-    return RT_OK;
+    return launched("rt_tree_spawn");
 }
 
 int rt_tree_gather(const uint32_t *d_index, const uint32_t *d_count, size_t max_count, const rt_ray *d_reflected, const rt_ray *d_escape,
@@ -231,19 +212,17 @@ int rt_tree_gather(const uint32_t *d_index, const uint32_t *d_count, size_t max_
     if ((uint64_t)max_count >= (1ull << 32))
         return fail(RT_ERR_UNSUPPORTED, "rt_tree_gather: a capacity of 2^32 records or more (checked first; split the level)");
     bool done;
-    const int rc = tree_args("rt_tree_gather", 31, n, false, nullptr,
+    const int rc = query_args("rt_tree_gather", n, TREE_2_31, false, nullptr,
                              d_index && d_count && d_reflected && d_escape && d_contribution && d_weights && d_child_count && d_overflow &&
                                  (max_count == 0 || (d_child_rays && d_child_contribution && d_child_parent)),
                              "index, count, ray, contribution, weight, child or overflow", &done);
     if (rc != RT_OK || done) return rc;
     /* the grid covers what can be kept; with no room at all one workgroup still writes the count and the overflow */
     const uint64_t most = (uint64_t)max_count < 2u * (uint64_t)n ? (uint64_t)max_count : 2u * (uint64_t)n;
-    hipLaunchKernelGGL(rt::tree_gather_kernel, rt::tree_grid(most > 0u ? most : 1u), dim3(RT_TREE_THREADS), 0, static_cast<hipStream_t>(hip_stream), d_index,
+    hipLaunchKernelGGL(rt::tree_gather_kernel, grid_of(most > 0u ? most : 1u, RT_TREE_THREADS), dim3(RT_TREE_THREADS), 0, static_cast<hipStream_t>(hip_stream), d_index,
                        d_count, (uint64_t)max_count, d_reflected, d_escape, d_contribution, d_weights, (uint64_t)n, d_child_rays, d_child_contribution,
                        d_child_parent, d_child_count, d_overflow);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail_hip("rt_tree_gather: launch", e);
-    return RT_OK;
+    return launched("rt_tree_gather");
 }
 
 int rt_tree_fold(const rt_hit *d_hits, const uint32_t *d_count, size_t n, int32_t depth_left, const float *d_shade, const float *d_weights,
@@ -251,14 +230,12 @@ int rt_tree_fold(const rt_hit *d_hits, const uint32_t *d_count, size_t n, int32_
                  void *hip_stream) {
     bool done;
     const bool below = depth_left <= 0 || (d_weights && d_refr_kind && d_travel && d_child_values);
-    const int rc = tree_args("rt_tree_fold", 32, n, false, nullptr, d_hits && d_shade && d_out && below, "hit, shade, weight, refraction, child-value or output",
+    const int rc = query_args("rt_tree_fold", n, TREE_2_32, false, nullptr, d_hits && d_shade && d_out && below, "hit, shade, weight, refraction, child-value or output",
                              &done);
     if (rc != RT_OK || done) return rc;
-    hipLaunchKernelGGL(rt::tree_fold_kernel, rt::tree_grid(n), dim3(RT_TREE_THREADS), 0, static_cast<hipStream_t>(hip_stream), d_hits, d_count, (uint64_t)n,
+    hipLaunchKernelGGL(rt::tree_fold_kernel, grid_of(n, RT_TREE_THREADS), dim3(RT_TREE_THREADS), 0, static_cast<hipStream_t>(hip_stream), d_hits, d_count, (uint64_t)n,
                        depth_left, d_shade, d_weights, d_refr_kind, d_travel, d_child_values, d_parent, d_out, (uint64_t)n_out);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail_hip("rt_tree_fold: launch", e);
-    return RT_OK;
+    return launched("rt_tree_fold");
 }
 
 } /* extern "C" */
