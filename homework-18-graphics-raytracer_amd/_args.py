@@ -1,0 +1,126 @@
+"""Argument helpers of the Python layer: the one tensor check, allocation, and the pointers the C entry points take.
+
+torch is imported here, on first use, and nowhere else in the package outside dist.py: importing the package does not load it, and
+the numpy-only paths never do.  Dtypes travel by name ("int32", "float32", "uint8", ...) so that callers need no torch of their own.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Sequence
+
+import numpy as np
+
+_torch_module = None
+
+
+def _torch():
+    global _torch_module
+    if _torch_module is None:
+        import torch
+
+        _torch_module = torch
+    return _torch_module
+
+
+def _dtype(dtype):
+    return getattr(_torch(), dtype) if isinstance(dtype, str) else dtype
+
+
+def _tensor(t, name, dtype, shape, cuda=True, contiguous=True, optional=False):
+    """THE check of a tensor argument: ``t`` must be a torch tensor of ``dtype`` (by name) whose shape matches the pattern ``shape`` —
+    a fixed integer must match, None accepts any extent; ``shape=None`` accepts any shape — on the device (``cuda``) and contiguous
+    (``contiguous``).  ``optional`` lets None through.  Returns ``t``; raises ValueError naming the parameter, dtype and shape."""
+    if t is None and optional:
+        return None
+    torch = _torch()
+    if torch.is_tensor(t) and t.dtype == getattr(torch, dtype) and (t.is_cuda or not cuda) and (not contiguous or t.is_contiguous()):
+        if shape is None:
+            return t
+        extents = t.shape
+        if len(extents) == len(shape):
+            for have, want in zip(extents, shape):
+                if want is not None and have != want:
+                    break
+            else:
+                return t
+    raise ValueError(_expected(name, dtype, shape, cuda, contiguous))
+
+
+def _expected(name, dtype, shape, cuda, contiguous):
+    extents = "of any shape" if shape is None else "(" + ", ".join("N" if e is None else str(e) for e in shape) + ("," if len(shape) == 1 else "") + ")"
+    return f"{name} must be a {'contiguous ' if contiguous else ''}{extents} {dtype} {'CUDA ' if cuda else ''}tensor"
+
+
+def _new(shape, dtype, device):
+    """an uninitialised tensor, dtype by name"""
+    return _torch().empty(shape, dtype=_dtype(dtype), device=device)
+
+
+def _allocator(device):
+    """new(shape, dtype) on ``device``: what the loops make their buffers with"""
+    return lambda shape, dtype: _new(shape, dtype, device)
+
+
+def _out_tensor(out, shape, dtype, device, name="out"):
+    """``out`` if the caller gave one — it must be a contiguous CUDA tensor of this shape and dtype — or a new one on ``device``"""
+    return _new(shape, dtype, device) if out is None else _tensor(out, name, dtype, shape)
+
+
+def _on_stream(stream):
+    """``with _on_stream(stream):`` — ``stream`` (default: the current one) as torch's current stream: what is allocated inside is
+    tied to it by the caching allocator, what torch enqueues inside goes to it"""
+    torch = _torch()
+    return torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream())
+
+
+def _stream_ptr(stream):
+    """``stream`` (default: torch's current stream) as the void pointer the C entry points take"""
+    s = stream if stream is not None else _torch().cuda.current_stream()
+    return C.c_void_p(s.cuda_stream)
+
+
+def _p(t):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _count_ptr(ray_count):
+    """the pointer of a cast counter, or None: any int64 CUDA tensor with one element, whatever its shape"""
+    if ray_count is None:
+        return None
+    if _tensor(ray_count, "ray_count", "int64", None, contiguous=False).numel() != 1:
+        raise ValueError("ray_count must be a 1-element int64 CUDA tensor")
+    return _p(ray_count)
+
+
+def _words(t, name):
+    """a contiguous CUDA tensor of 4-byte elements, one or two dimensional: (records, words per record)"""
+    if not (_torch().is_tensor(t) and t.is_cuda and t.is_contiguous() and t.element_size() == 4 and t.dim() in (1, 2)):
+        raise ValueError(f"{name} must be a contiguous CUDA tensor of 4-byte elements, (N,) or (N, words)")
+    return t.shape[0], (1 if t.dim() == 1 else t.shape[1])
+
+
+def _host_records(a, dtype, words, name):
+    a = np.asarray(a)
+    if a.dtype == dtype:
+        return np.ascontiguousarray(a).reshape(-1)
+    if a.ndim == 2 and a.shape[1] == words and a.dtype.itemsize == 4:
+        return np.ascontiguousarray(a).view(dtype).reshape(-1)
+    raise ValueError(f"{name}: expected a {'HIT' if words == 13 else 'RAY'}_DTYPE array or an (N, {words}) array of 4-byte words")
+
+
+def _host_column(a, dtype, n, name):
+    a = np.asarray(a)
+    if not (a.dtype.kind in dtype[0] and a.dtype.itemsize == 4 and a.shape == (n,)):
+        raise ValueError(f"{name}: expected an ({n},) array of {dtype[1]}")
+    return np.ascontiguousarray(a)
+
+
+def _box3(v, name):
+    a = np.asarray(v, dtype=np.float32).reshape(-1)
+    if a.shape != (3,):
+        raise ValueError(f"{name} must hold 3 floats")
+    return (C.c_float * 3)(*a.tolist())
+
+
+def _f3(v: Sequence[float]):
+    return (C.c_float * 3)(*[float(x) for x in v])
