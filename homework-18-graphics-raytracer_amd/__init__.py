@@ -22,11 +22,12 @@ reference's host-side names on top of them:
     cast_rays_ordered / trace_rays_ordered     cast_rays and trace_rays again, on rays the device put into a coherent order first
     triangle_keys / order_triangles / World.ordered   the order of a mesh: include/rt_amd.h "mesh ordering"
     unorder_hits / order_rays      triangle indices between an ordered world and the one it was made from
+    materials (a submodule)        src/main.rs:408-410 and materials.rs:46-66: approx, adjust_normal and the Phong terms on caller-supplied hits
     post_process / write_to_file   src/main.rs:748-776
 
 PyTorch is used only for device memory, streams and torch.distributed.
 """
-from . import _capi
+from . import _capi, materials
 from ._capi import Camera, Frame, Light, Material, RtError, SceneDesc, Sphere, Triangle, Vertex
 from ._world import DEFAULT_OBJ, ObjectProxy, Scene, World, reference_camera, reference_world
 from ._render import (Rng, focus_rays, options, render_distributed, render_distributed_numpy, render_whitted, render_whitted_numpy,

@@ -134,9 +134,18 @@ class Hit(C.Structure):  # main.rs:139-147 Hit, flattened (rt_hit)
     ]
 
 
+class Surface(C.Structure):  # materials.rs:21-31 ColorMaterial as approx returns it, and adjust_normal's result (rt_surface)
+    _fields_ = [
+        ("normal", C.c_float * 3), ("diffuse_color", C.c_float * 3), ("shiness", C.c_float), ("specular_color", C.c_float * 3),
+        ("smoothness", C.c_float), ("transparency", C.c_float), ("refraction_index", C.c_float), ("opaque_decay", C.c_float),
+        ("shading_normal", C.c_float * 3), ("valid", C.c_uint32),
+    ]
+
+
 RT_HIT_NONE = 0xFFFFFFFF
 RAY_WORDS = C.sizeof(Ray) // 4  # 11
 HIT_WORDS = C.sizeof(Hit) // 4  # 13
+SURFACE_WORDS = C.sizeof(Surface) // 4  # 18
 
 
 # every symbol include/rt_amd.h declares (checked by tests/test_capi_symbols.py)
@@ -169,6 +178,7 @@ AMD_SYMBOLS = [
     "rt_select_records", "rt_cast_rays_indexed", "rt_level_split", "rt_level_join", "rt_level_close", "rt_level_fold", "rt_level_finish",
     "rt_tree_gate", "rt_tree_split", "rt_tree_spawn", "rt_tree_gather", "rt_tree_fold",
     "rt_light_rays", "rt_light_terms", "rt_light_fold",
+    "rt_material_hits", "rt_material_hits_host", "rt_probe_surfaces", "rt_probe_surfaces_host",
     "rt_refract_enter", "rt_refract_step",
     "rt_scene_update_vertices", "rt_scene_update_spheres", "rt_scene_update_lights", "rt_scene_update_materials",
     "rt_ray_keys", "rt_sort_temp_bytes", "rt_sort_records", "rt_gather_records", "rt_scatter_records",
@@ -328,6 +338,10 @@ def amd_lib() -> C.CDLL:
         lib.rt_light_terms.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p]
         lib.rt_light_fold.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.rt_material_hits.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        lib.rt_material_hits_host.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.rt_probe_surfaces.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.rt_probe_surfaces_host.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         lib.rt_refract_enter.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p]
         lib.rt_refract_step.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

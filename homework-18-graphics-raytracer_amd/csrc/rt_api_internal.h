@@ -20,6 +20,7 @@
  *   rt_scene_update.hip the scene updates' rt_scene_update_*: kernels and entry points in one unit
  *   rt_order_query.hip the record ordering's rt_ray_keys / rt_sort_records / rt_gather_records / rt_scatter_records: kernels and entry points in one unit
  *   rt_mesh_order.hip  the mesh ordering's rt_triangle_keys / rt_order_triangles: the key kernel and entry points that call rt_order_query.hip's
+ *   rt_material_query.hip the material queries' rt_material_hits / rt_probe_surfaces: kernels and entry points in one unit
  * The kernel units rt_hit_query.hip and rt_scatter_query.hip include this header for the band loop of their launchers.
  */
 #ifndef RT_API_INTERNAL_H

@@ -379,6 +379,58 @@ int rt_light_terms(const rt_scene *scene, const rt_hit *d_hits, const rt_ray *d_
 int rt_light_fold(const rt_scene *scene, const rt_hit *d_hits, size_t n, uint32_t light_count, const unsigned char *d_lit, const float *d_diffuse,
                   const float *d_specular, float *d_rgb, void *hip_stream);
 
+/* ---- material queries: approx, adjust_normal and the Phong terms on caller-supplied hits ------------------------------
+
+ * The material at a hit, which every render and query kernel evaluates between two casts and none of the blocks above returns:
+ * Material::approx(hit.at), ColorMaterial::adjust_normal(hit.at.normal) and get_diffuse / get_specular on a MaterialProbe
+ * (materials.rs:33-66, 85-103).  rt_material_hits writes them as a record per hit — albedo, shading-normal and object planes for a
+ * denoiser or a compositor; transparency, refraction_index and opaque_decay where a generative material makes them depend on uv —
+ * and rt_probe_surfaces evaluates the two Phong terms of such records for directions of the caller's own: an area-light sample, an
+ * environment direction, a light chosen per record.  (rt_light_terms gives the terms for the lights stored in the scene only, and
+ * already multiplied by the light's colour.)  The functions are the ones get_shade runs (csrc/rt_shade.h), with the same operands in
+ * the same order, none fused: probe output times light.color is rt_light_terms' diffuse and specular bit for bit.
+ * Every pointer is a device pointer unless said otherwise; every call is stream-ordered and asynchronous on hip_stream (NULL = default
+ * stream), is one kernel with one record per lane, allocates nothing, uses no workspace and may be captured into a HIP graph at once.
+ * Not covered: textures or material functions beyond the enumerated ones; a light colour or attenuation on the probe; rt_multi_* forms. */
+
+typedef struct rt_surface {      /* 18 words, 72 bytes, read and written as dwords */
+    float normal[3];             /* ColorMaterial.normal as approx returns it (tangent space) */
+    float diffuse_color[3];
+    float shiness;
+    float specular_color[3];
+    float smoothness, transparency, refraction_index, opaque_decay;
+    float shading_normal[3];     /* adjust_normal(hit.at.normal), main.rs:410 */
+    uint32_t valid;              /* 1: the record was a hit naming a material of the scene */
+} rt_surface;
+
+/* main.rs:408-410 per record: d_surfaces[i] = approx(hit.at) of the material d_hits[i].object_index names, and adjust_normal of the
+ * hit's normal.  The record rules are the hit queries': a hit whose kind is neither 0 nor 1, or whose object_index >= n_materials, is
+ * "no hit" and is written as 18 ZERO WORDS, so the output is defined for every record; a primitive index outside its array does not
+ * invalidate (it is not read); NaN and Inf pass through the arithmetic.  The scene's live material array is read: after
+ * rt_scene_update_materials the call reports the new material.
+ * Checked before any device work, in this order: n >= 2^32 is RT_ERR_UNSUPPORTED; a null scene RT_ERR_INVALID_ARGUMENT; n == 0 is RT_OK
+ * and launches nothing; a null pointer RT_ERR_INVALID_ARGUMENT. */
+int rt_material_hits(const rt_scene *scene, const rt_hit *d_hits, size_t n, rt_surface *d_surfaces, void *hip_stream);
+/* The same on HOST arrays: allocates, copies, runs, synchronises the device and copies back. */
+int rt_material_hits_host(const rt_scene *scene, const rt_hit *h_hits, size_t n, rt_surface *h_surfaces);
+
+/* materials.rs:46-66 per (probe p, record i), entry k = p * n + i (probe-major, as the light queries are light-major), with
+ *     probe = { at.normal: d_surfaces[i].shading_normal, view_direction: d_view[3i ..], light_direction: d_light_dirs[3k ..] }
+ *   d_diffuse[3k ..]     get_diffuse(probe):  diffuse_color * cosine where cosine = dot(light_direction, normal) > 0, else +0
+ *   d_specular[3k ..]    get_specular(probe): +0 where cosine <= 0, else specular_color * (pow(max(dot(reflected, view_direction), 0),
+ *                        1 / (smoothness + EPSILON)) * (that exponent + 8) / (8 pi))
+ * d_view holds what the reference puts into view_direction: get_shade passes -hit.ray.direction.  No light colour is applied and
+ * nothing is weighted by shiness: the caller multiplies.  Where valid == 0 both are +0.  Only words 3..5, 7..10 and 14..17 of a surface
+ * are used.  The call takes NO SCENE: the surface carries everything the probe needs, so a caller may edit it between the two calls —
+ * a diffuse_color from a texture of its own, a shading normal from a normal map.
+ * Checked before any device work, in this order: n >= 2^32, or n * n_probes >= 2^32, is RT_ERR_UNSUPPORTED; n == 0 or n_probes == 0 is
+ * RT_OK and launches nothing; a null pointer RT_ERR_INVALID_ARGUMENT. */
+int rt_probe_surfaces(const rt_surface *d_surfaces, size_t n, const float *d_view, const float *d_light_dirs, uint32_t n_probes, float *d_diffuse,
+                      float *d_specular, void *hip_stream);
+/* The same on HOST arrays. */
+int rt_probe_surfaces_host(const rt_surface *h_surfaces, size_t n, const float *h_view, const float *h_light_dirs, uint32_t n_probes,
+                           float *h_diffuse, float *h_specular);
+
 /* ---- refraction queries: get_refract bounce by bounce on caller-supplied hits ------------------------------
 
  * get_refract (main.rs:343-405) opened into the calls between its casts.  rt_refract_rays runs the whole walk through the glass in one

@@ -1,0 +1,377 @@
+"""Material queries on the device (include/rt_amd.h rt_material_hits / rt_probe_surfaces, rt.materials): the surfaces against
+orc_material_approx + orc_adjust_normal, the Phong terms against orc_diffuse_specular and, times the light's colour, against
+rt_light_terms and rt_shade_hits on the device; wave and block edges; hand-made records for adjust_normal's branches and approx's
+conversions; records a caller got wrong; an edited surface; a scene update; a scene walked breadth-first; graph capture;
+primary_surfaces; the host forms.  Everything expected is made on the CPU with the oracle alone (tests/test_material_query_abi.py pins
+those helpers), once per module.  Every comparison is of f32 bit patterns: any NaN equals any NaN, -0.0 differs from +0.0."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import homework_18_graphics_raytracer_amd as rt
+from homework_18_graphics_raytracer_amd import _capi
+from homework_18_graphics_raytracer_amd._capi import Material, SceneDesc
+import _oracle
+import _scenes
+import test_gpu_hit_queries as hq
+import test_gpu_light_queries as lq
+import test_material_query_abi as mq
+
+pytestmark = pytest.mark.gpu
+F32 = np.float32
+SENTINEL = 0x5A5A5A5A
+same_f32, same_surfaces, dev = mq.same_f32, mq.same_surfaces, hq.dev
+m = rt.materials
+
+
+def _torch():
+    import torch
+
+    torch.cuda.set_device(0)
+    return torch
+
+
+def host(t):
+    return t.cpu().numpy()
+
+
+def u32(t):
+    return host(t).view(np.uint32)
+
+
+def fdev(a):
+    return _torch().tensor(np.ascontiguousarray(a, dtype=F32), device="cuda")
+
+
+def lights_at(desc, l, positions):
+    """orc_light_directional at every position: (some, direction, color)"""
+    lib = _oracle.lib()
+    n = positions.shape[0]
+    some, direction, color = np.zeros(n, dtype=bool), np.zeros((n, 3), dtype=F32), np.zeros((n, 3), dtype=F32)
+    d, c, o, h = (C.c_float * 3)(), (C.c_float * 3)(), (C.c_float * 3)(), C.c_int(0)
+    for i in range(n):
+        if lib.orc_light_directional(C.byref(desc.lights[l]), mq.f3(positions[i]), d, c, o, C.byref(h)):
+            some[i], direction[i], color[i] = True, d[:], c[:]
+    return some, direction, color
+
+
+@pytest.fixture(scope="module")
+def ref():
+    world = rt.reference_world()
+    b = lq.make_batch(world, lq.reference_rays(world.desc()))
+    b.world = world
+    assert 2500 <= b.valid.sum() <= 3500, b.valid.sum()
+    b.surfaces = mq.expected_surfaces(b.desc, b.hits)
+    b.view = -b.rays[:, 3:6].view(F32)  # probe.view_direction as get_shade passes it: -hit.ray.direction
+    pos = b.hits[:, 3:6].view(F32)
+    b.lights = [lights_at(b.desc, l, pos) for l in range(b.desc.n_lights)]
+    b.light_dirs = np.stack([-direction for _, direction, _ in b.lights])  # (3, N, 3); zeros where the light gives None
+    return b
+
+
+def surfaces_of(scene, hits, pad=0):
+    """rt_material_hits into a buffer filled with a sentinel, `pad` records longer than the batch"""
+    torch = _torch()
+    n = hits.shape[0]
+    out = torch.full((n + pad, 18), SENTINEL, dtype=torch.int32, device="cuda")
+    got = m.material_hits(scene, dev(hits), out=out[:n])
+    assert got.data_ptr() == out.data_ptr()
+    torch.cuda.synchronize()
+    return u32(out)
+
+
+def assert_surfaces(got, want, what):
+    bad = np.flatnonzero(~same_surfaces(got, want))
+    assert bad.size == 0, f"{what}: {bad.size} of {want.shape[0]} differ, first rows {bad[:5]}: {got[bad[:1]]} want {want[bad[:1]]}"
+
+
+def probe(surfaces, view, dirs):
+    torch = _torch()
+    d, s = m.probe_surfaces(dev(surfaces), fdev(view), fdev(dirs))
+    torch.cuda.synchronize()
+    return host(d), host(s)
+
+
+def assert_terms(got, want, what):
+    for name, g, w in zip(("diffuse", "specular"), got, want):
+        bad = np.argwhere(~same_f32(g, w).all(axis=-1))
+        assert bad.size == 0, f"{what}: {name} differs in {bad.shape[0]} pairs, first (probe, record) {bad[:3].tolist()}: {g[tuple(bad[0])]} want {w[tuple(bad[0])]}"
+
+
+# ---- rt_material_hits ----
+
+
+def test_material_hits_against_the_oracle(ref):
+    """all 18 words of the 4 011 records; the batch holds every material function of the reference scene and both primitive kinds"""
+    desc = ref.desc
+    v = ref.hits[ref.valid]
+    assert {desc.materials[int(o)].diffuse_fn for o in v[:, 2]} == {0, 1, 2}  # constant and both stripes
+    assert {desc.materials[int(o)].normal_fn for o in v[:, 2]} == {0, 1}     # constant and the wave normal
+    assert set(v[:, 0]) == {0, 1}                                            # spheres and triangles
+    assert (ref.surfaces[~ref.valid] == 0).all() and (ref.surfaces[ref.valid, 17] == 1).all()
+    got = surfaces_of(rt.Scene(ref.world), ref.hits)
+    assert_surfaces(got, ref.surfaces, "the reference batch")
+
+
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 255, 256, 257])
+def test_wave_and_block_edges(ref, n):
+    """the record after the last one is not written, by either kernel"""
+    torch = _torch()
+    rows = np.arange(n) * (ref.n // n) + 3
+    scene = rt.Scene(ref.world)
+    got = surfaces_of(scene, ref.hits[rows], pad=1)
+    assert (got[n] == SENTINEL).all()
+    assert_surfaces(got[:n], ref.surfaces[rows], f"{n} records")
+    assert n < 63 or ref.valid[rows].any() and not ref.valid[rows].all()
+    # the probe through the C entry point, into buffers one pair longer than the call's
+    probes = 2
+    dirs = ref.light_dirs[:probes, rows]
+    dif = torch.full((probes * n + 1, 3), 99.0, dtype=torch.float32, device="cuda")
+    spe = torch.full((probes * n + 1, 3), 99.0, dtype=torch.float32, device="cuda")
+    s_t, v_t, d_t = dev(ref.surfaces[rows]), fdev(ref.view[rows]), fdev(dirs)
+    p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    assert _capi.amd_lib().rt_probe_surfaces(p(s_t), n, p(v_t), p(d_t), probes, p(dif), p(spe), None) == 0
+    torch.cuda.synchronize()
+    dif, spe = host(dif), host(spe)
+    assert (dif[probes * n] == 99.0).all() and (spe[probes * n] == 99.0).all()
+    want = mq.expected_probe(ref.surfaces[rows], ref.view[rows], dirs)
+    assert_terms((dif[:-1].reshape(probes, n, 3), spe[:-1].reshape(probes, n, 3)), want, f"{n} records, {probes} probes")
+
+
+def test_handmade_records(ref):
+    """adjust_normal's branches (identity, antiparallel with sincosf, general; zero, NaN, infinite and non-unit normals), a negative
+    stripe cell, a saturating f32 -> i32 conversion, and the records a caller got wrong: 18 zero words where the record is no hit —
+    kind 2, an object_index at or beyond n_materials, a miss — while a primitive index outside its array does not invalidate"""
+    hits, labels, invalid = mq.handmade_hits(ref.desc)
+    want = mq.expected_surfaces(ref.desc, hits)
+    got = surfaces_of(rt.Scene(ref.world), hits, pad=1)
+    assert (got[len(labels)] == SENTINEL).all()
+    bad = np.flatnonzero(~same_surfaces(got[:-1], want))
+    assert bad.size == 0, [(labels[i], got[i], want[i]) for i in bad[:3]]
+    assert (got[invalid] == 0).all()
+    valid = np.setdiff1d(np.arange(len(labels)), invalid)
+    assert (got[valid, 17] == 1).all() and not (got[:-1] == SENTINEL).any()
+    assert sum("outside its array" in labels[i] or "0xFFFFFFFF: valid" in labels[i] for i in valid) == 2
+
+
+# ---- rt_probe_surfaces ----
+
+
+@pytest.mark.parametrize("probes", [1, 3])
+def test_probe_against_the_oracle(ref, probes):
+    """P = 3: the scene's lights, -direction of orc_light_directional at the hit (a zero vector where the spot light gives None).
+    P = 1: by record, the zero vector and a direction (ny, -nx, 0) perpendicular to the normal, both with cosine exactly 0, a negative
+    cosine, a NaN direction, and the normal itself"""
+    if probes == 3:
+        dirs = ref.light_dirs
+        assert any((~some[ref.valid]).any() for some, _, _ in ref.lights)  # hits outside the spot light's cone
+    else:
+        normal = ref.surfaces[:, 14:17].view(F32)
+        dirs = np.zeros((1, ref.n, 3), dtype=F32)
+        k = np.arange(ref.n) % 5
+        dirs[0, k == 1] = -normal[k == 1]
+        dirs[0, k == 2] = np.nan
+        dirs[0, k == 3] = normal[k == 3]
+        perp = np.stack([normal[:, 1], -normal[:, 0], np.zeros(ref.n, dtype=F32)], axis=1)  # ny * nx - nx * ny: exactly 0 in f32
+        dirs[0, k == 4] = perp[k == 4]
+        assert (np.abs(perp[(k == 4) & ref.valid]).max(axis=1) > 0.1).sum() > 300  # ... with a direction that is not zero
+    want = mq.expected_probe(ref.surfaces, ref.view, dirs)
+    got = probe(ref.surfaces, ref.view, dirs)
+    assert_terms(got, want, f"{probes} probes")
+    assert (got[0][:, ~ref.valid].view(np.uint32) == 0).all() and (got[1][:, ~ref.valid].view(np.uint32) == 0).all()
+    assert (want[0] != 0).any() and (want[1] != 0).any()
+
+
+def test_highlight_waves(ref):
+    """materials of smoothness 1e-5 (main.rs:866): a Phong exponent near 1e5, which underflows outside a highlight a few degrees wide.
+    Wave 0: no lane lies inside one — get_specular's wave-level branch skips the binary64 powf; wave 1: exactly one lane does.  The
+    oracle always evaluates the power"""
+    desc = ref.desc
+    shiny = [k for k in range(desc.n_materials) if desc.materials[k].smoothness < 2e-5 and desc.materials[k].normal_fn == 0]
+    assert shiny
+    hits = np.stack([mq.hit_record(1, 0, shiny[0], (0, 0, 1)) for _ in range(128)])
+    surfaces = surfaces_of(rt.Scene(ref.world), hits)
+    assert_surfaces(surfaces, mq.expected_surfaces(desc, hits), "the flat shiny records")
+    theta = np.linspace(0.1, 1.2, 128)
+    inside = 64 + 17
+    theta[inside] = 0.02
+    dirs = np.stack([np.sin(theta), np.zeros(128), np.cos(theta)], axis=1).astype(F32)[None]
+    view = np.tile(np.array([0, 0, 1], dtype=F32), (128, 1))
+    want = mq.expected_probe(surfaces, view, dirs)
+    assert (want[1][0, :64] == 0).all() and (want[0][0] > 0).any()          # wave 0: no highlight, lit all the same
+    assert np.flatnonzero((want[1][0] != 0).any(axis=1)).tolist() == [inside]  # wave 1: one lane inside
+    assert_terms(probe(surfaces, view, dirs), want, "highlight waves")
+
+
+def test_cross_check_against_light_terms_and_shade_hits(ref):
+    """probe output times dl.color — one f32 multiply per channel, in numpy — is rt_light_terms' diffuse and specular where that says lit,
+    and summed by rt_light_fold's rule it is rt_shade_hits (and orc_get_shade)"""
+    torch = _torch()
+    scene = rt.Scene(ref.world)
+    hits_t, rays_t = dev(ref.hits), dev(ref.rays)
+    g = lq.run_pieces(scene, hits_t, rays_t)
+    surf_t = m.material_hits(scene, hits_t)
+    dif_t, spe_t = m.probe_surfaces(surf_t, fdev(ref.view), fdev(ref.light_dirs))
+    shade = rt.shade_hits(scene, hits_t, rays_t)
+    torch.cuda.synchronize()
+    dif, spe, shade = host(dif_t), host(spe_t), host(shade)
+    n = ref.n
+    shiness = u32(surf_t)[:, 6].view(F32)
+    total = np.zeros((n, 3), dtype=F32)
+    with np.errstate(all="ignore"):
+        for l in range(3):
+            lit = g.lit[l * n:(l + 1) * n] == 1
+            assert lit.sum() > 300, l
+            color = ref.lights[l][2]
+            d, s = dif[l] * color, spe[l] * color
+            assert same_f32(d[lit], g.diffuse[l * n:(l + 1) * n][lit]).all(), l
+            assert same_f32(s[lit], g.specular[l * n:(l + 1) * n][lit]).all(), l
+            total[lit] = ((total + d * (F32(1.0) - shiness)[:, None]) + s * shiness[:, None])[lit]
+    assert same_f32(total[ref.valid], shade[ref.valid]).all()
+    assert same_f32(total[ref.valid], ref.shade[ref.valid]).all()
+
+
+def test_an_edited_surface(ref):
+    """the probe takes no scene: with diffuse_color overwritten in the surface tensor the diffuse term follows and the specular bits stay"""
+    torch = _torch()
+    rows = np.flatnonzero(ref.valid)[::7][:257]
+    scene = rt.Scene(ref.world)
+    surf_t = m.material_hits(scene, dev(ref.hits[rows]))
+    view_t, dirs_t = fdev(ref.view[rows]), fdev(ref.light_dirs[:, rows])
+    before = [host(t) for t in m.probe_surfaces(surf_t, view_t, dirs_t)]
+    texture = np.random.default_rng(3).uniform(0.0, 1.0, (rows.size, 3)).astype(F32)
+    surf_t.view(torch.float32)[:, 3:6] = fdev(texture)
+    after = [host(t) for t in m.probe_surfaces(surf_t, view_t, dirs_t)]
+    edited = ref.surfaces[rows].copy()
+    edited[:, 3:6] = texture.view(np.uint32)
+    assert np.array_equal(u32(surf_t), edited)
+    want = mq.expected_probe(edited, ref.view[rows], ref.light_dirs[:, rows])
+    assert_terms(after, want, "edited")
+    assert np.array_equal(after[1].view(np.uint32), before[1].view(np.uint32))
+    assert not np.array_equal(after[0].view(np.uint32), before[0].view(np.uint32))
+
+
+# ---- the scene ----
+
+
+def test_after_a_material_update(ref):
+    """rt_material_hits reads the live material array: after Scene.update_materials of one material it gives a fresh scene's surfaces"""
+    desc = ref.desc
+    _, wave, _ = mq.reference_material_roles(desc)
+    mats = (Material * desc.n_materials)(*[desc.materials[k] for k in range(desc.n_materials)])
+    mats[wave].normal_frequency, mats[wave].tex_frequency, mats[wave].tex_color_a, mats[wave].shiness = 3.0, 7.0, (0.9, 0.1, 0.2), 0.25
+    changed = SceneDesc(desc.triangles, desc.n_triangles, desc.spheres, desc.n_spheres, mats, desc.n_materials, desc.lights, desc.n_lights)
+    scene = rt.Scene(ref.world)
+    before = surfaces_of(scene, ref.hits)
+    scene.update_materials(wave, [mats[wave]])
+    got = surfaces_of(scene, ref.hits)
+    fresh = surfaces_of(rt.Scene(changed), ref.hits)
+    want = mq.expected_surfaces(desc, ref.hits, materials=mats)
+    assert_surfaces(got, want, "after the update")
+    assert_surfaces(fresh, want, "a fresh scene")
+    on_wave = ref.valid & (ref.hits[:, 2] == wave)
+    assert on_wave.sum() > 50 and not same_surfaces(got, before)[on_wave].all() and same_surfaces(got, before)[~on_wave].all()
+
+
+def test_a_scene_walked_breadth_first():
+    """a scene above rt_scene_create's breadth-first switch (8 192 triangles): the kernels do not walk, KernelScene is passed as it is"""
+    torch = _torch()
+    world = _scenes.random_world(11, 8200, 3)
+    desc = world.desc()
+    assert desc.n_triangles >= 8192
+    with rt.options(RT_AMD_BFS_WALK_TRIANGLES=8192):  # read when the scene is created
+        scene = rt.Scene(world)
+    rays = np.concatenate([lq.camera_rays_cpu(_scenes.camera(11), 32, 24), hq.source_b(desc, 9, 500)])
+    hits_t = rt.cast_rays(scene, dev(rays))
+    surf_t = m.material_hits(scene, hits_t)
+    torch.cuda.synchronize()
+    hits = u32(hits_t)
+    assert mq.valid_rows(desc, hits).sum() > 300
+    want = mq.expected_surfaces(desc, hits)
+    assert_surfaces(u32(surf_t), want, "8 200 triangles")
+    view = -rays[:, 3:6].view(F32)
+    dirs = want[:, 14:17].view(F32)[None].copy()
+    assert_terms(probe(want, view, dirs), mq.expected_probe(want, view, dirs), "8 200 triangles")
+
+
+def test_both_calls_in_a_graph(ref):
+    """material_hits + probe_surfaces captured on one stream — a linear graph — and replayed once on other records: the eager result"""
+    torch = _torch()
+    scene = rt.Scene(ref.world)
+    n = 1500
+    first, second = np.arange(n), np.arange(n) + ref.n - n
+    hits_t, view_t, dirs_t = dev(ref.hits[first]), fdev(ref.view[first]), fdev(ref.light_dirs[:, first])
+    surf_t = torch.full((n, 18), SENTINEL, dtype=torch.int32, device="cuda")
+    dif_t = torch.full((3, n, 3), 99.0, dtype=torch.float32, device="cuda")
+    spe_t = torch.full((3, n, 3), 99.0, dtype=torch.float32, device="cuda")
+    stream = torch.cuda.Stream()
+    stream.wait_stream(torch.cuda.current_stream())
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.stream(stream):
+        with torch.cuda.graph(graph, stream=stream):  # captured at once: neither call allocates
+            m.material_hits(scene, hits_t, out=surf_t, stream=stream)
+            m.probe_surfaces(surf_t, view_t, dirs_t, out_diffuse=dif_t, out_specular=spe_t, stream=stream)
+    torch.cuda.synchronize()
+    assert (u32(surf_t) == SENTINEL).all()  # capturing ran nothing
+    hits_t.copy_(dev(ref.hits[second]))
+    view_t.copy_(fdev(ref.view[second]))
+    dirs_t.copy_(fdev(ref.light_dirs[:, second]))
+    torch.cuda.synchronize()
+    graph.replay()
+    torch.cuda.synchronize()
+    got = u32(surf_t), host(dif_t), host(spe_t)
+    eager_s = m.material_hits(scene, hits_t)
+    eager_d, eager_p = m.probe_surfaces(eager_s, view_t, dirs_t)
+    torch.cuda.synchronize()
+    assert np.array_equal(got[0], u32(eager_s))
+    assert np.array_equal(got[1].view(np.uint32), u32(eager_d)) and np.array_equal(got[2].view(np.uint32), u32(eager_p))
+    assert_surfaces(got[0], ref.surfaces[second], "replayed")
+
+
+# ---- the Python conveniences ----
+
+
+def test_primary_surfaces(ref):
+    """48x36: the planes are views of the three record tensors, which are what camera_rays, cast_rays and material_hits give"""
+    torch = _torch()
+    scene = rt.Scene(ref.world)
+    camera, frame = rt.reference_camera(), rt.Frame.full(48, 36, 5)
+    p = m.primary_surfaces(scene, camera, frame)
+    rays, hits, surfaces = p[:3]
+    want_hits = rt.cast_rays(scene, rt.camera_rays(camera, frame))
+    torch.cuda.synchronize()
+    assert np.array_equal(u32(rays), ref.rays[:48 * 36]) and np.array_equal(u32(hits), u32(want_hits))
+    assert_surfaces(u32(surfaces), mq.expected_surfaces(ref.desc, u32(hits)), "primary surfaces")
+    h, s = u32(hits).reshape(36, 48, 13), u32(surfaces).reshape(36, 48, 18)
+    for name, plane, words in (("depth", p.depth, h[..., 12]), ("position", p.position, h[..., 3:6]), ("geometric_normal", p.geometric_normal, h[..., 6:9]),
+                               ("shading_normal", p.shading_normal, s[..., 14:17]), ("albedo", p.albedo, s[..., 3:6]),
+                               ("object_index", p.object_index, h[..., 2]), ("valid", p.valid, s[..., 17])):
+        assert tuple(plane.shape) == words.shape, name
+        assert plane.dtype == (torch.int32 if name in ("object_index", "valid") else torch.float32), name
+        assert np.array_equal(u32(plane.contiguous()), words), name
+        base = hits if name in ("depth", "position", "geometric_normal", "object_index") else surfaces
+        assert plane.untyped_storage().data_ptr() == base.untyped_storage().data_ptr(), name  # a view: no copy
+    assert 0 < int(p.valid.sum()) < 48 * 36
+    p.albedo[0, 0, 0] = 0.5  # ... so writing a plane writes the record
+    assert float(surfaces.view(torch.float32)[0, 3]) == 0.5
+
+
+def test_host_forms(ref):
+    """both _host forms against the device forms on 257 records"""
+    rows = np.arange(257) * (ref.n // 257) + 1
+    scene = rt.Scene(ref.world)
+    hits = ref.hits[rows]
+    want = surfaces_of(scene, hits)
+    got = m.material_hits_numpy(scene, hits)
+    assert got.dtype == m.SURFACE_DTYPE and got.shape == (257,)
+    assert np.array_equal(got.view(np.uint32).reshape(-1, 18), want)
+    assert np.array_equal(m.material_hits_numpy(scene, hits.view(rt.HIT_DTYPE).reshape(-1)).view(np.uint32).reshape(-1, 18), want)
+    view, dirs = ref.view[rows], ref.light_dirs[:, rows]
+    dev_terms = probe(want, view, dirs)
+    for surfaces in (got, want):
+        host_terms = m.probe_surfaces_numpy(surfaces, view, dirs)
+        assert host_terms[0].shape == (3, 257, 3)
+        assert np.array_equal(host_terms[0].view(np.uint32), dev_terms[0].view(np.uint32))
+        assert np.array_equal(host_terms[1].view(np.uint32), dev_terms[1].view(np.uint32))
+    assert_terms(dev_terms, mq.expected_probe(want, view, dirs), "257 records")

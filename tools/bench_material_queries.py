@@ -1,0 +1,141 @@
+#!/usr/bin/env python3
+"""Timing of the material queries (include/rt_amd.h rt_material_hits / rt_probe_surfaces; Python rt.materials) beside the existing
+rt_light_terms of the same build, which evaluates the same Phong terms plus approx, adjust_normal and the occlusion rule.
+
+    python tools/bench_material_queries.py [--steps 7 --warmup 2 --records 1000000] [--out profiles/material_query_bench.jsonl]
+
+The measurement is a child process of its own under its own `timeout -k 10 <--step-timeout>`; if it fails or runs out of time the run
+ends there.  On the hits of --records random rays through the reference scene's bounding sphere it reports milliseconds — device events,
+medians of --steps calls, the three forms alternated call by call, with their spread (max - min) — of
+    material_hits    rt_material_hits
+    probe_surfaces   rt_probe_surfaces with one probe per light of the scene: -direction of the light at the hit
+    light_terms      rt_light_terms over the scene's lights on the same records (flags and shadow hits made once, outside the timing)
+and checks that probe output times the light's colour is rt_light_terms' where that says lit.  No figure is a gate.  Appends one JSON
+line with the commit to --out and prints it.
+"""
+import argparse
+import json
+import subprocess
+import sys
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--steps", type=int, default=7, help="timed calls per form")
+ap.add_argument("--warmup", type=int, default=2)
+ap.add_argument("--records", type=int, default=1_000_000)
+ap.add_argument("--child", action="store_true", help="measure in this process and print the JSON")
+ap.add_argument("--step-timeout", type=int, default=300)
+ap.add_argument("--out", default=str(ROOT / "profiles" / "material_query_bench.jsonl"))
+a = ap.parse_args()
+
+if not a.child:
+    result = {"tool": "bench_material_queries"}
+    try:
+        result["commit"] = subprocess.run(["git", "-C", str(ROOT), "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip() or None
+    except OSError:
+        result["commit"] = None
+    cmd = ["timeout", "-k", "10", str(a.step_timeout), sys.executable, __file__, "--child", "--steps", str(a.steps), "--warmup", str(a.warmup),
+           "--records", str(a.records)]
+    proc = subprocess.run(cmd, capture_output=True, text=True)
+    if proc.returncode != 0:
+        sys.stderr.write(proc.stdout + proc.stderr)
+        sys.exit(f"exit status {proc.returncode}; nothing more is started")
+    result.update(json.loads(proc.stdout.strip().splitlines()[-1]))
+    line = json.dumps(result)
+    Path(a.out).parent.mkdir(parents=True, exist_ok=True)
+    with open(a.out, "a") as f:
+        f.write(line + "\n")
+    print(line)
+    sys.exit(0)
+
+import numpy as np
+import torch
+
+import homework_18_graphics_raytracer_amd as rt
+
+torch.cuda.set_device(0)
+world = rt.reference_world()
+scene = rt.Scene(world)
+desc = world.desc()
+g = np.random.default_rng(7)
+pts = np.array([list(desc.triangles[i].vertices[k].position) for i in range(desc.n_triangles) for k in range(3)], dtype=np.float64)
+centre = (pts.min(axis=0) + pts.max(axis=0)) / 2
+radius = float(np.linalg.norm(pts - centre, axis=1).max())
+o = g.normal(size=(a.records, 3))
+o = centre + radius * 1.5 * o / np.linalg.norm(o, axis=1, keepdims=True)
+d = centre + radius * g.uniform(-0.6, 0.6, size=(a.records, 3)) - o
+d /= np.linalg.norm(d, axis=1, keepdims=True)
+rays = rt.make_rays(torch.tensor(o.astype(np.float32), device="cuda"), torch.tensor(d.astype(np.float32), device="cuda"), face=rt.BOTH)
+hits = rt.cast_rays(scene, rays)
+N, L = rays.shape[0], scene.n_lights
+
+# what rt_light_terms reads, made once: the flags, the shadow rays and what a cast of them wrote
+shadow_rays, asks, _ = rt.light_rays(scene, hits, rays)
+index, count = rt.select_records(asks)
+shadow_hits = torch.empty((L * N, 13), dtype=torch.int32, device="cuda")
+rt.cast_rays_indexed(scene, shadow_rays, index, count, shadow_hits)
+lit = torch.empty((L * N,), dtype=torch.uint8, device="cuda")
+terms_d = torch.empty((L * N, 3), dtype=torch.float32, device="cuda")
+terms_s = torch.empty((L * N, 3), dtype=torch.float32, device="cuda")
+
+# the probes: -direction of each light at the hit, and its colour there, from the shadow rays (origin = the hit, direction = -light.direction)
+# where the light asks; elsewhere a zero direction
+view = -rays[:, 3:6].view(torch.float32).contiguous()
+light_dirs = shadow_rays[:, 3:6].view(torch.float32).contiguous().view(L, N, 3)
+surfaces = torch.empty((N, 18), dtype=torch.int32, device="cuda")
+probe_d = torch.empty((L, N, 3), dtype=torch.float32, device="cuda")
+probe_s = torch.empty((L, N, 3), dtype=torch.float32, device="cuda")
+stream = torch.cuda.Stream()
+stream.wait_stream(torch.cuda.current_stream())
+
+calls = {
+    "material_hits": lambda: rt.materials.material_hits(scene, hits, out=surfaces, stream=stream),
+    "probe_surfaces": lambda: rt.materials.probe_surfaces(surfaces, view, light_dirs, out_diffuse=probe_d, out_specular=probe_s, stream=stream),
+    "light_terms": lambda: rt.light_terms(scene, hits, rays, asks, shadow_hits, out_lit=lit, out_diffuse=terms_d, out_specular=terms_s, stream=stream),
+}
+
+
+def one(fn):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1)
+
+
+ms = {k: [] for k in calls}
+with torch.cuda.stream(stream):
+    for k in range(a.warmup + a.steps):
+        t = {name: one(fn) for name, fn in calls.items()}
+        if k >= a.warmup:
+            for name in ms:
+                ms[name].append(t[name])
+torch.cuda.synchronize()
+
+# the check: probe output times the light's colour is rt_light_terms' where that says lit — compared where the colour is known without
+# restating the reference: a directional light carries its own unchanged (lights.rs:48-93); a spot or point light's is attenuated per hit
+identical = True
+checked = 0
+for l in range(L):
+    light = desc.lights[l]
+    if light.kind != 0:
+        continue
+    color = torch.tensor(list(light.color), dtype=torch.float32, device="cuda")
+    on = lit.view(L, N)[l] != 0
+    for probe, terms in ((probe_d, terms_d), (probe_s, terms_s)):
+        x, y = (probe[l] * color)[on], terms.view(L, N, 3)[l][on]
+        identical = identical and bool(((x.view(torch.int32) == y.view(torch.int32)) | (x.isnan() & y.isnan())).all())
+    checked += int(on.sum().item())
+
+res = {"device": torch.cuda.get_device_name(0), "triangles": desc.n_triangles, "records": N, "hits": int(rt.Hits(hits).hit.sum().item()),
+       "lights": L, "lit_pairs": int((lit != 0).sum().item()), "steps": a.steps, "warmup": a.warmup}
+for name, v in ms.items():
+    res[name] = {"ms_median": round(float(np.median(v)), 4), "ms_spread": round(max(v) - min(v), 4), "ms_min": round(min(v), 4)}
+res["probe_over_light_terms"] = round(res["probe_surfaces"]["ms_median"] / res["light_terms"]["ms_median"], 3)
+res["identical_where_lit"] = identical
+res["pairs_checked"] = checked
+print(json.dumps(res))
