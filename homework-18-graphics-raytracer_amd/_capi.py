@@ -179,6 +179,7 @@ AMD_SYMBOLS = [
     "rt_tree_gate", "rt_tree_split", "rt_tree_spawn", "rt_tree_gather", "rt_tree_fold",
     "rt_light_rays", "rt_light_terms", "rt_light_fold",
     "rt_material_hits", "rt_material_hits_host", "rt_probe_surfaces", "rt_probe_surfaces_host",
+    "rt_film_offsets", "rt_camera_rays_offset", "rt_camera_rays_offset_host", "rt_film_splat",
     "rt_refract_enter", "rt_refract_step",
     "rt_scene_update_vertices", "rt_scene_update_spheres", "rt_scene_update_lights", "rt_scene_update_materials",
     "rt_ray_keys", "rt_sort_temp_bytes", "rt_sort_records", "rt_gather_records", "rt_scatter_records",
@@ -190,6 +191,7 @@ HOST_SYMBOLS = [
     "rt_world_push_light", "rt_world_push_flat_triangle", "rt_world_push_square", "rt_world_load_obj",
     "rt_world_build_reference_scene", "rt_world_save_scene", "rt_world_load_scene", "rt_reference_camera", "rt_world_desc", "rt_frame_full", "rt_post_process", "rt_luma_row",
     "rt_encode_srgb8", "rt_accumulate", "rt_accumulator_resolve", "rt_write_png", "rt_host_last_error",
+    "rt_film_offsets_host", "rt_film_splat_host",
 ]
 
 _amd = None
@@ -234,6 +236,9 @@ def host_lib() -> C.CDLL:
         lib.rt_accumulate.restype = None
         lib.rt_accumulator_resolve.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         lib.rt_accumulator_resolve.restype = None
+        lib.rt_film_offsets_host.argtypes = [C.POINTER(Frame), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+        lib.rt_film_splat_host.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p,
+                                           C.c_void_p]
         lib.rt_write_png.argtypes = [C.c_char_p, C.c_void_p, C.c_uint32, C.c_uint32]
         lib.rt_host_last_error.restype = C.c_char_p
         _host = lib
@@ -342,6 +347,11 @@ def amd_lib() -> C.CDLL:
         lib.rt_material_hits_host.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         lib.rt_probe_surfaces.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.rt_probe_surfaces_host.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+        lib.rt_film_offsets.argtypes = [C.POINTER(Frame), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+        lib.rt_camera_rays_offset.argtypes = [C.POINTER(Camera), C.POINTER(Frame), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+        lib.rt_camera_rays_offset_host.argtypes = [C.POINTER(Camera), C.POINTER(Frame), C.c_void_p, C.c_uint32, C.c_void_p]
+        lib.rt_film_splat.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p,
+                                      C.c_void_p]
         lib.rt_refract_enter.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p]
         lib.rt_refract_step.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -18,6 +18,7 @@
 #include "../../../include/rt_host.h"
 #include "../rt_vec.h"
 #include "../rt_luma.h"
+#include "../rt_film.h"
 
 using rt::V3;
 
@@ -524,6 +525,60 @@ void rt_accumulator_resolve(const float *sum, const float *weight, size_t n_pixe
         rgb[3 * i + 1] = empty ? 0.0f : sum[3 * i + 1] / weight[i];
         rgb[3 * i + 2] = empty ? 0.0f : sum[3 * i + 2] / weight[i];
     }
+}
+
+/* ---- film queries: the CPU definition (include/rt_amd.h "film queries"; the arithmetic is rt_film.h's, shared with the device) ---- */
+
+int rt_film_offsets_host(const rt_frame *frame, uint32_t spp, uint32_t pattern, uint32_t seed, float *offsets) {
+    bool unsupported;
+    const char *bad = rt::film_offsets_limits(frame, spp, pattern, &unsupported);
+    if (bad) return fail(unsupported ? RT_ERR_UNSUPPORTED : RT_ERR_INVALID_ARGUMENT, std::string("rt_film_offsets_host: ") + bad);
+    if (!offsets) return fail(RT_ERR_INVALID_ARGUMENT, "rt_film_offsets_host: null offset pointer");
+    const uint32_t cols = frame->x1 - frame->x0, rows = (uint32_t)(rt::film_frame_pixels(frame) / cols), k = rt::film_strata(spp);
+    const size_t n_pixels = (size_t)rows * cols;
+    for (uint32_t s = 0; s < spp; ++s)
+        for (uint32_t row = 0; row < rows; ++row)
+            for (uint32_t col = 0; col < cols; ++col) {
+                const uint32_t pixel = (frame->y0 + row * frame->y_step) * frame->width + (frame->x0 + col);
+                float *o = offsets + 2u * ((size_t)s * n_pixels + (size_t)row * cols + col);
+                o[0] = rt::film_offset(pattern, k, pixel, seed, s, 0u);
+                o[1] = rt::film_offset(pattern, k, pixel, seed, s, 1u);
+            }
+    return RT_OK;
+}
+
+int rt_film_splat_host(uint32_t rows, uint32_t cols, const float *samples, const uint8_t *valid, const float *offsets, uint32_t spp,
+                       uint32_t filter, float radius, float *sum, float *weight) {
+    const char *bad = rt::film_splat_limits(rows, cols, spp, filter, radius);
+    if (bad) return fail(RT_ERR_INVALID_ARGUMENT, std::string("rt_film_splat_host: ") + bad);
+    if (rows == 0u || cols == 0u) return RT_OK;
+    if (!samples || !offsets || !sum || !weight) return fail(RT_ERR_INVALID_ARGUMENT, "rt_film_splat_host: null sample, offset, sum or weight pointer");
+    const size_t n = (size_t)rows * cols;
+    const int reach = rt::film_reach(radius);
+    for (uint32_t r = 0; r < rows; ++r)
+        for (uint32_t c = 0; c < cols; ++c) {
+            const size_t i = (size_t)r * cols + c;
+            rt::FilmAcc a = {sum[3 * i], sum[3 * i + 1], sum[3 * i + 2], weight[i]};
+            for (uint32_t s = 0; s < spp; ++s)
+                for (int dr = -reach; dr <= reach; ++dr) {
+                    const int64_t qr = (int64_t)r + dr;
+                    if (qr < 0 || qr >= (int64_t)rows) continue;
+                    for (int dc = -reach; dc <= reach; ++dc) {
+                        const int64_t qc = (int64_t)c + dc;
+                        if (qc < 0 || qc >= (int64_t)cols) continue;
+                        const size_t rec = (size_t)s * n + (size_t)qr * cols + (size_t)qc;
+                        if (valid && !valid[rec]) continue;
+                        float ddx, ddy;
+                        if (!rt::film_covers(dr, dc, offsets[2 * rec], offsets[2 * rec + 1], radius, &ddx, &ddy)) continue;
+                        rt::film_apply(a, filter, radius, ddx, ddy, samples[3 * rec], samples[3 * rec + 1], samples[3 * rec + 2]);
+                    }
+                }
+            sum[3 * i] = a.s0;
+            sum[3 * i + 1] = a.s1;
+            sum[3 * i + 2] = a.s2;
+            weight[i] = a.w;
+        }
+    return RT_OK;
 }
 
 void rt_encode_srgb8(const float *rgb, size_t n_values, uint8_t *out) {

@@ -21,6 +21,8 @@
  *   rt_order_query.hip the record ordering's rt_ray_keys / rt_sort_records / rt_gather_records / rt_scatter_records: kernels and entry points in one unit
  *   rt_mesh_order.hip  the mesh ordering's rt_triangle_keys / rt_order_triangles: the key kernel and entry points that call rt_order_query.hip's
  *   rt_material_query.hip the material queries' rt_material_hits / rt_probe_surfaces: kernels and entry points in one unit
+ * The film queries' kernels are rt_film_query.hip; their entry points are rt_api_query.hip's (rt_camera_rays_offset, beside rt_camera_rays) and
+ * rt_api_post.hip's (rt_film_offsets / rt_film_splat, beside the accumulator).
  * The kernel units rt_hit_query.hip and rt_scatter_query.hip include this header for the band loop of their launchers.
  */
 #ifndef RT_API_INTERNAL_H
@@ -270,6 +272,25 @@ hipError_t launch_level_close(const rt_hit *hits, const uint32_t *type, const fl
 hipError_t launch_level_fold(const uint32_t *type, const float *cosine, const rt_hit *next_hits, const float *factor, const float *shade_next,
                              const float *shade_missed, uint32_t n, float *value, hipStream_t stream);
 hipError_t launch_level_finish(const float *value, uint32_t n, float *accum, unsigned char *valid, hipStream_t stream);
+/* The film queries' kernels (rt_film_query.hip).  FilmTile: what the sample positions need of a frame; FilmSplat: one rt_film_splat call
+ * (rows * cols < 2^32 and 0 < radius <= 4, checked by the entry point).  tiled: the LDS form of the splat instead of the simple one (same bits). */
+struct FilmTile {
+    uint32_t cols, rows, x0, y0, y_step, width;
+};
+struct FilmSplat {
+    const float *samples;
+    const unsigned char *valid; /* may be null */
+    const float *offsets;
+    float *sum, *weight;
+    uint32_t rows, cols, spp, filter;
+    float radius;
+};
+hipError_t launch_film_offsets(const FilmTile &t, uint32_t spp, uint32_t pattern, uint32_t seed, float *offsets, hipStream_t stream);
+hipError_t launch_camera_rays_offset(const KernelFrame &fr, const float *offsets, uint32_t spp, rt_ray *rays, hipStream_t stream);
+/* max_groups: both forms take their pixels or tiles grid-stride beyond this many workgroups, 1 .. RT_FILM_MAX_GROUPS (2^16 x 256 threads
+ * stay far below the 2^32 threads a launch may have); a smaller cap changes no bit */
+#define RT_FILM_MAX_GROUPS (1u << 16)
+hipError_t launch_film_splat(const FilmSplat &p, bool tiled, uint32_t max_groups, hipStream_t stream);
 } /* namespace rt */
 
 /* rt_select_records (rt_api_query.hip) keeps its block totals per (device, stream); rt_post_release (rt_api_post.hip) frees those of a

@@ -1,8 +1,14 @@
 /*
  * rt_api_post.hip — what follows the render path on the device (main.rs:748-762, image.rs:55-66, photon.rs): post_process, the
- * sRGB / u8 encode, the accumulator, and the rt_math_eval diagnostics.  Kernels: rt_post.hip.
+ * sRGB / u8 encode, the accumulator, and the rt_math_eval diagnostics.  Kernels: rt_post.hip.  And the film queries' rt_film_offsets /
+ * rt_film_splat (include/rt_amd.h "film queries"): the accumulator behind a reconstruction filter.  Kernels: rt_film_query.hip.
  */
 #include "rt_api_internal.h"
+#include "rt_film.h"
+
+/* which form of the splat rt_film_splat launches unless RT_AMD_FILM_SPLAT_FORM says otherwise: 0 simple, 1 tiled — the tiled one, which
+ * the measurement at 1920 x 1080 chose (DESIGN.md 3.20 has the figures and how they were taken) */
+#define RT_FILM_SPLAT_FORM_DEFAULT 1
 
 namespace rt {
 void math_eval_host(int op, const float *x, const float *y, float *out, size_t n);
@@ -100,6 +106,32 @@ int rt_accumulate_device(const float *d_samples, const unsigned char *d_valid, u
 int rt_accumulator_resolve_device(const float *d_sum, const float *d_weight, size_t n_pixels, float *d_rgb, void *hip_stream) {
     if (!d_sum || !d_weight || !d_rgb) return fail(RT_ERR_INVALID_ARGUMENT, "rt_accumulator_resolve_device: null argument");
     return launched("rt_accumulator_resolve_device", rt::launch_accumulator_resolve(d_sum, d_weight, n_pixels, d_rgb, static_cast<hipStream_t>(hip_stream)));
+}
+
+/* ---- film queries (rt_film_query.hip; rt_camera_rays_offset is rt_api_query.hip's) ---- */
+
+int rt_film_offsets(const rt_frame *frame, uint32_t spp, uint32_t pattern, uint32_t seed, float *d_offsets, void *hip_stream) {
+    bool unsupported;
+    const char *bad = rt::film_offsets_limits(frame, spp, pattern, &unsupported);
+    if (bad) return fail(unsupported ? RT_ERR_UNSUPPORTED : RT_ERR_INVALID_ARGUMENT, std::string("rt_film_offsets: ") + bad);
+    const int rc = check_pointers("rt_film_offsets", d_offsets != nullptr, "offset");
+    if (rc != RT_OK) return rc;
+    const rt::FilmTile t = {frame->x1 - frame->x0, rt_frame_rows(frame), frame->x0, frame->y0, frame->y_step, frame->width};
+    return launched("rt_film_offsets", rt::launch_film_offsets(t, spp, pattern, seed, d_offsets, static_cast<hipStream_t>(hip_stream)));
+}
+
+int rt_film_splat(uint32_t rows, uint32_t cols, const float *d_samples, const unsigned char *d_valid, const float *d_offsets, uint32_t spp,
+                  uint32_t filter, float radius, float *d_sum, float *d_weight, void *hip_stream) {
+    const char *bad = rt::film_splat_limits(rows, cols, spp, filter, radius);
+    if (bad) return fail(RT_ERR_INVALID_ARGUMENT, std::string("rt_film_splat: ") + bad);
+    if (rows == 0u || cols == 0u) return RT_OK;
+    const int rc = check_pointers("rt_film_splat", d_samples && d_offsets && d_sum && d_weight, "sample, offset, sum or weight");
+    if (rc != RT_OK) return rc;
+    const rt::FilmSplat p = {d_samples, d_valid, d_offsets, d_sum, d_weight, rows, cols, spp, filter, radius};
+    const bool tiled = rt::option(rt::OPT_FILM_SPLAT_FORM, RT_FILM_SPLAT_FORM_DEFAULT) == 1;
+    const long long cap = rt::option(rt::OPT_DIAG_FILM_MAX_GROUPS, RT_FILM_MAX_GROUPS); /* test hook: fewer workgroups, so a small image is taken grid-stride */
+    const uint32_t max_groups = cap >= 1 && cap < (long long)RT_FILM_MAX_GROUPS ? (uint32_t)cap : RT_FILM_MAX_GROUPS;
+    return launched("rt_film_splat", rt::launch_film_splat(p, tiled, max_groups, static_cast<hipStream_t>(hip_stream)));
 }
 
 int rt_encode_srgb8_device(const float *d_rgb, size_t n_values, unsigned char *d_out, void *hip_stream) {

@@ -2,7 +2,8 @@
  * rt_api_query.hip — rt_cast_rays / rt_cast_rays_host / rt_camera_rays (include/rt_amd.h "ray queries"): validation, the
  * per-(scene, stream) workspace of a scene walked breadth-first, the launches of rt_query.hip; and rt_shade_hits / rt_reflect_rays /
  * rt_refract_rays with their _host forms ("hit queries"): validation and the launches of rt_hit_query.hip, no workspace; and
- * rt_scatter_hits / rt_scatter_factors with theirs ("scatter queries", rt_scatter_query.hip).  No CPU path: without a device every
+ * rt_scatter_hits / rt_scatter_factors with theirs ("scatter queries", rt_scatter_query.hip); and rt_camera_rays_offset with its _host
+ * form ("film queries", rt_film_query.hip).  No CPU path: without a device every
  * call fails with a status.
  */
 #include "rt_api_internal.h"
@@ -87,6 +88,40 @@ int rt_camera_rays(const rt_camera *camera, const rt_frame *frame, rt_ray *d_ray
     const int rc = make_kernel_frame(camera, &f, &kf); /* refuses a tile of 2^32 pixels or more */
     if (rc != RT_OK) return rc;
     return launched("rt_camera_rays", rt::launch_camera_rays(kf, d_rays, static_cast<hipStream_t>(hip_stream)));
+}
+
+/* Camera::shoot through a sub-pixel position (include/rt_amd.h "film queries"; kernel: rt_film_query.hip) */
+static int camera_rays_offset_args(const char *who, const rt_camera *camera, const rt_frame *frame, const void *offsets, uint32_t spp, const void *rays,
+                                   rt::KernelFrame *kf) {
+    if (!camera || !frame) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": null argument");
+    if (!frame_ok(frame)) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": bad frame (need 0 <= x0 < x1 <= width, 0 <= y0 < y1 <= height, y_step >= 1)");
+    if (spp < 1u) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": spp must be at least 1");
+    rt_frame f = *frame;
+    f.max_depth = 0; /* not used here */
+    int rc = make_kernel_frame(camera, &f, kf); /* refuses a tile of 2^32 pixels or more */
+    if (rc == RT_OK) rc = check_count(who, rt_frame_pixels(frame) * (uint64_t)spp, {32u, "rays", "make them in several calls"});
+    if (rc == RT_OK) rc = check_pointers(who, offsets && rays, "offset or ray");
+    return rc;
+}
+
+int rt_camera_rays_offset(const rt_camera *camera, const rt_frame *frame, const float *d_offsets, uint32_t spp, rt_ray *d_rays, void *hip_stream) {
+    rt::KernelFrame kf;
+    const int rc = camera_rays_offset_args("rt_camera_rays_offset", camera, frame, d_offsets, spp, d_rays, &kf);
+    if (rc != RT_OK) return rc;
+    return launched("rt_camera_rays_offset", rt::launch_camera_rays_offset(kf, d_offsets, spp, d_rays, static_cast<hipStream_t>(hip_stream)));
+}
+
+int rt_camera_rays_offset_host(const rt_camera *camera, const rt_frame *frame, const float *h_offsets, uint32_t spp, rt_ray *h_rays) {
+    rt::KernelFrame kf;
+    int rc = camera_rays_offset_args("rt_camera_rays_offset_host", camera, frame, h_offsets, spp, h_rays, &kf);
+    if (rc != RT_OK) return rc;
+    const size_t n = (size_t)rt_frame_pixels(frame) * spp;
+    HostRoundTrip t("rt_camera_rays_offset_host");
+    const float *d_offsets = t.in(h_offsets, n * 2u * sizeof(float));
+    rt_ray *d_rays = t.out(h_rays, n * sizeof(rt_ray));
+    if (!t.ok()) return t.failed();
+    rc = rt_camera_rays_offset(camera, frame, d_offsets, spp, d_rays, nullptr);
+    return rc != RT_OK ? rc : t.finish();
 }
 
 /* ---- hit queries (rt_hit_query.hip) ---- */

@@ -14,6 +14,7 @@
  *   rt::camera_rays_kernel     one work-item per pixel of a tile, in its compact row order
  */
 #include "rt_cast.h"
+#include "rt_primary_ray.h"
 
 namespace rt {
 
@@ -192,33 +193,12 @@ __global__ __launch_bounds__(RT_QUERY_BFS_WAVES * 64u, 2) void cast_rays_indexed
     if (ray_count != nullptr && lane == 0u && casts != 0u) atomicAdd(ray_count, (unsigned long long)casts);
 }
 
-/* Camera::shoot(clip(x, y)) (main.rs:83-99, 1093-1096) with the per-frame basis of make_kernel_frame: the operations of the
- * Whitted kernels' primary ray (rt_kernels.hip) */
-__device__ __forceinline__ Ray primary_ray(const KernelFrame &fr, uint32_t col, uint32_t row) {
-    const uint32_t x = fr.x0 + col, y = fr.y0 + row * fr.y_step;
-    const float clip_y = (fr.half_height - (float)y) / fr.height_f;
-    const float clip_x = ((float)x - fr.half_width) / fr.height_f;
-    const V3 cx = v3(fr.cam_x[0], fr.cam_x[1], fr.cam_x[2]);
-    const V3 cy = v3(fr.cam_y[0], fr.cam_y[1], fr.cam_y[2]);
-    const V3 ct = v3(fr.cam_toward[0], fr.cam_toward[1], fr.cam_toward[2]);
-    Ray r;
-    r.o = v3(fr.cam_origin[0], fr.cam_origin[1], fr.cam_origin[2]);
-    r.d = normalize(clip_x * cx + clip_y * cy + ct);
-    r.mode = FACE_FRONT;
-    r.excl = 0u;
-    return r;
-}
-
+/* Camera::shoot(clip(x, y)): primary_ray and the record it is written as are rt_primary_ray.h's, shared with rt_film_query.hip */
 __global__ __launch_bounds__(256) void camera_rays_kernel(const KernelFrame fr, rt_ray *__restrict__ rays) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= fr.cols * fr.rows) return;
     const uint32_t row = i / fr.cols, col = i - row * fr.cols;
-    const Ray r = primary_ray(fr, col, row);
-    const uint32_t w[11] = {__float_as_uint(r.o.x), __float_as_uint(r.o.y), __float_as_uint(r.o.z), __float_as_uint(r.d.x),
-                            __float_as_uint(r.d.y), __float_as_uint(r.d.z), FACE_FRONT, 0u, 0u, 0u, 0u};
-    uint32_t *const o = reinterpret_cast<uint32_t *>(rays + i);
-#pragma unroll
-    for (int k = 0; k < 11; ++k) o[k] = w[k];
+    store_primary_ray(primary_ray(fr, col, row), rays + i);
 }
 
 hipError_t launch_cast_rays(const KernelScene &sc, const rt_ray *rays, rt_hit *hits, uint32_t n_rays, bool wave_uniform, hipStream_t stream) {

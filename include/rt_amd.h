@@ -1006,6 +1006,79 @@ int rt_accumulate_device(const float *d_samples, const unsigned char *d_valid, u
                          float *d_weight, void *hip_stream);
 int rt_accumulator_resolve_device(const float *d_sum, const float *d_weight, size_t n_pixels, float *d_rgb, void *hip_stream);
 
+/* ---- film queries: sub-pixel camera rays and filtered accumulation ------------------------------
+
+ * The image side of the per-pixel loop: where in its pixel a sample is taken, the primary ray through that position, and what a sample
+ * adds to the pixels around it — PhotonAccumulator::accumulate_weight (photon.rs:30-33: sum = sum + photon * weight; weight_sum +=
+ * weight), which the reference defines and never calls, behind a reconstruction filter.  With rt_trace_rays or
+ * rt_trace_rays_distributed in between this is a supersampled, antialiased frame:
+ *     rt_film_offsets -> rt_camera_rays_offset -> rt_trace_rays -> rt_film_splat -> rt_accumulator_resolve_device
+ * All buffers are SAMPLE-MAJOR: sample s of compact pixel i is record s * n_pixels + i, the (n_epochs, n_pixels) layout of
+ * rt_accumulate_device and rt_trace_rays_distributed.  Every pointer is a device pointer; every call is stream-ordered and asynchronous
+ * on hip_stream (NULL = default stream), allocates nothing, visits the host for nothing, uses no workspace and may be captured into a HIP
+ * graph at once.  The splat is a GATHER in a fixed order — no atomics — so a result does not change from run to run, does not depend on
+ * the launch geometry, and is bit-identical to the host forms rt_film_offsets_host / rt_film_splat_host of librt_host.so
+ * (include/rt_host.h), which are the CPU definition.
+ * Not covered: halos between the bands of a frame that is spread over several ranks — the image of rt_film_splat is ONE compact
+ * rows x cols array, and samples beyond its edge do not exist; rt_multi_* forms. */
+
+#define RT_FILM_CENTER 0u     /* every offset (+0, +0): the pixel's integer coordinate, as rt_camera_rays */
+#define RT_FILM_UNIFORM 1u    /* any spp: offset = u - 0.5f */
+#define RT_FILM_STRATIFIED 2u /* spp = k * k, 1 <= k <= 8: sample s in cell (s % k, s / k), offset = ((float)cell + u) / (float)k - 0.5f */
+
+#define RT_FILM_BOX 0u
+#define RT_FILM_TENT 1u
+#define RT_FILM_MITCHELL 2u
+
+/* d_offsets[2 * (s * n_pixels + i) + axis] (axis 0: dx, 1: dy, in pixels) for the spp samples of every pixel of a frame or tile, in its
+ * compact row order.  u is a counter hash of the GLOBAL pixel index pixel = y * width + x (u32, not the compact index: the tiles of a
+ * sharded frame agree with each other and with the full frame), all in u32 arithmetic:
+ *     mix(v):  v ^= v >> 16;  v *= 0x7feb352d;  v ^= v >> 15;  v *= 0x846ca68b;  v ^= v >> 16
+ *     h = mix(mix(pixel + seed) ^ (2 * s + axis));   u = (float)(h >> 8) * 2^-24        (0 <= u < 1)
+ * so every offset lies in [-0.5, 0.5].  frame->max_depth is not used.
+ * Checked before any device work, in this order: a null frame, a bad frame, spp == 0, an unknown pattern, a stratified spp that is no
+ * k * k with 1 <= k <= 8: RT_ERR_INVALID_ARGUMENT; 2^32 samples or more: RT_ERR_UNSUPPORTED; a null d_offsets: RT_ERR_INVALID_ARGUMENT. */
+int rt_film_offsets(const rt_frame *frame, uint32_t spp, uint32_t pattern, uint32_t seed, float *d_offsets, void *hip_stream);
+
+/* Camera::shoot through (x + dx, y + dy): d_rays[s * n_pixels + i] for the offsets d_offsets[2 * (s * n_pixels + i) ..] (rt_film_offsets, or
+ * the caller's own), with
+ *     clip_y = (half_height - ((float)y + dy)) / height_f;     clip_x = (((float)x + dx) - half_width) / height_f
+ * and everything after that in rt_camera_rays' operations (one function serves both); records as rt_camera_rays writes them.  With all
+ * offsets +0 the output is rt_camera_rays' byte for byte, spp times.  Tiles and y_step as in rt_camera_rays; frame->max_depth is not used.
+ * Checked in this order: a null camera or frame, a bad frame, spp == 0: RT_ERR_INVALID_ARGUMENT; 2^32 rays or more: RT_ERR_UNSUPPORTED; a
+ * null pointer: RT_ERR_INVALID_ARGUMENT. */
+int rt_camera_rays_offset(const rt_camera *camera, const rt_frame *frame, const float *d_offsets, uint32_t spp, rt_ray *d_rays, void *hip_stream);
+/* The same on HOST arrays: allocates, copies, runs, synchronises the device and copies back. */
+int rt_camera_rays_offset_host(const rt_camera *camera, const rt_frame *frame, const float *h_offsets, uint32_t spp, rt_ray *h_rays);
+
+/* accumulate_weight with a reconstruction filter, over a compact image of rows x cols pixels (n_pixels = rows * cols):
+ *     d_samples  3 f32 per sample          d_valid   1 u8 per sample, NULL: every sample counts
+ *     d_offsets  2 f32 per sample          d_sum     3 f32 per pixel, d_weight 1 f32 per pixel: READ, UPDATED AND WRITTEN — what
+ *                                                    PhotonAccumulator holds and rt_accumulator_resolve_device resolves; start them at zero
+ * For output pixel (r, c), with reach = (int)ceilf(radius + 0.5f):
+ *     for s = 0 .. spp - 1:                          (outermost)
+ *       for dr = -reach .. reach:  for dc = -reach .. reach:          (ascending)
+ *         q = (r + dr, c + dc); skipped when outside the image or when d_valid[s * n_pixels + q] == 0
+ *         ddx = (float)dc + dx_q;   ddy = (float)dr + dy_q                   (q's offset of sample s)
+ *         contributes only if  -radius <= ddx < radius  and  -radius <= ddy < radius      (half-open)
+ *         w = f(ddx) * f(ddy);   sum_c = sum_c + photon_c * w  (c = 0, 1, 2; the product is rounded, then added);   weight = weight + w
+ * with the filter f(d), every operation a single f32 operation in the order written, none fused:
+ *     RT_FILM_BOX       1.0f
+ *     RT_FILM_TENT      1.0f - fabsf(d) / radius
+ *     RT_FILM_MITCHELL  (Mitchell-Netravali, B = C = 1/3)   x = 2.0f * fabsf(d) / radius
+ *                       x < 1:      ((7.0f * x - 12.0f) * x * x + 16.0f / 3.0f) / 6.0f
+ *                       otherwise:  (((-7.0f / 3.0f * x + 12.0f) * x - 20.0f) * x + 32.0f / 3.0f) / 6.0f
+ *                       (16.0f / 3.0f, -7.0f / 3.0f and 32.0f / 3.0f are f32 constants; -7.0f / 3.0f * x is (-7.0f / 3.0f) * x)
+ * Consequences: a box of radius 0.5 with offsets in [-0.5, 0.5) gives every sample to its own pixel with w == 1, and the call is
+ * rt_accumulate_device bit for bit; because s is outermost, one call with spp samples equals spp calls with one sample each (progressive
+ * accumulation); nothing depends on how the kernel is launched.  An offset outside [-0.5, 0.5] is legal, NaN included: the sample simply
+ * does not reach every pixel its filter covers (only the (2 reach + 1)^2 pixels around its own are looked at), a NaN offset reaches none.
+ * A NaN or Inf sample value passes through the arithmetic into the pixels it contributes to, and only those.
+ * Checked before any device work: an unknown filter, a radius outside 0 < radius <= 4, spp == 0, rows * cols >= 2^32, a null pointer
+ * (other than d_valid): all RT_ERR_INVALID_ARGUMENT.  rows == 0 or cols == 0 is RT_OK and launches nothing. */
+int rt_film_splat(uint32_t rows, uint32_t cols, const float *d_samples, const unsigned char *d_valid, const float *d_offsets, uint32_t spp,
+                  uint32_t filter, float radius, float *d_sum, float *d_weight, void *hip_stream);
+
 /* ---- diagnostics ------------------------------------------------------------ */
 
 /* Which kernel renders the Whitted pass (process-wide; same results bit for bit):
@@ -1022,7 +1095,7 @@ int rt_accumulator_resolve_device(const float *d_sum, const float *d_weight, siz
  * named like the environment variable that seeds it — RT_AMD_DIST_PIPELINE, RT_AMD_DIST_WS_MB, RT_AMD_RNG_LOOKAHEAD,
  * RT_AMD_DIST_BY_COST, RT_AMD_DIST_OWN_FIRST, RT_AMD_DIST_PREP_FIRST, RT_AMD_DIST_SPLIT, RT_AMD_DIAG_WS_REFUSE,
  * RT_AMD_MULTI_FORCE_STAGE, RT_AMD_BFS_WALK_TRIANGLES (read by rt_scene_create), RT_AMD_WF_SHARE, RT_AMD_DIAG_BFS_CAP,
- * RT_AMD_DIAG_DIST_BAND_RAYS, RT_AMD_QUERY_WAVE_UNIFORM, RT_AMD_DIAG_HIT_BAND_RECORDS (INTEGRATION.md says what each does); any other name is RT_ERR_INVALID_ARGUMENT.  The environment is read ONCE per process, at the first use;
+ * RT_AMD_DIAG_DIST_BAND_RAYS, RT_AMD_QUERY_WAVE_UNIFORM, RT_AMD_DIAG_HIT_BAND_RECORDS, RT_AMD_FILM_SPLAT_FORM, RT_AMD_DIAG_FILM_MAX_GROUPS (INTEGRATION.md says what each does); any other name is RT_ERR_INVALID_ARGUMENT.  The environment is read ONCE per process, at the first use;
  * after that only this call changes a switch: value = decimal integer, NULL or "" = unset (the library's own choice).  Render
  * calls read the switches without locks: set them between calls, not during one. */
 int rt_set_option(const char *name, const char *value);

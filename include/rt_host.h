@@ -94,6 +94,13 @@ void rt_encode_srgb8(const float *rgb, size_t n_values, uint8_t *out);
 void rt_accumulate(const float *samples, const uint8_t *valid, uint32_t n_epochs, size_t n_pixels, float *sum, float *weight);
 void rt_accumulator_resolve(const float *sum, const float *weight, size_t n_pixels, float *rgb);
 
+/* The film queries' CPU definition (include/rt_amd.h "film queries": patterns, the hash, the filters and the order are stated there):
+ * plain loops over host arrays, bit-identical to rt_film_offsets / rt_film_splat of librt_amd.so.  Same arguments without the stream,
+ * same checks; a failure returns a negative rt_status and sets rt_host_last_error(). */
+int rt_film_offsets_host(const rt_frame *frame, uint32_t spp, uint32_t pattern, uint32_t seed, float *offsets);
+int rt_film_splat_host(uint32_t rows, uint32_t cols, const float *samples, const uint8_t *valid, const float *offsets, uint32_t spp,
+                       uint32_t filter, float radius, float *sum, float *weight);
+
 /* RGB8 PNG, written to "<path>.tmp" then renamed over path. */
 int rt_write_png(const char *path, const uint8_t *rgb8, uint32_t width, uint32_t height);
 
