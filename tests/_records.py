@@ -1,0 +1,257 @@
+"""Shared test support: what is about the ABI records and the device, not about any one feature.  No fixtures, no marks, and it
+imports without a GPU (torch is imported inside functions).  Where the rest of the shared helpers live:
+    _records.py               record constants, bit comparisons (same_f32, same_rays, same_hits, same_bits), ray_records, oracle_hits,
+                              bounds, tensor helpers (torch_device, host, u32, dev), tile_order, the tessellated scenes, the CPU camera
+                              rays and the ray sources (random_rays, source_b, source_c)
+    _hit_support.py           cast checks and the hit queries' expected / got sides (Want, Got, oracle_queries, gpu_queries, assert_parity)
+    _light_support.py         the light queries' batches (Batch, make_batch, oracle_shade, run_pieces)
+    _scatter_support.py       the scatter queries' restated level (restate_level, classify_level, chosen_rays)
+    _material_support.py      the material queries' expected surfaces and probes
+    _order_support.py         record ordering: coherence keys and the sort's size constants
+    _mesh_order_support.py    mesh ordering: triangle keys, permutations and the tessellation sweep
+    _scene_update_support.py  the dome scenes and the refit structure of the scene updates
+    _trace_support.py         trace_rays variants and the wavefront parity check
+    _film_support.py          the film cases and the host splat
+    _reference_support.py     the reference image pins, the progressive loop and the RNG constant
+    _oracle.py, _scenes.py    the CPU oracle's bindings and the scene builders"""
+import ctypes as C
+import subprocess
+import sys
+from pathlib import Path
+
+import numpy as np
+
+import homework_18_graphics_raytracer_amd as rt
+import _oracle
+
+ROOT = Path(__file__).resolve().parent.parent
+
+
+# ---- the records' constants ----
+NONE = 0xFFFFFFFF
+THRESHOLD = np.float32(0.001)  # main.rs:467
+ESCAPED, INFINITE, TRAPPED = 0, 1, 2
+FLOAT_WORDS = [3, 4, 5, 6, 7, 8, 9, 10, 12]  # position, normal, uv, distance of an rt_hit record
+
+
+# ---- tensors ----
+
+
+def torch_device():
+    import torch
+
+    torch.cuda.set_device(0)
+    return torch
+
+
+def host(t):
+    return t.cpu().numpy()
+
+
+def u32(t):
+    return host(t).view(np.uint32)
+
+
+def dev(records):
+    torch = torch_device()
+    return torch.tensor(np.ascontiguousarray(records).view(np.int32), device="cuda")
+
+
+# ---- comparisons of bit patterns: any NaN equals any NaN, -0.0 differs from +0.0 ----
+
+
+def same_f32(a, b):
+    """element-wise: the same bit pattern, or both NaN"""
+    a, b = np.ascontiguousarray(a, dtype=np.float32), np.ascontiguousarray(b, dtype=np.float32)
+    return (a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))
+
+
+def same_rays(got, want):
+    """per rt_ray record: all 11 words equal, the six float words also equal when both are NaN"""
+    got, want = np.asarray(got).view(np.uint32).reshape(-1, 11), np.asarray(want).view(np.uint32).reshape(-1, 11)
+    eq = got == want
+    eq[:, :6] |= np.isnan(got[:, :6].view(np.float32)) & np.isnan(want[:, :6].view(np.float32))
+    return eq.all(axis=1)
+
+
+def same_hits(got: np.ndarray, want: np.ndarray) -> np.ndarray:
+    """per record: every word equal, a float word also equal when both are NaN"""
+    got = np.asarray(got).view(np.uint32).reshape(-1, 13)
+    want = want.reshape(-1, 13)
+    eq = got == want
+    gf, wf = got[:, FLOAT_WORDS].view(np.float32), want[:, FLOAT_WORDS].view(np.float32)
+    eq[:, FLOAT_WORDS] |= np.isnan(gf) & np.isnan(wf)
+    return eq.all(axis=1)
+
+
+def same_bits(got, want):
+    g, w = np.asarray(got, dtype=np.float32), np.asarray(want, dtype=np.float32)
+    return (g.view(np.uint32) == w.view(np.uint32)) | (np.isnan(g) & np.isnan(w))
+
+
+# ---- records by hand and by the oracle ----
+
+
+def ray_records(origins, directions, face=0, exclude=None):
+    """(N, 11) uint32 rt_ray records; exclude: None or (kind, index, face) arrays"""
+    o = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
+    r = np.zeros((o.shape[0], 11), dtype=np.uint32)
+    r[:, 0:3] = o.view(np.uint32)
+    r[:, 3:6] = np.asarray(directions, dtype=np.float32).reshape(-1, 3).view(np.uint32)
+    r[:, 6] = face
+    if exclude is not None:
+        kind, index, ex_face = (np.asarray(a) for a in exclude)
+        some = kind >= 0
+        r[:, 7] = some
+        r[:, 8] = np.where(some, kind, 0)
+        r[:, 9] = np.where(some, index, 0)
+        r[:, 10] = np.where(some, ex_face, 0)
+    return r
+
+
+def oracle_hits(desc, rays):
+    """orc_cast of every record: (N, 13) uint32 rt_hit records, RT_HIT_NONE and zeros for a miss"""
+    rays = np.ascontiguousarray(rays).view(np.uint32).reshape(-1, 11).copy()
+    n = rays.shape[0]
+    out = np.zeros((n, 13), dtype=np.uint32)
+    out[:, 0] = NONE
+    lib = _oracle.lib()
+    orays = (_oracle.OrcRay * n).from_buffer(rays)
+    h = _oracle.OrcHit()
+    for i in range(n):
+        if lib.orc_cast(C.byref(desc), C.byref(orays[i]), C.byref(h)):
+            out[i] = np.frombuffer(bytes(h), dtype=np.uint32)
+    return out
+
+
+def valid_rows(desc, hits):
+    """the records that are hits of a triangle or a sphere of an object the scene has"""
+    return (hits[:, 0] <= 1) & (hits[:, 2] < desc.n_materials)
+
+
+def bounds(desc):
+    pts = []
+    for i in range(desc.n_triangles):
+        for v in desc.triangles[i].vertices:
+            pts.append(tuple(v.position))
+    for i in range(desc.n_spheres):
+        s = desc.spheres[i]
+        pts += [tuple(np.asarray(s.center) + s.radius), tuple(np.asarray(s.center) - s.radius)]
+    p = np.asarray(pts, dtype=np.float64)
+    c = (p.min(0) + p.max(0)) / 2
+    return c, float(np.linalg.norm(p - c, axis=1).max())
+
+
+def tile_order(cols, rows):
+    """position k of the Whitted kernels' slot order (8-row bands, column-major inside a band: 8x8 tiles) -> row-order index"""
+    s = np.arange(cols * rows, dtype=np.int64)
+    band = s // (cols * 8)
+    r = s - band * cols * 8
+    band_rows = np.minimum(8, rows - band * 8)
+    col = r // band_rows
+    return (band * 8 + (r - col * band_rows)) * cols + col
+
+
+# ---- scenes ----
+
+
+def tessellated_world(tmp_path, level, spherize):
+    obj = tmp_path / f"d{level}{'s' if spherize else 'f'}.obj"
+    cmd = [sys.executable, str(ROOT / "tools" / "make_tessellated_obj.py"), rt.DEFAULT_OBJ, str(obj), "--levels", str(level)]
+    subprocess.run(cmd + (["--spherize"] if spherize else []), check=True, capture_output=True)
+    return rt.reference_world(str(obj))
+
+
+def tessellated_scene(tmp_path, level):
+    """the literal scene around a tessellated dodecahedron, as tests/test_gpu_scene_sizes.py builds it"""
+    obj = tmp_path / f"d{level}s.obj"
+    cmd = [sys.executable, str(ROOT / "tools" / "make_tessellated_obj.py"), rt.DEFAULT_OBJ, str(obj), "--levels", str(level), "--spherize"]
+    subprocess.run(cmd, check=True, capture_output=True)
+    path = tmp_path / "scene.rtscene"
+    rt.reference_world(str(obj)).save_scene(path, rt.reference_camera())
+    return rt.World.load_scene(path)
+
+
+# ---- ray sources ----
+
+
+def camera_rays_cpu(camera, width, height):
+    """Camera::shoot of every pixel, by the oracle: what rt_camera_rays writes (tests/test_gpu_ray_query.py)"""
+    lib = _oracle.lib()
+    out = np.zeros((width * height, 11), dtype=np.uint32)
+    clip, r = (C.c_float * 2)(), _oracle.OrcRay()
+    for y in range(height):
+        for x in range(width):
+            lib.orc_clip(width, height, x, y, clip)
+            lib.orc_shoot(C.byref(camera), clip, C.byref(r))
+            out[y * width + x] = np.frombuffer(bytes(r), dtype=np.uint32)
+    return out
+
+
+def random_rays(seed, n, desc, centre, radius):
+    """origins inside and outside the scene's bounding sphere, every face mode, triangle and sphere exclusions with every face,
+    out-of-range exclusion indices, rays with no exclusion"""
+    torch = torch_device()
+    g = np.random.default_rng(seed)
+    scale = np.where(g.random(n) < 0.5, g.uniform(0.0, 1.0, n), g.uniform(1.0, 4.0, n)) * radius
+    u = g.normal(size=(n, 3))
+    origins = centre + u / np.linalg.norm(u, axis=1, keepdims=True) * scale[:, None]
+    towards = centre + g.normal(0.0, radius * 0.5, (n, 3))
+    d = towards - origins
+    d *= g.choice([1.0, 0.3, 2.5], n)[:, None] / np.maximum(np.linalg.norm(d, axis=1, keepdims=True), 1e-12)  # not all unit length
+    face = g.integers(0, 3, n)
+    kind = g.choice([-1, rt.SPHERE, rt.TRIANGLE], n, p=[0.3, 0.3, 0.4])
+    nt, ns = int(desc.n_triangles), int(desc.n_spheres)
+    index = np.where(kind == rt.TRIANGLE, g.integers(0, max(nt, 1) + 3, n), g.integers(0, max(ns, 1) + 3, n))  # some out of range
+    index[g.random(n) < 0.02] = 0x7FFFFFF0
+    ex_face = g.integers(0, 3, n)
+    f32 = lambda a: torch.tensor(np.asarray(a, dtype=np.float32), device="cuda")
+    i64 = lambda a: torch.tensor(np.asarray(a, dtype=np.int64), device="cuda")
+    return rt.make_rays(f32(origins), f32(d), i64(face), i64(kind), i64(index), i64(ex_face))
+
+
+def source_b(desc, seed, n):
+    """random rays from within 2x the bounding radius: every face mode, triangle and sphere exclusions, some with no exclusion"""
+    g = np.random.default_rng(seed)
+    centre, radius = bounds(desc)
+    u = g.normal(size=(n, 3))
+    origins = centre + u / np.linalg.norm(u, axis=1, keepdims=True) * (g.uniform(0.0, 2.0, n) * radius)[:, None]
+    d = centre + g.normal(0.0, radius * 0.5, (n, 3)) - origins
+    d *= g.choice([1.0, 0.3, 2.5], n)[:, None] / np.maximum(np.linalg.norm(d, axis=1, keepdims=True), 1e-12)  # not all unit length
+    kind = g.choice([-1, rt.SPHERE, rt.TRIANGLE], n, p=[0.6, 0.2, 0.2])
+    index = np.where(kind == rt.TRIANGLE, g.integers(0, desc.n_triangles, n), g.integers(0, max(desc.n_spheres, 1), n))
+    return ray_records(origins, d, g.integers(0, 3, n), (kind, index, g.integers(0, 3, n)))
+
+
+def source_c(desc, seed, n_each):
+    """rays started INSIDE every transparent object — the clear sphere, the glass slabs — with face modes Both and Back, half of them
+    at grazing angles (nearly tangent to the sphere, nearly parallel to a slab's large faces): they hit the object from within, and
+    get_refract of such hits walks on through the rest of the scene.  Chosen on the CPU with the oracle so that the batch holds
+    every Refraction kind and Escaped walks that bounced (test_oracle_parity asserts it)."""
+    g = np.random.default_rng(seed)
+    out = []
+    glass = [o for o in range(desc.n_materials) if desc.materials[o].transparency > 0.0]
+    for i in range(desc.n_spheres):
+        s = desc.spheres[i]
+        if s.object_index not in glass:
+            continue
+        u = g.normal(size=(n_each, 3))
+        u /= np.linalg.norm(u, axis=1, keepdims=True)
+        origins = np.asarray(s.center) + u * (g.uniform(0.0, 0.95, n_each) * s.radius)[:, None]
+        d = g.normal(size=(n_each, 3))
+        graze = g.random(n_each) < 0.5
+        d[graze] -= u[graze] * (d[graze] * u[graze]).sum(axis=1, keepdims=True) * 0.97  # nearly tangent
+        out.append(ray_records(origins, d / np.linalg.norm(d, axis=1, keepdims=True), g.choice([1, 2], n_each)))
+    for o in glass:
+        tris = [i for i in range(desc.n_triangles) if desc.triangles[i].object_index == o]
+        if not tris:
+            continue
+        p = np.array([[tuple(v.position) for v in desc.triangles[i].vertices] for i in tris], dtype=np.float64).reshape(-1, 3)
+        lo, hi = p.min(0), p.max(0)
+        thin = int(np.argmin(hi - lo))
+        origins = g.uniform(lo + (hi - lo) * 0.02, hi - (hi - lo) * 0.02, (n_each, 3))
+        d = g.normal(size=(n_each, 3))
+        graze = g.random(n_each) < 0.5
+        d[graze, thin] *= 0.1  # nearly parallel to the large faces
+        out.append(ray_records(origins, d / np.linalg.norm(d, axis=1, keepdims=True), g.choice([1, 2], n_each)))
+    return np.concatenate(out)

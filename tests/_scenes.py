@@ -402,3 +402,18 @@ def big_tree_world():
     for k, n in enumerate(BIG_RUNS):
         s.run(f"tree{n}", "curved", patch(n, "curved", (5.0 * k - 2.5, 0.0, 0.0), s.rng, cell=0.03, width=64, radius=3.0, tilt=0.15), glass=(k == 1))
     return s.finish([((0.0, 2.0, 0.3), 0.4)], (0.3, 6.0, 5.5), (0.0, 0.0, 0.0))
+
+
+def dealing(count):
+    """(K, ck, R) of a clustered leaf of `count` triangles: of K = 1 .. 8 chunks of ck = ceil(count / K) triangles (no chunks of fewer
+    than 4 once there are two) the first whose pairs per full pass, R * count / K with R = floor(64 / ck), beat the best so far by 5 %"""
+    best, best_fill = None, 0.0
+    for k in range(1, 9):
+        ck = -(-count // k)
+        if ck < 4 and k > 1:
+            break
+        r = 64 // ck
+        fill = r * count / k
+        if fill > best_fill * 1.05:
+            best, best_fill = (k, ck, r), fill
+    return best

@@ -4,56 +4,18 @@ the sources of a pixel in the stated order, the three consequences of the defini
 of spp samples is spp splats of one, a sample on a pixel border lands in one pixel), NaN samples, and the argument checks.  Every
 comparison is of the uint32 views: no tolerance anywhere.  No GPU is needed."""
 import ctypes as C
-import functools
 
 import numpy as np
 import pytest
 
 import homework_18_graphics_raytracer_amd as rt
 from homework_18_graphics_raytracer_amd import _capi, film
+from _film_support import bits, case_data, F32, FILTERS, host_splat, IMAGES, offsets_restated, SPPS
 
-F32 = np.float32
-IMAGES = [(1, 1), (1, 70), (70, 1), (23, 37)]
-FILTERS = ["box", "tent", "mitchell"]
 RADII = [0.5, 1.0, 2.0]  # reach 1, 2, 3
-SPPS = [1, 4]
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 # ---- the sample positions ----
-
-def mix(v):
-    v = v.astype(np.uint64)
-    v ^= v >> np.uint64(16)
-    v = (v * np.uint64(0x7FEB352D)) & np.uint64(0xFFFFFFFF)
-    v ^= v >> np.uint64(15)
-    v = (v * np.uint64(0x846CA68B)) & np.uint64(0xFFFFFFFF)
-    v ^= v >> np.uint64(16)
-    return v
-
-
-def offsets_restated(frame, spp, pattern, seed):
-    """(spp, rows * cols, 2) float32 from the definition in include/rt_amd.h"""
-    ys = np.arange(frame.y0, frame.y1, frame.y_step, dtype=np.uint64)
-    xs = np.arange(frame.x0, frame.x1, dtype=np.uint64)
-    pixel = ((ys[:, None] * np.uint64(frame.width) + xs[None, :]) & np.uint64(0xFFFFFFFF)).reshape(-1)
-    out = np.zeros((spp, pixel.size, 2), dtype=F32)
-    if pattern == "center":
-        return out
-    k = int(round(spp ** 0.5))
-    for s in range(spp):
-        for axis in (0, 1):
-            h = mix(mix((pixel + np.uint64(seed)) & np.uint64(0xFFFFFFFF)) ^ np.uint64(2 * s + axis))
-            u = (h >> np.uint64(8)).astype(F32) * F32(2.0 ** -24)
-            if pattern == "uniform":
-                out[s, :, axis] = u - F32(0.5)
-            else:
-                cell = s % k if axis == 0 else s // k
-                out[s, :, axis] = (F32(cell) + u) / F32(k) - F32(0.5)
-    return out
 
 
 @pytest.mark.parametrize("seed", [0, 0x9E3779B9])
@@ -147,35 +109,6 @@ def splat_restated(rows, cols, samples, valid, offsets, name, radius, total, wei
                     weight = np.where(hit, weight + w, weight)
     assert total.dtype == F32 and weight.dtype == F32
     return total, weight
-
-
-@functools.lru_cache(maxsize=None)
-def case_data(rows, cols, spp):
-    """samples, flags (about a quarter cleared), offsets (most in [-0.5, 0.5), a few beyond, some exactly on a border) and a running
-    (sum, weight) to continue from; read-only"""
-    rng = np.random.default_rng(rows * 1000 + cols * 10 + spp)
-    n = rows * cols
-    samples = rng.random((spp, n, 3), dtype=F32) * F32(4.0)
-    valid = (rng.random((spp, n)) >= 0.25).astype(np.uint8)
-    offsets = rng.random((spp, n, 2), dtype=F32) - F32(0.5)
-    pick = rng.random((spp, n, 2))
-    offsets[pick < 0.03] = F32(-0.5)
-    offsets[(pick >= 0.03) & (pick < 0.06)] = F32(0.5)
-    offsets[(pick >= 0.06) & (pick < 0.09)] *= F32(3.0)  # beyond the pixel: legal
-    total = rng.random((rows, cols, 3), dtype=F32)
-    weight = rng.random((rows, cols), dtype=F32)
-    for a in (samples, valid, offsets, total, weight):
-        a.setflags(write=False)
-    return samples, valid, offsets, total, weight
-
-
-def host_splat(rows, cols, samples, valid, offsets, name, radius, total=None, weight=None):
-    f = film.Film(rows, cols, name, radius)
-    if total is not None:
-        f.sum[...] = total
-        f.weight[...] = weight
-    f.splat(samples, offsets, valid)
-    return f.sum, f.weight
 
 
 @pytest.mark.parametrize("name", FILTERS)

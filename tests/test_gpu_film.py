@@ -11,7 +11,8 @@ import pytest
 import homework_18_graphics_raytracer_amd as rt
 from homework_18_graphics_raytracer_amd import film
 import _oracle
-from test_film_host import F32, FILTERS, IMAGES, SPPS, bits, case_data, host_splat, offsets_restated
+from _film_support import bits, case_data, F32, FILTERS, host_splat, IMAGES, offsets_restated, SPPS
+from _records import torch_device
 
 pytestmark = pytest.mark.gpu
 
@@ -20,19 +21,12 @@ GPU_RADII = [0.5, 1.0, 2.0, 4.0]            # reach 1, 2, 3 and 5, the largest h
 FORMS = [0, 1]                              # the simple and the tiled kernel
 
 
-def _torch():
-    import torch
-
-    torch.cuda.set_device(0)
-    return torch
-
-
 def dev(a):
-    return None if a is None else _torch().from_numpy(np.array(a)).cuda()
+    return None if a is None else torch_device().from_numpy(np.array(a)).cuda()
 
 
 def device_splat(rows, cols, samples, valid, offsets, name, radius, total=None, weight=None, form=None, stream=None):
-    torch = _torch()
+    torch = torch_device()
     f = film.Film(rows, cols, name, radius, device="cuda")
     if total is not None:
         f.sum.copy_(dev(total))
@@ -48,7 +42,7 @@ def device_splat(rows, cols, samples, valid, offsets, name, radius, total=None, 
 @pytest.mark.parametrize("seed", [0, 0x9E3779B9])
 @pytest.mark.parametrize("pattern,spp", [(p, s) for p in ("center", "uniform", "stratified") for s in (1, 4, 9)] + [("uniform", 3)])
 def test_offsets_equal_the_host_definition(pattern, spp, seed):
-    torch = _torch()
+    torch = torch_device()
     for frame in (rt.Frame.full(37, 23, 0), rt.Frame(37, 23, 0, 5, 3, 30, 20, 2)):
         got = film.offsets(frame, spp, pattern, seed)
         torch.cuda.synchronize()
@@ -57,7 +51,7 @@ def test_offsets_equal_the_host_definition(pattern, spp, seed):
 
 
 def test_camera_rays_offset_with_centre_offsets_is_camera_rays_repeated():
-    torch = _torch()
+    torch = torch_device()
     cam = rt.reference_camera()
     for frame in (rt.Frame.full(37, 23, 0), rt.Frame(37, 23, 0, 5, 3, 30, 20, 2)):
         rays = film.camera_rays_offset(cam, frame, film.offsets(frame, 2, "center"))
@@ -70,7 +64,7 @@ def test_camera_rays_offset_with_centre_offsets_is_camera_rays_repeated():
 
 def test_camera_rays_offset_equals_shoot_through_the_restated_clip():
     """Camera::shoot of the oracle (what rt_camera_rays is pinned to) on the clip coordinates of the definition, computed here in float32"""
-    torch = _torch()
+    torch = torch_device()
     cam = rt.reference_camera()
     lib = _oracle.lib()
     for frame in (rt.Frame.full(37, 23, 0), rt.Frame(37, 23, 0, 5, 3, 30, 20, 2)):
@@ -98,7 +92,7 @@ def test_camera_rays_offset_equals_shoot_through_the_restated_clip():
 @pytest.mark.parametrize("name", FILTERS)
 @pytest.mark.parametrize("rows,cols", GPU_IMAGES)
 def test_splat_equals_the_host_definition(rows, cols, name):
-    torch = _torch()
+    torch = torch_device()
     stream = torch.cuda.Stream()
     for spp in SPPS:
         samples, valid, offsets, total, weight = case_data(rows, cols, spp)
@@ -145,7 +139,7 @@ def test_a_nan_sample_on_the_device(form):
 @pytest.mark.parametrize("form", FORMS)
 @pytest.mark.parametrize("rows,cols", [(23, 37), (16, 16)])
 def test_box_of_radius_half_is_rt_accumulate_device(rows, cols, form):
-    torch = _torch()
+    torch = torch_device()
     samples, valid, _, _, _ = case_data(rows, cols, 4)
     offsets = np.random.default_rng(5).random((4, rows * cols, 2), dtype=F32) - F32(0.5)  # [-0.5, 0.5)
     offsets[0, 0] = F32(-0.5)
@@ -165,7 +159,7 @@ def test_box_of_radius_half_is_rt_accumulate_device(rows, cols, form):
 @pytest.mark.parametrize("form", FORMS)
 @pytest.mark.parametrize("name,radius", [("box", 0.5), ("tent", 1.0), ("mitchell", 2.0)])
 def test_one_splat_of_four_samples_is_four_splats_of_one(name, radius, form):
-    torch = _torch()
+    torch = torch_device()
     rows, cols = 33, 17
     samples, valid, offsets, total, weight = case_data(rows, cols, 4)
     once = device_splat(rows, cols, samples, valid, offsets, name, radius, total, weight, form=form)
@@ -182,7 +176,7 @@ def test_one_splat_of_four_samples_is_four_splats_of_one(name, radius, form):
 
 @pytest.mark.parametrize("form", FORMS)
 def test_splat_in_a_captured_graph(form):
-    torch = _torch()
+    torch = torch_device()
     rows, cols = 33, 17
     samples, valid, offsets, total, weight = case_data(rows, cols, 4)
     eager = device_splat(rows, cols, samples, valid, offsets, "mitchell", 2.0, total, weight, form=form)
@@ -206,7 +200,7 @@ def test_splat_in_a_captured_graph(form):
 
 
 def test_render_supersampled():
-    torch = _torch()
+    torch = torch_device()
     world, cam = rt.reference_world(), rt.reference_camera()
     scene = rt.Scene(world)
     frame = rt.Frame.full(48, 36, 3)

@@ -15,8 +15,8 @@ from homework_18_graphics_raytracer_amd import _capi
 from homework_18_graphics_raytracer_amd._capi import Light, Material
 import _oracle
 import _scenes
-from test_gpu_trace_rays import assert_same, tile_order, trace, variant
-from test_gpu_wavefront import _check, _mismatches
+from _records import tile_order
+from _trace_support import _check, _mismatches, assert_same, trace, variant
 
 pytestmark = pytest.mark.gpu
 

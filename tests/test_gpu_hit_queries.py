@@ -4,226 +4,17 @@ rt_trace_rays at depth 0; ray_trace rebuilt from the queries one level deep agai
 both casts and a scene above the breadth-first switch; graph capture.  Every comparison is of f32 bit patterns: any NaN equals
 any NaN, -0.0 differs from +0.0."""
 import ctypes as C
-import subprocess
-import sys
 from pathlib import Path
 
 import numpy as np
 import pytest
 
 import homework_18_graphics_raytracer_amd as rt
-import _oracle
+from _hit_support import _pow_host, _some_hits, assert_parity, gpu_queries, oracle_queries
+from _records import dev, ESCAPED, INFINITE, NONE, same_f32, same_rays, source_b, source_c, tessellated_scene, THRESHOLD, torch_device, TRAPPED
 
 pytestmark = pytest.mark.gpu
 ROOT = Path(__file__).resolve().parent.parent
-NONE = 0xFFFFFFFF
-THRESHOLD = np.float32(0.001)  # main.rs:467
-ESCAPED, INFINITE, TRAPPED = 0, 1, 2
-
-
-def _torch():
-    import torch
-
-    torch.cuda.set_device(0)
-    return torch
-
-
-def same_f32(a, b):
-    """element-wise: the same bit pattern, or both NaN"""
-    a, b = np.ascontiguousarray(a, dtype=np.float32), np.ascontiguousarray(b, dtype=np.float32)
-    return (a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))
-
-
-def same_rays(got, want):
-    """per rt_ray record: all 11 words equal, the six float words also equal when both are NaN"""
-    got, want = np.asarray(got).view(np.uint32).reshape(-1, 11), np.asarray(want).view(np.uint32).reshape(-1, 11)
-    eq = got == want
-    eq[:, :6] |= np.isnan(got[:, :6].view(np.float32)) & np.isnan(want[:, :6].view(np.float32))
-    return eq.all(axis=1)
-
-
-def ray_records(origins, directions, face=0, exclude=None):
-    """(N, 11) uint32 rt_ray records; exclude: None or (kind, index, face) arrays"""
-    o = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
-    r = np.zeros((o.shape[0], 11), dtype=np.uint32)
-    r[:, 0:3] = o.view(np.uint32)
-    r[:, 3:6] = np.asarray(directions, dtype=np.float32).reshape(-1, 3).view(np.uint32)
-    r[:, 6] = face
-    if exclude is not None:
-        kind, index, ex_face = (np.asarray(a) for a in exclude)
-        some = kind >= 0
-        r[:, 7] = some
-        r[:, 8] = np.where(some, kind, 0)
-        r[:, 9] = np.where(some, index, 0)
-        r[:, 10] = np.where(some, ex_face, 0)
-    return r
-
-
-def bounds(desc):
-    pts = []
-    for i in range(desc.n_triangles):
-        for v in desc.triangles[i].vertices:
-            pts.append(tuple(v.position))
-    for i in range(desc.n_spheres):
-        s = desc.spheres[i]
-        pts += [tuple(np.asarray(s.center) + s.radius), tuple(np.asarray(s.center) - s.radius)]
-    p = np.asarray(pts, dtype=np.float64)
-    c = (p.min(0) + p.max(0)) / 2
-    return c, float(np.linalg.norm(p - c, axis=1).max())
-
-
-def source_b(desc, seed, n):
-    """random rays from within 2x the bounding radius: every face mode, triangle and sphere exclusions, some with no exclusion"""
-    g = np.random.default_rng(seed)
-    centre, radius = bounds(desc)
-    u = g.normal(size=(n, 3))
-    origins = centre + u / np.linalg.norm(u, axis=1, keepdims=True) * (g.uniform(0.0, 2.0, n) * radius)[:, None]
-    d = centre + g.normal(0.0, radius * 0.5, (n, 3)) - origins
-    d *= g.choice([1.0, 0.3, 2.5], n)[:, None] / np.maximum(np.linalg.norm(d, axis=1, keepdims=True), 1e-12)  # not all unit length
-    kind = g.choice([-1, rt.SPHERE, rt.TRIANGLE], n, p=[0.6, 0.2, 0.2])
-    index = np.where(kind == rt.TRIANGLE, g.integers(0, desc.n_triangles, n), g.integers(0, max(desc.n_spheres, 1), n))
-    return ray_records(origins, d, g.integers(0, 3, n), (kind, index, g.integers(0, 3, n)))
-
-
-def source_c(desc, seed, n_each):
-    """rays started INSIDE every transparent object — the clear sphere, the glass slabs — with face modes Both and Back, half of them
-    at grazing angles (nearly tangent to the sphere, nearly parallel to a slab's large faces): they hit the object from within, and
-    get_refract of such hits walks on through the rest of the scene.  Chosen on the CPU with the oracle so that the batch holds
-    every Refraction kind and Escaped walks that bounced (test_oracle_parity asserts it)."""
-    g = np.random.default_rng(seed)
-    out = []
-    glass = [o for o in range(desc.n_materials) if desc.materials[o].transparency > 0.0]
-    for i in range(desc.n_spheres):
-        s = desc.spheres[i]
-        if s.object_index not in glass:
-            continue
-        u = g.normal(size=(n_each, 3))
-        u /= np.linalg.norm(u, axis=1, keepdims=True)
-        origins = np.asarray(s.center) + u * (g.uniform(0.0, 0.95, n_each) * s.radius)[:, None]
-        d = g.normal(size=(n_each, 3))
-        graze = g.random(n_each) < 0.5
-        d[graze] -= u[graze] * (d[graze] * u[graze]).sum(axis=1, keepdims=True) * 0.97  # nearly tangent
-        out.append(ray_records(origins, d / np.linalg.norm(d, axis=1, keepdims=True), g.choice([1, 2], n_each)))
-    for o in glass:
-        tris = [i for i in range(desc.n_triangles) if desc.triangles[i].object_index == o]
-        if not tris:
-            continue
-        p = np.array([[tuple(v.position) for v in desc.triangles[i].vertices] for i in tris], dtype=np.float64).reshape(-1, 3)
-        lo, hi = p.min(0), p.max(0)
-        thin = int(np.argmin(hi - lo))
-        origins = g.uniform(lo + (hi - lo) * 0.02, hi - (hi - lo) * 0.02, (n_each, 3))
-        d = g.normal(size=(n_each, 3))
-        graze = g.random(n_each) < 0.5
-        d[graze, thin] *= 0.1  # nearly parallel to the large faces
-        out.append(ray_records(origins, d / np.linalg.norm(d, axis=1, keepdims=True), g.choice([1, 2], n_each)))
-    return np.concatenate(out)
-
-
-def oracle_hits(desc, rays):
-    """orc_cast of every record: (N, 13) uint32 rt_hit records, RT_HIT_NONE and zeros for a miss"""
-    rays = np.ascontiguousarray(rays).view(np.uint32).reshape(-1, 11).copy()
-    n = rays.shape[0]
-    out = np.zeros((n, 13), dtype=np.uint32)
-    out[:, 0] = NONE
-    lib = _oracle.lib()
-    orays = (_oracle.OrcRay * n).from_buffer(rays)
-    h = _oracle.OrcHit()
-    for i in range(n):
-        if lib.orc_cast(C.byref(desc), C.byref(orays[i]), C.byref(h)):
-            out[i] = np.frombuffer(bytes(h), dtype=np.uint32)
-    return out
-
-
-class Want:
-    pass
-
-
-def oracle_queries(desc, rays, hits, max_distance=100.0, rows=None):
-    """orc_get_shade / orc_reflect / orc_get_refract of the given rows (default: every row whose record is a hit of kind 0 or 1)"""
-    rays = np.ascontiguousarray(rays).view(np.uint32).reshape(-1, 11).copy()
-    hits = np.ascontiguousarray(hits).view(np.uint32).reshape(-1, 13).copy()
-    n = rays.shape[0]
-    lib = _oracle.lib()
-    orays = (_oracle.OrcRay * n).from_buffer(rays)
-    ohits = (_oracle.OrcHit * n).from_buffer(hits)
-    w = Want()
-    w.rows = np.flatnonzero(hits[:, 0] <= 1) if rows is None else np.asarray(rows)
-    w.shade = np.zeros((n, 3), dtype=np.float32)
-    w.shade_casts = np.zeros(n, dtype=np.uint64)
-    w.reflect = np.zeros((n, 11), dtype=np.uint32)
-    w.kind = np.full(n, NONE, dtype=np.uint32)
-    w.travel = np.zeros(n, dtype=np.float32)
-    w.escape = np.zeros((n, 11), dtype=np.uint32)
-    w.first_inside = np.zeros(n, dtype=np.float32)  # Escaped only: the distance of the first cast inside
-    rgb, casts, tr = (C.c_float * 3)(), C.c_uint64(0), C.c_float(0.0)
-    refl, esc, inside, h2 = _oracle.OrcRay(), _oracle.OrcRay(), _oracle.OrcRay(), _oracle.OrcHit()
-    for i in w.rows:
-        lib.orc_get_shade(C.byref(desc), C.byref(ohits[i]), C.byref(orays[i]), rgb, C.byref(casts))
-        w.shade[i] = rgb[:]
-        w.shade_casts[i] = casts.value
-        lib.orc_reflect(C.byref(ohits[i]), C.byref(orays[i]), C.byref(refl))
-        w.reflect[i] = np.frombuffer(bytes(refl), dtype=np.uint32)
-        w.kind[i] = lib.orc_get_refract(C.byref(desc), C.byref(ohits[i]), C.byref(orays[i]), max_distance, C.byref(tr), C.byref(esc))
-        if w.kind[i] == ESCAPED:
-            w.travel[i] = tr.value
-            w.escape[i] = np.frombuffer(bytes(esc), dtype=np.uint32)
-            k = desc.materials[ohits[i].object_index].refraction_index
-            v = (C.c_float * 3)()
-            assert lib.orc_refract_dir(ohits[i].normal, orays[i].direction, k, v)
-            v = np.array(v[:], dtype=np.float32)
-            inside.origin = ohits[i].position
-            inside.direction = (C.c_float * 3)(*(v / np.sqrt((v * v).sum(dtype=np.float32))))
-            inside.face_direction, inside.has_exclude, inside.exclude_face = 1, 1, 0
-            inside.exclude_kind, inside.exclude_index = ohits[i].kind, ohits[i].index
-            assert lib.orc_cast(C.byref(desc), C.byref(inside), C.byref(h2))
-            w.first_inside[i] = np.linalg.norm(np.array(h2.position[:], dtype=np.float64) - np.array(ohits[i].position[:], dtype=np.float64))
-    return w
-
-
-def dev(records):
-    torch = _torch()
-    return torch.tensor(np.ascontiguousarray(records).view(np.int32), device="cuda")
-
-
-class Got:
-    pass
-
-
-def gpu_queries(scene, rays_t, hits_t, max_distance=100.0):
-    torch = _torch()
-    g = Got()
-    sc, rc = torch.zeros(1, dtype=torch.int64, device="cuda"), torch.zeros(1, dtype=torch.int64, device="cuda")
-    shade = rt.shade_hits(scene, hits_t, rays_t, ray_count=sc)
-    reflect = rt.reflect_rays(rt.Hits(hits_t), rays_t)
-    refr = rt.refract_rays(scene, hits_t, rays_t, max_distance, ray_count=rc)
-    torch.cuda.synchronize()
-    g.shade = shade.cpu().numpy()
-    g.shade_casts, g.refract_casts = int(sc.item()), int(rc.item())
-    g.reflect = reflect.cpu().numpy().view(np.uint32)
-    g.kind = refr.kind.cpu().numpy().view(np.uint32)
-    g.travel = refr.travel.cpu().numpy()
-    g.escape = refr.rays.cpu().numpy().view(np.uint32)
-    g.escaped = refr.escaped.cpu().numpy()
-    return g
-
-
-def assert_parity(got, want, hits, what):
-    hit = hits[:, 0] <= 1
-    rows = want.rows
-    bad = np.flatnonzero(~same_f32(got.shade[rows], want.shade[rows]).all(axis=1))
-    assert bad.size == 0, f"{what}: shade differs in {bad.size} of {rows.size}, first row {rows[bad[:3]]}: {got.shade[rows[bad[:1]]]} want {want.shade[rows[bad[:1]]]}"
-    assert got.shade_casts == int(want.shade_casts.sum()), (what, got.shade_casts, int(want.shade_casts.sum()))
-    bad = np.flatnonzero(~same_rays(got.reflect[rows], want.reflect[rows]))
-    assert bad.size == 0, f"{what}: reflect differs in {bad.size}, first row {rows[bad[:3]]}: {got.reflect[rows[bad[:1]]]} want {want.reflect[rows[bad[:1]]]}"
-    bad = np.flatnonzero(got.kind[rows] != want.kind[rows])
-    assert bad.size == 0, f"{what}: refract kind differs in {bad.size}, first row {rows[bad[:3]]}: {got.kind[rows[bad[:3]]]} want {want.kind[rows[bad[:3]]]}"
-    esc = rows[want.kind[rows] == ESCAPED]
-    assert same_f32(got.travel[esc], want.travel[esc]).all(), what
-    assert same_rays(got.escape[esc], want.escape[esc]).all(), what
-    assert np.array_equal(got.escaped, got.kind == ESCAPED)
-    # everything that is not Escaped carries zeros; everything that is no hit is black, zero and RT_HIT_NONE
-    assert (got.travel[got.kind != ESCAPED].view(np.uint32) == 0).all() and (got.escape[got.kind != ESCAPED] == 0).all(), what
-    assert (got.shade[~hit].view(np.uint32) == 0).all() and (got.reflect[~hit] == 0).all() and (got.kind[~hit] == NONE).all(), what
 
 
 FRAME_A = (96, 72)
@@ -231,7 +22,7 @@ FRAME_A = (96, 72)
 
 def test_oracle_parity():
     """1. hits from rt_cast_rays of (a) a small frame's camera rays, (b) random rays, (c) rays started inside the glass objects"""
-    torch = _torch()
+    torch = torch_device()
     world = rt.reference_world()
     desc = world.desc()
     scene = rt.Scene(world)
@@ -284,7 +75,7 @@ def _contributions(desc, obj):
 
 def test_depth_zero_identity():
     """2. where the hit object's shade contribution reaches THRESHOLD: rt_shade_hits(rt_cast_rays(r), r) == rt_trace_rays(r, 0)"""
-    torch = _torch()
+    torch = torch_device()
     world = rt.reference_world()
     desc = world.desc()
     scene = rt.Scene(world)
@@ -309,21 +100,13 @@ def test_depth_zero_identity():
     assert (black.cpu().numpy().view(np.uint32) == 0).all()
 
 
-def _pow_host(x, y):
-    x, y = np.ascontiguousarray(x, dtype=np.float32), np.ascontiguousarray(y, dtype=np.float32)
-    out = np.empty_like(x)
-    p = lambda a: a.ctypes.data_as(C.c_void_p)
-    rt._capi.check(rt._capi.amd_lib().rt_math_eval_host(5, p(x), p(y), p(out), x.size))  # RT_MATH_POW
-    return out
-
-
 @pytest.mark.parametrize("depth", [5, 1])
 def test_one_level_peeled(depth):
     """3. ray_trace (main.rs:466-519) rebuilt from the queries, one level: cast; per hit object shade_hits where sc >= T, reflect_rays ->
     rt_trace_rays(depth - 1, rc) where rc >= T, refract_rays -> rt_trace_rays(escape, depth - 1, fc) * pow(opaque_decay, travel) where
     fc > T; (shade * sc + reflection * rc) + refraction * fc.  Equal to rt_trace_rays(rays, depth) bit for bit, and the cast counts add
     up: primary + shade + refract + children — the only check of rt_refract_rays' count."""
-    torch = _torch()
+    torch = torch_device()
     world = rt.reference_world()
     desc = world.desc()
     scene = rt.Scene(world)
@@ -382,21 +165,12 @@ def test_one_level_peeled(depth):
     assert casts == want_casts, (depth, casts, want_casts, parts)
 
 
-def _some_hits(scene, desc, seed, n):
-    """n (ray, hit) pairs that are hits, from random rays"""
-    rays = source_b(desc, seed, 4 * n + 64)
-    hits = rt.cast_rays(scene, dev(rays)).cpu().numpy().view(np.uint32)
-    rows = np.flatnonzero(hits[:, 0] <= 1)[:n]
-    assert rows.size == n
-    return rays[rows].copy(), hits[rows].copy()
-
-
 def test_foreign_records():
     """4. records a caller got wrong: RT_OK, "no hit" records give black / zero / RT_HIT_NONE and add nothing to the counts, records used
     as given (an index far outside its array, NaN position and normal, a zero direction) compute what the reference computes, and the
     neighbours of a bad record are what they are in the same batch without it.  Validation, not an attempt at a fault: nothing in the
     kernels is indexed with an unchecked field."""
-    torch = _torch()
+    torch = torch_device()
     world = rt.reference_world()
     desc = world.desc()
     scene = rt.Scene(world)
@@ -454,19 +228,9 @@ def test_foreign_records():
     assert (sentinel.cpu().numpy() == 99.0).all()
 
 
-def _tessellated(tmp_path, level):
-    """the literal scene around a tessellated dodecahedron, as tests/test_gpu_scene_sizes.py builds it"""
-    obj = tmp_path / f"d{level}s.obj"
-    cmd = [sys.executable, str(ROOT / "tools" / "make_tessellated_obj.py"), rt.DEFAULT_OBJ, str(obj), "--levels", str(level), "--spherize"]
-    subprocess.run(cmd, check=True, capture_output=True)
-    path = tmp_path / "scene.rtscene"
-    rt.reference_world(str(obj)).save_scene(path, rt.reference_camera())
-    return rt.World.load_scene(path)
-
-
 def test_both_casts_and_a_large_scene(tmp_path):
     """5. the wave-uniform cast gives the bits of the pair-wise one, and a scene above the breadth-first switch the oracle's"""
-    torch = _torch()
+    torch = torch_device()
     world = rt.reference_world()
     desc = world.desc()
     scene = rt.Scene(world)
@@ -480,7 +244,7 @@ def test_both_casts_and_a_large_scene(tmp_path):
         x, y = getattr(a, name), getattr(b, name)
         assert (same_f32(x, y) if x.dtype == np.float32 else x == y).all(), name
     assert a.shade_casts == b.shade_casts and a.refract_casts == b.refract_casts and a.shade_casts > 0 and a.refract_casts > 0
-    big, cam = _tessellated(tmp_path, 4)
+    big, cam = tessellated_scene(tmp_path, 4)
     big_desc = big.desc()
     assert big_desc.n_triangles == 36 * 4 ** 4 + 28  # above rt_scene_create's default switch (8 192 triangles)
     with rt.options(RT_AMD_BFS_WALK_TRIANGLES=8192):  # the library's default switch, set here so that no environment moves it
@@ -522,7 +286,7 @@ def test_bands_give_the_bits_of_one_launch(band):
 
 def test_graph_capture_without_a_prior_call():
     """6. rt_shade_hits uses no workspace: captured on a fresh scene with no call before it, replayed twice"""
-    torch = _torch()
+    torch = torch_device()
     world = rt.reference_world()
     desc = world.desc()
     scene = rt.Scene(world)  # nothing has run on this scene but the cast that made the hits

@@ -9,28 +9,12 @@ import pytest
 
 import homework_18_graphics_raytracer_amd as rt
 import _scenes
-import test_gpu_hit_queries as hq
-import test_gpu_scatter_queries as sq
+import _scatter_support as sq
+from _records import dev, host, same_f32, source_b, torch_device, u32
 
 pytestmark = pytest.mark.gpu
 NONE = 0xFFFFFFFF
 F32 = np.float32
-dev, same_f32 = hq.dev, hq.same_f32
-
-
-def _torch():
-    import torch
-
-    torch.cuda.set_device(0)
-    return torch
-
-
-def host(t):
-    return t.cpu().numpy()
-
-
-def u32(t):
-    return host(t).view(np.uint32)
 
 
 @pytest.fixture(scope="module")
@@ -64,7 +48,7 @@ def _check_select(flags_np, torch, what):
 
 @pytest.mark.parametrize("n", [1, 63, 64, 65, 257, 256 * 5 + 1, 256 * 16 + 1, 4096, 4097, (1 << 22) + 37])
 def test_selection_against_flatnonzero(n):
-    torch = _torch()
+    torch = torch_device()
     g = np.random.default_rng(n)
     _check_select(np.zeros(n, dtype=np.uint8), torch, "all zero")
     _check_select(np.ones(n, dtype=np.uint8), torch, "all one")
@@ -75,7 +59,7 @@ def test_selection_against_flatnonzero(n):
 
 
 def test_selection_on_an_unaligned_array_and_in_a_graph():
-    torch = _torch()
+    torch = torch_device()
     g = np.random.default_rng(5)
     n = 10_001
     base = (g.random(n + 3) < 0.4).astype(np.uint8)
@@ -158,19 +142,19 @@ def _check_indexed(scene, rays, what, torch):
 @pytest.mark.parametrize("wave_uniform", [None, 1])
 @pytest.mark.parametrize("which", ["reference", "random 3", "random 8"])
 def test_indexed_cast_against_cast_rays(ref, which, wave_uniform):
-    torch = _torch()
+    torch = torch_device()
     if which == "reference":
         _, _, scene, rays, _, _ = ref
     else:
         world = _scenes.random_world(int(which.split()[1]), 40, 4)
         scene = rt.Scene(world)
-        rays = hq.source_b(world.desc(), 21, 3000)
+        rays = source_b(world.desc(), 21, 3000)
     with rt.options(RT_AMD_QUERY_WAVE_UNIFORM=wave_uniform):
         _check_indexed(scene, rays, (which, wave_uniform), torch)
 
 
 def test_indexed_cast_on_a_scene_walked_breadth_first(ref):
-    torch = _torch()
+    torch = torch_device()
     world, _, _, rays, _, _ = ref
     with rt.options(RT_AMD_BFS_WALK_TRIANGLES=1):  # read when the scene is created
         scene = rt.Scene(world)
@@ -193,7 +177,7 @@ def _none_hits(n):
 def test_glue_and_fold_against_numpy_on_every_branch(ref):
     """one real level of the chosen batch (which takes every branch of main.rs:556-613), plus records a caller may hold: a NaN cosine,
     a cosine of -0.0, a dead record, a type that is none of the three"""
-    torch = _torch()
+    torch = torch_device()
     _, _, scene, rays, _, _ = ref
     n = rays.shape[0]
     rays_t = dev(rays)
@@ -337,7 +321,7 @@ def _same_run(a, b, what):
 
 
 def _compose(scene, rays, depth, epochs, what):
-    torch = _torch()
+    torch = torch_device()
     n = rays.shape[0]
     rays_t = dev(rays)
     rng_a, _ = sq.seeded(n)
@@ -368,7 +352,7 @@ def test_levels_equal_the_fused_call_on_a_scene_walked_breadth_first(ref, depth)
 
 def test_levels_fused_levels_on_one_rng(ref):
     """continuation: a levels call, a fused call and a levels call on one rt_rng equal three fused calls on its twin; accum goes on"""
-    torch = _torch()
+    torch = torch_device()
     _, _, scene, rays, _, _ = ref
     rays_t = dev(rays)
     n = rays.shape[0]
@@ -387,7 +371,7 @@ def test_levels_fused_levels_on_one_rng(ref):
 
 def test_levels_on_a_stream_of_their_own_and_outputs_one_at_a_time(ref):
     """every library call on a non-default stream gives the same bits; so do accum alone and samples alone"""
-    torch = _torch()
+    torch = torch_device()
     _, _, scene, rays, _, _ = ref
     rays_t = dev(rays)
     n = rays.shape[0]

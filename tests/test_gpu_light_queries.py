@@ -9,107 +9,17 @@ import numpy as np
 import pytest
 
 import homework_18_graphics_raytracer_amd as rt
-from homework_18_graphics_raytracer_amd._capi import Light, SceneDesc
 import _oracle
 import _scenes
-import test_gpu_hit_queries as hq
+from _light_support import dist32, make_batch, oracle_shade, reference_rays, run_pieces, with_lights
+from _records import camera_rays_cpu, dev, host, same_f32, same_rays, source_b, tessellated_scene, torch_device, valid_rows
 
 pytestmark = pytest.mark.gpu
 NONE = 0xFFFFFFFF
 BACK = 1
-same_f32, same_rays, dev = hq.same_f32, hq.same_rays, hq.dev
-
-
-def _torch():
-    import torch
-
-    torch.cuda.set_device(0)
-    return torch
-
-
-def host(t):
-    return t.cpu().numpy()
-
-
-def u32(t):
-    return host(t).view(np.uint32)
 
 
 # ---- the expected side: the oracle alone, on the CPU ----
-
-
-def camera_rays_cpu(camera, width, height):
-    """Camera::shoot of every pixel, by the oracle: what rt_camera_rays writes (tests/test_gpu_ray_query.py)"""
-    lib = _oracle.lib()
-    out = np.zeros((width * height, 11), dtype=np.uint32)
-    clip, r = (C.c_float * 2)(), _oracle.OrcRay()
-    for y in range(height):
-        for x in range(width):
-            lib.orc_clip(width, height, x, y, clip)
-            lib.orc_shoot(C.byref(camera), clip, C.byref(r))
-            out[y * width + x] = np.frombuffer(bytes(r), dtype=np.uint32)
-    return out
-
-
-def with_lights(desc, lights):
-    """the scene of `desc` holding the given lights only (indices into desc.lights), in that order"""
-    arr = (Light * max(len(lights), 1))(*[desc.lights[int(l)] for l in lights])
-    d = SceneDesc(desc.triangles, desc.n_triangles, desc.spheres, desc.n_spheres, desc.materials, desc.n_materials, arr, len(lights))
-    d._keepalive = (desc, arr)
-    return d
-
-
-def valid_rows(desc, hits):
-    return (hits[:, 0] <= 1) & (hits[:, 2] < desc.n_materials)
-
-
-def oracle_shade(desc, rays, hits, rows=None):
-    """orc_get_shade of every valid record: (N, 3) f32 values and (N,) cast counts; zeros for the others"""
-    rays = np.ascontiguousarray(rays).view(np.uint32).reshape(-1, 11).copy()
-    hits = np.ascontiguousarray(hits).view(np.uint32).reshape(-1, 13).copy()
-    n = rays.shape[0]
-    lib = _oracle.lib()
-    orays, ohits = (_oracle.OrcRay * n).from_buffer(rays), (_oracle.OrcHit * n).from_buffer(hits)
-    shade, casts = np.zeros((n, 3), dtype=np.float32), np.zeros(n, dtype=np.int64)
-    rgb, c = (C.c_float * 3)(), C.c_uint64(0)
-    for i in np.flatnonzero(valid_rows(desc, hits)) if rows is None else rows:
-        lib.orc_get_shade(C.byref(desc), C.byref(ohits[i]), C.byref(orays[i]), rgb, C.byref(c))
-        shade[i] = rgb[:]
-        casts[i] = c.value
-    return shade, casts
-
-
-def dist32(a, b):
-    """cgmath's distance in f32 as the reference evaluates it: (b - a).magnitude(), the dot product summed left to right"""
-    d = np.asarray(b, dtype=np.float32) - np.asarray(a, dtype=np.float32)
-    with np.errstate(all="ignore"):
-        return np.sqrt((d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2])
-
-
-class Batch:
-    pass
-
-
-def make_batch(world_or_desc, rays, per_light=False):
-    """hits by orc_cast, get_shade by orc_get_shade on the whole scene and — per_light — on the scene holding each light alone"""
-    b = Batch()
-    b.desc = world_or_desc.desc() if isinstance(world_or_desc, rt.World) else world_or_desc
-    b.rays = np.ascontiguousarray(rays, dtype=np.uint32)
-    b.hits = hq.oracle_hits(b.desc, b.rays)
-    b.n = b.rays.shape[0]
-    b.valid = valid_rows(b.desc, b.hits)
-    b.shade, b.casts = oracle_shade(b.desc, b.rays, b.hits)
-    if per_light:
-        b.alone = [oracle_shade(with_lights(b.desc, [l]), b.rays, b.hits) for l in range(b.desc.n_lights)]
-    return b
-
-
-def reference_rays(desc):
-    """4 011 records: 48x36 camera rays, random rays drawn as source_b of tests/test_gpu_hit_queries.py draws them, rays started inside
-    the glass; about 3 000 of them hit"""
-    rays = np.concatenate([camera_rays_cpu(rt.reference_camera(), 48, 36), hq.source_b(desc, 3, 1272), hq.source_c(desc, 3, 337)])
-    assert rays.shape[0] == 4011
-    return rays
 
 
 @pytest.fixture(scope="module")
@@ -129,7 +39,7 @@ def ref():
 
 
 def fused(scene, hits_t, rays_t):
-    torch = _torch()
+    torch = torch_device()
     cnt = torch.zeros(1, dtype=torch.int64, device="cuda")
     out = rt.shade_hits(scene, hits_t, rays_t, ray_count=cnt)
     torch.cuda.synchronize()
@@ -138,7 +48,7 @@ def fused(scene, hits_t, rays_t):
 
 def by_light(scene, hits_t, rays_t, lights_per_pass=None, stream=None):
     """the loop, with every synchronising torch call inside it an error: no host visit hides there"""
-    torch = _torch()
+    torch = torch_device()
     n = hits_t.shape[0]
     out = torch.full((n, 3), 7.0, dtype=torch.float32, device="cuda")
     cnt = torch.zeros(1, dtype=torch.int64, device="cuda")
@@ -171,7 +81,7 @@ def assert_identity(scene, b, rows, what, passes=(None, 1)):
 def test_the_loop_is_shade_hits(ref, size):
     """1. shade_hits_by_light == rt.shade_hits == orc_get_shade, values and cast count, with all lights in one pass and with one light
     per pass; the smaller batches are taken with a stride, so that each holds camera, random and inside-the-glass records"""
-    _torch()
+    torch_device()
     scene = rt.Scene(ref.world)
     rows = np.arange(size) * (ref.n // size)
     if size == 1:
@@ -195,40 +105,11 @@ def light_of(desc, l, positions):
     return some, direction, has_origin, origin
 
 
-def run_pieces(scene, hits_t, rays_t, first=0, count=None, asks_override=None):
-    """light_rays -> select_records -> cast_rays_indexed -> light_terms, every output filled with a sentinel first"""
-    torch = _torch()
-    n = hits_t.shape[0]
-    lights = (scene.n_lights - first) if count is None else count
-    m = lights * n
-    g = Batch()
-    sr = torch.full((m, 11), 0x5A5A5A5A, dtype=torch.int32, device="cuda")
-    asks = torch.full((m,), 0x5A, dtype=torch.uint8, device="cuda")
-    dist = torch.full((m,), 99.0, dtype=torch.float32, device="cuda")
-    rt.light_rays(scene, hits_t, rays_t, first, count, out_rays=sr, out_asks=asks, out_distance=dist)
-    g.shadow_rays, g.asks, g.distance = u32(sr), host(asks).copy(), host(dist)
-    if asks_override is not None:
-        asks.copy_(torch.tensor(asks_override, device="cuda"))
-    sh = torch.full((m, 13), 0x5A5A5A5A, dtype=torch.int32, device="cuda")  # kind 0x5a5a5a5a: neither 0 nor 1
-    cnt = torch.zeros(1, dtype=torch.int64, device="cuda")
-    index, count_t = rt.select_records(asks)
-    rt.cast_rays_indexed(scene, sr, index, count_t, sh, ray_count=cnt)
-    lit = torch.full((m,), 0x5A, dtype=torch.uint8, device="cuda")
-    dif = torch.full((m, 3), 99.0, dtype=torch.float32, device="cuda")
-    spe = torch.full((m, 3), 99.0, dtype=torch.float32, device="cuda")
-    rt.light_terms(scene, hits_t, rays_t, asks, sh, first, count, out_lit=lit, out_diffuse=dif, out_specular=spe)
-    torch.cuda.synchronize()
-    g.shadow_hits, g.casts = u32(sh), int(host(cnt)[0])
-    g.lit, g.diffuse, g.specular = host(lit), host(dif), host(spe)
-    g.t = (asks, lit, dif, spe)
-    return g
-
-
 def test_the_pieces_against_the_oracle(ref):
     """2. per light: the flags are the cast counts of orc_get_shade on the scene holding that light alone; the shadow rays are made of
     the hit and orc_light_directional; d_lit is the reference's occlusion rule evaluated with orc_cast of that ray; the two terms,
     weighted in numpy f32, are that one-light scene's orc_get_shade"""
-    _torch()
+    torch_device()
     desc, n = ref.desc, ref.n
     scene = rt.Scene(ref.world)
     assert desc.n_lights == 3 and sorted(desc.lights[l].kind for l in range(3)) == [0, 1, 2]  # one light of each kind
@@ -284,7 +165,7 @@ def test_the_pieces_against_the_oracle(ref):
 
 
 def fold(scene, hits_t, g_t, n, rgb=None):
-    torch = _torch()
+    torch = torch_device()
     asks, lit, dif, spe = g_t
     out = torch.zeros((n, 3), dtype=torch.float32, device="cuda") if rgb is None else rgb
     rt.light_fold(scene, hits_t, lit, dif, spe, out)
@@ -294,7 +175,7 @@ def fold(scene, hits_t, g_t, n, rgb=None):
 
 def test_a_subset_of_lights(ref):
     """3. a caller's light linking: with one light's flags zeroed the fold is orc_get_shade on the scene without that light"""
-    _torch()
+    torch_device()
     n = ref.n
     scene = rt.Scene(ref.world)
     hits_t, rays_t = dev(ref.hits), dev(ref.rays)
@@ -311,7 +192,7 @@ def test_a_subset_of_lights(ref):
 def test_foreign_records(ref):
     """4. records a caller got wrong, outputs filled with a sentinel first.  Validation, not an attempt at a fault: nothing in the
     kernels is indexed with an unchecked field"""
-    torch = _torch()
+    torch = torch_device()
     desc = ref.desc
     scene = rt.Scene(ref.world)
     rows = np.flatnonzero(ref.valid & (ref.casts > 0))[:: 29][:65]  # one full wave plus one lane
@@ -409,14 +290,14 @@ def test_foreign_records(ref):
 def test_other_scenes():
     """5. behind_spot_world (a spot light whose acos is NaN for some pixels: the light asks, with a NaN colour) and a random world with
     five lights, so that lights_per_pass = 2 ends on a short pass"""
-    _torch()
+    torch_device()
     world, cam = _scenes.behind_spot_world()
     b = make_batch(world, camera_rays_cpu(cam, 48, 36))
     assert np.isnan(b.shade).any() and b.valid.sum() > 1000  # the case is there
     assert_identity(rt.Scene(world), b, np.arange(b.n), "behind_spot_world")
     world = _scenes.random_world(7, 40, 3, n_lights=5)
     desc = world.desc()
-    b = make_batch(world, np.concatenate([camera_rays_cpu(_scenes.camera(7), 32, 24), hq.source_b(desc, 8, 500)]))
+    b = make_batch(world, np.concatenate([camera_rays_cpu(_scenes.camera(7), 32, 24), source_b(desc, 8, 500)]))
     assert desc.n_lights == 5 and b.valid.sum() > 500 and b.casts.max() >= 3
     assert_identity(rt.Scene(world), b, np.arange(b.n), "random_world, 5 lights", passes=(None, 1, 2))
 
@@ -424,13 +305,13 @@ def test_other_scenes():
 def test_a_scene_walked_breadth_first(tmp_path):
     """6. the 9 244-triangle scene of tests/test_gpu_hit_queries.py, created under the breadth-first switch: the shadow casts of the
     loop go through rt_cast_rays_indexed and take that walk; rt_shade_hits' do not.  Same values, same count"""
-    _torch()
-    big, cam = hq._tessellated(tmp_path, 4)
+    torch_device()
+    big, cam = tessellated_scene(tmp_path, 4)
     desc = big.desc()
     assert desc.n_triangles == 36 * 4 ** 4 + 28  # above rt_scene_create's default switch (8 192 triangles)
     with rt.options(RT_AMD_BFS_WALK_TRIANGLES=8192):  # read when the scene is created
         scene = rt.Scene(big)
-    b = make_batch(big, np.concatenate([camera_rays_cpu(cam, 24, 18), hq.source_b(desc, 51, 300)]))
+    b = make_batch(big, np.concatenate([camera_rays_cpu(cam, 24, 18), source_b(desc, 51, 300)]))
     assert b.valid.sum() >= 300 and b.casts.sum() > 300
     # the first uncaptured call on the stream makes the record lists of the walk; the second finds them
     assert_identity(scene, b, np.arange(b.n), "9 244 triangles", passes=(None, None, 1))
@@ -439,7 +320,7 @@ def test_a_scene_walked_breadth_first(tmp_path):
 def test_the_loop_in_a_graph(ref):
     """7. after one uncaptured call (rt_select_records' scratch on that stream) the loop is captured with its cast count and replayed
     with other records copied into the same buffers, on a stream of its own"""
-    torch = _torch()
+    torch = torch_device()
     scene = rt.Scene(ref.world)
     n = 1500
     first, second = np.arange(n), np.arange(n) + ref.n - n  # camera rays; random rays and rays inside the glass

@@ -14,34 +14,18 @@ from homework_18_graphics_raytracer_amd import _capi
 from homework_18_graphics_raytracer_amd._capi import Material, SceneDesc
 import _oracle
 import _scenes
-import test_gpu_hit_queries as hq
-import test_gpu_light_queries as lq
-import test_material_query_abi as mq
+import _light_support as lq
+from _records import camera_rays_cpu, dev, host, same_f32, source_b, torch_device, u32, valid_rows
+from _material_support import expected_probe, expected_surfaces, f3, handmade_hits, hit_record, reference_material_roles, same_surfaces
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
 SENTINEL = 0x5A5A5A5A
-same_f32, same_surfaces, dev = mq.same_f32, mq.same_surfaces, hq.dev
 m = rt.materials
 
 
-def _torch():
-    import torch
-
-    torch.cuda.set_device(0)
-    return torch
-
-
-def host(t):
-    return t.cpu().numpy()
-
-
-def u32(t):
-    return host(t).view(np.uint32)
-
-
 def fdev(a):
-    return _torch().tensor(np.ascontiguousarray(a, dtype=F32), device="cuda")
+    return torch_device().tensor(np.ascontiguousarray(a, dtype=F32), device="cuda")
 
 
 def lights_at(desc, l, positions):
@@ -51,7 +35,7 @@ def lights_at(desc, l, positions):
     some, direction, color = np.zeros(n, dtype=bool), np.zeros((n, 3), dtype=F32), np.zeros((n, 3), dtype=F32)
     d, c, o, h = (C.c_float * 3)(), (C.c_float * 3)(), (C.c_float * 3)(), C.c_int(0)
     for i in range(n):
-        if lib.orc_light_directional(C.byref(desc.lights[l]), mq.f3(positions[i]), d, c, o, C.byref(h)):
+        if lib.orc_light_directional(C.byref(desc.lights[l]), f3(positions[i]), d, c, o, C.byref(h)):
             some[i], direction[i], color[i] = True, d[:], c[:]
     return some, direction, color
 
@@ -62,7 +46,7 @@ def ref():
     b = lq.make_batch(world, lq.reference_rays(world.desc()))
     b.world = world
     assert 2500 <= b.valid.sum() <= 3500, b.valid.sum()
-    b.surfaces = mq.expected_surfaces(b.desc, b.hits)
+    b.surfaces = expected_surfaces(b.desc, b.hits)
     b.view = -b.rays[:, 3:6].view(F32)  # probe.view_direction as get_shade passes it: -hit.ray.direction
     pos = b.hits[:, 3:6].view(F32)
     b.lights = [lights_at(b.desc, l, pos) for l in range(b.desc.n_lights)]
@@ -72,7 +56,7 @@ def ref():
 
 def surfaces_of(scene, hits, pad=0):
     """rt_material_hits into a buffer filled with a sentinel, `pad` records longer than the batch"""
-    torch = _torch()
+    torch = torch_device()
     n = hits.shape[0]
     out = torch.full((n + pad, 18), SENTINEL, dtype=torch.int32, device="cuda")
     got = m.material_hits(scene, dev(hits), out=out[:n])
@@ -87,7 +71,7 @@ def assert_surfaces(got, want, what):
 
 
 def probe(surfaces, view, dirs):
-    torch = _torch()
+    torch = torch_device()
     d, s = m.probe_surfaces(dev(surfaces), fdev(view), fdev(dirs))
     torch.cuda.synchronize()
     return host(d), host(s)
@@ -117,7 +101,7 @@ def test_material_hits_against_the_oracle(ref):
 @pytest.mark.parametrize("n", [1, 63, 64, 65, 255, 256, 257])
 def test_wave_and_block_edges(ref, n):
     """the record after the last one is not written, by either kernel"""
-    torch = _torch()
+    torch = torch_device()
     rows = np.arange(n) * (ref.n // n) + 3
     scene = rt.Scene(ref.world)
     got = surfaces_of(scene, ref.hits[rows], pad=1)
@@ -135,7 +119,7 @@ def test_wave_and_block_edges(ref, n):
     torch.cuda.synchronize()
     dif, spe = host(dif), host(spe)
     assert (dif[probes * n] == 99.0).all() and (spe[probes * n] == 99.0).all()
-    want = mq.expected_probe(ref.surfaces[rows], ref.view[rows], dirs)
+    want = expected_probe(ref.surfaces[rows], ref.view[rows], dirs)
     assert_terms((dif[:-1].reshape(probes, n, 3), spe[:-1].reshape(probes, n, 3)), want, f"{n} records, {probes} probes")
 
 
@@ -143,8 +127,8 @@ def test_handmade_records(ref):
     """adjust_normal's branches (identity, antiparallel with sincosf, general; zero, NaN, infinite and non-unit normals), a negative
     stripe cell, a saturating f32 -> i32 conversion, and the records a caller got wrong: 18 zero words where the record is no hit —
     kind 2, an object_index at or beyond n_materials, a miss — while a primitive index outside its array does not invalidate"""
-    hits, labels, invalid = mq.handmade_hits(ref.desc)
-    want = mq.expected_surfaces(ref.desc, hits)
+    hits, labels, invalid = handmade_hits(ref.desc)
+    want = expected_surfaces(ref.desc, hits)
     got = surfaces_of(rt.Scene(ref.world), hits, pad=1)
     assert (got[len(labels)] == SENTINEL).all()
     bad = np.flatnonzero(~same_surfaces(got[:-1], want))
@@ -176,7 +160,7 @@ def test_probe_against_the_oracle(ref, probes):
         perp = np.stack([normal[:, 1], -normal[:, 0], np.zeros(ref.n, dtype=F32)], axis=1)  # ny * nx - nx * ny: exactly 0 in f32
         dirs[0, k == 4] = perp[k == 4]
         assert (np.abs(perp[(k == 4) & ref.valid]).max(axis=1) > 0.1).sum() > 300  # ... with a direction that is not zero
-    want = mq.expected_probe(ref.surfaces, ref.view, dirs)
+    want = expected_probe(ref.surfaces, ref.view, dirs)
     got = probe(ref.surfaces, ref.view, dirs)
     assert_terms(got, want, f"{probes} probes")
     assert (got[0][:, ~ref.valid].view(np.uint32) == 0).all() and (got[1][:, ~ref.valid].view(np.uint32) == 0).all()
@@ -190,15 +174,15 @@ def test_highlight_waves(ref):
     desc = ref.desc
     shiny = [k for k in range(desc.n_materials) if desc.materials[k].smoothness < 2e-5 and desc.materials[k].normal_fn == 0]
     assert shiny
-    hits = np.stack([mq.hit_record(1, 0, shiny[0], (0, 0, 1)) for _ in range(128)])
+    hits = np.stack([hit_record(1, 0, shiny[0], (0, 0, 1)) for _ in range(128)])
     surfaces = surfaces_of(rt.Scene(ref.world), hits)
-    assert_surfaces(surfaces, mq.expected_surfaces(desc, hits), "the flat shiny records")
+    assert_surfaces(surfaces, expected_surfaces(desc, hits), "the flat shiny records")
     theta = np.linspace(0.1, 1.2, 128)
     inside = 64 + 17
     theta[inside] = 0.02
     dirs = np.stack([np.sin(theta), np.zeros(128), np.cos(theta)], axis=1).astype(F32)[None]
     view = np.tile(np.array([0, 0, 1], dtype=F32), (128, 1))
-    want = mq.expected_probe(surfaces, view, dirs)
+    want = expected_probe(surfaces, view, dirs)
     assert (want[1][0, :64] == 0).all() and (want[0][0] > 0).any()          # wave 0: no highlight, lit all the same
     assert np.flatnonzero((want[1][0] != 0).any(axis=1)).tolist() == [inside]  # wave 1: one lane inside
     assert_terms(probe(surfaces, view, dirs), want, "highlight waves")
@@ -207,7 +191,7 @@ def test_highlight_waves(ref):
 def test_cross_check_against_light_terms_and_shade_hits(ref):
     """probe output times dl.color — one f32 multiply per channel, in numpy — is rt_light_terms' diffuse and specular where that says lit,
     and summed by rt_light_fold's rule it is rt_shade_hits (and orc_get_shade)"""
-    torch = _torch()
+    torch = torch_device()
     scene = rt.Scene(ref.world)
     hits_t, rays_t = dev(ref.hits), dev(ref.rays)
     g = lq.run_pieces(scene, hits_t, rays_t)
@@ -234,7 +218,7 @@ def test_cross_check_against_light_terms_and_shade_hits(ref):
 
 def test_an_edited_surface(ref):
     """the probe takes no scene: with diffuse_color overwritten in the surface tensor the diffuse term follows and the specular bits stay"""
-    torch = _torch()
+    torch = torch_device()
     rows = np.flatnonzero(ref.valid)[::7][:257]
     scene = rt.Scene(ref.world)
     surf_t = m.material_hits(scene, dev(ref.hits[rows]))
@@ -246,7 +230,7 @@ def test_an_edited_surface(ref):
     edited = ref.surfaces[rows].copy()
     edited[:, 3:6] = texture.view(np.uint32)
     assert np.array_equal(u32(surf_t), edited)
-    want = mq.expected_probe(edited, ref.view[rows], ref.light_dirs[:, rows])
+    want = expected_probe(edited, ref.view[rows], ref.light_dirs[:, rows])
     assert_terms(after, want, "edited")
     assert np.array_equal(after[1].view(np.uint32), before[1].view(np.uint32))
     assert not np.array_equal(after[0].view(np.uint32), before[0].view(np.uint32))
@@ -258,7 +242,7 @@ def test_an_edited_surface(ref):
 def test_after_a_material_update(ref):
     """rt_material_hits reads the live material array: after Scene.update_materials of one material it gives a fresh scene's surfaces"""
     desc = ref.desc
-    _, wave, _ = mq.reference_material_roles(desc)
+    _, wave, _ = reference_material_roles(desc)
     mats = (Material * desc.n_materials)(*[desc.materials[k] for k in range(desc.n_materials)])
     mats[wave].normal_frequency, mats[wave].tex_frequency, mats[wave].tex_color_a, mats[wave].shiness = 3.0, 7.0, (0.9, 0.1, 0.2), 0.25
     changed = SceneDesc(desc.triangles, desc.n_triangles, desc.spheres, desc.n_spheres, mats, desc.n_materials, desc.lights, desc.n_lights)
@@ -267,7 +251,7 @@ def test_after_a_material_update(ref):
     scene.update_materials(wave, [mats[wave]])
     got = surfaces_of(scene, ref.hits)
     fresh = surfaces_of(rt.Scene(changed), ref.hits)
-    want = mq.expected_surfaces(desc, ref.hits, materials=mats)
+    want = expected_surfaces(desc, ref.hits, materials=mats)
     assert_surfaces(got, want, "after the update")
     assert_surfaces(fresh, want, "a fresh scene")
     on_wave = ref.valid & (ref.hits[:, 2] == wave)
@@ -276,28 +260,28 @@ def test_after_a_material_update(ref):
 
 def test_a_scene_walked_breadth_first():
     """a scene above rt_scene_create's breadth-first switch (8 192 triangles): the kernels do not walk, KernelScene is passed as it is"""
-    torch = _torch()
+    torch = torch_device()
     world = _scenes.random_world(11, 8200, 3)
     desc = world.desc()
     assert desc.n_triangles >= 8192
     with rt.options(RT_AMD_BFS_WALK_TRIANGLES=8192):  # read when the scene is created
         scene = rt.Scene(world)
-    rays = np.concatenate([lq.camera_rays_cpu(_scenes.camera(11), 32, 24), hq.source_b(desc, 9, 500)])
+    rays = np.concatenate([camera_rays_cpu(_scenes.camera(11), 32, 24), source_b(desc, 9, 500)])
     hits_t = rt.cast_rays(scene, dev(rays))
     surf_t = m.material_hits(scene, hits_t)
     torch.cuda.synchronize()
     hits = u32(hits_t)
-    assert mq.valid_rows(desc, hits).sum() > 300
-    want = mq.expected_surfaces(desc, hits)
+    assert valid_rows(desc, hits).sum() > 300
+    want = expected_surfaces(desc, hits)
     assert_surfaces(u32(surf_t), want, "8 200 triangles")
     view = -rays[:, 3:6].view(F32)
     dirs = want[:, 14:17].view(F32)[None].copy()
-    assert_terms(probe(want, view, dirs), mq.expected_probe(want, view, dirs), "8 200 triangles")
+    assert_terms(probe(want, view, dirs), expected_probe(want, view, dirs), "8 200 triangles")
 
 
 def test_both_calls_in_a_graph(ref):
     """material_hits + probe_surfaces captured on one stream — a linear graph — and replayed once on other records: the eager result"""
-    torch = _torch()
+    torch = torch_device()
     scene = rt.Scene(ref.world)
     n = 1500
     first, second = np.arange(n), np.arange(n) + ref.n - n
@@ -334,7 +318,7 @@ def test_both_calls_in_a_graph(ref):
 
 def test_primary_surfaces(ref):
     """48x36: the planes are views of the three record tensors, which are what camera_rays, cast_rays and material_hits give"""
-    torch = _torch()
+    torch = torch_device()
     scene = rt.Scene(ref.world)
     camera, frame = rt.reference_camera(), rt.Frame.full(48, 36, 5)
     p = m.primary_surfaces(scene, camera, frame)
@@ -342,7 +326,7 @@ def test_primary_surfaces(ref):
     want_hits = rt.cast_rays(scene, rt.camera_rays(camera, frame))
     torch.cuda.synchronize()
     assert np.array_equal(u32(rays), ref.rays[:48 * 36]) and np.array_equal(u32(hits), u32(want_hits))
-    assert_surfaces(u32(surfaces), mq.expected_surfaces(ref.desc, u32(hits)), "primary surfaces")
+    assert_surfaces(u32(surfaces), expected_surfaces(ref.desc, u32(hits)), "primary surfaces")
     h, s = u32(hits).reshape(36, 48, 13), u32(surfaces).reshape(36, 48, 18)
     for name, plane, words in (("depth", p.depth, h[..., 12]), ("position", p.position, h[..., 3:6]), ("geometric_normal", p.geometric_normal, h[..., 6:9]),
                                ("shading_normal", p.shading_normal, s[..., 14:17]), ("albedo", p.albedo, s[..., 3:6]),
@@ -374,4 +358,4 @@ def test_host_forms(ref):
         assert host_terms[0].shape == (3, 257, 3)
         assert np.array_equal(host_terms[0].view(np.uint32), dev_terms[0].view(np.uint32))
         assert np.array_equal(host_terms[1].view(np.uint32), dev_terms[1].view(np.uint32))
-    assert_terms(dev_terms, mq.expected_probe(want, view, dirs), "257 records")
+    assert_terms(dev_terms, expected_probe(want, view, dirs), "257 records")

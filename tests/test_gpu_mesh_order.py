@@ -16,26 +16,14 @@ import pytest
 
 import homework_18_graphics_raytracer_amd as rt
 import _oracle
-import test_gpu_hit_queries as hq
-import test_gpu_ray_query as rq
-import test_mesh_order_abi as mo
+import _hit_support as hq
+import _mesh_order_support as mo
+from _records import dev, ray_records, same_hits, source_b, torch_device, u32
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
 SENTINEL = 0x5A5A5A5A
 NONE = 0xFFFFFFFF
-dev = hq.dev
-
-
-def _torch():
-    import torch
-
-    torch.cuda.set_device(0)
-    return torch
-
-
-def u32(t):
-    return t.cpu().numpy().view(np.uint32)
 
 
 # ---- keys ----
@@ -67,7 +55,7 @@ KEY_BOXES = [(mo.LO, mo.HI), ((-2, 1, 0), (2, 1, 8)),            # a zero-extent
 
 @pytest.mark.parametrize("n", [1, 64, 65, 2304 + 64])
 def test_keys_equal_the_numpy_restatement(tmp_path, n):
-    torch = _torch()
+    torch = torch_device()
     world, natural, _, mesh = mo.sweep(3, tmp_path)
     everything = np.concatenate([special_triangles(), natural[mesh]])
     assert everything.shape[0] == 2304 + 64
@@ -105,7 +93,7 @@ def interleaved_objects(tmp_path):
 
 
 def test_permutation_of_interleaved_objects(tmp_path):
-    torch = _torch()
+    torch = torch_device()
     raw = interleaved_objects(tmp_path)
     n = raw.shape[0]
     p = raw[:, 1:].copy().view(F32).reshape(n, 3, 8)[:, :, :3].reshape(-1, 3)
@@ -191,7 +179,7 @@ def grazing_rays(raw, seed, max_runs=100):
             origins.append(eye)
             directions.append(c + r * scale * u - eye)
     o, d = np.concatenate(origins), np.concatenate(directions)
-    return hq.ray_records(o, d, g.integers(0, 3, len(o)))
+    return ray_records(o, d, g.integers(0, 3, len(o)))
 
 
 LEVELS = {3: (20_000, rt.Frame.full(64, 36, 5)), 4: (5_000, rt.Frame.full(32, 18, 5))}
@@ -201,7 +189,7 @@ _cases = {}
 def case(level, tmp_path):
     """the shuffled sweep scene, the device's order of it, the two scenes, and a batch of rays in both numberings"""
     if level not in _cases:
-        torch = _torch()
+        torch = torch_device()
         world, natural, shuffled, mesh = mo.sweep(level, tmp_path)
         base = world.desc()
         lo, hi = world.bounds()
@@ -213,7 +201,7 @@ def case(level, tmp_path):
         c = type("Case", (), {})()
         c.perm, c.shuffled_desc, c.ordered_desc = perm, mo.desc_with(base, shuffled), mo.desc_with(base, ordered)
         c.shuffled_scene, c.ordered_scene = rt.Scene(c.shuffled_desc), rt.Scene(c.ordered_desc)
-        c.rays_shuffled = np.concatenate([hq.source_b(c.shuffled_desc, 500 + level, LEVELS[level][0]), grazing_rays(ordered, level),
+        c.rays_shuffled = np.concatenate([source_b(c.shuffled_desc, 500 + level, LEVELS[level][0]), grazing_rays(ordered, level),
                                           grazing_rays(shuffled, 10 + level, max_runs=8)])
         c.rays_ordered = rt.order_rays(c.rays_shuffled, perm).view(np.uint32).reshape(-1, 11)
         _cases[level] = c
@@ -223,7 +211,7 @@ def case(level, tmp_path):
 def assert_tie_rule(got, want, what):
     """records equal except at ties: where two records differ, both are hits with the same distance bits; at most 1 % differ"""
     got, want = np.asarray(got).view(np.uint32).reshape(-1, 13), np.asarray(want).view(np.uint32).reshape(-1, 13)
-    differ = np.flatnonzero(~rq.same_hits(got, want))
+    differ = np.flatnonzero(~same_hits(got, want))
     print(f"{what}: {differ.size} of {got.shape[0]} records differ")
     bad = [i for i in differ if got[i, 0] == NONE or want[i, 0] == NONE or got[i, 12] != want[i, 12]]
     assert not bad, (what, len(bad), bad[:5], got[bad[:2]], want[bad[:2]])
@@ -241,7 +229,7 @@ def test_ordered_scene_equals_the_oracle_on_the_ordered_description(tmp_path, le
     breadth-first walk (and the wave-uniform one for the per-pixel kernel)"""
     c = case(level, tmp_path)
     assert c.ordered_desc.n_triangles == 36 * 4 ** level + 28
-    want = rq.check(c.ordered_scene, c.ordered_desc, dev(c.rays_ordered), f"level {level}")  # default and wave-uniform, bit for bit
+    want = hq.check(c.ordered_scene, c.ordered_desc, dev(c.rays_ordered), f"level {level}")  # default and wave-uniform, bit for bit
     assert (want[:, 0] == NONE).sum() > 0 and (want[:, 0] == rt.TRIANGLE).sum() > 1000
     camera, frame = rt.reference_camera(), LEVELS[level][1]
     image, casts = _oracle.render_whitted(c.ordered_desc, camera, frame)
@@ -287,4 +275,4 @@ def test_exclusions_through_the_permutation(tmp_path, level):
     assert_tie_rule(got, want, f"level {level}, reflected")
     # without the mapping the exclusion names another triangle: some ray hits the surface it leaves
     unmapped = rt.unorder_hits(u32(rt.cast_rays(c.ordered_scene, dev(reflected))), c.perm).view(np.uint32).reshape(-1, 13)
-    assert (~rq.same_hits(unmapped, want)).sum() > (~rq.same_hits(got.view(np.uint32).reshape(-1, 13), want)).sum()
+    assert (~same_hits(unmapped, want)).sum() > (~same_hits(got.view(np.uint32).reshape(-1, 13), want)).sum()

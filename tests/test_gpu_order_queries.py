@@ -7,33 +7,17 @@ import numpy as np
 import pytest
 
 import homework_18_graphics_raytracer_amd as rt
-import test_gpu_hit_queries as hq
-import test_order_query_abi as oq
+import _order_support as oq
+from _records import dev, host, ray_records, source_b, torch_device, u32
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
 SENTINEL = 0x5A5A5A5A
-dev = hq.dev
-
-
-def _torch():
-    import torch
-
-    torch.cuda.set_device(0)
-    return torch
-
-
-def host(t):
-    return t.cpu().numpy()
-
-
-def u32(t):
-    return host(t).view(np.uint32)
 
 
 def words(a):
     """a uint32 array as an int32 CUDA tensor"""
-    return _torch().tensor(np.ascontiguousarray(a, dtype=np.uint32).view(np.int32), device="cuda")
+    return torch_device().tensor(np.ascontiguousarray(a, dtype=np.uint32).view(np.int32), device="cuda")
 
 
 @pytest.fixture(scope="module")
@@ -49,7 +33,7 @@ def _special_rays():
     o = [(0, 0, 0)] * 12 + [(inf, -inf, nan), (nan, 0, inf), (-inf, inf, 0), (9, -9, 1e30), (-1e-30, 2.0, -2.0), (1.999, -1.999, 0.5)]
     d = [(0, 0, 0), (1, 1, 0.0), (1, 1, -0.0), (1, -1, nan), (nan, 1, -1), (1, nan, -1), (0, 0, -1), (-0.0, -0.0, -1), (inf, 1, 1),
          (1, 2, -inf), (1e-30, -1e-30, -1e-30), (-3, 4, -5)] + [(0.3, -0.2, -0.9)] * 6
-    return hq.ray_records(np.asarray(o, dtype=F32), np.asarray(d, dtype=F32), 0xABCDEF)
+    return ray_records(np.asarray(o, dtype=F32), np.asarray(d, dtype=F32), 0xABCDEF)
 
 
 BOXES = [((-2, -2, -2), (2, 2, 2)), ((0, 0, 0), (0, -1, np.nan)), ((np.nan, -np.inf, -1), (1, np.inf, -1)), ((-1, -1, -1), (np.inf, 1e-30, 1))]
@@ -57,11 +41,11 @@ BOXES = [((-2, -2, -2), (2, 2, 2)), ((0, 0, 0), (0, -1, np.nan)), ((np.nan, -np.
 
 @pytest.mark.parametrize("n", [1, 63, 64, 65, 4097])
 def test_keys_equal_the_numpy_restatement(ref, n):
-    torch = _torch()
+    torch = torch_device()
     _, desc, _, (lo, hi) = ref
     camera = u32(rt.camera_rays(rt.reference_camera(), rt.Frame.full(64, 32, 0)))
     special = _special_rays()
-    sources = {"random": hq.source_b(desc, 100 + n, n), "camera": np.resize(camera, (n, 11)), "special": np.resize(special, (n, 11))}
+    sources = {"random": source_b(desc, 100 + n, n), "camera": np.resize(camera, (n, 11)), "special": np.resize(special, (n, 11))}
     for name, rays in sources.items():
         rays_t = dev(rays)
         for box in [(lo, hi)] + (BOXES if name == "special" else []):
@@ -144,7 +128,7 @@ def _lists(n, g, torch):
 
 @pytest.mark.parametrize("n", [1, 2, 63, 64, 65, 255, 256, 257, 4097, 65537, (1 << 20) + 37])
 def test_sort_against_numpy_stable_argsort(n):
-    torch = _torch()
+    torch = torch_device()
     g = np.random.default_rng(n)
     sorter = _Sorter(n, torch)
     lists = _lists(n, g, torch)
@@ -185,7 +169,7 @@ def test_sort_of_more_than_2_to_the_21_entries(n):
     table — what a 4K frame of rays gets.  Lists rotate over key sets and bit ranges; every one of each is met."""
     import time
 
-    torch = _torch()
+    torch = torch_device()
     t0 = time.perf_counter()
     tile, tiles = oq.sort_tile(n)
     assert (tile, tiles) == oq.SORT_LARGE[n]  # a change of the constants fails here instead of moving the test off the path
@@ -224,7 +208,7 @@ def test_sort_of_more_than_2_to_the_21_entries(n):
 
 def test_sort_keeps_equal_keys_in_input_order_and_groups_a_level_by_branch():
     """rt_scatter_hits' d_type with key_bits = 2: the records of each branch stay in their order"""
-    torch = _torch()
+    torch = torch_device()
     g = np.random.default_rng(7)
     n = 10_000
     types = g.integers(0, 3, n).astype(np.uint32)
@@ -234,7 +218,7 @@ def test_sort_keeps_equal_keys_in_input_order_and_groups_a_level_by_branch():
 
 
 def test_sort_captured_into_a_graph_without_an_earlier_call():
-    torch = _torch()
+    torch = torch_device()
     g = np.random.default_rng(9)
     n = 5000
     keys = g.integers(0, 1 << 30, n, dtype=np.uint64).astype(np.uint32)
@@ -272,7 +256,7 @@ def test_sort_captured_into_a_graph_without_an_earlier_call():
 @pytest.mark.parametrize("record_bytes", [4, 12, 44, 52, 256])
 @pytest.mark.parametrize("n", [1, 65, 4097])
 def test_gather_and_scatter_against_fancy_indexing(n, record_bytes):
-    torch = _torch()
+    torch = torch_device()
     g = np.random.default_rng(n * 1000 + record_bytes)
     w = record_bytes // 4
     src = g.integers(1, 1 << 32, (n, w), dtype=np.uint64).astype(np.uint32)
@@ -329,12 +313,12 @@ W, H = 160, 90
 @pytest.fixture(scope="module")
 def batch(ref):
     """about 20 000 rays: the camera rays of a 160 x 90 frame in a random permutation, then random rays; with what the plain calls give"""
-    torch = _torch()
+    torch = torch_device()
     _, desc, scene, _ = ref
     g = np.random.default_rng(2024)
     perm = g.permutation(W * H)
     camera = u32(rt.camera_rays(rt.reference_camera(), rt.Frame.full(W, H, 3)))
-    rays = np.concatenate([camera[perm], hq.source_b(desc, 77, 20_000 - W * H)])
+    rays = np.concatenate([camera[perm], source_b(desc, 77, 20_000 - W * H)])
     rays_t = dev(rays)
     hits = u32(rt.cast_rays(scene, rays_t))
     count = torch.zeros(1, dtype=torch.int64, device="cuda")
@@ -359,7 +343,7 @@ def _guarded(fn, checked, torch):
 @pytest.mark.parametrize("checked", [False, True])
 @pytest.mark.parametrize("which", ["reference", "breadth-first"])
 def test_ordered_casts_equal_cast_rays(ref, batch, which, checked):
-    torch = _torch()
+    torch = torch_device()
     world, _, scene, _ = ref
     _, rays, rays_t, hits, _, _ = batch
     if which == "breadth-first":
@@ -383,11 +367,11 @@ def test_ordered_casts_equal_cast_rays(ref, batch, which, checked):
 
 def test_ordered_casts_of_more_than_2_to_the_21_rays(ref, batch):
     """a batch whose sort takes tiles of two steps (a 4K frame's worth): the permuted camera rays over and over, then random rays"""
-    torch = _torch()
+    torch = torch_device()
     _, desc, scene, _ = ref
     n = (1 << 21) + 4099
     assert oq.sort_tile(n) == (4096, 514)
-    rays_t = dev(np.concatenate([np.resize(batch[1][:W * H], (1 << 21, 11)), hq.source_b(desc, 78, 4099)]))
+    rays_t = dev(np.concatenate([np.resize(batch[1][:W * H], (1 << 21, 11)), source_b(desc, 78, 4099)]))
     assert rays_t.shape[0] == n
     hits = u32(rt.cast_rays(scene, rays_t))
     out = torch.full((n, 13), SENTINEL, dtype=torch.int32, device="cuda")
@@ -401,7 +385,7 @@ def test_ordered_casts_of_more_than_2_to_the_21_rays(ref, batch):
 
 @pytest.mark.parametrize("checked", [False, True])
 def test_ordered_traces_equal_trace_rays(ref, batch, checked):
-    torch = _torch()
+    torch = torch_device()
     _, _, scene, _ = ref
     _, rays, rays_t, _, rgb, casts = batch
     n = rays.shape[0]

@@ -2,8 +2,6 @@
 (orc_cast) bit for bit, NaN equal to NaN, through the pair-wise kernel, the wave-uniform one (RT_AMD_QUERY_WAVE_UNIFORM) and the
 breadth-first walk; camera rays equal orc_shoot(orc_clip(x, y)); stream order and graph capture."""
 import ctypes as C
-import subprocess
-import sys
 from pathlib import Path
 
 import numpy as np
@@ -12,96 +10,11 @@ import pytest
 import homework_18_graphics_raytracer_amd as rt
 import _oracle
 import _scenes
+from _hit_support import check
+from _records import bounds, oracle_hits, random_rays, same_hits, tessellated_world, torch_device
 
 pytestmark = pytest.mark.gpu
 ROOT = Path(__file__).resolve().parent.parent
-FLOAT_WORDS = [3, 4, 5, 6, 7, 8, 9, 10, 12]  # position, normal, uv, distance of an rt_hit record
-
-
-def _torch():
-    import torch
-
-    torch.cuda.set_device(0)
-    return torch
-
-
-def oracle_hits(desc, rays_words: np.ndarray) -> np.ndarray:
-    """orc_cast of every (11-word) ray record: (N, 13) uint32 rt_hit records, RT_HIT_NONE and zeros for a miss."""
-    rays = np.ascontiguousarray(rays_words).view(np.uint32).reshape(-1, 11).copy()
-    n = rays.shape[0]
-    out = np.zeros((n, 13), dtype=np.uint32)
-    out[:, 0] = 0xFFFFFFFF
-    lib = _oracle.lib()
-    orays = (_oracle.OrcRay * n).from_buffer(rays)
-    h = _oracle.OrcHit()
-    for i in range(n):
-        if lib.orc_cast(C.byref(desc), C.byref(orays[i]), C.byref(h)):
-            out[i] = np.frombuffer(bytes(h), dtype=np.uint32)
-    return out
-
-
-def same_hits(got: np.ndarray, want: np.ndarray) -> np.ndarray:
-    """per record: every word equal, a float word also equal when both are NaN"""
-    got = np.asarray(got).view(np.uint32).reshape(-1, 13)
-    want = want.reshape(-1, 13)
-    eq = got == want
-    gf, wf = got[:, FLOAT_WORDS].view(np.float32), want[:, FLOAT_WORDS].view(np.float32)
-    eq[:, FLOAT_WORDS] |= np.isnan(gf) & np.isnan(wf)
-    return eq.all(axis=1)
-
-
-def cast_both_ways(scene, rays_t):
-    """(pair-wise or breadth-first default, wave-uniform) results as numpy uint32"""
-    torch = _torch()
-    a = rt.cast_rays(scene, rays_t)
-    with rt.options(RT_AMD_QUERY_WAVE_UNIFORM=1):
-        b = rt.cast_rays(scene, rays_t)
-    torch.cuda.synchronize()
-    return a.cpu().numpy().view(np.uint32), b.cpu().numpy().view(np.uint32)
-
-
-def check(scene, desc, rays_t, what=""):
-    want = oracle_hits(desc, rays_t.cpu().numpy())
-    for name, got in zip(("default", "wave-uniform"), cast_both_ways(scene, rays_t)):
-        ok = same_hits(got, want)
-        bad = np.flatnonzero(~ok)
-        assert ok.all(), f"{what} {name}: {bad.size} of {ok.size} differ, first {bad[:5]}: got {got[bad[:1]]} want {want[bad[:1]]}"
-    return want
-
-
-def random_rays(seed, n, desc, centre, radius):
-    """origins inside and outside the scene's bounding sphere, every face mode, triangle and sphere exclusions with every face,
-    out-of-range exclusion indices, rays with no exclusion"""
-    torch = _torch()
-    g = np.random.default_rng(seed)
-    scale = np.where(g.random(n) < 0.5, g.uniform(0.0, 1.0, n), g.uniform(1.0, 4.0, n)) * radius
-    u = g.normal(size=(n, 3))
-    origins = centre + u / np.linalg.norm(u, axis=1, keepdims=True) * scale[:, None]
-    towards = centre + g.normal(0.0, radius * 0.5, (n, 3))
-    d = towards - origins
-    d *= g.choice([1.0, 0.3, 2.5], n)[:, None] / np.maximum(np.linalg.norm(d, axis=1, keepdims=True), 1e-12)  # not all unit length
-    face = g.integers(0, 3, n)
-    kind = g.choice([-1, rt.SPHERE, rt.TRIANGLE], n, p=[0.3, 0.3, 0.4])
-    nt, ns = int(desc.n_triangles), int(desc.n_spheres)
-    index = np.where(kind == rt.TRIANGLE, g.integers(0, max(nt, 1) + 3, n), g.integers(0, max(ns, 1) + 3, n))  # some out of range
-    index[g.random(n) < 0.02] = 0x7FFFFFF0
-    ex_face = g.integers(0, 3, n)
-    f32 = lambda a: torch.tensor(np.asarray(a, dtype=np.float32), device="cuda")
-    i64 = lambda a: torch.tensor(np.asarray(a, dtype=np.int64), device="cuda")
-    return rt.make_rays(f32(origins), f32(d), i64(face), i64(kind), i64(index), i64(ex_face))
-
-
-def bounds(desc):
-    pts = []
-    for i in range(desc.n_triangles):
-        for v in desc.triangles[i].vertices:
-            pts.append(tuple(v.position))
-    for i in range(desc.n_spheres):
-        s = desc.spheres[i]
-        pts += [tuple(np.asarray(s.center) + s.radius), tuple(np.asarray(s.center) - s.radius)]
-    p = np.asarray(pts, dtype=np.float64)
-    c = (p.min(0) + p.max(0)) / 2
-    return c, float(np.linalg.norm(p - c, axis=1).max())
 
 
 def test_reference_scene_random_rays():
@@ -118,7 +31,7 @@ def test_reference_scene_random_rays():
     host = rt.cast_rays_numpy(scene, rays.cpu().numpy())
     assert same_hits(host.view(np.uint32).reshape(-1, 13), want).all()
     hits = rt.Hits(rt.cast_rays(scene, rays))
-    torch = _torch()
+    torch = torch_device()
     torch.cuda.synchronize()
     mask = hits.hit.cpu().numpy()
     assert (mask == (want[:, 0] != 0xFFFFFFFF)).all()
@@ -129,7 +42,7 @@ def test_reference_scene_random_rays():
 def test_edge_rays():
     """rays in a triangle's plane (NaN distances: cast_pairs's whole-wave fallback), zero and non-normalised directions, infinite and
     NaN components, origins on a sphere's surface looking out with Back / Both, face values above 2 (read as Both)"""
-    torch = _torch()
+    torch = torch_device()
     world = rt.reference_world()
     desc = world.desc()
     scene = rt.Scene(world)
@@ -191,30 +104,23 @@ def test_scenes(make):
         check(scene, desc, random_rays(100 + seed, 3000, desc, centre, radius), f"{make} {seed}")
 
 
-def _tessellated(tmp_path, level, spherize):
-    obj = tmp_path / f"d{level}{'s' if spherize else 'f'}.obj"
-    cmd = [sys.executable, str(ROOT / "tools" / "make_tessellated_obj.py"), rt.DEFAULT_OBJ, str(obj), "--levels", str(level)]
-    subprocess.run(cmd + (["--spherize"] if spherize else []), check=True, capture_output=True)
-    return rt.reference_world(str(obj))
-
-
 @pytest.mark.parametrize("cap", [0, 96])
 def test_breadth_first_walk(tmp_path, cap):
     """a scene walked breadth-first (RT_AMD_BFS_WALK_TRIANGLES low before the scene is created): rt::cast_rays_bfs_kernel, once with
     record lists cut short (RT_AMD_DIAG_BFS_CAP) so that some wave-casts overflow into cast_asm"""
-    world = _tessellated(tmp_path, 2, True)
+    world = tessellated_world(tmp_path, 2, True)
     desc = world.desc()
     opts = {"RT_AMD_BFS_WALK_TRIANGLES": 1}
     if cap:
         opts["RT_AMD_DIAG_BFS_CAP"] = cap
     with rt.options(**opts):
         scene = rt.Scene(world)
-        flat = _tessellated(tmp_path, 2, False)
+        flat = tessellated_world(tmp_path, 2, False)
         flat_scene = rt.Scene(flat)
         centre, radius = bounds(desc)
         check(scene, desc, random_rays(11, 6000, desc, centre, radius), "bfs spherized")
         check(flat_scene, flat.desc(), random_rays(12, 4000, flat.desc(), centre, radius), "bfs flat")
-        torch = _torch()
+        torch = torch_device()
         frame = rt.Frame.full(64, 48, 1)
         check(scene, desc, rt.camera_rays(rt.reference_camera(), frame), "bfs camera")
 
@@ -235,7 +141,7 @@ def _orc_primary(camera, frame):
 
 
 def test_camera_rays():
-    torch = _torch()
+    torch = torch_device()
     world = rt.reference_world()
     desc = world.desc()
     scene = rt.Scene(world)
@@ -263,7 +169,7 @@ def test_camera_rays():
 
 
 def test_streams_capture_and_empty_batches():
-    torch = _torch()
+    torch = torch_device()
     world = _scenes.random_world(21, 24, 3)
     desc = world.desc()
     scene = rt.Scene(world)

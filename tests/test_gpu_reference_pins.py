@@ -19,8 +19,7 @@ from PIL import Image
 import homework_18_graphics_raytracer_amd as rt
 from homework_18_graphics_raytracer_amd import _capi
 import _oracle
-from test_oracle_reference_png import PINS, REFERENCE_EPOCHS, progressive_loop
-from test_oracle_rng import RAND_05_NEW_FROM_U64_0
+from _reference_support import PINS, progressive_loop, RAND_05_NEW_FROM_U64_0, REFERENCE_EPOCHS
 
 pytestmark = pytest.mark.gpu
 

@@ -13,24 +13,16 @@ import homework_18_graphics_raytracer_amd as rt
 from homework_18_graphics_raytracer_amd._capi import Material
 import _oracle
 import _scenes
-import test_gpu_hit_queries as hq
-import test_gpu_light_queries as lq
-import test_gpu_scatter_queries as sq
+import _hit_support as hq
+import _scatter_support as sq
+from _records import camera_rays_cpu, dev, host, oracle_hits, ray_records, same_f32, same_rays, source_b, source_c, tessellated_scene, torch_device, u32
+from _light_support import dist32
 
 pytestmark = pytest.mark.gpu
 NONE = 0xFFFFFFFF
 ESCAPED, INFINITE, TRAPPED, WALKING = 0, 1, 2, 3
 FRONT, BACK = 0, 1
 ROUNDS = 11
-same_f32, same_rays, dev, dist32 = hq.same_f32, hq.same_rays, hq.dev, lq.dist32
-host, u32 = lq.host, lq.u32
-
-
-def _torch():
-    import torch
-
-    torch.cuda.set_device(0)
-    return torch
 
 
 # ---- the expected side: get_refract (main.rs:343-405) replayed one cast at a time, on the CPU, from the oracle's exports ----
@@ -161,14 +153,14 @@ def box_rays(seed, n_each):
         target = c + np.array([0.0, h[1], 0.0]) + np.stack([g.uniform(-0.8, 0.8, n_each) * h[0], np.zeros(n_each), g.uniform(-0.8, 0.8, n_each) * h[2]], axis=1)
         tilt, turn = np.radians(g.uniform(2.0, 80.0, n_each)), g.uniform(0.0, 2 * np.pi, n_each)
         d = np.stack([np.sin(tilt) * np.cos(turn), -np.cos(tilt), np.sin(tilt) * np.sin(turn)], axis=1)
-        out.append(hq.ray_records(target - d * (0.5 * h[0]), d, FRONT))
+        out.append(ray_records(target - d * (0.5 * h[0]), d, FRONT))
     u = g.normal(size=(n_each // 2, 3))  # towards points of the sphere's disc as seen from the origin: centre to rim
     u /= np.linalg.norm(u, axis=1, keepdims=True)
     origins = np.asarray(THIN[0]) + u * 5.0
     side = np.cross(u, g.normal(size=u.shape))
     side /= np.linalg.norm(side, axis=1, keepdims=True)
     d = np.asarray(THIN[0]) + side * (g.uniform(0.0, 0.98, (u.shape[0], 1)) * THIN[1]) - origins
-    out.append(hq.ray_records(origins, d / np.linalg.norm(d, axis=1, keepdims=True), FRONT))
+    out.append(ray_records(origins, d / np.linalg.norm(d, axis=1, keepdims=True), FRONT))
     return np.concatenate(out)
 
 
@@ -189,11 +181,11 @@ def make_ref():
     b.world = fixture_world()
     b.desc = b.world.desc()
     plain = rt.reference_world().desc()
-    b.rays = np.concatenate([lq.camera_rays_cpu(rt.reference_camera(), 48, 36), hq.source_b(plain, 3, 1272), hq.source_c(plain, 3, 237),
+    b.rays = np.concatenate([camera_rays_cpu(rt.reference_camera(), 48, 36), source_b(plain, 3, 1272), source_c(plain, 3, 237),
                              box_rays(5, 120)])
     b.n = b.rays.shape[0]
     assert b.n == 4011
-    b.hits = hq.oracle_hits(b.desc, b.rays)
+    b.hits = oracle_hits(b.desc, b.rays)
     b.runs = {}
     for max_distance in (100.0, float("inf"), SMALL):
         states, why = replay(b.desc, b.rays, b.hits, max_distance)
@@ -230,7 +222,7 @@ def final(states):
 
 
 def fused(scene, hits_t, rays_t, max_distance):
-    torch = _torch()
+    torch = torch_device()
     cnt = torch.zeros(1, dtype=torch.int64, device="cuda")
     r = rt.refract_rays(scene, hits_t, rays_t, max_distance, ray_count=cnt)
     torch.cuda.synchronize()
@@ -238,14 +230,14 @@ def fused(scene, hits_t, rays_t, max_distance):
 
 
 def sentinel_out(n):
-    torch = _torch()
+    torch = torch_device()
     return rt.Refractions(torch.full((n,), 0x5A5A5A5A, dtype=torch.int32, device="cuda"), torch.full((n,), 99.0, dtype=torch.float32, device="cuda"),
                           torch.full((n, 11), 0x5A5A5A5A, dtype=torch.int32, device="cuda"))
 
 
 def by_bounce(scene, hits_t, rays_t, max_distance, rounds=ROUNDS, stream=None, out=None, workspace=None, resume=False):
     """the loop, with every synchronising torch call inside it an error: no host visit hides there"""
-    torch = _torch()
+    torch = torch_device()
     n = hits_t.shape[0]
     out = sentinel_out(n) if out is None else out
     ws = rt.refract_workspace(n, "cuda") if workspace is None else workspace
@@ -283,7 +275,7 @@ def rows_of(b, size, why):
 def test_the_loop_is_refract_rays(ref, size, max_distance):
     """1. refract_rays_by_bounce == rt.refract_rays == get_refract replayed on the CPU: kind, travel, escape words and cast count; and
     the casts counted per record add up to that count"""
-    _torch()
+    torch_device()
     scene = rt.Scene(ref.world)
     states, why = ref.runs[max_distance]
     rows = rows_of(ref, size, ref.runs[100.0][1])
@@ -305,7 +297,7 @@ def test_the_loop_is_refract_rays(ref, size, max_distance):
 def run_rounds(scene, hits_t, rays_t, max_distance, rounds=ROUNDS, tamper=None):
     """refract_enter, then `rounds` times select_records -> cast_rays_indexed -> refract_step, every output filled with a sentinel first;
     the state downloaded after every call.  tamper(state tensors): a caller's writes between the entry and the first round"""
-    torch = _torch()
+    torch = torch_device()
     n = hits_t.shape[0]
     i32 = torch.int32
     rays_s = torch.full((n, 11), 0x5A5A5A5A, dtype=i32, device="cuda")
@@ -352,7 +344,7 @@ def assert_state(got, want, what, escape_written):
 def test_every_round_against_the_replay(ref, max_distance):
     """2. after the entry and after each of the eleven steps, d_kind, d_travel, d_casts, d_flags and the words of d_rays are the CPU
     replay's; the ray an Infinite record keeps is the ray whose orc_cast misses"""
-    _torch()
+    torch_device()
     scene = rt.Scene(ref.world)
     states, why = ref.runs[max_distance]
     got = run_rounds(scene, dev(ref.hits), dev(ref.rays), max_distance)
@@ -375,7 +367,7 @@ def test_every_round_against_the_replay(ref, max_distance):
 def test_foreign_records(ref):
     """3. records and state words a caller got wrong, outputs filled with a sentinel first: exactly the documented words are written, and
     nothing is cast for a finished record.  Validation, not an attempt at a fault: nothing in the kernels is indexed with a state word"""
-    torch = _torch()
+    torch = torch_device()
     desc = ref.desc
     scene = rt.Scene(ref.world)
     states, why = ref.runs[100.0]
@@ -455,7 +447,7 @@ def test_foreign_records(ref):
 def test_a_bounce_limit_of_three_rounds(ref):
     """4. rounds=3 leaves exactly the replay's unfinished records WALKING, and eight more rounds on the same state end equal to the
     full loop"""
-    _torch()
+    torch_device()
     scene = rt.Scene(ref.world)
     states, why = ref.runs[100.0]
     hits_t, rays_t = dev(ref.hits), dev(ref.rays)
@@ -476,14 +468,14 @@ def test_a_bounce_limit_of_three_rounds(ref):
 def test_a_scene_walked_breadth_first(tmp_path):
     """5. the 9 244-triangle scene of tests/test_gpu_hit_queries.py, created under the breadth-first switch: the casts of the loop go
     through rt_cast_rays_indexed and take that walk; rt_refract_rays' do not.  Same bits, same count"""
-    _torch()
-    big, cam = hq._tessellated(tmp_path, 4)
+    torch_device()
+    big, cam = tessellated_scene(tmp_path, 4)
     desc = big.desc()
     assert desc.n_triangles == 36 * 4 ** 4 + 28  # above rt_scene_create's default switch (8 192 triangles)
     with rt.options(RT_AMD_BFS_WALK_TRIANGLES=8192):  # read when the scene is created
         scene = rt.Scene(big)
-    rays = np.concatenate([lq.camera_rays_cpu(cam, 24, 18), hq.source_b(desc, 51, 300), hq.source_c(desc, 3, 40)])
-    hits = hq.oracle_hits(desc, rays)
+    rays = np.concatenate([camera_rays_cpu(cam, 24, 18), source_b(desc, 51, 300), source_c(desc, 3, 40)])
+    hits = oracle_hits(desc, rays)
     states, why = replay(desc, rays, hits, 100.0)
     want = final(states)
     assert (states[0].kind == WALKING).sum() >= 100 and want[3] > 150 and (states[-1].casts >= 2).sum() > 0
@@ -498,7 +490,7 @@ def test_a_scene_walked_breadth_first(tmp_path):
 @pytest.mark.parametrize("depth", [0, 1, 5])
 def test_the_tree_loop_with_every_cast_opened(depth, per_ray):
     """6. trace_rays_levels(open_casts=True) == trace_rays, values and cast count, on a 64 x 48 camera frame"""
-    torch = _torch()
+    torch = torch_device()
     world = rt.reference_world()
     scene = rt.Scene(world)
     rays_t = rt.camera_rays(rt.reference_camera(), rt.Frame.full(64, 48, depth))
@@ -536,7 +528,7 @@ def test_the_tree_loop_with_every_cast_opened(depth, per_ray):
 def test_the_level_loop_with_every_cast_opened():
     """7. trace_rays_distributed_levels(open_casts=True) == trace_rays_distributed over two epochs: samples, flags, accumulated image,
     cast count and the downloaded generator records"""
-    torch = _torch()
+    torch = torch_device()
     world = rt.reference_world()
     scene = rt.Scene(world)
     rays_t = rt.camera_rays(rt.reference_camera(), rt.Frame.full(64, 48, 5))
@@ -572,7 +564,7 @@ def test_the_level_loop_with_every_cast_opened():
 def test_the_loop_in_a_graph(ref):
     """8. after one uncaptured call (rt_select_records' scratch on that stream) the loop is captured on a stream of its own, with its
     cast count, under a sync-debug mode that makes any host visit an error, and replayed twice with the same result"""
-    torch = _torch()
+    torch = torch_device()
     scene = rt.Scene(ref.world)
     states, why = ref.runs[100.0]
     n = ref.n

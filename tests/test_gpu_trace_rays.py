@@ -2,7 +2,6 @@
 channel equals the oracle's orc_ray_trace bit for bit (NaN equal to NaN, -0.0 not equal to +0.0) and the cast counts add up to the
 oracle's; a frame's camera rays give the frame (after + 0.0) and its cast count.  Each case runs on the persistent wavefront kernel
 (variant 18) and on the per-pixel kernel (variant 2)."""
-import contextlib
 import ctypes as C
 
 import numpy as np
@@ -12,31 +11,12 @@ import homework_18_graphics_raytracer_amd as rt
 from homework_18_graphics_raytracer_amd import _capi
 import _oracle
 import _scenes
-from test_gpu_ray_query import _tessellated, bounds, random_rays
+from _records import bounds, random_rays, tessellated_world, tile_order, torch_device
+from _trace_support import assert_same, trace, variant
 
 pytestmark = pytest.mark.gpu
 PATHS = [18, 2]
 HEADLINE_CASTS = 17756787  # World::cast evaluations of the 1920x1080 depth-8 frame (test_gpu_wavefront.py)
-
-
-def _torch():
-    import torch
-
-    torch.cuda.set_device(0)
-    return torch
-
-
-@contextlib.contextmanager
-def variant(v, budget=None):
-    lib = _capi.amd_lib()
-    _capi.check(lib.rt_set_variant(v))
-    if budget is not None:
-        _capi.check(lib.rt_set_wavefront_budget(budget))
-    try:
-        yield
-    finally:
-        _capi.check(lib.rt_set_variant(_capi.DEFAULT_VARIANT))
-        _capi.check(lib.rt_set_wavefront_budget(6))
 
 
 _oracle_cache = {}
@@ -64,21 +44,6 @@ def oracle_trace(desc, rays_t, depth, contribution, key=None):
     return rgb, total
 
 
-def trace(scene, rays, depth, contribution=1.0, **kw):
-    torch = _torch()
-    count = torch.zeros(1, dtype=torch.int64, device="cuda")
-    out = rt.trace_rays(scene, rays, depth, contribution, ray_count=count, **kw)
-    torch.cuda.synchronize()
-    return out.cpu().numpy(), int(count.item())
-
-
-def assert_same(got, want, what=""):
-    g, w = np.asarray(got, dtype=np.float32).reshape(-1, 3), np.asarray(want, dtype=np.float32).reshape(-1, 3)
-    same = (g.view(np.uint32) == w.view(np.uint32)) | (np.isnan(g) & np.isnan(w))
-    bad = np.argwhere(~same)
-    assert same.all(), f"{what}: {len(bad)} channels differ, first {bad[:3].tolist()}: got {g[bad[0][0]]} want {w[bad[0][0]]}"
-
-
 def check(scene, desc, rays, depth, contribution=1.0, key=None, what=""):
     got, casts = trace(scene, rays, depth, contribution)
     want, wcasts = oracle_trace(desc, rays, depth, contribution, key)
@@ -95,16 +60,6 @@ def ref():
     return world, desc, rt.Scene(world), rt.reference_camera(), random_rays(41, 10007, desc, centre, radius)
 
 
-def tile_order(cols, rows):
-    """position k of the Whitted kernels' slot order (8-row bands, column-major inside a band: 8x8 tiles) -> row-order index"""
-    s = np.arange(cols * rows, dtype=np.int64)
-    band = s // (cols * 8)
-    r = s - band * cols * 8
-    band_rows = np.minimum(8, rows - band * 8)
-    col = r // band_rows
-    return (band * 8 + (r - col * band_rows)) * cols + col
-
-
 # ---- 1. the camera's rays give the frame ----
 
 FRAMES = {"256x256d1": rt.Frame.full(256, 256, 1), "320x240d5": rt.Frame.full(320, 240, 5), "1080p_d8": rt.Frame.full(1920, 1080, 8),
@@ -114,7 +69,7 @@ FRAMES = {"256x256d1": rt.Frame.full(256, 256, 1), "320x240d5": rt.Frame.full(32
 @pytest.mark.parametrize("v", PATHS)
 @pytest.mark.parametrize("name", list(FRAMES))
 def test_camera_rays_give_the_frame(ref, name, v):
-    torch = _torch()
+    torch = torch_device()
     world, desc, scene, cam, _ = ref
     frame = FRAMES[name]
     with variant(v):
@@ -129,7 +84,7 @@ def test_camera_rays_give_the_frame(ref, name, v):
 
 @pytest.mark.parametrize("v", PATHS)
 def test_tile_ordered_rays_give_the_frame(ref, v):
-    torch = _torch()
+    torch = torch_device()
     world, desc, scene, cam, _ = ref
     for frame in (rt.Frame.full(320, 240, 5), rt.Frame.full(203, 97, 8)):  # a ragged last band too
         perm = torch.from_numpy(tile_order(frame.cols, frame.rows)).cuda()
@@ -175,7 +130,7 @@ def test_depths_and_contributions(ref, v):
 def edge_rays(desc):
     """rays in an axis-aligned triangle's plane (NaN distances), on sphere surfaces looking out, zero / tiny / huge / infinite / NaN
     directions from ordinary, infinite and NaN origins, face values above 2"""
-    torch = _torch()
+    torch = torch_device()
     g = np.random.default_rng(5)
     o, d, face = [], [], []
     for i in range(desc.n_triangles):
@@ -253,7 +208,7 @@ def negative_zero_world():
 @pytest.mark.parametrize("v", PATHS)
 def test_negative_zero_is_kept(v):
     """the value is ray_trace's own, not 0.0 + value: the -0.0 channels the oracle returns come back as -0.0"""
-    torch = _torch()
+    torch = torch_device()
     world = negative_zero_world()
     desc = world.desc()
     scene = rt.Scene(world)
@@ -287,7 +242,7 @@ def test_other_scenes(make, v):
 
 @pytest.mark.parametrize("v", PATHS)
 def test_equirectangular_panorama(ref, v):
-    torch = _torch()
+    torch = torch_device()
     world, desc, scene, cam, _ = ref
     W, H = 512, 256
     x = (torch.arange(W, device="cuda", dtype=torch.float32) + 0.5) / W * (2.0 * np.pi) - np.pi
@@ -313,7 +268,7 @@ def test_equirectangular_panorama(ref, v):
 def pwf_tiles_written(run, n):
     """run() with the wavefront kernel's per-tile record switched on (rt_diag_set_tile_cost): how many of the batch's ceil(n / 64)
     tiles it folded and wrote itself.  All of them: no arena overflowed and the trailing per-pixel launch had nothing to do"""
-    torch = _torch()
+    torch = torch_device()
     lib = _capi.amd_lib()
     tiles = (n + 63) // 64
     cost = torch.full((tiles,), -1, dtype=torch.int32, device="cuda")
@@ -341,7 +296,7 @@ def test_variant_18_renders_batches_in_the_wavefront_kernel(ref):
 def test_batch_that_overflows_the_arenas_is_finished_by_the_per_pixel_kernel(ref):
     """budget 1 on the 1080p camera rays: about 42 tiles per workgroup against arenas of 1 024 nodes, so the wavefront kernel gives up
     on some tiles and the trailing per-pixel launch renders the batch — the image and the cast count are still the frame's"""
-    torch = _torch()
+    torch = torch_device()
     world, desc, scene, cam, _ = ref
     frame = rt.Frame.full(1920, 1080, 8)
     count = torch.zeros(1, dtype=torch.int64, device="cuda")
@@ -375,7 +330,7 @@ def test_no_memory_for_the_arenas(ref):
 
 def test_batch_split_into_ray_bands(ref):
     """a large budget makes the arenas too small for the batch: several launches of whole 64-ray runs, the last one ragged"""
-    torch = _torch()
+    torch = torch_device()
     world, desc, scene, cam, _ = ref
     frame = rt.Frame.full(317, 313, 5)  # 99 221 rays: not a multiple of 64
     with variant(18, 2048):
@@ -389,7 +344,7 @@ def test_batch_split_into_ray_bands(ref):
 @pytest.mark.parametrize("v", PATHS)
 @pytest.mark.parametrize("cap", [0, 96])
 def test_breadth_first_scene(tmp_path, cap, v):
-    world = _tessellated(tmp_path, 2, True)
+    world = tessellated_world(tmp_path, 2, True)
     desc = world.desc()
     opts = {"RT_AMD_BFS_WALK_TRIANGLES": 1}
     if cap:
@@ -404,7 +359,7 @@ def test_breadth_first_scene(tmp_path, cap, v):
 # ---- 5. stream state ----
 
 def test_frames_and_batches_alternate_on_one_stream(ref):
-    torch = _torch()
+    torch = torch_device()
     world, desc, scene, cam, rays = ref
     fa = rt.Frame.full(256, 160, 8)
     wa, ca = _oracle.render_whitted(desc, cam, fa)
@@ -427,7 +382,7 @@ def test_frames_and_batches_alternate_on_one_stream(ref):
 
 
 def test_two_streams_at_once(ref):
-    torch = _torch()
+    torch = torch_device()
     world, desc, scene, cam, rays = ref
     x, y = rays[:4099].contiguous(), rays[4099:8198].contiguous()
     sa, sb = torch.cuda.Stream(), torch.cuda.Stream()
@@ -442,7 +397,7 @@ def test_two_streams_at_once(ref):
 
 
 def test_captured_call_replays_on_new_rays(ref):
-    torch = _torch()
+    torch = torch_device()
     world, desc, scene, cam, _ = ref
     centre, radius = bounds(desc)
     rays = random_rays(61, 1000, desc, centre, radius)
@@ -468,7 +423,7 @@ def test_captured_call_replays_on_new_rays(ref):
 
 
 def test_empty_batch_leaves_the_output_alone(ref):
-    torch = _torch()
+    torch = torch_device()
     world, desc, scene, cam, rays = ref
     empty = torch.empty((0, 11), dtype=torch.int32, device="cuda")
     assert tuple(rt.trace_rays(scene, empty, 5).shape) == (0, 3)

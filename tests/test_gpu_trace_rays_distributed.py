@@ -21,8 +21,8 @@ import homework_18_graphics_raytracer_amd as rt
 from homework_18_graphics_raytracer_amd import _capi
 import _oracle
 import _scenes
-from test_gpu_ray_query import _tessellated, bounds, oracle_hits, random_rays
-from test_oracle_rng import RAND_05_NEW_FROM_U64_0
+from _records import bounds, oracle_hits, random_rays, same_bits, tessellated_world, torch_device
+from _reference_support import RAND_05_NEW_FROM_U64_0
 
 pytestmark = pytest.mark.gpu
 L = _oracle._dist_lib()
@@ -35,13 +35,6 @@ def organisation(request):
     lib.rt_set_distributed_split(request.param)
     yield request.param
     lib.rt_set_distributed_split(-1)
-
-
-def _torch():
-    import torch
-
-    torch.cuda.set_device(0)
-    return torch
 
 
 @pytest.fixture(scope="module")
@@ -57,11 +50,6 @@ def seeds_of(frame):
     return (ys[:, None] * np.uint64(1 << 33) + xs[None, :]).reshape(-1)
 
 
-def same_bits(got, want):
-    g, w = np.asarray(got, dtype=np.float32), np.asarray(want, dtype=np.float32)
-    return (g.view(np.uint32) == w.view(np.uint32)) | (np.isnan(g) & np.isnan(w))
-
-
 def assert_same(got, want, what=""):
     g, w = np.asarray(got, dtype=np.float32).reshape(-1, 3), np.asarray(want, dtype=np.float32).reshape(-1, 3)
     same = same_bits(g, w)
@@ -75,7 +63,7 @@ def is_normal(v):
 
 def trace(scene, rays, depth, rng, n_epochs=1, accum=None, want_samples=True, **kw):
     """-> samples (n_epochs, N, 3), valid (n_epochs, N), casts"""
-    torch = _torch()
+    torch = torch_device()
     n = rays.shape[0]
     samples = torch.full((n_epochs, n, 3), 7.0, dtype=torch.float32, device="cuda") if want_samples else None
     valid = torch.full((n_epochs, n), 9, dtype=torch.uint8, device="cuda") if want_samples else None
@@ -181,7 +169,7 @@ def test_upload_is_the_inverse_of_download_and_the_device_continues_as_the_oracl
     rng.upload(adv)
     assert np.array_equal(rng.download(), adv)
     # ... and the device continues from there as the oracle does: two epochs of the camera's pass on these records
-    torch = _torch()
+    torch = torch_device()
     samples = torch.empty((2, frame.rows, frame.cols, 3), dtype=torch.float32, device="cuda")
     valid = torch.empty((2, frame.rows, frame.cols), dtype=torch.uint8, device="cuda")
     cnt = torch.zeros(1, dtype=torch.int64, device="cuda")
@@ -195,7 +183,7 @@ def test_upload_is_the_inverse_of_download_and_the_device_continues_as_the_oracl
 
 def test_render_distributed_refuses_a_seeded_rng_and_other_counts(ref):
     world, desc, scene, cam = ref
-    torch = _torch()
+    torch = torch_device()
     frame = rt.Frame.full(16, 8, 5)
     seeded = rt.Rng.seeded(seeds_of(frame))
     acc = torch.zeros((frame.rows, frame.cols, 3), dtype=torch.float32, device="cuda")
@@ -216,7 +204,7 @@ def test_render_distributed_refuses_a_seeded_rng_and_other_counts(ref):
 def test_argument_order_with_a_live_rng(ref):
     """the checks that follow the count (tests/test_trace_rays_distributed_abi.py pins the order up to it)"""
     world, desc, scene, cam = ref
-    torch = _torch()
+    torch = torch_device()
     lib = _capi.amd_lib()
     rng = rt.Rng.seeded([1, 2])
     rays = rt.camera_rays(cam, rt.Frame.full(2, 1, 5))
@@ -245,7 +233,7 @@ def test_argument_order_with_a_live_rng(ref):
 
 def composition(scene, desc, cam, frame, epochs, focus, blur, what, kinds=False, seeded=False):
     """E times rt_focus_rays + rt_trace_rays_distributed(n_epochs = 1) against orc_render_distributed, epoch by epoch"""
-    torch = _torch()
+    torch = torch_device()
     ws, wv, wc, wafter = oracle_epochs(desc, cam, frame, epochs, focus, blur)
     rng = rt.Rng.seeded(seeds_of(frame)) if seeded else rt.Rng(frame)
     before = _oracle.rng_init(frame)
@@ -288,7 +276,7 @@ def test_composition_on_random_and_degenerate_scenes(sq_seed, eye, seed):
 
 def test_composition_on_a_scene_walked_breadth_first(tmp_path):
     """forced by RT_AMD_BFS_WALK_TRIANGLES, as tests/test_gpu_scene_sizes.py does: distributed_kernel<.., BFS, RAYS>"""
-    world = _tessellated(tmp_path, 2, True)
+    world = tessellated_world(tmp_path, 2, True)
     with rt.options(RT_AMD_BFS_WALK_TRIANGLES=1):
         scene = rt.Scene(world)
         composition(scene, world.desc(), rt.reference_camera(), rt.Frame.full(64, 48, 5), 2, 3.0, 0.04, "bfs")
@@ -350,7 +338,7 @@ def _per_camera(ref):
     """per camera: rays of rt_focus_rays, the seeds, the oracle's records at the first level's draws and after the epoch, and its
     samples / flags / casts of that epoch"""
     world, desc, scene, cam0 = ref
-    torch = _torch()
+    torch = torch_device()
     parts = []
     for name, shift, frame, blur in CAMERAS:
         cam = rt.reference_camera()
@@ -370,7 +358,7 @@ def _per_camera(ref):
 @pytest.mark.parametrize("take", [None, 1000, 1], ids=["all", "not_a_multiple_of_64", "single_ray"])
 def test_a_permuted_batch_of_three_cameras_equals_the_per_camera_oracle(ref, take):
     world, desc, scene, cam0 = ref
-    torch = _torch()
+    torch = torch_device()
     parts = _per_camera(ref)
     rays = torch.cat([p[0] for p in parts])
     seeds, at_level, after = (np.concatenate([p[k] for p in parts]) for k in (1, 2, 3))
@@ -399,7 +387,7 @@ def test_a_permuted_batch_of_three_cameras_equals_the_per_camera_oracle(ref, tak
 @pytest.mark.parametrize("k", [3, 17])
 def test_k_epochs_in_one_call_equal_k_calls_of_one(ref, k):
     world, desc, scene, cam = ref
-    torch = _torch()
+    torch = torch_device()
     frame = rt.Frame.full(48, 36, 8)
     n = frame.rows * frame.cols
     rng = rt.Rng(frame)
@@ -434,7 +422,7 @@ def test_epochs_beyond_the_first_against_the_oracle(ref):
     """blur 0: the lens offsets are exactly +0.0, so the oracle's ray is the same in every epoch; its two lens draws per epoch are put
     into the streams on the host (download, orc_rng_draw_normal x 2, upload)"""
     world, desc, scene, cam = ref
-    torch = _torch()
+    torch = torch_device()
     k = 4
     frame = rt.Frame.full(48, 36, 5)
     ws, wv, wc, wafter = oracle_epochs(desc, cam, frame, k, 1.0, 0.0)
@@ -458,7 +446,7 @@ def test_epochs_beyond_the_first_against_the_oracle(ref):
 
 def test_switches_outputs_and_the_host_entry_point(ref):
     world, desc, scene, cam = ref
-    torch = _torch()
+    torch = torch_device()
     frame = rt.Frame.full(40, 30, 5)
     n = frame.rows * frame.cols
     k = 17  # more than one batch of 16
@@ -514,7 +502,7 @@ def test_switches_outputs_and_the_host_entry_point(ref):
 
 def test_profiling_covers_the_ray_entry_point(ref, organisation):
     world, desc, scene, cam = ref
-    torch = _torch()
+    torch = torch_device()
     lib = _capi.amd_lib()
     frame = rt.Frame.full(40, 30, 5)
     rng = rt.Rng(frame)

@@ -12,29 +12,14 @@ import pytest
 
 import homework_18_graphics_raytracer_amd as rt
 import _oracle
-import test_gpu_hit_queries as hq
+import _hit_support as hq
+from _records import dev, host, same_f32, source_b, tessellated_scene, torch_device, u32
 
 pytestmark = pytest.mark.gpu
 NONE = 0xFFFFFFFF
 F32 = np.float32
 T = F32(0.001)  # main.rs:467
 SENTINEL = 0x5A5A5A5A
-dev, same_f32 = hq.dev, hq.same_f32
-
-
-def _torch():
-    import torch
-
-    torch.cuda.set_device(0)
-    return torch
-
-
-def host(t):
-    return t.cpu().numpy()
-
-
-def u32(t):
-    return host(t).view(np.uint32)
 
 
 def _none_hits(n):
@@ -49,12 +34,12 @@ def _word(torch, value):
 
 @pytest.fixture(scope="module")
 def ref():
-    torch = _torch()
+    torch = torch_device()
     world = rt.reference_world()
     desc = world.desc()
     cam = rt.camera_rays(rt.reference_camera(), rt.Frame.full(160, 90, 5))
     torch.cuda.synchronize()
-    rays = np.concatenate([u32(cam), hq.source_b(desc, 33, 3000)])
+    rays = np.concatenate([u32(cam), source_b(desc, 33, 3000)])
     return world, desc, rt.Scene(world), rays
 
 
@@ -68,7 +53,7 @@ def _material_table(desc):
 
 @pytest.mark.parametrize("depth_left", [1, 0])
 def test_glue_kernels_against_numpy_on_every_branch(ref, depth_left):
-    torch = _torch()
+    torch = torch_device()
     _, desc, scene, rays = ref
     live_n = rays.shape[0]
     pad = 150
@@ -310,7 +295,7 @@ def _mixed(n, torch):
 @pytest.mark.parametrize("contribution", [1.0, 0.5, 0.0005, float("nan"), "per ray"])
 def test_levels_equal_trace_rays(ref, depth, contribution):
     """camera rays plus random rays, on a stream of their own, nothing read back and no synchronisation inside the loop"""
-    torch = _torch()
+    torch = torch_device()
     _, _, scene, rays = ref
     rays_t = dev(rays)
     n = rays.shape[0]
@@ -332,7 +317,7 @@ def test_levels_equal_trace_rays(ref, depth, contribution):
 @pytest.mark.parametrize("depth", [0, 5, 8])
 def test_levels_equal_the_oracle(ref, depth):
     """a sample of the rays against orc_ray_trace directly, with a contribution per ray"""
-    torch = _torch()
+    torch = torch_device()
     _, desc, scene, rays = ref
     g = np.random.default_rng(depth)
     rows = np.sort(g.choice(rays.shape[0], 2400, replace=False))
@@ -356,7 +341,7 @@ def test_levels_equal_the_oracle(ref, depth):
 # ---- 4. a level that is too small ----
 
 def test_overflow_is_counted_and_raised(ref):
-    torch = _torch()
+    torch = torch_device()
     _, _, scene, rays = ref
     rays_t = dev(rays)
     n = rays.shape[0]
@@ -377,13 +362,13 @@ def test_overflow_is_counted_and_raised(ref):
 # ---- 5. a scene walked breadth-first ----
 
 def test_levels_on_a_scene_walked_breadth_first(tmp_path):
-    torch = _torch()
-    big, cam = hq._tessellated(tmp_path, 4)
+    torch = torch_device()
+    big, cam = tessellated_scene(tmp_path, 4)
     desc = big.desc()
     assert desc.n_triangles == 36 * 4 ** 4 + 28  # above rt_scene_create's default switch (8 192 triangles)
     with rt.options(RT_AMD_BFS_WALK_TRIANGLES=8192):  # read when the scene is created
         scene = rt.Scene(big)
-    rays = np.concatenate([u32(rt.camera_rays(cam, rt.Frame.full(64, 48, 3))), hq.source_b(desc, 52, 1000)])
+    rays = np.concatenate([u32(rt.camera_rays(cam, rt.Frame.full(64, 48, 3))), source_b(desc, 52, 1000)])
     rays_t = dev(rays)
     n = rays.shape[0]
     want = _fused(scene, rays_t, 3, 1.0, torch)
@@ -403,11 +388,11 @@ def test_levels_on_a_scene_walked_breadth_first(tmp_path):
 # ---- 6. the whole loop in a graph ----
 
 def test_levels_in_a_graph(ref):
-    torch = _torch()
+    torch = torch_device()
     _, desc, scene, rays = ref
     rays_t = dev(rays)
     n = rays.shape[0]
-    other = np.concatenate([rays[5000:], hq.source_b(desc, 34, 5000)])
+    other = np.concatenate([rays[5000:], source_b(desc, 34, 5000)])
     assert other.shape[0] == n
     want, want_other = _fused(scene, rays_t, 5, 1.0, torch), _fused(scene, dev(other), 5, 1.0, torch)
     out = torch.full((n, 3), 7.0, dtype=torch.float32, device="cuda")

@@ -9,30 +9,11 @@ import homework_18_graphics_raytracer_amd as rt
 from homework_18_graphics_raytracer_amd import _capi
 import _oracle
 import _scenes
+from _trace_support import _check, _mismatches, PWF
 
 pytestmark = pytest.mark.gpu
 
-PWF = 16
 PATHS = [PWF | 2]
-
-
-def _check(world, cam, frame, budget=None, scene=None, variant=PWF | 2):
-    lib = _capi.amd_lib()
-    scene = scene or rt.Scene(world)
-    _capi.check(lib.rt_set_variant(variant))
-    if budget is not None:
-        _capi.check(lib.rt_set_wavefront_budget(budget))
-    try:
-        got, casts = rt.render_whitted_numpy(scene, cam, frame)
-    finally:
-        _capi.check(lib.rt_set_variant(_capi.DEFAULT_VARIANT))
-        _capi.check(lib.rt_set_wavefront_budget(6))
-    want, wcasts = _oracle.render_whitted(world.desc(), cam, frame)
-    g, w = got.view(np.uint32), want.view(np.uint32)
-    same = (g == w) | (np.isnan(got) & np.isnan(want))  # NaN payload/sign may differ between x86 and gfx950
-    assert same.all(), f"{(~same).sum()} channels differ; first {np.argwhere(~same)[:3].tolist()}"
-    assert casts == wcasts
-    return got
 
 
 @pytest.fixture(scope="module")
@@ -296,11 +277,6 @@ def test_no_memory_for_the_arenas_means_the_per_pixel_kernel(ref):
         _check(world, cam, rt.Frame.full(200, 150, 6), scene=rt.Scene(world))
     finally:
         rt.set_option("RT_AMD_DIAG_WS_REFUSE", None)
-
-
-def _mismatches(got, want):
-    same = (got.view(np.uint32) == want.view(np.uint32)) | (np.isnan(got) & np.isnan(want))  # as in _check
-    return int((~same).sum())
 
 
 def test_state_between_calls_on_one_stream(ref):

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import _scenes
+from _scenes import dealing
 
 CONE = 0xFFFFFFFF
 
@@ -22,21 +23,6 @@ DEALINGS = {
     (3, 15, 4): [43, 44, 45], (3, 16, 4): [46, 47, 48], (4, 7, 9): [28], (5, 4, 16): [19, 20], (5, 7, 9): [33, 34, 35],
     (5, 8, 8): [37, 38, 39, 40], (5, 10, 6): [50], (6, 9, 7): [51, 52, 53, 54], (7, 7, 9): [49], (7, 8, 8): [55, 56],
 }
-
-
-def dealing(count):
-    """(K, ck, R) of a clustered leaf of `count` triangles: of K = 1 .. 8 chunks of ck = ceil(count / K) triangles (no chunks of fewer
-    than 4 once there are two) the first whose pairs per full pass, R * count / K with R = floor(64 / ck), beat the best so far by 5 %"""
-    best, best_fill = None, 0.0
-    for k in range(1, 9):
-        ck = -(-count // k)
-        if ck < 4 and k > 1:
-            break
-        r = 64 // ck
-        fill = r * count / k
-        if fill > best_fill * 1.05:
-            best, best_fill = (k, ck, r), fill
-    return best
 
 
 def word(k, ck, r):

@@ -12,6 +12,7 @@ from PIL import Image
 
 import homework_18_graphics_raytracer_amd as rt
 import _oracle
+from _reference_support import PINS, progressive_loop, REFERENCE_EPOCHS
 
 
 @pytest.fixture(scope="module")
@@ -79,33 +80,6 @@ def test_glibc_libm_variant_is_close_but_not_closer(setup, ref_png):
 # outputs: IsaacRng::new_from_u64(y * 2^33 + x) and its output order, Uniform<f32>, the ziggurat Normal and its
 # regenerated tables, shoot_focus, weighted_select, scatter_hit, distributed_ray_trace, the is_normal filter, the
 # accumulation into the normalised image and the in-place renormalisation.
-
-REFERENCE_EPOCHS = 7
-PINS = [(0.04, "ref_out_distributed.png"), (0.02, "ref_out_small_blur.png")]
-
-
-_whitted_cache = {}
-
-
-def _whitted_normalised(world, camera, frame):
-    key = (frame.width, frame.height, frame.max_depth)
-    if key not in _whitted_cache:
-        img, _ = _oracle.render_whitted(world.desc(), camera, frame)
-        _oracle.post_process(img)
-        _whitted_cache[key] = img
-    return _whitted_cache[key].copy()
-
-
-def progressive_loop(world, camera, frame, blur, epochs, focus=3.0):
-    """main.rs:1087-1173 on the oracle; yields (k, u8 image) after the Whitted frame (k = 0) and after every epoch."""
-    img = _whitted_normalised(world, camera, frame)
-    yield 0, _oracle.encode_srgb8(img).astype(np.int32)
-    states = _oracle.rng_init(frame)
-    for k in range(1, epochs + 1):
-        s, v, _ = _oracle.render_distributed(world.desc(), camera, frame, states, 1, focus=focus, blur=blur)
-        img += np.where(v[0][..., None] != 0, s[0], np.float32(0))  # main.rs:1157-1167
-        _oracle.post_process(img)                                    # main.rs:1171
-        yield k, _oracle.encode_srgb8(img).astype(np.int32)
 
 
 @pytest.mark.parametrize("blur,name", PINS)

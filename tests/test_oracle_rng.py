@@ -10,6 +10,7 @@ import numpy as np
 
 import homework_18_graphics_raytracer_amd as rt
 import _oracle
+from _reference_support import RAND_05_NEW_FROM_U64_0
 
 L = _oracle._dist_lib()
 WORDS = L.orc_rng_state_words()
@@ -30,13 +31,6 @@ def test_layout_and_seed_mapping():
     assert len({bytes(s[:256].tobytes()) for s in st}) == 12
     fr2 = rt.Frame(640, 480, 5, 6, 9, 7, 10, 1)  # the single pixel (x=6, y=9)
     assert np.array_equal(_oracle.rng_init(fr2)[0], st[1 * 4 + 1])
-
-
-# rand 0.5.x src/prng/isaac.rs, #[test] fn test_isaac_new_uninitialized: IsaacRng::new_from_u64(0), 16 x next_u32()
-RAND_05_NEW_FROM_U64_0 = [
-    0x71D71FD2, 0xB54ADAE7, 0xD4788559, 0xC36129FA, 0x21DC1EA9, 0x3CB879CA, 0xD83B237F, 0xFA3CE5BD,
-    0x8D048509, 0xD82E9489, 0xDB452848, 0xCA20E846, 0x500F972E, 0x0EEFF940, 0x00D6B993, 0xBC12C17F,
-]
 
 
 def test_new_from_u64_zero_matches_rands_own_unit_test_vector():

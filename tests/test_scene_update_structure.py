@@ -2,8 +2,7 @@
 (rt_scene_describe_nodes) has a root above RT_REFIT_WAVE_MAX triangles that qualifies with a cone, two levels of inner nodes below
 it, and each case's description B has the tree the case is meant to reach."""
 import pytest
-
-import test_gpu_scene_update as su
+import _scene_update_support as su
 
 
 @pytest.fixture(scope="module")

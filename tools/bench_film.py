@@ -19,12 +19,12 @@ sources the library was built from (_capi.sources_sha256), which ties the figure
 """
 import argparse
 import json
-import subprocess
 import sys
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
+import _bench
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--steps", type=int, default=7, help="timed windows per form")
@@ -41,29 +41,13 @@ a = ap.parse_args()
 if not a.child:
     from homework_18_graphics_raytracer_amd import _capi
 
-    result = {"tool": "bench_film", "sources_sha256": _capi.sources_sha256()}
-    try:
-        result["commit"] = subprocess.run(["git", "-C", str(ROOT), "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip() or None
-    except OSError:
-        result["commit"] = None
-    for case in ("tent", "mitchell", "rays"):
-        cmd = ["timeout", "-k", "10", str(a.step_timeout), sys.executable, __file__, "--child", case, "--steps", str(a.steps), "--warmup", str(a.warmup),
-               "--launches", str(a.launches), "--width", str(a.width), "--height", str(a.height), "--hbm-tb-per-s", str(a.hbm_tb_per_s)]
-        proc = subprocess.run(cmd, capture_output=True, text=True)
-        if proc.returncode != 0:
-            sys.stderr.write(proc.stdout + proc.stderr)
-            sys.exit(f"{case}: exit status {proc.returncode}; nothing more is started")
-        result[case] = json.loads(proc.stdout.strip().splitlines()[-1])
-    line = json.dumps(result)
-    Path(a.out).parent.mkdir(parents=True, exist_ok=True)
-    with open(a.out, "a") as f:
-        f.write(line + "\n")
-    print(line)
+    _bench.run_cases("bench_film", ("tent", "mitchell", "rays"),
+                     lambda case: ["--child", case] + _bench.options(a, "steps", "warmup", "launches", "width", "height", "hbm_tb_per_s"), a.step_timeout, a.out,
+                     header={"sources_sha256": _capi.sources_sha256()})
     sys.exit(0)
 
 import ctypes as C
 
-import numpy as np
 import torch
 
 import homework_18_graphics_raytracer_amd as rt
@@ -104,7 +88,7 @@ def alternate(forms):
                 for name in ms:
                     ms[name].append(t[name])
     torch.cuda.synchronize()
-    return {name: {"ms_median": round(float(np.median(v)), 4), "ms_spread": round(max(v) - min(v), 4), "ms_min": round(min(v), 4)} for name, v in ms.items()}
+    return {name: _bench.summary(v, spread=True) for name, v in ms.items()}
 
 
 res = {"device": torch.cuda.get_device_name(0), "rows": rows, "cols": cols, "steps": a.steps, "warmup": a.warmup, "launches_per_window": a.launches}

@@ -24,6 +24,7 @@ from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
+import _bench
 import numpy as np
 import torch
 
@@ -38,59 +39,6 @@ ap.add_argument("--out", default=str(ROOT / "profiles" / "hit_query_bench.jsonl"
 a = ap.parse_args()
 
 torch.cuda.set_device(0)
-
-
-def random_rays(seed, n, centre, radius):
-    g = np.random.default_rng(seed)
-    scale = np.where(g.random(n) < 0.5, g.uniform(0.0, 1.0, n), g.uniform(1.0, 2.0, n)) * radius
-    u = g.normal(size=(n, 3))
-    origins = centre + u / np.linalg.norm(u, axis=1, keepdims=True) * scale[:, None]
-    d = centre + g.normal(0.0, radius * 0.5, (n, 3)) - origins
-    d /= np.maximum(np.linalg.norm(d, axis=1, keepdims=True), 1e-12)
-    dev = lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).cuda()
-    return rt.make_rays(dev(origins), dev(d))
-
-
-def bounds(desc):
-    p = [v.position[:] for i in range(desc.n_triangles) for v in desc.triangles[i].vertices]
-    for i in range(desc.n_spheres):
-        s = desc.spheres[i]
-        p += [list(np.asarray(s.center[:]) + s.radius), list(np.asarray(s.center[:]) - s.radius)]
-    p = np.asarray(p, dtype=np.float64)
-    c = (p.min(0) + p.max(0)) / 2
-    return c, float(np.linalg.norm(p - c, axis=1).max())
-
-
-def tile_order(cols, rows):
-    """position k of the Whitted kernels' slot order -> the row-order index of its pixel"""
-    s = np.arange(cols * rows, dtype=np.int64)
-    band = s // (cols * 8)
-    r = s - band * cols * 8
-    band_rows = np.minimum(8, rows - band * 8)
-    col = r // band_rows
-    return (band * 8 + (r - col * band_rows)) * cols + col
-
-
-def one(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1)
-
-
-def alternated(cases, steps, warmup):
-    """every case once per round, `steps` timed rounds after `warmup` untimed ones; returns per case the ms of every timed call"""
-    for _ in range(warmup):
-        for fn in cases.values():
-            fn()
-    torch.cuda.synchronize()
-    ms = {k: [] for k in cases}
-    for _ in range(steps):
-        for k, fn in cases.items():
-            ms[k].append(one(fn))
-    return ms
 
 
 count = torch.zeros(1, dtype=torch.int64, device="cuda")
@@ -126,7 +74,7 @@ def bench(scene, rays):
         "reflect": lambda: rt.reflect_rays(hits, rays, out=refl),
         "trace0": lambda: rt.trace_rays(scene, rays, 0, out=rgb["trace0"]),
     }
-    ms = alternated(cases, a.steps, a.warmup)
+    ms = _bench.alternate(cases, a.warmup, a.steps)
     casts = {"cast": n, "shade_pairs": casts_of(lambda c: shade("pairs", c)), "shade_uniform": casts_of(uniform(lambda c: shade("uniform", c))),
              "refract_pairs": casts_of(refract), "refract_uniform": casts_of(uniform(refract)), "reflect": 0,
              "trace0": casts_of(lambda c: rt.trace_rays(scene, rays, 0, out=rgb["trace0"], ray_count=c))}
@@ -143,11 +91,10 @@ def bench(scene, rays):
         r["shade" + tag + "_over_trace0"] = round(r[key]["ms_median"] / r["trace0"]["ms_median"], 4)
     r["shade_winner"] = "pairs" if r["shade_pairs"]["ms_median"] <= r["shade_uniform"]["ms_median"] else "uniform"
     r["refract_winner"] = "pairs" if r["refract_pairs"]["ms_median"] <= r["refract_uniform"]["ms_median"] else "uniform"
-    same = lambda x, y: ((x.view(torch.int32) == y.view(torch.int32)) | (x.isnan() & y.isnan()))
-    r["shade_variants_identical"] = bool(same(rgb["pairs"], rgb["uniform"]).all()) and casts["shade_pairs"] == casts["shade_uniform"]
+    r["shade_variants_identical"] = _bench.same(rgb["pairs"], rgb["uniform"]) and casts["shade_pairs"] == casts["shade_uniform"]
     # trace0 is black by rule on glass (shade contribution below THRESHOLD) and on misses; elsewhere it is get_shade of the same hit
     lit = (rgb["trace0"].view(torch.int32) != 0).any(dim=1)
-    r["shade_equals_trace0_where_lit"] = bool(same(rgb["pairs"][lit], rgb["trace0"][lit]).all())
+    r["shade_equals_trace0_where_lit"] = _bench.same(rgb["pairs"][lit], rgb["trace0"][lit])
     return r
 
 
@@ -157,12 +104,12 @@ scene = rt.Scene(world)
 W, H = 1920, 1080
 rows = rt.camera_rays(rt.reference_camera(), rt.Frame.full(W, H, 0))
 result["rows"] = bench(scene, rows)
-tiles = rows[torch.from_numpy(tile_order(W, H)).cuda()].contiguous()
+tiles = rows[torch.from_numpy(_bench.tile_order(W, H)).cuda()].contiguous()
 del rows
 result["tiles"] = bench(scene, tiles)
 del tiles
-centre, radius = bounds(world.desc())
-result["random"] = bench(scene, random_rays(a.seed, a.random_rays, centre, radius))
+centre, radius = _bench.bounds(world.desc())
+result["random"] = bench(scene, _bench.random_rays(a.seed, a.random_rays, centre, radius))
 line = json.dumps(result)
 Path(a.out).parent.mkdir(parents=True, exist_ok=True)
 with open(a.out, "a") as f:

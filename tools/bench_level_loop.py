@@ -15,12 +15,12 @@ records that the indexed cast actually casts.  No figure is a gate.  Appends one
 """
 import argparse
 import json
-import subprocess
 import sys
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
+import _bench
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--steps", type=int, default=5, help="timed epochs per form")
@@ -36,27 +36,8 @@ a = ap.parse_args()
 STEPS = ("primary", "random")
 
 if a.step is None:
-    result = {"tool": "bench_level_loop", "steps": a.steps, "warmup": a.warmup, "frame": [a.width, a.height], "depth": a.depth}
-    try:
-        result["commit"] = subprocess.run(["git", "-C", str(ROOT), "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip() or None
-    except OSError:
-        result["commit"] = None
-    for step in STEPS:
-        cmd = [sys.executable, __file__, "--step", step] + [x for k in ("steps", "warmup", "depth", "width", "height", "random_rays")
-                                                            for x in ("--" + k.replace("_", "-"), str(getattr(a, k)))]
-        try:
-            proc = subprocess.run(cmd, capture_output=True, text=True, timeout=a.step_timeout)
-        except subprocess.TimeoutExpired:
-            sys.exit(f"step {step}: no result within {a.step_timeout} s; nothing more is started")
-        if proc.returncode != 0:
-            sys.stderr.write(proc.stdout + proc.stderr)
-            sys.exit(f"step {step}: exit status {proc.returncode}; nothing more is started")
-        result[step] = json.loads(proc.stdout.strip().splitlines()[-1])
-    line = json.dumps(result)
-    Path(a.out).parent.mkdir(parents=True, exist_ok=True)
-    with open(a.out, "a") as f:
-        f.write(line + "\n")
-    print(line)
+    _bench.run_cases("bench_level_loop", STEPS, lambda step: ["--step", step] + _bench.options(a, "steps", "warmup", "depth", "width", "height", "random_rays"),
+                     a.step_timeout, a.out, header={"steps": a.steps, "warmup": a.warmup, "frame": [a.width, a.height], "depth": a.depth})
     sys.exit(0)
 
 import numpy as np
@@ -68,24 +49,6 @@ torch.cuda.set_device(0)
 world = rt.reference_world()
 scene = rt.Scene(world)
 camera = rt.reference_camera()
-
-
-def one(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1)
-
-
-def stats(ms, records):
-    med = float(np.median(ms))
-    return {"ms_median": round(med, 4), "ms_min": round(min(ms), 4), "mrecords_per_s": round(records / med / 1e3, 1)}
-
-
-def same(x, y):
-    return bool(((x.view(torch.int32) == y.view(torch.int32)) | (x.isnan() & y.isnan())).all())
 
 
 def masked(hits, mask):
@@ -171,12 +134,12 @@ def by_torch():
 ms = {"levels": [], "call": [], "torch": []}
 identical = True
 for k in range(a.warmup + a.steps):
-    t = {"levels": one(by_levels), "call": one(by_call), "torch": one(by_torch)}
-    identical = identical and same(samples["levels"][0], samples["call"][0]) and same(got[0], samples["call"][0])
+    t = {"levels": _bench.time_ms(by_levels), "call": _bench.time_ms(by_call), "torch": _bench.time_ms(by_torch)}
+    identical = identical and _bench.same(samples["levels"][0], samples["call"][0]) and _bench.same(got[0], samples["call"][0])
     if k >= a.warmup:
         for name in ms:
             ms[name].append(t[name])
-out = {"rays": N, "epoch_device_loop": stats(ms["levels"], N), "epoch_fused_call": stats(ms["call"], N), "epoch_torch_glued": stats(ms["torch"], N)}
+out = {"rays": N, "epoch_device_loop": _bench.summary(ms["levels"], rate=("mrecords_per_s", N)), "epoch_fused_call": _bench.summary(ms["call"], rate=("mrecords_per_s", N)), "epoch_torch_glued": _bench.summary(ms["torch"], rate=("mrecords_per_s", N))}
 out["device_loop_over_fused_call"] = round(out["epoch_device_loop"]["ms_median"] / out["epoch_fused_call"]["ms_median"], 3)
 out["device_loop_over_torch_glued"] = round(out["epoch_device_loop"]["ms_median"] / out["epoch_torch_glued"]["ms_median"], 3)
 out["cast_share_per_level"] = shares  # of the first epoch: records the indexed cast casts / records, level 1 .. depth

@@ -18,13 +18,13 @@ figure is a gate.  Appends one JSON line with the commit to --out and prints it.
 """
 import argparse
 import json
-import subprocess
 import sys
 import tempfile
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
+import _bench
 
 STEPS = ("tiles", "random", "spherized4", "spherized6")
 ap = argparse.ArgumentParser()
@@ -38,24 +38,8 @@ ap.add_argument("--out", default=str(ROOT / "profiles" / "light_query_bench.json
 a = ap.parse_args()
 
 if a.step is None:
-    result = {"tool": "bench_light_queries", "steps": a.steps, "warmup": a.warmup}
-    try:
-        result["commit"] = subprocess.run(["git", "-C", str(ROOT), "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip() or None
-    except OSError:
-        result["commit"] = None
-    for step in a.cases:
-        cmd = ["timeout", "-k", "10", str(a.step_timeout), sys.executable, __file__, "--step", step, "--steps", str(a.steps), "--warmup", str(a.warmup),
-               "--random-rays", str(a.random_rays)]
-        proc = subprocess.run(cmd, capture_output=True, text=True)
-        if proc.returncode != 0:
-            sys.stderr.write(proc.stdout + proc.stderr)
-            sys.exit(f"case {step}: exit status {proc.returncode}; nothing more is started")
-        result[step] = json.loads(proc.stdout.strip().splitlines()[-1])
-    line = json.dumps(result)
-    Path(a.out).parent.mkdir(parents=True, exist_ok=True)
-    with open(a.out, "a") as f:
-        f.write(line + "\n")
-    print(line)
+    _bench.run_cases("bench_light_queries", a.cases, lambda case: ["--step", case] + _bench.options(a, "steps", "warmup", "random_rays"), a.step_timeout, a.out,
+                     header={"steps": a.steps, "warmup": a.warmup})
     sys.exit(0)
 
 import numpy as np
@@ -66,36 +50,10 @@ import homework_18_graphics_raytracer_amd as rt
 torch.cuda.set_device(0)
 
 
-def tile_order(cols, rows):
-    """position k of the Whitted kernels' slot order (8-row bands, column-major inside a band) -> the row-order index of its pixel"""
-    s = np.arange(cols * rows, dtype=np.int64)
-    band = s // (cols * 8)
-    r = s - band * cols * 8
-    band_rows = np.minimum(8, rows - band * 8)
-    col = r // band_rows
-    return (band * 8 + (r - col * band_rows)) * cols + col
-
-
-def one(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1)
-
-
-def same(x, y):
-    return bool(((x.view(torch.int32) == y.view(torch.int32)) | (x.isnan() & y.isnan())).all())
-
-
 with tempfile.TemporaryDirectory() as tmp:
     if a.step.startswith("spherized"):
         level = int(a.step[-1])
-        obj = Path(tmp) / f"dodecahedron_l{level}s.obj"
-        cmd = [sys.executable, str(ROOT / "tools" / "make_tessellated_obj.py"), rt.DEFAULT_OBJ, str(obj), "--levels", str(level), "--spherize"]
-        subprocess.run(cmd, check=True, capture_output=True)
-        world = rt.reference_world(str(obj))
+        world = _bench.tessellated_world(tmp, level, True)
         with rt.options(RT_AMD_BFS_WALK_TRIANGLES=8192):  # the library's default switch, set here so that no environment moves it
             scene = rt.Scene(world)
         rays = rt.camera_rays(rt.reference_camera(), rt.Frame.full(480, 270, 0))
@@ -104,7 +62,7 @@ with tempfile.TemporaryDirectory() as tmp:
         scene = rt.Scene(world)
         if a.step == "tiles":
             rows = rt.camera_rays(rt.reference_camera(), rt.Frame.full(1920, 1080, 0))
-            rays = rows[torch.from_numpy(tile_order(1920, 1080)).cuda()].contiguous()
+            rays = rows[torch.from_numpy(_bench.tile_order(1920, 1080)).cuda()].contiguous()
         else:
             g = np.random.default_rng(7)
             desc = world.desc()
@@ -150,8 +108,8 @@ with torch.cuda.stream(stream):
     for k in range(a.warmup + a.steps):
         for c in count.values():
             c.zero_()
-        t = {name: one(fn) for name, fn in calls.items()}
-        identical = identical and all(same(out[name], out["shade_pairs"]) for name in forms[1:])
+        t = {name: _bench.time_ms(fn) for name, fn in calls.items()}
+        identical = identical and all(_bench.same(out[name], out["shade_pairs"]) for name in forms[1:])
         identical = identical and len({int(c.item()) for c in count.values()}) == 1
         if k >= a.warmup:
             for name in ms:
@@ -159,8 +117,7 @@ with torch.cuda.stream(stream):
 res = {"triangles": triangles, "records": N, "hits": int(rt.Hits(hits).hit.sum().item()), "lights": scene.n_lights,
        "shadow_casts": int(count["shade_pairs"].item())}
 for name, v in ms.items():
-    med = float(np.median(v))
-    res[name] = {"ms_median": round(med, 4), "ms_min": round(min(v), 4), "mcasts_per_s": round(res["shadow_casts"] / med / 1e3, 1)}
+    res[name] = _bench.summary(v, rate=("mcasts_per_s", res["shadow_casts"]))
 best = min(res["shade_pairs"]["ms_median"], res["shade_uniform"]["ms_median"])
 res["fused_winner"] = "pairs" if res["shade_pairs"]["ms_median"] <= res["shade_uniform"]["ms_median"] else "uniform"
 res["loop_over_fused"] = round(res["loop"]["ms_median"] / best, 3)

@@ -15,12 +15,12 @@ line with the commit to --out and prints it.
 """
 import argparse
 import json
-import subprocess
 import sys
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
+import _bench
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--steps", type=int, default=7, help="timed calls per form")
@@ -32,23 +32,8 @@ ap.add_argument("--out", default=str(ROOT / "profiles" / "material_query_bench.j
 a = ap.parse_args()
 
 if not a.child:
-    result = {"tool": "bench_material_queries"}
-    try:
-        result["commit"] = subprocess.run(["git", "-C", str(ROOT), "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip() or None
-    except OSError:
-        result["commit"] = None
-    cmd = ["timeout", "-k", "10", str(a.step_timeout), sys.executable, __file__, "--child", "--steps", str(a.steps), "--warmup", str(a.warmup),
-           "--records", str(a.records)]
-    proc = subprocess.run(cmd, capture_output=True, text=True)
-    if proc.returncode != 0:
-        sys.stderr.write(proc.stdout + proc.stderr)
-        sys.exit(f"exit status {proc.returncode}; nothing more is started")
-    result.update(json.loads(proc.stdout.strip().splitlines()[-1]))
-    line = json.dumps(result)
-    Path(a.out).parent.mkdir(parents=True, exist_ok=True)
-    with open(a.out, "a") as f:
-        f.write(line + "\n")
-    print(line)
+    _bench.run_cases("bench_material_queries", ("measurement",), lambda case: ["--child"] + _bench.options(a, "steps", "warmup", "records"), a.step_timeout, a.out,
+                     merge=True)
     sys.exit(0)
 
 import numpy as np
@@ -98,19 +83,10 @@ calls = {
 }
 
 
-def one(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1)
-
-
 ms = {k: [] for k in calls}
 with torch.cuda.stream(stream):
     for k in range(a.warmup + a.steps):
-        t = {name: one(fn) for name, fn in calls.items()}
+        t = {name: _bench.time_ms(fn) for name, fn in calls.items()}
         if k >= a.warmup:
             for name in ms:
                 ms[name].append(t[name])
@@ -128,13 +104,13 @@ for l in range(L):
     on = lit.view(L, N)[l] != 0
     for probe, terms in ((probe_d, terms_d), (probe_s, terms_s)):
         x, y = (probe[l] * color)[on], terms.view(L, N, 3)[l][on]
-        identical = identical and bool(((x.view(torch.int32) == y.view(torch.int32)) | (x.isnan() & y.isnan())).all())
+        identical = identical and _bench.same(x, y)
     checked += int(on.sum().item())
 
 res = {"device": torch.cuda.get_device_name(0), "triangles": desc.n_triangles, "records": N, "hits": int(rt.Hits(hits).hit.sum().item()),
        "lights": L, "lit_pairs": int((lit != 0).sum().item()), "steps": a.steps, "warmup": a.warmup}
 for name, v in ms.items():
-    res[name] = {"ms_median": round(float(np.median(v)), 4), "ms_spread": round(max(v) - min(v), 4), "ms_min": round(min(v), 4)}
+    res[name] = _bench.summary(v, spread=True)
 res["probe_over_light_terms"] = round(res["probe_surfaces"]["ms_median"] / res["light_terms"]["ms_median"], 3)
 res["identical_where_lit"] = identical
 res["pairs_checked"] = checked

@@ -18,13 +18,13 @@ import argparse
 import ctypes as C
 import json
 import signal
-import subprocess
 import sys
 import tempfile
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
+import _bench
 import numpy as np
 import torch
 
@@ -59,44 +59,14 @@ def desc_with(desc, raw):
     return out
 
 
-def random_rays(seed, n, centre, radius):  # tools/bench_trace_rays.py's
-    g = np.random.default_rng(seed)
-    scale = np.where(g.random(n) < 0.5, g.uniform(0.0, 1.0, n), g.uniform(1.0, 2.0, n)) * radius
-    u = g.normal(size=(n, 3))
-    origins = centre + u / np.linalg.norm(u, axis=1, keepdims=True) * scale[:, None]
-    d = centre + g.normal(0.0, radius * 0.5, (n, 3)) - origins
-    d /= np.maximum(np.linalg.norm(d, axis=1, keepdims=True), 1e-12)
-    dev = lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).cuda()
-    return rt.make_rays(dev(origins), dev(d))
-
-
-def one(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1)
-
-
 def alternated(cases, steps, warmup):
-    for _ in range(warmup):
-        for fn in cases.values():
-            fn()
-    torch.cuda.synchronize()
-    ms = {k: [] for k in cases}
-    for _ in range(steps):
-        for k, fn in cases.items():
-            ms[k].append(one(fn))
+    ms = _bench.alternate(cases, warmup, steps)
     return ({k: round(float(np.median(v)), 4) for k, v in ms.items()}, {k: round(float(max(v) - min(v)), 4) for k, v in ms.items()})
 
 
 def measure(level):
     with tempfile.TemporaryDirectory() as tmp:
-        obj = Path(tmp) / f"d{level}.obj"
-        subprocess.run([sys.executable, str(ROOT / "tools" / "make_tessellated_obj.py"), rt.DEFAULT_OBJ, str(obj), "--levels", str(level)],
-                       check=True, capture_output=True)
-        world = rt.reference_world(str(obj))
+        world = _bench.tessellated_world(tmp, level, False)
     base = world.desc()
     lo, hi = world.bounds()
     natural = raw_of(base)
@@ -117,7 +87,7 @@ def measure(level):
     scenes = {k: rt.Scene(d) for k, d in descs.items()}
     p = natural[:, 1:].copy().view(np.float32).reshape(n, 3, 8)[:, :, :3].reshape(-1, 3).astype(np.float64)
     centre = (p.min(0) + p.max(0)) / 2
-    rays = random_rays(a.seed + level, a.rays, centre, float(np.linalg.norm(p - centre, axis=1).max()))
+    rays = _bench.random_rays(a.seed + level, a.rays, centre, float(np.linalg.norm(p - centre, axis=1).max()))
     camera, frame = rt.reference_camera(), rt.Frame.full(a.width, a.height, a.depth)
     hits = {k: torch.empty((a.rays, 13), dtype=torch.int32, device="cuda") for k in scenes}
     image = {k: torch.empty((frame.rows, frame.cols, 3), dtype=torch.float32, device="cuda") for k in scenes}

@@ -16,13 +16,13 @@ The ordered results are checked against the plain ones bit for bit, cast counts 
 loses is printed like the others.  Prints one JSON line per ray set and appends them to --out when given."""
 import argparse
 import json
-import subprocess
 import sys
 import tempfile
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
+import _bench
 import numpy as np
 import torch
 
@@ -42,46 +42,8 @@ a = ap.parse_args()
 torch.cuda.set_device(0)
 
 
-def random_rays(seed, n, centre, radius):  # tools/bench_trace_rays.py's
-    g = np.random.default_rng(seed)
-    scale = np.where(g.random(n) < 0.5, g.uniform(0.0, 1.0, n), g.uniform(1.0, 2.0, n)) * radius
-    u = g.normal(size=(n, 3))
-    origins = centre + u / np.linalg.norm(u, axis=1, keepdims=True) * scale[:, None]
-    d = centre + g.normal(0.0, radius * 0.5, (n, 3)) - origins
-    d /= np.maximum(np.linalg.norm(d, axis=1, keepdims=True), 1e-12)
-    dev = lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).cuda()
-    return rt.make_rays(dev(origins), dev(d))
-
-
-def ball(world):  # tools/bench_trace_rays.py's bounds: the same rays as there
-    desc = world.desc()
-    p = [v.position[:] for i in range(desc.n_triangles) for v in desc.triangles[i].vertices]
-    for i in range(desc.n_spheres):
-        s = desc.spheres[i]
-        p += [list(np.asarray(s.center[:]) + s.radius), list(np.asarray(s.center[:]) - s.radius)]
-    p = np.asarray(p, dtype=np.float64)
-    c = (p.min(0) + p.max(0)) / 2
-    return c, float(np.linalg.norm(p - c, axis=1).max())
-
-
-def one(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1)
-
-
 def alternated(cases, steps, warmup):
-    for _ in range(warmup):
-        for fn in cases.values():
-            fn()
-    torch.cuda.synchronize()
-    ms = {k: [] for k in cases}
-    for _ in range(steps):
-        for k, fn in cases.items():
-            ms[k].append(one(fn))
+    ms = _bench.alternate(cases, warmup, steps)
     return {k: round(float(np.median(v)), 4) for k, v in ms.items()}
 
 
@@ -135,15 +97,12 @@ measure("b_rows", world, scene, rows, a.steps)
 perm = torch.from_numpy(np.random.default_rng(a.seed).permutation(W * H)).cuda()
 measure("b_rows_permuted", world, scene, rows[perm].contiguous(), a.steps)
 del rows
-centre, radius = ball(world)
-measure("d_random", world, scene, random_rays(a.seed, a.random_rays, centre, radius), a.steps)
+centre, radius = _bench.bounds(world.desc())
+measure("d_random", world, scene, _bench.random_rays(a.seed, a.random_rays, centre, radius), a.steps)
 
 if not a.no_large:
     with tempfile.TemporaryDirectory() as tmp:
-        obj = Path(tmp) / "d6.obj"
-        subprocess.run([sys.executable, str(ROOT / "tools" / "make_tessellated_obj.py"), rt.DEFAULT_OBJ, str(obj), "--levels", "6"], check=True,
-                       capture_output=True)
-        big = rt.reference_world(str(obj))
+        big = _bench.tessellated_world(tmp, 6, False)
     bscene = rt.Scene(big)
-    bcentre, bradius = ball(big)
-    measure("large_random", big, bscene, random_rays(a.seed + 1, a.large_rays, bcentre, bradius), a.steps)
+    bcentre, bradius = _bench.bounds(big.desc())
+    measure("large_random", big, bscene, _bench.random_rays(a.seed + 1, a.large_rays, bcentre, bradius), a.steps)

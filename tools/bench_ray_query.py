@@ -18,13 +18,13 @@ word for word on every batch (`agree`).  Prints one JSON line.  Kernel times: ru
 """
 import argparse
 import json
-import subprocess
 import sys
 import tempfile
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
+import _bench
 import numpy as np
 import torch
 
@@ -53,26 +53,12 @@ torch.cuda.set_device(0)
 
 def random_rays(seed, n, centre, radius, n_triangles, n_spheres, spread):
     g = np.random.default_rng(seed)
-    scale = np.where(g.random(n) < 0.5, g.uniform(0.0, 1.0, n), g.uniform(1.0, spread, n)) * radius
-    u = g.normal(size=(n, 3))
-    origins = centre + u / np.linalg.norm(u, axis=1, keepdims=True) * scale[:, None]
-    d = centre + g.normal(0.0, radius * 0.5, (n, 3)) - origins
-    d /= np.maximum(np.linalg.norm(d, axis=1, keepdims=True), 1e-12)
+    origins, d = _bench.ray_arrays(g, n, centre, radius, spread)
     kind = g.choice([-1, rt.SPHERE, rt.TRIANGLE], n, p=[0.4, 0.2, 0.4])
     index = np.where(kind == rt.TRIANGLE, g.integers(0, n_triangles + 2, n), g.integers(0, n_spheres + 2, n))
     dev = lambda x, dt: torch.from_numpy(np.ascontiguousarray(x, dtype=dt)).cuda()
     return rt.make_rays(dev(origins, np.float32), dev(d, np.float32), dev(g.integers(0, 3, n), np.int64), dev(kind, np.int64),
                         dev(index, np.int64), dev(g.integers(0, 3, n), np.int64))
-
-
-def bounds(desc):
-    p = [v.position[:] for i in range(desc.n_triangles) for v in desc.triangles[i].vertices]
-    for i in range(desc.n_spheres):
-        s = desc.spheres[i]
-        p += [list(np.asarray(s.center[:]) + s.radius), list(np.asarray(s.center[:]) - s.radius)]
-    p = np.asarray(p, dtype=np.float64)
-    c = (p.min(0) + p.max(0)) / 2
-    return c, float(np.linalg.norm(p - c, axis=1).max())
 
 
 def timed(fn, steps, warmup):
@@ -138,7 +124,7 @@ result["camera_rays_1080p_ms_median"] = round(float(np.median(c_ms)), 4)
 result["primary"] = summary("primary", primary.shape[0], *ab(scene, primary, a.steps, a.warmup))
 del primary
 
-centre, radius = bounds(desc)
+centre, radius = _bench.bounds(desc)
 for key, spread in (("random", 2.0), ("random_far", 4.0)):
     rays = random_rays(a.seed, a.random_rays, centre, radius, desc.n_triangles, desc.n_spheres, spread)
     result[key] = summary(key, rays.shape[0], *ab(scene, rays, a.steps, a.warmup))
@@ -146,13 +132,10 @@ for key, spread in (("random", 2.0), ("random_far", 4.0)):
 
 if not a.no_large:
     with tempfile.TemporaryDirectory() as tmp:
-        obj = Path(tmp) / "d6s.obj"
-        subprocess.run([sys.executable, str(ROOT / "tools" / "make_tessellated_obj.py"), rt.DEFAULT_OBJ, str(obj), "--levels", "6", "--spherize"],
-                       check=True, capture_output=True)
-        big = rt.reference_world(str(obj))
+        big = _bench.tessellated_world(tmp, 6, True)
     bdesc = big.desc()
     bscene = rt.Scene(big)
-    bcentre, bradius = bounds(bdesc)
+    bcentre, bradius = _bench.bounds(bdesc)
     for key, spread in (("large", 2.0), ("large_far", 4.0)):
         rays = random_rays(a.seed + 1, a.large_rays, bcentre, bradius, bdesc.n_triangles, bdesc.n_spheres, spread)
         result[key] = summary(key, rays.shape[0], *ab(bscene, rays, a.large_steps, 1))

@@ -20,13 +20,13 @@ each other bit for bit (values and cast count) first.  No figure is a gate.  App
 """
 import argparse
 import json
-import subprocess
 import sys
 import tempfile
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
+import _bench
 
 SCENES = ("reference", "spherized4", "spherized6")
 STEPS = tuple(f"{kind}_{scene}" for kind in ("refract", "levels") for scene in SCENES)
@@ -41,27 +41,10 @@ ap.add_argument("--out", default=str(ROOT / "profiles" / "refract_query_bench.js
 a = ap.parse_args()
 
 if a.step is None:
-    result = {"tool": "bench_refract_queries", "steps": a.steps, "warmup": a.warmup, "depth": a.depth}
-    try:
-        result["commit"] = subprocess.run(["git", "-C", str(ROOT), "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip() or None
-    except OSError:
-        result["commit"] = None
-    for step in a.cases:
-        cmd = ["timeout", "-k", "10", str(a.step_timeout), sys.executable, __file__, "--step", step, "--steps", str(a.steps), "--warmup", str(a.warmup),
-               "--depth", str(a.depth)]
-        proc = subprocess.run(cmd, capture_output=True, text=True)
-        if proc.returncode != 0:
-            sys.stderr.write(proc.stdout + proc.stderr)
-            sys.exit(f"case {step}: exit status {proc.returncode}; nothing more is started")
-        result[step] = json.loads(proc.stdout.strip().splitlines()[-1])
-    line = json.dumps(result)
-    Path(a.out).parent.mkdir(parents=True, exist_ok=True)
-    with open(a.out, "a") as f:
-        f.write(line + "\n")
-    print(line)
+    _bench.run_cases("bench_refract_queries", a.cases, lambda case: ["--step", case] + _bench.options(a, "steps", "warmup", "depth"), a.step_timeout, a.out,
+                     header={"steps": a.steps, "warmup": a.warmup, "depth": a.depth})
     sys.exit(0)
 
-import numpy as np
 import torch
 
 import homework_18_graphics_raytracer_amd as rt
@@ -69,39 +52,11 @@ import homework_18_graphics_raytracer_amd as rt
 torch.cuda.set_device(0)
 
 
-def tile_order(cols, rows):
-    """position k of the Whitted kernels' slot order (8-row bands, column-major inside a band) -> the row-order index of its pixel"""
-    s = np.arange(cols * rows, dtype=np.int64)
-    band = s // (cols * 8)
-    r = s - band * cols * 8
-    band_rows = np.minimum(8, rows - band * 8)
-    col = r // band_rows
-    return (band * 8 + (r - col * band_rows)) * cols + col
-
-
-def one(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1)
-
-
-def same(x, y):
-    if x.dtype != torch.float32:
-        return bool((x == y).all())
-    return bool(((x.view(torch.int32) == y.view(torch.int32)) | (x.isnan() & y.isnan())).all())
-
-
 kind, scene_name = a.step.split("_")
 with tempfile.TemporaryDirectory() as tmp:
     if scene_name.startswith("spherized"):
         level = int(scene_name[-1])
-        obj = Path(tmp) / f"dodecahedron_l{level}s.obj"
-        cmd = [sys.executable, str(ROOT / "tools" / "make_tessellated_obj.py"), rt.DEFAULT_OBJ, str(obj), "--levels", str(level), "--spherize"]
-        subprocess.run(cmd, check=True, capture_output=True)
-        world = rt.reference_world(str(obj))
+        world = _bench.tessellated_world(tmp, level, True)
         with rt.options(RT_AMD_BFS_WALK_TRIANGLES=8192):  # the library's default switch, set here so that no environment moves it
             scene = rt.Scene(world)
         rays = rt.camera_rays(rt.reference_camera(), rt.Frame.full(480, 270, 0))
@@ -109,7 +64,7 @@ with tempfile.TemporaryDirectory() as tmp:
         world = rt.reference_world()
         scene = rt.Scene(world)
         rows = rt.camera_rays(rt.reference_camera(), rt.Frame.full(1920, 1080, 0))
-        rays = rows[torch.from_numpy(tile_order(1920, 1080)).cuda()].contiguous()
+        rays = rows[torch.from_numpy(_bench.tile_order(1920, 1080)).cuda()].contiguous()
 desc = world.desc()
 stream = torch.cuda.Stream()
 res = {"triangles": desc.n_triangles}
@@ -140,7 +95,7 @@ if kind == "refract":
 
     def identical():
         ref = out[forms[0]]
-        ok = all(same(out[k].kind, ref.kind) and same(out[k].travel, ref.travel) and same(out[k].rays, ref.rays) for k in forms[1:])
+        ok = all(_bench.same(out[k].kind, ref.kind) and _bench.same(out[k].travel, ref.travel) and _bench.same(out[k].rays, ref.rays) for k in forms[1:])
         return ok and len({int(c.item()) for c in count.values()}) == 1
 
     calls = {"refract_pairs": lambda: fused("refract_pairs"), "refract_uniform": fused_uniform, "loop": by_loop}
@@ -157,7 +112,7 @@ else:
                              level_capacity=lambda level: 2 * N, open_casts=opened)
 
     def identical():
-        return same(out["levels"], out["levels_open_casts"]) and int(count["levels"].item()) == int(count["levels_open_casts"].item()) \
+        return _bench.same(out["levels"], out["levels_open_casts"]) and int(count["levels"].item()) == int(count["levels_open_casts"].item()) \
             and int(overflow.item()) == 0
 
     calls = {"levels": lambda: levels("levels", False), "levels_open_casts": lambda: levels("levels_open_casts", True)}
@@ -191,15 +146,14 @@ with torch.cuda.stream(stream):
     for k in range(a.warmup + a.steps):
         for c in count.values():
             c.zero_()
-        t = {name: one(fn) for name, fn in calls.items()}
+        t = {name: _bench.time_ms(fn) for name, fn in calls.items()}
         ok = ok and identical()
         if k >= a.warmup:
             for name in ms:
                 ms[name].append(t[name])
 res["casts"] = int(count[forms[0]].item())
 for name, v in ms.items():
-    med = float(np.median(v))
-    res[name] = {"ms_median": round(med, 4), "ms_min": round(min(v), 4), "mcasts_per_s": round(res["casts"] / med / 1e3, 1)}
+    res[name] = _bench.summary(v, rate=("mcasts_per_s", res["casts"]))
 if kind == "refract":
     best = min(res["refract_pairs"]["ms_median"], res["refract_uniform"]["ms_median"])
     res["fused_winner"] = "pairs" if res["refract_pairs"]["ms_median"] <= res["refract_uniform"]["ms_median"] else "uniform"

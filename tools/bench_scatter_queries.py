@@ -18,12 +18,12 @@ No figure is a gate.  Appends one JSON line to --out and prints it.
 """
 import argparse
 import json
-import subprocess
 import sys
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
+import _bench
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--steps", type=int, default=7, help="timed calls per case")
@@ -39,27 +39,8 @@ a = ap.parse_args()
 STEPS = ("kernels", "refill", "epoch")
 
 if a.step is None:
-    result = {"tool": "bench_scatter_queries", "steps": a.steps, "warmup": a.warmup, "frame": [a.width, a.height], "depth": a.depth}
-    try:
-        result["commit"] = subprocess.run(["git", "-C", str(ROOT), "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip() or None
-    except OSError:
-        result["commit"] = None
-    for step in STEPS:
-        cmd = [sys.executable, __file__, "--step", step] + [x for k in ("steps", "warmup", "refill_calls", "depth", "width", "height")
-                                                            for x in ("--" + k.replace("_", "-"), str(getattr(a, k)))]
-        try:
-            proc = subprocess.run(cmd, capture_output=True, text=True, timeout=a.step_timeout)
-        except subprocess.TimeoutExpired:
-            sys.exit(f"step {step}: no result within {a.step_timeout} s; nothing more is started")
-        if proc.returncode != 0:
-            sys.stderr.write(proc.stdout + proc.stderr)
-            sys.exit(f"step {step}: exit status {proc.returncode}; nothing more is started")
-        result.update(json.loads(proc.stdout.strip().splitlines()[-1]))
-    line = json.dumps(result)
-    Path(a.out).parent.mkdir(parents=True, exist_ok=True)
-    with open(a.out, "a") as f:
-        f.write(line + "\n")
-    print(line)
+    _bench.run_cases("bench_scatter_queries", STEPS, lambda step: ["--step", step] + _bench.options(a, "steps", "warmup", "refill_calls", "depth", "width", "height"),
+                     a.step_timeout, a.out, header={"steps": a.steps, "warmup": a.warmup, "frame": [a.width, a.height], "depth": a.depth}, merge=True)
     sys.exit(0)
 
 import numpy as np
@@ -73,24 +54,6 @@ scene = rt.Scene(world)
 camera = rt.reference_camera()
 frame = rt.Frame.full(a.width, a.height, a.depth)
 N = frame.rows * frame.cols
-
-
-def one(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1)
-
-
-def stats(ms, records):
-    med = float(np.median(ms))
-    return {"ms_median": round(med, 4), "ms_min": round(min(ms), 4), "mrecords_per_s": round(records / med / 1e3, 1)}
-
-
-def same(x, y):
-    return bool(((x.view(torch.int32) == y.view(torch.int32)) | (x.isnan() & y.isnan())).all())
 
 
 def masked(hits, mask):
@@ -143,10 +106,10 @@ if a.step == "kernels":
     rng = rt.Rng(frame)
     ms = []
     for k in range(a.warmup + a.steps):  # 3 words a call: far from the end of the first block
-        t = one(lambda: rt.scatter_hits(scene, hits, rays, rng))
+        t = _bench.time_ms(lambda: rt.scatter_hits(scene, hits, rays, rng))
         if k >= a.warmup:
             ms.append(t)
-    out["scatter_hits"] = dict(stats(ms, N), hits=int((hits[:, 0] >= 0).sum().item()))
+    out["scatter_hits"] = dict(_bench.summary(ms, rate=("mrecords_per_s", N)), hits=int((hits[:, 0] >= 0).sum().item()))
     sc = rt.scatter_hits(scene, hits, rays, rng)
     nxt = rt.reflect_rays(hits, sc.rays)
     travel = torch.full((N,), 0.5, dtype=torch.float32, device="cuda")
@@ -154,7 +117,7 @@ if a.step == "kernels":
     fn = lambda: rt.scatter_factors(scene, hits, rays, sc.type, nxt, travel, out=rgb)
     for _ in range(a.warmup):
         fn()
-    out["scatter_factors"] = stats([one(fn) for _ in range(a.steps)], N)
+    out["scatter_factors"] = _bench.summary([_bench.time_ms(fn) for _ in range(a.steps)], rate=("mrecords_per_s", N))
 elif a.step == "refill":
     kept = {}
     for name, value in (("in_kernel", 0), ("prepare_pass", 1)):
@@ -168,7 +131,7 @@ elif a.step == "refill":
                 for _ in range(a.refill_calls):
                     last[:] = [rt.scatter_hits(scene, hits, rays, rng)]
 
-            ms = one(calls)
+            ms = _bench.time_ms(calls)
             out["refill_" + name] = {"calls": a.refill_calls, "ms_total": round(ms, 3), "ms_per_call": round(ms / a.refill_calls, 4),
                                      "mrecords_per_s": round(N * a.refill_calls / ms / 1e3, 1)}
             kept[name] = (last[0].type.clone(), last[0].rays.clone(), torch.from_numpy(rng.download()[:4096].astype(np.int64)))
@@ -189,13 +152,13 @@ else:
     ms = {"levels": [], "call": []}
     identical = True
     for k in range(a.warmup + a.steps):
-        t_l, t_c = one(by_levels), one(by_call)
-        identical = identical and same(got[0], samples[0])
+        t_l, t_c = _bench.time_ms(by_levels), _bench.time_ms(by_call)
+        identical = identical and _bench.same(got[0], samples[0])
         if k >= a.warmup:
             ms["levels"].append(t_l)
             ms["call"].append(t_c)
-    out["epoch_by_levels"] = stats(ms["levels"], N)
-    out["epoch_by_call"] = stats(ms["call"], N)
+    out["epoch_by_levels"] = _bench.summary(ms["levels"], rate=("mrecords_per_s", N))
+    out["epoch_by_call"] = _bench.summary(ms["call"], rate=("mrecords_per_s", N))
     out["epoch_levels_over_call"] = round(out["epoch_by_levels"]["ms_median"] / out["epoch_by_call"]["ms_median"], 3)
     out["epoch_identical"] = identical
     out["device"] = torch.cuda.get_device_name(0)

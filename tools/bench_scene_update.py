@@ -16,7 +16,6 @@ bit for bit against the fresh scene's.  No figure is a gate.  Appends one JSON l
 import argparse
 import ctypes as C
 import json
-import subprocess
 import sys
 import tempfile
 import time
@@ -24,6 +23,7 @@ from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
+import _bench
 
 JOBS = ("reference", "spherized4", "spherized6")
 ap = argparse.ArgumentParser()
@@ -36,23 +36,8 @@ ap.add_argument("--out", default=str(ROOT / "profiles" / "scene_update_bench.jso
 a = ap.parse_args()
 
 if a.job is None:
-    result = {"tool": "bench_scene_update", "steps": a.steps, "warmup": a.warmup}
-    try:
-        result["commit"] = subprocess.run(["git", "-C", str(ROOT), "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip() or None
-    except OSError:
-        result["commit"] = None
-    for job in a.jobs:
-        cmd = ["timeout", "-k", "10", str(a.step_timeout), sys.executable, __file__, "--job", job, "--steps", str(a.steps), "--warmup", str(a.warmup)]
-        proc = subprocess.run(cmd, capture_output=True, text=True)
-        if proc.returncode != 0:
-            sys.stderr.write(proc.stdout + proc.stderr)
-            sys.exit(f"job {job}: exit status {proc.returncode}; nothing more is started")
-        result[job] = json.loads(proc.stdout.strip().splitlines()[-1])
-    line = json.dumps(result)
-    Path(a.out).parent.mkdir(parents=True, exist_ok=True)
-    with open(a.out, "a") as f:
-        f.write(line + "\n")
-    print(line)
+    _bench.run_cases("bench_scene_update", a.jobs, lambda job: ["--job", job] + _bench.options(a, "steps", "warmup"), a.step_timeout, a.out,
+                     header={"steps": a.steps, "warmup": a.warmup})
     sys.exit(0)
 
 import numpy as np
@@ -65,10 +50,7 @@ torch.cuda.set_device(0)
 with tempfile.TemporaryDirectory() as tmp:
     if a.job.startswith("spherized"):
         level = int(a.job[-1])
-        obj = Path(tmp) / f"dodecahedron_l{level}s.obj"
-        cmd = [sys.executable, str(ROOT / "tools" / "make_tessellated_obj.py"), rt.DEFAULT_OBJ, str(obj), "--levels", str(level), "--spherize"]
-        subprocess.run(cmd, check=True, capture_output=True)
-        world = rt.reference_world(str(obj))
+        world = _bench.tessellated_world(tmp, level, True)
     else:
         world = rt.reference_world()
 desc = world.desc()

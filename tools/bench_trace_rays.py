@@ -16,13 +16,13 @@ and the same cast count.  Prints one JSON line.  Kernel times: run it under rocp
 """
 import argparse
 import json
-import subprocess
 import sys
 import tempfile
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
+import _bench
 import numpy as np
 import torch
 
@@ -40,59 +40,6 @@ ap.add_argument("--seed", type=int, default=2024)
 a = ap.parse_args()
 
 torch.cuda.set_device(0)
-
-
-def random_rays(seed, n, centre, radius):
-    g = np.random.default_rng(seed)
-    scale = np.where(g.random(n) < 0.5, g.uniform(0.0, 1.0, n), g.uniform(1.0, 2.0, n)) * radius
-    u = g.normal(size=(n, 3))
-    origins = centre + u / np.linalg.norm(u, axis=1, keepdims=True) * scale[:, None]
-    d = centre + g.normal(0.0, radius * 0.5, (n, 3)) - origins
-    d /= np.maximum(np.linalg.norm(d, axis=1, keepdims=True), 1e-12)
-    dev = lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).cuda()
-    return rt.make_rays(dev(origins), dev(d))
-
-
-def bounds(desc):
-    p = [v.position[:] for i in range(desc.n_triangles) for v in desc.triangles[i].vertices]
-    for i in range(desc.n_spheres):
-        s = desc.spheres[i]
-        p += [list(np.asarray(s.center[:]) + s.radius), list(np.asarray(s.center[:]) - s.radius)]
-    p = np.asarray(p, dtype=np.float64)
-    c = (p.min(0) + p.max(0)) / 2
-    return c, float(np.linalg.norm(p - c, axis=1).max())
-
-
-def tile_order(cols, rows):
-    """position k of the Whitted kernels' slot order -> the row-order index of its pixel"""
-    s = np.arange(cols * rows, dtype=np.int64)
-    band = s // (cols * 8)
-    r = s - band * cols * 8
-    band_rows = np.minimum(8, rows - band * 8)
-    col = r // band_rows
-    return (band * 8 + (r - col * band_rows)) * cols + col
-
-
-def one(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1)
-
-
-def alternated(cases, steps, warmup):
-    """every case once per round, `steps` timed rounds after `warmup` untimed ones; returns per case the ms of every timed call"""
-    for _ in range(warmup):
-        for fn in cases.values():
-            fn()
-    torch.cuda.synchronize()
-    ms = {k: [] for k in cases}
-    for _ in range(steps):
-        for k, fn in cases.items():
-            ms[k].append(one(fn))
-    return ms
 
 
 def casts_of(fn, count):
@@ -116,10 +63,10 @@ cam = rt.reference_camera()
 W, H = 1920, 1080
 frame = rt.Frame.full(W, H, a.depth)
 rows = rt.camera_rays(cam, frame)
-perm = torch.from_numpy(tile_order(W, H)).cuda()
+perm = torch.from_numpy(_bench.tile_order(W, H)).cuda()
 tiles = rows[perm].contiguous()
-centre, radius = bounds(desc)
-rnd = random_rays(a.seed, a.random_rays, centre, radius)
+centre, radius = _bench.bounds(desc)
+rnd = _bench.random_rays(a.seed, a.random_rays, centre, radius)
 img = torch.empty((H, W, 3), dtype=torch.float32, device="cuda")
 out = {k: torch.empty((n, 3), dtype=torch.float32, device="cuda") for k, n in (("b_rows", W * H), ("c_tiles", W * H), ("d_random", rnd.shape[0]))}
 count = torch.zeros(1, dtype=torch.int64, device="cuda")
@@ -129,7 +76,7 @@ cases = {
     "c_tiles": lambda: rt.trace_rays(scene, tiles, a.depth, out=out["c_tiles"]),
     "d_random": lambda: rt.trace_rays(scene, rnd, a.depth, out=out["d_random"]),
 }
-ms = alternated(cases, a.steps, a.warmup)
+ms = _bench.alternate(cases, a.warmup, a.steps)
 casts = {
     "a_whitted": casts_of(lambda: rt.render_whitted(scene, cam, frame, out=img, ray_count=count), count),
     "b_rows": casts_of(lambda: rt.trace_rays(scene, rows, a.depth, out=out["b_rows"], ray_count=count), count),
@@ -150,16 +97,13 @@ del rows, tiles, rnd, out
 
 if not a.no_large:
     with tempfile.TemporaryDirectory() as tmp:
-        obj = Path(tmp) / "d6.obj"
-        subprocess.run([sys.executable, str(ROOT / "tools" / "make_tessellated_obj.py"), rt.DEFAULT_OBJ, str(obj), "--levels", "6"], check=True,
-                       capture_output=True)
-        big = rt.reference_world(str(obj))
+        big = _bench.tessellated_world(tmp, 6, False)
     bdesc = big.desc()
     bscene = rt.Scene(big)
-    bcentre, bradius = bounds(bdesc)
-    brays = random_rays(a.seed + 1, a.large_rays, bcentre, bradius)
+    bcentre, bradius = _bench.bounds(bdesc)
+    brays = _bench.random_rays(a.seed + 1, a.large_rays, bcentre, bradius)
     bout = torch.empty((brays.shape[0], 3), dtype=torch.float32, device="cuda")
-    bms = alternated({"large": lambda: rt.trace_rays(bscene, brays, a.depth, out=bout)}, a.large_steps, 1)["large"]
+    bms = _bench.alternate({"large": lambda: rt.trace_rays(bscene, brays, a.depth, out=bout)}, 1, a.large_steps)["large"]
     result["large"] = summary(brays.shape[0], bms, casts_of(lambda: rt.trace_rays(bscene, brays, a.depth, out=bout, ray_count=count), count))
     result["large"]["triangles"] = int(bdesc.n_triangles)
 print(json.dumps(result))

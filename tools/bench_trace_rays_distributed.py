@@ -24,6 +24,7 @@ from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
+import _bench
 import numpy as np
 import torch
 
@@ -44,58 +45,6 @@ a = ap.parse_args()
 torch.cuda.set_device(0)
 
 
-def random_rays(seed, n, centre, radius):
-    g = np.random.default_rng(seed)
-    scale = np.where(g.random(n) < 0.5, g.uniform(0.0, 1.0, n), g.uniform(1.0, 2.0, n)) * radius
-    u = g.normal(size=(n, 3))
-    origins = centre + u / np.linalg.norm(u, axis=1, keepdims=True) * scale[:, None]
-    d = centre + g.normal(0.0, radius * 0.5, (n, 3)) - origins
-    d /= np.maximum(np.linalg.norm(d, axis=1, keepdims=True), 1e-12)
-    dev = lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).cuda()
-    return rt.make_rays(dev(origins), dev(d))
-
-
-def bounds(desc):
-    p = [v.position[:] for i in range(desc.n_triangles) for v in desc.triangles[i].vertices]
-    for i in range(desc.n_spheres):
-        s = desc.spheres[i]
-        p += [list(np.asarray(s.center[:]) + s.radius), list(np.asarray(s.center[:]) - s.radius)]
-    p = np.asarray(p, dtype=np.float64)
-    c = (p.min(0) + p.max(0)) / 2
-    return c, float(np.linalg.norm(p - c, axis=1).max())
-
-
-def tile_order(cols, rows):
-    """position k of the chain kernel's slot order -> the row-order index of its pixel"""
-    s = np.arange(cols * rows, dtype=np.int64)
-    band = s // (cols * 8)
-    r = s - band * cols * 8
-    band_rows = np.minimum(8, rows - band * 8)
-    col = r // band_rows
-    return (band * 8 + (r - col * band_rows)) * cols + col
-
-
-def one(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1)
-
-
-def alternated(cases, steps, warmup):
-    for _ in range(warmup):
-        for fn in cases.values():
-            fn()
-    torch.cuda.synchronize()
-    ms = {k: [] for k in cases}
-    for _ in range(steps):
-        for k, fn in cases.items():
-            ms[k].append(one(fn))
-    return ms
-
-
 W, H, E, D = a.width, a.height, a.epochs, a.depth
 N = W * H
 world = rt.reference_world()
@@ -103,9 +52,9 @@ desc = world.desc()
 scene = rt.Scene(world)
 cam = rt.reference_camera()
 frame = rt.Frame.full(W, H, D)
-perm = torch.from_numpy(tile_order(W, H)).cuda()
-centre, radius = bounds(desc)
-rnd = random_rays(a.seed, a.random_rays, centre, radius)
+perm = torch.from_numpy(_bench.tile_order(W, H)).cuda()
+centre, radius = _bench.bounds(desc)
+rnd = _bench.random_rays(a.seed, a.random_rays, centre, radius)
 result = {"tool": "bench_trace_rays_distributed", "device": torch.cuda.get_device_name(0), "steps": a.steps, "warmup": a.warmup,
           "depth": D, "epochs": E, "width": W, "height": H}
 
@@ -157,7 +106,7 @@ cases = {
     "e_fixed": lambda: rt.trace_rays_distributed(scene, fixed, D, rng_e, E, accum=acc["e"]),
     "d_random": lambda: rt.trace_rays_distributed(scene, rnd, D, rng_d, E, accum=acc["d"]),
 }
-ms = alternated(cases, a.steps, a.warmup)
+ms = _bench.alternate(cases, a.warmup, a.steps)
 for k, v in ms.items():
     n = rnd.shape[0] if k == "d_random" else N
     med = float(np.median(v))

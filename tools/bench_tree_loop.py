@@ -18,12 +18,12 @@ JSON line to --out and prints it.
 """
 import argparse
 import json
-import subprocess
 import sys
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
+import _bench
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--steps", type=int, default=5, help="timed calls per form")
@@ -39,27 +39,8 @@ a = ap.parse_args()
 STEPS = ("tiles", "random")
 
 if a.step is None:
-    result = {"tool": "bench_tree_loop", "steps": a.steps, "warmup": a.warmup, "frame": [a.width, a.height], "depth": a.depth}
-    try:
-        result["commit"] = subprocess.run(["git", "-C", str(ROOT), "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip() or None
-    except OSError:
-        result["commit"] = None
-    for step in STEPS:
-        cmd = [sys.executable, __file__, "--step", step] + [x for k in ("steps", "warmup", "depth", "width", "height", "random_rays")
-                                                            for x in ("--" + k.replace("_", "-"), str(getattr(a, k)))]
-        try:
-            proc = subprocess.run(cmd, capture_output=True, text=True, timeout=a.step_timeout)
-        except subprocess.TimeoutExpired:
-            sys.exit(f"case {step}: no result within {a.step_timeout} s; nothing more is started")
-        if proc.returncode != 0:
-            sys.stderr.write(proc.stdout + proc.stderr)
-            sys.exit(f"case {step}: exit status {proc.returncode}; nothing more is started")
-        result[step] = json.loads(proc.stdout.strip().splitlines()[-1])
-    line = json.dumps(result)
-    Path(a.out).parent.mkdir(parents=True, exist_ok=True)
-    with open(a.out, "a") as f:
-        f.write(line + "\n")
-    print(line)
+    _bench.run_cases("bench_tree_loop", STEPS, lambda step: ["--step", step] + _bench.options(a, "steps", "warmup", "depth", "width", "height", "random_rays"),
+                     a.step_timeout, a.out, header={"steps": a.steps, "warmup": a.warmup, "frame": [a.width, a.height], "depth": a.depth})
     sys.exit(0)
 
 import numpy as np
@@ -73,37 +54,9 @@ scene = rt.Scene(world)
 camera = rt.reference_camera()
 
 
-def tile_order(cols, rows):
-    """position k of the Whitted kernels' slot order (8-row bands, column-major inside a band) -> the row-order index of its pixel"""
-    s = np.arange(cols * rows, dtype=np.int64)
-    band = s // (cols * 8)
-    r = s - band * cols * 8
-    band_rows = np.minimum(8, rows - band * 8)
-    col = r // band_rows
-    return (band * 8 + (r - col * band_rows)) * cols + col
-
-
-def one(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1)
-
-
-def stats(ms, records):
-    med = float(np.median(ms))
-    return {"ms_median": round(med, 4), "ms_min": round(min(ms), 4), "mrays_per_s": round(records / med / 1e3, 1)}
-
-
-def same(x, y):
-    return bool(((x.view(torch.int32) == y.view(torch.int32)) | (x.isnan() & y.isnan())).all())
-
-
 if a.step == "tiles":
     rows = rt.camera_rays(camera, rt.Frame.full(a.width, a.height, a.depth))
-    rays = rows[torch.from_numpy(tile_order(a.width, a.height)).cuda()].contiguous()
+    rays = rows[torch.from_numpy(_bench.tile_order(a.width, a.height)).cuda()].contiguous()
 else:
     g = np.random.default_rng(7)
     desc = world.desc()
@@ -149,13 +102,13 @@ with torch.cuda.stream(stream):
     for k in range(a.warmup + a.steps):
         for c in count.values():
             c.zero_()
-        t = {name: one(fn) for name, fn in forms.items()}
-        identical = identical and same(out["loop"], out["fused"]) and same(out["graph"], out["fused"])
+        t = {name: _bench.time_ms(fn) for name, fn in forms.items()}
+        identical = identical and _bench.same(out["loop"], out["fused"]) and _bench.same(out["graph"], out["fused"])
         identical = identical and count["loop"].item() == count["fused"].item() == count["graph"].item()
         if k >= a.warmup:
             for name in ms:
                 ms[name].append(t[name])
-res = {"rays": N, "loop": stats(ms["loop"], N), "loop_in_a_graph": stats(ms["graph"], N), "fused_call": stats(ms["fused"], N)}
+res = {"rays": N, "loop": _bench.summary(ms["loop"], rate=("mrays_per_s", N)), "loop_in_a_graph": _bench.summary(ms["graph"], rate=("mrays_per_s", N)), "fused_call": _bench.summary(ms["fused"], rate=("mrays_per_s", N))}
 res["loop_over_fused_call"] = round(res["loop"]["ms_median"] / res["fused_call"]["ms_median"], 3)
 res["graph_over_fused_call"] = round(res["loop_in_a_graph"]["ms_median"] / res["fused_call"]["ms_median"], 3)
 res["casts"] = int(count["fused"].item())

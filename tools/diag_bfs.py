@@ -6,13 +6,13 @@ TAG=bfsdiag EXTRA=-DRT_DIAG_BFS).
 """
 import argparse
 import ctypes as C
-import subprocess
 import sys
 import tempfile
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
+import _bench
 import torch  # noqa: E402
 
 from homework_18_graphics_raytracer_amd import _capi  # noqa: E402
@@ -33,10 +33,7 @@ rt.set_option("RT_AMD_BFS_WALK_TRIANGLES", 1)
 cam = rt.reference_camera()
 with tempfile.TemporaryDirectory() as tmp:
     for level in a.levels:
-        obj = Path(tmp) / f"d{level}.obj"
-        cmd = [sys.executable, str(ROOT / "tools" / "make_tessellated_obj.py"), rt.DEFAULT_OBJ, str(obj), "--levels", str(level)]
-        subprocess.run(cmd + (["--spherize"] if a.spherize else []), check=True, capture_output=True)
-        world = rt.reference_world(str(obj))
+        world = _bench.tessellated_world(tmp, level, a.spherize)
         scene = rt.Scene(world)
         W, H = (960, 540) if level <= 5 else (480, 270)
         frame = rt.Frame.full(W, H, 8)

@@ -14,7 +14,6 @@ brute-force cast costs algorithmically, main.rs:183-262), and the scene's size i
 """
 import argparse
 import json
-import subprocess
 import sys
 import tempfile
 import time
@@ -22,6 +21,7 @@ from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
+import _bench
 sys.path.insert(0, str(ROOT / "tests"))
 
 ap = argparse.ArgumentParser()
@@ -58,10 +58,7 @@ cam = rt.reference_camera()
 lines = []
 with tempfile.TemporaryDirectory() as tmp:
     for level in a.levels:
-        obj = Path(tmp) / f"dodecahedron_l{level}.obj"
-        cmd = [sys.executable, str(ROOT / "tools" / "make_tessellated_obj.py"), rt.DEFAULT_OBJ, str(obj), "--levels", str(level)]
-        subprocess.run(cmd + (["--spherize"] if a.spherize else []), check=True, capture_output=True)
-        built = rt.reference_world(str(obj))
+        built = _bench.tessellated_world(tmp, level, a.spherize)
         path = Path(tmp) / f"scene_l{level}.rtscene"
         built.save_scene(path, cam)
         world, file_cam = rt.World.load_scene(path)

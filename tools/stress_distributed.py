@@ -18,6 +18,7 @@ import torch
 
 import homework_18_graphics_raytracer_amd as rt
 from homework_18_graphics_raytracer_amd import _capi
+import _bench
 import _oracle
 import _scenes
 
@@ -27,10 +28,6 @@ ap.add_argument("--seed", type=int, default=0)
 a = ap.parse_args()
 lib = _capi.amd_lib()
 rng = np.random.default_rng(a.seed)
-
-
-def same(x, y):
-    return bool((((x.view(np.uint32) == y.view(np.uint32)) | (np.isnan(x) & np.isnan(y))).all()))
 
 
 def run_gpu(scene, cam, frame, calls):
@@ -74,12 +71,12 @@ for k in range(a.configs):
     s, v, casts, st = run_gpu(scene, cam, frame, calls)
     want_st = _oracle.rng_init(frame)
     ws, wv, wcasts = _oracle.render_distributed(world.desc(), cam, frame, want_st, total)
-    ok = same(s, ws) and np.array_equal(v, wv) and casts == wcasts and np.array_equal(st, want_st)
+    ok = _bench.same(s, ws) and np.array_equal(v, wv) and casts == wcasts and np.array_equal(st, want_st)
     if ok and k % 5 == 0:
         rt.set_option("RT_AMD_RNG_LOOKAHEAD", "0")
         s2, v2, casts2, st2 = run_gpu(scene, cam, frame, [total])
         rt.set_option("RT_AMD_RNG_LOOKAHEAD", None)
-        ok = same(s2, s) and np.array_equal(v2, v) and casts2 == casts and np.array_equal(st2, st)
+        ok = _bench.same(s2, s) and np.array_equal(v2, v) and casts2 == casts and np.array_equal(st2, st)
     if not ok:
         bad += 1
         print(f"MISMATCH config {k}: kind {kind} seed {seed} {w}x{h} d{d} rows {frame.rows} calls {calls} split {split} cap {cap} MB: casts {casts} vs {wcasts}", flush=True)

@@ -16,6 +16,7 @@ import numpy as np
 
 import homework_18_graphics_raytracer_amd as rt
 from homework_18_graphics_raytracer_amd import _capi
+import _bench
 import _oracle
 import _scenes
 
@@ -27,10 +28,6 @@ ap.add_argument("--seed", type=int, default=0)
 a = ap.parse_args()
 lib = _capi.amd_lib()
 rng = np.random.default_rng(a.seed)
-
-
-def same(x, y):
-    return bool((((x.view(np.uint32) == y.view(np.uint32)) | (np.isnan(x) & np.isnan(y))).all()))
 
 
 bad = 0
@@ -56,12 +53,12 @@ for k in range(a.configs):
     ok = True
     for r in range(a.repeats):
         img, casts = rt.render_whitted_numpy(scene, cam, frame)
-        if not same(img, ref) or casts != ref_casts:
+        if not _bench.same(img, ref) or casts != ref_casts:
             ok = False
             print(f"MISMATCH config {k}: kind {kind} seed {seed} {w}x{h} d{d} repeat {r}: casts {casts} vs {ref_casts}", flush=True)
     if ok and a.oracle_every and k % a.oracle_every == 0:
         want, wcasts = _oracle.render_whitted(world.desc(), cam, frame)
-        if not same(ref, want) or ref_casts != wcasts:
+        if not _bench.same(ref, want) or ref_casts != wcasts:
             ok = False
             print(f"ORACLE MISMATCH config {k}: kind {kind} seed {seed} {w}x{h} d{d}", flush=True)
     bad += 0 if ok else 1
