@@ -99,6 +99,27 @@ def _words(t, name):
     return t.shape[0], (1 if t.dim() == 1 else t.shape[1])
 
 
+def _plane_words(shape, strides, whole_words=True):
+    """The pixel stride, in 4-byte words, of a plane of (..., width) words whose pixels are taken in row order — ``strides`` in words — or
+    None when the last dimension is not contiguous or the leading dimensions do not advance by ONE stride from pixel to pixel: what lets a
+    strided view of records be handed to C as a base pointer and a record stride."""
+    if not whole_words or len(shape) != len(strides) or len(shape) < 1:
+        return None
+    width = shape[-1]
+    if width > 1 and strides[-1] != 1:
+        return None
+    pixel, expect = None, None
+    for extent, stride in zip(reversed(shape[:-1]), reversed(strides[:-1])):
+        if extent == 1:
+            continue
+        if pixel is None:
+            pixel = stride
+        elif stride != expect:
+            return None
+        expect = stride * extent
+    return width if pixel is None else (pixel if pixel > 0 else None)
+
+
 def _host_records(a, dtype, words, name):
     a = np.asarray(a)
     if a.dtype == dtype:

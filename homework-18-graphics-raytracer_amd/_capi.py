@@ -166,6 +166,18 @@ def sources_sha256() -> str:
     return h.hexdigest()
 
 
+class DenoiseGuides(C.Structure):
+    """rt_denoise_guides: a base pointer and a record stride in 4-byte words per guide plane; a null pointer leaves the plane out"""
+    _fields_ = [("normal", C.c_void_p), ("position", C.c_void_p), ("albedo", C.c_void_p), ("valid", C.c_void_p),
+                ("normal_stride", C.c_uint32), ("position_stride", C.c_uint32), ("albedo_stride", C.c_uint32), ("valid_stride", C.c_uint32)]
+
+
+class DenoiseParams(C.Structure):
+    """rt_denoise_params"""
+    _fields_ = [("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_position", C.c_float),
+                ("first_level", C.c_uint32), ("n_levels", C.c_uint32), ("flags", C.c_uint32)]
+
+
 AMD_SYMBOLS = [
     "rt_abi_version", "rt_last_error", "rt_device_count", "rt_set_device", "rt_frame_rows", "rt_frame_pixels",
     "rt_scene_create", "rt_scene_destroy", "rt_render_whitted", "rt_render_whitted_host", "rt_set_option", "rt_set_variant",
@@ -180,6 +192,7 @@ AMD_SYMBOLS = [
     "rt_light_rays", "rt_light_terms", "rt_light_fold",
     "rt_material_hits", "rt_material_hits_host", "rt_probe_surfaces", "rt_probe_surfaces_host",
     "rt_film_offsets", "rt_camera_rays_offset", "rt_camera_rays_offset_host", "rt_film_splat",
+    "rt_denoise_temp_bytes", "rt_denoise_atrous", "rt_denoise_atrous_host",
     "rt_refract_enter", "rt_refract_step",
     "rt_scene_update_vertices", "rt_scene_update_spheres", "rt_scene_update_lights", "rt_scene_update_materials",
     "rt_ray_keys", "rt_sort_temp_bytes", "rt_sort_records", "rt_gather_records", "rt_scatter_records",
@@ -191,7 +204,7 @@ HOST_SYMBOLS = [
     "rt_world_push_light", "rt_world_push_flat_triangle", "rt_world_push_square", "rt_world_load_obj",
     "rt_world_build_reference_scene", "rt_world_save_scene", "rt_world_load_scene", "rt_reference_camera", "rt_world_desc", "rt_frame_full", "rt_post_process", "rt_luma_row",
     "rt_encode_srgb8", "rt_accumulate", "rt_accumulator_resolve", "rt_write_png", "rt_host_last_error",
-    "rt_film_offsets_host", "rt_film_splat_host",
+    "rt_film_offsets_host", "rt_film_splat_host", "rt_denoise_atrous_cpu",
 ]
 
 _amd = None
@@ -239,6 +252,7 @@ def host_lib() -> C.CDLL:
         lib.rt_film_offsets_host.argtypes = [C.POINTER(Frame), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
         lib.rt_film_splat_host.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p,
                                            C.c_void_p]
+        lib.rt_denoise_atrous_cpu.argtypes = [C.c_void_p, C.POINTER(DenoiseGuides), C.POINTER(DenoiseParams), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
         lib.rt_write_png.argtypes = [C.c_char_p, C.c_void_p, C.c_uint32, C.c_uint32]
         lib.rt_host_last_error.restype = C.c_char_p
         _host = lib
@@ -352,6 +366,11 @@ def amd_lib() -> C.CDLL:
         lib.rt_camera_rays_offset_host.argtypes = [C.POINTER(Camera), C.POINTER(Frame), C.c_void_p, C.c_uint32, C.c_void_p]
         lib.rt_film_splat.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p,
                                       C.c_void_p]
+        lib.rt_denoise_temp_bytes.argtypes = [C.c_uint32, C.c_uint32]
+        lib.rt_denoise_temp_bytes.restype = C.c_size_t
+        lib.rt_denoise_atrous.argtypes = [C.c_void_p, C.POINTER(DenoiseGuides), C.POINTER(DenoiseParams), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]
+        lib.rt_denoise_atrous_host.argtypes = [C.c_void_p, C.POINTER(DenoiseGuides), C.POINTER(DenoiseParams), C.c_uint32, C.c_uint32, C.c_void_p]
         lib.rt_refract_enter.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p]
         lib.rt_refract_step.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -19,6 +19,7 @@
 #include "../rt_vec.h"
 #include "../rt_luma.h"
 #include "../rt_film.h"
+#include "../rt_denoise.h"
 
 using rt::V3;
 
@@ -578,6 +579,40 @@ int rt_film_splat_host(uint32_t rows, uint32_t cols, const float *samples, const
             sum[3 * i + 2] = a.s2;
             weight[i] = a.w;
         }
+    return RT_OK;
+}
+
+/* ---- denoise queries: the CPU definition (include/rt_amd.h "denoise queries"; the arithmetic is rt_denoise.h's, shared with the device) ---- */
+
+int rt_denoise_atrous_cpu(const float *color, const rt_denoise_guides *guides, const rt_denoise_params *params, uint32_t rows, uint32_t cols,
+                          float *out, float *temp) {
+    const char *bad = rt::denoise_limits(color, guides, params, rows, cols, out, temp, true);
+    if (bad) return fail(RT_ERR_INVALID_ARGUMENT, std::string("rt_denoise_atrous_cpu: ") + bad);
+    if (rows == 0u || cols == 0u) return RT_OK;
+    for (uint32_t j = 0; j < params->n_levels; ++j) {
+        const rt::DenoiseLevel L = rt::denoise_level(color, *guides, *params, rows, cols, out, temp, j);
+        for (uint32_t r = 0; r < rows; ++r)
+            for (uint32_t c = 0; c < cols; ++c) {
+                const uint64_t i = (uint64_t)r * cols + c;
+                const bool filtered = rt::denoise_valid(L, i);
+                rt::DenoiseAcc a = {0.0f, 0.0f, 0.0f, 0.0f};
+                if (filtered) {
+                    const rt::DenoisePix p = rt::denoise_load(L, i);
+                    for (int dr = -2; dr <= 2; ++dr) {
+                        const int64_t qr = (int64_t)r + (int64_t)dr * L.step;
+                        if (qr < 0 || qr >= (int64_t)rows) continue;
+                        for (int dc = -2; dc <= 2; ++dc) {
+                            const int64_t qc = (int64_t)c + (int64_t)dc * L.step;
+                            if (qc < 0 || qc >= (int64_t)cols) continue;
+                            const uint64_t qi = (uint64_t)qr * cols + (uint64_t)qc;
+                            if (!rt::denoise_valid(L, qi)) continue;
+                            rt::denoise_tap(L, a, p, rt::denoise_load(L, qi), dr, dc);
+                        }
+                    }
+                }
+                rt::denoise_store(L, i, filtered, a);
+            }
+    }
     return RT_OK;
 }
 

@@ -133,7 +133,9 @@ struct KernelQueues {
     X(OPT_DIAG_HIT_BAND_RECORDS, "RT_AMD_DIAG_HIT_BAND_RECORDS") /* test hook: the hit queries (rt_shade_hits / rt_reflect_rays / rt_refract_rays) launch at most this many records at a time, rounded up to whole 64-record chunks (default: 2^26) */ \
     X(OPT_SCATTER_PREPARE, "RT_AMD_SCATTER_PREPARE")       /* rt_scatter_hits: 1 runs the look-ahead pass ahead of its kernel, so that a dry generator only switches banks; 0 leaves IsaacCore::generate to the kernel's lane (DESIGN.md 3.11 has the A/B) */ \
     X(OPT_FILM_SPLAT_FORM, "RT_AMD_FILM_SPLAT_FORM")       /* rt_film_splat: 0 the simple gather from global memory, 1 the tiled gather from LDS (same bits; DESIGN.md 3.20 has the A/B) */ \
-    X(OPT_DIAG_FILM_MAX_GROUPS, "RT_AMD_DIAG_FILM_MAX_GROUPS") /* test hook: rt_film_splat launches at most this many workgroups (default and most: 2^16), the rest of the image taken grid-stride */
+    X(OPT_DIAG_FILM_MAX_GROUPS, "RT_AMD_DIAG_FILM_MAX_GROUPS") /* test hook: rt_film_splat launches at most this many workgroups (default and most: 2^16), the rest of the image taken grid-stride */ \
+    X(OPT_DENOISE_FORM, "RT_AMD_DENOISE_FORM")             /* rt_denoise_atrous: 0 the simple gather from global memory, 1 the tiled gather from LDS (same bits; DESIGN.md 3.21 has the A/B) */ \
+    X(OPT_DIAG_DENOISE_MAX_GROUPS, "RT_AMD_DIAG_DENOISE_MAX_GROUPS") /* test hook: a level of rt_denoise_atrous launches at most this many workgroups (default and most: 2^16), the rest of the image taken grid-stride */
 #define RT_OPTION_ID(id, name) id,
 enum Option : int { RT_OPTIONS(RT_OPTION_ID) OPT_COUNT };
 #undef RT_OPTION_ID

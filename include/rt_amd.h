@@ -1079,6 +1079,93 @@ int rt_camera_rays_offset_host(const rt_camera *camera, const rt_frame *frame, c
 int rt_film_splat(uint32_t rows, uint32_t cols, const float *d_samples, const unsigned char *d_valid, const float *d_offsets, uint32_t spp,
                   uint32_t filter, float radius, float *d_sum, float *d_weight, void *hip_stream);
 
+/* ---- denoise queries: an edge-avoiding A-Trous filter on guide planes ------------------------------
+
+ * What turns the noisy image of a few stochastic epochs into a clean one on the device: the edge-avoiding A-Trous wavelet filter
+ * (Dammertz, Sewtz, Hanika, Lensch: "Edge-Avoiding A-Trous Wavelet Transform for fast Global Illumination Filtering", HPG 2010), one
+ * level per kernel launch, guided by the planes rt_material_hits already produces (shading normal, position, albedo, valid):
+ *     rt_render_distributed / rt_film_splat -> resolve -> rt_camera_rays -> rt_cast_rays -> rt_material_hits -> rt_denoise_atrous -> rt_post_process_device
+ * The reference has no denoiser; the definition below is the contract.  It is written once (csrc/rt_denoise.h) and compiled into both
+ * libraries without contraction, so rt_denoise_atrous (both kernel forms, any launch geometry), rt_denoise_atrous_host and
+ * rt_denoise_atrous_cpu (librt_host.so, include/rt_host.h) return the same bits.  Every device call is stream-ordered and asynchronous on
+ * hip_stream, allocates nothing, visits the host for nothing, and may be captured into a HIP graph at once.  Each output pixel is written
+ * by one thread, which walks its 25 sources in a fixed order: no atomics, nothing depends on the launch.
+ *
+ * The image is ONE compact array of rows x cols pixels, 3 f32 each, pixel i = r * cols + c.  A guide plane is a base pointer and a
+ * record stride in 4-byte WORDS: pixel i's values are base[i * stride + 0 .. width - 1] (width 3 for normal, position and albedo, 1 for
+ * valid), so the fields of rt_hit (13 words) and rt_surface (18 words) records are passed where they lie — e.g. position =
+ * (const float *)hits + 3, stride 13; normal = (const float *)surfaces + 14, albedo = (const float *)surfaces + 3, valid =
+ * (const uint32_t *)surfaces + 17, stride 18.  Stride 3 (1 for valid) is the compact plane.  Any guide pointer may be NULL: that term of
+ * the exponent is left out / every pixel is valid.
+ *
+ * One level l (0 <= l <= 5), step s = 1 << l, input plane `in`, for output pixel p = (r, c); every operation is a single f32 operation
+ * in the order written, none fused, unless it says binary64:
+ *   1. the colour seen at a pixel q:  C_q[k] = in[3 q + k];  when the level demodulates its input, C_q[k] = in[3 q + k] / (albedo_q[k] + 1e-3f)
+ *   2. p passes through — out[3 p + k] = in[3 p + k], the raw words, no other arithmetic — when valid is not NULL and valid_p == 0
+ *   3. otherwise sum_0 = sum_1 = sum_2 = wsum = +0, and for dr = -2 .. 2 (outer), dc = -2 .. 2 (inner), both ascending:
+ *        q = (r + dr * s, c + dc * s);  skipped when outside the image, or when valid is not NULL and valid_q == 0
+ *        dist2(a, b):  d_k = a[k] - b[k];  (d_0 * d_0 + d_1 * d_1) + d_2 * d_2
+ *        x = dist2(C_p, C_q) / sc2;   if normal:  x = x + dist2(n_p, n_q) / sn2;   if position:  x = x + dist2(P_p, P_q) / sp2
+ *            where sc = sigma_color * 2^-(l - first_level) (an exact multiply by a power of two), sc2 = sc * sc,
+ *            sn2 = sigma_normal * sigma_normal, sp2 = sigma_position * sigma_position;  a sigma of +inf makes its term +0
+ *        skipped unless x >= 0  (so a NaN x — a NaN colour or guide on either side — skips the tap)
+ *        e = x > 100 ? +0 : (float)rtdm::exp_mid(-(double)x)     binary64 exponential of csrc/rt_detmath.h (+ - * / only), rounded once
+ *        w = h[dr + 2] * h[dc + 2] * e                           h = {1/16, 1/4, 3/8, 1/4, 1/16}, the B3 spline, exact in f32
+ *        sum_k = sum_k + C_q[k] * w  (the product rounded, then added; k = 0, 1, 2);   wsum = wsum + w
+ *   4. if wsum > 0:  out[3 p + k] = sum_k / wsum, times (albedo_p[k] + 1e-3f) when the level remodulates its output;
+ *      otherwise (a NaN centre colour, for one) p passes through as in 2.
+ * A tap with x > 100 still takes part, with w = +0: it changes nothing unless C_q is infinite (Inf * 0 = NaN) — mark such pixels invalid.
+ *
+ * A call runs levels first_level .. first_level + n_levels - 1, each reading the previous one's output; the planes alternate between
+ * d_out and d_temp so that the LAST level writes d_out; d_color is only read.  flags: RT_DENOISE_DEMODULATE_IN makes the call's first
+ * level demodulate its input (step 1), RT_DENOISE_DEMODULATE_OUT makes its last level remodulate its output (step 4);
+ * RT_DENOISE_DEMODULATE is both — the filter then works on irradiance and leaves texture detail alone.  The levels in between work on what
+ * the previous level wrote.  Consequence: one call of n levels equals n calls of one level each, level j (0-based) of them with
+ * first_level + j, sigma_color * 2^-j (sigma_color is the sigma of the CALL's first level), and DEMODULATE_IN on the first call only,
+ * DEMODULATE_OUT on the last only.
+ * Checked before any device work, all RT_ERR_INVALID_ARGUMENT with a message that names the argument: a null guides or params; rows * cols
+ * >= 2^32; n_levels < 1 or first_level + n_levels > 6; a sigma that is not > 0 (NaN included; +inf is legal); unknown flag bits; a
+ * demodulation flag without an albedo plane; a stride smaller than its plane's width; a null d_color or d_out; a null d_temp with
+ * n_levels >= 2; d_out or d_temp equal to d_color or to each other.  rows == 0 or cols == 0 is RT_OK and launches nothing.
+ * Not covered: variance-guided sigmas (SVGF), temporal accumulation, halos between the bands of a sharded frame (pixels beyond the
+ * edge of the array do not exist), rt_multi_* forms. */
+
+#define RT_DENOISE_DEMODULATE_IN 1u
+#define RT_DENOISE_DEMODULATE_OUT 2u
+#define RT_DENOISE_DEMODULATE 3u
+#define RT_DENOISE_MAX_LEVELS 6u
+
+typedef struct rt_denoise_guides {
+    const float *normal;      /* 3 f32 per pixel, or NULL */
+    const float *position;    /* 3 f32 per pixel, or NULL */
+    const float *albedo;      /* 3 f32 per pixel, or NULL; needed by the demodulation flags only */
+    const uint32_t *valid;    /* 1 word per pixel, 0: the pixel is neither filtered nor a source; or NULL */
+    uint32_t normal_stride;   /* record strides in 4-byte words: >= 3 ... */
+    uint32_t position_stride;
+    uint32_t albedo_stride;
+    uint32_t valid_stride;    /* ... >= 1; the stride of a NULL plane is not looked at */
+} rt_denoise_guides;         /* 48 bytes */
+
+typedef struct rt_denoise_params {
+    float sigma_color;        /* of the call's first level; halves with every further level */
+    float sigma_normal;
+    float sigma_position;     /* each > 0, +inf: the term is off */
+    uint32_t first_level;
+    uint32_t n_levels;        /* first_level + n_levels <= RT_DENOISE_MAX_LEVELS */
+    uint32_t flags;           /* RT_DENOISE_DEMODULATE_* */
+} rt_denoise_params;         /* 24 bytes */
+
+/* what d_temp of rt_denoise_atrous must hold: one colour plane, rows * cols * 12 bytes (no guide is repacked) */
+size_t rt_denoise_temp_bytes(uint32_t rows, uint32_t cols);
+/* d_color, d_out, d_temp: rows * cols * 3 f32 on the device, three different buffers; one kernel launch per level */
+int rt_denoise_atrous(const float *d_color, const rt_denoise_guides *guides, const rt_denoise_params *params, uint32_t rows, uint32_t cols,
+                      float *d_out, float *d_temp, void *hip_stream);
+/* The same kernels on HOST arrays (the pointers of `guides` are host pointers too): allocates, uploads every plane with its stride,
+ * runs, synchronises the device and downloads h_out.  No h_temp: the round trip makes its own.  NOT the CPU definition — that is
+ * rt_denoise_atrous_cpu of librt_host.so, which needs no device; this one is how a caller without device buffers runs the kernels. */
+int rt_denoise_atrous_host(const float *h_color, const rt_denoise_guides *guides, const rt_denoise_params *params, uint32_t rows, uint32_t cols,
+                           float *h_out);
+
 /* ---- diagnostics ------------------------------------------------------------ */
 
 /* Which kernel renders the Whitted pass (process-wide; same results bit for bit):
@@ -1095,7 +1182,8 @@ int rt_film_splat(uint32_t rows, uint32_t cols, const float *d_samples, const un
  * named like the environment variable that seeds it — RT_AMD_DIST_PIPELINE, RT_AMD_DIST_WS_MB, RT_AMD_RNG_LOOKAHEAD,
  * RT_AMD_DIST_BY_COST, RT_AMD_DIST_OWN_FIRST, RT_AMD_DIST_PREP_FIRST, RT_AMD_DIST_SPLIT, RT_AMD_DIAG_WS_REFUSE,
  * RT_AMD_MULTI_FORCE_STAGE, RT_AMD_BFS_WALK_TRIANGLES (read by rt_scene_create), RT_AMD_WF_SHARE, RT_AMD_DIAG_BFS_CAP,
- * RT_AMD_DIAG_DIST_BAND_RAYS, RT_AMD_QUERY_WAVE_UNIFORM, RT_AMD_DIAG_HIT_BAND_RECORDS, RT_AMD_FILM_SPLAT_FORM, RT_AMD_DIAG_FILM_MAX_GROUPS (INTEGRATION.md says what each does); any other name is RT_ERR_INVALID_ARGUMENT.  The environment is read ONCE per process, at the first use;
+ * RT_AMD_DIAG_DIST_BAND_RAYS, RT_AMD_QUERY_WAVE_UNIFORM, RT_AMD_DIAG_HIT_BAND_RECORDS, RT_AMD_FILM_SPLAT_FORM, RT_AMD_DIAG_FILM_MAX_GROUPS,
+ * RT_AMD_DENOISE_FORM, RT_AMD_DIAG_DENOISE_MAX_GROUPS (INTEGRATION.md says what each does); any other name is RT_ERR_INVALID_ARGUMENT.  The environment is read ONCE per process, at the first use;
  * after that only this call changes a switch: value = decimal integer, NULL or "" = unset (the library's own choice).  Render
  * calls read the switches without locks: set them between calls, not during one. */
 int rt_set_option(const char *name, const char *value);

@@ -101,6 +101,14 @@ int rt_film_offsets_host(const rt_frame *frame, uint32_t spp, uint32_t pattern, 
 int rt_film_splat_host(uint32_t rows, uint32_t cols, const float *samples, const uint8_t *valid, const float *offsets, uint32_t spp,
                        uint32_t filter, float radius, float *sum, float *weight);
 
+/* The denoise queries' CPU definition (include/rt_amd.h "denoise queries" states every operation and the order): the plain nested loops
+ * over host arrays, no device needed, bit-identical to rt_denoise_atrous of librt_amd.so.  Same arguments without the stream, same
+ * checks with the same messages; a failure returns a negative rt_status and sets rt_host_last_error().  It is called _cpu, not _host as
+ * the film's CPU forms are, because librt_amd.so already exports rt_denoise_atrous_host: that one is the round trip through the
+ * KERNELS on host buffers, this one the definition they are tested against. */
+int rt_denoise_atrous_cpu(const float *color, const rt_denoise_guides *guides, const rt_denoise_params *params, uint32_t rows, uint32_t cols,
+                          float *out, float *temp);
+
 /* RGB8 PNG, written to "<path>.tmp" then renamed over path. */
 int rt_write_png(const char *path, const uint8_t *rgb8, uint32_t width, uint32_t height);
 
