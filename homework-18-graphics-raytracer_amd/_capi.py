@@ -178,6 +178,22 @@ class DenoiseParams(C.Structure):
                 ("first_level", C.c_uint32), ("n_levels", C.c_uint32), ("flags", C.c_uint32)]
 
 
+class TemporalPixel(C.Structure):
+    """rt_temporal_pixel: one 32-byte history record"""
+    _fields_ = [("color", C.c_float * 3), ("moment1", C.c_float), ("moment2", C.c_float), ("length", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class TemporalGuides(C.Structure):
+    """rt_temporal_guides: a base pointer and a record stride in 4-byte words per guide plane; a null pointer leaves the plane out"""
+    _fields_ = [("normal", C.c_void_p), ("position", C.c_void_p), ("object", C.c_void_p), ("valid", C.c_void_p),
+                ("normal_stride", C.c_uint32), ("position_stride", C.c_uint32), ("object_stride", C.c_uint32), ("valid_stride", C.c_uint32)]
+
+
+class TemporalParams(C.Structure):
+    """rt_temporal_params"""
+    _fields_ = [("normal_min", C.c_float), ("position_max", C.c_float), ("alpha_min", C.c_float), ("max_length", C.c_uint32), ("flags", C.c_uint32)]
+
+
 AMD_SYMBOLS = [
     "rt_abi_version", "rt_last_error", "rt_device_count", "rt_set_device", "rt_frame_rows", "rt_frame_pixels",
     "rt_scene_create", "rt_scene_destroy", "rt_render_whitted", "rt_render_whitted_host", "rt_set_option", "rt_set_variant",
@@ -193,6 +209,7 @@ AMD_SYMBOLS = [
     "rt_material_hits", "rt_material_hits_host", "rt_probe_surfaces", "rt_probe_surfaces_host",
     "rt_film_offsets", "rt_camera_rays_offset", "rt_camera_rays_offset_host", "rt_film_splat",
     "rt_denoise_temp_bytes", "rt_denoise_atrous", "rt_denoise_atrous_host",
+    "rt_temporal_motion", "rt_temporal_accumulate", "rt_temporal_motion_host", "rt_temporal_accumulate_host",
     "rt_refract_enter", "rt_refract_step",
     "rt_scene_update_vertices", "rt_scene_update_spheres", "rt_scene_update_lights", "rt_scene_update_materials",
     "rt_ray_keys", "rt_sort_temp_bytes", "rt_sort_records", "rt_gather_records", "rt_scatter_records",
@@ -205,6 +222,7 @@ HOST_SYMBOLS = [
     "rt_world_build_reference_scene", "rt_world_save_scene", "rt_world_load_scene", "rt_reference_camera", "rt_world_desc", "rt_frame_full", "rt_post_process", "rt_luma_row",
     "rt_encode_srgb8", "rt_accumulate", "rt_accumulator_resolve", "rt_write_png", "rt_host_last_error",
     "rt_film_offsets_host", "rt_film_splat_host", "rt_denoise_atrous_cpu",
+    "rt_temporal_motion_cpu", "rt_temporal_accumulate_cpu",
 ]
 
 _amd = None
@@ -253,6 +271,9 @@ def host_lib() -> C.CDLL:
         lib.rt_film_splat_host.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p,
                                            C.c_void_p]
         lib.rt_denoise_atrous_cpu.argtypes = [C.c_void_p, C.POINTER(DenoiseGuides), C.POINTER(DenoiseParams), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+        lib.rt_temporal_motion_cpu.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(Camera), C.POINTER(Frame), C.c_void_p]
+        lib.rt_temporal_accumulate_cpu.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(TemporalGuides), C.POINTER(TemporalGuides), C.POINTER(TemporalParams),
+                                                   C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.rt_write_png.argtypes = [C.c_char_p, C.c_void_p, C.c_uint32, C.c_uint32]
         lib.rt_host_last_error.restype = C.c_char_p
         _host = lib
@@ -371,6 +392,12 @@ def amd_lib() -> C.CDLL:
         lib.rt_denoise_atrous.argtypes = [C.c_void_p, C.POINTER(DenoiseGuides), C.POINTER(DenoiseParams), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
                                           C.c_void_p]
         lib.rt_denoise_atrous_host.argtypes = [C.c_void_p, C.POINTER(DenoiseGuides), C.POINTER(DenoiseParams), C.c_uint32, C.c_uint32, C.c_void_p]
+        lib.rt_temporal_motion.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(Camera), C.POINTER(Frame), C.c_void_p, C.c_void_p]
+        lib.rt_temporal_motion_host.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(Camera), C.POINTER(Frame), C.c_void_p]
+        lib.rt_temporal_accumulate.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(TemporalGuides), C.POINTER(TemporalGuides), C.POINTER(TemporalParams),
+                                               C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.rt_temporal_accumulate_host.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(TemporalGuides), C.POINTER(TemporalGuides), C.POINTER(TemporalParams),
+                                                    C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.rt_refract_enter.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p]
         lib.rt_refract_step.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

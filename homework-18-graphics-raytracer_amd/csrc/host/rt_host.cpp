@@ -20,6 +20,7 @@
 #include "../rt_luma.h"
 #include "../rt_film.h"
 #include "../rt_denoise.h"
+#include "../rt_temporal.h"
 
 using rt::V3;
 
@@ -613,6 +614,34 @@ int rt_denoise_atrous_cpu(const float *color, const rt_denoise_guides *guides, c
                 rt::denoise_store(L, i, filtered, a);
             }
     }
+    return RT_OK;
+}
+
+/* ---- temporal queries: the CPU definition (include/rt_amd.h "temporal queries"; the arithmetic is rt_temporal.h's, shared with the device) ---- */
+
+int rt_temporal_motion_cpu(const float *position, uint32_t position_stride, const uint32_t *valid, uint32_t valid_stride, const rt_camera *prev_camera,
+                           const rt_frame *prev_frame, float *motion) {
+    int status;
+    const char *bad = rt::temporal_motion_limits(position, position_stride, valid, valid_stride, prev_camera, prev_frame, motion, &status);
+    if (bad) return fail(status, std::string("rt_temporal_motion_cpu: ") + bad);
+    rt::TemporalMotion m;
+    m.cam = rt::temporal_camera(prev_camera, prev_frame);
+    m.position = position, m.valid = valid, m.position_stride = position_stride, m.valid_stride = valid_stride, m.motion = motion;
+    m.n = (uint64_t)prev_frame->width * prev_frame->height;
+    for (uint64_t i = 0; i < m.n; ++i) rt::temporal_project(m, i);
+    return RT_OK;
+}
+
+int rt_temporal_accumulate_cpu(const float *color, const float *motion, const rt_temporal_guides *current, const rt_temporal_guides *previous,
+                               const rt_temporal_params *params, uint32_t rows, uint32_t cols, const rt_temporal_pixel *history_in,
+                               rt_temporal_pixel *history_out, float *variance) {
+    int status;
+    const char *bad = rt::temporal_limits(color, motion, current, previous, params, rows, cols, history_in, history_out, false, &status);
+    if (bad) return fail(status, std::string("rt_temporal_accumulate_cpu: ") + bad);
+    if (rows == 0u || cols == 0u) return RT_OK;
+    const rt::TemporalCall t = rt::temporal_call(color, motion, *current, *previous, *params, rows, cols, history_in, history_out, variance);
+    const uint64_t n = (uint64_t)rows * cols;
+    for (uint64_t i = 0; i < n; ++i) rt::temporal_pixel(t, i);
     return RT_OK;
 }
 

@@ -9,6 +9,7 @@
  * RT_ERR_NO_DEVICE / RT_ERR_HIP.
  */
 #include "rt_api_internal.h"
+#include "rt_temporal.h"
 
 /* Process-wide settings (rt_set_*): read by render calls on any thread, so they are atomics.  A value < 0 means "not set
  * yet": the first reader resolves it from the environment (two threads doing that at once compute the same value). */
@@ -426,14 +427,9 @@ int make_kernel_frame(const rt_camera *camera, const rt_frame *frame, rt::Kernel
     if (frame->max_depth > RT_MAX_DEPTH) return fail(RT_ERR_UNSUPPORTED, "render: max_depth above RT_MAX_DEPTH");
     /* max_depth < 0 is valid and renders as 0: TraceState.depth is an i32 tested with `depth <= 0` (main.rs:488, 669) */
     using rt::V3;
-    /* Camera::shoot, main.rs:85-92: the ray-independent part */
-    const V3 toward = rt::normalize(rt::v3p(camera->toward));
-    const V3 right = rt::normalize(rt::cross(toward, rt::v3p(camera->up)));
-    const V3 up = rt::normalize(rt::cross(right, toward));
-    const float th = rtdm::tanf(camera->fovy / 2.0f);
-    const V3 x = th * right;
-    const V3 y = th * up;
-    const V3 origin = rt::v3p(camera->center) + toward * camera->near;
+    /* Camera::shoot, main.rs:85-92: the ray-independent part (rt_temporal.h camera_basis, shared with librt_host.so) */
+    const rt::CameraBasis basis = rt::camera_basis(camera);
+    const V3 toward = basis.toward, x = basis.x, y = basis.y, origin = basis.origin;
     kf->cols = frame->x1 - frame->x0;
     kf->rows = rt_frame_rows(frame);
     kf->x0 = frame->x0;

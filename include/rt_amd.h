@@ -1166,6 +1166,114 @@ int rt_denoise_atrous(const float *d_color, const rt_denoise_guides *guides, con
 int rt_denoise_atrous_host(const float *h_color, const rt_denoise_guides *guides, const rt_denoise_params *params, uint32_t rows, uint32_t cols,
                            float *h_out);
 
+/* ---- temporal queries: reprojected history with luminance moments --------------------------------
+
+ * What lies between two frames of a sequence: where each pixel's surface point was in the previous frame (rt_temporal_motion), and the
+ * previous frame's accumulated colour gathered from there and blended with the current one, with the first two moments of luminance
+ * (rt_temporal_accumulate) — the temporal half of Schied et al., "Spatiotemporal Variance-Guided Filtering" (HPG 2017):
+ *     ... resolve -> rt_camera_rays -> rt_cast_rays -> rt_material_hits -> rt_temporal_motion -> rt_temporal_accumulate -> rt_denoise_atrous -> rt_post_process_device
+ * The reference has no counterpart; the definition below is the contract.  It is written once (csrc/rt_temporal.h) and compiled into
+ * both libraries without contraction, with no libm call and no device intrinsic, so rt_temporal_motion / rt_temporal_accumulate (any
+ * launch geometry), their _host forms and rt_temporal_motion_cpu / rt_temporal_accumulate_cpu (librt_host.so, include/rt_host.h) return
+ * the same bits.  Each device call is ONE stream-ordered kernel launch on hip_stream, allocates nothing, visits the host for nothing and
+ * may be captured into a HIP graph at once.  One thread per output pixel, grid-stride; a pixel is written by one thread: no atomics.
+ *
+ * Planes are those of the denoise queries: a base pointer and a record stride in 4-byte WORDS, pixel i = r * cols + c at
+ * base[i * stride + 0 .. width - 1] (width 3 for normal and position, 1 for object and valid), so rt_hit (13 words) and rt_surface (18
+ * words) fields are passed where they lie: position = (const float *)hits + 3 and object = (const uint32_t *)hits + 2, stride 13;
+ * normal = (const float *)surfaces + 14 and valid = (const uint32_t *)surfaces + 17, stride 18.  dot(a, b) is (a0*b0 + a1*b1) + a2*b2.
+ * Every operation is a single f32 operation in the order written, none fused.
+ *
+ * rt_temporal_motion, for pixel i of the FULL previous frame (x0 = y0 = 0, x1 = width, y1 = height, y_step = 1; rows = height, cols =
+ * width), with origin, cam_x, cam_y, cam_toward, half_width, half_height, height_f the camera basis every primary ray is shot with (of
+ * prev_camera and prev_frame), P = position_i:
+ *   1. v = P - origin
+ *   2. z = dot(v, cam_toward)
+ *   3. tt = dot(cam_x, cam_x)
+ *   4. clip_x = dot(v, cam_x) / (z * tt)
+ *   5. clip_y = dot(v, cam_y) / (z * tt)
+ *   6. px = clip_x * height_f + half_width
+ *   7. py = half_height - clip_y * height_f
+ * the inverse of the primary ray through the image position (px, py).  motion_i = (px, py), 2 f32, in previous-frame pixel
+ * coordinates; (NaN, NaN) (0x7fc00000) where valid is not NULL and valid_i == 0, or where z > 0 is false.  For a static scene position
+ * is the current frame's position plane; for moving geometry the caller passes its own plane of where each point WAS in the previous
+ * frame (deriving that plane from rt_scene_update_vertices is not provided).  A caller may also write the motion plane itself.
+ *
+ * rt_temporal_accumulate, for output pixel p with current colour C = color[3 p + k], L = lum(C) = (0.2126f * C0 + 0.7152f * C1) +
+ * 0.0722f * C2 and (px, py) = motion_p; history records are rt_temporal_pixel, read from history_in and written to history_out:
+ *   1. p RESETS when current.valid is not NULL and valid_p == 0, or when any of px >= -1, px < (float)cols, py >= -1, py < (float)rows
+ *      is false — float tests, made before any conversion to integer, false for a NaN, so 1e30 is refused, not wrapped.  A reset writes
+ *      color = C (the raw words: a NaN keeps its payload), moment1 = L, moment2 = L * L, length = 1, and variance 0.
+ *   2. otherwise fx = floor(px) (the truncation (float)(int64)px, less 1 where that is > px), wx = px - fx, likewise fy, wy; four taps
+ *      q = (fy + j, fx + i), j = 0, 1 outer, i = 0, 1 inner, with b = (i ? wx : 1 - wx) * (j ? wy : 1 - wy).  A tap is skipped when
+ *      b > 0 is false; when it lies outside the image; when previous.valid is not NULL and its word at q is 0; when history_in[q].length
+ *      is 0; when object planes are given and previous.object_q != current.object_p; when normal planes are given and
+ *      dot(n_p, n_q) >= normal_min is false; when position planes are given and, with d = P_p - P_q, dot(d, d) <= position_max *
+ *      position_max is false (P_p is current.position — where the point was — and P_q previous.position at the tap).  An accepted tap
+ *      adds: sum_k = sum_k + b * color_q[k], s1 = s1 + b * moment1_q, s2 = s2 + b * moment2_q, bsum = bsum + b (each product rounded
+ *      before its add), and its length to the running minimum.  A NaN in an accepted tap's history propagates; nothing special-cases it.
+ *   3. if bsum > 0 is false, p resets as in 1.
+ *   4. otherwise H = sum / bsum (five divides), n = min(minimum length + 1, max_length) in integers, a = 1.0f / (float)n,
+ *      alpha = a > alpha_min ? a : alpha_min, and out = H * (1 - alpha) + X * alpha for the three colours and the two moments with
+ *      X = C_k, L, L * L;  length = n;  reserved words 0.
+ *   5. variance_p (when d_variance is not NULL) = v > 0 ? v : +0 with v = moment2 - moment1 * moment1 of the record just written.
+ * Consequences: integer (px, py) leaves one tap with b = 1, so H is that record exactly; with alpha_min = 0 and integer coordinates k
+ * frames are the running mean written as the blend of 4; with max_length = 1 alpha is 1 and a finite history leaves the current frame.
+ * A guide plane other than valid is either given in BOTH sets or NULL in both (its test is then off); valid may be NULL in either.
+ * Checked before any device work, in this order, RT_ERR_INVALID_ARGUMENT unless said: rows * cols >= 2^32 (RT_ERR_UNSUPPORTED); rows ==
+ * 0 or cols == 0 is RT_OK and launches nothing; a null guide set, params, color, motion, history_in or history_out; a stride smaller
+ * than its plane's width; history_out == history_in; (device forms) a history array that is not 16-byte aligned; max_length < 1;
+ * alpha_min outside [0, 1]; position_max >= 0 false; flags != 0; a plane given in one set and NULL in the other.  rt_temporal_motion: a
+ * null camera or frame; a frame that is not the full frame; width * height >= 2^32 (RT_ERR_UNSUPPORTED); an empty frame is RT_OK; a null
+ * position or motion; a stride smaller than its plane's width.
+ * Not covered: the variance-guided A-Trous that reads the variance plane; a spatial variance estimate for short histories; motion of
+ * moving geometry derived from scene updates; tiles and banded frames; rt_multi_* forms; clamping history to the neighbourhood's
+ * colour box. */
+
+typedef struct rt_temporal_pixel {
+    float color[3];           /* the accumulated colour */
+    float moment1;            /* ... luminance */
+    float moment2;            /* ... squared luminance */
+    uint32_t length;          /* frames accumulated, 1 .. max_length; 0: no history here (an array of zero bytes is an empty history) */
+    uint32_t reserved[2];     /* written 0 */
+} rt_temporal_pixel;         /* 32 bytes: a tap's history is two 16-byte loads */
+
+typedef struct rt_temporal_guides {
+    const float *normal;      /* 3 f32 per pixel, or NULL */
+    const float *position;    /* 3 f32 per pixel, or NULL */
+    const uint32_t *object;   /* 1 word per pixel, or NULL */
+    const uint32_t *valid;    /* 1 word per pixel, 0: current — the pixel resets, previous — the pixel is no tap; or NULL */
+    uint32_t normal_stride;   /* record strides in 4-byte words: >= 3 ... */
+    uint32_t position_stride;
+    uint32_t object_stride;   /* ... >= 1 */
+    uint32_t valid_stride;    /* the stride of a NULL plane is not looked at */
+} rt_temporal_guides;        /* 48 bytes */
+
+typedef struct rt_temporal_params {
+    float normal_min;         /* a tap passes when dot(n_p, n_q) >= normal_min */
+    float position_max;       /* ... and |P_p - P_q| <= position_max; >= 0, +inf: every distance passes */
+    float alpha_min;          /* the least weight of the current frame, in [0, 1]; 0: the running mean up to max_length */
+    uint32_t max_length;      /* >= 1 */
+    uint32_t flags;           /* reserved: 0 */
+} rt_temporal_params;        /* 20 bytes */
+
+/* d_position (and d_valid, or NULL): planes of prev_frame->width * height pixels; d_motion: 2 f32 per pixel, compact; one kernel launch */
+int rt_temporal_motion(const float *d_position, uint32_t position_stride, const uint32_t *d_valid, uint32_t valid_stride,
+                       const rt_camera *prev_camera, const rt_frame *prev_frame, float *d_motion, void *hip_stream);
+/* d_color: rows * cols * 3 f32, d_motion: rows * cols * 2 f32, d_history_in / d_history_out: rows * cols records, two different arrays a
+ * caller ping-pongs, 16-byte aligned; d_variance: rows * cols f32, or NULL; one kernel launch.  Nothing but d_history_out and d_variance
+ * is written. */
+int rt_temporal_accumulate(const float *d_color, const float *d_motion, const rt_temporal_guides *current, const rt_temporal_guides *previous,
+                           const rt_temporal_params *params, uint32_t rows, uint32_t cols, const rt_temporal_pixel *d_history_in,
+                           rt_temporal_pixel *d_history_out, float *d_variance, void *hip_stream);
+/* The same kernels on HOST arrays (the pointers of the guide sets are host pointers too): allocate, upload every plane with its
+ * stride, run, synchronise the device and download.  NOT the CPU definition — that is rt_temporal_*_cpu of librt_host.so. */
+int rt_temporal_motion_host(const float *h_position, uint32_t position_stride, const uint32_t *h_valid, uint32_t valid_stride,
+                            const rt_camera *prev_camera, const rt_frame *prev_frame, float *h_motion);
+int rt_temporal_accumulate_host(const float *h_color, const float *h_motion, const rt_temporal_guides *current, const rt_temporal_guides *previous,
+                                const rt_temporal_params *params, uint32_t rows, uint32_t cols, const rt_temporal_pixel *h_history_in,
+                                rt_temporal_pixel *h_history_out, float *h_variance);
+
 /* ---- diagnostics ------------------------------------------------------------ */
 
 /* Which kernel renders the Whitted pass (process-wide; same results bit for bit):
@@ -1183,7 +1291,7 @@ int rt_denoise_atrous_host(const float *h_color, const rt_denoise_guides *guides
  * RT_AMD_DIST_BY_COST, RT_AMD_DIST_OWN_FIRST, RT_AMD_DIST_PREP_FIRST, RT_AMD_DIST_SPLIT, RT_AMD_DIAG_WS_REFUSE,
  * RT_AMD_MULTI_FORCE_STAGE, RT_AMD_BFS_WALK_TRIANGLES (read by rt_scene_create), RT_AMD_WF_SHARE, RT_AMD_DIAG_BFS_CAP,
  * RT_AMD_DIAG_DIST_BAND_RAYS, RT_AMD_QUERY_WAVE_UNIFORM, RT_AMD_DIAG_HIT_BAND_RECORDS, RT_AMD_FILM_SPLAT_FORM, RT_AMD_DIAG_FILM_MAX_GROUPS,
- * RT_AMD_DENOISE_FORM, RT_AMD_DIAG_DENOISE_MAX_GROUPS (INTEGRATION.md says what each does); any other name is RT_ERR_INVALID_ARGUMENT.  The environment is read ONCE per process, at the first use;
+ * RT_AMD_DENOISE_FORM, RT_AMD_DIAG_DENOISE_MAX_GROUPS, RT_AMD_DIAG_TEMPORAL_MAX_GROUPS (INTEGRATION.md says what each does); any other name is RT_ERR_INVALID_ARGUMENT.  The environment is read ONCE per process, at the first use;
  * after that only this call changes a switch: value = decimal integer, NULL or "" = unset (the library's own choice).  Render
  * calls read the switches without locks: set them between calls, not during one. */
 int rt_set_option(const char *name, const char *value);

@@ -109,6 +109,17 @@ int rt_film_splat_host(uint32_t rows, uint32_t cols, const float *samples, const
 int rt_denoise_atrous_cpu(const float *color, const rt_denoise_guides *guides, const rt_denoise_params *params, uint32_t rows, uint32_t cols,
                           float *out, float *temp);
 
+/* The temporal queries' CPU definition (include/rt_amd.h "temporal queries" states every operation and the order): plain loops over
+ * host arrays, no device needed, bit-identical to rt_temporal_motion / rt_temporal_accumulate of librt_amd.so.  Same arguments without
+ * the stream, same checks with the same messages (the history arrays need no alignment here); a failure returns a negative rt_status
+ * and sets rt_host_last_error().  Called _cpu for the reason rt_denoise_atrous_cpu is: the _host names are librt_amd.so's round trips
+ * through the kernels. */
+int rt_temporal_motion_cpu(const float *position, uint32_t position_stride, const uint32_t *valid, uint32_t valid_stride,
+                           const rt_camera *prev_camera, const rt_frame *prev_frame, float *motion);
+int rt_temporal_accumulate_cpu(const float *color, const float *motion, const rt_temporal_guides *current, const rt_temporal_guides *previous,
+                               const rt_temporal_params *params, uint32_t rows, uint32_t cols, const rt_temporal_pixel *history_in,
+                               rt_temporal_pixel *history_out, float *variance);
+
 /* RGB8 PNG, written to "<path>.tmp" then renamed over path. */
 int rt_write_png(const char *path, const uint8_t *rgb8, uint32_t width, uint32_t height);
 
