@@ -26,6 +26,11 @@
  * The film queries' kernels are rt_film_query.hip; their entry points are rt_api_query.hip's (rt_camera_rays_offset, beside rt_camera_rays) and
  * rt_api_post.hip's (rt_film_offsets / rt_film_splat, beside the accumulator).
  * The kernel units rt_hit_query.hip and rt_scatter_query.hip include this header for the band loop of their launchers.
+ *
+ * No unit includes another unit's source.  What two kernel units share is a header: the render kernels that are instantiated once for
+ * camera frames and once for ray batches are templates in rt_whitted_kernel.h (rt_kernels.hip, rt_kernels_rays.hip), rt_pwf_kernel.h
+ * (rt_pwf.hip, rt_pwf_rays.hip) and rt_dist_kernels.h (rt_distributed.hip, rt_distributed_rays.hip), and the stochastic pass's
+ * generator is rt_rng.h (those two and rt_scatter_query.hip).  Every *.hip of this directory is one object of the Makefile.
  */
 #ifndef RT_API_INTERNAL_H
 #define RT_API_INTERNAL_H

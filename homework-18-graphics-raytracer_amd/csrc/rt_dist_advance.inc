@@ -1,6 +1,6 @@
 /* rt_dist_advance.inc — one step of the scatter chain after its cast (distributed_ray_trace, main.rs:521-614, with
  * get_refract's loop, main.rs:343-405, unrolled into one cast per step).  Textually included in the body of the chain
- * kernel of rt_distributed.hip, which defines the names it uses:
+ * kernel (rt_dist_kernels.h), which defines the names it uses:
  *   in/out  phase, req, h, h_in_dir, h_in_mode, sdir, kind, sp, travel, retry, rng
  *   in      cr (the cast's result), sc, fr, dp, epoch, out_index, n_pixels, n_samples, emit_request(view)
  *   out     casting (another cast is due: phase and req say which), terminal (the sample ends in a get_shade request)

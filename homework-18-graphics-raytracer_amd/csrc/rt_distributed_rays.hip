@@ -8,13 +8,14 @@
  *   rng_import_kernel       the inverse of rng_export_kernel
  *   focus_rays_kernel       Camera::shoot_focus (main.rs:101-127) as a ray source: start_epoch's arithmetic, written out as rt_ray
  *
- * Including rt_distributed.hip compiles everything outside its RT_DIST_RAYS_TU guards once more, into this unit: the generator, the
- * two kernel templates and their helpers.  Release builds have no mutable device globals there (the ziggurat tables are constants).
- * A -DRT_DIAG_PAIR_TIME / -DRT_DIAG_NEED build has rt_cast.h's per-unit counters: this unit gets its own copies and no reader for
- * them (the readers sit inside the guards), so those counts cover camera frames only.
+ * The two kernel templates and their helpers are rt_dist_kernels.h and the generator is rt_rng.h, which this unit includes as
+ * rt_distributed.hip does.  Release builds have no mutable device globals there (the ziggurat tables are constants).  A
+ * -DRT_DIAG_PAIR_TIME / -DRT_DIAG_NEED build has rt_cast.h's per-unit counters: this unit includes the header and gets its own
+ * copies, and no reader for them (the readers are rt_distributed.hip's), so those counts cover camera frames only.
  */
-#define RT_DIST_RAYS_TU
-#include "rt_distributed.hip"
+#include <algorithm>
+
+#include "rt_dist_kernels.h"
 
 namespace rt {
 

@@ -3,13 +3,11 @@
  * rt_kernels.h frame_is_rays), in a translation unit of their own: rt_kernels.hip's code object holds the camera instantiations
  * alone, instruction for instruction as before ray batches existed.
  *
- * Including rt_kernels.hip compiles everything above its RT_KERNELS_RAYS_TU guard once more, into this unit: the kernel template and
- * its helpers.  Release builds have no device globals there.  A -DRT_DIAG_STAGES build has one: rt_cast.h's per-unit
- * g_stage_totals.  This unit gets its own copy, and no reader for it (the readers sit below the guard), so those stage counts
- * cover camera frames only.
+ * The kernel template and its helpers are rt_whitted_kernel.h, which this unit includes as rt_kernels.hip does.  Release builds have
+ * no device globals there.  A -DRT_DIAG_STAGES build has one: rt_cast.h's per-unit g_stage_totals.  This unit includes the header
+ * and gets its own copy, and no reader for it (the readers are rt_kernels.hip's), so those stage counts cover camera frames only.
  */
-#define RT_KERNELS_RAYS_TU
-#include "rt_kernels.hip"
+#include "rt_whitted_kernel.h"
 
 namespace rt {
 

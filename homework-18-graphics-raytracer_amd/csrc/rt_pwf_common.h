@@ -51,7 +51,7 @@ __device__ __forceinline__ void pw_slot_to_pixel(const Frame &fr, uint32_t slot,
  * Positions are reserved with one wave-aggregated atomic on `alloc` (lds_append), the items are written, and then counted
  * into `ready[page]` (pa_publish); consumers claim whole pages of 64 positions in order (pa_claim), full or — once nothing
  * fuller is to be had — SEALED: `alloc` is moved to the page boundary by compare-and-swap so that no reservation can slip
- * in, and the page is taken with the items it has.  All bookkeeping is in LDS; see the header of rt_pwf.hip. */
+ * in, and the page is taken with the items it has.  All bookkeeping is in LDS; see the header of rt_pwf_kernel.h. */
 #define PA_SEALED 0x80000000u
 /* ready[]: one entry per page (its item count, <= 64, and a sealed flag): a word each, or — PACKED — 16 bits each, two to a
  * word.  LDS is what limits the number of resident workgroups, and a frame of several megapixels has thousands of pages

@@ -9,14 +9,14 @@
  *
  * Nothing here is new arithmetic.  The level is rt_dist_advance.inc:70-99 with the same helper calls on the same values (rtdm::powf,
  * rtdm::acosf, the fused rtdm::sincosf, adjust_normal(v, normalize(lobe))), the factor is rt_dist_advance.inc:30-37, and the generator
- * is rt_distributed.hip's (rng_open, next_u32x3, range_f32_of, rng_park) — so that file's exactness argument carries over unchanged.
- * Records are validated as the hit queries validate them (rt_hit_abi.h); a record that is "no hit" never opens its generator.
+ * is the stochastic pass's, rt_rng.h (rng_open, next_u32x3, range_f32_of, rng_park) — so rt_distributed.hip's exactness argument carries
+ * over unchanged.  Records are validated as the hit queries validate them (rt_hit_abi.h); a record that is "no hit" never opens its
+ * generator.
  *
- * Including rt_distributed.hip under RT_DIST_RAYS_TU brings the generator and the (uninstantiated) kernel templates into this unit and
- * none of its kernels, as in rt_distributed_rays.hip: every other code object stays as it was.
+ * Of the stochastic pass this unit includes the generator alone; the materials (material_approx, get_diffuse, adjust_normal) are
+ * rt_shade.h's, which rt_hit_abi.h brings with rt_cast.h.
  */
-#define RT_DIST_RAYS_TU
-#include "rt_distributed.hip"
+#include "rt_rng.h"
 #include "rt_hit_abi.h"
 #include "rt_api_internal.h"
 
