@@ -136,6 +136,33 @@ int HostRoundTrip::finish(unsigned long long *h_count) {
     return RT_OK;
 }
 
+hipError_t DeviceBuffer::reserve(size_t bytes) {
+    if (bytes <= bytes_) return hipSuccess;
+    (void)release();
+    const hipError_t e = kind_ == PINNED_HOST ? hipHostMalloc(&p_, bytes, hipHostMallocDefault) : hipMalloc(&p_, bytes);
+    if (e == hipSuccess) bytes_ = bytes;
+    else { (void)hipGetLastError(); p_ = nullptr; }
+    return e;
+}
+hipError_t DeviceBuffer::release() {
+    const hipError_t e = !p_ ? hipSuccess : kind_ == PINNED_HOST ? hipHostFree(p_) : hipFree(p_);
+    p_ = nullptr;
+    bytes_ = 0;
+    return e;
+}
+
+BfsLists bfs_lists(Workspace &ws, uint32_t waves, bool may_allocate) {
+    const size_t bytes = (size_t)waves * rt::pwf_bfs_scratch_words_per_wave() * sizeof(uint32_t);
+    if (may_allocate) (void)ws.d_bfs.reserve(bytes);
+    BfsLists out = {ws.d_bfs.bytes() >= bytes ? ws.d_bfs.get<uint32_t>() : nullptr, RT_BFS_ITEMS_CAP, RT_BFS_JOBS_CAP};
+    const long long cap = rt::option(rt::OPT_DIAG_BFS_CAP, 0);
+    if (cap > 0) {
+        out.items_cap = (uint32_t)std::min<long long>(cap, RT_BFS_ITEMS_CAP);
+        out.jobs_cap = (uint32_t)std::min<long long>(cap, RT_BFS_JOBS_CAP);
+    }
+    return out;
+}
+
 /* 2 / 3: the per-pixel kernel with scalar / LDS triangle fetches; 18 / 19: the persistent wavefront kernel (with that as its fallback) */
 static bool variant_ok(int v) { return v == 2 || v == 3 || v == 18 || v == 19; }
 static int current_variant() {
@@ -232,7 +259,6 @@ int rt_set_wavefront_budget(unsigned nodes_per_pixel) {
 static std::mutex g_prof_mutex;
 static std::vector<std::pair<hipEvent_t, hipEvent_t>> g_prof_events;
 static size_t g_prof_used = 0;
-
 
 int rt_profile_enable(int on) {
     std::lock_guard<std::mutex> lock(g_prof_mutex);
@@ -406,12 +432,12 @@ int rt_scene_destroy(rt_scene *scene) {
     hipError_t e = hipSuccess;
     for (auto &kv : scene->workspaces) {
         if (kv.second.d_counters) (void)hipFree(kv.second.d_counters);
-        if (kv.second.d_pwf) (void)hipFree(kv.second.d_pwf);
-        if (kv.second.d_bfs) (void)hipFree(kv.second.d_bfs);
-        if (kv.second.d_split) (void)hipFree(kv.second.d_split);
+        (void)kv.second.d_pwf.release();
+        (void)kv.second.d_bfs.release();
+        (void)kv.second.d_split.release();
     }
-    if (scene->upd.d_nodes) (void)hipFree(scene->upd.d_nodes);
-    if (scene->upd.h_stage) (void)hipHostFree(scene->upd.h_stage);
+    (void)scene->upd.d_nodes.release();
+    (void)scene->upd.h_stage.release();
     if (scene->upd.stage_event) (void)hipEventDestroy(scene->upd.stage_event);
     if (scene->d_blob) e = hipFree(scene->d_blob);
     delete scene;
@@ -452,6 +478,89 @@ int make_kernel_frame(const rt_camera *camera, const rt_frame *frame, rt::Kernel
  * 32 bits hold (pw_slot_to_pixel's cols << 3 wraps at 2^29). */
 #define RT_TRACE_BAND_RAYS (1u << 26)
 
+/* What a call on the persistent-wavefront path asks of its workspace, from the frame, the scene and the settings alone (no HIP call,
+ * no lock): the grid and the arenas come from these numbers and from nowhere else, and the allocation is checked against `bytes`. */
+struct PwPlan {
+    uint32_t groups = 0;     /* the grid: one arena per workgroup */
+    uint32_t band_units = 0; /* rows (a camera frame) or rays (a batch) per launch */
+    uint32_t ring_cap = 0, node_cap = 0, tile_reserve = 0;
+    size_t arena_stride = 0, bytes = 0; /* ..., the 512-byte header and the arenas */
+};
+static PwPlan pw_plan(const rt_scene *scene, const rt::KernelFrame &kf, int wf_budget) {
+    const bool rays = rt::frame_is_rays(kf);
+    const uint32_t units = rays ? kf.cols : kf.rows;
+    PwPlan plan;
+    /* The kernel keeps one LDS word per 64 ring slots and per 64 nodes, so an arena holds 64 K ring slots at most.
+     * A tile too large for that at the budget asked for (beyond ~8 Mpixel at 6 nodes per pixel) is rendered as
+     * several bands of rows, one launch each, through the same workspace. */
+    const uint64_t ring_max = 1ull << 16;
+    const uint64_t pixels = (uint64_t)kf.cols * kf.rows;
+    uint64_t groups = (pixels + 63u) / 64u; /* a workgroup fetches one to eight tiles at a time */
+    if (groups > scene->pwf_workgroups) groups = scene->pwf_workgroups;
+    {   /* frames in flight on several streams: each launch takes a part of the device, so that they run side by side */
+        const long long share = rt::option(rt::OPT_WF_SHARE, 1);
+        const uint64_t cap = share > 1 ? ((uint64_t)scene->pwf_workgroups + (uint64_t)share - 1u) / (uint64_t)share : (uint64_t)scene->pwf_workgroups;
+        if (groups > cap) groups = cap;
+    }
+    if (groups < 1) groups = 1;
+    uint64_t max_pixels = (ring_max - 1024u) * groups / (uint64_t)wf_budget;
+    if (rays && max_pixels > RT_TRACE_BAND_RAYS) max_pixels = RT_TRACE_BAND_RAYS;
+    plan.band_units = units;
+    if (pixels > max_pixels) {
+        const uint64_t n_bands = (pixels + max_pixels - 1) / max_pixels;
+        const uint64_t grain = rays ? 64u : 8u; /* whole tiles: 64-ray runs, 8-row tile bands */
+        uint64_t len = (units + n_bands - 1) / n_bands;
+        len = (len + grain - 1u) & ~(grain - 1u);
+        plan.band_units = (uint32_t)(len < units ? len : units);
+    }
+    const uint64_t band_pixels = rays ? (uint64_t)plan.band_units : (uint64_t)kf.cols * plan.band_units;
+    const uint64_t want = (band_pixels * (uint64_t)wf_budget + groups - 1) / groups; /* nodes per arena */
+    /* tiles are handed out dynamically, so a workgroup may end up with several times the average: arenas have a
+     * floor of 8192 ring slots (1.5 MB) however small the frame (budgets below 4 waive it: tests of the fallback) */
+    uint64_t ring = wf_budget >= 4 ? 8192 : 2048;
+    while (ring < want + 1024u && ring < ring_max) ring <<= 1;
+    plan.ring_cap = (uint32_t)ring;
+    /* (the budget sizes the rings; an arena may use all of its ring's worth of nodes: tiles are handed out
+     * dynamically, and a workgroup that met expensive ones needs more than the average) */
+    plan.node_cap = (uint32_t)(ring - 1024u);
+    plan.tile_reserve = 10;
+    plan.arena_stride = (rt::pwf_arena_bytes(plan.node_cap, plan.ring_cap, (uint32_t)(kf.max_depth > 0 ? kf.max_depth : 0)) + 255u) & ~(size_t)255u;
+    plan.groups = (uint32_t)groups;
+    plan.bytes = 512 + (size_t)groups * plan.arena_stride;
+    return plan;
+}
+
+/* Which block of global words the call's launch(es) take and whether they prepare it themselves: the state a workspace carries from
+ * call to call (rt_api_internal.h Workspace), moved on by this call.  Under the scene's ws_mutex, the arenas held. */
+struct PwTurn {
+    uint32_t parity = 0;
+    bool init = true; /* several bands, or a stream that was captured: every launch prepares its own block */
+};
+static PwTurn pw_take_turn(Workspace &ws, const PwPlan &plan, const rt::KernelFrame &kf, bool capturing) {
+    PwTurn turn;
+    if (capturing) ws.pw_always_prepare = true;
+    const uint32_t units = rt::frame_is_rays(kf) ? kf.cols : kf.rows;
+    if (plan.band_units >= units && !ws.pw_always_prepare) { /* one launch: does it find its block zeroed and its frame description in place? */
+        rt::KernelFrame want_frame = kf;
+        want_frame.n_chunks = (kf.cols * kf.rows + 63u) / 64u; /* as launch_pwf fills it in */
+        turn.init = !ws.pw_ready || memcmp(&ws.pw_frame, &want_frame, sizeof want_frame) != 0;
+        turn.parity = ws.pw_parity;
+        ws.pw_parity ^= 1u;
+        ws.pw_frame = want_frame;
+        ws.pw_ready = true;
+    } else ws.pw_ready = false; /* several bands, each with its own frame description */
+    return turn;
+}
+
+/* a stride near the golden section of the tile count scatters consecutive tile fetches over the image */
+static uint32_t golden_tile_stride(uint64_t tiles) {
+    auto gcd = [](uint64_t a, uint64_t b) { while (b) { const uint64_t t = a % b; a = b; b = t; } return a; };
+    uint64_t stride = (uint64_t)((double)tiles * 0.6180339887498949);
+    if (stride < 1) stride = 1;
+    while (gcd(stride, tiles) != 1) stride += 1;
+    return (uint32_t)stride;
+}
+
 /* The Whitted render behind rt_render_whitted and rt_trace_rays: kf is a camera frame (make_kernel_frame) or a ray batch (one row of
  * rays whose first record is d_rays; rt_kernels.h frame_set_rays).  The per-(scene, stream) arenas, the bands, the profiling events
  * and the launches; `who` names the entry point in error messages. */
@@ -482,11 +591,10 @@ static int render_whitted_frame(const rt_scene *scene, const rt::KernelFrame &kf
     /* the persistent-wavefront path packs the ray's face mode and the depth left next to a 21-bit primitive id */
     if ((variant & RT_VARIANT_PWF) && (uint64_t)scene->ks.n_triangles + scene->ks.n_spheres >= (1ull << 21)) variant &= ~RT_VARIANT_PWF;
     if ((variant & RT_VARIANT_PWF) && (scene->ks.n_lights >= (1u << 14) || scene->ks.n_materials >= (1u << 16))) variant &= ~RT_VARIANT_PWF; /* a SHADE item's word: 16 + 14 bits */
-    const int wf_budget = current_wf_budget();
+    const PwPlan plan = (variant & RT_VARIANT_PWF) ? pw_plan(scene, kf, current_wf_budget()) : PwPlan();
     rt::PwParams pw;
     memset(&pw, 0, sizeof pw);
-    uint32_t pw_groups = 0, pw_band_units = 0, pw_parity = 0;
-    bool pw_init = true;
+    PwTurn turn;
     rt::KernelQueues qs;
     memset(&qs, 0, sizeof qs);
     {
@@ -495,107 +603,33 @@ static int render_whitted_frame(const rt_scene *scene, const rt::KernelFrame &kf
         Workspace &ws = mut->workspaces[stream];
         RT_HIP(ensure_counters(ws));
         if (variant & RT_VARIANT_PWF) {
-            /* The kernel keeps one LDS word per 64 ring slots and per 64 nodes, so an arena holds 64 K ring slots at most.
-             * A tile too large for that at the budget asked for (beyond ~8 Mpixel at 6 nodes per pixel) is rendered as
-             * several bands of rows, one launch each, through the same workspace. */
-            const uint64_t ring_max = 1ull << 16;
-            const uint64_t pixels = (uint64_t)kf.cols * kf.rows;
-            uint64_t groups = (pixels + 63u) / 64u; /* a workgroup fetches one to eight tiles at a time */
-            if (groups > scene->pwf_workgroups) groups = scene->pwf_workgroups;
-            {   /* frames in flight on several streams: each launch takes a part of the device, so that they run side by side */
-                const long long share = rt::option(rt::OPT_WF_SHARE, 1);
-                const uint64_t cap = share > 1 ? ((uint64_t)scene->pwf_workgroups + (uint64_t)share - 1u) / (uint64_t)share : (uint64_t)scene->pwf_workgroups;
-                if (groups > cap) groups = cap;
-            }
-            if (groups < 1) groups = 1;
-            uint64_t max_pixels = (ring_max - 1024u) * groups / (uint64_t)wf_budget;
-            if (rays && max_pixels > RT_TRACE_BAND_RAYS) max_pixels = RT_TRACE_BAND_RAYS;
-            pw_band_units = units;
-            if (pixels > max_pixels) {
-                const uint64_t n_bands = (pixels + max_pixels - 1) / max_pixels;
-                const uint64_t grain = rays ? 64u : 8u; /* whole tiles: 64-ray runs, 8-row tile bands */
-                uint64_t len = (units + n_bands - 1) / n_bands;
-                len = (len + grain - 1u) & ~(grain - 1u);
-                pw_band_units = (uint32_t)(len < units ? len : units);
-            }
-            const uint64_t band_pixels = rays ? (uint64_t)pw_band_units : (uint64_t)kf.cols * pw_band_units;
-            const uint64_t want = (band_pixels * (uint64_t)wf_budget + groups - 1) / groups; /* nodes per arena */
-            /* tiles are handed out dynamically, so a workgroup may end up with several times the average: arenas have a
-             * floor of 8192 ring slots (1.5 MB) however small the frame (budgets below 4 waive it: tests of the fallback) */
-            uint64_t ring = wf_budget >= 4 ? 8192 : 2048;
-            while (ring < want + 1024u && ring < ring_max) ring <<= 1;
-            pw.ring_cap = (uint32_t)ring;
-            /* (the budget sizes the rings; an arena may use all of its ring's worth of nodes: tiles are handed out
-             * dynamically, and a workgroup that met expensive ones needs more than the average) */
-            pw.node_cap = (uint32_t)(ring - 1024u);
-            pw.tile_reserve = 10;
-            pw.arena_stride = (rt::pwf_arena_bytes(pw.node_cap, pw.ring_cap, (uint32_t)(kf.max_depth > 0 ? kf.max_depth : 0)) + 255u) & ~(size_t)255u;
-            const size_t need = 512 + (size_t)groups * pw.arena_stride;
-            if (need > ws.pwf_bytes) {
-                if (ws.d_pwf) (void)hipFree(ws.d_pwf);
-                ws.d_pwf = nullptr;
-                ws.pwf_bytes = 0;
-                ws.pw_ready = false;
+            if (plan.bytes > ws.d_pwf.bytes()) {
+                ws.drop_arenas();
                 /* OPT_DIAG_WS_REFUSE: test hook, pretend the allocation fails */
-                if (rt::option(rt::OPT_DIAG_WS_REFUSE, 0) > 0 || hipMalloc(&ws.d_pwf, need) != hipSuccess) {
-                    (void)hipGetLastError();
-                    ws.d_pwf = nullptr;
-                } else {
-                    ws.pwf_bytes = need;
-                }
+                if (rt::option(rt::OPT_DIAG_WS_REFUSE, 0) <= 0) (void)ws.d_pwf.reserve(plan.bytes);
             }
-            /* the grid (groups) and the arenas (groups x arena_stride) come from the same numbers, under the same lock; should they ever
-             * disagree with the allocation the launch must not happen (round 1's memory fault was a kernel writing one page past a workspace) */
-            if (ws.d_pwf != nullptr && 512 + (size_t)groups * pw.arena_stride > ws.pwf_bytes) {
-                (void)hipFree(ws.d_pwf);
-                ws.d_pwf = nullptr;
-                ws.pwf_bytes = 0;
-                ws.pw_ready = false;
+            /* the grid (groups) and the arenas (groups x arena_stride) come from the one plan; should it ever disagree with the
+             * allocation the launch must not happen (round 1's memory fault was a kernel writing one page past a workspace) */
+            if (ws.d_pwf.bytes() != 0 && plan.bytes > ws.d_pwf.bytes()) ws.drop_arenas();
+            if (ws.d_pwf.bytes() != 0 && scene->ks.bfs_walk != 0u) { /* the breadth-first walk's item and job lists: per wave of the grid */
+                const BfsLists bl = bfs_lists(ws, plan.groups * 8u, true); /* PA_WAVES = 8 */
+                if (bl.lists == nullptr) ws.drop_arenas(); /* no room: the per-pixel kernel */
+                pw.bfs_scratch = bl.lists;
+                pw.bfs_items_cap = bl.items_cap; pw.bfs_jobs_cap = bl.jobs_cap;
             }
-            if (ws.d_pwf != nullptr && scene->ks.bfs_walk != 0u) { /* the breadth-first walk's item and job lists: per wave of the grid */
-                const size_t words = (size_t)groups * 8u * rt::pwf_bfs_scratch_words_per_wave(); /* PA_WAVES = 8 */
-                if (ws.bfs_words < words) {
-                    if (ws.d_bfs) (void)hipFree(ws.d_bfs);
-                    ws.d_bfs = nullptr;
-                    ws.bfs_words = 0;
-                    if (hipMalloc(reinterpret_cast<void **>(&ws.d_bfs), words * sizeof(uint32_t)) != hipSuccess) { (void)hipGetLastError(); ws.d_bfs = nullptr; }
-                    else ws.bfs_words = words;
-                }
-                if (ws.d_bfs == nullptr) { (void)hipFree(ws.d_pwf); ws.d_pwf = nullptr; ws.pwf_bytes = 0; ws.pw_ready = false; } /* no room: the per-pixel kernel */
-                pw.bfs_scratch = ws.d_bfs;
-                pw.bfs_items_cap = RT_BFS_ITEMS_CAP;
-                pw.bfs_jobs_cap = RT_BFS_JOBS_CAP;
-                const long long cap = rt::option(rt::OPT_DIAG_BFS_CAP, 0); /* test hook: shorter lists (the memory is the same) */
-                if (cap > 0) {
-                    pw.bfs_items_cap = (uint32_t)std::min<long long>(cap, RT_BFS_ITEMS_CAP);
-                    pw.bfs_jobs_cap = (uint32_t)std::min<long long>(cap, RT_BFS_JOBS_CAP);
-                }
-            }
-            if (ws.d_pwf == nullptr) variant = RT_VARIANT_SGPR | RT_VARIANT_STATIC; /* no room for the arenas: the per-pixel kernel renders the frame */
+            if (ws.d_pwf.bytes() == 0) variant = RT_VARIANT_SGPR | RT_VARIANT_STATIC; /* no room for the arenas: the per-pixel kernel renders the frame */
+            pw.ring_cap = plan.ring_cap;
+            pw.node_cap = plan.node_cap;
+            pw.tile_reserve = plan.tile_reserve;
+            pw.arena_stride = plan.arena_stride;
             pw.tile_order = g_diag_tile_order.load();
             pw.tile_cost = g_diag_tile_cost.load();
             static_assert(PW_G_BLOCK_WORDS * sizeof(uint32_t) == 128, "two blocks of global words and the frame description share the 512-byte header");
             static_assert(sizeof(rt::KernelFrame) <= 128, "the frame description must fit its slot of the workspace header");
-            pw.frame = reinterpret_cast<const rt::KernelFrame *>(static_cast<unsigned char *>(ws.d_pwf) + 256);
-            pw.arena = static_cast<unsigned char *>(ws.d_pwf) + 512;
+            pw.frame = reinterpret_cast<const rt::KernelFrame *>(ws.d_pwf.get<unsigned char>() + 256);
+            pw.arena = ws.d_pwf.get<unsigned char>() + 512;
             pw.ray_count = d_ray_count;
-            pw_groups = (uint32_t)groups;
-            if (ws.d_pwf != nullptr) {
-                if (stream_capturing(stream)) ws.pw_always_prepare = true;
-                if (pw_band_units >= units && !ws.pw_always_prepare) { /* one launch: does it find its block zeroed and its frame description in place? */
-                    rt::KernelFrame want_frame = kf;
-                    want_frame.n_chunks = (kf.cols * kf.rows + 63u) / 64u; /* as launch_pwf fills it in */
-                    pw_init = !ws.pw_ready || memcmp(&ws.pw_frame, &want_frame, sizeof want_frame) != 0;
-                    pw_parity = ws.pw_parity;
-                    ws.pw_parity ^= 1u;
-                    ws.pw_frame = want_frame;
-                    ws.pw_ready = true;
-                } else { /* several bands, each with its own frame description: every launch prepares its own */
-                    pw_init = true;
-                    pw_parity = 0;
-                    ws.pw_ready = false;
-                }
-            }
+            if (ws.d_pwf.bytes() != 0) turn = pw_take_turn(ws, plan, kf, stream_capturing(stream));
         }
 #ifdef RT_DIAG_TIMELINE
         qs.timeline = g_diag_timeline;
@@ -618,23 +652,16 @@ static int render_whitted_frame(const rt_scene *scene, const rt::KernelFrame &kf
     if (variant & RT_VARIANT_PWF) {
         /* a band that does not fit the arenas is rendered by the per-pixel kernel instead (a no-op otherwise) */
         uint32_t *const blocks = reinterpret_cast<uint32_t *>(const_cast<unsigned char *>(pw.arena) - 512);
-        pw.global = blocks + pw_parity * PW_G_BLOCK_WORDS;
-        pw.global_next = blocks + (pw_parity ^ 1u) * PW_G_BLOCK_WORDS;
+        pw.global = blocks + turn.parity * PW_G_BLOCK_WORDS;
+        pw.global_next = blocks + (turn.parity ^ 1u) * PW_G_BLOCK_WORDS;
         qs.run_if = pw.global + PW_G_OVERFLOW;
-        for (uint64_t u0 = 0; e == hipSuccess && u0 < units; u0 += pw_band_units) {
+        for (uint64_t u0 = 0; e == hipSuccess && u0 < units; u0 += plan.band_units) {
             rt::KernelFrame band;
             float *band_rgb;
-            band_of(u0, pw_band_units, &band, &band_rgb);
-            {   /* a stride near the golden section of the tile count scatters consecutive tile fetches over the image */
-                auto gcd = [](uint64_t a, uint64_t b) { while (b) { const uint64_t t = a % b; a = b; b = t; } return a; };
-                const uint64_t tiles = ((uint64_t)band.cols * band.rows + 63u) / 64u;
-                uint64_t stride = (uint64_t)((double)tiles * 0.6180339887498949);
-                if (stride < 1) stride = 1;
-                while (gcd(stride, tiles) != 1) stride += 1;
-                pw.tile_stride = (uint32_t)stride;
-            }
-            const bool first = u0 == 0, last = u0 + pw_band_units >= units;
-            e = rt::launch_pwf(scene->ks, band, band_rgb, pw, pw_groups, stream, pw_init, first, last);
+            band_of(u0, plan.band_units, &band, &band_rgb);
+            pw.tile_stride = golden_tile_stride(((uint64_t)band.cols * band.rows + 63u) / 64u);
+            const bool first = u0 == 0, last = u0 + plan.band_units >= units;
+            e = rt::launch_pwf(scene->ks, band, band_rgb, pw, plan.groups, stream, turn.init, first, last);
             if (e == hipSuccess) {
                 rt::mute_main_kernel_events(true); /* the event pair brackets the persistent kernel(s), not the fallback */
                 e = rt::launch_whitted(scene->ks, band, band_rgb, d_ray_count, qs, stream, (variant & RT_VARIANT_LDS) | RT_VARIANT_STATIC);

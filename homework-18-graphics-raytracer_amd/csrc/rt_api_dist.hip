@@ -67,29 +67,32 @@ int rt_profile_read_distributed(double ms_sum[4], unsigned n_launches[4]) {
 /* ---- distributed pass ------------------------------------------------------- */
 
 struct rt_rng {
-    int device;
-    uint32_t *d_states; /* RT_RNG_DEVICE_WORDS per pixel */
-    uint32_t *d_list;   /* scratch of the look-ahead pass: 1 + pixels words */
-    uint32_t compute_units;
+    int device = -1;
+    DeviceBuffer d_states; /* RT_RNG_DEVICE_WORDS per pixel */
+    DeviceBuffer d_list;   /* scratch of the look-ahead pass: 1 + pixels words */
+    uint32_t compute_units = 256;
     /* The look-ahead for the NEXT batch runs on a stream of its own next to this batch's shade kernel (nothing after
      * the chain kernel touches the records).  ahead = every pixel has its next block, as of the work enqueued so far. */
-    hipStream_t aux;
-    hipEvent_t ev_chain, ev_prepared;
-    bool ahead;
+    hipStream_t aux = nullptr;
+    hipEvent_t ev_chain = nullptr, ev_prepared = nullptr;
+    bool ahead = false;
     /* The shade and unwind kernels of a batch run on a third stream, beside the NEXT batch's chain kernel (two workspaces, used
      * in turn): they fill what its tail leaves idle.  ev_tail[b]: the unwind that read workspace b has finished. */
-    hipStream_t tail;
-    hipEvent_t ev_tail[2];
+    hipStream_t tail = nullptr;
+    hipEvent_t ev_tail[2] = {nullptr, nullptr};
     /* the chain kernel's pixels grouped by what their samples cost (rt_kernels.h DistParams::pixel_order): per pixel its cost in the
      * last batch unwound | two orders, one per workspace of a pipelined call | 512 words of scratch */
-    uint32_t *d_pix;
-    bool order_valid[2];
-    hipStream_t main_stream; /* of the call in progress (for the after-chain hook) */
-    uint32_t *la_states;     /* ... and the records that call (or band of a ray batch) works on */
-    uint32_t la_count;
+    DeviceBuffer d_pix;
+    bool order_valid[2] = {false, false};
+    hipStream_t main_stream = nullptr; /* of the call in progress (for the after-chain hook) */
+    uint32_t *la_states = nullptr;     /* ... and the records that call (or band of a ray batch) works on */
+    uint32_t la_count = 0;
     /* the tile the generators were seeded for (rt_rng_create); seeded ones (rt_rng_create_seeded) belong to no frame: one row of
      * `cols` records with y_step 0, which no frame has (frame_ok) */
-    uint32_t cols, rows, x0, y0, y_step;
+    uint32_t cols = 0, rows = 0, x0 = 0, y0 = 0, y_step = 0;
+    uint32_t *states() const { return d_states.get<uint32_t>(); }
+    uint32_t *list() const { return d_list.get<uint32_t>(); }
+    uint32_t *pix() const { return d_pix.get<uint32_t>(); }
 };
 
 static size_t rng_count(const rt_rng *r) { return (size_t)r->cols * r->rows; }
@@ -98,20 +101,6 @@ static rt_rng *rng_new(uint32_t cols, uint32_t rows, uint32_t x0, uint32_t y0, u
     rt_rng *r = new (std::nothrow) rt_rng();
     if (!r) return nullptr;
     r->cols = cols; r->rows = rows; r->x0 = x0; r->y0 = y0; r->y_step = y_step;
-    r->device = -1;
-    r->d_states = nullptr;
-    r->d_list = nullptr;
-    r->compute_units = 256;
-    r->aux = nullptr;
-    r->ev_chain = r->ev_prepared = nullptr;
-    r->tail = nullptr;
-    r->ev_tail[0] = r->ev_tail[1] = nullptr;
-    r->d_pix = nullptr;
-    r->order_valid[0] = r->order_valid[1] = false;
-    r->ahead = false;
-    r->main_stream = nullptr;
-    r->la_states = nullptr;
-    r->la_count = 0;
     return r;
 }
 
@@ -124,10 +113,10 @@ static hipError_t rng_device_init(rt_rng *r) {
         int cus = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, r->device) == hipSuccess && cus > 0) r->compute_units = (uint32_t)cus;
     }
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&r->d_states), bytes);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&r->d_list), (n + 1u) * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&r->d_pix), (n * 3u + 512u) * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMemset(r->d_pix, 0, (n * 3u + 512u) * sizeof(uint32_t));
+    if (e == hipSuccess) e = r->d_states.reserve(bytes);
+    if (e == hipSuccess) e = r->d_list.reserve((n + 1u) * sizeof(uint32_t));
+    if (e == hipSuccess) e = r->d_pix.reserve((n * 3u + 512u) * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemset(r->pix(), 0, r->d_pix.bytes());
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&r->aux, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&r->ev_chain, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&r->ev_prepared, hipEventDisableTiming);
@@ -137,16 +126,18 @@ static hipError_t rng_device_init(rt_rng *r) {
     return e;
 }
 
-static void rng_free(rt_rng *r) {
-    if (r->d_states) (void)hipFree(r->d_states);
-    if (r->d_list) (void)hipFree(r->d_list);
-    if (r->d_pix) (void)hipFree(r->d_pix);
+/* everything rng_device_init made (or as much of it as there is) and the object; the status of freeing the records */
+static hipError_t rng_free(rt_rng *r) {
+    const hipError_t e = r->d_states.release();
+    (void)r->d_list.release();
+    (void)r->d_pix.release();
     if (r->ev_chain) (void)hipEventDestroy(r->ev_chain);
     if (r->ev_prepared) (void)hipEventDestroy(r->ev_prepared);
     if (r->aux) (void)hipStreamDestroy(r->aux);
     for (int b = 0; b < 2; ++b) if (r->ev_tail[b]) (void)hipEventDestroy(r->ev_tail[b]);
     if (r->tail) (void)hipStreamDestroy(r->tail);
     delete r;
+    return e;
 }
 
 int rt_rng_state_words(void) { return (int)RT_RNG_STATE_WORDS; }
@@ -163,11 +154,11 @@ int rt_rng_create(const rt_frame *frame, rt_rng **out_rng) {
         rt::KernelFrame kf;
         memset(&kf, 0, sizeof kf);
         kf.cols = r->cols; kf.rows = r->rows; kf.x0 = r->x0; kf.y0 = r->y0; kf.y_step = r->y_step;
-        e = rt::launch_rng_seed(r->d_states, kf, nullptr);
+        e = rt::launch_rng_seed(r->states(), kf, nullptr);
     }
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) {
-        rng_free(r);
+        (void)rng_free(r);
         return fail_hip("rt_rng_create", e);
     }
     *out_rng = r;
@@ -191,11 +182,11 @@ int rt_rng_create_seeded(const uint64_t *h_seeds, size_t n, rt_rng **out_rng) {
     hipError_t e = rng_device_init(r);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_seeds), n * sizeof(uint64_t));
     if (e == hipSuccess) e = hipMemcpy(d_seeds, h_seeds, n * sizeof(uint64_t), hipMemcpyHostToDevice); /* the one upload */
-    if (e == hipSuccess) e = rt::launch_rng_seed_from(r->d_states, d_seeds, (uint32_t)n, nullptr);
+    if (e == hipSuccess) e = rt::launch_rng_seed_from(r->states(), d_seeds, (uint32_t)n, nullptr);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (d_seeds) (void)hipFree(d_seeds);
     if (e != hipSuccess) {
-        rng_free(r);
+        (void)rng_free(r);
         return fail_hip("rt_rng_create_seeded", e);
     }
     *out_rng = r;
@@ -206,15 +197,7 @@ int rt_rng_destroy(rt_rng *rng) {
     if (!rng) return RT_OK;
     if (rng->aux) (void)hipStreamSynchronize(rng->aux); /* a look-ahead pass may still be writing the records */
     if (rng->tail) (void)hipStreamSynchronize(rng->tail);
-    hipError_t e = rng->d_states ? hipFree(rng->d_states) : hipSuccess;
-    if (rng->d_list) (void)hipFree(rng->d_list);
-    if (rng->d_pix) (void)hipFree(rng->d_pix);
-    if (rng->ev_chain) (void)hipEventDestroy(rng->ev_chain);
-    if (rng->ev_prepared) (void)hipEventDestroy(rng->ev_prepared);
-    if (rng->aux) (void)hipStreamDestroy(rng->aux);
-    for (int b = 0; b < 2; ++b) if (rng->ev_tail[b]) (void)hipEventDestroy(rng->ev_tail[b]);
-    if (rng->tail) (void)hipStreamDestroy(rng->tail);
-    delete rng;
+    const hipError_t e = rng_free(rng);
     if (e != hipSuccess) return fail_hip("rt_rng_destroy: hipFree", e);
     return RT_OK;
 }
@@ -228,7 +211,7 @@ int rt_rng_download(const rt_rng *rng, uint32_t *h_states) {
     RT_HIP(hipDeviceSynchronize());
     uint32_t *d_tmp = nullptr;
     RT_HIP(hipMalloc(reinterpret_cast<void **>(&d_tmp), bytes));
-    hipError_t e = rt::launch_rng_export(rng->d_states, rng->cols * rng->rows, d_tmp, nullptr);
+    hipError_t e = rt::launch_rng_export(rng->states(), rng->cols * rng->rows, d_tmp, nullptr);
     if (e == hipSuccess) e = hipMemcpy(h_states, d_tmp, bytes, hipMemcpyDeviceToHost);
     (void)hipFree(d_tmp);
     if (e != hipSuccess) return fail_hip("rt_rng_download", e);
@@ -243,7 +226,7 @@ int rt_rng_upload(rt_rng *rng, const uint32_t *h_states) {
     uint32_t *d_tmp = nullptr;
     RT_HIP(hipMalloc(reinterpret_cast<void **>(&d_tmp), bytes));
     hipError_t e = hipMemcpy(d_tmp, h_states, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = rt::launch_rng_import(rng->d_states, (uint32_t)rng_count(rng), d_tmp, nullptr);
+    if (e == hipSuccess) e = rt::launch_rng_import(rng->states(), (uint32_t)rng_count(rng), d_tmp, nullptr);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     (void)hipFree(d_tmp);
     if (e != hipSuccess) return fail_hip("rt_rng_upload", e);
@@ -262,7 +245,7 @@ static hipError_t lookahead_after_chain(void *ctx) {
     hipEvent_t pe[2];
     const bool prof = dist_profile_pairs(DK_PREPARE, 1, pe);
     if (e == hipSuccess && prof) e = hipEventRecord(pe[0], rng->aux);
-    if (e == hipSuccess) e = rt::launch_rng_prepare(rng->la_states, rng->la_count, rng->d_list, rng->compute_units, rng->aux);
+    if (e == hipSuccess) e = rt::launch_rng_prepare(rng->la_states, rng->la_count, rng->list(), rng->compute_units, rng->aux);
     if (e == hipSuccess && prof) e = hipEventRecord(pe[1], rng->aux);
     if (e == hipSuccess) e = hipEventRecord(rng->ev_prepared, rng->aux);
     if (e == hipSuccess) rng->ahead = true;
@@ -274,22 +257,218 @@ static hipError_t lookahead_after_chain(void *ctx) {
 size_t rng_generator_count(const rt_rng *rng) { return rng_count(rng); }
 
 hipError_t rng_begin_draws(rt_rng *rng, bool prepare, hipStream_t stream, uint32_t **d_states) {
-    *d_states = rng->d_states;
+    *d_states = rng->states();
     hipError_t e = hipSuccess;
     if (prepare && !rng->ahead && rng_count(rng) != 0)
-        e = rt::launch_rng_prepare(rng->d_states, (uint32_t)rng_count(rng), rng->d_list, rng->compute_units, stream);
+        e = rt::launch_rng_prepare(rng->states(), (uint32_t)rng_count(rng), rng->list(), rng->compute_units, stream);
     rng->ahead = false; /* a generator may move on to its prepared block */
     return e;
+}
+
+/* One call of the pass (or one band of a ray batch) as its two organisations see it: what the caller passed and the switches
+ * (rt_kernels.h RT_OPTIONS; rt_set_option or, once per process, the environment). */
+struct DistCall {
+    const rt_scene *scene;
+    const rt::KernelFrame &kf;
+    rt_rng *rng;
+    hipStream_t stream;
+    const char *who;
+    size_t n_pixels;
+    uint32_t n_epochs, dist_waves; /* ..., the persistent grid */
+    bool lookahead;  /* RT_AMD_RNG_LOOKAHEAD=0 leaves every IsaacCore::generate to the render kernels */
+    /* ... and those of the split pass.  pipeline: two workspaces, used in turn, when the call has more than one batch: batch k's shade and
+     * unwind kernels then run on a stream of their own beside batch k+1's chain kernel (A/B: RT_AMD_DIST_PIPELINE=0: one workspace,
+     * everything in line).  by_cost: the chain kernel's pixels grouped by cost when a lane gets two of them at most (rt_kernels.h
+     * DistParams::pixel_order); A/B: RT_AMD_DIST_BY_COST=0 never, =1 always.  prep_first = 0: shade kernel and look-ahead start together.
+     * cap: RT_AMD_DIST_WS_MB, default 32 GiB for the two workspaces of a call of several batches. */
+    bool pipeline, by_cost, prep_first;
+    size_t cap;
+};
+
+/* The four arrays of one split workspace, [slot][sample of a batch]; set(epochs) places them and returns the bytes of ONE workspace */
+struct SplitLayout {
+    size_t n_pixels;
+    uint32_t slots;
+    size_t o_hdr = 0, o_req = 0, o_shade = 0, o_frame = 0;
+    size_t set(uint32_t epochs) {
+        auto carve = [](size_t &off, size_t bytes) { const size_t at = off; off = (off + bytes + 255u) & ~(size_t)255u; return at; };
+        const size_t n_samples = n_pixels * epochs;
+        size_t off = 0;
+        o_hdr = carve(off, n_samples * sizeof(uint32_t));
+        o_req = carve(off, n_samples * slots * 4u * sizeof(uint4));
+        o_shade = carve(off, n_samples * slots * sizeof(float4));
+        o_frame = carve(off, n_samples * (slots - 1u) * sizeof(float4));
+        return off;
+    }
+};
+
+/* How many epochs make a batch and how many workspaces the call uses, settled against what `buf` holds or can be made to hold: as
+ * many epochs as fit the cap (one at least) and never more than 16 — a visit of a pixel should not need more random words than the
+ * block in use plus the one prepared ahead.  batch == 0: no room for one epoch (buf holds nothing). */
+static int split_negotiate(DeviceBuffer &buf, hipStream_t stream, size_t cap, size_t per_epoch, uint32_t n_epochs, bool pipeline, SplitLayout &lay,
+                           uint32_t &batch, uint32_t &n_buf) {
+    batch = (uint32_t)std::min<size_t>(std::min<size_t>(n_epochs, 16), std::max<size_t>(1, cap / per_epoch));
+    if (pipeline && batch < n_epochs) /* more than one batch: each workspace gets half the cap */
+        batch = (uint32_t)std::min<size_t>(batch, std::max<size_t>(1, cap / 2u / per_epoch));
+    if (batch < n_epochs) batch = (n_epochs + (n_epochs + batch - 1u) / batch - 1u) / ((n_epochs + batch - 1u) / batch); /* as many batches, of equal size */
+    n_buf = pipeline && batch < n_epochs ? 2u : 1u;
+    size_t need = lay.set(batch) * n_buf;
+    if (buf.bytes() != 0 && buf.bytes() < need) {
+        /* A workspace that holds at least half the batch wanted is used as it is: giving back and obtaining
+         * gigabytes costs far more than the shorter batches do (measured: 0.65 s to replace a 14 GB workspace
+         * by a 16 GB one, against 0.15 s for the 64 epochs the call was made for; profiles/README.md) */
+        uint32_t fit = batch;
+        while (fit > 1u && lay.set(fit) * n_buf > buf.bytes()) fit -= 1u;
+        if (lay.set(fit) * n_buf <= buf.bytes() && fit * 2u >= batch) batch = fit;
+        need = lay.set(batch) * n_buf;
+    }
+    if (buf.bytes() < need) {
+        if (buf.bytes() != 0) {
+            RT_HIP(hipStreamSynchronize(stream));
+            const hipError_t e = buf.release();
+            if (e != hipSuccess) return fail_hip("hipFree(ws.d_split)", e);
+        }
+        /* no room for the batch the cap allows: halve it; no room for one epoch: the one-kernel organisation */
+        int refuse = (int)rt::option(rt::OPT_DIAG_WS_REFUSE, 0); /* test hook: pretend the first n allocations fail (tests/test_gpu_distributed_parity.py) */
+        while (refuse-- > 0 || buf.reserve(need) != hipSuccess) {
+            if (batch == 1u && n_buf == 1u) { batch = 0u; break; }
+            if (batch == 1u) n_buf = 1u;
+            else batch = (batch + 1u) / 2u;
+            need = lay.set(batch) * n_buf;
+        }
+    }
+    return RT_OK;
+}
+
+/* The split pass: chain / shade / unwind kernels over batches of epochs (rt_distributed.hip "the split pass"), the two workspaces in
+ * turn, the look-ahead on the aux stream, the profiling events.  *no_room: nothing was launched, the one-kernel pass renders the call. */
+static int dist_split_pass(const DistCall &c, rt::DistParams dp, bool *no_room) {
+    rt_rng *const rng = c.rng;
+    hipStream_t stream = c.stream;
+    const size_t n_pixels = c.n_pixels;
+    const uint32_t n_epochs = c.n_epochs;
+    SplitLayout lay = {n_pixels, (uint32_t)(c.kf.max_depth > 0 ? c.kf.max_depth : 0) + 1u};
+    const size_t per_epoch = rt::distributed_split_bytes_per_sample(c.kf.max_depth) * n_pixels + 4096;
+    uint32_t batch = 0, n_buf = 0;
+    char *base = nullptr;
+    {
+        rt_scene *mut = const_cast<rt_scene *>(c.scene);
+        std::lock_guard<std::mutex> lock(mut->ws_mutex);
+        Workspace &ws = mut->workspaces[stream];
+        RT_HIP(ensure_counters(ws));
+        const int rc = split_negotiate(ws.d_split, stream, c.cap, per_epoch, n_epochs, c.pipeline, lay, batch, n_buf);
+        if (rc != RT_OK) return rc;
+        dp.work_queue = ws.d_counters;
+        base = ws.d_split.get<char>();
+    }
+    *no_room = batch == 0u;
+    if (*no_room) return RT_OK;
+    const size_t buf_stride = lay.set(batch); /* places the arrays for the batch size settled on */
+    if (batch >= n_epochs) n_buf = 1u;
+    dp.sp_slots = lay.slots;
+    uint32_t k = 0;
+    bool tail_used[2] = {false, false};
+    hipError_t e = hipSuccess;
+    for (uint32_t e0 = 0; e0 < n_epochs && e == hipSuccess; e0 += batch, ++k) {
+        /* the layout is [slot][sample of THIS batch]: a short last batch just uses a prefix of every array */
+        const uint32_t b = n_buf == 2u ? (k & 1u) : 0u;
+        char *const ws_base = base + (size_t)b * buf_stride;
+        dp.sp_hdr = reinterpret_cast<uint32_t *>(ws_base + lay.o_hdr);
+        dp.sp_req = reinterpret_cast<uint4 *>(ws_base + lay.o_req);
+        dp.sp_shade = reinterpret_cast<float4 *>(ws_base + lay.o_shade);
+        dp.sp_frame = reinterpret_cast<float4 *>(ws_base + lay.o_frame);
+        dp.epoch0 = e0;
+        dp.n_epochs = std::min(batch, n_epochs - e0);
+        e = hipMemsetAsync(dp.work_queue, 0, sizeof(uint32_t), stream);
+        if (e == hipSuccess && tail_used[b]) e = hipStreamWaitEvent(stream, rng->ev_tail[b], 0); /* the unwind two batches ago has read this workspace */
+        hipEvent_t pe[8]; /* profiling: prepare | chain | shade, unwind */
+        if (e == hipSuccess && c.lookahead && !rng->ahead) {
+            const bool prof = dist_profile_pairs(DK_PREPARE, 1, pe);
+            if (prof) e = hipEventRecord(pe[0], stream);
+            if (e == hipSuccess) e = rt::launch_rng_prepare(dp.rng_states, (uint32_t)n_pixels, rng->list(), rng->compute_units, stream);
+            if (e == hipSuccess && prof) e = hipEventRecord(pe[1], stream);
+        }
+        rng->ahead = false; /* the chain kernel uses blocks up */
+        const bool prof_chain = dist_profile_pairs(DK_CHAIN, 1, pe + 2);
+        const bool prof_tail = dist_profile_pairs(DK_SHADE, 2, pe + 4);
+        const hipEvent_t *const tail_ev = prof_tail ? pe + 4 : nullptr;
+        rng->main_stream = stream;
+        /* the pixels in the order of what they cost in the batch that used this workspace last (two batches ago in a pipelined
+         * call, the last one else): rt_kernels.h DistParams::pixel_order */
+        uint32_t *const pix_cost = rng->pix(), *const pix_order = rng->pix() + (size_t)(1u + b) * n_pixels, *const pix_scratch = rng->pix() + 3u * n_pixels; /* (by_cost: the whole rng, so n_pixels is its count) */
+        dp.pixel_cost = c.by_cost ? pix_cost : nullptr;
+        dp.pixel_order = c.by_cost && rng->order_valid[b] ? pix_order : nullptr;
+        if (e == hipSuccess && prof_chain) e = hipEventRecord(pe[2], stream);
+        if (e == hipSuccess) e = rt::launch_dist_chain(c.scene->ks, c.kf, dp, c.dist_waves, stream);
+        if (e == hipSuccess && prof_chain) e = hipEventRecord(pe[3], stream);
+        /* from here on this batch does not touch the RNG records: the look-ahead for the next one, on its own stream */
+        if (e == hipSuccess && c.lookahead) e = lookahead_after_chain(rng);
+        if (n_buf == 2u) {
+            if (e == hipSuccess) e = hipEventRecord(rng->ev_tail[b], stream); /* first: the chain kernel has written workspace b ... */
+            if (e == hipSuccess) e = hipStreamWaitEvent(rng->tail, rng->ev_tail[b], 0);
+            /* the next chain kernel waits for the look-ahead, and the look-ahead's workgroups need 64 KB of LDS each: the shade
+             * kernel starts after it instead of taking that LDS first (between two chain kernels of a 1/8 share of the 1080p
+             * frame 1.1 -> 0.3 ms: 0.38 -> 0.365 ms per epoch, a 1/4 share 0.553 -> 0.517, the whole frame 1.685 -> 1.669) */
+            if (e == hipSuccess && c.prep_first && rng->ahead) e = hipStreamWaitEvent(rng->tail, rng->ev_prepared, 0);
+            if (e == hipSuccess) e = rt::launch_dist_shade_unwind(c.scene->ks, c.kf, dp, rng->tail, tail_ev);
+            if (e == hipSuccess && c.by_cost) {
+                e = rt::launch_dist_pixel_order(pix_cost, pix_order, (uint32_t)n_pixels, pix_scratch, rng->tail);
+                rng->order_valid[b] = e == hipSuccess;
+            }
+            if (e == hipSuccess) e = hipEventRecord(rng->ev_tail[b], rng->tail); /* ... then: and the unwind has read it */
+            tail_used[b] = e == hipSuccess;
+        } else if (e == hipSuccess) {
+            e = rt::launch_dist_shade_unwind(c.scene->ks, c.kf, dp, stream, tail_ev);
+            if (e == hipSuccess && c.by_cost) {
+                e = rt::launch_dist_pixel_order(pix_cost, pix_order, (uint32_t)n_pixels, pix_scratch, stream);
+                rng->order_valid[b] = e == hipSuccess;
+            }
+        }
+        /* the next chain kernel — of this call or, on whatever stream is ordered after this one, of the next — needs the prepared blocks */
+        if (e == hipSuccess && rng->ahead) e = hipStreamWaitEvent(stream, rng->ev_prepared, 0);
+    }
+    /* everything the call started is behind the caller's stream again */
+    for (uint32_t b = 0; b < 2u; ++b)
+        if (tail_used[b]) { const hipError_t e2 = hipStreamWaitEvent(stream, rng->ev_tail[b], 0); if (e == hipSuccess) e = e2; }
+    return launched(c.who, e);
+}
+
+/* The one-kernel organisation: persistent lanes, the grid's waves take 64-pixel chunks off the stream's chunk counter */
+static int dist_one_kernel_pass(const DistCall &c, rt::DistParams dp) {
+    uint32_t dist_waves = c.dist_waves;
+    dp.n_epochs = c.n_epochs;
+    dp.epoch0 = 0;
+    dp.sp_hdr = nullptr; dp.sp_req = nullptr; dp.sp_shade = nullptr; dp.sp_frame = nullptr; dp.sp_slots = 0;
+    {
+        rt_scene *mut = const_cast<rt_scene *>(c.scene);
+        std::lock_guard<std::mutex> lock(mut->ws_mutex);
+        Workspace &ws = mut->workspaces[c.stream];
+        RT_HIP(ensure_counters(ws));
+        dp.work_queue = ws.d_counters;
+        if (c.scene->ks.bfs_walk != 0u) { /* the breadth-first walk's lists, one set per wave of the grid (shared with the Whitted path of this stream) */
+            const uint32_t waves = rt::dist_bfs_waves(c.rng->compute_units);
+            const BfsLists bl = bfs_lists(ws, waves, true);
+            if (bl.lists != nullptr) { /* (no room: the wave-uniform walk renders the same samples) */
+                dp.bfs_scratch = bl.lists;
+                dp.bfs_items_cap = bl.items_cap; dp.bfs_jobs_cap = bl.jobs_cap;
+                if (dist_waves > waves) dist_waves = waves;
+            }
+        }
+    }
+    hipError_t e = hipMemsetAsync(dp.work_queue, 0, sizeof(uint32_t), c.stream);
+    if (e == hipSuccess && c.lookahead && !c.rng->ahead) e = rt::launch_rng_prepare(dp.rng_states, (uint32_t)c.n_pixels, c.rng->list(), c.rng->compute_units, c.stream);
+    c.rng->ahead = false;
+    if (e == hipSuccess) e = rt::launch_distributed(c.scene->ks, c.kf, dp, dist_waves, c.stream);
+    return launched(c.who, e);
 }
 
 /* The pass behind rt_render_distributed and rt_trace_rays_distributed: kf is a camera frame (make_kernel_frame) or a band of a ray
  * batch (one row of rays, rt_kernels.h frame_set_rays / frame_set_sample_stride); dp comes with what differs between the two — the
  * band's generator records, n_epochs, focus and blur, the outputs — and `first` is the band's first generator within rng (0 for a
- * frame).  Batches of epochs, the two workspaces in turn, the look-ahead on the aux stream, the fall to the one-kernel organisation,
- * the profiling events and every RT_AMD_DIST_* switch; `who` names the entry point in error messages. */
+ * frame).  Every RT_AMD_DIST_* switch is read here; the split pass is tried first and the one-kernel organisation renders what it
+ * has no room for; `who` names the entry point in error messages. */
 static int render_distributed_frame(const rt_scene *scene, const rt::KernelFrame &kf, rt_rng *rng, size_t first, rt::DistParams dp,
                                     hipStream_t stream, const char *who) {
-    const uint32_t n_epochs = dp.n_epochs;
     dp.work_queue = nullptr;
     dp.pixel_order = nullptr;
     dp.pixel_cost = nullptr;
@@ -297,197 +476,27 @@ static int render_distributed_frame(const rt_scene *scene, const rt::KernelFrame
     dp.bfs_scratch = nullptr;
     dp.bfs_items_cap = dp.bfs_jobs_cap = 0u;
     dp.epoch0 = 0u;
-    uint32_t dist_waves = scene->resident_waves;
     int split = g_dist_split.load();
     if (split < 0) split = rt::option(rt::OPT_DIST_SPLIT, RT_DIST_SPLIT_DEFAULT) != 0 ? 1 : 0;
-    if (scene->ks.bfs_walk != 0u) split = 0; /* a scene beyond the caches: the one-kernel organisation has the breadth-first walk (below) */
-    const size_t n_pixels = (size_t)kf.cols * kf.rows;
-    if (n_pixels == 0 || n_epochs == 0) return RT_OK;
-    const bool whole = first == 0 && n_pixels == rng_count(rng); /* not a band of a larger batch: the cost order covers what is launched */
+    if (scene->ks.bfs_walk != 0u) split = 0; /* a scene beyond the caches: the one-kernel organisation has the breadth-first walk */
+    DistCall c = {scene, kf, rng, stream, who, (size_t)kf.cols * kf.rows, dp.n_epochs, scene->resident_waves};
+    if (c.n_pixels == 0 || c.n_epochs == 0) return RT_OK;
+    const bool whole = first == 0 && c.n_pixels == rng_count(rng); /* not a band of a larger batch: the cost order covers what is launched */
     rng->la_states = dp.rng_states;
-    rng->la_count = (uint32_t)n_pixels;
-    /* the switches (rt_kernels.h RT_OPTIONS; rt_set_option or, once per process, the environment) */
-    const bool lookahead = rt::option(rt::OPT_RNG_LOOKAHEAD, 1) != 0; /* 0 leaves every IsaacCore::generate to the render kernels */
-    rt_scene *mut = const_cast<rt_scene *>(scene);
+    rng->la_count = (uint32_t)c.n_pixels;
+    c.lookahead = rt::option(rt::OPT_RNG_LOOKAHEAD, 1) != 0;
     if (split && kf.max_depth <= 254) {
-        /* chain / shade / unwind kernels over batches of epochs (rt_distributed.hip "the split pass"); a batch is as
-         * many epochs as fit the workspace cap (RT_AMD_DIST_WS_MB, default 32 GiB for the two workspaces of a call of several
-         * batches; one epoch at least) and never more than 16 — a visit of a pixel should not need more random words than the block
-         * in use plus the one prepared ahead */
-        const uint32_t slots = (uint32_t)(kf.max_depth > 0 ? kf.max_depth : 0) + 1u;
-        const size_t per_epoch = rt::distributed_split_bytes_per_sample(kf.max_depth) * n_pixels + 4096;
-        /* Two workspaces, used in turn, when the call has more than one batch: batch k's shade and unwind kernels then run on a
-         * stream of their own beside batch k+1's chain kernel (A/B: RT_AMD_DIST_PIPELINE=0: one workspace, everything in line) */
-        const bool pipeline = rt::option(rt::OPT_DIST_PIPELINE, 1) != 0;
-        /* the chain kernel's pixels grouped by cost when a lane gets two of them at most (rt_kernels.h DistParams::pixel_order);
-         * A/B: RT_AMD_DIST_BY_COST=0 never, =1 always */
-        const bool small_share = (n_pixels + 63u) / 64u <= 2u * (size_t)rt::dist_chain_waves(dist_waves);
-        const bool by_cost = whole && rt::option(rt::OPT_DIST_BY_COST, small_share ? 1 : 0) != 0;
+        c.pipeline = rt::option(rt::OPT_DIST_PIPELINE, 1) != 0;
+        const bool small_share = (c.n_pixels + 63u) / 64u <= 2u * (size_t)rt::dist_chain_waves(c.dist_waves);
+        c.by_cost = whole && rt::option(rt::OPT_DIST_BY_COST, small_share ? 1 : 0) != 0;
         dp.own_first_chunk = rt::option(rt::OPT_DIST_OWN_FIRST, small_share ? 1 : 0) != 0 ? 1u : 0u; /* rt_kernels.h */
-        const bool prep_first = rt::option(rt::OPT_DIST_PREP_FIRST, 1) != 0; /* 0: shade kernel and look-ahead start together */
-        const size_t cap = (size_t)std::max<long long>(0, rt::option(rt::OPT_DIST_WS_MB, pipeline ? 32768 : 16384)) << 20;
-        uint32_t batch = (uint32_t)std::min<size_t>(std::min<size_t>(n_epochs, 16), std::max<size_t>(1, cap / per_epoch));
-        if (pipeline && batch < n_epochs) /* more than one batch: each workspace gets half the cap */
-            batch = (uint32_t)std::min<size_t>(batch, std::max<size_t>(1, cap / 2u / per_epoch));
-        if (batch < n_epochs) batch = (n_epochs + (n_epochs + batch - 1u) / batch - 1u) / ((n_epochs + batch - 1u) / batch); /* as many batches, of equal size */
-        uint32_t n_buf = pipeline && batch < n_epochs ? 2u : 1u;
-        size_t o_hdr = 0, o_req = 0, o_shade = 0, o_frame = 0;
-        auto layout = [&](uint32_t epochs) { /* -> bytes of ONE workspace */
-            auto carve = [](size_t &off, size_t bytes) { const size_t at = off; off = (off + bytes + 255u) & ~(size_t)255u; return at; };
-            const size_t n_samples = n_pixels * epochs;
-            size_t off = 0;
-            o_hdr = carve(off, n_samples * sizeof(uint32_t));
-            o_req = carve(off, n_samples * slots * 4u * sizeof(uint4));
-            o_shade = carve(off, n_samples * slots * sizeof(float4));
-            o_frame = carve(off, n_samples * (slots - 1u) * sizeof(float4));
-            return off;
-        };
-        auto total_bytes = [&](uint32_t epochs, uint32_t bufs) { return layout(epochs) * bufs; };
-        char *base = nullptr;
-        size_t buf_stride = 0;
-        {
-            std::lock_guard<std::mutex> lock(mut->ws_mutex);
-            Workspace &ws = mut->workspaces[stream];
-            RT_HIP(ensure_counters(ws));
-            size_t need = total_bytes(batch, n_buf);
-            if (ws.d_split && ws.split_bytes < need) {
-                /* A workspace that holds at least half the batch wanted is used as it is: giving back and obtaining
-                 * gigabytes costs far more than the shorter batches do (measured: 0.65 s to replace a 14 GB workspace
-                 * by a 16 GB one, against 0.15 s for the 64 epochs the call was made for; profiles/README.md) */
-                uint32_t fit = batch;
-                while (fit > 1u && total_bytes(fit, n_buf) > ws.split_bytes) fit -= 1u;
-                if (total_bytes(fit, n_buf) <= ws.split_bytes && fit * 2u >= batch) batch = fit;
-                need = total_bytes(batch, n_buf);
-            }
-            if (ws.split_bytes < need) {
-                if (ws.d_split) {
-                    RT_HIP(hipStreamSynchronize(stream));
-                    RT_HIP(hipFree(ws.d_split));
-                    ws.d_split = nullptr;
-                    ws.split_bytes = 0;
-                }
-                /* no room for the batch the cap allows: halve it; no room for one epoch: the one-kernel organisation */
-                int refuse = (int)rt::option(rt::OPT_DIAG_WS_REFUSE, 0); /* test hook: pretend the first n allocations fail (tests/test_gpu_distributed_parity.py) */
-                while (refuse-- > 0 || hipMalloc(&ws.d_split, need) != hipSuccess) {
-                    (void)hipGetLastError();
-                    ws.d_split = nullptr;
-                    if (batch == 1u && n_buf == 1u) break;
-                    if (batch == 1u) n_buf = 1u;
-                    else batch = (batch + 1u) / 2u;
-                    need = total_bytes(batch, n_buf);
-                }
-                ws.split_bytes = ws.d_split ? need : 0;
-            }
-            dp.work_queue = ws.d_counters;
-            base = static_cast<char *>(ws.d_split);
-            buf_stride = layout(batch); /* sets the offsets for the batch size settled on */
-        }
-        if (base == nullptr) goto one_kernel;
-        if (batch >= n_epochs) n_buf = 1u;
-        dp.sp_slots = slots;
-        uint32_t k = 0;
-        bool tail_used[2] = {false, false};
-        hipError_t e = hipSuccess;
-        for (uint32_t e0 = 0; e0 < n_epochs && e == hipSuccess; e0 += batch, ++k) {
-            /* the layout is [slot][sample of THIS batch]: a short last batch just uses a prefix of every array */
-            const uint32_t b = n_buf == 2u ? (k & 1u) : 0u;
-            char *const ws_base = base + (size_t)b * buf_stride;
-            dp.sp_hdr = reinterpret_cast<uint32_t *>(ws_base + o_hdr);
-            dp.sp_req = reinterpret_cast<uint4 *>(ws_base + o_req);
-            dp.sp_shade = reinterpret_cast<float4 *>(ws_base + o_shade);
-            dp.sp_frame = reinterpret_cast<float4 *>(ws_base + o_frame);
-            dp.epoch0 = e0;
-            dp.n_epochs = std::min(batch, n_epochs - e0);
-            e = hipMemsetAsync(dp.work_queue, 0, sizeof(uint32_t), stream);
-            if (e == hipSuccess && tail_used[b]) e = hipStreamWaitEvent(stream, rng->ev_tail[b], 0); /* the unwind two batches ago has read this workspace */
-            hipEvent_t pe[8]; /* profiling: prepare | chain | shade, unwind */
-            if (e == hipSuccess && lookahead && !rng->ahead) {
-                const bool prof = dist_profile_pairs(DK_PREPARE, 1, pe);
-                if (prof) e = hipEventRecord(pe[0], stream);
-                if (e == hipSuccess) e = rt::launch_rng_prepare(dp.rng_states, (uint32_t)n_pixels, rng->d_list, rng->compute_units, stream);
-                if (e == hipSuccess && prof) e = hipEventRecord(pe[1], stream);
-            }
-            rng->ahead = false; /* the chain kernel uses blocks up */
-            const bool prof_chain = dist_profile_pairs(DK_CHAIN, 1, pe + 2);
-            const bool prof_tail = dist_profile_pairs(DK_SHADE, 2, pe + 4);
-            const hipEvent_t *const tail_ev = prof_tail ? pe + 4 : nullptr;
-            rng->main_stream = stream;
-            /* the pixels in the order of what they cost in the batch that used this workspace last (two batches ago in a pipelined
-             * call, the last one else): rt_kernels.h DistParams::pixel_order */
-            uint32_t *const pix_cost = rng->d_pix, *const pix_order = rng->d_pix + (size_t)(1u + b) * n_pixels, *const pix_scratch = rng->d_pix + 3u * n_pixels; /* (by_cost: the whole rng, so n_pixels is its count) */
-            dp.pixel_cost = by_cost ? pix_cost : nullptr;
-            dp.pixel_order = by_cost && rng->order_valid[b] ? pix_order : nullptr;
-            if (e == hipSuccess && prof_chain) e = hipEventRecord(pe[2], stream);
-            if (e == hipSuccess) e = rt::launch_dist_chain(scene->ks, kf, dp, dist_waves, stream);
-            if (e == hipSuccess && prof_chain) e = hipEventRecord(pe[3], stream);
-            /* from here on this batch does not touch the RNG records: the look-ahead for the next one, on its own stream */
-            if (e == hipSuccess && lookahead) e = lookahead_after_chain(rng);
-            if (n_buf == 2u) {
-                if (e == hipSuccess) e = hipEventRecord(rng->ev_tail[b], stream); /* first: the chain kernel has written workspace b ... */
-                if (e == hipSuccess) e = hipStreamWaitEvent(rng->tail, rng->ev_tail[b], 0);
-                /* the next chain kernel waits for the look-ahead, and the look-ahead's workgroups need 64 KB of LDS each: the shade
-                 * kernel starts after it instead of taking that LDS first (between two chain kernels of a 1/8 share of the 1080p
-                 * frame 1.1 -> 0.3 ms: 0.38 -> 0.365 ms per epoch, a 1/4 share 0.553 -> 0.517, the whole frame 1.685 -> 1.669) */
-                if (e == hipSuccess && prep_first && rng->ahead) e = hipStreamWaitEvent(rng->tail, rng->ev_prepared, 0);
-                if (e == hipSuccess) e = rt::launch_dist_shade_unwind(scene->ks, kf, dp, rng->tail, tail_ev);
-                if (e == hipSuccess && by_cost) {
-                    e = rt::launch_dist_pixel_order(pix_cost, pix_order, (uint32_t)n_pixels, pix_scratch, rng->tail);
-                    rng->order_valid[b] = e == hipSuccess;
-                }
-                if (e == hipSuccess) e = hipEventRecord(rng->ev_tail[b], rng->tail); /* ... then: and the unwind has read it */
-                tail_used[b] = e == hipSuccess;
-            } else if (e == hipSuccess) {
-                e = rt::launch_dist_shade_unwind(scene->ks, kf, dp, stream, tail_ev);
-                if (e == hipSuccess && by_cost) {
-                    e = rt::launch_dist_pixel_order(pix_cost, pix_order, (uint32_t)n_pixels, pix_scratch, stream);
-                    rng->order_valid[b] = e == hipSuccess;
-                }
-            }
-            /* the next chain kernel — of this call or, on whatever stream is ordered after this one, of the next — needs the prepared blocks */
-            if (e == hipSuccess && rng->ahead) e = hipStreamWaitEvent(stream, rng->ev_prepared, 0);
-        }
-        /* everything the call started is behind the caller's stream again */
-        for (uint32_t b = 0; b < 2u; ++b)
-            if (tail_used[b]) { const hipError_t e2 = hipStreamWaitEvent(stream, rng->ev_tail[b], 0); if (e == hipSuccess) e = e2; }
-        return launched(who, e);
+        c.prep_first = rt::option(rt::OPT_DIST_PREP_FIRST, 1) != 0;
+        c.cap = (size_t)std::max<long long>(0, rt::option(rt::OPT_DIST_WS_MB, c.pipeline ? 32768 : 16384)) << 20;
+        bool no_room = false;
+        const int rc = dist_split_pass(c, dp, &no_room);
+        if (rc != RT_OK || !no_room) return rc;
     }
-one_kernel:
-    dp.n_epochs = n_epochs;
-    dp.epoch0 = 0;
-    dp.sp_hdr = nullptr; dp.sp_req = nullptr; dp.sp_shade = nullptr; dp.sp_frame = nullptr; dp.sp_slots = 0;
-    { /* persistent lanes: the grid's waves take 64-pixel chunks off the stream's chunk counter */
-        std::lock_guard<std::mutex> lock(mut->ws_mutex);
-        Workspace &ws = mut->workspaces[stream];
-        RT_HIP(ensure_counters(ws));
-        dp.work_queue = ws.d_counters;
-        if (scene->ks.bfs_walk != 0u) { /* the breadth-first walk's lists, one set per wave of the grid (shared with the Whitted path of this stream) */
-            const uint32_t waves = rt::dist_bfs_waves(rng->compute_units);
-            const size_t words = (size_t)waves * rt::pwf_bfs_scratch_words_per_wave();
-            if (ws.bfs_words < words) {
-                if (ws.d_bfs) (void)hipFree(ws.d_bfs);
-                ws.d_bfs = nullptr;
-                ws.bfs_words = 0;
-                if (hipMalloc(reinterpret_cast<void **>(&ws.d_bfs), words * sizeof(uint32_t)) != hipSuccess) { (void)hipGetLastError(); ws.d_bfs = nullptr; }
-                else ws.bfs_words = words;
-            }
-            if (ws.d_bfs != nullptr) { /* (no room: the wave-uniform walk renders the same samples) */
-                dp.bfs_scratch = ws.d_bfs;
-                dp.bfs_items_cap = RT_BFS_ITEMS_CAP;
-                dp.bfs_jobs_cap = RT_BFS_JOBS_CAP;
-                const long long cap = rt::option(rt::OPT_DIAG_BFS_CAP, 0);
-                if (cap > 0) {
-                    dp.bfs_items_cap = (uint32_t)std::min<long long>(cap, RT_BFS_ITEMS_CAP);
-                    dp.bfs_jobs_cap = (uint32_t)std::min<long long>(cap, RT_BFS_JOBS_CAP);
-                }
-                if (dist_waves > waves) dist_waves = waves;
-            }
-        }
-    }
-    hipError_t e = hipMemsetAsync(dp.work_queue, 0, sizeof(uint32_t), stream);
-    if (e == hipSuccess && lookahead && !rng->ahead) e = rt::launch_rng_prepare(dp.rng_states, (uint32_t)n_pixels, rng->d_list, rng->compute_units, stream);
-    rng->ahead = false;
-    if (e == hipSuccess) e = rt::launch_distributed(scene->ks, kf, dp, dist_waves, stream);
-    return launched(who, e);
+    return dist_one_kernel_pass(c, dp);
 }
 
 /* A ray batch runs in bands of at most this many rays per launch set, whole 64-ray chunks (as RT_TRACE_BAND_RAYS of rt_trace_rays):
@@ -526,7 +535,7 @@ int rt_render_distributed(const rt_scene *scene, const rt_camera *camera, const 
         return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_distributed: the RNG was created for a different tile");
     rt::DistParams dp;
     memset(&dp, 0, sizeof dp);
-    dp.rng_states = rng->d_states;
+    dp.rng_states = rng->states();
     dp.n_epochs = n_epochs;
     dp.focus = focus;
     dp.blur = blur;
@@ -557,7 +566,7 @@ int rt_trace_rays_distributed(const rt_scene *scene, const rt_ray *d_rays, size_
         rt::frame_set_sample_stride(&kf, n);
         rt::DistParams dp;
         memset(&dp, 0, sizeof dp);
-        dp.rng_states = rng->d_states + (size_t)u0 * RT_RNG_DEVICE_WORDS;
+        dp.rng_states = rng->states() + (size_t)u0 * RT_RNG_DEVICE_WORDS;
         dp.n_epochs = n_epochs;
         dp.accum = d_accum ? d_accum + (size_t)u0 * 3u : nullptr;
         dp.samples = d_samples ? d_samples + (size_t)u0 * 3u : nullptr;
@@ -601,7 +610,7 @@ int rt_focus_rays(const rt_camera *camera, const rt_frame *frame, float focus, f
     const bool seeded_same_count = rng->y_step == 0u && (size_t)kf.cols * kf.rows == rng_count(rng);
     if (!same_tile && !seeded_same_count)
         return fail(RT_ERR_INVALID_ARGUMENT, "rt_focus_rays: the RNG was created for a different tile (or, seeded, holds a different number of generators)");
-    const hipError_t e = rt::launch_focus_rays(kf, focus, blur, rng->d_states, d_rays, static_cast<hipStream_t>(hip_stream));
+    const hipError_t e = rt::launch_focus_rays(kf, focus, blur, rng->states(), d_rays, static_cast<hipStream_t>(hip_stream));
     if (e == hipSuccess) rng->ahead = false; /* a generator may have moved on to its prepared block: the next call looks */
     return launched("rt_focus_rays", e);
 }

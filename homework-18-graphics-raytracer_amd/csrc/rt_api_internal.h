@@ -59,13 +59,38 @@
 
 #define RT_API_HIDDEN __attribute__((visibility("hidden")))
 
-/* Per-(scene, stream) scratch.  Launches on one stream are ordered, so they can share it; other streams get
- * their own.  Grow-only; allocated on the first call that needs it (not inside a graph capture). */
+/* A device (or pinned host) allocation and the size it really has: every persistent buffer of the library is one of these.
+ * reserve() grows only: a request beyond what is held frees, then allocates; when that fails the buffer holds nothing, the sticky HIP
+ * error is cleared and the error is returned — what a failure means is each caller's business.  Move-only, and no HIP call in the
+ * destructor (statics outlive the runtime, and a buffer is freed with its own device current): release() is called by whoever owns
+ * the buffer, where the comments below say.  Definitions: rt_api.hip. */
+class RT_API_HIDDEN DeviceBuffer {
+public:
+    enum Kind { DEVICE, PINNED_HOST };
+    explicit DeviceBuffer(Kind kind = DEVICE) : kind_(kind) {}
+    DeviceBuffer(DeviceBuffer &&o) noexcept : p_(o.p_), bytes_(o.bytes_), kind_(o.kind_) { o.p_ = nullptr; o.bytes_ = 0; }
+    DeviceBuffer &operator=(DeviceBuffer &&o) noexcept { std::swap(p_, o.p_); std::swap(bytes_, o.bytes_); std::swap(kind_, o.kind_); return *this; }
+    DeviceBuffer(const DeviceBuffer &) = delete;
+    DeviceBuffer &operator=(const DeviceBuffer &) = delete;
+    hipError_t reserve(size_t bytes);
+    hipError_t release(); /* the status of the free; holds nothing afterwards either way, and may be called again */
+    template <class T> T *get() const { return static_cast<T *>(p_); }
+    size_t bytes() const { return bytes_; }
+
+private:
+    void *p_ = nullptr;
+    size_t bytes_ = 0;
+    Kind kind_;
+};
+
+/* Per-(scene, stream) scratch.  Launches on one stream are ordered, so they can share it; other streams get their own.  Grow-only;
+ * allocated on the first call that needs it.  The scene owns its workspaces: they are made and changed under rt_scene::ws_mutex only,
+ * by rt_render_whitted / rt_trace_rays (arenas, lists), rt_render_distributed / rt_trace_rays_distributed (split, lists, counters) and
+ * rt_cast_rays / rt_cast_rays_indexed (lists), and rt_scene_destroy frees them all. */
 #define RT_WS_COUNTER_BYTES 256u
 struct Workspace {
     uint32_t *d_counters = nullptr; /* RT_WS_COUNTER_BYTES, zeroed once: [0] the stochastic pass's chunk counter */
-    void *d_pwf = nullptr; /* persistent-wavefront path: two blocks of global words, the frame description, one arena per workgroup */
-    size_t pwf_bytes = 0;
+    DeviceBuffer d_pwf; /* persistent-wavefront path: two blocks of global words, the frame description, one arena per workgroup */
     /* Launches on this workspace alternate between the two blocks of global words: a launch's last workgroup zeroes the
      * other block, so the next launch needs no preparation of its own unless its frame description differs from what is in
      * device memory (or nothing has run here yet). */
@@ -74,11 +99,20 @@ struct Workspace {
     bool pw_always_prepare = false; /* a call on this stream was captured into a graph: replays come unannounced, so from then on
                                      * every launch prepares its own block and frame description, as a captured one does */
     rt::KernelFrame pw_frame;
-    uint32_t *d_bfs = nullptr; /* persistent-wavefront path on a scene walked breadth-first: item and job lists per wave (rt_kernels.h PwParams) */
-    size_t bfs_words = 0;
-    void *d_split = nullptr; /* split distributed pass: requests, shades and frames of one batch of epochs */
-    size_t split_bytes = 0;
+    DeviceBuffer d_bfs;   /* a scene walked breadth-first: item and job lists per wave (rt_kernels.h PwParams), through bfs_lists() below */
+    DeviceBuffer d_split; /* split distributed pass: requests, shades and frames of one batch of epochs */
+    void drop_arenas() { (void)d_pwf.release(); pw_ready = false; } /* whatever the blocks held went with them */
 };
+
+/* The breadth-first walk's record lists for a grid of `waves` waves, in the stream's workspace (the Whitted frame, the one-kernel
+ * stochastic pass and the ray queries of one stream share them): grown to that many waves when may_allocate, and `lists` is null when
+ * what is held is too small.  The caps: RT_BFS_ITEMS_CAP / RT_BFS_JOBS_CAP, or what the test hook RT_AMD_DIAG_BFS_CAP shortens them
+ * to (the memory is the same).  Call under the scene's ws_mutex.  Definition: rt_api.hip. */
+struct BfsLists {
+    uint32_t *lists;
+    uint32_t items_cap, jobs_cap;
+};
+RT_API_HIDDEN BfsLists bfs_lists(Workspace &ws, uint32_t waves, bool may_allocate);
 
 inline hipError_t ensure_counters(Workspace &ws) {
     if (ws.d_counters) return hipSuccess;
@@ -96,15 +130,14 @@ struct RefitNode {
     uint32_t bfs_pos; /* ... and in bfs_nodes / bfs_soa (level order) */
 };
 #define RT_REFIT_WAVE_MAX 1024u /* a node of up to this many triangles is refitted by one wave, a larger one by a workgroup */
-struct SceneUpdate {
+struct SceneUpdate { /* the buffers and the event: freed by rt_scene_destroy */
     double extent = 0.0;          /* the scene's box at creation: fixed (KernelScene::filter_origin2 travels by value) */
     std::vector<RefitNode> nodes; /* kept on the host by rt_scene_create, uploaded with the first rt_scene_update_vertices */
     std::mutex mutex;
     bool uploaded = false;
-    RefitNode *d_nodes = nullptr; /* n_small nodes for a wave each, then n_large for a workgroup each */
+    DeviceBuffer d_nodes;         /* RefitNode: n_small nodes for a wave each, then n_large for a workgroup each */
     uint32_t n_small = 0, n_large = 0;
-    void *h_stage = nullptr;      /* pinned: the light and material records of one call on their way to the device */
-    size_t stage_bytes = 0;
+    DeviceBuffer h_stage{DeviceBuffer::PINNED_HOST}; /* the light and material records of one call on their way to the device */
     hipEvent_t stage_event = nullptr; /* recorded after that call's copies */
 };
 

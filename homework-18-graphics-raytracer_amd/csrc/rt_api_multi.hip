@@ -23,19 +23,19 @@ struct rt_multi {
         int device = 0;
         rt_scene *scene = nullptr;
         hipStream_t stream = nullptr;
-        float *d_band = nullptr;
-        size_t band_floats = 0;
+        DeviceBuffer d_band; /* this part's rows, as floats: freed with `device` current */
         unsigned long long *d_count = nullptr;
-        float *h_band = nullptr; /* pinned */
-        size_t h_floats = 0;
+        DeviceBuffer h_band{DeviceBuffer::PINNED_HOST}; /* likewise */
         rt_rng *rng = nullptr; /* stochastic pass: the streams of this part's rows */
         rt_frame rng_frame;
         hipEvent_t done = nullptr;   /* recorded on `stream` after a band is rendered (the device-resident entry points) */
-        float *d_stage = nullptr;    /* on parts[0].device: where a band of another device lands before it is de-interleaved */
-        size_t stage_floats = 0;
+        DeviceBuffer d_stage;        /* on parts[0].device (and freed with it current): where a band of another device lands before it is de-interleaved */
         unsigned long long *d_stage_count = nullptr; /* likewise its cast count */
         hipEvent_t staged = nullptr; /* on parts[0].device, recorded on the CALLER's stream: this part's rows of the image are on their way to it
                                       * (an event is recorded on a stream of its own device only: `done` belongs to `device`, the caller's stream to parts[0].device) */
+        float *band() const { return d_band.get<float>(); }
+        float *host_band() const { return h_band.get<float>(); }
+        float *stage() const { return d_stage.get<float>(); }
     };
     hipEvent_t ready = nullptr; /* recorded on the caller's stream: the parts' streams wait for it before touching the image */
     std::vector<Part> parts;
@@ -58,16 +58,16 @@ int rt_multi_destroy(rt_multi *m) {
         if (p.stream) (void)hipStreamSynchronize(p.stream);
         if (p.rng) (void)rt_rng_destroy(p.rng);
         if (p.scene) (void)rt_scene_destroy(p.scene);
-        if (p.d_band) (void)hipFree(p.d_band);
+        (void)p.d_band.release();
         if (p.d_count) (void)hipFree(p.d_count);
-        if (p.h_band) (void)hipHostFree(p.h_band);
+        (void)p.h_band.release();
         if (p.done) (void)hipEventDestroy(p.done);
         if (p.stream) (void)hipStreamDestroy(p.stream);
     }
     if (!m->parts.empty()) {
         (void)hipSetDevice(m->parts[0].device);
         for (auto &p : m->parts) {
-            if (p.d_stage) (void)hipFree(p.d_stage);
+            (void)p.d_stage.release();
             if (p.d_stage_count) (void)hipFree(p.d_stage_count);
             if (p.staged) (void)hipEventDestroy(p.staged);
         }
@@ -129,29 +129,13 @@ static int multi_prepare(rt_multi *m, const rt_frame *frame, std::vector<rt_fram
         rt_multi::Part &p = m->parts[(size_t)r];
         multi_part_frame(frame, r, n, &(*frames)[(size_t)r]);
         const rt_frame &pf = (*frames)[(size_t)r];
-        const size_t floats = pf.y0 < pf.y1 ? (size_t)rt_frame_pixels(&pf) * 3u : 0u;
+        const size_t bytes = pf.y0 < pf.y1 ? (size_t)rt_frame_pixels(&pf) * 3u * sizeof(float) : 0u;
         hipError_t e = hipSetDevice(p.device);
-        if (e == hipSuccess && floats > p.band_floats) {
-            if (p.d_band) (void)hipFree(p.d_band);
-            p.d_band = nullptr;
-            p.band_floats = 0;
-            e = hipMalloc(reinterpret_cast<void **>(&p.d_band), floats * sizeof(float));
-            if (e == hipSuccess) p.band_floats = floats;
-        }
-        if (e == hipSuccess && host_bands && floats > p.h_floats) {
-            if (p.h_band) (void)hipHostFree(p.h_band);
-            p.h_band = nullptr;
-            p.h_floats = 0;
-            e = hipHostMalloc(reinterpret_cast<void **>(&p.h_band), floats * sizeof(float), hipHostMallocDefault);
-            if (e == hipSuccess) p.h_floats = floats;
-        }
-        if (e == hipSuccess && !host_bands && floats > p.stage_floats && (p.device != m->parts[0].device || rt::option(rt::OPT_MULTI_FORCE_STAGE, 0) != 0)) {
+        if (e == hipSuccess) e = p.d_band.reserve(bytes);
+        if (e == hipSuccess && host_bands) e = p.h_band.reserve(bytes);
+        if (e == hipSuccess && !host_bands && bytes > p.d_stage.bytes() && (p.device != m->parts[0].device || rt::option(rt::OPT_MULTI_FORCE_STAGE, 0) != 0)) {
             e = hipSetDevice(m->parts[0].device);
-            if (e == hipSuccess && p.d_stage) (void)hipFree(p.d_stage);
-            p.d_stage = nullptr;
-            p.stage_floats = 0;
-            if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&p.d_stage), floats * sizeof(float));
-            if (e == hipSuccess) p.stage_floats = floats;
+            if (e == hipSuccess) e = p.d_stage.reserve(bytes);
         }
         if (e != hipSuccess) return fail_hip("rt_multi: band buffers", e);
     }
@@ -165,7 +149,7 @@ static void multi_deinterleave(const rt_multi *m, const rt_frame *frame, float *
     const size_t rows = rt_frame_rows(frame);
     for (size_t k = 0; k < rows; ++k) {
         const rt_multi::Part &p = m->parts[k % n];
-        const float *src = p.h_band + (k / n) * cols * 3u;
+        const float *src = p.h_band.get<float>() + (k / n) * cols * 3u;
         float *dst = h_rgb + k * cols * 3u;
         memcpy(dst, src, cols * 3u * sizeof(float));
     }
@@ -204,9 +188,9 @@ int rt_multi_render_whitted_host(rt_multi *m, const rt_camera *camera, const rt_
         if (e == hipSuccess) e = hipMemsetAsync(p.d_count, 0, sizeof(unsigned long long), p.stream);
         if (e != hipSuccess) { rc = fail_hip("rt_multi_render_whitted_host", e); break; }
         if (!(pf.y0 < pf.y1)) continue; /* more parts than rows */
-        rc = rt_render_whitted(p.scene, camera, &pf, p.d_band, p.d_count, p.stream);
+        rc = rt_render_whitted(p.scene, camera, &pf, p.band(), p.d_count, p.stream);
         if (rc == RT_OK) {
-            e = hipMemcpyAsync(p.h_band, p.d_band, (size_t)rt_frame_pixels(&pf) * 3u * sizeof(float), hipMemcpyDeviceToHost, p.stream);
+            e = hipMemcpyAsync(p.host_band(), p.band(), (size_t)rt_frame_pixels(&pf) * 3u * sizeof(float), hipMemcpyDeviceToHost, p.stream);
             if (e != hipSuccess) rc = fail_hip("rt_multi_render_whitted_host: copy", e);
         }
     }
@@ -246,13 +230,13 @@ int rt_multi_render_distributed_host(rt_multi *m, const rt_camera *camera, const
         if (e != hipSuccess) { rc = fail_hip("rt_multi_render_distributed_host", e); break; }
         if (!(pf.y0 < pf.y1)) continue;
         /* img continues from the caller's sums: this part's rows of it, interleaved -> band */
-        for (size_t k = (size_t)r, b = 0; k < rows; k += (size_t)n, ++b) memcpy(p.h_band + b * cols * 3u, h_accum + k * cols * 3u, cols * 3u * sizeof(float));
+        for (size_t k = (size_t)r, b = 0; k < rows; k += (size_t)n, ++b) memcpy(p.host_band() + b * cols * 3u, h_accum + k * cols * 3u, cols * 3u * sizeof(float));
         const size_t bytes = (size_t)rt_frame_pixels(&pf) * 3u * sizeof(float);
-        e = hipMemcpyAsync(p.d_band, p.h_band, bytes, hipMemcpyHostToDevice, p.stream);
+        e = hipMemcpyAsync(p.band(), p.host_band(), bytes, hipMemcpyHostToDevice, p.stream);
         if (e != hipSuccess) { rc = fail_hip("rt_multi_render_distributed_host: upload", e); break; }
-        rc = rt_render_distributed(p.scene, camera, &pf, focus, blur, p.rng, n_epochs, p.d_band, nullptr, nullptr, p.d_count, p.stream);
+        rc = rt_render_distributed(p.scene, camera, &pf, focus, blur, p.rng, n_epochs, p.band(), nullptr, nullptr, p.d_count, p.stream);
         if (rc == RT_OK) {
-            e = hipMemcpyAsync(p.h_band, p.d_band, bytes, hipMemcpyDeviceToHost, p.stream);
+            e = hipMemcpyAsync(p.host_band(), p.band(), bytes, hipMemcpyDeviceToHost, p.stream);
             if (e != hipSuccess) rc = fail_hip("rt_multi_render_distributed_host: copy", e);
         }
     }
@@ -290,13 +274,13 @@ static int multi_gather_band(rt_multi *m, int r, const rt_frame &pf, const rt_fr
     const size_t row_bytes = cols * 3u * sizeof(float);
     hipError_t e = hipSetDevice(m->parts[0].device);
     if (e == hipSuccess) e = hipStreamWaitEvent(stream, p.done, 0);
-    const float *src = p.d_band;
+    const float *src = p.band();
     const unsigned long long *src_count = p.d_count;
-    if (e == hipSuccess && p.d_stage != nullptr) { /* another device's band (or the test hook): over the link into the staging buffer */
-        e = hipMemcpyPeerAsync(p.d_stage, m->parts[0].device, p.d_band, p.device, band_rows * row_bytes, stream);
-        src = p.d_stage;
+    if (e == hipSuccess && p.stage() != nullptr) { /* another device's band (or the test hook): over the link into the staging buffer */
+        e = hipMemcpyPeerAsync(p.stage(), m->parts[0].device, p.band(), p.device, band_rows * row_bytes, stream);
+        src = p.stage();
     }
-    if (e == hipSuccess && d_ray_count != nullptr && (p.device != m->parts[0].device || p.d_stage != nullptr)) {
+    if (e == hipSuccess && d_ray_count != nullptr && (p.device != m->parts[0].device || p.stage() != nullptr)) {
         e = hipMemcpyPeerAsync(p.d_stage_count, m->parts[0].device, p.d_count, p.device, sizeof(unsigned long long), stream);
         src_count = p.d_stage_count;
     }
@@ -325,7 +309,7 @@ int rt_multi_render_whitted(rt_multi *m, const rt_camera *camera, const rt_frame
         hipError_t e = hipSetDevice(p.device);
         if (e == hipSuccess) e = hipMemsetAsync(p.d_count, 0, sizeof(unsigned long long), p.stream);
         if (e != hipSuccess) { rc = fail_hip("rt_multi_render_whitted", e); break; }
-        if (pf.y0 < pf.y1) rc = rt_render_whitted(p.scene, camera, &pf, p.d_band, p.d_count, p.stream);
+        if (pf.y0 < pf.y1) rc = rt_render_whitted(p.scene, camera, &pf, p.band(), p.d_count, p.stream);
         if (rc == RT_OK && (e = hipEventRecord(p.done, p.stream)) != hipSuccess) rc = fail_hip("rt_multi_render_whitted", e);
     }
     for (int r = 0; r < n && rc == RT_OK; ++r) rc = multi_gather_band(m, r, frames[(size_t)r], frame, d_rgb, d_ray_count, stream);
@@ -358,20 +342,20 @@ int rt_multi_render_distributed(rt_multi *m, const rt_camera *camera, const rt_f
         if (e == hipSuccess) e = hipMemsetAsync(p.d_count, 0, sizeof(unsigned long long), p.stream);
         if (e == hipSuccess) e = hipStreamWaitEvent(p.stream, m->ready, 0);
         if (e == hipSuccess && band_rows != 0u) {
-            if (p.d_stage != nullptr) { /* rows of the image -> staging (on the image's device), then over the link */
+            if (p.stage() != nullptr) { /* rows of the image -> staging (on the image's device), then over the link */
                 e = hipSetDevice(m->parts[0].device);
                 if (e == hipSuccess)
-                    e = hipMemcpy2DAsync(p.d_stage, row_bytes, d_accum + (size_t)r * cols * 3u, (size_t)n * row_bytes, row_bytes, band_rows, hipMemcpyDeviceToDevice, stream);
-                if (e == hipSuccess) e = hipMemcpyPeerAsync(p.d_band, p.device, p.d_stage, m->parts[0].device, band_rows * row_bytes, stream);
+                    e = hipMemcpy2DAsync(p.stage(), row_bytes, d_accum + (size_t)r * cols * 3u, (size_t)n * row_bytes, row_bytes, band_rows, hipMemcpyDeviceToDevice, stream);
+                if (e == hipSuccess) e = hipMemcpyPeerAsync(p.band(), p.device, p.stage(), m->parts[0].device, band_rows * row_bytes, stream);
                 if (e == hipSuccess) e = hipEventRecord(p.staged, stream); /* an event of the caller's stream's device (`done` is p.device's) */
                 if (e == hipSuccess) e = hipSetDevice(p.device);
                 if (e == hipSuccess) e = hipStreamWaitEvent(p.stream, p.staged, 0);
             } else {
-                e = hipMemcpy2DAsync(p.d_band, row_bytes, d_accum + (size_t)r * cols * 3u, (size_t)n * row_bytes, row_bytes, band_rows, hipMemcpyDeviceToDevice, p.stream);
+                e = hipMemcpy2DAsync(p.band(), row_bytes, d_accum + (size_t)r * cols * 3u, (size_t)n * row_bytes, row_bytes, band_rows, hipMemcpyDeviceToDevice, p.stream);
             }
         }
         if (e != hipSuccess) { rc = fail_hip("rt_multi_render_distributed", e); break; }
-        if (band_rows != 0u) rc = rt_render_distributed(p.scene, camera, &pf, focus, blur, p.rng, n_epochs, p.d_band, nullptr, nullptr, p.d_count, p.stream);
+        if (band_rows != 0u) rc = rt_render_distributed(p.scene, camera, &pf, focus, blur, p.rng, n_epochs, p.band(), nullptr, nullptr, p.d_count, p.stream);
         if (rc == RT_OK && (e = hipEventRecord(p.done, p.stream)) != hipSuccess) rc = fail_hip("rt_multi_render_distributed", e);
     }
     for (int r = 0; r < n && rc == RT_OK; ++r) rc = multi_gather_band(m, r, frames[(size_t)r], frame, d_accum, d_ray_count, stream);

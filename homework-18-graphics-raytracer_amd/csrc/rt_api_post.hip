@@ -19,9 +19,8 @@ extern "C" {
 /* ---- post_process / encode on the device ----------------------------------------- */
 
 struct PostWs {
-    uint32_t *d_keys = nullptr;
-    size_t n = 0;
-    uint32_t *d_state = nullptr;
+    DeviceBuffer d_keys;  /* one word per pixel of the largest frame so far */
+    DeviceBuffer d_state; /* 260 words */
 };
 /* keyed by (device, stream): the default stream is nullptr on every device, and a buffer allocated on one device must
  * not serve a launch on another.  Grow-only; rt_post_release() frees the buffers of the current device. */
@@ -36,8 +35,8 @@ int rt_post_release(void) {
     std::lock_guard<std::mutex> lock(g_post_mutex);
     for (auto it = g_post_ws.begin(); it != g_post_ws.end();) {
         if (it->first.first == device) {
-            if (it->second.d_keys) (void)hipFree(it->second.d_keys);
-            if (it->second.d_state) (void)hipFree(it->second.d_state);
+            (void)it->second.d_keys.release();
+            (void)it->second.d_state.release();
             it = g_post_ws.erase(it);
         } else {
             ++it;
@@ -56,16 +55,12 @@ int rt_post_process_device(float *d_rgb, size_t n_pixels, float *d_divisor, void
     {
         std::lock_guard<std::mutex> lock(g_post_mutex);
         PostWs &ws = g_post_ws[std::make_pair(device, stream)];
-        if (!ws.d_state) RT_HIP(hipMalloc(reinterpret_cast<void **>(&ws.d_state), 260 * sizeof(uint32_t)));
-        if (n_pixels > ws.n) {
-            if (ws.d_keys) (void)hipFree(ws.d_keys);
-            ws.d_keys = nullptr;
-            ws.n = 0;
-            RT_HIP(hipMalloc(reinterpret_cast<void **>(&ws.d_keys), n_pixels * sizeof(uint32_t)));
-            ws.n = n_pixels;
-        }
-        keys = ws.d_keys;
-        state = ws.d_state;
+        hipError_t e = ws.d_state.reserve(260 * sizeof(uint32_t));
+        if (e != hipSuccess) return fail_hip("hipMalloc(reinterpret_cast<void **>(&ws.d_state), 260 * sizeof(uint32_t))", e);
+        e = ws.d_keys.reserve(n_pixels * sizeof(uint32_t));
+        if (e != hipSuccess) return fail_hip("hipMalloc(reinterpret_cast<void **>(&ws.d_keys), n_pixels * sizeof(uint32_t))", e);
+        keys = ws.d_keys.get<uint32_t>();
+        state = ws.d_state.get<uint32_t>();
     }
     float row[3];
     rt::luma_row(row);

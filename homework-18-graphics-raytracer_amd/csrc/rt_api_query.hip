@@ -10,40 +10,23 @@
 
 static_assert(sizeof(rt_ray) == 44 && sizeof(rt_hit) == 52, "the ABI records are flat u32 / f32 words");
 
-/* The breadth-first walk's record lists for a cast of n rays (or index entries) on `stream`: per wave of the grid, in the workspace
- * rt_render_whitted keeps them in (sized and grown as there: workgroups x 8 waves x pwf_bfs_scratch_words_per_wave), one workgroup per
- * CU at most.  false: no room for the lists, or a capture before the first call on this stream (allocation cannot be captured). */
-namespace {
-struct BfsLists {
-    uint32_t *lists = nullptr;
-    uint32_t items_cap = RT_BFS_ITEMS_CAP, jobs_cap = RT_BFS_JOBS_CAP, groups = 0;
-};
-} /* namespace */
-static bool bfs_lists(const rt_scene *scene, hipStream_t stream, uint32_t n, BfsLists *out) {
+/* The breadth-first walk's record lists for a cast of n rays (or index entries) on `stream` (rt_api_internal.h bfs_lists), for *groups
+ * workgroups: one per CU at most.  lists == nullptr: no room for them, or a capture before the first call on this stream
+ * (allocation cannot be captured). */
+static BfsLists query_bfs_lists(const rt_scene *scene, hipStream_t stream, uint32_t n, uint32_t *groups_out) {
     const uint64_t cus = scene->resident_waves / (4u * (uint32_t)RT_MIN_WAVES);
     uint64_t groups = ((uint64_t)n + 64u * RT_QUERY_BFS_WAVES - 1u) / (64u * RT_QUERY_BFS_WAVES);
     if (groups > cus) groups = cus;
     if (groups < 1) groups = 1;
     static_assert(RT_QUERY_BFS_WAVES == 8u, "the lists are sized per wave of an 8-wave workgroup, as rt_render_whitted sizes them");
-    const size_t words = (size_t)groups * RT_QUERY_BFS_WAVES * rt::pwf_bfs_scratch_words_per_wave();
-    out->groups = (uint32_t)groups;
+    const uint32_t waves = (uint32_t)groups * RT_QUERY_BFS_WAVES;
+    *groups_out = (uint32_t)groups;
     rt_scene *mut = const_cast<rt_scene *>(scene); /* workspaces are the only mutable part of a scene */
     std::lock_guard<std::mutex> lock(mut->ws_mutex);
     Workspace &ws = mut->workspaces[stream];
-    if (ws.bfs_words < words && !stream_capturing(stream)) { /* allocation cannot be captured */
-        if (ws.d_bfs) (void)hipFree(ws.d_bfs);
-        ws.d_bfs = nullptr;
-        ws.bfs_words = 0;
-        if (hipMalloc(reinterpret_cast<void **>(&ws.d_bfs), words * sizeof(uint32_t)) != hipSuccess) { (void)hipGetLastError(); ws.d_bfs = nullptr; }
-        else ws.bfs_words = words;
-    }
-    if (ws.d_bfs != nullptr && ws.bfs_words >= words) out->lists = ws.d_bfs;
-    const long long cap = rt::option(rt::OPT_DIAG_BFS_CAP, 0); /* test hook: shorter lists (the memory is the same) */
-    if (cap > 0) {
-        out->items_cap = (uint32_t)std::min<long long>(cap, RT_BFS_ITEMS_CAP);
-        out->jobs_cap = (uint32_t)std::min<long long>(cap, RT_BFS_JOBS_CAP);
-    }
-    return out->lists != nullptr;
+    BfsLists bl = bfs_lists(ws, waves, false);
+    if (bl.lists == nullptr && !stream_capturing(stream)) bl = bfs_lists(ws, waves, true); /* what is held is too small */
+    return bl;
 }
 
 static const CountLimit CAST_RAYS_LIMIT = {32u, "rays", "cast them in several calls"};
@@ -58,9 +41,10 @@ int rt_cast_rays(const rt_scene *scene, const rt_ray *d_rays, size_t n_rays, rt_
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     const bool wave_uniform = rt::option(rt::OPT_QUERY_WAVE_UNIFORM, 0) == 1;
     if (scene->ks.bfs_walk != 0u && !wave_uniform) {
-        BfsLists bl;
-        if (bfs_lists(scene, stream, n, &bl))
-            return launched("rt_cast_rays", rt::launch_cast_rays_bfs(scene->ks, d_rays, d_hits, n, bl.lists, bl.items_cap, bl.jobs_cap, bl.groups, stream));
+        uint32_t groups;
+        const BfsLists bl = query_bfs_lists(scene, stream, n, &groups);
+        if (bl.lists != nullptr)
+            return launched("rt_cast_rays", rt::launch_cast_rays_bfs(scene->ks, d_rays, d_hits, n, bl.lists, bl.items_cap, bl.jobs_cap, groups, stream));
         /* no room for the lists (or a capture before the first call on this stream): the pair-wise kernel, exact as well */
     }
     return launched("rt_cast_rays", rt::launch_cast_rays(scene->ks, d_rays, d_hits, n, wave_uniform, stream));
@@ -277,13 +261,13 @@ int rt_scatter_factors_host(const rt_scene *scene, const rt_hit *h_hits, const r
 
 /* rt_select_records' block totals: RT_SELECT_MAX_GROUPS words per (device, stream), as rt_post_process_device keeps its scratch */
 static std::mutex g_select_mutex;
-static std::map<std::pair<int, hipStream_t>, uint32_t *> g_select_totals;
+static std::map<std::pair<int, hipStream_t>, DeviceBuffer> g_select_totals;
 
 void select_release(int device) {
     std::lock_guard<std::mutex> lock(g_select_mutex);
     for (auto it = g_select_totals.begin(); it != g_select_totals.end();) {
         if (it->first.first == device) {
-            if (it->second) (void)hipFree(it->second);
+            (void)it->second.release();
             it = g_select_totals.erase(it);
         } else {
             ++it;
@@ -303,13 +287,14 @@ int rt_select_records(const unsigned char *d_flags, size_t n, uint32_t *d_index,
     uint32_t *totals = nullptr;
     {
         std::lock_guard<std::mutex> lock(g_select_mutex);
-        uint32_t *&slot = g_select_totals[std::make_pair(device, stream)];
-        if (!slot) {
+        DeviceBuffer &slot = g_select_totals[std::make_pair(device, stream)];
+        if (slot.bytes() == 0) {
             if (stream_capturing(stream))
                 return fail(RT_ERR_UNSUPPORTED, "rt_select_records: the first call on a stream allocates its scratch and cannot be captured; call once uncaptured");
-            RT_HIP(hipMalloc(reinterpret_cast<void **>(&slot), RT_SELECT_MAX_GROUPS * sizeof(uint32_t)));
+            const hipError_t e = slot.reserve(RT_SELECT_MAX_GROUPS * sizeof(uint32_t));
+            if (e != hipSuccess) return fail_hip("hipMalloc(reinterpret_cast<void **>(&slot), RT_SELECT_MAX_GROUPS * sizeof(uint32_t))", e);
         }
-        totals = slot;
+        totals = slot.get<uint32_t>();
     }
     return launched("rt_select_records", rt::launch_select_records(d_flags, (uint32_t)n, d_index, d_count, totals, stream));
 }
@@ -324,10 +309,11 @@ int rt_cast_rays_indexed(const rt_scene *scene, const rt_ray *d_rays, size_t n, 
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     const bool wave_uniform = rt::option(rt::OPT_QUERY_WAVE_UNIFORM, 0) == 1;
     if (scene->ks.bfs_walk != 0u && !wave_uniform) {
-        BfsLists bl;
-        if (bfs_lists(scene, stream, (uint32_t)max_count, &bl))
+        uint32_t groups;
+        const BfsLists bl = query_bfs_lists(scene, stream, (uint32_t)max_count, &groups);
+        if (bl.lists != nullptr)
             return launched("rt_cast_rays_indexed", rt::launch_cast_rays_indexed_bfs(scene->ks, d_rays, d_hits, (uint32_t)n, d_index, d_count, (uint32_t)max_count,
-                                                                                     d_ray_count, bl.lists, bl.items_cap, bl.jobs_cap, bl.groups, stream));
+                                                                                     d_ray_count, bl.lists, bl.items_cap, bl.jobs_cap, groups, stream));
         /* no room for the lists (or a capture before the first call on this stream): the pair-wise kernel, exact as well */
     }
     return launched("rt_cast_rays_indexed", rt::launch_cast_rays_indexed(scene->ks, d_rays, d_hits, (uint32_t)n, d_index, d_count, (uint32_t)max_count, d_ray_count,

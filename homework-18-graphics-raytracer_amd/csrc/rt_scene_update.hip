@@ -339,17 +339,14 @@ int stage_and_copy(rt_scene *scene, const char *who, hipStream_t stream, void *d
     SceneUpdate &u = scene->upd;
     std::lock_guard<std::mutex> lock(u.mutex);
     const size_t need = bytes_a + bytes_b;
-    if (u.stage_bytes < need) {
+    if (u.h_stage.bytes() < need) {
         if (u.stage_event) RT_HIP(hipEventSynchronize(u.stage_event));
-        if (u.h_stage) (void)hipHostFree(u.h_stage);
-        u.h_stage = nullptr;
-        u.stage_bytes = 0;
-        RT_HIP(hipHostMalloc(&u.h_stage, need, hipHostMallocDefault));
-        u.stage_bytes = need;
+        const hipError_t e = u.h_stage.reserve(need);
+        if (e != hipSuccess) return fail_hip("hipHostMalloc(&u.h_stage, need, hipHostMallocDefault)", e);
     }
     if (!u.stage_event) RT_HIP(hipEventCreateWithFlags(&u.stage_event, hipEventDisableTiming));
     else RT_HIP(hipEventSynchronize(u.stage_event));
-    unsigned char *stage = static_cast<unsigned char *>(u.h_stage);
+    unsigned char *stage = u.h_stage.get<unsigned char>();
     memcpy(stage, h_a, bytes_a);
     if (bytes_b) memcpy(stage + bytes_a, h_b, bytes_b);
     RT_HIP(hipMemcpyAsync(d_a, stage, bytes_a, hipMemcpyHostToDevice, stream));
@@ -376,13 +373,13 @@ int rt_scene_update_vertices(rt_scene *scene, uint32_t first, uint32_t count, co
             for (const RefitNode &n : u.nodes) (n.hi - n.lo > RT_REFIT_WAVE_MAX ? large : small).push_back(n);
             const size_t total = small.size() + large.size();
             if (total != 0u) {
-                RT_HIP(hipMalloc(reinterpret_cast<void **>(&u.d_nodes), total * sizeof(RefitNode)));
-                hipError_t e = hipSuccess;
-                if (!small.empty()) e = hipMemcpy(u.d_nodes, small.data(), small.size() * sizeof(RefitNode), hipMemcpyHostToDevice);
-                if (e == hipSuccess && !large.empty()) e = hipMemcpy(u.d_nodes + small.size(), large.data(), large.size() * sizeof(RefitNode), hipMemcpyHostToDevice);
+                hipError_t e = u.d_nodes.reserve(total * sizeof(RefitNode));
+                if (e != hipSuccess) return fail_hip("hipMalloc(reinterpret_cast<void **>(&u.d_nodes), total * sizeof(RefitNode))", e);
+                RefitNode *const d_nodes = u.d_nodes.get<RefitNode>();
+                if (!small.empty()) e = hipMemcpy(d_nodes, small.data(), small.size() * sizeof(RefitNode), hipMemcpyHostToDevice);
+                if (e == hipSuccess && !large.empty()) e = hipMemcpy(d_nodes + small.size(), large.data(), large.size() * sizeof(RefitNode), hipMemcpyHostToDevice);
                 if (e != hipSuccess) {
-                    (void)hipFree(u.d_nodes);
-                    u.d_nodes = nullptr;
+                    (void)u.d_nodes.release();
                     return fail_hip("rt_scene_update_vertices: node ranges", e);
                 }
             }
@@ -399,8 +396,8 @@ int rt_scene_update_vertices(rt_scene *scene, uint32_t first, uint32_t count, co
         if (to > from) update_plane_sharing<<<(to - from + 255u) / 256u, 256, 0, stream>>>(sc, from, to);
     }
     /* the whole scene: whether a node qualifies depends on every triangle below it */
-    if (u.n_small) refit_nodes<64><<<u.n_small, 64, 0, stream>>>(sc, u.d_nodes, u.n_small);
-    if (u.n_large) refit_nodes<256><<<u.n_large, 256, 0, stream>>>(sc, u.d_nodes + u.n_small, u.n_large);
+    if (u.n_small) refit_nodes<64><<<u.n_small, 64, 0, stream>>>(sc, u.d_nodes.get<RefitNode>(), u.n_small);
+    if (u.n_large) refit_nodes<256><<<u.n_large, 256, 0, stream>>>(sc, u.d_nodes.get<RefitNode>() + u.n_small, u.n_large);
     RT_HIP(hipGetLastError());
     return RT_OK;
 }
