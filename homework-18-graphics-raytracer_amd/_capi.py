@@ -194,6 +194,17 @@ class TemporalParams(C.Structure):
     _fields_ = [("normal_min", C.c_float), ("position_max", C.c_float), ("alpha_min", C.c_float), ("max_length", C.c_uint32), ("flags", C.c_uint32)]
 
 
+class SvgfVarianceParams(C.Structure):
+    """rt_svgf_variance_params"""
+    _fields_ = [("sigma_normal", C.c_float), ("sigma_position", C.c_float), ("min_length", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class SvgfAtrousParams(C.Structure):
+    """rt_svgf_atrous_params"""
+    _fields_ = [("sigma_luminance", C.c_float), ("sigma_normal", C.c_float), ("sigma_position", C.c_float),
+                ("first_level", C.c_uint32), ("n_levels", C.c_uint32), ("flags", C.c_uint32)]
+
+
 AMD_SYMBOLS = [
     "rt_abi_version", "rt_last_error", "rt_device_count", "rt_set_device", "rt_frame_rows", "rt_frame_pixels",
     "rt_scene_create", "rt_scene_destroy", "rt_render_whitted", "rt_render_whitted_host", "rt_set_option", "rt_set_variant",
@@ -210,6 +221,7 @@ AMD_SYMBOLS = [
     "rt_film_offsets", "rt_camera_rays_offset", "rt_camera_rays_offset_host", "rt_film_splat",
     "rt_denoise_temp_bytes", "rt_denoise_atrous", "rt_denoise_atrous_host",
     "rt_temporal_motion", "rt_temporal_accumulate", "rt_temporal_motion_host", "rt_temporal_accumulate_host",
+    "rt_svgf_variance", "rt_svgf_temp_bytes", "rt_svgf_atrous", "rt_svgf_variance_host", "rt_svgf_atrous_host",
     "rt_refract_enter", "rt_refract_step",
     "rt_scene_update_vertices", "rt_scene_update_spheres", "rt_scene_update_lights", "rt_scene_update_materials",
     "rt_ray_keys", "rt_sort_temp_bytes", "rt_sort_records", "rt_gather_records", "rt_scatter_records",
@@ -222,7 +234,7 @@ HOST_SYMBOLS = [
     "rt_world_build_reference_scene", "rt_world_save_scene", "rt_world_load_scene", "rt_reference_camera", "rt_world_desc", "rt_frame_full", "rt_post_process", "rt_luma_row",
     "rt_encode_srgb8", "rt_accumulate", "rt_accumulator_resolve", "rt_write_png", "rt_host_last_error",
     "rt_film_offsets_host", "rt_film_splat_host", "rt_denoise_atrous_cpu",
-    "rt_temporal_motion_cpu", "rt_temporal_accumulate_cpu",
+    "rt_temporal_motion_cpu", "rt_temporal_accumulate_cpu", "rt_svgf_variance_cpu", "rt_svgf_atrous_cpu",
 ]
 
 _amd = None
@@ -274,6 +286,9 @@ def host_lib() -> C.CDLL:
         lib.rt_temporal_motion_cpu.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(Camera), C.POINTER(Frame), C.c_void_p]
         lib.rt_temporal_accumulate_cpu.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(TemporalGuides), C.POINTER(TemporalGuides), C.POINTER(TemporalParams),
                                                    C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.rt_svgf_variance_cpu.argtypes = [C.c_void_p, C.POINTER(DenoiseGuides), C.POINTER(SvgfVarianceParams), C.c_uint32, C.c_uint32, C.c_void_p]
+        lib.rt_svgf_atrous_cpu.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(DenoiseGuides), C.POINTER(SvgfAtrousParams), C.c_uint32, C.c_uint32,
+                                           C.c_void_p, C.c_void_p, C.c_void_p]
         lib.rt_write_png.argtypes = [C.c_char_p, C.c_void_p, C.c_uint32, C.c_uint32]
         lib.rt_host_last_error.restype = C.c_char_p
         _host = lib
@@ -398,6 +413,14 @@ def amd_lib() -> C.CDLL:
                                                C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.rt_temporal_accumulate_host.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(TemporalGuides), C.POINTER(TemporalGuides), C.POINTER(TemporalParams),
                                                     C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.rt_svgf_variance.argtypes = [C.c_void_p, C.POINTER(DenoiseGuides), C.POINTER(SvgfVarianceParams), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+        lib.rt_svgf_variance_host.argtypes = [C.c_void_p, C.POINTER(DenoiseGuides), C.POINTER(SvgfVarianceParams), C.c_uint32, C.c_uint32, C.c_void_p]
+        lib.rt_svgf_temp_bytes.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
+        lib.rt_svgf_temp_bytes.restype = C.c_size_t
+        lib.rt_svgf_atrous.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(DenoiseGuides), C.POINTER(SvgfAtrousParams), C.c_uint32, C.c_uint32,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.rt_svgf_atrous_host.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(DenoiseGuides), C.POINTER(SvgfAtrousParams), C.c_uint32, C.c_uint32,
+                                            C.c_void_p, C.c_void_p]
         lib.rt_refract_enter.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p]
         lib.rt_refract_step.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

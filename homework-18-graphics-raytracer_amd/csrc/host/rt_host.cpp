@@ -21,6 +21,7 @@
 #include "../rt_film.h"
 #include "../rt_denoise.h"
 #include "../rt_temporal.h"
+#include "../rt_svgf.h"
 
 using rt::V3;
 
@@ -642,6 +643,32 @@ int rt_temporal_accumulate_cpu(const float *color, const float *motion, const rt
     const rt::TemporalCall t = rt::temporal_call(color, motion, *current, *previous, *params, rows, cols, history_in, history_out, variance);
     const uint64_t n = (uint64_t)rows * cols;
     for (uint64_t i = 0; i < n; ++i) rt::temporal_pixel(t, i);
+    return RT_OK;
+}
+
+/* ---- variance-guided filter queries: the CPU definition (include/rt_amd.h "variance-guided filter queries"; the arithmetic is rt_svgf.h's, shared with the device) ---- */
+
+int rt_svgf_variance_cpu(const rt_temporal_pixel *history, const rt_denoise_guides *guides, const rt_svgf_variance_params *params, uint32_t rows,
+                         uint32_t cols, float *variance_out) {
+    const char *bad = rt::svgf_variance_limits(history, guides, params, rows, cols, variance_out, false);
+    if (bad) return fail(RT_ERR_INVALID_ARGUMENT, std::string("rt_svgf_variance_cpu: ") + bad);
+    if (rows == 0u || cols == 0u) return RT_OK;
+    const rt::SvgfVariance v = rt::svgf_variance_call(history, *guides, *params, rows, cols, variance_out);
+    for (uint32_t r = 0; r < rows; ++r)
+        for (uint32_t c = 0; c < cols; ++c) variance_out[(uint64_t)r * cols + c] = rt::svgf_variance_pixel(v, r, c);
+    return RT_OK;
+}
+
+int rt_svgf_atrous_cpu(const float *color, uint32_t color_stride, const float *variance, const rt_denoise_guides *guides,
+                       const rt_svgf_atrous_params *params, uint32_t rows, uint32_t cols, float *out, float *variance_out, void *temp) {
+    const char *bad = rt::svgf_atrous_limits(color, color_stride, variance, guides, params, rows, cols, out, variance_out, static_cast<float *>(temp), true);
+    if (bad) return fail(RT_ERR_INVALID_ARGUMENT, std::string("rt_svgf_atrous_cpu: ") + bad);
+    if (rows == 0u || cols == 0u) return RT_OK;
+    for (uint32_t j = 0; j < params->n_levels; ++j) {
+        const rt::SvgfLevel L = rt::svgf_level(color, color_stride, variance, *guides, *params, rows, cols, out, variance_out, static_cast<float *>(temp), j);
+        for (uint32_t r = 0; r < rows; ++r)
+            for (uint32_t c = 0; c < cols; ++c) rt::svgf_pixel(L, r, c);
+    }
     return RT_OK;
 }
 

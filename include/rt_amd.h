@@ -1127,8 +1127,9 @@ int rt_film_splat(uint32_t rows, uint32_t cols, const float *d_samples, const un
  * >= 2^32; n_levels < 1 or first_level + n_levels > 6; a sigma that is not > 0 (NaN included; +inf is legal); unknown flag bits; a
  * demodulation flag without an albedo plane; a stride smaller than its plane's width; a null d_color or d_out; a null d_temp with
  * n_levels >= 2; d_out or d_temp equal to d_color or to each other.  rows == 0 or cols == 0 is RT_OK and launches nothing.
- * Not covered: variance-guided sigmas (SVGF), temporal accumulation, halos between the bands of a sharded frame (pixels beyond the
- * edge of the array do not exist), rt_multi_* forms. */
+ * Not covered here: variance-guided sigmas — they are rt_svgf_atrous of the "variance-guided filter queries" below; temporal accumulation
+ * — the "temporal queries" below; halos between the bands of a sharded frame (pixels beyond the edge of the array do not exist),
+ * rt_multi_* forms. */
 
 #define RT_DENOISE_DEMODULATE_IN 1u
 #define RT_DENOISE_DEMODULATE_OUT 2u
@@ -1226,9 +1227,10 @@ int rt_denoise_atrous_host(const float *h_color, const rt_denoise_guides *guides
  * alpha_min outside [0, 1]; position_max >= 0 false; flags != 0; a plane given in one set and NULL in the other.  rt_temporal_motion: a
  * null camera or frame; a frame that is not the full frame; width * height >= 2^32 (RT_ERR_UNSUPPORTED); an empty frame is RT_OK; a null
  * position or motion; a stride smaller than its plane's width.
- * Not covered: the variance-guided A-Trous that reads the variance plane; a spatial variance estimate for short histories; motion of
- * moving geometry derived from scene updates; tiles and banded frames; rt_multi_* forms; clamping history to the neighbourhood's
- * colour box. */
+ * The variance-guided A-Trous that reads the variance plane, and the spatial variance estimate for short histories, are the
+ * "variance-guided filter queries" below (rt_svgf_atrous, rt_svgf_variance).
+ * Not covered: motion of moving geometry derived from scene updates; tiles and banded frames; rt_multi_* forms; clamping history to
+ * the neighbourhood's colour box. */
 
 typedef struct rt_temporal_pixel {
     float color[3];           /* the accumulated colour */
@@ -1274,6 +1276,109 @@ int rt_temporal_accumulate_host(const float *h_color, const float *h_motion, con
                                 const rt_temporal_params *params, uint32_t rows, uint32_t cols, const rt_temporal_pixel *h_history_in,
                                 rt_temporal_pixel *h_history_out, float *h_variance);
 
+/* ---- variance-guided filter queries: the spatial half of SVGF -------------------------------------
+
+ * What consumes the temporal block: a per-pixel luminance variance that is usable at every history length (rt_svgf_variance), and an
+ * edge-avoiding A-Trous filter whose luminance weight is scaled by that variance and which filters the variance along with the colour
+ * (rt_svgf_atrous) — the spatial half of Schied et al., "Spatiotemporal Variance-Guided Filtering" (HPG 2017):
+ *     ... rt_temporal_motion -> rt_temporal_accumulate -> rt_svgf_variance -> rt_svgf_atrous -> rt_post_process_device
+ * The reference has no counterpart; the definition below is the contract.  It is written once (csrc/rt_svgf.h, on pieces of
+ * csrc/rt_denoise.h and csrc/rt_temporal.h where the operation is the same) and compiled into both libraries without contraction, so
+ * the device forms (every kernel form, any launch geometry), the _host forms and rt_svgf_variance_cpu / rt_svgf_atrous_cpu (librt_host.so,
+ * include/rt_host.h) return the same bits.  Every device call is stream-ordered and asynchronous on hip_stream, allocates nothing,
+ * visits the host for nothing and may be captured into a HIP graph at once.  Every output word is written by one thread, which walks
+ * its own taps in the order written here: no atomics, nothing depends on the launch.
+ *
+ * Planes are those of the two blocks above: a base pointer and a record stride in 4-byte WORDS, pixel i = r * cols + c; the guides are
+ * rt_denoise_guides as they are.  Every operation is a single f32 operation in the order written, none fused.
+ *   e(x)     x > 100 ? +0 : (float)rtdm::exp_mid(-(double)x)       as in step 3 of the denoise queries
+ *   lum(C)   (0.2126f * C0 + 0.7152f * C1) + 0.0722f * C2          as in the temporal queries
+ *   dist2    as in the denoise queries
+ *   vpos(v)  v >= 0 ? v : +0      a negative or NaN variance reads as +0: THE rule wherever a variance is read
+ *
+ * rt_svgf_variance, for pixel p = (r, c) with record R_p of `history` (the records rt_temporal_accumulate just wrote):
+ *   1. +0 when valid is not NULL and valid_p == 0, or when R_p.length == 0
+ *   2. when R_p.length >= min_length:  v = moment2 - moment1 * moment1, written as v > 0 ? v : +0 — the bits rt_temporal_accumulate
+ *      wrote to its variance plane
+ *   3. otherwise s1 = s2 = wsum = +0, and for dr = -3 .. 3 (outer), dc = -3 .. 3 (inner), both ascending, always at step 1:
+ *        q = (r + dr, c + dc);  skipped when outside the image, when valid is not NULL and valid_q == 0, or when R_q.length == 0
+ *        x = +0;   if normal:  x = x + dist2(n_p, n_q) / sn2;   if position:  x = x + dist2(P_p, P_q) / sp2     (sn2, sp2: the squared sigmas)
+ *        skipped unless x >= 0
+ *        w = e(x);   s1 = s1 + moment1_q * w;   s2 = s2 + moment2_q * w;   wsum = wsum + w
+ *      then, if wsum > 0:  a1 = s1 / wsum;  a2 = s2 / wsum;  v = a2 - a1 * a1;  v = v > 0 ? v : +0;  written:
+ *      v * ((float)min_length / (float)R_p.length) — a short history's estimate is inflated, as in the paper;  otherwise +0.
+ * A reset pixel (length 1, temporal variance +0) so gets the variance of its neighbourhood's first moments instead of "converged".
+ * Consequences: with min_length = 1 the output is the temporal variance plane bit for bit; a pixel with length >= min_length does not
+ * look at the guides.
+ *
+ * rt_svgf_atrous: d_color is 3 f32 per pixel at a word stride >= 3 (the colour inside the history records, stride 8, goes in where it
+ * lies), d_variance one compact f32 per pixel, d_out a compact colour plane, d_variance_out a compact variance plane or NULL.  The
+ * variance must be of the colour the filter SEES: a caller who demodulates passes the variance of the demodulated colour.
+ * One level l (0 <= l <= 5), step s = 1 << l, input colour `in`, input variance `vin`, for output pixel p = (r, c):
+ *   1. the colour seen at q:  C_q = in at q, divided by (albedo_q + 1e-3f) on a demodulating level exactly as in the denoise queries;
+ *      l_q = lum(C_q);   V_q = vpos(vin_q)
+ *   2. an invalid p (valid is not NULL and valid_p == 0) passes through: the colour's raw words and the variance's raw word
+ *   3. the variance at p, prefiltered, always at step 1:  gs = ks = +0;  for dr = -1 .. 1 (outer), dc = -1 .. 1 (inner), each tap inside
+ *      the image and valid, k = hk[dr + 1] * hk[dc + 1] with hk = {1/4, 1/2, 1/4}:   gs = gs + k * V_q;   ks = ks + k
+ *      g = ks > 0 ? gs / ks : +0;    sl = sigma_luminance * (rtdm::f_sqrt(g) + 1e-6f)
+ *   4. sum_k = vsum = wsum = +0, and dr, dc = -2 .. 2 at step s as in the denoise queries, with the same skip rules:
+ *        d = |l_p - l_q|  (the sign bit cleared);   x = d / sl;   the normal and position terms added exactly as in the denoise queries
+ *        skipped unless x >= 0
+ *        w = h[dr + 2] * h[dc + 2] * e(x)
+ *        sum_k = sum_k + C_q[k] * w;    vsum = vsum + V_q * (w * w);    wsum = wsum + w
+ *   5. if wsum > 0:  out = sum_k / wsum, remodulated on a remodulating level;  variance_out = vsum / (wsum * wsum);
+ *      otherwise p passes through as in 2.
+ * sigma_luminance does not change with the level.  A call runs levels first_level .. first_level + n_levels - 1; they alternate between
+ * d_temp and the outputs so that the LAST level writes d_out and d_variance_out; the inputs are only read.  flags are the
+ * RT_DENOISE_DEMODULATE_* bits with the meaning they have in rt_denoise_atrous.  d_temp is opaque scratch of rt_svgf_temp_bytes bytes
+ * (0 for one level).  Consequences: one call of n levels equals n calls of one level that chain (colour, variance), level j of them
+ * with first_level + j, DEMODULATE_IN on the first only, DEMODULATE_OUT on the last only; for colours that are finite or NaN,
+ * sigma_luminance = +inf gives the colour bits of rt_denoise_atrous with sigma_color = +inf on the same guides and flags.
+ *
+ * Checked before any device work, all RT_ERR_INVALID_ARGUMENT with a message that names the argument, in this order: a null guides or
+ * params; rows * cols >= 2^32; (atrous) n_levels < 1 or first_level + n_levels > 6; a sigma that is not > 0 (NaN included; +inf is
+ * legal); (variance) min_length < 1; unknown flag bits; a demodulation flag without an albedo plane; a stride smaller than its plane's
+ * width; then rows == 0 or cols == 0 is RT_OK and launches nothing; a null required pointer (history, color, variance, out, the
+ * variance call's variance_out; d_temp with n_levels >= 2); an output or the scratch equal to an input, to each other or to the scratch;
+ * (device forms) a history array that is not 16-byte aligned.
+ * Not covered: writing a filtered level back into the history records (SVGF's feedback of level 0); SVGF's depth-gradient and dot^128
+ * normal weights — this block keeps the project's own normal and position terms; banded frames and rt_multi_* forms; clamping history
+ * to the neighbourhood's colour box. */
+
+typedef struct rt_svgf_variance_params {
+    float sigma_normal;
+    float sigma_position;     /* each > 0, +inf: the term is off */
+    uint32_t min_length;      /* >= 1: histories shorter than this take the spatial estimate */
+    uint32_t flags;           /* reserved: 0 */
+} rt_svgf_variance_params;   /* 16 bytes */
+
+typedef struct rt_svgf_atrous_params {
+    float sigma_luminance;    /* the same at every level: scaled per pixel by the square root of the prefiltered variance */
+    float sigma_normal;
+    float sigma_position;     /* each > 0, +inf: the term is off */
+    uint32_t first_level;
+    uint32_t n_levels;        /* first_level + n_levels <= RT_DENOISE_MAX_LEVELS */
+    uint32_t flags;           /* RT_DENOISE_DEMODULATE_* */
+} rt_svgf_atrous_params;     /* 24 bytes */
+
+/* d_history: rows * cols records, 16-byte aligned; guides->albedo is not looked at; d_variance_out: rows * cols f32; one kernel launch */
+int rt_svgf_variance(const rt_temporal_pixel *d_history, const rt_denoise_guides *guides, const rt_svgf_variance_params *params, uint32_t rows,
+                     uint32_t cols, float *d_variance_out, void *hip_stream);
+/* what d_temp of rt_svgf_atrous must hold for a call of n_levels levels: 0 for one level, else 16 bytes per pixel (colour and variance
+ * interleaved), and 4 more per pixel from three levels on */
+size_t rt_svgf_temp_bytes(uint32_t rows, uint32_t cols, uint32_t n_levels);
+/* one kernel launch per level; nothing but d_out, d_variance_out and d_temp is written */
+int rt_svgf_atrous(const float *d_color, uint32_t color_stride, const float *d_variance, const rt_denoise_guides *guides,
+                   const rt_svgf_atrous_params *params, uint32_t rows, uint32_t cols, float *d_out, float *d_variance_out, void *d_temp,
+                   void *hip_stream);
+/* The same kernels on HOST arrays (the pointers of `guides` are host pointers too): allocate, upload every plane with its stride, run,
+ * synchronise the device and download.  No h_temp: the round trip makes its own.  NOT the CPU definition — that is rt_svgf_*_cpu of
+ * librt_host.so. */
+int rt_svgf_variance_host(const rt_temporal_pixel *h_history, const rt_denoise_guides *guides, const rt_svgf_variance_params *params, uint32_t rows,
+                          uint32_t cols, float *h_variance_out);
+int rt_svgf_atrous_host(const float *h_color, uint32_t color_stride, const float *h_variance, const rt_denoise_guides *guides,
+                        const rt_svgf_atrous_params *params, uint32_t rows, uint32_t cols, float *h_out, float *h_variance_out);
+
 /* ---- diagnostics ------------------------------------------------------------ */
 
 /* Which kernel renders the Whitted pass (process-wide; same results bit for bit):
@@ -1291,7 +1396,7 @@ int rt_temporal_accumulate_host(const float *h_color, const float *h_motion, con
  * RT_AMD_DIST_BY_COST, RT_AMD_DIST_OWN_FIRST, RT_AMD_DIST_PREP_FIRST, RT_AMD_DIST_SPLIT, RT_AMD_DIAG_WS_REFUSE,
  * RT_AMD_MULTI_FORCE_STAGE, RT_AMD_BFS_WALK_TRIANGLES (read by rt_scene_create), RT_AMD_WF_SHARE, RT_AMD_DIAG_BFS_CAP,
  * RT_AMD_DIAG_DIST_BAND_RAYS, RT_AMD_QUERY_WAVE_UNIFORM, RT_AMD_DIAG_HIT_BAND_RECORDS, RT_AMD_FILM_SPLAT_FORM, RT_AMD_DIAG_FILM_MAX_GROUPS,
- * RT_AMD_DENOISE_FORM, RT_AMD_DIAG_DENOISE_MAX_GROUPS, RT_AMD_DIAG_TEMPORAL_MAX_GROUPS (INTEGRATION.md says what each does); any other name is RT_ERR_INVALID_ARGUMENT.  The environment is read ONCE per process, at the first use;
+ * RT_AMD_DENOISE_FORM, RT_AMD_DIAG_DENOISE_MAX_GROUPS, RT_AMD_DIAG_TEMPORAL_MAX_GROUPS, RT_AMD_SVGF_FORM, RT_AMD_DIAG_SVGF_MAX_GROUPS (INTEGRATION.md says what each does); any other name is RT_ERR_INVALID_ARGUMENT.  The environment is read ONCE per process, at the first use;
  * after that only this call changes a switch: value = decimal integer, NULL or "" = unset (the library's own choice).  Render
  * calls read the switches without locks: set them between calls, not during one. */
 int rt_set_option(const char *name, const char *value);

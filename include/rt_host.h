@@ -120,6 +120,15 @@ int rt_temporal_accumulate_cpu(const float *color, const float *motion, const rt
                                const rt_temporal_params *params, uint32_t rows, uint32_t cols, const rt_temporal_pixel *history_in,
                                rt_temporal_pixel *history_out, float *variance);
 
+/* The variance-guided filter queries' CPU definition (include/rt_amd.h "variance-guided filter queries" states every operation and the
+ * order): plain loops over host arrays, no device needed, bit-identical to rt_svgf_variance / rt_svgf_atrous of librt_amd.so.  Same
+ * arguments without the stream (the history needs no alignment here; temp: rt_svgf_temp_bytes bytes, or NULL for one level), same
+ * checks; a refusal returns RT_ERR_INVALID_ARGUMENT and sets rt_host_last_error().  Called _cpu for the reason rt_denoise_atrous_cpu is. */
+int rt_svgf_variance_cpu(const rt_temporal_pixel *history, const rt_denoise_guides *guides, const rt_svgf_variance_params *params, uint32_t rows,
+                         uint32_t cols, float *variance_out);
+int rt_svgf_atrous_cpu(const float *color, uint32_t color_stride, const float *variance, const rt_denoise_guides *guides,
+                       const rt_svgf_atrous_params *params, uint32_t rows, uint32_t cols, float *out, float *variance_out, void *temp);
+
 /* RGB8 PNG, written to "<path>.tmp" then renamed over path. */
 int rt_write_png(const char *path, const uint8_t *rgb8, uint32_t width, uint32_t height);
 
