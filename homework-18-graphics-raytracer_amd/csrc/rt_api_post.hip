@@ -46,9 +46,21 @@ int rt_post_release(void) {
 }
 
 int rt_post_process_device(float *d_rgb, size_t n_pixels, float *d_divisor, void *hip_stream) {
-    if (!d_rgb) return fail(RT_ERR_INVALID_ARGUMENT, "rt_post_process_device: null argument");
-    if (n_pixels == 0) return RT_OK;
+    if (n_pixels && !d_rgb) return fail(RT_ERR_INVALID_ARGUMENT, "rt_post_process_device: null argument"); /* no pixels: nothing is read */
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    if (n_pixels == 0) {
+        /* an empty image is "left untouched": divisor 0 (all bits zero), written in stream order as a memset node — nothing written from
+         * the host, and capturable.  Only memory the runtime knows a device can reach takes a stream-ordered write; for any other
+         * pointer (and without a device) there is nothing to enqueue, as before. */
+        if (!d_divisor) return RT_OK;
+        hipPointerAttribute_t attr;
+        if (hipPointerGetAttributes(&attr, d_divisor) != hipSuccess) {
+            (void)hipGetLastError();
+            return RT_OK;
+        }
+        if (attr.type != hipMemoryTypeDevice && attr.type != hipMemoryTypeManaged && attr.type != hipMemoryTypeHost) return RT_OK;
+        return launched("rt_post_process_device", hipMemsetAsync(d_divisor, 0, sizeof(float), stream));
+    }
     uint32_t *keys = nullptr, *state = nullptr;
     int device = 0;
     RT_HIP(hipGetDevice(&device));
@@ -94,7 +106,9 @@ int rt_post_scale_device(float *d_rgb, size_t n_pixels, const uint32_t *d_state,
 
 int rt_accumulate_device(const float *d_samples, const unsigned char *d_valid, uint32_t n_epochs, size_t n_pixels, float *d_sum,
                          float *d_weight, void *hip_stream) {
-    if (!d_samples || !d_valid || !d_sum || !d_weight) return fail(RT_ERR_INVALID_ARGUMENT, "rt_accumulate_device: null argument");
+    /* what an empty call never reads may be NULL (an empty tensor's pointer is): no epochs -> no samples, no pixels -> nothing at all */
+    if (n_pixels && (!d_sum || !d_weight || (n_epochs && (!d_samples || !d_valid))))
+        return fail(RT_ERR_INVALID_ARGUMENT, "rt_accumulate_device: null argument");
     return launched("rt_accumulate_device", rt::launch_accumulate(d_samples, d_valid, n_epochs, n_pixels, d_sum, d_weight, static_cast<hipStream_t>(hip_stream)));
 }
 

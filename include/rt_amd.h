@@ -972,7 +972,10 @@ int rt_multi_render_distributed(rt_multi *m, const rt_camera *camera, const rt_f
  * post_process (src/main.rs:748-762): divide the image in place by the 99th-percentile luma of its normal
  * lumas (exact radix select; no sort).  *d_divisor (device float, may be NULL) receives the divisor used, 0 when
  * the image was left untouched (no normal luma, or percentile <= f32::EPSILON).  Bit-identical to
- * rt_post_process in librt_host.so.  Stream-ordered. */
+ * rt_post_process in librt_host.so.  Stream-ordered.  n_pixels = 0 is an image left untouched: nothing is read, and *d_divisor
+ * (when not NULL) still receives 0 — by a write enqueued on hip_stream like every other, never from the host, so the call stays
+ * asynchronous and can be captured (as rt_post_scale_device with n_pixels = 0, and as rt_post_process returns 0 for an empty
+ * image; d_rgb may then be NULL).  d_divisor must be memory a device can reach; a pointer the runtime does not know as such is not written. */
 int rt_post_process_device(float *d_rgb, size_t n_pixels, float *d_divisor, void *hip_stream);
 /* rt_post_process_device keeps a grow-only scratch buffer per (device, stream); this frees those of the current device
  * (synchronises it first). */
@@ -1001,7 +1004,8 @@ int rt_encode_srgb8_device(const float *d_rgb, size_t n_values, unsigned char *d
  * rt_accumulate / rt_accumulator_resolve in librt_host.so: d_sum (3 f32 per pixel) and d_weight (1 f32 per pixel) start
  * at zero; rt_accumulate_device applies accumulate() for every sample whose filter flag is set (d_samples, d_valid: the
  * n_epochs x n_pixels outputs of rt_render_distributed), in epoch order; rt_accumulator_resolve_device writes
- * sum / weight, black while weight < f32::EPSILON.  Stream-ordered. */
+ * sum / weight, black while weight < f32::EPSILON.  Stream-ordered.  n_epochs = 0 or n_pixels = 0 changes nothing, and the arrays
+ * such a call would not read (d_samples and d_valid without epochs, all four without pixels) may be NULL. */
 int rt_accumulate_device(const float *d_samples, const unsigned char *d_valid, uint32_t n_epochs, size_t n_pixels, float *d_sum,
                          float *d_weight, void *hip_stream);
 int rt_accumulator_resolve_device(const float *d_sum, const float *d_weight, size_t n_pixels, float *d_rgb, void *hip_stream);

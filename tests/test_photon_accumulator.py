@@ -5,6 +5,7 @@ import pytest
 
 import homework_18_graphics_raytracer_amd as rt
 import _oracle
+import _post_support as ps
 
 
 def _random_epochs(seed, n_epochs, rows, cols):
@@ -80,3 +81,97 @@ def test_averaged_stochastic_pass_end_to_end():
     _oracle.accumulate(np.ascontiguousarray(s), np.ascontiguousarray(v.astype(np.uint8)), want_sum, want_w)
     want = _oracle.accumulator_resolve(want_sum, want_w)
     assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
+
+
+# ---- the edges, against a numpy float32 restatement (tests/_post_support.py) ---------------------------------------------------------
+
+def _edge_case(name, n_pixels):
+    """(samples, valid) of shape (n_epochs, 1, n_pixels, ...)"""
+    rng = np.random.default_rng(n_pixels)
+    n_epochs = {"one_epoch": 1, "no_epochs": 0}.get(name, 3)
+    s = rng.normal(0.5, 2.0, (n_epochs, 1, n_pixels, 3)).astype(np.float32)
+    v = (rng.random((n_epochs, 1, n_pixels)) < 0.7).astype(np.uint8)
+    if name == "nothing_valid":
+        v[:] = 0
+    elif name == "odd_valid":  # NaN and inf samples that passed the filter
+        s[rng.random(s.shape) < 0.2] = np.nan
+        s[rng.random(s.shape) < 0.1] = np.inf
+        s[rng.random(s.shape) < 0.1] = -np.inf
+        v[:] = 1
+    elif name == "nan_invalid":  # every sample that did not pass holds NaN: it must not reach the sum, not even as NaN * 0
+        s[v == 0] = np.nan
+    return s, v
+
+
+EDGE_CASES = ["nothing_valid", "one_epoch", "odd_valid", "nan_invalid", "no_epochs"]
+EDGE_PIXELS = [1, 255, 257, 2048 * 256 + 257]
+
+
+def _check_accumulator(device, name, n_pixels):
+    s, v = _edge_case(name, n_pixels)
+    start = np.random.default_rng(1).normal(0, 1, (1, n_pixels, 3)).astype(np.float32)  # a running accumulator: it does not start at zero
+    start_w = np.full((1, n_pixels), 2.0, np.float32)
+    if name == "nothing_valid":
+        start[:], start_w[:] = 0.0, 0.0
+    want_sum, want_w = start.copy(), start_w.copy()
+    ps.accumulate_reference(s, v, want_sum, want_w)
+    acc = rt.PhotonAccumulator(1, n_pixels, device=device)
+    if device == "cpu":
+        acc.sum[:], acc.weight[:] = start, start_w
+        acc.accumulate(s, v)
+        g_sum, g_w, got = acc.sum, acc.weight, acc.resolve()
+    else:
+        import torch
+
+        acc.sum.copy_(torch.from_numpy(start)); acc.weight.copy_(torch.from_numpy(start_w))
+        acc.accumulate(torch.from_numpy(s).cuda(), torch.from_numpy(v).cuda())
+        g_sum, g_w, got = acc.sum.cpu().numpy(), acc.weight.cpu().numpy(), acc.resolve().cpu().numpy()
+    assert ((ps.bits(g_sum) == ps.bits(want_sum)) | (np.isnan(g_sum) & np.isnan(want_sum))).all() and np.array_equal(g_w, want_w)
+    want = ps.resolve_reference(want_sum, want_w)
+    assert ((ps.bits(got) == ps.bits(want)) | (np.isnan(got) & np.isnan(want))).all()
+    if name == "nothing_valid":
+        assert not g_w.any() and not ps.bits(got).any()  # weight stays 0, resolve gives black (+0)
+    if name == "no_epochs":
+        assert np.array_equal(ps.bits(g_sum), ps.bits(start)) and np.array_equal(g_w, start_w)
+    if name == "nan_invalid":
+        assert not np.isnan(g_sum).any()
+
+
+def _check_resolve_weights(device):
+    """weight 0, 2^-24, 2^-23 and 1: the test is w < f32::EPSILON, so 2^-23 divides"""
+    weights = np.tile(np.array([0.0, 2.0 ** -24, 2.0 ** -23, 1.0], np.float32), 65)[None, :257]
+    sums = np.random.default_rng(2).normal(0, 3, (1, 257, 3)).astype(np.float32)
+    acc = rt.PhotonAccumulator(1, 257, device=device)
+    if device == "cpu":
+        acc.sum[:], acc.weight[:] = sums, weights
+        got = acc.resolve()
+    else:
+        import torch
+
+        acc.sum.copy_(torch.from_numpy(sums)); acc.weight.copy_(torch.from_numpy(weights))
+        got = acc.resolve().cpu().numpy()
+    assert np.array_equal(ps.bits(got), ps.bits(ps.resolve_reference(sums, weights)))
+    assert not ps.bits(got[0, 0::4]).any() and not ps.bits(got[0, 1::4]).any()
+    assert np.array_equal(got[0, 2::4], sums[0, 2::4] * np.float32(2.0 ** 23)) and np.array_equal(got[0, 3::4], sums[0, 3::4])
+
+
+@pytest.mark.parametrize("n_pixels", EDGE_PIXELS[:3])
+@pytest.mark.parametrize("name", EDGE_CASES)
+def test_host_accumulator_edges(name, n_pixels):
+    _check_accumulator("cpu", name, n_pixels)
+
+
+def test_host_resolve_at_the_epsilon_test():
+    _check_resolve_weights("cpu")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n_pixels", EDGE_PIXELS)
+@pytest.mark.parametrize("name", EDGE_CASES)
+def test_device_accumulator_edges(name, n_pixels):
+    _check_accumulator("cuda", name, n_pixels)
+
+
+@pytest.mark.gpu
+def test_device_resolve_at_the_epsilon_test():
+    _check_resolve_weights("cuda")
