@@ -224,6 +224,7 @@ AMD_SYMBOLS = [
     "rt_svgf_variance", "rt_svgf_temp_bytes", "rt_svgf_atrous", "rt_svgf_variance_host", "rt_svgf_atrous_host",
     "rt_refract_enter", "rt_refract_step",
     "rt_scene_update_vertices", "rt_scene_update_spheres", "rt_scene_update_lights", "rt_scene_update_materials",
+    "rt_scene_keep_positions", "rt_scene_positions_kept", "rt_previous_positions", "rt_previous_positions_host",
     "rt_ray_keys", "rt_sort_temp_bytes", "rt_sort_records", "rt_gather_records", "rt_scatter_records",
     "rt_triangle_keys", "rt_order_triangles_temp_bytes", "rt_order_triangles", "rt_order_triangles_host",
     "rt_diag_scene_nodes",
@@ -235,6 +236,7 @@ HOST_SYMBOLS = [
     "rt_encode_srgb8", "rt_accumulate", "rt_accumulator_resolve", "rt_write_png", "rt_host_last_error",
     "rt_film_offsets_host", "rt_film_splat_host", "rt_denoise_atrous_cpu",
     "rt_temporal_motion_cpu", "rt_temporal_accumulate_cpu", "rt_svgf_variance_cpu", "rt_svgf_atrous_cpu",
+    "rt_previous_positions_cpu",
 ]
 
 _amd = None
@@ -289,6 +291,7 @@ def host_lib() -> C.CDLL:
         lib.rt_svgf_variance_cpu.argtypes = [C.c_void_p, C.POINTER(DenoiseGuides), C.POINTER(SvgfVarianceParams), C.c_uint32, C.c_uint32, C.c_void_p]
         lib.rt_svgf_atrous_cpu.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(DenoiseGuides), C.POINTER(SvgfAtrousParams), C.c_uint32, C.c_uint32,
                                            C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.rt_previous_positions_cpu.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32]
         lib.rt_write_png.argtypes = [C.c_char_p, C.c_void_p, C.c_uint32, C.c_uint32]
         lib.rt_host_last_error.restype = C.c_char_p
         _host = lib
@@ -429,6 +432,10 @@ def amd_lib() -> C.CDLL:
         lib.rt_scene_update_spheres.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
         lib.rt_scene_update_lights.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(Light), C.c_void_p]
         lib.rt_scene_update_materials.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(Material), C.c_void_p]
+        lib.rt_scene_keep_positions.argtypes = [C.c_void_p, C.c_void_p]
+        lib.rt_scene_positions_kept.argtypes = [C.c_void_p]
+        lib.rt_previous_positions.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p]
+        lib.rt_previous_positions_host.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32]
         lib.rt_ray_keys.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.c_void_p, C.c_void_p]
         lib.rt_sort_temp_bytes.argtypes = [C.c_size_t]
         lib.rt_sort_temp_bytes.restype = C.c_size_t

@@ -22,6 +22,7 @@
 #include "../rt_denoise.h"
 #include "../rt_temporal.h"
 #include "../rt_svgf.h"
+#include "../rt_motion.h"
 
 using rt::V3;
 
@@ -669,6 +670,59 @@ int rt_svgf_atrous_cpu(const float *color, uint32_t color_stride, const float *v
         for (uint32_t r = 0; r < rows; ++r)
             for (uint32_t c = 0; c < cols; ++c) rt::svgf_pixel(L, r, c);
     }
+    return RT_OK;
+}
+
+/* ---- motion queries: the CPU definition (include/rt_amd.h "motion queries"; the arithmetic is rt_motion.h's, shared with the device) ---- */
+
+int rt_previous_positions_cpu(const rt_scene_desc *now, const float *was_triangles, const float *was_spheres, const rt_hit *hits, size_t n, float *was,
+                              uint32_t was_stride) {
+    int status;
+    bool done;
+    const bool kept = now && (was_triangles || now->n_triangles == 0u) && (was_spheres || now->n_spheres == 0u);
+    const char *bad = rt::motion_limits(n, now, kept, "null was_triangles with n_triangles > 0, or null was_spheres with n_spheres > 0", hits, was,
+                                        was_stride, &status, &done);
+    if (bad) return fail(status, std::string("rt_previous_positions_cpu: ") + bad);
+    if (done) return RT_OK;
+    if ((now->n_triangles && !now->triangles) || (now->n_spheres && !now->spheres))
+        return fail(RT_ERR_INVALID_ARGUMENT, "rt_previous_positions_cpu: null triangle or sphere array in the scene description");
+    /* what rt_scene_create and rt_scene_update_vertices derive of a triangle, operation for operation (rt_api_layout.hip, rt_scene_update.hip) */
+    std::vector<rt::DevTri> tris(now->n_triangles);
+    std::vector<rt::DevSphere> spheres(now->n_spheres);
+    std::vector<rt::MotionPiece> pieces(rt::motion_kept_pieces(now->n_triangles, now->n_spheres));
+    for (uint32_t i = 0; i < now->n_triangles; ++i) {
+        const rt_triangle &s = now->triangles[i];
+        rt::DevTri &t = tris[i];
+        memset(&t, 0, sizeof t);
+        const V3 v0 = rt::v3p(s.vertices[0].position), v1 = rt::v3p(s.vertices[1].position), v2 = rt::v3p(s.vertices[2].position);
+        const V3 nn = rt::normalize(rt::cross(v1 - v0, v2 - v1)); /* Triangle::face_normal, primitives.rs:36-42 */
+        const V3 e0 = v2 - v1, e1 = v0 - v2, e2 = v1 - v0;        /* main.rs:219-221 */
+        t.n[0] = nn.x; t.n[1] = nn.y; t.n[2] = nn.z;
+        t.v0[0] = v0.x; t.v0[1] = v0.y; t.v0[2] = v0.z;
+        t.v1[0] = v1.x; t.v1[1] = v1.y; t.v1[2] = v1.z;
+        t.v2[0] = v2.x; t.v2[1] = v2.y; t.v2[2] = v2.z;
+        t.e0[0] = e0.x; t.e0[1] = e0.y; t.e0[2] = e0.z;
+        t.e1[0] = e1.x; t.e1[1] = e1.y; t.e1[2] = e1.z;
+        t.e2[0] = e2.x; t.e2[1] = e2.y; t.e2[2] = e2.z;
+        t.area = rt::dot(rt::cross(v1 - v0, v2 - v0), nn); /* main.rs:235 */
+        for (uint32_t k = 0; k < RT_MOTION_TRI_PIECES; ++k) {
+            const float *q = was_triangles + 9u * (size_t)i + 3u * k;
+            pieces[(size_t)RT_MOTION_TRI_PIECES * i + k] = rt::MotionPiece{q[0], q[1], q[2], 0.0f};
+        }
+    }
+    for (uint32_t i = 0; i < now->n_spheres; ++i) {
+        const rt_sphere &s = now->spheres[i];
+        rt::DevSphere &d = spheres[i];
+        memset(&d, 0, sizeof d);
+        d.c[0] = s.center[0]; d.c[1] = s.center[1]; d.c[2] = s.center[2];
+        d.radius = s.radius;
+        const float *q = was_spheres + 4u * (size_t)i;
+        pieces[(size_t)RT_MOTION_TRI_PIECES * now->n_triangles + i] = rt::MotionPiece{q[0], q[1], q[2], q[3]};
+    }
+    rt::MotionScene sc;
+    sc.tris = tris.data(), sc.spheres = spheres.data(), sc.kept = pieces.data();
+    sc.n_triangles = now->n_triangles, sc.n_spheres = now->n_spheres;
+    for (uint64_t i = 0; i < n; ++i) rt::motion_record(sc, hits, was, was_stride, i);
     return RT_OK;
 }
 

@@ -439,6 +439,7 @@ int rt_scene_destroy(rt_scene *scene) {
     (void)scene->upd.d_nodes.release();
     (void)scene->upd.h_stage.release();
     if (scene->upd.stage_event) (void)hipEventDestroy(scene->upd.stage_event);
+    (void)scene->kept.d_pieces.release();
     if (scene->d_blob) e = hipFree(scene->d_blob);
     delete scene;
     if (e != hipSuccess) return fail_hip("rt_scene_destroy: hipFree", e);

@@ -18,6 +18,7 @@
  *   rt_light_query.hip the light queries' rt_light_*: kernels and entry points in one unit
  *   rt_refract_query.hip the refraction queries' rt_refract_enter / rt_refract_step: kernels and entry points in one unit
  *   rt_scene_update.hip the scene updates' rt_scene_update_*: kernels and entry points in one unit
+ *   rt_motion_query.hip the motion queries' rt_scene_keep_positions / rt_scene_positions_kept / rt_previous_positions and its _host form: kernels and entry points in one unit
  *   rt_order_query.hip the record ordering's rt_ray_keys / rt_sort_records / rt_gather_records / rt_scatter_records: kernels and entry points in one unit
  *   rt_mesh_order.hip  the mesh ordering's rt_triangle_keys / rt_order_triangles: the key kernel and entry points that call rt_order_query.hip's
  *   rt_material_query.hip the material queries' rt_material_hits / rt_probe_surfaces: kernels and entry points in one unit
@@ -142,6 +143,15 @@ struct SceneUpdate { /* the buffers and the event: freed by rt_scene_destroy */
     hipEvent_t stage_event = nullptr; /* recorded after that call's copies */
 };
 
+/* What the motion queries (rt_motion_query.hip) keep of a scene: the positions as they stood at the last rt_scene_keep_positions, in the
+ * pieces of rt_motion.h.  Allocated by the first keep under the mutex, the size fixed from then on (the counts of a scene never change);
+ * freed by rt_scene_destroy. */
+struct KeptPositions {
+    std::mutex mutex;
+    std::atomic<bool> kept{false}; /* rt_scene_keep_positions has been called (true also for a scene with nothing to keep) */
+    DeviceBuffer d_pieces;
+};
+
 /* a spot light's cone edge as a cosine, with margins (rt_shade.h light_asks); anything unusual switches the shortcut off */
 inline rt::LightAux light_aux_of(const rt_light &l) {
     rt::LightAux aux;
@@ -164,6 +174,7 @@ struct rt_scene {
     std::mutex ws_mutex;
     std::map<hipStream_t, Workspace> workspaces;
     SceneUpdate upd;
+    KeptPositions kept;
 };
 
 /* rt_last_error() of the calling thread.  (Thread-local state is reached through functions of the translation unit that defines

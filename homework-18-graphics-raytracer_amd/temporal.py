@@ -19,8 +19,8 @@ apart are then taken for another surface; POSITION_MAX 0.1 scene unit because th
 a pixel's footprint on them is of the order of a hundredth; ALPHA_MIN 0.05 so that a change of lighting fades in within about twenty
 frames; MAX_LENGTH 32 because beyond it 1 / n lies below ALPHA_MIN anyway and the length stays a small integer.
 
-For moving geometry pass ``motion``/``accumulate`` a position plane of your own that says where each point was in the previous frame;
-deriving it from scene updates is not provided.
+For moving geometry pass ``motion``/``accumulate`` the position plane that says where each point was in the previous frame:
+``rt.moving.previous_positions`` derives it from the scene updates, and ``History.push`` takes it as ``position_was``.
 """
 from __future__ import annotations
 
@@ -198,15 +198,19 @@ class History:
         r = self.records.view(self.rows, self.cols, _RECORD_WORDS)
         return r[..., 0:3].view(torch.float32), self.variance, r[..., 5]
 
-    def push(self, surfaces, camera: Camera, frame: Frame, image, stream=None):
+    def push(self, surfaces, camera: Camera, frame: Frame, image, stream=None, position_was=None):
         """Accumulate ``image``, a (rows, cols, 3) float32 CUDA tensor rendered from ``camera`` over the full frame ``frame`` whose
         ``surfaces`` are its ``materials.primary_surfaces``: motion through the previous push's camera, then accumulate against the
         previous push's surfaces and records — two kernel launches on ``stream``.  The first push finds no history: every pixel resets.
+        ``position_was``: for a scene that moved since the previous push, the plane of where each pixel's point was then
+        (``moving.previous_positions`` of ``surfaces.hits``), projected and compared instead of ``surfaces.position``.
         Returns (color, variance, length): views of the new records and the variance plane, valid until the push after the next."""
         if _full(frame) != (self.rows, self.cols):
             raise ValueError(f"frame must be {self.cols} x {self.rows}")
         prev_surfaces, prev_camera, prev_frame = self._previous if self._previous is not None else (surfaces, camera, frame)
         cur = Guides.of(surfaces)
+        if position_was is not None:
+            cur = cur._replace(position=position_was)
         motion(cur.position, prev_camera, prev_frame, valid=cur.valid, out=self.motion, stream=stream)
         accumulate(image, self.motion, self.rows, self.cols, self._records[self.frames % 2], current=cur, previous=Guides.of(prev_surfaces),
                    out=self._records[(self.frames + 1) % 2], variance=self.variance, stream=stream, **self.params)

@@ -938,6 +938,58 @@ int rt_scene_update_spheres(rt_scene *scene, uint32_t first, uint32_t count, con
 int rt_scene_update_lights(rt_scene *scene, uint32_t first, uint32_t count, const rt_light *h_lights, void *hip_stream);
 int rt_scene_update_materials(rt_scene *scene, uint32_t first, uint32_t count, const rt_material *h_materials, void *hip_stream);
 
+/* ---- motion queries: where a hit's point was before the scene update ------------------------------
+ * What an animated sequence needs between a scene update and the temporal queries below: for each hit on the scene as it stands NOW,
+ * the point of the same surface on the scene as it stood BEFORE the update — the plane of previous positions rt_temporal_motion
+ * projects and rt_temporal_accumulate compares.  The scene keeps a snapshot (rt_scene_keep_positions), and a per-hit query carries a
+ * hit point back onto it (rt_previous_positions).  Per frame: keep, then rt_scene_update_*, then cast, then rt_previous_positions.  The
+ * hits must come from the scene as it stands now; the answer lies on the scene as it stood at the keep.  The reference has no
+ * counterpart; the definition below is the contract.  It is written once (csrc/rt_motion.h) and compiled into both libraries without
+ * contraction, so rt_previous_positions (any launch geometry), its _host form and rt_previous_positions_cpu (librt_host.so,
+ * include/rt_host.h) return the same bits.
+ *
+ * rt_scene_keep_positions copies, into arrays the scene owns, the three vertex positions of every triangle and the centre and radius
+ * of every sphere as they stand on the device at that point of hip_stream: "the kept positions".  Stream-ordered: an update put on the
+ * same stream after it needs no synchronisation.  The first call on a scene allocates and is RT_ERR_UNSUPPORTED on a stream that is
+ * being captured, as the first rt_scene_update_vertices is; later calls allocate nothing and can be captured.  The arrays are freed by
+ * rt_scene_destroy; their layout is internal.  A scene with no triangles and no spheres is RT_OK, and afterwards counts as kept.  Each
+ * keep replaces the one before.  rt_scene_positions_kept: 1 after a keep, 0 before; a null scene is RT_ERR_INVALID_ARGUMENT.
+ *
+ * rt_previous_positions writes, for record i, three f32 at d_was[i * was_stride + 0 .. 2]; other words of a wider stride are not
+ * touched.  Every operation is a single f32 operation in the order written, none fused; dot(a, b) is (a0*b0 + a1*b1) + a2*b2 and
+ * cross(a, b) is (a1*b2 - a2*b1, a2*b0 - a0*b2, a0*b1 - a1*b0).  P = hit.position.
+ *   TRIANGLE (kind == 1 and index < n_triangles), with v0, v1, v2, n, e0 = v2 - v1, e1 = v0 - v2, e2 = v1 - v0 and area the triangle's
+ *   current values as rt_scene_create and rt_scene_update_vertices derive them, and q0, q1, q2 its kept vertices:
+ *     1. m_k = q_k - v_k for k = 0, 1, 2
+ *     2. if all nine components of m compare equal to zero, was = P, the raw words (a NaN keeps its payload, -0.0 stays -0.0): an
+ *        unmoved triangle returns the hit position bit for bit, and the temporal queries on a scene where nothing moved give what they
+ *        give without this block
+ *     3. otherwise a0 = dot(cross(e0, P - v1), n), a1 = dot(cross(e1, P - v2), n), a2 = dot(cross(e2, P - v0), n) — the signed areas
+ *        of the cast — and b_k = a_k / area: three divides, the barycentric weights of the hit
+ *     4. was = P + ((m0 * b0 + m1 * b1) + m2 * b2) per component, each product rounded before its add
+ *   NaN and Inf pass through the arithmetic; a moved degenerate triangle (area == 0) gives whatever the divides give.
+ *   SPHERE (kind == 0 and index < n_spheres), with c, r the current centre and radius and cq, rq the kept ones: if cq == c in all three
+ *   components and rq == r, was = P, the raw words; otherwise s = rq / r and was = cq + (P - c) * s.  rt_sphere has no orientation, so
+ *   no rotation is modelled: a sphere that spins in place counts as unmoved.
+ *   ANYTHING ELSE (RT_HIT_NONE, another kind, an index beyond its array): three words 0x7fc00000.  rt_temporal_motion then finds z > 0
+ *   false and the pixel resets.
+ * Checked before any device work, in this order: n >= 2^32 is RT_ERR_UNSUPPORTED; a null scene is RT_ERR_INVALID_ARGUMENT; a scene on
+ * which rt_scene_keep_positions was never called is RT_ERR_INVALID_ARGUMENT (the message names that call); n == 0 is RT_OK and launches
+ * nothing; a null pointer is RT_ERR_INVALID_ARGUMENT; was_stride < 3 is RT_ERR_INVALID_ARGUMENT.  ONE stream-ordered kernel launch on
+ * hip_stream, one hit per lane; allocates nothing, visits the host for nothing and may be captured into a HIP graph at once.  It reads
+ * the scene's arrays: ordering it after an update on another stream is the caller's business, as for a cast.
+ * RT_AMD_DIAG_MOTION_MAX_GROUPS (rt_set_option): a test hook, both kernels launch at most this many workgroups and take the rest
+ * grid-stride — same bits.
+ * Not covered: the previous NORMAL of a rotating surface (the temporal normal test compares the current normal with the previous
+ * frame's, and normal_min absorbs small rotations); motion of lights; rt_multi_* forms; tiles (rt_temporal_motion wants the full frame). */
+int rt_scene_keep_positions(rt_scene *scene, void *hip_stream);
+int rt_scene_positions_kept(const rt_scene *scene); /* 1 / 0 */
+int rt_previous_positions(const rt_scene *scene, const rt_hit *d_hits, size_t n, float *d_was, uint32_t was_stride, void *hip_stream);
+/* The same kernel on HOST arrays: allocates, uploads the hits (and, for a stride above 3, the was plane, so that the words between the
+ * records come back as they were), runs, synchronises the device and downloads.  NOT the CPU definition — that is
+ * rt_previous_positions_cpu of librt_host.so. */
+int rt_previous_positions_host(const rt_scene *scene, const rt_hit *h_hits, size_t n, float *h_was, uint32_t was_stride);
+
 /* ---- several GPUs from one process (SURVEY §8e without Python or MPI) -------------------
  * Image rows are interleaved over the entries of `devices` exactly as homework-18-graphics-raytracer_amd/dist.py interleaves
  * them over ranks (entry r renders rows y0 + r*y_step, y0 + (r+n)*y_step, ...): the scene is replicated, the bands are
@@ -1201,8 +1253,8 @@ int rt_denoise_atrous_host(const float *h_color, const rt_denoise_guides *guides
  *   7. py = half_height - clip_y * height_f
  * the inverse of the primary ray through the image position (px, py).  motion_i = (px, py), 2 f32, in previous-frame pixel
  * coordinates; (NaN, NaN) (0x7fc00000) where valid is not NULL and valid_i == 0, or where z > 0 is false.  For a static scene position
- * is the current frame's position plane; for moving geometry the caller passes its own plane of where each point WAS in the previous
- * frame (deriving that plane from rt_scene_update_vertices is not provided).  A caller may also write the motion plane itself.
+ * is the current frame's position plane; for moving geometry it is the plane of where each point WAS in the previous frame, which
+ * rt_previous_positions derives from the scene updates ("motion queries" above).  A caller may also write the motion plane itself.
  *
  * rt_temporal_accumulate, for output pixel p with current colour C = color[3 p + k], L = lum(C) = (0.2126f * C0 + 0.7152f * C1) +
  * 0.0722f * C2 and (px, py) = motion_p; history records are rt_temporal_pixel, read from history_in and written to history_out:
@@ -1233,7 +1285,7 @@ int rt_denoise_atrous_host(const float *h_color, const rt_denoise_guides *guides
  * position or motion; a stride smaller than its plane's width.
  * The variance-guided A-Trous that reads the variance plane, and the spatial variance estimate for short histories, are the
  * "variance-guided filter queries" below (rt_svgf_atrous, rt_svgf_variance).
- * Not covered: motion of moving geometry derived from scene updates; tiles and banded frames; rt_multi_* forms; clamping history to
+ * Not covered (moving geometry is: "motion queries" above): tiles and banded frames; rt_multi_* forms; clamping history to
  * the neighbourhood's colour box. */
 
 typedef struct rt_temporal_pixel {
@@ -1400,7 +1452,7 @@ int rt_svgf_atrous_host(const float *h_color, uint32_t color_stride, const float
  * RT_AMD_DIST_BY_COST, RT_AMD_DIST_OWN_FIRST, RT_AMD_DIST_PREP_FIRST, RT_AMD_DIST_SPLIT, RT_AMD_DIAG_WS_REFUSE,
  * RT_AMD_MULTI_FORCE_STAGE, RT_AMD_BFS_WALK_TRIANGLES (read by rt_scene_create), RT_AMD_WF_SHARE, RT_AMD_DIAG_BFS_CAP,
  * RT_AMD_DIAG_DIST_BAND_RAYS, RT_AMD_QUERY_WAVE_UNIFORM, RT_AMD_DIAG_HIT_BAND_RECORDS, RT_AMD_FILM_SPLAT_FORM, RT_AMD_DIAG_FILM_MAX_GROUPS,
- * RT_AMD_DENOISE_FORM, RT_AMD_DIAG_DENOISE_MAX_GROUPS, RT_AMD_DIAG_TEMPORAL_MAX_GROUPS, RT_AMD_SVGF_FORM, RT_AMD_DIAG_SVGF_MAX_GROUPS (INTEGRATION.md says what each does); any other name is RT_ERR_INVALID_ARGUMENT.  The environment is read ONCE per process, at the first use;
+ * RT_AMD_DENOISE_FORM, RT_AMD_DIAG_DENOISE_MAX_GROUPS, RT_AMD_DIAG_TEMPORAL_MAX_GROUPS, RT_AMD_SVGF_FORM, RT_AMD_DIAG_SVGF_MAX_GROUPS, RT_AMD_DIAG_MOTION_MAX_GROUPS (INTEGRATION.md says what each does); any other name is RT_ERR_INVALID_ARGUMENT.  The environment is read ONCE per process, at the first use;
  * after that only this call changes a switch: value = decimal integer, NULL or "" = unset (the library's own choice).  Render
  * calls read the switches without locks: set them between calls, not during one. */
 int rt_set_option(const char *name, const char *value);

@@ -120,6 +120,16 @@ int rt_temporal_accumulate_cpu(const float *color, const float *motion, const rt
                                const rt_temporal_params *params, uint32_t rows, uint32_t cols, const rt_temporal_pixel *history_in,
                                rt_temporal_pixel *history_out, float *variance);
 
+/* The motion queries' CPU definition (include/rt_amd.h "motion queries" states every operation and the order): a plain loop over host
+ * arrays, no device needed, bit-identical to rt_previous_positions of librt_amd.so.  `now` is the description of the scene as it stands
+ * (what the hits were cast on); was_triangles holds 9 f32 per triangle — the kept x y z of vertices 0, 1, 2 — and was_spheres 4 per
+ * sphere, cx cy cz r: what rt_scene_keep_positions would have kept, i.e. the description before the update.  n, e0..e2 and area are
+ * derived from now's vertices operation for operation as rt_scene_create and rt_scene_update_vertices derive them.  Same checks in the
+ * same order with the same texts; in the place of "never kept", a null was_triangles with n_triangles > 0 or a null was_spheres with
+ * n_spheres > 0 is RT_ERR_INVALID_ARGUMENT.  A failure returns a negative rt_status and sets rt_host_last_error(). */
+int rt_previous_positions_cpu(const rt_scene_desc *now, const float *was_triangles, const float *was_spheres, const rt_hit *hits, size_t n,
+                              float *was, uint32_t was_stride);
+
 /* The variance-guided filter queries' CPU definition (include/rt_amd.h "variance-guided filter queries" states every operation and the
  * order): plain loops over host arrays, no device needed, bit-identical to rt_svgf_variance / rt_svgf_atrous of librt_amd.so.  Same
  * arguments without the stream (the history needs no alignment here; temp: rt_svgf_temp_bytes bytes, or NULL for one level), same
