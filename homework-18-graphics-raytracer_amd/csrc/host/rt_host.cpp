@@ -592,30 +592,7 @@ int rt_denoise_atrous_cpu(const float *color, const rt_denoise_guides *guides, c
     const char *bad = rt::denoise_limits(color, guides, params, rows, cols, out, temp, true);
     if (bad) return fail(RT_ERR_INVALID_ARGUMENT, std::string("rt_denoise_atrous_cpu: ") + bad);
     if (rows == 0u || cols == 0u) return RT_OK;
-    for (uint32_t j = 0; j < params->n_levels; ++j) {
-        const rt::DenoiseLevel L = rt::denoise_level(color, *guides, *params, rows, cols, out, temp, j);
-        for (uint32_t r = 0; r < rows; ++r)
-            for (uint32_t c = 0; c < cols; ++c) {
-                const uint64_t i = (uint64_t)r * cols + c;
-                const bool filtered = rt::denoise_valid(L, i);
-                rt::DenoiseAcc a = {0.0f, 0.0f, 0.0f, 0.0f};
-                if (filtered) {
-                    const rt::DenoisePix p = rt::denoise_load(L, i);
-                    for (int dr = -2; dr <= 2; ++dr) {
-                        const int64_t qr = (int64_t)r + (int64_t)dr * L.step;
-                        if (qr < 0 || qr >= (int64_t)rows) continue;
-                        for (int dc = -2; dc <= 2; ++dc) {
-                            const int64_t qc = (int64_t)c + (int64_t)dc * L.step;
-                            if (qc < 0 || qc >= (int64_t)cols) continue;
-                            const uint64_t qi = (uint64_t)qr * cols + (uint64_t)qc;
-                            if (!rt::denoise_valid(L, qi)) continue;
-                            rt::denoise_tap(L, a, p, rt::denoise_load(L, qi), dr, dc);
-                        }
-                    }
-                }
-                rt::denoise_store(L, i, filtered, a);
-            }
-    }
+    rt::atrous_cpu<rt::DenoiseFilter>(params->n_levels, rows, cols, [&](uint32_t j) { return rt::denoise_level(color, *guides, *params, rows, cols, out, temp, j); });
     return RT_OK;
 }
 
@@ -665,11 +642,9 @@ int rt_svgf_atrous_cpu(const float *color, uint32_t color_stride, const float *v
     const char *bad = rt::svgf_atrous_limits(color, color_stride, variance, guides, params, rows, cols, out, variance_out, static_cast<float *>(temp), true);
     if (bad) return fail(RT_ERR_INVALID_ARGUMENT, std::string("rt_svgf_atrous_cpu: ") + bad);
     if (rows == 0u || cols == 0u) return RT_OK;
-    for (uint32_t j = 0; j < params->n_levels; ++j) {
-        const rt::SvgfLevel L = rt::svgf_level(color, color_stride, variance, *guides, *params, rows, cols, out, variance_out, static_cast<float *>(temp), j);
-        for (uint32_t r = 0; r < rows; ++r)
-            for (uint32_t c = 0; c < cols; ++c) rt::svgf_pixel(L, r, c);
-    }
+    rt::atrous_cpu<rt::SvgfFilter>(params->n_levels, rows, cols, [&](uint32_t j) {
+        return rt::svgf_level(color, color_stride, variance, *guides, *params, rows, cols, out, variance_out, static_cast<float *>(temp), j);
+    });
     return RT_OK;
 }
 

@@ -119,6 +119,14 @@ void *HostRoundTrip::add(void *h, size_t bytes, bool wanted, bool upload, bool d
     if (upload) e_ = hipMemcpy(d, h, bytes, hipMemcpyHostToDevice);
     return d;
 }
+rt_denoise_guides HostRoundTrip::guides(const rt_denoise_guides &h, size_t n, bool albedo) {
+    rt_denoise_guides g = h;
+    g.normal = plane(h.normal, n, h.normal_stride, 3u);
+    g.position = plane(h.position, n, h.position_stride, 3u);
+    g.albedo = albedo ? plane(h.albedo, n, h.albedo_stride, 3u) : nullptr;
+    g.valid = plane(h.valid, n, h.valid_stride, 1u);
+    return g;
+}
 unsigned long long *HostRoundTrip::counter() {
     if (e_ != hipSuccess) return nullptr;
     e_ = hipMalloc(reinterpret_cast<void **>(&d_count_), sizeof *d_count_);

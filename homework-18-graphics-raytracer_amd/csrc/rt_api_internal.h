@@ -27,6 +27,8 @@
  *   rt_svgf_query.hip    the variance-guided filter queries' rt_svgf_variance / rt_svgf_atrous, their _host forms and rt_svgf_temp_bytes: kernels and entry points in one unit
  * The film queries' kernels are rt_film_query.hip; their entry points are rt_api_query.hip's (rt_camera_rays_offset, beside rt_camera_rays) and
  * rt_api_post.hip's (rt_film_offsets / rt_film_splat, beside the accumulator).
+ * The two A-Trous filters, rt_denoise_query.hip and rt_svgf_query.hip, instantiate the kernel templates of rt_atrous_kernel.h, each with
+ * its filter (rt_denoise.h, rt_svgf.h) on the shared walk, guide readers and argument checks of rt_atrous.h.
  * The kernel units rt_hit_query.hip and rt_scatter_query.hip include this header for the band loop of their launchers.
  *
  * No unit includes another unit's source.  What two kernel units share is a header: the render kernels that are instantiated once for
@@ -224,6 +226,12 @@ static inline uint32_t band_limit(rt::Option hook, uint32_t limit) {
     const long long h = rt::option(hook, 0);
     return h > 0 && h < (long long)limit ? (uint32_t)round_up_64((uint64_t)h) : limit;
 }
+/* Workgroups: a grid-stride kernel is launched with at most `limit` of them, or with what the test hook `hook` asks for, 1 .. limit, so
+ * that a small image or batch is taken grid-stride; a smaller cap changes no bit. */
+static inline uint32_t max_groups(rt::Option hook, uint32_t limit) {
+    const long long cap = rt::option(hook, limit);
+    return cap >= 1 && cap < (long long)limit ? (uint32_t)cap : limit;
+}
 template <class Launch>
 static inline hipError_t for_each_band(uint32_t n, uint32_t band, Launch launch) {
     for (uint64_t off = 0u; off < n; off += band) {
@@ -238,7 +246,8 @@ static inline hipError_t for_each_band(uint32_t n, uint32_t band, Launch launch)
  * host pointer is an optional array the caller left out: nothing is allocated and the device pointer is null.  The first HIP error
  * sticks: every later step is skipped, ok() is false and failed() reports it under the entry point's name.  finish(): one
  * hipDeviceSynchronize, the downloads in declaration order, then the counter (*h_count is written last, and only if all went well).
- * The destructor frees everything, whichever way the call ends. */
+ * A strided plane — n pixels, `stride` words apart, `width` words each — travels as the span from its first word to its last: (n - 1)
+ * strides and one width.  The destructor frees everything, whichever way the call ends. */
 class RT_API_HIDDEN HostRoundTrip {
 public:
     explicit HostRoundTrip(const char *who) : who_(who) {}
@@ -246,6 +255,8 @@ public:
     HostRoundTrip(const HostRoundTrip &) = delete;
     HostRoundTrip &operator=(const HostRoundTrip &) = delete;
     template <class T> T *in(const T *h, size_t bytes) { return static_cast<T *>(add(const_cast<T *>(h), bytes, h != nullptr, true, false)); }
+    template <class T> T *plane(const T *h, size_t n, uint32_t stride, uint32_t width) { return in(h, ((n - 1u) * stride + width) * sizeof(uint32_t)); }
+    rt_denoise_guides guides(const rt_denoise_guides &h, size_t n, bool albedo = true); /* the four planes of n pixels; albedo only where the call reads it */
     template <class T> T *out(T *h, size_t bytes) { return static_cast<T *>(add(h, bytes, h != nullptr, false, true)); }
     template <class T> T *inout(T *h, size_t bytes) { return static_cast<T *>(add(h, bytes, h != nullptr, true, true)); } /* continues from the caller's values */
     void *scratch(size_t bytes) { return add(nullptr, bytes, true, false, false); }

@@ -138,9 +138,7 @@ int rt_film_splat(uint32_t rows, uint32_t cols, const float *d_samples, const un
     if (rc != RT_OK) return rc;
     const rt::FilmSplat p = {d_samples, d_valid, d_offsets, d_sum, d_weight, rows, cols, spp, filter, radius};
     const bool tiled = rt::option(rt::OPT_FILM_SPLAT_FORM, RT_FILM_SPLAT_FORM_DEFAULT) == 1;
-    const long long cap = rt::option(rt::OPT_DIAG_FILM_MAX_GROUPS, RT_FILM_MAX_GROUPS); /* test hook: fewer workgroups, so a small image is taken grid-stride */
-    const uint32_t max_groups = cap >= 1 && cap < (long long)RT_FILM_MAX_GROUPS ? (uint32_t)cap : RT_FILM_MAX_GROUPS;
-    return launched("rt_film_splat", rt::launch_film_splat(p, tiled, max_groups, static_cast<hipStream_t>(hip_stream)));
+    return launched("rt_film_splat", rt::launch_film_splat(p, tiled, max_groups(rt::OPT_DIAG_FILM_MAX_GROUPS, RT_FILM_MAX_GROUPS), static_cast<hipStream_t>(hip_stream)));
 }
 
 int rt_encode_srgb8_device(const float *d_rgb, size_t n_values, unsigned char *d_out, void *hip_stream) {

@@ -45,9 +45,7 @@ __global__ __launch_bounds__(RT_MOTION_THREADS) void previous_positions_kernel(c
 }
 
 static dim3 motion_grid(uint64_t n) {
-    const long long cap = option(OPT_DIAG_MOTION_MAX_GROUPS, RT_MOTION_MAX_GROUPS); /* test hook: fewer workgroups, so a small batch is taken grid-stride */
-    const uint64_t max_groups = cap >= 1 && cap < (long long)RT_MOTION_MAX_GROUPS ? (uint64_t)cap : RT_MOTION_MAX_GROUPS;
-    return dim3((uint32_t)std::min<uint64_t>((n + RT_MOTION_THREADS - 1u) / RT_MOTION_THREADS, max_groups));
+    return dim3((uint32_t)std::min<uint64_t>((n + RT_MOTION_THREADS - 1u) / RT_MOTION_THREADS, max_groups(OPT_DIAG_MOTION_MAX_GROUPS, RT_MOTION_MAX_GROUPS)));
 }
 
 } /* namespace rt */

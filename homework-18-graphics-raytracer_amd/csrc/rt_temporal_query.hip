@@ -31,9 +31,7 @@ __global__ __launch_bounds__(RT_TEMPORAL_THREADS) void temporal_accumulate_kerne
 }
 
 static dim3 temporal_grid(uint64_t n) {
-    const long long cap = option(OPT_DIAG_TEMPORAL_MAX_GROUPS, RT_TEMPORAL_MAX_GROUPS); /* test hook: fewer workgroups, so a small image is taken grid-stride */
-    const uint64_t max_groups = cap >= 1 && cap < (long long)RT_TEMPORAL_MAX_GROUPS ? (uint64_t)cap : RT_TEMPORAL_MAX_GROUPS;
-    return dim3((uint32_t)std::min<uint64_t>((n + RT_TEMPORAL_THREADS - 1u) / RT_TEMPORAL_THREADS, max_groups));
+    return dim3((uint32_t)std::min<uint64_t>((n + RT_TEMPORAL_THREADS - 1u) / RT_TEMPORAL_THREADS, max_groups(OPT_DIAG_TEMPORAL_MAX_GROUPS, RT_TEMPORAL_MAX_GROUPS)));
 }
 
 static hipError_t launch_motion(const float *position, uint32_t position_stride, const uint32_t *valid, uint32_t valid_stride, const rt_camera *camera,
@@ -84,11 +82,9 @@ int rt_temporal_motion_host(const float *h_position, uint32_t position_stride, c
     if (bad) return fail(status, std::string("rt_temporal_motion_host: ") + bad);
     if (prev_frame->width == 0u || prev_frame->height == 0u) return RT_OK;
     const size_t n = (size_t)prev_frame->width * prev_frame->height;
-    /* a strided plane travels as the span from its first word to its last: (n - 1) strides and one width */
-    const auto span = [n](uint32_t stride, uint32_t width) { return ((n - 1u) * stride + width) * sizeof(uint32_t); };
     HostRoundTrip t("rt_temporal_motion_host");
-    const float *d_position = t.in(h_position, span(position_stride, 3u));
-    const uint32_t *d_valid = t.in(h_valid, span(valid_stride, 1u));
+    const float *d_position = t.plane(h_position, n, position_stride, 3u);
+    const uint32_t *d_valid = t.plane(h_valid, n, valid_stride, 1u);
     float *d_motion = t.out(h_motion, n * 2u * sizeof(float));
     if (!t.ok()) return t.failed();
     const hipError_t e = rt::launch_motion(d_position, position_stride, d_valid, valid_stride, prev_camera, prev_frame, d_motion, nullptr);
@@ -105,14 +101,13 @@ int rt_temporal_accumulate_host(const float *h_color, const float *h_motion, con
     if (bad) return fail(status, std::string("rt_temporal_accumulate_host: ") + bad);
     if (rows == 0u || cols == 0u) return RT_OK;
     const size_t n = (size_t)rows * cols;
-    const auto span = [n](uint32_t stride, uint32_t width) { return ((n - 1u) * stride + width) * sizeof(uint32_t); };
     HostRoundTrip t("rt_temporal_accumulate_host");
     const auto upload = [&](const rt_temporal_guides &h) {
         rt_temporal_guides g = h;
-        g.normal = t.in(h.normal, span(h.normal_stride, 3u));
-        g.position = t.in(h.position, span(h.position_stride, 3u));
-        g.object = t.in(h.object, span(h.object_stride, 1u));
-        g.valid = t.in(h.valid, span(h.valid_stride, 1u));
+        g.normal = t.plane(h.normal, n, h.normal_stride, 3u);
+        g.position = t.plane(h.position, n, h.position_stride, 3u);
+        g.object = t.plane(h.object, n, h.object_stride, 1u);
+        g.valid = t.plane(h.valid, n, h.valid_stride, 1u);
         return g;
     };
     const float *d_color = t.in(h_color, n * 3u * sizeof(float));

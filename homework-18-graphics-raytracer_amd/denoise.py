@@ -57,6 +57,16 @@ def _np_plane(a, name, kinds, n, width):
                      "and one pixel stride of whole words")
 
 
+def _np_guides(n, normal, position, albedo, valid):
+    """DenoiseGuides of numpy planes (``svgf`` builds its guides here too)"""
+    g = _capi.DenoiseGuides()
+    g.normal, g.normal_stride = _np_plane(normal, "normal", "f", n, 3)
+    g.position, g.position_stride = _np_plane(position, "position", "f", n, 3)
+    g.albedo, g.albedo_stride = _np_plane(albedo, "albedo", "f", n, 3)
+    g.valid, g.valid_stride = _np_plane(valid, "valid", "iu", n, 1)
+    return g
+
+
 def atrous_numpy(color, rows: int, cols: int, normal=None, position=None, albedo=None, valid=None, levels: int = 5, first_level: int = 0,
                  sigma_color: float = SIGMA_COLOR, sigma_normal: float = SIGMA_NORMAL, sigma_position: float = SIGMA_POSITION, demodulate=False):
     """The CPU definition (rt_denoise_atrous_cpu, librt_host.so; no device, no torch): ``color`` rows * cols pixels of 3 float32;
@@ -71,11 +81,7 @@ def atrous_numpy(color, rows: int, cols: int, normal=None, position=None, albedo
     if c.dtype != np.float32 or c.size != n * 3 or (c.ndim and c.shape[-1] != 3):
         raise ValueError(f"color: expected {n} pixels of 3 float32")
     c = np.ascontiguousarray(c)
-    g = _capi.DenoiseGuides()
-    g.normal, g.normal_stride = _np_plane(normal, "normal", "f", n, 3)
-    g.position, g.position_stride = _np_plane(position, "position", "f", n, 3)
-    g.albedo, g.albedo_stride = _np_plane(albedo, "albedo", "f", n, 3)
-    g.valid, g.valid_stride = _np_plane(valid, "valid", "iu", n, 1)
+    g = _np_guides(n, normal, position, albedo, valid)
     out = np.zeros((rows, cols, 3), dtype=np.float32)
     temp = np.zeros((rows, cols, 3), dtype=np.float32) if int(levels) >= 2 else None
     p = _params(levels, first_level, sigma_color, sigma_normal, sigma_position, demodulate)
@@ -96,6 +102,16 @@ def _plane(t, name, dtype, n, width):
     raise ValueError(f"{name} must be a {dtype} CUDA tensor of {n} pixels x {width}, the last dimension contiguous and one pixel stride")
 
 
+def _guides(n, normal, position, albedo, valid):
+    """DenoiseGuides of CUDA planes"""
+    g = _capi.DenoiseGuides()
+    g.normal, g.normal_stride = _plane(normal, "normal", "float32", n, 3)
+    g.position, g.position_stride = _plane(position, "position", "float32", n, 3)
+    g.albedo, g.albedo_stride = _plane(albedo, "albedo", "float32", n, 3)
+    g.valid, g.valid_stride = _plane(valid, "valid", "int32", n, 1)
+    return g
+
+
 def atrous(color, rows: int, cols: int, normal=None, position=None, albedo=None, valid=None, levels: int = 5, first_level: int = 0,
            sigma_color: float = SIGMA_COLOR, sigma_normal: float = SIGMA_NORMAL, sigma_position: float = SIGMA_POSITION, demodulate=False,
            out=None, temp=None, stream=None):
@@ -107,11 +123,7 @@ def atrous(color, rows: int, cols: int, normal=None, position=None, albedo=None,
     rows, cols = int(rows), int(cols)
     n = rows * cols
     _tensor(color, "color", "float32", (rows, cols, 3))
-    g = _capi.DenoiseGuides()
-    g.normal, g.normal_stride = _plane(normal, "normal", "float32", n, 3)
-    g.position, g.position_stride = _plane(position, "position", "float32", n, 3)
-    g.albedo, g.albedo_stride = _plane(albedo, "albedo", "float32", n, 3)
-    g.valid, g.valid_stride = _plane(valid, "valid", "int32", n, 1)
+    g = _guides(n, normal, position, albedo, valid)
     with _on_stream(stream):
         out = _out_tensor(out, (rows, cols, 3), "float32", color.device)
         if temp is not None or int(levels) >= 2:

@@ -30,7 +30,7 @@ from . import _capi
 from ._args import _on_stream, _out_tensor, _p, _stream_ptr, _tensor
 from ._capi import Camera, Frame
 from ._world import Scene
-from .denoise import SIGMA_NORMAL, SIGMA_POSITION, _np_plane, _plane
+from .denoise import SIGMA_NORMAL, SIGMA_POSITION, _guides, _np_guides, _np_plane, _plane
 from .temporal import _RECORD_WORDS, HISTORY_DTYPE, History, accumulate_frame
 
 __all__ = ["variance", "variance_numpy", "atrous", "atrous_numpy", "temp_bytes", "filter_frame"]
@@ -56,24 +56,6 @@ def _variance_params(sigma_normal, sigma_position, min_length):
 def _atrous_params(levels, first_level, sigma_luminance, sigma_normal, sigma_position, demodulate):
     return _capi.SvgfAtrousParams(float(sigma_luminance), float(sigma_normal), float(sigma_position), int(first_level), int(levels),
                                   _DEMODULATE if demodulate is True else int(demodulate))
-
-
-def _np_guides(n, normal, position, albedo, valid):
-    g = _capi.DenoiseGuides()
-    g.normal, g.normal_stride = _np_plane(normal, "normal", "f", n, 3)
-    g.position, g.position_stride = _np_plane(position, "position", "f", n, 3)
-    g.albedo, g.albedo_stride = _np_plane(albedo, "albedo", "f", n, 3)
-    g.valid, g.valid_stride = _np_plane(valid, "valid", "iu", n, 1)
-    return g
-
-
-def _guides(n, normal, position, albedo, valid):
-    g = _capi.DenoiseGuides()
-    g.normal, g.normal_stride = _plane(normal, "normal", "float32", n, 3)
-    g.position, g.position_stride = _plane(position, "position", "float32", n, 3)
-    g.albedo, g.albedo_stride = _plane(albedo, "albedo", "float32", n, 3)
-    g.valid, g.valid_stride = _plane(valid, "valid", "int32", n, 1)
-    return g
 
 
 def variance_numpy(history, rows: int, cols: int, normal=None, position=None, valid=None, min_length: int = MIN_LENGTH,

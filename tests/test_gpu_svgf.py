@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 import homework_18_graphics_raytracer_amd as rt
-from homework_18_graphics_raytracer_amd import _capi, svgf, temporal
+from homework_18_graphics_raytracer_amd import _capi, denoise, svgf, temporal
 from _denoise_support import ALBEDO_AT, NORMAL_AT, POSITION_AT, VALID_AT, dist2, embed, record_views
 from _records import torch_device
 from _svgf_support import F32, FINITE_SIGMAS, HISTORY, IMAGES, LEVELS, MIN_LENGTH, bits, case_data
@@ -104,6 +104,25 @@ def test_atrous_equals_the_cpu_definition(rows, cols, form):
         for first, levels, config in calls:
             assert same(device_atrous(rows, cols, first, levels, **config), cpu_atrous(rows, cols, first, levels, **config)), (first, levels, config)
     assert np.isnan(cpu_atrous(rows, cols, 0, 6, **CONFIGS[0])[0].view(F32)).any()  # the NaN colours passed through, payload and all
+
+
+@pytest.mark.parametrize("form", FORMS)
+@pytest.mark.parametrize("rows,cols", [(23, 37), (40, 50)])
+def test_an_infinite_luminance_sigma_gives_the_bits_of_the_denoise_filter(rows, cols, form):
+    """the two instantiations of the shared A-Trous kernels check each other, as the CPU forms do in the test of this name"""
+    torch = torch_device()
+    color = dev(case_data(rows, cols)[0]).view(rows, cols, 3)  # finite or NaN colours
+    variance = dev(case_data(rows, cols)[1]).view(rows, cols)
+    for config in CONFIGS:
+        g = device_guides(rows, cols, config["strided"], config["flags"])
+        kw = dict(levels=6, demodulate=config["demodulate"], **GUIDE_SIGMAS)
+        torch.cuda.synchronize()
+        with rt.options(RT_AMD_SVGF_FORM=form, RT_AMD_DENOISE_FORM=form):
+            got, _ = svgf.atrous(color, variance, rows, cols, sigma_luminance=float("inf"), **g, **kw)
+            want = denoise.atrous(color, rows, cols, sigma_color=float("inf"), **g, **kw)
+        torch.cuda.synchronize()
+        got, want = bits(got.cpu().numpy()), bits(want.cpu().numpy())
+        assert np.array_equal(got, want) and np.isnan(got.view(F32)).any(), config
 
 
 def test_atrous_without_a_variance_output_keeps_the_colour():
