@@ -194,6 +194,16 @@ class TemporalParams(C.Structure):
     _fields_ = [("normal_min", C.c_float), ("position_max", C.c_float), ("alpha_min", C.c_float), ("max_length", C.c_uint32), ("flags", C.c_uint32)]
 
 
+class TemporalBox(C.Structure):
+    """rt_temporal_box: the colour box of one pixel, channels 0..2 colour and 3 luminance"""
+    _fields_ = [("lo", C.c_float * 4), ("hi", C.c_float * 4)]
+
+
+class BoundsParams(C.Structure):
+    """rt_bounds_params"""
+    _fields_ = [("gamma", C.c_float), ("radius", C.c_uint32), ("flags", C.c_uint32)]
+
+
 class SvgfVarianceParams(C.Structure):
     """rt_svgf_variance_params"""
     _fields_ = [("sigma_normal", C.c_float), ("sigma_position", C.c_float), ("min_length", C.c_uint32), ("flags", C.c_uint32)]
@@ -221,6 +231,8 @@ AMD_SYMBOLS = [
     "rt_film_offsets", "rt_camera_rays_offset", "rt_camera_rays_offset_host", "rt_film_splat",
     "rt_denoise_temp_bytes", "rt_denoise_atrous", "rt_denoise_atrous_host",
     "rt_temporal_motion", "rt_temporal_accumulate", "rt_temporal_motion_host", "rt_temporal_accumulate_host",
+    "rt_temporal_bounds", "rt_temporal_accumulate_bounded", "rt_temporal_feedback",
+    "rt_temporal_bounds_host", "rt_temporal_accumulate_bounded_host", "rt_temporal_feedback_host",
     "rt_svgf_variance", "rt_svgf_temp_bytes", "rt_svgf_atrous", "rt_svgf_variance_host", "rt_svgf_atrous_host",
     "rt_refract_enter", "rt_refract_step",
     "rt_scene_update_vertices", "rt_scene_update_spheres", "rt_scene_update_lights", "rt_scene_update_materials",
@@ -237,6 +249,7 @@ HOST_SYMBOLS = [
     "rt_film_offsets_host", "rt_film_splat_host", "rt_denoise_atrous_cpu",
     "rt_temporal_motion_cpu", "rt_temporal_accumulate_cpu", "rt_svgf_variance_cpu", "rt_svgf_atrous_cpu",
     "rt_previous_positions_cpu",
+    "rt_temporal_bounds_cpu", "rt_temporal_accumulate_bounded_cpu", "rt_temporal_feedback_cpu",
 ]
 
 _amd = None
@@ -288,6 +301,11 @@ def host_lib() -> C.CDLL:
         lib.rt_temporal_motion_cpu.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(Camera), C.POINTER(Frame), C.c_void_p]
         lib.rt_temporal_accumulate_cpu.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(TemporalGuides), C.POINTER(TemporalGuides), C.POINTER(TemporalParams),
                                                    C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.rt_temporal_bounds_cpu.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(BoundsParams), C.c_uint32, C.c_uint32,
+                                               C.c_void_p]
+        lib.rt_temporal_accumulate_bounded_cpu.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(TemporalGuides), C.POINTER(TemporalGuides), C.POINTER(TemporalParams),
+                                                           C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        lib.rt_temporal_feedback_cpu.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
         lib.rt_svgf_variance_cpu.argtypes = [C.c_void_p, C.POINTER(DenoiseGuides), C.POINTER(SvgfVarianceParams), C.c_uint32, C.c_uint32, C.c_void_p]
         lib.rt_svgf_atrous_cpu.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(DenoiseGuides), C.POINTER(SvgfAtrousParams), C.c_uint32, C.c_uint32,
                                            C.c_void_p, C.c_void_p, C.c_void_p]
@@ -416,6 +434,17 @@ def amd_lib() -> C.CDLL:
                                                C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.rt_temporal_accumulate_host.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(TemporalGuides), C.POINTER(TemporalGuides), C.POINTER(TemporalParams),
                                                     C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.rt_temporal_bounds.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(BoundsParams), C.c_uint32, C.c_uint32,
+                                           C.c_void_p, C.c_void_p]
+        lib.rt_temporal_bounds_host.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(BoundsParams), C.c_uint32,
+                                                C.c_uint32, C.c_void_p]
+        lib.rt_temporal_accumulate_bounded.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(TemporalGuides), C.POINTER(TemporalGuides), C.POINTER(TemporalParams),
+                                                       C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+        lib.rt_temporal_accumulate_bounded_host.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(TemporalGuides), C.POINTER(TemporalGuides),
+                                                            C.POINTER(TemporalParams), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                            C.c_uint32, C.c_void_p]
+        lib.rt_temporal_feedback.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+        lib.rt_temporal_feedback_host.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
         lib.rt_svgf_variance.argtypes = [C.c_void_p, C.POINTER(DenoiseGuides), C.POINTER(SvgfVarianceParams), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
         lib.rt_svgf_variance_host.argtypes = [C.c_void_p, C.POINTER(DenoiseGuides), C.POINTER(SvgfVarianceParams), C.c_uint32, C.c_uint32, C.c_void_p]
         lib.rt_svgf_temp_bytes.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]

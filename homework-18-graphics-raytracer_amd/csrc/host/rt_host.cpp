@@ -22,6 +22,7 @@
 #include "../rt_denoise.h"
 #include "../rt_temporal.h"
 #include "../rt_svgf.h"
+#include "../rt_rectify.h"
 #include "../rt_motion.h"
 
 using rt::V3;
@@ -621,6 +622,46 @@ int rt_temporal_accumulate_cpu(const float *color, const float *motion, const rt
     const rt::TemporalCall t = rt::temporal_call(color, motion, *current, *previous, *params, rows, cols, history_in, history_out, variance);
     const uint64_t n = (uint64_t)rows * cols;
     for (uint64_t i = 0; i < n; ++i) rt::temporal_pixel(t, i);
+    return RT_OK;
+}
+
+/* ---- history rectification queries: the CPU definition (include/rt_amd.h "history rectification queries"; the arithmetic is rt_rectify.h's, shared with the device) ---- */
+
+int rt_temporal_bounds_cpu(const float *color, uint32_t color_stride, const uint32_t *object, uint32_t object_stride, const uint32_t *valid,
+                           uint32_t valid_stride, const rt_bounds_params *params, uint32_t rows, uint32_t cols, rt_temporal_box *box) {
+    int status;
+    const char *bad = rt::rectify_bounds_limits(color, color_stride, object, object_stride, valid, valid_stride, params, rows, cols, box, false, &status);
+    if (bad) return fail(status, std::string("rt_temporal_bounds_cpu: ") + bad);
+    if (rows == 0u || cols == 0u) return RT_OK;
+    const rt::RectifyBounds b = rt::rectify_bounds_call(color, color_stride, object, object_stride, valid, valid_stride, *params, rows, cols, box);
+    for (uint32_t r = 0; r < rows; ++r)
+        for (uint32_t c = 0; c < cols; ++c) rt::rectify_bounds_pixel(b, r, c);
+    return RT_OK;
+}
+
+int rt_temporal_accumulate_bounded_cpu(const float *color, const float *motion, const rt_temporal_guides *current, const rt_temporal_guides *previous,
+                                       const rt_temporal_params *params, uint32_t rows, uint32_t cols, const rt_temporal_pixel *history_in,
+                                       rt_temporal_pixel *history_out, float *variance, const rt_temporal_box *box, uint32_t clamped_length,
+                                       uint32_t *clamped) {
+    int status;
+    const char *bad = rt::rectify_accumulate_limits(color, motion, current, previous, params, rows, cols, history_in, history_out, box, clamped_length, false, &status);
+    if (bad) return fail(status, std::string("rt_temporal_accumulate_bounded_cpu: ") + bad);
+    if (rows == 0u || cols == 0u) return RT_OK;
+    const rt::RectifyAccumulate a = {rt::temporal_call(color, motion, *current, *previous, *params, rows, cols, history_in, history_out, variance), box,
+                                     clamped_length, clamped};
+    const uint64_t n = (uint64_t)rows * cols;
+    for (uint64_t i = 0; i < n; ++i) rt::rectify_pixel(a, i);
+    return RT_OK;
+}
+
+int rt_temporal_feedback_cpu(const float *color, uint32_t color_stride, const uint32_t *valid, uint32_t valid_stride, uint32_t rows, uint32_t cols,
+                             rt_temporal_pixel *history) {
+    int status;
+    const char *bad = rt::rectify_feedback_limits(color, color_stride, valid, valid_stride, rows, cols, history, false, &status);
+    if (bad) return fail(status, std::string("rt_temporal_feedback_cpu: ") + bad);
+    if (rows == 0u || cols == 0u) return RT_OK;
+    const rt::RectifyFeedback f = {color, valid, color_stride, valid_stride, (uint64_t)rows * cols, history};
+    for (uint64_t i = 0; i < f.n; ++i) rt::rectify_feedback_pixel(f, i);
     return RT_OK;
 }
 

@@ -4,6 +4,8 @@
  * f32 operations in the order the header comment of the block gives; both libraries are built with -ffp-contract=off, the divides are
  * correctly rounded on either side, nothing comes from libm and nothing from a device intrinsic (the floor is two conversions and a
  * compare), so host and device agree bit for bit.  The loops (CPU, kernel) differ only in how they walk the pixels.
+ * temporal_pixel is temporal_gather, then temporal_blend or temporal_reset: rt_rectify.h puts its clamp between the first two, so the
+ * gather of rt_temporal_accumulate_bounded is this header's and is stated once.
  *
  * camera_basis is Camera::shoot's ray-independent part (main.rs:85-92), moved here from make_kernel_frame (rt_api.hip), which calls it:
  * the CPU form needs the same basis without HIP.  Its operation order is the contract of every primary ray and is not to change.
@@ -241,9 +243,14 @@ RT_TP_HD void temporal_write(const TemporalCall &t, uint64_t i, uint32_t w0, uin
     if (t.variance) t.variance[i] = variance;
 }
 
-/* steps 1 to 5 for output pixel i */
-RT_TP_HD void temporal_pixel(const TemporalCall &t, uint64_t i) {
-    const TemporalPix p = temporal_load(t, i);
+/* what steps 1 to 3 leave of the previous frame: H = sum / bsum (five divides) and n = min(minimum length + 1, max_length) */
+struct TemporalHist {
+    float c0, c1, c2, m1, m2;
+    uint32_t n;
+};
+
+/* THE gather, steps 1 to 3 and step 4's H and n, for output pixel i whose current values are p; false: the pixel resets */
+RT_TP_HD bool temporal_gather(const TemporalCall &t, uint64_t i, const TemporalPix &p, TemporalHist &h) {
     const float px = t.motion[2u * i], py = t.motion[2u * i + 1u];
     TemporalAcc a = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0xffffffffu};
     const bool valid = t.cur.valid == nullptr || t.cur.valid[i * t.cur.valid_stride] != 0u;
@@ -262,23 +269,41 @@ RT_TP_HD void temporal_pixel(const TemporalCall &t, uint64_t i) {
         for (int k = 0; k < 4; ++k)
             if (read[k]) temporal_tap(t, a, p, q[k]);
     }
-    if (a.bsum > 0.0f) {
-        const uint32_t n = a.min_length >= t.max_length ? t.max_length : a.min_length + 1u; /* min(min length + 1, max_length), no wrap */
-        const float inv = 1.0f / (float)n;
-        const float alpha = inv > t.alpha_min ? inv : t.alpha_min;
-        const float keep = 1.0f - alpha;
-        const float lum2 = p.lum * p.lum;
-        const float o0 = (a.s0 / a.bsum) * keep + p.c0 * alpha;
-        const float o1 = (a.s1 / a.bsum) * keep + p.c1 * alpha;
-        const float o2 = (a.s2 / a.bsum) * keep + p.c2 * alpha;
-        const float m1 = (a.m1 / a.bsum) * keep + p.lum * alpha;
-        const float m2 = (a.m2 / a.bsum) * keep + lum2 * alpha;
-        const float v = m2 - m1 * m1;
-        temporal_write(t, i, temporal_bits(o0), temporal_bits(o1), temporal_bits(o2), m1, m2, n, v > 0.0f ? v : 0.0f);
-    } else { /* a reset: the colour's raw words, so a NaN keeps its payload */
-        const uint32_t *c = reinterpret_cast<const uint32_t *>(t.color) + 3u * i;
-        temporal_write(t, i, c[0], c[1], c[2], p.lum, p.lum * p.lum, 1u, 0.0f);
-    }
+    if (!(a.bsum > 0.0f)) return false;
+    h.n = a.min_length >= t.max_length ? t.max_length : a.min_length + 1u; /* min(min length + 1, max_length), no wrap */
+    h.c0 = a.s0 / a.bsum, h.c1 = a.s1 / a.bsum, h.c2 = a.s2 / a.bsum, h.m1 = a.m1 / a.bsum, h.m2 = a.m2 / a.bsum;
+    return true;
+}
+
+/* the rest of step 4 and step 5: the history h of length h.n blended with the current pixel and written */
+RT_TP_HD void temporal_blend(const TemporalCall &t, uint64_t i, const TemporalPix &p, const TemporalHist &h) {
+    const float inv = 1.0f / (float)h.n;
+    const float alpha = inv > t.alpha_min ? inv : t.alpha_min;
+    const float keep = 1.0f - alpha;
+    const float lum2 = p.lum * p.lum;
+    const float o0 = h.c0 * keep + p.c0 * alpha;
+    const float o1 = h.c1 * keep + p.c1 * alpha;
+    const float o2 = h.c2 * keep + p.c2 * alpha;
+    const float m1 = h.m1 * keep + p.lum * alpha;
+    const float m2 = h.m2 * keep + lum2 * alpha;
+    const float v = m2 - m1 * m1;
+    temporal_write(t, i, temporal_bits(o0), temporal_bits(o1), temporal_bits(o2), m1, m2, h.n, v > 0.0f ? v : 0.0f);
+}
+
+/* a reset: the colour's raw words, so a NaN keeps its payload */
+RT_TP_HD void temporal_reset(const TemporalCall &t, uint64_t i, const TemporalPix &p) {
+    const uint32_t *c = reinterpret_cast<const uint32_t *>(t.color) + 3u * i;
+    temporal_write(t, i, c[0], c[1], c[2], p.lum, p.lum * p.lum, 1u, 0.0f);
+}
+
+/* steps 1 to 5 for output pixel i */
+RT_TP_HD void temporal_pixel(const TemporalCall &t, uint64_t i) {
+    const TemporalPix p = temporal_load(t, i);
+    TemporalHist h;
+    if (temporal_gather(t, i, p, h))
+        temporal_blend(t, i, p, h);
+    else
+        temporal_reset(t, i, p);
 }
 
 /* ---- THE argument checks, in the order include/rt_amd.h states; null: all in range, *status says how a refusal is reported ---- */

@@ -198,12 +198,14 @@ class History:
         r = self.records.view(self.rows, self.cols, _RECORD_WORDS)
         return r[..., 0:3].view(torch.float32), self.variance, r[..., 5]
 
-    def push(self, surfaces, camera: Camera, frame: Frame, image, stream=None, position_was=None):
+    def push(self, surfaces, camera: Camera, frame: Frame, image, stream=None, position_was=None, box=None, clamped_length=0, clamped=None):
         """Accumulate ``image``, a (rows, cols, 3) float32 CUDA tensor rendered from ``camera`` over the full frame ``frame`` whose
         ``surfaces`` are its ``materials.primary_surfaces``: motion through the previous push's camera, then accumulate against the
         previous push's surfaces and records — two kernel launches on ``stream``.  The first push finds no history: every pixel resets.
         ``position_was``: for a scene that moved since the previous push, the plane of where each pixel's point was then
         (``moving.previous_positions`` of ``surfaces.hits``), projected and compared instead of ``surfaces.position``.
+        ``box``: a (rows * cols, 8) float32 CUDA tensor of colour boxes (``rectify.bounds`` of ``image``): the accumulate is then
+        ``rectify.accumulate_bounded`` with ``clamped_length`` and ``clamped``, which clamps the history into them.
         Returns (color, variance, length): views of the new records and the variance plane, valid until the push after the next."""
         if _full(frame) != (self.rows, self.cols):
             raise ValueError(f"frame must be {self.cols} x {self.rows}")
@@ -212,8 +214,15 @@ class History:
         if position_was is not None:
             cur = cur._replace(position=position_was)
         motion(cur.position, prev_camera, prev_frame, valid=cur.valid, out=self.motion, stream=stream)
-        accumulate(image, self.motion, self.rows, self.cols, self._records[self.frames % 2], current=cur, previous=Guides.of(prev_surfaces),
-                   out=self._records[(self.frames + 1) % 2], variance=self.variance, stream=stream, **self.params)
+        args = (image, self.motion, self.rows, self.cols, self._records[self.frames % 2])
+        keywords = dict(current=cur, previous=Guides.of(prev_surfaces), out=self._records[(self.frames + 1) % 2], variance=self.variance, stream=stream,
+                        **self.params)
+        if box is None:
+            accumulate(*args, **keywords)
+        else:
+            from .rectify import accumulate_bounded  # rectify imports this module
+
+            accumulate_bounded(*args, box, clamped_length=clamped_length, clamped=clamped, **keywords)
         self.frames += 1
         self._previous = (surfaces, Camera.from_buffer_copy(camera), Frame.from_buffer_copy(frame))
         return self.views()

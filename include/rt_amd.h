@@ -981,7 +981,9 @@ int rt_scene_update_materials(rt_scene *scene, uint32_t first, uint32_t count, c
  * RT_AMD_DIAG_MOTION_MAX_GROUPS (rt_set_option): a test hook, both kernels launch at most this many workgroups and take the rest
  * grid-stride — same bits.
  * Not covered: the previous NORMAL of a rotating surface (the temporal normal test compares the current normal with the previous
- * frame's, and normal_min absorbs small rotations); motion of lights; rt_multi_* forms; tiles (rt_temporal_motion wants the full frame). */
+ * frame's, and normal_min absorbs small rotations); motion of lights; rt_multi_* forms; tiles (rt_temporal_motion wants the full frame).
+ * (A light that moved leaves no geometry to follow: what a history needs then is the colour-box clamp of the "history rectification
+ * queries" below.) */
 int rt_scene_keep_positions(rt_scene *scene, void *hip_stream);
 int rt_scene_positions_kept(const rt_scene *scene); /* 1 / 0 */
 int rt_previous_positions(const rt_scene *scene, const rt_hit *d_hits, size_t n, float *d_was, uint32_t was_stride, void *hip_stream);
@@ -1285,8 +1287,8 @@ int rt_denoise_atrous_host(const float *h_color, const rt_denoise_guides *guides
  * position or motion; a stride smaller than its plane's width.
  * The variance-guided A-Trous that reads the variance plane, and the spatial variance estimate for short histories, are the
  * "variance-guided filter queries" below (rt_svgf_atrous, rt_svgf_variance).
- * Not covered (moving geometry is: "motion queries" above): tiles and banded frames; rt_multi_* forms; clamping history to
- * the neighbourhood's colour box. */
+ * Clamping the history to the neighbourhood's colour box is rt_temporal_accumulate_bounded of the "history rectification queries" below.
+ * Not covered (moving geometry is: "motion queries" above): tiles and banded frames; rt_multi_* forms. */
 
 typedef struct rt_temporal_pixel {
     float color[3];           /* the accumulated colour */
@@ -1331,6 +1333,99 @@ int rt_temporal_motion_host(const float *h_position, uint32_t position_stride, c
 int rt_temporal_accumulate_host(const float *h_color, const float *h_motion, const rt_temporal_guides *current, const rt_temporal_guides *previous,
                                 const rt_temporal_params *params, uint32_t rows, uint32_t cols, const rt_temporal_pixel *h_history_in,
                                 rt_temporal_pixel *h_history_out, float *h_variance);
+
+/* ---- history rectification queries: colour-box clamp and filtered feedback --------------------------
+
+ * What keeps a history honest when shading changes and geometry does not — a light or a material was updated, a highlight slides over a
+ * surface: rt_temporal_accumulate keeps a tap on geometry alone, so the stale colour fades at 1 / length only.  The defence is variance
+ * clipping: the box mean +- gamma * deviation of the CURRENT frame's neighbourhood (rt_temporal_bounds), and the reprojected history
+ * pulled into it before the blend (rt_temporal_accumulate_bounded).  rt_temporal_feedback writes a filtered colour back into the records,
+ * which makes the filter below spatiotemporal — Schied et al.'s feedback of level 0:
+ *     rt_temporal_motion -> rt_temporal_bounds -> rt_temporal_accumulate_bounded -> rt_svgf_variance -> rt_svgf_atrous (level 0)
+ *         -> rt_temporal_feedback -> rt_svgf_atrous (levels 1 ..) -> rt_post_process_device
+ * The reference has no counterpart; the definition below is the contract.  It is written once (csrc/rt_rectify.h, on csrc/rt_temporal.h
+ * for everything the bounded accumulate shares with rt_temporal_accumulate) and compiled into both libraries without contraction, so the
+ * device forms (any launch geometry), the _host forms and rt_temporal_bounds_cpu / rt_temporal_accumulate_bounded_cpu /
+ * rt_temporal_feedback_cpu (librt_host.so, include/rt_host.h) return the same bits.  Each device call is ONE stream-ordered kernel launch
+ * on hip_stream, allocates nothing, visits the host for nothing and may be captured into a HIP graph at once.  Every output word is
+ * written by one thread: no atomics.  Planes, strides and lum(C) are the temporal block's; vpos and rtdm::f_sqrt the filter block's.
+ * Every operation is a single f32 operation in the order written, none fused.
+ *
+ * rt_temporal_bounds, for output pixel p = (r, c).  color is 3 f32 per pixel at a word stride >= 3, read as rt_svgf_atrous reads it; a
+ * pixel's four channels are x_0..2 = its colour and x_3 = lum of it.  The sources are the pixels q = (r + dr, c + dc), dr = -radius ..
+ * radius (outer), dc = -radius .. radius (inner), both ascending, always at step 1; radius is 1, 2 or 3.  A source COUNTS when it lies
+ * inside the image, valid is NULL or valid_q != 0, and object is NULL or object_q == object_p.  Two passes, per channel:
+ *   1. s = +0, k = 0, and for each counting source in tap order:  s = s + x_q;  k = k + 1
+ *   2. mean = s / (float)k
+ *   3. v = +0, and in the same tap order over the same sources:  d = x_q - mean;  v = v + d * d
+ *   4. var = vpos(v / (float)k)
+ *   5. sd = rtdm::f_sqrt(var)
+ *   6. half = gamma * sd
+ *   7. lo = mean - half,  hi = mean + half
+ * A pixel that does not count itself (valid_p == 0) gets lo = -inf, hi = +inf in all four channels: its history resets anyway.  A NaN in
+ * a counting source propagates into mean, lo and hi of that channel; a NaN bound compares false and therefore clamps nothing.  The box
+ * is a plane of its own and not fused into the accumulate so that a caller may fill rt_temporal_box itself (a min/max box, say).
+ * Checked before any device work, in this order, RT_ERR_INVALID_ARGUMENT unless said: rows * cols >= 2^32 (RT_ERR_UNSUPPORTED); rows == 0
+ * or cols == 0 is RT_OK and launches nothing; a null params, color or box; a stride smaller than its plane's width; radius outside 1 .. 3;
+ * gamma >= 0 and finite false; flags != 0; (device form) a box array that is not 16-byte aligned.
+ *
+ * rt_temporal_accumulate_bounded: rt_temporal_accumulate with box_p = d_box[p] between its step 4's H = sum / bsum and the blend.  Steps 1
+ * to 3 — the reset, the four taps, the sums — and n = min(minimum length + 1, max_length) are unchanged.  Then, for a p that did not reset:
+ *   a. for k = 0 .. 2:  H'_k = H_k < lo_k ? lo_k : (H_k > hi_k ? hi_k : H_k)      (a NaN passes)
+ *   b. the first moment likewise into [lo_3, hi_3]:  M1' = clamp(M1);  only where that changed M1:  M2' = M2 + (M1' * M1' - M1 * M1),
+ *      so the history's variance is kept while its mean is shifted; otherwise M2 keeps its bits
+ *   c. if any of the four was changed and clamped_length != 0:  n = min(n, clamped_length), before alpha = 1 / n is formed — a pixel whose
+ *      history was contradicted answers at 1 / clamped_length instead of 1 / max_length
+ * and the blend, the record, the variance plane and the reset are rt_temporal_accumulate's on H', M1', M2' and n.  d_clamped_p (when not
+ * NULL) is the number of channels changed, 0 .. 4; 0 on a reset.  Consequence: with every box at (-inf, +inf) the records and the variance
+ * are rt_temporal_accumulate's bit for bit, and d_clamped is 0.  Checked: everything rt_temporal_accumulate checks, in its order; then,
+ * for an image that is not empty: a null box; (device form) a box array that is not 16-byte aligned; clamped_length > max_length.
+ *
+ * rt_temporal_feedback, in place on `history`: where valid is NULL or valid_p != 0, and history[p].length != 0, the record's three colour
+ * words become the raw words of color_p (3 f32 at a word stride >= 3: a NaN keeps its payload); moments, length and reserved words keep
+ * their bits, and every other record is untouched.  Checked, in this order: rows * cols >= 2^32 (RT_ERR_UNSUPPORTED); an empty image is
+ * RT_OK; a null color or history; a stride smaller than its plane's width; (device form) a history array that is not 16-byte aligned.
+ * RT_AMD_DIAG_RECTIFY_MAX_GROUPS (rt_set_option): a test hook, the three kernels launch at most this many workgroups and take the rest
+ * of the image grid-stride; same bits.
+ * Not covered: banded frames and rt_multi_* forms; a min/max box (a caller may write the box plane itself); the previous normal of
+ * rotating surfaces. */
+
+typedef struct rt_temporal_box {
+    float lo[4];              /* k = 0 .. 2 colour, 3 luminance */
+    float hi[4];
+} rt_temporal_box;           /* 32 bytes: two 16-byte words */
+
+typedef struct rt_bounds_params {
+    float gamma;              /* the box is mean +- gamma * deviation; >= 0, finite */
+    uint32_t radius;          /* 1, 2 or 3: a window of (2 radius + 1)^2 */
+    uint32_t flags;           /* reserved: 0 */
+} rt_bounds_params;          /* 12 bytes */
+
+/* d_color: rows * cols pixels of 3 f32 at color_stride words; d_object, d_valid: one word per pixel at their strides, or NULL; d_box:
+ * rows * cols boxes, 16-byte aligned; one kernel launch.  Nothing but d_box is written. */
+int rt_temporal_bounds(const float *d_color, uint32_t color_stride, const uint32_t *d_object, uint32_t object_stride,
+                       const uint32_t *d_valid, uint32_t valid_stride, const rt_bounds_params *params,
+                       uint32_t rows, uint32_t cols, rt_temporal_box *d_box, void *hip_stream);
+/* every argument of rt_temporal_accumulate, then d_box: rows * cols boxes, 16-byte aligned; clamped_length: 0 .. max_length, 0: the
+ * length is not cut; d_clamped: rows * cols words, or NULL; one kernel launch */
+int rt_temporal_accumulate_bounded(const float *d_color, const float *d_motion, const rt_temporal_guides *current, const rt_temporal_guides *previous,
+                                   const rt_temporal_params *params, uint32_t rows, uint32_t cols, const rt_temporal_pixel *d_history_in,
+                                   rt_temporal_pixel *d_history_out, float *d_variance, const rt_temporal_box *d_box,
+                                   uint32_t clamped_length, uint32_t *d_clamped, void *hip_stream);
+/* d_history: rows * cols records, 16-byte aligned, changed in place; one kernel launch */
+int rt_temporal_feedback(const float *d_color, uint32_t color_stride, const uint32_t *d_valid, uint32_t valid_stride,
+                         uint32_t rows, uint32_t cols, rt_temporal_pixel *d_history, void *hip_stream);
+/* The same kernels on HOST arrays: allocate, upload every plane with its stride, run, synchronise the device and download.  NOT the CPU
+ * definition — that is rt_temporal_bounds_cpu / rt_temporal_accumulate_bounded_cpu / rt_temporal_feedback_cpu of librt_host.so. */
+int rt_temporal_bounds_host(const float *h_color, uint32_t color_stride, const uint32_t *h_object, uint32_t object_stride,
+                            const uint32_t *h_valid, uint32_t valid_stride, const rt_bounds_params *params,
+                            uint32_t rows, uint32_t cols, rt_temporal_box *h_box);
+int rt_temporal_accumulate_bounded_host(const float *h_color, const float *h_motion, const rt_temporal_guides *current, const rt_temporal_guides *previous,
+                                        const rt_temporal_params *params, uint32_t rows, uint32_t cols, const rt_temporal_pixel *h_history_in,
+                                        rt_temporal_pixel *h_history_out, float *h_variance, const rt_temporal_box *h_box,
+                                        uint32_t clamped_length, uint32_t *h_clamped);
+int rt_temporal_feedback_host(const float *h_color, uint32_t color_stride, const uint32_t *h_valid, uint32_t valid_stride,
+                              uint32_t rows, uint32_t cols, rt_temporal_pixel *h_history);
 
 /* ---- variance-guided filter queries: the spatial half of SVGF -------------------------------------
 
@@ -1397,9 +1492,10 @@ int rt_temporal_accumulate_host(const float *h_color, const float *h_motion, con
  * width; then rows == 0 or cols == 0 is RT_OK and launches nothing; a null required pointer (history, color, variance, out, the
  * variance call's variance_out; d_temp with n_levels >= 2); an output or the scratch equal to an input, to each other or to the scratch;
  * (device forms) a history array that is not 16-byte aligned.
- * Not covered: writing a filtered level back into the history records (SVGF's feedback of level 0); SVGF's depth-gradient and dot^128
- * normal weights — this block keeps the project's own normal and position terms; banded frames and rt_multi_* forms; clamping history
- * to the neighbourhood's colour box. */
+ * Writing a filtered level back into the history records (SVGF's feedback of level 0) is rt_temporal_feedback, and clamping the history to
+ * the neighbourhood's colour box rt_temporal_bounds / rt_temporal_accumulate_bounded, of the "history rectification queries" above.
+ * Not covered: SVGF's depth-gradient and dot^128 normal weights — this block keeps the project's own normal and position terms; banded
+ * frames and rt_multi_* forms. */
 
 typedef struct rt_svgf_variance_params {
     float sigma_normal;
@@ -1452,7 +1548,7 @@ int rt_svgf_atrous_host(const float *h_color, uint32_t color_stride, const float
  * RT_AMD_DIST_BY_COST, RT_AMD_DIST_OWN_FIRST, RT_AMD_DIST_PREP_FIRST, RT_AMD_DIST_SPLIT, RT_AMD_DIAG_WS_REFUSE,
  * RT_AMD_MULTI_FORCE_STAGE, RT_AMD_BFS_WALK_TRIANGLES (read by rt_scene_create), RT_AMD_WF_SHARE, RT_AMD_DIAG_BFS_CAP,
  * RT_AMD_DIAG_DIST_BAND_RAYS, RT_AMD_QUERY_WAVE_UNIFORM, RT_AMD_DIAG_HIT_BAND_RECORDS, RT_AMD_FILM_SPLAT_FORM, RT_AMD_DIAG_FILM_MAX_GROUPS,
- * RT_AMD_DENOISE_FORM, RT_AMD_DIAG_DENOISE_MAX_GROUPS, RT_AMD_DIAG_TEMPORAL_MAX_GROUPS, RT_AMD_SVGF_FORM, RT_AMD_DIAG_SVGF_MAX_GROUPS, RT_AMD_DIAG_MOTION_MAX_GROUPS (INTEGRATION.md says what each does); any other name is RT_ERR_INVALID_ARGUMENT.  The environment is read ONCE per process, at the first use;
+ * RT_AMD_DENOISE_FORM, RT_AMD_DIAG_DENOISE_MAX_GROUPS, RT_AMD_DIAG_TEMPORAL_MAX_GROUPS, RT_AMD_SVGF_FORM, RT_AMD_DIAG_SVGF_MAX_GROUPS, RT_AMD_DIAG_MOTION_MAX_GROUPS, RT_AMD_DIAG_RECTIFY_MAX_GROUPS (INTEGRATION.md says what each does); any other name is RT_ERR_INVALID_ARGUMENT.  The environment is read ONCE per process, at the first use;
  * after that only this call changes a switch: value = decimal integer, NULL or "" = unset (the library's own choice).  Render
  * calls read the switches without locks: set them between calls, not during one. */
 int rt_set_option(const char *name, const char *value);

@@ -120,6 +120,20 @@ int rt_temporal_accumulate_cpu(const float *color, const float *motion, const rt
                                const rt_temporal_params *params, uint32_t rows, uint32_t cols, const rt_temporal_pixel *history_in,
                                rt_temporal_pixel *history_out, float *variance);
 
+/* The history rectification queries' CPU definition (include/rt_amd.h "history rectification queries" states every operation and the
+ * order): plain loops over host arrays, no device needed, bit-identical to rt_temporal_bounds / rt_temporal_accumulate_bounded /
+ * rt_temporal_feedback of librt_amd.so.  Same arguments without the stream, same checks with the same messages (no array needs an
+ * alignment here); a failure returns a negative rt_status and sets rt_host_last_error().  Called _cpu for the reason
+ * rt_denoise_atrous_cpu is. */
+int rt_temporal_bounds_cpu(const float *color, uint32_t color_stride, const uint32_t *object, uint32_t object_stride, const uint32_t *valid,
+                           uint32_t valid_stride, const rt_bounds_params *params, uint32_t rows, uint32_t cols, rt_temporal_box *box);
+int rt_temporal_accumulate_bounded_cpu(const float *color, const float *motion, const rt_temporal_guides *current, const rt_temporal_guides *previous,
+                                       const rt_temporal_params *params, uint32_t rows, uint32_t cols, const rt_temporal_pixel *history_in,
+                                       rt_temporal_pixel *history_out, float *variance, const rt_temporal_box *box, uint32_t clamped_length,
+                                       uint32_t *clamped);
+int rt_temporal_feedback_cpu(const float *color, uint32_t color_stride, const uint32_t *valid, uint32_t valid_stride, uint32_t rows,
+                             uint32_t cols, rt_temporal_pixel *history);
+
 /* The motion queries' CPU definition (include/rt_amd.h "motion queries" states every operation and the order): a plain loop over host
  * arrays, no device needed, bit-identical to rt_previous_positions of librt_amd.so.  `now` is the description of the scene as it stands
  * (what the hits were cast on); was_triangles holds 9 f32 per triangle — the kept x y z of vertices 0, 1, 2 — and was_spheres 4 per
