@@ -215,6 +215,11 @@ class SvgfAtrousParams(C.Structure):
                 ("first_level", C.c_uint32), ("n_levels", C.c_uint32), ("flags", C.c_uint32)]
 
 
+class SampleBudgetParams(C.Structure):
+    """rt_sample_budget_params"""
+    _fields_ = [("gain", C.c_float), ("epsilon", C.c_float), ("min_count", C.c_uint32), ("max_count", C.c_uint32), ("flags", C.c_uint32)]
+
+
 AMD_SYMBOLS = [
     "rt_abi_version", "rt_last_error", "rt_device_count", "rt_set_device", "rt_frame_rows", "rt_frame_pixels",
     "rt_scene_create", "rt_scene_destroy", "rt_render_whitted", "rt_render_whitted_host", "rt_set_option", "rt_set_variant",
@@ -229,6 +234,7 @@ AMD_SYMBOLS = [
     "rt_light_rays", "rt_light_terms", "rt_light_fold",
     "rt_material_hits", "rt_material_hits_host", "rt_probe_surfaces", "rt_probe_surfaces_host",
     "rt_film_offsets", "rt_camera_rays_offset", "rt_camera_rays_offset_host", "rt_film_splat",
+    "rt_sample_budget", "rt_sample_list_temp_bytes", "rt_sample_list", "rt_film_offsets_listed", "rt_camera_rays_listed", "rt_film_splat_listed",
     "rt_denoise_temp_bytes", "rt_denoise_atrous", "rt_denoise_atrous_host",
     "rt_temporal_motion", "rt_temporal_accumulate", "rt_temporal_motion_host", "rt_temporal_accumulate_host",
     "rt_temporal_bounds", "rt_temporal_accumulate_bounded", "rt_temporal_feedback",
@@ -250,6 +256,7 @@ HOST_SYMBOLS = [
     "rt_temporal_motion_cpu", "rt_temporal_accumulate_cpu", "rt_svgf_variance_cpu", "rt_svgf_atrous_cpu",
     "rt_previous_positions_cpu",
     "rt_temporal_bounds_cpu", "rt_temporal_accumulate_bounded_cpu", "rt_temporal_feedback_cpu",
+    "rt_sample_budget_cpu", "rt_sample_list_cpu", "rt_film_offsets_listed_cpu", "rt_camera_rays_listed_cpu", "rt_film_splat_listed_cpu",
 ]
 
 _amd = None
@@ -311,6 +318,13 @@ def host_lib() -> C.CDLL:
                                            C.c_void_p, C.c_void_p, C.c_void_p]
         lib.rt_previous_positions_cpu.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32]
         lib.rt_write_png.argtypes = [C.c_char_p, C.c_void_p, C.c_uint32, C.c_uint32]
+        lib.rt_sample_budget_cpu.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                             C.POINTER(SampleBudgetParams), C.c_size_t, C.c_void_p]
+        lib.rt_sample_list_cpu.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.rt_film_offsets_listed_cpu.argtypes = [C.POINTER(Frame), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.rt_camera_rays_listed_cpu.argtypes = [C.POINTER(Camera), C.POINTER(Frame), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.rt_film_splat_listed_cpu.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32,
+                                                 C.c_float, C.c_void_p, C.c_void_p]
         lib.rt_host_last_error.restype = C.c_char_p
         _host = lib
     return _host
@@ -466,6 +480,16 @@ def amd_lib() -> C.CDLL:
         lib.rt_previous_positions.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p]
         lib.rt_previous_positions_host.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32]
         lib.rt_ray_keys.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.c_void_p, C.c_void_p]
+        lib.rt_sample_budget.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                         C.POINTER(SampleBudgetParams), C.c_size_t, C.c_void_p, C.c_void_p]
+        lib.rt_sample_list_temp_bytes.argtypes = [C.c_size_t]
+        lib.rt_sample_list_temp_bytes.restype = C.c_size_t
+        lib.rt_sample_list.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                       C.c_void_p]
+        lib.rt_film_offsets_listed.argtypes = [C.POINTER(Frame), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        lib.rt_camera_rays_listed.argtypes = [C.POINTER(Camera), C.POINTER(Frame), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        lib.rt_film_splat_listed.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32,
+                                             C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.rt_sort_temp_bytes.argtypes = [C.c_size_t]
         lib.rt_sort_temp_bytes.restype = C.c_size_t
         lib.rt_sort_records.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,

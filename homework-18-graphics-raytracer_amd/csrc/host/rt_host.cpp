@@ -24,6 +24,7 @@
 #include "../rt_svgf.h"
 #include "../rt_rectify.h"
 #include "../rt_motion.h"
+#include "../rt_adaptive.h"
 
 using rt::V3;
 
@@ -583,6 +584,87 @@ int rt_film_splat_host(uint32_t rows, uint32_t cols, const float *samples, const
             sum[3 * i + 2] = a.s2;
             weight[i] = a.w;
         }
+    return RT_OK;
+}
+
+/* ---- adaptive sampling queries: the CPU definition (include/rt_amd.h "adaptive sampling queries"; the arithmetic is rt_adaptive.h's, shared with the device) ---- */
+
+int rt_sample_budget_cpu(const float *mean, uint32_t mean_stride, const float *variance, uint32_t variance_stride, const uint32_t *count,
+                         uint32_t count_stride, const uint32_t *valid, uint32_t valid_stride, const rt_sample_budget_params *params, size_t n,
+                         uint32_t *budget) {
+    int status;
+    const char *bad = rt::sample_budget_limits(mean, mean_stride, variance, variance_stride, count, count_stride, valid, valid_stride, params, n, budget, &status);
+    if (bad) return fail(status, std::string("rt_sample_budget_cpu: ") + bad);
+    if (n == 0u) return RT_OK;
+    const rt::SampleBudget b = rt::sample_budget_call(mean, mean_stride, variance, variance_stride, count, count_stride, valid, valid_stride, *params, n, budget);
+    for (uint64_t i = 0; i < b.n; ++i) budget[i] = rt::sample_budget_pixel(b, i);
+    return RT_OK;
+}
+
+int rt_sample_list_cpu(const uint32_t *counts, size_t n, size_t capacity, uint32_t *first, uint32_t *start, uint32_t *pixel, uint32_t *sample,
+                       uint32_t *total) {
+    int status;
+    const char *bad = rt::sample_list_limits(counts, n, capacity, start, pixel, sample, total, &status);
+    if (bad) return fail(status, std::string("rt_sample_list_cpu: ") + bad);
+    uint64_t sum = 0u; /* S_i: below 2^32 */
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint64_t lo = sum < capacity ? sum : capacity;
+        sum += rt::sample_count_clamped(counts[i]);
+        const uint64_t hi = sum < capacity ? sum : capacity;
+        const uint32_t f = first ? first[i] : 0u;
+        start[i] = (uint32_t)lo;
+        for (uint64_t j = lo; j < hi; ++j) pixel[j] = (uint32_t)i, sample[j] = f + (uint32_t)(j - lo);
+        if (first) first[i] = f + (uint32_t)(hi - lo);
+    }
+    start[n] = (uint32_t)(sum < capacity ? sum : capacity);
+    total[0] = start[n];
+    total[1] = (uint32_t)sum;
+    return RT_OK;
+}
+
+int rt_film_offsets_listed_cpu(const rt_frame *frame, uint32_t pattern, uint32_t seed, const uint32_t *pixel, const uint32_t *sample,
+                               const uint32_t *total, size_t capacity, float *offsets) {
+    int status;
+    const char *bad = rt::listed_offsets_limits(frame, pattern, pixel, sample, total, capacity, offsets, &status);
+    if (bad) return fail(status, std::string("rt_film_offsets_listed_cpu: ") + bad);
+    if (capacity == 0u) return RT_OK;
+    const rt::ListedOffsets o = {rt::listed_tile(frame), pattern, seed, pixel, sample, total, capacity, offsets};
+    const uint64_t listed = rt::listed_count(total, capacity);
+    for (uint64_t j = 0; j < capacity; ++j) rt::listed_offsets_record(o, j, listed);
+    return RT_OK;
+}
+
+int rt_camera_rays_listed_cpu(const rt_camera *camera, const rt_frame *frame, const float *offsets, const uint32_t *pixel, const uint32_t *total,
+                              size_t capacity, rt_ray *rays) {
+    int status;
+    const char *bad = rt::listed_rays_limits(camera, frame, offsets, pixel, total, capacity, rays, &status);
+    if (bad) return fail(status, std::string("rt_camera_rays_listed_cpu: ") + bad);
+    if (capacity == 0u) return RT_OK;
+    const rt::ListedCamera c = {rt::temporal_camera(camera, frame), rt::listed_tile(frame)};
+    const uint64_t listed = rt::listed_count(total, capacity), n_pixels = (uint64_t)c.t.rows * c.t.cols;
+    for (uint64_t j = 0; j < capacity; ++j) {
+        uint32_t w[11] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+        const uint32_t pix = j < listed ? pixel[j] : 0xffffffffu;
+        if ((uint64_t)pix < n_pixels) {
+            const uint32_t row = pix / c.t.cols, col = pix - row * c.t.cols;
+            const uint32_t x = c.t.x0 + col, y = c.t.y0 + row * c.t.y_step;
+            rt::listed_ray_words(c, (float)x + offsets[2u * j], (float)y + offsets[2u * j + 1u], w);
+        }
+        memcpy(rays + j, w, sizeof w);
+    }
+    return RT_OK;
+}
+
+int rt_film_splat_listed_cpu(uint32_t rows, uint32_t cols, const float *samples, const uint8_t *valid, const float *offsets, const uint32_t *start,
+                             size_t capacity, uint32_t max_count, uint32_t filter, float radius, float *sum, float *weight) {
+    int status;
+    const char *bad = rt::listed_splat_limits(rows, cols, samples, offsets, start, capacity, max_count, filter, radius, sum, weight, &status);
+    if (bad) return fail(status, std::string("rt_film_splat_listed_cpu: ") + bad);
+    if (rows == 0u || cols == 0u) return RT_OK;
+    const rt::ListedSplat p = {samples, valid, offsets, start, sum, weight, capacity, rows, cols, max_count, filter, radius};
+    for (uint32_t r = 0; r < rows; ++r)
+        for (uint32_t c = 0; c < cols; ++c)
+            rt::listed_splat_pixel(p, r, c, [&](rt::FilmAcc &a, float ddx, float ddy, float p0, float p1, float p2) { rt::film_apply(a, filter, radius, ddx, ddy, p0, p1, p2); });
     return RT_OK;
 }
 

@@ -1,0 +1,392 @@
+/*
+ * rt_adaptive_query.hip — the adaptive sampling queries (include/rt_amd.h "adaptive sampling queries"): a sample budget per pixel from a
+ * mean and a variance plane, the ragged pixel-major list of the samples that budget asks for, and the film queries on such a list:
+ * sample positions, camera rays and the filtered splat; kernels and entry points in one unit.
+ *
+ *   rt::sample_budget_kernel        one thread per pixel, grid-stride: rt_adaptive.h's sample_budget_pixel
+ *   rt::sample_totals_kernel        rt_sample_list, 1 of 3: a workgroup takes 256-pixel steps grid-stride and writes the sum of each step's
+ *                                   clamped counts (a wave reduction by __shfl_down, four wave sums through LDS) to totals[step]
+ *   rt::sample_scan_kernel          2 of 3: ONE workgroup turns totals[0 .. steps) into their exclusive sums in place, 256 entries at a time
+ *                                   with a carried base (coalesced), and writes totals[steps] = S_n, start_n and d_total
+ *   rt::sample_expand_kernel        3 of 3: the same steps again.  A workgroup scans its 256 counts (an inclusive scan per wave by
+ *                                   __shfl_up, the wave sums through LDS) into 257 LDS prefix values, writes start_i and first_i, and its
+ *                                   threads then walk the step's OUTPUT range [base, base + block_total) with stride 256: record base + k
+ *                                   belongs to the pixel p with prefix[p] <= k < prefix[p + 1], found by a binary search of eight LDS
+ *                                   reads.  So the stores to d_pixel and d_sample are coalesced whatever the counts are, and a pixel with
+ *                                   64 samples costs its neighbours' lanes nothing.  block_total <= 256 * 64 = 16 384.
+ *   rt::offsets_listed_kernel       one thread per record of [0, capacity), grid-stride: rt_adaptive.h's listed_offsets_record
+ *   rt::camera_rays_listed_kernel   one thread per record: rt_primary_ray.h's primary_ray_through, or the all-zero ray
+ *   rt::splat_listed_kernel<FILTER>        the splat as a gather, one thread per output pixel: rt_adaptive.h's listed_splat_pixel
+ *   rt::splat_listed_tiled_kernel<FILTER>  the same gather from LDS: a workgroup owns a 16 x 16 tile, stages the halo's record ranges once
+ *                                   per tile and, per sample index s, the halo's offsets and samples; an s that no pixel of the halo has is
+ *                                   skipped (it would contribute to nobody)
+ *
+ * Everything the list kernels compute is u32 arithmetic on sums below 2^32 (n * RT_SAMPLE_MAX < 2^32 is checked by the entry point), so
+ * the result cannot depend on the launch geometry: there is no atomic and no order to decide.  Both splat kernels walk a pixel's sources
+ * in the order of the definition — s outermost, then dr, then dc, ascending — and call film_covers / film_apply on the same operands.
+ * A record index is clamped into [0, capacity) before anything is read through it (listed_range).  Every loop that holds a barrier is
+ * workgroup-uniform.
+ */
+#include "rt_api_internal.h"
+#include "rt_adaptive.h"
+#include "rt_primary_ray.h"
+
+namespace rt {
+
+#define RT_ADAPTIVE_THREADS 256u
+#define RT_ADAPTIVE_WAVES (RT_ADAPTIVE_THREADS / 64u)
+#define RT_ADAPTIVE_MAX_GROUPS (1u << 16)
+static_assert(RT_ADAPTIVE_THREADS == RT_SAMPLE_LIST_STEP, "a workgroup takes one step of the list per pass");
+
+/* ---- the budget ---- */
+
+__global__ __launch_bounds__(RT_ADAPTIVE_THREADS) void sample_budget_kernel(const SampleBudget b) {
+    const uint64_t stride = (uint64_t)gridDim.x * RT_ADAPTIVE_THREADS;
+    for (uint64_t i = (uint64_t)blockIdx.x * RT_ADAPTIVE_THREADS + threadIdx.x; i < b.n; i += stride) b.budget[i] = sample_budget_pixel(b, i);
+}
+
+/* ---- the list ---- */
+
+/* the sum of one value per thread over the workgroup, in every thread; lds: RT_ADAPTIVE_WAVES words */
+__device__ __forceinline__ uint32_t adaptive_group_sum(uint32_t v, uint32_t *lds) {
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    __syncthreads(); /* the previous use of lds is over */
+    if ((threadIdx.x & 63u) == 0u) lds[threadIdx.x >> 6] = v;
+    __syncthreads();
+    uint32_t sum = 0u;
+#pragma unroll
+    for (uint32_t w = 0; w < RT_ADAPTIVE_WAVES; ++w) sum += lds[w];
+    return sum;
+}
+
+/* the inclusive sum of one value per thread over the workgroup, in thread order; *total: the sum of all; lds: RT_ADAPTIVE_WAVES words */
+__device__ __forceinline__ uint32_t adaptive_group_scan(uint32_t v, uint32_t *lds, uint32_t *total) {
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t up = __shfl_up(v, off, 64);
+        if (lane >= (uint32_t)off) v += up;
+    }
+    __syncthreads(); /* the previous use of lds is over */
+    if (lane == 63u) lds[wave] = v;
+    __syncthreads();
+    uint32_t before = 0u, all = 0u;
+#pragma unroll
+    for (uint32_t w = 0; w < RT_ADAPTIVE_WAVES; ++w) {
+        const uint32_t c = lds[w];
+        if (w < wave) before += c;
+        all += c;
+    }
+    *total = all;
+    return v + before;
+}
+
+__global__ __launch_bounds__(RT_ADAPTIVE_THREADS) void sample_totals_kernel(const uint32_t *__restrict__ counts, const uint64_t n, const uint64_t steps,
+                                                                            uint32_t *__restrict__ totals) {
+    __shared__ uint32_t lds[RT_ADAPTIVE_WAVES];
+    for (uint64_t step = blockIdx.x; step < steps; step += gridDim.x) { /* workgroup-uniform */
+        const uint64_t i = step * RT_ADAPTIVE_THREADS + threadIdx.x;
+        const uint32_t sum = adaptive_group_sum(i < n ? sample_count_clamped(counts[i]) : 0u, lds);
+        if (threadIdx.x == 0u) totals[step] = sum;
+    }
+}
+
+__global__ __launch_bounds__(RT_ADAPTIVE_THREADS) void sample_scan_kernel(uint32_t *__restrict__ totals, const uint64_t steps, const uint64_t n,
+                                                                          const uint64_t capacity, uint32_t *__restrict__ start, uint32_t *__restrict__ total) {
+    __shared__ uint32_t lds[RT_ADAPTIVE_WAVES];
+    uint32_t base = 0u; /* the sum of the entries before this round's: below 2^32, as S_n is */
+    for (uint64_t first = 0u; first < steps; first += RT_ADAPTIVE_THREADS) { /* workgroup-uniform */
+        const uint64_t k = first + threadIdx.x;
+        const uint32_t v = k < steps ? totals[k] : 0u;
+        uint32_t all;
+        const uint32_t inclusive = adaptive_group_scan(v, lds, &all);
+        if (k < steps) totals[k] = base + (inclusive - v);
+        base += all;
+    }
+    if (threadIdx.x == 0u) {
+        const uint32_t listed = (uint64_t)base < capacity ? base : (uint32_t)capacity;
+        totals[steps] = base;
+        start[n] = listed;
+        total[0] = listed;
+        total[1] = base;
+    }
+}
+
+__global__ __launch_bounds__(RT_ADAPTIVE_THREADS) void sample_expand_kernel(const uint32_t *__restrict__ counts, const uint64_t n, const uint64_t steps,
+                                                                            const uint32_t *__restrict__ totals, const uint64_t capacity,
+                                                                            uint32_t *__restrict__ first, uint32_t *__restrict__ start,
+                                                                            uint32_t *__restrict__ pixel, uint32_t *__restrict__ sample) {
+    __shared__ uint32_t lds[RT_ADAPTIVE_WAVES];
+    __shared__ uint32_t l_prefix[RT_ADAPTIVE_THREADS + 1u];
+    __shared__ uint32_t l_first[RT_ADAPTIVE_THREADS];
+    for (uint64_t step = blockIdx.x; step < steps; step += gridDim.x) { /* workgroup-uniform */
+        const uint64_t i = step * RT_ADAPTIVE_THREADS + threadIdx.x;
+        const uint32_t c = i < n ? sample_count_clamped(counts[i]) : 0u;
+        uint32_t block_total;
+        const uint32_t inclusive = adaptive_group_scan(c, lds, &block_total); /* its first barrier: the previous step's LDS reads are done */
+        const uint64_t base = totals[step];
+        const uint32_t f = (first != nullptr && i < n) ? first[i] : 0u;
+        l_prefix[threadIdx.x + 1u] = inclusive;
+        if (threadIdx.x == 0u) l_prefix[0] = 0u;
+        l_first[threadIdx.x] = f;
+        if (i < n) {
+            const uint64_t s0 = base + (inclusive - c), s1 = base + inclusive;
+            const uint32_t lo = (uint32_t)(s0 < capacity ? s0 : capacity), hi = (uint32_t)(s1 < capacity ? s1 : capacity);
+            start[i] = lo;
+            if (first != nullptr) first[i] = f + (hi - lo);
+        }
+        __syncthreads();
+        for (uint32_t k = threadIdx.x; k < block_total; k += RT_ADAPTIVE_THREADS) { /* no barrier inside */
+            const uint64_t j = base + k;
+            if (j >= capacity) break; /* j grows with k: nothing of this thread's lies below capacity any more */
+            uint32_t lo = 0u, hi = RT_ADAPTIVE_THREADS; /* l_prefix[lo] <= k < l_prefix[hi] throughout */
+            while (hi - lo > 1u) {
+                const uint32_t mid = (lo + hi) >> 1;
+                if (l_prefix[mid] <= k) lo = mid;
+                else hi = mid;
+            }
+            pixel[j] = (uint32_t)(step * RT_ADAPTIVE_THREADS) + lo;
+            sample[j] = l_first[lo] + (k - l_prefix[lo]);
+        }
+    }
+}
+
+/* n == 0: start_0 and both totals, nothing else */
+__global__ void sample_list_empty_kernel(uint32_t *__restrict__ start, uint32_t *__restrict__ total) {
+    if (threadIdx.x == 0u && blockIdx.x == 0u) start[0] = 0u, total[0] = 0u, total[1] = 0u;
+}
+
+/* ---- positions and rays of a list ---- */
+
+__global__ __launch_bounds__(RT_ADAPTIVE_THREADS) void offsets_listed_kernel(const ListedOffsets o) {
+    const uint64_t listed = listed_count(o.total, o.capacity), stride = (uint64_t)gridDim.x * RT_ADAPTIVE_THREADS;
+    for (uint64_t j = (uint64_t)blockIdx.x * RT_ADAPTIVE_THREADS + threadIdx.x; j < o.capacity; j += stride) listed_offsets_record(o, j, listed);
+}
+
+__global__ __launch_bounds__(RT_ADAPTIVE_THREADS) void camera_rays_listed_kernel(const KernelFrame fr, const float *__restrict__ offsets,
+                                                                                 const uint32_t *__restrict__ pixel, const uint32_t *__restrict__ total,
+                                                                                 const uint64_t capacity, rt_ray *__restrict__ rays) {
+    const uint64_t listed = listed_count(total, capacity), stride = (uint64_t)gridDim.x * RT_ADAPTIVE_THREADS;
+    const uint64_t n_pixels = (uint64_t)fr.rows * fr.cols;
+    for (uint64_t j = (uint64_t)blockIdx.x * RT_ADAPTIVE_THREADS + threadIdx.x; j < capacity; j += stride) {
+        const uint32_t pix = j < listed ? pixel[j] : 0xffffffffu;
+        if ((uint64_t)pix >= n_pixels) { /* beyond the list, or a pixel the frame does not have: the record of an absent candidate */
+            uint32_t *const o = reinterpret_cast<uint32_t *>(rays + j);
+#pragma unroll
+            for (int k = 0; k < 11; ++k) o[k] = 0u;
+            continue;
+        }
+        const uint32_t row = pix / fr.cols, col = pix - row * fr.cols;
+        const uint32_t x = fr.x0 + col, y = fr.y0 + row * fr.y_step;
+        store_primary_ray(primary_ray_through(fr, (float)x + offsets[2u * j], (float)y + offsets[2u * j + 1u]), rays + j);
+    }
+}
+
+/* ---- the splat ---- */
+
+template <uint32_t FILTER>
+__global__ __launch_bounds__(RT_ADAPTIVE_THREADS) void splat_listed_kernel(const ListedSplat p) {
+    const uint64_t n = (uint64_t)p.rows * p.cols, stride = (uint64_t)gridDim.x * RT_ADAPTIVE_THREADS;
+    for (uint64_t i = (uint64_t)blockIdx.x * RT_ADAPTIVE_THREADS + threadIdx.x; i < n; i += stride) {
+        const uint32_t r = (uint32_t)(i / p.cols), c = (uint32_t)(i - (uint64_t)r * p.cols);
+        listed_splat_pixel(p, r, c, [&](FilmAcc &a, float ddx, float ddy, float p0, float p1, float p2) { film_apply(a, FILTER, p.radius, ddx, ddy, p0, p1, p2); });
+    }
+}
+
+/* 256 threads = a 16 x 16 tile; the halo is (16 + 2 reach) entries wide, reach <= 5 (radius <= 4): at most 676 entries of 7 words, 18.5 KB
+ * of LDS.  Entry e of the halo is staged by thread e, e + 256, ...: consecutive threads read consecutive pixels of an image row, whose
+ * records are adjacent in a pixel-major list. */
+#define RT_LISTED_TILE 16u
+#define RT_LISTED_HALO_MAX (RT_LISTED_TILE + 2u * 5u)
+template <uint32_t FILTER>
+__global__ __launch_bounds__(RT_ADAPTIVE_THREADS) void splat_listed_tiled_kernel(const ListedSplat p, const uint32_t tiles_x, const uint64_t n_tiles) {
+    __shared__ float2 l_off[RT_LISTED_HALO_MAX * RT_LISTED_HALO_MAX];
+    __shared__ float l_smp[RT_LISTED_HALO_MAX * RT_LISTED_HALO_MAX * 3u];
+    __shared__ uint32_t l_lo[RT_LISTED_HALO_MAX * RT_LISTED_HALO_MAX], l_cnt[RT_LISTED_HALO_MAX * RT_LISTED_HALO_MAX];
+    __shared__ uint32_t l_max[RT_ADAPTIVE_WAVES];
+    const int reach = film_reach(p.radius);
+    const uint32_t halo = RT_LISTED_TILE + 2u * (uint32_t)reach; /* <= RT_LISTED_HALO_MAX: the entry point bounds the radius */
+    const uint32_t ty = threadIdx.x / RT_LISTED_TILE, tx = threadIdx.x % RT_LISTED_TILE;
+    for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) { /* workgroup-uniform */
+        const uint32_t tile_r = (uint32_t)(tile / tiles_x), tile_c = (uint32_t)(tile - (uint64_t)tile_r * tiles_x);
+        const int64_t r0 = (int64_t)tile_r * RT_LISTED_TILE, c0 = (int64_t)tile_c * RT_LISTED_TILE;
+        const int64_t r = r0 + ty, c = c0 + tx;
+        const bool inside = r < (int64_t)p.rows && c < (int64_t)p.cols;
+        const uint64_t i = inside ? (uint64_t)r * p.cols + (uint64_t)c : 0u;
+        FilmAcc a = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (inside) a = {p.sum[3u * i], p.sum[3u * i + 1u], p.sum[3u * i + 2u], p.weight[i]};
+        __syncthreads(); /* the previous tile's reads are done */
+        uint32_t most = 0u;
+        for (uint32_t e = threadIdx.x; e < halo * halo; e += RT_ADAPTIVE_THREADS) { /* the halo's record ranges, once per tile */
+            const uint32_t hr = e / halo, hc = e - hr * halo;
+            const int64_t qr = r0 - reach + hr, qc = c0 - reach + hc;
+            uint32_t lo = 0u, cnt = 0u;
+            if (qr >= 0 && qr < (int64_t)p.rows && qc >= 0 && qc < (int64_t)p.cols) cnt = listed_range(p, (uint64_t)qr * p.cols + (uint64_t)qc, &lo);
+            l_lo[e] = lo;
+            l_cnt[e] = cnt;
+            most = cnt > most ? cnt : most;
+        }
+        for (int off = 32; off > 0; off >>= 1) {
+            const uint32_t other = __shfl_down(most, off, 64);
+            most = other > most ? other : most;
+        }
+        if ((threadIdx.x & 63u) == 0u) l_max[threadIdx.x >> 6] = most;
+        __syncthreads();
+        most = 0u;
+#pragma unroll
+        for (uint32_t w = 0; w < RT_ADAPTIVE_WAVES; ++w) most = l_max[w] > most ? l_max[w] : most;
+        const uint32_t s_end = most < p.max_count ? most : p.max_count; /* workgroup-uniform: an s at or beyond it has no source in the halo */
+        for (uint32_t s = 0; s < s_end; ++s) {
+            __syncthreads(); /* the previous sample's reads are done */
+            for (uint32_t e = threadIdx.x; e < halo * halo; e += RT_ADAPTIVE_THREADS) {
+                float2 off = make_float2(__uint_as_float(RT_LISTED_NAN), 0.0f); /* NaN dx: contributes to nobody */
+                float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
+                if (s < l_cnt[e]) {
+                    const uint64_t rec = (uint64_t)l_lo[e] + s;
+                    if (p.valid == nullptr || p.valid[rec] != 0u) {
+                        off = make_float2(p.offsets[2u * rec], p.offsets[2u * rec + 1u]);
+                        s0 = p.samples[3u * rec];
+                        s1 = p.samples[3u * rec + 1u];
+                        s2 = p.samples[3u * rec + 2u];
+                    }
+                }
+                l_off[e] = off;
+                l_smp[3u * e] = s0;
+                l_smp[3u * e + 1u] = s1;
+                l_smp[3u * e + 2u] = s2;
+            }
+            __syncthreads();
+            if (inside) {
+                for (int dr = -reach; dr <= reach; ++dr) {
+                    const uint32_t row_e = (uint32_t)((int)ty + reach + dr) * halo + (uint32_t)((int)tx + reach);
+                    for (int dc = -reach; dc <= reach; ++dc) {
+                        const uint32_t e = (uint32_t)((int)row_e + dc);
+                        const float2 off = l_off[e];
+                        float ddx, ddy;
+                        if (!film_covers(dr, dc, off.x, off.y, p.radius, &ddx, &ddy)) continue;
+                        film_apply(a, FILTER, p.radius, ddx, ddy, l_smp[3u * e], l_smp[3u * e + 1u], l_smp[3u * e + 2u]);
+                    }
+                }
+            }
+        }
+        if (inside) {
+            p.sum[3u * i] = a.s0;
+            p.sum[3u * i + 1u] = a.s1;
+            p.sum[3u * i + 2u] = a.s2;
+            p.weight[i] = a.w;
+        }
+    }
+}
+
+/* ---- launchers ---- */
+
+static uint32_t adaptive_groups(uint64_t wanted) {
+    return (uint32_t)std::min<uint64_t>(wanted, max_groups(OPT_DIAG_ADAPTIVE_MAX_GROUPS, RT_ADAPTIVE_MAX_GROUPS));
+}
+static uint32_t adaptive_groups_of(uint64_t n) { return adaptive_groups((n + RT_ADAPTIVE_THREADS - 1u) / RT_ADAPTIVE_THREADS); }
+
+static hipError_t launch_sample_list(const uint32_t *counts, uint64_t n, uint64_t capacity, uint32_t *first, uint32_t *start, uint32_t *pixel, uint32_t *sample,
+                                     uint32_t *total, uint32_t *totals, hipStream_t stream) {
+    const uint64_t steps = sample_list_steps(n);
+    const dim3 grid(adaptive_groups(steps)), block(RT_ADAPTIVE_THREADS);
+    hipLaunchKernelGGL(sample_totals_kernel, grid, block, 0, stream, counts, n, steps, totals);
+    hipLaunchKernelGGL(sample_scan_kernel, dim3(1), block, 0, stream, totals, steps, n, capacity, start, total);
+    hipLaunchKernelGGL(sample_expand_kernel, grid, block, 0, stream, counts, n, steps, totals, capacity, first, start, pixel, sample);
+    return hipGetLastError();
+}
+
+template <uint32_t FILTER>
+static void launch_splat_listed_of(const ListedSplat &p, bool tiled, hipStream_t stream) {
+    if (tiled) {
+        const uint32_t tiles_x = (p.cols + RT_LISTED_TILE - 1u) / RT_LISTED_TILE, tiles_y = (p.rows + RT_LISTED_TILE - 1u) / RT_LISTED_TILE;
+        const uint64_t n_tiles = (uint64_t)tiles_x * tiles_y;
+        hipLaunchKernelGGL(splat_listed_tiled_kernel<FILTER>, dim3(adaptive_groups(n_tiles)), dim3(RT_ADAPTIVE_THREADS), 0, stream, p, tiles_x, n_tiles);
+    } else {
+        hipLaunchKernelGGL(splat_listed_kernel<FILTER>, dim3(adaptive_groups_of((uint64_t)p.rows * p.cols)), dim3(RT_ADAPTIVE_THREADS), 0, stream, p);
+    }
+}
+
+static hipError_t launch_splat_listed(const ListedSplat &p, bool tiled, hipStream_t stream) {
+    if (p.filter == RT_FILM_BOX) launch_splat_listed_of<RT_FILM_BOX>(p, tiled, stream);
+    else if (p.filter == RT_FILM_TENT) launch_splat_listed_of<RT_FILM_TENT>(p, tiled, stream);
+    else launch_splat_listed_of<RT_FILM_MITCHELL>(p, tiled, stream);
+    return hipGetLastError();
+}
+
+} /* namespace rt */
+
+/* which form rt_film_splat_listed launches unless RT_AMD_FILM_SPLAT_FORM says otherwise: 0 plain, 1 tiled, as rt_film_splat (DESIGN.md 3.26
+ * has the figures of both) */
+#define RT_LISTED_SPLAT_FORM_DEFAULT 1
+
+extern "C" {
+
+int rt_sample_budget(const float *d_mean, uint32_t mean_stride, const float *d_variance, uint32_t variance_stride, const uint32_t *d_count,
+                     uint32_t count_stride, const uint32_t *d_valid, uint32_t valid_stride, const rt_sample_budget_params *params, size_t n,
+                     uint32_t *d_budget, void *hip_stream) {
+    int status;
+    const char *bad = rt::sample_budget_limits(d_mean, mean_stride, d_variance, variance_stride, d_count, count_stride, d_valid, valid_stride, params, n, d_budget, &status);
+    if (bad) return fail(status, std::string("rt_sample_budget: ") + bad);
+    if (n == 0u) return RT_OK;
+    const rt::SampleBudget b = rt::sample_budget_call(d_mean, mean_stride, d_variance, variance_stride, d_count, count_stride, d_valid, valid_stride, *params, n, d_budget);
+    hipLaunchKernelGGL(rt::sample_budget_kernel, dim3(rt::adaptive_groups_of(n)), dim3(RT_ADAPTIVE_THREADS), 0, static_cast<hipStream_t>(hip_stream), b);
+    return launched("rt_sample_budget");
+}
+
+size_t rt_sample_list_temp_bytes(size_t n) { return (size_t)rt::sample_list_temp_bytes(n); }
+
+int rt_sample_list(const uint32_t *d_counts, size_t n, size_t capacity, uint32_t *d_first, uint32_t *d_start, uint32_t *d_pixel, uint32_t *d_sample,
+                   uint32_t *d_total, void *d_temp, size_t temp_bytes, void *hip_stream) {
+    int status;
+    const char *bad = rt::sample_list_limits(d_counts, n, capacity, d_start, d_pixel, d_sample, d_total, &status);
+    if (bad) return fail(status, std::string("rt_sample_list: ") + bad);
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    if (n == 0u) {
+        hipLaunchKernelGGL(rt::sample_list_empty_kernel, dim3(1), dim3(64), 0, stream, d_start, d_total);
+        return launched("rt_sample_list");
+    }
+    if (!d_temp || temp_bytes < rt::sample_list_temp_bytes(n))
+        return fail(RT_ERR_INVALID_ARGUMENT, "rt_sample_list: temp is null or smaller than rt_sample_list_temp_bytes(n)");
+    if ((reinterpret_cast<uintptr_t>(d_temp) & 3u) != 0u) return fail(RT_ERR_INVALID_ARGUMENT, "rt_sample_list: temp is not 4-byte aligned");
+    return launched("rt_sample_list",
+                    rt::launch_sample_list(d_counts, n, capacity, d_first, d_start, d_pixel, d_sample, d_total, static_cast<uint32_t *>(d_temp), stream));
+}
+
+int rt_film_offsets_listed(const rt_frame *frame, uint32_t pattern, uint32_t seed, const uint32_t *d_pixel, const uint32_t *d_sample, const uint32_t *d_total,
+                           size_t capacity, float *d_offsets, void *hip_stream) {
+    int status;
+    const char *bad = rt::listed_offsets_limits(frame, pattern, d_pixel, d_sample, d_total, capacity, d_offsets, &status);
+    if (bad) return fail(status, std::string("rt_film_offsets_listed: ") + bad);
+    if (capacity == 0u) return RT_OK;
+    const rt::ListedOffsets o = {rt::listed_tile(frame), pattern, seed, d_pixel, d_sample, d_total, capacity, d_offsets};
+    hipLaunchKernelGGL(rt::offsets_listed_kernel, dim3(rt::adaptive_groups_of(capacity)), dim3(RT_ADAPTIVE_THREADS), 0, static_cast<hipStream_t>(hip_stream), o);
+    return launched("rt_film_offsets_listed");
+}
+
+int rt_camera_rays_listed(const rt_camera *camera, const rt_frame *frame, const float *d_offsets, const uint32_t *d_pixel, const uint32_t *d_total,
+                          size_t capacity, rt_ray *d_rays, void *hip_stream) {
+    int status;
+    const char *bad = rt::listed_rays_limits(camera, frame, d_offsets, d_pixel, d_total, capacity, d_rays, &status);
+    if (bad) return fail(status, std::string("rt_camera_rays_listed: ") + bad);
+    if (capacity == 0u) return RT_OK;
+    rt_frame f = *frame;
+    f.max_depth = 0; /* not used here */
+    rt::KernelFrame kf;
+    const int rc = make_kernel_frame(camera, &f, &kf);
+    if (rc != RT_OK) return rc;
+    hipLaunchKernelGGL(rt::camera_rays_listed_kernel, dim3(rt::adaptive_groups_of(capacity)), dim3(RT_ADAPTIVE_THREADS), 0, static_cast<hipStream_t>(hip_stream), kf,
+                       d_offsets, d_pixel, d_total, (uint64_t)capacity, d_rays);
+    return launched("rt_camera_rays_listed");
+}
+
+int rt_film_splat_listed(uint32_t rows, uint32_t cols, const float *d_samples, const unsigned char *d_valid, const float *d_offsets, const uint32_t *d_start,
+                         size_t capacity, uint32_t max_count, uint32_t filter, float radius, float *d_sum, float *d_weight, void *hip_stream) {
+    int status;
+    const char *bad = rt::listed_splat_limits(rows, cols, d_samples, d_offsets, d_start, capacity, max_count, filter, radius, d_sum, d_weight, &status);
+    if (bad) return fail(status, std::string("rt_film_splat_listed: ") + bad);
+    if (rows == 0u || cols == 0u) return RT_OK;
+    const rt::ListedSplat p = {d_samples, d_valid, d_offsets, d_start, d_sum, d_weight, capacity, rows, cols, max_count, filter, radius};
+    const bool tiled = rt::option(rt::OPT_FILM_SPLAT_FORM, RT_LISTED_SPLAT_FORM_DEFAULT) == 1;
+    return launched("rt_film_splat_listed", rt::launch_splat_listed(p, tiled, static_cast<hipStream_t>(hip_stream)));
+}
+
+} /* extern "C" */

@@ -140,7 +140,9 @@ struct KernelQueues {
     X(OPT_SVGF_FORM, "RT_AMD_SVGF_FORM")                   /* rt_svgf_atrous: 0 the simple gather from global memory, 1 the tiled gather from LDS (same bits; DESIGN.md 3.23 has the A/B) */ \
     X(OPT_DIAG_SVGF_MAX_GROUPS, "RT_AMD_DIAG_SVGF_MAX_GROUPS") /* test hook: rt_svgf_variance and a level of rt_svgf_atrous launch at most this many workgroups (default and most: 2^16), the rest of the image taken grid-stride */ \
     X(OPT_DIAG_MOTION_MAX_GROUPS, "RT_AMD_DIAG_MOTION_MAX_GROUPS") /* test hook: rt_previous_positions and rt_scene_keep_positions launch at most this many workgroups (default and most: 2^16), the rest of the batch taken grid-stride */ \
-    X(OPT_DIAG_RECTIFY_MAX_GROUPS, "RT_AMD_DIAG_RECTIFY_MAX_GROUPS") /* test hook: rt_temporal_bounds, rt_temporal_accumulate_bounded and rt_temporal_feedback launch at most this many workgroups (default and most: 2^16), the rest of the image taken grid-stride */
+    X(OPT_DIAG_RECTIFY_MAX_GROUPS, "RT_AMD_DIAG_RECTIFY_MAX_GROUPS") /* test hook: rt_temporal_bounds, rt_temporal_accumulate_bounded and rt_temporal_feedback launch at most this many workgroups (default and most: 2^16), the rest of the image taken grid-stride */ \
+    X(OPT_DIAG_ADAPTIVE_MAX_GROUPS,                                                                                                            \
+      "RT_AMD_DIAG_ADAPTIVE_MAX_GROUPS") /* test hook: the kernels of the adaptive sampling queries (rt_sample_budget, rt_sample_list's totals and expansion, rt_film_offsets_listed, rt_camera_rays_listed, rt_film_splat_listed) launch at most this many workgroups (default and most: 2^16), the rest taken grid-stride */
 #define RT_OPTION_ID(id, name) id,
 enum Option : int { RT_OPTIONS(RT_OPTION_ID) OPT_COUNT };
 #undef RT_OPTION_ID

@@ -1137,6 +1137,116 @@ int rt_camera_rays_offset_host(const rt_camera *camera, const rt_frame *frame, c
 int rt_film_splat(uint32_t rows, uint32_t cols, const float *d_samples, const unsigned char *d_valid, const float *d_offsets, uint32_t spp,
                   uint32_t filter, float radius, float *d_sum, float *d_weight, void *hip_stream);
 
+/* ---- adaptive sampling queries: sample budgets, lists and listed splats ----------------------------
+
+ * What turns a variance estimate into more samples where they are needed.  The film queries above take ONE spp for the whole frame and
+ * are sample-major; these five calls are their ragged counterpart, PIXEL-MAJOR: a budget per pixel (rt_sample_budget), the list of the
+ * samples it asks for (rt_sample_list), and the film queries on that list:
+ *     rt_sample_budget -> rt_sample_list -> rt_film_offsets_listed -> rt_camera_rays_listed -> rt_trace_rays -> rt_film_splat_listed
+ * The reference has no counterpart; the definitions below are the contract.  The arithmetic is written once (csrc/rt_adaptive.h, on
+ * csrc/rt_film.h's film_u / film_offset / film_reach / film_covers / film_apply, unchanged) and compiled into both libraries without
+ * contraction, so the device forms (any launch geometry, either splat form) and rt_sample_budget_cpu / rt_sample_list_cpu /
+ * rt_film_offsets_listed_cpu / rt_camera_rays_listed_cpu / rt_film_splat_listed_cpu (librt_host.so, include/rt_host.h) return the same
+ * bits.  Every pointer is a device pointer; every call is stream-ordered and asynchronous on hip_stream (NULL = default stream),
+ * allocates nothing, visits the host for nothing — the number of listed records stays on the device, in d_total — and may be captured
+ * into a HIP graph at once, the first call on a stream included: the only scratch is the caller's d_temp.  Every output word is written
+ * by one thread; no atomics; record numbers are counted in 64 bits.  Every f32 operation is a single operation in the order written, none
+ * fused; divide and square root are correctly rounded.
+ *
+ * rt_sample_budget, for pixel p of n.  mean, variance (f32) and count, valid (u32) are planes of one word per pixel read through record
+ * strides given in 4-byte words, so moment1 and length inside rt_temporal_pixel records are read with stride 8 and no copy, beside a
+ * compact variance plane (rt_temporal_accumulate's d_variance, rt_svgf_variance).  count NULL is 1 everywhere; valid NULL is "all".
+ *   1. valid given and valid_p == 0:  budget_p = 0
+ *   2. count_p == 0 (no estimate):   budget_p = max_count
+ *   3. e = sqrtf(variance_p / (float)count_p) / (fabsf(mean_p) + epsilon)        the relative standard error of the mean
+ *   4. t = e * gain
+ *   5. range = max_count - min_count
+ *   6. budget_p = min_count + (t < (float)range ? (uint32_t)t : range)
+ * The float test comes before the conversion, so a NaN or a huge t gives max_count and is never converted.  A negative variance gives a
+ * NaN under the root and therefore max_count; so do a NaN variance, a NaN mean and +inf variance.  Variance 0 or gain 0 gives min_count
+ * (gain 0 with an infinite e is 0 * inf = NaN: max_count).  d_budget is a compact u32 plane.  One element-wise kernel, grid-stride.
+ * Checked before any device work, in this order, RT_ERR_INVALID_ARGUMENT unless said: n >= 2^32 (RT_ERR_UNSUPPORTED); n == 0 is RT_OK and
+ * launches nothing; a null params; a null mean, variance or budget; a stride of 0 words; gain >= 0 false; epsilon > 0 false;
+ * min_count <= max_count <= RT_SAMPLE_MAX false; flags != 0.
+ * Normalising the budgets to a fixed total is not part of it: the total comes out of rt_sample_list on the device, and a caller adjusts
+ * gain from it.
+ *
+ * rt_sample_list.  c_i = min(d_counts[i], RT_SAMPLE_MAX) — the caller's counts are validated, never trusted — and S_i = c_0 + .. + c_(i-1)
+ * (S_0 = 0), all below 2^32 because n * RT_SAMPLE_MAX < 2^32 is required.
+ *   start_i = min(S_i, capacity)                                   for i = 0 .. n                     d_start[n + 1]
+ *   for start_i <= j < start_(i+1):  pixel[j] = i,  sample[j] = first_i + (j - start_i)                d_pixel, d_sample[capacity]
+ *   d_total[0] = start_n  (the records listed);   d_total[1] = S_n  (the records asked for: larger only when the list was cut)
+ *   first_i = 0 when d_first is NULL; with d_first (n words, in and out) afterwards  first_i += start_(i+1) - start_i,  so a progressive
+ *   caller never repeats a sample index
+ * A pixel that straddles capacity keeps its first samples.  Entries of d_pixel / d_sample at and beyond d_total[0] are unspecified.  The
+ * list is pixel-major on purpose: the samples of one pixel, and of neighbouring pixels, are adjacent, so 64 consecutive rays stay
+ * coherent.  Three kernel launches: per-step totals, a one-workgroup scan, placement and expansion — integer sums only, so nothing depends
+ * on the launch geometry.  d_temp: rt_sample_list_temp_bytes(n) bytes of opaque scratch, 4-byte aligned (host arithmetic, monotone in n,
+ * 0 for n == 0 and for an n the call refuses).
+ * Checked before any device work, in this order: n * RT_SAMPLE_MAX >= 2^32, then capacity >= 2^32 (RT_ERR_UNSUPPORTED); a null start or
+ * total; n == 0 is RT_OK, writes start_0 = 0 and both totals 0 and launches nothing else; a null counts; capacity != 0 and a null pixel or
+ * sample; a temp that is null, too small or misaligned (all RT_ERR_INVALID_ARGUMENT).
+ *
+ * rt_film_offsets_listed.  listed = min(d_total[0], capacity).  For j < listed with pixel[j] < rows * cols of the frame or tile:
+ *   offsets[2 j + axis] = film_offset(pattern, global pixel, seed, sample[j], axis)      (rt_film_offsets' hash, keyed by the GLOBAL index
+ *   (y0 + row * y_step) * width + (x0 + col) of compact pixel pixel[j] = row * cols + col)
+ * so sample s of a pixel has the offset rt_film_offsets gives sample s of that pixel.  RT_FILM_CENTER and RT_FILM_UNIFORM only:
+ * RT_FILM_STRATIFIED is RT_ERR_INVALID_ARGUMENT (a ragged pass has no k x k).  Every other record of [0, capacity) — from listed on, or of
+ * a pixel the frame does not have — gets NaN for both offsets; a NaN dx is covered by no one, as in rt_film_splat.
+ * Checked in this order: a null frame; a bad frame; a stratified, then an unknown pattern; 2^32 pixels or capacity >= 2^32
+ * (RT_ERR_UNSUPPORTED); capacity == 0 is RT_OK and launches nothing; a null pointer.
+ *
+ * rt_camera_rays_listed.  For j < listed with pixel[j] in range: rays[j] = rt_camera_rays_offset's record of that pixel through
+ * (x + offsets[2 j], y + offsets[2 j + 1]) (one function serves both).  Every other record of [0, capacity) is the all-zero ray — the
+ * record rt_tree_gather writes for an absent candidate — so a fixed-size rt_trace_rays(capacity) in a captured graph is defined; what
+ * it returns for those records is never read by rt_film_splat_listed.  Checked in this order: a null camera or frame; a bad frame; 2^32
+ * pixels or capacity >= 2^32 (RT_ERR_UNSUPPORTED); capacity == 0 is RT_OK; a null pointer.
+ *
+ * rt_film_splat_listed: rt_film_splat on a list.  d_samples (3 f32), d_valid (1 u8, or NULL), d_offsets (2 f32) hold one record per
+ * listed sample, [0, capacity); d_start is rt_sample_list's; max_count (1 .. RT_SAMPLE_MAX) is the host's bound on a pixel's count.
+ * With lo_q = min(start_q, capacity), hi_q = min(start_(q+1), capacity) and count_q = hi_q > lo_q ? hi_q - lo_q : 0 — so a d_start that
+ * decreases or exceeds capacity never causes a read outside [0, capacity) — for output pixel (r, c), reach = (int)ceilf(radius + 0.5f):
+ *     for s = 0 .. max_count - 1:                    (outermost)
+ *       for dr = -reach .. reach:  for dc = -reach .. reach:          (ascending)
+ *         q = (r + dr, c + dc); skipped when outside the image, when s >= count_q, or when d_valid[lo_q + s] == 0
+ *         then rt_film_splat's support test, weight and sums on record lo_q + s
+ * d_sum and d_weight are read, updated and written in place by one thread per output pixel.  Samples of a pixel beyond max_count are not
+ * applied.  Two kernel forms, the plain gather and a 16 x 16 LDS tile that skips an s no pixel of its halo has, chosen by
+ * RT_AMD_FILM_SPLAT_FORM as for rt_film_splat: same bits.
+ * Consequences: with every count equal to spp the result is rt_film_splat's bit for bit (the records are the same samples, merely laid
+ * out pixel-major); with a box of radius 0.5, centre offsets and count 1 it is rt_accumulate_device's.
+ * Checked in this order: an unknown filter; a radius outside 0 < radius <= 4; max_count outside 1 .. RT_SAMPLE_MAX (RT_ERR_INVALID_ARGUMENT);
+ * rows * cols >= 2^32 or capacity >= 2^32 (RT_ERR_UNSUPPORTED); rows == 0 or cols == 0 is RT_OK and launches nothing; a null start, sum or
+ * weight; capacity != 0 and a null sample or offset pointer.
+ * RT_AMD_DIAG_ADAPTIVE_MAX_GROUPS (rt_set_option): a test hook, every kernel of this block launches at most this many workgroups and takes
+ * the rest grid-stride; same bits.
+ * Not covered: banded frames and rt_multi_* forms; stratified or low-discrepancy ragged patterns; a budget normalised to a fixed total;
+ * _host forms (host buffers through the device); adaptive depth-of-field epochs, whose generators are per pixel, not per sample. */
+
+#define RT_SAMPLE_MAX 64u    /* the most samples one pixel may take in one list */
+
+typedef struct rt_sample_budget_params {
+    float gain;               /* samples per unit of relative standard error; >= 0 */
+    float epsilon;            /* added to |mean|; > 0 */
+    uint32_t min_count;       /* min_count <= max_count <= RT_SAMPLE_MAX */
+    uint32_t max_count;
+    uint32_t flags;           /* reserved: 0 */
+} rt_sample_budget_params;   /* 20 bytes */
+
+int rt_sample_budget(const float *d_mean, uint32_t mean_stride, const float *d_variance, uint32_t variance_stride,
+                     const uint32_t *d_count /* or NULL */, uint32_t count_stride, const uint32_t *d_valid /* or NULL */, uint32_t valid_stride,
+                     const rt_sample_budget_params *params, size_t n, uint32_t *d_budget, void *hip_stream);
+size_t rt_sample_list_temp_bytes(size_t n);
+int rt_sample_list(const uint32_t *d_counts, size_t n, size_t capacity, uint32_t *d_first /* or NULL */, uint32_t *d_start, uint32_t *d_pixel,
+                   uint32_t *d_sample, uint32_t *d_total, void *d_temp, size_t temp_bytes, void *hip_stream);
+int rt_film_offsets_listed(const rt_frame *frame, uint32_t pattern, uint32_t seed, const uint32_t *d_pixel, const uint32_t *d_sample,
+                           const uint32_t *d_total, size_t capacity, float *d_offsets, void *hip_stream);
+int rt_camera_rays_listed(const rt_camera *camera, const rt_frame *frame, const float *d_offsets, const uint32_t *d_pixel, const uint32_t *d_total,
+                          size_t capacity, rt_ray *d_rays, void *hip_stream);
+int rt_film_splat_listed(uint32_t rows, uint32_t cols, const float *d_samples, const unsigned char *d_valid, const float *d_offsets,
+                         const uint32_t *d_start, size_t capacity, uint32_t max_count, uint32_t filter, float radius, float *d_sum,
+                         float *d_weight, void *hip_stream);
+
 /* ---- denoise queries: an edge-avoiding A-Trous filter on guide planes ------------------------------
 
  * What turns the noisy image of a few stochastic epochs into a clean one on the device: the edge-avoiding A-Trous wavelet filter
@@ -1548,7 +1658,7 @@ int rt_svgf_atrous_host(const float *h_color, uint32_t color_stride, const float
  * RT_AMD_DIST_BY_COST, RT_AMD_DIST_OWN_FIRST, RT_AMD_DIST_PREP_FIRST, RT_AMD_DIST_SPLIT, RT_AMD_DIAG_WS_REFUSE,
  * RT_AMD_MULTI_FORCE_STAGE, RT_AMD_BFS_WALK_TRIANGLES (read by rt_scene_create), RT_AMD_WF_SHARE, RT_AMD_DIAG_BFS_CAP,
  * RT_AMD_DIAG_DIST_BAND_RAYS, RT_AMD_QUERY_WAVE_UNIFORM, RT_AMD_DIAG_HIT_BAND_RECORDS, RT_AMD_FILM_SPLAT_FORM, RT_AMD_DIAG_FILM_MAX_GROUPS,
- * RT_AMD_DENOISE_FORM, RT_AMD_DIAG_DENOISE_MAX_GROUPS, RT_AMD_DIAG_TEMPORAL_MAX_GROUPS, RT_AMD_SVGF_FORM, RT_AMD_DIAG_SVGF_MAX_GROUPS, RT_AMD_DIAG_MOTION_MAX_GROUPS, RT_AMD_DIAG_RECTIFY_MAX_GROUPS (INTEGRATION.md says what each does); any other name is RT_ERR_INVALID_ARGUMENT.  The environment is read ONCE per process, at the first use;
+ * RT_AMD_DENOISE_FORM, RT_AMD_DIAG_DENOISE_MAX_GROUPS, RT_AMD_DIAG_TEMPORAL_MAX_GROUPS, RT_AMD_SVGF_FORM, RT_AMD_DIAG_SVGF_MAX_GROUPS, RT_AMD_DIAG_MOTION_MAX_GROUPS, RT_AMD_DIAG_RECTIFY_MAX_GROUPS, RT_AMD_DIAG_ADAPTIVE_MAX_GROUPS (INTEGRATION.md says what each does); any other name is RT_ERR_INVALID_ARGUMENT.  The environment is read ONCE per process, at the first use;
  * after that only this call changes a switch: value = decimal integer, NULL or "" = unset (the library's own choice).  Render
  * calls read the switches without locks: set them between calls, not during one. */
 int rt_set_option(const char *name, const char *value);

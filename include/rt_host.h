@@ -134,6 +134,23 @@ int rt_temporal_accumulate_bounded_cpu(const float *color, const float *motion, 
 int rt_temporal_feedback_cpu(const float *color, uint32_t color_stride, const uint32_t *valid, uint32_t valid_stride, uint32_t rows,
                              uint32_t cols, rt_temporal_pixel *history);
 
+/* The adaptive sampling queries' CPU definition (include/rt_amd.h "adaptive sampling queries" states every operation and the order): plain
+ * loops over host arrays, no device needed, bit-identical to rt_sample_budget / rt_sample_list / rt_film_offsets_listed /
+ * rt_camera_rays_listed / rt_film_splat_listed of librt_amd.so.  Same arguments without the stream (and, for the list, without the
+ * scratch), same checks with the same messages; a failure returns a negative rt_status and sets rt_host_last_error().  Called _cpu for
+ * the reason rt_denoise_atrous_cpu is. */
+int rt_sample_budget_cpu(const float *mean, uint32_t mean_stride, const float *variance, uint32_t variance_stride, const uint32_t *count,
+                         uint32_t count_stride, const uint32_t *valid, uint32_t valid_stride, const rt_sample_budget_params *params, size_t n,
+                         uint32_t *budget);
+int rt_sample_list_cpu(const uint32_t *counts, size_t n, size_t capacity, uint32_t *first, uint32_t *start, uint32_t *pixel, uint32_t *sample,
+                       uint32_t *total);
+int rt_film_offsets_listed_cpu(const rt_frame *frame, uint32_t pattern, uint32_t seed, const uint32_t *pixel, const uint32_t *sample,
+                               const uint32_t *total, size_t capacity, float *offsets);
+int rt_camera_rays_listed_cpu(const rt_camera *camera, const rt_frame *frame, const float *offsets, const uint32_t *pixel, const uint32_t *total,
+                              size_t capacity, rt_ray *rays);
+int rt_film_splat_listed_cpu(uint32_t rows, uint32_t cols, const float *samples, const uint8_t *valid, const float *offsets, const uint32_t *start,
+                             size_t capacity, uint32_t max_count, uint32_t filter, float radius, float *sum, float *weight);
+
 /* The motion queries' CPU definition (include/rt_amd.h "motion queries" states every operation and the order): a plain loop over host
  * arrays, no device needed, bit-identical to rt_previous_positions of librt_amd.so.  `now` is the description of the scene as it stands
  * (what the hits were cast on); was_triangles holds 9 f32 per triangle — the kept x y z of vertices 0, 1, 2 — and was_spheres 4 per
