@@ -540,13 +540,14 @@ int rt_film_offsets_host(const rt_frame *frame, uint32_t spp, uint32_t pattern, 
     const char *bad = rt::film_offsets_limits(frame, spp, pattern, &unsupported);
     if (bad) return fail(unsupported ? RT_ERR_UNSUPPORTED : RT_ERR_INVALID_ARGUMENT, std::string("rt_film_offsets_host: ") + bad);
     if (!offsets) return fail(RT_ERR_INVALID_ARGUMENT, "rt_film_offsets_host: null offset pointer");
-    const uint32_t cols = frame->x1 - frame->x0, rows = (uint32_t)(rt::film_frame_pixels(frame) / cols), k = rt::film_strata(spp);
-    const size_t n_pixels = (size_t)rows * cols;
+    const rt::FilmTile t = rt::film_tile(frame);
+    const uint32_t k = rt::film_strata(spp);
+    const size_t n_pixels = (size_t)t.rows * t.cols;
     for (uint32_t s = 0; s < spp; ++s)
-        for (uint32_t row = 0; row < rows; ++row)
-            for (uint32_t col = 0; col < cols; ++col) {
-                const uint32_t pixel = (frame->y0 + row * frame->y_step) * frame->width + (frame->x0 + col);
-                float *o = offsets + 2u * ((size_t)s * n_pixels + (size_t)row * cols + col);
+        for (uint32_t row = 0; row < t.rows; ++row)
+            for (uint32_t col = 0; col < t.cols; ++col) {
+                const uint32_t pixel = rt::film_global_pixel(t, row, col);
+                float *o = offsets + 2u * ((size_t)s * n_pixels + (size_t)row * t.cols + col);
                 o[0] = rt::film_offset(pattern, k, pixel, seed, s, 0u);
                 o[1] = rt::film_offset(pattern, k, pixel, seed, s, 1u);
             }
@@ -559,31 +560,7 @@ int rt_film_splat_host(uint32_t rows, uint32_t cols, const float *samples, const
     if (bad) return fail(RT_ERR_INVALID_ARGUMENT, std::string("rt_film_splat_host: ") + bad);
     if (rows == 0u || cols == 0u) return RT_OK;
     if (!samples || !offsets || !sum || !weight) return fail(RT_ERR_INVALID_ARGUMENT, "rt_film_splat_host: null sample, offset, sum or weight pointer");
-    const size_t n = (size_t)rows * cols;
-    const int reach = rt::film_reach(radius);
-    for (uint32_t r = 0; r < rows; ++r)
-        for (uint32_t c = 0; c < cols; ++c) {
-            const size_t i = (size_t)r * cols + c;
-            rt::FilmAcc a = {sum[3 * i], sum[3 * i + 1], sum[3 * i + 2], weight[i]};
-            for (uint32_t s = 0; s < spp; ++s)
-                for (int dr = -reach; dr <= reach; ++dr) {
-                    const int64_t qr = (int64_t)r + dr;
-                    if (qr < 0 || qr >= (int64_t)rows) continue;
-                    for (int dc = -reach; dc <= reach; ++dc) {
-                        const int64_t qc = (int64_t)c + dc;
-                        if (qc < 0 || qc >= (int64_t)cols) continue;
-                        const size_t rec = (size_t)s * n + (size_t)qr * cols + (size_t)qc;
-                        if (valid && !valid[rec]) continue;
-                        float ddx, ddy;
-                        if (!rt::film_covers(dr, dc, offsets[2 * rec], offsets[2 * rec + 1], radius, &ddx, &ddy)) continue;
-                        rt::film_apply(a, filter, radius, ddx, ddy, samples[3 * rec], samples[3 * rec + 1], samples[3 * rec + 2]);
-                    }
-                }
-            sum[3 * i] = a.s0;
-            sum[3 * i + 1] = a.s1;
-            sum[3 * i + 2] = a.s2;
-            weight[i] = a.w;
-        }
+    rt::film_splat_cpu<rt::UniformLayout>({{samples, valid, offsets, (uint64_t)rows * cols, spp}, sum, weight, rows, cols, filter, radius});
     return RT_OK;
 }
 
@@ -628,7 +605,7 @@ int rt_film_offsets_listed_cpu(const rt_frame *frame, uint32_t pattern, uint32_t
     const char *bad = rt::listed_offsets_limits(frame, pattern, pixel, sample, total, capacity, offsets, &status);
     if (bad) return fail(status, std::string("rt_film_offsets_listed_cpu: ") + bad);
     if (capacity == 0u) return RT_OK;
-    const rt::ListedOffsets o = {rt::listed_tile(frame), pattern, seed, pixel, sample, total, capacity, offsets};
+    const rt::ListedOffsets o = {rt::film_tile(frame), pattern, seed, pixel, sample, total, capacity, offsets};
     const uint64_t listed = rt::listed_count(total, capacity);
     for (uint64_t j = 0; j < capacity; ++j) rt::listed_offsets_record(o, j, listed);
     return RT_OK;
@@ -640,7 +617,7 @@ int rt_camera_rays_listed_cpu(const rt_camera *camera, const rt_frame *frame, co
     const char *bad = rt::listed_rays_limits(camera, frame, offsets, pixel, total, capacity, rays, &status);
     if (bad) return fail(status, std::string("rt_camera_rays_listed_cpu: ") + bad);
     if (capacity == 0u) return RT_OK;
-    const rt::ListedCamera c = {rt::temporal_camera(camera, frame), rt::listed_tile(frame)};
+    const rt::ListedCamera c = {rt::temporal_camera(camera, frame), rt::film_tile(frame)};
     const uint64_t listed = rt::listed_count(total, capacity), n_pixels = (uint64_t)c.t.rows * c.t.cols;
     for (uint64_t j = 0; j < capacity; ++j) {
         uint32_t w[11] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
@@ -661,10 +638,7 @@ int rt_film_splat_listed_cpu(uint32_t rows, uint32_t cols, const float *samples,
     const char *bad = rt::listed_splat_limits(rows, cols, samples, offsets, start, capacity, max_count, filter, radius, sum, weight, &status);
     if (bad) return fail(status, std::string("rt_film_splat_listed_cpu: ") + bad);
     if (rows == 0u || cols == 0u) return RT_OK;
-    const rt::ListedSplat p = {samples, valid, offsets, start, sum, weight, capacity, rows, cols, max_count, filter, radius};
-    for (uint32_t r = 0; r < rows; ++r)
-        for (uint32_t c = 0; c < cols; ++c)
-            rt::listed_splat_pixel(p, r, c, [&](rt::FilmAcc &a, float ddx, float ddy, float p0, float p1, float p2) { rt::film_apply(a, filter, radius, ddx, ddy, p0, p1, p2); });
+    rt::film_splat_cpu<rt::ListedLayout>({{samples, valid, offsets, start, capacity, max_count}, sum, weight, rows, cols, filter, radius});
     return RT_OK;
 }
 

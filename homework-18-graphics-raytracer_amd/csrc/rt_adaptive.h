@@ -3,8 +3,9 @@
  * host (librt_host.so: rt_sample_budget_cpu / rt_sample_list_cpu / rt_film_offsets_listed_cpu / rt_camera_rays_listed_cpu /
  * rt_film_splat_listed_cpu) and the device (rt_adaptive_query.hip).  Every function is a sequence of single f32 or u32 operations in
  * the order the header comment of the block gives; both libraries are built with -ffp-contract=off, divide and square root are
- * correctly rounded on either side, so host and device agree bit for bit.  The sample positions, the support test and the filter are
- * rt_film.h's, unchanged: film_u / film_offset, film_reach, film_covers, film_apply, FilmAcc.
+ * correctly rounded on either side, so host and device agree bit for bit.  The sample positions, the tile, the filter and the whole
+ * splat walk are rt_film.h's: film_u / film_offset, FilmTile, film_splat_pixel.  The listed splat adds one thing, ListedLayout: where
+ * the samples of a source pixel lie in a pixel-major list.
  *
  * listed_ray_words restates rt_primary_ray.h's primary_ray_through for the CPU form (that header is device code on rt_cast.h); the
  * device kernel calls primary_ray_through itself, and the tests hold the two against each other.
@@ -16,8 +17,6 @@
 #include "rt_temporal.h"
 
 namespace rt {
-
-#define RT_LISTED_NAN 0x7fc00000u
 
 /* ---- rt_sample_budget ---- */
 
@@ -94,18 +93,8 @@ inline const char *sample_list_limits(const uint32_t *counts, uint64_t n, uint64
 
 /* ---- rt_film_offsets_listed / rt_camera_rays_listed ---- */
 
-/* what a listed pixel needs of a frame or tile: the compact pixel p = row * cols + col has the global index (y0 + row * y_step) * width +
- * (x0 + col), as film_offsets_kernel computes it */
-struct ListedTile {
-    uint32_t cols, rows, x0, y0, y_step, width;
-};
-inline ListedTile listed_tile(const rt_frame *f) {
-    const uint32_t cols = f->x1 - f->x0;
-    return {cols, (uint32_t)(film_frame_pixels(f) / cols), f->x0, f->y0, f->y_step, f->width};
-}
-
 struct ListedOffsets {
-    ListedTile t;
+    FilmTile t;
     uint32_t pattern, seed;
     const uint32_t *pixel, *sample, *total;
     uint64_t capacity;
@@ -117,12 +106,12 @@ RT_FILM_HD uint64_t listed_count(const uint32_t *total, uint64_t capacity) { ret
 /* record j of the offsets; listed: listed_count(total, capacity) */
 RT_FILM_HD void listed_offsets_record(const ListedOffsets &o, uint64_t j, uint64_t listed) {
     uint32_t *out = reinterpret_cast<uint32_t *>(o.offsets) + 2u * j;
-    out[0] = RT_LISTED_NAN, out[1] = RT_LISTED_NAN;
+    out[0] = RT_FILM_NAN, out[1] = RT_FILM_NAN;
     if (j >= listed) return;
     const uint32_t pix = o.pixel[j];
     if ((uint64_t)pix >= (uint64_t)o.t.rows * o.t.cols) return;
     const uint32_t row = pix / o.t.cols, col = pix - row * o.t.cols;
-    const uint32_t global = (o.t.y0 + row * o.t.y_step) * o.t.width + (o.t.x0 + col);
+    const uint32_t global = film_global_pixel(o.t, row, col);
     const uint32_t s = o.sample[j];
     o.offsets[2u * j] = film_offset(o.pattern, 0u, global, o.seed, s, 0u);
     o.offsets[2u * j + 1u] = film_offset(o.pattern, 0u, global, o.seed, s, 1u);
@@ -148,7 +137,7 @@ inline const char *listed_offsets_limits(const rt_frame *frame, uint32_t pattern
 /* the camera of a listed ray: make_kernel_frame's fields (rt_temporal.h temporal_camera) and the tile */
 struct ListedCamera {
     TemporalCamera cam;
-    ListedTile t;
+    FilmTile t;
 };
 
 /* primary_ray_through (rt_primary_ray.h) and store_primary_ray as the eleven words of an rt_ray, for the CPU form */
@@ -178,52 +167,27 @@ inline const char *listed_rays_limits(const rt_camera *camera, const rt_frame *f
 
 /* ---- rt_film_splat_listed ---- */
 
-struct ListedSplat {
+/* the records of source pixel q of a list: [*lo, *lo + the return value), always inside [0, capacity) whatever `start` holds */
+RT_FILM_HD uint32_t listed_range(const uint32_t *start, uint64_t capacity, uint64_t q, uint64_t *lo) {
+    const uint64_t a = (uint64_t)start[q] < capacity ? (uint64_t)start[q] : capacity;
+    const uint64_t b = (uint64_t)start[q + 1u] < capacity ? (uint64_t)start[q + 1u] : capacity;
+    *lo = a;
+    return b > a ? (uint32_t)(b - a) : 0u;
+}
+
+/* the pixel-major list as a layout of rt_film.h's walk (film_splat_pixel) and of rt_film_splat_kernel.h's tiled kernel */
+struct ListedLayout {
+    static constexpr bool ragged = true;
     const float *samples;
     const unsigned char *valid; /* may be null */
     const float *offsets;
     const uint32_t *start;
-    float *sum, *weight;
     uint64_t capacity;
-    uint32_t rows, cols, max_count, filter;
-    float radius;
+    uint32_t max_count;
+    RT_FILM_HD uint32_t s_end() const { return max_count; }
+    RT_FILM_HD uint32_t range(uint64_t q, uint64_t *lo) const { return listed_range(start, capacity, q, lo); }
+    RT_FILM_HD uint64_t record(uint64_t lo, uint32_t s) const { return lo + s; }
 };
-
-/* the records of source pixel q: [*lo, *lo + the return value), always inside [0, capacity) whatever `start` holds */
-RT_FILM_HD uint32_t listed_range(const ListedSplat &p, uint64_t q, uint32_t *lo) {
-    const uint64_t a = (uint64_t)p.start[q] < p.capacity ? (uint64_t)p.start[q] : p.capacity;
-    const uint64_t b = (uint64_t)p.start[q + 1u] < p.capacity ? (uint64_t)p.start[q + 1u] : p.capacity;
-    *lo = (uint32_t)a;
-    return b > a ? (uint32_t)(b - a) : 0u;
-}
-
-/* output pixel (r, c): the walk of the definition straight from the arrays (the CPU form and the plain kernel) */
-template <class Apply>
-RT_FILM_HD void listed_splat_pixel(const ListedSplat &p, uint32_t r, uint32_t c, Apply apply) {
-    const uint64_t i = (uint64_t)r * p.cols + c;
-    const int reach = film_reach(p.radius);
-    FilmAcc a = {p.sum[3u * i], p.sum[3u * i + 1u], p.sum[3u * i + 2u], p.weight[i]};
-    for (uint32_t s = 0; s < p.max_count; ++s)
-        for (int dr = -reach; dr <= reach; ++dr) {
-            const int64_t qr = (int64_t)r + dr;
-            if (qr < 0 || qr >= (int64_t)p.rows) continue;
-            for (int dc = -reach; dc <= reach; ++dc) {
-                const int64_t qc = (int64_t)c + dc;
-                if (qc < 0 || qc >= (int64_t)p.cols) continue;
-                uint32_t lo;
-                if (s >= listed_range(p, (uint64_t)qr * p.cols + (uint64_t)qc, &lo)) continue;
-                const uint64_t rec = (uint64_t)lo + s;
-                if (p.valid != nullptr && p.valid[rec] == 0u) continue;
-                float ddx, ddy;
-                if (!film_covers(dr, dc, p.offsets[2u * rec], p.offsets[2u * rec + 1u], p.radius, &ddx, &ddy)) continue;
-                apply(a, ddx, ddy, p.samples[3u * rec], p.samples[3u * rec + 1u], p.samples[3u * rec + 2u]);
-            }
-        }
-    p.sum[3u * i] = a.s0;
-    p.sum[3u * i + 1u] = a.s1;
-    p.sum[3u * i + 2u] = a.s2;
-    p.weight[i] = a.w;
-}
 
 inline const char *listed_splat_limits(uint64_t rows, uint64_t cols, const float *samples, const float *offsets, const uint32_t *start, uint64_t capacity,
                                        uint32_t max_count, uint32_t filter, float radius, const float *sum, const float *weight, int *status) {

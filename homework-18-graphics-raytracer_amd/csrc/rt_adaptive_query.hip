@@ -15,20 +15,17 @@
  *                                   reads.  So the stores to d_pixel and d_sample are coalesced whatever the counts are, and a pixel with
  *                                   64 samples costs its neighbours' lanes nothing.  block_total <= 256 * 64 = 16 384.
  *   rt::offsets_listed_kernel       one thread per record of [0, capacity), grid-stride: rt_adaptive.h's listed_offsets_record
- *   rt::camera_rays_listed_kernel   one thread per record: rt_primary_ray.h's primary_ray_through, or the all-zero ray
- *   rt::splat_listed_kernel<FILTER>        the splat as a gather, one thread per output pixel: rt_adaptive.h's listed_splat_pixel
- *   rt::splat_listed_tiled_kernel<FILTER>  the same gather from LDS: a workgroup owns a 16 x 16 tile, stages the halo's record ranges once
- *                                   per tile and, per sample index s, the halo's offsets and samples; an s that no pixel of the halo has is
- *                                   skipped (it would contribute to nobody)
+ *   rt::camera_rays_listed_kernel   one thread per record: rt_primary_ray.h's primary_ray_offset, or the all-zero ray
+ *   the splat                       rt_film_splat_kernel.h's two forms, the kernels of rt_film_splat, instantiated for rt_adaptive.h's
+ *                                   ListedLayout (record lo_q + s for s < count_q); that header says what a ragged layout adds to them
  *
  * Everything the list kernels compute is u32 arithmetic on sums below 2^32 (n * RT_SAMPLE_MAX < 2^32 is checked by the entry point), so
- * the result cannot depend on the launch geometry: there is no atomic and no order to decide.  Both splat kernels walk a pixel's sources
- * in the order of the definition — s outermost, then dr, then dc, ascending — and call film_covers / film_apply on the same operands.
- * A record index is clamped into [0, capacity) before anything is read through it (listed_range).  Every loop that holds a barrier is
- * workgroup-uniform.
+ * the result cannot depend on the launch geometry: there is no atomic and no order to decide.  A record index is clamped into
+ * [0, capacity) before anything is read through it (listed_range).  Every loop that holds a barrier is workgroup-uniform.
  */
 #include "rt_api_internal.h"
 #include "rt_adaptive.h"
+#include "rt_film_splat_kernel.h"
 #include "rt_primary_ray.h"
 
 namespace rt {
@@ -175,105 +172,7 @@ __global__ __launch_bounds__(RT_ADAPTIVE_THREADS) void camera_rays_listed_kernel
             for (int k = 0; k < 11; ++k) o[k] = 0u;
             continue;
         }
-        const uint32_t row = pix / fr.cols, col = pix - row * fr.cols;
-        const uint32_t x = fr.x0 + col, y = fr.y0 + row * fr.y_step;
-        store_primary_ray(primary_ray_through(fr, (float)x + offsets[2u * j], (float)y + offsets[2u * j + 1u]), rays + j);
-    }
-}
-
-/* ---- the splat ---- */
-
-template <uint32_t FILTER>
-__global__ __launch_bounds__(RT_ADAPTIVE_THREADS) void splat_listed_kernel(const ListedSplat p) {
-    const uint64_t n = (uint64_t)p.rows * p.cols, stride = (uint64_t)gridDim.x * RT_ADAPTIVE_THREADS;
-    for (uint64_t i = (uint64_t)blockIdx.x * RT_ADAPTIVE_THREADS + threadIdx.x; i < n; i += stride) {
-        const uint32_t r = (uint32_t)(i / p.cols), c = (uint32_t)(i - (uint64_t)r * p.cols);
-        listed_splat_pixel(p, r, c, [&](FilmAcc &a, float ddx, float ddy, float p0, float p1, float p2) { film_apply(a, FILTER, p.radius, ddx, ddy, p0, p1, p2); });
-    }
-}
-
-/* 256 threads = a 16 x 16 tile; the halo is (16 + 2 reach) entries wide, reach <= 5 (radius <= 4): at most 676 entries of 7 words, 18.5 KB
- * of LDS.  Entry e of the halo is staged by thread e, e + 256, ...: consecutive threads read consecutive pixels of an image row, whose
- * records are adjacent in a pixel-major list. */
-#define RT_LISTED_TILE 16u
-#define RT_LISTED_HALO_MAX (RT_LISTED_TILE + 2u * 5u)
-template <uint32_t FILTER>
-__global__ __launch_bounds__(RT_ADAPTIVE_THREADS) void splat_listed_tiled_kernel(const ListedSplat p, const uint32_t tiles_x, const uint64_t n_tiles) {
-    __shared__ float2 l_off[RT_LISTED_HALO_MAX * RT_LISTED_HALO_MAX];
-    __shared__ float l_smp[RT_LISTED_HALO_MAX * RT_LISTED_HALO_MAX * 3u];
-    __shared__ uint32_t l_lo[RT_LISTED_HALO_MAX * RT_LISTED_HALO_MAX], l_cnt[RT_LISTED_HALO_MAX * RT_LISTED_HALO_MAX];
-    __shared__ uint32_t l_max[RT_ADAPTIVE_WAVES];
-    const int reach = film_reach(p.radius);
-    const uint32_t halo = RT_LISTED_TILE + 2u * (uint32_t)reach; /* <= RT_LISTED_HALO_MAX: the entry point bounds the radius */
-    const uint32_t ty = threadIdx.x / RT_LISTED_TILE, tx = threadIdx.x % RT_LISTED_TILE;
-    for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) { /* workgroup-uniform */
-        const uint32_t tile_r = (uint32_t)(tile / tiles_x), tile_c = (uint32_t)(tile - (uint64_t)tile_r * tiles_x);
-        const int64_t r0 = (int64_t)tile_r * RT_LISTED_TILE, c0 = (int64_t)tile_c * RT_LISTED_TILE;
-        const int64_t r = r0 + ty, c = c0 + tx;
-        const bool inside = r < (int64_t)p.rows && c < (int64_t)p.cols;
-        const uint64_t i = inside ? (uint64_t)r * p.cols + (uint64_t)c : 0u;
-        FilmAcc a = {0.0f, 0.0f, 0.0f, 0.0f};
-        if (inside) a = {p.sum[3u * i], p.sum[3u * i + 1u], p.sum[3u * i + 2u], p.weight[i]};
-        __syncthreads(); /* the previous tile's reads are done */
-        uint32_t most = 0u;
-        for (uint32_t e = threadIdx.x; e < halo * halo; e += RT_ADAPTIVE_THREADS) { /* the halo's record ranges, once per tile */
-            const uint32_t hr = e / halo, hc = e - hr * halo;
-            const int64_t qr = r0 - reach + hr, qc = c0 - reach + hc;
-            uint32_t lo = 0u, cnt = 0u;
-            if (qr >= 0 && qr < (int64_t)p.rows && qc >= 0 && qc < (int64_t)p.cols) cnt = listed_range(p, (uint64_t)qr * p.cols + (uint64_t)qc, &lo);
-            l_lo[e] = lo;
-            l_cnt[e] = cnt;
-            most = cnt > most ? cnt : most;
-        }
-        for (int off = 32; off > 0; off >>= 1) {
-            const uint32_t other = __shfl_down(most, off, 64);
-            most = other > most ? other : most;
-        }
-        if ((threadIdx.x & 63u) == 0u) l_max[threadIdx.x >> 6] = most;
-        __syncthreads();
-        most = 0u;
-#pragma unroll
-        for (uint32_t w = 0; w < RT_ADAPTIVE_WAVES; ++w) most = l_max[w] > most ? l_max[w] : most;
-        const uint32_t s_end = most < p.max_count ? most : p.max_count; /* workgroup-uniform: an s at or beyond it has no source in the halo */
-        for (uint32_t s = 0; s < s_end; ++s) {
-            __syncthreads(); /* the previous sample's reads are done */
-            for (uint32_t e = threadIdx.x; e < halo * halo; e += RT_ADAPTIVE_THREADS) {
-                float2 off = make_float2(__uint_as_float(RT_LISTED_NAN), 0.0f); /* NaN dx: contributes to nobody */
-                float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
-                if (s < l_cnt[e]) {
-                    const uint64_t rec = (uint64_t)l_lo[e] + s;
-                    if (p.valid == nullptr || p.valid[rec] != 0u) {
-                        off = make_float2(p.offsets[2u * rec], p.offsets[2u * rec + 1u]);
-                        s0 = p.samples[3u * rec];
-                        s1 = p.samples[3u * rec + 1u];
-                        s2 = p.samples[3u * rec + 2u];
-                    }
-                }
-                l_off[e] = off;
-                l_smp[3u * e] = s0;
-                l_smp[3u * e + 1u] = s1;
-                l_smp[3u * e + 2u] = s2;
-            }
-            __syncthreads();
-            if (inside) {
-                for (int dr = -reach; dr <= reach; ++dr) {
-                    const uint32_t row_e = (uint32_t)((int)ty + reach + dr) * halo + (uint32_t)((int)tx + reach);
-                    for (int dc = -reach; dc <= reach; ++dc) {
-                        const uint32_t e = (uint32_t)((int)row_e + dc);
-                        const float2 off = l_off[e];
-                        float ddx, ddy;
-                        if (!film_covers(dr, dc, off.x, off.y, p.radius, &ddx, &ddy)) continue;
-                        film_apply(a, FILTER, p.radius, ddx, ddy, l_smp[3u * e], l_smp[3u * e + 1u], l_smp[3u * e + 2u]);
-                    }
-                }
-            }
-        }
-        if (inside) {
-            p.sum[3u * i] = a.s0;
-            p.sum[3u * i + 1u] = a.s1;
-            p.sum[3u * i + 2u] = a.s2;
-            p.weight[i] = a.w;
-        }
+        store_primary_ray(primary_ray_offset(fr, pix, offsets[2u * j], offsets[2u * j + 1u]), rays + j);
     }
 }
 
@@ -291,24 +190,6 @@ static hipError_t launch_sample_list(const uint32_t *counts, uint64_t n, uint64_
     hipLaunchKernelGGL(sample_totals_kernel, grid, block, 0, stream, counts, n, steps, totals);
     hipLaunchKernelGGL(sample_scan_kernel, dim3(1), block, 0, stream, totals, steps, n, capacity, start, total);
     hipLaunchKernelGGL(sample_expand_kernel, grid, block, 0, stream, counts, n, steps, totals, capacity, first, start, pixel, sample);
-    return hipGetLastError();
-}
-
-template <uint32_t FILTER>
-static void launch_splat_listed_of(const ListedSplat &p, bool tiled, hipStream_t stream) {
-    if (tiled) {
-        const uint32_t tiles_x = (p.cols + RT_LISTED_TILE - 1u) / RT_LISTED_TILE, tiles_y = (p.rows + RT_LISTED_TILE - 1u) / RT_LISTED_TILE;
-        const uint64_t n_tiles = (uint64_t)tiles_x * tiles_y;
-        hipLaunchKernelGGL(splat_listed_tiled_kernel<FILTER>, dim3(adaptive_groups(n_tiles)), dim3(RT_ADAPTIVE_THREADS), 0, stream, p, tiles_x, n_tiles);
-    } else {
-        hipLaunchKernelGGL(splat_listed_kernel<FILTER>, dim3(adaptive_groups_of((uint64_t)p.rows * p.cols)), dim3(RT_ADAPTIVE_THREADS), 0, stream, p);
-    }
-}
-
-static hipError_t launch_splat_listed(const ListedSplat &p, bool tiled, hipStream_t stream) {
-    if (p.filter == RT_FILM_BOX) launch_splat_listed_of<RT_FILM_BOX>(p, tiled, stream);
-    else if (p.filter == RT_FILM_TENT) launch_splat_listed_of<RT_FILM_TENT>(p, tiled, stream);
-    else launch_splat_listed_of<RT_FILM_MITCHELL>(p, tiled, stream);
     return hipGetLastError();
 }
 
@@ -357,7 +238,7 @@ int rt_film_offsets_listed(const rt_frame *frame, uint32_t pattern, uint32_t see
     const char *bad = rt::listed_offsets_limits(frame, pattern, d_pixel, d_sample, d_total, capacity, d_offsets, &status);
     if (bad) return fail(status, std::string("rt_film_offsets_listed: ") + bad);
     if (capacity == 0u) return RT_OK;
-    const rt::ListedOffsets o = {rt::listed_tile(frame), pattern, seed, d_pixel, d_sample, d_total, capacity, d_offsets};
+    const rt::ListedOffsets o = {rt::film_tile(frame), pattern, seed, d_pixel, d_sample, d_total, capacity, d_offsets};
     hipLaunchKernelGGL(rt::offsets_listed_kernel, dim3(rt::adaptive_groups_of(capacity)), dim3(RT_ADAPTIVE_THREADS), 0, static_cast<hipStream_t>(hip_stream), o);
     return launched("rt_film_offsets_listed");
 }
@@ -384,9 +265,10 @@ int rt_film_splat_listed(uint32_t rows, uint32_t cols, const float *d_samples, c
     const char *bad = rt::listed_splat_limits(rows, cols, d_samples, d_offsets, d_start, capacity, max_count, filter, radius, d_sum, d_weight, &status);
     if (bad) return fail(status, std::string("rt_film_splat_listed: ") + bad);
     if (rows == 0u || cols == 0u) return RT_OK;
-    const rt::ListedSplat p = {d_samples, d_valid, d_offsets, d_start, d_sum, d_weight, capacity, rows, cols, max_count, filter, radius};
+    const rt::FilmSplat<rt::ListedLayout> p = {{d_samples, d_valid, d_offsets, d_start, capacity, max_count}, d_sum, d_weight, rows, cols, filter, radius};
     const bool tiled = rt::option(rt::OPT_FILM_SPLAT_FORM, RT_LISTED_SPLAT_FORM_DEFAULT) == 1;
-    return launched("rt_film_splat_listed", rt::launch_splat_listed(p, tiled, static_cast<hipStream_t>(hip_stream)));
+    return launched("rt_film_splat_listed",
+                    rt::launch_film_splat_forms(p, tiled, max_groups(rt::OPT_DIAG_ADAPTIVE_MAX_GROUPS, RT_FILM_MAX_GROUPS), static_cast<hipStream_t>(hip_stream)));
 }
 
 } /* extern "C" */

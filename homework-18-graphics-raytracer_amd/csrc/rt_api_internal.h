@@ -28,7 +28,8 @@
  *   rt_adaptive_query.hip the adaptive sampling queries' rt_sample_budget / rt_sample_list / rt_film_offsets_listed / rt_camera_rays_listed / rt_film_splat_listed: kernels and entry points in one unit
  *   rt_svgf_query.hip    the variance-guided filter queries' rt_svgf_variance / rt_svgf_atrous, their _host forms and rt_svgf_temp_bytes: kernels and entry points in one unit
  * The film queries' kernels are rt_film_query.hip; their entry points are rt_api_query.hip's (rt_camera_rays_offset, beside rt_camera_rays) and
- * rt_api_post.hip's (rt_film_offsets / rt_film_splat, beside the accumulator).
+ * rt_api_post.hip's (rt_film_offsets / rt_film_splat, beside the accumulator).  The two splats, rt_film_query.hip's and
+ * rt_adaptive_query.hip's, instantiate the kernel templates of rt_film_splat_kernel.h, each with its layout (rt_film.h, rt_adaptive.h).
  * The two A-Trous filters, rt_denoise_query.hip and rt_svgf_query.hip, instantiate the kernel templates of rt_atrous_kernel.h, each with
  * its filter (rt_denoise.h, rt_svgf.h) on the shared walk, guide readers and argument checks of rt_atrous.h.
  * The kernel units rt_hit_query.hip and rt_scatter_query.hip include this header for the band loop of their launchers.
@@ -62,6 +63,7 @@
 #include "rt_kernels.h"
 #include "rt_vec.h"
 #include "rt_luma.h"
+#include "rt_film.h"
 
 #define RT_API_HIDDEN __attribute__((visibility("hidden")))
 
@@ -337,25 +339,15 @@ hipError_t launch_level_close(const rt_hit *hits, const uint32_t *type, const fl
 hipError_t launch_level_fold(const uint32_t *type, const float *cosine, const rt_hit *next_hits, const float *factor, const float *shade_next,
                              const float *shade_missed, uint32_t n, float *value, hipStream_t stream);
 hipError_t launch_level_finish(const float *value, uint32_t n, float *accum, unsigned char *valid, hipStream_t stream);
-/* The film queries' kernels (rt_film_query.hip).  FilmTile: what the sample positions need of a frame; FilmSplat: one rt_film_splat call
- * (rows * cols < 2^32 and 0 < radius <= 4, checked by the entry point).  tiled: the LDS form of the splat instead of the simple one (same bits). */
-struct FilmTile {
-    uint32_t cols, rows, x0, y0, y_step, width;
-};
-struct FilmSplat {
-    const float *samples;
-    const unsigned char *valid; /* may be null */
-    const float *offsets;
-    float *sum, *weight;
-    uint32_t rows, cols, spp, filter;
-    float radius;
-};
+/* The film queries' kernels (rt_film_query.hip); FilmTile, FilmSplat and UniformLayout are rt_film.h's, shared with the host.  The splat's
+ * two forms and their launcher are rt_film_splat_kernel.h's, instantiated there for rt_film_splat and in rt_adaptive_query.hip for
+ * rt_film_splat_listed.  tiled: the LDS form of the splat instead of the simple one (same bits). */
 hipError_t launch_film_offsets(const FilmTile &t, uint32_t spp, uint32_t pattern, uint32_t seed, float *offsets, hipStream_t stream);
 hipError_t launch_camera_rays_offset(const KernelFrame &fr, const float *offsets, uint32_t spp, rt_ray *rays, hipStream_t stream);
 /* max_groups: both forms take their pixels or tiles grid-stride beyond this many workgroups, 1 .. RT_FILM_MAX_GROUPS (2^16 x 256 threads
  * stay far below the 2^32 threads a launch may have); a smaller cap changes no bit */
 #define RT_FILM_MAX_GROUPS (1u << 16)
-hipError_t launch_film_splat(const FilmSplat &p, bool tiled, uint32_t max_groups, hipStream_t stream);
+hipError_t launch_film_splat(const FilmSplat<UniformLayout> &p, bool tiled, uint32_t max_groups, hipStream_t stream);
 } /* namespace rt */
 
 /* rt_select_records (rt_api_query.hip) keeps its block totals per (device, stream); rt_post_release (rt_api_post.hip) frees those of a

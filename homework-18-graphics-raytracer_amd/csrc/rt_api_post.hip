@@ -125,8 +125,7 @@ int rt_film_offsets(const rt_frame *frame, uint32_t spp, uint32_t pattern, uint3
     if (bad) return fail(unsupported ? RT_ERR_UNSUPPORTED : RT_ERR_INVALID_ARGUMENT, std::string("rt_film_offsets: ") + bad);
     const int rc = check_pointers("rt_film_offsets", d_offsets != nullptr, "offset");
     if (rc != RT_OK) return rc;
-    const rt::FilmTile t = {frame->x1 - frame->x0, rt_frame_rows(frame), frame->x0, frame->y0, frame->y_step, frame->width};
-    return launched("rt_film_offsets", rt::launch_film_offsets(t, spp, pattern, seed, d_offsets, static_cast<hipStream_t>(hip_stream)));
+    return launched("rt_film_offsets", rt::launch_film_offsets(rt::film_tile(frame), spp, pattern, seed, d_offsets, static_cast<hipStream_t>(hip_stream)));
 }
 
 int rt_film_splat(uint32_t rows, uint32_t cols, const float *d_samples, const unsigned char *d_valid, const float *d_offsets, uint32_t spp,
@@ -136,7 +135,7 @@ int rt_film_splat(uint32_t rows, uint32_t cols, const float *d_samples, const un
     if (rows == 0u || cols == 0u) return RT_OK;
     const int rc = check_pointers("rt_film_splat", d_samples && d_offsets && d_sum && d_weight, "sample, offset, sum or weight");
     if (rc != RT_OK) return rc;
-    const rt::FilmSplat p = {d_samples, d_valid, d_offsets, d_sum, d_weight, rows, cols, spp, filter, radius};
+    const rt::FilmSplat<rt::UniformLayout> p = {{d_samples, d_valid, d_offsets, (uint64_t)rows * cols, spp}, d_sum, d_weight, rows, cols, filter, radius};
     const bool tiled = rt::option(rt::OPT_FILM_SPLAT_FORM, RT_FILM_SPLAT_FORM_DEFAULT) == 1;
     return launched("rt_film_splat", rt::launch_film_splat(p, tiled, max_groups(rt::OPT_DIAG_FILM_MAX_GROUPS, RT_FILM_MAX_GROUPS), static_cast<hipStream_t>(hip_stream)));
 }

@@ -84,11 +84,93 @@ RT_FILM_HD void film_apply(FilmAcc &a, uint32_t filter, float radius, float ddx,
     a.w = a.w + w;
 }
 
+/* ---- the splat: one walk over two layouts ----
+ * A layout says where sample s of source pixel q lives and how many samples q has; everything else of the gather is written once.
+ *   ragged                 a constant: counts differ from pixel to pixel (the tiled kernel then stages the ranges and skips an s nobody has)
+ *   s_end()                no pixel has a sample s at or beyond it
+ *   range(q, &lo)          the samples of q; lo: what record() needs of q, below 2^32 (the tiled kernel keeps it in one LDS word)
+ *   record(lo, s)          the index of sample s < range(q, &lo) in samples / valid / offsets
+ * UniformLayout is rt_film_splat's sample-major record s * n + q; rt_adaptive.h's ListedLayout is the pixel-major list's lo_q + s. */
+struct UniformLayout {
+    static constexpr bool ragged = false;
+    const float *samples;
+    const unsigned char *valid; /* may be null */
+    const float *offsets;
+    uint64_t n; /* rows * cols < 2^32 */
+    uint32_t spp;
+    RT_FILM_HD uint32_t s_end() const { return spp; }
+    RT_FILM_HD uint32_t range(uint64_t q, uint64_t *lo) const {
+        *lo = q;
+        return spp;
+    }
+    RT_FILM_HD uint64_t record(uint64_t lo, uint32_t s) const { return (uint64_t)s * n + lo; }
+};
+
+/* one splat call (0 < radius <= 4 and rows * cols < 2^32, checked by the entry points) */
+template <class Layout>
+struct FilmSplat {
+    Layout layout;
+    float *sum, *weight;
+    uint32_t rows, cols, filter;
+    float radius;
+};
+
+/* a dx that fails the support test of film_covers for every output pixel */
+#define RT_FILM_NAN 0x7fc00000u
+
+/* Output pixel i = r * cols + c: the walk of the definition straight from the arrays — s outermost, then dr, then dc, ascending.  The CPU
+ * forms and the plain kernel; apply(a, ddx, ddy, p0, p1, p2) is film_apply with the caller's filter (a constant in a kernel). */
+template <class Layout, class Apply>
+RT_FILM_HD void film_splat_pixel(const FilmSplat<Layout> &p, uint64_t i, Apply apply) {
+    const Layout &L = p.layout;
+    const uint32_t r = (uint32_t)(i / p.cols), c = (uint32_t)(i - (uint64_t)r * p.cols);
+    const int reach = film_reach(p.radius);
+    FilmAcc a = {p.sum[3u * i], p.sum[3u * i + 1u], p.sum[3u * i + 2u], p.weight[i]};
+    for (uint32_t s = 0; s < L.s_end(); ++s)
+        for (int dr = -reach; dr <= reach; ++dr) {
+            const int64_t qr = (int64_t)r + dr;
+            if (qr < 0 || qr >= (int64_t)p.rows) continue;
+            for (int dc = -reach; dc <= reach; ++dc) {
+                const int64_t qc = (int64_t)c + dc;
+                if (qc < 0 || qc >= (int64_t)p.cols) continue;
+                uint64_t lo;
+                if (s >= L.range((uint64_t)qr * p.cols + (uint64_t)qc, &lo)) continue;
+                const uint64_t rec = L.record(lo, s);
+                if (L.valid != nullptr && L.valid[rec] == 0u) continue;
+                float ddx, ddy;
+                if (!film_covers(dr, dc, L.offsets[2u * rec], L.offsets[2u * rec + 1u], p.radius, &ddx, &ddy)) continue;
+                apply(a, ddx, ddy, L.samples[3u * rec], L.samples[3u * rec + 1u], L.samples[3u * rec + 2u]);
+            }
+        }
+    p.sum[3u * i] = a.s0;
+    p.sum[3u * i + 1u] = a.s1;
+    p.sum[3u * i + 2u] = a.s2;
+    p.weight[i] = a.w;
+}
+
+/* the CPU form of a splat: every output pixel in turn */
+template <class Layout>
+inline void film_splat_cpu(const FilmSplat<Layout> &p) {
+    for (uint64_t i = 0; i < (uint64_t)p.rows * p.cols; ++i)
+        film_splat_pixel(p, i, [&](FilmAcc &a, float ddx, float ddy, float p0, float p1, float p2) { film_apply(a, p.filter, p.radius, ddx, ddy, p0, p1, p2); });
+}
+
 /* the pixels of a frame's tile, or 0 for a frame that is none (include/rt_amd.h rt_frame) */
 inline uint64_t film_frame_pixels(const rt_frame *f) {
     if (!(f && f->width > 0 && f->height > 0 && f->y_step >= 1 && f->x0 < f->x1 && f->y0 < f->y1 && f->x1 <= f->width && f->y1 <= f->height)) return 0u;
     return (((uint64_t)f->y1 - f->y0 + f->y_step - 1u) / f->y_step) * (uint64_t)(f->x1 - f->x0);
 }
+
+/* what a sample position needs of a frame or tile (one that film_frame_pixels accepts): the compact pixel row * cols + col has the
+ * GLOBAL index y * width + x, so the tiles of one frame agree with the full frame */
+struct FilmTile {
+    uint32_t cols, rows, x0, y0, y_step, width;
+};
+inline FilmTile film_tile(const rt_frame *f) {
+    const uint32_t cols = f->x1 - f->x0;
+    return {cols, (uint32_t)(film_frame_pixels(f) / cols), f->x0, f->y0, f->y_step, f->width};
+}
+RT_FILM_HD uint32_t film_global_pixel(const FilmTile &t, uint32_t row, uint32_t col) { return (t.y0 + row * t.y_step) * t.width + (t.x0 + col); }
 
 /* the argument limits of rt_film_offsets and rt_film_offsets_host; null: all in range.  *unsupported: the refusal is about size */
 inline const char *film_offsets_limits(const rt_frame *frame, uint32_t spp, uint32_t pattern, bool *unsupported) {

@@ -1,8 +1,8 @@
 /*
  * rt_primary_ray.h — Camera::shoot(clip(x, y)) (main.rs:83-99, 1093-1096) with the per-frame basis of make_kernel_frame: the operations
- * of the Whitted kernels' primary ray (rt_kernels.hip), written once for the two units that hand primary rays to the caller:
- * rt_query.hip (rt_camera_rays: through the pixel's integer coordinate) and rt_film_query.hip (rt_camera_rays_offset: through a
- * sub-pixel position).
+ * of the Whitted kernels' primary ray (rt_kernels.hip), written once for the units that hand primary rays to the caller:
+ * rt_query.hip (rt_camera_rays: through the pixel's integer coordinate), rt_film_query.hip and rt_adaptive_query.hip
+ * (rt_camera_rays_offset / rt_camera_rays_listed: through a sub-pixel position).
  */
 #ifndef RT_PRIMARY_RAY_H
 #define RT_PRIMARY_RAY_H
@@ -30,6 +30,13 @@ __device__ __forceinline__ Ray primary_ray_through(const KernelFrame &fr, float 
 __device__ __forceinline__ Ray primary_ray(const KernelFrame &fr, uint32_t col, uint32_t row) {
     const uint32_t x = fr.x0 + col, y = fr.y0 + row * fr.y_step;
     return primary_ray_through(fr, (float)x, (float)y);
+}
+
+/* the ray of compact pixel pix = row * cols + col of a tile, through the sub-pixel position (dx, dy) of it */
+__device__ __forceinline__ Ray primary_ray_offset(const KernelFrame &fr, uint32_t pix, float dx, float dy) {
+    const uint32_t row = pix / fr.cols, col = pix - row * fr.cols;
+    const uint32_t x = fr.x0 + col, y = fr.y0 + row * fr.y_step;
+    return primary_ray_through(fr, (float)x + dx, (float)y + dy);
 }
 
 /* the rt_ray record of a primary ray: face Front, no exclusion */

@@ -164,6 +164,27 @@ def test_listed_splat_equals_the_cpu_definition(rows, cols, form):
 
 
 @pytest.mark.parametrize("form", FORMS)
+def test_one_pixel_of_64_samples_beside_a_tile_border(form):
+    """48 x 40, every count 0 but pixel (15, 16)'s 64: first of the tile of columns 16 .. 31, last row of its tile row, and in the halo of
+    the tiles to the left and below.  Tiles whose halo holds it run all 64 sample indices — those to the left and below take the largest
+    count from a pixel that is not theirs — and every other tile runs none"""
+    rows, cols = 48, 40
+    counts = np.zeros(rows * cols, dtype=U32)
+    counts[15 * cols + 16] = 64
+    sl = adaptive.sample_list_numpy(counts)
+    rng = np.random.default_rng(64)
+    samples = rng.random((64, 3), dtype=F32) * F32(4.0)
+    offsets = rng.random((64, 2), dtype=F32) - F32(0.5)
+    total, weight = np.zeros((rows, cols, 3), dtype=F32), np.zeros((rows, cols), dtype=F32)
+    for name, radius in (("tent", 1.0), ("mitchell", 4.0)):
+        want = S.host_splat_listed(rows, cols, samples, None, offsets, sl, name, radius, total, weight)
+        assert want[1][15, 15] != 0 and want[1][15, 16] != 0 and want[1][16, 16] != 0 and want[1][16, 15] != 0  # on every side of the corner
+        assert not want[1][:, 32:].any() and not want[1][32:].any()  # ... and nothing in the tiles that stage nothing
+        got = device_splat_listed(rows, cols, samples, None, offsets, sl, name, radius, total, weight, form, 64)
+        assert np.array_equal(S.bits(got[0]), S.bits(want[0])) and np.array_equal(S.bits(got[1]), S.bits(want[1])), name
+
+
+@pytest.mark.parametrize("form", FORMS)
 def test_a_start_that_is_not_a_prefix_sum_is_clamped_on_the_device(form):
     rows, cols = 17, 17
     _, sl, samples, valid, offsets, total, weight = S.splat_case(rows, cols, 3, seed=9)

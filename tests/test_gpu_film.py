@@ -106,6 +106,16 @@ def test_splat_equals_the_host_definition(rows, cols, name):
 
 
 @pytest.mark.parametrize("form", FORMS)
+def test_splat_at_reach_four(form):
+    """radius 3.0 is reach 4, the halo width GPU_RADII leaves out; 17 x 17 is four tiles, three of them one pixel wide or tall"""
+    rows, cols = 17, 17
+    samples, valid, offsets, total, weight = case_data(rows, cols, 4)
+    want = host_splat(rows, cols, samples, valid, offsets, "mitchell", 3.0, total, weight)
+    got = device_splat(rows, cols, samples, valid, offsets, "mitchell", 3.0, total, weight, form=form)
+    assert np.array_equal(bits(got[0]), bits(want[0])) and np.array_equal(bits(got[1]), bits(want[1]))
+
+
+@pytest.mark.parametrize("form", FORMS)
 @pytest.mark.parametrize("rows,cols", [(33, 17), (70, 1)])
 def test_splat_does_not_depend_on_the_launch_geometry(rows, cols, form):
     """33 x 17 is 3 workgroups of pixels or 6 tiles, 70 x 1 is 1 workgroup or 5 tiles: with at most 1, 2 or 4 workgroups launched, the rest

@@ -1,6 +1,6 @@
 /*
- * adaptive_sanitize.cpp — the five CPU forms of the adaptive sampling queries (include/rt_host.h) on their edge inputs, as a stand-alone
- * program for AddressSanitizer and UndefinedBehaviorSanitizer.  Every array is a heap allocation of exactly the size the interface
+ * adaptive_sanitize.cpp — the five CPU forms of the adaptive sampling queries (include/rt_host.h) on their edge inputs, and
+ * rt_film_splat_host, which shares the listed splat's walk, as a stand-alone program for AddressSanitizer and UndefinedBehaviorSanitizer.  Every array is a heap allocation of exactly the size the interface
  * states, so a read or write one element outside it is reported.  Build and run, from the repository root (no device, no Python):
  *
  *   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -ffp-contract=off -fno-fast-math \
@@ -130,11 +130,34 @@ static void splat_edges() {
            RT_ERR_INVALID_ARGUMENT);
 }
 
+/* rt_film_splat_host walks the same loop with the uniform layout: record s * n + q */
+static void uniform_splat_edges() {
+    const uint32_t shapes[2][2] = {{1u, 1u}, {17u, 13u}}, spp = 3;
+    for (const auto &shape : shapes) {
+        const uint32_t rows = shape[0], cols = shape[1], n = rows * cols;
+        std::vector<float> samples(3 * spp * n, 1.0f), offsets(2 * spp * n, -0.5f), sum(3 * n, 0.0f), weight(n, 0.0f);
+        std::vector<uint8_t> valid(spp * n, 1u);
+        valid[spp * n - 1] = 0u;
+        offsets[0] = nanf("");
+        for (uint32_t filter = 0; filter < 3; ++filter) {
+            EXPECT(rt_film_splat_host(rows, cols, samples.data(), valid.data(), offsets.data(), spp, filter, 4.0f, sum.data(), weight.data()) == RT_OK);
+            EXPECT(rt_film_splat_host(rows, cols, samples.data(), nullptr, offsets.data(), spp, filter, 0.5f, sum.data(), weight.data()) == RT_OK);
+        }
+        for (float w : weight) EXPECT(w == w);
+        std::vector<float> s1(3 * n, 0.0f), w1(n, 0.0f);
+        EXPECT(rt_film_splat_host(rows, cols, samples.data(), valid.data(), offsets.data(), spp, RT_FILM_BOX, 0.5f, s1.data(), w1.data()) == RT_OK);
+        EXPECT(n == 1u ? w1[0] == (float)(spp - 2) : w1[0] == (float)(spp - 1) && w1[n - 1] == (float)(spp - 1)); /* a NaN offset, a cleared flag */
+    }
+    EXPECT(rt_film_splat_host(0, 5, nullptr, nullptr, nullptr, spp, RT_FILM_BOX, 0.5f, nullptr, nullptr) == RT_OK);
+    EXPECT(rt_film_splat_host(1, 1, nullptr, nullptr, nullptr, spp, RT_FILM_BOX, 4.5f, nullptr, nullptr) == RT_ERR_INVALID_ARGUMENT);
+}
+
 int main() {
     budget_edges();
     list_edges();
     listed_edges();
     splat_edges();
+    uniform_splat_edges();
     if (failures) {
         fprintf(stderr, "adaptive_sanitize: %d expectation(s) failed\n", failures);
         return 1;
