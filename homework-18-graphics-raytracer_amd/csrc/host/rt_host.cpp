@@ -41,6 +41,13 @@ static int fail(int code, const std::string &msg) {
     return code;
 }
 
+/* The CPU form of an element loop: the Op of a query's shared header (count() and operator()(i), the loop body written once for both
+ * libraries), every element in turn; the device runs the same Op through rt_image_kernel.h's each_kernel. */
+template <class Op>
+static void each(const Op &op) {
+    for (uint64_t i = 0; i < op.count(); ++i) op(i);
+}
+
 extern "C" {
 
 const char *rt_host_last_error(void) { return g_host_error.c_str(); }
@@ -574,7 +581,7 @@ int rt_sample_budget_cpu(const float *mean, uint32_t mean_stride, const float *v
     if (bad) return fail(status, std::string("rt_sample_budget_cpu: ") + bad);
     if (n == 0u) return RT_OK;
     const rt::SampleBudget b = rt::sample_budget_call(mean, mean_stride, variance, variance_stride, count, count_stride, valid, valid_stride, *params, n, budget);
-    for (uint64_t i = 0; i < b.n; ++i) budget[i] = rt::sample_budget_pixel(b, i);
+    each(b);
     return RT_OK;
 }
 
@@ -649,7 +656,7 @@ int rt_denoise_atrous_cpu(const float *color, const rt_denoise_guides *guides, c
     const char *bad = rt::denoise_limits(color, guides, params, rows, cols, out, temp, true);
     if (bad) return fail(RT_ERR_INVALID_ARGUMENT, std::string("rt_denoise_atrous_cpu: ") + bad);
     if (rows == 0u || cols == 0u) return RT_OK;
-    rt::atrous_cpu<rt::DenoiseFilter>(params->n_levels, rows, cols, [&](uint32_t j) { return rt::denoise_level(color, *guides, *params, rows, cols, out, temp, j); });
+    rt::atrous_cpu<rt::DenoiseFilter>(params->n_levels, [&](uint32_t j) { return rt::denoise_level(color, *guides, *params, rows, cols, out, temp, j); });
     return RT_OK;
 }
 
@@ -664,7 +671,7 @@ int rt_temporal_motion_cpu(const float *position, uint32_t position_stride, cons
     m.cam = rt::temporal_camera(prev_camera, prev_frame);
     m.position = position, m.valid = valid, m.position_stride = position_stride, m.valid_stride = valid_stride, m.motion = motion;
     m.n = (uint64_t)prev_frame->width * prev_frame->height;
-    for (uint64_t i = 0; i < m.n; ++i) rt::temporal_project(m, i);
+    each(m);
     return RT_OK;
 }
 
@@ -675,9 +682,7 @@ int rt_temporal_accumulate_cpu(const float *color, const float *motion, const rt
     const char *bad = rt::temporal_limits(color, motion, current, previous, params, rows, cols, history_in, history_out, false, &status);
     if (bad) return fail(status, std::string("rt_temporal_accumulate_cpu: ") + bad);
     if (rows == 0u || cols == 0u) return RT_OK;
-    const rt::TemporalCall t = rt::temporal_call(color, motion, *current, *previous, *params, rows, cols, history_in, history_out, variance);
-    const uint64_t n = (uint64_t)rows * cols;
-    for (uint64_t i = 0; i < n; ++i) rt::temporal_pixel(t, i);
+    each(rt::temporal_call(color, motion, *current, *previous, *params, rows, cols, history_in, history_out, variance));
     return RT_OK;
 }
 
@@ -703,10 +708,8 @@ int rt_temporal_accumulate_bounded_cpu(const float *color, const float *motion, 
     const char *bad = rt::rectify_accumulate_limits(color, motion, current, previous, params, rows, cols, history_in, history_out, box, clamped_length, false, &status);
     if (bad) return fail(status, std::string("rt_temporal_accumulate_bounded_cpu: ") + bad);
     if (rows == 0u || cols == 0u) return RT_OK;
-    const rt::RectifyAccumulate a = {rt::temporal_call(color, motion, *current, *previous, *params, rows, cols, history_in, history_out, variance), box,
-                                     clamped_length, clamped};
-    const uint64_t n = (uint64_t)rows * cols;
-    for (uint64_t i = 0; i < n; ++i) rt::rectify_pixel(a, i);
+    each(rt::RectifyAccumulate{rt::temporal_call(color, motion, *current, *previous, *params, rows, cols, history_in, history_out, variance), box,
+                               clamped_length, clamped});
     return RT_OK;
 }
 
@@ -716,8 +719,7 @@ int rt_temporal_feedback_cpu(const float *color, uint32_t color_stride, const ui
     const char *bad = rt::rectify_feedback_limits(color, color_stride, valid, valid_stride, rows, cols, history, false, &status);
     if (bad) return fail(status, std::string("rt_temporal_feedback_cpu: ") + bad);
     if (rows == 0u || cols == 0u) return RT_OK;
-    const rt::RectifyFeedback f = {color, valid, color_stride, valid_stride, (uint64_t)rows * cols, history};
-    for (uint64_t i = 0; i < f.n; ++i) rt::rectify_feedback_pixel(f, i);
+    each(rt::RectifyFeedback{color, valid, color_stride, valid_stride, (uint64_t)rows * cols, history});
     return RT_OK;
 }
 
@@ -739,7 +741,7 @@ int rt_svgf_atrous_cpu(const float *color, uint32_t color_stride, const float *v
     const char *bad = rt::svgf_atrous_limits(color, color_stride, variance, guides, params, rows, cols, out, variance_out, static_cast<float *>(temp), true);
     if (bad) return fail(RT_ERR_INVALID_ARGUMENT, std::string("rt_svgf_atrous_cpu: ") + bad);
     if (rows == 0u || cols == 0u) return RT_OK;
-    rt::atrous_cpu<rt::SvgfFilter>(params->n_levels, rows, cols, [&](uint32_t j) {
+    rt::atrous_cpu<rt::SvgfFilter>(params->n_levels, [&](uint32_t j) {
         return rt::svgf_level(color, color_stride, variance, *guides, *params, rows, cols, out, variance_out, static_cast<float *>(temp), j);
     });
     return RT_OK;
@@ -791,10 +793,7 @@ int rt_previous_positions_cpu(const rt_scene_desc *now, const float *was_triangl
         const float *q = was_spheres + 4u * (size_t)i;
         pieces[(size_t)RT_MOTION_TRI_PIECES * now->n_triangles + i] = rt::MotionPiece{q[0], q[1], q[2], q[3]};
     }
-    rt::MotionScene sc;
-    sc.tris = tris.data(), sc.spheres = spheres.data(), sc.kept = pieces.data();
-    sc.n_triangles = now->n_triangles, sc.n_spheres = now->n_spheres;
-    for (uint64_t i = 0; i < n; ++i) rt::motion_record(sc, hits, was, was_stride, i);
+    each(rt::MotionRecords{{tris.data(), spheres.data(), pieces.data(), now->n_triangles, now->n_spheres}, hits, (uint64_t)n, was, was_stride});
     return RT_OK;
 }
 

@@ -22,24 +22,27 @@ namespace rt {
 
 struct SampleBudget {
     const float *mean, *variance;
-    const uint32_t *count, *valid; /* may be null */
+    const uint32_t *taken, *valid; /* the count plane and the valid plane: each may be null */
     uint32_t mean_stride, variance_stride, count_stride, valid_stride;
     float gain, epsilon;
     uint32_t min_count, max_count;
     uint32_t *budget;
     uint64_t n;
+    RT_FILM_HD uint64_t count() const { return n; }
+    RT_FILM_HD void operator()(uint64_t i) const; /* budget[i] = sample_budget_pixel */
 };
 
 /* the six steps of the definition for pixel i */
 RT_FILM_HD uint32_t sample_budget_pixel(const SampleBudget &b, uint64_t i) {
     if (b.valid != nullptr && b.valid[i * b.valid_stride] == 0u) return 0u;
-    const uint32_t count = b.count != nullptr ? b.count[i * b.count_stride] : 1u;
+    const uint32_t count = b.taken != nullptr ? b.taken[i * b.count_stride] : 1u;
     if (count == 0u) return b.max_count;
     const float e = rtdm::f_sqrt(b.variance[i * b.variance_stride] / (float)count) / (fabsf(b.mean[i * b.mean_stride]) + b.epsilon);
     const float t = e * b.gain;
     const uint32_t range = b.max_count - b.min_count;
     return b.min_count + (t < (float)range ? (uint32_t)t : range); /* the test first: a NaN or a huge t is never converted */
 }
+RT_FILM_HD void SampleBudget::operator()(uint64_t i) const { budget[i] = sample_budget_pixel(*this, i); }
 
 /* the argument limits of rt_sample_budget and its CPU form; null: all in range */
 inline const char *sample_budget_limits(const float *mean, uint32_t mean_stride, const float *variance, uint32_t variance_stride, const uint32_t *count,

@@ -3,7 +3,7 @@
  * mean and a variance plane, the ragged pixel-major list of the samples that budget asks for, and the film queries on such a list:
  * sample positions, camera rays and the filtered splat; kernels and entry points in one unit.
  *
- *   rt::sample_budget_kernel        one thread per pixel, grid-stride: rt_adaptive.h's sample_budget_pixel
+ *   rt::each_kernel<SampleBudget>   one thread per pixel: rt_adaptive.h's sample_budget_pixel (rt_image_kernel.h has the element loop)
  *   rt::sample_totals_kernel        rt_sample_list, 1 of 3: a workgroup takes 256-pixel steps grid-stride and writes the sum of each step's
  *                                   clamped counts (a wave reduction by __shfl_down, four wave sums through LDS) to totals[step]
  *   rt::sample_scan_kernel          2 of 3: ONE workgroup turns totals[0 .. steps) into their exclusive sums in place, 256 entries at a time
@@ -23,24 +23,15 @@
  * the result cannot depend on the launch geometry: there is no atomic and no order to decide.  A record index is clamped into
  * [0, capacity) before anything is read through it (listed_range).  Every loop that holds a barrier is workgroup-uniform.
  */
-#include "rt_api_internal.h"
+#include "rt_image_kernel.h"
 #include "rt_adaptive.h"
 #include "rt_film_splat_kernel.h"
 #include "rt_primary_ray.h"
 
 namespace rt {
 
-#define RT_ADAPTIVE_THREADS 256u
-#define RT_ADAPTIVE_WAVES (RT_ADAPTIVE_THREADS / 64u)
-#define RT_ADAPTIVE_MAX_GROUPS (1u << 16)
-static_assert(RT_ADAPTIVE_THREADS == RT_SAMPLE_LIST_STEP, "a workgroup takes one step of the list per pass");
-
-/* ---- the budget ---- */
-
-__global__ __launch_bounds__(RT_ADAPTIVE_THREADS) void sample_budget_kernel(const SampleBudget b) {
-    const uint64_t stride = (uint64_t)gridDim.x * RT_ADAPTIVE_THREADS;
-    for (uint64_t i = (uint64_t)blockIdx.x * RT_ADAPTIVE_THREADS + threadIdx.x; i < b.n; i += stride) b.budget[i] = sample_budget_pixel(b, i);
-}
+#define RT_ADAPTIVE_WAVES (RT_IMAGE_THREADS / 64u)
+static_assert(RT_IMAGE_THREADS == RT_SAMPLE_LIST_STEP, "a workgroup takes one step of the list per pass");
 
 /* ---- the list ---- */
 
@@ -77,21 +68,21 @@ __device__ __forceinline__ uint32_t adaptive_group_scan(uint32_t v, uint32_t *ld
     return v + before;
 }
 
-__global__ __launch_bounds__(RT_ADAPTIVE_THREADS) void sample_totals_kernel(const uint32_t *__restrict__ counts, const uint64_t n, const uint64_t steps,
+__global__ __launch_bounds__(RT_IMAGE_THREADS) void sample_totals_kernel(const uint32_t *__restrict__ counts, const uint64_t n, const uint64_t steps,
                                                                             uint32_t *__restrict__ totals) {
     __shared__ uint32_t lds[RT_ADAPTIVE_WAVES];
     for (uint64_t step = blockIdx.x; step < steps; step += gridDim.x) { /* workgroup-uniform */
-        const uint64_t i = step * RT_ADAPTIVE_THREADS + threadIdx.x;
+        const uint64_t i = step * RT_IMAGE_THREADS + threadIdx.x;
         const uint32_t sum = adaptive_group_sum(i < n ? sample_count_clamped(counts[i]) : 0u, lds);
         if (threadIdx.x == 0u) totals[step] = sum;
     }
 }
 
-__global__ __launch_bounds__(RT_ADAPTIVE_THREADS) void sample_scan_kernel(uint32_t *__restrict__ totals, const uint64_t steps, const uint64_t n,
+__global__ __launch_bounds__(RT_IMAGE_THREADS) void sample_scan_kernel(uint32_t *__restrict__ totals, const uint64_t steps, const uint64_t n,
                                                                           const uint64_t capacity, uint32_t *__restrict__ start, uint32_t *__restrict__ total) {
     __shared__ uint32_t lds[RT_ADAPTIVE_WAVES];
     uint32_t base = 0u; /* the sum of the entries before this round's: below 2^32, as S_n is */
-    for (uint64_t first = 0u; first < steps; first += RT_ADAPTIVE_THREADS) { /* workgroup-uniform */
+    for (uint64_t first = 0u; first < steps; first += RT_IMAGE_THREADS) { /* workgroup-uniform */
         const uint64_t k = first + threadIdx.x;
         const uint32_t v = k < steps ? totals[k] : 0u;
         uint32_t all;
@@ -108,15 +99,15 @@ __global__ __launch_bounds__(RT_ADAPTIVE_THREADS) void sample_scan_kernel(uint32
     }
 }
 
-__global__ __launch_bounds__(RT_ADAPTIVE_THREADS) void sample_expand_kernel(const uint32_t *__restrict__ counts, const uint64_t n, const uint64_t steps,
+__global__ __launch_bounds__(RT_IMAGE_THREADS) void sample_expand_kernel(const uint32_t *__restrict__ counts, const uint64_t n, const uint64_t steps,
                                                                             const uint32_t *__restrict__ totals, const uint64_t capacity,
                                                                             uint32_t *__restrict__ first, uint32_t *__restrict__ start,
                                                                             uint32_t *__restrict__ pixel, uint32_t *__restrict__ sample) {
     __shared__ uint32_t lds[RT_ADAPTIVE_WAVES];
-    __shared__ uint32_t l_prefix[RT_ADAPTIVE_THREADS + 1u];
-    __shared__ uint32_t l_first[RT_ADAPTIVE_THREADS];
+    __shared__ uint32_t l_prefix[RT_IMAGE_THREADS + 1u];
+    __shared__ uint32_t l_first[RT_IMAGE_THREADS];
     for (uint64_t step = blockIdx.x; step < steps; step += gridDim.x) { /* workgroup-uniform */
-        const uint64_t i = step * RT_ADAPTIVE_THREADS + threadIdx.x;
+        const uint64_t i = step * RT_IMAGE_THREADS + threadIdx.x;
         const uint32_t c = i < n ? sample_count_clamped(counts[i]) : 0u;
         uint32_t block_total;
         const uint32_t inclusive = adaptive_group_scan(c, lds, &block_total); /* its first barrier: the previous step's LDS reads are done */
@@ -132,16 +123,16 @@ __global__ __launch_bounds__(RT_ADAPTIVE_THREADS) void sample_expand_kernel(cons
             if (first != nullptr) first[i] = f + (hi - lo);
         }
         __syncthreads();
-        for (uint32_t k = threadIdx.x; k < block_total; k += RT_ADAPTIVE_THREADS) { /* no barrier inside */
+        for (uint32_t k = threadIdx.x; k < block_total; k += RT_IMAGE_THREADS) { /* no barrier inside */
             const uint64_t j = base + k;
             if (j >= capacity) break; /* j grows with k: nothing of this thread's lies below capacity any more */
-            uint32_t lo = 0u, hi = RT_ADAPTIVE_THREADS; /* l_prefix[lo] <= k < l_prefix[hi] throughout */
+            uint32_t lo = 0u, hi = RT_IMAGE_THREADS; /* l_prefix[lo] <= k < l_prefix[hi] throughout */
             while (hi - lo > 1u) {
                 const uint32_t mid = (lo + hi) >> 1;
                 if (l_prefix[mid] <= k) lo = mid;
                 else hi = mid;
             }
-            pixel[j] = (uint32_t)(step * RT_ADAPTIVE_THREADS) + lo;
+            pixel[j] = (uint32_t)(step * RT_IMAGE_THREADS) + lo;
             sample[j] = l_first[lo] + (k - l_prefix[lo]);
         }
     }
@@ -154,17 +145,19 @@ __global__ void sample_list_empty_kernel(uint32_t *__restrict__ start, uint32_t 
 
 /* ---- positions and rays of a list ---- */
 
-__global__ __launch_bounds__(RT_ADAPTIVE_THREADS) void offsets_listed_kernel(const ListedOffsets o) {
-    const uint64_t listed = listed_count(o.total, o.capacity), stride = (uint64_t)gridDim.x * RT_ADAPTIVE_THREADS;
-    for (uint64_t j = (uint64_t)blockIdx.x * RT_ADAPTIVE_THREADS + threadIdx.x; j < o.capacity; j += stride) listed_offsets_record(o, j, listed);
+/* These two keep their own grid-stride loops: the list's length is read once per thread, ahead of the loop.  As Ops of each_kernel it
+ * is read per element, and the pass that runs both (adaptive.render_pass) then measured above the parent's range. */
+__global__ __launch_bounds__(RT_IMAGE_THREADS) void offsets_listed_kernel(const ListedOffsets o) {
+    const uint64_t listed = listed_count(o.total, o.capacity), stride = (uint64_t)gridDim.x * RT_IMAGE_THREADS;
+    for (uint64_t j = (uint64_t)blockIdx.x * RT_IMAGE_THREADS + threadIdx.x; j < o.capacity; j += stride) listed_offsets_record(o, j, listed);
 }
 
-__global__ __launch_bounds__(RT_ADAPTIVE_THREADS) void camera_rays_listed_kernel(const KernelFrame fr, const float *__restrict__ offsets,
-                                                                                 const uint32_t *__restrict__ pixel, const uint32_t *__restrict__ total,
-                                                                                 const uint64_t capacity, rt_ray *__restrict__ rays) {
-    const uint64_t listed = listed_count(total, capacity), stride = (uint64_t)gridDim.x * RT_ADAPTIVE_THREADS;
+__global__ __launch_bounds__(RT_IMAGE_THREADS) void camera_rays_listed_kernel(const KernelFrame fr, const float *__restrict__ offsets,
+                                                                              const uint32_t *__restrict__ pixel, const uint32_t *__restrict__ total,
+                                                                              const uint64_t capacity, rt_ray *__restrict__ rays) {
+    const uint64_t listed = listed_count(total, capacity), stride = (uint64_t)gridDim.x * RT_IMAGE_THREADS;
     const uint64_t n_pixels = (uint64_t)fr.rows * fr.cols;
-    for (uint64_t j = (uint64_t)blockIdx.x * RT_ADAPTIVE_THREADS + threadIdx.x; j < capacity; j += stride) {
+    for (uint64_t j = (uint64_t)blockIdx.x * RT_IMAGE_THREADS + threadIdx.x; j < capacity; j += stride) {
         const uint32_t pix = j < listed ? pixel[j] : 0xffffffffu;
         if ((uint64_t)pix >= n_pixels) { /* beyond the list, or a pixel the frame does not have: the record of an absent candidate */
             uint32_t *const o = reinterpret_cast<uint32_t *>(rays + j);
@@ -178,19 +171,13 @@ __global__ __launch_bounds__(RT_ADAPTIVE_THREADS) void camera_rays_listed_kernel
 
 /* ---- launchers ---- */
 
-static uint32_t adaptive_groups(uint64_t wanted) {
-    return (uint32_t)std::min<uint64_t>(wanted, max_groups(OPT_DIAG_ADAPTIVE_MAX_GROUPS, RT_ADAPTIVE_MAX_GROUPS));
-}
-static uint32_t adaptive_groups_of(uint64_t n) { return adaptive_groups((n + RT_ADAPTIVE_THREADS - 1u) / RT_ADAPTIVE_THREADS); }
-
 static hipError_t launch_sample_list(const uint32_t *counts, uint64_t n, uint64_t capacity, uint32_t *first, uint32_t *start, uint32_t *pixel, uint32_t *sample,
                                      uint32_t *total, uint32_t *totals, hipStream_t stream) {
     const uint64_t steps = sample_list_steps(n);
-    const dim3 grid(adaptive_groups(steps)), block(RT_ADAPTIVE_THREADS);
-    hipLaunchKernelGGL(sample_totals_kernel, grid, block, 0, stream, counts, n, steps, totals);
-    hipLaunchKernelGGL(sample_scan_kernel, dim3(1), block, 0, stream, totals, steps, n, capacity, start, total);
-    hipLaunchKernelGGL(sample_expand_kernel, grid, block, 0, stream, counts, n, steps, totals, capacity, first, start, pixel, sample);
-    return hipGetLastError();
+    const hipError_t e = launch_groups(sample_totals_kernel, steps, OPT_DIAG_ADAPTIVE_MAX_GROUPS, stream, counts, n, steps, totals);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(sample_scan_kernel, dim3(1), dim3(RT_IMAGE_THREADS), 0, stream, totals, steps, n, capacity, start, total);
+    return launch_groups(sample_expand_kernel, steps, OPT_DIAG_ADAPTIVE_MAX_GROUPS, stream, counts, n, steps, totals, capacity, first, start, pixel, sample);
 }
 
 } /* namespace rt */
@@ -209,8 +196,7 @@ int rt_sample_budget(const float *d_mean, uint32_t mean_stride, const float *d_v
     if (bad) return fail(status, std::string("rt_sample_budget: ") + bad);
     if (n == 0u) return RT_OK;
     const rt::SampleBudget b = rt::sample_budget_call(d_mean, mean_stride, d_variance, variance_stride, d_count, count_stride, d_valid, valid_stride, *params, n, d_budget);
-    hipLaunchKernelGGL(rt::sample_budget_kernel, dim3(rt::adaptive_groups_of(n)), dim3(RT_ADAPTIVE_THREADS), 0, static_cast<hipStream_t>(hip_stream), b);
-    return launched("rt_sample_budget");
+    return launched("rt_sample_budget", rt::launch_each(b, rt::OPT_DIAG_ADAPTIVE_MAX_GROUPS, static_cast<hipStream_t>(hip_stream)));
 }
 
 size_t rt_sample_list_temp_bytes(size_t n) { return (size_t)rt::sample_list_temp_bytes(n); }
@@ -239,8 +225,8 @@ int rt_film_offsets_listed(const rt_frame *frame, uint32_t pattern, uint32_t see
     if (bad) return fail(status, std::string("rt_film_offsets_listed: ") + bad);
     if (capacity == 0u) return RT_OK;
     const rt::ListedOffsets o = {rt::film_tile(frame), pattern, seed, d_pixel, d_sample, d_total, capacity, d_offsets};
-    hipLaunchKernelGGL(rt::offsets_listed_kernel, dim3(rt::adaptive_groups_of(capacity)), dim3(RT_ADAPTIVE_THREADS), 0, static_cast<hipStream_t>(hip_stream), o);
-    return launched("rt_film_offsets_listed");
+    return launched("rt_film_offsets_listed", rt::launch_groups(rt::offsets_listed_kernel, (capacity + RT_IMAGE_THREADS - 1u) / RT_IMAGE_THREADS,
+                                                                 rt::OPT_DIAG_ADAPTIVE_MAX_GROUPS, static_cast<hipStream_t>(hip_stream), o));
 }
 
 int rt_camera_rays_listed(const rt_camera *camera, const rt_frame *frame, const float *d_offsets, const uint32_t *d_pixel, const uint32_t *d_total,
@@ -254,9 +240,9 @@ int rt_camera_rays_listed(const rt_camera *camera, const rt_frame *frame, const 
     rt::KernelFrame kf;
     const int rc = make_kernel_frame(camera, &f, &kf);
     if (rc != RT_OK) return rc;
-    hipLaunchKernelGGL(rt::camera_rays_listed_kernel, dim3(rt::adaptive_groups_of(capacity)), dim3(RT_ADAPTIVE_THREADS), 0, static_cast<hipStream_t>(hip_stream), kf,
-                       d_offsets, d_pixel, d_total, (uint64_t)capacity, d_rays);
-    return launched("rt_camera_rays_listed");
+    return launched("rt_camera_rays_listed",
+                    rt::launch_groups(rt::camera_rays_listed_kernel, (capacity + RT_IMAGE_THREADS - 1u) / RT_IMAGE_THREADS, rt::OPT_DIAG_ADAPTIVE_MAX_GROUPS,
+                                      static_cast<hipStream_t>(hip_stream), kf, d_offsets, d_pixel, d_total, (uint64_t)capacity, d_rays));
 }
 
 int rt_film_splat_listed(uint32_t rows, uint32_t cols, const float *d_samples, const unsigned char *d_valid, const float *d_offsets, const uint32_t *d_start,
@@ -268,7 +254,7 @@ int rt_film_splat_listed(uint32_t rows, uint32_t cols, const float *d_samples, c
     const rt::FilmSplat<rt::ListedLayout> p = {{d_samples, d_valid, d_offsets, d_start, capacity, max_count}, d_sum, d_weight, rows, cols, filter, radius};
     const bool tiled = rt::option(rt::OPT_FILM_SPLAT_FORM, RT_LISTED_SPLAT_FORM_DEFAULT) == 1;
     return launched("rt_film_splat_listed",
-                    rt::launch_film_splat_forms(p, tiled, max_groups(rt::OPT_DIAG_ADAPTIVE_MAX_GROUPS, RT_FILM_MAX_GROUPS), static_cast<hipStream_t>(hip_stream)));
+                    rt::launch_film_splat_forms(p, tiled, rt::OPT_DIAG_ADAPTIVE_MAX_GROUPS, static_cast<hipStream_t>(hip_stream)));
 }
 
 } /* extern "C" */

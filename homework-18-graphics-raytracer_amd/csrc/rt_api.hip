@@ -127,6 +127,14 @@ rt_denoise_guides HostRoundTrip::guides(const rt_denoise_guides &h, size_t n, bo
     g.valid = plane(h.valid, n, h.valid_stride, 1u);
     return g;
 }
+rt_temporal_guides HostRoundTrip::temporal_guides(const rt_temporal_guides &h, size_t n) {
+    rt_temporal_guides g = h;
+    g.normal = plane(h.normal, n, h.normal_stride, 3u);
+    g.position = plane(h.position, n, h.position_stride, 3u);
+    g.object = plane(h.object, n, h.object_stride, 1u);
+    g.valid = plane(h.valid, n, h.valid_stride, 1u);
+    return g;
+}
 unsigned long long *HostRoundTrip::counter() {
     if (e_ != hipSuccess) return nullptr;
     e_ = hipMalloc(reinterpret_cast<void **>(&d_count_), sizeof *d_count_);

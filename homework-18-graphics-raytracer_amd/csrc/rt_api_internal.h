@@ -231,7 +231,8 @@ static inline uint32_t band_limit(rt::Option hook, uint32_t limit) {
     return h > 0 && h < (long long)limit ? (uint32_t)round_up_64((uint64_t)h) : limit;
 }
 /* Workgroups: a grid-stride kernel is launched with at most `limit` of them, or with what the test hook `hook` asks for, 1 .. limit, so
- * that a small image or batch is taken grid-stride; a smaller cap changes no bit. */
+ * that a small image or batch is taken grid-stride; a smaller cap changes no bit.  The image-side kernels' launchers are
+ * rt_image_kernel.h's, which take the hook. */
 static inline uint32_t max_groups(rt::Option hook, uint32_t limit) {
     const long long cap = rt::option(hook, limit);
     return cap >= 1 && cap < (long long)limit ? (uint32_t)cap : limit;
@@ -261,6 +262,7 @@ public:
     template <class T> T *in(const T *h, size_t bytes) { return static_cast<T *>(add(const_cast<T *>(h), bytes, h != nullptr, true, false)); }
     template <class T> T *plane(const T *h, size_t n, uint32_t stride, uint32_t width) { return in(h, ((n - 1u) * stride + width) * sizeof(uint32_t)); }
     rt_denoise_guides guides(const rt_denoise_guides &h, size_t n, bool albedo = true); /* the four planes of n pixels; albedo only where the call reads it */
+    rt_temporal_guides temporal_guides(const rt_temporal_guides &h, size_t n);          /* the four planes of n pixels */
     template <class T> T *out(T *h, size_t bytes) { return static_cast<T *>(add(h, bytes, h != nullptr, false, true)); }
     template <class T> T *inout(T *h, size_t bytes) { return static_cast<T *>(add(h, bytes, h != nullptr, true, true)); } /* continues from the caller's values */
     void *scratch(size_t bytes) { return add(nullptr, bytes, true, false, false); }
@@ -344,10 +346,7 @@ hipError_t launch_level_finish(const float *value, uint32_t n, float *accum, uns
  * rt_film_splat_listed.  tiled: the LDS form of the splat instead of the simple one (same bits). */
 hipError_t launch_film_offsets(const FilmTile &t, uint32_t spp, uint32_t pattern, uint32_t seed, float *offsets, hipStream_t stream);
 hipError_t launch_camera_rays_offset(const KernelFrame &fr, const float *offsets, uint32_t spp, rt_ray *rays, hipStream_t stream);
-/* max_groups: both forms take their pixels or tiles grid-stride beyond this many workgroups, 1 .. RT_FILM_MAX_GROUPS (2^16 x 256 threads
- * stay far below the 2^32 threads a launch may have); a smaller cap changes no bit */
-#define RT_FILM_MAX_GROUPS (1u << 16)
-hipError_t launch_film_splat(const FilmSplat<UniformLayout> &p, bool tiled, uint32_t max_groups, hipStream_t stream);
+hipError_t launch_film_splat(const FilmSplat<UniformLayout> &p, bool tiled, hipStream_t stream);
 } /* namespace rt */
 
 /* rt_select_records (rt_api_query.hip) keeps its block totals per (device, stream); rt_post_release (rt_api_post.hip) frees those of a

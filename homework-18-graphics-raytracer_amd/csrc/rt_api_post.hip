@@ -137,7 +137,7 @@ int rt_film_splat(uint32_t rows, uint32_t cols, const float *d_samples, const un
     if (rc != RT_OK) return rc;
     const rt::FilmSplat<rt::UniformLayout> p = {{d_samples, d_valid, d_offsets, (uint64_t)rows * cols, spp}, d_sum, d_weight, rows, cols, filter, radius};
     const bool tiled = rt::option(rt::OPT_FILM_SPLAT_FORM, RT_FILM_SPLAT_FORM_DEFAULT) == 1;
-    return launched("rt_film_splat", rt::launch_film_splat(p, tiled, max_groups(rt::OPT_DIAG_FILM_MAX_GROUPS, RT_FILM_MAX_GROUPS), static_cast<hipStream_t>(hip_stream)));
+    return launched("rt_film_splat", rt::launch_film_splat(p, tiled, static_cast<hipStream_t>(hip_stream)));
 }
 
 int rt_encode_srgb8_device(const float *d_rgb, size_t n_values, unsigned char *d_out, void *hip_stream) {

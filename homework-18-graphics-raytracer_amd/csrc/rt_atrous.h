@@ -150,13 +150,23 @@ RT_AT_HD void atrous_pixel(const typename F::Level &L, uint32_t r, uint32_t c) {
     F::store(L, i, filtered, a);
 }
 
+/* one level as an element loop: output pixel i = r * cols + c */
+template <class F>
+struct AtrousEach {
+    typename F::Level L;
+    RT_AT_HD uint64_t count() const { return (uint64_t)L.rows * L.cols; }
+    RT_AT_HD void operator()(uint64_t i) const {
+        const uint32_t r = (uint32_t)(i / L.cols), c = (uint32_t)(i - (uint64_t)r * L.cols);
+        atrous_pixel<F>(L, r, c);
+    }
+};
+
 /* every level of a call on the host: level_of(j) is the filter's Level */
 template <class F, class LevelOf>
-inline void atrous_cpu(uint32_t n_levels, uint32_t rows, uint32_t cols, LevelOf level_of) {
+inline void atrous_cpu(uint32_t n_levels, LevelOf level_of) {
     for (uint32_t j = 0; j < n_levels; ++j) {
-        const typename F::Level L = level_of(j);
-        for (uint32_t r = 0; r < rows; ++r)
-            for (uint32_t c = 0; c < cols; ++c) atrous_pixel<F>(L, r, c);
+        const AtrousEach<F> level = {level_of(j)};
+        for (uint64_t i = 0; i < level.count(); ++i) level(i);
     }
 }
 

@@ -2,8 +2,8 @@
  * rt_denoise_query.hip — the denoise queries (include/rt_amd.h "denoise queries"): the edge-avoiding A-Trous filter, one launch per level,
  * kernels and entry points in one unit.
  *
- *   rt::atrous_kernel<DenoiseFilter>        the simple form
- *   rt::atrous_tiled_kernel<DenoiseFilter>  the tiled form: 400 staged entries of 9 words, 14.4 KB of LDS
+ *   rt::each_kernel<AtrousEach<DenoiseFilter>>  the simple form
+ *   rt::atrous_tiled_kernel<DenoiseFilter>      the tiled form: 400 staged entries of 9 words, 14.4 KB of LDS
  *
  * The kernels are rt_atrous_kernel.h's, which says what they do and why they agree bit for bit; the arithmetic is rt_denoise.h's
  * DenoiseFilter, shared with librt_host.so.  The temp plane is one colour plane.
@@ -21,8 +21,8 @@ namespace rt {
 
 static hipError_t launch_denoise(const float *color, const rt_denoise_guides &g, const rt_denoise_params &p, uint32_t rows, uint32_t cols, float *out, float *temp,
                                  hipStream_t stream) {
-    return launch_atrous<DenoiseFilter>(p.n_levels, option(OPT_DENOISE_FORM, RT_DENOISE_FORM_DEFAULT) == 1, max_groups(OPT_DIAG_DENOISE_MAX_GROUPS, RT_ATROUS_MAX_GROUPS),
-                                        stream, [&](uint32_t j) { return denoise_level(color, g, p, rows, cols, out, temp, j); });
+    return launch_atrous<DenoiseFilter>(p.n_levels, option(OPT_DENOISE_FORM, RT_DENOISE_FORM_DEFAULT) == 1, OPT_DIAG_DENOISE_MAX_GROUPS, stream,
+                                        [&](uint32_t j) { return denoise_level(color, g, p, rows, cols, out, temp, j); });
 }
 
 } /* namespace rt */

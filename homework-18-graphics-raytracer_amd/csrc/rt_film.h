@@ -148,6 +148,16 @@ RT_FILM_HD void film_splat_pixel(const FilmSplat<Layout> &p, uint64_t i, Apply a
     p.weight[i] = a.w;
 }
 
+/* a splat as an element loop over its output pixels, the filter a constant (the plain kernel) */
+template <uint32_t FILTER, class Layout>
+struct FilmSplatEach {
+    FilmSplat<Layout> p;
+    RT_FILM_HD uint64_t count() const { return (uint64_t)p.rows * p.cols; }
+    RT_FILM_HD void operator()(uint64_t i) const {
+        film_splat_pixel(p, i, [&](FilmAcc &a, float ddx, float ddy, float p0, float p1, float p2) { film_apply(a, FILTER, p.radius, ddx, ddy, p0, p1, p2); });
+    }
+};
+
 /* the CPU form of a splat: every output pixel in turn */
 template <class Layout>
 inline void film_splat_cpu(const FilmSplat<Layout> &p) {

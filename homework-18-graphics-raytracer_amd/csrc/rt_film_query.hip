@@ -14,10 +14,10 @@
 
 namespace rt {
 
-__global__ __launch_bounds__(RT_FILM_THREADS) void film_offsets_kernel(const FilmTile t, const uint32_t spp, const uint32_t pattern, const uint32_t k,
+__global__ __launch_bounds__(RT_IMAGE_THREADS) void film_offsets_kernel(const FilmTile t, const uint32_t spp, const uint32_t pattern, const uint32_t k,
                                                                        const uint32_t seed, float *__restrict__ offsets) {
     const uint64_t n_pixels = (uint64_t)t.rows * t.cols;
-    const uint64_t i = (uint64_t)blockIdx.x * RT_FILM_THREADS + threadIdx.x;
+    const uint64_t i = (uint64_t)blockIdx.x * RT_IMAGE_THREADS + threadIdx.x;
     if (i >= n_pixels * spp) return;
     const uint32_t s = (uint32_t)(i / n_pixels), pix = (uint32_t)(i - (uint64_t)s * n_pixels);
     const uint32_t row = pix / t.cols, col = pix - row * t.cols;
@@ -26,10 +26,10 @@ __global__ __launch_bounds__(RT_FILM_THREADS) void film_offsets_kernel(const Fil
     offsets[2u * i + 1u] = film_offset(pattern, k, pixel, seed, s, 1u);
 }
 
-__global__ __launch_bounds__(RT_FILM_THREADS) void camera_rays_offset_kernel(const KernelFrame fr, const float *__restrict__ offsets, const uint32_t spp,
+__global__ __launch_bounds__(RT_IMAGE_THREADS) void camera_rays_offset_kernel(const KernelFrame fr, const float *__restrict__ offsets, const uint32_t spp,
                                                                              rt_ray *__restrict__ rays) {
     const uint64_t n_pixels = (uint64_t)fr.rows * fr.cols;
-    const uint64_t i = (uint64_t)blockIdx.x * RT_FILM_THREADS + threadIdx.x;
+    const uint64_t i = (uint64_t)blockIdx.x * RT_IMAGE_THREADS + threadIdx.x;
     if (i >= n_pixels * spp) return;
     store_primary_ray(primary_ray_offset(fr, (uint32_t)(i % n_pixels), offsets[2u * i], offsets[2u * i + 1u]), rays + i);
 }
@@ -37,19 +37,19 @@ __global__ __launch_bounds__(RT_FILM_THREADS) void camera_rays_offset_kernel(con
 hipError_t launch_film_offsets(const FilmTile &t, uint32_t spp, uint32_t pattern, uint32_t seed, float *offsets, hipStream_t stream) {
     const uint64_t n = (uint64_t)t.rows * t.cols * spp;
     if (n == 0u) return hipSuccess;
-    hipLaunchKernelGGL(film_offsets_kernel, grid_of(n, RT_FILM_THREADS), dim3(RT_FILM_THREADS), 0, stream, t, spp, pattern, film_strata(spp), seed, offsets);
+    hipLaunchKernelGGL(film_offsets_kernel, grid_of(n, RT_IMAGE_THREADS), dim3(RT_IMAGE_THREADS), 0, stream, t, spp, pattern, film_strata(spp), seed, offsets);
     return hipGetLastError();
 }
 
 hipError_t launch_camera_rays_offset(const KernelFrame &fr, const float *offsets, uint32_t spp, rt_ray *rays, hipStream_t stream) {
     const uint64_t n = (uint64_t)fr.rows * fr.cols * spp;
     if (n == 0u) return hipSuccess;
-    hipLaunchKernelGGL(camera_rays_offset_kernel, grid_of(n, RT_FILM_THREADS), dim3(RT_FILM_THREADS), 0, stream, fr, offsets, spp, rays);
+    hipLaunchKernelGGL(camera_rays_offset_kernel, grid_of(n, RT_IMAGE_THREADS), dim3(RT_IMAGE_THREADS), 0, stream, fr, offsets, spp, rays);
     return hipGetLastError();
 }
 
-hipError_t launch_film_splat(const FilmSplat<UniformLayout> &p, bool tiled, uint32_t max_groups, hipStream_t stream) {
-    return launch_film_splat_forms(p, tiled, max_groups, stream);
+hipError_t launch_film_splat(const FilmSplat<UniformLayout> &p, bool tiled, hipStream_t stream) {
+    return launch_film_splat_forms(p, tiled, OPT_DIAG_FILM_MAX_GROUPS, stream);
 }
 
 } /* namespace rt */

@@ -2,8 +2,8 @@
  * rt_film_splat_kernel.h — the two forms of the film splat, templates over the filter and a layout of rt_film.h; rt_film_query.hip
  * instantiates them with UniformLayout (rt_film_splat), rt_adaptive_query.hip with rt_adaptive.h's ListedLayout (rt_film_splat_listed).
  *
- *   rt::film_splat_kernel<FILTER, Layout>        the plain gather: one thread per output pixel, grid-stride, straight from global memory
- *                                                (film_splat_pixel, which is also the CPU form)
+ *   rt::each_kernel<FilmSplatEach<FILTER, Layout>>  the plain gather: one thread per output pixel (rt_image_kernel.h), straight from global
+ *                                                memory (film_splat_pixel, which is also the CPU form)
  *   rt::film_splat_tiled_kernel<FILTER, Layout>  the same gather from LDS: a 256-thread workgroup owns a 16 x 16 tile of output pixels and
  *                                                stages, for one sample index at a time, the (16 + 2 reach)^2 halo of offsets and samples:
  *                                                at most 26 x 26 = 676 entries of 5 words, 13.5 KB.  Entry e is staged by thread e,
@@ -24,36 +24,27 @@
 #ifndef RT_FILM_SPLAT_KERNEL_H
 #define RT_FILM_SPLAT_KERNEL_H
 
-#include "rt_api_internal.h"
+#include "rt_image_kernel.h"
 #include "rt_film.h"
 
 namespace rt {
 
-#define RT_FILM_THREADS 256u
-#define RT_FILM_TILE 16u
-#define RT_FILM_HALO_MAX (RT_FILM_TILE + 2u * 5u) /* reach <= 5: radius <= 4 */
+#define RT_FILM_HALO_MAX (RT_IMAGE_TILE + 2u * 5u) /* reach <= 5: radius <= 4 */
 #define RT_FILM_HALO_ENTRIES (RT_FILM_HALO_MAX * RT_FILM_HALO_MAX)
 
 template <uint32_t FILTER, class Layout>
-__global__ __launch_bounds__(RT_FILM_THREADS) void film_splat_kernel(const FilmSplat<Layout> p) {
-    const uint64_t n = (uint64_t)p.rows * p.cols, stride = (uint64_t)gridDim.x * RT_FILM_THREADS;
-    for (uint64_t i = (uint64_t)blockIdx.x * RT_FILM_THREADS + threadIdx.x; i < n; i += stride)
-        film_splat_pixel(p, i, [&](FilmAcc &a, float ddx, float ddy, float p0, float p1, float p2) { film_apply(a, FILTER, p.radius, ddx, ddy, p0, p1, p2); });
-}
-
-template <uint32_t FILTER, class Layout>
-__global__ __launch_bounds__(RT_FILM_THREADS) void film_splat_tiled_kernel(const FilmSplat<Layout> p, const uint32_t tiles_x, const uint64_t n_tiles) {
+__global__ __launch_bounds__(RT_IMAGE_THREADS) void film_splat_tiled_kernel(const FilmSplat<Layout> p, const uint32_t tiles_x, const uint64_t n_tiles) {
     constexpr uint32_t RANGES = Layout::ragged ? RT_FILM_HALO_ENTRIES : 1u;
     __shared__ float2 l_off[RT_FILM_HALO_ENTRIES];
     __shared__ float l_smp[RT_FILM_HALO_ENTRIES * 3u];
-    __shared__ uint32_t l_lo[RANGES], l_cnt[RANGES], l_max[Layout::ragged ? RT_FILM_THREADS / 64u : 1u];
+    __shared__ uint32_t l_lo[RANGES], l_cnt[RANGES], l_max[Layout::ragged ? RT_IMAGE_THREADS / 64u : 1u];
     const Layout &L = p.layout;
     const int reach = film_reach(p.radius);
-    const uint32_t halo = RT_FILM_TILE + 2u * (uint32_t)reach; /* <= RT_FILM_HALO_MAX: the launcher bounds the reach */
-    const uint32_t ty = threadIdx.x / RT_FILM_TILE, tx = threadIdx.x % RT_FILM_TILE;
+    const uint32_t halo = RT_IMAGE_TILE + 2u * (uint32_t)reach; /* <= RT_FILM_HALO_MAX: the launcher bounds the reach */
+    const auto [ty, tx] = tile_thread();
     for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) { /* workgroup-uniform */
-        const uint32_t tile_r = (uint32_t)(tile / tiles_x), tile_c = (uint32_t)(tile - (uint64_t)tile_r * tiles_x);
-        const int64_t r0 = (int64_t)tile_r * RT_FILM_TILE, c0 = (int64_t)tile_c * RT_FILM_TILE;
+        const TileOrigin origin = tile_origin(tile, tiles_x);
+        const int64_t r0 = origin.r0, c0 = origin.c0; /* by name: the lambda below captures them */
         const int64_t r = r0 + ty, c = c0 + tx;
         const bool inside = r < (int64_t)p.rows && c < (int64_t)p.cols;
         const uint64_t i = inside ? (uint64_t)r * p.cols + (uint64_t)c : 0u;
@@ -71,7 +62,7 @@ __global__ __launch_bounds__(RT_FILM_THREADS) void film_splat_tiled_kernel(const
         if constexpr (Layout::ragged) {
             __syncthreads(); /* the previous tile's reads are done */
             uint32_t most = 0u;
-            for (uint32_t e = threadIdx.x; e < halo * halo; e += RT_FILM_THREADS) { /* the halo's record ranges, once per tile */
+            for (uint32_t e = threadIdx.x; e < halo * halo; e += RT_IMAGE_THREADS) { /* the halo's record ranges, once per tile */
                 uint64_t lo;
                 const uint32_t cnt = entry_range(e, &lo);
                 l_lo[e] = (uint32_t)lo; /* below 2^32 in every layout */
@@ -86,12 +77,12 @@ __global__ __launch_bounds__(RT_FILM_THREADS) void film_splat_tiled_kernel(const
             __syncthreads();
             most = 0u;
 #pragma unroll
-            for (uint32_t w = 0; w < RT_FILM_THREADS / 64u; ++w) most = l_max[w] > most ? l_max[w] : most;
+            for (uint32_t w = 0; w < RT_IMAGE_THREADS / 64u; ++w) most = l_max[w] > most ? l_max[w] : most;
             s_end = most < s_end ? most : s_end; /* workgroup-uniform: an s at or beyond it has no source in the halo */
         }
         for (uint32_t s = 0; s < s_end; ++s) {
             __syncthreads(); /* the previous sample's (or tile's) reads are done */
-            for (uint32_t e = threadIdx.x; e < halo * halo; e += RT_FILM_THREADS) {
+            for (uint32_t e = threadIdx.x; e < halo * halo; e += RT_IMAGE_THREADS) {
                 uint64_t lo;
                 uint32_t cnt;
                 if constexpr (Layout::ragged) lo = l_lo[e], cnt = l_cnt[e];
@@ -136,29 +127,19 @@ __global__ __launch_bounds__(RT_FILM_THREADS) void film_splat_tiled_kernel(const
 }
 
 template <uint32_t FILTER, class Layout>
-static void launch_film_splat_of(const FilmSplat<Layout> &p, bool tiled, uint32_t max_groups, hipStream_t stream) {
-    if (tiled) {
-        const uint32_t tiles_x = (p.cols + RT_FILM_TILE - 1u) / RT_FILM_TILE, tiles_y = (p.rows + RT_FILM_TILE - 1u) / RT_FILM_TILE;
-        const uint64_t n_tiles = (uint64_t)tiles_x * tiles_y;
-        hipLaunchKernelGGL((film_splat_tiled_kernel<FILTER, Layout>), dim3((uint32_t)std::min<uint64_t>(n_tiles, max_groups)), dim3(RT_FILM_THREADS), 0, stream, p,
-                           tiles_x, n_tiles);
-    } else {
-        const uint64_t groups = ((uint64_t)p.rows * p.cols + RT_FILM_THREADS - 1u) / RT_FILM_THREADS;
-        hipLaunchKernelGGL((film_splat_kernel<FILTER, Layout>), dim3((uint32_t)std::min<uint64_t>(groups, max_groups)), dim3(RT_FILM_THREADS), 0, stream, p);
-    }
+static hipError_t launch_film_splat_of(const FilmSplat<Layout> &p, bool tiled, Option hook, hipStream_t stream) {
+    if (tiled) return launch_tiles(film_splat_tiled_kernel<FILTER, Layout>, p.rows, p.cols, hook, stream, p);
+    return launch_each(FilmSplatEach<FILTER, Layout>{p}, hook, stream);
 }
 
-/* tiled: the LDS form instead of the plain one (same bits).  max_groups: both forms take their pixels or tiles grid-stride beyond this
- * many workgroups, 1 .. RT_FILM_MAX_GROUPS; a smaller cap changes no bit */
+/* tiled: the LDS form instead of the plain one (same bits).  hook: the unit's cap on the workgroups of either form */
 template <class Layout>
-static hipError_t launch_film_splat_forms(const FilmSplat<Layout> &p, bool tiled, uint32_t max_groups, hipStream_t stream) {
+static hipError_t launch_film_splat_forms(const FilmSplat<Layout> &p, bool tiled, Option hook, hipStream_t stream) {
     if (p.rows == 0u || p.cols == 0u || p.layout.s_end() == 0u) return hipSuccess;
-    if (max_groups < 1u || max_groups > RT_FILM_MAX_GROUPS) return hipErrorInvalidValue;
     if (!(p.radius > 0.0f) || film_reach(p.radius) > 5) return hipErrorInvalidValue; /* the tiled form's LDS holds a halo of reach 5 */
-    if (p.filter == RT_FILM_BOX) launch_film_splat_of<RT_FILM_BOX>(p, tiled, max_groups, stream);
-    else if (p.filter == RT_FILM_TENT) launch_film_splat_of<RT_FILM_TENT>(p, tiled, max_groups, stream);
-    else launch_film_splat_of<RT_FILM_MITCHELL>(p, tiled, max_groups, stream);
-    return hipGetLastError();
+    if (p.filter == RT_FILM_BOX) return launch_film_splat_of<RT_FILM_BOX>(p, tiled, hook, stream);
+    if (p.filter == RT_FILM_TENT) return launch_film_splat_of<RT_FILM_TENT>(p, tiled, hook, stream);
+    return launch_film_splat_of<RT_FILM_MITCHELL>(p, tiled, hook, stream);
 }
 
 } /* namespace rt */

@@ -108,6 +108,17 @@ RT_MO_HD void motion_record(const MotionScene &s, const rt_hit *hits, float *was
     o[0] = out[0], o[1] = out[1], o[2] = out[2];
 }
 
+/* rt_previous_positions as an element loop over the n records */
+struct MotionRecords {
+    MotionScene s;
+    const rt_hit *hits;
+    uint64_t n;
+    float *was;
+    uint32_t was_stride;
+    RT_MO_HD uint64_t count() const { return n; }
+    RT_MO_HD void operator()(uint64_t i) const { motion_record(s, hits, was, was_stride, i); }
+};
+
 /* ---- THE argument checks of rt_previous_positions, in the order include/rt_amd.h states; null: go on (*done: nothing to launch),
  * *status says how a refusal is reported.  kept: the scene holds kept positions (the CPU form: the arrays of them it needs). ---- */
 inline const char *motion_limits(uint64_t n, const void *scene, bool kept, const char *not_kept, const void *hits, const void *was, uint32_t was_stride,

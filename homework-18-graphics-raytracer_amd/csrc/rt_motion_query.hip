@@ -2,10 +2,11 @@
  * rt_motion_query.hip — the motion queries (include/rt_amd.h "motion queries"): the positions a scene keeps before it is updated, and
  * where each hit's point was on them; kernels and entry points in one unit.
  *
- *   rt::keep_positions_kernel      one primitive per lane, grid-stride, triangles and spheres in one launch: three 16-byte loads and
- *                                  stores per triangle, one per sphere
- *   rt::previous_positions_kernel  one hit per lane, grid-stride: the hit's kind, index and position as dwords, then the primitive's
- *                                  record and its kept pieces as 16-byte loads
+ *   rt::each_kernel<KeepPositions>  one primitive per lane, triangles and spheres in one launch: three 16-byte loads and stores per
+ *                                  triangle, one per sphere
+ *   rt::each_kernel<MotionRecords>  one hit per lane: the hit's kind, index and position as dwords, then the primitive's record and its
+ *                                  kept pieces as 16-byte loads
+ * (rt_image_kernel.h has the element loop and its launch)
  *
  * The arithmetic is rt_motion.h's, shared with librt_host.so: the kernel calls motion_record on the same operands as
  * rt_previous_positions_cpu, so it gives the same bits by construction, whatever the launch geometry.  The kind branch is left
@@ -13,19 +14,19 @@
  * neighbouring lanes name the same primitive — and are served by the caches: nothing is staged in LDS.  Every index is checked against
  * its array before anything is read with it; the record number and the output index are 64-bit.  No atomics, no workspace.
  */
-#include "rt_api_internal.h"
+#include "rt_image_kernel.h"
 #include "rt_motion.h"
 
 namespace rt {
 
-#define RT_MOTION_THREADS 256u
-#define RT_MOTION_MAX_GROUPS (1u << 16)
-
-__global__ __launch_bounds__(RT_MOTION_THREADS) void keep_positions_kernel(const DevTri *__restrict__ tris, const DevSphere *__restrict__ spheres,
-                                                                           const uint32_t n_triangles, const uint32_t n_spheres,
-                                                                           MotionPiece *__restrict__ kept) {
-    const uint64_t n = (uint64_t)n_triangles + n_spheres, stride = (uint64_t)gridDim.x * RT_MOTION_THREADS;
-    for (uint64_t i = (uint64_t)blockIdx.x * RT_MOTION_THREADS + threadIdx.x; i < n; i += stride) {
+/* primitive i of rt_scene_keep_positions, the triangles first */
+struct KeepPositions {
+    const DevTri *tris;
+    const DevSphere *spheres;
+    uint32_t n_triangles, n_spheres;
+    MotionPiece *kept;
+    __host__ __device__ uint64_t count() const { return (uint64_t)n_triangles + n_spheres; }
+    __device__ void operator()(uint64_t i) const {
         if (i < n_triangles) {
             const unsigned char *T = reinterpret_cast<const unsigned char *>(tris + i);
             MotionPiece v0 = motion_load(T + 16), v1 = motion_load(T + 32), v2 = motion_load(T + 48); /* v0 obj | v1 area | v2 bq */
@@ -36,17 +37,7 @@ __global__ __launch_bounds__(RT_MOTION_THREADS) void keep_positions_kernel(const
             kept[(uint64_t)RT_MOTION_TRI_PIECES * n_triangles + (i - n_triangles)] = motion_load(spheres + (i - n_triangles)); /* c radius */
         }
     }
-}
-
-__global__ __launch_bounds__(RT_MOTION_THREADS) void previous_positions_kernel(const MotionScene s, const rt_hit *__restrict__ hits, const uint64_t n,
-                                                                               float *__restrict__ was, const uint32_t was_stride) {
-    const uint64_t stride = (uint64_t)gridDim.x * RT_MOTION_THREADS;
-    for (uint64_t i = (uint64_t)blockIdx.x * RT_MOTION_THREADS + threadIdx.x; i < n; i += stride) motion_record(s, hits, was, was_stride, i);
-}
-
-static dim3 motion_grid(uint64_t n) {
-    return dim3((uint32_t)std::min<uint64_t>((n + RT_MOTION_THREADS - 1u) / RT_MOTION_THREADS, max_groups(OPT_DIAG_MOTION_MAX_GROUPS, RT_MOTION_MAX_GROUPS)));
-}
+};
 
 } /* namespace rt */
 
@@ -67,9 +58,8 @@ int rt_scene_keep_positions(rt_scene *scene, void *hip_stream) {
         }
     }
     if (bytes != 0u) {
-        hipLaunchKernelGGL(rt::keep_positions_kernel, rt::motion_grid((uint64_t)n_triangles + n_spheres), dim3(RT_MOTION_THREADS), 0, stream, scene->ks.tris,
-                           scene->ks.spheres, n_triangles, n_spheres, k.d_pieces.get<rt::MotionPiece>());
-        const int rc = launched("rt_scene_keep_positions");
+        const rt::KeepPositions keep = {scene->ks.tris, scene->ks.spheres, n_triangles, n_spheres, k.d_pieces.get<rt::MotionPiece>()};
+        const int rc = launched("rt_scene_keep_positions", rt::launch_each(keep, rt::OPT_DIAG_MOTION_MAX_GROUPS, stream));
         if (rc != RT_OK) return rc;
     }
     k.kept.store(true);
@@ -87,12 +77,9 @@ int rt_previous_positions(const rt_scene *scene, const rt_hit *d_hits, size_t n,
     const char *bad = rt::motion_limits(n, scene, scene && scene->kept.kept.load(), RT_MOTION_NOT_KEPT, d_hits, d_was, was_stride, &status, &done);
     if (bad) return fail(status, std::string("rt_previous_positions: ") + bad);
     if (done) return RT_OK;
-    rt::MotionScene s;
-    s.tris = scene->ks.tris, s.spheres = scene->ks.spheres, s.kept = scene->kept.d_pieces.get<rt::MotionPiece>();
-    s.n_triangles = scene->ks.n_triangles, s.n_spheres = scene->ks.n_spheres;
-    hipLaunchKernelGGL(rt::previous_positions_kernel, rt::motion_grid(n), dim3(RT_MOTION_THREADS), 0, static_cast<hipStream_t>(hip_stream), s, d_hits,
-                       (uint64_t)n, d_was, was_stride);
-    return launched("rt_previous_positions");
+    const rt::MotionRecords m = {{scene->ks.tris, scene->ks.spheres, scene->kept.d_pieces.get<rt::MotionPiece>(), scene->ks.n_triangles, scene->ks.n_spheres},
+                                 d_hits, (uint64_t)n, d_was, was_stride};
+    return launched("rt_previous_positions", rt::launch_each(m, rt::OPT_DIAG_MOTION_MAX_GROUPS, static_cast<hipStream_t>(hip_stream)));
 }
 
 int rt_previous_positions_host(const rt_scene *scene, const rt_hit *h_hits, size_t n, float *h_was, uint32_t was_stride) {

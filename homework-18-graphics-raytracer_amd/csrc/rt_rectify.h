@@ -159,6 +159,8 @@ struct RectifyAccumulate {
     const rt_temporal_box *box;
     uint32_t clamped_length;
     uint32_t *clamped; /* may be null */
+    RT_TP_HD uint64_t count() const { return t.count(); }
+    RT_TP_HD void operator()(uint64_t i) const; /* rectify_pixel */
 };
 
 /* operation 1 and the first half of 2: x into [lo, hi]; a NaN x, or a NaN bound, compares false and passes */
@@ -212,6 +214,7 @@ RT_TP_HD void rectify_pixel(const RectifyAccumulate &a, uint64_t i) {
     }
     if (a.clamped) a.clamped[i] = changed;
 }
+RT_TP_HD void RectifyAccumulate::operator()(uint64_t i) const { rectify_pixel(*this, i); }
 
 /* ---- rt_temporal_feedback ---- */
 
@@ -221,6 +224,8 @@ struct RectifyFeedback {
     uint32_t color_stride, valid_stride;
     uint64_t n;
     rt_temporal_pixel *history;
+    RT_TP_HD uint64_t count() const { return n; }
+    RT_TP_HD void operator()(uint64_t i) const; /* rectify_feedback_pixel */
 };
 
 /* record i: the colour's raw words over the record's three colour words; the moments, the length and the reserved words keep their bits */
@@ -237,6 +242,7 @@ RT_TP_HD void rectify_feedback_pixel(const RectifyFeedback &f, uint64_t i) {
     h[0] = c[0], h[1] = c[1], h[2] = c[2];
 #endif
 }
+RT_TP_HD void RectifyFeedback::operator()(uint64_t i) const { rectify_feedback_pixel(*this, i); }
 
 /* ---- THE argument checks, in the order include/rt_amd.h states; null: all in range, *status says how a refusal is reported ---- */
 

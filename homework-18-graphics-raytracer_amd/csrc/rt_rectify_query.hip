@@ -8,46 +8,34 @@
  *                                  Of the halo only the ring the call's radius reaches is read from global memory; the entries beyond
  *                                  it are never looked at.  Each thread then walks its window twice in LDS — sums, then squared
  *                                  deviations from the mean — and writes its box as two 128-bit stores.
- *   rt::accumulate_bounded_kernel  rt_temporal_accumulate's kernel with the box, two 128-bit loads more per pixel, between its gather
- *                                  and its blend: one thread per output pixel, grid-stride
- *   rt::feedback_kernel            one thread per record, grid-stride: a 128-bit load and a 128-bit store of the record's first 16 bytes
+ *   rt::each_kernel<RectifyAccumulate>  rt_temporal_accumulate's loop with the box, two 128-bit loads more per pixel, between its
+ *                                  gather and its blend: one thread per output pixel
+ *   rt::each_kernel<RectifyFeedback>  one thread per record: a 128-bit load and a 128-bit store of the record's first 16 bytes
  *
- * The arithmetic is rt_rectify.h's, shared with librt_host.so; the gather of the accumulate is rt_temporal.h's.  bounds_kernel walks a
- * pixel's sources in the order of the definition — dr, then dc, ascending — and calls the same functions on the same operands as the
- * CPU form, so the forms give the same bits by construction, whatever the launch geometry.  It has svgf_variance_kernel's shape
- * (rt_svgf_query.hip) and is not a template shared with it: that one stages history records, leaves early and weighs its taps.  An entry
- * that lies outside the image or whose valid word is cleared is marked ONCE, while staging, with RectifySource::none().  Entries have an
- * odd number of words, so a tile row spreads over the LDS banks (rt_atrous_kernel.h).  Workgroups take tiles grid-stride and every
- * barrier is workgroup-uniform.  An output word is written by one thread: no atomics.  Every index into a plane is 64-bit; every global
- * read is behind an inside-the-image test; rows * cols < 2^32 is checked by the entry points.
+ * The arithmetic is rt_rectify.h's, shared with librt_host.so; the gather of the accumulate is rt_temporal.h's.  bounds_kernel walks
+ * pixel's sources in the order of the definition — dr, then dc, ascending — and calls the same functions on the same operands as the CPU
+ * form, so the forms give the same bits by construction, whatever the launch geometry.  The element loop, the tile walk and the halo stager
+ * are rt_image_kernel.h's.  An entry that lies outside the image or whose valid word is cleared is marked ONCE, while staging, with
+ * RectifySource::none().  Entries have an odd number of words, so a tile row spreads over the LDS banks (rt_atrous_kernel.h).  Workgroups
+ * take tiles grid-stride and every barrier is workgroup-uniform.  An output word is written by one thread: no atomics.  Every index into a
+ * plane is 64-bit; every global read is behind an inside-the-image test; rows * cols < 2^32 is checked by the entry points.
  */
-#include "rt_api_internal.h"
+#include "rt_image_kernel.h"
 #include "rt_rectify.h"
 
 namespace rt {
 
-#define RT_RECTIFY_THREADS 256u
-#define RT_RECTIFY_TILE 16u
-#define RT_RECTIFY_HALO (RT_RECTIFY_TILE + 2u * RT_RECTIFY_MAX_RADIUS)
-#define RT_RECTIFY_MAX_GROUPS (1u << 16)
+#define RT_RECTIFY_HALO (RT_IMAGE_TILE + 2u * RT_RECTIFY_MAX_RADIUS)
 
 /* tiles_x: tiles of 16 x 16 pixels across the image */
-__global__ __launch_bounds__(RT_RECTIFY_THREADS) void bounds_kernel(const RectifyBounds b, const uint32_t tiles_x, const uint64_t n_tiles) {
+__global__ __launch_bounds__(RT_IMAGE_THREADS) void bounds_kernel(const RectifyBounds b, const uint32_t tiles_x, const uint64_t n_tiles) {
     __shared__ RectifySource l_src[RT_RECTIFY_HALO * RT_RECTIFY_HALO];
-    const uint32_t ty = threadIdx.x / RT_RECTIFY_TILE, tx = threadIdx.x % RT_RECTIFY_TILE;
-    const uint32_t ring_lo = (uint32_t)(RT_RECTIFY_MAX_RADIUS - b.radius), ring_hi = RT_RECTIFY_HALO - ring_lo; /* the entries a window can reach */
+    const auto [ty, tx] = tile_thread();
+    const uint32_t ring = (uint32_t)(RT_RECTIFY_MAX_RADIUS - b.radius); /* outer entries no window of this radius can reach */
     for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) { /* workgroup-uniform */
-        const uint32_t tile_r = (uint32_t)(tile / tiles_x), tile_c = (uint32_t)(tile - (uint64_t)tile_r * tiles_x);
-        const int64_t r0 = (int64_t)tile_r * RT_RECTIFY_TILE, c0 = (int64_t)tile_c * RT_RECTIFY_TILE;
+        const auto [r0, c0] = tile_origin(tile, tiles_x);
         __syncthreads(); /* the previous tile's reads are done */
-        for (uint32_t e = threadIdx.x; e < RT_RECTIFY_HALO * RT_RECTIFY_HALO; e += RT_RECTIFY_THREADS) {
-            const uint32_t hr = e / RT_RECTIFY_HALO, hc = e - hr * RT_RECTIFY_HALO;
-            if (hr < ring_lo || hr >= ring_hi || hc < ring_lo || hc >= ring_hi) continue;
-            const int64_t qr = r0 + (int64_t)hr - RT_RECTIFY_MAX_RADIUS, qc = c0 + (int64_t)hc - RT_RECTIFY_MAX_RADIUS;
-            RectifySource q = RectifySource::none(); /* a source of nobody */
-            if (qr >= 0 && qr < (int64_t)b.rows && qc >= 0 && qc < (int64_t)b.cols) q = rectify_source(b, (uint64_t)qr * b.cols + (uint64_t)qc);
-            l_src[e] = q;
-        }
+        stage_halo<RT_RECTIFY_MAX_RADIUS>(l_src, r0, c0, b.rows, b.cols, 1, ring, RectifySource::none(), [&](uint64_t qi) { return rectify_source(b, qi); });
         __syncthreads();
         const int64_t r = r0 + ty, c = c0 + tx;
         if (r >= (int64_t)b.rows || c >= (int64_t)b.cols) continue; /* no barrier below */
@@ -60,46 +48,8 @@ __global__ __launch_bounds__(RT_RECTIFY_THREADS) void bounds_kernel(const Rectif
     }
 }
 
-__global__ __launch_bounds__(RT_RECTIFY_THREADS) void accumulate_bounded_kernel(const RectifyAccumulate a) {
-    const uint64_t n = (uint64_t)a.t.rows * a.t.cols, stride = (uint64_t)gridDim.x * RT_RECTIFY_THREADS;
-    for (uint64_t i = (uint64_t)blockIdx.x * RT_RECTIFY_THREADS + threadIdx.x; i < n; i += stride) rectify_pixel(a, i);
-}
-
-__global__ __launch_bounds__(RT_RECTIFY_THREADS) void feedback_kernel(const RectifyFeedback f) {
-    const uint64_t stride = (uint64_t)gridDim.x * RT_RECTIFY_THREADS;
-    for (uint64_t i = (uint64_t)blockIdx.x * RT_RECTIFY_THREADS + threadIdx.x; i < f.n; i += stride) rectify_feedback_pixel(f, i);
-}
-
-static uint32_t rectify_groups(uint64_t wanted) {
-    return (uint32_t)std::min<uint64_t>(wanted, max_groups(OPT_DIAG_RECTIFY_MAX_GROUPS, RT_RECTIFY_MAX_GROUPS));
-}
-
 static hipError_t launch_box(const RectifyBounds &b, hipStream_t stream) {
-    const uint32_t tiles_x = (b.cols + RT_RECTIFY_TILE - 1u) / RT_RECTIFY_TILE, tiles_y = (b.rows + RT_RECTIFY_TILE - 1u) / RT_RECTIFY_TILE;
-    const uint64_t n_tiles = (uint64_t)tiles_x * tiles_y;
-    hipLaunchKernelGGL(bounds_kernel, dim3(rectify_groups(n_tiles)), dim3(RT_RECTIFY_THREADS), 0, stream, b, tiles_x, n_tiles);
-    return hipGetLastError();
-}
-
-static hipError_t launch_accumulate_bounded(const RectifyAccumulate &a, hipStream_t stream) {
-    const uint64_t n = (uint64_t)a.t.rows * a.t.cols;
-    hipLaunchKernelGGL(accumulate_bounded_kernel, dim3(rectify_groups((n + RT_RECTIFY_THREADS - 1u) / RT_RECTIFY_THREADS)), dim3(RT_RECTIFY_THREADS), 0, stream, a);
-    return hipGetLastError();
-}
-
-static hipError_t launch_feedback(const RectifyFeedback &f, hipStream_t stream) {
-    hipLaunchKernelGGL(feedback_kernel, dim3(rectify_groups((f.n + RT_RECTIFY_THREADS - 1u) / RT_RECTIFY_THREADS)), dim3(RT_RECTIFY_THREADS), 0, stream, f);
-    return hipGetLastError();
-}
-
-/* the four guide planes of n pixels on their way to the device, as rt_temporal_accumulate_host sends them */
-static rt_temporal_guides upload_guides(HostRoundTrip &t, const rt_temporal_guides &h, size_t n) {
-    rt_temporal_guides g = h;
-    g.normal = t.plane(h.normal, n, h.normal_stride, 3u);
-    g.position = t.plane(h.position, n, h.position_stride, 3u);
-    g.object = t.plane(h.object, n, h.object_stride, 1u);
-    g.valid = t.plane(h.valid, n, h.valid_stride, 1u);
-    return g;
+    return launch_tiles(bounds_kernel, b.rows, b.cols, OPT_DIAG_RECTIFY_MAX_GROUPS, stream, b);
 }
 
 } /* namespace rt */
@@ -128,7 +78,7 @@ int rt_temporal_accumulate_bounded(const float *d_color, const float *d_motion, 
     if (rows == 0u || cols == 0u) return RT_OK;
     const rt::RectifyAccumulate a = {rt::temporal_call(d_color, d_motion, *current, *previous, *params, rows, cols, d_history_in, d_history_out, d_variance),
                                      d_box, clamped_length, d_clamped};
-    return launched("rt_temporal_accumulate_bounded", rt::launch_accumulate_bounded(a, static_cast<hipStream_t>(hip_stream)));
+    return launched("rt_temporal_accumulate_bounded", rt::launch_each(a, rt::OPT_DIAG_RECTIFY_MAX_GROUPS, static_cast<hipStream_t>(hip_stream)));
 }
 
 int rt_temporal_feedback(const float *d_color, uint32_t color_stride, const uint32_t *d_valid, uint32_t valid_stride, uint32_t rows, uint32_t cols,
@@ -138,7 +88,7 @@ int rt_temporal_feedback(const float *d_color, uint32_t color_stride, const uint
     if (bad) return fail(status, std::string("rt_temporal_feedback: ") + bad);
     if (rows == 0u || cols == 0u) return RT_OK;
     const rt::RectifyFeedback f = {d_color, d_valid, color_stride, valid_stride, (uint64_t)rows * cols, d_history};
-    return launched("rt_temporal_feedback", rt::launch_feedback(f, static_cast<hipStream_t>(hip_stream)));
+    return launched("rt_temporal_feedback", rt::launch_each(f, rt::OPT_DIAG_RECTIFY_MAX_GROUPS, static_cast<hipStream_t>(hip_stream)));
 }
 
 int rt_temporal_bounds_host(const float *h_color, uint32_t color_stride, const uint32_t *h_object, uint32_t object_stride, const uint32_t *h_valid,
@@ -173,7 +123,7 @@ int rt_temporal_accumulate_bounded_host(const float *h_color, const float *h_mot
     HostRoundTrip t("rt_temporal_accumulate_bounded_host");
     const float *d_color = t.in(h_color, n * 3u * sizeof(float));
     const float *d_motion = t.in(h_motion, n * 2u * sizeof(float));
-    const rt_temporal_guides cur = rt::upload_guides(t, *current, n), prev = rt::upload_guides(t, *previous, n);
+    const rt_temporal_guides cur = t.temporal_guides(*current, n), prev = t.temporal_guides(*previous, n);
     const rt_temporal_pixel *d_in = t.in(h_history_in, n * sizeof(rt_temporal_pixel));
     rt_temporal_pixel *d_out = t.out(h_history_out, n * sizeof(rt_temporal_pixel));
     float *d_variance = t.out(h_variance, n * sizeof(float));
@@ -181,7 +131,7 @@ int rt_temporal_accumulate_bounded_host(const float *h_color, const float *h_mot
     uint32_t *d_clamped = t.out(h_clamped, n * sizeof(uint32_t));
     if (!t.ok()) return t.failed();
     const rt::RectifyAccumulate a = {rt::temporal_call(d_color, d_motion, cur, prev, *params, rows, cols, d_in, d_out, d_variance), d_box, clamped_length, d_clamped};
-    const hipError_t e = rt::launch_accumulate_bounded(a, nullptr);
+    const hipError_t e = rt::launch_each(a, rt::OPT_DIAG_RECTIFY_MAX_GROUPS, nullptr);
     if (e != hipSuccess) return launched("rt_temporal_accumulate_bounded_host", e);
     return t.finish();
 }
@@ -199,7 +149,7 @@ int rt_temporal_feedback_host(const float *h_color, uint32_t color_stride, const
     rt_temporal_pixel *d_history = t.inout(h_history, n * sizeof(rt_temporal_pixel));
     if (!t.ok()) return t.failed();
     const rt::RectifyFeedback f = {d_color, d_valid, color_stride, valid_stride, (uint64_t)n, d_history};
-    const hipError_t e = rt::launch_feedback(f, nullptr);
+    const hipError_t e = rt::launch_each(f, rt::OPT_DIAG_RECTIFY_MAX_GROUPS, nullptr);
     if (e != hipSuccess) return launched("rt_temporal_feedback_host", e);
     return t.finish();
 }

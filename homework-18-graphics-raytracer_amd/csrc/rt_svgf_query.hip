@@ -7,21 +7,20 @@
  *                             (__syncthreads_or).  A tile without one — after a few frames most of the image — writes steps 1 and 2
  *                             and stages nothing.  Otherwise the tile and its halo of 3, 22 x 22 entries of 9 words (17.4 KB of LDS),
  *                             are staged once and the short pixels walk their 49 taps there.
- *   rt::atrous_kernel<SvgfFilter>        the A-Trous level, simple form
+ *   rt::each_kernel<AtrousEach<SvgfFilter>>  the A-Trous level, simple form
  *   rt::atrous_tiled_kernel<SvgfFilter>  the A-Trous level, tiled form: 400 staged entries of 11 words (the colour as seen, its
  *                             luminance, the variance through vpos, normal, position), 17.6 KB of LDS at every level.  The 3 x 3
  *                             prefilter of the variance concerns the output pixel alone and its neighbours lie at step 1, not in the
  *                             residue class: each thread reads it from global memory.
  *
- * The A-Trous kernels are rt_atrous_kernel.h's, which says what they do and why they agree bit for bit.  The variance kernel is this
- * unit's own: its tile is contiguous, its halo 3 and it leaves early, so it shares the guide readers and the weight terms and not the
- * tile.  The arithmetic is rt_svgf.h's, shared with librt_host.so.  Every kernel walks a pixel's sources in the order of the definition
- * — dr, then dc, ascending — and calls the same functions on the same operands, so the forms give the same bits as each other and as
- * the CPU forms by construction, whatever the launch geometry.  An output word is written by one thread: no atomics.  A staged entry of
- * the variance tile that lies outside the image or whose valid word is cleared is marked ONCE, while staging, by length 0, which the
- * definition skips anyway.  Entries have an odd number of words, so a tile row spreads over the LDS banks.  Guides are read through
- * their record strides where they lie.  Every index into a plane is 64-bit; every read is behind an inside-the-image test;
- * rows * cols < 2^32 is checked by the entry point.
+ * The A-Trous kernels are rt_atrous_kernel.h's, which says what they do and why they agree bit for bit.  The variance kernel is this unit's
+ * own from its early leave on; its tile walk, halo stager and launch are rt_image_kernel.h's.  The arithmetic is rt_svgf.h's, shared with
+ * librt_host.so.  Every kernel walks a pixel's sources in the order of the definition — dr, then dc, ascending — and calls the same
+ * functions on the same operands, so the forms give the same bits as each other and as the CPU forms by construction, whatever the launch
+ * geometry.  An output word is written by one thread: no atomics.  A staged entry of the variance tile that lies outside the image or whose
+ * valid word is cleared is marked ONCE, while staging, by length 0, which the definition skips anyway.  Entries have an odd number of
+ * words, so a tile row spreads over the LDS banks.  Guides are read through their record strides where they lie.  Every index into a plane
+ * is 64-bit; every read is behind an inside-the-image test; rows * cols < 2^32 is checked by the entry point.
  */
 #include "rt_api_internal.h"
 #include "rt_atrous_kernel.h"
@@ -32,18 +31,16 @@
 
 namespace rt {
 
-/* the variance tile: the workgroup and the 16 x 16 outputs of the A-Trous tile, three pixels either side */
-#define RT_SVGF_VARIANCE_HALO (RT_ATROUS_TILE + 2u * RT_SVGF_VARIANCE_REACH)
+#define RT_SVGF_VARIANCE_HALO (RT_IMAGE_TILE + 2u * RT_SVGF_VARIANCE_REACH)
 
 /* tiles_x: tiles of 16 x 16 pixels across the image.  Workgroups take tiles grid-stride; `any_short` is the same in every thread of the
  * workgroup, so every thread meets the same barriers.  The __syncthreads_or at the top of a tile is also what separates the previous
  * tile's reads of l_pix from this tile's writes. */
-__global__ __launch_bounds__(RT_ATROUS_THREADS) void svgf_variance_kernel(const SvgfVariance v, const uint32_t tiles_x, const uint64_t n_tiles) {
+__global__ __launch_bounds__(RT_IMAGE_THREADS) void svgf_variance_kernel(const SvgfVariance v, const uint32_t tiles_x, const uint64_t n_tiles) {
     __shared__ SvgfMoments l_pix[RT_SVGF_VARIANCE_HALO * RT_SVGF_VARIANCE_HALO];
-    const uint32_t ty = threadIdx.x / RT_ATROUS_TILE, tx = threadIdx.x % RT_ATROUS_TILE;
+    const auto [ty, tx] = tile_thread();
     for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) { /* workgroup-uniform */
-        const uint32_t tile_r = (uint32_t)(tile / tiles_x), tile_c = (uint32_t)(tile - (uint64_t)tile_r * tiles_x);
-        const int64_t r0 = (int64_t)tile_r * RT_ATROUS_TILE, c0 = (int64_t)tile_c * RT_ATROUS_TILE;
+        const auto [r0, c0] = tile_origin(tile, tiles_x);
         const int64_t r = r0 + ty, c = c0 + tx;
         const bool inside = r < (int64_t)v.rows && c < (int64_t)v.cols;
         const uint64_t i = inside ? (uint64_t)r * v.cols + (uint64_t)c : 0u;
@@ -55,13 +52,8 @@ __global__ __launch_bounds__(RT_ATROUS_THREADS) void svgf_variance_kernel(const 
             if (inside) v.out[i] = svgf_variance_temporal(p);
             continue;
         }
-        for (uint32_t e = threadIdx.x; e < RT_SVGF_VARIANCE_HALO * RT_SVGF_VARIANCE_HALO; e += RT_ATROUS_THREADS) {
-            const uint32_t hr = e / RT_SVGF_VARIANCE_HALO, hc = e - hr * RT_SVGF_VARIANCE_HALO;
-            const int64_t qr = r0 + (int64_t)hr - RT_SVGF_VARIANCE_REACH, qc = c0 + (int64_t)hc - RT_SVGF_VARIANCE_REACH;
-            SvgfMoments q = {0.0f, 0.0f, 0u, {}}; /* length 0: a source of nobody */
-            if (qr >= 0 && qr < (int64_t)v.rows && qc >= 0 && qc < (int64_t)v.cols) q = svgf_moments_load(v, (uint64_t)qr * v.cols + (uint64_t)qc);
-            l_pix[e] = q;
-        }
+        stage_halo<RT_SVGF_VARIANCE_REACH>(l_pix, r0, c0, v.rows, v.cols, 1, 0u, SvgfMoments{0.0f, 0.0f, 0u, {}} /* length 0 */,
+                                           [&](uint64_t qi) { return svgf_moments_load(v, qi); });
         __syncthreads();
         if (!inside) continue; /* no barrier below */
         float out = svgf_variance_temporal(p);
@@ -77,15 +69,12 @@ __global__ __launch_bounds__(RT_ATROUS_THREADS) void svgf_variance_kernel(const 
 }
 
 static hipError_t launch_svgf_variance(const SvgfVariance &v, hipStream_t stream) {
-    const uint32_t tiles_x = (v.cols + RT_ATROUS_TILE - 1u) / RT_ATROUS_TILE, tiles_y = (v.rows + RT_ATROUS_TILE - 1u) / RT_ATROUS_TILE;
-    const uint64_t n_tiles = (uint64_t)tiles_x * tiles_y;
-    hipLaunchKernelGGL(svgf_variance_kernel, dim3((uint32_t)std::min<uint64_t>(n_tiles, max_groups(OPT_DIAG_SVGF_MAX_GROUPS, RT_ATROUS_MAX_GROUPS))), dim3(RT_ATROUS_THREADS), 0, stream, v, tiles_x, n_tiles);
-    return hipGetLastError();
+    return launch_tiles(svgf_variance_kernel, v.rows, v.cols, OPT_DIAG_SVGF_MAX_GROUPS, stream, v);
 }
 
 static hipError_t launch_svgf(const float *color, uint32_t color_stride, const float *variance, const rt_denoise_guides &g, const rt_svgf_atrous_params &p,
                               uint32_t rows, uint32_t cols, float *out, float *variance_out, float *temp, hipStream_t stream) {
-    return launch_atrous<SvgfFilter>(p.n_levels, option(OPT_SVGF_FORM, RT_SVGF_FORM_DEFAULT) == 1, max_groups(OPT_DIAG_SVGF_MAX_GROUPS, RT_ATROUS_MAX_GROUPS), stream,
+    return launch_atrous<SvgfFilter>(p.n_levels, option(OPT_SVGF_FORM, RT_SVGF_FORM_DEFAULT) == 1, OPT_DIAG_SVGF_MAX_GROUPS, stream,
                                      [&](uint32_t j) { return svgf_level(color, color_stride, variance, g, p, rows, cols, out, variance_out, temp, j); });
 }
 

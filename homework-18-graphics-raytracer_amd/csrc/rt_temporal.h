@@ -3,7 +3,8 @@
  * rt_temporal_motion_cpu / rt_temporal_accumulate_cpu) and the device (rt_temporal_query.hip).  Every function is a sequence of single
  * f32 operations in the order the header comment of the block gives; both libraries are built with -ffp-contract=off, the divides are
  * correctly rounded on either side, nothing comes from libm and nothing from a device intrinsic (the floor is two conversions and a
- * compare), so host and device agree bit for bit.  The loops (CPU, kernel) differ only in how they walk the pixels.
+ * compare), so host and device agree bit for bit.  A call struct is the Op of its element loop — count() and operator()(i) — which the
+ * device runs through rt_image_kernel.h's each_kernel and the host in a plain loop.
  * temporal_pixel is temporal_gather, then temporal_blend or temporal_reset: rt_rectify.h puts its clamp between the first two, so the
  * gather of rt_temporal_accumulate_bounded is this header's and is stated once.
  *
@@ -75,6 +76,8 @@ struct TemporalMotion {
     uint32_t position_stride, valid_stride;
     float *motion;
     uint64_t n;
+    RT_TP_HD uint64_t count() const { return n; }
+    RT_TP_HD void operator()(uint64_t i) const; /* temporal_project */
 };
 
 RT_TP_HD float temporal_dot(float a0, float a1, float a2, float b0, float b1, float b2) { return (a0 * b0 + a1 * b1) + a2 * b2; }
@@ -110,6 +113,7 @@ RT_TP_HD void temporal_project(const TemporalMotion &m, uint64_t i) {
     m.motion[2u * i] = clip_x * c.height_f + c.half_width;
     m.motion[2u * i + 1u] = c.half_height - clip_y * c.height_f;
 }
+RT_TP_HD void TemporalMotion::operator()(uint64_t i) const { temporal_project(*this, i); }
 
 /* ---- rt_temporal_accumulate ---- */
 
@@ -123,6 +127,8 @@ struct TemporalCall {
     float rows_f, cols_f;
     float normal_min, position_max2, alpha_min;
     uint32_t max_length;
+    RT_TP_HD uint64_t count() const { return (uint64_t)rows * cols; }
+    RT_TP_HD void operator()(uint64_t i) const; /* temporal_pixel */
 };
 
 inline TemporalCall temporal_call(const float *color, const float *motion, const rt_temporal_guides &cur, const rt_temporal_guides &prev,
@@ -305,6 +311,7 @@ RT_TP_HD void temporal_pixel(const TemporalCall &t, uint64_t i) {
     else
         temporal_reset(t, i, p);
 }
+RT_TP_HD void TemporalCall::operator()(uint64_t i) const { temporal_pixel(*this, i); }
 
 /* ---- THE argument checks, in the order include/rt_amd.h states; null: all in range, *status says how a refusal is reported ---- */
 

@@ -2,8 +2,9 @@
  * rt_temporal_query.hip — the temporal queries (include/rt_amd.h "temporal queries"): where each pixel's surface point was in the previous
  * frame, and the previous frame's history gathered from there and blended with the current frame; kernels and entry points in one unit.
  *
- *   rt::temporal_motion_kernel      one thread per pixel, grid-stride: the seven steps of the projection
- *   rt::temporal_accumulate_kernel  one thread per output pixel, grid-stride: a data-dependent 2 x 2 gather over the previous frame
+ *   rt::each_kernel<TemporalMotion>  one thread per pixel: the seven steps of the projection
+ *   rt::each_kernel<TemporalCall>    one thread per output pixel: a data-dependent 2 x 2 gather over the previous frame
+ * (rt_image_kernel.h has the element loop and its launch)
  *
  * The arithmetic is rt_temporal.h's, shared with librt_host.so: the kernels call temporal_project / temporal_pixel on the same operands
  * as rt_temporal_motion_cpu / rt_temporal_accumulate_cpu, so they give the same bits by construction, whatever the launch geometry.
@@ -12,27 +13,10 @@
  * output pixel is written by one thread (two 128-bit stores): no atomics, no LDS.  Every index into a plane is 64-bit; every read of
  * the previous frame is behind its inside-the-image test; rows * cols < 2^32 is checked by the entry point.
  */
-#include "rt_api_internal.h"
+#include "rt_image_kernel.h"
 #include "rt_temporal.h"
 
 namespace rt {
-
-#define RT_TEMPORAL_THREADS 256u
-#define RT_TEMPORAL_MAX_GROUPS (1u << 16)
-
-__global__ __launch_bounds__(RT_TEMPORAL_THREADS) void temporal_motion_kernel(const TemporalMotion m) {
-    const uint64_t stride = (uint64_t)gridDim.x * RT_TEMPORAL_THREADS;
-    for (uint64_t i = (uint64_t)blockIdx.x * RT_TEMPORAL_THREADS + threadIdx.x; i < m.n; i += stride) temporal_project(m, i);
-}
-
-__global__ __launch_bounds__(RT_TEMPORAL_THREADS) void temporal_accumulate_kernel(const TemporalCall t) {
-    const uint64_t n = (uint64_t)t.rows * t.cols, stride = (uint64_t)gridDim.x * RT_TEMPORAL_THREADS;
-    for (uint64_t i = (uint64_t)blockIdx.x * RT_TEMPORAL_THREADS + threadIdx.x; i < n; i += stride) temporal_pixel(t, i);
-}
-
-static dim3 temporal_grid(uint64_t n) {
-    return dim3((uint32_t)std::min<uint64_t>((n + RT_TEMPORAL_THREADS - 1u) / RT_TEMPORAL_THREADS, max_groups(OPT_DIAG_TEMPORAL_MAX_GROUPS, RT_TEMPORAL_MAX_GROUPS)));
-}
 
 static hipError_t launch_motion(const float *position, uint32_t position_stride, const uint32_t *valid, uint32_t valid_stride, const rt_camera *camera,
                                 const rt_frame *frame, float *motion, hipStream_t stream) {
@@ -40,14 +24,10 @@ static hipError_t launch_motion(const float *position, uint32_t position_stride,
     m.cam = temporal_camera(camera, frame);
     m.position = position, m.valid = valid, m.position_stride = position_stride, m.valid_stride = valid_stride, m.motion = motion;
     m.n = (uint64_t)frame->width * frame->height;
-    hipLaunchKernelGGL(temporal_motion_kernel, temporal_grid(m.n), dim3(RT_TEMPORAL_THREADS), 0, stream, m);
-    return hipGetLastError();
+    return launch_each(m, OPT_DIAG_TEMPORAL_MAX_GROUPS, stream);
 }
 
-static hipError_t launch_accumulate(const TemporalCall &t, hipStream_t stream) {
-    hipLaunchKernelGGL(temporal_accumulate_kernel, temporal_grid((uint64_t)t.rows * t.cols), dim3(RT_TEMPORAL_THREADS), 0, stream, t);
-    return hipGetLastError();
-}
+static hipError_t launch_accumulate(const TemporalCall &t, hipStream_t stream) { return launch_each(t, OPT_DIAG_TEMPORAL_MAX_GROUPS, stream); }
 
 } /* namespace rt */
 
@@ -102,17 +82,9 @@ int rt_temporal_accumulate_host(const float *h_color, const float *h_motion, con
     if (rows == 0u || cols == 0u) return RT_OK;
     const size_t n = (size_t)rows * cols;
     HostRoundTrip t("rt_temporal_accumulate_host");
-    const auto upload = [&](const rt_temporal_guides &h) {
-        rt_temporal_guides g = h;
-        g.normal = t.plane(h.normal, n, h.normal_stride, 3u);
-        g.position = t.plane(h.position, n, h.position_stride, 3u);
-        g.object = t.plane(h.object, n, h.object_stride, 1u);
-        g.valid = t.plane(h.valid, n, h.valid_stride, 1u);
-        return g;
-    };
     const float *d_color = t.in(h_color, n * 3u * sizeof(float));
     const float *d_motion = t.in(h_motion, n * 2u * sizeof(float));
-    const rt_temporal_guides cur = upload(*current), prev = upload(*previous);
+    const rt_temporal_guides cur = t.temporal_guides(*current, n), prev = t.temporal_guides(*previous, n);
     const rt_temporal_pixel *d_in = t.in(h_history_in, n * sizeof(rt_temporal_pixel));
     rt_temporal_pixel *d_out = t.out(h_history_out, n * sizeof(rt_temporal_pixel));
     float *d_variance = t.out(h_variance, n * sizeof(float));

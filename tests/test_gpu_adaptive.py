@@ -67,6 +67,17 @@ def test_budget_equals_the_cpu_definition(cap):
                 assert np.array_equal(host(adaptive.budget(dev(mean), dev(variance), **kw)), adaptive.budget_numpy(mean, variance, **kw))
 
 
+@pytest.mark.parametrize("n", [1, 255, 256, 257])
+def test_budget_around_one_workgroup_of_elements_under_one_workgroup(n):
+    """the element loop both libraries run: one element, a workgroup of them less one, exactly one, and one more that the only workgroup
+    takes in its second stride"""
+    mean, variance, count, valid = S.budget_case(n)
+    kw = dict(gain=8.0, min_count=1, max_count=16)
+    with capped(1):
+        got = adaptive.budget(dev(mean), dev(variance), dev(count), dev(valid), **kw)
+        assert np.array_equal(host(got), adaptive.budget_numpy(mean, variance, count, valid, **kw))
+
+
 # ---- the list ----
 
 @pytest.mark.parametrize("cap", CAPS)

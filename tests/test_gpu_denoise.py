@@ -106,6 +106,18 @@ def test_result_does_not_depend_on_the_launch_geometry(form, cap):
         assert np.array_equal(bits(got), bits(cpu_result(70, 1, 2, 1, **CONFIGS[1])))
 
 
+def test_the_tiled_form_at_step_16_on_a_ragged_image_under_one_workgroup():
+    """the stager with a step, one workgroup striding every residue class.  17 x 33 through levels 0 .. 4 and at level 4 alone: at step 16
+    the image is one block of 256 x 256 pixels whose 256 classes all start inside it and reach across it with most of their 20 x 20 entries
+    outside; the uniform `continue` ahead of the first barrier is taken at step 2 only, where the second block's odd columns start at
+    column 33.  17 x 257 at level 4: the second block holds column 256 alone, so 15 of every 16 of its classes start outside the image
+    and take the `continue` at step 16"""
+    with rt.options(RT_AMD_DENOISE_FORM=1, RT_AMD_DIAG_DENOISE_MAX_GROUPS=1):
+        for rows, cols, first, levels in ((17, 33, 0, 5), (17, 33, 4, 1), (17, 257, 4, 1)):
+            got = device_result(rows, cols, first, levels, **CONFIGS[1])
+            assert np.array_equal(bits(got), bits(cpu_result(rows, cols, first, levels, **CONFIGS[1]))), (rows, cols, first, levels)
+
+
 @pytest.mark.parametrize("form", FORMS)
 def test_on_a_stream_and_in_a_captured_graph(form):
     torch = torch_device()

@@ -67,6 +67,21 @@ def test_bounds_equal_the_cpu_definition(rows, cols, radius, cap):
             assert S.same_or_both_nan(host(got), want), planes
 
 
+@pytest.mark.parametrize("radius", S.RADII)
+def test_bounds_of_a_ragged_image_with_a_checkerboard_of_sources_under_one_workgroup(radius):
+    """the halo stager, its ring and the image's edge together: 17 x 33 is 2 x 3 tiles whose last row and column are one pixel wide, one
+    workgroup strides all six, every second source is cleared and the object changes across the tile border at column 16"""
+    rows, cols = 17, 33
+    color = S.case_data(rows, cols)[0]
+    r, c = np.meshgrid(np.arange(rows), np.arange(cols), indexing="ij")
+    valid = ((r + c) % 2 == 0).reshape(-1).astype(np.uint32)
+    obj = (c >= 16).reshape(-1).astype(np.uint32)
+    want = rectify.bounds_numpy(color, rows, cols, object=obj, valid=valid, gamma=1.25, radius=radius)
+    with rt.options(**{OPTION: 1}):
+        got = rectify.bounds(dev(color), rows, cols, object=dev(obj), valid=dev(valid), gamma=1.25, radius=radius)
+        assert S.same_or_both_nan(host(got), want)
+
+
 # ---- rt_temporal_accumulate_bounded and rt_temporal_feedback: one thread per pixel ----
 
 @pytest.mark.parametrize("cap", [None, 1])

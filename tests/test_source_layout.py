@@ -1,6 +1,6 @@
 """The layout of csrc/: no file includes another unit's source, and every *.hip there is exactly one object of the Makefile.
 Kernels that two units instantiate are templates in headers (rt_whitted_kernel.h, rt_pwf_kernel.h, rt_dist_kernels.h, rt_rng.h, rt_atrous_kernel.h,
-rt_film_splat_kernel.h).
+rt_film_splat_kernel.h); the launch shape the image-side units share is rt_image_kernel.h.
 Pure text: needs no build."""
 import re
 from pathlib import Path

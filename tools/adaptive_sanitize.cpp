@@ -1,7 +1,8 @@
 /*
- * adaptive_sanitize.cpp — the five CPU forms of the adaptive sampling queries (include/rt_host.h) on their edge inputs, and
- * rt_film_splat_host, which shares the listed splat's walk, as a stand-alone program for AddressSanitizer and UndefinedBehaviorSanitizer.  Every array is a heap allocation of exactly the size the interface
- * states, so a read or write one element outside it is reported.  Build and run, from the repository root (no device, no Python):
+ * adaptive_sanitize.cpp — the five CPU forms of the adaptive sampling queries (include/rt_host.h) on their edge inputs, rt_film_splat_host,
+ * which shares the listed splat's walk, and the other CPU forms that go through the one element loop, as a stand-alone program for
+ * AddressSanitizer and UndefinedBehaviorSanitizer.  Every array is a heap allocation of exactly the size the interface states, so a read or
+ * write one element outside it is reported.  Build and run, from the repository root (no device, no Python):
  *
  *   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -ffp-contract=off -fno-fast-math \
  *       -o /tmp/adaptive_sanitize tools/adaptive_sanitize.cpp homework-18-graphics-raytracer_amd/csrc/host/rt_host.cpp -lz \
@@ -152,7 +153,65 @@ static void uniform_splat_edges() {
     EXPECT(rt_film_splat_host(1, 1, nullptr, nullptr, nullptr, spp, RT_FILM_BOX, 4.5f, nullptr, nullptr) == RT_ERR_INVALID_ARGUMENT);
 }
 
+/* The CPU forms that run an Op of a shared header through rt_host.cpp's one element loop, beside the budget and the listed offsets above:
+ * the temporal, rectification and denoise queries on a 3 x 5 image, 15 = count() elements, every plane of exactly the stated size */
+static void element_loops() {
+    const uint32_t rows = 3, cols = 5, n = rows * cols;
+    const rt_camera camera = {1.0f, {0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, -1.0f}, {0.0f, 1.0f, 0.0f}, 0.1f};
+    const rt_frame frame = {cols, rows, 1, 0u, 0u, cols, rows, 1u};
+    std::vector<float> position((n - 1) * 4 + 3, -2.0f), normal(3 * n, 0.0f), color(3 * n, 0.5f), motion(2 * n, 0.0f), variance(n, 9.0f), out(3 * n, 9.0f);
+    std::vector<uint32_t> valid(n, 1u), object(n, 7u), clamped(n, 99u);
+    for (uint32_t i = 0; i < n; ++i) normal[3 * i + 2] = 1.0f;
+    valid[n - 1] = 0u;
+    EXPECT(rt_temporal_motion_cpu(position.data(), 4, valid.data(), 1, &camera, &frame, motion.data()) == RT_OK);
+    EXPECT(motion[0] == motion[0] && motion[2 * n - 1] != motion[2 * n - 1]); /* projected; a cleared pixel is NaN */
+    for (uint32_t i = 0; i < n; ++i) motion[2 * i] = (float)(i % cols) + 0.5f, motion[2 * i + 1] = (float)(i / cols) + 0.5f;
+    position.assign(3 * n, -2.0f);
+    const rt_temporal_guides g = {normal.data(), position.data(), object.data(), valid.data(), 3u, 3u, 1u, 1u};
+    const rt_temporal_params p = {0.9f, 0.1f, 0.05f, 8u, 0u};
+    std::vector<rt_temporal_pixel> in(n, rt_temporal_pixel{{0.25f, 0.25f, 0.25f}, 0.25f, 0.0625f, 3u, {0u, 0u}}), hist(n), hist2(n);
+    EXPECT(rt_temporal_accumulate_cpu(color.data(), motion.data(), &g, &g, &p, rows, cols, in.data(), hist.data(), variance.data()) == RT_OK);
+    EXPECT(hist[0].length == 4u && hist[n - 1].length == 1u);
+    std::vector<rt_temporal_box> box(n);
+    const rt_bounds_params bp = {1.0f, 3u, 0u};
+    EXPECT(rt_temporal_bounds_cpu(color.data(), 3, object.data(), 1, valid.data(), 1, &bp, rows, cols, box.data()) == RT_OK);
+    EXPECT(rt_temporal_accumulate_bounded_cpu(color.data(), motion.data(), &g, &g, &p, rows, cols, in.data(), hist2.data(), nullptr, box.data(), 2u, clamped.data()) ==
+           RT_OK);
+    EXPECT(clamped[0] == 4u && hist2[0].length == 2u && clamped[n - 1] == 0u); /* 0.25 lies outside the box of a constant 0.5 */
+    EXPECT(rt_temporal_feedback_cpu(out.data(), 3, valid.data(), 1, rows, cols, hist2.data()) == RT_OK);
+    EXPECT(hist2[0].color[0] == 9.0f && hist2[0].length == 2u && hist2[n - 1].color[0] == 0.5f);
+    const rt_denoise_guides dg = {normal.data(), position.data(), nullptr, valid.data(), 3u, 3u, 0u, 1u};
+    const rt_denoise_params dp = {1.0f, 1.0f, 1.0f, 0u, 3u, 0u};
+    std::vector<float> temp(3 * n, 0.0f);
+    EXPECT(rt_denoise_atrous_cpu(color.data(), &dg, &dp, rows, cols, out.data(), temp.data()) == RT_OK);
+    EXPECT(out[0] == 0.5f && out[3 * n - 1] == 0.5f);
+    /* three levels: 16 + 4 bytes of scratch per pixel */
+    const rt_svgf_atrous_params sp = {1.0f, 1.0f, 1.0f, 0u, 3u, 0u};
+    std::vector<float> svgf_temp(5 * n, 0.0f), variance_out(n, 9.0f);
+    variance.assign(n, 0.25f);
+    EXPECT(rt_svgf_atrous_cpu(color.data(), 3, variance.data(), &dg, &sp, rows, cols, out.data(), variance_out.data(), svgf_temp.data()) == RT_OK);
+    EXPECT(out[0] == 0.5f && variance_out[0] >= 0.0f && variance_out[0] <= 0.25f);
+    /* one triangle that moved by (1, 0, 0) and one sphere that did not; a triangle hit, a sphere hit, a miss and an index out of range */
+    rt_triangle tri = {};
+    const float corners[3][3] = {{0.0f, 0.0f, 0.0f}, {1.0f, 0.0f, 0.0f}, {0.0f, 1.0f, 0.0f}};
+    for (int k = 0; k < 3; ++k) memcpy(tri.vertices[k].position, corners[k], sizeof corners[k]);
+    const rt_sphere sphere = {0u, {0.0f, 0.0f, 5.0f}, 1.0f};
+    rt_scene_desc now = {};
+    now.triangles = &tri, now.n_triangles = 1u, now.spheres = &sphere, now.n_spheres = 1u;
+    const std::vector<float> was_triangles = {1.0f, 0.0f, 0.0f, 2.0f, 0.0f, 0.0f, 1.0f, 1.0f, 0.0f}, was_spheres = {0.0f, 0.0f, 5.0f, 1.0f};
+    std::vector<rt_hit> hits(4);
+    memset(hits.data(), 0, hits.size() * sizeof(rt_hit));
+    hits[0].kind = 1u, hits[0].position[0] = 0.25f, hits[0].position[1] = 0.25f;
+    hits[1].kind = 0u, hits[1].position[2] = 4.0f;
+    hits[2].kind = 0xffffffffu;
+    hits[3].kind = 1u, hits[3].index = 1u;
+    std::vector<float> was((hits.size() - 1) * 4 + 3, 9.0f);
+    EXPECT(rt_previous_positions_cpu(&now, was_triangles.data(), was_spheres.data(), hits.data(), hits.size(), was.data(), 4) == RT_OK);
+    EXPECT(was[0] == 1.25f && was[1] == 0.25f && was[3] == 9.0f && was[4 + 2] == 4.0f && was[8] != was[8] && was[12] != was[12]);
+}
+
 int main() {
+    element_loops();
     budget_edges();
     list_edges();
     listed_edges();
