@@ -25,6 +25,7 @@
 #include "../rt_rectify.h"
 #include "../rt_motion.h"
 #include "../rt_adaptive.h"
+#include "../rt_upsample.h"
 
 using rt::V3;
 
@@ -720,6 +721,18 @@ int rt_temporal_feedback_cpu(const float *color, uint32_t color_stride, const ui
     if (bad) return fail(status, std::string("rt_temporal_feedback_cpu: ") + bad);
     if (rows == 0u || cols == 0u) return RT_OK;
     each(rt::RectifyFeedback{color, valid, color_stride, valid_stride, (uint64_t)rows * cols, history});
+    return RT_OK;
+}
+
+/* ---- guided upsampling queries: the CPU definition (include/rt_amd.h "guided upsampling queries"; the arithmetic is rt_upsample.h's, shared with the device) ---- */
+
+int rt_upsample_guided_cpu(const float *color_lo, uint32_t color_stride, const rt_denoise_guides *low, const uint32_t *object_lo, uint32_t object_lo_stride,
+                           const rt_denoise_guides *full, const uint32_t *object_full, uint32_t object_full_stride, const rt_upsample_params *params,
+                           uint32_t rows, uint32_t cols, float *out) {
+    const char *bad = rt::upsample_limits(color_lo, color_stride, low, object_lo, object_lo_stride, full, object_full, object_full_stride, params, rows, cols, out);
+    if (bad) return fail(RT_ERR_INVALID_ARGUMENT, std::string("rt_upsample_guided_cpu: ") + bad);
+    if (rows == 0u || cols == 0u) return RT_OK;
+    each(rt::upsample_call(color_lo, color_stride, *low, object_lo, object_lo_stride, *full, object_full, object_full_stride, *params, rows, cols, out));
     return RT_OK;
 }
 

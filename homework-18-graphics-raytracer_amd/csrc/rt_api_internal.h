@@ -26,6 +26,7 @@
  *   rt_temporal_query.hip the temporal queries' rt_temporal_motion / rt_temporal_accumulate and their _host forms: kernels and entry points in one unit
  *   rt_rectify_query.hip the history rectification queries' rt_temporal_bounds / rt_temporal_accumulate_bounded / rt_temporal_feedback and their _host forms: kernels and entry points in one unit
  *   rt_adaptive_query.hip the adaptive sampling queries' rt_sample_budget / rt_sample_list / rt_film_offsets_listed / rt_camera_rays_listed / rt_film_splat_listed: kernels and entry points in one unit
+ *   rt_upsample_query.hip the guided upsampling queries' rt_upsample_guided and its _host form: kernels and entry points in one unit
  *   rt_svgf_query.hip    the variance-guided filter queries' rt_svgf_variance / rt_svgf_atrous, their _host forms and rt_svgf_temp_bytes: kernels and entry points in one unit
  * The film queries' kernels are rt_film_query.hip; their entry points are rt_api_query.hip's (rt_camera_rays_offset, beside rt_camera_rays) and
  * rt_api_post.hip's (rt_film_offsets / rt_film_splat, beside the accumulator).  The two splats, rt_film_query.hip's and

@@ -1641,6 +1641,80 @@ int rt_svgf_variance_host(const rt_temporal_pixel *h_history, const rt_denoise_g
 int rt_svgf_atrous_host(const float *h_color, uint32_t color_stride, const float *h_variance, const rt_denoise_guides *guides,
                         const rt_svgf_atrous_params *params, uint32_t rows, uint32_t cols, float *h_out, float *h_variance_out);
 
+/* ---- guided upsampling queries: low-resolution radiance onto full-size guides ------------------------
+
+ * What makes a frame cheaper everywhere instead of where it is easy: the radiance — the expensive part — rendered at 1/s of the
+ * resolution each way, the guide planes (rt_probe_surfaces on the primary hits: position, shading normal, albedo, object, valid) at
+ * full resolution, and the radiance carried up onto them by a joint bilateral upsample (Kopf et al., "Joint Bilateral Upsampling",
+ * SIGGRAPH 2007).  With the albedo divided out below and multiplied back above, texture detail returns at full resolution; the object
+ * test and the normal and position terms keep geometric edges sharp.
+ *     rt_probe_surfaces (low) -> radiance (low) -> rt_probe_surfaces (full) -> rt_upsample_guided -> rt_post_process_device
+ * The low image is taken at the CENTRES of the s x s blocks of output pixels (step 2).  rt_camera_rays shoots through a pixel's integer
+ * coordinate, so the low frame's own rays look where output pixel j s looks, (s - 1) / 2 output pixels off: take the low rays from
+ * rt_camera_rays_offset on the low frame with the offset (s - 1) / (2 s) both ways, and trace and probe those.
+ * The reference has no counterpart; the definition below is the contract.  It is written once (csrc/rt_upsample.h, on the guide readers,
+ * the weight terms and e(x) of csrc/rt_atrous.h) and compiled into both libraries without contraction, so the device form (either
+ * kernel form, any launch geometry), the _host form and rt_upsample_guided_cpu (librt_host.so, include/rt_host.h) return the same bits.
+ * The device call is ONE stream-ordered kernel launch on hip_stream, allocates nothing, visits the host for nothing and may be captured
+ * into a HIP graph at once.  Every output word is written by one thread: no atomics, nothing depends on the launch.
+ *
+ * Planes are those of the denoise queries: a base pointer and a record stride in 4-byte WORDS, pixel i = r * cols + c.  rows and cols
+ * are the OUTPUT's; the low-resolution image has rows_lo = ceil(rows / s) rows and cols_lo = ceil(cols / s) columns, s = scale, derived
+ * and not passed.  color_lo: 3 f32 per low pixel at color_stride words (the colour inside rt_temporal_pixel records, stride 8, goes in
+ * where it lies).  `low` and `full` are rt_denoise_guides of the two resolutions; object_lo / object_full one word per pixel at their
+ * strides, or NULL.  out: 3 f32 per output pixel, compact.  A guide term is ON where both guide sets carry its plane; the object test
+ * is on where both object planes are given.  Every operation is a single f32 operation in the order written, none fused; e(x) and dist2
+ * are the denoise queries'.  For output pixel p = (r, c), with R = radius:
+ *   1. nearest: N = (r / s, c / s) in integer division, a pixel of the low image.  If full->valid is not NULL and valid_p == 0, out_p is
+ *      the raw words of color_lo at N (a NaN keeps its payload), and nothing else is looked at.
+ *   2. the position in the low grid, in integers:  a = 2 r + 1 - s;   b_y = floor(a / 2 s)  (a floor: a is negative on the first rows);
+ *      n_y = a - 2 s * b_y  (0 .. 2 s - 1);   f_y = (float)n_y / (float)(2 s);   b_x, f_x the same from c.  The centre of output pixel r
+ *      lies at (2 r + 1 - s) / 2 s low pixels from the centre of low pixel 0.
+ *   3. sum_k = wsum = +0, and for dr = -(R - 1) .. R (outer), dc = -(R - 1) .. R (inner), both ascending, the source q = (b_y + dr, b_x + dc):
+ *        t_y = 1 - fabsf((float)dr - f_y) / (float)R;    t_x = 1 - fabsf((float)dc - f_x) / (float)R
+ *        skipped when t_y <= 0 or t_x <= 0; when q is outside the low image; when low->valid is not NULL and valid_q == 0
+ *        C_q = color_lo at q, divided by (albedo_q + 1e-3f) of the LOW albedo with RT_DENOISE_DEMODULATE_IN, channel by channel
+ *        skipped unless all three channels of C_q are finite (C - C == 0): one inf or NaN sample does not become a block of s x s
+ *        skipped when the object test is on and object_q != object_p
+ *        x = +0;   if normal:  x = x + dist2(n_p, n_q) / sn2;   if position:  x = x + dist2(P_p, P_q) / sp2     (sn2, sp2: the squared sigmas;
+ *        n_p, P_p of `full`, n_q, P_q of `low`);   skipped unless x >= 0
+ *        w = (t_y * t_x) * e(x);    sum_k = sum_k + C_q[k] * w;    wsum = wsum + w
+ *   4. if wsum > 0:  out_k = sum_k / wsum, multiplied by (albedo_p + 1e-3f) of the FULL albedo with RT_DENOISE_DEMODULATE_OUT;
+ *      otherwise out_p is the raw words of color_lo at N, as in 1.
+ * Consequences: with radius 1, both sigmas +inf and no object planes, valid everywhere, the result is the bilinear interpolation of the
+ * low image whose pixel centres coincide with step 2's positions, renormalised at the border; a constant low image whose value is a
+ * power of two returns itself; where the object test is on no colour crosses an object's edge.
+ *
+ * Checked before any device work, all RT_ERR_INVALID_ARGUMENT with a message that names the argument, in this order: a null params,
+ * low or full; rows * cols >= 2^32; scale outside 2 .. 4; radius outside 1 .. 2; a sigma that is not > 0 (NaN included; +inf is legal:
+ * the term is off); unknown flag bits; RT_DENOISE_DEMODULATE_IN without low->albedo, RT_DENOISE_DEMODULATE_OUT without full->albedo;
+ * a stride smaller than its plane's width (the guides of low, of full, color_stride < 3, an object stride < 1 of a plane that is
+ * given); then rows == 0 or cols == 0 is RT_OK and launches nothing; a null color_lo or out; out == color_lo.
+ * RT_AMD_UPSAMPLE_FORM (rt_set_option): 0 the plain kernel, every source read from global memory; 1 the tiled kernel, a workgroup's
+ * low-resolution window staged in LDS once; same bits (DESIGN.md 3.28 says which is the default and why).  RT_AMD_DIAG_UPSAMPLE_MAX_GROUPS:
+ * a test hook, the kernel launches at most this many workgroups and takes the rest of the image grid-stride; same bits.
+ * Not covered: banded frames and rt_multi_* forms; fractional scales and scales beyond 4; the variance plane and history records (a
+ * caller upsamples colour); a jitter of the low-resolution grid from frame to frame. */
+
+typedef struct rt_upsample_params {
+    float sigma_normal;
+    float sigma_position;     /* each > 0, +inf: the term is off */
+    uint32_t scale;           /* s: 2, 3 or 4 output pixels per low pixel, each way */
+    uint32_t radius;          /* R: 1 or 2, a window of (2 R)^2 low pixels; 1 is the bilinear footprint */
+    uint32_t flags;           /* RT_DENOISE_DEMODULATE_* */
+} rt_upsample_params;        /* 20 bytes */
+
+/* d_color_lo: ceil(rows / s) * ceil(cols / s) pixels of 3 f32 at color_stride words; low / d_object_lo: planes of that many pixels;
+ * full / d_object_full: planes of rows * cols pixels; d_out: rows * cols * 3 f32; one kernel launch.  Nothing but d_out is written. */
+int rt_upsample_guided(const float *d_color_lo, uint32_t color_stride, const rt_denoise_guides *low, const uint32_t *d_object_lo,
+                       uint32_t object_lo_stride, const rt_denoise_guides *full, const uint32_t *d_object_full, uint32_t object_full_stride,
+                       const rt_upsample_params *params, uint32_t rows, uint32_t cols, float *d_out, void *hip_stream);
+/* The same kernel on HOST arrays (the pointers of the guide sets are host pointers too): allocate, upload every plane with its stride,
+ * run, synchronise the device and download.  NOT the CPU definition — that is rt_upsample_guided_cpu of librt_host.so. */
+int rt_upsample_guided_host(const float *h_color_lo, uint32_t color_stride, const rt_denoise_guides *low, const uint32_t *h_object_lo,
+                            uint32_t object_lo_stride, const rt_denoise_guides *full, const uint32_t *h_object_full, uint32_t object_full_stride,
+                            const rt_upsample_params *params, uint32_t rows, uint32_t cols, float *h_out);
+
 /* ---- diagnostics ------------------------------------------------------------ */
 
 /* Which kernel renders the Whitted pass (process-wide; same results bit for bit):
@@ -1658,7 +1732,7 @@ int rt_svgf_atrous_host(const float *h_color, uint32_t color_stride, const float
  * RT_AMD_DIST_BY_COST, RT_AMD_DIST_OWN_FIRST, RT_AMD_DIST_PREP_FIRST, RT_AMD_DIST_SPLIT, RT_AMD_DIAG_WS_REFUSE,
  * RT_AMD_MULTI_FORCE_STAGE, RT_AMD_BFS_WALK_TRIANGLES (read by rt_scene_create), RT_AMD_WF_SHARE, RT_AMD_DIAG_BFS_CAP,
  * RT_AMD_DIAG_DIST_BAND_RAYS, RT_AMD_QUERY_WAVE_UNIFORM, RT_AMD_DIAG_HIT_BAND_RECORDS, RT_AMD_FILM_SPLAT_FORM, RT_AMD_DIAG_FILM_MAX_GROUPS,
- * RT_AMD_DENOISE_FORM, RT_AMD_DIAG_DENOISE_MAX_GROUPS, RT_AMD_DIAG_TEMPORAL_MAX_GROUPS, RT_AMD_SVGF_FORM, RT_AMD_DIAG_SVGF_MAX_GROUPS, RT_AMD_DIAG_MOTION_MAX_GROUPS, RT_AMD_DIAG_RECTIFY_MAX_GROUPS, RT_AMD_DIAG_ADAPTIVE_MAX_GROUPS (INTEGRATION.md says what each does); any other name is RT_ERR_INVALID_ARGUMENT.  The environment is read ONCE per process, at the first use;
+ * RT_AMD_DENOISE_FORM, RT_AMD_DIAG_DENOISE_MAX_GROUPS, RT_AMD_DIAG_TEMPORAL_MAX_GROUPS, RT_AMD_SVGF_FORM, RT_AMD_DIAG_SVGF_MAX_GROUPS, RT_AMD_DIAG_MOTION_MAX_GROUPS, RT_AMD_DIAG_RECTIFY_MAX_GROUPS, RT_AMD_DIAG_ADAPTIVE_MAX_GROUPS, RT_AMD_UPSAMPLE_FORM, RT_AMD_DIAG_UPSAMPLE_MAX_GROUPS (INTEGRATION.md says what each does); any other name is RT_ERR_INVALID_ARGUMENT.  The environment is read ONCE per process, at the first use;
  * after that only this call changes a switch: value = decimal integer, NULL or "" = unset (the library's own choice).  Render
  * calls read the switches without locks: set them between calls, not during one. */
 int rt_set_option(const char *name, const char *value);

@@ -134,6 +134,14 @@ int rt_temporal_accumulate_bounded_cpu(const float *color, const float *motion, 
 int rt_temporal_feedback_cpu(const float *color, uint32_t color_stride, const uint32_t *valid, uint32_t valid_stride, uint32_t rows,
                              uint32_t cols, rt_temporal_pixel *history);
 
+/* The guided upsampling queries' CPU definition (include/rt_amd.h "guided upsampling queries" states every operation and the order): a
+ * plain loop over host arrays, no device needed, bit-identical to rt_upsample_guided of librt_amd.so.  Same arguments without the
+ * stream, same checks with the same messages; a failure returns a negative rt_status and sets rt_host_last_error().  Called _cpu for
+ * the reason rt_denoise_atrous_cpu is. */
+int rt_upsample_guided_cpu(const float *color_lo, uint32_t color_stride, const rt_denoise_guides *low, const uint32_t *object_lo,
+                           uint32_t object_lo_stride, const rt_denoise_guides *full, const uint32_t *object_full, uint32_t object_full_stride,
+                           const rt_upsample_params *params, uint32_t rows, uint32_t cols, float *out);
+
 /* The adaptive sampling queries' CPU definition (include/rt_amd.h "adaptive sampling queries" states every operation and the order): plain
  * loops over host arrays, no device needed, bit-identical to rt_sample_budget / rt_sample_list / rt_film_offsets_listed /
  * rt_camera_rays_listed / rt_film_splat_listed of librt_amd.so.  Same arguments without the stream (and, for the list, without the
