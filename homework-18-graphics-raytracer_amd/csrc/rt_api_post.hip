@@ -12,6 +12,29 @@
 
 namespace rt {
 void math_eval_host(int op, const float *x, const float *y, float *out, size_t n);
+void math_eval_host(int op, const double *a, const double *b, double *out, size_t n);
+}
+
+/* rt_math_eval_device and rt_math_eval64_device: the operands to the device, one launch, the results back */
+template <typename T>
+static int math_eval_round_trip(const char *who, int op, const T *h_x, const T *h_y, T *h_out, size_t n) {
+    if (!h_x || !h_out) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": null argument");
+    if (n == 0) return RT_OK;
+    T *d_x = nullptr, *d_y = nullptr, *d_o = nullptr;
+    const size_t bytes = n * sizeof(T);
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(&d_x), bytes);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_y), bytes);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_o), bytes);
+    if (e == hipSuccess) e = hipMemcpy(d_x, h_x, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = h_y ? hipMemcpy(d_y, h_y, bytes, hipMemcpyHostToDevice) : hipMemset(d_y, 0, bytes);
+    if (e == hipSuccess) e = rt::launch_math_eval(op, d_x, d_y, d_o, n, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(h_out, d_o, bytes, hipMemcpyDeviceToHost);
+    if (d_x) (void)hipFree(d_x);
+    if (d_y) (void)hipFree(d_y);
+    if (d_o) (void)hipFree(d_o);
+    if (e != hipSuccess) return fail_hip(who, e);
+    return RT_OK;
 }
 
 extern "C" {
@@ -152,23 +175,17 @@ int rt_math_eval_host(int op, const float *x, const float *y, float *out, size_t
 }
 
 int rt_math_eval_device(int op, const float *h_x, const float *h_y, float *h_out, size_t n) {
-    if (!h_x || !h_out) return fail(RT_ERR_INVALID_ARGUMENT, "rt_math_eval_device: null argument");
-    if (n == 0) return RT_OK;
-    float *d_x = nullptr, *d_y = nullptr, *d_o = nullptr;
-    const size_t bytes = n * sizeof(float);
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&d_x), bytes);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_y), bytes);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_o), bytes);
-    if (e == hipSuccess) e = hipMemcpy(d_x, h_x, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = h_y ? hipMemcpy(d_y, h_y, bytes, hipMemcpyHostToDevice) : hipMemset(d_y, 0, bytes);
-    if (e == hipSuccess) e = rt::launch_math_eval(op, d_x, d_y, d_o, n, nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(h_out, d_o, bytes, hipMemcpyDeviceToHost);
-    if (d_x) (void)hipFree(d_x);
-    if (d_y) (void)hipFree(d_y);
-    if (d_o) (void)hipFree(d_o);
-    if (e != hipSuccess) return fail_hip("rt_math_eval_device", e);
+    return math_eval_round_trip("rt_math_eval_device", op, h_x, h_y, h_out, n);
+}
+
+int rt_math_eval64_host(int op, const double *a, const double *b, double *out, size_t n) {
+    if (!a || !out) return fail(RT_ERR_INVALID_ARGUMENT, "rt_math_eval64_host: null argument");
+    rt::math_eval_host(op, a, b, out, n);
     return RT_OK;
+}
+
+int rt_math_eval64_device(int op, const double *h_a, const double *h_b, double *h_out, size_t n) {
+    return math_eval_round_trip("rt_math_eval64_device", op, h_a, h_b, h_out, n);
 }
 
 } /* extern "C" */

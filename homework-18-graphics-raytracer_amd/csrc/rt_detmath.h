@@ -10,7 +10,9 @@
  * integer ops and comparisons (all IEEE-754 exact operations, no fma, no libm),
  * then round ONCE to binary32.  Compiled with -ffp-contract=off they return
  * identical bits from g++ on x86-64 and from hipcc on gfx950, and the binary64
- * intermediate (rel. error < 2^-48) makes the result the correctly rounded
+ * intermediate (rel. error < 2^-48 for binary32 operands widened, whose
+ * quotients stay normal doubles; tests/test_detmath_cpu.py measures 2^-51.5)
+ * makes the result the correctly rounded
  * binary32 value except when the exact value lies within ~2^-24 ulp of a
  * rounding boundary — i.e. it agrees with any "< 1 ulp" libm to within the last
  * bit and with a correctly rounded one almost always.

@@ -304,8 +304,9 @@ hipError_t launch_cast_rays_indexed_bfs(const KernelScene &sc, const rt_ray *ray
 /* the level loop's selection (rt_level_query.hip): at most this many workgroups, one block total each in a scratch of as many words */
 #define RT_SELECT_MAX_GROUPS 1024u
 
-/* diagnostics: evaluate rt_detmath on the device (op codes = rt_math_op) */
+/* diagnostics: evaluate rt_detmath on the device (op codes = rt_math_op; for doubles rt_math64_op) */
 hipError_t launch_math_eval(int op, const float *d_x, const float *d_y, float *d_out, size_t n, hipStream_t stream);
+hipError_t launch_math_eval(int op, const double *d_a, const double *d_b, double *d_out, size_t n, hipStream_t stream);
 
 } /* namespace rt */
 

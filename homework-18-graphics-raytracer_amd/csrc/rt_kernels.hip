@@ -75,7 +75,25 @@ __host__ __device__ float math_eval_one(int op, float x, float y) {
             rtdm::sincosf(x, &s, &c);
             return op == RT_MATH_SINCOS_SIN ? s : c;
         }
+        case RT_MATH_F32_AS_I32: return rtdm::f32_from_bits((uint32_t)rtdm::f32_as_i32(x));
+        case RT_MATH_IS_NORMAL: return rtdm::is_normal(x) ? 1.0f : 0.0f;
+        case RT_MATH_INT_CLASS: return (float)rtdm::f32_int_class(x);
         default: return 0.0f;
+    }
+}
+
+/* the binary64 primitives and intermediates under the f32 results above, returned whole (op codes = rt_math64_op) */
+__host__ __device__ double math_eval64_one(int op, double a, double b) {
+    switch (op) {
+        case RT_MATH64_DIV: return a / b;
+        case RT_MATH64_SQRT: return rtdm::d_sqrt(a);
+        case RT_MATH64_NARROW: return (double)(float)a;
+        case RT_MATH64_ROUND_I32: return (double)rtdm::d_round_to_i32(a);
+        case RT_MATH64_FROM_I64: return (double)(int64_t)rtdm::f64_bits(a);
+        case RT_MATH64_EXP_MID: return rtdm::exp_mid(a);
+        case RT_MATH64_LOG_POS: return rtdm::log_pos(a);
+        case RT_MATH64_ATAN2_UPPER: return rtdm::atan2_upper(a, b);
+        default: return 0.0;
     }
 }
 
@@ -84,16 +102,34 @@ __global__ void math_eval_kernel(int op, const float *__restrict__ x, const floa
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[i] = math_eval_one(op, x[i], y[i]);
 }
 
+__global__ void math_eval64_kernel(int op, const double *__restrict__ a, const double *__restrict__ b, double *__restrict__ out, size_t n) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[i] = math_eval64_one(op, a[i], b[i]);
+}
+
+static unsigned math_eval_blocks(size_t n) {
+    const size_t blocks = (n + 255) / 256;
+    return blocks > 4096 ? 4096u : (unsigned)blocks;
+}
+
 hipError_t launch_math_eval(int op, const float *d_x, const float *d_y, float *d_out, size_t n, hipStream_t stream) {
     if (n == 0) return hipSuccess;
-    size_t blocks = (n + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(math_eval_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, op, d_x, d_y, d_out, n);
+    hipLaunchKernelGGL(math_eval_kernel, dim3(math_eval_blocks(n)), dim3(256), 0, stream, op, d_x, d_y, d_out, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_math_eval(int op, const double *d_a, const double *d_b, double *d_out, size_t n, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(math_eval64_kernel, dim3(math_eval_blocks(n)), dim3(256), 0, stream, op, d_a, d_b, d_out, n);
     return hipGetLastError();
 }
 
 void math_eval_host(int op, const float *x, const float *y, float *out, size_t n) {
     for (size_t i = 0; i < n; ++i) out[i] = math_eval_one(op, x[i], y ? y[i] : 0.0f);
+}
+
+void math_eval_host(int op, const double *a, const double *b, double *out, size_t n) {
+    for (size_t i = 0; i < n; ++i) out[i] = math_eval64_one(op, a[i], b ? b[i] : 0.0);
 }
 
 } /* namespace rt */

@@ -1786,10 +1786,29 @@ typedef enum rt_math_op {
     RT_MATH_F64_SQRT_HI = 8, RT_MATH_F64_SQRT_LO = 9,   /* sqrt((double)x * (double)y) */
     RT_MATH_F64_DIV_HI = 10, RT_MATH_F64_DIV_LO = 11,   /* (double)x / (double)y */
     RT_MATH_ROUND = 12,
-    RT_MATH_SINCOS_SIN = 13, RT_MATH_SINCOS_COS = 14    /* the two results of the fused sincosf the kernels call */
+    RT_MATH_SINCOS_SIN = 13, RT_MATH_SINCOS_COS = 14,   /* the two results of the fused sincosf the kernels call */
+    RT_MATH_F32_AS_I32 = 15,  /* f32_as_i32(x), the i32 as an f32 bit pattern */
+    RT_MATH_IS_NORMAL = 16,   /* is_normal(x): 0.0f or 1.0f */
+    RT_MATH_INT_CLASS = 17    /* f32_int_class(x) as a float: 0 not an integer, 1 odd, 2 even */
 } rt_math_op;
 int rt_math_eval_host(int op, const float *x, const float *y, float *out, size_t n);
 int rt_math_eval_device(int op, const float *h_x, const float *h_y, float *h_out, size_t n);
+
+/* The binary64 primitives those f32 results rest on, and three binary64 intermediates, each returned as a whole double so that
+ * tests compare all 64 bits of host and device.  op is an rt_math64_op; b is ignored by unary ops (and may be NULL).  Operands
+ * outside an op's stated domain are the caller's mistake: nothing is checked. */
+typedef enum rt_math64_op {
+    RT_MATH64_DIV = 0,          /* a / b */
+    RT_MATH64_SQRT = 1,         /* d_sqrt(a) */
+    RT_MATH64_NARROW = 2,       /* (double)(float)a: the f64 -> f32 rounding */
+    RT_MATH64_ROUND_I32 = 3,    /* (double)d_round_to_i32(a), |a| < 2^31 - 1 */
+    RT_MATH64_FROM_I64 = 4,     /* (double)(int64_t)bits(a): a's bit pattern read as an i64 and converted */
+    RT_MATH64_EXP_MID = 5,      /* exp_mid(a), |a| <= 200 */
+    RT_MATH64_LOG_POS = 6,      /* log_pos(a), finite a > 0 */
+    RT_MATH64_ATAN2_UPPER = 7   /* atan2_upper(a, b): a >= 0 the ordinate, not NaN, not both zero or both infinite */
+} rt_math64_op;
+int rt_math_eval64_host(int op, const double *a, const double *b, double *out, size_t n);
+int rt_math_eval64_device(int op, const double *h_a, const double *h_b, double *h_out, size_t n);
 
 /* The node array rt_scene_create builds over the triangles for the intersection loop (csrc/rt_device_scene.h: a pre-order
  * array of leaves — runs of consecutive triangles — and inner nodes with skip pointers), computed on the host without

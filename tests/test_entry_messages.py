@@ -118,6 +118,8 @@ SIGNATURES = {
     "rt_encode_srgb8_device": [("rgb", P), ("n", 6), ("out", P), ("stream", None)],
     "rt_math_eval_host": [("op", 0), ("x", P), ("y", P), ("out", P), ("n", 2)],
     "rt_math_eval_device": [("op", 0), ("x", P), ("y", P), ("out", P), ("n", 2)],
+    "rt_math_eval64_host": [("op", 0), ("a", P), ("b", P), ("out", P), ("n", 2)],
+    "rt_math_eval64_device": [("op", 0), ("a", P), ("b", P), ("out", P), ("n", 2)],
 }
 
 RECORDS = "2^32 records or more (checked first; query them in several calls)"
@@ -421,6 +423,11 @@ CASES = [
     ("rt_math_eval_host", _null("x"), INVALID, "rt_math_eval_host: null argument"),
     ("rt_math_eval_device", _null("out"), INVALID, "rt_math_eval_device: null argument"),
     ("rt_math_eval_device", {"n": 0}, OK, None),
+    ("rt_math_eval64_host", _null("a"), INVALID, "rt_math_eval64_host: null argument"),
+    ("rt_math_eval64_host", _null("out"), INVALID, "rt_math_eval64_host: null argument"),
+    ("rt_math_eval64_device", _null("a"), INVALID, "rt_math_eval64_device: null argument"),
+    ("rt_math_eval64_device", _null("out"), INVALID, "rt_math_eval64_device: null argument"),
+    ("rt_math_eval64_device", {"n": 0}, OK, None),
 ]
 
 
