@@ -35,7 +35,7 @@ reference's host-side names on top of them:
 
 PyTorch is used only for device memory, streams and torch.distributed.
 """
-from . import _capi, adaptive, denoise, film, materials, moving, rectify, svgf, temporal, upsample
+from . import _capi, adaptive, denoise, diagnostics, film, materials, moving, rectify, svgf, temporal, upsample
 from ._capi import Camera, Frame, Light, Material, RtError, SceneDesc, Sphere, Triangle, Vertex
 from ._world import DEFAULT_OBJ, ObjectProxy, Scene, World, reference_camera, reference_world
 from ._render import (Rng, focus_rays, options, render_distributed, render_distributed_numpy, render_whitted, render_whitted_numpy,

@@ -251,7 +251,7 @@ AMD_SYMBOLS = [
     "rt_scene_keep_positions", "rt_scene_positions_kept", "rt_previous_positions", "rt_previous_positions_host",
     "rt_ray_keys", "rt_sort_temp_bytes", "rt_sort_records", "rt_gather_records", "rt_scatter_records",
     "rt_triangle_keys", "rt_order_triangles_temp_bytes", "rt_order_triangles", "rt_order_triangles_host",
-    "rt_diag_scene_nodes",
+    "rt_diag_scene_nodes", "rt_diag_pwf_plan", "rt_diag_pwf_plan_rays", "rt_diag_pwf_outcome",
 ]
 HOST_SYMBOLS = [
     "rt_world_new", "rt_world_free", "rt_world_push_object", "rt_world_push_triangle", "rt_world_push_sphere",
@@ -519,6 +519,9 @@ def amd_lib() -> C.CDLL:
         lib.rt_order_triangles_host.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.c_void_p, C.c_void_p]
         lib.rt_scene_describe_nodes.argtypes = [C.POINTER(SceneDesc), C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32)]
         lib.rt_diag_scene_nodes.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        lib.rt_diag_pwf_plan.argtypes = [C.c_void_p, C.POINTER(Frame), C.c_void_p, C.c_void_p]
+        lib.rt_diag_pwf_plan_rays.argtypes = [C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p, C.c_void_p]
+        lib.rt_diag_pwf_outcome.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         _amd = lib
     return _amd
 

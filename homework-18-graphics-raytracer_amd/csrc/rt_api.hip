@@ -10,6 +10,7 @@
  */
 #include "rt_api_internal.h"
 #include "rt_temporal.h"
+#include "rt_pwf_common.h" /* pa_ready_packed, the rule launch_pwf and pwf_kernel share: rt_diag_pwf_plan reports it */
 
 /* Process-wide settings (rt_set_*): read by render calls on any thread, so they are atomics.  A value < 0 means "not set
  * yet": the first reader resolves it from the environment (two threads doing that at once compute the same value). */
@@ -463,22 +464,31 @@ int rt_scene_destroy(rt_scene *scene) {
 }
 
 } /* extern "C" */
-int make_kernel_frame(const rt_camera *camera, const rt_frame *frame, rt::KernelFrame *kf) {
-    if (!camera) return fail(RT_ERR_INVALID_ARGUMENT, "render: null camera");
+/* the frame's own part of make_kernel_frame, without the camera: the checks, and the tile with its depth (all that pw_plan reads) */
+static int check_render_frame(const rt_frame *frame) {
     if (!frame_ok(frame)) return fail(RT_ERR_INVALID_ARGUMENT, "render: bad frame (need 0 <= x0 < x1 <= width, 0 <= y0 < y1 <= height, y_step >= 1)");
     if (!frame_fits(frame)) return fail(RT_ERR_UNSUPPORTED, "render: tile of 2^32 pixels or more (render it as several tiles)");
     if (frame->max_depth > RT_MAX_DEPTH) return fail(RT_ERR_UNSUPPORTED, "render: max_depth above RT_MAX_DEPTH");
     /* max_depth < 0 is valid and renders as 0: TraceState.depth is an i32 tested with `depth <= 0` (main.rs:488, 669) */
-    using rt::V3;
-    /* Camera::shoot, main.rs:85-92: the ray-independent part (rt_temporal.h camera_basis, shared with librt_host.so) */
-    const rt::CameraBasis basis = rt::camera_basis(camera);
-    const V3 toward = basis.toward, x = basis.x, y = basis.y, origin = basis.origin;
+    return RT_OK;
+}
+static void set_frame_tile(const rt_frame *frame, rt::KernelFrame *kf) {
     kf->cols = frame->x1 - frame->x0;
     kf->rows = rt_frame_rows(frame);
     kf->x0 = frame->x0;
     kf->y0 = frame->y0;
     kf->y_step = frame->y_step;
     kf->max_depth = frame->max_depth;
+}
+int make_kernel_frame(const rt_camera *camera, const rt_frame *frame, rt::KernelFrame *kf) {
+    if (!camera) return fail(RT_ERR_INVALID_ARGUMENT, "render: null camera");
+    const int rc = check_render_frame(frame);
+    if (rc != RT_OK) return rc;
+    using rt::V3;
+    /* Camera::shoot, main.rs:85-92: the ray-independent part (rt_temporal.h camera_basis, shared with librt_host.so) */
+    const rt::CameraBasis basis = rt::camera_basis(camera);
+    const V3 toward = basis.toward, x = basis.x, y = basis.y, origin = basis.origin;
+    set_frame_tile(frame, kf);
     kf->half_height = (float)frame->height / 2.0f;
     kf->half_width = (float)frame->width / 2.0f;
     kf->height_f = (float)frame->height;
@@ -547,6 +557,22 @@ static PwPlan pw_plan(const rt_scene *scene, const rt::KernelFrame &kf, int wf_b
     return plan;
 }
 
+/* The variant a call on this scene takes: the setting, without the persistent-wavefront path where the scene does not fit its items */
+static int scene_variant(const rt_scene *scene) {
+    int variant = current_variant();
+    /* the persistent-wavefront path packs the ray's face mode and the depth left next to a 21-bit primitive id */
+    if ((variant & RT_VARIANT_PWF) && (uint64_t)scene->ks.n_triangles + scene->ks.n_spheres >= (1ull << 21)) variant &= ~RT_VARIANT_PWF;
+    if ((variant & RT_VARIANT_PWF) && (scene->ks.n_lights >= (1u << 14) || scene->ks.n_materials >= (1u << 16))) variant &= ~RT_VARIANT_PWF; /* a SHADE item's word: 16 + 14 bits */
+    return variant;
+}
+/* The breadth-first walk's lists for the plan's grid, one set per wave (PA_WAVES = 8 per workgroup): `lists` is null for a scene that
+ * is not walked breadth-first, and where the workspace holds too little (and may not grow).  launch_pwf picks pwf_kernel's BFS
+ * instantiations when it is handed lists.  Under the scene's ws_mutex. */
+static BfsLists pw_bfs_lists(const rt_scene *scene, Workspace &ws, const PwPlan &plan, bool may_allocate) {
+    if (scene->ks.bfs_walk == 0u) return BfsLists{nullptr, 0u, 0u};
+    return bfs_lists(ws, plan.groups * 8u, may_allocate);
+}
+
 /* Which block of global words the call's launch(es) take and whether they prepare it themselves: the state a workspace carries from
  * call to call (rt_api_internal.h Workspace), moved on by this call.  Under the scene's ws_mutex, the arenas held. */
 struct PwTurn {
@@ -604,10 +630,7 @@ static int render_whitted_frame(const rt_scene *scene, const rt::KernelFrame &kf
             *band_rgb = d_rgb + (size_t)u0 * kf.cols * 3u;
         }
     };
-    int variant = current_variant();
-    /* the persistent-wavefront path packs the ray's face mode and the depth left next to a 21-bit primitive id */
-    if ((variant & RT_VARIANT_PWF) && (uint64_t)scene->ks.n_triangles + scene->ks.n_spheres >= (1ull << 21)) variant &= ~RT_VARIANT_PWF;
-    if ((variant & RT_VARIANT_PWF) && (scene->ks.n_lights >= (1u << 14) || scene->ks.n_materials >= (1u << 16))) variant &= ~RT_VARIANT_PWF; /* a SHADE item's word: 16 + 14 bits */
+    int variant = scene_variant(scene);
     const PwPlan plan = (variant & RT_VARIANT_PWF) ? pw_plan(scene, kf, current_wf_budget()) : PwPlan();
     rt::PwParams pw;
     memset(&pw, 0, sizeof pw);
@@ -619,6 +642,7 @@ static int render_whitted_frame(const rt_scene *scene, const rt::KernelFrame &kf
         std::lock_guard<std::mutex> lock(mut->ws_mutex);
         Workspace &ws = mut->workspaces[stream];
         RT_HIP(ensure_counters(ws));
+        ws.pw_last_block = -1;
         if (variant & RT_VARIANT_PWF) {
             if (plan.bytes > ws.d_pwf.bytes()) {
                 ws.drop_arenas();
@@ -629,7 +653,7 @@ static int render_whitted_frame(const rt_scene *scene, const rt::KernelFrame &kf
              * allocation the launch must not happen (round 1's memory fault was a kernel writing one page past a workspace) */
             if (ws.d_pwf.bytes() != 0 && plan.bytes > ws.d_pwf.bytes()) ws.drop_arenas();
             if (ws.d_pwf.bytes() != 0 && scene->ks.bfs_walk != 0u) { /* the breadth-first walk's item and job lists: per wave of the grid */
-                const BfsLists bl = bfs_lists(ws, plan.groups * 8u, true); /* PA_WAVES = 8 */
+                const BfsLists bl = pw_bfs_lists(scene, ws, plan, true);
                 if (bl.lists == nullptr) ws.drop_arenas(); /* no room: the per-pixel kernel */
                 pw.bfs_scratch = bl.lists;
                 pw.bfs_items_cap = bl.items_cap; pw.bfs_jobs_cap = bl.jobs_cap;
@@ -646,7 +670,10 @@ static int render_whitted_frame(const rt_scene *scene, const rt::KernelFrame &kf
             pw.frame = reinterpret_cast<const rt::KernelFrame *>(ws.d_pwf.get<unsigned char>() + 256);
             pw.arena = ws.d_pwf.get<unsigned char>() + 512;
             pw.ray_count = d_ray_count;
-            if (ws.d_pwf.bytes() != 0) turn = pw_take_turn(ws, plan, kf, stream_capturing(stream));
+            if (ws.d_pwf.bytes() != 0) {
+                turn = pw_take_turn(ws, plan, kf, stream_capturing(stream));
+                ws.pw_last_block = (int)turn.parity;
+            }
         }
 #ifdef RT_DIAG_TIMELINE
         qs.timeline = g_diag_timeline;
@@ -724,6 +751,17 @@ int rt_render_whitted(const rt_scene *scene, const rt_camera *camera, const rt_f
 
 static const CountLimit TRACE_RAYS_LIMIT = {32u, "rays", "trace them in several calls"};
 
+/* a ray batch as a frame: one row of n_rays roots (rt_kernels.h frame_set_rays) */
+static rt::KernelFrame rays_kernel_frame(const rt_ray *d_rays, size_t n_rays, int32_t max_depth, float contribution) {
+    rt::KernelFrame kf;
+    memset(&kf, 0, sizeof kf);
+    kf.cols = (uint32_t)n_rays;
+    kf.rows = 1u;
+    kf.max_depth = max_depth;
+    rt::frame_set_rays(&kf, d_rays, contribution);
+    return kf;
+}
+
 int rt_trace_rays(const rt_scene *scene, const rt_ray *d_rays, size_t n_rays, int32_t max_depth, float contribution, float *d_rgb,
                   unsigned long long *d_ray_count, void *hip_stream) {
     bool done;
@@ -731,13 +769,79 @@ int rt_trace_rays(const rt_scene *scene, const rt_ray *d_rays, size_t n_rays, in
     if (rc != RT_OK || done) return rc;
     if (max_depth > RT_MAX_DEPTH) return fail(RT_ERR_UNSUPPORTED, "rt_trace_rays: max_depth above RT_MAX_DEPTH");
     /* max_depth < 0 renders as 0, as in rt_render_whitted (TraceState.depth is tested with `depth <= 0`, main.rs:488) */
+    const rt::KernelFrame kf = rays_kernel_frame(d_rays, n_rays, max_depth, contribution);
+    return render_whitted_frame(scene, kf, d_rays, d_rgb, d_ray_count, static_cast<hipStream_t>(hip_stream), "rt_trace_rays");
+}
+
+/* ---- diagnostics (include/rt_amd.h): which instantiation of pwf_kernel a call reaches, and how the last call's frame ended ---- */
+
+/* What render_whitted_frame would make of kf on this scene and stream, the workspace as it stands (nothing is allocated or changed):
+ * pw_plan's numbers under the current budget and RT_AMD_WF_SHARE, and the three template arguments launch_pwf derives from them. */
+static int diag_pwf_plan(const rt_scene *scene, const rt::KernelFrame &kf, hipStream_t stream, uint32_t *out_words) {
+    const PwPlan plan = pw_plan(scene, kf, current_wf_budget());
+    bool arenas = false, lists = false;
+    {
+        rt_scene *mut = const_cast<rt_scene *>(scene);
+        std::lock_guard<std::mutex> lock(mut->ws_mutex);
+        const auto it = mut->workspaces.find(stream);
+        if (it != mut->workspaces.end()) {
+            arenas = it->second.d_pwf.bytes() != 0 && plan.bytes <= it->second.d_pwf.bytes();
+            lists = pw_bfs_lists(scene, it->second, plan, false).lists != nullptr;
+        }
+    }
+    const bool persistent = (scene_variant(scene) & RT_VARIANT_PWF) != 0 && arenas && (scene->ks.bfs_walk == 0u || lists);
+    out_words[RT_DIAG_PWF_PERSISTENT] = persistent ? 1u : 0u;
+    out_words[RT_DIAG_PWF_GROUPS] = plan.groups;
+    out_words[RT_DIAG_PWF_UNITS] = rt::frame_is_rays(kf) ? kf.cols : kf.rows;
+    out_words[RT_DIAG_PWF_BAND_UNITS] = plan.band_units;
+    out_words[RT_DIAG_PWF_RING_CAP] = plan.ring_cap;
+    out_words[RT_DIAG_PWF_NODE_CAP] = plan.node_cap;
+    out_words[RT_DIAG_PWF_PACKED] = rt::pa_ready_packed(plan.node_cap, plan.ring_cap) ? 1u : 0u;
+    out_words[RT_DIAG_PWF_BFS] = scene->ks.bfs_walk != 0u && lists ? 1u : 0u; /* launch_pwf: sc.bfs_walk != 0u && pp.bfs_scratch != nullptr */
+    out_words[RT_DIAG_PWF_RAYS] = rt::frame_is_rays(kf) ? 1u : 0u;
+    out_words[RT_DIAG_PWF_BUDGET] = (uint32_t)current_wf_budget();
+    return RT_OK;
+}
+
+int rt_diag_pwf_plan(const rt_scene *scene, const rt_frame *frame, void *hip_stream, uint32_t *out_words) {
+    if (!scene || !out_words) return fail(RT_ERR_INVALID_ARGUMENT, "rt_diag_pwf_plan: null argument");
+    const int rc = check_render_frame(frame);
+    if (rc != RT_OK) return rc;
     rt::KernelFrame kf;
     memset(&kf, 0, sizeof kf);
-    kf.cols = (uint32_t)n_rays;
-    kf.rows = 1u;
-    kf.max_depth = max_depth;
-    rt::frame_set_rays(&kf, d_rays, contribution);
-    return render_whitted_frame(scene, kf, d_rays, d_rgb, d_ray_count, static_cast<hipStream_t>(hip_stream), "rt_trace_rays");
+    set_frame_tile(frame, &kf);
+    return diag_pwf_plan(scene, kf, static_cast<hipStream_t>(hip_stream), out_words);
+}
+
+int rt_diag_pwf_plan_rays(const rt_scene *scene, size_t n_rays, int32_t max_depth, void *hip_stream, uint32_t *out_words) {
+    int rc = check_count("rt_diag_pwf_plan_rays", n_rays, TRACE_RAYS_LIMIT);
+    if (rc != RT_OK) return rc;
+    if (!scene || !out_words) return fail(RT_ERR_INVALID_ARGUMENT, "rt_diag_pwf_plan_rays: null argument");
+    if (n_rays == 0) return fail(RT_ERR_INVALID_ARGUMENT, "rt_diag_pwf_plan_rays: an empty batch launches nothing");
+    if (max_depth > RT_MAX_DEPTH) return fail(RT_ERR_UNSUPPORTED, "rt_diag_pwf_plan_rays: max_depth above RT_MAX_DEPTH");
+    return diag_pwf_plan(scene, rays_kernel_frame(nullptr, n_rays, max_depth, 1.0f), static_cast<hipStream_t>(hip_stream), out_words);
+}
+
+int rt_diag_pwf_outcome(const rt_scene *scene, void *hip_stream, uint32_t *out_words) {
+    if (!scene || !out_words) return fail(RT_ERR_INVALID_ARGUMENT, "rt_diag_pwf_outcome: null argument");
+    const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    for (int i = 0; i < RT_DIAG_PWF_OUTCOME_WORDS; ++i) out_words[i] = 0u;
+    rt_scene *mut = const_cast<rt_scene *>(scene);
+    std::lock_guard<std::mutex> lock(mut->ws_mutex); /* held over the copy: no call may drop the arenas under it */
+    const auto it = mut->workspaces.find(stream);
+    if (it == mut->workspaces.end() || it->second.pw_last_block < 0 || it->second.d_pwf.bytes() == 0) return RT_OK; /* no persistent launch to speak of */
+    uint32_t block[PW_G_WORDS];
+    hipError_t e = hipMemcpyAsync(block, it->second.d_pwf.get<uint32_t>() + (size_t)it->second.pw_last_block * PW_G_BLOCK_WORDS, sizeof block,
+                                  hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) return fail_hip("rt_diag_pwf_outcome: copy", e);
+    out_words[RT_DIAG_PWF_LAUNCHED] = 1u;
+    out_words[RT_DIAG_PWF_OVERFLOW] = block[PW_G_OVERFLOW];
+    out_words[RT_DIAG_PWF_TILES_DONE] = block[PW_G_TILES_DONE];
+    out_words[RT_DIAG_PWF_GROUPS_DONE] = block[PW_G_GROUPS_DONE];
+    out_words[RT_DIAG_PWF_CASTS_LO] = block[PW_G_CASTS];
+    out_words[RT_DIAG_PWF_CASTS_HI] = block[PW_G_CASTS + 1u];
+    return RT_OK;
 }
 
 int rt_trace_rays_host(const rt_scene *scene, const rt_ray *h_rays, size_t n_rays, int32_t max_depth, float contribution, float *h_rgb,

@@ -5,7 +5,8 @@
  * extern "C" entry points of include/rt_amd.h and nothing else.
  *
  *   rt_api.hip         errors and the shared host plumbing declared below, settings, profiling, rt_scene_create/destroy,
- *                      rt_render_whitted (the per-stream arenas), rt_trace_rays
+ *                      rt_render_whitted (the per-stream arenas), rt_trace_rays, and the diagnostics that report their plan and
+ *                      outcome (rt_diag_pwf_plan / _plan_rays / _outcome)
  *   rt_api_layout.hip  the device records and the node tree built from the ABI arrays — host only, no HIP call
  *   rt_api_dist.hip    rt_rng_*, rt_render_distributed and rt_trace_rays_distributed: batches, the two workspaces, the streams of a
  *                      pipelined call
@@ -108,9 +109,11 @@ struct Workspace {
     bool pw_always_prepare = false; /* a call on this stream was captured into a graph: replays come unannounced, so from then on
                                      * every launch prepares its own block and frame description, as a captured one does */
     rt::KernelFrame pw_frame;
+    int pw_last_block = -1; /* the block the last call's launch(es) of the persistent kernel took; -1: that call launched none.  The
+                             * block stays as the kernel left it until the next launch here (rt_diag_pwf_outcome reads it) */
     DeviceBuffer d_bfs;   /* a scene walked breadth-first: item and job lists per wave (rt_kernels.h PwParams), through bfs_lists() below */
     DeviceBuffer d_split; /* split distributed pass: requests, shades and frames of one batch of epochs */
-    void drop_arenas() { (void)d_pwf.release(); pw_ready = false; } /* whatever the blocks held went with them */
+    void drop_arenas() { (void)d_pwf.release(); pw_ready = false; pw_last_block = -1; } /* whatever the blocks held went with them */
 };
 
 /* The breadth-first walk's record lists for a grid of `waves` waves, in the stream's workspace (the Whitted frame, the one-kernel

@@ -1825,6 +1825,58 @@ int rt_scene_describe_nodes(const rt_scene_desc *desc, uint32_t *out_words, uint
  * updates the scene.  For tests of rt_scene_update_vertices: what it leaves against what rt_scene_create builds. */
 int rt_diag_scene_nodes(const rt_scene *scene, int which, uint32_t *h_words, size_t cap_words, size_t *n_words);
 
+/* Which code a Whitted call on the persistent-wavefront path runs.  The kernel has eight instantiations, pwf_kernel<PACKED, BFS, RAYS>
+ * (csrc/rt_pwf_kernel.h), and the launcher picks one per call: PACKED from the arenas' size (csrc/rt_pwf_common.h pa_ready_packed),
+ * BFS for a scene walked breadth-first (RT_AMD_BFS_WALK_TRIANGLES at rt_scene_create) whose lists the stream's workspace holds, RAYS
+ * for a ray batch.  rt_diag_pwf_plan reports, for `frame` rendered on `hip_stream` (rt_render_whitted; the camera does not matter),
+ * what the launcher computes from the frame, the scene, the current rt_set_wavefront_budget and RT_AMD_WF_SHARE, with the stream's
+ * workspace as it stands — it calls the launcher's own functions, allocates nothing, launches nothing and changes nothing.
+ * rt_diag_pwf_plan_rays is the same for a batch of n_rays rays at max_depth (rt_trace_rays).  Workspaces only grow and are made by the
+ * first call that needs them, so ask AFTER the call in question, the settings unchanged: the answer is then what that call launched.
+ * out_words receives RT_DIAG_PWF_PLAN_WORDS words:
+ *   RT_DIAG_PWF_PERSISTENT  1: the call launches the persistent kernel (the variant has it, the scene fits its items, the workspace
+ *                           holds the arenas and, for BFS, the lists); 0: the per-pixel kernel renders the frame
+ *   RT_DIAG_PWF_GROUPS      workgroups of the grid, one arena each
+ *   RT_DIAG_PWF_UNITS       rows of the frame, or rays of the batch
+ *   RT_DIAG_PWF_BAND_UNITS  ... of them per launch: below UNITS the call is several bands, one launch each
+ *   RT_DIAG_PWF_RING_CAP, RT_DIAG_PWF_NODE_CAP   ring slots and nodes per arena
+ *   RT_DIAG_PWF_PACKED, RT_DIAG_PWF_BFS, RT_DIAG_PWF_RAYS   the three template arguments, 0 or 1 each
+ *   RT_DIAG_PWF_BUDGET      the nodes per pixel the plan was made for
+ * For tests that must know which instantiation they ran. */
+#define RT_DIAG_PWF_PERSISTENT 0
+#define RT_DIAG_PWF_GROUPS 1
+#define RT_DIAG_PWF_UNITS 2
+#define RT_DIAG_PWF_BAND_UNITS 3
+#define RT_DIAG_PWF_RING_CAP 4
+#define RT_DIAG_PWF_NODE_CAP 5
+#define RT_DIAG_PWF_PACKED 6
+#define RT_DIAG_PWF_BFS 7
+#define RT_DIAG_PWF_RAYS 8
+#define RT_DIAG_PWF_BUDGET 9
+#define RT_DIAG_PWF_PLAN_WORDS 10
+int rt_diag_pwf_plan(const rt_scene *scene, const rt_frame *frame, void *hip_stream, uint32_t *out_words);
+int rt_diag_pwf_plan_rays(const rt_scene *scene, size_t n_rays, int32_t max_depth, void *hip_stream, uint32_t *out_words);
+
+/* How the last rt_render_whitted / rt_trace_rays call on `hip_stream` ended on the persistent-wavefront path: a frame the arenas cannot
+ * finish raises an overflow flag and the trailing per-pixel launch renders it, with the same pixels and cast count, so results cannot
+ * tell the two apart.  The flag lives in the block of counters the call's launch took, which stays as the kernel left it until the
+ * next launch on that workspace; this copies it out behind the stream's work and waits for the copy (the kernel writes nothing for
+ * it).  A call of several bands reuses one block, so what is reported is its LAST band.  Direct calls only, not graph replays.
+ * out_words receives RT_DIAG_PWF_OUTCOME_WORDS words, all 0 when that call launched no persistent kernel:
+ *   RT_DIAG_PWF_LAUNCHED    1: the call launched the persistent kernel
+ *   RT_DIAG_PWF_OVERFLOW    1: the frame (band) was not finished within the arenas and the per-pixel kernel rendered it
+ *   RT_DIAG_PWF_TILES_DONE  64-pixel tiles whose pixels the persistent kernel wrote
+ *   RT_DIAG_PWF_GROUPS_DONE workgroups that left the kernel (all of them)
+ *   RT_DIAG_PWF_CASTS_LO, RT_DIAG_PWF_CASTS_HI   the casts the persistent kernel counted (added to the caller's count only without overflow) */
+#define RT_DIAG_PWF_LAUNCHED 0
+#define RT_DIAG_PWF_OVERFLOW 1
+#define RT_DIAG_PWF_TILES_DONE 2
+#define RT_DIAG_PWF_GROUPS_DONE 3
+#define RT_DIAG_PWF_CASTS_LO 4
+#define RT_DIAG_PWF_CASTS_HI 5
+#define RT_DIAG_PWF_OUTCOME_WORDS 6
+int rt_diag_pwf_outcome(const rt_scene *scene, void *hip_stream, uint32_t *out_words);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,6 +33,9 @@ SIGNATURES = {
     "rt_profile_read_distributed": [("ms", P), ("launches", P)],
     "rt_scene_create": [("desc", C.pointer(_capi.SceneDesc())), ("out", OUT)],
     "rt_diag_scene_nodes": [("scene", SCENE), ("which", 0), ("words", P), ("cap", 4), ("n_words", C.pointer(C.c_size_t()))],
+    "rt_diag_pwf_plan": [("scene", SCENE), ("frame", FRAME), ("stream", None), ("words", P)],
+    "rt_diag_pwf_plan_rays": [("scene", SCENE), ("n", 2), ("depth", 3), ("stream", None), ("words", P)],
+    "rt_diag_pwf_outcome": [("scene", SCENE), ("stream", None), ("words", P)],
     "rt_render_whitted": [("scene", SCENE), ("camera", CAMERA), ("frame", FRAME), ("rgb", P), ("count", P), ("stream", None)],
     "rt_render_whitted_host": [("scene", SCENE), ("camera", CAMERA), ("frame", FRAME), ("rgb", P), ("count", None)],
     "rt_trace_rays": [("scene", SCENE), ("rays", P), ("n", 2), ("depth", 3), ("contribution", 1.0), ("rgb", P), ("count", P), ("stream", None)],
@@ -145,6 +148,19 @@ CASES = [
     ("rt_scene_create", _null("desc"), INVALID, "rt_scene_create: null argument"),
     ("rt_scene_create", _null("out"), INVALID, "rt_scene_create: null argument"),
     ("rt_diag_scene_nodes", _null("scene"), INVALID, "rt_diag_scene_nodes: null argument"),
+    ("rt_diag_pwf_plan", _null("scene"), INVALID, "rt_diag_pwf_plan: null argument"),
+    ("rt_diag_pwf_plan", _null("words"), INVALID, "rt_diag_pwf_plan: null argument"),
+    ("rt_diag_pwf_plan", _null("frame"), INVALID, "render: " + FRAME_NEEDS),
+    ("rt_diag_pwf_plan", {"frame": BAD_FRAME}, INVALID, "render: " + FRAME_NEEDS),
+    ("rt_diag_pwf_plan", {"frame": HUGE_FRAME}, UNSUPPORTED, "render: tile of 2^32 pixels or more (render it as several tiles)"),
+    ("rt_diag_pwf_plan", {"frame": DEEP_FRAME}, UNSUPPORTED, "render: max_depth above RT_MAX_DEPTH"),
+    ("rt_diag_pwf_plan_rays", {"n": BIG}, UNSUPPORTED, "rt_diag_pwf_plan_rays: 2^32 rays or more (checked first; trace them in several calls)"),
+    ("rt_diag_pwf_plan_rays", _null("scene"), INVALID, "rt_diag_pwf_plan_rays: null argument"),
+    ("rt_diag_pwf_plan_rays", _null("words"), INVALID, "rt_diag_pwf_plan_rays: null argument"),
+    ("rt_diag_pwf_plan_rays", {"n": 0}, INVALID, "rt_diag_pwf_plan_rays: an empty batch launches nothing"),
+    ("rt_diag_pwf_plan_rays", {"depth": 33}, UNSUPPORTED, "rt_diag_pwf_plan_rays: max_depth above RT_MAX_DEPTH"),
+    ("rt_diag_pwf_outcome", _null("scene"), INVALID, "rt_diag_pwf_outcome: null argument"),
+    ("rt_diag_pwf_outcome", _null("words"), INVALID, "rt_diag_pwf_outcome: null argument"),
     # the Whitted frame and the ray batch
     ("rt_render_whitted", _null("scene"), INVALID, "rt_render_whitted: null argument"),
     ("rt_render_whitted", _null("rgb"), INVALID, "rt_render_whitted: null argument"),

@@ -6,10 +6,10 @@ import numpy as np
 import pytest
 
 import homework_18_graphics_raytracer_amd as rt
-from homework_18_graphics_raytracer_amd import _capi
+from homework_18_graphics_raytracer_amd import _capi, diagnostics
 import _oracle
 import _scenes
-from _trace_support import _check, _mismatches, PWF
+from _trace_support import _check, _mismatches, PWF, variant as settings
 
 pytestmark = pytest.mark.gpu
 
@@ -106,6 +106,9 @@ def test_oversized_tiles_are_rendered_as_row_bands(ref, w, h, depth):
     _check(world, cam, rt.Frame.full(w, h, depth), budget=1024, scene=scene)
     # ... also for an interleaved (multi-GPU) share of the frame
     lib = _capi.amd_lib()
+    with settings(_capi.DEFAULT_VARIANT, 1024):
+        plan = diagnostics.pwf_plan(scene, rt.Frame.full(w, h, depth))
+    assert plan.persistent and plan.band_units < plan.units == h  # several bands, as the name says
     full, _ = _oracle.render_whitted(world.desc(), cam, rt.Frame.full(w, h, depth))
     _capi.check(lib.rt_set_wavefront_budget(2048))
     try:
@@ -193,6 +196,7 @@ def test_frames_in_flight_side_by_side_on_parts_of_the_device(ref, share):
                 for o, st in zip(outs, streams):
                     rt.render_whitted(scene, cam, f, out=o, ray_count=cnt, stream=st)
             torch.cuda.synchronize()
+            assert share != 1000 or diagnostics.pwf_plan(scene, f, stream=streams[0]).groups == 1  # one workgroup has the frame
             for o in outs:
                 assert np.array_equal(o.cpu().numpy().view(np.uint32), want[k][0].view(np.uint32))
             assert int(cnt.item()) == 2 * len(streams) * want[k][1]
@@ -352,6 +356,7 @@ def test_frame_large_enough_for_packed_page_counters(ref):
     world, cam, scene = ref
     frame = rt.Frame.full(3840, 2160, 3)
     got, casts = rt.render_whitted_numpy(scene, cam, frame)
+    assert diagnostics.pwf_plan(scene, frame).instantiation == (True, False, False)  # pwf_kernel<PACKED, BFS, RAYS>
     want, wcasts = _oracle.render_whitted(world.desc(), cam, frame)
     assert _mismatches(got, want) == 0
     assert casts == wcasts
