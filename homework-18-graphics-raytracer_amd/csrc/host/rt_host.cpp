@@ -49,6 +49,18 @@ static void each(const Op &op) {
     for (uint64_t i = 0; i < op.count(); ++i) op(i);
 }
 
+/* The _cpu form of an image-side query, written once: `a` is the query's argument struct (rt_query_args.h) — its limits under the entry
+ * point's name, nothing to do for an empty image, then run(a), the query's loop. */
+template <class Args, class Run>
+static int cpu_query(const char *who, const Args &a, Run run) {
+    int status = RT_ERR_INVALID_ARGUMENT;
+    if (const char *bad = a.limits(rt::QUERY_CPU, &status)) return fail(status, std::string(who) + ": " + bad);
+    if (!a.empty()) run(a);
+    return RT_OK;
+}
+/* the loop of a query whose call() is an Op */
+static const auto each_call = [](const auto &a) { each(a.call()); };
+
 extern "C" {
 
 const char *rt_host_last_error(void) { return g_host_error.c_str(); }
@@ -577,13 +589,8 @@ int rt_film_splat_host(uint32_t rows, uint32_t cols, const float *samples, const
 int rt_sample_budget_cpu(const float *mean, uint32_t mean_stride, const float *variance, uint32_t variance_stride, const uint32_t *count,
                          uint32_t count_stride, const uint32_t *valid, uint32_t valid_stride, const rt_sample_budget_params *params, size_t n,
                          uint32_t *budget) {
-    int status;
-    const char *bad = rt::sample_budget_limits(mean, mean_stride, variance, variance_stride, count, count_stride, valid, valid_stride, params, n, budget, &status);
-    if (bad) return fail(status, std::string("rt_sample_budget_cpu: ") + bad);
-    if (n == 0u) return RT_OK;
-    const rt::SampleBudget b = rt::sample_budget_call(mean, mean_stride, variance, variance_stride, count, count_stride, valid, valid_stride, *params, n, budget);
-    each(b);
-    return RT_OK;
+    return cpu_query("rt_sample_budget_cpu",
+                     rt::SampleBudgetArgs{mean, mean_stride, variance, variance_stride, count, count_stride, valid, valid_stride, params, n, budget}, each_call);
 }
 
 int rt_sample_list_cpu(const uint32_t *counts, size_t n, size_t capacity, uint32_t *first, uint32_t *start, uint32_t *pixel, uint32_t *sample,
@@ -609,14 +616,12 @@ int rt_sample_list_cpu(const uint32_t *counts, size_t n, size_t capacity, uint32
 
 int rt_film_offsets_listed_cpu(const rt_frame *frame, uint32_t pattern, uint32_t seed, const uint32_t *pixel, const uint32_t *sample,
                                const uint32_t *total, size_t capacity, float *offsets) {
-    int status;
-    const char *bad = rt::listed_offsets_limits(frame, pattern, pixel, sample, total, capacity, offsets, &status);
-    if (bad) return fail(status, std::string("rt_film_offsets_listed_cpu: ") + bad);
-    if (capacity == 0u) return RT_OK;
-    const rt::ListedOffsets o = {rt::film_tile(frame), pattern, seed, pixel, sample, total, capacity, offsets};
-    const uint64_t listed = rt::listed_count(total, capacity);
-    for (uint64_t j = 0; j < capacity; ++j) rt::listed_offsets_record(o, j, listed);
-    return RT_OK;
+    return cpu_query("rt_film_offsets_listed_cpu", rt::ListedOffsetsArgs{frame, pattern, seed, pixel, sample, total, capacity, offsets},
+                     [](const rt::ListedOffsetsArgs &a) {
+                         const rt::ListedOffsets o = a.call();
+                         const uint64_t listed = rt::listed_count(o.total, o.capacity);
+                         for (uint64_t j = 0; j < o.capacity; ++j) rt::listed_offsets_record(o, j, listed);
+                     });
 }
 
 int rt_camera_rays_listed_cpu(const rt_camera *camera, const rt_frame *frame, const float *offsets, const uint32_t *pixel, const uint32_t *total,
@@ -654,74 +659,47 @@ int rt_film_splat_listed_cpu(uint32_t rows, uint32_t cols, const float *samples,
 
 int rt_denoise_atrous_cpu(const float *color, const rt_denoise_guides *guides, const rt_denoise_params *params, uint32_t rows, uint32_t cols,
                           float *out, float *temp) {
-    const char *bad = rt::denoise_limits(color, guides, params, rows, cols, out, temp, true);
-    if (bad) return fail(RT_ERR_INVALID_ARGUMENT, std::string("rt_denoise_atrous_cpu: ") + bad);
-    if (rows == 0u || cols == 0u) return RT_OK;
-    rt::atrous_cpu<rt::DenoiseFilter>(params->n_levels, [&](uint32_t j) { return rt::denoise_level(color, *guides, *params, rows, cols, out, temp, j); });
-    return RT_OK;
+    return cpu_query("rt_denoise_atrous_cpu", rt::DenoiseArgs{color, guides, params, rows, cols, out, temp}, rt::atrous_cpu<rt::DenoiseFilter, rt::DenoiseArgs>);
 }
 
 /* ---- temporal queries: the CPU definition (include/rt_amd.h "temporal queries"; the arithmetic is rt_temporal.h's, shared with the device) ---- */
 
 int rt_temporal_motion_cpu(const float *position, uint32_t position_stride, const uint32_t *valid, uint32_t valid_stride, const rt_camera *prev_camera,
                            const rt_frame *prev_frame, float *motion) {
-    int status;
-    const char *bad = rt::temporal_motion_limits(position, position_stride, valid, valid_stride, prev_camera, prev_frame, motion, &status);
-    if (bad) return fail(status, std::string("rt_temporal_motion_cpu: ") + bad);
-    rt::TemporalMotion m;
-    m.cam = rt::temporal_camera(prev_camera, prev_frame);
-    m.position = position, m.valid = valid, m.position_stride = position_stride, m.valid_stride = valid_stride, m.motion = motion;
-    m.n = (uint64_t)prev_frame->width * prev_frame->height;
-    each(m);
-    return RT_OK;
+    return cpu_query("rt_temporal_motion_cpu", rt::TemporalMotionArgs{position, position_stride, valid, valid_stride, prev_camera, prev_frame, motion}, each_call);
 }
 
 int rt_temporal_accumulate_cpu(const float *color, const float *motion, const rt_temporal_guides *current, const rt_temporal_guides *previous,
                                const rt_temporal_params *params, uint32_t rows, uint32_t cols, const rt_temporal_pixel *history_in,
                                rt_temporal_pixel *history_out, float *variance) {
-    int status;
-    const char *bad = rt::temporal_limits(color, motion, current, previous, params, rows, cols, history_in, history_out, false, &status);
-    if (bad) return fail(status, std::string("rt_temporal_accumulate_cpu: ") + bad);
-    if (rows == 0u || cols == 0u) return RT_OK;
-    each(rt::temporal_call(color, motion, *current, *previous, *params, rows, cols, history_in, history_out, variance));
-    return RT_OK;
+    return cpu_query("rt_temporal_accumulate_cpu",
+                     rt::TemporalAccumulateArgs{color, motion, current, previous, params, rows, cols, history_in, history_out, variance}, each_call);
 }
 
 /* ---- history rectification queries: the CPU definition (include/rt_amd.h "history rectification queries"; the arithmetic is rt_rectify.h's, shared with the device) ---- */
 
 int rt_temporal_bounds_cpu(const float *color, uint32_t color_stride, const uint32_t *object, uint32_t object_stride, const uint32_t *valid,
                            uint32_t valid_stride, const rt_bounds_params *params, uint32_t rows, uint32_t cols, rt_temporal_box *box) {
-    int status;
-    const char *bad = rt::rectify_bounds_limits(color, color_stride, object, object_stride, valid, valid_stride, params, rows, cols, box, false, &status);
-    if (bad) return fail(status, std::string("rt_temporal_bounds_cpu: ") + bad);
-    if (rows == 0u || cols == 0u) return RT_OK;
-    const rt::RectifyBounds b = rt::rectify_bounds_call(color, color_stride, object, object_stride, valid, valid_stride, *params, rows, cols, box);
-    for (uint32_t r = 0; r < rows; ++r)
-        for (uint32_t c = 0; c < cols; ++c) rt::rectify_bounds_pixel(b, r, c);
-    return RT_OK;
+    return cpu_query("rt_temporal_bounds_cpu", rt::RectifyBoundsArgs{color, color_stride, object, object_stride, valid, valid_stride, params, rows, cols, box},
+                     [](const rt::RectifyBoundsArgs &a) {
+                         const rt::RectifyBounds b = a.call();
+                         for (uint32_t r = 0; r < b.rows; ++r)
+                             for (uint32_t c = 0; c < b.cols; ++c) rt::rectify_bounds_pixel(b, r, c);
+                     });
 }
 
 int rt_temporal_accumulate_bounded_cpu(const float *color, const float *motion, const rt_temporal_guides *current, const rt_temporal_guides *previous,
                                        const rt_temporal_params *params, uint32_t rows, uint32_t cols, const rt_temporal_pixel *history_in,
                                        rt_temporal_pixel *history_out, float *variance, const rt_temporal_box *box, uint32_t clamped_length,
                                        uint32_t *clamped) {
-    int status;
-    const char *bad = rt::rectify_accumulate_limits(color, motion, current, previous, params, rows, cols, history_in, history_out, box, clamped_length, false, &status);
-    if (bad) return fail(status, std::string("rt_temporal_accumulate_bounded_cpu: ") + bad);
-    if (rows == 0u || cols == 0u) return RT_OK;
-    each(rt::RectifyAccumulate{rt::temporal_call(color, motion, *current, *previous, *params, rows, cols, history_in, history_out, variance), box,
-                               clamped_length, clamped});
-    return RT_OK;
+    return cpu_query("rt_temporal_accumulate_bounded_cpu",
+                     rt::RectifyAccumulateArgs{{color, motion, current, previous, params, rows, cols, history_in, history_out, variance}, box, clamped_length, clamped},
+                     each_call);
 }
 
 int rt_temporal_feedback_cpu(const float *color, uint32_t color_stride, const uint32_t *valid, uint32_t valid_stride, uint32_t rows, uint32_t cols,
                              rt_temporal_pixel *history) {
-    int status;
-    const char *bad = rt::rectify_feedback_limits(color, color_stride, valid, valid_stride, rows, cols, history, false, &status);
-    if (bad) return fail(status, std::string("rt_temporal_feedback_cpu: ") + bad);
-    if (rows == 0u || cols == 0u) return RT_OK;
-    each(rt::RectifyFeedback{color, valid, color_stride, valid_stride, (uint64_t)rows * cols, history});
-    return RT_OK;
+    return cpu_query("rt_temporal_feedback_cpu", rt::RectifyFeedbackArgs{color, color_stride, valid, valid_stride, rows, cols, history}, each_call);
 }
 
 /* ---- guided upsampling queries: the CPU definition (include/rt_amd.h "guided upsampling queries"; the arithmetic is rt_upsample.h's, shared with the device) ---- */
@@ -729,35 +707,27 @@ int rt_temporal_feedback_cpu(const float *color, uint32_t color_stride, const ui
 int rt_upsample_guided_cpu(const float *color_lo, uint32_t color_stride, const rt_denoise_guides *low, const uint32_t *object_lo, uint32_t object_lo_stride,
                            const rt_denoise_guides *full, const uint32_t *object_full, uint32_t object_full_stride, const rt_upsample_params *params,
                            uint32_t rows, uint32_t cols, float *out) {
-    const char *bad = rt::upsample_limits(color_lo, color_stride, low, object_lo, object_lo_stride, full, object_full, object_full_stride, params, rows, cols, out);
-    if (bad) return fail(RT_ERR_INVALID_ARGUMENT, std::string("rt_upsample_guided_cpu: ") + bad);
-    if (rows == 0u || cols == 0u) return RT_OK;
-    each(rt::upsample_call(color_lo, color_stride, *low, object_lo, object_lo_stride, *full, object_full, object_full_stride, *params, rows, cols, out));
-    return RT_OK;
+    return cpu_query("rt_upsample_guided_cpu",
+                     rt::UpsampleArgs{color_lo, color_stride, low, object_lo, object_lo_stride, full, object_full, object_full_stride, params, rows, cols, out},
+                     each_call);
 }
 
 /* ---- variance-guided filter queries: the CPU definition (include/rt_amd.h "variance-guided filter queries"; the arithmetic is rt_svgf.h's, shared with the device) ---- */
 
 int rt_svgf_variance_cpu(const rt_temporal_pixel *history, const rt_denoise_guides *guides, const rt_svgf_variance_params *params, uint32_t rows,
                          uint32_t cols, float *variance_out) {
-    const char *bad = rt::svgf_variance_limits(history, guides, params, rows, cols, variance_out, false);
-    if (bad) return fail(RT_ERR_INVALID_ARGUMENT, std::string("rt_svgf_variance_cpu: ") + bad);
-    if (rows == 0u || cols == 0u) return RT_OK;
-    const rt::SvgfVariance v = rt::svgf_variance_call(history, *guides, *params, rows, cols, variance_out);
-    for (uint32_t r = 0; r < rows; ++r)
-        for (uint32_t c = 0; c < cols; ++c) variance_out[(uint64_t)r * cols + c] = rt::svgf_variance_pixel(v, r, c);
-    return RT_OK;
+    return cpu_query("rt_svgf_variance_cpu", rt::SvgfVarianceArgs{history, guides, params, rows, cols, variance_out}, [](const rt::SvgfVarianceArgs &a) {
+        const rt::SvgfVariance v = a.call();
+        for (uint32_t r = 0; r < v.rows; ++r)
+            for (uint32_t c = 0; c < v.cols; ++c) v.out[(uint64_t)r * v.cols + c] = rt::svgf_variance_pixel(v, r, c);
+    });
 }
 
 int rt_svgf_atrous_cpu(const float *color, uint32_t color_stride, const float *variance, const rt_denoise_guides *guides,
                        const rt_svgf_atrous_params *params, uint32_t rows, uint32_t cols, float *out, float *variance_out, void *temp) {
-    const char *bad = rt::svgf_atrous_limits(color, color_stride, variance, guides, params, rows, cols, out, variance_out, static_cast<float *>(temp), true);
-    if (bad) return fail(RT_ERR_INVALID_ARGUMENT, std::string("rt_svgf_atrous_cpu: ") + bad);
-    if (rows == 0u || cols == 0u) return RT_OK;
-    rt::atrous_cpu<rt::SvgfFilter>(params->n_levels, [&](uint32_t j) {
-        return rt::svgf_level(color, color_stride, variance, *guides, *params, rows, cols, out, variance_out, static_cast<float *>(temp), j);
-    });
-    return RT_OK;
+    return cpu_query("rt_svgf_atrous_cpu",
+                     rt::SvgfAtrousArgs{color, color_stride, variance, guides, params, rows, cols, out, variance_out, static_cast<float *>(temp)},
+                     rt::atrous_cpu<rt::SvgfFilter, rt::SvgfAtrousArgs>);
 }
 
 /* ---- motion queries: the CPU definition (include/rt_amd.h "motion queries"; the arithmetic is rt_motion.h's, shared with the device) ---- */

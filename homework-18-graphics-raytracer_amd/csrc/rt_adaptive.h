@@ -44,29 +44,36 @@ RT_FILM_HD uint32_t sample_budget_pixel(const SampleBudget &b, uint64_t i) {
 }
 RT_FILM_HD void SampleBudget::operator()(uint64_t i) const { budget[i] = sample_budget_pixel(*this, i); }
 
-/* the argument limits of rt_sample_budget and its CPU form; null: all in range */
-inline const char *sample_budget_limits(const float *mean, uint32_t mean_stride, const float *variance, uint32_t variance_stride, const uint32_t *count,
-                                        uint32_t count_stride, const uint32_t *valid, uint32_t valid_stride, const rt_sample_budget_params *p, uint64_t n,
-                                        const uint32_t *budget, int *status) {
-    *status = RT_ERR_UNSUPPORTED;
-    if (n >= (1ull << 32)) return "2^32 pixels or more";
-    *status = RT_ERR_INVALID_ARGUMENT;
-    if (n == 0u) return nullptr;
-    if (!p) return "null params";
-    if (!mean || !variance || !budget) return "null mean, variance or budget pointer";
-    if (mean_stride < 1u || variance_stride < 1u || (count && count_stride < 1u) || (valid && valid_stride < 1u)) return "a stride smaller than its plane's width (1 word)";
-    if (!(p->gain >= 0.0f)) return "gain must be >= 0";
-    if (!(p->epsilon > 0.0f)) return "epsilon must be > 0";
-    if (!(p->min_count <= p->max_count && p->max_count <= RT_SAMPLE_MAX)) return "need min_count <= max_count <= RT_SAMPLE_MAX";
-    if (p->flags != 0u) return "flags must be 0";
-    return nullptr;
-}
+/* the arguments of rt_sample_budget and its CPU form (rt_query_args.h; there is no _host form, so no arrays()) */
+struct SampleBudgetArgs {
+    const float *mean; uint32_t mean_stride;
+    const float *variance; uint32_t variance_stride;
+    const uint32_t *count; uint32_t count_stride;
+    const uint32_t *valid; uint32_t valid_stride;
+    const rt_sample_budget_params *params; uint64_t n; uint32_t *budget;
 
-inline SampleBudget sample_budget_call(const float *mean, uint32_t mean_stride, const float *variance, uint32_t variance_stride, const uint32_t *count,
-                                       uint32_t count_stride, const uint32_t *valid, uint32_t valid_stride, const rt_sample_budget_params &p, uint64_t n,
-                                       uint32_t *budget) {
-    return {mean, variance, count, valid, mean_stride, variance_stride, count_stride, valid_stride, p.gain, p.epsilon, p.min_count, p.max_count, budget, n};
-}
+    const char *limits(QueryForm, int *status) const {
+        *status = RT_ERR_UNSUPPORTED;
+        if (n >= (1ull << 32)) return "2^32 pixels or more";
+        *status = RT_ERR_INVALID_ARGUMENT;
+        if (empty()) return nullptr;
+        if (!params) return "null params";
+        if (!mean || !variance || !budget) return "null mean, variance or budget pointer";
+        if (mean_stride < 1u || variance_stride < 1u || (count && count_stride < 1u) || (valid && valid_stride < 1u)) return "a stride smaller than its plane's width (1 word)";
+        if (!(params->gain >= 0.0f)) return "gain must be >= 0";
+        if (!(params->epsilon > 0.0f)) return "epsilon must be > 0";
+        if (!(params->min_count <= params->max_count && params->max_count <= RT_SAMPLE_MAX)) return "need min_count <= max_count <= RT_SAMPLE_MAX";
+        if (params->flags != 0u) return "flags must be 0";
+        return nullptr;
+    }
+
+    bool empty() const { return n == 0u; }
+
+    SampleBudget call() const {
+        return {mean, variance, count, valid, mean_stride, variance_stride, count_stride, valid_stride, params->gain, params->epsilon, params->min_count,
+                params->max_count, budget, n};
+    }
+};
 
 /* ---- rt_sample_list ---- */
 
@@ -120,22 +127,34 @@ RT_FILM_HD void listed_offsets_record(const ListedOffsets &o, uint64_t j, uint64
     o.offsets[2u * j + 1u] = film_offset(o.pattern, 0u, global, o.seed, s, 1u);
 }
 
-inline const char *listed_offsets_limits(const rt_frame *frame, uint32_t pattern, const uint32_t *pixel, const uint32_t *sample, const uint32_t *total,
-                                         uint64_t capacity, const float *offsets, int *status) {
-    *status = RT_ERR_INVALID_ARGUMENT;
-    if (!frame) return "null frame";
-    const uint64_t pixels = film_frame_pixels(frame);
-    if (pixels == 0u) return "bad frame (need 0 <= x0 < x1 <= width, 0 <= y0 < y1 <= height, y_step >= 1)";
-    if (pattern == RT_FILM_STRATIFIED) return "RT_FILM_STRATIFIED has no k x k in a ragged pass (RT_FILM_CENTER or RT_FILM_UNIFORM)";
-    if (pattern != RT_FILM_CENTER && pattern != RT_FILM_UNIFORM) return "unknown pattern (RT_FILM_CENTER or RT_FILM_UNIFORM)";
-    if (pixels >= (1ull << 32) || capacity >= (1ull << 32)) {
-        *status = RT_ERR_UNSUPPORTED;
-        return "2^32 pixels or records or more";
+/* the arguments of rt_film_offsets_listed and its CPU form (rt_query_args.h; no _host form) */
+struct ListedOffsetsArgs {
+    const rt_frame *frame;
+    uint32_t pattern, seed;
+    const uint32_t *pixel, *sample, *total;
+    uint64_t capacity;
+    float *offsets;
+
+    const char *limits(QueryForm, int *status) const {
+        *status = RT_ERR_INVALID_ARGUMENT;
+        if (!frame) return "null frame";
+        const uint64_t pixels = film_frame_pixels(frame);
+        if (pixels == 0u) return "bad frame (need 0 <= x0 < x1 <= width, 0 <= y0 < y1 <= height, y_step >= 1)";
+        if (pattern == RT_FILM_STRATIFIED) return "RT_FILM_STRATIFIED has no k x k in a ragged pass (RT_FILM_CENTER or RT_FILM_UNIFORM)";
+        if (pattern != RT_FILM_CENTER && pattern != RT_FILM_UNIFORM) return "unknown pattern (RT_FILM_CENTER or RT_FILM_UNIFORM)";
+        if (pixels >= (1ull << 32) || capacity >= (1ull << 32)) {
+            *status = RT_ERR_UNSUPPORTED;
+            return "2^32 pixels or records or more";
+        }
+        if (empty()) return nullptr;
+        if (!pixel || !sample || !total || !offsets) return "null pixel, sample, total or offset pointer";
+        return nullptr;
     }
-    if (capacity == 0u) return nullptr;
-    if (!pixel || !sample || !total || !offsets) return "null pixel, sample, total or offset pointer";
-    return nullptr;
-}
+
+    bool empty() const { return capacity == 0u; }
+
+    ListedOffsets call() const { return {film_tile(frame), pattern, seed, pixel, sample, total, capacity, offsets}; }
+};
 
 /* the camera of a listed ray: make_kernel_frame's fields (rt_temporal.h temporal_camera) and the tile */
 struct ListedCamera {

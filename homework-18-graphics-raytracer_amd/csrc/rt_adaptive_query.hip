@@ -171,6 +171,10 @@ __global__ __launch_bounds__(RT_IMAGE_THREADS) void camera_rays_listed_kernel(co
 
 /* ---- launchers ---- */
 
+static hipError_t launch_offsets_listed(const ListedOffsetsArgs &a, hipStream_t stream) {
+    return launch_groups(offsets_listed_kernel, (a.capacity + RT_IMAGE_THREADS - 1u) / RT_IMAGE_THREADS, OPT_DIAG_ADAPTIVE_MAX_GROUPS, stream, a.call());
+}
+
 static hipError_t launch_sample_list(const uint32_t *counts, uint64_t n, uint64_t capacity, uint32_t *first, uint32_t *start, uint32_t *pixel, uint32_t *sample,
                                      uint32_t *total, uint32_t *totals, hipStream_t stream) {
     const uint64_t steps = sample_list_steps(n);
@@ -191,12 +195,9 @@ extern "C" {
 int rt_sample_budget(const float *d_mean, uint32_t mean_stride, const float *d_variance, uint32_t variance_stride, const uint32_t *d_count,
                      uint32_t count_stride, const uint32_t *d_valid, uint32_t valid_stride, const rt_sample_budget_params *params, size_t n,
                      uint32_t *d_budget, void *hip_stream) {
-    int status;
-    const char *bad = rt::sample_budget_limits(d_mean, mean_stride, d_variance, variance_stride, d_count, count_stride, d_valid, valid_stride, params, n, d_budget, &status);
-    if (bad) return fail(status, std::string("rt_sample_budget: ") + bad);
-    if (n == 0u) return RT_OK;
-    const rt::SampleBudget b = rt::sample_budget_call(d_mean, mean_stride, d_variance, variance_stride, d_count, count_stride, d_valid, valid_stride, *params, n, d_budget);
-    return launched("rt_sample_budget", rt::launch_each(b, rt::OPT_DIAG_ADAPTIVE_MAX_GROUPS, static_cast<hipStream_t>(hip_stream)));
+    return device_query("rt_sample_budget",
+                        rt::SampleBudgetArgs{d_mean, mean_stride, d_variance, variance_stride, d_count, count_stride, d_valid, valid_stride, params, n, d_budget},
+                        rt::LaunchEach<rt::OPT_DIAG_ADAPTIVE_MAX_GROUPS>(), hip_stream);
 }
 
 size_t rt_sample_list_temp_bytes(size_t n) { return (size_t)rt::sample_list_temp_bytes(n); }
@@ -220,13 +221,8 @@ int rt_sample_list(const uint32_t *d_counts, size_t n, size_t capacity, uint32_t
 
 int rt_film_offsets_listed(const rt_frame *frame, uint32_t pattern, uint32_t seed, const uint32_t *d_pixel, const uint32_t *d_sample, const uint32_t *d_total,
                            size_t capacity, float *d_offsets, void *hip_stream) {
-    int status;
-    const char *bad = rt::listed_offsets_limits(frame, pattern, d_pixel, d_sample, d_total, capacity, d_offsets, &status);
-    if (bad) return fail(status, std::string("rt_film_offsets_listed: ") + bad);
-    if (capacity == 0u) return RT_OK;
-    const rt::ListedOffsets o = {rt::film_tile(frame), pattern, seed, d_pixel, d_sample, d_total, capacity, d_offsets};
-    return launched("rt_film_offsets_listed", rt::launch_groups(rt::offsets_listed_kernel, (capacity + RT_IMAGE_THREADS - 1u) / RT_IMAGE_THREADS,
-                                                                 rt::OPT_DIAG_ADAPTIVE_MAX_GROUPS, static_cast<hipStream_t>(hip_stream), o));
+    return device_query("rt_film_offsets_listed", rt::ListedOffsetsArgs{frame, pattern, seed, d_pixel, d_sample, d_total, capacity, d_offsets},
+                        rt::launch_offsets_listed, hip_stream);
 }
 
 int rt_camera_rays_listed(const rt_camera *camera, const rt_frame *frame, const float *d_offsets, const uint32_t *d_pixel, const uint32_t *d_total,

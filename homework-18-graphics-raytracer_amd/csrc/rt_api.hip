@@ -120,21 +120,23 @@ void *HostRoundTrip::add(void *h, size_t bytes, bool wanted, bool upload, bool d
     if (upload) e_ = hipMemcpy(d, h, bytes, hipMemcpyHostToDevice);
     return d;
 }
-rt_denoise_guides HostRoundTrip::guides(const rt_denoise_guides &h, size_t n, bool albedo) {
-    rt_denoise_guides g = h;
-    g.normal = plane(h.normal, n, h.normal_stride, 3u);
-    g.position = plane(h.position, n, h.position_stride, 3u);
-    g.albedo = albedo ? plane(h.albedo, n, h.albedo_stride, 3u) : nullptr;
-    g.valid = plane(h.valid, n, h.valid_stride, 1u);
-    return g;
+const rt_denoise_guides *HostRoundTrip::guides(const rt_denoise_guides *h, size_t n, bool albedo) {
+    rt_denoise_guides g = *h;
+    g.normal = plane(h->normal, n, h->normal_stride, 3u);
+    g.position = plane(h->position, n, h->position_stride, 3u);
+    g.albedo = albedo ? plane(h->albedo, n, h->albedo_stride, 3u) : nullptr;
+    g.valid = plane(h->valid, n, h->valid_stride, 1u);
+    guides_.push_back(g);
+    return &guides_.back();
 }
-rt_temporal_guides HostRoundTrip::temporal_guides(const rt_temporal_guides &h, size_t n) {
-    rt_temporal_guides g = h;
-    g.normal = plane(h.normal, n, h.normal_stride, 3u);
-    g.position = plane(h.position, n, h.position_stride, 3u);
-    g.object = plane(h.object, n, h.object_stride, 1u);
-    g.valid = plane(h.valid, n, h.valid_stride, 1u);
-    return g;
+const rt_temporal_guides *HostRoundTrip::guides(const rt_temporal_guides *h, size_t n) {
+    rt_temporal_guides g = *h;
+    g.normal = plane(h->normal, n, h->normal_stride, 3u);
+    g.position = plane(h->position, n, h->position_stride, 3u);
+    g.object = plane(h->object, n, h->object_stride, 1u);
+    g.valid = plane(h->valid, n, h->valid_stride, 1u);
+    temporal_guides_.push_back(g);
+    return &temporal_guides_.back();
 }
 unsigned long long *HostRoundTrip::counter() {
     if (e_ != hipSuccess) return nullptr;

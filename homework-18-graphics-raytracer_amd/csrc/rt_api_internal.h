@@ -29,6 +29,9 @@
  *   rt_adaptive_query.hip the adaptive sampling queries' rt_sample_budget / rt_sample_list / rt_film_offsets_listed / rt_camera_rays_listed / rt_film_splat_listed: kernels and entry points in one unit
  *   rt_upsample_query.hip the guided upsampling queries' rt_upsample_guided and its _host form: kernels and entry points in one unit
  *   rt_svgf_query.hip    the variance-guided filter queries' rt_svgf_variance / rt_svgf_atrous, their _host forms and rt_svgf_temp_bytes: kernels and entry points in one unit
+ * The image-side units from rt_denoise_query.hip on state each query's arguments once, as the struct of rt_query_args.h in the query's
+ * shared header; their device and _host entry points are device_query / host_query below, one statement each (rt_sample_list,
+ * rt_camera_rays_listed and the splats keep bodies of their own).
  * The film queries' kernels are rt_film_query.hip; their entry points are rt_api_query.hip's (rt_camera_rays_offset, beside rt_camera_rays) and
  * rt_api_post.hip's (rt_film_offsets / rt_film_splat, beside the accumulator).  The two splats, rt_film_query.hip's and
  * rt_adaptive_query.hip's, instantiate the kernel templates of rt_film_splat_kernel.h, each with its layout (rt_film.h, rt_adaptive.h).
@@ -51,6 +54,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <deque>
 #include <functional>
 #include <cmath>
 #include <limits>
@@ -66,6 +70,7 @@
 #include "rt_vec.h"
 #include "rt_luma.h"
 #include "rt_film.h"
+#include "rt_query_args.h"
 
 #define RT_API_HIDDEN __attribute__((visibility("hidden")))
 
@@ -265,8 +270,10 @@ public:
     HostRoundTrip &operator=(const HostRoundTrip &) = delete;
     template <class T> T *in(const T *h, size_t bytes) { return static_cast<T *>(add(const_cast<T *>(h), bytes, h != nullptr, true, false)); }
     template <class T> T *plane(const T *h, size_t n, uint32_t stride, uint32_t width) { return in(h, ((n - 1u) * stride + width) * sizeof(uint32_t)); }
-    rt_denoise_guides guides(const rt_denoise_guides &h, size_t n, bool albedo = true); /* the four planes of n pixels; albedo only where the call reads it */
-    rt_temporal_guides temporal_guides(const rt_temporal_guides &h, size_t n);          /* the four planes of n pixels */
+    /* the four planes of n pixels of a guides struct (albedo only where the call reads it): a copy of *h, held here until the
+     * destructor, that points at the device planes */
+    const rt_denoise_guides *guides(const rt_denoise_guides *h, size_t n, bool albedo = true);
+    const rt_temporal_guides *guides(const rt_temporal_guides *h, size_t n);
     template <class T> T *out(T *h, size_t bytes) { return static_cast<T *>(add(h, bytes, h != nullptr, false, true)); }
     template <class T> T *inout(T *h, size_t bytes) { return static_cast<T *>(add(h, bytes, h != nullptr, true, true)); } /* continues from the caller's values */
     void *scratch(size_t bytes) { return add(nullptr, bytes, true, false, false); }
@@ -284,8 +291,44 @@ private:
     const char *who_;
     hipError_t e_ = hipSuccess;
     std::vector<Buffer> buffers_;
+    std::deque<rt_denoise_guides> guides_; /* deques: an element stays where it is */
+    std::deque<rt_temporal_guides> temporal_guides_;
     unsigned long long *d_count_ = nullptr;
 };
+
+/* ---- the device form and the _host form of an image-side query, each written once.  `a` is the query's argument struct
+ * (rt_query_args.h); launch(a, stream) puts its kernels on the stream and returns the launch's status. ---- */
+
+/* the limits under the entry point's name, then "nothing to do"; *done: nothing to launch */
+template <class Args>
+static inline int query_checked(const char *who, const Args &a, rt::QueryForm form, bool *done) {
+    int status = RT_ERR_INVALID_ARGUMENT;
+    const char *bad = a.limits(form, &status);
+    *done = bad || a.empty();
+    return bad ? fail(status, std::string(who) + ": " + bad) : RT_OK;
+}
+
+template <class Args, class Launch>
+static inline int device_query(const char *who, const Args &a, Launch launch, void *hip_stream) {
+    bool done;
+    const int rc = query_checked(who, a, rt::QUERY_DEVICE, &done);
+    if (done) return rc;
+    return launched(who, launch(a, static_cast<hipStream_t>(hip_stream)));
+}
+
+/* the round trip: a.arrays() swaps every host pointer of the copy for its device array */
+template <class Args, class Launch>
+static inline int host_query(const char *who, Args a, Launch launch) {
+    bool done;
+    const int rc = query_checked(who, a, rt::QUERY_HOST_COPY, &done);
+    if (done) return rc;
+    HostRoundTrip t(who);
+    a.arrays(t);
+    if (!t.ok()) return t.failed();
+    const hipError_t e = launch(a, nullptr);
+    if (e != hipSuccess) return launched(who, e);
+    return t.finish();
+}
 
 RT_API_HIDDEN bool frame_ok(const rt_frame *f);
 RT_API_HIDDEN bool frame_fits(const rt_frame *f);

@@ -20,6 +20,7 @@
 
 #include "../../include/rt_amd.h"
 #include "rt_detmath.h"
+#include "rt_query_args.h"
 
 #if defined(__HIPCC__)
 #define RT_AT_HD __host__ __device__ __forceinline__
@@ -161,16 +162,16 @@ struct AtrousEach {
     }
 };
 
-/* every level of a call on the host: level_of(j) is the filter's Level */
-template <class F, class LevelOf>
-inline void atrous_cpu(uint32_t n_levels, LevelOf level_of) {
-    for (uint32_t j = 0; j < n_levels; ++j) {
-        const AtrousEach<F> level = {level_of(j)};
+/* every level of a call on the host: a.level(j) is the filter's Level */
+template <class F, class Args>
+inline void atrous_cpu(const Args &a) {
+    for (uint32_t j = 0; j < a.params->n_levels; ++j) {
+        const AtrousEach<F> level = {a.level(j)};
         for (uint64_t i = 0; i < level.count(); ++i) level(i);
     }
 }
 
-/* ---- the pieces of the argument checks: each returns its text, or null; the *_limits functions put them in the order
+/* ---- the pieces of the argument checks: each returns its text, or null; a query's limits() puts them in the order
  * include/rt_amd.h states ---- */
 
 inline const char *limits_image(uint64_t rows, uint64_t cols) {

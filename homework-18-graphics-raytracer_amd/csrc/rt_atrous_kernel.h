@@ -77,11 +77,11 @@ static hipError_t launch_atrous_level(const typename F::Level &L, bool tiled, Op
     return launch_groups(atrous_tiled_kernel<F>, n_tiles, hook, stream, L, blocks_x, n_tiles);
 }
 
-/* one launch per level of a call: level_of(j) is the filter's Level */
-template <class F, class LevelOf>
-static hipError_t launch_atrous(uint32_t n_levels, bool tiled, Option hook, hipStream_t stream, LevelOf level_of) {
-    for (uint32_t j = 0; j < n_levels; ++j) {
-        const hipError_t e = launch_atrous_level<F>(level_of(j), tiled, hook, stream);
+/* one launch per level of a call: a.level(j) is the filter's Level */
+template <class F, class Args>
+static hipError_t launch_atrous(const Args &a, bool tiled, Option hook, hipStream_t stream) {
+    for (uint32_t j = 0; j < a.params->n_levels; ++j) {
+        const hipError_t e = launch_atrous_level<F>(a.level(j), tiled, hook, stream);
         if (e != hipSuccess) return e;
     }
     return hipSuccess;

@@ -82,44 +82,62 @@ struct DenoiseFilter {
     static RT_AT_HD bool takes_taps(const DenoisePix &) { return true; }
 };
 
-/* Level j (0-based) of a call: which planes it reads and writes and its colour sigma.  sigma_color * 2^-j is an exact multiply by a
- * power of two. */
-inline DenoiseLevel denoise_level(const float *color, const rt_denoise_guides &g, const rt_denoise_params &p, uint32_t rows, uint32_t cols, float *out,
-                                  float *temp, uint32_t j) {
-    DenoiseLevel L;
-    const AtrousTurn t = atrous_schedule(L, g, p, rows, cols, j);
-    L.in = j == 0u ? color : (t.to_out ? temp : out);
-    L.out = t.to_out ? out : temp;
-    const float sc = p.sigma_color * (1.0f / (float)(1u << j));
-    L.sc2 = sc * sc;
-    return L;
-}
+/* The arguments of rt_denoise_atrous, rt_denoise_atrous_host and rt_denoise_atrous_cpu (rt_query_args.h).  temp is the caller's plane; the
+ * _host form passes null and its round trip makes its own. */
+struct DenoiseArgs {
+    const float *color;
+    const rt_denoise_guides *guides;
+    const rt_denoise_params *params;
+    uint32_t rows, cols;
+    float *out, *temp;
 
-/* THE argument check of rt_denoise_atrous, rt_denoise_atrous_host and rt_denoise_atrous_cpu, in the order include/rt_amd.h states;
- * null: all in range.  needs_temp: the caller passes a temp plane (the _host round trip makes its own). */
-inline const char *denoise_limits(const float *color, const rt_denoise_guides *g, const rt_denoise_params *p, uint64_t rows, uint64_t cols, const float *out,
-                                  const float *temp, bool needs_temp) {
-    if (!g) return "null guides";
-    if (!p) return "null params";
-    const char *bad = limits_image(rows, cols);
-    if (!bad) bad = limits_levels(p->first_level, p->n_levels);
-    if (!bad) bad = RT_LIMITS_SIGMA(p, sigma_color);
-    if (!bad) bad = RT_LIMITS_SIGMA(p, sigma_normal);
-    if (!bad) bad = RT_LIMITS_SIGMA(p, sigma_position);
-    if (!bad) bad = limits_demodulation(p->flags, g);
-    if (!bad) bad = limits_guide_strides(g);
-    if (bad) return bad;
-    if (rows == 0u || cols == 0u) return nullptr;
-    if (!color) return "null color pointer";
-    if (!out) return "null out pointer";
-    if (out == color) return "out must not be color";
-    if (needs_temp) {
-        if (!temp && p->n_levels >= 2u) return "null temp pointer with n_levels >= 2";
-        if (temp && temp == color) return "temp must not be color";
-        if (temp && temp == out) return "temp must not be out";
+    const char *limits(QueryForm form, int *status) const {
+        *status = RT_ERR_INVALID_ARGUMENT;
+        if (!guides) return "null guides";
+        if (!params) return "null params";
+        const char *bad = limits_image(rows, cols);
+        if (!bad) bad = limits_levels(params->first_level, params->n_levels);
+        if (!bad) bad = RT_LIMITS_SIGMA(params, sigma_color);
+        if (!bad) bad = RT_LIMITS_SIGMA(params, sigma_normal);
+        if (!bad) bad = RT_LIMITS_SIGMA(params, sigma_position);
+        if (!bad) bad = limits_demodulation(params->flags, guides);
+        if (!bad) bad = limits_guide_strides(guides);
+        if (bad) return bad;
+        if (empty()) return nullptr;
+        if (!color) return "null color pointer";
+        if (!out) return "null out pointer";
+        if (out == color) return "out must not be color";
+        if (query_takes_temp(form)) {
+            if (!temp && params->n_levels >= 2u) return "null temp pointer with n_levels >= 2";
+            if (temp && temp == color) return "temp must not be color";
+            if (temp && temp == out) return "temp must not be out";
+        }
+        return nullptr;
     }
-    return nullptr;
-}
+
+    bool empty() const { return rows == 0u || cols == 0u; }
+
+    template <class Stage>
+    void arrays(Stage &s) {
+        const size_t n = (size_t)rows * cols, plane = n * 3u * sizeof(float);
+        color = s.in(color, plane);
+        guides = s.guides(guides, n);
+        out = s.out(out, plane);
+        temp = params->n_levels >= 2u ? static_cast<float *>(s.scratch(plane)) : nullptr;
+    }
+
+    /* Level j (0-based) of the call: which planes it reads and writes and its colour sigma.  sigma_color * 2^-j is an exact multiply by
+     * a power of two. */
+    DenoiseLevel level(uint32_t j) const {
+        DenoiseLevel L;
+        const AtrousTurn t = atrous_schedule(L, *guides, *params, rows, cols, j);
+        L.in = j == 0u ? color : (t.to_out ? temp : out);
+        L.out = t.to_out ? out : temp;
+        const float sc = params->sigma_color * (1.0f / (float)(1u << j));
+        L.sc2 = sc * sc;
+        return L;
+    }
+};
 
 } /* namespace rt */
 

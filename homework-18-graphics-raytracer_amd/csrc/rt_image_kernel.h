@@ -52,6 +52,13 @@ static hipError_t launch_each(const Op &op, Option hook, hipStream_t stream) {
     return launch_groups(each_kernel<Op>, (op.count() + RT_IMAGE_THREADS - 1u) / RT_IMAGE_THREADS, hook, stream, op);
 }
 
+/* the launcher of a query (rt_query_args.h) whose call() is such an Op, under the unit's hook */
+template <Option HOOK>
+struct LaunchEach {
+    template <class Args>
+    hipError_t operator()(const Args &a, hipStream_t stream) const { return launch_each(a.call(), HOOK, stream); }
+};
+
 /* ---- one workgroup per 16 x 16 tile ---- */
 
 struct TilePixel { uint32_t ty, tx; };

@@ -44,15 +44,6 @@ struct RectifyBounds {
     rt_temporal_box *box;
 };
 
-inline RectifyBounds rectify_bounds_call(const float *color, uint32_t color_stride, const uint32_t *object, uint32_t object_stride, const uint32_t *valid,
-                                         uint32_t valid_stride, const rt_bounds_params &p, uint32_t rows, uint32_t cols, rt_temporal_box *box) {
-    RectifyBounds b;
-    b.color = color, b.object = object, b.valid = valid;
-    b.color_stride = color_stride, b.object_stride = object_stride, b.valid_stride = valid_stride;
-    b.rows = rows, b.cols = cols, b.radius = (int)p.radius, b.gamma = p.gamma, b.box = box;
-    return b;
-}
-
 /* what the box knows of a pixel: five words, x[3] the luminance.  An odd number, so a tile row spreads over the LDS banks. */
 struct RectifySource {
     float x[4];
@@ -244,60 +235,117 @@ RT_TP_HD void rectify_feedback_pixel(const RectifyFeedback &f, uint64_t i) {
 }
 RT_TP_HD void RectifyFeedback::operator()(uint64_t i) const { rectify_feedback_pixel(*this, i); }
 
-/* ---- THE argument checks, in the order include/rt_amd.h states; null: all in range, *status says how a refusal is reported ---- */
+/* ---- the arguments of the entry points (rt_query_args.h): the checks in the order include/rt_amd.h states.  The device forms read and
+ * write a box, and a record's first 16 bytes, as 128-bit words. ---- */
 
-/* aligned: the device form writes a box as two 128-bit words */
-inline const char *rectify_bounds_limits(const float *color, uint32_t color_stride, const uint32_t *object, uint32_t object_stride, const uint32_t *valid,
-                                         uint32_t valid_stride, const rt_bounds_params *p, uint64_t rows, uint64_t cols, const rt_temporal_box *box,
-                                         bool aligned, int *status) {
-    *status = RT_ERR_INVALID_ARGUMENT;
-    if (const char *bad = limits_image(rows, cols)) {
-        *status = RT_ERR_UNSUPPORTED;
-        return bad;
+/* rt_temporal_bounds, rt_temporal_bounds_host and rt_temporal_bounds_cpu */
+struct RectifyBoundsArgs {
+    const float *color; uint32_t color_stride;
+    const uint32_t *object; uint32_t object_stride;
+    const uint32_t *valid; uint32_t valid_stride;
+    const rt_bounds_params *params; uint32_t rows, cols; rt_temporal_box *box;
+
+    const char *limits(QueryForm form, int *status) const {
+        *status = RT_ERR_INVALID_ARGUMENT;
+        if (const char *bad = limits_image(rows, cols)) {
+            *status = RT_ERR_UNSUPPORTED;
+            return bad;
+        }
+        if (empty()) return nullptr;
+        if (!params) return "null params";
+        if (!color) return "null color pointer";
+        if (!box) return "null box pointer";
+        if (color_stride < 3u) return "color_stride must be at least 3 words";
+        if (object && object_stride < 1u) return "object_stride must be at least 1 word";
+        if (valid && valid_stride < 1u) return "valid_stride must be at least 1 word";
+        if (params->radius < 1u || params->radius > (uint32_t)RT_RECTIFY_MAX_RADIUS) return "radius must be 1, 2 or 3";
+        if (!(params->gamma >= 0.0f && params->gamma < __builtin_inff())) return "gamma must be >= 0 and finite";
+        if (params->flags != 0u) return "flags: unknown bits (none is defined)";
+        if (query_misaligned(form, box)) return "box must be 16-byte aligned";
+        return nullptr;
     }
-    if (rows == 0u || cols == 0u) return nullptr;
-    if (!p) return "null params";
-    if (!color) return "null color pointer";
-    if (!box) return "null box pointer";
-    if (color_stride < 3u) return "color_stride must be at least 3 words";
-    if (object && object_stride < 1u) return "object_stride must be at least 1 word";
-    if (valid && valid_stride < 1u) return "valid_stride must be at least 1 word";
-    if (p->radius < 1u || p->radius > (uint32_t)RT_RECTIFY_MAX_RADIUS) return "radius must be 1, 2 or 3";
-    if (!(p->gamma >= 0.0f && p->gamma < __builtin_inff())) return "gamma must be >= 0 and finite";
-    if (p->flags != 0u) return "flags: unknown bits (none is defined)";
-    if (aligned && ((uintptr_t)box & 15u)) return "box must be 16-byte aligned";
-    return nullptr;
-}
 
-/* rt_temporal_accumulate's checks (temporal_limits), then the box's */
-inline const char *rectify_accumulate_limits(const float *color, const float *motion, const rt_temporal_guides *cur, const rt_temporal_guides *prev,
-                                             const rt_temporal_params *p, uint64_t rows, uint64_t cols, const rt_temporal_pixel *in, const rt_temporal_pixel *out,
-                                             const rt_temporal_box *box, uint32_t clamped_length, bool aligned, int *status) {
-    if (const char *bad = temporal_limits(color, motion, cur, prev, p, rows, cols, in, out, aligned, status)) return bad;
-    if (rows == 0u || cols == 0u) return nullptr;
-    if (!box) return "null box pointer";
-    if (aligned && ((uintptr_t)box & 15u)) return "box must be 16-byte aligned";
-    if (clamped_length > p->max_length) return "clamped_length must not exceed max_length (0: the length is not cut)";
-    return nullptr;
-}
+    bool empty() const { return rows == 0u || cols == 0u; }
 
-/* aligned: the device form loads and stores a record's first 16 bytes as one word */
-inline const char *rectify_feedback_limits(const float *color, uint32_t color_stride, const uint32_t *valid, uint32_t valid_stride, uint64_t rows,
-                                           uint64_t cols, const rt_temporal_pixel *history, bool aligned, int *status) {
-    *status = RT_ERR_INVALID_ARGUMENT;
-    if (const char *bad = limits_image(rows, cols)) {
-        *status = RT_ERR_UNSUPPORTED;
-        return bad;
+    template <class Stage>
+    void arrays(Stage &s) {
+        const size_t n = (size_t)rows * cols;
+        color = s.plane(color, n, color_stride, 3u);
+        object = s.plane(object, n, object_stride, 1u);
+        valid = s.plane(valid, n, valid_stride, 1u);
+        box = s.out(box, n * sizeof(rt_temporal_box));
     }
-    if (rows == 0u || cols == 0u) return nullptr;
-    if (!color) return "null color pointer";
-    if (!history) return "null history pointer";
-    if (color_stride < 3u) return "color_stride must be at least 3 words";
-    if (valid && valid_stride < 1u) return "valid_stride must be at least 1 word";
-    if (aligned && ((uintptr_t)history & 15u)) return "history must be 16-byte aligned";
-    return nullptr;
-}
+
+    RectifyBounds call() const {
+        RectifyBounds b;
+        b.color = color, b.object = object, b.valid = valid;
+        b.color_stride = color_stride, b.object_stride = object_stride, b.valid_stride = valid_stride;
+        b.rows = rows, b.cols = cols, b.radius = (int)params->radius, b.gamma = params->gamma, b.box = box;
+        return b;
+    }
+};
+
+/* rt_temporal_accumulate_bounded, its _host and its _cpu form: rt_temporal_accumulate's arguments and checks, then the box's */
+struct RectifyAccumulateArgs : TemporalAccumulateArgs {
+    const rt_temporal_box *box;
+    uint32_t clamped_length;
+    uint32_t *clamped;
+
+    const char *limits(QueryForm form, int *status) const {
+        if (const char *bad = TemporalAccumulateArgs::limits(form, status)) return bad;
+        if (empty()) return nullptr;
+        if (!box) return "null box pointer";
+        if (query_misaligned(form, box)) return "box must be 16-byte aligned";
+        if (clamped_length > params->max_length) return "clamped_length must not exceed max_length (0: the length is not cut)";
+        return nullptr;
+    }
+
+    template <class Stage>
+    void arrays(Stage &s) {
+        const size_t n = (size_t)rows * cols;
+        TemporalAccumulateArgs::arrays(s);
+        box = s.in(box, n * sizeof(rt_temporal_box));
+        clamped = s.out(clamped, n * sizeof(uint32_t));
+    }
+
+    RectifyAccumulate call() const { return {TemporalAccumulateArgs::call(), box, clamped_length, clamped}; }
+};
+
+/* rt_temporal_feedback, rt_temporal_feedback_host and rt_temporal_feedback_cpu */
+struct RectifyFeedbackArgs {
+    const float *color; uint32_t color_stride;
+    const uint32_t *valid; uint32_t valid_stride;
+    uint32_t rows, cols; rt_temporal_pixel *history;
+
+    const char *limits(QueryForm form, int *status) const {
+        *status = RT_ERR_INVALID_ARGUMENT;
+        if (const char *bad = limits_image(rows, cols)) {
+            *status = RT_ERR_UNSUPPORTED;
+            return bad;
+        }
+        if (empty()) return nullptr;
+        if (!color) return "null color pointer";
+        if (!history) return "null history pointer";
+        if (color_stride < 3u) return "color_stride must be at least 3 words";
+        if (valid && valid_stride < 1u) return "valid_stride must be at least 1 word";
+        if (query_misaligned(form, history)) return "history must be 16-byte aligned";
+        return nullptr;
+    }
+
+    bool empty() const { return rows == 0u || cols == 0u; }
+
+    template <class Stage>
+    void arrays(Stage &s) {
+        const size_t n = (size_t)rows * cols;
+        color = s.plane(color, n, color_stride, 3u);
+        valid = s.plane(valid, n, valid_stride, 1u);
+        history = s.inout(history, n * sizeof(rt_temporal_pixel));
+    }
+
+    RectifyFeedback call() const { return {color, valid, color_stride, valid_stride, (uint64_t)rows * cols, history}; }
+};
 
 } /* namespace rt */
 
 #endif /* RT_RECTIFY_H */
+

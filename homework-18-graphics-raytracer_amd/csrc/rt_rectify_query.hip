@@ -48,110 +48,58 @@ __global__ __launch_bounds__(RT_IMAGE_THREADS) void bounds_kernel(const RectifyB
     }
 }
 
-static hipError_t launch_box(const RectifyBounds &b, hipStream_t stream) {
-    return launch_tiles(bounds_kernel, b.rows, b.cols, OPT_DIAG_RECTIFY_MAX_GROUPS, stream, b);
+static hipError_t launch_box(const RectifyBoundsArgs &a, hipStream_t stream) {
+    return launch_tiles(bounds_kernel, a.rows, a.cols, OPT_DIAG_RECTIFY_MAX_GROUPS, stream, a.call());
 }
 
 } /* namespace rt */
+
+static const rt::LaunchEach<rt::OPT_DIAG_RECTIFY_MAX_GROUPS> launch_rectify;
 
 extern "C" {
 
 int rt_temporal_bounds(const float *d_color, uint32_t color_stride, const uint32_t *d_object, uint32_t object_stride, const uint32_t *d_valid,
                        uint32_t valid_stride, const rt_bounds_params *params, uint32_t rows, uint32_t cols, rt_temporal_box *d_box, void *hip_stream) {
-    int status;
-    const char *bad = rt::rectify_bounds_limits(d_color, color_stride, d_object, object_stride, d_valid, valid_stride, params, rows, cols, d_box, true, &status);
-    if (bad) return fail(status, std::string("rt_temporal_bounds: ") + bad);
-    if (rows == 0u || cols == 0u) return RT_OK;
-    return launched("rt_temporal_bounds",
-                    rt::launch_box(rt::rectify_bounds_call(d_color, color_stride, d_object, object_stride, d_valid, valid_stride, *params, rows, cols, d_box),
-                                      static_cast<hipStream_t>(hip_stream)));
+    return device_query("rt_temporal_bounds", rt::RectifyBoundsArgs{d_color, color_stride, d_object, object_stride, d_valid, valid_stride, params, rows, cols, d_box},
+                        rt::launch_box, hip_stream);
 }
 
 int rt_temporal_accumulate_bounded(const float *d_color, const float *d_motion, const rt_temporal_guides *current, const rt_temporal_guides *previous,
                                    const rt_temporal_params *params, uint32_t rows, uint32_t cols, const rt_temporal_pixel *d_history_in,
                                    rt_temporal_pixel *d_history_out, float *d_variance, const rt_temporal_box *d_box, uint32_t clamped_length,
                                    uint32_t *d_clamped, void *hip_stream) {
-    int status;
-    const char *bad = rt::rectify_accumulate_limits(d_color, d_motion, current, previous, params, rows, cols, d_history_in, d_history_out, d_box, clamped_length,
-                                                    true, &status);
-    if (bad) return fail(status, std::string("rt_temporal_accumulate_bounded: ") + bad);
-    if (rows == 0u || cols == 0u) return RT_OK;
-    const rt::RectifyAccumulate a = {rt::temporal_call(d_color, d_motion, *current, *previous, *params, rows, cols, d_history_in, d_history_out, d_variance),
-                                     d_box, clamped_length, d_clamped};
-    return launched("rt_temporal_accumulate_bounded", rt::launch_each(a, rt::OPT_DIAG_RECTIFY_MAX_GROUPS, static_cast<hipStream_t>(hip_stream)));
+    return device_query("rt_temporal_accumulate_bounded",
+                        rt::RectifyAccumulateArgs{{d_color, d_motion, current, previous, params, rows, cols, d_history_in, d_history_out, d_variance},
+                                                  d_box, clamped_length, d_clamped},
+                        launch_rectify, hip_stream);
 }
 
 int rt_temporal_feedback(const float *d_color, uint32_t color_stride, const uint32_t *d_valid, uint32_t valid_stride, uint32_t rows, uint32_t cols,
                          rt_temporal_pixel *d_history, void *hip_stream) {
-    int status;
-    const char *bad = rt::rectify_feedback_limits(d_color, color_stride, d_valid, valid_stride, rows, cols, d_history, true, &status);
-    if (bad) return fail(status, std::string("rt_temporal_feedback: ") + bad);
-    if (rows == 0u || cols == 0u) return RT_OK;
-    const rt::RectifyFeedback f = {d_color, d_valid, color_stride, valid_stride, (uint64_t)rows * cols, d_history};
-    return launched("rt_temporal_feedback", rt::launch_each(f, rt::OPT_DIAG_RECTIFY_MAX_GROUPS, static_cast<hipStream_t>(hip_stream)));
+    return device_query("rt_temporal_feedback", rt::RectifyFeedbackArgs{d_color, color_stride, d_valid, valid_stride, rows, cols, d_history}, launch_rectify,
+                        hip_stream);
 }
 
 int rt_temporal_bounds_host(const float *h_color, uint32_t color_stride, const uint32_t *h_object, uint32_t object_stride, const uint32_t *h_valid,
                             uint32_t valid_stride, const rt_bounds_params *params, uint32_t rows, uint32_t cols, rt_temporal_box *h_box) {
-    int status;
-    /* the device copy is hipMalloc's and aligned whatever the host array is */
-    const char *bad = rt::rectify_bounds_limits(h_color, color_stride, h_object, object_stride, h_valid, valid_stride, params, rows, cols, h_box, false, &status);
-    if (bad) return fail(status, std::string("rt_temporal_bounds_host: ") + bad);
-    if (rows == 0u || cols == 0u) return RT_OK;
-    const size_t n = (size_t)rows * cols;
-    HostRoundTrip t("rt_temporal_bounds_host");
-    const float *d_color = t.plane(h_color, n, color_stride, 3u);
-    const uint32_t *d_object = t.plane(h_object, n, object_stride, 1u);
-    const uint32_t *d_valid = t.plane(h_valid, n, valid_stride, 1u);
-    rt_temporal_box *d_box = t.out(h_box, n * sizeof(rt_temporal_box));
-    if (!t.ok()) return t.failed();
-    const hipError_t e = rt::launch_box(rt::rectify_bounds_call(d_color, color_stride, d_object, object_stride, d_valid, valid_stride, *params, rows, cols, d_box), nullptr);
-    if (e != hipSuccess) return launched("rt_temporal_bounds_host", e);
-    return t.finish();
+    return host_query("rt_temporal_bounds_host", rt::RectifyBoundsArgs{h_color, color_stride, h_object, object_stride, h_valid, valid_stride, params, rows, cols, h_box},
+                      rt::launch_box);
 }
 
 int rt_temporal_accumulate_bounded_host(const float *h_color, const float *h_motion, const rt_temporal_guides *current, const rt_temporal_guides *previous,
                                         const rt_temporal_params *params, uint32_t rows, uint32_t cols, const rt_temporal_pixel *h_history_in,
                                         rt_temporal_pixel *h_history_out, float *h_variance, const rt_temporal_box *h_box, uint32_t clamped_length,
                                         uint32_t *h_clamped) {
-    int status;
-    const char *bad = rt::rectify_accumulate_limits(h_color, h_motion, current, previous, params, rows, cols, h_history_in, h_history_out, h_box, clamped_length,
-                                                    false, &status);
-    if (bad) return fail(status, std::string("rt_temporal_accumulate_bounded_host: ") + bad);
-    if (rows == 0u || cols == 0u) return RT_OK;
-    const size_t n = (size_t)rows * cols;
-    HostRoundTrip t("rt_temporal_accumulate_bounded_host");
-    const float *d_color = t.in(h_color, n * 3u * sizeof(float));
-    const float *d_motion = t.in(h_motion, n * 2u * sizeof(float));
-    const rt_temporal_guides cur = t.temporal_guides(*current, n), prev = t.temporal_guides(*previous, n);
-    const rt_temporal_pixel *d_in = t.in(h_history_in, n * sizeof(rt_temporal_pixel));
-    rt_temporal_pixel *d_out = t.out(h_history_out, n * sizeof(rt_temporal_pixel));
-    float *d_variance = t.out(h_variance, n * sizeof(float));
-    const rt_temporal_box *d_box = t.in(h_box, n * sizeof(rt_temporal_box));
-    uint32_t *d_clamped = t.out(h_clamped, n * sizeof(uint32_t));
-    if (!t.ok()) return t.failed();
-    const rt::RectifyAccumulate a = {rt::temporal_call(d_color, d_motion, cur, prev, *params, rows, cols, d_in, d_out, d_variance), d_box, clamped_length, d_clamped};
-    const hipError_t e = rt::launch_each(a, rt::OPT_DIAG_RECTIFY_MAX_GROUPS, nullptr);
-    if (e != hipSuccess) return launched("rt_temporal_accumulate_bounded_host", e);
-    return t.finish();
+    return host_query("rt_temporal_accumulate_bounded_host",
+                      rt::RectifyAccumulateArgs{{h_color, h_motion, current, previous, params, rows, cols, h_history_in, h_history_out, h_variance},
+                                                h_box, clamped_length, h_clamped},
+                      launch_rectify);
 }
 
 int rt_temporal_feedback_host(const float *h_color, uint32_t color_stride, const uint32_t *h_valid, uint32_t valid_stride, uint32_t rows, uint32_t cols,
                               rt_temporal_pixel *h_history) {
-    int status;
-    const char *bad = rt::rectify_feedback_limits(h_color, color_stride, h_valid, valid_stride, rows, cols, h_history, false, &status);
-    if (bad) return fail(status, std::string("rt_temporal_feedback_host: ") + bad);
-    if (rows == 0u || cols == 0u) return RT_OK;
-    const size_t n = (size_t)rows * cols;
-    HostRoundTrip t("rt_temporal_feedback_host");
-    const float *d_color = t.plane(h_color, n, color_stride, 3u);
-    const uint32_t *d_valid = t.plane(h_valid, n, valid_stride, 1u);
-    rt_temporal_pixel *d_history = t.inout(h_history, n * sizeof(rt_temporal_pixel));
-    if (!t.ok()) return t.failed();
-    const rt::RectifyFeedback f = {d_color, d_valid, color_stride, valid_stride, (uint64_t)n, d_history};
-    const hipError_t e = rt::launch_each(f, rt::OPT_DIAG_RECTIFY_MAX_GROUPS, nullptr);
-    if (e != hipSuccess) return launched("rt_temporal_feedback_host", e);
-    return t.finish();
+    return host_query("rt_temporal_feedback_host", rt::RectifyFeedbackArgs{h_color, color_stride, h_valid, valid_stride, rows, cols, h_history}, launch_rectify);
 }
 
 } /* extern "C" */
+

@@ -35,17 +35,6 @@ struct SvgfVariance : GuidePlanes { /* the albedo plane is not looked at */
     float *out;
 };
 
-inline SvgfVariance svgf_variance_call(const rt_temporal_pixel *history, const rt_denoise_guides &g, const rt_svgf_variance_params &p, uint32_t rows,
-                                       uint32_t cols, float *out) {
-    SvgfVariance v;
-    guide_planes(v, g, rows, cols);
-    v.history = history;
-    v.sn2 = p.sigma_normal * p.sigma_normal, v.sp2 = p.sigma_position * p.sigma_position;
-    v.min_length = p.min_length, v.min_length_f = (float)p.min_length;
-    v.out = out;
-    return v;
-}
-
 /* what the estimate knows of a pixel: nine words.  length == 0 says "no source": no history there, or its valid word is cleared (or, in
  * a staged tile, it lies outside the image). */
 struct SvgfMoments {
@@ -222,82 +211,129 @@ struct SvgfFilter {
 #define RT_SVGF_ENTRY_WORDS 4u
 inline uint32_t svgf_temp_words(uint32_t n_levels) { return n_levels < 2u ? 0u : n_levels == 2u ? RT_SVGF_ENTRY_WORDS : RT_SVGF_ENTRY_WORDS + 1u; }
 
-/* Level j (0-based) of a call: which planes it reads and writes.  sigma_luminance is the same at every level. */
-inline SvgfLevel svgf_level(const float *color, uint32_t color_stride, const float *variance, const rt_denoise_guides &g, const rt_svgf_atrous_params &p,
-                            uint32_t rows, uint32_t cols, float *out, float *variance_out, float *temp, uint32_t j) {
-    SvgfLevel L;
-    const AtrousTurn t = atrous_schedule(L, g, p, rows, cols, j);
-    const uint64_t n = (uint64_t)rows * cols;
-    /* where a level that writes "the outputs" puts its variance: the caller's plane, else (unless it is the last level) the spare plane */
-    float *const spare = temp ? temp + n * RT_SVGF_ENTRY_WORDS : nullptr;
-    float *const out_variance = variance_out ? variance_out : spare;
-    if (j == 0u) {
-        L.in = color, L.in_stride = color_stride, L.vin = variance, L.vin_stride = 1u;
-    } else if (t.to_out) { /* the level before wrote the entries */
-        L.in = temp, L.in_stride = RT_SVGF_ENTRY_WORDS, L.vin = temp + 3, L.vin_stride = RT_SVGF_ENTRY_WORDS;
-    } else {
-        L.in = out, L.in_stride = 3u, L.vin = out_variance, L.vin_stride = 1u;
-    }
-    if (t.to_out) {
-        L.out = out, L.out_stride = 3u, L.vout = t.after == 0u ? variance_out : out_variance, L.vout_stride = 1u;
-    } else {
-        L.out = temp, L.out_stride = RT_SVGF_ENTRY_WORDS, L.vout = temp + 3, L.vout_stride = RT_SVGF_ENTRY_WORDS;
-    }
-    L.sigma_l = p.sigma_luminance;
-    return L;
-}
+/* ---- the arguments of the entry points (rt_query_args.h): the checks in the order include/rt_amd.h states ---- */
 
-/* ---- THE argument checks, in the order include/rt_amd.h states; null: all in range ---- */
+/* rt_svgf_variance, rt_svgf_variance_host and rt_svgf_variance_cpu.  The device form takes the records rt_temporal_accumulate wrote,
+ * which are 16-byte aligned there. */
+struct SvgfVarianceArgs {
+    const rt_temporal_pixel *history;
+    const rt_denoise_guides *guides;
+    const rt_svgf_variance_params *params;
+    uint32_t rows, cols;
+    float *variance_out;
 
-/* rt_svgf_variance, rt_svgf_variance_host and rt_svgf_variance_cpu.  aligned: the device form takes the records rt_temporal_accumulate
- * wrote, which are 16-byte aligned there. */
-inline const char *svgf_variance_limits(const rt_temporal_pixel *history, const rt_denoise_guides *g, const rt_svgf_variance_params *p, uint64_t rows,
-                                        uint64_t cols, const float *out, bool aligned) {
-    if (!g) return "null guides";
-    if (!p) return "null params";
-    const char *bad = limits_image(rows, cols);
-    if (!bad) bad = RT_LIMITS_SIGMA(p, sigma_normal);
-    if (!bad) bad = RT_LIMITS_SIGMA(p, sigma_position);
-    if (!bad && p->min_length < 1u) bad = "min_length must be at least 1";
-    if (!bad && p->flags != 0u) bad = "flags: unknown bits (none is defined)";
-    if (!bad) bad = limits_guide_strides(g);
-    if (bad) return bad;
-    if (rows == 0u || cols == 0u) return nullptr;
-    if (!history) return "null history pointer";
-    if (!out) return "null variance_out pointer";
-    if ((const void *)out == (const void *)history) return "variance_out must not be history";
-    if (aligned && ((uintptr_t)history & 15u)) return "history must be 16-byte aligned";
-    return nullptr;
-}
-
-/* rt_svgf_atrous, rt_svgf_atrous_host and rt_svgf_atrous_cpu.  needs_temp: the caller passes the scratch (the _host round trip makes its own). */
-inline const char *svgf_atrous_limits(const float *color, uint32_t color_stride, const float *variance, const rt_denoise_guides *g,
-                                      const rt_svgf_atrous_params *p, uint64_t rows, uint64_t cols, const float *out, const float *variance_out,
-                                      const float *temp, bool needs_temp) {
-    if (!g) return "null guides";
-    if (!p) return "null params";
-    const char *bad = limits_image(rows, cols);
-    if (!bad) bad = limits_levels(p->first_level, p->n_levels);
-    if (!bad) bad = RT_LIMITS_SIGMA(p, sigma_luminance);
-    if (!bad) bad = RT_LIMITS_SIGMA(p, sigma_normal);
-    if (!bad) bad = RT_LIMITS_SIGMA(p, sigma_position);
-    if (!bad) bad = limits_demodulation(p->flags, g);
-    if (!bad && color_stride < 3u) bad = "color_stride must be at least 3 words";
-    if (!bad) bad = limits_guide_strides(g);
-    if (bad) return bad;
-    if (rows == 0u || cols == 0u) return nullptr;
-    if (!color) return "null color pointer";
-    if (!variance) return "null variance pointer";
-    if (!out) return "null out pointer";
-    if (out == color || out == variance) return "out must not be color or variance";
-    if (variance_out && (variance_out == color || variance_out == variance || variance_out == out)) return "variance_out must not be color, variance or out";
-    if (needs_temp) {
-        if (!temp && p->n_levels >= 2u) return "null temp pointer with n_levels >= 2";
-        if (temp && (temp == color || temp == variance || temp == out || temp == variance_out)) return "temp must not be color, variance, out or variance_out";
+    const char *limits(QueryForm form, int *status) const {
+        *status = RT_ERR_INVALID_ARGUMENT;
+        if (!guides) return "null guides";
+        if (!params) return "null params";
+        const char *bad = limits_image(rows, cols);
+        if (!bad) bad = RT_LIMITS_SIGMA(params, sigma_normal);
+        if (!bad) bad = RT_LIMITS_SIGMA(params, sigma_position);
+        if (!bad && params->min_length < 1u) bad = "min_length must be at least 1";
+        if (!bad && params->flags != 0u) bad = "flags: unknown bits (none is defined)";
+        if (!bad) bad = limits_guide_strides(guides);
+        if (bad) return bad;
+        if (empty()) return nullptr;
+        if (!history) return "null history pointer";
+        if (!variance_out) return "null variance_out pointer";
+        if ((const void *)variance_out == (const void *)history) return "variance_out must not be history";
+        if (query_misaligned(form, history)) return "history must be 16-byte aligned";
+        return nullptr;
     }
-    return nullptr;
-}
+
+    bool empty() const { return rows == 0u || cols == 0u; }
+
+    template <class Stage>
+    void arrays(Stage &s) {
+        const size_t n = (size_t)rows * cols;
+        history = s.in(history, n * sizeof(rt_temporal_pixel));
+        guides = s.guides(guides, n, false); /* the estimate reads no albedo */
+        variance_out = s.out(variance_out, n * sizeof(float));
+    }
+
+    SvgfVariance call() const {
+        SvgfVariance v;
+        guide_planes(v, *guides, rows, cols);
+        v.history = history;
+        v.sn2 = params->sigma_normal * params->sigma_normal, v.sp2 = params->sigma_position * params->sigma_position;
+        v.min_length = params->min_length, v.min_length_f = (float)params->min_length;
+        v.out = variance_out;
+        return v;
+    }
+};
+
+/* rt_svgf_atrous, rt_svgf_atrous_host and rt_svgf_atrous_cpu.  temp is the caller's scratch; the _host form passes null and its round
+ * trip makes its own. */
+struct SvgfAtrousArgs {
+    const float *color; uint32_t color_stride; const float *variance;
+    const rt_denoise_guides *guides; const rt_svgf_atrous_params *params;
+    uint32_t rows, cols; float *out, *variance_out, *temp;
+
+    const char *limits(QueryForm form, int *status) const {
+        *status = RT_ERR_INVALID_ARGUMENT;
+        if (!guides) return "null guides";
+        if (!params) return "null params";
+        const char *bad = limits_image(rows, cols);
+        if (!bad) bad = limits_levels(params->first_level, params->n_levels);
+        if (!bad) bad = RT_LIMITS_SIGMA(params, sigma_luminance);
+        if (!bad) bad = RT_LIMITS_SIGMA(params, sigma_normal);
+        if (!bad) bad = RT_LIMITS_SIGMA(params, sigma_position);
+        if (!bad) bad = limits_demodulation(params->flags, guides);
+        if (!bad && color_stride < 3u) bad = "color_stride must be at least 3 words";
+        if (!bad) bad = limits_guide_strides(guides);
+        if (bad) return bad;
+        if (empty()) return nullptr;
+        if (!color) return "null color pointer";
+        if (!variance) return "null variance pointer";
+        if (!out) return "null out pointer";
+        if (out == color || out == variance) return "out must not be color or variance";
+        if (variance_out && (variance_out == color || variance_out == variance || variance_out == out)) return "variance_out must not be color, variance or out";
+        if (query_takes_temp(form)) {
+            if (!temp && params->n_levels >= 2u) return "null temp pointer with n_levels >= 2";
+            if (temp && (temp == color || temp == variance || temp == out || temp == variance_out)) return "temp must not be color, variance, out or variance_out";
+        }
+        return nullptr;
+    }
+
+    bool empty() const { return rows == 0u || cols == 0u; }
+
+    template <class Stage>
+    void arrays(Stage &s) {
+        const size_t n = (size_t)rows * cols, temp_bytes = n * svgf_temp_words(params->n_levels) * sizeof(float);
+        color = s.plane(color, n, color_stride, 3u);
+        variance = s.in(variance, n * sizeof(float));
+        guides = s.guides(guides, n);
+        out = s.out(out, n * 3u * sizeof(float));
+        variance_out = s.out(variance_out, n * sizeof(float));
+        temp = temp_bytes ? static_cast<float *>(s.scratch(temp_bytes)) : nullptr;
+    }
+
+    /* Level j (0-based) of the call: which planes it reads and writes.  sigma_luminance is the same at every level. */
+    SvgfLevel level(uint32_t j) const {
+        SvgfLevel L;
+        const AtrousTurn t = atrous_schedule(L, *guides, *params, rows, cols, j);
+        const uint64_t n = (uint64_t)rows * cols;
+        /* where a level that writes "the outputs" puts its variance: the caller's plane, else (unless it is the last level) the spare plane */
+        float *const spare = temp ? temp + n * RT_SVGF_ENTRY_WORDS : nullptr;
+        float *const out_variance = variance_out ? variance_out : spare;
+        if (j == 0u) {
+            L.in = color, L.in_stride = color_stride, L.vin = variance, L.vin_stride = 1u;
+        } else if (t.to_out) { /* the level before wrote the entries */
+            L.in = temp, L.in_stride = RT_SVGF_ENTRY_WORDS, L.vin = temp + 3, L.vin_stride = RT_SVGF_ENTRY_WORDS;
+        } else {
+            L.in = out, L.in_stride = 3u, L.vin = out_variance, L.vin_stride = 1u;
+        }
+        if (t.to_out) {
+            L.out = out, L.out_stride = 3u, L.vout = t.after == 0u ? variance_out : out_variance, L.vout_stride = 1u;
+        } else {
+            L.out = temp, L.out_stride = RT_SVGF_ENTRY_WORDS, L.vout = temp + 3, L.vout_stride = RT_SVGF_ENTRY_WORDS;
+        }
+        L.sigma_l = params->sigma_luminance;
+        return L;
+    }
+};
 
 } /* namespace rt */
 
 #endif /* RT_SVGF_H */
+

@@ -68,14 +68,12 @@ __global__ __launch_bounds__(RT_IMAGE_THREADS) void svgf_variance_kernel(const S
     }
 }
 
-static hipError_t launch_svgf_variance(const SvgfVariance &v, hipStream_t stream) {
-    return launch_tiles(svgf_variance_kernel, v.rows, v.cols, OPT_DIAG_SVGF_MAX_GROUPS, stream, v);
+static hipError_t launch_svgf_variance(const SvgfVarianceArgs &a, hipStream_t stream) {
+    return launch_tiles(svgf_variance_kernel, a.rows, a.cols, OPT_DIAG_SVGF_MAX_GROUPS, stream, a.call());
 }
 
-static hipError_t launch_svgf(const float *color, uint32_t color_stride, const float *variance, const rt_denoise_guides &g, const rt_svgf_atrous_params &p,
-                              uint32_t rows, uint32_t cols, float *out, float *variance_out, float *temp, hipStream_t stream) {
-    return launch_atrous<SvgfFilter>(p.n_levels, option(OPT_SVGF_FORM, RT_SVGF_FORM_DEFAULT) == 1, OPT_DIAG_SVGF_MAX_GROUPS, stream,
-                                     [&](uint32_t j) { return svgf_level(color, color_stride, variance, g, p, rows, cols, out, variance_out, temp, j); });
+static hipError_t launch_svgf(const SvgfAtrousArgs &a, hipStream_t stream) {
+    return launch_atrous<SvgfFilter>(a, option(OPT_SVGF_FORM, RT_SVGF_FORM_DEFAULT) == 1, OPT_DIAG_SVGF_MAX_GROUPS, stream);
 }
 
 } /* namespace rt */
@@ -86,58 +84,27 @@ size_t rt_svgf_temp_bytes(uint32_t rows, uint32_t cols, uint32_t n_levels) { ret
 
 int rt_svgf_variance(const rt_temporal_pixel *d_history, const rt_denoise_guides *guides, const rt_svgf_variance_params *params, uint32_t rows,
                      uint32_t cols, float *d_variance_out, void *hip_stream) {
-    const char *bad = rt::svgf_variance_limits(d_history, guides, params, rows, cols, d_variance_out, true);
-    if (bad) return fail(RT_ERR_INVALID_ARGUMENT, std::string("rt_svgf_variance: ") + bad);
-    if (rows == 0u || cols == 0u) return RT_OK;
-    return launched("rt_svgf_variance",
-                    rt::launch_svgf_variance(rt::svgf_variance_call(d_history, *guides, *params, rows, cols, d_variance_out), static_cast<hipStream_t>(hip_stream)));
+    return device_query("rt_svgf_variance", rt::SvgfVarianceArgs{d_history, guides, params, rows, cols, d_variance_out}, rt::launch_svgf_variance, hip_stream);
 }
 
 int rt_svgf_atrous(const float *d_color, uint32_t color_stride, const float *d_variance, const rt_denoise_guides *guides,
                    const rt_svgf_atrous_params *params, uint32_t rows, uint32_t cols, float *d_out, float *d_variance_out, void *d_temp,
                    void *hip_stream) {
-    const char *bad = rt::svgf_atrous_limits(d_color, color_stride, d_variance, guides, params, rows, cols, d_out, d_variance_out, static_cast<float *>(d_temp), true);
-    if (bad) return fail(RT_ERR_INVALID_ARGUMENT, std::string("rt_svgf_atrous: ") + bad);
-    if (rows == 0u || cols == 0u) return RT_OK;
-    return launched("rt_svgf_atrous", rt::launch_svgf(d_color, color_stride, d_variance, *guides, *params, rows, cols, d_out, d_variance_out,
-                                                      static_cast<float *>(d_temp), static_cast<hipStream_t>(hip_stream)));
+    return device_query("rt_svgf_atrous",
+                        rt::SvgfAtrousArgs{d_color, color_stride, d_variance, guides, params, rows, cols, d_out, d_variance_out, static_cast<float *>(d_temp)},
+                        rt::launch_svgf, hip_stream);
 }
 
 int rt_svgf_variance_host(const rt_temporal_pixel *h_history, const rt_denoise_guides *guides, const rt_svgf_variance_params *params, uint32_t rows,
                           uint32_t cols, float *h_variance_out) {
-    /* the device copy is hipMalloc's and aligned whatever the host array is */
-    const char *bad = rt::svgf_variance_limits(h_history, guides, params, rows, cols, h_variance_out, false);
-    if (bad) return fail(RT_ERR_INVALID_ARGUMENT, std::string("rt_svgf_variance_host: ") + bad);
-    if (rows == 0u || cols == 0u) return RT_OK;
-    const size_t n = (size_t)rows * cols;
-    HostRoundTrip t("rt_svgf_variance_host");
-    const rt_temporal_pixel *d_history = t.in(h_history, n * sizeof(rt_temporal_pixel));
-    const rt_denoise_guides g = t.guides(*guides, n, false); /* the estimate reads no albedo */
-    float *d_out = t.out(h_variance_out, n * sizeof(float));
-    if (!t.ok()) return t.failed();
-    const hipError_t e = rt::launch_svgf_variance(rt::svgf_variance_call(d_history, g, *params, rows, cols, d_out), nullptr);
-    if (e != hipSuccess) return launched("rt_svgf_variance_host", e);
-    return t.finish();
+    return host_query("rt_svgf_variance_host", rt::SvgfVarianceArgs{h_history, guides, params, rows, cols, h_variance_out}, rt::launch_svgf_variance);
 }
 
 int rt_svgf_atrous_host(const float *h_color, uint32_t color_stride, const float *h_variance, const rt_denoise_guides *guides,
                         const rt_svgf_atrous_params *params, uint32_t rows, uint32_t cols, float *h_out, float *h_variance_out) {
-    const char *bad = rt::svgf_atrous_limits(h_color, color_stride, h_variance, guides, params, rows, cols, h_out, h_variance_out, nullptr, false);
-    if (bad) return fail(RT_ERR_INVALID_ARGUMENT, std::string("rt_svgf_atrous_host: ") + bad);
-    if (rows == 0u || cols == 0u) return RT_OK;
-    const size_t n = (size_t)rows * cols;
-    HostRoundTrip t("rt_svgf_atrous_host");
-    const float *d_color = t.plane(h_color, n, color_stride, 3u);
-    const float *d_variance = t.in(h_variance, n * sizeof(float));
-    const rt_denoise_guides g = t.guides(*guides, n);
-    float *d_out = t.out(h_out, n * 3u * sizeof(float));
-    float *d_variance_out = t.out(h_variance_out, n * sizeof(float));
-    const size_t temp_bytes = rt_svgf_temp_bytes(rows, cols, params->n_levels);
-    float *d_temp = temp_bytes ? static_cast<float *>(t.scratch(temp_bytes)) : nullptr;
-    if (!t.ok()) return t.failed();
-    const hipError_t e = rt::launch_svgf(d_color, color_stride, d_variance, g, *params, rows, cols, d_out, d_variance_out, d_temp, nullptr);
-    if (e != hipSuccess) return launched("rt_svgf_atrous_host", e);
-    return t.finish();
+    return host_query("rt_svgf_atrous_host", rt::SvgfAtrousArgs{h_color, color_stride, h_variance, guides, params, rows, cols, h_out, h_variance_out, nullptr},
+                      rt::launch_svgf);
 }
 
 } /* extern "C" */
+

@@ -17,6 +17,7 @@
 #include <stdint.h>
 
 #include "../../include/rt_amd.h"
+#include "rt_query_args.h"
 #include "rt_vec.h"
 
 #if defined(__HIPCC__)
@@ -130,16 +131,6 @@ struct TemporalCall {
     RT_TP_HD uint64_t count() const { return (uint64_t)rows * cols; }
     RT_TP_HD void operator()(uint64_t i) const; /* temporal_pixel */
 };
-
-inline TemporalCall temporal_call(const float *color, const float *motion, const rt_temporal_guides &cur, const rt_temporal_guides &prev,
-                                  const rt_temporal_params &p, uint32_t rows, uint32_t cols, const rt_temporal_pixel *in, rt_temporal_pixel *out,
-                                  float *variance) {
-    TemporalCall t;
-    t.color = color, t.motion = motion, t.cur = cur, t.prev = prev, t.in = in, t.out = out, t.variance = variance;
-    t.rows = rows, t.cols = cols, t.rows_f = (float)rows, t.cols_f = (float)cols;
-    t.normal_min = p.normal_min, t.position_max2 = p.position_max * p.position_max, t.alpha_min = p.alpha_min, t.max_length = p.max_length;
-    return t;
-}
 
 /* the current pixel as the taps see it; a plane that is null leaves its fields +0 (they are not looked at) */
 struct TemporalPix {
@@ -313,26 +304,50 @@ RT_TP_HD void temporal_pixel(const TemporalCall &t, uint64_t i) {
 }
 RT_TP_HD void TemporalCall::operator()(uint64_t i) const { temporal_pixel(*this, i); }
 
-/* ---- THE argument checks, in the order include/rt_amd.h states; null: all in range, *status says how a refusal is reported ---- */
+/* ---- the arguments of the entry points (rt_query_args.h): the checks in the order include/rt_amd.h states ---- */
 
-inline const char *temporal_motion_limits(const float *position, uint32_t position_stride, const uint32_t *valid, uint32_t valid_stride,
-                                          const rt_camera *camera, const rt_frame *frame, const float *motion, int *status) {
-    *status = RT_ERR_INVALID_ARGUMENT;
-    if (!camera) return "null prev_camera";
-    if (!frame) return "null prev_frame";
-    if (frame->x0 != 0u || frame->y0 != 0u || frame->x1 != frame->width || frame->y1 != frame->height || frame->y_step != 1u)
-        return "prev_frame must be the full frame (x0 = y0 = 0, x1 = width, y1 = height, y_step = 1)";
-    if ((uint64_t)frame->width * frame->height >= (1ull << 32)) {
-        *status = RT_ERR_UNSUPPORTED;
-        return "rows * cols: 2^32 pixels or more";
+/* rt_temporal_motion, rt_temporal_motion_host and rt_temporal_motion_cpu */
+struct TemporalMotionArgs {
+    const float *position; uint32_t position_stride;
+    const uint32_t *valid; uint32_t valid_stride;
+    const rt_camera *camera; const rt_frame *frame; float *motion;
+
+    const char *limits(QueryForm, int *status) const {
+        *status = RT_ERR_INVALID_ARGUMENT;
+        if (!camera) return "null prev_camera";
+        if (!frame) return "null prev_frame";
+        if (frame->x0 != 0u || frame->y0 != 0u || frame->x1 != frame->width || frame->y1 != frame->height || frame->y_step != 1u)
+            return "prev_frame must be the full frame (x0 = y0 = 0, x1 = width, y1 = height, y_step = 1)";
+        if ((uint64_t)frame->width * frame->height >= (1ull << 32)) {
+            *status = RT_ERR_UNSUPPORTED;
+            return "rows * cols: 2^32 pixels or more";
+        }
+        if (empty()) return nullptr;
+        if (!position) return "null position pointer";
+        if (!motion) return "null motion pointer";
+        if (position_stride < 3u) return "position_stride must be at least 3 words";
+        if (valid && valid_stride < 1u) return "valid_stride must be at least 1 word";
+        return nullptr;
     }
-    if (frame->width == 0u || frame->height == 0u) return nullptr;
-    if (!position) return "null position pointer";
-    if (!motion) return "null motion pointer";
-    if (position_stride < 3u) return "position_stride must be at least 3 words";
-    if (valid && valid_stride < 1u) return "valid_stride must be at least 1 word";
-    return nullptr;
-}
+
+    bool empty() const { return frame->width == 0u || frame->height == 0u; }
+    size_t pixels() const { return (size_t)frame->width * frame->height; }
+
+    template <class Stage>
+    void arrays(Stage &s) {
+        position = s.plane(position, pixels(), position_stride, 3u);
+        valid = s.plane(valid, pixels(), valid_stride, 1u);
+        motion = s.out(motion, pixels() * 2u * sizeof(float));
+    }
+
+    TemporalMotion call() const {
+        TemporalMotion m;
+        m.cam = temporal_camera(camera, frame);
+        m.position = position, m.valid = valid, m.position_stride = position_stride, m.valid_stride = valid_stride, m.motion = motion;
+        m.n = pixels();
+        return m;
+    }
+};
 
 inline const char *temporal_guide_strides(const rt_temporal_guides *g, bool current) {
     if (g->normal && g->normal_stride < 3u) return current ? "current: normal_stride must be at least 3 words" : "previous: normal_stride must be at least 3 words";
@@ -343,36 +358,66 @@ inline const char *temporal_guide_strides(const rt_temporal_guides *g, bool curr
     return nullptr;
 }
 
-/* aligned: the device forms read and write a record as two 128-bit words, so its arrays must be 16-byte aligned there */
-inline const char *temporal_limits(const float *color, const float *motion, const rt_temporal_guides *cur, const rt_temporal_guides *prev,
-                                   const rt_temporal_params *p, uint64_t rows, uint64_t cols, const rt_temporal_pixel *in, const rt_temporal_pixel *out,
-                                   bool aligned, int *status) {
-    *status = RT_ERR_INVALID_ARGUMENT;
-    if (rows >= (1ull << 32) || cols >= (1ull << 32) || rows * cols >= (1ull << 32)) {
-        *status = RT_ERR_UNSUPPORTED;
-        return "rows * cols: 2^32 pixels or more";
+/* rt_temporal_accumulate, rt_temporal_accumulate_host and rt_temporal_accumulate_cpu; rt_rectify.h's bounded accumulate begins with them */
+struct TemporalAccumulateArgs {
+    const float *color, *motion;
+    const rt_temporal_guides *current, *previous;
+    const rt_temporal_params *params;
+    uint32_t rows, cols;
+    const rt_temporal_pixel *history_in;
+    rt_temporal_pixel *history_out;
+    float *variance;
+
+    const char *limits(QueryForm form, int *status) const {
+        *status = RT_ERR_INVALID_ARGUMENT;
+        if ((uint64_t)rows * cols >= (1ull << 32)) {
+            *status = RT_ERR_UNSUPPORTED;
+            return "rows * cols: 2^32 pixels or more";
+        }
+        if (empty()) return nullptr;
+        if (!current) return "null current guides";
+        if (!previous) return "null previous guides";
+        if (!params) return "null params";
+        if (!color) return "null color pointer";
+        if (!motion) return "null motion pointer";
+        if (!history_in) return "null history_in pointer";
+        if (!history_out) return "null history_out pointer";
+        if (const char *bad = temporal_guide_strides(current, true)) return bad;
+        if (const char *bad = temporal_guide_strides(previous, false)) return bad;
+        if (history_out == history_in) return "history_out must not be history_in";
+        if (query_misaligned(form, history_in, history_out)) return "history_in and history_out must be 16-byte aligned";
+        if (params->max_length < 1u) return "max_length must be at least 1";
+        if (!(params->alpha_min >= 0.0f && params->alpha_min <= 1.0f)) return "alpha_min must lie in [0, 1]";
+        if (!(params->position_max >= 0.0f)) return "position_max must be >= 0 (+inf: every distance passes)";
+        if (params->flags != 0u) return "flags: unknown bits (none is defined)";
+        if ((current->normal == nullptr) != (previous->normal == nullptr)) return "normal: a plane in one guide set and null in the other";
+        if ((current->position == nullptr) != (previous->position == nullptr)) return "position: a plane in one guide set and null in the other";
+        if ((current->object == nullptr) != (previous->object == nullptr)) return "object: a plane in one guide set and null in the other";
+        return nullptr;
     }
-    if (rows == 0u || cols == 0u) return nullptr;
-    if (!cur) return "null current guides";
-    if (!prev) return "null previous guides";
-    if (!p) return "null params";
-    if (!color) return "null color pointer";
-    if (!motion) return "null motion pointer";
-    if (!in) return "null history_in pointer";
-    if (!out) return "null history_out pointer";
-    if (const char *bad = temporal_guide_strides(cur, true)) return bad;
-    if (const char *bad = temporal_guide_strides(prev, false)) return bad;
-    if (out == in) return "history_out must not be history_in";
-    if (aligned && (((uintptr_t)in | (uintptr_t)out) & 15u)) return "history_in and history_out must be 16-byte aligned";
-    if (p->max_length < 1u) return "max_length must be at least 1";
-    if (!(p->alpha_min >= 0.0f && p->alpha_min <= 1.0f)) return "alpha_min must lie in [0, 1]";
-    if (!(p->position_max >= 0.0f)) return "position_max must be >= 0 (+inf: every distance passes)";
-    if (p->flags != 0u) return "flags: unknown bits (none is defined)";
-    if ((cur->normal == nullptr) != (prev->normal == nullptr)) return "normal: a plane in one guide set and null in the other";
-    if ((cur->position == nullptr) != (prev->position == nullptr)) return "position: a plane in one guide set and null in the other";
-    if ((cur->object == nullptr) != (prev->object == nullptr)) return "object: a plane in one guide set and null in the other";
-    return nullptr;
-}
+
+    bool empty() const { return rows == 0u || cols == 0u; }
+
+    template <class Stage>
+    void arrays(Stage &s) {
+        const size_t n = (size_t)rows * cols;
+        color = s.in(color, n * 3u * sizeof(float));
+        motion = s.in(motion, n * 2u * sizeof(float));
+        current = s.guides(current, n), previous = s.guides(previous, n);
+        history_in = s.in(history_in, n * sizeof(rt_temporal_pixel));
+        history_out = s.out(history_out, n * sizeof(rt_temporal_pixel));
+        variance = s.out(variance, n * sizeof(float));
+    }
+
+    TemporalCall call() const {
+        TemporalCall t;
+        t.color = color, t.motion = motion, t.cur = *current, t.prev = *previous, t.in = history_in, t.out = history_out, t.variance = variance;
+        t.rows = rows, t.cols = cols, t.rows_f = (float)rows, t.cols_f = (float)cols;
+        t.normal_min = params->normal_min, t.position_max2 = params->position_max * params->position_max, t.alpha_min = params->alpha_min;
+        t.max_length = params->max_length;
+        return t;
+    }
+};
 
 } /* namespace rt */
 

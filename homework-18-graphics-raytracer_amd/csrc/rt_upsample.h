@@ -26,7 +26,7 @@ namespace rt {
 
 /* one call, as the loops see it.  lo: the low-resolution guides and the size derived from the output's; hi: the full-resolution guides
  * and the output's size.  A guide term is on where BOTH sets carry its plane, the object test where both object planes are given:
- * upsample_call clears the other side's pointer otherwise, so the readers of rt_atrous.h see the planes the definition uses. */
+ * UpsampleArgs::call clears the other side's pointer otherwise, so the readers of rt_atrous.h see the planes the definition uses. */
 struct UpsampleCall {
     const float *color;
     GuidePlanes lo, hi;
@@ -42,27 +42,6 @@ struct UpsampleCall {
 };
 
 inline uint32_t upsample_low_size(uint32_t full, uint32_t scale) { return (uint32_t)(((uint64_t)full + scale - 1u) / scale); }
-
-inline UpsampleCall upsample_call(const float *color, uint32_t color_stride, const rt_denoise_guides &low, const uint32_t *object_lo, uint32_t object_lo_stride,
-                                  const rt_denoise_guides &full, const uint32_t *object_hi, uint32_t object_hi_stride, const rt_upsample_params &p,
-                                  uint32_t rows, uint32_t cols, float *out) {
-    UpsampleCall u;
-    u.color = color, u.color_stride = color_stride;
-    guide_planes(u.lo, low, upsample_low_size(rows, p.scale), upsample_low_size(cols, p.scale));
-    guide_planes(u.hi, full, rows, cols);
-    if (!u.lo.normal || !u.hi.normal) u.lo.normal = u.hi.normal = nullptr;
-    if (!u.lo.position || !u.hi.position) u.lo.position = u.hi.position = nullptr;
-    const bool objects = object_lo && object_hi;
-    u.object_lo = objects ? object_lo : nullptr, u.object_hi = objects ? object_hi : nullptr;
-    u.object_lo_stride = object_lo_stride, u.object_hi_stride = object_hi_stride;
-    u.scale = p.scale, u.radius = (int)p.radius;
-    u.sn2 = p.sigma_normal * p.sigma_normal;
-    u.sp2 = p.sigma_position * p.sigma_position;
-    u.demod_in = (p.flags & RT_DENOISE_DEMODULATE_IN) ? 1u : 0u;
-    u.demod_out = (p.flags & RT_DENOISE_DEMODULATE_OUT) ? 1u : 0u;
-    u.out = out;
-    return u;
-}
 
 /* what the walk knows of a low-resolution pixel, and an entry of the staged window: the colour it sees (demodulated where the call
  * says so), shading normal and position, the object (+0 without object planes) */
@@ -172,33 +151,73 @@ RT_AT_HD void UpsampleCall::operator()(uint64_t i) const {
     }
 }
 
-/* THE argument check of rt_upsample_guided, rt_upsample_guided_host and rt_upsample_guided_cpu, in the order include/rt_amd.h states;
- * null: all in range */
-inline const char *upsample_limits(const float *color, uint32_t color_stride, const rt_denoise_guides *low, const uint32_t *object_lo, uint32_t object_lo_stride,
-                                   const rt_denoise_guides *full, const uint32_t *object_hi, uint32_t object_hi_stride, const rt_upsample_params *p,
-                                   uint64_t rows, uint64_t cols, const float *out) {
-    if (!p) return "null params";
-    if (!low) return "null low guides";
-    if (!full) return "null full guides";
-    if (const char *bad = limits_image(rows, cols)) return bad;
-    if (p->scale < RT_UPSAMPLE_MIN_SCALE || p->scale > RT_UPSAMPLE_MAX_SCALE) return "scale must be 2, 3 or 4";
-    if (p->radius < 1u || p->radius > (uint32_t)RT_UPSAMPLE_MAX_RADIUS) return "radius must be 1 or 2";
-    if (const char *bad = RT_LIMITS_SIGMA(p, sigma_normal)) return bad;
-    if (const char *bad = RT_LIMITS_SIGMA(p, sigma_position)) return bad;
-    if (p->flags & ~RT_DENOISE_DEMODULATE) return "flags: unknown bits (RT_DENOISE_DEMODULATE_IN, RT_DENOISE_DEMODULATE_OUT)";
-    if ((p->flags & RT_DENOISE_DEMODULATE_IN) && !low->albedo) return "flags: RT_DENOISE_DEMODULATE_IN needs the low albedo plane";
-    if ((p->flags & RT_DENOISE_DEMODULATE_OUT) && !full->albedo) return "flags: RT_DENOISE_DEMODULATE_OUT needs the full albedo plane";
-    if (const char *bad = limits_guide_strides(low)) return bad;
-    if (const char *bad = limits_guide_strides(full)) return bad;
-    if (color_stride < 3u) return "color_stride must be at least 3 words";
-    if (object_lo && object_lo_stride < 1u) return "object_lo_stride must be at least 1 word";
-    if (object_hi && object_hi_stride < 1u) return "object_full_stride must be at least 1 word";
-    if (rows == 0u || cols == 0u) return nullptr;
-    if (!color) return "null color pointer";
-    if (!out) return "null out pointer";
-    if (out == color) return "out must not be color";
-    return nullptr;
-}
+/* The arguments of rt_upsample_guided, rt_upsample_guided_host and rt_upsample_guided_cpu (rt_query_args.h); the checks in the order
+ * include/rt_amd.h states */
+struct UpsampleArgs {
+    const float *color; uint32_t color_stride;
+    const rt_denoise_guides *low; const uint32_t *object_lo; uint32_t object_lo_stride;
+    const rt_denoise_guides *full; const uint32_t *object_hi; uint32_t object_hi_stride;
+    const rt_upsample_params *params; uint32_t rows, cols; float *out;
+
+    const char *limits(QueryForm, int *status) const {
+        *status = RT_ERR_INVALID_ARGUMENT;
+        if (!params) return "null params";
+        if (!low) return "null low guides";
+        if (!full) return "null full guides";
+        if (const char *bad = limits_image(rows, cols)) return bad;
+        if (params->scale < RT_UPSAMPLE_MIN_SCALE || params->scale > RT_UPSAMPLE_MAX_SCALE) return "scale must be 2, 3 or 4";
+        if (params->radius < 1u || params->radius > (uint32_t)RT_UPSAMPLE_MAX_RADIUS) return "radius must be 1 or 2";
+        if (const char *bad = RT_LIMITS_SIGMA(params, sigma_normal)) return bad;
+        if (const char *bad = RT_LIMITS_SIGMA(params, sigma_position)) return bad;
+        if (params->flags & ~RT_DENOISE_DEMODULATE) return "flags: unknown bits (RT_DENOISE_DEMODULATE_IN, RT_DENOISE_DEMODULATE_OUT)";
+        if ((params->flags & RT_DENOISE_DEMODULATE_IN) && !low->albedo) return "flags: RT_DENOISE_DEMODULATE_IN needs the low albedo plane";
+        if ((params->flags & RT_DENOISE_DEMODULATE_OUT) && !full->albedo) return "flags: RT_DENOISE_DEMODULATE_OUT needs the full albedo plane";
+        if (const char *bad = limits_guide_strides(low)) return bad;
+        if (const char *bad = limits_guide_strides(full)) return bad;
+        if (color_stride < 3u) return "color_stride must be at least 3 words";
+        if (object_lo && object_lo_stride < 1u) return "object_lo_stride must be at least 1 word";
+        if (object_hi && object_hi_stride < 1u) return "object_full_stride must be at least 1 word";
+        if (empty()) return nullptr;
+        if (!color) return "null color pointer";
+        if (!out) return "null out pointer";
+        if (out == color) return "out must not be color";
+        return nullptr;
+    }
+
+    bool empty() const { return rows == 0u || cols == 0u; }
+    uint32_t low_rows() const { return upsample_low_size(rows, params->scale); }
+    uint32_t low_cols() const { return upsample_low_size(cols, params->scale); }
+
+    template <class Stage>
+    void arrays(Stage &s) {
+        const size_t n = (size_t)rows * cols, n_lo = (size_t)low_rows() * low_cols();
+        color = s.plane(color, n_lo, color_stride, 3u);
+        low = s.guides(low, n_lo, (params->flags & RT_DENOISE_DEMODULATE_IN) != 0u);
+        full = s.guides(full, n, (params->flags & RT_DENOISE_DEMODULATE_OUT) != 0u);
+        object_lo = s.plane(object_lo, n_lo, object_lo_stride, 1u);
+        object_hi = s.plane(object_hi, n, object_hi_stride, 1u);
+        out = s.out(out, n * 3u * sizeof(float));
+    }
+
+    UpsampleCall call() const {
+        UpsampleCall u;
+        u.color = color, u.color_stride = color_stride;
+        guide_planes(u.lo, *low, low_rows(), low_cols());
+        guide_planes(u.hi, *full, rows, cols);
+        if (!u.lo.normal || !u.hi.normal) u.lo.normal = u.hi.normal = nullptr;
+        if (!u.lo.position || !u.hi.position) u.lo.position = u.hi.position = nullptr;
+        const bool objects = object_lo && object_hi;
+        u.object_lo = objects ? object_lo : nullptr, u.object_hi = objects ? object_hi : nullptr;
+        u.object_lo_stride = object_lo_stride, u.object_hi_stride = object_hi_stride;
+        u.scale = params->scale, u.radius = (int)params->radius;
+        u.sn2 = params->sigma_normal * params->sigma_normal;
+        u.sp2 = params->sigma_position * params->sigma_position;
+        u.demod_in = (params->flags & RT_DENOISE_DEMODULATE_IN) ? 1u : 0u;
+        u.demod_out = (params->flags & RT_DENOISE_DEMODULATE_OUT) ? 1u : 0u;
+        u.out = out;
+        return u;
+    }
+};
 
 } /* namespace rt */
 

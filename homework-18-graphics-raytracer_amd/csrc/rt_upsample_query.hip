@@ -71,7 +71,8 @@ __global__ __launch_bounds__(RT_IMAGE_THREADS) void upsample_tiled_kernel(const 
 /* which form rt_upsample_guided launches unless RT_AMD_UPSAMPLE_FORM says otherwise: 0 plain, 1 tiled (same bits; DESIGN.md 3.28 has the A/B) */
 #define RT_UPSAMPLE_FORM_DEFAULT 1
 
-static hipError_t launch_upsample(const UpsampleCall &u, hipStream_t stream) {
+static hipError_t launch_upsample(const UpsampleArgs &a, hipStream_t stream) {
+    const UpsampleCall u = a.call();
     if (option(OPT_UPSAMPLE_FORM, RT_UPSAMPLE_FORM_DEFAULT) != 1) return launch_each(u, OPT_DIAG_UPSAMPLE_MAX_GROUPS, stream);
     if (u.radius == 1) return launch_tiles(upsample_tiled_kernel<1>, u.hi.rows, u.hi.cols, OPT_DIAG_UPSAMPLE_MAX_GROUPS, stream, u);
     return launch_tiles(upsample_tiled_kernel<2>, u.hi.rows, u.hi.cols, OPT_DIAG_UPSAMPLE_MAX_GROUPS, stream, u);
@@ -84,35 +85,18 @@ extern "C" {
 int rt_upsample_guided(const float *d_color_lo, uint32_t color_stride, const rt_denoise_guides *low, const uint32_t *d_object_lo, uint32_t object_lo_stride,
                        const rt_denoise_guides *full, const uint32_t *d_object_full, uint32_t object_full_stride, const rt_upsample_params *params,
                        uint32_t rows, uint32_t cols, float *d_out, void *hip_stream) {
-    const char *bad = rt::upsample_limits(d_color_lo, color_stride, low, d_object_lo, object_lo_stride, full, d_object_full, object_full_stride, params, rows, cols, d_out);
-    if (bad) return fail(RT_ERR_INVALID_ARGUMENT, std::string("rt_upsample_guided: ") + bad);
-    if (rows == 0u || cols == 0u) return RT_OK;
-    return launched("rt_upsample_guided",
-                    rt::launch_upsample(rt::upsample_call(d_color_lo, color_stride, *low, d_object_lo, object_lo_stride, *full, d_object_full, object_full_stride,
-                                                          *params, rows, cols, d_out),
-                                        static_cast<hipStream_t>(hip_stream)));
+    return device_query("rt_upsample_guided",
+                        rt::UpsampleArgs{d_color_lo, color_stride, low, d_object_lo, object_lo_stride, full, d_object_full, object_full_stride, params, rows, cols, d_out},
+                        rt::launch_upsample, hip_stream);
 }
 
 int rt_upsample_guided_host(const float *h_color_lo, uint32_t color_stride, const rt_denoise_guides *low, const uint32_t *h_object_lo, uint32_t object_lo_stride,
                             const rt_denoise_guides *full, const uint32_t *h_object_full, uint32_t object_full_stride, const rt_upsample_params *params,
                             uint32_t rows, uint32_t cols, float *h_out) {
-    const char *bad = rt::upsample_limits(h_color_lo, color_stride, low, h_object_lo, object_lo_stride, full, h_object_full, object_full_stride, params, rows, cols, h_out);
-    if (bad) return fail(RT_ERR_INVALID_ARGUMENT, std::string("rt_upsample_guided_host: ") + bad);
-    if (rows == 0u || cols == 0u) return RT_OK;
-    const size_t n = (size_t)rows * cols;
-    const size_t n_lo = (size_t)rt::upsample_low_size(rows, params->scale) * rt::upsample_low_size(cols, params->scale);
-    HostRoundTrip t("rt_upsample_guided_host");
-    const float *d_color = t.plane(h_color_lo, n_lo, color_stride, 3u);
-    const rt_denoise_guides lo = t.guides(*low, n_lo, (params->flags & RT_DENOISE_DEMODULATE_IN) != 0u);
-    const rt_denoise_guides hi = t.guides(*full, n, (params->flags & RT_DENOISE_DEMODULATE_OUT) != 0u);
-    const uint32_t *d_object_lo = t.plane(h_object_lo, n_lo, object_lo_stride, 1u);
-    const uint32_t *d_object_hi = t.plane(h_object_full, n, object_full_stride, 1u);
-    float *d_out = t.out(h_out, n * 3u * sizeof(float));
-    if (!t.ok()) return t.failed();
-    const hipError_t e = rt::launch_upsample(
-        rt::upsample_call(d_color, color_stride, lo, d_object_lo, object_lo_stride, hi, d_object_hi, object_full_stride, *params, rows, cols, d_out), nullptr);
-    if (e != hipSuccess) return launched("rt_upsample_guided_host", e);
-    return t.finish();
+    return host_query("rt_upsample_guided_host",
+                      rt::UpsampleArgs{h_color_lo, color_stride, low, h_object_lo, object_lo_stride, full, h_object_full, object_full_stride, params, rows, cols, h_out},
+                      rt::launch_upsample);
 }
 
 } /* extern "C" */
+

@@ -57,6 +57,20 @@ def dev(records):
     return torch.tensor(np.ascontiguousarray(records).view(np.int32), device="cuda")
 
 
+def spread(plane, stride):
+    """the n pixels of a compact plane `stride` words apart, as a strided record view lies, in a host array of EXACTLY
+    (n - 1) * stride + width words (the words between the pixels hold a filler): a _host form that stages a shorter span loses the
+    last pixel"""
+    plane = np.asarray(plane)
+    pixels = plane.reshape(plane.shape[0], -1)
+    n, width = pixels.shape
+    assert pixels.dtype.itemsize == 4 and stride >= width
+    flat = np.full((n - 1) * stride + width, 0x7F, dtype=np.uint8).repeat(4).view(pixels.dtype)
+    for k in range(width):
+        flat[k::stride] = pixels[:, k]
+    return flat
+
+
 # ---- comparisons of bit patterns: any NaN equals any NaN, -0.0 differs from +0.0 ----
 
 

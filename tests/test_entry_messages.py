@@ -125,14 +125,115 @@ SIGNATURES = {
     "rt_math_eval64_device": [("op", 0), ("a", P), ("b", P), ("out", P), ("n", 2)],
 }
 
-RECORDS = "2^32 records or more (checked first; query them in several calls)"
-LEVEL = "2^32 records or more (checked first; split the level)"
-FRAME_NEEDS = "bad frame (need 0 <= x0 < x1 <= width, 0 <= y0 < y1 <= height, y_step >= 1)"
-
-
 def _null(*names):
     return dict.fromkeys(names)
 
+
+# ---- the image-side queries: a device form (the arguments, then the stream), a _host form (the arguments) and a _cpu form of
+# librt_host.so (the arguments), all three on one argument check.  The two A-Trous filters take a temp plane in the device and the
+# _cpu form; the adaptive queries have no _host form.
+_BASE = (C.addressof(BUF) + 15) & ~15
+A, B, D = C.c_void_p(_BASE), C.c_void_p(_BASE + 1024), C.c_void_p(_BASE + 2048)  # three distinct arrays, 16-byte aligned
+ODD = C.c_void_p(_BASE + 4)  # not 16-byte aligned
+GUIDES = _capi.DenoiseGuides()  # every plane left out
+TGUIDES = _capi.TemporalGuides()
+DENOISE = _capi.DenoiseParams(1.0, 1.0, 1.0, 0, 1, 0)
+DENOISE_2 = _capi.DenoiseParams(1.0, 1.0, 1.0, 0, 2, 0)  # two levels: needs a temp plane
+TEMPORAL = _capi.TemporalParams(0.9, 1.0, 0.1, 8, 0)
+BOUNDS = _capi.BoundsParams(1.0, 1, 0)
+SVGF_VARIANCE = _capi.SvgfVarianceParams(1.0, 1.0, 4, 0)
+SVGF_ATROUS = _capi.SvgfAtrousParams(1.0, 1.0, 1.0, 0, 1, 0)
+SVGF_ATROUS_2 = _capi.SvgfAtrousParams(1.0, 1.0, 1.0, 0, 2, 0)
+UPSAMPLE = _capi.UpsampleParams(1.0, 1.0, 2, 1, 0)
+BUDGET = _capi.SampleBudgetParams(1.0, 1e-3, 1, 4, 0)
+EMPTY_FRAME = _capi.Frame.full(0, 6, 3)
+SIDE = 1 << 16  # SIDE x SIDE is 2^32 pixels
+
+_ACCUMULATE = [("color", A), ("motion", A), ("current", TGUIDES), ("previous", TGUIDES), ("params", TEMPORAL), ("rows", 4), ("cols", 4),
+               ("history_in", A), ("history_out", B), ("variance", None)]
+IMAGE_QUERIES = {
+    "rt_denoise_atrous": [("color", A), ("guides", GUIDES), ("params", DENOISE), ("rows", 4), ("cols", 4), ("out", B)],
+    "rt_temporal_motion": [("position", A), ("position_stride", 3), ("valid", None), ("valid_stride", 1), ("camera", CAMERA), ("frame", FRAME),
+                           ("motion", B)],
+    "rt_temporal_accumulate": _ACCUMULATE,
+    "rt_svgf_variance": [("history", A), ("guides", GUIDES), ("params", SVGF_VARIANCE), ("rows", 4), ("cols", 4), ("variance_out", B)],
+    "rt_svgf_atrous": [("color", A), ("color_stride", 3), ("variance", B), ("guides", GUIDES), ("params", SVGF_ATROUS), ("rows", 4), ("cols", 4),
+                       ("out", D), ("variance_out", None)],
+    "rt_temporal_bounds": [("color", A), ("color_stride", 3), ("object", None), ("object_stride", 1), ("valid", None), ("valid_stride", 1),
+                           ("params", BOUNDS), ("rows", 4), ("cols", 4), ("box", B)],
+    "rt_temporal_accumulate_bounded": _ACCUMULATE + [("box", D), ("clamped_length", 0), ("clamped", None)],
+    "rt_temporal_feedback": [("color", A), ("color_stride", 3), ("valid", None), ("valid_stride", 1), ("rows", 4), ("cols", 4), ("history", B)],
+    "rt_upsample_guided": [("color", A), ("color_stride", 3), ("low", GUIDES), ("object_lo", None), ("object_lo_stride", 1), ("full", GUIDES),
+                           ("object_full", None), ("object_full_stride", 1), ("params", UPSAMPLE), ("rows", 4), ("cols", 4), ("out", B)],
+    "rt_sample_budget": [("mean", A), ("mean_stride", 1), ("variance", B), ("variance_stride", 1), ("count", None), ("count_stride", 1),
+                         ("valid", None), ("valid_stride", 1), ("params", BUDGET), ("n", 4), ("budget", D)],
+    "rt_film_offsets_listed": [("frame", FRAME), ("pattern", 1), ("seed", 1), ("pixel", A), ("sample", B), ("total", D),
+                               ("capacity", 4), ("offsets", A)],
+}
+WITH_TEMP = ("rt_denoise_atrous", "rt_svgf_atrous")
+WITHOUT_HOST = ("rt_sample_budget", "rt_film_offsets_listed")
+DEVICE, HOST, CPU = "", "_host", "_cpu"
+for _name, _args in IMAGE_QUERIES.items():
+    _temp = [("temp", None)] if _name in WITH_TEMP else []
+    SIGNATURES[_name + DEVICE] = _args + _temp + [("stream", None)]
+    SIGNATURES[_name + CPU] = _args + _temp
+    if _name not in WITHOUT_HOST:
+        SIGNATURES[_name + HOST] = _args
+
+PIXELS = "rows * cols: 2^32 pixels or more"
+# (query, its forms the row holds for — None: all it has, the arguments that differ, status, the text after "<entry point>: ")
+IMAGE_CASES = [
+    ("rt_denoise_atrous", None, _null("guides"), INVALID, "null guides"),
+    ("rt_denoise_atrous", None, {"rows": 0, "color": None, "out": None}, OK, None),
+    ("rt_denoise_atrous", None, {"rows": SIDE, "cols": SIDE}, INVALID, PIXELS),
+    ("rt_denoise_atrous", (DEVICE, CPU), {"params": DENOISE_2}, INVALID, "null temp pointer with n_levels >= 2"),
+    ("rt_denoise_atrous", (DEVICE, CPU), {"params": DENOISE_2, "temp": B}, INVALID, "temp must not be out"),
+    ("rt_temporal_motion", None, _null("camera"), INVALID, "null prev_camera"),
+    ("rt_temporal_motion", None, {"frame": EMPTY_FRAME, "position": None, "motion": None}, OK, None),
+    ("rt_temporal_motion", None, {"frame": HUGE_FRAME}, UNSUPPORTED, PIXELS),
+    ("rt_temporal_motion", None, _null("motion"), INVALID, "null motion pointer"),
+    ("rt_temporal_accumulate", None, {"rows": SIDE, "cols": SIDE}, UNSUPPORTED, PIXELS),
+    ("rt_temporal_accumulate", None, {"cols": 0, "current": None, "previous": None, "params": None, "color": None, "history_out": None}, OK, None),
+    ("rt_temporal_accumulate", None, _null("current"), INVALID, "null current guides"),
+    ("rt_temporal_accumulate", (DEVICE,), {"history_in": ODD}, INVALID, "history_in and history_out must be 16-byte aligned"),
+    ("rt_svgf_variance", None, _null("guides"), INVALID, "null guides"),
+    ("rt_svgf_variance", None, {"cols": 0, "history": None, "variance_out": None}, OK, None),
+    ("rt_svgf_variance", None, _null("history"), INVALID, "null history pointer"),
+    ("rt_svgf_variance", (DEVICE,), {"history": ODD}, INVALID, "history must be 16-byte aligned"),
+    ("rt_svgf_atrous", None, _null("guides"), INVALID, "null guides"),
+    ("rt_svgf_atrous", None, {"rows": 0, "color": None, "variance": None, "out": None}, OK, None),
+    ("rt_svgf_atrous", None, {"color_stride": 2}, INVALID, "color_stride must be at least 3 words"),
+    ("rt_svgf_atrous", (DEVICE, CPU), {"params": SVGF_ATROUS_2}, INVALID, "null temp pointer with n_levels >= 2"),
+    ("rt_svgf_atrous", (DEVICE, CPU), {"params": SVGF_ATROUS_2, "temp": D}, INVALID, "temp must not be color, variance, out or variance_out"),
+    ("rt_temporal_bounds", None, {"rows": SIDE, "cols": SIDE}, UNSUPPORTED, PIXELS),
+    ("rt_temporal_bounds", None, {"rows": 0, "params": None, "color": None, "box": None}, OK, None),
+    ("rt_temporal_bounds", None, _null("params"), INVALID, "null params"),
+    ("rt_temporal_bounds", (DEVICE,), {"box": ODD}, INVALID, "box must be 16-byte aligned"),
+    ("rt_temporal_accumulate_bounded", None, {"rows": SIDE, "cols": SIDE}, UNSUPPORTED, PIXELS),
+    ("rt_temporal_accumulate_bounded", None, {"rows": 0, "current": None, "params": None, "history_in": None, "box": None}, OK, None),
+    ("rt_temporal_accumulate_bounded", None, _null("box"), INVALID, "null box pointer"),
+    ("rt_temporal_accumulate_bounded", None, {"clamped_length": 9}, INVALID, "clamped_length must not exceed max_length (0: the length is not cut)"),
+    ("rt_temporal_accumulate_bounded", (DEVICE,), {"history_out": ODD}, INVALID, "history_in and history_out must be 16-byte aligned"),
+    ("rt_temporal_accumulate_bounded", (DEVICE,), {"box": ODD}, INVALID, "box must be 16-byte aligned"),
+    ("rt_temporal_feedback", None, {"rows": SIDE, "cols": SIDE}, UNSUPPORTED, PIXELS),
+    ("rt_temporal_feedback", None, {"cols": 0, "color": None, "history": None}, OK, None),
+    ("rt_temporal_feedback", None, _null("color"), INVALID, "null color pointer"),
+    ("rt_temporal_feedback", (DEVICE,), {"history": ODD}, INVALID, "history must be 16-byte aligned"),
+    ("rt_upsample_guided", None, _null("params"), INVALID, "null params"),
+    ("rt_upsample_guided", None, {"rows": 0, "color": None, "out": None}, OK, None),
+    ("rt_upsample_guided", None, {"object_full": A, "object_full_stride": 0}, INVALID, "object_full_stride must be at least 1 word"),
+    ("rt_upsample_guided", None, _null("out"), INVALID, "null out pointer"),
+    ("rt_sample_budget", None, {"n": BIG}, UNSUPPORTED, "2^32 pixels or more"),
+    ("rt_sample_budget", None, {"n": 0, "params": None, "mean": None, "budget": None}, OK, None),
+    ("rt_sample_budget", None, _null("params"), INVALID, "null params"),
+    ("rt_film_offsets_listed", None, _null("frame"), INVALID, "null frame"),
+    ("rt_film_offsets_listed", None, {"capacity": 0, "pixel": None, "sample": None, "total": None, "offsets": None}, OK, None),
+    ("rt_film_offsets_listed", None, {"capacity": BIG}, UNSUPPORTED, "2^32 pixels or records or more"),
+]
+
+RECORDS = "2^32 records or more (checked first; query them in several calls)"
+LEVEL = "2^32 records or more (checked first; split the level)"
+FRAME_NEEDS = "bad frame (need 0 <= x0 < x1 <= width, 0 <= y0 < y1 <= height, y_step >= 1)"
 
 # (entry point, the arguments that differ from SIGNATURES, status, rt_last_error() — None where the status is RT_OK)
 CASES = [
@@ -445,6 +546,10 @@ CASES = [
     ("rt_math_eval64_device", _null("out"), INVALID, "rt_math_eval64_device: null argument"),
     ("rt_math_eval64_device", {"n": 0}, OK, None),
 ]
+# the image-side queries: every row in every form it holds for, under that entry point's name
+CASES += [(name + form, changed, status, None if text is None else f"{name + form}: {text}")
+          for name, forms, changed, status, text in IMAGE_CASES
+          for form in (forms or (DEVICE, HOST, CPU)) if name + form in SIGNATURES]
 
 
 def case_id(case):
@@ -452,17 +557,22 @@ def case_id(case):
     return name + "(" + ",".join(k if v is None else f"{k}={'BIG' if v == BIG else v if isinstance(v, int) else '*'}" for k, v in changed.items()) + ")"
 
 
-def call(lib, rng, case):
-    """-> (status, rt_last_error() as text) of one case; the message is cleared of what an earlier case left by a call that fails
-    with a text of its own"""
+def call(rng, case):
+    """-> (status, the library's last error as text) of one case; the message is cleared of what an earlier case left by a call that
+    fails with a text of its own.  A _cpu form is librt_host.so's and leaves its text in rt_host_last_error()."""
     name, changed = case[0], case[1]
     names = [k for k, _ in SIGNATURES[name]]
     assert set(changed) <= set(names), (name, changed)
     args = dict(SIGNATURES[name])
     args.update(changed)
     values = [rng if args[k] is RNG else args[k] for k in names]
-    values = [C.byref(v) if isinstance(v, (_capi.Camera, _capi.Frame)) else v for v in values]
-    assert lib.rt_set_variant(-1) == INVALID  # leaves its own text behind: a case that sets none is seen
+    values = [C.byref(v) if isinstance(v, C.Structure) else v for v in values]
+    if name.endswith(CPU):
+        lib = _capi.host_lib()
+        assert lib.rt_world_push_object(None, None) == INVALID  # leaves its own text behind: a case that sets none is seen
+        return getattr(lib, name)(*values), lib.rt_host_last_error().decode()
+    lib = _capi.amd_lib()
+    assert lib.rt_set_variant(-1) == INVALID  # as above
     return getattr(lib, name)(*values), lib.rt_last_error().decode()
 
 
@@ -477,7 +587,7 @@ def empty_rng():
 
 @pytest.mark.parametrize("case", CASES, ids=case_id)
 def test_status_and_message(case, empty_rng):
-    status, text = call(_capi.amd_lib(), empty_rng, case)
+    status, text = call(empty_rng, case)
     assert status == case[2]
     if case[3] is not None:
         assert text == case[3]
@@ -485,4 +595,13 @@ def test_status_and_message(case, empty_rng):
 
 def test_every_entry_point_of_the_table_has_a_case_and_is_exported():
     assert {c[0] for c in CASES} == set(SIGNATURES)
-    assert set(SIGNATURES) <= set(_capi.AMD_SYMBOLS)
+    assert {name for name in SIGNATURES if not name.endswith(CPU)} <= set(_capi.AMD_SYMBOLS)
+    assert {name for name in SIGNATURES if name.endswith(CPU)} <= set(_capi.HOST_SYMBOLS)
+
+
+def test_every_form_of_an_image_side_query_has_its_first_refusal_and_its_empty_image():
+    for name in IMAGE_QUERIES:
+        for form in (DEVICE, HOST, CPU):
+            if name + form in SIGNATURES:
+                statuses = [c[2] for c in CASES if c[0] == name + form]
+                assert OK in statuses and any(s != OK for s in statuses), name + form

@@ -10,7 +10,7 @@ import pytest
 import homework_18_graphics_raytracer_amd as rt
 from homework_18_graphics_raytracer_amd import _capi, rectify, svgf, temporal
 from _denoise_support import record_views
-from _records import torch_device
+from _records import spread, torch_device
 import _rectify_support as S
 from _temporal_support import F32, HISTORY, PARAMS, case_data as temporal_case, embed as embed_guides, motion_field
 
@@ -253,6 +253,22 @@ def test_accumulate_bounded_and_feedback_on_the_host_cases(rows, cols, field, cl
     check(out, var, clamped, fed)
     if (rows, cols, field) == (17, 33, "special3"):  # the case is not idle: payload NaNs among the resets and among the fed records
         assert (raw[reset] == PAYLOAD_NAN).any() and (raw_half[taken] == PAYLOAD_NAN).any() and (~reset).any()
+
+
+def test_the_feedback_host_form_stages_strided_planes_to_their_last_word():
+    """17 x 19, partial tiles: the colour 13 and the valid words 11 words apart, as strided record views lie, each in a host array of
+    exactly (n - 1) * stride + width words — a staged span one pixel short would lose the last pixel, which the compact planes of the
+    test above cannot show"""
+    rows, cols = 17, 19
+    n = rows * cols
+    color, history, cur, _ = temporal_case(rows, cols)
+    color, history, valid = np.array(color), np.array(history), np.array(cur.valid)
+    valid[-1], history["length"][-1] = 1, 3  # the last record is fed
+    want = rectify.feedback_numpy(color, history.copy(), rows, cols, valid=valid)  # the _cpu form on the same values
+    c, v, fed = spread(color, 13), spread(valid, 11), history.copy()
+    _capi.check(_capi.amd_lib().rt_temporal_feedback_host(ptr(c), 13, ptr(v), 11, rows, cols, ptr(fed)))
+    assert np.array_equal(S.bits(fed).reshape(n, 8)[-1, :3], S.bits(color).reshape(n, 3)[-1])
+    assert np.array_equal(S.bits(fed).reshape(n, 8), S.bits(want).reshape(n, 8))
 
 
 # ---- end to end on the reference scene at 64 x 48: a light moves between two frames ----

@@ -11,7 +11,7 @@ import pytest
 import homework_18_graphics_raytracer_amd as rt
 from homework_18_graphics_raytracer_amd import _capi, upsample
 from homework_18_graphics_raytracer_amd.upsample import Guides
-from _records import torch_device
+from _records import spread, torch_device
 import _upsample_support as S
 
 pytestmark = pytest.mark.gpu
@@ -115,6 +115,26 @@ def test_the_host_form_equals_the_device(rows, cols, s, radius):
                                                         ptr(out)))
     got = upsample.guided(dev(color), rows, cols, low=Guides(*(dev(a) for a in lo)), full=Guides(*(dev(a) for a in hi)), scale=s, radius=radius, **KW)
     assert np.array_equal(S.bits(out), S.bits(host(got))) and np.array_equal(S.bits(out), S.bits(want(rows, cols, s, radius, True, 3)))
+
+
+def test_the_host_form_stages_every_strided_plane_to_its_last_word():
+    """17 x 19 at scale 2 — partial tiles, a 9 x 10 low image — with EVERY plane a strided record view, 11 or 13 words apart, in a host
+    array of exactly (n - 1) * stride + width words: a staged span one pixel short would lose the last pixel, which the compact planes
+    of the test above cannot show"""
+    rows, cols, s, radius = 17, 19, 2, 2
+    color, lo, hi = planes(rows, cols, s)
+    assert (S.low(rows, s), S.low(cols, s)) == (9, 10)
+    held = [spread(color, 13)] + [spread(a, k) for a, k in zip(lo, (11, 13, 11, 13, 11))] + [spread(a, k) for a, k in zip(hi, (13, 11, 13, 11, 13))]
+    ptr = lambda a: C.c_void_p(a.ctypes.data)
+    g_lo = _capi.DenoiseGuides(*(a.ctypes.data for a in held[1:5]), 11, 13, 11, 13)
+    g_hi = _capi.DenoiseGuides(*(a.ctypes.data for a in held[6:10]), 13, 11, 13, 11)
+    p = _capi.UpsampleParams(KW["sigma_normal"], KW["sigma_position"], s, radius, 3)
+    out = np.zeros((rows, cols, 3), dtype=F32)
+    _capi.check(_capi.amd_lib().rt_upsample_guided_host(ptr(held[0]), 13, C.byref(g_lo), ptr(held[5]), 11, C.byref(g_hi), ptr(held[10]), 13, C.byref(p), rows, cols,
+                                                        ptr(out)))
+    expect = S.bits(want(rows, cols, s, radius, True, 3)).reshape(rows, cols, 3)  # the _cpu form on the same values
+    assert np.array_equal(S.bits(out)[-1, -1], expect[-1, -1])
+    assert np.array_equal(S.bits(out), expect)
 
 
 def test_on_a_stream_and_in_a_captured_graph():
