@@ -24,10 +24,10 @@ import numpy as np
 from . import _capi
 from ._args import _new, _on_stream, _out_tensor, _p, _stream_ptr, _tensor, _torch
 from ._capi import Camera, Frame
+from ._forms import CUDA, NUMPY
 from ._post import luma_row
 from ._queries import RAY_DTYPE, trace_rays
 from ._world import Scene
-from .denoise import _np_plane, _plane
 from .film import FILTERS, PATTERNS, Film, _code, _np_ptr
 
 __all__ = ["SAMPLE_MAX", "GAIN", "EPSILON", "SampleList", "budget", "budget_numpy", "list_temp_bytes", "sample_list", "sample_list_numpy",
@@ -52,6 +52,15 @@ def _budget_params(gain, epsilon, min_count, max_count):
     return _capi.SampleBudgetParams(float(gain), float(epsilon), int(min_count), int(max_count), 0)
 
 
+def _budget(form, n, m, v, count, valid, params, shape, dtype, like, out=None, stream=None):
+    """``m``, ``v``: the (pointer, stride) of mean and variance, which each form sizes and refuses in its own words"""
+    c, c_stride = form.plane(count, "count", "i", n, 1)
+    w, w_stride = form.plane(valid, "valid", "i", n, 1)
+    out = form.out(out, shape, dtype, like, stream=stream)
+    form.call("rt_sample_budget", stream, *m, *v, c, c_stride, w, w_stride, C.byref(params), n, form.ptr(out))
+    return out
+
+
 def budget_numpy(mean, variance, count=None, valid=None, gain: float = GAIN, epsilon: float = EPSILON, min_count: int = 1,
                  max_count: int = SAMPLE_MAX) -> np.ndarray:
     """The CPU definition (rt_sample_budget_cpu, librt_host.so; no device, no torch): ``mean`` / ``variance`` float32 planes of one word
@@ -61,16 +70,10 @@ def budget_numpy(mean, variance, count=None, valid=None, gain: float = GAIN, eps
     ``gain * sqrt(variance / count) / (|mean| + epsilon)``, at most ``max_count``."""
     shape = np.asarray(mean).shape
     n = int(np.asarray(mean).size)
-    m, m_stride = _np_plane(mean, "mean", "f", n, 1)
-    v, v_stride = _np_plane(variance, "variance", "f", n, 1)
-    if m is None or v is None:
+    m, v = NUMPY.plane(mean, "mean", "f", n, 1), NUMPY.plane(variance, "variance", "f", n, 1)
+    if m[0] is None or v[0] is None:
         raise ValueError("mean and variance: expected planes, not None")
-    c, c_stride = _np_plane(count, "count", "iu", n, 1)
-    w, w_stride = _np_plane(valid, "valid", "iu", n, 1)
-    out = np.zeros(shape, dtype=np.uint32)
-    p = _budget_params(gain, epsilon, min_count, max_count)
-    _capi.check_host(_capi.host_lib().rt_sample_budget_cpu(m, m_stride, v, v_stride, c, c_stride, w, w_stride, C.byref(p), n, _np_ptr(out)))
-    return out
+    return _budget(NUMPY, n, m, v, count, valid, _budget_params(gain, epsilon, min_count, max_count), shape, "uint32", None)
 
 
 def budget(mean, variance, count=None, valid=None, gain: float = GAIN, epsilon: float = EPSILON, min_count: int = 1, max_count: int = SAMPLE_MAX,
@@ -80,17 +83,8 @@ def budget(mean, variance, count=None, valid=None, gain: float = GAIN, epsilon: 
     torch's current stream), capturable when ``out`` is given."""
     _tensor(mean, "mean", "float32", None, contiguous=False)
     n = mean.numel()
-    m, m_stride = _plane(mean, "mean", "float32", n, 1)
-    v, v_stride = _plane(variance, "variance", "float32", n, 1)
-    if v is None:
-        raise ValueError("variance must be a float32 CUDA tensor, not None")
-    c, c_stride = _plane(count, "count", "int32", n, 1)
-    w, w_stride = _plane(valid, "valid", "int32", n, 1)
-    with _on_stream(stream):
-        out = _out_tensor(out, (n,), "int32", mean.device)
-    p = _budget_params(gain, epsilon, min_count, max_count)
-    _capi.check(_capi.amd_lib().rt_sample_budget(m, m_stride, v, v_stride, c, c_stride, w, w_stride, C.byref(p), n, _p(out), _stream_ptr(stream)))
-    return out
+    m, v = CUDA.plane(mean, "mean", "f", n, 1), CUDA.required(variance, "variance", "f", n, 1)
+    return _budget(CUDA, n, m, v, count, valid, _budget_params(gain, epsilon, min_count, max_count), (n,), "int32", mean, out, stream)
 
 
 def list_temp_bytes(n: int) -> int:

@@ -19,9 +19,9 @@ import numpy as np
 from . import _capi
 from ._args import _host_records, _on_stream, _out_tensor, _p, _stream_ptr
 from ._capi import Camera, Frame
+from ._forms import CUDA
 from ._queries import HIT_DTYPE, _hit_records
 from ._world import Scene, World
-from .denoise import _plane
 from .materials import primary_surfaces
 from .temporal import History
 
@@ -51,7 +51,7 @@ def previous_positions(scene: Scene, hits, out=None, stream=None):
     if out is None:
         with _on_stream(stream):
             out = _out_tensor(None, (n, 3), "float32", records.device)
-    p, stride = _plane(out, "out", "float32", n, 3)
+    p, stride = CUDA.plane(out, "out", "f", n, 3)
     _capi.check(_capi.amd_lib().rt_previous_positions(scene._h, _p(records), n, p, stride if n else 3, _stream_ptr(stream)))
     return out
 

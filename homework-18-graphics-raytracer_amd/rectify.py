@@ -32,24 +32,59 @@ import ctypes as C
 import numpy as np
 
 from . import _capi, svgf
-from ._args import _on_stream, _out_tensor, _p, _stream_ptr, _tensor
+from ._args import _on_stream, _out_tensor
 from ._capi import Camera, Frame
+from ._forms import CUDA, NUMPY, temporal_guides
 from ._world import Scene
-from .denoise import _np_plane, _plane
 from .materials import primary_surfaces
-from .temporal import (_RECORD_WORDS, ALPHA_MIN, HISTORY_DTYPE, MAX_LENGTH, NORMAL_MIN, POSITION_MAX, Guides, History, _guides, _np_guides,
-                       _params)
+from .temporal import _HISTORY, ALPHA_MIN, HISTORY_DTYPE, MAX_LENGTH, NORMAL_MIN, POSITION_MAX, Guides, History, _params
 
 __all__ = ["bounds", "bounds_numpy", "accumulate_bounded", "accumulate_bounded_numpy", "feedback", "feedback_numpy", "BOX_DTYPE", "GAMMA",
            "RADIUS", "CLAMPED_LENGTH", "filter_frame"]
 
 GAMMA, RADIUS, CLAMPED_LENGTH = 1.0, 1, 4
 BOX_DTYPE = np.dtype([("lo", "<f4", (4,)), ("hi", "<f4", (4,))])
-_BOX_WORDS = 8
+_BOX = ("BOX_DTYPE", BOX_DTYPE, "float32", 8)  # the record type of _forms' compact and out
 
 
 def _bounds_params(gamma, radius):
     return _capi.BoundsParams(float(gamma), int(radius), 0)
+
+
+def _bounds(form, color, rows, cols, object, valid, params, out=None, stream=None):
+    rows, cols = int(rows), int(cols)
+    n = rows * cols
+    c, c_stride = form.required(color, "color", "f", n, 3)
+    o, o_stride = form.plane(object, "object", "i", n, 1)
+    v, v_stride = form.plane(valid, "valid", "i", n, 1)
+    out = form.out(out, (rows, cols), None, color, stream=stream, record=_BOX)
+    form.call("rt_temporal_bounds", stream, c, c_stride, o, o_stride, v, v_stride, C.byref(params), rows, cols, form.ptr(out))
+    return out
+
+
+def _accumulate_bounded(form, color, motion, rows, cols, history, box, current, previous, params, clamped_length, out, variance, clamped, counts,
+                        stream=None):
+    """``variance``, ``clamped``: False for none, else as ``out``; ``counts``: the dtype of ``clamped``"""
+    rows, cols = int(rows), int(cols)
+    c = form.compact(color, "color", rows, cols, 3)
+    m = form.compact(motion, "motion", rows, cols, 2)
+    h = form.compact(history, "history", rows, cols, record=_HISTORY)
+    b = form.compact(box, "box", rows, cols, record=_BOX)
+    cur, prev = temporal_guides(form, current, rows * cols), temporal_guides(form, previous, rows * cols)
+    out = form.out(out, (rows, cols), None, color, stream=stream, record=_HISTORY)
+    variance = None if variance is False else form.out(variance, (rows, cols), "float32", color, "variance", stream)
+    clamped = None if clamped is False else form.out(clamped, (rows, cols), counts, color, "clamped", stream)
+    form.call("rt_temporal_accumulate_bounded", stream, c, m, C.byref(cur), C.byref(prev), C.byref(params), rows, cols, h, form.ptr(out), form.ptr(variance),
+              b, int(clamped_length), form.ptr(clamped))
+    return out, variance, clamped
+
+
+def _feedback(form, color, history, rows, cols, valid, stream=None):
+    """``history`` is written in place"""
+    rows, cols = int(rows), int(cols)
+    c, c_stride = form.required(color, "color", "f", rows * cols, 3)
+    v, v_stride = form.plane(valid, "valid", "i", rows * cols, 1)
+    form.call("rt_temporal_feedback", stream, c, c_stride, v, v_stride, rows, cols, form.compact(history, "history", rows, cols, record=_HISTORY))
 
 
 def bounds_numpy(color, rows: int, cols: int, object=None, valid=None, gamma: float = GAMMA, radius: int = RADIUS):
@@ -57,17 +92,7 @@ def bounds_numpy(color, rows: int, cols: int, object=None, valid=None, gamma: fl
     or a strided record view; ``object`` / ``valid`` rows * cols 4-byte integers, compact or strided, or None.  Returns a new (rows, cols)
     BOX_DTYPE array: ``lo`` and ``hi`` of the three colour channels and, last, of the luminance; (-inf, +inf) where ``valid`` is 0.
     Nothing given is written."""
-    rows, cols = int(rows), int(cols)
-    n = rows * cols
-    c, c_stride = _np_plane(color, "color", "f", n, 3)
-    if c is None:
-        raise ValueError("color: expected a plane, not None")
-    o, o_stride = _np_plane(object, "object", "iu", n, 1)
-    v, v_stride = _np_plane(valid, "valid", "iu", n, 1)
-    out = np.zeros((rows, cols), dtype=BOX_DTYPE)
-    p = _bounds_params(gamma, radius)
-    _capi.check_host(_capi.host_lib().rt_temporal_bounds_cpu(c, c_stride, o, o_stride, v, v_stride, C.byref(p), rows, cols, C.c_void_p(out.ctypes.data)))
-    return out
+    return _bounds(NUMPY, color, rows, cols, object, valid, _bounds_params(gamma, radius))
 
 
 def bounds(color, rows: int, cols: int, object=None, valid=None, gamma: float = GAMMA, radius: int = RADIUS, out=None, stream=None):
@@ -75,18 +100,7 @@ def bounds(color, rows: int, cols: int, object=None, valid=None, gamma: float = 
     or a strided view; ``object`` / ``valid`` int32 CUDA tensors, contiguous or strided views such as those of
     ``materials.PrimarySurfaces``.  Returns ``out``, a contiguous (rows * cols, 8) float32 CUDA tensor of boxes — lo[4], hi[4] — allocated
     if None.  One kernel launch, stream-ordered on ``stream`` (default: torch's current stream), capturable when ``out`` is given."""
-    rows, cols = int(rows), int(cols)
-    n = rows * cols
-    c, c_stride = _plane(color, "color", "float32", n, 3)
-    if c is None:
-        raise ValueError("color must be a float32 CUDA tensor, not None")
-    o, o_stride = _plane(object, "object", "int32", n, 1)
-    v, v_stride = _plane(valid, "valid", "int32", n, 1)
-    with _on_stream(stream):
-        out = _out_tensor(out, (n, _BOX_WORDS), "float32", color.device)
-    p = _bounds_params(gamma, radius)
-    _capi.check(_capi.amd_lib().rt_temporal_bounds(c, c_stride, o, o_stride, v, v_stride, C.byref(p), rows, cols, _p(out), _stream_ptr(stream)))
-    return out
+    return _bounds(CUDA, color, rows, cols, object, valid, _bounds_params(gamma, radius), out, stream)
 
 
 def accumulate_bounded_numpy(color, motion, rows: int, cols: int, history, box, current: Guides = None, previous: Guides = None,
@@ -96,28 +110,8 @@ def accumulate_bounded_numpy(color, motion, rows: int, cols: int, history, box, 
     ``box``, rows * cols BOX_DTYPE records (bounds_numpy's of ``color``, or your own), clamping the gathered history before the blend, and
     ``clamped_length`` (0 .. max_length; 0: lengths are not cut).  Returns (history_out, variance, clamped): as accumulate_numpy, and a
     (rows, cols) uint32 array of how many of the four channels the clamp changed.  Nothing given is written."""
-    rows, cols = int(rows), int(cols)
-    n = rows * cols
-    c, m, h, b = np.asarray(color), np.asarray(motion), np.asarray(history), np.asarray(box)
-    if c.dtype != np.float32 or c.size != n * 3 or (c.ndim and c.shape[-1] != 3):
-        raise ValueError(f"color: expected {n} pixels of 3 float32")
-    if m.dtype != np.float32 or m.size != n * 2 or (m.ndim and m.shape[-1] != 2):
-        raise ValueError(f"motion: expected {n} pixels of 2 float32")
-    if h.dtype != HISTORY_DTYPE or h.size != n:
-        raise ValueError(f"history: expected {n} HISTORY_DTYPE records")
-    if b.dtype != BOX_DTYPE or b.size != n:
-        raise ValueError(f"box: expected {n} BOX_DTYPE records")
-    c, m, h, b = np.ascontiguousarray(c), np.ascontiguousarray(m), np.ascontiguousarray(h), np.ascontiguousarray(b)
-    out = np.zeros((rows, cols), dtype=HISTORY_DTYPE)
-    var = np.zeros((rows, cols), dtype=np.float32) if variance else None
-    clamped = np.zeros((rows, cols), dtype=np.uint32)
-    cur, prev = _np_guides(current, n), _np_guides(previous, n)
-    p = _params(normal_min, position_max, alpha_min, max_length)
-    _capi.check_host(_capi.host_lib().rt_temporal_accumulate_bounded_cpu(
-        C.c_void_p(c.ctypes.data), C.c_void_p(m.ctypes.data), C.byref(cur), C.byref(prev), C.byref(p), rows, cols, C.c_void_p(h.ctypes.data),
-        C.c_void_p(out.ctypes.data), None if var is None else C.c_void_p(var.ctypes.data), C.c_void_p(b.ctypes.data), int(clamped_length),
-        C.c_void_p(clamped.ctypes.data)))
-    return out, var, clamped
+    return _accumulate_bounded(NUMPY, color, motion, rows, cols, history, box, current, previous, _params(normal_min, position_max, alpha_min, max_length),
+                               clamped_length, None, None if variance else False, None, "uint32")
 
 
 def accumulate_bounded(color, motion, rows: int, cols: int, history, box, current: Guides = None, previous: Guides = None,
@@ -127,38 +121,17 @@ def accumulate_bounded(color, motion, rows: int, cols: int, history, box, curren
     ``box`` a contiguous (rows * cols, 8) float32 CUDA tensor (``bounds``'s).  ``clamped``: a (rows, cols) int32 CUDA tensor, allocated if
     None, or False for none.  Returns (out, variance, clamped).  One kernel launch, stream-ordered on ``stream`` (default: torch's current
     stream), capturable when ``out``, ``variance`` and ``clamped`` are given."""
-    rows, cols = int(rows), int(cols)
-    n = rows * cols
-    _tensor(color, "color", "float32", (rows, cols, 3))
-    _tensor(motion, "motion", "float32", (rows, cols, 2))
-    _tensor(history, "history", "int32", (n, _RECORD_WORDS))
-    _tensor(box, "box", "float32", (n, _BOX_WORDS))
-    cur, prev = _guides(current, n), _guides(previous, n)
-    with _on_stream(stream):
-        out = _out_tensor(out, (n, _RECORD_WORDS), "int32", color.device)
-        variance = None if variance is False else _out_tensor(variance, (rows, cols), "float32", color.device, name="variance")
-        clamped = None if clamped is False else _out_tensor(clamped, (rows, cols), "int32", color.device, name="clamped")
-    p = _params(normal_min, position_max, alpha_min, max_length)
-    _capi.check(_capi.amd_lib().rt_temporal_accumulate_bounded(_p(color), _p(motion), C.byref(cur), C.byref(prev), C.byref(p), rows, cols, _p(history),
-                                                               _p(out), _p(variance), _p(box), int(clamped_length), _p(clamped), _stream_ptr(stream)))
-    return out, variance, clamped
+    return _accumulate_bounded(CUDA, color, motion, rows, cols, history, box, current, previous, _params(normal_min, position_max, alpha_min, max_length),
+                               clamped_length, out, variance, clamped, "int32", stream)
 
 
 def feedback_numpy(color, history, rows: int, cols: int, valid=None):
     """The CPU definition (rt_temporal_feedback_cpu, librt_host.so; no device, no torch): a COPY of ``history`` (rows * cols HISTORY_DTYPE
     records) whose colour is ``color`` — rows * cols pixels of 3 float32, compact or strided, the raw words — where the record's length is
     not 0 and ``valid`` (rows * cols 4-byte integers, or None) is not 0.  Returns the new (rows, cols) array; nothing given is written."""
-    rows, cols = int(rows), int(cols)
-    n = rows * cols
-    c, c_stride = _np_plane(color, "color", "f", n, 3)
-    if c is None:
-        raise ValueError("color: expected a plane, not None")
-    v, v_stride = _np_plane(valid, "valid", "iu", n, 1)
-    h = np.asarray(history)
-    if h.dtype != HISTORY_DTYPE or h.size != n:
-        raise ValueError(f"history: expected {n} HISTORY_DTYPE records")
-    out = np.array(h, dtype=HISTORY_DTYPE, order="C").reshape(rows, cols)
-    _capi.check_host(_capi.host_lib().rt_temporal_feedback_cpu(c, c_stride, v, v_stride, rows, cols, C.c_void_p(out.ctypes.data)))
+    NUMPY.compact(history, "history", int(rows), int(cols), record=_HISTORY)
+    out = np.array(history, dtype=HISTORY_DTYPE, order="C").reshape(int(rows), int(cols))  # the copy is what the call writes
+    _feedback(NUMPY, color, out, rows, cols, valid)
     return out
 
 
@@ -167,14 +140,7 @@ def feedback(color, history, rows: int, cols: int, valid=None, stream=None):
     tensor of history records (``temporal.History.records``), ``color`` a float32 CUDA tensor of rows * cols pixels x 3, contiguous or a
     strided view, ``valid`` an int32 CUDA tensor or None.  Returns ``history``.  One kernel launch, stream-ordered on ``stream`` (default:
     torch's current stream), capturable."""
-    rows, cols = int(rows), int(cols)
-    n = rows * cols
-    c, c_stride = _plane(color, "color", "float32", n, 3)
-    if c is None:
-        raise ValueError("color must be a float32 CUDA tensor, not None")
-    v, v_stride = _plane(valid, "valid", "int32", n, 1)
-    _tensor(history, "history", "int32", (n, _RECORD_WORDS))
-    _capi.check(_capi.amd_lib().rt_temporal_feedback(c, c_stride, v, v_stride, rows, cols, _p(history), _stream_ptr(stream)))
+    _feedback(CUDA, color, history, rows, cols, valid, stream)
     return history
 
 

@@ -24,19 +24,17 @@ from __future__ import annotations
 
 import ctypes as C
 
-import numpy as np
-
 from . import _capi
-from ._args import _on_stream, _out_tensor, _p, _stream_ptr, _tensor
+from ._args import _on_stream
 from ._capi import Camera, Frame
+from ._forms import CUDA, DEMODULATE, NUMPY, denoise_guides
 from ._world import Scene
-from .denoise import SIGMA_NORMAL, SIGMA_POSITION, _guides, _np_guides, _np_plane, _plane
-from .temporal import _RECORD_WORDS, HISTORY_DTYPE, History, accumulate_frame
+from .denoise import SIGMA_NORMAL, SIGMA_POSITION
+from .temporal import _HISTORY, History, accumulate_frame
 
 __all__ = ["variance", "variance_numpy", "atrous", "atrous_numpy", "temp_bytes", "filter_frame"]
 
 SIGMA_LUMINANCE, MIN_LENGTH = 4.0, 4
-_DEMODULATE = 3  # RT_DENOISE_DEMODULATE
 
 
 def temp_bytes(rows: int, cols: int, levels: int) -> int:
@@ -55,7 +53,32 @@ def _variance_params(sigma_normal, sigma_position, min_length):
 
 def _atrous_params(levels, first_level, sigma_luminance, sigma_normal, sigma_position, demodulate):
     return _capi.SvgfAtrousParams(float(sigma_luminance), float(sigma_normal), float(sigma_position), int(first_level), int(levels),
-                                  _DEMODULATE if demodulate is True else int(demodulate))
+                                  DEMODULATE if demodulate is True else int(demodulate))
+
+
+def _variance(form, history, rows, cols, normal, position, valid, params, out=None, stream=None):
+    rows, cols = int(rows), int(cols)
+    h = form.compact(history, "history", rows, cols, record=_HISTORY)
+    g = denoise_guides(form, rows * cols, normal, position, None, valid)
+    out = form.out(out, (rows, cols), "float32", history, stream=stream)
+    form.call("rt_svgf_variance", stream, h, C.byref(g), C.byref(params), rows, cols, form.ptr(out))
+    return out
+
+
+def _atrous(form, color, variance, rows, cols, normal, position, albedo, valid, params, out, variance_out, temp=None, stream=None):
+    """``variance_out``: False for none, else as ``out``"""
+    rows, cols = int(rows), int(cols)
+    n = rows * cols
+    c, c_stride = form.required(color, "color", "f", n, 3)
+    v = form.compact(variance, "variance", rows, cols)
+    g = denoise_guides(form, n, normal, position, albedo, valid)
+    words = _temp_words(n, params.n_levels)
+    out = form.out(out, (rows, cols, 3), "float32", color, stream=stream)
+    variance_out = None if variance_out is False else form.out(variance_out, (rows, cols), "float32", color, "variance_out", stream)
+    if temp is not None or words:
+        temp = form.out(temp, (words,), "float32", color, "temp", stream)
+    form.call("rt_svgf_atrous", stream, c, c_stride, v, C.byref(g), C.byref(params), rows, cols, form.ptr(out), form.ptr(variance_out), form.ptr(temp))
+    return out, variance_out
 
 
 def variance_numpy(history, rows: int, cols: int, normal=None, position=None, valid=None, min_length: int = MIN_LENGTH,
@@ -63,17 +86,7 @@ def variance_numpy(history, rows: int, cols: int, normal=None, position=None, va
     """The CPU definition (rt_svgf_variance_cpu, librt_host.so; no device, no torch): ``history`` rows * cols HISTORY_DTYPE records as
     ``temporal.accumulate_numpy`` returns them; ``normal`` / ``position`` rows * cols pixels of 3 float32, compact or strided record
     views, ``valid`` rows * cols 4-byte integers, any of them None.  Returns a new (rows, cols) float32 array; nothing given is written."""
-    rows, cols = int(rows), int(cols)
-    n = rows * cols
-    h = np.asarray(history)
-    if h.dtype != HISTORY_DTYPE or h.size != n:
-        raise ValueError(f"history: expected {n} HISTORY_DTYPE records")
-    h = np.ascontiguousarray(h)
-    g = _np_guides(n, normal, position, None, valid)
-    out = np.zeros((rows, cols), dtype=np.float32)
-    p = _variance_params(sigma_normal, sigma_position, min_length)
-    _capi.check_host(_capi.host_lib().rt_svgf_variance_cpu(C.c_void_p(h.ctypes.data), C.byref(g), C.byref(p), rows, cols, C.c_void_p(out.ctypes.data)))
-    return out
+    return _variance(NUMPY, history, rows, cols, normal, position, valid, _variance_params(sigma_normal, sigma_position, min_length))
 
 
 def variance(history, rows: int, cols: int, normal=None, position=None, valid=None, min_length: int = MIN_LENGTH,
@@ -82,15 +95,7 @@ def variance(history, rows: int, cols: int, normal=None, position=None, valid=No
     history records (``temporal.History.records``); the guides float32 (``valid``: int32) CUDA tensors, contiguous or strided views.
     Returns ``out``, a (rows, cols) float32 CUDA tensor (allocated if None).  One kernel launch, stream-ordered on ``stream`` (default:
     torch's current stream), capturable when ``out`` is given."""
-    rows, cols = int(rows), int(cols)
-    n = rows * cols
-    _tensor(history, "history", "int32", (n, _RECORD_WORDS))
-    g = _guides(n, normal, position, None, valid)
-    with _on_stream(stream):
-        out = _out_tensor(out, (rows, cols), "float32", history.device)
-    p = _variance_params(sigma_normal, sigma_position, min_length)
-    _capi.check(_capi.amd_lib().rt_svgf_variance(_p(history), C.byref(g), C.byref(p), rows, cols, _p(out), _stream_ptr(stream)))
-    return out
+    return _variance(CUDA, history, rows, cols, normal, position, valid, _variance_params(sigma_normal, sigma_position, min_length), out, stream)
 
 
 def atrous_numpy(color, variance, rows: int, cols: int, normal=None, position=None, albedo=None, valid=None, levels: int = 5, first_level: int = 0,
@@ -102,25 +107,8 @@ def atrous_numpy(color, variance, rows: int, cols: int, normal=None, position=No
     ``sigma_luminance`` at each; a sigma of ``math.inf`` switches its term off.  ``demodulate`` as in ``denoise.atrous_numpy``.  Returns
     (color, variance): new (rows, cols, 3) and (rows, cols) float32 arrays, the second None without ``variance_out``.  Nothing given is
     written."""
-    rows, cols = int(rows), int(cols)
-    n = rows * cols
-    c, c_stride = _np_plane(color, "color", "f", n, 3)
-    if c is None:
-        raise ValueError("color: expected a plane, not None")
-    v = np.asarray(variance)
-    if v.dtype != np.float32 or v.size != n:
-        raise ValueError(f"variance: expected {n} float32")
-    v = np.ascontiguousarray(v)
-    g = _np_guides(n, normal, position, albedo, valid)
-    out = np.zeros((rows, cols, 3), dtype=np.float32)
-    var = np.zeros((rows, cols), dtype=np.float32) if variance_out else None
-    words = _temp_words(n, int(levels))
-    temp = np.zeros(words, dtype=np.float32) if words else None
-    p = _atrous_params(levels, first_level, sigma_luminance, sigma_normal, sigma_position, demodulate)
-    _capi.check_host(_capi.host_lib().rt_svgf_atrous_cpu(c, c_stride, C.c_void_p(v.ctypes.data), C.byref(g), C.byref(p), rows, cols,
-                                                         C.c_void_p(out.ctypes.data), None if var is None else C.c_void_p(var.ctypes.data),
-                                                         None if temp is None else C.c_void_p(temp.ctypes.data)))
-    return out, var
+    return _atrous(NUMPY, color, variance, rows, cols, normal, position, albedo, valid,
+                   _atrous_params(levels, first_level, sigma_luminance, sigma_normal, sigma_position, demodulate), None, None if variance_out else False)
 
 
 def atrous(color, variance, rows: int, cols: int, normal=None, position=None, albedo=None, valid=None, levels: int = 5, first_level: int = 0,
@@ -133,23 +121,8 @@ def atrous(color, variance, rows: int, cols: int, normal=None, position=None, al
     cols, levels) / 4 elements, allocated if None and levels >= 2.  One kernel launch per level, stream-ordered on ``stream`` (default:
     torch's current stream), capturable when ``out``, ``variance_out`` and ``temp`` are given.  The inputs are not written; outputs and
     scratch must be other tensors than the inputs and each other."""
-    rows, cols = int(rows), int(cols)
-    n = rows * cols
-    c, c_stride = _plane(color, "color", "float32", n, 3)
-    if c is None:
-        raise ValueError("color must be a float32 CUDA tensor, not None")
-    _tensor(variance, "variance", "float32", (rows, cols))
-    g = _guides(n, normal, position, albedo, valid)
-    words = _temp_words(n, int(levels))
-    with _on_stream(stream):
-        out = _out_tensor(out, (rows, cols, 3), "float32", color.device)
-        variance_out = None if variance_out is False else _out_tensor(variance_out, (rows, cols), "float32", color.device, name="variance_out")
-        if temp is not None or words:
-            temp = _out_tensor(temp, (words,), "float32", color.device, name="temp")
-    p = _atrous_params(levels, first_level, sigma_luminance, sigma_normal, sigma_position, demodulate)
-    _capi.check(_capi.amd_lib().rt_svgf_atrous(c, c_stride, _p(variance), C.byref(g), C.byref(p), rows, cols, _p(out), _p(variance_out), _p(temp),
-                                               _stream_ptr(stream)))
-    return out, variance_out
+    return _atrous(CUDA, color, variance, rows, cols, normal, position, albedo, valid,
+                   _atrous_params(levels, first_level, sigma_luminance, sigma_normal, sigma_position, demodulate), out, variance_out, temp, stream)
 
 
 def filter_frame(scene: Scene, camera: Camera, frame: Frame, image, history: History, stream=None, min_length: int = MIN_LENGTH, **params):

@@ -30,10 +30,10 @@ from typing import NamedTuple
 import numpy as np
 
 from . import _capi
-from ._args import _on_stream, _out_tensor, _p, _stream_ptr, _tensor, _torch
+from ._args import _on_stream, _torch
 from ._capi import Camera, Frame
+from ._forms import CUDA, NUMPY, temporal_guides
 from ._world import Scene
-from .denoise import _np_plane, _plane
 from .materials import primary_surfaces
 
 __all__ = ["motion", "motion_numpy", "accumulate", "accumulate_numpy", "HISTORY_DTYPE", "Guides", "History", "accumulate_frame"]
@@ -41,6 +41,7 @@ __all__ = ["motion", "motion_numpy", "accumulate", "accumulate_numpy", "HISTORY_
 NORMAL_MIN, POSITION_MAX, ALPHA_MIN, MAX_LENGTH = 0.9, 0.1, 0.05, 32
 HISTORY_DTYPE = np.dtype([("color", "<f4", (3,)), ("moment1", "<f4"), ("moment2", "<f4"), ("length", "<u4"), ("reserved", "<u4", (2,))])
 _RECORD_WORDS = 8
+_HISTORY = ("HISTORY_DTYPE", HISTORY_DTYPE, "int32", _RECORD_WORDS)  # the record type of _forms' compact and out
 
 
 class Guides(NamedTuple):
@@ -67,24 +68,26 @@ def _full(frame: Frame):
     return int(frame.height), int(frame.width)
 
 
-def _np_guides(g, n):
-    g = Guides() if g is None else g
-    c = _capi.TemporalGuides()
-    c.normal, c.normal_stride = _np_plane(g.normal, "normal", "f", n, 3)
-    c.position, c.position_stride = _np_plane(g.position, "position", "f", n, 3)
-    c.object, c.object_stride = _np_plane(g.object, "object", "iu", n, 1)
-    c.valid, c.valid_stride = _np_plane(g.valid, "valid", "iu", n, 1)
-    return c
+def _motion(form, position, camera, frame, valid, out=None, stream=None):
+    rows, cols = _full(frame)
+    p, p_stride = form.required(position, "position", "f", rows * cols, 3)
+    v, v_stride = form.plane(valid, "valid", "i", rows * cols, 1)
+    out = form.out(out, (rows, cols, 2), "float32", position, stream=stream)
+    form.call("rt_temporal_motion", stream, p, p_stride, v, v_stride, C.byref(camera), C.byref(frame), form.ptr(out))
+    return out
 
 
-def _guides(g, n):
-    g = Guides() if g is None else g
-    c = _capi.TemporalGuides()
-    c.normal, c.normal_stride = _plane(g.normal, "normal", "float32", n, 3)
-    c.position, c.position_stride = _plane(g.position, "position", "float32", n, 3)
-    c.object, c.object_stride = _plane(g.object, "object", "int32", n, 1)
-    c.valid, c.valid_stride = _plane(g.valid, "valid", "int32", n, 1)
-    return c
+def _accumulate(form, color, motion, rows, cols, history, current, previous, params, out, variance, stream=None):
+    """``variance``: False for none, else as ``out``"""
+    rows, cols = int(rows), int(cols)
+    c = form.compact(color, "color", rows, cols, 3)
+    m = form.compact(motion, "motion", rows, cols, 2)
+    h = form.compact(history, "history", rows, cols, record=_HISTORY)
+    cur, prev = temporal_guides(form, current, rows * cols), temporal_guides(form, previous, rows * cols)
+    out = form.out(out, (rows, cols), None, color, stream=stream, record=_HISTORY)
+    variance = None if variance is False else form.out(variance, (rows, cols), "float32", color, "variance", stream)
+    form.call("rt_temporal_accumulate", stream, c, m, C.byref(cur), C.byref(prev), C.byref(params), rows, cols, h, form.ptr(out), form.ptr(variance))
+    return out, variance
 
 
 def motion_numpy(position, camera: Camera, frame: Frame, valid=None):
@@ -92,31 +95,14 @@ def motion_numpy(position, camera: Camera, frame: Frame, valid=None):
     3 float32 — compact or a strided record view — projected through ``camera`` over the full frame ``frame``, both of the PREVIOUS
     frame; ``valid`` the same number of 4-byte integers or None.  Returns a new (rows, cols, 2) float32 array of (px, py), NaN where
     valid is 0 or the point is not in front of the camera."""
-    rows, cols = _full(frame)
-    n = rows * cols
-    p, p_stride = _np_plane(position, "position", "f", n, 3)
-    v, v_stride = _np_plane(valid, "valid", "iu", n, 1)
-    if p is None:
-        raise ValueError("position: expected a plane, not None")
-    out = np.zeros((rows, cols, 2), dtype=np.float32)
-    _capi.check_host(_capi.host_lib().rt_temporal_motion_cpu(p, p_stride, v, v_stride, C.byref(camera), C.byref(frame), C.c_void_p(out.ctypes.data)))
-    return out
+    return _motion(NUMPY, position, camera, frame, valid)
 
 
 def motion(position, camera: Camera, frame: Frame, valid=None, out=None, stream=None):
     """motion_numpy on the device (rt_temporal_motion), bit for bit: ``position`` a float32 CUDA tensor (``valid``: int32), contiguous or
     a strided view such as ``PrimarySurfaces.position``.  Returns ``out``, a (rows, cols, 2) float32 CUDA tensor (allocated if None).  One
     kernel launch, stream-ordered on ``stream`` (default: torch's current stream), capturable when ``out`` is given."""
-    rows, cols = _full(frame)
-    n = rows * cols
-    p, p_stride = _plane(position, "position", "float32", n, 3)
-    v, v_stride = _plane(valid, "valid", "int32", n, 1)
-    if p is None:
-        raise ValueError("position must be a float32 CUDA tensor, not None")
-    with _on_stream(stream):
-        out = _out_tensor(out, (rows, cols, 2), "float32", position.device)
-    _capi.check(_capi.amd_lib().rt_temporal_motion(p, p_stride, v, v_stride, C.byref(camera), C.byref(frame), _p(out), _stream_ptr(stream)))
-    return out
+    return _motion(CUDA, position, camera, frame, valid, out, stream)
 
 
 def accumulate_numpy(color, motion, rows: int, cols: int, history, current: Guides = None, previous: Guides = None,
@@ -127,24 +113,8 @@ def accumulate_numpy(color, motion, rows: int, cols: int, history, current: Guid
     history), ``current`` / ``previous`` the Guides of the two frames (``current.position`` is where the point WAS: the plane given to
     motion).  Returns (history_out, variance): a new (rows, cols) HISTORY_DTYPE array and a (rows, cols) float32 array, or None without
     ``variance``.  Nothing given is written."""
-    rows, cols = int(rows), int(cols)
-    n = rows * cols
-    c, m, h = np.asarray(color), np.asarray(motion), np.asarray(history)
-    if c.dtype != np.float32 or c.size != n * 3 or (c.ndim and c.shape[-1] != 3):
-        raise ValueError(f"color: expected {n} pixels of 3 float32")
-    if m.dtype != np.float32 or m.size != n * 2 or (m.ndim and m.shape[-1] != 2):
-        raise ValueError(f"motion: expected {n} pixels of 2 float32")
-    if h.dtype != HISTORY_DTYPE or h.size != n:
-        raise ValueError(f"history: expected {n} HISTORY_DTYPE records")
-    c, m, h = np.ascontiguousarray(c), np.ascontiguousarray(m), np.ascontiguousarray(h)
-    out = np.zeros((rows, cols), dtype=HISTORY_DTYPE)
-    var = np.zeros((rows, cols), dtype=np.float32) if variance else None
-    cur, prev = _np_guides(current, n), _np_guides(previous, n)
-    p = _params(normal_min, position_max, alpha_min, max_length)
-    _capi.check_host(_capi.host_lib().rt_temporal_accumulate_cpu(
-        C.c_void_p(c.ctypes.data), C.c_void_p(m.ctypes.data), C.byref(cur), C.byref(prev), C.byref(p), rows, cols, C.c_void_p(h.ctypes.data),
-        C.c_void_p(out.ctypes.data), None if var is None else C.c_void_p(var.ctypes.data)))
-    return out, var
+    return _accumulate(NUMPY, color, motion, rows, cols, history, current, previous, _params(normal_min, position_max, alpha_min, max_length),
+                       None, None if variance else False)
 
 
 def accumulate(color, motion, rows: int, cols: int, history, current: Guides = None, previous: Guides = None, normal_min: float = NORMAL_MIN,
@@ -155,19 +125,8 @@ def accumulate(color, motion, rows: int, cols: int, history, current: Guides = N
     tensors; the guides float32 (``object``, ``valid``: int32) CUDA tensors, contiguous or strided views.  ``variance``: a (rows, cols)
     float32 CUDA tensor, allocated if None, or False for none.  Returns (out, variance).  One kernel launch, stream-ordered on ``stream``
     (default: torch's current stream), capturable when ``out`` and ``variance`` are given."""
-    rows, cols = int(rows), int(cols)
-    n = rows * cols
-    _tensor(color, "color", "float32", (rows, cols, 3))
-    _tensor(motion, "motion", "float32", (rows, cols, 2))
-    _tensor(history, "history", "int32", (n, _RECORD_WORDS))
-    cur, prev = _guides(current, n), _guides(previous, n)
-    with _on_stream(stream):
-        out = _out_tensor(out, (n, _RECORD_WORDS), "int32", color.device)
-        variance = None if variance is False else _out_tensor(variance, (rows, cols), "float32", color.device, name="variance")
-    p = _params(normal_min, position_max, alpha_min, max_length)
-    _capi.check(_capi.amd_lib().rt_temporal_accumulate(_p(color), _p(motion), C.byref(cur), C.byref(prev), C.byref(p), rows, cols, _p(history), _p(out),
-                                                       _p(variance), _stream_ptr(stream)))
-    return out, variance
+    return _accumulate(CUDA, color, motion, rows, cols, history, current, previous, _params(normal_min, position_max, alpha_min, max_length),
+                       out, variance, stream)
 
 
 class History:

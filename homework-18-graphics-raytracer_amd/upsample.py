@@ -24,21 +24,19 @@ from __future__ import annotations
 import ctypes as C
 from typing import NamedTuple
 
-import numpy as np
-
 from . import _capi
-from ._args import _new, _on_stream, _out_tensor, _p, _stream_ptr, _torch
+from ._args import _new, _on_stream, _torch
 from ._capi import Camera, Frame
+from ._forms import CUDA, DEMODULATE, NUMPY, denoise_guides
 from ._queries import cast_rays, trace_rays
 from ._world import Scene
-from .denoise import SIGMA_NORMAL, SIGMA_POSITION, _guides, _np_guides, _np_plane, _plane
+from .denoise import SIGMA_NORMAL, SIGMA_POSITION
 from .film import camera_rays_offset
 from .materials import SURFACE_WORDS, PrimarySurfaces, material_hits, primary_surfaces
 
 __all__ = ["guided", "guided_numpy", "Guides", "low_frame", "low_rays", "render_upsampled"]
 
 SCALE, RADIUS = 2, 1
-_DEMODULATE = 3  # RT_DENOISE_DEMODULATE
 
 
 class Guides(NamedTuple):
@@ -68,13 +66,27 @@ def low_frame(frame: Frame, scale: int = SCALE) -> Frame:
 
 def _params(scale, radius, sigma_normal, sigma_position, demodulate):
     return _capi.UpsampleParams(float(sigma_normal), float(sigma_position), int(scale), int(radius),
-                                _DEMODULATE if demodulate is True else int(demodulate))
+                                DEMODULATE if demodulate is True else int(demodulate))
 
 
 def _sizes(rows, cols, scale):
     rows, cols = int(rows), int(cols)
     s = int(scale) if int(scale) >= 1 else 1  # the entry point refuses a scale outside 2 .. 4; the planes are sized for it first
     return rows, cols, rows * cols, _low_size(rows, s) * _low_size(cols, s)
+
+
+def _guided(form, color_lo, rows, cols, low, full, scale, params, out=None, stream=None):
+    rows, cols, n, n_lo = _sizes(rows, cols, scale)
+    low, full = low or Guides(), full or Guides()
+    c, c_stride = form.required(color_lo, "color_lo", "f", n_lo, 3)
+    g_lo = denoise_guides(form, n_lo, low.normal, low.position, low.albedo, low.valid)
+    g_hi = denoise_guides(form, n, full.normal, full.position, full.albedo, full.valid)
+    o_lo, o_lo_stride = form.plane(low.object, "low.object", "i", n_lo, 1)
+    o_hi, o_hi_stride = form.plane(full.object, "full.object", "i", n, 1)
+    out = form.out(out, (rows, cols, 3), "float32", color_lo, stream=stream)
+    form.call("rt_upsample_guided", stream, c, c_stride, C.byref(g_lo), o_lo, o_lo_stride, C.byref(g_hi), o_hi, o_hi_stride, C.byref(params), rows, cols,
+              form.ptr(out))
+    return out
 
 
 def guided_numpy(color_lo, rows: int, cols: int, low: Guides = None, full: Guides = None, scale: int = SCALE, radius: int = RADIUS,
@@ -84,19 +96,7 @@ def guided_numpy(color_lo, rows: int, cols: int, low: Guides = None, full: Guide
     ``demodulate``: True for both directions, or the RT_DENOISE_DEMODULATE_IN (1) / _OUT (2) bits; it needs the albedo plane of the
     side it touches.  A sigma of ``math.inf`` switches its term off.  Returns a new (rows, cols, 3) float32 array; nothing given is
     written."""
-    rows, cols, n, n_lo = _sizes(rows, cols, scale)
-    low, full = low or Guides(), full or Guides()
-    c, c_stride = _np_plane(color_lo, "color_lo", "f", n_lo, 3)
-    if c is None:
-        raise ValueError("color_lo: expected a plane, not None")
-    g_lo, g_hi = _np_guides(n_lo, low.normal, low.position, low.albedo, low.valid), _np_guides(n, full.normal, full.position, full.albedo, full.valid)
-    o_lo, o_lo_stride = _np_plane(low.object, "low.object", "iu", n_lo, 1)
-    o_hi, o_hi_stride = _np_plane(full.object, "full.object", "iu", n, 1)
-    out = np.zeros((rows, cols, 3), dtype=np.float32)
-    p = _params(scale, radius, sigma_normal, sigma_position, demodulate)
-    _capi.check_host(_capi.host_lib().rt_upsample_guided_cpu(c, c_stride, C.byref(g_lo), o_lo, o_lo_stride, C.byref(g_hi), o_hi, o_hi_stride, C.byref(p),
-                                                             rows, cols, C.c_void_p(out.ctypes.data)))
-    return out
+    return _guided(NUMPY, color_lo, rows, cols, low, full, scale, _params(scale, radius, sigma_normal, sigma_position, demodulate))
 
 
 def guided(color_lo, rows: int, cols: int, low: Guides = None, full: Guides = None, scale: int = SCALE, radius: int = RADIUS,
@@ -106,20 +106,7 @@ def guided(color_lo, rows: int, cols: int, low: Guides = None, full: Guides = No
     those of ``materials.PrimarySurfaces`` (``Guides.of``).  Returns ``out``, a (rows, cols, 3) float32 CUDA tensor (allocated if None),
     which must be another tensor than ``color_lo``.  One kernel launch, stream-ordered on ``stream`` (default: torch's current stream),
     capturable when ``out`` is given."""
-    rows, cols, n, n_lo = _sizes(rows, cols, scale)
-    low, full = low or Guides(), full or Guides()
-    c, c_stride = _plane(color_lo, "color_lo", "float32", n_lo, 3)
-    if c is None:
-        raise ValueError("color_lo must be a float32 CUDA tensor, not None")
-    g_lo, g_hi = _guides(n_lo, low.normal, low.position, low.albedo, low.valid), _guides(n, full.normal, full.position, full.albedo, full.valid)
-    o_lo, o_lo_stride = _plane(low.object, "low.object", "int32", n_lo, 1)
-    o_hi, o_hi_stride = _plane(full.object, "full.object", "int32", n, 1)
-    with _on_stream(stream):
-        out = _out_tensor(out, (rows, cols, 3), "float32", color_lo.device)
-    p = _params(scale, radius, sigma_normal, sigma_position, demodulate)
-    _capi.check(_capi.amd_lib().rt_upsample_guided(c, c_stride, C.byref(g_lo), o_lo, o_lo_stride, C.byref(g_hi), o_hi, o_hi_stride, C.byref(p), rows, cols,
-                                                   _p(out), _stream_ptr(stream)))
-    return out
+    return _guided(CUDA, color_lo, rows, cols, low, full, scale, _params(scale, radius, sigma_normal, sigma_position, demodulate), out, stream)
 
 
 def _whole_blocks(frame, scale):

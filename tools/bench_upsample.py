@@ -48,7 +48,7 @@ import ctypes as C
 import torch
 
 import homework_18_graphics_raytracer_amd as rt
-from homework_18_graphics_raytracer_amd import _capi, upsample
+from homework_18_graphics_raytracer_amd import _capi, _forms, upsample
 from homework_18_graphics_raytracer_amd.materials import primary_surfaces
 
 torch.cuda.set_device(0)
@@ -67,7 +67,7 @@ torch.cuda.synchronize()
 
 lib = _capi.amd_lib()
 sp = C.c_void_p(stream.cuda_stream)
-pl = {name: upsample._guides(g[0].shape[0] * g[0].shape[1], g.normal, g.position, g.albedo, g.valid) for name, g in (("lo", g_lo), ("hi", g_hi))}
+pl = {name: _forms.denoise_guides(_forms.CUDA, g[0].shape[0] * g[0].shape[1], g.normal, g.position, g.albedo, g.valid) for name, g in (("lo", g_lo), ("hi", g_hi))}
 params = _capi.UpsampleParams(upsample.SIGMA_NORMAL, upsample.SIGMA_POSITION, scale, radius, 3)
 
 
