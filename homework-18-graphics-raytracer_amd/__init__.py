@@ -30,12 +30,13 @@ reference's host-side names on top of them:
     moving (a submodule)           no counterpart in the reference: the positions a scene keeps before an update, and where each hit's point was on them — the plane temporal wants for moving geometry
     rectify (a submodule)          no counterpart in the reference: the colour box of a pixel's neighbourhood, the accumulate that clamps the history into it, and the feedback of the filtered colour into the records
     adaptive (a submodule)         no counterpart in the reference: a sample budget per pixel from a variance estimate, the ragged pixel-major list of those samples, and the film queries on such a list
+    arealights (a submodule)       no counterpart in the reference: get_shade's light loop on lights that have a radius — sampled points on the light, the light queries on the displaced light, and a fold that averages the samples: soft shadows
     upsample (a submodule)         no counterpart in the reference: a low-resolution radiance carried onto full-resolution guide planes by a joint bilateral upsample
     post_process / write_to_file   src/main.rs:748-776
 
 PyTorch is used only for device memory, streams and torch.distributed.
 """
-from . import _capi, adaptive, denoise, diagnostics, film, materials, moving, rectify, svgf, temporal, upsample
+from . import _capi, adaptive, arealights, denoise, diagnostics, film, materials, moving, rectify, svgf, temporal, upsample
 from ._capi import Camera, Frame, Light, Material, RtError, SceneDesc, Sphere, Triangle, Vertex
 from ._world import DEFAULT_OBJ, ObjectProxy, Scene, World, reference_camera, reference_world
 from ._render import (Rng, focus_rays, options, render_distributed, render_distributed_numpy, render_whitted, render_whitted_numpy,

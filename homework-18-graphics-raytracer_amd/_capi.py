@@ -237,6 +237,7 @@ AMD_SYMBOLS = [
     "rt_select_records", "rt_cast_rays_indexed", "rt_level_split", "rt_level_join", "rt_level_close", "rt_level_fold", "rt_level_finish",
     "rt_tree_gate", "rt_tree_split", "rt_tree_spawn", "rt_tree_gather", "rt_tree_fold",
     "rt_light_rays", "rt_light_terms", "rt_light_fold",
+    "rt_area_light_rays", "rt_area_light_terms", "rt_area_light_fold",
     "rt_material_hits", "rt_material_hits_host", "rt_probe_surfaces", "rt_probe_surfaces_host",
     "rt_film_offsets", "rt_camera_rays_offset", "rt_camera_rays_offset_host", "rt_film_splat",
     "rt_sample_budget", "rt_sample_list_temp_bytes", "rt_sample_list", "rt_film_offsets_listed", "rt_camera_rays_listed", "rt_film_splat_listed",
@@ -264,6 +265,7 @@ HOST_SYMBOLS = [
     "rt_temporal_bounds_cpu", "rt_temporal_accumulate_bounded_cpu", "rt_temporal_feedback_cpu",
     "rt_sample_budget_cpu", "rt_sample_list_cpu", "rt_film_offsets_listed_cpu", "rt_camera_rays_listed_cpu", "rt_film_splat_listed_cpu",
     "rt_upsample_guided_cpu",
+    "rt_area_light_samples_cpu",
 ]
 
 _amd = None
@@ -334,6 +336,8 @@ def host_lib() -> C.CDLL:
                                                  C.c_float, C.c_void_p, C.c_void_p]
         lib.rt_upsample_guided_cpu.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(DenoiseGuides), C.c_void_p, C.c_uint32, C.POINTER(DenoiseGuides), C.c_void_p,
                                                C.c_uint32, C.POINTER(UpsampleParams), C.c_uint32, C.c_uint32, C.c_void_p]
+        lib.rt_area_light_samples_cpu.argtypes = [C.POINTER(Light), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32,
+                                                  C.c_uint32, C.c_void_p]
         lib.rt_host_last_error.restype = C.c_char_p
         _host = lib
     return _host
@@ -439,6 +443,12 @@ def amd_lib() -> C.CDLL:
         lib.rt_light_terms.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p]
         lib.rt_light_fold.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.rt_area_light_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
+                                           C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.rt_area_light_terms.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.rt_area_light_fold.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p]
         lib.rt_material_hits.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         lib.rt_material_hits_host.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         lib.rt_probe_surfaces.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]

@@ -26,6 +26,7 @@
 #include "../rt_motion.h"
 #include "../rt_adaptive.h"
 #include "../rt_upsample.h"
+#include "../rt_area_light.h"
 
 using rt::V3;
 
@@ -581,6 +582,32 @@ int rt_film_splat_host(uint32_t rows, uint32_t cols, const float *samples, const
     if (rows == 0u || cols == 0u) return RT_OK;
     if (!samples || !offsets || !sum || !weight) return fail(RT_ERR_INVALID_ARGUMENT, "rt_film_splat_host: null sample, offset, sum or weight pointer");
     rt::film_splat_cpu<rt::UniformLayout>({{samples, valid, offsets, (uint64_t)rows * cols, spp}, sum, weight, rows, cols, filter, radius});
+    return RT_OK;
+}
+
+/* ---- area-light queries: the sampler on the CPU (include/rt_amd.h "area-light queries"; the arithmetic is rt_area_light.h's, shared with the device) ---- */
+
+int rt_area_light_samples_cpu(const rt_light *lights, uint32_t light_first, uint32_t light_count, const float *radii, const uint32_t *ids, size_t n,
+                              uint32_t spp, uint32_t pattern, uint32_t seed, float *sample) {
+    const char *const who = "rt_area_light_samples_cpu: ";
+    const uint64_t pairs = (uint64_t)n * light_count;
+    if ((uint64_t)n >= (1ull << 32) || pairs >= (1ull << 32) || pairs * spp >= (1ull << 32))
+        return fail(RT_ERR_UNSUPPORTED, std::string(who) + "2^32 (sample, light, record) entries or more (pass the lights in several ranges, or fewer samples)");
+    if (n == 0 || light_count == 0) return RT_OK;
+    if (!lights || !radii || !sample) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + "null light, radius or sample pointer");
+    if (const char *bad = rt::area_light_limits(spp, true, pattern)) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + bad);
+    const uint32_t k = rt::film_strata(spp);
+    for (uint32_t s = 0; s < spp; ++s)
+        for (uint32_t l = 0; l < light_count; ++l) {
+            const rt_light &L = lights[(size_t)light_first + l];
+            float *const plane = sample + 3u * ((size_t)s * light_count + l) * n;
+            for (size_t i = 0; i < n; ++i) {
+                const V3 p = rt::area_light_sample(L, light_first + l, radii[l], pattern, k, ids ? ids[i] : (uint32_t)i, seed, s);
+                plane[3u * i] = p.x;
+                plane[3u * i + 1u] = p.y;
+                plane[3u * i + 2u] = p.z;
+            }
+        }
     return RT_OK;
 }
 

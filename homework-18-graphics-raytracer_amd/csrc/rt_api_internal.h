@@ -17,6 +17,8 @@
  *                      rt_level_*
  *   rt_tree_query.hip  the tree loop's rt_tree_*: kernels and entry points in one unit
  *   rt_light_query.hip the light queries' rt_light_*: kernels and entry points in one unit
+ *   rt_area_light_query.hip the area-light queries' rt_area_light_*: kernels and entry points in one unit (the sampler is rt_area_light.h's, shared
+ *                      with librt_host.so; the per-hit record rt_light_record.h's, shared with rt_light_query.hip)
  *   rt_refract_query.hip the refraction queries' rt_refract_enter / rt_refract_step: kernels and entry points in one unit
  *   rt_scene_update.hip the scene updates' rt_scene_update_*: kernels and entry points in one unit
  *   rt_motion_query.hip the motion queries' rt_scene_keep_positions / rt_scene_positions_kept / rt_previous_positions and its _host form: kernels and entry points in one unit

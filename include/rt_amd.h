@@ -379,6 +379,76 @@ int rt_light_terms(const rt_scene *scene, const rt_hit *d_hits, const rt_ray *d_
 int rt_light_fold(const rt_scene *scene, const rt_hit *d_hits, size_t n, uint32_t light_count, const unsigned char *d_lit, const float *d_diffuse,
                   const float *d_specular, float *d_rgb, void *hip_stream);
 
+/* ---- area-light queries: soft shadows from sampled lights on caller-supplied hits ------------------------------
+
+ * The light queries above on lights that have a size.  Every light of the reference is a point, so every shadow has a hard edge; here
+ * a light l with radius rad is a sphere around its origin (around the tip of its direction, for a directional light without origin),
+ * each (record, light) pair is evaluated spp times, each time with the light displaced to a point chosen on that sphere, and the fold
+ * averages a light's samples before it weights and sums the lights — the noisy input the film, temporal, variance-guided and
+ * upsampling queries below are there to clean.  The sequence, per range of lights,
+ *     rt_area_light_rays -> rt_select_records(d_asks) -> rt_cast_rays_indexed(d_shadow_rays -> d_shadow_hits) -> rt_area_light_terms
+ *         -> rt_area_light_fold
+ * with every radius 0 and spp 1 is the light queries' sequence bit for bit, and therefore rt_shade_hits (INTEGRATION.md writes it out;
+ * DESIGN.md §3.29 says why).  With a radius above 0 every value is what rt_light_rays / rt_light_terms give for the scene whose light
+ * has been moved to the sample; the same arguments give the same bits on every run.
+ *
+ * The sample.  (record id, absolute light index l, sample number s in 0 .. spp - 1) name a point on the unit sphere, in single f32
+ * operations in this order, none fused (csrc/rt_area_light.h, shared by both libraries; film_mix and film_offset are the film
+ * queries', rtdm::sinf / cosf / f_sqrt csrc/rt_detmath.h's):
+ *     seed_l = film_mix(seed ^ (0x9e3779b9u * (l + 1u)))
+ *     u_a    = film_offset(pattern, k, id, seed_l, s, a) + 0.5f        a = 0, 1;  k = the side of a stratified pattern, spp = k * k
+ *     z      = 1.0f - 2.0f * u_0
+ *     r      = sqrt(max(1.0f - z * z, 0.0f))                           correctly rounded
+ *     phi    = 6.2831855f * u_1
+ *     offset = (r * cosf(phi), r * sinf(phi), z)
+ * which is uniform on the sphere.  pattern is RT_FILM_UNIFORM or RT_FILM_STRATIFIED (spp = k * k, 1 <= k <= 8: one sample per cell of
+ * the k x k grid over (u_0, u_1)); RT_FILM_CENTER is refused; 1 <= spp <= 64.  The displaced light of radius rad:
+ *   - !(rad > 0) — zero, negative, NaN: the light exactly as stored; nothing is added to any of its words, and the sample is the
+ *     stored origin (the stored direction, for a directional light without origin);
+ *   - a light with an origin (spot, point, directional with has_origin): origin' = origin + offset * rad, per component the product,
+ *     then the add; every other field unchanged;
+ *   - a directional light without origin: direction' = normalize(direction + offset * rad).
+ *
+ * Per-entry arrays are sample-major, then light-major: entry k = (s * light_count + (l - light_first)) * n + i,
+ * spp * light_count * n entries — one (sample, light) plane is contiguous, and the whole array is one batch of records for
+ * rt_select_records and rt_cast_rays_indexed.  The record rules are those of the light queries.  Every pointer is a device pointer;
+ * every call is stream-ordered and asynchronous on hip_stream (NULL = default stream), is one kernel with one record per lane,
+ * allocates nothing, uses no workspace and may be captured into a HIP graph at once.
+ * Checked before any device work, in this order: n >= 2^32, n * light_count >= 2^32 or n * light_count * spp >= 2^32 is
+ * RT_ERR_UNSUPPORTED; a null scene RT_ERR_INVALID_ARGUMENT; n == 0 or light_count == 0 is RT_OK and launches nothing; a null required
+ * pointer RT_ERR_INVALID_ARGUMENT; spp outside 1 .. 64, RT_FILM_CENTER, an unknown pattern or a stratified spp that is no square
+ * RT_ERR_INVALID_ARGUMENT with a message that names the limit; only then is the scene read: light_first + light_count > n_lights.
+ * Not covered: _host forms of these three (they sit between device calls; the sampler alone has a CPU form, rt_area_light_samples_cpu
+ * of include/rt_host.h); rt_multi_* forms; area lights inside rt_render_whitted; importance sampling towards the hit or an emitter
+ * that is no sphere — for those a caller writes d_sample itself. */
+
+/* rt_light_rays on the displaced lights.  d_radii: light_count floats, the radius of light light_first + j at j.  d_ids: n u32, the
+ * record id of the hash — the global pixel index, say, so that a pixel draws the same points wherever it lies in the batch — or NULL
+ * for id = (uint32_t)i.
+ *   d_sample[3k ..]      the displaced origin, or the displaced direction for a directional light without origin; written for every
+ *                        entry, whether the light asks or not, "no hit" records included
+ *   d_asks[k], d_shadow_rays[k]   what rt_light_rays gives for the displaced light: the ray starts at the hit and runs along
+ *                        -direction of the displaced light, face Back, exclusion { hit.kind, hit.index, Back }; all-zero words where
+ *                        the light does not ask */
+int rt_area_light_rays(const rt_scene *scene, const rt_hit *d_hits, const rt_ray *d_incoming, size_t n, uint32_t light_first, uint32_t light_count,
+                       const float *d_radii, const uint32_t *d_ids, uint32_t spp, uint32_t pattern, uint32_t seed, rt_ray *d_shadow_rays,
+                       unsigned char *d_asks, float *d_sample, void *hip_stream);
+/* rt_light_terms with the light replaced by a copy whose origin — direction, for a directional light without origin — is d_sample[3k ..]:
+ * the occlusion distance is measured to that origin, and approximate_into_directional, get_diffuse and get_specular see that light.
+ * It takes no radii and no seed: d_sample is the caller's, and may hold points of its own (a quad light, another sampling scheme). */
+int rt_area_light_terms(const rt_scene *scene, const rt_hit *d_hits, const rt_ray *d_incoming, size_t n, uint32_t light_first, uint32_t light_count,
+                        uint32_t spp, const unsigned char *d_asks, const float *d_sample, const rt_hit *d_shadow_hits, unsigned char *d_lit,
+                        float *d_diffuse, float *d_specular, void *hip_stream);
+/* Per record, for l = 0 .. light_count - 1 in order: over the samples s = 0 .. spp - 1 in order where d_lit[k], acc starts as the first
+ * lit sample's term and every later lit term is added to it, for diffuse and specular separately; a light without a lit sample is
+ * skipped, as rt_light_fold skips an unlit light; otherwise D = acc_d / (float)spp, S = acc_s / (float)spp and
+ *     rgb = (rgb + D * (1 - shiness)) + S * shiness                     per channel, in place on d_rgb[3i ..]
+ * Every operation rounds to f32 and none is fused.  The call ADDS, as rt_light_fold does; "no hit" records are not written.
+ *   d_visibility         NULL, or light_count * n floats: entry l * n + i is (float)(lit samples) / (float)spp, 0 for a "no hit"
+ *                        record — the shadow mask of light l, for a denoiser */
+int rt_area_light_fold(const rt_scene *scene, const rt_hit *d_hits, size_t n, uint32_t light_count, uint32_t spp, const unsigned char *d_lit,
+                       const float *d_diffuse, const float *d_specular, float *d_rgb, float *d_visibility, void *hip_stream);
+
 /* ---- material queries: approx, adjust_normal and the Phong terms on caller-supplied hits ------------------------------
 
  * The material at a hit, which every render and query kernel evaluates between two casts and none of the blocks above returns:

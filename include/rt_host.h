@@ -178,6 +178,16 @@ int rt_svgf_variance_cpu(const rt_temporal_pixel *history, const rt_denoise_guid
 int rt_svgf_atrous_cpu(const float *color, uint32_t color_stride, const float *variance, const rt_denoise_guides *guides,
                        const rt_svgf_atrous_params *params, uint32_t rows, uint32_t cols, float *out, float *variance_out, void *temp);
 
+/* The area-light queries' sampler on the CPU (include/rt_amd.h "area-light queries" states every operation and the order; the
+ * arithmetic is csrc/rt_area_light.h's, shared with the device): sample[3k ..] of rt_area_light_rays, bit for bit, for host arrays and
+ * no device.  lights: the scene's lights (light_first + light_count of them are read); radii: light_count floats; ids: n u32 or NULL for
+ * id = i; sample: spp * light_count * n * 3 floats, entry k = (s * light_count + (l - light_first)) * n + i.  The casts and the Phong
+ * terms have no CPU form: their oracle is the light queries on a scene whose lights were moved to these samples.  The limits are
+ * rt_area_light_rays' with the same texts: the three counts (RT_ERR_UNSUPPORTED), n == 0 or light_count == 0 is RT_OK, a null lights,
+ * radii or sample pointer, then spp and pattern.  A failure returns a negative rt_status and sets rt_host_last_error(). */
+int rt_area_light_samples_cpu(const rt_light *lights, uint32_t light_first, uint32_t light_count, const float *radii, const uint32_t *ids, size_t n,
+                              uint32_t spp, uint32_t pattern, uint32_t seed, float *sample);
+
 /* RGB8 PNG, written to "<path>.tmp" then renamed over path. */
 int rt_write_png(const char *path, const uint8_t *rgb8, uint32_t width, uint32_t height);
 
