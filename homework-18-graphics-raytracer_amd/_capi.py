@@ -228,7 +228,7 @@ class UpsampleParams(C.Structure):
 AMD_SYMBOLS = [
     "rt_abi_version", "rt_last_error", "rt_device_count", "rt_set_device", "rt_frame_rows", "rt_frame_pixels",
     "rt_scene_create", "rt_scene_destroy", "rt_render_whitted", "rt_render_whitted_host", "rt_set_option", "rt_set_variant",
-    "rt_get_variant", "rt_set_wavefront_budget", "rt_set_distributed_split", "rt_profile_enable", "rt_profile_read", "rt_profile_read_distributed", "rt_math_eval_host", "rt_math_eval_device", "rt_math_eval64_host", "rt_math_eval64_device", "rt_scene_describe_nodes", "rt_rng_state_words", "rt_rng_create",
+    "rt_get_variant", "rt_set_wavefront_budget", "rt_set_distributed_split", "rt_profile_enable", "rt_profile_read", "rt_profile_read_distributed", "rt_math_eval_host", "rt_math_eval_device", "rt_math_eval64_host", "rt_math_eval64_device", "rt_scene_describe_nodes", "rt_scene_describe_filters", "rt_rng_state_words", "rt_rng_create",
     "rt_rng_destroy", "rt_rng_download", "rt_render_distributed", "rt_render_distributed_host", "rt_multi_create", "rt_multi_destroy", "rt_multi_render_whitted_host", "rt_multi_render_distributed_host", "rt_multi_render_whitted", "rt_multi_render_distributed", "rt_post_process_device", "rt_post_keys_device", "rt_post_hist_device", "rt_post_pick_device", "rt_post_scale_device", "rt_post_release", "rt_encode_srgb8_device", "rt_accumulate_device", "rt_accumulator_resolve_device",
     "rt_cast_rays", "rt_cast_rays_host", "rt_camera_rays", "rt_trace_rays", "rt_trace_rays_host",
     "rt_rng_create_seeded", "rt_rng_upload", "rt_trace_rays_distributed", "rt_trace_rays_distributed_host", "rt_focus_rays",
@@ -528,6 +528,7 @@ def amd_lib() -> C.CDLL:
                                            C.c_void_p, C.c_size_t, C.c_void_p]
         lib.rt_order_triangles_host.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.c_void_p, C.c_void_p]
         lib.rt_scene_describe_nodes.argtypes = [C.POINTER(SceneDesc), C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32)]
+        lib.rt_scene_describe_filters.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
         lib.rt_diag_scene_nodes.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
         lib.rt_diag_pwf_plan.argtypes = [C.c_void_p, C.POINTER(Frame), C.c_void_p, C.c_void_p]
         lib.rt_diag_pwf_plan_rays.argtypes = [C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p, C.c_void_p]

@@ -429,7 +429,7 @@ int rt_scene_create(const rt_scene_desc *desc, rt_scene **out_scene) {
     sc->ks.n_segments = (uint32_t)segments.size();
     sc->ks.heads = reinterpret_cast<const rt::DevTriHead *>(base + off_heads);
     sc->ks.light_aux = reinterpret_cast<const rt::LightAux *>(base + off_light_aux);
-    sc->ks.filter_origin2 = (float)(16.0 * scene_extent * scene_extent); /* |origin| <= 4 x extent */
+    sc->ks.filter_origin2 = filter_origin2_of(scene_extent); /* |origin| <= 4 x extent */
     sc->ks.bfs_nodes = reinterpret_cast<const rt::DevSegment *>(base + off_bfs_nodes);
     sc->ks.bfs_soa = reinterpret_cast<const float4 *>(base + off_bfs_soa);
     sc->ks.bfs_top = bfs_top;

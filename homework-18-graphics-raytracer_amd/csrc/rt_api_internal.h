@@ -361,6 +361,8 @@ struct SceneLayout {
     double scene_extent = 0.0;
 };
 RT_API_HIDDEN int layout_scene(const rt_scene_desc *desc, SceneLayout &layout);
+/* KernelScene::filter_origin2 of a scene of that extent: origins up to 4 x extent from the centre of coordinates use the rejections */
+inline float filter_origin2_of(double scene_extent) { return (float)(16.0 * scene_extent * scene_extent); }
 
 /* The hit queries' kernels (rt_hit_query.hip): get_shade / get_refract / get_reflect on n ABI records, in bands of at most
  * band_records per launch (a multiple of 64, RT_HITQ_BAND at most).  wave_uniform: the casts go through cast_asm instead of cast_pairs

@@ -389,4 +389,24 @@ int rt_scene_describe_nodes(const rt_scene_desc *desc, uint32_t *out_words, uint
     return RT_OK;
 }
 
+/* Diagnostics: what the exactness-preserving shortcuts of the cast and the light loop would be given for `desc` — the layout's
+ * and light_aux_of's own values, without touching a device.  Every output may be null. */
+int rt_scene_describe_filters(const rt_scene_desc *desc, float *tri4, float *sphere1, float *light2, float *filter_origin2) {
+    if (!desc) return fail(RT_ERR_INVALID_ARGUMENT, "rt_scene_describe_filters: null argument");
+    SceneLayout layout;
+    const int rc = layout_scene(desc, layout);
+    if (rc != RT_OK) return rc;
+    for (size_t i = 0; tri4 && i < layout.tris.size(); ++i) {
+        const rt::DevTri &t = layout.tris[i];
+        tri4[4u * i] = t.bcx; tri4[4u * i + 1u] = t.bcy; tri4[4u * i + 2u] = t.bcz; tri4[4u * i + 3u] = t.bq;
+    }
+    for (size_t i = 0; sphere1 && i < layout.spheres.size(); ++i) sphere1[i] = layout.spheres[i].q_miss;
+    for (uint32_t i = 0; light2 && i < desc->n_lights; ++i) {
+        const rt::LightAux aux = light_aux_of(desc->lights[i]);
+        light2[2u * i] = aux.cos_in; light2[2u * i + 1u] = aux.cos_out;
+    }
+    if (filter_origin2) *filter_origin2 = filter_origin2_of(layout.scene_extent);
+    return RT_OK;
+}
+
 } /* extern "C" */

@@ -1887,6 +1887,15 @@ int rt_math_eval64_device(int op, const double *h_a, const double *h_b, double *
  * never pair-wise), 0.  Writes at most cap_nodes nodes, always reports the count.  For tests of the builder's invariants. */
 int rt_scene_describe_nodes(const rt_scene_desc *desc, uint32_t *out_words, uint32_t cap_nodes, uint32_t *n_nodes);
 
+/* What the shortcuts that skip work of a certain outcome would be given for `desc`, computed on the host without touching a device by
+ * the code rt_scene_create runs: per triangle the centre and the padded squared radius of its bounding sphere (tri4: bcx, bcy, bcz, bq;
+ * bq = +inf: no rejection for this triangle), per sphere the squared distance above which a ray misses before the root is taken
+ * (sphere1: q_miss; +inf: never), per light the cosines outside which a spot light's cone is decided without the arc cosine (light2:
+ * cos_in, cos_out; +inf and -inf: never), and the squared origin distance up to which a ray uses the bounding-sphere rejections at all
+ * (*filter_origin2).  Each array holds one entry per primitive of `desc`; any of the four outputs may be NULL.  For tests that aim at
+ * those margins. */
+int rt_scene_describe_filters(const rt_scene_desc *desc, float *tri4, float *sphere1, float *light2, float *filter_origin2);
+
 /* The node records of a scene as they stand on the device, copied to host memory with a blocking copy: `which` 0 the pre-order
  * array (csrc/rt_device_scene.h DevSegment, 40 words per node), 1 the same records in level order (an inner node's first / skip_to
  * name its children there), 2 the 16-byte pieces of the breadth-first walk (per node in level order: first, count, n_normals, r2_hi;

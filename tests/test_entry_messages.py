@@ -32,6 +32,7 @@ SIGNATURES = {
     "rt_profile_read": [("ms", C.pointer(C.c_double())), ("launches", C.pointer(C.c_uint()))],
     "rt_profile_read_distributed": [("ms", P), ("launches", P)],
     "rt_scene_create": [("desc", C.pointer(_capi.SceneDesc())), ("out", OUT)],
+    "rt_scene_describe_filters": [("desc", C.pointer(_capi.SceneDesc())), ("tri4", P), ("sphere1", P), ("light2", P), ("origin2", C.pointer(C.c_float()))],
     "rt_diag_scene_nodes": [("scene", SCENE), ("which", 0), ("words", P), ("cap", 4), ("n_words", C.pointer(C.c_size_t()))],
     "rt_diag_pwf_plan": [("scene", SCENE), ("frame", FRAME), ("stream", None), ("words", P)],
     "rt_diag_pwf_plan_rays": [("scene", SCENE), ("n", 2), ("depth", 3), ("stream", None), ("words", P)],
@@ -248,6 +249,7 @@ CASES = [
     ("rt_profile_read_distributed", _null("ms"), INVALID, "rt_profile_read_distributed: null argument"),
     ("rt_scene_create", _null("desc"), INVALID, "rt_scene_create: null argument"),
     ("rt_scene_create", _null("out"), INVALID, "rt_scene_create: null argument"),
+    ("rt_scene_describe_filters", _null("desc"), INVALID, "rt_scene_describe_filters: null argument"),
     ("rt_diag_scene_nodes", _null("scene"), INVALID, "rt_diag_scene_nodes: null argument"),
     ("rt_diag_pwf_plan", _null("scene"), INVALID, "rt_diag_pwf_plan: null argument"),
     ("rt_diag_pwf_plan", _null("words"), INVALID, "rt_diag_pwf_plan: null argument"),
