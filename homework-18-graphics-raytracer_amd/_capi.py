@@ -225,6 +225,11 @@ class UpsampleParams(C.Structure):
     _fields_ = [("sigma_normal", C.c_float), ("sigma_position", C.c_float), ("scale", C.c_uint32), ("radius", C.c_uint32), ("flags", C.c_uint32)]
 
 
+class BloomParams(C.Structure):
+    """rt_bloom_params"""
+    _fields_ = [("threshold", C.c_float), ("knee", C.c_float), ("intensity", C.c_float), ("n_levels", C.c_uint32)]
+
+
 AMD_SYMBOLS = [
     "rt_abi_version", "rt_last_error", "rt_device_count", "rt_set_device", "rt_frame_rows", "rt_frame_pixels",
     "rt_scene_create", "rt_scene_destroy", "rt_render_whitted", "rt_render_whitted_host", "rt_set_option", "rt_set_variant",
@@ -247,6 +252,7 @@ AMD_SYMBOLS = [
     "rt_temporal_bounds_host", "rt_temporal_accumulate_bounded_host", "rt_temporal_feedback_host",
     "rt_svgf_variance", "rt_svgf_temp_bytes", "rt_svgf_atrous", "rt_svgf_variance_host", "rt_svgf_atrous_host",
     "rt_upsample_guided", "rt_upsample_guided_host",
+    "rt_bloom_temp_bytes", "rt_bloom", "rt_bloom_host",
     "rt_refract_enter", "rt_refract_step",
     "rt_scene_update_vertices", "rt_scene_update_spheres", "rt_scene_update_lights", "rt_scene_update_materials",
     "rt_scene_keep_positions", "rt_scene_positions_kept", "rt_previous_positions", "rt_previous_positions_host",
@@ -265,6 +271,7 @@ HOST_SYMBOLS = [
     "rt_temporal_bounds_cpu", "rt_temporal_accumulate_bounded_cpu", "rt_temporal_feedback_cpu",
     "rt_sample_budget_cpu", "rt_sample_list_cpu", "rt_film_offsets_listed_cpu", "rt_camera_rays_listed_cpu", "rt_film_splat_listed_cpu",
     "rt_upsample_guided_cpu",
+    "rt_bloom_cpu",
     "rt_area_light_samples_cpu",
 ]
 
@@ -336,6 +343,7 @@ def host_lib() -> C.CDLL:
                                                  C.c_float, C.c_void_p, C.c_void_p]
         lib.rt_upsample_guided_cpu.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(DenoiseGuides), C.c_void_p, C.c_uint32, C.POINTER(DenoiseGuides), C.c_void_p,
                                                C.c_uint32, C.POINTER(UpsampleParams), C.c_uint32, C.c_uint32, C.c_void_p]
+        lib.rt_bloom_cpu.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(BloomParams), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
         lib.rt_area_light_samples_cpu.argtypes = [C.POINTER(Light), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32,
                                                   C.c_uint32, C.c_void_p]
         lib.rt_host_last_error.restype = C.c_char_p
@@ -492,6 +500,10 @@ def amd_lib() -> C.CDLL:
                                            C.c_uint32, C.POINTER(UpsampleParams), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
         lib.rt_upsample_guided_host.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(DenoiseGuides), C.c_void_p, C.c_uint32, C.POINTER(DenoiseGuides), C.c_void_p,
                                                 C.c_uint32, C.POINTER(UpsampleParams), C.c_uint32, C.c_uint32, C.c_void_p]
+        lib.rt_bloom_temp_bytes.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
+        lib.rt_bloom_temp_bytes.restype = C.c_size_t
+        lib.rt_bloom.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(BloomParams), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.rt_bloom_host.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(BloomParams), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
         lib.rt_refract_enter.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p]
         lib.rt_refract_step.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

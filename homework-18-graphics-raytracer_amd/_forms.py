@@ -10,7 +10,7 @@ only that form has (``out``, ``temp``, ``stream``).
                                                 record type (label, numpy dtype, device dtype, words): numpy arrays are made
                                                 contiguous, tensors must be (rows, cols[, width]) or (rows * cols, words)
     out(given, shape, dtype, like, name, stream, record)
-                                                an output: a new zeroed array, or ``given`` (checked) or a new tensor on ``like``'s
+                                                an output: ``given`` (checked), or a new zeroed array, or a new tensor on ``like``'s
                                                 device made with ``stream`` current
     ptr(x)                                      the pointer of what ``out`` returned, None for None
     call(entry, stream, *args)                  the library call and its status check; the device form appends the stream
@@ -58,7 +58,12 @@ class _Numpy:
         return np.ascontiguousarray(a).ctypes.data_as(C.c_void_p)  # the pointer object keeps the array alive
 
     def out(self, given, shape, dtype, like=None, name="out", stream=None, record=None):
-        return np.zeros(shape, dtype=dtype if record is None else record[1])
+        dtype = np.dtype(dtype if record is None else record[1])
+        if given is None:
+            return np.zeros(shape, dtype=dtype)
+        if not (isinstance(given, np.ndarray) and given.dtype == dtype and given.shape == tuple(shape) and given.flags.c_contiguous and given.flags.writeable):
+            raise ValueError(f"{name}: expected a writable C-contiguous {dtype} array of shape {tuple(shape)}")
+        return given
 
     def ptr(self, a):
         return None if a is None else C.c_void_p(a.ctypes.data)

@@ -26,6 +26,7 @@
 #include "../rt_motion.h"
 #include "../rt_adaptive.h"
 #include "../rt_upsample.h"
+#include "../rt_bloom.h"
 #include "../rt_area_light.h"
 
 using rt::V3;
@@ -737,6 +738,15 @@ int rt_upsample_guided_cpu(const float *color_lo, uint32_t color_stride, const r
     return cpu_query("rt_upsample_guided_cpu",
                      rt::UpsampleArgs{color_lo, color_stride, low, object_lo, object_lo_stride, full, object_full, object_full_stride, params, rows, cols, out},
                      each_call);
+}
+
+/* ---- bloom queries: the CPU definition (include/rt_amd.h "bloom queries"; the arithmetic and the order of a call's steps are rt_bloom.h's, shared with the device) ---- */
+
+int rt_bloom_cpu(const float *color, uint32_t color_stride, const rt_bloom_params *params, uint32_t rows, uint32_t cols, float *temp, float *out) {
+    return cpu_query("rt_bloom_cpu", rt::BloomArgs{color, color_stride, params, rows, cols, temp, out}, [](const rt::BloomArgs &a) {
+        const auto step = [](const auto &op) { return each(op), true; };
+        rt::bloom_steps(a, step, step);
+    });
 }
 
 /* ---- variance-guided filter queries: the CPU definition (include/rt_amd.h "variance-guided filter queries"; the arithmetic is rt_svgf.h's, shared with the device) ---- */

@@ -30,6 +30,7 @@
  *   rt_rectify_query.hip the history rectification queries' rt_temporal_bounds / rt_temporal_accumulate_bounded / rt_temporal_feedback and their _host forms: kernels and entry points in one unit
  *   rt_adaptive_query.hip the adaptive sampling queries' rt_sample_budget / rt_sample_list / rt_film_offsets_listed / rt_camera_rays_listed / rt_film_splat_listed: kernels and entry points in one unit
  *   rt_upsample_query.hip the guided upsampling queries' rt_upsample_guided and its _host form: kernels and entry points in one unit
+ *   rt_bloom_query.hip   the bloom queries' rt_bloom / rt_bloom_host / rt_bloom_temp_bytes: kernels and entry points in one unit
  *   rt_svgf_query.hip    the variance-guided filter queries' rt_svgf_variance / rt_svgf_atrous, their _host forms and rt_svgf_temp_bytes: kernels and entry points in one unit
  * The image-side units from rt_denoise_query.hip on state each query's arguments once, as the struct of rt_query_args.h in the query's
  * shared header; their device and _host entry points are device_query / host_query below, one statement each (rt_sample_list,

@@ -144,7 +144,9 @@ struct KernelQueues {
     X(OPT_DIAG_ADAPTIVE_MAX_GROUPS,                                                                                                            \
       "RT_AMD_DIAG_ADAPTIVE_MAX_GROUPS") /* test hook: the kernels of the adaptive sampling queries (rt_sample_budget, rt_sample_list's totals and expansion, rt_film_offsets_listed, rt_camera_rays_listed, rt_film_splat_listed) launch at most this many workgroups (default and most: 2^16), the rest taken grid-stride */ \
     X(OPT_UPSAMPLE_FORM, /* rt_upsample_guided: 0 the plain gather from global memory, 1 the tiled gather from LDS (same bits; DESIGN.md 3.28 has the A/B) */ "RT_AMD_UPSAMPLE_FORM") \
-    X(OPT_DIAG_UPSAMPLE_MAX_GROUPS, /* test hook: rt_upsample_guided launches at most this many workgroups (default and most: 2^16), the rest of the image taken grid-stride */ "RT_AMD_DIAG_UPSAMPLE_MAX_GROUPS")
+    X(OPT_DIAG_UPSAMPLE_MAX_GROUPS, /* test hook: rt_upsample_guided launches at most this many workgroups (default and most: 2^16), the rest of the image taken grid-stride */ "RT_AMD_DIAG_UPSAMPLE_MAX_GROUPS") \
+    X(OPT_BLOOM_FORM, /* rt_bloom: 0 every step the plain gather from global memory, 1 the down steps the tiled gather from LDS (same bits; DESIGN.md 3.30 has the A/B) */ "RT_AMD_BLOOM_FORM") \
+    X(OPT_DIAG_BLOOM_MAX_GROUPS, /* test hook: a step of rt_bloom launches at most this many workgroups (default and most: 2^16), the rest of the level taken grid-stride */ "RT_AMD_DIAG_BLOOM_MAX_GROUPS")
 #define RT_OPTION_ID(id, name) id,
 enum Option : int { RT_OPTIONS(RT_OPTION_ID) OPT_COUNT };
 #undef RT_OPTION_ID

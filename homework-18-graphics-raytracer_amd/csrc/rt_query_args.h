@@ -1,7 +1,7 @@
 /*
  * rt_query_args.h — how an image-side query states its arguments ONCE for its three entry points: the device form (rt_X), the _host form
  * (a round trip through the device) and the _cpu form (librt_host.so).  Beside its arithmetic, in the header both libraries share
- * (rt_denoise.h, rt_temporal.h, rt_svgf.h, rt_rectify.h, rt_upsample.h, rt_adaptive.h), a query has a plain aggregate of the entry
+ * (rt_denoise.h, rt_temporal.h, rt_svgf.h, rt_rectify.h, rt_upsample.h, rt_adaptive.h, rt_bloom.h), a query has a plain aggregate of the entry
  * point's arguments in interface order, without the stream, with these members:
  *     limits(form, &status)   THE argument check, in the order include/rt_amd.h states: the text of the first refusal and how it is
  *                             reported, or null.  What depends on the form is written as a question to it (below).

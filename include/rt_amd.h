@@ -1134,6 +1134,77 @@ int rt_accumulate_device(const float *d_samples, const unsigned char *d_valid, u
                          float *d_weight, void *hip_stream);
 int rt_accumulator_resolve_device(const float *d_sum, const float *d_weight, size_t n_pixels, float *d_rgb, void *hip_stream);
 
+/* ---- bloom queries: the highlight bloom post_process leaves as a TODO ------------------------------
+
+ * The reference's post_process ends with "TODO: highlight bloom effect".  rt_post_process_device divides by the 99th-percentile luma, so
+ * about one pixel in a hundred ends above 1.0 and rt_encode_srgb8_device clips it flat: lamp reflections and specular peaks become hard
+ * white blobs.  Bloom spreads what lies above a threshold over its surroundings before the encode, the one step between the two:
+ *     ... -> rt_post_process_device -> rt_bloom -> rt_encode_srgb8_device
+ * The reference has no counterpart; the definition below is the contract.  It is written once (csrc/rt_bloom.h) and compiled into both
+ * libraries without contraction, so the device form (either kernel form, any launch geometry), the _host form and rt_bloom_cpu
+ * (librt_host.so, include/rt_host.h) return the same bits.  The device call is 2 L stream-ordered kernel launches on hip_stream and
+ * nothing else — L down launches (the first fused with the bright pass), L - 1 up-and-add launches, one composite —, allocates nothing,
+ * visits the host for nothing and may be captured into a HIP graph at once.  Every output word is written by one thread: no atomics,
+ * nothing depends on the launch.
+ *
+ * color is a plane as in the denoise queries: a base pointer and a pixel stride in 4-byte WORDS (>= 3), pixel i = r * cols + c, so the
+ * colour inside rt_temporal_pixel records (stride 8) is read where it lies.  out: 3 f32 per pixel, compact; it may be color itself when
+ * color_stride == 3 (the composite reads a pixel's colour only at that pixel).  temp: opaque scratch of rt_bloom_temp_bytes bytes.
+ * Every operation is a single f32 operation in the order written, none fused; the divide is correctly rounded.  Level sizes:
+ * rows_0 = rows, rows_j = ceil(rows_{j-1} / 2), the same for columns; a level may be 1 x 1, and the level after it is 1 x 1 again.
+ * L = n_levels; clamp(i, n) puts an index into 0 .. n - 1.
+ *   1. bright pass: at a level-0 pixel with colour c,  l = (w0 * c_r + w1 * c_g) + w2 * c_b  with post_process's luma row (computed on the
+ *      host, as rt_post_process_device gets it).  If any channel has c - c != 0 (not finite), or !(l > 0):  B = (+0, +0, +0) — the
+ *      reference's is_normal filters keep such pixels out of its sums; here they are kept from spreading.  Otherwise  s = l - threshold;
+ *      with knee > 0:  t = fminf(fmaxf(s + knee, 0), 2 * knee);   q = (t * t) / (4 * knee);   m = fmaxf(s, q);   with knee == 0:  m = s.
+ *      If !(m > 0):  B = +0;  otherwise  B_k = c_k * (m / l).
+ *   2. down: for j = 1 .. L, D_j(r, c) from the source S = B (j = 1) or D_{j-1}: source rows clamp(2 r - 1 + kr), columns
+ *      clamp(2 c - 1 + kc), kr, kc = 0 .. 3;  per source row  h_kr = (s_0 + 3 * s_1) + (3 * s_2 + s_3);   then
+ *      D = ((h_0 + 3 * h_1) + (3 * h_2 + h_3)) * (1 / 64),  per channel: the [1 3 3 1] / 8 tent centred on the 2 x 2 block with replicated
+ *      edges, so a constant stays a constant at every border and every odd size.
+ *   3. up and add: U_L = D_L; for j = L - 1 .. 1,  U_j(r, c) = D_j(r, c) + up(U_{j+1})(r, c),  written over D_j in place, where
+ *      up(X)(r, c):  near_r = r >> 1;   far_r = clamp(near_r + (r odd ? 1 : -1));  the same for columns;
+ *      h_near = 3 * X(near_r, near_c) + X(near_r, far_c);   h_far likewise on row far_r;   up = (3 * h_near + h_far) * (1 / 16).
+ *   4. composite:  g = intensity / (float)L, computed once on the host;   out_k = c_k + g * up(U_1)_k.  A colour that is not finite stays
+ *      whatever c_k + ... gives; it glows nowhere else (step 1).
+ *   5. temp holds D_1 .. D_L compact, one after the other: rt_bloom_temp_bytes = sum over j = 1 .. L of rows_j * cols_j * 12, and 0 for
+ *      an n_levels that is refused.
+ * Consequences: threshold = +inf or intensity = 0 returns the colour's values; the tap sums are mirror-symmetric, so on a size that is
+ * a multiple of 2^L both ways a mirrored image gives the mirrored result, bit for bit.
+ *
+ * Checked before any device work, all RT_ERR_INVALID_ARGUMENT with a message that names the argument, in this order: a null params;
+ * n_levels outside 1 .. RT_BLOOM_MAX_LEVELS; a threshold that is NaN or negative (+inf is legal: nothing glows); a knee that is NaN,
+ * negative or infinite; an intensity that is NaN, negative or infinite; color_stride < 3; rows * cols >= 2^32; then rows == 0 or
+ * cols == 0 is RT_OK and launches nothing; a null color, out or (where the form takes it: not rt_bloom_host, whose round trip makes
+ * its own) temp; out == color with color_stride != 3.
+ * RT_AMD_BLOOM_FORM (rt_set_option): 0 every step the plain kernel, every tap read from global memory; 1 the down steps the tiled
+ * kernel, a workgroup's 34 x 34 sources staged in LDS once, after the bright pass; same bits (DESIGN.md 3.30 says which is the default
+ * and why).  RT_AMD_DIAG_BLOOM_MAX_GROUPS: a test hook, a step launches at most this many workgroups and takes the rest of its level
+ * grid-stride; same bits.
+ * Not covered: the rt_multi_* sharded finish (a band's bloom needs its neighbours' rows); lens dirt and anamorphic kernels; tone
+ * mapping other than post_process's divide; rt_render, which gets no flag. */
+
+#define RT_BLOOM_MAX_LEVELS 8u
+
+typedef struct rt_bloom_params {
+    float threshold;    /* luma above which a pixel glows; +inf: nothing does */
+    float knee;         /* half-width of the soft transition around threshold; 0: a hard cut */
+    float intensity;    /* weight of the whole bloom in the composite */
+    uint32_t n_levels;  /* 1 .. RT_BLOOM_MAX_LEVELS (8) */
+} rt_bloom_params;      /* 16 bytes */
+
+/* the bytes of d_temp for an image of rows x cols at n_levels (step 5); host arithmetic, 0 for an n_levels outside 1 .. 8 */
+size_t rt_bloom_temp_bytes(uint32_t rows, uint32_t cols, uint32_t n_levels);
+/* d_color: rows * cols pixels of 3 f32 at color_stride words; d_temp: rt_bloom_temp_bytes bytes; d_out: rows * cols * 3 f32, or d_color
+ * itself when color_stride == 3; 2 n_levels kernel launches.  Nothing but d_temp and d_out is written. */
+int rt_bloom(const float *d_color, uint32_t color_stride, const rt_bloom_params *params, uint32_t rows, uint32_t cols, float *d_temp,
+             float *d_out, void *hip_stream);
+/* The same kernels on HOST arrays: allocate, upload the colour with its stride, run, synchronise the device and download.  h_temp is
+ * not looked at (it may be NULL): the round trip makes the scratch on the device.  NOT the CPU definition — that is rt_bloom_cpu of
+ * librt_host.so. */
+int rt_bloom_host(const float *h_color, uint32_t color_stride, const rt_bloom_params *params, uint32_t rows, uint32_t cols, float *h_temp,
+                  float *h_out);
+
 /* ---- film queries: sub-pixel camera rays and filtered accumulation ------------------------------
 
  * The image side of the per-pixel loop: where in its pixel a sample is taken, the primary ray through that position, and what a sample
@@ -1802,7 +1873,7 @@ int rt_upsample_guided_host(const float *h_color_lo, uint32_t color_stride, cons
  * RT_AMD_DIST_BY_COST, RT_AMD_DIST_OWN_FIRST, RT_AMD_DIST_PREP_FIRST, RT_AMD_DIST_SPLIT, RT_AMD_DIAG_WS_REFUSE,
  * RT_AMD_MULTI_FORCE_STAGE, RT_AMD_BFS_WALK_TRIANGLES (read by rt_scene_create), RT_AMD_WF_SHARE, RT_AMD_DIAG_BFS_CAP,
  * RT_AMD_DIAG_DIST_BAND_RAYS, RT_AMD_QUERY_WAVE_UNIFORM, RT_AMD_DIAG_HIT_BAND_RECORDS, RT_AMD_FILM_SPLAT_FORM, RT_AMD_DIAG_FILM_MAX_GROUPS,
- * RT_AMD_DENOISE_FORM, RT_AMD_DIAG_DENOISE_MAX_GROUPS, RT_AMD_DIAG_TEMPORAL_MAX_GROUPS, RT_AMD_SVGF_FORM, RT_AMD_DIAG_SVGF_MAX_GROUPS, RT_AMD_DIAG_MOTION_MAX_GROUPS, RT_AMD_DIAG_RECTIFY_MAX_GROUPS, RT_AMD_DIAG_ADAPTIVE_MAX_GROUPS, RT_AMD_UPSAMPLE_FORM, RT_AMD_DIAG_UPSAMPLE_MAX_GROUPS (INTEGRATION.md says what each does); any other name is RT_ERR_INVALID_ARGUMENT.  The environment is read ONCE per process, at the first use;
+ * RT_AMD_DENOISE_FORM, RT_AMD_DIAG_DENOISE_MAX_GROUPS, RT_AMD_DIAG_TEMPORAL_MAX_GROUPS, RT_AMD_SVGF_FORM, RT_AMD_DIAG_SVGF_MAX_GROUPS, RT_AMD_DIAG_MOTION_MAX_GROUPS, RT_AMD_DIAG_RECTIFY_MAX_GROUPS, RT_AMD_DIAG_ADAPTIVE_MAX_GROUPS, RT_AMD_UPSAMPLE_FORM, RT_AMD_DIAG_UPSAMPLE_MAX_GROUPS, RT_AMD_BLOOM_FORM, RT_AMD_DIAG_BLOOM_MAX_GROUPS (INTEGRATION.md says what each does); any other name is RT_ERR_INVALID_ARGUMENT.  The environment is read ONCE per process, at the first use;
  * after that only this call changes a switch: value = decimal integer, NULL or "" = unset (the library's own choice).  Render
  * calls read the switches without locks: set them between calls, not during one. */
 int rt_set_option(const char *name, const char *value);

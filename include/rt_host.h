@@ -142,6 +142,12 @@ int rt_upsample_guided_cpu(const float *color_lo, uint32_t color_stride, const r
                            uint32_t object_lo_stride, const rt_denoise_guides *full, const uint32_t *object_full, uint32_t object_full_stride,
                            const rt_upsample_params *params, uint32_t rows, uint32_t cols, float *out);
 
+/* The bloom queries' CPU definition (include/rt_amd.h "bloom queries" states every operation and the order): plain loops over host
+ * arrays, no device needed, bit-identical to rt_bloom of librt_amd.so.  Same arguments without the stream — temp is the caller's scratch
+ * of rt_bloom_temp_bytes bytes —, same checks with the same messages; a failure returns a negative rt_status and sets
+ * rt_host_last_error().  Called _cpu for the reason rt_denoise_atrous_cpu is. */
+int rt_bloom_cpu(const float *color, uint32_t color_stride, const rt_bloom_params *params, uint32_t rows, uint32_t cols, float *temp, float *out);
+
 /* The adaptive sampling queries' CPU definition (include/rt_amd.h "adaptive sampling queries" states every operation and the order): plain
  * loops over host arrays, no device needed, bit-identical to rt_sample_budget / rt_sample_list / rt_film_offsets_listed /
  * rt_camera_rays_listed / rt_film_splat_listed of librt_amd.so.  Same arguments without the stream (and, for the list, without the
