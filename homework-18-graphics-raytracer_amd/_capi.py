@@ -243,6 +243,7 @@ AMD_SYMBOLS = [
     "rt_tree_gate", "rt_tree_split", "rt_tree_spawn", "rt_tree_gather", "rt_tree_fold",
     "rt_light_rays", "rt_light_terms", "rt_light_fold",
     "rt_area_light_rays", "rt_area_light_terms", "rt_area_light_fold",
+    "rt_hemisphere_rays", "rt_hemisphere_fold",
     "rt_material_hits", "rt_material_hits_host", "rt_probe_surfaces", "rt_probe_surfaces_host",
     "rt_film_offsets", "rt_camera_rays_offset", "rt_camera_rays_offset_host", "rt_film_splat",
     "rt_sample_budget", "rt_sample_list_temp_bytes", "rt_sample_list", "rt_film_offsets_listed", "rt_camera_rays_listed", "rt_film_splat_listed",
@@ -273,6 +274,7 @@ HOST_SYMBOLS = [
     "rt_upsample_guided_cpu",
     "rt_bloom_cpu",
     "rt_area_light_samples_cpu",
+    "rt_hemisphere_dirs_cpu", "rt_hemisphere_fold_cpu",
 ]
 
 _amd = None
@@ -346,6 +348,9 @@ def host_lib() -> C.CDLL:
         lib.rt_bloom_cpu.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(BloomParams), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
         lib.rt_area_light_samples_cpu.argtypes = [C.POINTER(Light), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32,
                                                   C.c_uint32, C.c_void_p]
+        lib.rt_hemisphere_dirs_cpu.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+        lib.rt_hemisphere_fold_cpu.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_float,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.rt_host_last_error.restype = C.c_char_p
         _host = lib
     return _host
@@ -457,6 +462,10 @@ def amd_lib() -> C.CDLL:
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.rt_area_light_fold.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p]
+        lib.rt_hemisphere_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.rt_hemisphere_fold.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p]
         lib.rt_material_hits.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         lib.rt_material_hits_host.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         lib.rt_probe_surfaces.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]

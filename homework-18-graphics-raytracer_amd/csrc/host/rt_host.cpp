@@ -28,6 +28,7 @@
 #include "../rt_upsample.h"
 #include "../rt_bloom.h"
 #include "../rt_area_light.h"
+#include "../rt_hemisphere.h"
 
 using rt::V3;
 
@@ -612,7 +613,52 @@ int rt_area_light_samples_cpu(const rt_light *lights, uint32_t light_first, uint
     return RT_OK;
 }
 
-/* ---- adaptive sampling queries: the CPU definition (include/rt_amd.h "adaptive sampling queries"; the arithmetic is rt_adaptive.h's, shared with the device) ---- */
+/* ---- hemisphere queries: the sampler and the fold on the CPU (include/rt_amd.h "hemisphere queries"; the arithmetic is rt_hemisphere.h's, shared with the device) ---- */
+
+static int hemisphere_counts(const char *who, size_t n, uint32_t spp) {
+    if ((uint64_t)n >= (1ull << 32) || (uint64_t)n * spp >= (1ull << 32))
+        return fail(RT_ERR_UNSUPPORTED, std::string(who) + "2^32 (sample, record) entries or more (query the records in several calls, or fewer samples)");
+    return RT_OK;
+}
+
+int rt_hemisphere_dirs_cpu(const float *normals, const uint32_t *ids, size_t n, uint32_t spp, uint32_t pattern, uint32_t seed, float *dirs) {
+    const char *const who = "rt_hemisphere_dirs_cpu: ";
+    if (const int rc = hemisphere_counts(who, n, spp)) return rc;
+    if (n == 0) return RT_OK;
+    if (!normals || !dirs) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + "null normal or direction pointer");
+    if (const char *bad = rt::hemisphere_limits(spp, true, pattern, RT_HEMISPHERE_GEOMETRIC)) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + bad);
+    const uint32_t k = rt::film_strata(spp), seed_h = rt::hemisphere_seed(seed);
+    for (uint32_t s = 0; s < spp; ++s) {
+        float *const plane = dirs + 3u * (size_t)s * n;
+        for (size_t i = 0; i < n; ++i) {
+            const V3 d = rt::hemisphere_dir(pattern, k, ids ? ids[i] : (uint32_t)i, seed_h, s, rt::v3p(normals + 3u * i));
+            plane[3u * i] = d.x;
+            plane[3u * i + 1u] = d.y;
+            plane[3u * i + 2u] = d.z;
+        }
+    }
+    return RT_OK;
+}
+
+int rt_hemisphere_fold_cpu(const rt_hit *hits, const unsigned char *valid, const float *diffuse_color, const float *shiness, size_t n, uint32_t spp,
+                           const unsigned char *asks, const rt_hit *shadow_hits, float max_distance, const float *radiance, unsigned char *open,
+                           float *ambient, float *rgb) {
+    const char *const who = "rt_hemisphere_fold_cpu: ";
+    if (const int rc = hemisphere_counts(who, n, spp)) return rc;
+    if (n == 0) return RT_OK;
+    if ((radiance != nullptr) != (rgb != nullptr))
+        return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + "null radiance or rgb (they are given together or not at all) pointer");
+    if (!hits || !valid || !asks || (rgb && (!diffuse_color || !shiness)))
+        return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + "null hit, valid, flag, diffuse-colour or shiness pointer");
+    if (const char *bad = rt::hemisphere_limits(spp, false, 0u, 0u)) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + bad);
+    const rt::HemisphereFold f = {(uint64_t)n, spp, asks, reinterpret_cast<const uint32_t *>(shadow_hits), max_distance, radiance, open, ambient, rgb};
+    for (size_t i = 0; i < n; ++i)
+        rt::hemisphere_fold_record(f, i, valid[i] != 0, rt::v3p(hits[i].position), rgb ? rt::v3p(diffuse_color + 3u * i) : rt::v3(0.0f, 0.0f, 0.0f),
+                                   rgb ? shiness[i] : 0.0f);
+    return RT_OK;
+}
+
+/* ---- adaptive sampling queries: the CPU definition (include/rt_amd.h "adaptive sampling queries";the arithmetic is rt_adaptive.h's, shared with the device) ---- */
 
 int rt_sample_budget_cpu(const float *mean, uint32_t mean_stride, const float *variance, uint32_t variance_stride, const uint32_t *count,
                          uint32_t count_stride, const uint32_t *valid, uint32_t valid_stride, const rt_sample_budget_params *params, size_t n,

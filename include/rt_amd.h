@@ -449,6 +449,74 @@ int rt_area_light_terms(const rt_scene *scene, const rt_hit *d_hits, const rt_ra
 int rt_area_light_fold(const rt_scene *scene, const rt_hit *d_hits, size_t n, uint32_t light_count, uint32_t spp, const unsigned char *d_lit,
                        const float *d_diffuse, const float *d_specular, float *d_rgb, float *d_visibility, void *hip_stream);
 
+/* ---- hemisphere queries: ambient occlusion and one bounce of diffuse light on caller-supplied hits ------------------------------
+
+ * get_shade lights a hit from the stored lights alone: no ambient term, no light from other surfaces, black where no light asks
+ * (the `continue`s at main.rs:407).  This block samples the hemisphere over a hit with cosine-distributed directions and folds what
+ * comes back along them into two products: ambient occlusion — a plane that a compositor or a denoiser multiplies an ambient or sky
+ * colour by — and one bounce of diffuse inter-reflection, the radiance rt_trace_rays returns along the directions weighed by the
+ * hit's diffuse colour.  Both are noisy; the film, temporal, variance-guided and upsampling queries below are there to clean them.
+ *     ambient occlusion   rt_hemisphere_rays -> rt_select_records(d_asks) -> rt_cast_rays_indexed(d_rays -> d_shadow_hits)
+ *                             -> rt_hemisphere_fold(d_shadow_hits, max_distance -> d_ambient)
+ *     one bounce          rt_hemisphere_rays -> rt_trace_rays(d_rays -> d_radiance, all spp * n of them) -> rt_hemisphere_fold(d_radiance -> d_rgb)
+ * (INTEGRATION.md writes both out)
+ *
+ * The sample.  (record id, sample number s in 0 .. spp - 1) name a direction, in single f32 or u32 operations in this order, none
+ * fused (csrc/rt_hemisphere.h, shared by both libraries; film_mix and film_offset are the film queries', rtdm::sinf / cosf / f_sqrt
+ * csrc/rt_detmath.h's, adjust_normal csrc/rt_shade.h's — the reference's Quaternion::from_arc(+z, N) applied to a vector):
+ *     seed_h = film_mix(seed ^ 0x85ebca6bu)                            a stream of its own, apart from the area lights'
+ *     u_a    = film_offset(pattern, k, id, seed_h, s, a) + 0.5f        a = 0, 1;  k = the side of a stratified pattern, spp = k * k
+ *     r      = sqrt(u_0)                                               correctly rounded
+ *     z      = sqrt(max(1.0f - u_0, 0.0f))
+ *     phi    = 6.2831855f * u_1
+ *     local  = (r * cosf(phi), r * sinf(phi), z)                       cosine-distributed about +z (Malley)
+ *     dir    = adjust_normal(local, N)
+ * N is chosen by normal_kind: RT_HEMISPHERE_SHADING is adjust_normal(material.normal, hit.normal) — the normal get_shade lights with,
+ * rt_material_hits' shading_normal bit for bit; RT_HEMISPHERE_GEOMETRIC is hit.normal.  pattern is RT_FILM_UNIFORM or
+ * RT_FILM_STRATIFIED (spp = k * k, 1 <= k <= 8: one sample per cell of the k x k grid over (u_0, u_1)); RT_FILM_CENTER is refused;
+ * 1 <= spp <= 64.  A stratified u_0 may round to exactly 1: then z is 0, the direction lies in the tangent plane and does not ask.
+ *
+ * Per-entry arrays are sample-major: entry k = s * n + i, spp * n entries — one sample's plane is contiguous, and the whole array is
+ * one batch of records for rt_select_records, rt_cast_rays_indexed and rt_trace_rays.  The record rules are those of the hit queries.
+ * Every pointer is a device pointer; every call is stream-ordered and asynchronous on hip_stream (NULL = default stream), is one
+ * kernel with one record per lane, allocates nothing, uses no workspace and may be captured into a HIP graph at once.
+ * Checked before any device work, in this order: n >= 2^32 or n * spp >= 2^32 is RT_ERR_UNSUPPORTED; a null scene
+ * RT_ERR_INVALID_ARGUMENT; n == 0 is RT_OK and launches nothing; a null required pointer RT_ERR_INVALID_ARGUMENT; spp outside
+ * 1 .. 64, RT_FILM_CENTER, an unknown pattern, a stratified spp that is no square or an unknown normal_kind RT_ERR_INVALID_ARGUMENT
+ * with a message that names the limit; only then is the scene read.
+ * Not covered: _host forms of these two (they sit between device calls; rt_hemisphere_dirs_cpu and rt_hemisphere_fold_cpu of
+ * include/rt_host.h are the CPU forms); rt_multi_* forms; hemisphere sampling inside rt_render_*; other distributions — for those a
+ * caller overwrites d_dirs and d_rays; more than one bounce. */
+#define RT_HEMISPHERE_SHADING 0u   /* N = adjust_normal(material.normal, hit.normal) */
+#define RT_HEMISPHERE_GEOMETRIC 1u /* N = hit.normal */
+
+/* d_ids: n u32, the record id of the hash — the global pixel index, say, so that a pixel draws the same directions wherever it lies
+ * in the batch — or NULL for id = (uint32_t)i.
+ *   d_dirs[3k ..]   dir, for every entry of a record that is a hit; zero words for a "no hit" record
+ *   d_asks[k]       !(dot(dir, N) <= 0) on a hit, else 0
+ *   d_rays[k]       the shadow ray get_shade builds (main.rs:425-433) with -light.direction = dir: origin hit.position, direction dir,
+ *                   face Back, exclusion { hit.kind, hit.index, Back }; all-zero words where d_asks[k] is 0, as with rt_light_rays
+ * — which is rt_light_rays for a directional light without origin whose direction is -dir, bit for bit.  A Back ray is answered by
+ * back faces only (main.rs:185): occluders are closed objects, as for every shadow ray of the reference. */
+int rt_hemisphere_rays(const rt_scene *scene, const rt_hit *d_hits, size_t n, const uint32_t *d_ids, uint32_t spp, uint32_t pattern, uint32_t seed,
+                       uint32_t normal_kind, rt_ray *d_rays, unsigned char *d_asks, float *d_dirs, void *hip_stream);
+/* Per record, over the samples s = 0 .. spp - 1 in order:
+ *     open[k] = d_asks[k] && !(d_shadow_hits[k] is a hit && distance(hit.position, d_shadow_hits[k].position) < max_distance)
+ * with rt_light_terms' f32 distance.  max_distance = +inf makes every answered cast at a finite distance occlude (the directional
+ * rule); a NaN distance leaves the sample open (the point-light compare); d_shadow_hits NULL: open = d_asks.  d_shadow_hits[k] is
+ * read only where d_asks[k] is set.  On a "no hit" record every flag is 0.
+ *   d_open       NULL, or spp * n bytes: open[k]
+ *   d_ambient    NULL, or n floats: (float)(open samples) / (float)spp, 0 for a "no hit" record
+ *   d_rgb, d_radiance   both NULL, or n * 3 floats and spp * n * 3 floats (what rt_trace_rays wrote for d_rays, say): over s where
+ *                d_asks[k] is set, acc starts as the first such radiance and every later one is added to it; a record with none adds
+ *                nothing; otherwise E = acc / (float)spp and
+ *                    rgb = rgb + (diffuse_color * E) * (1 - shiness)          per channel, in place on d_rgb[3i ..]
+ *                with the material's values as get_shade reads them.  Every operation rounds to f32 and none is fused.  The call
+ *                ADDS, as rt_light_fold does; "no hit" records are not written.  The radiance of an entry that did not ask is never
+ *                read. */
+int rt_hemisphere_fold(const rt_scene *scene, const rt_hit *d_hits, size_t n, uint32_t spp, const unsigned char *d_asks, const rt_hit *d_shadow_hits,
+                       float max_distance, const float *d_radiance, unsigned char *d_open, float *d_ambient, float *d_rgb, void *hip_stream);
+
 /* ---- material queries: approx, adjust_normal and the Phong terms on caller-supplied hits ------------------------------
 
  * The material at a hit, which every render and query kernel evaluates between two casts and none of the blocks above returns:

@@ -194,6 +194,20 @@ int rt_svgf_atrous_cpu(const float *color, uint32_t color_stride, const float *v
 int rt_area_light_samples_cpu(const rt_light *lights, uint32_t light_first, uint32_t light_count, const float *radii, const uint32_t *ids, size_t n,
                               uint32_t spp, uint32_t pattern, uint32_t seed, float *sample);
 
+/* The hemisphere queries on the CPU (include/rt_amd.h "hemisphere queries" states every operation and the order; the arithmetic is
+ * csrc/rt_hemisphere.h's, shared with the device), for host arrays and no device.
+ * rt_hemisphere_dirs_cpu: dirs[3k ..] of rt_hemisphere_rays, bit for bit, k = s * n + i, for the normals it is given — n * 3 floats,
+ * the N of each record; it evaluates no material and knows no "no hit".  ids: n u32 or NULL for id = i.
+ * rt_hemisphere_fold_cpu: rt_hemisphere_fold, bit for bit, with what the device reads from the scene as plain arrays: valid (n bytes:
+ * the record is a hit), diffuse_color (n * 3 floats) and shiness (n floats), read only where rgb is given; hits: the records, of which
+ * the position is read; shadow_hits, radiance, open, ambient and rgb as the device call's, NULL where it allows NULL.
+ * The limits are the device calls' with the same texts: the counts (RT_ERR_UNSUPPORTED), n == 0 is RT_OK, a null required pointer, then
+ * spp (and pattern).  A failure returns a negative rt_status and sets rt_host_last_error(). */
+int rt_hemisphere_dirs_cpu(const float *normals, const uint32_t *ids, size_t n, uint32_t spp, uint32_t pattern, uint32_t seed, float *dirs);
+int rt_hemisphere_fold_cpu(const rt_hit *hits, const unsigned char *valid, const float *diffuse_color, const float *shiness, size_t n, uint32_t spp,
+                           const unsigned char *asks, const rt_hit *shadow_hits, float max_distance, const float *radiance, unsigned char *open,
+                           float *ambient, float *rgb);
+
 /* RGB8 PNG, written to "<path>.tmp" then renamed over path. */
 int rt_write_png(const char *path, const uint8_t *rgb8, uint32_t width, uint32_t height);
 
