@@ -13,6 +13,7 @@ imports without a GPU (torch is imported inside functions).  Where the rest of t
     _trace_support.py         trace_rays variants and the wavefront parity check
     _film_support.py          the film cases and the host splat
     _reference_support.py     the reference image pins, the progressive loop and the RNG constant
+    _guard_support.py         operands inside poisoned guards: where an image query read and wrote (guarded, Case, check_written, run_poisoned)
     _margin_support.py        what the exactness-preserving shortcuts were given, their compares restated, inputs at their margins
     _oracle.py, _scenes.py    the CPU oracle's bindings and the scene builders"""
 import ctypes as C
