@@ -230,6 +230,12 @@ class BloomParams(C.Structure):
     _fields_ = [("threshold", C.c_float), ("knee", C.c_float), ("intensity", C.c_float), ("n_levels", C.c_uint32)]
 
 
+class EnvironmentDesc(C.Structure):
+    """rt_environment"""
+    _fields_ = [("d_texels", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32), ("rotation", C.c_float), ("scale", C.c_float),
+                ("filter", C.c_uint32)]
+
+
 AMD_SYMBOLS = [
     "rt_abi_version", "rt_last_error", "rt_device_count", "rt_set_device", "rt_frame_rows", "rt_frame_pixels",
     "rt_scene_create", "rt_scene_destroy", "rt_render_whitted", "rt_render_whitted_host", "rt_set_option", "rt_set_variant",
@@ -244,6 +250,7 @@ AMD_SYMBOLS = [
     "rt_light_rays", "rt_light_terms", "rt_light_fold",
     "rt_area_light_rays", "rt_area_light_terms", "rt_area_light_fold",
     "rt_hemisphere_rays", "rt_hemisphere_fold",
+    "rt_environment_lookup", "rt_environment_table_bytes", "rt_environment_table", "rt_environment_rays", "rt_environment_fold",
     "rt_material_hits", "rt_material_hits_host", "rt_probe_surfaces", "rt_probe_surfaces_host",
     "rt_film_offsets", "rt_camera_rays_offset", "rt_camera_rays_offset_host", "rt_film_splat",
     "rt_sample_budget", "rt_sample_list_temp_bytes", "rt_sample_list", "rt_film_offsets_listed", "rt_camera_rays_listed", "rt_film_splat_listed",
@@ -276,6 +283,9 @@ HOST_SYMBOLS = [
     "rt_area_light_samples_cpu",
     "rt_hemisphere_dirs_cpu", "rt_hemisphere_fold_cpu",
 ]
+# librt_host.so's CPU forms of the environment queries, declared in include/rt_environment_host.h (which says why they have a header and
+# a list of their own: they are no image-side rt_X / rt_X_cpu pairs)
+ENVIRONMENT_HOST_SYMBOLS = ["rt_environment_lookup_cpu", "rt_environment_table_cpu", "rt_environment_samples_cpu", "rt_environment_fold_cpu"]
 
 _amd = None
 _host = None
@@ -351,6 +361,12 @@ def host_lib() -> C.CDLL:
         lib.rt_hemisphere_dirs_cpu.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
         lib.rt_hemisphere_fold_cpu.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_float,
                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.rt_environment_lookup_cpu.argtypes = [C.POINTER(EnvironmentDesc), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        lib.rt_environment_table_cpu.argtypes = [C.POINTER(EnvironmentDesc), C.c_void_p]
+        lib.rt_environment_samples_cpu.argtypes = [C.POINTER(EnvironmentDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.rt_environment_fold_cpu.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p]
         lib.rt_host_last_error.restype = C.c_char_p
         _host = lib
     return _host
@@ -466,6 +482,15 @@ def amd_lib() -> C.CDLL:
                                            C.c_void_p, C.c_void_p, C.c_void_p]
         lib.rt_hemisphere_fold.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.rt_environment_lookup.argtypes = [C.POINTER(EnvironmentDesc), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                              C.c_void_p]
+        lib.rt_environment_table_bytes.argtypes = [C.c_uint32, C.c_uint32]
+        lib.rt_environment_table_bytes.restype = C.c_size_t
+        lib.rt_environment_table.argtypes = [C.POINTER(EnvironmentDesc), C.c_void_p, C.c_void_p]
+        lib.rt_environment_rays.argtypes = [C.c_void_p, C.POINTER(EnvironmentDesc), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_uint32,
+                                            C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.rt_environment_fold.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p]
         lib.rt_material_hits.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         lib.rt_material_hits_host.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         lib.rt_probe_surfaces.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]

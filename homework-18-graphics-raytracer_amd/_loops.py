@@ -287,11 +287,24 @@ def trace_rays_levels(scene: Scene, rays, max_depth: int, contribution=1.0, out=
     up front: every cast of the loop is then a cast_rays_indexed — on a scene walked breadth-first, that walk — with the same bits and
     count (the two add a few element-wise fills to what is enqueued).
     (Being a sequence of calls it may not be captured before select_records has run once on the stream.)"""
+    return _trace_rays_levels(scene, rays, max_depth, contribution, out, ray_count, stream, level_capacity, check, overflow, level_counts, open_casts, None)
+
+
+def _trace_rays_levels(scene, rays, max_depth, contribution, out, ray_count, stream, level_capacity, check, overflow, level_counts, open_casts, environment):
+    """trace_rays_levels, and environment.trace_rays_levels: with ``environment`` (an environment.Environment) every level's tree_fold is
+    followed by environment.lookup on that level's rays, hits, count and parent links, which replaces the +0 the fold wrote for the
+    level's misses before the parent level folds; the levels' rays are then kept per level instead of in two buffers used in turn.  With
+    None the calls enqueued are trace_rays_levels' as they always were."""
     torch = _torch()
     n, dev = _tensor(rays, "rays", "int32", (None, 11)).shape[0], rays.device
     out = _out_tensor(out, (n, 3), "float32", dev)
     _count_ptr(ray_count)
     _tensor(overflow, "overflow", "int32", (1,), optional=True)
+    if environment is not None:
+        from .environment import Environment, lookup as environment_lookup
+
+        if not isinstance(environment, Environment):
+            raise ValueError("environment must be an environment.Environment or None")
     if max_depth > _capi.RT_MAX_DEPTH:
         raise RtError(-5, f"max_depth above RT_MAX_DEPTH ({_capi.RT_MAX_DEPTH})")
     depth = max(int(max_depth), 0)
@@ -333,6 +346,7 @@ def trace_rays_levels(scene: Scene, rays, max_depth: int, contribution=1.0, out=
         h_shade, h_reflect, h_refract = new((top, 13), i32), new((top, 13), i32), new((top, 13), i32)
         reflected, escape = new((top, 11), i32), new((top, 11), i32)
         level_rays = [None, new((top, 11), i32), new((top, 11), i32)]  # children's rays and contributions, in turn
+        kept_rays = [rays] + [new((c, 11), i32) for c in caps[1:]] if environment is not None else None  # the lookup wants a level's rays at its fold
         level_contribution = [None, new((top,), f32), new((top,), f32)]
         flags, index, selected = new((2 * top,), u8), new((2 * top,), i32), new((1,), i32)
         identity, n_all = new((top,), i32), new((1,), i32)
@@ -366,14 +380,18 @@ def trace_rays_levels(scene: Scene, rays, max_depth: int, contribution=1.0, out=
             tree_spawn(h_reflect[:c], refr_kind[k], flags[:2 * c], child_values[k], stream=s)
             select_records(flags[:2 * c], index[:2 * c], selected, stream=s)
             nxt = 1 + (k & 1)
+            next_rays = level_rays[nxt] if kept_rays is None else kept_rays[k + 1]
             tree_gather(index[:2 * c], selected, reflected[:c], escape[:c], cur_contribution[:c], weights[k], overflow, caps[k + 1],
-                        level_rays[nxt], level_contribution[nxt], parent[k + 1], count[k + 1], stream=s)
-            cur_rays, cur_contribution = level_rays[nxt], level_contribution[nxt]
+                        next_rays, level_contribution[nxt], parent[k + 1], count[k + 1], stream=s)
+            cur_rays, cur_contribution = next_rays, level_contribution[nxt]
     for k in reversed(range(depth + 1)):
         left = depth - k
         tree_fold(hits[k], left, shade[k], out if k == 0 else child_values[k - 1], None if k == 0 else count[k],
                   weights[k] if left > 0 else None, refr_kind[k] if left > 0 else None, travel[k] if left > 0 else None,
                   child_values[k] if left > 0 else None, parent[k], stream=s)
+        if kept_rays is not None:  # the sky behind the level's misses, into the slots the fold just wrote +0 to
+            environment_lookup(environment, kept_rays[k][:caps[k]], hits[k], None if k == 0 else count[k], parent[k],
+                               out if k == 0 else child_values[k - 1], stream=s)
     if check:
         with _on_stream(stream):
             dropped = int(overflow.item())  # the one readback: it waits for the loop

@@ -29,6 +29,7 @@
 #include "../rt_bloom.h"
 #include "../rt_area_light.h"
 #include "../rt_hemisphere.h"
+#include "../rt_environment.h"
 
 using rt::V3;
 
@@ -655,6 +656,123 @@ int rt_hemisphere_fold_cpu(const rt_hit *hits, const unsigned char *valid, const
     for (size_t i = 0; i < n; ++i)
         rt::hemisphere_fold_record(f, i, valid[i] != 0, rt::v3p(hits[i].position), rgb ? rt::v3p(diffuse_color + 3u * i) : rt::v3(0.0f, 0.0f, 0.0f),
                                    rgb ? shiness[i] : 0.0f);
+    return RT_OK;
+}
+
+/* ---- environment queries: the lookup, the table, the sampler and the fold on the CPU (include/rt_amd.h "environment queries"; the arithmetic is rt_environment.h's, shared with the device) ---- */
+
+static int environment_counts(const char *who, size_t n, uint32_t spp) {
+    if ((uint64_t)n >= (1ull << 32) || (uint64_t)n * spp >= (1ull << 32))
+        return fail(RT_ERR_UNSUPPORTED, std::string(who) + "2^32 (sample, record) entries or more (query the records in several calls, or fewer samples)");
+    return RT_OK;
+}
+
+static int environment_ok(const char *who, const rt_environment *env) {
+    bool unsupported;
+    if (const char *bad = rt::environment_limits(env, &unsupported)) return fail(unsupported ? RT_ERR_UNSUPPORTED : RT_ERR_INVALID_ARGUMENT, std::string(who) + bad);
+    return RT_OK;
+}
+
+int rt_environment_lookup_cpu(const rt_environment *env, const rt_ray *rays, size_t n, const uint32_t *count, const rt_hit *hits, const uint32_t *parent,
+                              float *out, size_t n_out) {
+    const char *const who = "rt_environment_lookup_cpu: ";
+    if (const int rc = environment_counts(who, n, 1u)) return rc;
+    if (const int rc = environment_ok(who, env)) return rc;
+    if (n == 0) return RT_OK;
+    if (!rays || !out) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + "null ray or output pointer");
+    const rt::EnvLookup a = {*env, reinterpret_cast<const uint32_t *>(rays), (uint64_t)n, count, reinterpret_cast<const uint32_t *>(hits), parent, out, (uint64_t)n_out};
+    const uint64_t live = count != nullptr && *count < n ? *count : n;
+    for (uint64_t j = 0; j < live; ++j) rt::env_lookup_record(a, j);
+    return RT_OK;
+}
+
+int rt_environment_table_cpu(const rt_environment *env, void *table) {
+    const char *const who = "rt_environment_table_cpu: ";
+    if (const int rc = environment_ok(who, env)) return rc;
+    if (!table) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + "null table pointer");
+    if ((reinterpret_cast<uintptr_t>(table) & 7u) != 0u) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + "the table is not 8-byte aligned");
+    float luma[3];
+    rt::luma_row(luma);
+    const uint32_t w = env->width, h = env->height;
+    uint32_t *const header = static_cast<uint32_t *>(table);
+    uint64_t *const marginal = rt::env_table_marginal(table);
+    uint32_t *const rows = rt::env_table_rows(table, h);
+    float w_max = 0.0f;
+    for (uint32_t y = 0; y < h; ++y) {
+        const float sin_row = rt::env_sin_row(y, h);
+        for (uint32_t x = 0; x < w; ++x) {
+            bool usable;
+            const float v = rt::env_weight(*env, x, y, sin_row, luma[0], luma[1], luma[2], &usable);
+            if (usable && v > w_max) w_max = v;
+        }
+    }
+    uint64_t total = 0u;
+    for (uint32_t y = 0; y < h; ++y) {
+        const float sin_row = rt::env_sin_row(y, h);
+        uint32_t sum = 0u;
+        for (uint32_t x = 0; x < w; ++x) {
+            bool usable;
+            const float v = rt::env_weight(*env, x, y, sin_row, luma[0], luma[1], luma[2], &usable);
+            sum += rt::env_quantum(v, usable, w_max);
+            rows[(size_t)y * w + x] = sum;
+        }
+        total += sum;
+        marginal[y] = total;
+    }
+    header[RT_ENV_TABLE_WIDTH] = w;
+    header[RT_ENV_TABLE_HEIGHT] = h;
+    header[RT_ENV_TABLE_TOTAL] = (uint32_t)total;
+    header[RT_ENV_TABLE_TOTAL + 1u] = (uint32_t)(total >> 32);
+    header[RT_ENV_TABLE_W_MAX] = rtdm::f32_bits(w_max);
+    header[RT_ENV_TABLE_W_MAX + 1u] = 0u;
+    return RT_OK;
+}
+
+int rt_environment_samples_cpu(const rt_environment *env, const void *table, const float *normals, const uint32_t *ids, size_t n, uint32_t spp,
+                               uint32_t pattern, uint32_t seed, float *dirs, float *radiance, uint32_t *texel, unsigned char *asks) {
+    const char *const who = "rt_environment_samples_cpu: ";
+    if (const int rc = environment_counts(who, n, spp)) return rc;
+    if (const int rc = environment_ok(who, env)) return rc;
+    if (n == 0) return RT_OK;
+    if (!table || !normals || !dirs || !radiance) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + "null table, normal, direction or radiance pointer");
+    if (const char *bad = rt::hemisphere_limits(spp, true, pattern, RT_HEMISPHERE_GEOMETRIC)) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + bad);
+    const uint32_t k = rt::film_strata(spp), seed_e = rt::environment_seed(seed);
+    const rt::EnvTable t = rt::env_table_view(*env, table);
+    for (uint32_t s = 0; s < spp; ++s)
+        for (size_t i = 0; i < n; ++i) {
+            const size_t e = (size_t)s * n + i;
+            V3 dir = rt::v3(0.0f, 0.0f, 0.0f), l = rt::v3(0.0f, 0.0f, 0.0f);
+            uint32_t at = 0u;
+            bool need = false;
+            if (t.total > 0u) {
+                const rt::EnvSample p = rt::env_sample_of(*env, t, pattern, k, ids ? ids[i] : (uint32_t)i, seed_e, s);
+                dir = p.dir;
+                at = p.y * env->width + p.x;
+                need = p.ok && rt::hemisphere_asks(dir, rt::v3p(normals + 3u * i));
+                if (need) l = rt::env_sample_radiance(*env, p);
+            }
+            dirs[3u * e] = dir.x;
+            dirs[3u * e + 1u] = dir.y;
+            dirs[3u * e + 2u] = dir.z;
+            radiance[3u * e] = l.x;
+            radiance[3u * e + 1u] = l.y;
+            radiance[3u * e + 2u] = l.z;
+            if (texel) texel[e] = at;
+            if (asks) asks[e] = need ? 1 : 0;
+        }
+    return RT_OK;
+}
+
+int rt_environment_fold_cpu(const unsigned char *valid, const float *shiness, size_t n, uint32_t spp, const unsigned char *asks, const rt_hit *shadow_hits,
+                            const float *radiance, const float *diffuse, const float *specular, unsigned char *open, float *rgb) {
+    const char *const who = "rt_environment_fold_cpu: ";
+    if (const int rc = environment_counts(who, n, spp)) return rc;
+    if (n == 0) return RT_OK;
+    if (!valid || !shiness || !asks || !radiance || !diffuse || !specular || !rgb)
+        return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + "null valid, shiness, flag, radiance, diffuse, specular or rgb pointer");
+    if (const char *bad = rt::hemisphere_limits(spp, false, 0u, 0u)) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + bad);
+    const rt::EnvFold f = {(uint64_t)n, spp, asks, reinterpret_cast<const uint32_t *>(shadow_hits), radiance, diffuse, specular, open, rgb};
+    for (size_t i = 0; i < n; ++i) rt::env_fold_record(f, i, valid[i] != 0, shiness[i]);
     return RT_OK;
 }
 

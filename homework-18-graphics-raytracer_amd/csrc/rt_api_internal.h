@@ -21,6 +21,8 @@
  *                      with librt_host.so; the per-hit record rt_light_record.h's, shared with rt_light_query.hip)
  *   rt_hemisphere_query.hip the hemisphere queries' rt_hemisphere_rays / rt_hemisphere_fold: kernels and entry points in one unit (the sampler and the
  *                      fold are rt_hemisphere.h's, shared with librt_host.so)
+ *   rt_environment_query.hip the environment queries' rt_environment_lookup / _table / _rays / _fold: kernels and entry points in one unit (the arithmetic
+ *                      is rt_environment.h's, shared with librt_host.so)
  *   rt_refract_query.hip the refraction queries' rt_refract_enter / rt_refract_step: kernels and entry points in one unit
  *   rt_scene_update.hip the scene updates' rt_scene_update_*: kernels and entry points in one unit
  *   rt_motion_query.hip the motion queries' rt_scene_keep_positions / rt_scene_positions_kept / rt_previous_positions and its _host form: kernels and entry points in one unit

@@ -517,6 +517,115 @@ int rt_hemisphere_rays(const rt_scene *scene, const rt_hit *d_hits, size_t n, co
 int rt_hemisphere_fold(const rt_scene *scene, const rt_hit *d_hits, size_t n, uint32_t spp, const unsigned char *d_asks, const rt_hit *d_shadow_hits,
                        float max_distance, const float *d_radiance, unsigned char *d_open, float *d_ambient, float *d_rgb, void *hip_stream);
 
+/* ---- environment queries: a lat-long sky for the rays that found nothing, and sky light on caller-supplied hits ----------------
+
+ * A ray that leaves the scene is black (main.rs:475), and a hit is lit by the stored lights alone.  This block adds the sky: an
+ * environment map that answers the rays which found nothing, and that lights a hit through directions drawn in proportion to its
+ * brightness.  The environment is a caller-owned device image of height x width x 3 f32, linear RGB, row-major, row 0 at the zenith,
+ * equirectangular with y up (the reference scene's camera).  Texel-space point (x_f, y_f) lies in the direction
+ *     theta = 3.1415927f * y_f / (float)H     phi = 6.2831855f * x_f / (float)W + rotation
+ *     dir   = (sin theta * cos phi, cos theta, sin theta * sin phi)
+ * with rtdm::sincosf, every operation a single f32 one in the order written, none fused (csrc/rt_environment.h, shared by both
+ * libraries).  The sequences
+ *     the sky behind a batch   rt_cast_rays -> rt_environment_lookup(d_hits)
+ *     the sky in the tree loop rt_tree_fold of a level -> rt_environment_lookup(the level's rays, hits, count and parent links), before
+ *                              the parent level folds: it replaces the +0 the fold wrote for the level's misses
+ *     sky light on hits        rt_environment_table (once per image) -> rt_environment_rays -> rt_select_records(d_asks) ->
+ *                              rt_cast_rays_indexed(d_rays -> d_shadow_hits) -> rt_material_hits + rt_probe_surfaces(d_dirs, n_probes = spp)
+ *                              -> rt_environment_fold
+ * are written out in INTEGRATION.md; DESIGN.md §3.32 has what they cost.
+ *
+ * The lookup.  d = dir / |dir| (|dir| = sqrt of the f32 dot product; a length that is 0, NaN or Inf — a zero or non-finite
+ * direction — gives +0), theta = acosf(min(max(d.y, -1), 1)), phi = atan2f(d.z, d.x) - rotation, x_f = phi * W / 6.2831855f,
+ * x_f = x_f - floorf(x_f / W) * W, y_f = theta * H / 3.1415927f, both clamped to [0, W] and [0, H].  RT_ENV_NEAREST: x = min((uint32)x_f,
+ * W - 1), y likewise, rgb = texel(x, y) * scale.  RT_ENV_BILINEAR: texel centres at + 0.5 — xs = x_f - 0.5f, x0 = floorf(xs), fx = xs -
+ * x0, columns x0 and x0 + 1 wrapped around the phi seam; ys, y0, fy likewise, rows clamped at the poles; mix(a, b, t) = a * (1 - t) +
+ * b * t along x on both rows, then along y, then * scale.  NaN and Inf texels pass through the arithmetic.
+ *
+ * The table.  sin_row(y) = sinf(3.1415927f * ((float)y + 0.5f) / (float)H); w = ((r * l0 + g * l1) + b * l2) * sin_row(y) with the
+ * three luma weights of rt_post_process (csrc/rt_luma.h); a texel is usable where its three channels and w are finite and w > 0;
+ * w_max = the largest usable w; q = usable ? 1 + (uint32)(w / w_max * 65534.0f) : 0, so every texel that carries light can be sampled,
+ * and the density below is that of the table actually sampled from: quantisation costs variance, never bias.  The table holds, in this
+ * order, a header of 24 bytes (u32 width, u32 height, u64 total, f32 w_max, u32 0), the inclusive marginal M[y] = the sum of q over
+ * rows 0 .. y (u64, H entries) and the inclusive rows C[y][x] = the sum of q over columns 0 .. x of row y (u32, W * H entries):
+ * rt_environment_table_bytes(W, H) = 24 + 8 H + 4 W H.  It is all integers but w_max, a maximum: any scan order gives the same bits.
+ * Limits: width <= 16384, height <= 8192, width * height < 2^27 (row sums then fit u32); anything larger is RT_ERR_UNSUPPORTED.
+ *
+ * The sample.  (record id, sample number s in 0 .. spp - 1) name a texel and a point inside it:
+ *     seed_e = film_mix(seed ^ 0xc2b2ae35u)                            a stream of its own, apart from the hemispheres' and the area lights'
+ *     u_a    = film_offset(pattern, k, id, seed_e, s, a) + 0.5f        a = 0, 1;  k = the side of a stratified pattern, spp = k * k
+ *     a = (double)u_0 * (double)total;  t = min((uint64)a, total - 1);  y = the first row with M[y] > t
+ *     fy = min((float)((a - (double)M[y - 1]) / (double)rowsum), 0.99999994f)          rowsum = M[y] - M[y - 1];  M[-1] = 0
+ *     b = (double)u_1 * (double)rowsum;  tx = min((uint64)b, rowsum - 1);  x = the first column with C[y][x] > tx
+ *     fx = min((float)((b - (double)C[y][x - 1]) / (double)q), 0.99999994f)             q = C[y][x] - C[y][x - 1];  C[y][-1] = 0
+ *     (x_f, y_f) = ((float)x + fx, (float)y + fy), dir as above
+ *     pdf = (float)((double)q / (double)total) * (float)(W * H) / (19.739209f * sin theta)      per solid angle; sin theta the sample's own
+ * pattern, spp and normal_kind have the hemisphere queries' limits and messages.  A table whose header does not name the
+ * environment's width and height reads as total = 0; the two searches stay inside the table whatever it holds.
+ *
+ * Per-entry arrays are sample-major, as the hemisphere queries': entry k = s * n + i, spp * n entries.  The record rules are those of
+ * the hit queries.  Every pointer but the descriptor is a device pointer; the descriptor is a small struct read on the host and passed
+ * to the kernels by value.  Every call is stream-ordered and asynchronous on hip_stream (NULL = default stream), allocates nothing, uses
+ * no workspace beyond the caller's table and may be captured into a HIP graph at once.
+ * Checked before any device work, in this order: n >= 2^32 or n * spp >= 2^32 is RT_ERR_UNSUPPORTED; a null scene
+ * RT_ERR_INVALID_ARGUMENT (rt_environment_rays, rt_environment_fold); a null descriptor, null texels, a width or height of 0
+ * (RT_ERR_INVALID_ARGUMENT), an image over the limits (RT_ERR_UNSUPPORTED), an unknown filter (RT_ERR_INVALID_ARGUMENT); n == 0 is RT_OK
+ * and launches nothing; a null required pointer RT_ERR_INVALID_ARGUMENT; then spp, pattern and normal_kind as the hemisphere queries
+ * check them; only then is the scene read.
+ * Not covered: octahedral or cube maps; mip levels (a lookup takes one or four texels whatever the ray's footprint); the sky inside
+ * rt_render_whitted, rt_trace_rays or the distributed pass (the tree loop written from the public calls takes it: trace_rays_levels in
+ * Python); Refraction::Infinite rays (the refraction queries hand them back, a caller looks them up itself); rt_multi_* forms; multiple
+ * importance sampling with the hemisphere sampler; _host forms (rt_environment_*_cpu of include/rt_environment_host.h are the CPU
+ * forms). */
+#define RT_ENV_NEAREST 0u
+#define RT_ENV_BILINEAR 1u
+#define RT_ENV_MAX_WIDTH 16384u
+#define RT_ENV_MAX_HEIGHT 8192u
+typedef struct rt_environment {
+    const float *d_texels;  /* height * width * 3 floats, row 0 at the zenith */
+    uint32_t width, height;
+    float rotation;         /* radians about +y, added to phi */
+    float scale;            /* multiplies every looked-up radiance */
+    uint32_t filter;        /* RT_ENV_NEAREST or RT_ENV_BILINEAR */
+} rt_environment;
+
+/* The radiance along rays that found nothing.  d_rays: n rays, of which the direction is read.  d_count: NULL, or one device u32, the
+ * number of live records (a count above n is read as n), as in the tree loop.  d_hits: NULL — every live record is written — or the n
+ * hits of the rays: only the records that are "no hit" (kind > 1) are written, the others are left untouched.  The value goes to
+ * d_out[3 * d_parent[j] ..], or with d_parent == NULL to d_out[3 * j ..]; n_out is the number of 3-float slots d_out holds, and a
+ * slot at or beyond it is not written (0xffffffff, rt_tree_gather's "no candidate", folds nowhere) — rt_tree_fold's addressing.  One
+ * kernel, one record per lane, rays read as dwords. */
+int rt_environment_lookup(const rt_environment *env, const rt_ray *d_rays, size_t n, const uint32_t *d_count, const rt_hit *d_hits,
+                          const uint32_t *d_parent, float *d_out, size_t n_out, void *hip_stream);
+/* The sampling table of an environment, built on the device into d_table (rt_environment_table_bytes(width, height) bytes, 8-byte
+ * aligned; 0 for an image over the limits): a max reduction, an inclusive scan per row (one workgroup per row) and one over the rows.
+ * The luma weights are computed on the host.  Until the last kernel has run the header reads as "no table". */
+size_t rt_environment_table_bytes(uint32_t width, uint32_t height);
+int rt_environment_table(const rt_environment *env, void *d_table, void *hip_stream);
+/* spp directions per hit, drawn from the table.  d_ids: n u32, the record id of the hash, or NULL for id = (uint32_t)i.
+ *   d_dirs[3k ..]      dir, for every entry of a record that is a hit while total > 0; zero words otherwise
+ *   d_texel[k]         y * W + x of the sampled texel, where d_dirs[k] is written; 0 otherwise (may be NULL)
+ *   d_asks[k]          the record is a hit, total > 0, pdf is finite and > 0, and !(dot(dir, N) <= 0) — N by normal_kind, as
+ *                      rt_hemisphere_rays chooses it
+ *   d_radiance[3k ..]  texel(x, y) * scale / pdf where d_asks[k] — the sampled texel itself, whatever `filter` says; zeros elsewhere
+ *   d_rays[k]          rt_hemisphere_rays' shadow ray for that direction: from the hit, face Back, the hit's primitive excluded;
+ *                      all-zero words where d_asks[k] is 0 */
+int rt_environment_rays(const rt_scene *scene, const rt_environment *env, const void *d_table, const rt_hit *d_hits, size_t n, const uint32_t *d_ids,
+                        uint32_t spp, uint32_t pattern, uint32_t seed, uint32_t normal_kind, rt_ray *d_rays, unsigned char *d_asks, float *d_dirs,
+                        float *d_radiance, uint32_t *d_texel, void *hip_stream);
+/* Per record, over the samples s = 0 .. spp - 1 in order: a sample is open where d_asks[k] is set and d_shadow_hits[k] is "no hit" —
+ * the light is infinitely far, so whatever the cast found occludes (d_shadow_hits NULL: nothing occludes; it is read only where
+ * d_asks[k] is set).  d_diffuse and d_specular are what rt_probe_surfaces returns for d_dirs with n_probes = spp (its probe-major
+ * layout is this block's sample-major one).  acc_d = d_diffuse[3k ..] * d_radiance[3k ..] and acc_s = d_specular[3k ..] *
+ * d_radiance[3k ..] per channel, the first open sample's as they are and every later one's added; a record without an open sample
+ * adds nothing; otherwise D = acc_d / (float)spp, S = acc_s / (float)spp and
+ *     rgb = (rgb + D * (1 - shiness)) + S * shiness                     per channel, in place on d_rgb[3i ..]
+ * which is rt_area_light_fold's association.  Every operation rounds to f32 and none is fused.  The call ADDS, as that one does; "no
+ * hit" records are not written.  d_open: NULL, or spp * n bytes, the flag per sample (0 on a "no hit" record). */
+int rt_environment_fold(const rt_scene *scene, const rt_hit *d_hits, size_t n, uint32_t spp, const unsigned char *d_asks, const rt_hit *d_shadow_hits,
+                        const float *d_radiance, const float *d_diffuse, const float *d_specular, unsigned char *d_open, float *d_rgb,
+                        void *hip_stream);
+
 /* ---- material queries: approx, adjust_normal and the Phong terms on caller-supplied hits ------------------------------
 
  * The material at a hit, which every render and query kernel evaluates between two casts and none of the blocks above returns:

@@ -208,6 +208,10 @@ int rt_hemisphere_fold_cpu(const rt_hit *hits, const unsigned char *valid, const
                            const unsigned char *asks, const rt_hit *shadow_hits, float max_distance, const float *radiance, unsigned char *open,
                            float *ambient, float *rgb);
 
+/* The environment queries on the CPU — rt_environment_lookup_cpu, rt_environment_table_cpu, rt_environment_samples_cpu and
+ * rt_environment_fold_cpu, exported by librt_host.so like everything above — are declared in a header of their own, included at the end
+ * of this one.  That header says why. */
+
 /* RGB8 PNG, written to "<path>.tmp" then renamed over path. */
 int rt_write_png(const char *path, const uint8_t *rgb8, uint32_t width, uint32_t height);
 
@@ -216,4 +220,5 @@ const char *rt_host_last_error(void);
 #ifdef __cplusplus
 }
 #endif
+#include "rt_environment_host.h"
 #endif /* RT_HOST_H */
