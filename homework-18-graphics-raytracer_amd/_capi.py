@@ -252,6 +252,7 @@ AMD_SYMBOLS = [
     "rt_hemisphere_rays", "rt_hemisphere_fold",
     "rt_environment_lookup", "rt_environment_table_bytes", "rt_environment_table", "rt_environment_rays", "rt_environment_fold",
     "rt_material_hits", "rt_material_hits_host", "rt_probe_surfaces", "rt_probe_surfaces_host",
+    "rt_lobe_rays", "rt_lobe_pdf", "rt_environment_pdf", "rt_mis_weigh",
     "rt_film_offsets", "rt_camera_rays_offset", "rt_camera_rays_offset_host", "rt_film_splat",
     "rt_sample_budget", "rt_sample_list_temp_bytes", "rt_sample_list", "rt_film_offsets_listed", "rt_camera_rays_listed", "rt_film_splat_listed",
     "rt_denoise_temp_bytes", "rt_denoise_atrous", "rt_denoise_atrous_host",
@@ -286,6 +287,8 @@ HOST_SYMBOLS = [
 # librt_host.so's CPU forms of the environment queries, declared in include/rt_environment_host.h (which says why they have a header and
 # a list of their own: they are no image-side rt_X / rt_X_cpu pairs)
 ENVIRONMENT_HOST_SYMBOLS = ["rt_environment_lookup_cpu", "rt_environment_table_cpu", "rt_environment_samples_cpu", "rt_environment_fold_cpu"]
+# ... and of the lobe queries, declared in include/rt_lobe_host.h for the same reason
+LOBE_HOST_SYMBOLS = ["rt_lobe_samples_cpu", "rt_lobe_pdf_cpu", "rt_environment_pdf_cpu", "rt_mis_weigh_cpu"]
 
 _amd = None
 _host = None
@@ -367,6 +370,11 @@ def host_lib() -> C.CDLL:
                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.rt_environment_fold_cpu.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_void_p, C.c_void_p]
+        lib.rt_lobe_samples_cpu.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.rt_lobe_pdf_cpu.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+        lib.rt_environment_pdf_cpu.argtypes = [C.POINTER(EnvironmentDesc), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        lib.rt_mis_weigh_cpu.argtypes = [C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p]
         lib.rt_host_last_error.restype = C.c_char_p
         _host = lib
     return _host
@@ -491,6 +499,11 @@ def amd_lib() -> C.CDLL:
                                             C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.rt_environment_fold.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.rt_lobe_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.rt_lobe_pdf.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+        lib.rt_environment_pdf.argtypes = [C.POINTER(EnvironmentDesc), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.rt_mis_weigh.argtypes = [C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.rt_material_hits.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         lib.rt_material_hits_host.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         lib.rt_probe_surfaces.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]

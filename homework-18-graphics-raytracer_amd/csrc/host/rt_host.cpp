@@ -30,6 +30,7 @@
 #include "../rt_area_light.h"
 #include "../rt_hemisphere.h"
 #include "../rt_environment.h"
+#include "../rt_lobe.h"
 
 using rt::V3;
 
@@ -773,6 +774,82 @@ int rt_environment_fold_cpu(const unsigned char *valid, const float *shiness, si
     if (const char *bad = rt::hemisphere_limits(spp, false, 0u, 0u)) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + bad);
     const rt::EnvFold f = {(uint64_t)n, spp, asks, reinterpret_cast<const uint32_t *>(shadow_hits), radiance, diffuse, specular, open, rgb};
     for (size_t i = 0; i < n; ++i) rt::env_fold_record(f, i, valid[i] != 0, shiness[i]);
+    return RT_OK;
+}
+
+/* ---- lobe queries: the sampler, the two densities and the weights on the CPU (include/rt_amd.h "lobe queries"; the arithmetic is rt_lobe.h's, shared with the device) ---- */
+
+static rt::LobeSurface lobe_surface_of(const rt_surface &s, const float *normal, const float *view) {
+    return rt::lobe_surface(rt::v3p(normal ? normal : s.shading_normal), rt::v3p(view), s.shiness, s.smoothness);
+}
+
+int rt_lobe_samples_cpu(const rt_surface *surfaces, const float *normals, const float *view, const uint32_t *ids, size_t n, uint32_t spp,
+                        uint32_t pattern, uint32_t seed, float *dirs, float *pdf, unsigned char *lobe, unsigned char *asks) {
+    const char *const who = "rt_lobe_samples_cpu: ";
+    if (const int rc = hemisphere_counts(who, n, spp)) return rc;
+    if (n == 0) return RT_OK;
+    if (!surfaces || !view || !dirs || !pdf) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + "null surface, view, direction or pdf pointer");
+    if (const char *bad = rt::hemisphere_limits(spp, true, pattern, RT_HEMISPHERE_SHADING)) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + bad);
+    const uint32_t k = rt::film_strata(spp), seed_h = rt::hemisphere_seed(seed);
+    for (size_t i = 0; i < n; ++i) {
+        const bool valid = surfaces[i].valid != 0u;
+        const rt::LobeSurface l = lobe_surface_of(surfaces[i], normals ? normals + 3u * i : nullptr, view + 3u * i);
+        for (uint32_t s = 0; s < spp; ++s) {
+            const size_t e = (size_t)s * n + i;
+            const rt::LobeSample p = rt::lobe_sample(l, pattern, k, ids ? ids[i] : (uint32_t)i, seed_h, s, valid);
+            dirs[3u * e] = p.dir.x;
+            dirs[3u * e + 1u] = p.dir.y;
+            dirs[3u * e + 2u] = p.dir.z;
+            pdf[e] = valid ? p.pdf : 0.0f;
+            if (lobe) lobe[e] = p.specular ? 1 : 0;
+            if (asks) asks[e] = p.ok ? 1 : 0;
+        }
+    }
+    return RT_OK;
+}
+
+int rt_lobe_pdf_cpu(const rt_surface *surfaces, size_t n, const float *view, const float *dirs, uint32_t n_probes, uint32_t normal_kind, float *pdf) {
+    const char *const who = "rt_lobe_pdf_cpu: ";
+    if ((uint64_t)n >= (1ull << 32) || (uint64_t)n * n_probes >= (1ull << 32))
+        return fail(RT_ERR_UNSUPPORTED, std::string(who) + "2^32 (record, probe) pairs or more (pass the probes in several calls)");
+    if (n == 0 || n_probes == 0) return RT_OK;
+    if (!surfaces || !view || !dirs || !pdf) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + "null surface, view, direction or pdf pointer");
+    if (const char *bad = rt::lobe_pdf_limits(normal_kind)) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + bad);
+    for (size_t i = 0; i < n; ++i) {
+        const bool valid = surfaces[i].valid != 0u;
+        const rt::LobeSurface l = lobe_surface_of(surfaces[i], nullptr, view + 3u * i);
+        for (uint32_t q = 0; q < n_probes; ++q) {
+            const size_t e = (size_t)q * n + i;
+            pdf[e] = valid ? rt::lobe_pdf(l, rt::v3p(dirs + 3u * e), true) : 0.0f;
+        }
+    }
+    return RT_OK;
+}
+
+int rt_environment_pdf_cpu(const rt_environment *env, const void *table, const float *dirs, size_t count, float *pdf, uint32_t *texel) {
+    const char *const who = "rt_environment_pdf_cpu: ";
+    if ((uint64_t)count >= (1ull << 32)) return fail(RT_ERR_UNSUPPORTED, std::string(who) + "2^32 directions or more (query them in several calls)");
+    if (const int rc = environment_ok(who, env)) return rc;
+    if (count == 0) return RT_OK;
+    if (!table || !dirs || !pdf) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + "null table, direction or pdf pointer");
+    const rt::EnvTable t = rt::env_table_view(*env, table);
+    for (size_t e = 0; e < count; ++e) {
+        uint32_t at;
+        pdf[e] = rt::env_pdf(*env, t, rt::v3p(dirs + 3u * e), &at);
+        if (texel) texel[e] = at;
+    }
+    return RT_OK;
+}
+
+int rt_mis_weigh_cpu(size_t count, const float *pdf_own, uint32_t n_own, const float *pdf_other, uint32_t n_other, uint32_t heuristic, int divide_by_own,
+                     float *weight, float *rgb) {
+    const char *const who = "rt_mis_weigh_cpu: ";
+    if ((uint64_t)count >= (1ull << 32)) return fail(RT_ERR_UNSUPPORTED, std::string(who) + "2^32 entries or more (weigh them in several calls)");
+    if (count == 0) return RT_OK;
+    if (!pdf_own || (!weight && !rgb)) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + "null own-pdf, or weight and rgb (one of the two is given) pointer");
+    if (const char *bad = rt::mis_limits(heuristic)) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + bad);
+    const rt::MisWeigh m = rt::mis_weigh_call((uint64_t)count, pdf_own, n_own, pdf_other, n_other, heuristic, divide_by_own != 0, weight, rgb);
+    for (uint64_t e = 0; e < count; ++e) rt::mis_weigh_entry(m, e);
     return RT_OK;
 }
 

@@ -48,7 +48,7 @@ RT_FILM_HD V3 env_texel(const rt_environment &e, uint32_t x, uint32_t y) { retur
 /* dir -> (x_f, y_f) in [0, W] x [0, H]; false: a zero or non-finite direction.  d = dir / |dir|, theta = acosf(clamp(d.y)),
  * phi = atan2f(d.z, d.x) - rotation, x_f = phi * W / 6.2831855f wrapped into one turn by x_f - floorf(x_f / W) * W, y_f = theta * H /
  * 3.1415927f; both are then clamped to their range (a NaN, from a rotation that is not finite, becomes 0) */
-RT_FILM_HD bool env_texel_point(const rt_environment &e, V3 dir, float *x_f, float *y_f) {
+RT_FILM_HD bool env_texel_point(const rt_environment &e, V3 dir, float *x_f, float *y_f, float *theta_out) {
     const float len = magnitude(dir);
     if (!(len > 0.0f) || !env_finite(len)) return false;
     const V3 d = dir / len;
@@ -59,7 +59,12 @@ RT_FILM_HD bool env_texel_point(const rt_environment &e, V3 dir, float *x_f, flo
     x = x - floorf(x / w) * w;
     *x_f = fminf(fmaxf(x, 0.0f), w);
     *y_f = fminf(fmaxf(theta * h / 3.1415927f, 0.0f), h);
+    *theta_out = theta;
     return true;
+}
+RT_FILM_HD bool env_texel_point(const rt_environment &e, V3 dir, float *x_f, float *y_f) {
+    float theta; /* the lobe queries' density reads it (rt_lobe.h) */
+    return env_texel_point(e, dir, x_f, y_f, &theta);
 }
 
 /* a * (1 - t) + b * t, per channel */

@@ -485,8 +485,8 @@ int rt_area_light_fold(const rt_scene *scene, const rt_hit *d_hits, size_t n, ui
  * 1 .. 64, RT_FILM_CENTER, an unknown pattern, a stratified spp that is no square or an unknown normal_kind RT_ERR_INVALID_ARGUMENT
  * with a message that names the limit; only then is the scene read.
  * Not covered: _host forms of these two (they sit between device calls; rt_hemisphere_dirs_cpu and rt_hemisphere_fold_cpu of
- * include/rt_host.h are the CPU forms); rt_multi_* forms; hemisphere sampling inside rt_render_*; other distributions — for those a
- * caller overwrites d_dirs and d_rays; more than one bounce. */
+ * include/rt_host.h are the CPU forms); rt_multi_* forms; hemisphere sampling inside rt_render_*; other distributions — the
+ * surface's Phong lobes are the lobe queries' below, for any other a caller overwrites d_dirs and d_rays; more than one bounce. */
 #define RT_HEMISPHERE_SHADING 0u   /* N = adjust_normal(material.normal, hit.normal) */
 #define RT_HEMISPHERE_GEOMETRIC 1u /* N = hit.normal */
 
@@ -574,9 +574,9 @@ int rt_hemisphere_fold(const rt_scene *scene, const rt_hit *d_hits, size_t n, ui
  * check them; only then is the scene read.
  * Not covered: octahedral or cube maps; mip levels (a lookup takes one or four texels whatever the ray's footprint); the sky inside
  * rt_render_whitted, rt_trace_rays or the distributed pass (the tree loop written from the public calls takes it: trace_rays_levels in
- * Python); Refraction::Infinite rays (the refraction queries hand them back, a caller looks them up itself); rt_multi_* forms; multiple
- * importance sampling with the hemisphere sampler; _host forms (rt_environment_*_cpu of include/rt_environment_host.h are the CPU
- * forms). */
+ * Python); Refraction::Infinite rays (the refraction queries hand them back, a caller looks them up itself); rt_multi_* forms; _host
+ * forms (rt_environment_*_cpu of include/rt_environment_host.h are the CPU forms).  Multiple importance sampling with the surface's
+ * own lobes is the lobe queries' below: rt_environment_pdf returns the density rt_environment_rays divides by. */
 #define RT_ENV_NEAREST 0u
 #define RT_ENV_BILINEAR 1u
 #define RT_ENV_MAX_WIDTH 16384u
@@ -677,6 +677,90 @@ int rt_probe_surfaces(const rt_surface *d_surfaces, size_t n, const float *d_vie
 /* The same on HOST arrays. */
 int rt_probe_surfaces_host(const rt_surface *h_surfaces, size_t n, const float *h_view, const float *h_light_dirs, uint32_t n_probes,
                            float *h_diffuse, float *h_specular);
+
+/* ---- lobe queries: directions drawn from a surface's own Phong lobes, densities, and the weights that combine two samplers ---------
+
+ * rt_hemisphere_rays draws cosine-distributed directions and rt_environment_rays draws by the sky's brightness; neither looks at the
+ * surface's specular lobe, whose exponent reaches 1e5 in the reference scene (smoothness 1e-5): a glossy surface under a sky is black
+ * with fireflies, and a small sun over a rough surface is found by the table alone.  This block adds the third sampler, the density
+ * of any direction under each sampler, and the weight of multiple importance sampling on the device.  Its fold is
+ * rt_environment_fold: there is one weighting convention.  The sequences
+ *     one glossy bounce   rt_lobe_rays -> rt_trace_rays(d_rays -> d_radiance, all spp * n of them) -> rt_material_hits +
+ *                         rt_probe_surfaces(d_dirs) -> rt_mis_weigh(d_pdf, divide_by_own, no other: d_radiance /= pdf) ->
+ *                         rt_environment_fold(d_shadow_hits = NULL)
+ *     sky light, both samplers   the environment's samples as in "sky light on hits", with rt_environment_pdf(d_dirs) and
+ *                         rt_lobe_pdf(d_dirs) -> rt_mis_weigh(d_radiance, already over its density); the lobe's samples:
+ *                         rt_lobe_rays -> rt_cast_rays(d_rays) -> rt_environment_lookup(the casts' misses, into zeros) ->
+ *                         rt_environment_pdf(d_dirs) -> rt_mis_weigh(divide_by_own); each set through rt_environment_fold into one rgb
+ * are written out in INTEGRATION.md; DESIGN.md §3.33 has what they cost and what f32 does to the sampler at high exponents.
+ *
+ * The mixture.  With N chosen by normal_kind as the hemisphere queries choose it and V = -d_incoming[i].direction, what get_shade
+ * passes as view_direction, in single f32 operations in this order, none fused (csrc/rt_lobe.h, shared by both libraries):
+ *     e   = 1 / (smoothness + 1.1920929e-7f)                           get_specular's exponent
+ *     R   = (2 * dot(V, N)) * N - V                                    get_specular's `reflected` with V in the place of the light
+ *     p_s = shiness > 0 ? (shiness < 1 ? shiness : 1) : 0              NaN reads as 0
+ *     pdf(dir) = ((1 - p_s) * max(dot(dir, N), 0)) * 0.31830987f + ((p_s * (e + 1)) * 0.15915494f) * powf(max(dot(dir, R), 0), e)
+ * max(x, 0) is x > 0 ? x : 0 and powf is rtdm::powf, skipped for the +0 it would return exactly where get_specular skips it.
+ * specular(dir) / pdf(dir) on a surface of shiness 1 is the constant (e + 8) / (4 (e + 1)) times specular_color: that is why the lobe
+ * lies about R and not about N.
+ *
+ * The sample.  u_0 and u_1 are rt_hemisphere_rays' for (id, seed, s) — the same seed_h and the same pattern rules — and
+ *     u_2 = film_u(id, film_mix(seed_h ^ 0x27d4eb2fu), s, 0)           never stratified;  lobe = u_2 < p_s
+ *     lobe 0   rt_hemisphere_rays' direction about N
+ *     lobe 1   c = powf(u_0, 1 / (e + 1));  r = sqrt(max(1 - c * c, 0));  phi = 6.2831855f * u_1
+ *              dir = adjust_normal((r * cosf(phi), r * sinf(phi), c), R)
+ * and the density written is pdf(dir) above, evaluated at the direction produced, not taken from c.
+ *
+ * Per-entry arrays are sample-major, entry k = s * n + i.  The record rules are those of the hit queries.  Every pointer but an
+ * environment's descriptor is a device pointer; every call is stream-ordered and asynchronous on hip_stream (NULL = default stream), is
+ * one kernel with one record or entry per lane and 256 lanes per workgroup, allocates nothing, uses no workspace and may be captured
+ * into a HIP graph at once.
+ * Not covered: _host and rt_multi_* forms (rt_*_cpu of include/rt_lobe_host.h are the CPU forms); lobes inside rt_render_*; refraction
+ * lobes; more than one bounce; any selection probability other than shiness. */
+#define RT_MIS_BALANCE 0u /* w = a / (a + b) */
+#define RT_MIS_POWER 1u   /* w = a * a / (a * a + b * b) */
+
+/* spp directions per hit from the mixture.  d_ids as rt_hemisphere_rays'; d_incoming[i] is Hit.ray of d_hits[i], as in rt_shade_hits.
+ *   d_dirs[3k ..]   dir; zero words for a "no hit" record
+ *   d_lobe[k]       1: drawn from the specular lobe; 0: from the diffuse one, or "no hit"
+ *   d_pdf[k]        pdf(dir), the mixture's; +0 for a "no hit" record
+ *   d_asks[k]       the record is a hit, the pdf is finite and > 0, and !(dot(dir, N) <= 0)
+ *   d_rays[k]       rt_hemisphere_rays' shadow ray for dir; all-zero words where d_asks[k] is 0
+ * With every shiness 0 the call writes rt_hemisphere_rays' d_rays, d_asks and d_dirs bit for bit (a cosine below 2^-126 * pi, whose
+ * density rounds to 0, aside).
+ * Checked before any device work as the hemisphere queries check, in their order and with their messages; d_incoming is among the
+ * required pointers. */
+int rt_lobe_rays(const rt_scene *scene, const rt_hit *d_hits, const rt_ray *d_incoming, size_t n, const uint32_t *d_ids, uint32_t spp, uint32_t pattern,
+                 uint32_t seed, uint32_t normal_kind, rt_ray *d_rays, unsigned char *d_asks, float *d_dirs, float *d_pdf, unsigned char *d_lobe,
+                 void *hip_stream);
+/* d_pdf[k] = pdf(d_dirs[3k ..]) on d_surfaces[i] with V = d_view[3i ..], k = p * n + i over n_probes directions per record — rt_probe_surfaces'
+ * layout and, like it, NO SCENE: N is the record's shading_normal, so normal_kind is RT_HEMISPHERE_SHADING, and RT_HEMISPHERE_GEOMETRIC
+ * is refused (a surface record carries no geometric normal).  valid == 0 gives +0.  For rt_material_hits' surfaces and d_view = -d_incoming's
+ * direction, the density of rt_lobe_rays' own d_dirs is its d_pdf bit for bit.
+ * Checked in this order: n >= 2^32 or n * n_probes >= 2^32 is RT_ERR_UNSUPPORTED; n == 0 or n_probes == 0 is RT_OK and launches nothing; a
+ * null pointer, then the normal_kind, RT_ERR_INVALID_ARGUMENT. */
+int rt_lobe_pdf(const rt_surface *d_surfaces, size_t n, const float *d_view, const float *d_dirs, uint32_t n_probes, uint32_t normal_kind, float *d_pdf,
+                void *hip_stream);
+/* The density of `count` directions (3 floats each) under an environment's table: what rt_environment_rays keeps to itself, and what a
+ * lobe sample needs when it escapes to the sky.  The direction goes through the lookup's own map to (x_f, y_f) and theta;
+ * x = min((uint32)x_f, W - 1), y likewise; q = C[y][x] - C[y][x - 1] and
+ *     pdf = (float)((double)q / (double)total) * (float)(W * H) / (19.739209f * sinf(theta))
+ * +0 for a zero or non-finite direction, a table whose header names another size, total == 0, and a pdf that is not finite.  d_texel:
+ * NULL, or count u32: y * W + x, 0 where no texel is named.  The loads are bounded by the image's size, not by what the table holds.
+ * Checked in this order: count >= 2^32 is RT_ERR_UNSUPPORTED; the descriptor as the environment queries check it; count == 0 is RT_OK; a
+ * null table, direction or pdf pointer RT_ERR_INVALID_ARGUMENT. */
+int rt_environment_pdf(const rt_environment *env, const void *d_table, const float *d_dirs, size_t count, float *d_pdf, uint32_t *d_texel,
+                       void *hip_stream);
+/* Per entry k of `count`: a = (float)n_own * d_pdf_own[k], b = (float)n_other * d_pdf_other[k], w as the heuristic says.  An a that is
+ * not finite or <= 0 gives w = +0.  Otherwise, with d_pdf_other NULL or n_other == 0 there is no other strategy: w = 1, nothing is
+ * computed and — without divide_by_own — d_rgb is not touched.
+ *   d_weight[k]     w (may be NULL)
+ *   d_rgb[3k ..]    *= w, or with divide_by_own *= (w / d_pdf_own[k]); a w of 0 multiplies by +0 either way (may be NULL; not both)
+ * Each of a, b, the sum and the quotient rounds to f32 once, so the two strategies' balance weights of one direction sum to 1 within
+ * 2^-22.  Checked in this order: count >= 2^32 is RT_ERR_UNSUPPORTED; count == 0 is RT_OK; a null d_pdf_own, or d_weight and d_rgb both
+ * NULL, then an unknown heuristic, RT_ERR_INVALID_ARGUMENT. */
+int rt_mis_weigh(size_t count, const float *d_pdf_own, uint32_t n_own, const float *d_pdf_other, uint32_t n_other, uint32_t heuristic, int divide_by_own,
+                 float *d_weight, float *d_rgb, void *hip_stream);
 
 /* ---- refraction queries: get_refract bounce by bounce on caller-supplied hits ------------------------------
 
