@@ -236,6 +236,12 @@ class EnvironmentDesc(C.Structure):
                 ("filter", C.c_uint32)]
 
 
+class TextureDesc(C.Structure):
+    """rt_texture"""
+    _fields_ = [("d_texels", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32), ("n_levels", C.c_uint32), ("filter", C.c_uint32),
+                ("wrap_u", C.c_uint32), ("wrap_v", C.c_uint32), ("scale", C.c_float * 2), ("offset", C.c_float * 2)]
+
+
 AMD_SYMBOLS = [
     "rt_abi_version", "rt_last_error", "rt_device_count", "rt_set_device", "rt_frame_rows", "rt_frame_pixels",
     "rt_scene_create", "rt_scene_destroy", "rt_render_whitted", "rt_render_whitted_host", "rt_set_option", "rt_set_variant",
@@ -253,6 +259,8 @@ AMD_SYMBOLS = [
     "rt_environment_lookup", "rt_environment_table_bytes", "rt_environment_table", "rt_environment_rays", "rt_environment_fold",
     "rt_material_hits", "rt_material_hits_host", "rt_probe_surfaces", "rt_probe_surfaces_host",
     "rt_lobe_rays", "rt_lobe_pdf", "rt_environment_pdf", "rt_mis_weigh",
+    "rt_texture_levels", "rt_texture_pyramid_floats", "rt_texture_pyramid", "rt_texture_footprint", "rt_texture_sample", "rt_texture_surfaces",
+    "rt_light_terms_surfaces",
     "rt_film_offsets", "rt_camera_rays_offset", "rt_camera_rays_offset_host", "rt_film_splat",
     "rt_sample_budget", "rt_sample_list_temp_bytes", "rt_sample_list", "rt_film_offsets_listed", "rt_camera_rays_listed", "rt_film_splat_listed",
     "rt_denoise_temp_bytes", "rt_denoise_atrous", "rt_denoise_atrous_host",
@@ -289,6 +297,8 @@ HOST_SYMBOLS = [
 ENVIRONMENT_HOST_SYMBOLS = ["rt_environment_lookup_cpu", "rt_environment_table_cpu", "rt_environment_samples_cpu", "rt_environment_fold_cpu"]
 # ... and of the lobe queries, declared in include/rt_lobe_host.h for the same reason
 LOBE_HOST_SYMBOLS = ["rt_lobe_samples_cpu", "rt_lobe_pdf_cpu", "rt_environment_pdf_cpu", "rt_mis_weigh_cpu"]
+# ... and of the texture queries, declared in include/rt_texture_host.h
+TEXTURE_HOST_SYMBOLS = ["rt_texture_pyramid_cpu", "rt_texture_footprint_cpu", "rt_texture_sample_cpu", "rt_texture_surfaces_cpu"]
 
 _amd = None
 _host = None
@@ -375,6 +385,11 @@ def host_lib() -> C.CDLL:
         lib.rt_lobe_pdf_cpu.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
         lib.rt_environment_pdf_cpu.argtypes = [C.POINTER(EnvironmentDesc), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         lib.rt_mis_weigh_cpu.argtypes = [C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p]
+        lib.rt_texture_pyramid_cpu.argtypes = [C.POINTER(TextureDesc)]
+        lib.rt_texture_footprint_cpu.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p]
+        lib.rt_texture_sample_cpu.argtypes = [C.POINTER(TextureDesc), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
+        lib.rt_texture_surfaces_cpu.argtypes = [C.POINTER(TextureDesc), C.POINTER(TextureDesc), C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32,
+                                                C.c_uint32, C.c_void_p]
         lib.rt_host_last_error.restype = C.c_char_p
         _host = lib
     return _host
@@ -504,6 +519,17 @@ def amd_lib() -> C.CDLL:
         lib.rt_lobe_pdf.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
         lib.rt_environment_pdf.argtypes = [C.POINTER(EnvironmentDesc), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.rt_mis_weigh.argtypes = [C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.rt_texture_levels.argtypes = [C.c_uint32, C.c_uint32]
+        lib.rt_texture_levels.restype = C.c_uint32
+        lib.rt_texture_pyramid_floats.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
+        lib.rt_texture_pyramid_floats.restype = C.c_size_t
+        lib.rt_texture_pyramid.argtypes = [C.POINTER(TextureDesc), C.c_void_p]
+        lib.rt_texture_footprint.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.rt_texture_sample.argtypes = [C.POINTER(TextureDesc), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.rt_texture_surfaces.argtypes = [C.POINTER(TextureDesc), C.POINTER(TextureDesc), C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32,
+                                            C.c_void_p, C.c_void_p]
+        lib.rt_light_terms_surfaces.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.rt_material_hits.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         lib.rt_material_hits_host.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         lib.rt_probe_surfaces.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]

@@ -290,11 +290,13 @@ def trace_rays_levels(scene: Scene, rays, max_depth: int, contribution=1.0, out=
     return _trace_rays_levels(scene, rays, max_depth, contribution, out, ray_count, stream, level_capacity, check, overflow, level_counts, open_casts, None)
 
 
-def _trace_rays_levels(scene, rays, max_depth, contribution, out, ray_count, stream, level_capacity, check, overflow, level_counts, open_casts, environment):
+def _trace_rays_levels(scene, rays, max_depth, contribution, out, ray_count, stream, level_capacity, check, overflow, level_counts, open_casts, environment,
+                       shade_step=None):
     """trace_rays_levels, and environment.trace_rays_levels: with ``environment`` (an environment.Environment) every level's tree_fold is
     followed by environment.lookup on that level's rays, hits, count and parent links, which replaces the +0 the fold wrote for the
     level's misses before the parent level folds; the levels' rays are then kept per level instead of in two buffers used in turn.  With
-    None the calls enqueued are trace_rays_levels' as they always were."""
+    None the calls enqueued are trace_rays_levels' as they always were.  ``shade_step`` (textures.trace_rays_levels): a callable
+    (records of room, device) -> shade(hits, rays, out), made once, up front, which takes the place of the level's get_shade."""
     torch = _torch()
     n, dev = _tensor(rays, "rays", "int32", (None, 11)).shape[0], rays.device
     out = _out_tensor(out, (n, 3), "float32", dev)
@@ -361,6 +363,8 @@ def _trace_rays_levels(scene, rays, max_depth, contribution, out, ray_count, str
         counts.zero_()  # a level without room is not visited by any kernel: its count stays 0
         flags[:top].fill_(1)
         shade_level, refract = _level_steps(scene, open_casts, top, depth > 0, dev, ray_count, s)
+        if shade_step is not None:
+            shade_level = shade_step(top, dev)
     select_records(flags[:top], identity, n_all, stream=s)  # 0 .. top-1: the child levels are cast through it with their own counts
     cur_rays, cur_contribution = rays, root_contribution
     for k in range(depth + 1):

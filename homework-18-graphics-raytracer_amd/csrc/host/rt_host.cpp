@@ -31,6 +31,7 @@
 #include "../rt_hemisphere.h"
 #include "../rt_environment.h"
 #include "../rt_lobe.h"
+#include "../rt_texture.h"
 
 using rt::V3;
 
@@ -850,6 +851,102 @@ int rt_mis_weigh_cpu(size_t count, const float *pdf_own, uint32_t n_own, const f
     if (const char *bad = rt::mis_limits(heuristic)) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + bad);
     const rt::MisWeigh m = rt::mis_weigh_call((uint64_t)count, pdf_own, n_own, pdf_other, n_other, heuristic, divide_by_own != 0, weight, rgb);
     for (uint64_t e = 0; e < count; ++e) rt::mis_weigh_entry(m, e);
+    return RT_OK;
+}
+
+/* ---- texture queries: the pyramid, the footprint, the lookup and the surface edit on the CPU (include/rt_amd.h "texture queries"; the arithmetic is rt_texture.h's, shared with the device) ---- */
+
+static int texture_ok(const char *who, const rt_texture *tex) {
+    bool unsupported;
+    if (const char *bad = rt::texture_limits(tex, &unsupported)) return fail(unsupported ? RT_ERR_UNSUPPORTED : RT_ERR_INVALID_ARGUMENT, std::string(who) + bad);
+    return RT_OK;
+}
+
+static int texture_count(const char *who, size_t n) {
+    if ((uint64_t)n >= (1ull << 32)) return fail(RT_ERR_UNSUPPORTED, std::string(who) + "2^32 records or more (checked first; query them in several calls)");
+    return RT_OK;
+}
+
+int rt_texture_pyramid_cpu(const rt_texture *tex) {
+    if (const int rc = texture_ok("rt_texture_pyramid_cpu: ", tex)) return rc;
+    const rt::TexView t = rt::tex_view(*tex);
+    float *const texels = const_cast<float *>(tex->d_texels);
+    for (uint32_t level = 1u; level < t.n_levels; ++level) {
+        const uint32_t w = rt::tex_extent(t.width, level), h = rt::tex_extent(t.height, level);
+        const rt::TexLevel src = {t.texels + 3u * (uint64_t)t.start[level - 1u], rt::tex_extent(t.width, level - 1u), rt::tex_extent(t.height, level - 1u)};
+        float *const out = texels + 3u * (uint64_t)t.start[level];
+        for (uint32_t y = 0; y < h; ++y)
+            for (uint32_t x = 0; x < w; ++x) {
+                const V3 value = rt::tex_reduce(src, x, y);
+                float *const o = out + 3u * ((uint64_t)y * w + x);
+                o[0] = value.x, o[1] = value.y, o[2] = value.z;
+            }
+    }
+    return RT_OK;
+}
+
+int rt_texture_footprint_cpu(const rt_scene_desc *scene, const rt_hit *hits, const rt_ray *incoming, size_t n, float spread, const float *width0,
+                             float *footprint) {
+    const char *const who = "rt_texture_footprint_cpu: ";
+    if (const int rc = texture_count(who, n)) return rc;
+    if (!scene) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + "null scene");
+    if (n == 0) return RT_OK;
+    if (!hits || !incoming || !footprint) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + "null hit, incoming-ray or footprint pointer");
+    if ((scene->n_triangles && !scene->triangles) || (scene->n_spheres && !scene->spheres))
+        return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + "null triangle or sphere array in the scene description");
+    for (size_t i = 0; i < n; ++i) {
+        const uint32_t *const hit = reinterpret_cast<const uint32_t *>(hits + i);
+        const uint32_t kind = hit[0], index = hit[1];
+        const bool valid = kind <= 1u && hit[RT_TEX_HIT_OBJECT] < scene->n_materials;
+        float ratio = 0.0f;
+        bool ok = false;
+        if (valid && kind == 1u && index < scene->n_triangles) {
+            const rt_vertex *const v = scene->triangles[index].vertices;
+            ratio = rt::tex_triangle_ratio(rt::v3p(v[0].position), rt::v3p(v[1].position), rt::v3p(v[2].position), v[0].uv[0], v[0].uv[1], v[1].uv[0],
+                                           v[1].uv[1], v[2].uv[0], v[2].uv[1], &ok);
+        } else if (valid && kind == 0u && index < scene->n_spheres) {
+            ratio = rt::tex_sphere_ratio(scene->spheres[index].radius, &ok);
+        }
+        footprint[i] = rt::tex_footprint_record(hit, reinterpret_cast<const uint32_t *>(incoming + i), width0 ? width0[i] : 0.0f, spread, ratio, ok);
+    }
+    return RT_OK;
+}
+
+int rt_texture_sample_cpu(const rt_texture *tex, const float *uv, size_t uv_stride_words, const float *footprint, size_t n, float *out,
+                          size_t out_stride_words) {
+    const char *const who = "rt_texture_sample_cpu: ";
+    if (const int rc = texture_count(who, n)) return rc;
+    if (const int rc = texture_ok(who, tex)) return rc;
+    if (n == 0) return RT_OK;
+    if (!uv || !out) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + "null uv or output pointer");
+    if (const char *bad = rt::tex_stride_limits(uv_stride_words, out_stride_words)) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + bad);
+    const rt::TexSample a = {rt::tex_view(*tex), uv, (uint64_t)uv_stride_words, footprint, (uint64_t)n, out, (uint64_t)out_stride_words};
+    for (uint64_t i = 0; i < a.n; ++i) rt::tex_sample_record(a, i);
+    return RT_OK;
+}
+
+int rt_texture_surfaces_cpu(const rt_texture *diffuse_tex, const rt_texture *normal_tex, const rt_hit *hits, const float *footprint, size_t n,
+                            uint32_t object_index, uint32_t flags, rt_surface *surfaces) {
+    const char *const who = "rt_texture_surfaces_cpu: ";
+    if (const int rc = texture_count(who, n)) return rc;
+    if (diffuse_tex)
+        if (const int rc = texture_ok(who, diffuse_tex)) return rc;
+    if (normal_tex)
+        if (const int rc = texture_ok(who, normal_tex)) return rc;
+    if (n == 0) return RT_OK;
+    if (!hits || !surfaces) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + "null hit or surface pointer");
+    if (const char *bad = rt::tex_surface_limits(flags)) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + bad);
+    if (!diffuse_tex && !normal_tex) return RT_OK;
+    rt::TexSurfaces a = {};
+    if (diffuse_tex) a.diffuse = rt::tex_view(*diffuse_tex);
+    if (normal_tex) a.normal = rt::tex_view(*normal_tex);
+    a.has_diffuse = diffuse_tex != nullptr, a.has_normal = normal_tex != nullptr;
+    a.hits = reinterpret_cast<const uint32_t *>(hits);
+    a.footprint = footprint;
+    a.n = (uint64_t)n;
+    a.object_index = object_index, a.flags = flags;
+    a.surfaces = reinterpret_cast<uint32_t *>(surfaces);
+    for (uint64_t i = 0; i < a.n; ++i) rt::tex_surface_record(a, i);
     return RT_OK;
 }
 

@@ -762,6 +762,119 @@ int rt_environment_pdf(const rt_environment *env, const void *d_table, const flo
 int rt_mis_weigh(size_t count, const float *d_pdf_own, uint32_t n_own, const float *d_pdf_other, uint32_t n_other, uint32_t heuristic, int divide_by_own,
                  float *d_weight, float *d_rgb, void *hip_stream);
 
+/* ---- texture queries: mip-mapped image textures and normal maps on caller-supplied hits ------------------------------
+
+ * The reference's GenerativeMaterial takes two closures of uv, diffuse_fn and normal_fn (materials.rs:70-103); rt_material enumerates
+ * the three bodies main.rs holds and nothing else, so every rt_hit carries a uv and no surface can show an image.  This block is an
+ * approx() whose diffuse_fn / normal_fn read an image, followed by the unchanged adjust_normal: rt_texture_surfaces edits the
+ * rt_surface records rt_material_hits wrote, and rt_light_terms_surfaces is rt_light_terms with the material and the shading normal
+ * taken from those records, so that an edited surface reaches get_shade's own lights as it reaches rt_probe_surfaces.  The sequence
+ *     rt_material_hits -> [rt_texture_footprint ->] rt_texture_surfaces per texture binding -> rt_light_rays -> casts ->
+ *     rt_light_terms_surfaces -> rt_light_fold
+ * is written out in INTEGRATION.md; DESIGN.md §3.34 has what the calls cost.
+ *
+ * The texture.  A pyramid of row-major levels of 3 floats per texel (linear RGB, or a tangent-space vector), level 0 first, level l of
+ * extent max(1, width >> l) by max(1, height >> l); a full pyramid has rt_texture_levels(w, h) = 1 + floor(log2(max(w, h))) levels.
+ * The caller owns the memory and fills level 0; rt_texture_pyramid makes the others.  uv maps to the point p = uv * scale + offset and,
+ * on a level of extent (w, h), to the texel-space coordinate s = p * (float)extent per axis.  All arithmetic is csrc/rt_texture.h's,
+ * single f32 and u32 operations in the order given here, none fused, shared by both libraries.
+ *
+ * Every device pointer is stream-ordered and asynchronous on hip_stream (NULL = default stream); no call allocates or uses a workspace
+ * and each may be captured into a HIP graph at once.  A descriptor is read on the host, at the call.
+ * Not covered: sRGB or 8-bit texels; anisotropic filtering; mirror wrap; specular, shiness or transparency maps; textures inside
+ * rt_render_*, rt_trace_rays or the distributed pass; _host and rt_multi_* forms (rt_*_cpu of include/rt_texture_host.h are the CPU
+ * forms); mip levels for the environment. */
+#define RT_TEX_NEAREST 0u
+#define RT_TEX_BILINEAR 1u
+#define RT_TEX_TRILINEAR 2u
+#define RT_TEX_REPEAT 0u
+#define RT_TEX_CLAMP 1u
+#define RT_TEX_MAX_SIDE 16384u
+#define RT_TEX_MODULATE 1u            /* rt_texture_surfaces: diffuse_color *= sample, not = sample */
+#define RT_TEX_NORMALIZE 2u           /* rt_texture_surfaces: normal = v / |v| */
+#define RT_TEX_ALL_OBJECTS 0xffffffffu
+typedef struct rt_texture {
+    const float *d_texels;  /* the whole pyramid: rt_texture_pyramid_floats(width, height, n_levels) floats */
+    uint32_t width, height; /* of level 0: 1 .. RT_TEX_MAX_SIDE each */
+    uint32_t n_levels;      /* 1 .. rt_texture_levels(width, height); 1: level 0 only */
+    uint32_t filter;        /* RT_TEX_NEAREST, RT_TEX_BILINEAR, RT_TEX_TRILINEAR */
+    uint32_t wrap_u, wrap_v; /* RT_TEX_REPEAT, RT_TEX_CLAMP */
+    float scale[2], offset[2];
+} rt_texture;               /* 48 bytes */
+
+/* 1 + floor(log2(max(width, height))); 0 for a side of 0.  Host arithmetic. */
+uint32_t rt_texture_levels(uint32_t width, uint32_t height);
+/* The floats of levels 0 .. n_levels - 1: 3 * sum of the extents' products; 0 for a side of 0 or above RT_TEX_MAX_SIDE, n_levels 0 or
+ * above rt_texture_levels.  Host arithmetic. */
+size_t rt_texture_pyramid_floats(uint32_t width, uint32_t height, uint32_t n_levels);
+
+/* Levels 1 .. n_levels - 1 from level 0, in place in tex->d_texels: the exact box filter for any extent, x before y.  Along an axis of
+ * the source level, destination texel x of a source p(0 ..):
+ *     extent 1         p(0)
+ *     extent 2m        (p(2x) + p(2x + 1)) * 0.5f
+ *     extent 2m + 1    (((float)(m - x) * p(2x) + (float)m * p(2x + 1)) + (float)(1 + x) * p(2x + 2)) / (float)(2m + 1)
+ * The three integer weights are what of each source texel lies under the destination texel: no column is dropped.  The rows a
+ * destination texel covers are reduced along x first, then those up to three partial rows along y by the same rule.  One launch per
+ * level while the source level is above 32 texels either way; from the first level whose source is at most 32 x 32, one workgroup
+ * makes all the remaining levels in one launch through LDS.  Each level is computed from the f32 values of the one before, so both
+ * forms give the same bits.  A texel that is not finite spreads by the arithmetic.
+ * Checked before any device work, in this order: a null texture or null texels, a side of 0 — RT_ERR_INVALID_ARGUMENT; a side above
+ * RT_TEX_MAX_SIDE — RT_ERR_UNSUPPORTED; n_levels, filter, wrap — RT_ERR_INVALID_ARGUMENT.  n_levels == 1 launches nothing. */
+int rt_texture_pyramid(const rt_texture *tex, void *hip_stream);
+
+/* The uv-space length a ray cone covers at each hit; it depends on no texture.  d_incoming[i] is Hit.ray of d_hits[i].
+ *     w = width0 + spread * magnitude(hit.position - ray.origin)         width0 = d_width0[i], or 0 with d_width0 NULL
+ *     c = max(|dot(D / |D|, hit.normal)|, 2^-6)                          D = ray.direction
+ *     ratio = sqrt(|du1 * dv2 - du2 * dv1| / magnitude(cross(e1, e2)))   a triangle: e_k = v_k.position - v_0.position, du_k and dv_k
+ *                                                                        likewise, of the scene's live vertices
+ *             0.28209479f / radius                                       a sphere
+ *     d_footprint[i] = w * ratio / c
+ * +0 — which selects level 0 — for a "no hit" record (the hit queries' rules), a primitive index outside its array, a primitive
+ * without area (a cross product of length 0, or not finite; a radius that is not finite and > 0), and any result that is not finite.
+ * Nothing is indexed with a word that was not checked against its array.  After rt_scene_update_vertices the new vertices are read.
+ * Checked in this order: n >= 2^32 is RT_ERR_UNSUPPORTED; a null scene RT_ERR_INVALID_ARGUMENT; n == 0 is RT_OK; a null hit,
+ * incoming-ray or footprint pointer RT_ERR_INVALID_ARGUMENT. */
+int rt_texture_footprint(const rt_scene *scene, const rt_hit *d_hits, const rt_ray *d_incoming, size_t n, float spread, const float *d_width0,
+                         float *d_footprint, void *hip_stream);
+
+/* The filtered lookup.  Record i reads (u, v) = d_uv[i * uv_stride_words ..] and writes 3 floats at d_out[i * out_stride_words ..]:
+ * with d_uv = (const float *)d_hits + 9 and a stride of 13 the uv is read inside rt_hit records, and the result may go into any
+ * field of a record without a copy.  d_footprint: n floats or NULL for 0.
+ *   RT_TEX_NEAREST    x = min((uint32)x_f, W - 1), x_f = s wrapped by s - floorf(s / W) * W (RT_TEX_REPEAT) or left as it is
+ *                     (RT_TEX_CLAMP), then clamped to [0, W]; y likewise
+ *   RT_TEX_BILINEAR   texel centres at + 0.5: xs = x_f - 0.5f, x0 = floorf(xs), fx = xs - x0, texels x0 and x0 + 1 wrapped or clamped;
+ *                     a * (1 - fx) + b * fx along x on both rows, then the same along y — rt_environment_lookup's mixing
+ *   RT_TEX_TRILINEAR  t = footprint * max(|scale_u| * W, |scale_v| * H); !(t > 1): level 0, bilinear; else l = the unbiased exponent
+ *                     of t and f = t * 2^-l - 1, both exact; the bilinear samples of levels l and l + 1 mixed by f; with l at or
+ *                     above the top level, that level alone.  No transcendental is evaluated.
+ * The other two filters read level 0 and no footprint.  A u or v that is not finite writes zeros.
+ * Checked in this order: n >= 2^32 is RT_ERR_UNSUPPORTED; the descriptor as rt_texture_pyramid checks it; n == 0 is RT_OK; a null uv
+ * or output pointer, then uv_stride_words < 2 or out_stride_words < 3, RT_ERR_INVALID_ARGUMENT. */
+int rt_texture_sample(const rt_texture *tex, const float *d_uv, size_t uv_stride_words, const float *d_footprint, size_t n, float *d_out,
+                      size_t out_stride_words, void *hip_stream);
+
+/* rt_surface records edited in place: approx() with diffuse_fn / normal_fn read from images.  Record i is edited only where
+ * d_surfaces[i].valid != 0, d_hits[i].object_index == object_index (RT_TEX_ALL_OBJECTS: any) and the hit's uv is finite.
+ *   diffuse_tex   diffuse_color = sample(uv); with RT_TEX_MODULATE the old colour times the sample
+ *   normal_tex    normal = sample(uv); with RT_TEX_NORMALIZE v / magnitude(v), and a length that is 0 or not finite leaves normal and
+ *                 shading_normal as they are; shading_normal = adjust_normal(normal, hit.normal), csrc/rt_shade.h's function called
+ *                 as rt_material_hits calls it
+ * Either texture may be NULL (both: nothing is launched).  Words 0..5 and 14..16 of an edited record move and no other.
+ * Checked in this order: n >= 2^32 is RT_ERR_UNSUPPORTED; each descriptor given; n == 0 is RT_OK; a null hit or surface pointer, then
+ * unknown flags, RT_ERR_INVALID_ARGUMENT. */
+int rt_texture_surfaces(const rt_texture *diffuse_tex, const rt_texture *normal_tex, const rt_hit *d_hits, const float *d_footprint, size_t n,
+                        uint32_t object_index, uint32_t flags, rt_surface *d_surfaces, void *hip_stream);
+
+/* rt_light_terms with the material (words 0..13 of the record, Material::approx's fields in its order; get_diffuse and get_specular
+ * consume words 3..5 and 7..10) and the shading normal (words 14..16) taken from d_surfaces[i] instead of the scene's material; a record
+ * whose valid is 0 is "no hit".  The position, the occlusion rule, approximate_into_directional,
+ * get_diffuse, get_specular and the wave-level skip are rt_light_terms': on the records rt_material_hits wrote, unedited, d_lit,
+ * d_diffuse and d_specular are that call's bit for bit.  rt_light_fold stays the fold: a texture does not change shiness.
+ * Checked as rt_light_terms checks, with the surfaces among the pointers. */
+int rt_light_terms_surfaces(const rt_scene *scene, const rt_surface *d_surfaces, const rt_hit *d_hits, const rt_ray *d_incoming, size_t n,
+                            uint32_t light_first, uint32_t light_count, const unsigned char *d_asks, const rt_hit *d_shadow_hits,
+                            unsigned char *d_lit, float *d_diffuse, float *d_specular, void *hip_stream);
+
 /* ---- refraction queries: get_refract bounce by bounce on caller-supplied hits ------------------------------
 
  * get_refract (main.rs:343-405) opened into the calls between its casts.  rt_refract_rays runs the whole walk through the glass in one
