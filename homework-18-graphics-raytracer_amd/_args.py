@@ -10,6 +10,8 @@ from typing import Sequence
 
 import numpy as np
 
+from ._capi import RtError
+
 _torch_module = None
 
 
@@ -134,6 +136,64 @@ def _host_column(a, dtype, n, name):
     if not (a.dtype.kind in dtype[0] and a.dtype.itemsize == 4 and a.shape == (n,)):
         raise ValueError(f"{name}: expected an ({n},) array of {dtype[1]}")
     return np.ascontiguousarray(a)
+
+
+# ---- what the hit-sample modules (hemisphere, environment, lobes, arealights, textures, _opened) share ----
+
+def _samples(spp):
+    spp = int(spp)
+    if spp < 0:
+        raise ValueError("spp must not be negative")
+    return spp
+
+
+def _below_2_32(count, what, where=""):
+    """a sequence's refusal of a batch no call of the library takes, raised before its workspace is looked at or made"""
+    if count >= 1 << 32:
+        raise RtError(-5, f"2^32 {what} or more{where}")
+
+
+def _zeroed_out(out, n, device, stream):
+    """the (N, 3) float32 a sequence ADDS to: ``out`` as given, checked, or a new zeroed tensor made with ``stream`` current"""
+    if out is not None:
+        return _tensor(out, "out", "float32", (n, 3))
+    with _on_stream(stream):
+        return _new((n, 3), "float32", device).zero_()
+
+
+def _room(workspace, cls, sizes, wanted, device, stream):
+    """A sequence's workspace: ``workspace`` if it is a ``cls`` whose attributes hold at least ``sizes`` (name -> extent; the names are
+    the constructor's parameters too), else ValueError("workspace must be " + wanted); None: a new cls(device=device, **sizes),
+    allocated with ``stream`` as torch's current stream — the caching allocator then ties the blocks to it."""
+    if workspace is None:
+        with _on_stream(stream):
+            return cls(device=device, **sizes)
+    if not isinstance(workspace, cls) or any(getattr(workspace, name) < extent for name, extent in sizes.items()):
+        raise ValueError("workspace must be " + wanted)
+    return workspace
+
+
+def _void(a):
+    """a numpy array (or None) as the void pointer the CPU forms take"""
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _host(a, dtype, shape, name, optional=False):
+    """a contiguous numpy array of ``dtype`` and ``shape`` for a CPU form: integers of the same size are viewed, anything else is
+    converted"""
+    if a is None and optional:
+        return None
+    a = np.ascontiguousarray(a)
+    if a.dtype != dtype:
+        a = a.view(dtype) if a.dtype.itemsize == np.dtype(dtype).itemsize and a.dtype.kind in "iu" and np.dtype(dtype).kind in "iu" else a.astype(dtype)
+    if a.shape != shape:
+        raise ValueError(f"{name}: expected an array of shape {shape}")
+    return a
+
+
+def _aligned_bytes(size):
+    """``size`` zero bytes, 8-byte aligned"""
+    return np.zeros((size + 7) // 8, dtype=np.uint64).view(np.uint8)[:size]
 
 
 def _box3(v, name):

@@ -2,8 +2,7 @@
 from __future__ import annotations
 
 from . import _capi
-from ._args import _count_ptr, _new, _on_stream, _out_tensor, _p, _stream_ptr, _tensor, _torch
-from ._capi import RtError
+from ._args import _below_2_32, _count_ptr, _new, _on_stream, _out_tensor, _p, _stream_ptr, _tensor, _torch
 from ._queries import ESCAPED, Refractions, _hit_records, _hits_and_rays, _refractions, cast_rays_indexed, select_records
 from ._world import Scene
 
@@ -113,8 +112,7 @@ def shade_hits_by_light(scene: Scene, hits, rays, out=None, ray_count=None, stre
     if lights_per_pass is not None and per_pass < 1:
         raise ValueError("lights_per_pass must be at least 1")
     per_pass = min(per_pass, lights)
-    if n * per_pass >= 1 << 32:
-        raise RtError(-5, "2^32 (hit, light) pairs or more in one pass (lights_per_pass)")
+    _below_2_32(n * per_pass, "(hit, light) pairs", " in one pass (lights_per_pass)")
     s = stream
     # allocated (and the fill enqueued) with `stream` as torch's current stream: the caching allocator then ties the blocks to it
     with _on_stream(stream):

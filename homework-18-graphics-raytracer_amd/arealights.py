@@ -13,26 +13,17 @@ Arrays are sample-major, then light-major: entry (s * L + (l - light_first)) * N
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
 from . import _capi
-from ._args import _count_ptr, _new, _on_stream, _out_tensor, _p, _stream_ptr, _tensor
-from ._capi import Light, RtError, SceneDesc
+from ._args import _below_2_32, _count_ptr, _new, _on_stream, _out_tensor, _p, _room, _samples, _stream_ptr, _tensor, _void
+from ._capi import Light, SceneDesc
 from ._opened import _light_range
 from ._queries import _hit_records, _hits_and_rays, cast_rays_indexed, select_records
 from ._world import Scene, World
 
 UNIFORM, STRATIFIED = 1, 2  # RT_FILM_UNIFORM / RT_FILM_STRATIFIED (RT_FILM_CENTER, 0, is no pattern of an area light)
 MAX_SPP = 64
-
-
-def _samples(spp):
-    spp = int(spp)
-    if spp < 0:
-        raise ValueError("spp must not be negative")
-    return spp
 
 
 def rays(scene: Scene, hits, rays, radii, spp: int, pattern: int = STRATIFIED, seed: int = 0, ids=None, light_first: int = 0, light_count=None,
@@ -129,9 +120,8 @@ def samples_numpy(lights, radii, n: int, spp: int, pattern: int = STRATIFIED, se
         if ids.shape != (n,):
             raise ValueError(f"ids: expected an ({n},) array")
     out = np.zeros((spp, count, n, 3), dtype=np.float32)
-    _capi.check_host(_capi.host_lib().rt_area_light_samples_cpu(arr, first, count, radii.ctypes.data_as(C.c_void_p),
-                                                                None if ids is None else ids.ctypes.data_as(C.c_void_p), n, spp, int(pattern),
-                                                                int(seed) & 0xFFFFFFFF, out.ctypes.data_as(C.c_void_p)))
+    _capi.check_host(_capi.host_lib().rt_area_light_samples_cpu(arr, first, count, _void(radii), _void(ids), n, spp, int(pattern), int(seed) & 0xFFFFFFFF,
+                                                                _void(out)))
     return out
 
 
@@ -181,20 +171,15 @@ def shade_hits_soft(scene: Scene, hits, rays, radii, spp: int = 16, pattern: int
     if lights_per_pass is not None and per_pass < 1:
         raise ValueError("lights_per_pass must be at least 1")
     per_pass = min(per_pass, lights)
-    if n * per_pass * spp >= 1 << 32:
-        raise RtError(-5, "2^32 (sample, light, hit) entries or more in one pass (lights_per_pass)")
+    _below_2_32(n * per_pass * spp, "(sample, light, hit) entries", " in one pass (lights_per_pass)")
     s = stream
-    # allocated (and the fill enqueued) with `stream` as torch's current stream: the caching allocator then ties the blocks to it
-    with _on_stream(stream):
+    with _on_stream(stream):  # the fill is enqueued with `stream` as torch's current stream
         out.zero_()
-        if n == 0 or lights == 0:
-            return out
-        entries = per_pass * n * spp
-        if workspace is None:
-            workspace = Workspace(entries, dev)
-        elif not isinstance(workspace, Workspace) or workspace.entries < entries:
-            raise ValueError(f"workspace must be an arealights.Workspace with room for {entries} (sample, light, hit) entries (arealights.workspace)")
-    w = workspace
+    if n == 0 or lights == 0:
+        return out
+    entries = per_pass * n * spp
+    w = _room(workspace, Workspace, {"entries": entries},
+              f"an arealights.Workspace with room for {entries} (sample, light, hit) entries (arealights.workspace)", dev, stream)
     for first in range(0, lights, per_pass):
         c = min(per_pass, lights - first)
         m = c * n * spp

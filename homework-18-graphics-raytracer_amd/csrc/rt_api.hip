@@ -95,6 +95,25 @@ int query_args(const char *who, size_t n, const CountLimit &limit, bool needs_sc
     *done = rc != RT_OK;
     return rc;
 }
+int hit_sample_args(const char *who, const rt_scene *scene, const HitSampleArgs &a, bool *done) {
+    *done = true;
+    const uint64_t pairs = (uint64_t)a.n * (uint64_t)a.per_record; /* below 2^64: both factors are below 2^32 where it is used */
+    int rc = check_count(who, a.n, RECORDS_2_32);
+    if (rc == RT_OK && a.pairs) rc = check_count(who, pairs, *a.pairs);
+    if (rc == RT_OK && a.takes_samples)
+        rc = check_count(who, pairs * (uint64_t)a.spp, a.of_lights ? SAMPLE_LIGHT_ENTRIES_2_32 : SAMPLE_ENTRIES_2_32);
+    if (rc == RT_OK && a.takes_scene) rc = check_scene(who, scene);
+    if (rc == RT_OK && a.descriptor) rc = a.descriptor();
+    if (rc != RT_OK || pairs == 0) return rc;
+    rc = check_pointers(who, a.pointers_ok, a.pointers);
+    if (rc != RT_OK) return rc;
+    if (a.bad) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": " + a.bad);
+    if (a.light_first >= 0 && (uint64_t)a.light_first + (uint64_t)a.per_record > (uint64_t)scene->ks.n_lights)
+        return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": lights " + std::to_string(a.light_first) + " .. " +
+                                                 std::to_string((uint64_t)a.light_first + a.per_record) + " of a scene with " + std::to_string(scene->ks.n_lights));
+    *done = false;
+    return RT_OK;
+}
 
 int launched(const char *who, hipError_t e) {
     if (e == hipSuccess) return RT_OK;

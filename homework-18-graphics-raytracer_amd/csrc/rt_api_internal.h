@@ -18,7 +18,8 @@
  *   rt_tree_query.hip  the tree loop's rt_tree_*: kernels and entry points in one unit
  *   rt_light_query.hip the light queries' rt_light_*: kernels and entry points in one unit
  *   rt_area_light_query.hip the area-light queries' rt_area_light_*: kernels and entry points in one unit (the sampler is rt_area_light.h's, shared
- *                      with librt_host.so; the per-hit record rt_light_record.h's, shared with rt_light_query.hip)
+ *                      with librt_host.so; the per-hit record, the shadow ray and the light-term body rt_light_record.h's, shared with
+ *                      rt_light_query.hip and the other hit-sample units; their entry points' checks are hit_sample_args below)
  *   rt_hemisphere_query.hip the hemisphere queries' rt_hemisphere_rays / rt_hemisphere_fold: kernels and entry points in one unit (the sampler and the
  *                      fold are rt_hemisphere.h's, shared with librt_host.so)
  *   rt_environment_query.hip the environment queries' rt_environment_lookup / _table / _rays / _fold: kernels and entry points in one unit (the arithmetic
@@ -228,6 +229,45 @@ RT_API_HIDDEN int check_pointers(const char *who, bool ok, const char *names); /
  * own in between composes the three above itself. */
 RT_API_HIDDEN int query_args(const char *who, size_t n, const CountLimit &limit, bool needs_scene, const void *scene, bool pointers_ok,
                              const char *names, bool *done);
+
+/* The checks of a hit-sample query — the light, area-light, hemisphere, environment, lobe, texture and material blocks' calls on n
+ * records times lights, probes or samples — in the documented order: 1 the counts (records, then records x lights or probes, then
+ * those x samples), 2 the scene, 3 the descriptor, 4 the empty batch (no records, no lights, no probes: RT_OK, *done), 5 the pointers,
+ * 6 the block's limits, 7 the light range.  A call states what it takes and leaves the rest out. */
+constexpr CountLimit LIGHT_PAIRS_2_32 = {32u, "(record, light) pairs", "pass the lights in several ranges"};
+constexpr CountLimit PROBE_PAIRS_2_32 = {32u, "(record, probe) pairs", "pass the probes in several calls"};
+constexpr CountLimit SAMPLE_ENTRIES_2_32 = {32u, "(sample, record) entries", "query the records in several calls, or fewer samples"};
+constexpr CountLimit SAMPLE_LIGHT_ENTRIES_2_32 = {32u, "(sample, light, record) entries", "pass the lights in several ranges, or fewer samples"};
+struct HitSampleArgs {
+    HitSampleArgs(size_t n, bool pointers_ok, const char *pointers) : n(n), pointers_ok(pointers_ok), pointers(pointers) {}
+    size_t n; /* records */
+    bool pointers_ok;
+    const char *pointers;                /* the names of "<who>: null <names> pointer" */
+    bool takes_scene = true;
+    std::function<int()> descriptor;     /* the check of the call's descriptor, run in its place in the order; empty: the call has none */
+    const CountLimit *pairs = nullptr;   /* the call takes `per_record` lights or probes per record: their limit */
+    uint32_t per_record = 1u;
+    bool of_lights = false;              /* ... and they are lights: the samples' limit names them */
+    int64_t light_first = -1;            /* < 0: no range of the scene's lights */
+    bool takes_samples = false;
+    uint32_t spp = 0u;
+    const char *bad = nullptr;           /* what the block's limits (the *_limits of its header) say, or null */
+    HitSampleArgs &no_scene() { takes_scene = false; return *this; }
+    HitSampleArgs &described(std::function<int()> check) { descriptor = std::move(check); return *this; }
+    HitSampleArgs &lights(uint32_t count, int64_t first = -1) { pairs = &LIGHT_PAIRS_2_32, per_record = count, of_lights = true, light_first = first; return *this; }
+    HitSampleArgs &probes(uint32_t count) { pairs = &PROBE_PAIRS_2_32, per_record = count; return *this; }
+    HitSampleArgs &samples(uint32_t count) { takes_samples = true, spp = count; return *this; }
+    HitSampleArgs &limits(const char *text) { bad = text; return *this; }
+};
+RT_API_HIDDEN int hit_sample_args(const char *who, const rt_scene *scene, const HitSampleArgs &a, bool *done);
+
+/* a descriptor's limits (rt::environment_limits, rt::texture_limits) under the entry point's name */
+template <class Desc>
+static inline int check_descriptor(const char *who, const Desc *d, const char *(*limits)(const Desc *, bool *)) {
+    bool unsupported;
+    if (const char *bad = limits(d, &unsupported)) return fail(unsupported ? RT_ERR_UNSUPPORTED : RT_ERR_INVALID_ARGUMENT, std::string(who) + ": " + bad);
+    return RT_OK;
+}
 
 /* the end of an entry point that launched: RT_OK, or "<who>: launch: <the HIP error>" with its status */
 RT_API_HIDDEN int launched(const char *who, hipError_t e);

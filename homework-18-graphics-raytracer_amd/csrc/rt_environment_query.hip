@@ -146,9 +146,8 @@ __global__ __launch_bounds__(RT_LIGHT_THREADS) void environment_rays_kernel(cons
     const uint64_t i = (uint64_t)blockIdx.x * RT_LIGHT_THREADS + threadIdx.x;
     if (i >= n) return;
     const LightRecord r = light_record(sc, hits, i);
-    const V3 pos = r.h.g.pos;
-    const V3 normal = normal_kind == RT_HEMISPHERE_GEOMETRIC ? r.h.g.normal : r.adj_n; /* wave-uniform choice */
-    const uint32_t id = ids != nullptr ? ids[i] : (uint32_t)i;
+    const V3 normal = sampling_normal(r, normal_kind);
+    const uint32_t id = record_id(ids, i);
     const uint32_t seed_e = environment_seed(seed);
     const EnvTable t = env_table_view(e, table);
     const bool drawn = r.valid && t.total > 0u;
@@ -164,27 +163,20 @@ __global__ __launch_bounds__(RT_LIGHT_THREADS) void environment_rays_kernel(cons
             need = p.ok && hemisphere_asks(dir, normal);
             if (need) l = env_sample_radiance(e, p);
         }
-        dirs[k * 3u] = dir.x;
-        dirs[k * 3u + 1u] = dir.y;
-        dirs[k * 3u + 2u] = dir.z;
-        radiance[k * 3u] = l.x;
-        radiance[k * 3u + 1u] = l.y;
-        radiance[k * 3u + 2u] = l.z;
+        store_v3(dirs, k, dir);
+        store_v3(radiance, k, l);
         if (texel != nullptr) texel[k] = at;
         asks[k] = need ? 1 : 0;
-        if (need) /* hemisphere_rays_kernel's shadow ray */
-            store_ray(shadow_rays + k, pos, dir, FACE_BACK, 1u, r.h.kind, r.h.index, FACE_BACK);
-        else
-            store_ray(shadow_rays + k, v3(0.0f, 0.0f, 0.0f), v3(0.0f, 0.0f, 0.0f), 0u, 0u, 0u, 0u, 0u);
+        store_shadow_ray(shadow_rays + k, r, dir, need);
     }
 }
 
 __global__ __launch_bounds__(RT_LIGHT_THREADS) void environment_fold_kernel(const KernelScene sc, const rt_hit *__restrict__ hits, const EnvFold f) {
     const uint64_t i = (uint64_t)blockIdx.x * RT_LIGHT_THREADS + threadIdx.x;
     if (i >= f.n) return;
-    const AbiHit h = hit_from_abi(hits + i, sc.n_triangles, sc.n_spheres, sc.n_materials, true);
-    const float shiness = h.valid ? material_approx(sc.materials[h.g.obj], h.g.u, h.g.v).shiness : 0.0f;
-    env_fold_record(f, i, h.valid, shiness);
+    bool valid;
+    const float shiness = fold_shiness(sc, hits, i, &valid);
+    env_fold_record(f, i, valid, shiness);
 }
 
 } /* namespace rt */
@@ -192,38 +184,18 @@ __global__ __launch_bounds__(RT_LIGHT_THREADS) void environment_fold_kernel(cons
 /* ---- the C entry points (include/rt_amd.h "environment queries") ---- */
 
 /* the descriptor's checks under the entry point's name */
-static int environment_ok(const char *who, const rt_environment *env) {
-    bool unsupported;
-    if (const char *bad = rt::environment_limits(env, &unsupported))
-        return fail(unsupported ? RT_ERR_UNSUPPORTED : RT_ERR_INVALID_ARGUMENT, std::string(who) + ": " + bad);
-    return RT_OK;
-}
+static int environment_ok(const char *who, const rt_environment *env) { return check_descriptor(who, env, rt::environment_limits); }
 
-/* the block's checks before any device work, in the documented order — the hemisphere queries' with the descriptor after the scene;
- * *done: nothing to launch.  check_sampler: the call takes a pattern and a normal_kind */
-static int environment_args(const char *who, bool needs_scene, const rt_scene *scene, bool needs_env, const rt_environment *env, size_t n, uint32_t spp,
-                            bool check_spp, bool check_sampler, uint32_t pattern, uint32_t normal_kind, bool pointers_ok, const char *pointers, bool *done) {
-    *done = true;
-    int rc = check_count(who, n, RECORDS_2_32);
-    if (rc == RT_OK && check_spp)
-        rc = check_count(who, (uint64_t)n * (uint64_t)spp, {32u, "(sample, record) entries", "query the records in several calls, or fewer samples"});
-    if (rc == RT_OK && needs_scene) rc = check_scene(who, scene);
-    if (rc == RT_OK && needs_env) rc = environment_ok(who, env);
-    if (rc != RT_OK || n == 0) return rc;
-    rc = check_pointers(who, pointers_ok, pointers);
-    if (rc != RT_OK) return rc;
-    if (check_spp)
-        if (const char *bad = rt::hemisphere_limits(spp, check_sampler, pattern, normal_kind)) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": " + bad);
-    *done = false;
-    return RT_OK;
-}
-
+/* the checks before any device work are hit_sample_args' (rt_api_internal.h): the hemisphere queries' with the descriptor after the
+ * scene.  rt_environment_lookup takes no scene and no samples, rt_environment_fold no descriptor */
 extern "C" {
 
 int rt_environment_lookup(const rt_environment *env, const rt_ray *d_rays, size_t n, const uint32_t *d_count, const rt_hit *d_hits,
                           const uint32_t *d_parent, float *d_out, size_t n_out, void *hip_stream) {
     bool done;
-    const int rc = environment_args("rt_environment_lookup", false, nullptr, true, env, n, 0u, false, false, 0u, 0u, d_rays && d_out, "ray or output", &done);
+    const int rc = hit_sample_args("rt_environment_lookup", nullptr,
+                                   HitSampleArgs(n, d_rays && d_out, "ray or output").no_scene().described([env] { return environment_ok("rt_environment_lookup", env); }),
+                                   &done);
     if (rc != RT_OK || done) return rc;
     const rt::EnvLookup a = {*env, reinterpret_cast<const uint32_t *>(d_rays), (uint64_t)n, d_count, reinterpret_cast<const uint32_t *>(d_hits), d_parent,
                              d_out, (uint64_t)n_out};
@@ -261,8 +233,10 @@ int rt_environment_rays(const rt_scene *scene, const rt_environment *env, const 
                         uint32_t spp, uint32_t pattern, uint32_t seed, uint32_t normal_kind, rt_ray *d_rays, unsigned char *d_asks, float *d_dirs,
                         float *d_radiance, uint32_t *d_texel, void *hip_stream) {
     bool done;
-    const int rc = environment_args("rt_environment_rays", true, scene, true, env, n, spp, true, true, pattern, normal_kind,
-                                    d_table && d_hits && d_rays && d_asks && d_dirs && d_radiance, "table, hit, ray, flag, direction or radiance", &done);
+    const int rc = hit_sample_args("rt_environment_rays", scene,
+                                   HitSampleArgs(n, d_table && d_hits && d_rays && d_asks && d_dirs && d_radiance, "table, hit, ray, flag, direction or radiance")
+                                       .described([env] { return environment_ok("rt_environment_rays", env); }).samples(spp)
+                                       .limits(rt::hemisphere_limits(spp, true, pattern, normal_kind)), &done);
     if (rc != RT_OK || done) return rc;
     hipLaunchKernelGGL(rt::environment_rays_kernel, grid_of(n, RT_LIGHT_THREADS), dim3(RT_LIGHT_THREADS), 0, static_cast<hipStream_t>(hip_stream), scene->ks, *env,
                        d_table, d_hits, (uint64_t)n, d_ids, spp, pattern, rt::film_strata(spp), seed, normal_kind, d_rays, d_asks, d_dirs, d_radiance, d_texel);
@@ -272,8 +246,9 @@ int rt_environment_rays(const rt_scene *scene, const rt_environment *env, const 
 int rt_environment_fold(const rt_scene *scene, const rt_hit *d_hits, size_t n, uint32_t spp, const unsigned char *d_asks, const rt_hit *d_shadow_hits,
                         const float *d_radiance, const float *d_diffuse, const float *d_specular, unsigned char *d_open, float *d_rgb, void *hip_stream) {
     bool done;
-    const int rc = environment_args("rt_environment_fold", true, scene, false, nullptr, n, spp, true, false, 0u, 0u,
-                                    d_hits && d_asks && d_radiance && d_diffuse && d_specular && d_rgb, "hit, flag, radiance, diffuse, specular or rgb", &done);
+    const int rc = hit_sample_args("rt_environment_fold", scene,
+                                   HitSampleArgs(n, d_hits && d_asks && d_radiance && d_diffuse && d_specular && d_rgb, "hit, flag, radiance, diffuse, specular or rgb")
+                                       .samples(spp).limits(rt::hemisphere_limits(spp, false, 0u, 0u)), &done);
     if (rc != RT_OK || done) return rc;
     const rt::EnvFold f = {(uint64_t)n, spp, d_asks, reinterpret_cast<const uint32_t *>(d_shadow_hits), d_radiance, d_diffuse, d_specular, d_open, d_rgb};
     hipLaunchKernelGGL(rt::environment_fold_kernel, grid_of(n, RT_LIGHT_THREADS), dim3(RT_LIGHT_THREADS), 0, static_cast<hipStream_t>(hip_stream), scene->ks, d_hits, f);

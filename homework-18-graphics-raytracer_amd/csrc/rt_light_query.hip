@@ -11,14 +11,16 @@
  *
  * Nothing here is new arithmetic: hit_from_abi, ray_from_abi, material_approx, adjust_normal, light_asks, approximate_into_directional,
  * get_diffuse and get_specular are called as rt::shade_hits_kernel (rt_hit_query.hip) calls them, with the same operands in the same
- * order, and the unit is compiled with -ffp-contract=off like every other — so every bit is rt_shade_hits'.  One record per lane, the
+ * order, and the unit is compiled with -ffp-contract=off like every other — so every bit is rt_shade_hits'.  What is done per record
+ * and per entry (light_record, store_shadow_ray, light_terms, fold_shiness) is rt_light_record.h's, where the area-light, hemisphere,
+ * environment, lobe and texture queries take it from too; the kernels here are the loops around it.  One record per lane, the
  * record number counted in 64 bits; the material and the bump normal once per record, not once per pair; the light loop is wave-uniform
  * (the light record comes through uniform_ref: scalar loads); per-(light, record) arrays are light-major, entry (l - light_first) * n + i,
  * so that the stores of one light's plane are coalesced.  Records move as dwords.  No LDS, no cast.  The C entry points of the block are
  * at the end of the file.
  */
 #include "rt_api_internal.h"
-#include "rt_light_record.h" /* light_record: what get_shade computes once per hit */
+#include "rt_light_record.h"
 
 namespace rt {
 
@@ -37,13 +39,9 @@ __global__ __launch_bounds__(RT_LIGHT_THREADS) void light_rays_kernel(const Kern
         V3 l_direction = v3(0.0f, 0.0f, 0.0f);
         const bool need = light_asks(L, uniform_ref(sc.light_aux + (light_first + l)), pos, r.adj_n, &l_direction) && r.valid;
         asks[k] = need ? 1 : 0;
-        if (need) /* shadow_ray, main.rs:426-433: bit for bit the ray shade_hits_kernel casts */
-            store_ray(shadow_rays + k, pos, -l_direction, FACE_BACK, 1u, r.h.kind, r.h.index, FACE_BACK);
-        else
-            store_ray(shadow_rays + k, v3(0.0f, 0.0f, 0.0f), v3(0.0f, 0.0f, 0.0f), 0u, 0u, 0u, 0u, 0u);
+        store_shadow_ray(shadow_rays + k, r, -l_direction, need);
         if (light_distance != nullptr) { /* what main.rs:439 compares against */
-            const bool has_origin = (L.kind != RT_LIGHT_DIRECTIONAL) || (L.has_origin != 0u);
-            const float d = has_origin ? distance(pos, v3(L.origin[0], L.origin[1], L.origin[2])) : __builtin_inff();
+            const float d = area_light_has_origin(L) ? distance(pos, v3(L.origin[0], L.origin[1], L.origin[2])) : __builtin_inff();
             light_distance[k] = need ? d : 0.0f;
         }
     }
@@ -65,42 +63,12 @@ __global__ __launch_bounds__(RT_LIGHT_THREADS) void light_terms_kernel(const Ker
     for (uint32_t l = 0; l < light_count; ++l) { /* wave-uniform */
         const uint64_t k = (uint64_t)l * n + i;
         const bool asked = r.valid && asks[k] != 0;
-        bool lit = false;
-        V3 diffuse = v3(0.0f, 0.0f, 0.0f), specular = v3(0.0f, 0.0f, 0.0f);
+        LightTerms t; /* not lit, +0 */
         if (__builtin_amdgcn_ballot_w64(asked) != 0ull) { /* a wave nobody asks in skips the light: its acosf and powf are binary64 */
             const auto &L = uniform_ref(sc.lights + (light_first + l));
-            if (asked) {
-                lit = true;
-                const uint32_t *const occluder = reinterpret_cast<const uint32_t *>(shadow_hits + k);
-                if (occluder[0] <= 1u) { /* main.rs:435-448: Some(occlusion) */
-                    const bool has_origin = (L.kind != RT_LIGHT_DIRECTIONAL) || (L.has_origin != 0u);
-                    if (has_origin) {
-                        const V3 occ = v3(__uint_as_float(occluder[RT_LIGHT_HIT_POSITION]), __uint_as_float(occluder[RT_LIGHT_HIT_POSITION + 1u]),
-                                          __uint_as_float(occluder[RT_LIGHT_HIT_POSITION + 2u])); /* occlusion.at.position */
-                        if (distance(pos, occ) < distance(pos, v3(L.origin[0], L.origin[1], L.origin[2]))) lit = false;
-                    } else {
-                        lit = false;
-                    }
-                }
-                if (lit) {
-                    DirLight dl;
-                    dl.direction = dl.color = v3(0.0f, 0.0f, 0.0f);
-                    lit = approximate_into_directional(L, pos, &dl); /* None only where the caller set a flag the light did not */
-                    if (lit) {
-                        const V3 light_direction = -dl.direction; /* the light's own, not the shadow record's: a caller may have replaced that ray */
-                        diffuse = get_diffuse(r.m, r.adj_n, light_direction) * dl.color;
-                        specular = get_specular(r.m, r.adj_n, -view, light_direction) * dl.color;
-                    }
-                }
-            }
+            t = light_terms(L, area_light_has_origin(L), v3(L.origin[0], L.origin[1], L.origin[2]), pos, r.m, r.adj_n, view, asked, shadow_hits + k);
         }
-        lit_out[k] = lit ? 1 : 0;
-        diffuse_out[k * 3u] = diffuse.x;
-        diffuse_out[k * 3u + 1u] = diffuse.y;
-        diffuse_out[k * 3u + 2u] = diffuse.z;
-        specular_out[k * 3u] = specular.x;
-        specular_out[k * 3u + 1u] = specular.y;
-        specular_out[k * 3u + 2u] = specular.z;
+        store_light_terms(lit_out, diffuse_out, specular_out, k, t);
     }
 }
 
@@ -111,51 +79,32 @@ __global__ __launch_bounds__(RT_LIGHT_THREADS) void light_fold_kernel(const Kern
                                                                       float *__restrict__ rgb) {
     const uint64_t i = (uint64_t)blockIdx.x * RT_LIGHT_THREADS + threadIdx.x;
     if (i >= n) return;
-    const AbiHit h = hit_from_abi(hits + i, sc.n_triangles, sc.n_spheres, sc.n_materials, true);
-    if (!h.valid) return; /* "no hit": not written */
-    const float shiness = material_approx(sc.materials[h.g.obj], h.g.u, h.g.v).shiness;
-    V3 sum = v3(rgb[i * 3u], rgb[i * 3u + 1u], rgb[i * 3u + 2u]);
+    bool valid;
+    const float shiness = fold_shiness(sc, hits, i, &valid);
+    if (!valid) return; /* "no hit": not written */
+    V3 sum = load_v3(rgb, i);
     for (uint32_t l = 0; l < light_count; ++l) {
         const uint64_t k = (uint64_t)l * n + i;
         if (lit[k] == 0) continue;
-        const V3 d = v3(diffuse[k * 3u], diffuse[k * 3u + 1u], diffuse[k * 3u + 2u]);
-        const V3 s = v3(specular[k * 3u], specular[k * 3u + 1u], specular[k * 3u + 2u]);
-        sum = sum + d * (1.0f - shiness) + s * shiness;
+        sum = sum + load_v3(diffuse, k) * (1.0f - shiness) + load_v3(specular, k) * shiness;
     }
-    rgb[i * 3u] = sum.x;
-    rgb[i * 3u + 1u] = sum.y;
-    rgb[i * 3u + 2u] = sum.z;
+    store_v3(rgb, i, sum);
 }
 
 } /* namespace rt */
 
 /* ---- the C entry points (include/rt_amd.h "light queries") ---- */
 
-/* the block's checks before any device work, in the documented order; *done: nothing to launch.  light_first < 0: the call takes no
- * range of lights (rt_light_fold reads the material only) */
-static int light_args(const char *who, const rt_scene *scene, size_t n, int64_t light_first, uint32_t light_count, bool pointers_ok,
-                      const char *pointers, bool *done) {
-    *done = true;
-    int rc = check_count(who, n, RECORDS_2_32);
-    if (rc == RT_OK) rc = check_count(who, (uint64_t)n * (uint64_t)light_count, {32u, "(record, light) pairs", "pass the lights in several ranges"});
-    if (rc == RT_OK) rc = check_scene(who, scene);
-    if (rc != RT_OK || n == 0 || light_count == 0) return rc;
-    rc = check_pointers(who, pointers_ok, pointers);
-    if (rc != RT_OK) return rc;
-    if (light_first >= 0 && (uint64_t)light_first + (uint64_t)light_count > (uint64_t)scene->ks.n_lights)
-        return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": lights " + std::to_string(light_first) + " .. " +
-                                                 std::to_string((uint64_t)light_first + light_count) + " of a scene with " + std::to_string(scene->ks.n_lights));
-    *done = false;
-    return RT_OK;
-}
-
+/* the checks before any device work are hit_sample_args' (rt_api_internal.h); rt_light_fold takes no range of lights: it reads the
+ * material only */
 extern "C" {
 
 int rt_light_rays(const rt_scene *scene, const rt_hit *d_hits, const rt_ray *d_incoming, size_t n, uint32_t light_first, uint32_t light_count,
                   rt_ray *d_shadow_rays, unsigned char *d_asks, float *d_light_distance, void *hip_stream) {
     bool done;
-    const int rc = light_args("rt_light_rays", scene, n, light_first, light_count, d_hits && d_incoming && d_shadow_rays && d_asks,
-                              "hit, incoming-ray, shadow-ray or flag", &done);
+    const int rc = hit_sample_args("rt_light_rays", scene,
+                                   HitSampleArgs(n, d_hits && d_incoming && d_shadow_rays && d_asks, "hit, incoming-ray, shadow-ray or flag")
+                                       .lights(light_count, light_first), &done);
     if (rc != RT_OK || done) return rc;
     hipLaunchKernelGGL(rt::light_rays_kernel, grid_of(n, RT_LIGHT_THREADS), dim3(RT_LIGHT_THREADS), 0, static_cast<hipStream_t>(hip_stream), scene->ks, d_hits,
                        (uint64_t)n, light_first, light_count, d_shadow_rays, d_asks, d_light_distance);
@@ -166,9 +115,10 @@ int rt_light_terms(const rt_scene *scene, const rt_hit *d_hits, const rt_ray *d_
                    const unsigned char *d_asks, const rt_hit *d_shadow_hits, unsigned char *d_lit, float *d_diffuse, float *d_specular,
                    void *hip_stream) {
     bool done;
-    const int rc = light_args("rt_light_terms", scene, n, light_first, light_count,
-                              d_hits && d_incoming && d_asks && d_shadow_hits && d_lit && d_diffuse && d_specular,
-                              "hit, incoming-ray, flag, shadow-hit, lit, diffuse or specular", &done);
+    const int rc = hit_sample_args("rt_light_terms", scene,
+                                   HitSampleArgs(n, d_hits && d_incoming && d_asks && d_shadow_hits && d_lit && d_diffuse && d_specular,
+                                                 "hit, incoming-ray, flag, shadow-hit, lit, diffuse or specular")
+                                       .lights(light_count, light_first), &done);
     if (rc != RT_OK || done) return rc;
     hipLaunchKernelGGL(rt::light_terms_kernel, grid_of(n, RT_LIGHT_THREADS), dim3(RT_LIGHT_THREADS), 0, static_cast<hipStream_t>(hip_stream), scene->ks, d_hits,
                        d_incoming, (uint64_t)n, light_first, light_count, d_asks, d_shadow_hits, d_lit, d_diffuse, d_specular);
@@ -178,8 +128,9 @@ int rt_light_terms(const rt_scene *scene, const rt_hit *d_hits, const rt_ray *d_
 int rt_light_fold(const rt_scene *scene, const rt_hit *d_hits, size_t n, uint32_t light_count, const unsigned char *d_lit, const float *d_diffuse,
                   const float *d_specular, float *d_rgb, void *hip_stream) {
     bool done;
-    const int rc = light_args("rt_light_fold", scene, n, -1, light_count, d_hits && d_lit && d_diffuse && d_specular && d_rgb,
-                              "hit, lit, diffuse, specular or rgb", &done);
+    const int rc = hit_sample_args("rt_light_fold", scene,
+                                   HitSampleArgs(n, d_hits && d_lit && d_diffuse && d_specular && d_rgb, "hit, lit, diffuse, specular or rgb").lights(light_count),
+                                   &done);
     if (rc != RT_OK || done) return rc;
     hipLaunchKernelGGL(rt::light_fold_kernel, grid_of(n, RT_LIGHT_THREADS), dim3(RT_LIGHT_THREADS), 0, static_cast<hipStream_t>(hip_stream), scene->ks, d_hits,
                        (uint64_t)n, light_count, d_lit, d_diffuse, d_specular, d_rgb);

@@ -8,8 +8,9 @@
  *   rt::environment_pdf_kernel   per direction: the texel the lookup names and the table's density there
  *   rt::mis_weigh_kernel         per entry: the balance or power weight, and rgb times it (over the entry's own density)
  *
- * The arithmetic is rt_lobe.h's, shared with librt_host.so: light_record, adjust_normal, hemisphere_dir, env_texel_point and store_ray
- * are called as the hemisphere and environment queries call them, so a surface of shiness 0 gets rt_hemisphere_rays' words.  One record
+ * The arithmetic is rt_lobe.h's, shared with librt_host.so: the record, the sampling normal and the shadow ray are the hemisphere and
+ * environment queries' own (rt_light_record.h), and hemisphere_dir and env_texel_point are called as those queries call them, so a
+ * surface of shiness 0 gets rt_hemisphere_rays' words.  One record
  * (or entry) per lane, the number counted in 64 bits; the material, N, R and e once per record; the sample and probe loops are
  * wave-uniform; arrays are sample-major, entry s * n + i.  Records move as dwords.  No LDS, no cast, no workspace.  The C entry points
  * of the block are at the end of the file.
@@ -21,9 +22,7 @@
 namespace rt {
 
 #define RT_LOBE_THREADS 256u
-#define RT_LOBE_SURFACE_WORDS 18u
 #define RT_LOBE_RAY_DIRECTION 3u /* word of rt_ray.direction */
-static_assert(sizeof(rt_surface) == RT_LOBE_SURFACE_WORDS * sizeof(uint32_t), "rt_surface is 18 dwords");
 
 __global__ __launch_bounds__(RT_LOBE_THREADS) void lobe_rays_kernel(const KernelScene sc, const rt_hit *__restrict__ hits, const rt_ray *__restrict__ incoming,
                                                                     const uint64_t n, const uint32_t *__restrict__ ids, const uint32_t spp,
@@ -34,29 +33,23 @@ __global__ __launch_bounds__(RT_LOBE_THREADS) void lobe_rays_kernel(const Kernel
     const uint64_t i = (uint64_t)blockIdx.x * RT_LOBE_THREADS + threadIdx.x;
     if (i >= n) return;
     const LightRecord r = light_record(sc, hits, i);
-    const V3 pos = r.h.g.pos;
-    const V3 normal = normal_kind == RT_HEMISPHERE_GEOMETRIC ? r.h.g.normal : r.adj_n; /* wave-uniform choice */
+    const V3 normal = sampling_normal(r, normal_kind);
     V3 view = v3(0.0f, 0.0f, 1.0f);
     if (r.valid) {
         const float *const d = reinterpret_cast<const float *>(incoming + i) + RT_LOBE_RAY_DIRECTION;
         view = -v3(d[0], d[1], d[2]); /* what get_shade passes as view_direction */
     }
     const LobeSurface surface = lobe_surface(normal, view, r.m.shiness, r.m.smoothness);
-    const uint32_t id = ids != nullptr ? ids[i] : (uint32_t)i;
+    const uint32_t id = record_id(ids, i);
     const uint32_t seed_h = hemisphere_seed(seed);
     for (uint32_t s = 0; s < spp; ++s) { /* wave-uniform */
         const uint64_t k = (uint64_t)s * n + i;
         const LobeSample p = lobe_sample(surface, pattern, strata, id, seed_h, s, r.valid);
-        dirs[k * 3u] = p.dir.x;
-        dirs[k * 3u + 1u] = p.dir.y;
-        dirs[k * 3u + 2u] = p.dir.z;
+        store_v3(dirs, k, p.dir);
         pdf[k] = r.valid ? p.pdf : 0.0f;
         lobe[k] = p.specular ? 1 : 0;
         asks[k] = p.ok ? 1 : 0;
-        if (p.ok) /* hemisphere_rays_kernel's shadow ray */
-            store_ray(shadow_rays + k, pos, p.dir, FACE_BACK, 1u, r.h.kind, r.h.index, FACE_BACK);
-        else
-            store_ray(shadow_rays + k, v3(0.0f, 0.0f, 0.0f), v3(0.0f, 0.0f, 0.0f), 0u, 0u, 0u, 0u, 0u);
+        store_shadow_ray(shadow_rays + k, r, p.dir, p.ok);
     }
 }
 
@@ -64,13 +57,13 @@ __global__ __launch_bounds__(RT_LOBE_THREADS) void lobe_pdf_kernel(const rt_surf
                                                                    const float *__restrict__ dirs, const uint32_t n_probes, float *__restrict__ pdf) {
     const uint64_t i = (uint64_t)blockIdx.x * RT_LOBE_THREADS + threadIdx.x;
     if (i >= n) return;
-    const uint32_t *const p = reinterpret_cast<const uint32_t *>(surfaces + i);
+    const uint32_t *const p = reinterpret_cast<const uint32_t *>(surfaces + i); /* six words of the record, not surface_record's eighteen */
     const bool valid = p[17] != 0u;
     const V3 normal = v3(__uint_as_float(p[14]), __uint_as_float(p[15]), __uint_as_float(p[16])); /* shading_normal */
-    const LobeSurface surface = lobe_surface(normal, v3p(view + i * 3u), __uint_as_float(p[6]), __uint_as_float(p[10]));
+    const LobeSurface surface = lobe_surface(normal, load_v3(view, i), __uint_as_float(p[6]), __uint_as_float(p[10]));
     for (uint32_t q = 0; q < n_probes; ++q) { /* wave-uniform */
         const uint64_t k = (uint64_t)q * n + i;
-        const V3 dir = valid ? v3p(dirs + k * 3u) : v3(0.0f, 0.0f, 0.0f);
+        const V3 dir = valid ? load_v3(dirs, k) : v3(0.0f, 0.0f, 0.0f);
         const float density = lobe_pdf(surface, dir, valid);
         pdf[k] = valid ? density : 0.0f;
     }
@@ -96,22 +89,19 @@ __global__ __launch_bounds__(RT_LOBE_THREADS) void mis_weigh_kernel(const MisWei
 
 /* ---- the C entry points (include/rt_amd.h "lobe queries") ---- */
 
-static const CountLimit ENTRIES_2_32 = {32u, "(sample, record) entries", "query the records in several calls, or fewer samples"};
-
 extern "C" {
 
-/* the hemisphere queries' checks, in their order and with their messages, with the incoming rays among the pointers */
+/* rt_hemisphere_rays' checks (hit_sample_args, rt_api_internal.h), with the incoming rays among the pointers */
 int rt_lobe_rays(const rt_scene *scene, const rt_hit *d_hits, const rt_ray *d_incoming, size_t n, const uint32_t *d_ids, uint32_t spp, uint32_t pattern,
                  uint32_t seed, uint32_t normal_kind, rt_ray *d_rays, unsigned char *d_asks, float *d_dirs, float *d_pdf, unsigned char *d_lobe,
                  void *hip_stream) {
     const char *const who = "rt_lobe_rays";
-    int rc = check_count(who, n, RECORDS_2_32);
-    if (rc == RT_OK) rc = check_count(who, (uint64_t)n * (uint64_t)spp, ENTRIES_2_32);
-    if (rc == RT_OK) rc = check_scene(who, scene);
-    if (rc != RT_OK || n == 0) return rc;
-    rc = check_pointers(who, d_hits && d_incoming && d_rays && d_asks && d_dirs && d_pdf && d_lobe, "hit, incoming-ray, ray, flag, direction, pdf or lobe");
-    if (rc != RT_OK) return rc;
-    if (const char *bad = rt::hemisphere_limits(spp, true, pattern, normal_kind)) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": " + bad);
+    bool done;
+    const int rc = hit_sample_args(who, scene,
+                                   HitSampleArgs(n, d_hits && d_incoming && d_rays && d_asks && d_dirs && d_pdf && d_lobe,
+                                                 "hit, incoming-ray, ray, flag, direction, pdf or lobe")
+                                       .samples(spp).limits(rt::hemisphere_limits(spp, true, pattern, normal_kind)), &done);
+    if (rc != RT_OK || done) return rc;
     hipLaunchKernelGGL(rt::lobe_rays_kernel, grid_of(n, RT_LOBE_THREADS), dim3(RT_LOBE_THREADS), 0, static_cast<hipStream_t>(hip_stream), scene->ks, d_hits,
                        d_incoming, (uint64_t)n, d_ids, spp, pattern, rt::film_strata(spp), seed, normal_kind, d_rays, d_asks, d_dirs, d_pdf, d_lobe);
     return launched(who);
@@ -121,12 +111,11 @@ int rt_lobe_rays(const rt_scene *scene, const rt_hit *d_hits, const rt_ray *d_in
 int rt_lobe_pdf(const rt_surface *d_surfaces, size_t n, const float *d_view, const float *d_dirs, uint32_t n_probes, uint32_t normal_kind, float *d_pdf,
                 void *hip_stream) {
     const char *const who = "rt_lobe_pdf";
-    int rc = check_count(who, n, RECORDS_2_32);
-    if (rc == RT_OK) rc = check_count(who, (uint64_t)n * (uint64_t)n_probes, {32u, "(record, probe) pairs", "pass the probes in several calls"});
-    if (rc != RT_OK || n == 0 || n_probes == 0) return rc;
-    rc = check_pointers(who, d_surfaces && d_view && d_dirs && d_pdf, "surface, view, direction or pdf");
-    if (rc != RT_OK) return rc;
-    if (const char *bad = rt::lobe_pdf_limits(normal_kind)) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": " + bad);
+    bool done;
+    const int rc = hit_sample_args(who, nullptr,
+                                   HitSampleArgs(n, d_surfaces && d_view && d_dirs && d_pdf, "surface, view, direction or pdf")
+                                       .no_scene().probes(n_probes).limits(rt::lobe_pdf_limits(normal_kind)), &done);
+    if (rc != RT_OK || done) return rc;
     hipLaunchKernelGGL(rt::lobe_pdf_kernel, grid_of(n, RT_LOBE_THREADS), dim3(RT_LOBE_THREADS), 0, static_cast<hipStream_t>(hip_stream), d_surfaces, (uint64_t)n,
                        d_view, d_dirs, n_probes, d_pdf);
     return launched(who);

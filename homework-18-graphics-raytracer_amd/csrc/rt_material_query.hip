@@ -9,21 +9,19 @@
  *   rt::probe_surfaces_kernel   materials.rs:46-66 per (probe, record): get_diffuse and get_specular, no light colour applied
  *
  * Nothing here is new arithmetic: hit_from_abi, material_approx, adjust_normal, get_diffuse and get_specular are called as
- * light_record() and rt::light_terms_kernel (rt_light_query.hip) call them, with the same operands in the same order, and the unit is
- * compiled with -ffp-contract=off like every other — so every bit is rt_shade_hits'.  One record per lane, the record number counted in
+ * light_record() and light_terms() (rt_light_record.h) call them, with the same operands in the same order, and the unit is
+ * compiled with -ffp-contract=off like every other — so every bit is rt_shade_hits'.  A surface is read back by that header's
+ * surface_record, the one rt_light_terms_surfaces reads it with.  One record per lane, the record number counted in
  * 64 bits; a surface is read once per record, not once per pair; the probe loop is wave-uniform; per-(probe, record) arrays are
  * probe-major, entry p * n + i, as the light queries' are light-major.  Records move as dwords.  No LDS, no cast, no workspace.  The C
  * entry points of the block are at the end of the file.
  */
 #include "rt_api_internal.h"
-#include "rt_cast.h"
-#include "rt_hit_abi.h"
+#include "rt_light_record.h" /* surface_record and RT_SURFACE_WORDS: the record as the other hit-sample units read it */
 
 namespace rt {
 
 #define RT_MATERIAL_THREADS 256u
-#define RT_SURFACE_WORDS 18u
-static_assert(sizeof(rt_surface) == RT_SURFACE_WORDS * sizeof(uint32_t), "rt_surface is 18 dwords");
 
 /* main.rs:408-410: material = approx(hit.at), normal = adjust_normal(hit.at.normal) */
 __global__ __launch_bounds__(RT_MATERIAL_THREADS) void material_hits_kernel(const KernelScene sc, const rt_hit *__restrict__ hits, const uint64_t n,
@@ -55,36 +53,18 @@ __global__ __launch_bounds__(RT_MATERIAL_THREADS) void probe_surfaces_kernel(con
                                                                              float *__restrict__ specular_out) {
     const uint64_t i = (uint64_t)blockIdx.x * RT_MATERIAL_THREADS + threadIdx.x;
     if (i >= n) return;
-    const uint32_t *const p = reinterpret_cast<const uint32_t *>(surfaces + i);
-    float f[17];
-#pragma unroll
-    for (uint32_t k = 0; k < 17u; ++k) f[k] = __uint_as_float(p[k]);
-    const bool valid = p[17] != 0u;
-    Mat m;
-    m.normal = v3(f[0], f[1], f[2]);
-    m.diffuse = v3(f[3], f[4], f[5]);
-    m.shiness = f[6];
-    m.specular = v3(f[7], f[8], f[9]);
-    m.smoothness = f[10];
-    m.transparency = f[11];
-    m.refraction_index = f[12];
-    m.opaque_decay = f[13];
-    const V3 adj_n = v3(f[14], f[15], f[16]);
-    const V3 view_direction = v3(view[i * 3u], view[i * 3u + 1u], view[i * 3u + 2u]);
+    const SurfaceRecord s = surface_record(surfaces, i);
+    const V3 view_direction = load_v3(view, i);
     for (uint32_t q = 0; q < n_probes; ++q) { /* wave-uniform */
         const uint64_t k = (uint64_t)q * n + i;
         V3 diffuse = v3(0.0f, 0.0f, 0.0f), specular = v3(0.0f, 0.0f, 0.0f);
-        if (valid) { /* a record that is no hit stays out of get_specular's wave-level branch */
-            const V3 light_direction = v3(light_dirs[k * 3u], light_dirs[k * 3u + 1u], light_dirs[k * 3u + 2u]);
-            diffuse = get_diffuse(m, adj_n, light_direction);
-            specular = get_specular(m, adj_n, view_direction, light_direction);
+        if (s.valid) { /* a record that is no hit stays out of get_specular's wave-level branch */
+            const V3 light_direction = load_v3(light_dirs, k);
+            diffuse = get_diffuse(s.m, s.adj_n, light_direction);
+            specular = get_specular(s.m, s.adj_n, view_direction, light_direction);
         }
-        diffuse_out[k * 3u] = diffuse.x;
-        diffuse_out[k * 3u + 1u] = diffuse.y;
-        diffuse_out[k * 3u + 2u] = diffuse.z;
-        specular_out[k * 3u] = specular.x;
-        specular_out[k * 3u + 1u] = specular.y;
-        specular_out[k * 3u + 2u] = specular.z;
+        store_v3(diffuse_out, k, diffuse);
+        store_v3(specular_out, k, specular);
     }
 }
 
@@ -95,14 +75,7 @@ __global__ __launch_bounds__(RT_MATERIAL_THREADS) void probe_surfaces_kernel(con
 /* rt_probe_surfaces' checks before any device work, in the documented order (no scene: the surface carries what the probe needs);
  * *done: nothing to launch */
 static int probe_args(const char *who, size_t n, uint32_t n_probes, bool pointers_ok, bool *done) {
-    *done = true;
-    int rc = check_count(who, n, RECORDS_2_32);
-    if (rc == RT_OK) rc = check_count(who, (uint64_t)n * (uint64_t)n_probes, {32u, "(record, probe) pairs", "pass the probes in several calls"});
-    if (rc != RT_OK || n == 0 || n_probes == 0) return rc;
-    rc = check_pointers(who, pointers_ok, "surface, view, light-direction, diffuse or specular");
-    if (rc != RT_OK) return rc;
-    *done = false;
-    return RT_OK;
+    return hit_sample_args(who, nullptr, HitSampleArgs(n, pointers_ok, "surface, view, light-direction, diffuse or specular").no_scene().probes(n_probes), done);
 }
 
 extern "C" {

@@ -10,9 +10,9 @@
  *   rt::texture_surfaces_kernel        per record: diffuse_color, normal and shading_normal of an rt_surface, in place
  *   rt::light_terms_surfaces_kernel    main.rs:435-459 per (record, light), the material and the bump normal read from an rt_surface
  *
- * The arithmetic of the first five is rt_texture.h's, shared with librt_host.so; the last makes light_terms_kernel's calls
- * (rt_light_query.hip) on the same operands in the same order.  One element per lane, counted in 64 bits; records move as dwords;
- * every index that addresses the scene is checked against its array first.  No atomics, no workspace.  The C entry points of the block
+ * The arithmetic of the first five is rt_texture.h's, shared with librt_host.so; the last is light_terms_kernel's loop
+ * (rt_light_query.hip) around the same body (rt_light_record.h light_terms), on surface_record's material and normal.  One element
+ * per lane, counted in 64 bits; records move as dwords; every index that addresses the scene is checked against its array first.  No atomics, no workspace.  The C entry points of the block
  * are at the end of the file.
  */
 #include "rt_api_internal.h"
@@ -98,7 +98,8 @@ __global__ __launch_bounds__(RT_TEX_THREADS) void texture_surfaces_kernel(const 
     tex_surface_record(a, i);
 }
 
-/* light_terms_kernel (rt_light_query.hip) with r.m and r.adj_n read from the surface record, as probe_surfaces_kernel reads them */
+/* light_terms_kernel (rt_light_query.hip) with the material and the normal of the surface record, which probe_surfaces_kernel reads
+ * with the same surface_record */
 __global__ __launch_bounds__(RT_LIGHT_THREADS) void light_terms_surfaces_kernel(const KernelScene sc, const rt_surface *__restrict__ surfaces,
                                                                                 const rt_hit *__restrict__ hits, const rt_ray *__restrict__ incoming,
                                                                                 const uint64_t n, const uint32_t light_first, const uint32_t light_count,
@@ -108,68 +109,23 @@ __global__ __launch_bounds__(RT_LIGHT_THREADS) void light_terms_surfaces_kernel(
     const uint64_t i = (uint64_t)blockIdx.x * RT_LIGHT_THREADS + threadIdx.x;
     if (i >= n) return;
     const AbiHit h = hit_from_abi(hits + i, sc.n_triangles, sc.n_spheres, sc.n_materials, true);
-    const uint32_t *const p = reinterpret_cast<const uint32_t *>(surfaces + i);
-    const bool valid = h.valid && p[17] != 0u;
-    Mat m;
-    m.normal = v3(0.0f, 0.0f, 1.0f);
-    m.diffuse = m.specular = v3(0.0f, 0.0f, 0.0f);
-    m.shiness = m.smoothness = m.transparency = m.refraction_index = m.opaque_decay = 0.0f;
-    V3 adj_n = v3(0.0f, 0.0f, 1.0f), pos = v3(0.0f, 0.0f, 0.0f), view = v3(0.0f, 0.0f, 1.0f);
+    const bool valid = h.valid && surface_flag(surfaces, i);
+    SurfaceRecord s; /* "no hit": the flag word alone is read of such a record */
+    V3 pos = v3(0.0f, 0.0f, 0.0f), view = v3(0.0f, 0.0f, 1.0f);
     if (valid) {
-        float f[17];
-#pragma unroll
-        for (uint32_t k = 0; k < 17u; ++k) f[k] = __uint_as_float(p[k]);
-        m.normal = v3(f[0], f[1], f[2]);
-        m.diffuse = v3(f[3], f[4], f[5]);
-        m.shiness = f[6];
-        m.specular = v3(f[7], f[8], f[9]);
-        m.smoothness = f[10];
-        m.transparency = f[11];
-        m.refraction_index = f[12];
-        m.opaque_decay = f[13];
-        adj_n = v3(f[14], f[15], f[16]);
+        s = surface_record(surfaces, i);
         pos = h.g.pos;
         view = ray_from_abi(incoming + i, sc.n_triangles, sc.n_spheres).d; /* hit.ray.direction */
     }
     for (uint32_t l = 0; l < light_count; ++l) { /* wave-uniform */
         const uint64_t k = (uint64_t)l * n + i;
         const bool asked = valid && asks[k] != 0;
-        bool lit = false;
-        V3 diffuse = v3(0.0f, 0.0f, 0.0f), specular = v3(0.0f, 0.0f, 0.0f);
+        LightTerms t; /* not lit, +0 */
         if (__builtin_amdgcn_ballot_w64(asked) != 0ull) { /* a wave nobody asks in skips the light: its acosf and powf are binary64 */
             const auto &L = uniform_ref(sc.lights + (light_first + l));
-            if (asked) {
-                lit = true;
-                const uint32_t *const occluder = reinterpret_cast<const uint32_t *>(shadow_hits + k);
-                if (occluder[0] <= 1u) { /* main.rs:435-448: Some(occlusion) */
-                    const bool has_origin = (L.kind != RT_LIGHT_DIRECTIONAL) || (L.has_origin != 0u);
-                    if (has_origin) {
-                        const V3 occ = v3(__uint_as_float(occluder[RT_LIGHT_HIT_POSITION]), __uint_as_float(occluder[RT_LIGHT_HIT_POSITION + 1u]),
-                                          __uint_as_float(occluder[RT_LIGHT_HIT_POSITION + 2u])); /* occlusion.at.position */
-                        if (distance(pos, occ) < distance(pos, v3(L.origin[0], L.origin[1], L.origin[2]))) lit = false;
-                    } else {
-                        lit = false;
-                    }
-                }
-                if (lit) {
-                    DirLight dl;
-                    dl.direction = dl.color = v3(0.0f, 0.0f, 0.0f);
-                    lit = approximate_into_directional(L, pos, &dl);
-                    if (lit) {
-                        const V3 light_direction = -dl.direction;
-                        diffuse = get_diffuse(m, adj_n, light_direction) * dl.color;
-                        specular = get_specular(m, adj_n, -view, light_direction) * dl.color;
-                    }
-                }
-            }
+            t = light_terms(L, area_light_has_origin(L), v3(L.origin[0], L.origin[1], L.origin[2]), pos, s.m, s.adj_n, view, asked, shadow_hits + k);
         }
-        lit_out[k] = lit ? 1 : 0;
-        diffuse_out[k * 3u] = diffuse.x;
-        diffuse_out[k * 3u + 1u] = diffuse.y;
-        diffuse_out[k * 3u + 2u] = diffuse.z;
-        specular_out[k * 3u] = specular.x;
-        specular_out[k * 3u + 1u] = specular.y;
-        specular_out[k * 3u + 2u] = specular.z;
+        store_light_terms(lit_out, diffuse_out, specular_out, k, t);
     }
 }
 
@@ -177,12 +133,7 @@ __global__ __launch_bounds__(RT_LIGHT_THREADS) void light_terms_surfaces_kernel(
 
 /* ---- the C entry points (include/rt_amd.h "texture queries") ---- */
 
-static int check_texture(const char *who, const rt_texture *tex) {
-    bool unsupported;
-    if (const char *bad = rt::texture_limits(tex, &unsupported))
-        return fail(unsupported ? RT_ERR_UNSUPPORTED : RT_ERR_INVALID_ARGUMENT, std::string(who) + ": " + bad);
-    return RT_OK;
-}
+static int check_texture(const char *who, const rt_texture *tex) { return check_descriptor(who, tex, rt::texture_limits); }
 
 extern "C" {
 
@@ -259,21 +210,17 @@ int rt_texture_surfaces(const rt_texture *diffuse_tex, const rt_texture *normal_
     return launched(who);
 }
 
-/* rt_light_terms' checks (rt_light_query.hip light_args), in its order and with its messages */
+/* rt_light_terms' checks (hit_sample_args, rt_api_internal.h), with the surfaces among the pointers */
 int rt_light_terms_surfaces(const rt_scene *scene, const rt_surface *d_surfaces, const rt_hit *d_hits, const rt_ray *d_incoming, size_t n,
                             uint32_t light_first, uint32_t light_count, const unsigned char *d_asks, const rt_hit *d_shadow_hits,
                             unsigned char *d_lit, float *d_diffuse, float *d_specular, void *hip_stream) {
     const char *const who = "rt_light_terms_surfaces";
-    int rc = check_count(who, n, RECORDS_2_32);
-    if (rc == RT_OK) rc = check_count(who, (uint64_t)n * (uint64_t)light_count, {32u, "(record, light) pairs", "pass the lights in several ranges"});
-    if (rc == RT_OK) rc = check_scene(who, scene);
-    if (rc != RT_OK || n == 0 || light_count == 0) return rc;
-    rc = check_pointers(who, d_surfaces && d_hits && d_incoming && d_asks && d_shadow_hits && d_lit && d_diffuse && d_specular,
-                        "surface, hit, incoming-ray, flag, shadow-hit, lit, diffuse or specular");
-    if (rc != RT_OK) return rc;
-    if ((uint64_t)light_first + (uint64_t)light_count > (uint64_t)scene->ks.n_lights)
-        return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": lights " + std::to_string(light_first) + " .. " +
-                                                 std::to_string((uint64_t)light_first + light_count) + " of a scene with " + std::to_string(scene->ks.n_lights));
+    bool done;
+    const int rc = hit_sample_args(who, scene,
+                                   HitSampleArgs(n, d_surfaces && d_hits && d_incoming && d_asks && d_shadow_hits && d_lit && d_diffuse && d_specular,
+                                                 "surface, hit, incoming-ray, flag, shadow-hit, lit, diffuse or specular")
+                                       .lights(light_count, light_first), &done);
+    if (rc != RT_OK || done) return rc;
     hipLaunchKernelGGL(rt::light_terms_surfaces_kernel, grid_of(n, RT_LIGHT_THREADS), dim3(RT_LIGHT_THREADS), 0, static_cast<hipStream_t>(hip_stream), scene->ks,
                        d_surfaces, d_hits, d_incoming, (uint64_t)n, light_first, light_count, d_asks, d_shadow_hits, d_lit, d_diffuse, d_specular);
     return launched(who);

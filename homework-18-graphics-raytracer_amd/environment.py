@@ -24,7 +24,8 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from ._args import _count_ptr, _new, _on_stream, _out_tensor, _p, _stream_ptr, _tensor, _torch
+from ._args import (_aligned_bytes, _below_2_32, _count_ptr, _host, _new, _on_stream, _out_tensor, _p, _room, _samples, _stream_ptr, _tensor, _void,
+                    _zeroed_out)
 from ._loops import _trace_rays_levels
 from ._queries import _hit_records, cast_rays, cast_rays_indexed, select_records
 from ._world import Scene
@@ -37,13 +38,6 @@ MAX_SPP = 64
 MAX_WIDTH, MAX_HEIGHT = 16384, 8192
 ROW_TILE = 256              # the columns one workgroup of the row scan takes at a time (csrc/rt_environment_query.hip)
 TABLE_HEADER_BYTES = 24
-
-
-def _samples(spp):
-    spp = int(spp)
-    if spp < 0:
-        raise ValueError("spp must not be negative")
-    return spp
 
 
 def table_bytes(width: int, height: int) -> int:
@@ -182,21 +176,6 @@ def fold(scene: Scene, hits, asks, spp: int, radiance, diffuse, specular, out, s
 
 # ---- the CPU forms ----
 
-def _void(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
-def _host(a, dtype, shape, name, optional=False):
-    if a is None and optional:
-        return None
-    a = np.ascontiguousarray(a)
-    if a.dtype != dtype:
-        a = a.view(dtype) if a.dtype.itemsize == np.dtype(dtype).itemsize and a.dtype.kind in "iu" and np.dtype(dtype).kind in "iu" else a.astype(dtype)
-    if a.shape != shape:
-        raise ValueError(f"{name}: expected an array of shape {shape}")
-    return a
-
-
 def _host_environment(texels, rotation, scale, filter):
     """-> (the image, held by the caller of this for as long as the descriptor is used; the descriptor)"""
     texels = np.ascontiguousarray(texels, dtype=np.float32)
@@ -205,10 +184,6 @@ def _host_environment(texels, rotation, scale, filter):
     if not (texels.shape[0] < 1 << 32 and texels.shape[1] < 1 << 32):
         raise ValueError("texels: a side of 2^32 or more")
     return texels, _capi.EnvironmentDesc(texels.ctypes.data, texels.shape[1], texels.shape[0], float(rotation), float(scale), int(filter))
-
-
-def _aligned_bytes(size):
-    return np.zeros((size + 7) // 8, dtype=np.uint64).view(np.uint8)[:size]
 
 
 def table_numpy(texels) -> np.ndarray:
@@ -331,13 +306,9 @@ def workspace(n: int, device, spp: int = 0) -> Workspace:
     return Workspace(int(n), int(n) * int(spp), device)
 
 
-def _room(workspace, n, entries, dev, stream):
-    if workspace is None:
-        with _on_stream(stream):  # allocated with `stream` as torch's current stream: the caching allocator then ties the blocks to it
-            return Workspace(n, entries, dev)
-    if not isinstance(workspace, Workspace) or workspace.entries < entries or workspace.n < n:
-        raise ValueError(f"workspace must be an environment.Workspace with room for {n} records and {entries} (sample, hit) entries (environment.workspace)")
-    return workspace
+def _environment_room(workspace, n, entries, dev, stream):
+    return _room(workspace, Workspace, {"n": n, "entries": entries},
+                 f"an environment.Workspace with room for {n} records and {entries} (sample, hit) entries (environment.workspace)", dev, stream)
 
 
 def sky_hits(scene: Scene, env: Environment, hits, view, spp: int = 16, out=None, pattern: int = STRATIFIED, seed: int = 0, ids=None,
@@ -359,18 +330,12 @@ def sky_hits(scene: Scene, env: Environment, hits, view, spp: int = 16, out=None
     _tensor(ids, "ids", "int32", (n,), optional=True)
     _tensor(open, "open", "uint8", (spp * n,), optional=True)
     _count_ptr(ray_count)
-    if out is None:
-        with _on_stream(stream):
-            out = _new((n, 3), "float32", dev)
-            out.zero_()
-    else:
-        _tensor(out, "out", "float32", (n, 3))
+    out = _zeroed_out(out, n, dev, stream)
     m = spp * n
-    if m >= 1 << 32:
-        raise _capi.RtError(-5, "2^32 (sample, hit) entries or more")
+    _below_2_32(m, "(sample, hit) entries")
     if n == 0:
         return out
-    w = _room(workspace, n, m, dev, stream)
+    w = _environment_room(workspace, n, m, dev, stream)
     s = stream
     _environment_rays(scene, env, records, spp, pattern, seed, ids, normal_kind, env.table(s), w.rays[:m], w.asks[:m], w.dirs[:m], w.radiance[:m], w.texel[:m],
                       stream=s)
@@ -388,16 +353,11 @@ def miss_radiance(scene: Scene, env: Environment, rays, out=None, hits=None, str
     cast's records go (for shade_hits or sky_hits afterwards).  Written from the public calls alone; returns ``out``."""
     env = _environment(env)
     n, dev = _tensor(rays, "rays", "int32", (None, 11)).shape[0], rays.device
-    if out is None:
-        with _on_stream(stream):
-            out = _new((n, 3), "float32", dev)
-            out.zero_()
-    else:
-        _tensor(out, "out", "float32", (n, 3))
+    out = _zeroed_out(out, n, dev, stream)
     if n == 0:
         return out
     if hits is None:
-        hits = _room(workspace, n, 0, dev, stream).hits[:n]
+        hits = _environment_room(workspace, n, 0, dev, stream).hits[:n]
     else:
         _tensor(hits, "hits", "int32", (n, 13))
     cast_rays(scene, rays, out=hits, stream=stream)

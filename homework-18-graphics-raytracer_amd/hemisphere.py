@@ -14,12 +14,10 @@ Arrays are sample-major: entry s * N + i belongs to sample s and hit i.
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
 from . import _capi
-from ._args import _count_ptr, _new, _on_stream, _out_tensor, _p, _stream_ptr, _tensor
+from ._args import _below_2_32, _count_ptr, _host, _new, _on_stream, _out_tensor, _p, _room, _samples, _stream_ptr, _tensor, _void, _zeroed_out
 from ._queries import _hit_records, cast_rays_indexed, select_records, trace_rays
 from ._world import Scene
 
@@ -27,13 +25,6 @@ UNIFORM, STRATIFIED = 1, 2  # RT_FILM_UNIFORM / RT_FILM_STRATIFIED (RT_FILM_CENT
 SHADING, GEOMETRIC = 0, 1   # RT_HEMISPHERE_SHADING / RT_HEMISPHERE_GEOMETRIC
 MAX_SPP = 64
 INF = float("inf")
-
-
-def _samples(spp):
-    spp = int(spp)
-    if spp < 0:
-        raise ValueError("spp must not be negative")
-    return spp
 
 
 def rays(scene: Scene, hits, spp: int, pattern: int = STRATIFIED, seed: int = 0, ids=None, normal_kind: int = SHADING, out_rays=None, out_asks=None,
@@ -83,21 +74,6 @@ def fold(scene: Scene, hits, asks, spp: int, shadow_hits=None, max_distance: flo
     _capi.check(_capi.amd_lib().rt_hemisphere_fold(scene._h, _p(records), n, spp, _p(asks), _p(shadow_hits), float(max_distance), _p(radiance), _p(open),
                                                    _p(ambient), _p(out), _stream_ptr(stream)))
     return open, ambient, out
-
-
-def _void(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
-def _host(a, dtype, shape, name, optional=False):
-    if a is None and optional:
-        return None
-    a = np.ascontiguousarray(a)
-    if a.dtype != dtype:
-        a = a.view(dtype) if a.dtype.itemsize == np.dtype(dtype).itemsize and a.dtype.kind in "iu" and np.dtype(dtype).kind in "iu" else a.astype(dtype)
-    if a.shape != shape:
-        raise ValueError(f"{name}: expected an array of shape {shape}")
-    return a
 
 
 def dirs_numpy(normals, spp: int, pattern: int = STRATIFIED, seed: int = 0, ids=None) -> np.ndarray:
@@ -162,13 +138,9 @@ def workspace(n: int, device, spp: int) -> Workspace:
     return Workspace(int(n) * int(spp), device)
 
 
-def _room(workspace, entries, dev, stream):
-    if workspace is None:
-        with _on_stream(stream):  # allocated with `stream` as torch's current stream: the caching allocator then ties the blocks to it
-            return Workspace(entries, dev)
-    if not isinstance(workspace, Workspace) or workspace.entries < entries:
-        raise ValueError(f"workspace must be a hemisphere.Workspace with room for {entries} (sample, hit) entries (hemisphere.workspace)")
-    return workspace
+def _hemisphere_room(workspace, entries, dev, stream):
+    return _room(workspace, Workspace, {"entries": entries}, f"a hemisphere.Workspace with room for {entries} (sample, hit) entries (hemisphere.workspace)",
+                 dev, stream)
 
 
 def ambient_hits(scene: Scene, hits, spp: int = 16, max_distance: float = INF, pattern: int = STRATIFIED, seed: int = 0, ids=None,
@@ -190,11 +162,10 @@ def ambient_hits(scene: Scene, hits, spp: int = 16, max_distance: float = INF, p
     with _on_stream(stream):
         out = _out_tensor(out, (n,), "float32", dev)
     m = spp * n
-    if m >= 1 << 32:
-        raise _capi.RtError(-5, "2^32 (sample, hit) entries or more")
+    _below_2_32(m, "(sample, hit) entries")
     if n == 0:
         return out
-    w = _room(workspace, m, dev, stream)
+    w = _hemisphere_room(workspace, m, dev, stream)
     s = stream
     _hemisphere_rays(scene, records, spp, pattern, seed, ids, normal_kind, w.rays[:m], w.asks[:m], w.dirs[:m], stream=s)
     select_records(w.asks[:m], w.index[:m], w.count, stream=s)
@@ -217,18 +188,12 @@ def indirect_hits(scene: Scene, hits, spp: int, max_depth: int, contribution: fl
     spp = _samples(spp)
     _tensor(ids, "ids", "int32", (n,), optional=True)
     _count_ptr(ray_count)
-    if out is None:
-        with _on_stream(stream):
-            out = _new((n, 3), "float32", dev)
-            out.zero_()
-    else:
-        _tensor(out, "out", "float32", (n, 3))
+    out = _zeroed_out(out, n, dev, stream)
     m = spp * n
-    if m >= 1 << 32:
-        raise _capi.RtError(-5, "2^32 (sample, hit) entries or more")
+    _below_2_32(m, "(sample, hit) entries")
     if n == 0:
         return out
-    w = _room(workspace, m, dev, stream)
+    w = _hemisphere_room(workspace, m, dev, stream)
     s = stream
     _hemisphere_rays(scene, records, spp, pattern, seed, ids, normal_kind, w.rays[:m], w.asks[:m], w.dirs[:m], stream=s)
     trace_rays(scene, w.rays[:m], max_depth, contribution, out=w.radiance[:m], ray_count=ray_count, stream=s)

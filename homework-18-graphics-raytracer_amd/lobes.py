@@ -24,11 +24,11 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from ._args import _count_ptr, _new, _on_stream, _out_tensor, _p, _stream_ptr, _tensor, _torch
+from ._args import (_aligned_bytes, _below_2_32, _count_ptr, _host, _new, _on_stream, _out_tensor, _p, _room, _samples, _stream_ptr, _tensor, _torch, _void,
+                    _zeroed_out)
 from ._queries import _hit_records, cast_rays, trace_rays
 from ._world import Scene
-from .environment import (TABLE_HEADER_BYTES, Environment, _aligned_bytes, _environment, _environment_rays, _host, _host_environment, _samples, _void,
-                          fold, lookup, table_bytes)
+from .environment import TABLE_HEADER_BYTES, Environment, _environment, _environment_rays, _host_environment, fold, lookup, table_bytes
 from .materials import SURFACE_DTYPE, material_hits, probe_surfaces
 
 UNIFORM, STRATIFIED = 1, 2  # RT_FILM_UNIFORM / RT_FILM_STRATIFIED (RT_FILM_CENTER, 0, is no pattern of a sampler)
@@ -226,13 +226,9 @@ def workspace(n: int, device, spp: int) -> Workspace:
     return Workspace(int(n), int(n) * int(spp), device)
 
 
-def _room(workspace, n, entries, dev, stream):
-    if workspace is None:
-        with _on_stream(stream):  # allocated with `stream` as torch's current stream: the caching allocator then ties the blocks to it
-            return Workspace(n, entries, dev)
-    if not isinstance(workspace, Workspace) or workspace.entries < entries or workspace.n < n:
-        raise ValueError(f"workspace must be a lobes.Workspace with room for {n} records and {entries} (sample, hit) entries (lobes.workspace)")
-    return workspace
+def _lobe_room(workspace, n, entries, dev, stream):
+    return _room(workspace, Workspace, {"n": n, "entries": entries},
+                 f"a lobes.Workspace with room for {n} records and {entries} (sample, hit) entries (lobes.workspace)", dev, stream)
 
 
 def _begin(hits, incoming, ids, out, entries, stream):
@@ -241,14 +237,8 @@ def _begin(hits, incoming, ids, out, entries, stream):
     n, dev = records.shape[0], records.device
     _tensor(incoming, "incoming", "int32", (n, 11))
     _tensor(ids, "ids", "int32", (n,), optional=True)
-    if out is None:
-        with _on_stream(stream):
-            out = _new((n, 3), "float32", dev)
-            out.zero_()
-    else:
-        _tensor(out, "out", "float32", (n, 3))
-    if entries >= 1 << 32:
-        raise _capi.RtError(-5, "2^32 (sample, hit) entries or more")
+    out = _zeroed_out(out, n, dev, stream)
+    _below_2_32(entries, "(sample, hit) entries")
     return records, n, dev, out
 
 
@@ -277,7 +267,7 @@ def glossy_hits(scene: Scene, hits, incoming, spp: int, max_depth: int, contribu
         return out
     m = spp * n
     view = _view_of(incoming, view, n, stream)
-    w = _room(workspace, n, m, dev, stream)
+    w = _lobe_room(workspace, n, m, dev, stream)
     s = stream
     _lobe_rays(scene, records, incoming, spp, pattern, seed, ids, normal_kind, w.rays[:m], w.asks[:m], w.dirs[:m], w.pdf[:m], w.lobe[:m], stream=s)
     trace_rays(scene, w.rays[:m], max_depth, contribution, out=w.radiance[:m], ray_count=ray_count, stream=s)
@@ -309,7 +299,7 @@ def sky_hits_mis(scene: Scene, env: Environment, hits, incoming, spp_env: int = 
     if n == 0 or total == 0:
         return out
     view = _view_of(incoming, view, n, stream)
-    w = _room(workspace, n, total, dev, stream)
+    w = _lobe_room(workspace, n, total, dev, stream)
     s = stream
     material_hits(scene, records, w.surfaces[:n], stream=s)
     if spp_env:

@@ -23,8 +23,7 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from ._args import _count_ptr, _new, _on_stream, _out_tensor, _p, _stream_ptr, _tensor, _torch
-from ._capi import RtError
+from ._args import _below_2_32, _count_ptr, _new, _on_stream, _out_tensor, _p, _stream_ptr, _tensor, _torch, _void
 from ._loops import _trace_rays_levels
 from ._opened import LightWorkspace, _light_range, light_fold, light_rays, shade_hits_by_light
 from ._queries import _hit_records, _hits_and_rays, cast_rays_indexed, select_records
@@ -246,10 +245,6 @@ def light_terms_surfaces(scene: Scene, surfaces, hits, rays, asks, shadow_hits, 
 
 # ---- the CPU forms ----
 
-def _void(a):
-    return None if a is None else C.c_void_p(a.ctypes.data)
-
-
 def _host_words(a, words, name):
     a = np.asarray(a)
     if a.dtype.itemsize != 4 * words and not (a.ndim == 2 and a.shape[1] == words and a.dtype.itemsize == 4):
@@ -395,8 +390,7 @@ def shade_hits_textured(scene: Scene, hits, rays, bindings=None, spread: float =
     if lights_per_pass is not None and per_pass < 1:
         raise ValueError("lights_per_pass must be at least 1")
     per_pass = min(per_pass, lights)
-    if n * per_pass >= 1 << 32:
-        raise RtError(-5, "2^32 (hit, light) pairs or more in one pass (lights_per_pass)")
+    _below_2_32(n * per_pass, "(hit, light) pairs", " in one pass (lights_per_pass)")
     s = stream
     with _on_stream(stream):
         out.zero_()  # `sum` starts black (main.rs:411)
