@@ -35,13 +35,14 @@ reference's host-side names on top of them:
     hemisphere (a submodule)       no counterpart in the reference: cosine-distributed directions over a hit, their shadow rays, and a fold of the answers into ambient occlusion and one bounce of diffuse light
     environment (a submodule)      no counterpart in the reference (a ray that leaves the scene is black, src/main.rs:475): a lat-long sky looked up along the rays that found nothing, its sampling table built on the device, directions drawn from it over a hit with their shadow rays, and a fold of the answers: sky light
     lobes (a submodule)            no counterpart in the reference: directions drawn from a hit's own Phong lobes (the diffuse lobe about the normal, the specular lobe about the mirrored view), the density of a direction under that mixture and under an environment's table, and the weights of multiple importance sampling
+    paths (a submodule)            no counterpart in the reference: the inner step of a path tracer on caller hits — a record that carries the throughput from bounce to bounce, one kernel per bounce that draws from the hit's lobes, weighs, deposits and plays Russian roulette, the mean of a pixel's paths, and the multi-bounce loop written from them
     textures (a submodule)         materials.rs:70-103, GenerativeMaterial's closures of uv read from images: mip-mapped textures and normal maps on rt_surface records, the cone footprint that chooses the level, and get_shade's light terms on such records
     bloom (a submodule)           src/main.rs:761, post_process's "TODO: highlight bloom effect": the highlights above a luma threshold spread down and up a pyramid and added back, between post_process and the encode
     post_process / write_to_file   src/main.rs:748-776
 
 PyTorch is used only for device memory, streams and torch.distributed.
 """
-from . import _capi, adaptive, arealights, bloom, denoise, diagnostics, environment, film, hemisphere, lobes, materials, moving, rectify, svgf, temporal, textures, upsample
+from . import _capi, adaptive, arealights, bloom, denoise, diagnostics, environment, film, hemisphere, lobes, materials, moving, paths, rectify, svgf, temporal, textures, upsample
 from ._capi import Camera, Frame, Light, Material, RtError, SceneDesc, Sphere, Triangle, Vertex
 from ._world import DEFAULT_OBJ, ObjectProxy, Scene, World, reference_camera, reference_world
 from ._render import (Rng, focus_rays, options, render_distributed, render_distributed_numpy, render_whitted, render_whitted_numpy,

@@ -31,6 +31,7 @@
 #include "../rt_hemisphere.h"
 #include "../rt_environment.h"
 #include "../rt_lobe.h"
+#include "../rt_path.h"
 #include "../rt_texture.h"
 
 using rt::V3;
@@ -851,6 +852,72 @@ int rt_mis_weigh_cpu(size_t count, const float *pdf_own, uint32_t n_own, const f
     if (const char *bad = rt::mis_limits(heuristic)) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + bad);
     const rt::MisWeigh m = rt::mis_weigh_call((uint64_t)count, pdf_own, n_own, pdf_other, n_other, heuristic, divide_by_own != 0, weight, rgb);
     for (uint64_t e = 0; e < count; ++e) rt::mis_weigh_entry(m, e);
+    return RT_OK;
+}
+
+/* ---- path queries: the record, the step and the resolve on the CPU (include/rt_amd.h "path queries"; the arithmetic is rt_path.h's, shared with the device) ---- */
+
+int rt_path_begin_cpu(size_t n, uint32_t spp, const uint32_t *ids, rt_path *paths, float *radiance) {
+    const char *const who = "rt_path_begin_cpu: ";
+    if (const int rc = hemisphere_counts(who, n, spp)) return rc;
+    if (n == 0) return RT_OK;
+    if (!paths || !radiance) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + "null path or radiance pointer");
+    if (const char *bad = rt::hemisphere_limits(spp, false, 0u, 0u)) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + bad);
+    for (uint32_t s = 0; s < spp; ++s)
+        for (size_t i = 0; i < n; ++i) {
+            const size_t k = (size_t)s * n + i;
+            paths[k] = rt::path_begin_record((uint32_t)i, ids ? ids[i] : (uint32_t)i, s);
+            radiance[3u * k] = radiance[3u * k + 1u] = radiance[3u * k + 2u] = 0.0f;
+        }
+    return RT_OK;
+}
+
+int rt_path_advance_cpu(const rt_surface *surfaces, const float *normals, const float *view, rt_path *paths, size_t m, const uint32_t *index,
+                        const uint32_t *count, const float *emitted, uint32_t seed, uint32_t rr_start, float rr_floor, int last, float *radiance, float *dirs,
+                        unsigned char *alive) {
+    const char *const who = "rt_path_advance_cpu: ";
+    if ((uint64_t)m >= (1ull << 32)) return fail(RT_ERR_UNSUPPORTED, std::string(who) + "2^32 records or more (checked first; query them in several calls)");
+    if (m == 0) return RT_OK;
+    if (!surfaces || !view || !paths || (index && !count) || !radiance || !dirs || !alive)
+        return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + "null surface, view, path, count (with an index), radiance, direction or flag pointer");
+    if (const char *bad = rt::path_limits(RT_HEMISPHERE_SHADING, rr_floor)) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + bad);
+    const rt::PathStep step = {seed, rr_start, rr_floor, last != 0};
+    const uint32_t listed = rt::path_listed(index, count, (uint32_t)m);
+    for (uint32_t e = 0; e < listed; ++e) {
+        const uint32_t j = index ? index[e] : e;
+        if (j >= m) continue;
+        rt_path &p = paths[j];
+        if ((p.flags & RT_PATH_ALIVE) == 0u) continue;
+        if (emitted)
+            for (uint32_t c = 0; c < 3u; ++c) radiance[3u * j + c] = rt::path_deposit(radiance[3u * j + c], p.beta[c], emitted[3u * j + c]);
+        const rt_surface &s = surfaces[j];
+        rt::Mat mat;
+        mat.normal = rt::v3p(s.normal);
+        mat.diffuse = rt::v3p(s.diffuse_color);
+        mat.specular = rt::v3p(s.specular_color);
+        mat.shiness = s.shiness;
+        mat.smoothness = s.smoothness;
+        mat.transparency = s.transparency;
+        mat.refraction_index = s.refraction_index;
+        mat.opaque_decay = s.opaque_decay;
+        const V3 shading_n = rt::v3p(s.shading_normal);
+        V3 dir;
+        const bool lives = rt::path_advance_record(p, s.valid != 0u, mat, shading_n, normals ? rt::v3p(normals + 3u * j) : shading_n, rt::v3p(view + 3u * j), step, &dir);
+        dirs[3u * j] = dir.x;
+        dirs[3u * j + 1u] = dir.y;
+        dirs[3u * j + 2u] = dir.z;
+        alive[j] = lives ? 1 : 0;
+    }
+    return RT_OK;
+}
+
+int rt_path_resolve_cpu(const float *radiance, size_t n, uint32_t spp, const uint32_t *root, float *rgb) {
+    const char *const who = "rt_path_resolve_cpu: ";
+    if (const int rc = hemisphere_counts(who, n, spp)) return rc;
+    if (n == 0) return RT_OK;
+    if (!radiance || !rgb) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + "null radiance or rgb pointer");
+    if (const char *bad = rt::hemisphere_limits(spp, false, 0u, 0u)) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + bad);
+    for (size_t i = 0; i < n; ++i) rt::path_resolve_root(radiance, (uint64_t)n, spp, i, root, rgb);
     return RT_OK;
 }
 

@@ -24,6 +24,8 @@
  *                      fold are rt_hemisphere.h's, shared with librt_host.so)
  *   rt_environment_query.hip the environment queries' rt_environment_lookup / _table / _rays / _fold: kernels and entry points in one unit (the arithmetic
  *                      is rt_environment.h's, shared with librt_host.so)
+ *   rt_path_query.hip  the path queries' rt_path_begin / rt_path_advance / rt_path_resolve: kernels and entry points in one unit (the record, the step
+ *                      and the resolve are rt_path.h's, shared with librt_host.so; the step calls rt_lobe.h's sampler and rt_shade.h's terms)
  *   rt_refract_query.hip the refraction queries' rt_refract_enter / rt_refract_step: kernels and entry points in one unit
  *   rt_scene_update.hip the scene updates' rt_scene_update_*: kernels and entry points in one unit
  *   rt_motion_query.hip the motion queries' rt_scene_keep_positions / rt_scene_positions_kept / rt_previous_positions and its _host form: kernels and entry points in one unit

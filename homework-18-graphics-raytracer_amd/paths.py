@@ -1,0 +1,242 @@
+"""Path queries (include/rt_amd.h "path queries"): the inner step of a path tracer on caller-supplied hits.
+
+lobes.glossy_hits is one stochastic bounce with the Whitted recursion behind it.  Here a path is a 32-byte record that carries its
+throughput from bounce to bounce; ``advance`` does between two casts what materials.material_hits, lobes.rays,
+materials.probe_surfaces, lobes.mis_weigh and environment.fold do in five launches — one direction from the hit's own lobes, the Phong
+terms along it, the throughput over the direction's density — deposits the light the vertex sends back, and ends paths by Russian
+roulette on the device; ``begin`` makes the records and ``resolve`` adds the mean of a pixel's paths to its slot.
+
+    begin / advance / resolve                       rt_path_begin / rt_path_advance / rt_path_resolve
+    begin_numpy / advance_numpy / resolve_numpy     the CPU forms (rt_path_begin_cpu, rt_path_advance_cpu and rt_path_resolve_cpu of
+                                                    librt_host.so): the device's bits
+    trace_paths                                     begin -> per bounce: shade_hits -> environment.lookup -> advance -> select_records
+                                                    -> cast_rays_indexed -> resolve — written from the public calls alone: to be
+                                                    copied and changed
+
+Arrays are sample-major: path s * N + i is sample s of root i.  The weighting is environment.fold's: the Phong terms are the
+reference's, not normalised, so a white diffuse surface under a constant sky L returns pi * L.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _capi
+from ._args import _below_2_32, _host, _new, _on_stream, _out_tensor, _p, _room, _samples, _stream_ptr, _tensor, _void, _zeroed_out
+from ._opened import LightWorkspace, shade_hits_by_light
+from ._queries import _hit_records, cast_rays_indexed, select_records, shade_hits
+from ._world import Scene
+from .environment import lookup
+from .lobes import _host_surfaces
+
+SHADING, GEOMETRIC = 0, 1  # RT_HEMISPHERE_SHADING / RT_HEMISPHERE_GEOMETRIC
+ALIVE, SPECULAR, ESCAPED, ROULETTE, DARK = 1, 2, 4, 8, 16  # RT_PATH_*
+NO_ROULETTE = 0xFFFFFFFF  # an rr_start no bounce reaches
+PATH_WORDS = 8
+SAMPLE_SHIFT = 24  # rt_path.bounce: the sample index above, the bounces taken below
+PATH_DTYPE = np.dtype([("beta", "<f4", (3,)), ("pdf", "<f4"), ("root", "<u4"), ("id", "<u4"), ("bounce", "<u4"), ("flags", "<u4")])
+assert PATH_DTYPE.itemsize == 4 * PATH_WORDS
+
+
+def begin(n: int, spp: int, ids=None, out_paths=None, out_radiance=None, device="cuda", stream=None):
+    """rt_path_begin: ``spp`` fresh paths for each of ``n`` roots.  Returns (paths, radiance): ``paths`` (S*N, 8) int32 CUDA, the
+    rt_path records (PATH_DTYPE on the host) — beta 1, pdf +0, root i, id ``ids[i]`` ((N,) int32 or None: i), bounce s << 24, flags
+    ALIVE; ``radiance`` (S*N, 3) float32, zeroed.  Both are allocated on ``device`` if not given."""
+    n, spp = int(n), _samples(spp)
+    if n < 0:
+        raise ValueError("n must not be negative")
+    _tensor(ids, "ids", "int32", (n,), optional=True)
+    if ids is not None:
+        device = ids.device
+    with _on_stream(stream):
+        out_paths = _out_tensor(out_paths, (spp * n, PATH_WORDS), "int32", device, "out_paths")
+        out_radiance = _out_tensor(out_radiance, (spp * n, 3), "float32", device, "out_radiance")
+    _capi.check(_capi.amd_lib().rt_path_begin(n, spp, _p(ids), _p(out_paths), _p(out_radiance), _stream_ptr(stream)))
+    return out_paths, out_radiance
+
+
+def advance(scene: Scene, paths, hits, incoming, radiance, emitted=None, index=None, count=None, seed: int = 0, normal_kind: int = SHADING,
+            rr_start: int = 3, rr_floor: float = 0.05, last: bool = False, out_rays=None, out_alive=None, stream=None):
+    """rt_path_advance: one bounce of the listed paths.  ``paths`` (M, 8) int32, ``hits`` (a Hits or its (M, 13) int32 records: the
+    paths' vertices), ``incoming`` (M, 11) int32 (the rays that found them), ``radiance`` (M, 3) float32 and ``emitted`` ((M, 3)
+    float32 or None: what each vertex sends back, shade_hits' or the sky's).  ``index`` ((M,) int32) and ``count`` ((1,) int32), what
+    select_records returns, list the slots to advance; None: all M.  Per listed live path: radiance += beta * emitted; a "no hit"
+    vertex ends it (ESCAPED); ``last`` ends the rest (flags 0); else one direction from the hit's lobes (lobes.rays' for spp 1, UNIFORM,
+    the path's id and sample, seed + 0x9e3779b9 * bounce), beta *= (diffuse (1 - shiness) + specular shiness) / pdf, DARK where that
+    is not positive, and from bounce ``rr_start`` on Russian roulette with survival max(beta) clamped to [``rr_floor``, 1] (ROULETTE;
+    NO_ROULETTE switches it off).  Returns (rays, alive): ``out_rays`` (M, 11) int32, the next ray of a survivor and zero words for a
+    path that ended, and ``out_alive`` (M,) uint8.  ``paths`` and ``radiance`` are updated in place, and so is ``hits``: a path that
+    ended leaves a "no hit" record.  Slots that are not listed or not alive are not touched in any of them."""
+    records = _hit_records(hits)
+    m, dev = records.shape[0], records.device
+    _tensor(paths, "paths", "int32", (m, PATH_WORDS))
+    _tensor(incoming, "incoming", "int32", (m, 11))
+    _tensor(radiance, "radiance", "float32", (m, 3))
+    _tensor(emitted, "emitted", "float32", (m, 3), optional=True)
+    _tensor(index, "index", "int32", (m,), optional=True)  # the call reads up to min(count, M) entries
+    _tensor(count, "count", "int32", (1,), optional=index is None)
+    out_rays = _out_tensor(out_rays, (m, 11), "int32", dev, "out_rays")
+    out_alive = _out_tensor(out_alive, (m,), "uint8", dev, "out_alive")
+    _capi.check(_capi.amd_lib().rt_path_advance(scene._h, _p(paths), m, _p(index), _p(count) if index is not None else None, _p(records), _p(incoming),
+                                                _p(emitted), int(seed) & 0xFFFFFFFF, int(normal_kind), int(rr_start) & 0xFFFFFFFF, float(rr_floor),
+                                                int(bool(last)), _p(radiance), _p(out_rays), _p(out_alive), _stream_ptr(stream)))
+    return out_rays, out_alive
+
+
+def resolve(radiance, n: int, spp: int, out=None, root=None, stream=None):
+    """rt_path_resolve: the mean over the ``spp`` samples of each of ``n`` roots of ``radiance`` ((S*N, 3) float32), the samples added
+    in ascending order, ADDED to ``out`` ((R, 3) float32; None: a new, zeroed (N, 3) tensor) at slot ``root[i]`` ((N,) int32, distinct
+    and below R) or i.  Returns ``out``."""
+    n, spp = int(n), _samples(spp)
+    _tensor(radiance, "radiance", "float32", (spp * n, 3))
+    _tensor(root, "root", "int32", (n,), optional=True)
+    if out is None or root is None:
+        out = _zeroed_out(out, n, radiance.device, stream)
+    else:
+        _tensor(out, "out", "float32", (None, 3))
+    _capi.check(_capi.amd_lib().rt_path_resolve(_p(radiance), n, spp, _p(root), _p(out), _stream_ptr(stream)))
+    return out
+
+
+# ---- the CPU forms ----
+
+def _host_paths(paths):
+    a = np.ascontiguousarray(paths)
+    if a.dtype == PATH_DTYPE:
+        return a.reshape(-1).copy()
+    if a.ndim == 2 and a.shape[1] == PATH_WORDS and a.dtype.itemsize == 4:
+        return a.view(PATH_DTYPE).reshape(-1).copy()
+    raise ValueError("paths: expected a PATH_DTYPE array or an (M, 8) array of 4-byte words")
+
+
+def begin_numpy(n: int, spp: int, ids=None):
+    """rt_path_begin_cpu: begin on the CPU, bit for bit.  Returns (paths — a PATH_DTYPE array of S*N records —, radiance (S*N, 3))."""
+    n, spp = int(n), _samples(spp)
+    ids = _host(ids, np.uint32, (n,), "ids", optional=True)
+    paths, radiance = np.zeros(spp * n, dtype=PATH_DTYPE), np.full((spp * n, 3), np.nan, dtype=np.float32)
+    _capi.check_host(_capi.host_lib().rt_path_begin_cpu(n, spp, _void(ids), _void(paths), _void(radiance)))
+    return paths, radiance
+
+
+def advance_numpy(surfaces, view, paths, radiance, emitted=None, index=None, count=None, seed: int = 0, normals=None, rr_start: int = 3,
+                  rr_floor: float = 0.05, last: bool = False, dirs=None, alive=None):
+    """rt_path_advance_cpu: what advance writes for paths whose vertices' materials are ``surfaces`` (materials.material_hits; valid 0:
+    "no hit") seen from ``view`` ((M, 3) float32), bit for bit, on the CPU.  ``normals`` (M, 3) float32 or None: the N to draw about —
+    None is the record's shading normal (SHADING); pass hit.normal for GEOMETRIC.  ``index`` (K,) and ``count`` (an int): the list, or
+    None for all M.  Returns new arrays (paths, radiance, dirs (M, 3) float32, alive (M,) uint8): the direction of the next ray in
+    place of the ray; ``dirs`` and ``alive`` as given (zeros if None) where a slot is not touched."""
+    surfaces = _host_surfaces(surfaces)
+    m = surfaces.shape[0]
+    view = _host(view, np.float32, (m, 3), "view")
+    normals = _host(normals, np.float32, (m, 3), "normals", optional=True)
+    paths = _host_paths(paths)
+    if paths.shape[0] != m:
+        raise ValueError(f"paths: expected {m} records")
+    radiance = _host(radiance, np.float32, (m, 3), "radiance").copy()
+    emitted = _host(emitted, np.float32, (m, 3), "emitted", optional=True)
+    dirs = np.zeros((m, 3), dtype=np.float32) if dirs is None else _host(dirs, np.float32, (m, 3), "dirs").copy()
+    alive = np.zeros(m, dtype=np.uint8) if alive is None else _host(alive, np.uint8, (m,), "alive").copy()
+    if index is not None:
+        index = np.ascontiguousarray(index).reshape(-1)
+        given = _host(index, np.uint32, index.shape, "index")[:m]
+        index = np.full(m, 0xFFFFFFFF, dtype=np.uint32)  # the C form reads up to min(count, M) entries: the rest name nothing
+        index[:given.shape[0]] = given
+        count = np.array([given.shape[0] if count is None else int(count) & 0xFFFFFFFF], dtype=np.uint32)
+    _capi.check_host(_capi.host_lib().rt_path_advance_cpu(_void(surfaces), _void(normals), _void(view), _void(paths), m, _void(index),
+                                                          _void(count) if index is not None else None, _void(emitted), int(seed) & 0xFFFFFFFF,
+                                                          int(rr_start) & 0xFFFFFFFF, float(rr_floor), int(bool(last)), _void(radiance), _void(dirs),
+                                                          _void(alive)))
+    return paths, radiance, dirs, alive
+
+
+def resolve_numpy(radiance, n: int, spp: int, rgb=None, root=None) -> np.ndarray:
+    """rt_path_resolve_cpu: resolve on the CPU, bit for bit.  Returns a new array: ``rgb`` ((R, 3) float32; None: zeros (N, 3)) plus the
+    roots' means."""
+    n, spp = int(n), _samples(spp)
+    radiance = _host(radiance, np.float32, (spp * n, 3), "radiance")
+    root = _host(root, np.uint32, (n,), "root", optional=True)
+    rgb = np.zeros((n, 3), dtype=np.float32) if rgb is None else np.ascontiguousarray(rgb, dtype=np.float32).copy()
+    if rgb.ndim != 2 or rgb.shape[1] != 3 or (root is None and rgb.shape[0] < n) or (root is not None and n and int(root.max()) >= rgb.shape[0]):
+        raise ValueError("rgb: expected an (R, 3) float32 array that holds every root's slot")
+    _capi.check_host(_capi.host_lib().rt_path_resolve_cpu(_void(radiance), n, spp, _void(root), _void(rgb)))
+    return rgb
+
+
+# ---- the loop ----
+
+class Workspace:
+    """The buffers of trace_paths, made once by workspace() so that a caller's loop allocates nothing: ``entries`` paths of room, about
+    190 B each, and ``pairs`` (path, light) pairs for the opened shade step (126 B each; 0: none)."""
+
+    def __init__(self, entries: int, pairs: int, device):
+        self.entries, self.pairs = int(entries), int(pairs)
+        self.paths, self.radiance = _new((entries, PATH_WORDS), "int32", device), _new((entries, 3), "float32", device)
+        self.hits, self.emitted = _new((entries, 13), "int32", device), _new((entries, 3), "float32", device)
+        self.rays, self.next_rays = _new((entries, 11), "int32", device), _new((entries, 11), "int32", device)
+        self.alive, self.index, self.count = _new((entries,), "uint8", device), _new((entries,), "int32", device), _new((1,), "int32", device)
+        self.lights = LightWorkspace(pairs, device) if pairs else None
+
+
+def workspace(n: int, device, spp: int, scene: Scene = None) -> Workspace:
+    """A Workspace for trace_paths on up to ``n`` roots with ``spp`` samples; with ``scene`` also for ``open_casts`` on its lights."""
+    if n < 0 or spp < 0:
+        raise ValueError("n and spp must not be negative")
+    entries = int(n) * int(spp)
+    return Workspace(entries, entries * scene.n_lights if scene is not None else 0, device)
+
+
+def trace_paths(scene: Scene, hits, incoming, spp: int, max_bounces: int, env=None, rr_start: int = 3, rr_floor: float = 0.05, seed: int = 0, ids=None,
+                out=None, open_casts: bool = True, stream=None, workspace=None):
+    """``spp`` paths of up to ``max_bounces`` bounces from every hit, their mean ADDED to ``out`` ((N, 3) float32 CUDA; None: a new,
+    zeroed tensor): at each vertex the light of the scene's lights (shade_hits) — with ``env`` (an environment.Environment) the sky for
+    the paths that left the scene — times the throughput, then one direction from the vertex's own lobes.  ``hits`` and ``incoming`` are
+    the roots: N hits and the rays that found them.  Written from the public calls alone — the executable form of the sequence in
+    INTEGRATION.md, to be copied and changed:
+      begin -> the spp copies of the roots' hits and rays
+      per bounce b = 0 .. max_bounces:  shade_hits (all slots) -> environment.lookup (the misses; only with env) ->
+                  advance(list_b, last = (b == max_bounces)) -> select_records(alive) -> cast_rays_indexed(next rays, list_b+1);
+                  the next rays are the next bounce's incoming rays
+      resolve
+    Bounce b draws with seed + 0x9e3779b9 * b; roulette starts at bounce ``rr_start`` (NO_ROULETTE: never).  ``open_casts``:
+    shade_hits_by_light in the place of shade_hits, so that every cast of the loop is a cast_rays_indexed (the same bits).  The loop
+    visits the host nowhere, and with ``out`` and ``workspace`` (workspace(n, device, spp, scene)) it allocates nothing; after one
+    eager call on the stream it may be captured into a graph (select_records and the indexed casts need that first call)."""
+    spp, max_bounces = _samples(spp), int(max_bounces)
+    if max_bounces < 0:
+        raise ValueError("max_bounces must not be negative")
+    records = _hit_records(hits)
+    n, dev = records.shape[0], records.device
+    _tensor(incoming, "incoming", "int32", (n, 11))
+    _tensor(ids, "ids", "int32", (n,), optional=True)
+    out = _zeroed_out(out, n, dev, stream)
+    m = spp * n
+    _below_2_32(m, "(sample, hit) entries")
+    if m == 0:
+        return out
+    pairs = m * scene.n_lights if open_casts else 0
+    _below_2_32(pairs, "(path, light) pairs")
+    w = _room(workspace, Workspace, {"entries": m, "pairs": pairs},
+              f"a paths.Workspace with room for {m} paths and {pairs} (path, light) pairs (paths.workspace)", dev, stream)
+    s = stream
+    vertices, emitted, radiance, paths, alive, index = w.hits[:m], w.emitted[:m], w.radiance[:m], w.paths[:m], w.alive[:m], w.index[:m]
+    rays, next_rays = w.rays[:m], w.next_rays[:m]
+    begin(n, spp, ids, paths, radiance, stream=s)
+    with _on_stream(s):  # the spp copies of the roots
+        vertices.view(spp, n, 13).copy_(records.unsqueeze(0).expand(spp, n, 13))
+        rays.view(spp, n, 11).copy_(incoming.unsqueeze(0).expand(spp, n, 11))
+    listed = counted = None  # bounce 0: every slot
+    for b in range(max_bounces + 1):
+        if open_casts:
+            shade_hits_by_light(scene, vertices, rays, out=emitted, stream=s, workspace=w.lights)
+        else:
+            shade_hits(scene, vertices, rays, out=emitted, stream=s)
+        if env is not None:
+            lookup(env, rays, vertices, out=emitted, stream=s)
+        advance(scene, paths, vertices, rays, radiance, emitted, listed, counted, seed, SHADING, rr_start, rr_floor, b == max_bounces, next_rays, alive, stream=s)
+        if b == max_bounces:
+            break
+        listed, counted = select_records(alive, index, w.count, stream=s)
+        cast_rays_indexed(scene, next_rays, listed, counted, vertices, stream=s)
+        rays, next_rays = next_rays, rays
+    return resolve(radiance, n, spp, out, stream=s)

@@ -716,7 +716,7 @@ int rt_probe_surfaces_host(const rt_surface *h_surfaces, size_t n, const float *
  * one kernel with one record or entry per lane and 256 lanes per workgroup, allocates nothing, uses no workspace and may be captured
  * into a HIP graph at once.
  * Not covered: _host and rt_multi_* forms (rt_*_cpu of include/rt_lobe_host.h are the CPU forms); lobes inside rt_render_*; refraction
- * lobes; more than one bounce; any selection probability other than shiness. */
+ * lobes; any selection probability other than shiness.  More than one bounce is the path queries', below. */
 #define RT_MIS_BALANCE 0u /* w = a / (a + b) */
 #define RT_MIS_POWER 1u   /* w = a * a / (a * a + b * b) */
 
@@ -761,6 +761,83 @@ int rt_environment_pdf(const rt_environment *env, const void *d_table, const flo
  * NULL, then an unknown heuristic, RT_ERR_INVALID_ARGUMENT. */
 int rt_mis_weigh(size_t count, const float *d_pdf_own, uint32_t n_own, const float *d_pdf_other, uint32_t n_other, uint32_t heuristic, int divide_by_own,
                  float *d_weight, float *d_rgb, void *hip_stream);
+
+/* ---- path queries: throughput, Russian roulette and multi-bounce paths on caller-supplied hits ---------------------------------------
+
+ * The lobe queries give one stochastic bounce: rt_lobe_rays draws, rt_trace_rays (the Whitted recursion) answers.  A path tracer written
+ * from the public calls takes five launches between two casts — rt_material_hits, rt_lobe_rays, rt_probe_surfaces, rt_mis_weigh and
+ * rt_environment_fold — and still has nothing that carries a throughput from bounce to bounce, ends a path by Russian roulette on the
+ * device, or averages a pixel's paths.  This block is that inner step as ONE kernel (rt_path_advance), the record it keeps (rt_path),
+ * and a begin and a resolve around it.  The loop
+ *     rt_path_begin -> [spp copies of the roots' hits and rays]
+ *     per bounce b: rt_shade_hits (all slots -> d_emitted) -> rt_environment_lookup (the misses; with a sky) ->
+ *                   rt_path_advance(list_b, last = (b == max_bounces)) -> rt_select_records(d_alive -> list_b+1) ->
+ *                   rt_cast_rays_indexed(d_next_rays, list_b+1 -> d_hits);  d_incoming = d_next_rays
+ *     rt_path_resolve
+ * is written out in INTEGRATION.md; DESIGN.md §3.35 has what the fusion saves and the weighting convention.
+ *
+ * Per-path arrays are sample-major: path k = s * n + i is sample s of root i.  Every pointer is a device pointer; every call is
+ * stream-ordered and asynchronous on hip_stream (NULL = default stream), is one kernel with one path or root per lane and 256 lanes per
+ * workgroup, allocates nothing, uses no workspace, no atomics, and may be captured into a HIP graph at once.  All arithmetic is
+ * csrc/rt_path.h's, single f32 and u32 operations in the order given here, none fused, shared by both libraries.
+ * Not covered: refraction lobes; next-event estimation of the sky inside the step (rt_path.pdf is kept for it); _host and rt_multi_*
+ * forms (rt_path_*_cpu of include/rt_path_host.h are the CPU forms); paths inside rt_render_*. */
+#define RT_PATH_ALIVE 1u     /* the path goes on */
+#define RT_PATH_SPECULAR 2u  /* the direction last drawn came from the specular lobe */
+#define RT_PATH_ESCAPED 4u   /* ended on a record that is "no hit" */
+#define RT_PATH_ROULETTE 8u  /* ended by Russian roulette */
+#define RT_PATH_DARK 16u     /* ended: the direction did not ask, or no channel of the new throughput is > 0 (NaN is not) */
+typedef struct rt_path {     /* 8 words, 32 bytes, 16-byte aligned: read and written as two 16-byte accesses */
+    float beta[3];           /* the throughput */
+    float pdf;               /* the density of the direction last drawn; +0 before the first bounce: what a caller's MIS needs on a miss */
+    uint32_t root;           /* the root i the path belongs to */
+    uint32_t id;             /* the id the counter hash takes: the same for every sample of a root */
+    uint32_t bounce;         /* bits 0-23: the bounces taken; bits 24-31: the sample index s, the hash's sample argument */
+    uint32_t flags;          /* RT_PATH_ALIVE, with RT_PATH_SPECULAR; or how the path ended; 0: ended by `last` */
+} rt_path;
+
+/* spp fresh paths per root: d_paths[k] = { beta 1, pdf +0, root i, id d_ids[i] (NULL: i), bounce s << 24, flags RT_PATH_ALIVE } and
+ * d_radiance[3k ..] = 0 for k = s * n + i.  Checked in this order: n >= 2^32 or n * spp >= 2^32 is RT_ERR_UNSUPPORTED; n == 0 is RT_OK and
+ * launches nothing; a null d_paths or d_radiance, then spp outside 1 .. 64, then a d_paths that is not 16-byte aligned,
+ * RT_ERR_INVALID_ARGUMENT. */
+int rt_path_begin(size_t n, uint32_t spp, const uint32_t *d_ids, rt_path *d_paths, float *d_radiance, void *hip_stream);
+/* One bounce of the listed paths among m slots.  d_index / d_count are rt_cast_rays_indexed's list: slot j = d_index[e] for
+ * e < min(*d_count, m); an index >= m names nothing; a slot is listed at most once.  d_index NULL: every j < m, and d_count is not
+ * read.  d_hits[j] is the path's vertex and d_incoming[j] the ray that found it (Hit.ray), as in rt_shade_hits; d_emitted[3j ..] the
+ * light the vertex sends back along that ray (rt_shade_hits', the sky's for a miss), or NULL.  For each listed slot whose flags have
+ * RT_PATH_ALIVE, in this order:
+ *   deposit      d_radiance[3j + c] = d_radiance[3j + c] + beta[c] * d_emitted[3j + c]: the product rounded, then the sum
+ *   escape       d_hits[j] is "no hit" by the hit queries' rules: the path ends with RT_PATH_ESCAPED
+ *   last         last != 0: the path ends with flags 0 and nothing is drawn
+ *   sample       rt_lobe_rays' direction, density, lobe and flag for spp = 1, RT_FILM_UNIFORM, id = path.id and, as the hash's
+ *                sample argument, the path's own s (bounce >> 24): the hash's argument carries s, so the seed carries the bounce
+ *                alone — seed_b = seed + 0x9e3779b9u * b with b the bounces taken, a u32 wrap; bounce 0 draws with `seed` itself
+ *   terms        rt_probe_surfaces' diffuse and specular of that direction on rt_material_hits' surface, V = -d_incoming[j].direction
+ *   throughput   t = beta * (1.0f / pdf) per channel — rt_mis_weigh with divide_by_own and no other strategy — and
+ *                beta' = (+0 + (diffuse * t) * (1 - shiness)) + (specular * t) * shiness — rt_environment_fold for spp = 1 into a
+ *                zeroed rgb, so a -0 reads +0.  The flag is 0, or no channel of beta' is > 0: the path ends with RT_PATH_DARK
+ *   roulette     where b + 1 >= rr_start: q = the largest channel of beta' (q = 0, then q = c > q ? c : q for r, g, b: a NaN channel is
+ *                passed over), q = q < rr_floor ? rr_floor : q, q = q > 1 ? 1 : q, and
+ *                    u_3 = film_u(id, film_mix(seed_h ^ 0x165667b1u), s, 0)
+ *                with the sample's seed_h, a stream apart from u_0, u_1 and the lobe's u_2 (0x27d4eb2fu).  u_3 < q: beta' = beta' / q
+ *                per channel; else the path ends with RT_PATH_ROULETTE.  rr_start 0xffffffff: no roulette
+ *   write        a survivor: beta = beta', pdf, bounce + 1, flags RT_PATH_ALIVE | RT_PATH_SPECULAR as drawn, d_alive[j] = 1 and
+ *                d_next_rays[j] = rt_lobe_rays' shadow ray.  A path that ended: its flags alone change in the record, d_alive[j] = 0,
+ *                d_next_rays[j] all-zero words and d_hits[j] the "no hit" record (kind RT_HIT_NONE, every other word 0), so that
+ *                a later rt_shade_hits over all slots spends nothing on it and a later advance cannot revive it
+ * Slots that are not listed, and listed ones that are not alive, are not touched.  normal_kind chooses the N the direction is drawn
+ * about, as in rt_lobe_rays; the terms take the shading normal.
+ * Checked before any device work as rt_lobe_rays checks, in its order and with its messages: m >= 2^32 is RT_ERR_UNSUPPORTED; a null
+ * scene; m == 0 is RT_OK and launches nothing; a null pointer (d_index, d_emitted may be NULL; d_count only with d_index); the
+ * normal_kind; then an rr_floor outside (0, 1] (NaN is), then a d_paths that is not 16-byte aligned, RT_ERR_INVALID_ARGUMENT. */
+int rt_path_advance(const rt_scene *scene, rt_path *d_paths, size_t m, const uint32_t *d_index, const uint32_t *d_count, rt_hit *d_hits,
+                    const rt_ray *d_incoming, const float *d_emitted, uint32_t seed, uint32_t normal_kind, uint32_t rr_start, float rr_floor, int last,
+                    float *d_radiance, rt_ray *d_next_rays, unsigned char *d_alive, void *hip_stream);
+/* Per root i of n: the samples s = 0 .. spp - 1 of d_radiance in that order, the first as it is and each later one added, the sum
+ * / (float)spp, ADDED to d_rgb[3r ..] with r = d_root[i], or i where d_root is NULL (the caller keeps r inside d_rgb and the r of two
+ * roots apart).  No atomics: the same bits on every run.  Checked as rt_path_begin checks: the counts, n == 0, a null d_radiance or
+ * d_rgb, spp. */
+int rt_path_resolve(const float *d_radiance, size_t n, uint32_t spp, const uint32_t *d_root, float *d_rgb, void *hip_stream);
 
 /* ---- texture queries: mip-mapped image textures and normal maps on caller-supplied hits ------------------------------
 
