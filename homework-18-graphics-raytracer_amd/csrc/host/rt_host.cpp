@@ -32,6 +32,7 @@
 #include "../rt_environment.h"
 #include "../rt_lobe.h"
 #include "../rt_path.h"
+#include "../rt_transmit.h"
 #include "../rt_texture.h"
 
 using rt::V3;
@@ -918,6 +919,77 @@ int rt_path_resolve_cpu(const float *radiance, size_t n, uint32_t spp, const uin
     if (!radiance || !rgb) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + "null radiance or rgb pointer");
     if (const char *bad = rt::hemisphere_limits(spp, false, 0u, 0u)) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + bad);
     for (size_t i = 0; i < n; ++i) rt::path_resolve_root(radiance, (uint64_t)n, spp, i, root, rgb);
+    return RT_OK;
+}
+
+/* ---- transmission queries: the choice and the fold on the CPU (include/rt_amd.h "transmission queries"; the arithmetic is rt_transmit.h's, shared with the device) ---- */
+
+int rt_path_branch_cpu(const rt_surface *surfaces, const rt_hit *hits, const rt_ray *incoming, rt_path *paths, size_t m, const uint32_t *index,
+                       const uint32_t *count, uint32_t seed, int last, unsigned char *lobe, unsigned char *transmit, rt_ray *walk_rays, uint32_t *kind,
+                       float *travel, uint32_t *casts, unsigned char *walk_flags) {
+    const char *const who = "rt_path_branch_cpu: ";
+    if ((uint64_t)m >= (1ull << 32)) return fail(RT_ERR_UNSUPPORTED, std::string(who) + "2^32 records or more (checked first; query them in several calls)");
+    if (m == 0) return RT_OK;
+    if (!surfaces || !hits || !incoming || !paths || (index && !count) || !lobe || !transmit || !walk_rays || !kind || !travel || !casts || !walk_flags)
+        return fail(RT_ERR_INVALID_ARGUMENT,
+                    std::string(who) + "null surface, hit, incoming-ray, path, count (with an index), lobe, transmit, walk-ray, kind, travel, cast-count or walk-flag pointer");
+    const uint32_t listed = rt::path_listed(index, count, (uint32_t)m);
+    for (uint32_t e = 0; e < listed; ++e) {
+        const uint32_t j = index ? index[e] : e;
+        if (j >= m) continue;
+        rt_path &p = paths[j];
+        bool transmits = false, lobes = false;
+        uint32_t result = RT_HIT_NONE;
+        rt_ray inside = rt::no_ray_record();
+        if ((p.flags & RT_PATH_ALIVE) != 0u) {
+            const rt_surface &s = surfaces[j];
+            const bool valid = s.valid != 0u;
+            transmits = rt::path_transmits(p.id, p.bounce, seed, valid, valid ? s.transparency : 0.0f);
+            if (transmits && last) {
+                p.flags = 0u;
+                transmits = false;
+            } else if (transmits) {
+                result = rt::refract_enter_record(true, rt::v3p(hits[j].position), rt::v3p(hits[j].normal), rt::v3p(incoming[j].direction), s.refraction_index,
+                                                  hits[j].kind, hits[j].index, &inside);
+            } else {
+                lobes = true;
+            }
+        }
+        lobe[j] = lobes ? 1 : 0;
+        transmit[j] = transmits ? 1 : 0;
+        walk_rays[j] = inside;
+        kind[j] = result;
+        travel[j] = 0.0f;
+        casts[j] = 0u;
+        walk_flags[j] = result == RT_REFR_WALKING ? 1 : 0;
+    }
+    return RT_OK;
+}
+
+int rt_path_transmit_cpu(const rt_surface *surfaces, rt_path *paths, size_t m, const uint32_t *index, const uint32_t *count, uint32_t *kind, const float *travel,
+                         const rt_ray *escape, uint32_t seed, uint32_t rr_start, float rr_floor, rt_ray *next_rays, unsigned char *alive,
+                         unsigned char *walk_flags) {
+    const char *const who = "rt_path_transmit_cpu: ";
+    if ((uint64_t)m >= (1ull << 32)) return fail(RT_ERR_UNSUPPORTED, std::string(who) + "2^32 records or more (checked first; query them in several calls)");
+    if (m == 0) return RT_OK;
+    if (!surfaces || !paths || (index && !count) || !kind || !travel || !escape || !next_rays || !alive || !walk_flags)
+        return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + "null surface, path, count (with an index), kind, travel, escape-ray, ray, flag or walk-flag pointer");
+    if (const char *bad = rt::path_limits(RT_HEMISPHERE_SHADING, rr_floor)) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + bad);
+    const rt::PathStep step = {seed, rr_start, rr_floor, false};
+    const uint32_t listed = rt::path_listed(index, count, (uint32_t)m);
+    for (uint32_t e = 0; e < listed; ++e) {
+        const uint32_t j = index ? index[e] : e;
+        if (j >= m) continue;
+        const uint32_t walk = kind[j];
+        kind[j] = RT_HIT_NONE;
+        walk_flags[j] = 0;
+        rt_path &p = paths[j];
+        if ((p.flags & RT_PATH_ALIVE) == 0u) continue;
+        const bool valid = surfaces[j].valid != 0u;
+        const bool lives = rt::path_transmit_record(p, walk, valid, valid ? surfaces[j].opaque_decay : 0.0f, travel[j], step);
+        alive[j] = lives ? 1 : 0;
+        next_rays[j] = lives ? escape[j] : rt::no_ray_record();
+    }
     return RT_OK;
 }
 

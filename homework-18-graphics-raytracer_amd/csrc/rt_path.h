@@ -4,7 +4,8 @@
  * calls of the other blocks compute between two casts, on one record: rt_lobe.h's sampler and density for the direction, rt_shade.h's
  * get_diffuse and get_specular for the terms, rt_lobe.h's weighing "over its own density" for the throughput and rt_environment.h's
  * fold association for the mixture of the two terms — called here, none of them written again — and then what no call had: the
- * throughput carried in the record, Russian roulette from a stream of the counter hash, and the mean of a pixel's paths.  Every
+ * throughput carried in the record, Russian roulette from a stream of the counter hash (path_step_tail, which rt_transmit.h's fold of a
+ * walk through glass calls too), and the mean of a pixel's paths.  Every
  * function is a sequence of single f32 or u32 operations in the order the header comment of the block gives; both libraries are built
  * with -ffp-contract=off and the divides are correctly rounded on either side, so the host and the device forms agree bit for bit.
  */
@@ -62,6 +63,29 @@ inline const char *path_limits(uint32_t normal_kind, float rr_floor) {
 /* the deposit of one channel: the product rounded, then the sum */
 RT_FILM_HD float path_deposit(float radiance, float beta, float emitted) { return radiance + beta * emitted; }
 
+/* The end of a step, on the new throughput *next — shared by path_advance_record and rt_transmit.h's path_transmit_record: the dark test
+ * (`ok` is the direction's flag), then roulette from the bounce's own stream where bounces + 1 >= rr_start, with `seed_h` the bounce's
+ * hemisphere_seed.  Returns the flag the path ends with, or 0: it survives, and *next is divided by its chance. */
+RT_FILM_HD uint32_t path_step_tail(V3 *next_io, bool ok, uint32_t id, uint32_t s, uint32_t bounces, uint32_t seed_h, const PathStep &q) {
+    V3 next = *next_io;
+    if (!ok || !(next.x > 0.0f || next.y > 0.0f || next.z > 0.0f)) return RT_PATH_DARK;
+
+    /* roulette: q = the largest channel (a NaN channel is passed over), raised to rr_floor, cut at 1 */
+    if (bounces + 1u >= q.rr_start) {
+        float chance = 0.0f;
+        chance = next.x > chance ? next.x : chance;
+        chance = next.y > chance ? next.y : chance;
+        chance = next.z > chance ? next.z : chance;
+        chance = chance < q.rr_floor ? q.rr_floor : chance;
+        chance = chance > 1.0f ? 1.0f : chance;
+        const float u3 = film_u(id, film_mix(seed_h ^ RT_PATH_ROULETTE_STREAM), s, 0u);
+        if (!(u3 < chance)) return RT_PATH_ROULETTE;
+        next = next / chance;
+    }
+    *next_io = next;
+    return 0u;
+}
+
 /* One ALIVE path at a vertex, after the deposit.  `hit`: the record is a hit by the hit queries' rules, `m` its material, `shading_n`
  * adjust_normal of its normal — the N of the terms — and `sampling_n` the N the direction is drawn about (normal_kind), `view` minus
  * the incoming direction.  The record `p` is advanced in place; *dir: the direction drawn, zeros for a path that ended.  Returns
@@ -95,25 +119,9 @@ RT_FILM_HD bool path_advance_record(rt_path &p, bool hit, const Mat &m, V3 shadi
     const float f = d.ok ? 1.0f / d.pdf : 0.0f;
     const V3 t = beta * f;
     V3 next = v3(0.0f, 0.0f, 0.0f) + (diffuse * t) * (1.0f - m.shiness) + (specular * t) * m.shiness;
-    if (!d.ok || !(next.x > 0.0f || next.y > 0.0f || next.z > 0.0f)) {
-        p.flags = RT_PATH_DARK;
+    if (const uint32_t ended = path_step_tail(&next, d.ok, p.id, s, bounces, seed_h, q)) {
+        p.flags = ended;
         return false;
-    }
-
-    /* roulette: q = the largest channel (a NaN channel is passed over), raised to rr_floor, cut at 1 */
-    if (bounces + 1u >= q.rr_start) {
-        float chance = 0.0f;
-        chance = next.x > chance ? next.x : chance;
-        chance = next.y > chance ? next.y : chance;
-        chance = next.z > chance ? next.z : chance;
-        chance = chance < q.rr_floor ? q.rr_floor : chance;
-        chance = chance > 1.0f ? 1.0f : chance;
-        const float u3 = film_u(p.id, film_mix(seed_h ^ RT_PATH_ROULETTE_STREAM), s, 0u);
-        if (!(u3 < chance)) {
-            p.flags = RT_PATH_ROULETTE;
-            return false;
-        }
-        next = next / chance;
     }
 
     p.beta[0] = next.x;

@@ -9,7 +9,7 @@
  *   rt::refract_step_kernel   main.rs:371-402 per walking record, for ONE answered cast: Infinite, the bounce ray, the escape ray or Trapped
  *
  * Nothing here is new arithmetic: hit_from_abi, ray_from_abi, material_approx, refract_dir, reflect_dir, normalize and distance are called
- * as rt::refract_rays_kernel (rt_hit_query.hip) calls them, with the same operands in the same order, and the unit is compiled with
+ * as rt::refract_rays_kernel (rt_hit_query.hip) calls them (the entry through rt_refract_entry.h, which rt_path_branch shares), with the same operands in the same order, and the unit is compiled with
  * -ffp-contract=off like every other — so every bit is rt_refract_rays'.  One record per lane, the record number counted in 64 bits.
  * The walk's state lives in the caller's arrays (kind, travel, casts, the ray in flight) and is validated, never trusted: nothing is
  * indexed with a state word.  Records move as dwords.  No LDS, no cast.  The C entry points of the block are at the end of the file.
@@ -17,6 +17,7 @@
 #include "rt_api_internal.h"
 #include "rt_cast.h"
 #include "rt_hit_abi.h"
+#include "rt_refract_entry.h"
 
 namespace rt {
 
@@ -35,21 +36,16 @@ __global__ __launch_bounds__(RT_REFR_THREADS) void refract_enter_kernel(const Ke
                                                                         unsigned char *__restrict__ flags) {
     const uint64_t i = (uint64_t)blockIdx.x * RT_REFR_THREADS + threadIdx.x;
     if (i >= n) return;
-    uint32_t result = RT_HIT_NONE;
     const AbiHit h = hit_from_abi(hits + i, sc.n_triangles, sc.n_spheres, sc.n_materials, true);
+    V3 in_dir = v3(0.0f, 0.0f, 0.0f);
+    float k = 1.0f;
     if (h.valid) {
-        const V3 in_dir = ray_from_abi(incoming + i, sc.n_triangles, sc.n_spheres).d; /* hit.ray.direction */
-        const float k = material_approx(sc.materials[h.g.obj], h.g.u, h.g.v).refraction_index; /* main.rs:354 */
-        V3 refract_in;
-        if (refract_dir(h.g.normal, in_dir, k, &refract_in)) {
-            result = RT_REFR_WALKING;
-            /* ray_inside, main.rs:360-368: the direction normalised a second time; bit for bit the ray refract_rays_kernel casts first */
-            store_ray(rays + i, h.g.pos, normalize(refract_in), FACE_BACK, 1u, h.kind, h.index, FACE_FRONT);
-        } else {
-            result = 2u; /* Trapped, main.rs:356-358 */
-        }
+        in_dir = ray_from_abi(incoming + i, sc.n_triangles, sc.n_spheres).d; /* hit.ray.direction */
+        k = material_approx(sc.materials[h.g.obj], h.g.u, h.g.v).refraction_index; /* main.rs:354 */
     }
-    if (result != RT_REFR_WALKING) store_no_ray(rays + i);
+    rt_ray inside; /* Trapped at entry (main.rs:356-358), or ray_inside (main.rs:360-368): rt_refract_entry.h */
+    const uint32_t result = refract_enter_record(h.valid, h.g.pos, h.g.normal, in_dir, k, h.kind, h.index, &inside);
+    store_ray_record(rays + i, inside);
     kind[i] = result;
     travel[i] = 0.0f;
     casts[i] = 0u;

@@ -9,6 +9,9 @@ roulette on the device; ``begin`` makes the records and ``resolve`` adds the mea
     begin / advance / resolve                       rt_path_begin / rt_path_advance / rt_path_resolve
     begin_numpy / advance_numpy / resolve_numpy     the CPU forms (rt_path_begin_cpu, rt_path_advance_cpu and rt_path_resolve_cpu of
                                                     librt_host.so): the device's bits
+    branch / transmit                               rt_path_branch / rt_path_transmit ("transmission queries"): the choice between a
+                                                    vertex's lobes and its glass, and a finished walk folded into the record
+    branch_numpy / transmit_numpy                   their CPU forms (rt_path_branch_cpu and rt_path_transmit_cpu): the device's bits
     trace_paths                                     begin -> per bounce: shade_hits -> environment.lookup -> advance -> select_records
                                                     -> cast_rays_indexed -> resolve — written from the public calls alone: to be
                                                     copied and changed
@@ -23,15 +26,16 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from ._args import _below_2_32, _host, _new, _on_stream, _out_tensor, _p, _room, _samples, _stream_ptr, _tensor, _void, _zeroed_out
-from ._opened import LightWorkspace, shade_hits_by_light
-from ._queries import _hit_records, cast_rays_indexed, select_records, shade_hits
+from ._args import _below_2_32, _host, _host_records, _new, _on_stream, _out_tensor, _p, _room, _samples, _stream_ptr, _tensor, _void, _zeroed_out
+from ._opened import LightWorkspace, refract_step, shade_hits_by_light
+from ._queries import HIT_DTYPE, HIT_NONE, RAY_DTYPE, _hit_records, cast_rays_indexed, select_records, shade_hits
 from ._world import Scene
 from .environment import lookup
 from .lobes import _host_surfaces
 
 SHADING, GEOMETRIC = 0, 1  # RT_HEMISPHERE_SHADING / RT_HEMISPHERE_GEOMETRIC
-ALIVE, SPECULAR, ESCAPED, ROULETTE, DARK = 1, 2, 4, 8, 16  # RT_PATH_*
+ALIVE, SPECULAR, ESCAPED, ROULETTE, DARK, TRANSMITTED, TRAPPED = 1, 2, 4, 8, 16, 32, 64  # RT_PATH_*
+MAX_DISTANCE = 100.0  # what the reference passes to get_refract (main.rs:502): the walk's max_distance in trace_paths
 NO_ROULETTE = 0xFFFFFFFF  # an rr_start no bounce reaches
 PATH_WORDS = 8
 SAMPLE_SHIFT = 24  # rt_path.bounce: the sample index above, the bounces taken below
@@ -99,6 +103,65 @@ def resolve(radiance, n: int, spp: int, out=None, root=None, stream=None):
     return out
 
 
+# ---- transmission (include/rt_amd.h "transmission queries") ----
+
+def _listed(m, dev, paths, index, count):
+    _tensor(paths, "paths", "int32", (m, PATH_WORDS))
+    _tensor(index, "index", "int32", (m,), optional=True)  # the call reads up to min(count, M) entries
+    _tensor(count, "count", "int32", (1,), optional=index is None)
+    return _p(index), (_p(count) if index is not None else None)
+
+
+def branch(scene: Scene, paths, hits, incoming, index=None, count=None, seed: int = 0, last: bool = False, out_lobe=None, out_transmit=None,
+           out_walk_rays=None, out_kind=None, out_travel=None, out_casts=None, out_walk_flags=None, stream=None):
+    """rt_path_branch: per listed live path the choice between the vertex's lobes and its glass — it transmits iff the vertex is a hit
+    and u_4 < its material's transparency, u_4 from the path's id and sample, seed + 0x9e3779b9 * bounce and a stream of its own — and
+    for a path that transmits refract_enter's state of a walk that has cast nothing.  ``paths`` (M, 8) int32, ``hits`` (a Hits or its
+    (M, 13) int32 records), ``incoming`` (M, 11) int32; ``index`` / ``count``: advance's list.  Returns (lobe, transmit, walk_rays, kind,
+    travel, casts, walk_flags): ``lobe`` and ``transmit`` (M,) uint8, exactly one of them 1 for a listed live path — the operands of
+    select_records for advance and for transmit —, and the five arrays of refract_enter, which hold a finished walk (kind HIT_NONE, flag
+    0) wherever nothing walks.  ``last``: a transmitting path ends here (flags 0, both bytes 0, its hit "no hit").  Slots that are not
+    listed are not touched."""
+    records = _hit_records(hits)
+    m, dev = records.shape[0], records.device
+    index_p, count_p = _listed(m, dev, paths, index, count)
+    _tensor(incoming, "incoming", "int32", (m, 11))
+    out_lobe = _out_tensor(out_lobe, (m,), "uint8", dev, "out_lobe")
+    out_transmit = _out_tensor(out_transmit, (m,), "uint8", dev, "out_transmit")
+    out_walk_rays = _out_tensor(out_walk_rays, (m, 11), "int32", dev, "out_walk_rays")
+    out_kind = _out_tensor(out_kind, (m,), "int32", dev, "out_kind")
+    out_travel = _out_tensor(out_travel, (m,), "float32", dev, "out_travel")
+    out_casts = _out_tensor(out_casts, (m,), "int32", dev, "out_casts")
+    out_walk_flags = _out_tensor(out_walk_flags, (m,), "uint8", dev, "out_walk_flags")
+    _capi.check(_capi.amd_lib().rt_path_branch(scene._h, _p(paths), m, index_p, count_p, _p(records), _p(incoming), int(seed) & 0xFFFFFFFF, int(bool(last)),
+                                               _p(out_lobe), _p(out_transmit), _p(out_walk_rays), _p(out_kind), _p(out_travel), _p(out_casts),
+                                               _p(out_walk_flags), _stream_ptr(stream)))
+    return out_lobe, out_transmit, out_walk_rays, out_kind, out_travel, out_casts, out_walk_flags
+
+
+def transmit(scene: Scene, paths, hits, kind, travel, escape, walk_flags, index=None, count=None, seed: int = 0, rr_start: int = 3,
+             rr_floor: float = 0.05, out_rays=None, out_alive=None, stream=None):
+    """rt_path_transmit: the finished walk of each listed live path folded into its record.  ``kind`` (M,) int32, ``travel`` (M,)
+    float32 and ``escape`` (M, 11) int32 as refract_step left them, ``hits`` still the vertices the paths entered the glass at.  An
+    ESCAPED walk: beta *= opaque_decay ** travel, then advance's own tail (DARK, and from bounce ``rr_start`` on its roulette), and the
+    survivor goes on along the escape ray with pdf +0, one bounce more and flags ALIVE | TRANSMITTED; anything else ends the path with
+    TRAPPED.  Returns (rays, alive) as advance does; ``paths`` and ``hits`` are updated in place as advance updates them, and ``kind``
+    and ``walk_flags`` of every listed slot are left HIT_NONE and 0.  Slots that are not listed are not touched."""
+    records = _hit_records(hits)
+    m, dev = records.shape[0], records.device
+    index_p, count_p = _listed(m, dev, paths, index, count)
+    _tensor(kind, "kind", "int32", (m,))
+    _tensor(travel, "travel", "float32", (m,))
+    _tensor(escape, "escape", "int32", (m, 11))
+    _tensor(walk_flags, "walk_flags", "uint8", (m,))
+    out_rays = _out_tensor(out_rays, (m, 11), "int32", dev, "out_rays")
+    out_alive = _out_tensor(out_alive, (m,), "uint8", dev, "out_alive")
+    _capi.check(_capi.amd_lib().rt_path_transmit(scene._h, _p(paths), m, index_p, count_p, _p(records), _p(kind), _p(travel), _p(escape),
+                                                 int(seed) & 0xFFFFFFFF, int(rr_start) & 0xFFFFFFFF, float(rr_floor), _p(out_rays), _p(out_alive),
+                                                 _p(walk_flags), _stream_ptr(stream)))
+    return out_rays, out_alive
+
+
 # ---- the CPU forms ----
 
 def _host_paths(paths):
@@ -163,31 +226,103 @@ def resolve_numpy(radiance, n: int, spp: int, rgb=None, root=None) -> np.ndarray
     return rgb
 
 
+def _host_list(index, count, m):
+    """(index, count) as the C forms take them: ``index`` padded to M entries that name nothing, ``count`` one u32"""
+    if index is None:
+        return None, None
+    index = np.ascontiguousarray(index).reshape(-1)
+    given = _host(index, np.uint32, index.shape, "index")[:m]
+    padded = np.full(m, 0xFFFFFFFF, dtype=np.uint32)  # the C form reads up to min(count, M) entries: the rest name nothing
+    padded[:given.shape[0]] = given
+    return padded, np.array([given.shape[0] if count is None else int(count) & 0xFFFFFFFF], dtype=np.uint32)
+
+
+def _start(a, dtype, shape, name, fill=0):
+    return np.full(shape, fill, dtype=dtype) if a is None else _host(a, dtype, shape, name).copy()
+
+
+def branch_numpy(surfaces, hits, incoming, paths, index=None, count=None, seed: int = 0, last: bool = False, lobe=None, transmit=None,
+                 walk_rays=None, kind=None, travel=None, casts=None, walk_flags=None):
+    """rt_path_branch_cpu: what branch writes for paths whose vertices are ``hits`` (HIT_DTYPE or (M, 13) words) with the materials
+    ``surfaces`` (materials.material_hits; valid 0: "no hit") found by ``incoming`` (RAY_DTYPE or (M, 11) words), bit for bit, on the CPU.
+    Returns new arrays (paths, lobe, transmit, walk_rays (M, 11) uint32, kind, travel, casts, walk_flags); the seven outputs as given
+    (zeros, kind HIT_NONE, if None) where a slot is not touched.  No hit record is rewritten: the "no hit" of a path ``last`` ends is
+    the device's alone."""
+    surfaces = _host_surfaces(surfaces)
+    m = surfaces.shape[0]
+    hits = _host_records(hits, HIT_DTYPE, 13, "hits")
+    incoming = _host_records(incoming, RAY_DTYPE, 11, "incoming")
+    paths = _host_paths(paths)
+    if not hits.shape[0] == incoming.shape[0] == paths.shape[0] == m:
+        raise ValueError(f"hits, incoming, paths: expected {m} records each")
+    lobe, transmit = _start(lobe, np.uint8, (m,), "lobe"), _start(transmit, np.uint8, (m,), "transmit")
+    walk_rays = _start(walk_rays, np.uint32, (m, 11), "walk_rays")
+    kind, travel = _start(kind, np.uint32, (m,), "kind", _capi.RT_HIT_NONE), _start(travel, np.float32, (m,), "travel")
+    casts, walk_flags = _start(casts, np.uint32, (m,), "casts"), _start(walk_flags, np.uint8, (m,), "walk_flags")
+    index, count = _host_list(index, count, m)
+    _capi.check_host(_capi.host_lib().rt_path_branch_cpu(_void(surfaces), _void(hits), _void(incoming), _void(paths), m, _void(index), _void(count),
+                                                         int(seed) & 0xFFFFFFFF, int(bool(last)), _void(lobe), _void(transmit), _void(walk_rays), _void(kind),
+                                                         _void(travel), _void(casts), _void(walk_flags)))
+    return paths, lobe, transmit, walk_rays, kind, travel, casts, walk_flags
+
+
+def transmit_numpy(surfaces, paths, kind, travel, escape, index=None, count=None, seed: int = 0, rr_start: int = 3, rr_floor: float = 0.05,
+                   rays=None, alive=None, walk_flags=None):
+    """rt_path_transmit_cpu: what transmit writes, bit for bit, on the CPU.  Returns new arrays (paths, kind, rays (M, 11) uint32, alive,
+    walk_flags); ``rays``, ``alive`` and ``walk_flags`` as given (zeros if None) where a slot is not touched."""
+    surfaces = _host_surfaces(surfaces)
+    m = surfaces.shape[0]
+    paths = _host_paths(paths)
+    if paths.shape[0] != m:
+        raise ValueError(f"paths: expected {m} records")
+    kind = _host(kind, np.uint32, (m,), "kind").copy()
+    travel = _host(travel, np.float32, (m,), "travel")
+    escape = _host(escape, np.uint32, (m, 11), "escape")
+    rays, alive = _start(rays, np.uint32, (m, 11), "rays"), _start(alive, np.uint8, (m,), "alive")
+    walk_flags = _start(walk_flags, np.uint8, (m,), "walk_flags")
+    index, count = _host_list(index, count, m)
+    _capi.check_host(_capi.host_lib().rt_path_transmit_cpu(_void(surfaces), _void(paths), m, _void(index), _void(count), _void(kind), _void(travel),
+                                                           _void(escape), int(seed) & 0xFFFFFFFF, int(rr_start) & 0xFFFFFFFF, float(rr_floor), _void(rays),
+                                                           _void(alive), _void(walk_flags)))
+    return paths, kind, rays, alive, walk_flags
+
+
 # ---- the loop ----
 
 class Workspace:
     """The buffers of trace_paths, made once by workspace() so that a caller's loop allocates nothing: ``entries`` paths of room, about
-    190 B each, and ``pairs`` (path, light) pairs for the opened shade step (126 B each; 0: none)."""
+    190 B each, ``pairs`` (path, light) pairs for the opened shade step (126 B each; 0: none), and ``walk`` paths of room for
+    ``transmission`` (0: none), 159 B each: the lobe and transmit bytes (1 + 1), a second index (4; its count is 4 B once), the walk rays
+    (44), the inside hits (52), kind, travel and casts (4 + 4 + 4), the walk flags (1) and the escape rays (44).  ``kind`` is filled with
+    HIT_NONE and the walk flags and the escape rays with zeros, once, here."""
 
-    def __init__(self, entries: int, pairs: int, device):
-        self.entries, self.pairs = int(entries), int(pairs)
+    def __init__(self, entries: int, pairs: int, device, walk: int = 0):
+        self.entries, self.pairs, self.walk = int(entries), int(pairs), int(walk)
         self.paths, self.radiance = _new((entries, PATH_WORDS), "int32", device), _new((entries, 3), "float32", device)
         self.hits, self.emitted = _new((entries, 13), "int32", device), _new((entries, 3), "float32", device)
         self.rays, self.next_rays = _new((entries, 11), "int32", device), _new((entries, 11), "int32", device)
         self.alive, self.index, self.count = _new((entries,), "uint8", device), _new((entries,), "int32", device), _new((1,), "int32", device)
         self.lights = LightWorkspace(pairs, device) if pairs else None
+        if walk:
+            self.lobe, self.transmit = _new((walk,), "uint8", device), _new((walk,), "uint8", device)
+            self.walk_index, self.walk_count = _new((walk,), "int32", device), _new((1,), "int32", device)
+            self.walk_rays, self.inside_hits = _new((walk, 11), "int32", device), _new((walk, 13), "int32", device)
+            self.kind = _new((walk,), "int32", device).fill_(HIT_NONE)
+            self.travel, self.casts = _new((walk,), "float32", device), _new((walk,), "int32", device)
+            self.walk_flags, self.escape = _new((walk,), "uint8", device).zero_(), _new((walk, 11), "int32", device).zero_()
 
 
-def workspace(n: int, device, spp: int, scene: Scene = None) -> Workspace:
-    """A Workspace for trace_paths on up to ``n`` roots with ``spp`` samples; with ``scene`` also for ``open_casts`` on its lights."""
+def workspace(n: int, device, spp: int, scene: Scene = None, transmission: bool = False) -> Workspace:
+    """A Workspace for trace_paths on up to ``n`` roots with ``spp`` samples; with ``scene`` also for ``open_casts`` on its lights, with
+    ``transmission`` also the walk buffers of trace_paths(transmission=True)."""
     if n < 0 or spp < 0:
         raise ValueError("n and spp must not be negative")
     entries = int(n) * int(spp)
-    return Workspace(entries, entries * scene.n_lights if scene is not None else 0, device)
+    return Workspace(entries, entries * scene.n_lights if scene is not None else 0, device, entries if transmission else 0)
 
 
 def trace_paths(scene: Scene, hits, incoming, spp: int, max_bounces: int, env=None, rr_start: int = 3, rr_floor: float = 0.05, seed: int = 0, ids=None,
-                out=None, open_casts: bool = True, stream=None, workspace=None):
+                out=None, open_casts: bool = True, stream=None, workspace=None, transmission: bool = False, walk_rounds: int = 11):
     """``spp`` paths of up to ``max_bounces`` bounces from every hit, their mean ADDED to ``out`` ((N, 3) float32 CUDA; None: a new,
     zeroed tensor): at each vertex the light of the scene's lights (shade_hits) — with ``env`` (an environment.Environment) the sky for
     the paths that left the scene — times the throughput, then one direction from the vertex's own lobes.  ``hits`` and ``incoming`` are
@@ -201,10 +336,20 @@ def trace_paths(scene: Scene, hits, incoming, spp: int, max_bounces: int, env=No
     Bounce b draws with seed + 0x9e3779b9 * b; roulette starts at bounce ``rr_start`` (NO_ROULETTE: never).  ``open_casts``:
     shade_hits_by_light in the place of shade_hits, so that every cast of the loop is a cast_rays_indexed (the same bits).  The loop
     visits the host nowhere, and with ``out`` and ``workspace`` (workspace(n, device, spp, scene)) it allocates nothing; after one
-    eager call on the stream it may be captured into a graph (select_records and the indexed casts need that first call)."""
-    spp, max_bounces = _samples(spp), int(max_bounces)
+    eager call on the stream it may be captured into a graph (select_records and the indexed casts need that first call).
+    ``transmission``: paths pass through glass.  At a vertex a path takes the material's refraction with probability transparency and
+    the lobes otherwise, and advance(list_b, last) in the sequence above becomes
+      branch(list_b, last) -> select_records(lobe) -> advance(that list, last) ->
+      ``walk_rounds`` times: select_records(walk flags) -> cast_rays_indexed(walk rays -> inside hits) -> refract_step (all slots) ->
+      select_records(transmit) -> transmit(that list)
+    (the walk and the transmit are left out of the last bounce: branch ends the paths that would have walked).  Eleven rounds finish
+    every walk; fewer end the paths still walking with TRAPPED.  With the default not one call of the sequence changes.  The workspace
+    is then workspace(n, device, spp, scene, transmission=True)."""
+    spp, max_bounces, walk_rounds = _samples(spp), int(max_bounces), int(walk_rounds)
     if max_bounces < 0:
         raise ValueError("max_bounces must not be negative")
+    if walk_rounds < 0:
+        raise ValueError("walk_rounds must not be negative")
     records = _hit_records(hits)
     n, dev = records.shape[0], records.device
     _tensor(incoming, "incoming", "int32", (n, 11))
@@ -216,8 +361,9 @@ def trace_paths(scene: Scene, hits, incoming, spp: int, max_bounces: int, env=No
         return out
     pairs = m * scene.n_lights if open_casts else 0
     _below_2_32(pairs, "(path, light) pairs")
-    w = _room(workspace, Workspace, {"entries": m, "pairs": pairs},
-              f"a paths.Workspace with room for {m} paths and {pairs} (path, light) pairs (paths.workspace)", dev, stream)
+    sizes = {"entries": m, "pairs": pairs, "walk": m} if transmission else {"entries": m, "pairs": pairs}
+    w = _room(workspace, Workspace, sizes,
+              f"a paths.Workspace with room for {m} paths and {pairs} (path, light) pairs{' and their walks' if transmission else ''} (paths.workspace)", dev, stream)
     s = stream
     vertices, emitted, radiance, paths, alive, index = w.hits[:m], w.emitted[:m], w.radiance[:m], w.paths[:m], w.alive[:m], w.index[:m]
     rays, next_rays = w.rays[:m], w.next_rays[:m]
@@ -225,6 +371,9 @@ def trace_paths(scene: Scene, hits, incoming, spp: int, max_bounces: int, env=No
     with _on_stream(s):  # the spp copies of the roots
         vertices.view(spp, n, 13).copy_(records.unsqueeze(0).expand(spp, n, 13))
         rays.view(spp, n, 11).copy_(incoming.unsqueeze(0).expand(spp, n, 11))
+    if transmission:
+        lobe, through, walk_index, walk_rays, inside_hits = w.lobe[:m], w.transmit[:m], w.walk_index[:m], w.walk_rays[:m], w.inside_hits[:m]
+        kind, travel, casts, walk_flags, escape = w.kind[:m], w.travel[:m], w.casts[:m], w.walk_flags[:m], w.escape[:m]
     listed = counted = None  # bounce 0: every slot
     for b in range(max_bounces + 1):
         if open_casts:
@@ -233,9 +382,22 @@ def trace_paths(scene: Scene, hits, incoming, spp: int, max_bounces: int, env=No
             shade_hits(scene, vertices, rays, out=emitted, stream=s)
         if env is not None:
             lookup(env, rays, vertices, out=emitted, stream=s)
-        advance(scene, paths, vertices, rays, radiance, emitted, listed, counted, seed, SHADING, rr_start, rr_floor, b == max_bounces, next_rays, alive, stream=s)
-        if b == max_bounces:
+        last = b == max_bounces
+        if not transmission:
+            advance(scene, paths, vertices, rays, radiance, emitted, listed, counted, seed, SHADING, rr_start, rr_floor, last, next_rays, alive, stream=s)
+        else:
+            branch(scene, paths, vertices, rays, listed, counted, seed, last, lobe, through, walk_rays, kind, travel, casts, walk_flags, stream=s)
+            select_records(lobe, walk_index, w.walk_count, stream=s)
+            advance(scene, paths, vertices, rays, radiance, emitted, walk_index, w.walk_count, seed, SHADING, rr_start, rr_floor, last, next_rays, alive, stream=s)
+        if last:
             break
+        if transmission:
+            for _ in range(walk_rounds):
+                select_records(walk_flags, walk_index, w.walk_count, stream=s)
+                cast_rays_indexed(scene, walk_rays, walk_index, w.walk_count, inside_hits, stream=s)
+                refract_step(scene, vertices, inside_hits, walk_rays, kind, travel, casts, walk_flags, MAX_DISTANCE, escape, stream=s)
+            select_records(through, walk_index, w.walk_count, stream=s)
+            transmit(scene, paths, vertices, kind, travel, escape, walk_flags, walk_index, w.walk_count, seed, rr_start, rr_floor, next_rays, alive, stream=s)
         listed, counted = select_records(alive, index, w.count, stream=s)
         cast_rays_indexed(scene, next_rays, listed, counted, vertices, stream=s)
         rays, next_rays = next_rays, rays

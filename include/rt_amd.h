@@ -780,7 +780,7 @@ int rt_mis_weigh(size_t count, const float *d_pdf_own, uint32_t n_own, const flo
  * stream-ordered and asynchronous on hip_stream (NULL = default stream), is one kernel with one path or root per lane and 256 lanes per
  * workgroup, allocates nothing, uses no workspace, no atomics, and may be captured into a HIP graph at once.  All arithmetic is
  * csrc/rt_path.h's, single f32 and u32 operations in the order given here, none fused, shared by both libraries.
- * Not covered: refraction lobes; next-event estimation of the sky inside the step (rt_path.pdf is kept for it); _host and rt_multi_*
+ * Not covered: refraction lobes inside the step (the "transmission queries" block takes them as a branch beside it); next-event estimation of the sky inside the step (rt_path.pdf is kept for it); _host and rt_multi_*
  * forms (rt_path_*_cpu of include/rt_path_host.h are the CPU forms); paths inside rt_render_*. */
 #define RT_PATH_ALIVE 1u     /* the path goes on */
 #define RT_PATH_SPECULAR 2u  /* the direction last drawn came from the specular lobe */
@@ -1014,6 +1014,79 @@ int rt_refract_enter(const rt_scene *scene, const rt_hit *d_hits, const rt_ray *
  * max_distance: the reference passes 100.0. */
 int rt_refract_step(const rt_scene *scene, const rt_hit *d_hits, size_t n, float max_distance, const rt_hit *d_inside_hits, rt_ray *d_rays,
                     uint32_t *d_kind, float *d_travel, uint32_t *d_casts, unsigned char *d_flags, rt_ray *d_escape, void *hip_stream);
+
+/* ---- transmission queries: paths that pass through glass ------------------------------------------------------------------------------
+
+ * The path queries treat every surface as its two Phong lobes; ray_trace (main.rs:502-514) and distributed_ray_trace (main.rs:595-611)
+ * send light through a material with transparency > 0.  The refraction queries above open that walk into its casts.  What no caller can
+ * supply from the existing calls is the stochastic choice per vertex between "through the glass" and "off the lobes", and the step that
+ * folds a finished walk into the 32-byte rt_path record.  These two calls are that, and bounce b of the path loop becomes
+ *     rt_shade_hits -> rt_environment_lookup (with a sky) -> rt_path_branch(list_b, last) ->
+ *     rt_select_records(d_lobe) -> rt_path_advance(that list) ->
+ *     walk_rounds times: rt_select_records(d_walk_flags) -> rt_cast_rays_indexed(d_walk_rays -> d_inside_hits) -> rt_refract_step (all m) ->
+ *     rt_select_records(d_transmit) -> rt_path_transmit(that list) ->
+ *     rt_select_records(d_alive -> list_b+1) -> rt_cast_rays_indexed(d_next_rays, list_b+1 -> d_hits)
+ * (INTEGRATION.md writes it out; DESIGN.md §3.36 has the estimator and what the calls cost.)
+ *
+ * The estimator.  The Whitted weights at a vertex are (1 - t) for shade + lobes and t for the refraction, t = approx(hit.at).transparency
+ * (main.rs:480-502).  A path takes the refraction with probability t and the lobes with probability 1 - t: either way the weight over the
+ * probability is 1, and beta is not touched by the choice.  A path that takes the lobes goes through rt_path_advance unchanged, deposit
+ * included.  A path that takes the refraction deposits nothing at this vertex (the (1 - t) share of the direct light is the lobe paths'
+ * deposit), walks get_refract, has beta multiplied by opaque_decay.powf(travel_distance) (main.rs:508) where the walk Escaped, and goes
+ * on along the escape ray; a transmission counts as one bounce however many casts the walk took.
+ *
+ * Every pointer is a device pointer; every call is stream-ordered and asynchronous on hip_stream (NULL = default stream), is one kernel
+ * with one listed slot per lane and 256 lanes per workgroup, allocates nothing, uses no workspace, no atomics, and may be captured into a
+ * HIP graph at once.  The list is rt_path_advance's: slot j = d_index[e] for e < min(*d_count, m); an index >= m names nothing; d_index
+ * NULL: every j < m, and d_count is not read.  Records are read by the hit queries' rules.  The walk's state words are the caller's and
+ * are validated, never trusted, by the refraction block's rule: a d_kind word is compared, and nothing is indexed with a state word.
+ * All arithmetic is csrc/rt_transmit.h's, single f32 and u32 operations in the order given here, none fused, shared by both libraries.
+ * Checked before any device work, in rt_path_advance's order and with its messages: m >= 2^32 is RT_ERR_UNSUPPORTED; a null scene; m == 0
+ * is RT_OK and launches nothing; a null pointer (d_index may be NULL; d_count only with d_index); (rt_path_transmit) an rr_floor outside
+ * (0, 1]; then a d_paths that is not 16-byte aligned, RT_ERR_INVALID_ARGUMENT.
+ * Not covered: rough transmission — the event is a delta: no roughness, and no scatter_hit perturbation of the incoming direction;
+ * _host and rt_multi_* forms (rt_path_branch_cpu and rt_path_transmit_cpu of include/rt_transmit_host.h are the CPU forms); paths inside
+ * rt_render_*. */
+#define RT_PATH_TRANSMITTED 32u /* with RT_PATH_ALIVE: the path's last event was a transmission (never with RT_PATH_SPECULAR) */
+#define RT_PATH_TRAPPED 64u     /* ended: the walk through the glass did not escape (Infinite, Trapped, no hit, or left RT_REFR_WALKING) */
+
+/* The choice, per listed slot whose flags have RT_PATH_ALIVE.  With b the bounces taken, s the sample index (bounce >> 24) and seed_h the
+ * hemisphere seed of seed + 0x9e3779b9u * b — exactly rt_path_advance's —
+ *     u_4 = film_u(id, film_mix(seed_h ^ 0x85ebca6bu), s, 0)
+ * a fifth stream, beside u_0, u_1, the lobe's u_2 (0x27d4eb2fu) and the roulette's u_3 (0x165667b1u).  The path transmits iff d_hits[j] is
+ * a hit and u_4 < transparency of approx(hit.at): film_u lies in [0, 1), so t = 0 never transmits, t >= 1 always does and a NaN t never
+ * does; a "no hit" record takes the lobes, so that rt_path_advance ends it with RT_PATH_ESCAPED and deposits its sky.
+ *   a path that transmits, last == 0   d_lobe[j] = 0, d_transmit[j] = 1, and d_walk_rays[j], d_kind[j], d_travel[j], d_casts[j] and
+ *                                      d_walk_flags[j] are what rt_refract_enter writes for d_hits[j] and d_incoming[j], bit for bit
+ *                                      (RT_REFR_WALKING with ray_inside and flag 1, or 2 Trapped at entry with an all-zero ray and flag 0)
+ *   a path that transmits, last != 0   the path ends here: flags 0 (they alone change in the record), d_lobe[j] = d_transmit[j] = 0,
+ *                                      nothing walks, and d_hits[j] becomes the "no hit" record, as rt_path_advance leaves an ended path
+ *   a path that takes the lobes        d_lobe[j] = 1, d_transmit[j] = 0
+ *   a listed slot that is not alive    d_lobe[j] = d_transmit[j] = 0
+ * Every listed slot that does not walk gets the state of a finished walk: d_kind[j] = RT_HIT_NONE, d_walk_flags[j] = 0, an all-zero
+ * d_walk_rays[j], d_travel[j] = +0 and d_casts[j] = 0, so that a later rt_refract_step over all m slots skips it.  Slots that are not
+ * listed are not touched.  d_paths is read (and for a path `last` ends, written) as the 16-byte second half of the record. */
+int rt_path_branch(const rt_scene *scene, rt_path *d_paths, size_t m, const uint32_t *d_index, const uint32_t *d_count, rt_hit *d_hits,
+                   const rt_ray *d_incoming, uint32_t seed, int last, unsigned char *d_lobe, unsigned char *d_transmit, rt_ray *d_walk_rays,
+                   uint32_t *d_kind, float *d_travel, uint32_t *d_casts, unsigned char *d_walk_flags, void *hip_stream);
+/* The fold of a finished walk, per listed slot whose flags have RT_PATH_ALIVE, with d_kind[j], d_travel[j] and d_escape[j] as
+ * rt_refract_step left them and d_hits[j] still the vertex the path entered the glass at:
+ *   d_kind[j] is 0 (Escaped) and d_hits[j] is a hit
+ *                w = powf(opaque_decay of approx(hit.at), d_travel[j]) — the function of main.rs:508 in the Whitted kernels — and
+ *                beta' = beta * w per channel; then rt_path_advance's own tail: no channel of beta' is > 0 (NaN is not): the path ends
+ *                with RT_PATH_DARK; where b + 1 >= rr_start its roulette with the same u_3 (this path did not use u_3 at this bounce):
+ *                RT_PATH_ROULETTE, or beta' = beta' / q
+ *   anything else (1 Infinite, 2 Trapped, RT_HIT_NONE, a walk still RT_REFR_WALKING because the caller ran fewer rounds, any other word)
+ *                the path ends with RT_PATH_TRAPPED
+ *   write        a survivor: beta = beta', pdf = +0 (a delta event that no other strategy could have drawn, as before the first
+ *                bounce), bounce + 1, flags RT_PATH_ALIVE | RT_PATH_TRANSMITTED, d_alive[j] = 1 and d_next_rays[j] = d_escape[j].  A path
+ *                that ended: what rt_path_advance writes — its flags alone change in the record, d_alive[j] = 0, d_next_rays[j] all-zero
+ *                words and d_hits[j] the "no hit" record
+ * and for every listed slot, alive or not, d_kind[j] = RT_HIT_NONE and d_walk_flags[j] = 0: stale walk state never walks in a later
+ * bounce.  Slots that are not listed are not touched; of a listed slot that is not alive nothing else is. */
+int rt_path_transmit(const rt_scene *scene, rt_path *d_paths, size_t m, const uint32_t *d_index, const uint32_t *d_count, rt_hit *d_hits,
+                     uint32_t *d_kind, const float *d_travel, const rt_ray *d_escape, uint32_t seed, uint32_t rr_start, float rr_floor,
+                     rt_ray *d_next_rays, unsigned char *d_alive, unsigned char *d_walk_flags, void *hip_stream);
 
 /* ---- distributed (stochastic / depth-of-field) pass ----------------------------
 

@@ -35,4 +35,7 @@ int rt_path_resolve_cpu(const float *radiance, size_t n, uint32_t spp, const uin
 #ifdef __cplusplus
 }
 #endif
+
+#include "rt_transmit_host.h" /* the transmission queries' CPU forms: the same paths, through glass */
+
 #endif /* RT_PATH_HOST_H */
