@@ -33,6 +33,7 @@
 #include "../rt_lobe.h"
 #include "../rt_path.h"
 #include "../rt_transmit.h"
+#include "../rt_connect.h"
 #include "../rt_texture.h"
 
 using rt::V3;
@@ -989,6 +990,94 @@ int rt_path_transmit_cpu(const rt_surface *surfaces, rt_path *paths, size_t m, c
         const bool lives = rt::path_transmit_record(p, walk, valid, valid ? surfaces[j].opaque_decay : 0.0f, travel[j], step);
         alive[j] = lives ? 1 : 0;
         next_rays[j] = lives ? escape[j] : rt::no_ray_record();
+    }
+    return RT_OK;
+}
+
+/* ---- connection queries: the connection, the settlement and the escape weight on the CPU (include/rt_amd.h "connection queries"; the arithmetic is rt_connect.h's, shared with the device) ---- */
+
+static int connect_count(const char *who, size_t m) {
+    if ((uint64_t)m >= (1ull << 32)) return fail(RT_ERR_UNSUPPORTED, std::string(who) + "2^32 records or more (checked first; query them in several calls)");
+    return RT_OK;
+}
+
+int rt_path_connect_cpu(const rt_surface *surfaces, const float *normals, const float *view, const rt_environment *env, const void *table,
+                        const rt_path *paths, size_t m, const uint32_t *index, const uint32_t *count, uint32_t seed, uint32_t heuristic, int last,
+                        float *dirs, unsigned char *asks, float *pending) {
+    const char *const who = "rt_path_connect_cpu: ";
+    if (const int rc = connect_count(who, m)) return rc;
+    if (const int rc = environment_ok(who, env)) return rc;
+    if (m == 0) return RT_OK;
+    if (!surfaces || !view || !table || !paths || (index && !count) || !dirs || !asks || !pending)
+        return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + "null surface, view, table, path, count (with an index), direction, flag or pending pointer");
+    if (const char *bad = rt::connect_limits(RT_HEMISPHERE_SHADING, heuristic)) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + bad);
+    const rt::PathConnect step = {seed, heuristic, last != 0};
+    const rt::EnvTable t = rt::env_table_view(*env, table);
+    const uint32_t listed = rt::path_listed(index, count, (uint32_t)m);
+    for (uint32_t e = 0; e < listed; ++e) {
+        const uint32_t j = index ? index[e] : e;
+        if (j >= m) continue;
+        const rt_path &p = paths[j];
+        if ((p.flags & RT_PATH_ALIVE) == 0u) continue;
+        const rt_surface &s = surfaces[j];
+        rt::Mat mat;
+        mat.normal = rt::v3p(s.normal);
+        mat.diffuse = rt::v3p(s.diffuse_color);
+        mat.specular = rt::v3p(s.specular_color);
+        mat.shiness = s.shiness;
+        mat.smoothness = s.smoothness;
+        mat.transparency = s.transparency;
+        mat.refraction_index = s.refraction_index;
+        mat.opaque_decay = s.opaque_decay;
+        const V3 shading_n = rt::v3p(s.shading_normal);
+        const rt::Connection c = rt::path_connect_record(p, s.valid != 0u, mat, shading_n, normals ? rt::v3p(normals + 3u * j) : shading_n, rt::v3p(view + 3u * j),
+                                                         *env, t, step);
+        dirs[3u * j] = c.dir.x;
+        dirs[3u * j + 1u] = c.dir.y;
+        dirs[3u * j + 2u] = c.dir.z;
+        asks[j] = c.ask ? 1 : 0;
+        if (c.ask) {
+            pending[3u * j] = c.pending.x;
+            pending[3u * j + 1u] = c.pending.y;
+            pending[3u * j + 2u] = c.pending.z;
+        }
+    }
+    return RT_OK;
+}
+
+int rt_path_settle_cpu(const rt_path *paths, size_t m, const uint32_t *index, const uint32_t *count, unsigned char *asks, const rt_hit *shadow_hits,
+                       const float *pending, float *radiance) {
+    const char *const who = "rt_path_settle_cpu: ";
+    if (const int rc = connect_count(who, m)) return rc;
+    if (m == 0) return RT_OK;
+    if (!paths || (index && !count) || !asks || !pending || !radiance)
+        return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + "null path, count (with an index), flag, pending or radiance pointer");
+    const uint32_t listed = rt::path_listed(index, count, (uint32_t)m);
+    for (uint32_t e = 0; e < listed; ++e) {
+        const uint32_t j = index ? index[e] : e;
+        if (j < m) rt::path_settle_record(j, asks, reinterpret_cast<const uint32_t *>(shadow_hits), pending, radiance);
+    }
+    return RT_OK;
+}
+
+int rt_path_weigh_escape_cpu(const rt_environment *env, const void *table, const rt_path *paths, size_t m, const uint32_t *index, const uint32_t *count,
+                             const rt_hit *hits, const rt_ray *incoming, uint32_t heuristic, float *emitted) {
+    const char *const who = "rt_path_weigh_escape_cpu: ";
+    if (const int rc = connect_count(who, m)) return rc;
+    if (const int rc = environment_ok(who, env)) return rc;
+    if (m == 0) return RT_OK;
+    if (!table || !paths || (index && !count) || !hits || !incoming || !emitted)
+        return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + "null table, path, count (with an index), hit, incoming-ray or emitted pointer");
+    if (const char *bad = rt::mis_limits(heuristic)) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + bad);
+    const rt::EnvTable t = rt::env_table_view(*env, table);
+    const uint32_t listed = rt::path_listed(index, count, (uint32_t)m);
+    for (uint32_t e = 0; e < listed; ++e) {
+        const uint32_t j = index ? index[e] : e;
+        if (j >= m) continue;
+        const rt_path &p = paths[j];
+        if (!rt::path_escape_weighed(p.flags, hits[j].kind, p.pdf, t)) continue;
+        const float w = rt::path_escape_weight(*env, t, heuristic, p.pdf, rt::v3p(incoming[j].direction));
+        for (uint32_t c = 0; c < 3u; ++c) emitted[3u * j + c] = emitted[3u * j + c] * w;
     }
     return RT_OK;
 }

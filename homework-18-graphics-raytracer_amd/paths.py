@@ -12,7 +12,14 @@ roulette on the device; ``begin`` makes the records and ``resolve`` adds the mea
     branch / transmit                               rt_path_branch / rt_path_transmit ("transmission queries"): the choice between a
                                                     vertex's lobes and its glass, and a finished walk folded into the record
     branch_numpy / transmit_numpy                   their CPU forms (rt_path_branch_cpu and rt_path_transmit_cpu): the device's bits
-    trace_paths                                     begin -> per bounce: shade_hits -> environment.lookup -> advance -> select_records
+    connect / settle / weigh_escape                 rt_path_connect / rt_path_settle / rt_path_weigh_escape ("connection queries"):
+                                                    next-event estimation of the sky — a direction from the environment's table at
+                                                    every vertex, weighed against the lobes, its shadow cast settled into the
+                                                    radiance, and the sky a lobe ray escaped to weighed the other way round
+    connect_numpy / settle_numpy / weigh_escape_numpy
+                                                    their CPU forms (rt_path_connect_cpu, rt_path_settle_cpu and
+                                                    rt_path_weigh_escape_cpu): the device's bits
+    trace_paths                                   begin -> per bounce: shade_hits -> environment.lookup -> advance -> select_records
                                                     -> cast_rays_indexed -> resolve — written from the public calls alone: to be
                                                     copied and changed
 
@@ -26,12 +33,13 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from ._args import _below_2_32, _host, _host_records, _new, _on_stream, _out_tensor, _p, _room, _samples, _stream_ptr, _tensor, _void, _zeroed_out
+from ._args import (_aligned_bytes, _below_2_32, _host, _host_records, _new, _on_stream, _out_tensor, _p, _room, _samples, _stream_ptr, _tensor, _void,
+                    _zeroed_out)
 from ._opened import LightWorkspace, refract_step, shade_hits_by_light
 from ._queries import HIT_DTYPE, HIT_NONE, RAY_DTYPE, _hit_records, cast_rays_indexed, select_records, shade_hits
 from ._world import Scene
-from .environment import lookup
-from .lobes import _host_surfaces
+from .environment import TABLE_HEADER_BYTES, Environment, _environment, _host_environment, lookup, table_bytes
+from .lobes import BALANCE, POWER, _host_surfaces  # RT_MIS_BALANCE / RT_MIS_POWER: connect's and weigh_escape's heuristic
 
 SHADING, GEOMETRIC = 0, 1  # RT_HEMISPHERE_SHADING / RT_HEMISPHERE_GEOMETRIC
 ALIVE, SPECULAR, ESCAPED, ROULETTE, DARK, TRANSMITTED, TRAPPED = 1, 2, 4, 8, 16, 32, 64  # RT_PATH_*
@@ -162,6 +170,74 @@ def transmit(scene: Scene, paths, hits, kind, travel, escape, walk_flags, index=
     return out_rays, out_alive
 
 
+# ---- connections (include/rt_amd.h "connection queries") ----
+
+def _table(env, table, stream):
+    if table is None:
+        table = env.table(stream)
+    return _tensor(table, "table", "uint8", (table_bytes(env.width, env.height),))
+
+
+def connect(scene: Scene, env: Environment, paths, hits, incoming, index=None, count=None, seed: int = 0, normal_kind: int = SHADING,
+            heuristic: int = BALANCE, last: bool = False, table=None, out_rays=None, out_asks=None, out_pending=None, stream=None):
+    """rt_path_connect: per listed live path one direction drawn from the environment's table (``table``; None: env.table(stream)) at the
+    path's vertex — environment.rays' sample for spp 1, UNIFORM, the path's id and sample and seed + 0x9e3779b9 * bounce, a stream apart
+    from the lobe's — weighed against the vertex's own lobes (lobes.mis_weigh's weight of environment_pdf against lobes.pdf, one sample
+    each) and multiplied by the throughput and the Phong terms.  To be called before advance, on the hits and rays advance will get.
+    Returns (rays, asks, pending): ``out_asks`` (M,) uint8, 1 where environment.rays asks and the weight is finite; ``out_rays`` (M, 11)
+    int32, the shadow ray where it asks and zero words where it does not; ``out_pending`` (M, 3) float32, what the path's radiance gains
+    if that ray finds nothing — written where it asks.  ``last``, a "no hit" vertex and an environment without light ask nothing.  The
+    record is read only.  Slots that are not listed or not alive are not touched: ``out_asks`` is zeroed here if not given."""
+    env = _environment(env)
+    records = _hit_records(hits)
+    m, dev = records.shape[0], records.device
+    index_p, count_p = _listed(m, dev, paths, index, count)
+    _tensor(incoming, "incoming", "int32", (m, 11))
+    table = _table(env, table, stream)
+    out_rays = _out_tensor(out_rays, (m, 11), "int32", dev, "out_rays")
+    if out_asks is None:
+        with _on_stream(stream):
+            out_asks = _new((m,), "uint8", dev).zero_()
+    _tensor(out_asks, "out_asks", "uint8", (m,))
+    out_pending = _out_tensor(out_pending, (m, 3), "float32", dev, "out_pending")
+    _capi.check(_capi.amd_lib().rt_path_connect(scene._h, C.byref(env.desc), _p(table), _p(paths), m, index_p, count_p, _p(records), _p(incoming),
+                                                int(seed) & 0xFFFFFFFF, int(normal_kind), int(heuristic), int(bool(last)), _p(out_rays), _p(out_asks),
+                                                _p(out_pending), _stream_ptr(stream)))
+    return out_rays, out_asks, out_pending
+
+
+def settle(paths, asks, pending, radiance, shadow_hits=None, index=None, count=None, stream=None):
+    """rt_path_settle: per listed slot, radiance += pending where ``asks`` is set and the slot's record of ``shadow_hits`` ((M, 13) int32:
+    what the cast of connect's rays found; None: nothing occludes) is "no hit" at all; the ask is cleared either way.  To be called after
+    advance, so that a vertex's deposit is added before its connection.  ``paths`` is not read: a path advance ended still settles.
+    Returns ``radiance``."""
+    m, dev = _tensor(asks, "asks", "uint8", (None,)).shape[0], asks.device
+    index_p, count_p = _listed(m, dev, paths, index, count)
+    _tensor(shadow_hits, "shadow_hits", "int32", (m, 13), optional=True)
+    _tensor(pending, "pending", "float32", (m, 3))
+    _tensor(radiance, "radiance", "float32", (m, 3))
+    _capi.check(_capi.amd_lib().rt_path_settle(_p(paths), m, index_p, count_p, _p(asks), _p(shadow_hits), _p(pending), _p(radiance), _stream_ptr(stream)))
+    return radiance
+
+
+def weigh_escape(env: Environment, paths, hits, incoming, emitted, index=None, count=None, heuristic: int = BALANCE, table=None, stream=None):
+    """rt_path_weigh_escape: per listed live path whose vertex is "no hit" (environment.lookup's rule) and whose record holds the density
+    of the direction it was drawn with — pdf finite and > 0 — ``emitted`` ((M, 3) float32: the sky lookup wrote) is multiplied by
+    lobes.mis_weigh's weight of that density against environment_pdf of the incoming direction.  A pdf of +0 (a camera ray, a ray that
+    left glass), a hit and an environment without light leave it alone.  To be called after lookup and before advance.  Returns
+    ``emitted``."""
+    env = _environment(env)
+    records = _hit_records(hits)
+    m, dev = records.shape[0], records.device
+    index_p, count_p = _listed(m, dev, paths, index, count)
+    _tensor(incoming, "incoming", "int32", (m, 11))
+    _tensor(emitted, "emitted", "float32", (m, 3))
+    table = _table(env, table, stream)
+    _capi.check(_capi.amd_lib().rt_path_weigh_escape(C.byref(env.desc), _p(table), _p(paths), m, index_p, count_p, _p(records), _p(incoming), int(heuristic),
+                                                     _p(emitted), _stream_ptr(stream)))
+    return emitted
+
+
 # ---- the CPU forms ----
 
 def _host_paths(paths):
@@ -287,6 +363,75 @@ def transmit_numpy(surfaces, paths, kind, travel, escape, index=None, count=None
     return paths, kind, rays, alive, walk_flags
 
 
+def _host_table(texels, table):
+    """the table in 8-byte-aligned host memory, held by the caller for as long as the call reads it"""
+    size = TABLE_HEADER_BYTES + 8 * texels.shape[0] + 4 * texels.shape[0] * texels.shape[1]
+    held = _aligned_bytes(size)
+    held[:] = _host(table, np.uint8, (size,), "table")
+    return held
+
+
+def connect_numpy(surfaces, view, texels, table, paths, index=None, count=None, seed: int = 0, normals=None, heuristic: int = BALANCE,
+                  last: bool = False, rotation: float = 0.0, scale: float = 1.0, dirs=None, asks=None, pending=None):
+    """rt_path_connect_cpu: what connect writes for paths whose vertices' materials are ``surfaces`` (materials.material_hits; valid 0:
+    "no hit") seen from ``view`` ((M, 3) float32) under the (H, W, 3) float32 image ``texels`` with ``table`` (environment.table_numpy),
+    bit for bit, on the CPU.  ``normals`` (M, 3) float32 or None: the N of the lobes' density and of "leaves the surface" — None is the
+    record's shading normal (SHADING); pass hit.normal for GEOMETRIC.  Returns new arrays (dirs (M, 3) float32, asks (M,) uint8, pending
+    (M, 3) float32): the direction drawn in place of the ray — also where it does not ask, zeros where nothing was drawn —; each as given
+    (zeros if None) where a slot is not touched, ``pending`` also where a slot does not ask."""
+    surfaces = _host_surfaces(surfaces)
+    m = surfaces.shape[0]
+    view = _host(view, np.float32, (m, 3), "view")
+    normals = _host(normals, np.float32, (m, 3), "normals", optional=True)
+    texels, desc = _host_environment(texels, rotation, scale, 0)
+    held = _host_table(texels, table)
+    paths = _host_paths(paths)
+    if paths.shape[0] != m:
+        raise ValueError(f"paths: expected {m} records")
+    dirs, asks, pending = _start(dirs, np.float32, (m, 3), "dirs"), _start(asks, np.uint8, (m,), "asks"), _start(pending, np.float32, (m, 3), "pending")
+    index, count = _host_list(index, count, m)
+    _capi.check_host(_capi.host_lib().rt_path_connect_cpu(_void(surfaces), _void(normals), _void(view), C.byref(desc), _void(held), _void(paths), m,
+                                                          _void(index), _void(count), int(seed) & 0xFFFFFFFF, int(heuristic), int(bool(last)), _void(dirs),
+                                                          _void(asks), _void(pending)))
+    return dirs, asks, pending
+
+
+def settle_numpy(asks, pending, radiance, shadow_hits=None, index=None, count=None):
+    """rt_path_settle_cpu: settle on the CPU, bit for bit.  ``shadow_hits``: HIT_DTYPE or (M, 13) words, or None: nothing occludes.
+    Returns new arrays (asks, radiance)."""
+    asks = np.ascontiguousarray(asks, dtype=np.uint8).reshape(-1).copy()
+    m = asks.shape[0]
+    pending = _host(pending, np.float32, (m, 3), "pending")
+    radiance = _host(radiance, np.float32, (m, 3), "radiance").copy()
+    if shadow_hits is not None:
+        shadow_hits = _host_records(shadow_hits, HIT_DTYPE, 13, "shadow_hits")
+        if shadow_hits.shape[0] != m:
+            raise ValueError(f"shadow_hits: expected {m} records")
+    paths = np.zeros(max(m, 1), dtype=PATH_DTYPE)  # not read
+    index, count = _host_list(index, count, m)
+    _capi.check_host(_capi.host_lib().rt_path_settle_cpu(_void(paths), m, _void(index), _void(count), _void(asks), _void(shadow_hits), _void(pending),
+                                                         _void(radiance)))
+    return asks, radiance
+
+
+def weigh_escape_numpy(texels, table, paths, hits, incoming, emitted, index=None, count=None, heuristic: int = BALANCE, rotation: float = 0.0):
+    """rt_path_weigh_escape_cpu: weigh_escape on the CPU, bit for bit.  ``hits``: HIT_DTYPE or (M, 13) words (the kind is read);
+    ``incoming``: RAY_DTYPE or (M, 11) words (the direction is read).  Returns a new ``emitted``."""
+    texels, desc = _host_environment(texels, rotation, 1.0, 0)
+    held = _host_table(texels, table)
+    paths = _host_paths(paths)
+    m = paths.shape[0]
+    hits = _host_records(hits, HIT_DTYPE, 13, "hits")
+    incoming = _host_records(incoming, RAY_DTYPE, 11, "incoming")
+    if not hits.shape[0] == incoming.shape[0] == m:
+        raise ValueError(f"hits, incoming: expected {m} records each")
+    emitted = _host(emitted, np.float32, (m, 3), "emitted").copy()
+    index, count = _host_list(index, count, m)
+    _capi.check_host(_capi.host_lib().rt_path_weigh_escape_cpu(C.byref(desc), _void(held), _void(paths), m, _void(index), _void(count), _void(hits),
+                                                               _void(incoming), int(heuristic), _void(emitted)))
+    return emitted
+
+
 # ---- the loop ----
 
 class Workspace:
@@ -294,10 +439,16 @@ class Workspace:
     190 B each, ``pairs`` (path, light) pairs for the opened shade step (126 B each; 0: none), and ``walk`` paths of room for
     ``transmission`` (0: none), 159 B each: the lobe and transmit bytes (1 + 1), a second index (4; its count is 4 B once), the walk rays
     (44), the inside hits (52), kind, travel and casts (4 + 4 + 4), the walk flags (1) and the escape rays (44).  ``kind`` is filled with
-    HIT_NONE and the walk flags and the escape rays with zeros, once, here."""
+    HIT_NONE and the walk flags and the escape rays with zeros, once, here.  ``connections`` paths of room for ``nee`` (0: none), 113 B
+    each: the shadow rays (44), the shadow hits (52), the asks (1), the pending radiance (12) and a second index (4; its count is 4 B
+    once).  The asks are zeroed once, here: settle leaves them so."""
 
-    def __init__(self, entries: int, pairs: int, device, walk: int = 0):
-        self.entries, self.pairs, self.walk = int(entries), int(pairs), int(walk)
+    def __init__(self, entries: int, pairs: int, device, walk: int = 0, connections: int = 0):
+        self.entries, self.pairs, self.walk, self.connections = int(entries), int(pairs), int(walk), int(connections)
+        if connections:
+            self.shadow_rays, self.shadow_hits = _new((connections, 11), "int32", device), _new((connections, 13), "int32", device)
+            self.asks, self.pending = _new((connections,), "uint8", device).zero_(), _new((connections, 3), "float32", device)
+            self.ask_index, self.ask_count = _new((connections,), "int32", device), _new((1,), "int32", device)
         self.paths, self.radiance = _new((entries, PATH_WORDS), "int32", device), _new((entries, 3), "float32", device)
         self.hits, self.emitted = _new((entries, 13), "int32", device), _new((entries, 3), "float32", device)
         self.rays, self.next_rays = _new((entries, 11), "int32", device), _new((entries, 11), "int32", device)
@@ -312,17 +463,19 @@ class Workspace:
             self.walk_flags, self.escape = _new((walk,), "uint8", device).zero_(), _new((walk, 11), "int32", device).zero_()
 
 
-def workspace(n: int, device, spp: int, scene: Scene = None, transmission: bool = False) -> Workspace:
+def workspace(n: int, device, spp: int, scene: Scene = None, transmission: bool = False, nee: bool = False) -> Workspace:
     """A Workspace for trace_paths on up to ``n`` roots with ``spp`` samples; with ``scene`` also for ``open_casts`` on its lights, with
-    ``transmission`` also the walk buffers of trace_paths(transmission=True)."""
+    ``transmission`` also the walk buffers of trace_paths(transmission=True), with ``nee`` also the connection buffers of
+    trace_paths(nee=True): 113 B per path more — shadow rays 44, shadow hits 52, asks 1, pending 12, a second index 4 — and one count."""
     if n < 0 or spp < 0:
         raise ValueError("n and spp must not be negative")
     entries = int(n) * int(spp)
-    return Workspace(entries, entries * scene.n_lights if scene is not None else 0, device, entries if transmission else 0)
+    return Workspace(entries, entries * scene.n_lights if scene is not None else 0, device, entries if transmission else 0, entries if nee else 0)
 
 
 def trace_paths(scene: Scene, hits, incoming, spp: int, max_bounces: int, env=None, rr_start: int = 3, rr_floor: float = 0.05, seed: int = 0, ids=None,
-                out=None, open_casts: bool = True, stream=None, workspace=None, transmission: bool = False, walk_rounds: int = 11):
+                out=None, open_casts: bool = True, stream=None, workspace=None, transmission: bool = False, walk_rounds: int = 11, nee: bool = False,
+                heuristic: int = BALANCE):
     """``spp`` paths of up to ``max_bounces`` bounces from every hit, their mean ADDED to ``out`` ((N, 3) float32 CUDA; None: a new,
     zeroed tensor): at each vertex the light of the scene's lights (shade_hits) — with ``env`` (an environment.Environment) the sky for
     the paths that left the scene — times the throughput, then one direction from the vertex's own lobes.  ``hits`` and ``incoming`` are
@@ -344,12 +497,28 @@ def trace_paths(scene: Scene, hits, incoming, spp: int, max_bounces: int, env=No
       select_records(transmit) -> transmit(that list)
     (the walk and the transmit are left out of the last bounce: branch ends the paths that would have walked).  Eleven rounds finish
     every walk; fewer end the paths still walking with TRAPPED.  With the default not one call of the sequence changes.  The workspace
-    is then workspace(n, device, spp, scene, transmission=True)."""
+    is then workspace(n, device, spp, scene, transmission=True).
+    ``nee`` (``env`` is then required): next-event estimation of the sky.  At every vertex but the last bounce's one direction is drawn
+    from the environment's table and weighed against the vertex's lobes by ``heuristic`` (BALANCE or POWER), and the sky a lobe-sampled
+    ray escapes to is weighed the other way round with the density kept in the record; per bounce the sequence becomes
+      shade_hits -> environment.lookup -> weigh_escape(list_b) -> connect(list_b) -> advance(list_b, last) ->
+      select_records(asks) -> cast_rays_indexed(shadow rays -> shadow hits) -> settle(that list) ->
+      select_records(alive) -> cast_rays_indexed(next rays, list_b+1)
+    connect before advance, which moves the throughput and rewrites an ended path's hit; settle after it, so that a vertex's deposit is
+    added before its connection.  On the last bounce connect and settle are left out: both estimators integrate the same paths.  With
+    ``transmission`` connect takes the lobe list, as advance does — a path that goes through the glass deposits nothing at the vertex and
+    connects nothing there — and settle follows transmit.  A sky seen through glass arrives with pdf +0 in the record and keeps its full
+    weight, and a connection through glass is occluded by it, so nothing is counted twice.  The connection carries its own texel's
+    radiance and the escape the lookup's: with environment.NEAREST the two estimate one integrand.  The workspace is then
+    workspace(n, device, spp, scene, nee=True); the table is env.table(stream), built (and allocated) by the first call that asks for it.
+    With ``nee`` False not one call of the sequence changes."""
     spp, max_bounces, walk_rounds = _samples(spp), int(max_bounces), int(walk_rounds)
     if max_bounces < 0:
         raise ValueError("max_bounces must not be negative")
     if walk_rounds < 0:
         raise ValueError("walk_rounds must not be negative")
+    if nee and env is None:
+        raise ValueError("nee needs env: an environment.Environment")
     records = _hit_records(hits)
     n, dev = records.shape[0], records.device
     _tensor(incoming, "incoming", "int32", (n, 11))
@@ -362,8 +531,11 @@ def trace_paths(scene: Scene, hits, incoming, spp: int, max_bounces: int, env=No
     pairs = m * scene.n_lights if open_casts else 0
     _below_2_32(pairs, "(path, light) pairs")
     sizes = {"entries": m, "pairs": pairs, "walk": m} if transmission else {"entries": m, "pairs": pairs}
+    if nee:
+        sizes["connections"] = m
     w = _room(workspace, Workspace, sizes,
-              f"a paths.Workspace with room for {m} paths and {pairs} (path, light) pairs{' and their walks' if transmission else ''} (paths.workspace)", dev, stream)
+              f"a paths.Workspace with room for {m} paths and {pairs} (path, light) pairs{' and their walks' if transmission else ''}"
+              f"{' and their connections' if nee else ''} (paths.workspace)", dev, stream)
     s = stream
     vertices, emitted, radiance, paths, alive, index = w.hits[:m], w.emitted[:m], w.radiance[:m], w.paths[:m], w.alive[:m], w.index[:m]
     rays, next_rays = w.rays[:m], w.next_rays[:m]
@@ -374,6 +546,9 @@ def trace_paths(scene: Scene, hits, incoming, spp: int, max_bounces: int, env=No
     if transmission:
         lobe, through, walk_index, walk_rays, inside_hits = w.lobe[:m], w.transmit[:m], w.walk_index[:m], w.walk_rays[:m], w.inside_hits[:m]
         kind, travel, casts, walk_flags, escape = w.kind[:m], w.travel[:m], w.casts[:m], w.walk_flags[:m], w.escape[:m]
+    if nee:
+        table = _environment(env).table(s)
+        shadow_rays, shadow_hits, asks, pending, ask_index = w.shadow_rays[:m], w.shadow_hits[:m], w.asks[:m], w.pending[:m], w.ask_index[:m]
     listed = counted = None  # bounce 0: every slot
     for b in range(max_bounces + 1):
         if open_casts:
@@ -383,11 +558,17 @@ def trace_paths(scene: Scene, hits, incoming, spp: int, max_bounces: int, env=No
         if env is not None:
             lookup(env, rays, vertices, out=emitted, stream=s)
         last = b == max_bounces
+        if nee:
+            weigh_escape(env, paths, vertices, rays, emitted, listed, counted, heuristic, table, stream=s)
         if not transmission:
+            if nee and not last:
+                connect(scene, env, paths, vertices, rays, listed, counted, seed, SHADING, heuristic, False, table, shadow_rays, asks, pending, stream=s)
             advance(scene, paths, vertices, rays, radiance, emitted, listed, counted, seed, SHADING, rr_start, rr_floor, last, next_rays, alive, stream=s)
         else:
             branch(scene, paths, vertices, rays, listed, counted, seed, last, lobe, through, walk_rays, kind, travel, casts, walk_flags, stream=s)
             select_records(lobe, walk_index, w.walk_count, stream=s)
+            if nee and not last:
+                connect(scene, env, paths, vertices, rays, walk_index, w.walk_count, seed, SHADING, heuristic, False, table, shadow_rays, asks, pending, stream=s)
             advance(scene, paths, vertices, rays, radiance, emitted, walk_index, w.walk_count, seed, SHADING, rr_start, rr_floor, last, next_rays, alive, stream=s)
         if last:
             break
@@ -398,6 +579,10 @@ def trace_paths(scene: Scene, hits, incoming, spp: int, max_bounces: int, env=No
                 refract_step(scene, vertices, inside_hits, walk_rays, kind, travel, casts, walk_flags, MAX_DISTANCE, escape, stream=s)
             select_records(through, walk_index, w.walk_count, stream=s)
             transmit(scene, paths, vertices, kind, travel, escape, walk_flags, walk_index, w.walk_count, seed, rr_start, rr_floor, next_rays, alive, stream=s)
+        if nee:
+            select_records(asks, ask_index, w.ask_count, stream=s)
+            cast_rays_indexed(scene, shadow_rays, ask_index, w.ask_count, shadow_hits, stream=s)
+            settle(paths, asks, pending, radiance, shadow_hits, ask_index, w.ask_count, stream=s)
         listed, counted = select_records(alive, index, w.count, stream=s)
         cast_rays_indexed(scene, next_rays, listed, counted, vertices, stream=s)
         rays, next_rays = next_rays, rays

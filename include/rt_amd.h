@@ -1088,6 +1088,88 @@ int rt_path_transmit(const rt_scene *scene, rt_path *d_paths, size_t m, const ui
                      uint32_t *d_kind, const float *d_travel, const rt_ray *d_escape, uint32_t seed, uint32_t rr_start, float rr_floor,
                      rt_ray *d_next_rays, unsigned char *d_alive, unsigned char *d_walk_flags, void *hip_stream);
 
+/* ---- connection queries: next-event estimation of the sky in path loops --------------------------------------------------------------
+
+ * The path loop finds the scene's lights at every vertex (rt_shade_hits) and the sky only when a lobe-sampled ray happens to leave the
+ * scene, where rt_environment_lookup deposits it unweighed: under a sky with a small bright sun that estimator is noisy.  The lobe
+ * queries' "sky light, both samplers" has the cure for one bounce in seven to eight launches and carries no throughput.  These three
+ * calls are what a caller could not supply from outside — a sky sample per vertex from the path's own hash streams, the throughput
+ * multiplied in before the shadow cast is answered, and the escape weighed by the density rt_path_advance stored in the record — and
+ * bounce b of the path loop becomes
+ *     rt_shade_hits -> rt_environment_lookup -> rt_path_weigh_escape(list_b) ->
+ *     rt_path_connect(list_b, last) -> rt_path_advance(list_b, last) ->                                 [b < max_bounces, from here on]
+ *     rt_select_records(d_asks -> the asking list) -> rt_cast_rays_indexed(d_shadow_rays, that list -> d_shadow_hits) ->
+ *     rt_path_settle(that list) ->
+ *     rt_select_records(d_alive -> list_b+1) -> rt_cast_rays_indexed(d_next_rays, list_b+1 -> d_hits)
+ * With the transmission queries rt_path_branch and rt_select_records(d_lobe) come first and rt_path_connect and rt_path_advance take that
+ * list: a path that goes through the glass deposits nothing at the vertex and connects nothing there.  rt_path_connect precedes
+ * rt_path_advance, which advances beta and rewrites the hit of a path that ends; rt_path_settle follows its deposit, so the order of the
+ * additions into d_radiance is fixed: deposit, then connection.  On the last bounce the connection and the settlement are left out (with
+ * `last` the call asks nothing), so both estimators integrate the same set of paths.  INTEGRATION.md writes the sequence out; DESIGN.md
+ * §3.37 has the estimator, the bytes and the resources.
+ *
+ * The estimator.  At a vertex two strategies can find the sky along a direction d: the connection, which draws d from the table with
+ * density p_env(d) = rt_environment_pdf's, and the next lobe sample, density p_lobe(d) = rt_lobe_pdf's about the sampling normal.  Each
+ * is weighed by rt_mis_weigh's weight against the other, one sample each; the weights add up to 1 wherever either density is positive.
+ * The sky a path sees after a delta event — a camera ray, a ray that left glass: pdf +0 in the record — no connection could have found:
+ * it keeps its full weight.  A connection is occluded by whatever its shadow ray hits, glass included, so light that reaches a vertex
+ * through glass is counted by the transmitted path alone.  The connection's radiance is the sampled texel's and the escape's is
+ * rt_environment_lookup's: with RT_ENV_NEAREST the two estimate one integrand.
+ *
+ * The streams.  With b the bounces taken, s the sample index (bounce >> 24) and seed_b = seed + 0x9e3779b9u * b — rt_path_advance's —
+ * the connection's two uniforms are rt_environment_rays' for seed_b, id and s: film_mix(seed_b ^ 0xc2b2ae35u) is their stream, while the
+ * lobe's u_0 and u_1 come from film_mix(seed_b ^ 0x85ebca6bu).  The two directions of a vertex are drawn independently.
+ *
+ * Every pointer is a device pointer; every call is stream-ordered and asynchronous on hip_stream (NULL = default stream), is one kernel
+ * with one listed slot per lane and 256 lanes per workgroup, allocates nothing, uses no workspace, no atomics, and may be captured into a
+ * HIP graph at once.  The list is rt_path_advance's: slot j = d_index[e] for e < min(*d_count, m); an index >= m names nothing; d_index
+ * NULL: every j < m, and d_count is not read.  Slots that are not listed are not touched.  d_paths is read as two 16-byte accesses and
+ * never written.  d_table is rt_environment_table's for this env; one whose header names another size reads as a table without light,
+ * as in rt_environment_pdf, and nothing is read outside the size the descriptor gives.  All arithmetic is csrc/rt_connect.h's, single f32
+ * and u32 operations in the order given here, none fused, shared by both libraries.
+ * Checked before any device work, in rt_path_advance's order and with its messages: m >= 2^32 is RT_ERR_UNSUPPORTED; a null scene
+ * (rt_path_connect); the descriptor, as rt_environment_rays checks it; m == 0 is RT_OK and launches nothing; a null pointer (d_index may
+ * be NULL; d_count only with d_index; d_shadow_hits may be NULL); the normal_kind (rt_path_connect), then an unknown heuristic; then a
+ * d_paths that is not 16-byte aligned or a d_table that is not 8-byte aligned, RT_ERR_INVALID_ARGUMENT.
+ * Not covered: connections to the scene's own lights with a radius (area-light next-event estimation inside the loop); more than one
+ * sky sample per vertex; connections through glass; _host and rt_multi_* forms (rt_path_connect_cpu, rt_path_settle_cpu and
+ * rt_path_weigh_escape_cpu of include/rt_connect_host.h are the CPU forms); paths inside rt_render_*; any change to rt_path_advance's
+ * record or bits. */
+
+/* The connection, per listed slot whose flags have RT_PATH_ALIVE, with d_hits[j] the path's vertex and d_incoming[j] the ray that found
+ * it, before rt_path_advance moves the path.  `last`, a vertex that is "no hit" by the hit queries' rules and a table without light ask
+ * nothing and draw nothing.  Otherwise, in this order:
+ *   sample     rt_environment_rays' direction, texel and density for spp = 1, RT_FILM_UNIFORM, id = path.id, sample s and seed_b;
+ *              r = texel * scale / pdf where that call asks (a finite density > 0, a direction that leaves the surface about the
+ *              normal normal_kind chooses)
+ *   densities  p_env = rt_environment_pdf(direction); p_lobe = rt_lobe_pdf(direction) on the surface rt_path_advance samples: the
+ *              normal of normal_kind, V = -d_incoming[j].direction, the material's shiness and smoothness
+ *   weight     w = rt_mis_weigh's for n_own = n_other = 1, p_env against p_lobe, and r = r * w per channel
+ *   throughput t = beta * r per channel
+ *   terms      rt_probe_surfaces' diffuse and specular of the direction on rt_material_hits' surface, and
+ *              pending = (+0 + (diffuse * t) * (1 - shiness)) + (specular * t) * shiness — rt_environment_fold for spp = 1 into a
+ *              zeroed rgb, so a -0 reads +0
+ * The slot asks where rt_environment_rays asks and w is finite.  d_asks[j] = 1 or 0; d_shadow_rays[j] = rt_hemisphere_rays' ray along
+ * the direction where it asks, all-zero words where it does not; d_pending[3j ..] is written where it asks and left as it is elsewhere.
+ * Listed slots that are not alive are not touched. */
+int rt_path_connect(const rt_scene *scene, const rt_environment *env, const void *d_table, const rt_path *d_paths, size_t m, const uint32_t *d_index,
+                    const uint32_t *d_count, const rt_hit *d_hits, const rt_ray *d_incoming, uint32_t seed, uint32_t normal_kind, uint32_t heuristic,
+                    int last, rt_ray *d_shadow_rays, unsigned char *d_asks, float *d_pending, void *hip_stream);
+/* The settlement, per listed slot, alive or not (rt_path_advance may have ended the path since it connected): where d_asks[j] != 0 and
+ * d_shadow_hits[j] is "no hit" at all (kind word > 1: rt_environment_fold's rule; d_shadow_hits NULL: nothing occludes),
+ * d_radiance[3j + c] = d_radiance[3j + c] + d_pending[3j + c]; either way d_asks[j] = 0, so that the flags of all m slots are 0 again
+ * when the next bounce connects.  d_paths is not read: it is taken so that the three calls share their list arguments and checks. */
+int rt_path_settle(const rt_path *d_paths, size_t m, const uint32_t *d_index, const uint32_t *d_count, unsigned char *d_asks, const rt_hit *d_shadow_hits,
+                   const float *d_pending, float *d_radiance, void *hip_stream);
+/* The escape, per listed slot whose flags have RT_PATH_ALIVE, after rt_shade_hits and rt_environment_lookup filled d_emitted and before
+ * rt_path_advance deposits it: where d_hits[j] is "no hit" by rt_environment_lookup's rule (kind word > 1 — rt_shade_hits wrote zeros
+ * there, so d_emitted[3j ..] is the sky alone), the record's pdf is finite and > 0 and the table has light,
+ *     d_emitted[3j + c] = d_emitted[3j + c] * w,  w = rt_mis_weigh's for n_own = n_other = 1, pdf against
+ *                                                     rt_environment_pdf(d_incoming[j].direction)
+ * A pdf of +0 (a camera ray, a ray that left glass), a hit, a slot that is not alive and a table without light leave d_emitted alone. */
+int rt_path_weigh_escape(const rt_environment *env, const void *d_table, const rt_path *d_paths, size_t m, const uint32_t *d_index,
+                         const uint32_t *d_count, const rt_hit *d_hits, const rt_ray *d_incoming, uint32_t heuristic, float *d_emitted, void *hip_stream);
+
 /* ---- distributed (stochastic / depth-of-field) pass ----------------------------
 
  * Replaces the par_iter_mut closure at src/main.rs:1131-1156 and the per-pixel RNG construction at
