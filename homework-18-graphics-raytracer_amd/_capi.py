@@ -262,6 +262,7 @@ AMD_SYMBOLS = [
     "rt_path_begin", "rt_path_advance", "rt_path_resolve",
     "rt_path_branch", "rt_path_transmit",
     "rt_path_connect", "rt_path_settle", "rt_path_weigh_escape",
+    "rt_path_connect_lights", "rt_path_settle_lights",
     "rt_texture_levels", "rt_texture_pyramid_floats", "rt_texture_pyramid", "rt_texture_footprint", "rt_texture_sample", "rt_texture_surfaces",
     "rt_light_terms_surfaces",
     "rt_film_offsets", "rt_camera_rays_offset", "rt_camera_rays_offset_host", "rt_film_splat",
@@ -306,6 +307,8 @@ PATH_HOST_SYMBOLS = ["rt_path_begin_cpu", "rt_path_advance_cpu", "rt_path_resolv
 TRANSMIT_HOST_SYMBOLS = ["rt_path_branch_cpu", "rt_path_transmit_cpu"]
 # ... and of the connection queries, declared in include/rt_connect_host.h
 CONNECT_HOST_SYMBOLS = ["rt_path_connect_cpu", "rt_path_settle_cpu", "rt_path_weigh_escape_cpu"]
+# ... and of the light-connection queries, declared in include/rt_light_connect_host.h
+LIGHT_CONNECT_HOST_SYMBOLS = ["rt_path_connect_lights_cpu", "rt_path_settle_lights_cpu"]
 # ... and of the texture queries, declared in include/rt_texture_host.h
 TEXTURE_HOST_SYMBOLS = ["rt_texture_pyramid_cpu", "rt_texture_footprint_cpu", "rt_texture_sample_cpu", "rt_texture_surfaces_cpu"]
 
@@ -407,6 +410,11 @@ def host_lib() -> C.CDLL:
         lib.rt_path_settle_cpu.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.rt_path_weigh_escape_cpu.argtypes = [C.POINTER(EnvironmentDesc), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_uint32, C.c_void_p]
+        lib.rt_path_connect_lights_cpu.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                   C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p]
+        lib.rt_path_settle_lights_cpu.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p]
         lib.rt_texture_pyramid_cpu.argtypes = [C.POINTER(TextureDesc)]
         lib.rt_texture_footprint_cpu.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p]
         lib.rt_texture_sample_cpu.argtypes = [C.POINTER(TextureDesc), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
@@ -554,6 +562,10 @@ def amd_lib() -> C.CDLL:
         lib.rt_path_settle.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.rt_path_weigh_escape.argtypes = [C.POINTER(EnvironmentDesc), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_uint32, C.c_void_p, C.c_void_p]
+        lib.rt_path_connect_lights.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                               C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.rt_path_settle_lights.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p]
         lib.rt_texture_levels.argtypes = [C.c_uint32, C.c_uint32]
         lib.rt_texture_levels.restype = C.c_uint32
         lib.rt_texture_pyramid_floats.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]

@@ -34,6 +34,7 @@
 #include "../rt_path.h"
 #include "../rt_transmit.h"
 #include "../rt_connect.h"
+#include "../rt_light_connect.h"
 #include "../rt_texture.h"
 
 using rt::V3;
@@ -1078,6 +1079,74 @@ int rt_path_weigh_escape_cpu(const rt_environment *env, const void *table, const
         if (!rt::path_escape_weighed(p.flags, hits[j].kind, p.pdf, t)) continue;
         const float w = rt::path_escape_weight(*env, t, heuristic, p.pdf, rt::v3p(incoming[j].direction));
         for (uint32_t c = 0; c < 3u; ++c) emitted[3u * j + c] = emitted[3u * j + c] * w;
+    }
+    return RT_OK;
+}
+
+/* ---- light-connection queries: the connection and the settlement on the CPU (include/rt_amd.h "light-connection queries"; the arithmetic is rt_light_connect.h's, shared with the device) ---- */
+
+int rt_path_connect_lights_cpu(const rt_surface *surfaces, const float *positions, const float *view, const rt_light *lights, const float *aux,
+                               const rt_path *paths, size_t m, const uint32_t *index, const uint32_t *count, uint32_t light_first, uint32_t light_count,
+                               const float *radii, const float *weights, uint32_t seed, float *dirs, unsigned char *asks, float *pending, float *reach,
+                               uint32_t *chosen) {
+    const char *const who = "rt_path_connect_lights_cpu: ";
+    if (const int rc = connect_count(who, m)) return rc;
+    if (m == 0 || light_count == 0) return RT_OK;
+    if (!surfaces || !positions || !view || !lights || !paths || (index && !count) || !dirs || !asks || !pending || !reach)
+        return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + "null surface, position, view, light, path, count (with an index), direction, flag, pending or reach pointer");
+    const size_t n_lights = (size_t)light_first + light_count;
+    std::vector<rt::LightAux> light_aux(n_lights);
+    for (size_t i = 0; i < n_lights; ++i) {
+        light_aux[i] = rt::light_aux_of(lights[i]);
+        if (aux) light_aux[i].cos_in = aux[2u * i], light_aux[i].cos_out = aux[2u * i + 1u];
+    }
+    const rt::LightConnect step = {seed, light_first, light_count, radii, weights};
+    const uint32_t listed = rt::path_listed(index, count, (uint32_t)m);
+    for (uint32_t e = 0; e < listed; ++e) {
+        const uint32_t j = index ? index[e] : e;
+        if (j >= m) continue;
+        const rt_path &p = paths[j];
+        if ((p.flags & RT_PATH_ALIVE) == 0u) continue;
+        const rt_surface &s = surfaces[j];
+        rt::Mat mat;
+        mat.normal = rt::v3p(s.normal);
+        mat.diffuse = rt::v3p(s.diffuse_color);
+        mat.specular = rt::v3p(s.specular_color);
+        mat.shiness = s.shiness;
+        mat.smoothness = s.smoothness;
+        mat.transparency = s.transparency;
+        mat.refraction_index = s.refraction_index;
+        mat.opaque_decay = s.opaque_decay;
+        const rt::LightConnection c = rt::light_connect_record(p, s.valid != 0u, mat, rt::v3p(s.shading_normal), rt::v3p(positions + 3u * (size_t)j),
+                                                               rt::v3p(view + 3u * (size_t)j), lights, light_aux.data(), step);
+        dirs[3u * (size_t)j] = c.dir.x;
+        dirs[3u * (size_t)j + 1u] = c.dir.y;
+        dirs[3u * (size_t)j + 2u] = c.dir.z;
+        asks[j] = c.ask ? 1 : 0;
+        if (chosen) chosen[j] = c.chosen;
+        if (c.ask) {
+            pending[3u * (size_t)j] = c.pending.x;
+            pending[3u * (size_t)j + 1u] = c.pending.y;
+            pending[3u * (size_t)j + 2u] = c.pending.z;
+            reach[j] = c.reach;
+        }
+    }
+    return RT_OK;
+}
+
+int rt_path_settle_lights_cpu(const rt_path *paths, size_t m, const uint32_t *index, const uint32_t *count, unsigned char *asks, const rt_ray *shadow_rays,
+                              const rt_hit *shadow_hits, const float *reach, const float *pending, float *radiance) {
+    const char *const who = "rt_path_settle_lights_cpu: ";
+    if (const int rc = connect_count(who, m)) return rc;
+    if (m == 0) return RT_OK;
+    if (!paths || (index && !count) || !asks || !shadow_rays || !reach || !pending || !radiance)
+        return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + "null path, count (with an index), flag, ray, reach, pending or radiance pointer");
+    const uint32_t listed = rt::path_listed(index, count, (uint32_t)m);
+    for (uint32_t e = 0; e < listed; ++e) {
+        const uint32_t j = index ? index[e] : e;
+        if (j < m)
+            rt::light_settle_record(j, asks, reinterpret_cast<const uint32_t *>(shadow_rays), reinterpret_cast<const uint32_t *>(shadow_hits), reach, pending,
+                                    radiance);
     }
     return RT_OK;
 }

@@ -177,18 +177,7 @@ struct KeptPositions {
     DeviceBuffer d_pieces;
 };
 
-/* a spot light's cone edge as a cosine, with margins (rt_shade.h light_asks); anything unusual switches the shortcut off */
-inline rt::LightAux light_aux_of(const rt_light &l) {
-    rt::LightAux aux;
-    aux.cos_in = std::numeric_limits<float>::infinity();
-    aux.cos_out = -std::numeric_limits<float>::infinity();
-    const double a = (double)l.angle;
-    if (l.kind == RT_LIGHT_SPOT && a > 1e-3 && a < 3.14) {
-        aux.cos_in = std::nextafter((float)(cos(a) + 1e-4), std::numeric_limits<float>::infinity());
-        aux.cos_out = std::nextafter((float)(cos(a) - 1e-4), -std::numeric_limits<float>::infinity());
-    }
-    return aux;
-}
+using rt::light_aux_of; /* rt_shade.h: a spot light's cone edge as a cosine, with margins */
 
 struct rt_scene {
     int device;

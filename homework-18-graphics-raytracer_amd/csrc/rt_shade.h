@@ -12,6 +12,9 @@
 #ifndef RT_SHADE_H
 #define RT_SHADE_H
 
+#include <cmath>
+#include <limits>
+
 #include "../../include/rt_amd.h"
 #include "rt_vec.h"
 
@@ -190,6 +193,20 @@ RT_HD bool approximate_into_directional(const Light &l, V3 position, DirLight *o
 struct LightAux {
     float cos_in, cos_out;
 };
+/* a spot light's cone edge as a cosine, with margins (light_asks); anything unusual switches the shortcut off.  Host code: what
+ * rt_scene_create and rt_scene_update_lights store per light, and what librt_host.so's CPU forms compute for the same answer */
+inline LightAux light_aux_of(const rt_light &l) {
+    LightAux aux;
+    aux.cos_in = std::numeric_limits<float>::infinity();
+    aux.cos_out = -std::numeric_limits<float>::infinity();
+    const double a = (double)l.angle;
+    if (l.kind == RT_LIGHT_SPOT && a > 1e-3 && a < 3.14) {
+        aux.cos_in = std::nextafter((float)(cos(a) + 1e-4), std::numeric_limits<float>::infinity());
+        aux.cos_out = std::nextafter((float)(cos(a) - 1e-4), -std::numeric_limits<float>::infinity());
+    }
+    return aux;
+}
+
 template <class Light, class Aux>
 RT_HD bool light_asks(const Light &l, const Aux &aux, V3 position, V3 adj_n, V3 *direction_out) {
     V3 direction;

@@ -19,6 +19,13 @@ roulette on the device; ``begin`` makes the records and ``resolve`` adds the mea
     connect_numpy / settle_numpy / weigh_escape_numpy
                                                     their CPU forms (rt_path_connect_cpu, rt_path_settle_cpu and
                                                     rt_path_weigh_escape_cpu): the device's bits
+    connect_lights / settle_lights                  rt_path_connect_lights / rt_path_settle_lights ("light-connection queries"): next-event
+                                                    estimation of the scene's own lights — one light and one point on it per vertex,
+                                                    its terms times the throughput over the chance of the choice, its shadow cast
+                                                    settled by get_shade's rule; light_seed: the seed arealights.rays draws the same
+                                                    points with
+    connect_lights_numpy / settle_lights_numpy      their CPU forms (rt_path_connect_lights_cpu and rt_path_settle_lights_cpu): the
+                                                    device's bits
     trace_paths                                   begin -> per bounce: shade_hits -> environment.lookup -> advance -> select_records
                                                     -> cast_rays_indexed -> resolve — written from the public calls alone: to be
                                                     copied and changed
@@ -35,9 +42,10 @@ import numpy as np
 from . import _capi
 from ._args import (_aligned_bytes, _below_2_32, _host, _host_records, _new, _on_stream, _out_tensor, _p, _room, _samples, _stream_ptr, _tensor, _void,
                     _zeroed_out)
-from ._opened import LightWorkspace, refract_step, shade_hits_by_light
+from ._capi import Light, SceneDesc
+from ._opened import LightWorkspace, _light_range, refract_step, shade_hits_by_light
 from ._queries import HIT_DTYPE, HIT_NONE, RAY_DTYPE, _hit_records, cast_rays_indexed, select_records, shade_hits
-from ._world import Scene
+from ._world import Scene, World
 from .environment import TABLE_HEADER_BYTES, Environment, _environment, _host_environment, lookup, table_bytes
 from .lobes import BALANCE, POWER, _host_surfaces  # RT_MIS_BALANCE / RT_MIS_POWER: connect's and weigh_escape's heuristic
 
@@ -238,6 +246,78 @@ def weigh_escape(env: Environment, paths, hits, incoming, emitted, index=None, c
     return emitted
 
 
+# ---- light connections (include/rt_amd.h "light-connection queries") ----
+
+NO_LIGHT = 0xFFFFFFFF  # ``chosen`` of a path that drew no light
+BOUNCE_STEP, LIGHT_POINT_STREAM = 0x9E3779B9, 0x68E31DA4  # RT_PATH_BOUNCE_STEP / RT_LIGHT_CONNECT_POINT_STREAM
+
+
+def _film_mix(v: int) -> int:
+    v &= 0xFFFFFFFF
+    v ^= v >> 16
+    v = (v * 0x7FEB352D) & 0xFFFFFFFF
+    v ^= v >> 15
+    v = (v * 0x846CA68B) & 0xFFFFFFFF
+    return v ^ (v >> 16)
+
+
+def light_seed(seed: int, bounce: int) -> int:
+    """The seed with which arealights.rays (spp 1, UNIFORM, the paths' ids, sample index s) and arealights.samples_numpy draw the points
+    connect_lights draws at bounce ``bounce`` of a loop whose seed is ``seed``: film_mix((seed + 0x9e3779b9 * bounce) ^ 0x68e31da4)."""
+    return _film_mix(((int(seed) + BOUNCE_STEP * int(bounce)) & 0xFFFFFFFF) ^ LIGHT_POINT_STREAM)
+
+
+def connect_lights(scene: Scene, paths, hits, incoming, index=None, count=None, seed: int = 0, radii=None, weights=None, light_first: int = 0,
+                   light_count=None, out_rays=None, out_asks=None, out_pending=None, out_reach=None, out_chosen=None, stream=None):
+    """rt_path_connect_lights: per listed live path one of the lights light_first .. light_first + light_count - 1 (default: every light
+    from light_first on) — uniformly, or by ``weights`` ((L,) float32; one that is not > 0 counts as 0) — and one point on its sphere of
+    radius ``radii[l]`` ((L,) float32 or None: points), both from the path's own hash streams for seed + 0x9e3779b9 * bounce; the light's
+    Phong terms at the path's vertex times the throughput over the chance of the choice.  To be called before advance, on the hits and
+    rays advance will get.  Returns (rays, asks, pending, reach, chosen): ``out_asks`` (M,) uint8, 1 where get_shade would cast towards
+    that light; ``out_rays`` (M, 11) int32, the shadow ray where it asks and zero words where it does not; ``out_pending`` (M, 3)
+    float32, what the path's radiance gains if the light is not occluded, and ``out_reach`` (M,) float32, the distance to the point
+    (-1: a directional light without origin) — both written where it asks; ``out_chosen`` ((M,) int32 or None: not wanted, and None is
+    returned) the light drawn, NO_LIGHT where none was.  The record is read only.  Slots that are not listed or not alive are not touched:
+    ``out_asks`` is zeroed here if not given."""
+    records = _hit_records(hits)
+    m, dev = records.shape[0], records.device
+    index_p, count_p = _listed(m, dev, paths, index, count)
+    _tensor(incoming, "incoming", "int32", (m, 11))
+    first, lights = _light_range(scene, light_first, light_count)
+    _tensor(radii, "radii", "float32", (lights,), optional=True)
+    _tensor(weights, "weights", "float32", (lights,), optional=True)
+    out_rays = _out_tensor(out_rays, (m, 11), "int32", dev, "out_rays")
+    if out_asks is None:
+        with _on_stream(stream):
+            out_asks = _new((m,), "uint8", dev).zero_()
+    _tensor(out_asks, "out_asks", "uint8", (m,))
+    out_pending = _out_tensor(out_pending, (m, 3), "float32", dev, "out_pending")
+    out_reach = _out_tensor(out_reach, (m,), "float32", dev, "out_reach")
+    _tensor(out_chosen, "out_chosen", "int32", (m,), optional=True)
+    _capi.check(_capi.amd_lib().rt_path_connect_lights(scene._h, _p(paths), m, index_p, count_p, _p(records), _p(incoming), first, lights, _p(radii),
+                                                       _p(weights), int(seed) & 0xFFFFFFFF, _p(out_rays), _p(out_asks), _p(out_pending), _p(out_reach),
+                                                       _p(out_chosen), _stream_ptr(stream)))
+    return out_rays, out_asks, out_pending, out_reach, out_chosen
+
+
+def settle_lights(paths, asks, shadow_rays, reach, pending, radiance, shadow_hits=None, index=None, count=None, stream=None):
+    """rt_path_settle_lights: per listed slot, radiance += pending where ``asks`` is set, unless the slot's record of ``shadow_hits``
+    ((M, 13) int32: what the cast of connect_lights' rays found; None: nothing occludes) is a hit and either ``reach`` is negative or the
+    hit lies nearer to the ray's origin than ``reach`` — get_shade's rule; the ask is cleared either way.  To be called after advance, so
+    that a vertex's deposit is added before its connection.  ``paths`` is not read: a path advance ended still settles.  Returns
+    ``radiance``."""
+    m, dev = _tensor(asks, "asks", "uint8", (None,)).shape[0], asks.device
+    index_p, count_p = _listed(m, dev, paths, index, count)
+    _tensor(shadow_rays, "shadow_rays", "int32", (m, 11))
+    _tensor(shadow_hits, "shadow_hits", "int32", (m, 13), optional=True)
+    _tensor(reach, "reach", "float32", (m,))
+    _tensor(pending, "pending", "float32", (m, 3))
+    _tensor(radiance, "radiance", "float32", (m, 3))
+    _capi.check(_capi.amd_lib().rt_path_settle_lights(_p(paths), m, index_p, count_p, _p(asks), _p(shadow_rays), _p(shadow_hits), _p(reach), _p(pending),
+                                                      _p(radiance), _stream_ptr(stream)))
+    return radiance
+
+
 # ---- the CPU forms ----
 
 def _host_paths(paths):
@@ -432,6 +512,66 @@ def weigh_escape_numpy(texels, table, paths, hits, incoming, emitted, index=None
     return emitted
 
 
+def connect_lights_numpy(surfaces, positions, view, lights, paths, index=None, count=None, seed: int = 0, radii=None, weights=None, light_first: int = 0,
+                         light_count=None, aux=None, dirs=None, asks=None, pending=None, reach=None, chosen=None):
+    """rt_path_connect_lights_cpu: what connect_lights writes for paths whose vertices' materials are ``surfaces`` (materials.material_hits;
+    valid 0: "no hit") at ``positions`` ((M, 3) float32) seen from ``view`` ((M, 3) float32, minus the incoming direction), bit for bit,
+    on the CPU.  ``lights``: a World, a SceneDesc or a sequence of Light — the scene's lights, indexed as the scene indexes them; ``aux``
+    (n_lights, 2) float32 (cos_in, cos_out) or None: computed as the scene's are.  Returns new arrays (dirs (M, 3) float32, asks (M,)
+    uint8, pending (M, 3) float32, reach (M,) float32, chosen (M,) uint32): the shadow ray's direction in place of the ray; each as
+    given (zeros, ``chosen`` NO_LIGHT, if None) where a slot is not touched, ``pending`` and ``reach`` also where a slot does not ask."""
+    if isinstance(lights, World):
+        lights = lights.desc()
+    if isinstance(lights, SceneDesc):
+        desc = lights
+        lights = [desc.lights[l] for l in range(desc.n_lights)]
+    arr = (Light * max(len(lights), 1))(*lights)
+    first = int(light_first)
+    n_range = len(lights) - first if light_count is None else int(light_count)
+    if first < 0 or n_range < 0 or first + n_range > len(lights):
+        raise ValueError(f"lights {first} .. {first + n_range} of {len(lights)}")
+    surfaces = _host_surfaces(surfaces)
+    m = surfaces.shape[0]
+    positions = _host(positions, np.float32, (m, 3), "positions")
+    view = _host(view, np.float32, (m, 3), "view")
+    radii = _host(radii, np.float32, (n_range,), "radii", optional=True)
+    weights = _host(weights, np.float32, (n_range,), "weights", optional=True)
+    aux = _host(aux, np.float32, (len(lights), 2), "aux", optional=True)
+    paths = _host_paths(paths)
+    if paths.shape[0] != m:
+        raise ValueError(f"paths: expected {m} records")
+    dirs, asks, pending = _start(dirs, np.float32, (m, 3), "dirs"), _start(asks, np.uint8, (m,), "asks"), _start(pending, np.float32, (m, 3), "pending")
+    reach, chosen = _start(reach, np.float32, (m,), "reach"), _start(chosen, np.uint32, (m,), "chosen", NO_LIGHT)
+    index, count = _host_list(index, count, m)
+    _capi.check_host(_capi.host_lib().rt_path_connect_lights_cpu(_void(surfaces), _void(positions), _void(view), C.cast(arr, C.c_void_p), _void(aux),
+                                                                 _void(paths), m, _void(index), _void(count), first, n_range, _void(radii), _void(weights),
+                                                                 int(seed) & 0xFFFFFFFF, _void(dirs), _void(asks), _void(pending), _void(reach),
+                                                                 _void(chosen)))
+    return dirs, asks, pending, reach, chosen
+
+
+def settle_lights_numpy(asks, shadow_rays, reach, pending, radiance, shadow_hits=None, index=None, count=None):
+    """rt_path_settle_lights_cpu: settle_lights on the CPU, bit for bit.  ``shadow_rays``: RAY_DTYPE or (M, 11) words; ``shadow_hits``:
+    HIT_DTYPE or (M, 13) words, or None: nothing occludes.  Returns new arrays (asks, radiance)."""
+    asks = np.ascontiguousarray(asks, dtype=np.uint8).reshape(-1).copy()
+    m = asks.shape[0]
+    shadow_rays = _host_records(shadow_rays, RAY_DTYPE, 11, "shadow_rays")
+    if shadow_rays.shape[0] != m:
+        raise ValueError(f"shadow_rays: expected {m} records")
+    reach = _host(reach, np.float32, (m,), "reach")
+    pending = _host(pending, np.float32, (m, 3), "pending")
+    radiance = _host(radiance, np.float32, (m, 3), "radiance").copy()
+    if shadow_hits is not None:
+        shadow_hits = _host_records(shadow_hits, HIT_DTYPE, 13, "shadow_hits")
+        if shadow_hits.shape[0] != m:
+            raise ValueError(f"shadow_hits: expected {m} records")
+    paths = np.zeros(max(m, 1), dtype=PATH_DTYPE)  # not read
+    index, count = _host_list(index, count, m)
+    _capi.check_host(_capi.host_lib().rt_path_settle_lights_cpu(_void(paths), m, _void(index), _void(count), _void(asks), _void(shadow_rays),
+                                                                _void(shadow_hits), _void(reach), _void(pending), _void(radiance)))
+    return asks, radiance
+
+
 # ---- the loop ----
 
 class Workspace:
@@ -441,10 +581,22 @@ class Workspace:
     (44), the inside hits (52), kind, travel and casts (4 + 4 + 4), the walk flags (1) and the escape rays (44).  ``kind`` is filled with
     HIT_NONE and the walk flags and the escape rays with zeros, once, here.  ``connections`` paths of room for ``nee`` (0: none), 113 B
     each: the shadow rays (44), the shadow hits (52), the asks (1), the pending radiance (12) and a second index (4; its count is 4 B
-    once).  The asks are zeroed once, here: settle leaves them so."""
+    once).  The asks are zeroed once, here: settle leaves them so.  ``light_connections`` paths of room for ``light_nee`` (0: none), 117 B
+    each and 4 B more with ``chosen``: buffers of their own, since a vertex's sky connection and its light connection are outstanding at
+    once — the shadow rays (44), the shadow hits (52), the asks (1, zeroed once, here), the pending radiance (12), the reach (4) and a
+    second index (4; its count is 4 B once), and optionally the light chosen (4)."""
 
-    def __init__(self, entries: int, pairs: int, device, walk: int = 0, connections: int = 0):
+    def __init__(self, entries: int, pairs: int, device, walk: int = 0, connections: int = 0, light_connections: int = 0, chosen: bool = False):
         self.entries, self.pairs, self.walk, self.connections = int(entries), int(pairs), int(walk), int(connections)
+        self.light_connections = lc = int(light_connections)
+        self.light_chosen = None
+        if lc:
+            self.light_shadow_rays, self.light_shadow_hits = _new((lc, 11), "int32", device), _new((lc, 13), "int32", device)
+            self.light_asks, self.light_pending = _new((lc,), "uint8", device).zero_(), _new((lc, 3), "float32", device)
+            self.light_reach = _new((lc,), "float32", device)
+            self.light_ask_index, self.light_ask_count = _new((lc,), "int32", device), _new((1,), "int32", device)
+            if chosen:
+                self.light_chosen = _new((lc,), "int32", device)
         if connections:
             self.shadow_rays, self.shadow_hits = _new((connections, 11), "int32", device), _new((connections, 13), "int32", device)
             self.asks, self.pending = _new((connections,), "uint8", device).zero_(), _new((connections, 3), "float32", device)
@@ -463,19 +615,23 @@ class Workspace:
             self.walk_flags, self.escape = _new((walk,), "uint8", device).zero_(), _new((walk, 11), "int32", device).zero_()
 
 
-def workspace(n: int, device, spp: int, scene: Scene = None, transmission: bool = False, nee: bool = False) -> Workspace:
+def workspace(n: int, device, spp: int, scene: Scene = None, transmission: bool = False, nee: bool = False, light_nee: bool = False,
+              chosen: bool = False) -> Workspace:
     """A Workspace for trace_paths on up to ``n`` roots with ``spp`` samples; with ``scene`` also for ``open_casts`` on its lights, with
     ``transmission`` also the walk buffers of trace_paths(transmission=True), with ``nee`` also the connection buffers of
-    trace_paths(nee=True): 113 B per path more — shadow rays 44, shadow hits 52, asks 1, pending 12, a second index 4 — and one count."""
+    trace_paths(nee=True): 113 B per path more — shadow rays 44, shadow hits 52, asks 1, pending 12, a second index 4 — and one count; with ``light_nee`` also the light-connection buffers of
+    trace_paths(light_nee=True), separate from the sky's: 117 B per path more — shadow rays 44, shadow hits 52, asks 1, pending 12, reach
+    4, a second index 4 — and one count, and with ``chosen`` 4 B per path for the light each vertex drew (Workspace.light_chosen)."""
     if n < 0 or spp < 0:
         raise ValueError("n and spp must not be negative")
     entries = int(n) * int(spp)
-    return Workspace(entries, entries * scene.n_lights if scene is not None else 0, device, entries if transmission else 0, entries if nee else 0)
+    return Workspace(entries, entries * scene.n_lights if scene is not None else 0, device, entries if transmission else 0, entries if nee else 0,
+                     entries if light_nee else 0, bool(chosen))
 
 
 def trace_paths(scene: Scene, hits, incoming, spp: int, max_bounces: int, env=None, rr_start: int = 3, rr_floor: float = 0.05, seed: int = 0, ids=None,
                 out=None, open_casts: bool = True, stream=None, workspace=None, transmission: bool = False, walk_rounds: int = 11, nee: bool = False,
-                heuristic: int = BALANCE):
+                heuristic: int = BALANCE, light_nee: bool = False, light_radii=None, light_weights=None):
     """``spp`` paths of up to ``max_bounces`` bounces from every hit, their mean ADDED to ``out`` ((N, 3) float32 CUDA; None: a new,
     zeroed tensor): at each vertex the light of the scene's lights (shade_hits) — with ``env`` (an environment.Environment) the sky for
     the paths that left the scene — times the throughput, then one direction from the vertex's own lobes.  ``hits`` and ``incoming`` are
@@ -511,7 +667,20 @@ def trace_paths(scene: Scene, hits, incoming, spp: int, max_bounces: int, env=No
     weight, and a connection through glass is occluded by it, so nothing is counted twice.  The connection carries its own texel's
     radiance and the escape the lookup's: with environment.NEAREST the two estimate one integrand.  The workspace is then
     workspace(n, device, spp, scene, nee=True); the table is env.table(stream), built (and allocated) by the first call that asks for it.
-    With ``nee`` False not one call of the sequence changes."""
+    With ``nee`` False not one call of the sequence changes.
+    ``light_nee``: next-event estimation of the scene's own lights — one light per vertex, chosen uniformly or by ``light_weights``
+    ((n_lights,) float32), and one point on its sphere of radius ``light_radii[l]`` ((n_lights,) float32; None: points), so one shadow
+    cast per vertex whatever the number of lights, and soft shadows where the lights have radii.  The shade step is left out (the
+    emitted light of the hits is zeros; ``open_casts`` then has nothing to open) and per bounce the sequence becomes
+      [zeros] -> environment.lookup (only with env) -> connect_lights(list_b) -> advance(list_b, last) ->
+      select_records(light asks) -> cast_rays_indexed(shadow rays -> shadow hits) -> settle_lights(that list) ->
+      select_records(alive) -> cast_rays_indexed(next rays, list_b+1)
+    The last bounce connects and settles too, as shade_hits lights the last vertex.  With ``nee`` both connections of a vertex are
+    outstanding at once, in buffers of their own, and the lights are settled before the sky: a vertex adds deposit, lights, sky, the
+    order in which the loop without ``light_nee`` adds them — with one light the two loops give the same bits.  With ``transmission``
+    connect_lights takes the lobe list, as advance does, and settle_lights follows transmit.  The workspace is then
+    workspace(n, device, spp, scene, light_nee=True) (``chosen``: Workspace.light_chosen receives the light each vertex drew).  With
+    ``light_nee`` False not one call of the sequence changes."""
     spp, max_bounces, walk_rounds = _samples(spp), int(max_bounces), int(walk_rounds)
     if max_bounces < 0:
         raise ValueError("max_bounces must not be negative")
@@ -528,14 +697,18 @@ def trace_paths(scene: Scene, hits, incoming, spp: int, max_bounces: int, env=No
     _below_2_32(m, "(sample, hit) entries")
     if m == 0:
         return out
-    pairs = m * scene.n_lights if open_casts else 0
+    pairs = m * scene.n_lights if open_casts and not light_nee else 0
     _below_2_32(pairs, "(path, light) pairs")
     sizes = {"entries": m, "pairs": pairs, "walk": m} if transmission else {"entries": m, "pairs": pairs}
     if nee:
         sizes["connections"] = m
+    if light_nee:
+        sizes["light_connections"] = m
+        _tensor(light_radii, "light_radii", "float32", (scene.n_lights,), optional=True)
+        _tensor(light_weights, "light_weights", "float32", (scene.n_lights,), optional=True)
     w = _room(workspace, Workspace, sizes,
               f"a paths.Workspace with room for {m} paths and {pairs} (path, light) pairs{' and their walks' if transmission else ''}"
-              f"{' and their connections' if nee else ''} (paths.workspace)", dev, stream)
+              f"{' and their connections' if nee else ''}{' and their light connections' if light_nee else ''} (paths.workspace)", dev, stream)
     s = stream
     vertices, emitted, radiance, paths, alive, index = w.hits[:m], w.emitted[:m], w.radiance[:m], w.paths[:m], w.alive[:m], w.index[:m]
     rays, next_rays = w.rays[:m], w.next_rays[:m]
@@ -549,9 +722,25 @@ def trace_paths(scene: Scene, hits, incoming, spp: int, max_bounces: int, env=No
     if nee:
         table = _environment(env).table(s)
         shadow_rays, shadow_hits, asks, pending, ask_index = w.shadow_rays[:m], w.shadow_hits[:m], w.asks[:m], w.pending[:m], w.ask_index[:m]
+    if light_nee:
+        light_rays, light_hits, light_asks, light_pending = w.light_shadow_rays[:m], w.light_shadow_hits[:m], w.light_asks[:m], w.light_pending[:m]
+        light_reach, light_index = w.light_reach[:m], w.light_ask_index[:m]
+        light_chosen = w.light_chosen[:m] if w.light_chosen is not None else None
+
+        def connect_to_lights(list_index, list_count):
+            connect_lights(scene, paths, vertices, rays, list_index, list_count, seed, light_radii, light_weights, 0, None, light_rays, light_asks,
+                           light_pending, light_reach, light_chosen, stream=s)
+
+        def settle_the_lights():
+            select_records(light_asks, light_index, w.light_ask_count, stream=s)
+            cast_rays_indexed(scene, light_rays, light_index, w.light_ask_count, light_hits, stream=s)
+            settle_lights(paths, light_asks, light_rays, light_reach, light_pending, radiance, light_hits, light_index, w.light_ask_count, stream=s)
     listed = counted = None  # bounce 0: every slot
     for b in range(max_bounces + 1):
-        if open_casts:
+        if light_nee:
+            with _on_stream(s):
+                emitted.zero_()  # the shade step is left out
+        elif open_casts:
             shade_hits_by_light(scene, vertices, rays, out=emitted, stream=s, workspace=w.lights)
         else:
             shade_hits(scene, vertices, rays, out=emitted, stream=s)
@@ -563,14 +752,20 @@ def trace_paths(scene: Scene, hits, incoming, spp: int, max_bounces: int, env=No
         if not transmission:
             if nee and not last:
                 connect(scene, env, paths, vertices, rays, listed, counted, seed, SHADING, heuristic, False, table, shadow_rays, asks, pending, stream=s)
+            if light_nee:
+                connect_to_lights(listed, counted)
             advance(scene, paths, vertices, rays, radiance, emitted, listed, counted, seed, SHADING, rr_start, rr_floor, last, next_rays, alive, stream=s)
         else:
             branch(scene, paths, vertices, rays, listed, counted, seed, last, lobe, through, walk_rays, kind, travel, casts, walk_flags, stream=s)
             select_records(lobe, walk_index, w.walk_count, stream=s)
             if nee and not last:
                 connect(scene, env, paths, vertices, rays, walk_index, w.walk_count, seed, SHADING, heuristic, False, table, shadow_rays, asks, pending, stream=s)
+            if light_nee:
+                connect_to_lights(walk_index, w.walk_count)
             advance(scene, paths, vertices, rays, radiance, emitted, walk_index, w.walk_count, seed, SHADING, rr_start, rr_floor, last, next_rays, alive, stream=s)
         if last:
+            if light_nee:
+                settle_the_lights()
             break
         if transmission:
             for _ in range(walk_rounds):
@@ -579,6 +774,8 @@ def trace_paths(scene: Scene, hits, incoming, spp: int, max_bounces: int, env=No
                 refract_step(scene, vertices, inside_hits, walk_rays, kind, travel, casts, walk_flags, MAX_DISTANCE, escape, stream=s)
             select_records(through, walk_index, w.walk_count, stream=s)
             transmit(scene, paths, vertices, kind, travel, escape, walk_flags, walk_index, w.walk_count, seed, rr_start, rr_floor, next_rays, alive, stream=s)
+        if light_nee:
+            settle_the_lights()
         if nee:
             select_records(asks, ask_index, w.ask_count, stream=s)
             cast_rays_indexed(scene, shadow_rays, ask_index, w.ask_count, shadow_hits, stream=s)

@@ -1170,6 +1170,84 @@ int rt_path_settle(const rt_path *d_paths, size_t m, const uint32_t *d_index, co
 int rt_path_weigh_escape(const rt_environment *env, const void *d_table, const rt_path *d_paths, size_t m, const uint32_t *d_index,
                          const uint32_t *d_count, const rt_hit *d_hits, const rt_ray *d_incoming, uint32_t heuristic, float *d_emitted, void *hip_stream);
 
+/* ---- light-connection queries: one sampled scene light per path vertex ------------------------------------------------------------
+
+ * The path loop lights every vertex with rt_shade_hits, which evaluates all of the scene's lights as points: one shadow cast per light
+ * and vertex, and a hard edge on every shadow inside a path-traced frame.  These two calls are next-event estimation of the scene's own
+ * lights — what a caller could not put together from rt_area_light_rays, rt_light_terms and the connection queries from outside: the
+ * light and the point on it drawn from the path's own hash streams, the throughput multiplied in before rt_path_advance moves it, and
+ * get_shade's occlusion rule applied after rt_path_advance has rewritten the hit of a path that ended.  One light per vertex, one shadow
+ * cast per vertex, soft shadows where the lights have radii.  Bounce b of the path loop becomes
+ *     [rt_shade_hits is left out: d_emitted of the hits is zeros] -> rt_environment_lookup (the sky on the misses, if any) ->
+ *     rt_path_connect_lights(list_b) -> rt_path_advance(list_b, last) ->
+ *     rt_select_records(d_asks -> the asking list) -> rt_cast_rays_indexed(d_shadow_rays, that list -> d_shadow_hits) ->
+ *     rt_path_settle_lights(that list) ->                                                                  [the last bounce ends here]
+ *     rt_select_records(d_alive -> list_b+1) -> rt_cast_rays_indexed(d_next_rays, list_b+1 -> d_hits)
+ * The last bounce connects and settles too, as rt_shade_hits lights the last vertex.  With the transmission queries the connection takes
+ * the lobe list, as rt_path_advance does, and the settlement follows rt_path_transmit.  With the connection queries both connections of
+ * a vertex are outstanding at once and need buffers of their own; the lights are settled before the sky, so that a vertex adds its
+ * contributions in rt_shade_hits' order: deposit, the lights, the sky.  INTEGRATION.md writes the sequence out; DESIGN.md §3.38 has the
+ * estimator, the bytes and the resources.
+ *
+ * The estimator.  With L_l(x) what light l sends to the vertex x through get_shade's terms, rt_shade_hits adds sum_l L_l.  This block
+ * draws l with chance p_l and adds L_l / p_l: the same mean, one cast.  With a radius the light is a sphere (the area-light queries'), one
+ * point of it is drawn uniformly and the light displaced there, so the mean is rt_area_light_fold's, a soft shadow.  No multiple
+ * importance sampling is needed: the scene's lights are not geometry, no lobe-sampled ray ever finds one, and the connection is the only
+ * strategy that reaches them.
+ *
+ * The streams.  With b the bounces taken, s the sample index (bounce >> 24), seed_b = seed + 0x9e3779b9u * b and seed_h =
+ * film_mix(seed_b ^ 0x85ebca6bu) — rt_path_advance's — the light is chosen by u_5 = the hash of (id, film_mix(seed_h ^ 0x2545f491u), s,
+ * axis 0), made as the roulette's u_3 is with a constant of its own; the point is rt_area_light_rays' d_sample for spp = 1,
+ * RT_FILM_UNIFORM, that light, id, s and the seed film_mix(seed_b ^ 0x68e31da4u), bit for bit.
+ *
+ * Every pointer is a device pointer; both calls are stream-ordered and asynchronous on hip_stream (NULL = default stream), one kernel
+ * with one listed slot per lane and 256 lanes per workgroup, allocate nothing, use no workspace, no LDS, no atomics, and may be captured
+ * into a HIP graph at once.  The list is rt_path_advance's: slot j = d_index[e] for e < min(*d_count, m); an index >= m names nothing;
+ * d_index NULL: every j < m, and d_count is not read.  Slots that are not listed are not touched.  d_paths is read as two 16-byte
+ * accesses and never written.  All arithmetic is csrc/rt_light_connect.h's, single f32 and u32 operations in the order given here, none
+ * fused, shared by both libraries.
+ * Checked before any device work, in rt_path_connect's order and with its words: m >= 2^32 is RT_ERR_UNSUPPORTED; a null scene
+ * (rt_path_connect_lights); m == 0 or light_count == 0 is RT_OK and launches nothing; a null pointer (d_index may be NULL; d_count only
+ * with d_index; d_radii, d_weights, d_chosen and d_shadow_hits may be NULL); a d_paths that is not 16-byte aligned; then, as in
+ * rt_area_light_rays, light_first + light_count beyond the scene's lights, RT_ERR_INVALID_ARGUMENT.
+ * Not covered: more than one light sample per vertex; emitters that are geometry (and with them any weighing against the lobes); _host
+ * and rt_multi_* forms (rt_path_connect_lights_cpu and rt_path_settle_lights_cpu of include/rt_light_connect_host.h are the CPU forms);
+ * paths inside rt_render_*; any change to rt_path_advance's record or bits. */
+
+/* The connection, per listed slot whose flags have RT_PATH_ALIVE, with d_hits[j] the path's vertex and d_incoming[j] the ray that found
+ * it, before rt_path_advance moves the path.  A vertex that is "no hit" by the hit queries' rules asks nothing and draws nothing.
+ * Otherwise, in this order:
+ *   light      d_weights NULL: uniform, l = min((uint32_t)(u_5 * light_count), light_count - 1) and inv_p = (float)light_count.  Else
+ *              d_weights holds light_count floats; one that is not > 0 counts as 0; total = their sum in ascending order in f32; l is the
+ *              first light whose running sum exceeds u_5 * total (a light of weight 0 is never chosen) and inv_p = total / w_l; a total
+ *              that is not > 0 asks nothing
+ *   point      rt_area_light_rays' sample of light light_first + l with radius d_radii[l]; d_radii NULL or a radius that is not > 0:
+ *              the stored light, no word touched
+ *   ask        on the light displaced to the point, rt_light_rays' test (get_shade reaches the shadow cast) and
+ *              approximate_into_directional must both hold
+ *   terms      rt_light_terms' diffuse and specular of that light; e = (+0 + diffuse * (1 - shiness)) + specular * shiness, which is
+ *              rt_light_fold for one light into a zeroed rgb
+ *   pending    beta * (e * inv_p) per channel, each product rounded once: with one light, d_radiance + d_pending is rt_path_advance's
+ *              deposit of rt_shade_hits' light, bit for bit
+ *   reach      the distance from the vertex to the point, or -1.0f for a directional light without origin
+ * d_asks[j] = 1 or 0; d_shadow_rays[j] = rt_light_rays' ray towards the point where it asks, all-zero words where it does not;
+ * d_pending[3j ..] and d_reach[j] are written where it asks and left as they are elsewhere; d_chosen[j] (d_chosen may be NULL) = the
+ * absolute index of the light drawn, whether it asks or not, or 0xffffffff where none was drawn.  Listed slots that are not alive are
+ * not touched. */
+int rt_path_connect_lights(const rt_scene *scene, const rt_path *d_paths, size_t m, const uint32_t *d_index, const uint32_t *d_count,
+                           const rt_hit *d_hits, const rt_ray *d_incoming, uint32_t light_first, uint32_t light_count,
+                           const float *d_radii, const float *d_weights, uint32_t seed, rt_ray *d_shadow_rays, unsigned char *d_asks,
+                           float *d_pending, float *d_reach, uint32_t *d_chosen, void *hip_stream);
+/* The settlement, per listed slot, alive or not (rt_path_advance may have ended the path since it connected): where d_asks[j] != 0,
+ * d_radiance[3j + c] = d_radiance[3j + c] + d_pending[3j + c] unless the slot is occluded by rt_light_terms' rule — d_shadow_hits[j]'s
+ * kind word is <= 1 and either d_reach[j] is negative or distance(d_shadow_rays[j].origin, d_shadow_hits[j].position) < d_reach[j]; an
+ * occluder at exactly the light's distance does not occlude, and a NaN makes the compare false.  The vertex is read from the slot's own
+ * shadow ray, not from d_hits.  d_shadow_hits NULL: nothing occludes.  Either way d_asks[j] = 0, so that the flags of all m slots are 0
+ * again when the next bounce connects.  d_paths is not read: it is taken so that the calls share their list arguments and checks. */
+int rt_path_settle_lights(const rt_path *d_paths, size_t m, const uint32_t *d_index, const uint32_t *d_count, unsigned char *d_asks,
+                          const rt_ray *d_shadow_rays, const rt_hit *d_shadow_hits, const float *d_reach, const float *d_pending,
+                          float *d_radiance, void *hip_stream);
+
 /* ---- distributed (stochastic / depth-of-field) pass ----------------------------
 
  * Replaces the par_iter_mut closure at src/main.rs:1131-1156 and the per-pixel RNG construction at

@@ -224,5 +224,6 @@ const char *rt_host_last_error(void);
 #include "rt_lobe_host.h"
 #include "rt_path_host.h"
 #include "rt_connect_host.h"
+#include "rt_light_connect_host.h"
 #include "rt_texture_host.h"
 #endif /* RT_HOST_H */
