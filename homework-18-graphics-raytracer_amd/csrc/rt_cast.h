@@ -166,18 +166,20 @@ static __device__ unsigned long long g_stage_totals[9]; /* per translation unit;
 
 /* Lane predicates of one cast as wave-wide masks (SGPR pairs), shared by all its segments */
 struct CastMasks {
-    unsigned long long keep_back, keep_front, ex_if_back, ex_if_front, filter_ok;
+    unsigned long long keep_back, keep_front, filter_ok;
+    bool filter_lane; /* this lane's bit of filter_ok, as the condition itself: shifting the mask down by the lane number costs four
+                       * vector instructions and a second SGPR pair held across the cast */
+    float dd;         /* dot(ray.d, ray.d), once per cast: every node's sphere test and a cone's test scale by it */
 };
 __device__ __forceinline__ CastMasks cast_masks(const Ray &ray, float filter_origin2) {
-    const bool ex_some = (ray.excl >> 31) != 0u;
-    const uint32_t ex_face = (ray.excl >> 29) & 3u;
     CastMasks m;
     m.keep_back = __builtin_amdgcn_ballot_w64(ray.mode != FACE_FRONT); /* backfaces survive culling */
     m.keep_front = __builtin_amdgcn_ballot_w64(ray.mode != FACE_BACK);
-    m.ex_if_back = __builtin_amdgcn_ballot_w64(ex_some && ex_face != FACE_FRONT);  /* Back or Both */
-    m.ex_if_front = __builtin_amdgcn_ballot_w64(ex_some && ex_face != FACE_BACK);  /* Front or Both */
+    /* (which face an excluded triangle is excluded for — main.rs:190-200 — the loop reads off ray.excl where a lane's exid matches) */
     /* lanes whose origin is inside the scene's neighbourhood may use the bounding-sphere rejections (rt_device_scene.h) */
-    m.filter_ok = __builtin_amdgcn_ballot_w64(dot(ray.o, ray.o) <= filter_origin2);
+    m.filter_lane = dot(ray.o, ray.o) <= filter_origin2;
+    m.filter_ok = __builtin_amdgcn_ballot_w64(m.filter_lane);
+    m.dd = dot(ray.d, ray.d);
     return m;
 }
 
@@ -214,8 +216,8 @@ __device__ __forceinline__ void cast_asm_triangles(const DevTri *tris_range, uin
                  : "+v"(best_t), "+v"(local_prim), "+v"(best_nd), "+v"(best_a0), "+v"(best_a1), "+v"(best_a2), "=&v"(r0), "=&v"(r1),
                    "=&v"(r2), "=&v"(r3), "=&v"(r4), "=&v"(r5), "=&v"(r6), "=&v"(r7), "=&v"(r8), "=&v"(r9), "=&v"(r10), "=&v"(r11),
                    "=&v"(r12), "=&v"(r13) RT_STAGE_OPERANDS
-                 : "v"(ray.o.x), "v"(ray.o.y), "v"(ray.o.z), "v"(ray.d.x), "v"(ray.d.y), "v"(ray.d.z), "v"(exid), "s"(m.keep_back),
-                   "s"(m.keep_front), "s"(m.ex_if_back), "s"(m.ex_if_front), "s"(ptr), "s"(n), "s"(m.filter_ok)
+                 : "v"(ray.o.x), "v"(ray.o.y), "v"(ray.o.z), "v"(ray.d.x), "v"(ray.d.y), "v"(ray.d.z), "v"(exid), "v"(ray.excl),
+                   "s"(m.keep_back), "s"(m.keep_front), "s"(ptr), "s"(n), "s"(m.filter_ok)
                  : RT_CAST_ASM_CLOBBERS);
 #ifdef RT_DIAG_STAGES
     if (__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) == 0u) { /* first active lane: the counts are wave-uniform */
@@ -255,8 +257,7 @@ static __device__ unsigned long long g_need_totals[RT_DIAG_NEED_WORDS];
 template <class Segment>
 __device__ __forceinline__ bool cluster_skippable_lane(const Segment &g, const Ray &ray, const CastMasks &m) {
     if (g.n_normals == 0u) return false;
-    const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-    if (((m.filter_ok >> lane) & 1ull) == 0ull) return false;
+    if (!m.filter_lane) return false;
     const V3 disp = v3(g.c[0], g.c[1], g.c[2]) - ray.o;
     const V3 cr = cross(disp, ray.d);
     const float dd = dot(ray.d, ray.d);
@@ -312,24 +313,24 @@ __device__ __forceinline__ NodeRec load_node(const DevSegment *node) {
     return r;
 }
 /* cluster_skippable_lane in two halves: the ray's line misses the node's sphere (and the ray may use the rejections at all) ... */
-__device__ __forceinline__ bool node_missed(const NodeRec &g, const Ray &ray, const CastMasks &m, uint32_t lane) {
+__device__ __forceinline__ bool node_missed(const NodeRec &g, const Ray &ray, const CastMasks &m) {
     const V3 disp = v3(__uint_as_float(g.h1.x), __uint_as_float(g.h1.y), __uint_as_float(g.h1.z)) - ray.o;
     const V3 cr = cross(disp, ray.d);
-    return ((m.filter_ok >> lane) & 1ull) != 0ull && dot(cr, cr) > __uint_as_float(g.h0.w) * dot(ray.d, ray.d);
+    return m.filter_lane && dot(cr, cr) > __uint_as_float(g.h0.w) * m.dd;
 }
-/* ... and it is not (nearly) parallel to a plane below the node: without a branch per normal */
-__device__ __forceinline__ bool node_steep(const NodeRec &g, const Ray &ray) {
+/* ... and it is not (nearly) parallel to a plane below the node.  The number of normals is the record's, i.e. wave-uniform: the
+ * branches below are scalar ones, and a node pays for the normals it has — six products and sums each — not for all eight slots
+ * (the reference scene's two clustered nodes have six and three; evaluated slot-blind they cost 100 vector instructions a visit,
+ * by count 58: profiles/r06_cast_fixed_part.txt).  `dd` is dot(ray.d, ray.d), which the caller has for the sphere test anyway. */
+__device__ __forceinline__ bool node_steep(const NodeRec &g, const Ray &ray, const float dd) {
     const uint32_t n_normals = g.h0.z;
-    const bool cone = n_normals == RT_SEGMENT_CONE;
     const float ad = dot(v3(g.nrm[0].x, g.nrm[0].y, g.nrm[0].z), ray.d);
-    bool steep = cone ? ad * ad >= g.nrm[0].w * dot(ray.d, ray.d) : rtdm::f_abs(ad) >= 1.0e-3f;
+    if (n_normals == RT_SEGMENT_CONE) return ad * ad >= g.nrm[0].w * dd;
+    bool steep = rtdm::f_abs(ad) >= 1.0e-3f;
 #pragma unroll
-    for (uint32_t q = 1; q < 4u; ++q)
-        steep = steep & ((rtdm::f_abs(dot(v3(g.nrm[q].x, g.nrm[q].y, g.nrm[q].z), ray.d)) >= 1.0e-3f) | (cone | (q >= n_normals)));
-    if (!cone && n_normals > 4u) {
-#pragma unroll
-        for (uint32_t q = 4u; q < RT_SEGMENT_NORMALS; ++q)
-            steep = steep & ((rtdm::f_abs(dot(v3(g.nrm[q].x, g.nrm[q].y, g.nrm[q].z), ray.d)) >= 1.0e-3f) | (q >= n_normals));
+    for (uint32_t q = 1; q < RT_SEGMENT_NORMALS; ++q) {
+        if (q >= n_normals) break;
+        steep = steep & (rtdm::f_abs(dot(v3(g.nrm[q].x, g.nrm[q].y, g.nrm[q].z), ray.d)) >= 1.0e-3f);
     }
     return steep;
 }
@@ -400,7 +401,6 @@ __device__ __forceinline__ CastResult cast_finish(const Scene &sc, const Ray &ra
 template <class Scene> /* KernelScene, by value or in the kernel-argument segment (constant address space) */
 __device__ __forceinline__ CastResult cast_asm(const Scene &sc, const Ray &ray) {
     const CastMasks m = cast_masks(ray, sc.filter_origin2);
-    const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
     TriBest best;
     best.t = rtdm::quiet_nan();
     best.prim = -1;
@@ -424,14 +424,14 @@ __device__ __forceinline__ CastResult cast_asm(const Scene &sc, const Ray &ray) 
             g_first = g.h0.x;
             g_count = g.h0.y;
             if (g.h0.z != 0u) { /* the normals only if every lane's line misses the sphere */
-                const bool missed = node_missed(g, ray, m, lane);
-                if (__builtin_amdgcn_ballot_w64(!missed) == 0ull) skip = __builtin_amdgcn_ballot_w64(!node_steep(g, ray)) == 0ull;
+                const bool missed = node_missed(g, ray, m);
+                if (__builtin_amdgcn_ballot_w64(!missed) == 0ull) skip = __builtin_amdgcn_ballot_w64(!node_steep(g, ray, m.dd)) == 0ull;
             }
             leaf = !skip && g_count != 0u;
             next_k = skip ? g.h1.w : k + 1u;
 #ifdef RT_DIAG_NEED
             if (leaf) {
-                const unsigned long long need = __builtin_amdgcn_ballot_w64(!(g.h0.z != 0u && node_missed(g, ray, m, lane) && node_steep(g, ray)));
+                const unsigned long long need = __builtin_amdgcn_ballot_w64(!(g.h0.z != 0u && node_missed(g, ray, m) && node_steep(g, ray, m.dd)));
                 if (diag_first) {
                     atomicAdd(&g_need_totals[1], (unsigned long long)g_count);
                     atomicAdd(&g_need_totals[2], (unsigned long long)g_count * (unsigned long long)__builtin_popcountll(diag_act));
@@ -573,7 +573,7 @@ __device__ __forceinline__ CastResult cast_pairs(const Scene &sc, const Ray &ray
     const uint32_t ex_prim = ray.excl & 0x1fffffffu;
     const uint32_t ray_bits = ((ex_some && ex_prim < sc.n_triangles) ? ex_prim : 0x07ffffffu) | (ray.mode != FACE_FRONT ? 1u << 27 : 0u) |
                               (ray.mode != FACE_BACK ? 1u << 28 : 0u) | ((ex_some && ex_face != FACE_FRONT) ? 1u << 29 : 0u) |
-                              ((ex_some && ex_face != FACE_BACK) ? 1u << 30 : 0u) | ((uint32_t)((m.filter_ok >> lane) & 1ull) << 31);
+                              ((ex_some && ex_face != FACE_BACK) ? 1u << 30 : 0u) | (m.filter_lane ? 1u << 31 : 0u);
     const uint32_t n_nodes = sc.n_segments;
     /* every leaf wave-uniformly — what cast_asm does — when some lanes of the wave are not here to help, and, the second time
      * round, when the first found a NaN distance */
@@ -617,7 +617,7 @@ __device__ __forceinline__ CastResult cast_pairs(const Scene &sc, const Ray &ray
                 const u32x4 h1 = g.h1;
                 need = active;
                 if (n_normals != 0u) { /* cluster_skippable_lane */
-                    const bool missed = node_missed(g, ray, m, lane), steep = node_steep(g, ray);
+                    const bool missed = node_missed(g, ray, m), steep = node_steep(g, ray, m.dd);
                     need = active && !(missed && steep);
                 }
                 needing = __builtin_amdgcn_ballot_w64(need);

@@ -31,7 +31,7 @@ only consumed by SALU (interlocked) and branches use SCC, never VCCZ/EXECZ.
 # backface flag) and the three signed areas (the barycentric numerators), exactly the values the accept was decided on
 OUT = {"best_t": 0, "best_prim": 1, "best_nd": 2, "best_a0": 3, "best_a1": 4, "best_a2": 5}
 TEMPS = {f"r{k}": 6 + k for k in range(14)}
-_IN_NAMES = ["ox", "oy", "oz", "dx", "dy", "dz", "exid", "keep_back", "keep_front", "ex_if_back", "ex_if_front", "ptr", "n", "filter_ok"]
+_IN_NAMES = ["ox", "oy", "oz", "dx", "dy", "dz", "exid", "excl", "keep_back", "keep_front", "ptr", "n", "filter_ok"]
 IN = {name: 20 + k for k, name in enumerate(_IN_NAMES)}
 
 import sys
@@ -153,8 +153,12 @@ def test(buf, label_next):
         L += [f"v_mul_f32 {p[k]}, {d[k]}, {t}", f"v_add_f32 {p[k]}, {o[k]}, {p[k]}"]
     # ---- this triangle (leaders fall in; followers enter here with the plane's registers) ----
     L += [f".Lcast_tri{buf}_%=:"]
-    # exclusion (main.rs:190-200): same primitive and (bf ? ex_if_back : ex_if_front).  Almost every triangle is excluded
-    # by no lane at all: test that first and keep the mask algebra out of line.
+    # exclusion (main.rs:190-200): same primitive and (bf ? face != Front : face != Back).  Almost every triangle is excluded
+    # by no lane at all: test that first and keep the mask algebra out of line.  The face comes out of the ray's packed
+    # exclusion word (bits 29..30, rt_cast.h) there and then: a lane whose exid equals a triangle index HAS an exclusion (exid
+    # is 0xffffffff otherwise, and no index is), so "Some" need not be tested again, and the two masks that used to arrive as
+    # SGPR pairs — made at the head of every cast, parked in VGPR lanes across the node walk, read back for every call — are
+    # three vector instructions on the one triangle per cast that somebody excludes.
     # nearest (main.rs:229-233): a lane that already holds a nearer hit cannot accept this triangle whatever its areas are
     # (one more `continue`; the order of the rejections is immaterial); best_t = NaN while None, equal t passes (the later
     # primitive wins a tie)
@@ -166,9 +170,12 @@ def test(buf, label_next):
           f"s_cbranch_scc0 {label_next}"]
     SLOW[buf] = [f".Lcast_excl{buf}_%=:",
                  f"s_and_b64 {S_ALIVE}, {S_PLANE}, vcc",
+                 f"v_bfe_u32 {r[3]}, {op('excl')}, 29, 2",  # r3: a temporary of the divide, not yet the bounding-sphere test's
                  f"v_cmp_lt_f32 vcc, 0, {nd}",
-                 f"s_and_b64 {S_T1}, vcc, {op('ex_if_back')}", f"s_and_b64 {S_T1}, {S_T1}, {S_T2}", f"s_andn2_b64 {S_ALIVE}, {S_ALIVE}, {S_T1}",
-                 f"s_andn2_b64 {S_T1}, {op('ex_if_front')}, vcc", f"s_and_b64 {S_T1}, {S_T1}, {S_T2}", f"s_andn2_b64 {S_ALIVE}, {S_ALIVE}, {S_T1}",
+                 f"v_cmp_ne_u32_e64 {S_T1}, 0, {r[3]}",  # excluded if back-facing: Back or Both
+                 f"s_and_b64 {S_T1}, {S_T1}, vcc", f"s_and_b64 {S_T1}, {S_T1}, {S_T2}", f"s_andn2_b64 {S_ALIVE}, {S_ALIVE}, {S_T1}",
+                 f"v_cmp_ne_u32_e64 {S_T1}, 1, {r[3]}",  # excluded if front-facing: Front or Both
+                 f"s_andn2_b64 {S_T1}, {S_T1}, vcc", f"s_and_b64 {S_T1}, {S_T1}, {S_T2}", f"s_andn2_b64 {S_ALIVE}, {S_ALIVE}, {S_T1}",
                  f"s_branch .Lcast_excl{buf}_back_%=",
                  # A triangle on the previous triangle's plane.  Bit 30: its n and d equal the predecessor's only up to the
                  # signs of zero components ((-0, 1, 0) after (0, 1, 0): the two halves of most square()s).  Every product and sum
