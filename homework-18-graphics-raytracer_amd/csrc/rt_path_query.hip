@@ -9,7 +9,9 @@
  *   rt::path_resolve_kernel   per root: the samples' radiance in ascending order, their mean added to the root's slot
  *
  * The arithmetic is rt_path.h's, shared with librt_host.so, and that header calls rt_lobe.h's sampler and rt_shade.h's terms as
- * lobe_rays_kernel and probe_surfaces_kernel call them: the record, the sampling normal and the shadow ray are rt_light_record.h's.
+ * lobe_rays_kernel and probe_surfaces_kernel call them: the record and the sampling normal are rt_light_record.h's.  The ray a survivor
+ * goes on along is no shadow ray: it looks for the path's next vertex, the nearest surface whichever way it faces, so it is cast with
+ * face Both and the vertex's own primitive excluded for both faces (store_continuation_ray); Back is an occlusion query's face.
  * One listed path (or root) per lane, 256 lanes per workgroup; the path record moves as two 16-byte accesses, the hit and the rays as
  * dwords.  No LDS, no cast, no workspace, no atomics.  The C entry points of the block are at the end of the file.
  */
@@ -34,6 +36,15 @@ __global__ __launch_bounds__(RT_PATH_THREADS) void path_begin_kernel(const uint6
     out[0] = make_uint4(__float_as_uint(p.beta[0]), __float_as_uint(p.beta[1]), __float_as_uint(p.beta[2]), __float_as_uint(p.pdf));
     out[1] = make_uint4(p.root, p.id, p.bounce, p.flags);
     store_v3(radiance, k, v3(0.0f, 0.0f, 0.0f));
+}
+
+/* the ray a path goes on along: rt_light_record.h's shadow ray — from the hit along `dir`, the hit's own primitive excluded — with its
+ * two face words Both in the place of Back, or all-zero words for a path that ended */
+__device__ __forceinline__ void store_continuation_ray(rt_ray *__restrict__ ray, const LightRecord &r, const V3 dir, const bool lives) {
+    if (lives)
+        store_ray(ray, r.h.g.pos, dir, FACE_BOTH, 1u, r.h.kind, r.h.index, FACE_BOTH);
+    else
+        store_ray(ray, v3(0.0f, 0.0f, 0.0f), v3(0.0f, 0.0f, 0.0f), 0u, 0u, 0u, 0u, 0u);
 }
 
 /* hits is read (the record's own slot) and, for a path that ends, written: not restrict, not const */
@@ -76,7 +87,7 @@ __global__ __launch_bounds__(RT_PATH_THREADS) void path_advance_kernel(const Ker
     record[0] = make_uint4(__float_as_uint(p.beta[0]), __float_as_uint(p.beta[1]), __float_as_uint(p.beta[2]), __float_as_uint(p.pdf));
     record[1] = make_uint4(p.root, p.id, p.bounce, p.flags);
     alive[j] = lives ? 1 : 0;
-    store_shadow_ray(next_rays + j, r, dir, lives);
+    store_continuation_ray(next_rays + j, r, dir, lives);
     if (!lives) { /* "no hit", as the tree loop presets it: a later rt_shade_hits spends nothing here, a later advance escapes at once */
         uint32_t *const preset = reinterpret_cast<uint32_t *>(hits + j);
 #pragma unroll

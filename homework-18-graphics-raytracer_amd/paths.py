@@ -85,7 +85,9 @@ def advance(scene: Scene, paths, hits, incoming, radiance, emitted=None, index=N
     vertex ends it (ESCAPED); ``last`` ends the rest (flags 0); else one direction from the hit's lobes (lobes.rays' for spp 1, UNIFORM,
     the path's id and sample, seed + 0x9e3779b9 * bounce), beta *= (diffuse (1 - shiness) + specular shiness) / pdf, DARK where that
     is not positive, and from bounce ``rr_start`` on Russian roulette with survival max(beta) clamped to [``rr_floor``, 1] (ROULETTE;
-    NO_ROULETTE switches it off).  Returns (rays, alive): ``out_rays`` (M, 11) int32, the next ray of a survivor and zero words for a
+    NO_ROULETTE switches it off).  Returns (rays, alive): ``out_rays`` (M, 11) int32, the continuation ray of a survivor — from the
+    vertex along the direction drawn, face BOTH, the vertex's own primitive excluded for both faces: its cast finds the path's next
+    vertex, the nearest surface whichever way it faces (lobes.rays' ray, face BACK, is an occlusion query) — and zero words for a
     path that ended, and ``out_alive`` (M,) uint8.  ``paths`` and ``radiance`` are updated in place, and so is ``hits``: a path that
     ended leaves a "no hit" record.  Slots that are not listed or not alive are not touched in any of them."""
     records = _hit_records(hits)
@@ -640,7 +642,8 @@ def trace_paths(scene: Scene, hits, incoming, spp: int, max_bounces: int, env=No
       begin -> the spp copies of the roots' hits and rays
       per bounce b = 0 .. max_bounces:  shade_hits (all slots) -> environment.lookup (the misses; only with env) ->
                   advance(list_b, last = (b == max_bounces)) -> select_records(alive) -> cast_rays_indexed(next rays, list_b+1);
-                  the next rays are the next bounce's incoming rays
+                  the next rays are the next bounce's incoming rays, and what they hit — the nearest surface, front or back: they
+                  are cast with face BOTH — the next bounce's vertices
       resolve
     Bounce b draws with seed + 0x9e3779b9 * b; roulette starts at bounce ``rr_start`` (NO_ROULETTE: never).  ``open_casts``:
     shade_hits_by_light in the place of shade_hits, so that every cast of the loop is a cast_rays_indexed (the same bits).  The loop

@@ -781,7 +781,8 @@ int rt_mis_weigh(size_t count, const float *d_pdf_own, uint32_t n_own, const flo
  * workgroup, allocates nothing, uses no workspace, no atomics, and may be captured into a HIP graph at once.  All arithmetic is
  * csrc/rt_path.h's, single f32 and u32 operations in the order given here, none fused, shared by both libraries.
  * Not covered: refraction lobes inside the step (the "transmission queries" block takes them as a branch beside it); next-event estimation of the sky inside the step (rt_path.pdf is kept for it); _host and rt_multi_*
- * forms (rt_path_*_cpu of include/rt_path_host.h are the CPU forms); paths inside rt_render_*. */
+ * forms (rt_path_*_cpu of include/rt_path_host.h are the CPU forms); paths inside rt_render_*; the inside of the sphere a path leaves
+ * (the continuation ray excludes the vertex's primitive for both faces, so a path cannot meet the far, inner side of its own sphere). */
 #define RT_PATH_ALIVE 1u     /* the path goes on */
 #define RT_PATH_SPECULAR 2u  /* the direction last drawn came from the specular lobe */
 #define RT_PATH_ESCAPED 4u   /* ended on a record that is "no hit" */
@@ -822,7 +823,11 @@ int rt_path_begin(size_t n, uint32_t spp, const uint32_t *d_ids, rt_path *d_path
  *                with the sample's seed_h, a stream apart from u_0, u_1 and the lobe's u_2 (0x27d4eb2fu).  u_3 < q: beta' = beta' / q
  *                per channel; else the path ends with RT_PATH_ROULETTE.  rr_start 0xffffffff: no roulette
  *   write        a survivor: beta = beta', pdf, bounce + 1, flags RT_PATH_ALIVE | RT_PATH_SPECULAR as drawn, d_alive[j] = 1 and
- *                d_next_rays[j] = rt_lobe_rays' shadow ray.  A path that ended: its flags alone change in the record, d_alive[j] = 0,
+ *                d_next_rays[j] = the continuation ray: rt_lobe_rays' shadow ray word for word — origin the vertex's position, the
+ *                direction drawn — but for its two face words: face Both, exclusion { hit.kind, hit.index, Both }.  It looks for
+ *                the path's next vertex, the nearest surface whichever way it faces; a Back ray is an occlusion query, answered by
+ *                back faces only (main.rs:185), and would land on the far, inner side of a closed object and pass an open
+ *                surface met from its front.  A path that ended: its flags alone change in the record, d_alive[j] = 0,
  *                d_next_rays[j] all-zero words and d_hits[j] the "no hit" record (kind RT_HIT_NONE, every other word 0), so that
  *                a later rt_shade_hits over all slots spends nothing on it and a later advance cannot revive it
  * Slots that are not listed, and listed ones that are not alive, are not touched.  normal_kind chooses the N the direction is drawn

@@ -24,6 +24,7 @@ BATCHES = [1, 63, 64, 65, 257]
 OFF = P.NO_ROULETTE
 POISON, POISON_BYTE = 0x5A5A5A5A, 0x5A
 NO_HIT = np.array([0xFFFFFFFF] + [0] * 12, dtype=np.uint32)
+BOTH = 2  # the face of a continuation ray and of its exclusion: words 6 and 10 of the record
 
 
 def ids_of(n):
@@ -92,8 +93,9 @@ def same_paths(got, want, what):
 
 
 def want_rays_and_hits(hits, before, after, dirs, alive, poison_dirs):
-    """the next rays restated from the CPU form's directions, and the hit records: a path that ended in this call leaves zero words and
-    a "no hit" record; a slot that was not touched keeps the poison and its hit"""
+    """the next rays restated from the CPU form's directions — continuation rays: face Both, the vertex's primitive excluded for both
+    faces — and the hit records: a path that ended in this call leaves zero words and a "no hit" record; a slot that was not touched
+    keeps the poison and its hit"""
     n = hits.shape[0]
     touched = (alive != POISON_BYTE)
     rays = np.full((n, 11), POISON, dtype=np.uint32)
@@ -101,7 +103,7 @@ def want_rays_and_hits(hits, before, after, dirs, alive, poison_dirs):
     rays[touched] = 0
     rays[live, 0:3] = hits[live, 3:6]
     rays[live, 3:6] = dirs[live].view(np.uint32)
-    rays[live, 6], rays[live, 7], rays[live, 10] = 1, 1, 1
+    rays[live, 6], rays[live, 7], rays[live, 10] = BOTH, 1, BOTH
     rays[live, 8], rays[live, 9] = hits[live, 0], hits[live, 1]
     want_hits = hits.copy()
     want_hits[touched & ~live] = NO_HIT
@@ -208,7 +210,8 @@ def test_the_three_calls_are_their_cpu_forms(ref, n):
 @pytest.mark.parametrize("n", BATCHES)
 def test_one_advance_is_the_five_calls_it_fuses(ref, n):
     """material_hits -> lobes.rays(spp 1, UNIFORM, the bounce's seed) -> probe_surfaces -> mis_weigh(divide_by_own) -> environment.fold
-    (spp 1, into zeros), on the device, against one advance without roulette: bit for bit, -0 as +0"""
+    (spp 1, into zeros), on the device, against one advance without roulette: bit for bit, -0 as +0; the ray is lobes.rays' but for its
+    two face words, Both where the shadow ray says Back"""
     torch = torch_device()
     rows = slice(MIDDLE, MIDDLE + n)
     rng = np.random.default_rng(n + 1)
@@ -233,7 +236,9 @@ def test_one_advance_is_the_five_calls_it_fuses(ref, n):
         assert_same(PS.no_negative_zero(got_paths["beta"][lives]), PS.no_negative_zero(beta[lives]), "beta: " + what)
         assert_same(got_paths["pdf"][lives], host(pdf_t)[lives], "pdf: " + what)
         assert_same(got_paths["flags"][lives], (P.ALIVE | np.where(lobe[lives] != 0, P.SPECULAR, 0)).astype(np.uint32), "lobe: " + what)
-        assert_same(got_rays[lives], u32(rays_t)[lives], "the shadow ray: " + what)
+        want_rays = u32(rays_t).copy()  # rt_lobe_rays' shadow ray with exactly its two face words replaced
+        want_rays[:, 6] = want_rays[:, 10] = BOTH
+        assert_same(got_rays[lives], want_rays[lives], "the continuation ray: " + what)
         assert not got_rays[~lives].any() and (got_paths["bounce"][lives] == bounce + 1).all()
         assert (got_paths["flags"][~lives] == np.where(ref.valid[rows][~lives], P.DARK, P.ESCAPED)).all()
         assert n < 63 or lives.any()
