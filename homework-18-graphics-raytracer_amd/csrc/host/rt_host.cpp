@@ -71,6 +71,17 @@ static int cpu_query(const char *who, const Args &a, Run run) {
 /* the loop of a query whose call() is an Op */
 static const auto each_call = [](const auto &a) { each(a.call()); };
 
+/* The walk of a listed form of the path loop (the path, transmission, connection and light-connection queries): body(j) for every slot
+ * the list names, in the list's order; an index beyond the slots names nothing, as in rt_cast_rays_indexed. */
+template <class Body>
+static void each_listed(const uint32_t *index, const uint32_t *count, size_t m, Body body) {
+    const uint32_t listed = rt::path_listed(index, count, (uint32_t)m);
+    for (uint32_t e = 0; e < listed; ++e) {
+        const uint32_t j = index ? index[e] : e;
+        if (j < m) body(j);
+    }
+}
+
 extern "C" {
 
 const char *rt_host_last_error(void) { return g_host_error.c_str(); }
@@ -860,6 +871,32 @@ int rt_mis_weigh_cpu(size_t count, const float *pdf_own, uint32_t n_own, const f
 
 /* ---- path queries: the record, the step and the resolve on the CPU (include/rt_amd.h "path queries"; the arithmetic is rt_path.h's, shared with the device) ---- */
 
+/* What the listed forms of the path loop share — the path, transmission, connection and light-connection queries below: the count's
+ * limit, the material of a surface record and the store into a plane of three floats; the walk is each_listed, above the C region. */
+static int listed_count(const char *who, size_t m) {
+    if ((uint64_t)m >= (1ull << 32)) return fail(RT_ERR_UNSUPPORTED, std::string(who) + "2^32 records or more (checked first; query them in several calls)");
+    return RT_OK;
+}
+
+static rt::Mat mat_of(const rt_surface &s) {
+    rt::Mat mat;
+    mat.normal = rt::v3p(s.normal);
+    mat.diffuse = rt::v3p(s.diffuse_color);
+    mat.specular = rt::v3p(s.specular_color);
+    mat.shiness = s.shiness;
+    mat.smoothness = s.smoothness;
+    mat.transparency = s.transparency;
+    mat.refraction_index = s.refraction_index;
+    mat.opaque_decay = s.opaque_decay;
+    return mat;
+}
+
+static void put_v3(float *plane, size_t j, V3 v) {
+    plane[3u * j] = v.x;
+    plane[3u * j + 1u] = v.y;
+    plane[3u * j + 2u] = v.z;
+}
+
 int rt_path_begin_cpu(size_t n, uint32_t spp, const uint32_t *ids, rt_path *paths, float *radiance) {
     const char *const who = "rt_path_begin_cpu: ";
     if (const int rc = hemisphere_counts(who, n, spp)) return rc;
@@ -879,38 +916,25 @@ int rt_path_advance_cpu(const rt_surface *surfaces, const float *normals, const 
                         const uint32_t *count, const float *emitted, uint32_t seed, uint32_t rr_start, float rr_floor, int last, float *radiance, float *dirs,
                         unsigned char *alive) {
     const char *const who = "rt_path_advance_cpu: ";
-    if ((uint64_t)m >= (1ull << 32)) return fail(RT_ERR_UNSUPPORTED, std::string(who) + "2^32 records or more (checked first; query them in several calls)");
+    if (const int rc = listed_count(who, m)) return rc;
     if (m == 0) return RT_OK;
     if (!surfaces || !view || !paths || (index && !count) || !radiance || !dirs || !alive)
         return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + "null surface, view, path, count (with an index), radiance, direction or flag pointer");
     if (const char *bad = rt::path_limits(RT_HEMISPHERE_SHADING, rr_floor)) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + bad);
     const rt::PathStep step = {seed, rr_start, rr_floor, last != 0};
-    const uint32_t listed = rt::path_listed(index, count, (uint32_t)m);
-    for (uint32_t e = 0; e < listed; ++e) {
-        const uint32_t j = index ? index[e] : e;
-        if (j >= m) continue;
+    each_listed(index, count, m, [&](uint32_t j) {
         rt_path &p = paths[j];
-        if ((p.flags & RT_PATH_ALIVE) == 0u) continue;
+        if ((p.flags & RT_PATH_ALIVE) == 0u) return;
         if (emitted)
             for (uint32_t c = 0; c < 3u; ++c) radiance[3u * j + c] = rt::path_deposit(radiance[3u * j + c], p.beta[c], emitted[3u * j + c]);
         const rt_surface &s = surfaces[j];
-        rt::Mat mat;
-        mat.normal = rt::v3p(s.normal);
-        mat.diffuse = rt::v3p(s.diffuse_color);
-        mat.specular = rt::v3p(s.specular_color);
-        mat.shiness = s.shiness;
-        mat.smoothness = s.smoothness;
-        mat.transparency = s.transparency;
-        mat.refraction_index = s.refraction_index;
-        mat.opaque_decay = s.opaque_decay;
         const V3 shading_n = rt::v3p(s.shading_normal);
         V3 dir;
-        const bool lives = rt::path_advance_record(p, s.valid != 0u, mat, shading_n, normals ? rt::v3p(normals + 3u * j) : shading_n, rt::v3p(view + 3u * j), step, &dir);
-        dirs[3u * j] = dir.x;
-        dirs[3u * j + 1u] = dir.y;
-        dirs[3u * j + 2u] = dir.z;
+        const bool lives = rt::path_advance_record(p, s.valid != 0u, mat_of(s), shading_n, normals ? rt::v3p(normals + 3u * j) : shading_n, rt::v3p(view + 3u * j),
+                                                   step, &dir);
+        put_v3(dirs, j, dir);
         alive[j] = lives ? 1 : 0;
-    }
+    });
     return RT_OK;
 }
 
@@ -930,15 +954,12 @@ int rt_path_branch_cpu(const rt_surface *surfaces, const rt_hit *hits, const rt_
                        const uint32_t *count, uint32_t seed, int last, unsigned char *lobe, unsigned char *transmit, rt_ray *walk_rays, uint32_t *kind,
                        float *travel, uint32_t *casts, unsigned char *walk_flags) {
     const char *const who = "rt_path_branch_cpu: ";
-    if ((uint64_t)m >= (1ull << 32)) return fail(RT_ERR_UNSUPPORTED, std::string(who) + "2^32 records or more (checked first; query them in several calls)");
+    if (const int rc = listed_count(who, m)) return rc;
     if (m == 0) return RT_OK;
     if (!surfaces || !hits || !incoming || !paths || (index && !count) || !lobe || !transmit || !walk_rays || !kind || !travel || !casts || !walk_flags)
         return fail(RT_ERR_INVALID_ARGUMENT,
                     std::string(who) + "null surface, hit, incoming-ray, path, count (with an index), lobe, transmit, walk-ray, kind, travel, cast-count or walk-flag pointer");
-    const uint32_t listed = rt::path_listed(index, count, (uint32_t)m);
-    for (uint32_t e = 0; e < listed; ++e) {
-        const uint32_t j = index ? index[e] : e;
-        if (j >= m) continue;
+    each_listed(index, count, m, [&](uint32_t j) {
         rt_path &p = paths[j];
         bool transmits = false, lobes = false;
         uint32_t result = RT_HIT_NONE;
@@ -964,7 +985,7 @@ int rt_path_branch_cpu(const rt_surface *surfaces, const rt_hit *hits, const rt_
         travel[j] = 0.0f;
         casts[j] = 0u;
         walk_flags[j] = result == RT_REFR_WALKING ? 1 : 0;
-    }
+    });
     return RT_OK;
 }
 
@@ -972,41 +993,33 @@ int rt_path_transmit_cpu(const rt_surface *surfaces, rt_path *paths, size_t m, c
                          const rt_ray *escape, uint32_t seed, uint32_t rr_start, float rr_floor, rt_ray *next_rays, unsigned char *alive,
                          unsigned char *walk_flags) {
     const char *const who = "rt_path_transmit_cpu: ";
-    if ((uint64_t)m >= (1ull << 32)) return fail(RT_ERR_UNSUPPORTED, std::string(who) + "2^32 records or more (checked first; query them in several calls)");
+    if (const int rc = listed_count(who, m)) return rc;
     if (m == 0) return RT_OK;
     if (!surfaces || !paths || (index && !count) || !kind || !travel || !escape || !next_rays || !alive || !walk_flags)
         return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + "null surface, path, count (with an index), kind, travel, escape-ray, ray, flag or walk-flag pointer");
     if (const char *bad = rt::path_limits(RT_HEMISPHERE_SHADING, rr_floor)) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + bad);
     const rt::PathStep step = {seed, rr_start, rr_floor, false};
-    const uint32_t listed = rt::path_listed(index, count, (uint32_t)m);
-    for (uint32_t e = 0; e < listed; ++e) {
-        const uint32_t j = index ? index[e] : e;
-        if (j >= m) continue;
+    each_listed(index, count, m, [&](uint32_t j) {
         const uint32_t walk = kind[j];
         kind[j] = RT_HIT_NONE;
         walk_flags[j] = 0;
         rt_path &p = paths[j];
-        if ((p.flags & RT_PATH_ALIVE) == 0u) continue;
+        if ((p.flags & RT_PATH_ALIVE) == 0u) return;
         const bool valid = surfaces[j].valid != 0u;
         const bool lives = rt::path_transmit_record(p, walk, valid, valid ? surfaces[j].opaque_decay : 0.0f, travel[j], step);
         alive[j] = lives ? 1 : 0;
         next_rays[j] = lives ? escape[j] : rt::no_ray_record();
-    }
+    });
     return RT_OK;
 }
 
 /* ---- connection queries: the connection, the settlement and the escape weight on the CPU (include/rt_amd.h "connection queries"; the arithmetic is rt_connect.h's, shared with the device) ---- */
 
-static int connect_count(const char *who, size_t m) {
-    if ((uint64_t)m >= (1ull << 32)) return fail(RT_ERR_UNSUPPORTED, std::string(who) + "2^32 records or more (checked first; query them in several calls)");
-    return RT_OK;
-}
-
 int rt_path_connect_cpu(const rt_surface *surfaces, const float *normals, const float *view, const rt_environment *env, const void *table,
                         const rt_path *paths, size_t m, const uint32_t *index, const uint32_t *count, uint32_t seed, uint32_t heuristic, int last,
                         float *dirs, unsigned char *asks, float *pending) {
     const char *const who = "rt_path_connect_cpu: ";
-    if (const int rc = connect_count(who, m)) return rc;
+    if (const int rc = listed_count(who, m)) return rc;
     if (const int rc = environment_ok(who, env)) return rc;
     if (m == 0) return RT_OK;
     if (!surfaces || !view || !table || !paths || (index && !count) || !dirs || !asks || !pending)
@@ -1014,72 +1027,47 @@ int rt_path_connect_cpu(const rt_surface *surfaces, const float *normals, const 
     if (const char *bad = rt::connect_limits(RT_HEMISPHERE_SHADING, heuristic)) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + bad);
     const rt::PathConnect step = {seed, heuristic, last != 0};
     const rt::EnvTable t = rt::env_table_view(*env, table);
-    const uint32_t listed = rt::path_listed(index, count, (uint32_t)m);
-    for (uint32_t e = 0; e < listed; ++e) {
-        const uint32_t j = index ? index[e] : e;
-        if (j >= m) continue;
+    each_listed(index, count, m, [&](uint32_t j) {
         const rt_path &p = paths[j];
-        if ((p.flags & RT_PATH_ALIVE) == 0u) continue;
+        if ((p.flags & RT_PATH_ALIVE) == 0u) return;
         const rt_surface &s = surfaces[j];
-        rt::Mat mat;
-        mat.normal = rt::v3p(s.normal);
-        mat.diffuse = rt::v3p(s.diffuse_color);
-        mat.specular = rt::v3p(s.specular_color);
-        mat.shiness = s.shiness;
-        mat.smoothness = s.smoothness;
-        mat.transparency = s.transparency;
-        mat.refraction_index = s.refraction_index;
-        mat.opaque_decay = s.opaque_decay;
         const V3 shading_n = rt::v3p(s.shading_normal);
-        const rt::Connection c = rt::path_connect_record(p, s.valid != 0u, mat, shading_n, normals ? rt::v3p(normals + 3u * j) : shading_n, rt::v3p(view + 3u * j),
-                                                         *env, t, step);
-        dirs[3u * j] = c.dir.x;
-        dirs[3u * j + 1u] = c.dir.y;
-        dirs[3u * j + 2u] = c.dir.z;
+        const rt::Connection c = rt::path_connect_record(p, s.valid != 0u, mat_of(s), shading_n, normals ? rt::v3p(normals + 3u * j) : shading_n,
+                                                         rt::v3p(view + 3u * j), *env, t, step);
+        put_v3(dirs, j, c.dir);
         asks[j] = c.ask ? 1 : 0;
-        if (c.ask) {
-            pending[3u * j] = c.pending.x;
-            pending[3u * j + 1u] = c.pending.y;
-            pending[3u * j + 2u] = c.pending.z;
-        }
-    }
+        if (c.ask) put_v3(pending, j, c.pending);
+    });
     return RT_OK;
 }
 
 int rt_path_settle_cpu(const rt_path *paths, size_t m, const uint32_t *index, const uint32_t *count, unsigned char *asks, const rt_hit *shadow_hits,
                        const float *pending, float *radiance) {
     const char *const who = "rt_path_settle_cpu: ";
-    if (const int rc = connect_count(who, m)) return rc;
+    if (const int rc = listed_count(who, m)) return rc;
     if (m == 0) return RT_OK;
     if (!paths || (index && !count) || !asks || !pending || !radiance)
         return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + "null path, count (with an index), flag, pending or radiance pointer");
-    const uint32_t listed = rt::path_listed(index, count, (uint32_t)m);
-    for (uint32_t e = 0; e < listed; ++e) {
-        const uint32_t j = index ? index[e] : e;
-        if (j < m) rt::path_settle_record(j, asks, reinterpret_cast<const uint32_t *>(shadow_hits), pending, radiance);
-    }
+    each_listed(index, count, m, [&](uint32_t j) { rt::path_settle_record(j, asks, reinterpret_cast<const uint32_t *>(shadow_hits), pending, radiance); });
     return RT_OK;
 }
 
 int rt_path_weigh_escape_cpu(const rt_environment *env, const void *table, const rt_path *paths, size_t m, const uint32_t *index, const uint32_t *count,
                              const rt_hit *hits, const rt_ray *incoming, uint32_t heuristic, float *emitted) {
     const char *const who = "rt_path_weigh_escape_cpu: ";
-    if (const int rc = connect_count(who, m)) return rc;
+    if (const int rc = listed_count(who, m)) return rc;
     if (const int rc = environment_ok(who, env)) return rc;
     if (m == 0) return RT_OK;
     if (!table || !paths || (index && !count) || !hits || !incoming || !emitted)
         return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + "null table, path, count (with an index), hit, incoming-ray or emitted pointer");
     if (const char *bad = rt::mis_limits(heuristic)) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + bad);
     const rt::EnvTable t = rt::env_table_view(*env, table);
-    const uint32_t listed = rt::path_listed(index, count, (uint32_t)m);
-    for (uint32_t e = 0; e < listed; ++e) {
-        const uint32_t j = index ? index[e] : e;
-        if (j >= m) continue;
+    each_listed(index, count, m, [&](uint32_t j) {
         const rt_path &p = paths[j];
-        if (!rt::path_escape_weighed(p.flags, hits[j].kind, p.pdf, t)) continue;
+        if (!rt::path_escape_weighed(p.flags, hits[j].kind, p.pdf, t)) return;
         const float w = rt::path_escape_weight(*env, t, heuristic, p.pdf, rt::v3p(incoming[j].direction));
         for (uint32_t c = 0; c < 3u; ++c) emitted[3u * j + c] = emitted[3u * j + c] * w;
-    }
+    });
     return RT_OK;
 }
 
@@ -1090,7 +1078,7 @@ int rt_path_connect_lights_cpu(const rt_surface *surfaces, const float *position
                                const float *radii, const float *weights, uint32_t seed, float *dirs, unsigned char *asks, float *pending, float *reach,
                                uint32_t *chosen) {
     const char *const who = "rt_path_connect_lights_cpu: ";
-    if (const int rc = connect_count(who, m)) return rc;
+    if (const int rc = listed_count(who, m)) return rc;
     if (m == 0 || light_count == 0) return RT_OK;
     if (!surfaces || !positions || !view || !lights || !paths || (index && !count) || !dirs || !asks || !pending || !reach)
         return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + "null surface, position, view, light, path, count (with an index), direction, flag, pending or reach pointer");
@@ -1101,53 +1089,33 @@ int rt_path_connect_lights_cpu(const rt_surface *surfaces, const float *position
         if (aux) light_aux[i].cos_in = aux[2u * i], light_aux[i].cos_out = aux[2u * i + 1u];
     }
     const rt::LightConnect step = {seed, light_first, light_count, radii, weights};
-    const uint32_t listed = rt::path_listed(index, count, (uint32_t)m);
-    for (uint32_t e = 0; e < listed; ++e) {
-        const uint32_t j = index ? index[e] : e;
-        if (j >= m) continue;
+    each_listed(index, count, m, [&](uint32_t j) {
         const rt_path &p = paths[j];
-        if ((p.flags & RT_PATH_ALIVE) == 0u) continue;
+        if ((p.flags & RT_PATH_ALIVE) == 0u) return;
         const rt_surface &s = surfaces[j];
-        rt::Mat mat;
-        mat.normal = rt::v3p(s.normal);
-        mat.diffuse = rt::v3p(s.diffuse_color);
-        mat.specular = rt::v3p(s.specular_color);
-        mat.shiness = s.shiness;
-        mat.smoothness = s.smoothness;
-        mat.transparency = s.transparency;
-        mat.refraction_index = s.refraction_index;
-        mat.opaque_decay = s.opaque_decay;
-        const rt::LightConnection c = rt::light_connect_record(p, s.valid != 0u, mat, rt::v3p(s.shading_normal), rt::v3p(positions + 3u * (size_t)j),
+        const rt::LightConnection c = rt::light_connect_record(p, s.valid != 0u, mat_of(s), rt::v3p(s.shading_normal), rt::v3p(positions + 3u * (size_t)j),
                                                                rt::v3p(view + 3u * (size_t)j), lights, light_aux.data(), step);
-        dirs[3u * (size_t)j] = c.dir.x;
-        dirs[3u * (size_t)j + 1u] = c.dir.y;
-        dirs[3u * (size_t)j + 2u] = c.dir.z;
+        put_v3(dirs, j, c.dir);
         asks[j] = c.ask ? 1 : 0;
         if (chosen) chosen[j] = c.chosen;
         if (c.ask) {
-            pending[3u * (size_t)j] = c.pending.x;
-            pending[3u * (size_t)j + 1u] = c.pending.y;
-            pending[3u * (size_t)j + 2u] = c.pending.z;
+            put_v3(pending, j, c.pending);
             reach[j] = c.reach;
         }
-    }
+    });
     return RT_OK;
 }
 
 int rt_path_settle_lights_cpu(const rt_path *paths, size_t m, const uint32_t *index, const uint32_t *count, unsigned char *asks, const rt_ray *shadow_rays,
                               const rt_hit *shadow_hits, const float *reach, const float *pending, float *radiance) {
     const char *const who = "rt_path_settle_lights_cpu: ";
-    if (const int rc = connect_count(who, m)) return rc;
+    if (const int rc = listed_count(who, m)) return rc;
     if (m == 0) return RT_OK;
     if (!paths || (index && !count) || !asks || !shadow_rays || !reach || !pending || !radiance)
         return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + "null path, count (with an index), flag, ray, reach, pending or radiance pointer");
-    const uint32_t listed = rt::path_listed(index, count, (uint32_t)m);
-    for (uint32_t e = 0; e < listed; ++e) {
-        const uint32_t j = index ? index[e] : e;
-        if (j < m)
-            rt::light_settle_record(j, asks, reinterpret_cast<const uint32_t *>(shadow_rays), reinterpret_cast<const uint32_t *>(shadow_hits), reach, pending,
-                                    radiance);
-    }
+    each_listed(index, count, m, [&](uint32_t j) {
+        rt::light_settle_record(j, asks, reinterpret_cast<const uint32_t *>(shadow_rays), reinterpret_cast<const uint32_t *>(shadow_hits), reach, pending, radiance);
+    });
     return RT_OK;
 }
 

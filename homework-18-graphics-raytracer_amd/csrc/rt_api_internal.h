@@ -252,6 +252,21 @@ struct HitSampleArgs {
 };
 RT_API_HIDDEN int hit_sample_args(const char *who, const rt_scene *scene, const HitSampleArgs &a, bool *done);
 
+static inline bool aligned_16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0u; }
+static inline bool aligned_8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0u; }
+
+/* The checks of a path-loop call on listed rt_path records (the path, transmission, connection and light-connection blocks):
+ * hit_sample_args with the record pointer and the list pair — an index comes with its count — among the pointers, `a` stating the
+ * call's own operands and every name of the text, and after everything else the record's alignment. */
+static inline int listed_path_args(const char *who, const rt_scene *scene, const rt_path *d_paths, const uint32_t *d_index, const uint32_t *d_count,
+                                   HitSampleArgs a, bool *done) {
+    a.pointers_ok = a.pointers_ok && d_paths && (d_index == nullptr || d_count != nullptr);
+    const int rc = hit_sample_args(who, scene, a, done);
+    if (rc != RT_OK || *done) return rc;
+    if (!aligned_16(d_paths)) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": d_paths is not 16-byte aligned");
+    return RT_OK;
+}
+
 /* a descriptor's limits (rt::environment_limits, rt::texture_limits) under the entry point's name */
 template <class Desc>
 static inline int check_descriptor(const char *who, const Desc *d, const char *(*limits)(const Desc *, bool *)) {

@@ -11,84 +11,53 @@
  *
  * The arithmetic is rt_connect.h's, shared with librt_host.so, and that header calls rt_environment.h's sampler, rt_lobe.h's densities
  * and weight and rt_shade.h's terms as environment_rays_kernel, lobe_pdf_kernel, environment_pdf_kernel, mis_weigh_kernel and
- * probe_surfaces_kernel call them: the record, the sampling normal and the shadow ray are rt_light_record.h's.  The launch shape is
- * path_advance_kernel's: one listed path per lane, 256 lanes per workgroup; the path record is read as two 16-byte accesses and never
- * written, the hit, the rays and the planes move as dwords.  The table is read by binary search inside the bounds the descriptor's size
- * gives, whatever it holds.  No LDS, no cast, no workspace, no atomics.  The C entry points of the block are at the end of the file.
+ * probe_surfaces_kernel call them: the record, the sampling normal and the shadow ray are rt_light_record.h's.  The launch shape,
+ * the listed slot, the record's codec and the view direction are rt_path_kernel.h's: one listed path per lane; the path record is
+ * read as two 16-byte accesses and never written, the hit, the rays and the planes move as dwords.  The table is read by binary
+ * search inside the bounds the descriptor's size gives, whatever it holds.  No LDS, no cast, no workspace, no atomics.  The C entry
+ * points of the block are at the end of the file.
  */
 #include "rt_api_internal.h"
 #include "rt_connect.h"
-#include "rt_light_record.h"
+#include "rt_path_kernel.h"
 
 namespace rt {
 
-#define RT_CONNECT_THREADS 256u
-#define RT_CONNECT_RAY_DIRECTION 3u /* word of rt_ray.direction */
-
-/* the listed slot of a lane, or m: the lane has nothing to do */
-__device__ __forceinline__ uint32_t connect_slot(const uint32_t *__restrict__ index, const uint32_t *__restrict__ count, const uint32_t m) {
-    const uint64_t lane = (uint64_t)blockIdx.x * RT_CONNECT_THREADS + threadIdx.x;
-    if (lane >= path_listed(index, count, m)) return m;
-    const uint32_t j = index != nullptr ? index[lane] : (uint32_t)lane;
-    return j < m ? j : m; /* an index beyond the slots names nothing, as in rt_cast_rays_indexed */
-}
-
-__device__ __forceinline__ rt_path load_path(const rt_path *__restrict__ paths, const uint32_t j) {
-    const uint4 *const record = reinterpret_cast<const uint4 *>(paths + j);
-    const uint4 lo = record[0], hi = record[1];
-    rt_path p;
-    p.beta[0] = __uint_as_float(lo.x);
-    p.beta[1] = __uint_as_float(lo.y);
-    p.beta[2] = __uint_as_float(lo.z);
-    p.pdf = __uint_as_float(lo.w);
-    p.root = hi.x;
-    p.id = hi.y;
-    p.bounce = hi.z;
-    p.flags = hi.w;
-    return p;
-}
-
-__device__ __forceinline__ V3 ray_direction(const rt_ray *__restrict__ rays, const uint32_t j) {
-    const float *const d = reinterpret_cast<const float *>(rays + j) + RT_CONNECT_RAY_DIRECTION;
-    return v3(d[0], d[1], d[2]);
-}
-
-__global__ __launch_bounds__(RT_CONNECT_THREADS) void path_connect_kernel(const KernelScene sc, const rt_environment e, const void *__restrict__ table,
+__global__ __launch_bounds__(RT_PATH_THREADS) void path_connect_kernel(const KernelScene sc, const rt_environment e, const void *__restrict__ table,
                                                                           const rt_path *__restrict__ paths, const uint32_t m,
                                                                           const uint32_t *__restrict__ index, const uint32_t *__restrict__ count,
                                                                           const rt_hit *__restrict__ hits, const rt_ray *__restrict__ incoming,
                                                                           const PathConnect step, const uint32_t normal_kind,
                                                                           rt_ray *__restrict__ shadow_rays, unsigned char *__restrict__ asks,
                                                                           float *__restrict__ pending) {
-    const uint32_t j = connect_slot(index, count, m);
+    const uint32_t j = path_slot(index, count, m);
     if (j >= m) return;
     const rt_path p = load_path(paths, j);
     if ((p.flags & RT_PATH_ALIVE) == 0u) return;
 
     const LightRecord r = light_record(sc, hits, j);
-    V3 view = v3(0.0f, 0.0f, 1.0f);
-    if (r.valid) view = -ray_direction(incoming, j); /* what get_shade passes as view_direction */
-    const Connection c = path_connect_record(p, r.valid, r.m, r.adj_n, sampling_normal(r, normal_kind), view, e, env_table_view(e, table), step);
+    const Connection c = path_connect_record(p, r.valid, r.m, r.adj_n, sampling_normal(r, normal_kind), view_of(r.valid, incoming, j), e,
+                                             env_table_view(e, table), step);
 
     asks[j] = c.ask ? 1 : 0;
     store_shadow_ray(shadow_rays + j, r, c.dir, c.ask);
     if (c.ask) store_v3(pending, j, c.pending);
 }
 
-__global__ __launch_bounds__(RT_CONNECT_THREADS) void path_settle_kernel(const uint32_t m, const uint32_t *__restrict__ index, const uint32_t *__restrict__ count,
+__global__ __launch_bounds__(RT_PATH_THREADS) void path_settle_kernel(const uint32_t m, const uint32_t *__restrict__ index, const uint32_t *__restrict__ count,
                                                                          unsigned char *__restrict__ asks, const rt_hit *__restrict__ shadow_hits,
                                                                          const float *__restrict__ pending, float *__restrict__ radiance) {
-    const uint32_t j = connect_slot(index, count, m);
+    const uint32_t j = path_slot(index, count, m);
     if (j >= m) return;
     path_settle_record(j, asks, reinterpret_cast<const uint32_t *>(shadow_hits), pending, radiance);
 }
 
-__global__ __launch_bounds__(RT_CONNECT_THREADS) void path_weigh_escape_kernel(const rt_environment e, const void *__restrict__ table,
+__global__ __launch_bounds__(RT_PATH_THREADS) void path_weigh_escape_kernel(const rt_environment e, const void *__restrict__ table,
                                                                                const rt_path *__restrict__ paths, const uint32_t m,
                                                                                const uint32_t *__restrict__ index, const uint32_t *__restrict__ count,
                                                                                const rt_hit *__restrict__ hits, const rt_ray *__restrict__ incoming,
                                                                                const uint32_t heuristic, float *__restrict__ emitted) {
-    const uint32_t j = connect_slot(index, count, m);
+    const uint32_t j = path_slot(index, count, m);
     if (j >= m) return;
     const rt_path p = load_path(paths, j);
     const EnvTable t = env_table_view(e, table);
@@ -101,37 +70,32 @@ __global__ __launch_bounds__(RT_CONNECT_THREADS) void path_weigh_escape_kernel(c
 
 /* ---- the C entry points (include/rt_amd.h "connection queries") ---- */
 
-static bool aligned_16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0u; }
-static bool aligned_8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0u; }
-
 /* the descriptor's checks under the entry point's name */
 static int environment_ok(const char *who, const rt_environment *env) { return check_descriptor(who, env, rt::environment_limits); }
 
-/* what follows hit_sample_args in the two calls that read the record and the table */
-static int record_and_table_ok(const char *who, const rt_path *d_paths, const void *d_table) {
-    if (!aligned_16(d_paths)) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": d_paths is not 16-byte aligned");
+/* what follows listed_path_args in the two calls that read the table */
+static int table_ok(const char *who, const void *d_table) {
     if (!aligned_8(d_table)) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": the table is not 8-byte aligned");
     return RT_OK;
 }
 
 extern "C" {
 
-/* rt_path_advance's checks (hit_sample_args, rt_api_internal.h) on the m slots, with the descriptor after the scene as in
+/* rt_path_advance's checks (listed_path_args, rt_api_internal.h) on the m slots, with the descriptor after the scene as in
  * rt_environment_rays; then the normal_kind, then the heuristic, then the alignment of the record and of the table */
 int rt_path_connect(const rt_scene *scene, const rt_environment *env, const void *d_table, const rt_path *d_paths, size_t m, const uint32_t *d_index,
                     const uint32_t *d_count, const rt_hit *d_hits, const rt_ray *d_incoming, uint32_t seed, uint32_t normal_kind, uint32_t heuristic, int last,
                     rt_ray *d_shadow_rays, unsigned char *d_asks, float *d_pending, void *hip_stream) {
     const char *const who = "rt_path_connect";
     bool done;
-    const int rc = hit_sample_args(who, scene,
-                                   HitSampleArgs(m, d_table && d_paths && (d_index == nullptr || d_count != nullptr) && d_hits && d_incoming && d_shadow_rays &&
-                                                        d_asks && d_pending,
-                                                 "table, path, count (with an index), hit, incoming-ray, ray, flag or pending")
-                                       .described([env, who] { return environment_ok(who, env); }).limits(rt::connect_limits(normal_kind, heuristic)), &done);
+    const int rc = listed_path_args(who, scene, d_paths, d_index, d_count,
+                                    HitSampleArgs(m, d_table && d_hits && d_incoming && d_shadow_rays && d_asks && d_pending,
+                                                  "table, path, count (with an index), hit, incoming-ray, ray, flag or pending")
+                                        .described([env, who] { return environment_ok(who, env); }).limits(rt::connect_limits(normal_kind, heuristic)), &done);
     if (rc != RT_OK || done) return rc;
-    if (const int bad = record_and_table_ok(who, d_paths, d_table)) return bad;
+    if (const int bad = table_ok(who, d_table)) return bad;
     const rt::PathConnect step = {seed, heuristic, last != 0};
-    hipLaunchKernelGGL(rt::path_connect_kernel, grid_of(m, RT_CONNECT_THREADS), dim3(RT_CONNECT_THREADS), 0, static_cast<hipStream_t>(hip_stream), scene->ks, *env,
+    hipLaunchKernelGGL(rt::path_connect_kernel, grid_of(m, RT_PATH_THREADS), dim3(RT_PATH_THREADS), 0, static_cast<hipStream_t>(hip_stream), scene->ks, *env,
                        d_table, d_paths, (uint32_t)m, d_index, d_count, d_hits, d_incoming, step, normal_kind, d_shadow_rays, d_asks, d_pending);
     return launched(who);
 }
@@ -141,12 +105,10 @@ int rt_path_settle(const rt_path *d_paths, size_t m, const uint32_t *d_index, co
                    const float *d_pending, float *d_radiance, void *hip_stream) {
     const char *const who = "rt_path_settle";
     bool done;
-    const int rc = hit_sample_args(who, nullptr,
-                                   HitSampleArgs(m, d_paths && (d_index == nullptr || d_count != nullptr) && d_asks && d_pending && d_radiance,
-                                                 "path, count (with an index), flag, pending or radiance").no_scene(), &done);
+    const int rc = listed_path_args(who, nullptr, d_paths, d_index, d_count,
+                                    HitSampleArgs(m, d_asks && d_pending && d_radiance, "path, count (with an index), flag, pending or radiance").no_scene(), &done);
     if (rc != RT_OK || done) return rc;
-    if (!aligned_16(d_paths)) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": d_paths is not 16-byte aligned");
-    hipLaunchKernelGGL(rt::path_settle_kernel, grid_of(m, RT_CONNECT_THREADS), dim3(RT_CONNECT_THREADS), 0, static_cast<hipStream_t>(hip_stream), (uint32_t)m,
+    hipLaunchKernelGGL(rt::path_settle_kernel, grid_of(m, RT_PATH_THREADS), dim3(RT_PATH_THREADS), 0, static_cast<hipStream_t>(hip_stream), (uint32_t)m,
                        d_index, d_count, d_asks, d_shadow_hits, d_pending, d_radiance);
     return launched(who);
 }
@@ -156,13 +118,12 @@ int rt_path_weigh_escape(const rt_environment *env, const void *d_table, const r
                          const rt_hit *d_hits, const rt_ray *d_incoming, uint32_t heuristic, float *d_emitted, void *hip_stream) {
     const char *const who = "rt_path_weigh_escape";
     bool done;
-    const int rc = hit_sample_args(who, nullptr,
-                                   HitSampleArgs(m, d_table && d_paths && (d_index == nullptr || d_count != nullptr) && d_hits && d_incoming && d_emitted,
-                                                 "table, path, count (with an index), hit, incoming-ray or emitted")
-                                       .no_scene().described([env, who] { return environment_ok(who, env); }).limits(rt::mis_limits(heuristic)), &done);
+    const int rc = listed_path_args(who, nullptr, d_paths, d_index, d_count,
+                                    HitSampleArgs(m, d_table && d_hits && d_incoming && d_emitted, "table, path, count (with an index), hit, incoming-ray or emitted")
+                                        .no_scene().described([env, who] { return environment_ok(who, env); }).limits(rt::mis_limits(heuristic)), &done);
     if (rc != RT_OK || done) return rc;
-    if (const int bad = record_and_table_ok(who, d_paths, d_table)) return bad;
-    hipLaunchKernelGGL(rt::path_weigh_escape_kernel, grid_of(m, RT_CONNECT_THREADS), dim3(RT_CONNECT_THREADS), 0, static_cast<hipStream_t>(hip_stream), *env,
+    if (const int bad = table_ok(who, d_table)) return bad;
+    hipLaunchKernelGGL(rt::path_weigh_escape_kernel, grid_of(m, RT_PATH_THREADS), dim3(RT_PATH_THREADS), 0, static_cast<hipStream_t>(hip_stream), *env,
                        d_table, d_paths, (uint32_t)m, d_index, d_count, d_hits, d_incoming, heuristic, d_emitted);
     return launched(who);
 }

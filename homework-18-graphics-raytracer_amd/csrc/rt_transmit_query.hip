@@ -8,54 +8,35 @@
  *                             ray — or the path's end
  *
  * The arithmetic is rt_transmit.h's, shared with librt_host.so: the entry is rt_refract_entry.h's body, which refract_enter_kernel
- * calls too, the tail rt_path.h's path_step_tail, which path_advance_record calls too.  One listed path per lane, 256 lanes per
- * workgroup; the path record moves as 16-byte accesses (the branch reads and writes its second half alone: it needs no throughput),
- * hits, rays and state as dwords.  The walk's state words are the caller's: they are compared, never indexed with.  No LDS, no cast, no
- * workspace, no atomics.  The C entry points of the block are at the end of the file.
+ * calls too, the tail rt_path.h's path_step_tail, which path_advance_record calls too.  The launch shape, the listed slot, the record's
+ * codec and the "no hit" preset are rt_path_kernel.h's: one listed path per lane, the path record as 16-byte accesses (the branch reads
+ * and writes its second half alone: it needs no throughput), hits, rays and state as dwords.  The walk's state words are the
+ * caller's: they are compared, never indexed with.  No LDS, no cast, no workspace, no atomics.  The C entry points of the block are at
+ * the end of the file.
  */
 #include "rt_api_internal.h"
-#include "rt_cast.h"
-#include "rt_hit_abi.h"
+#include "rt_path_kernel.h"
 #include "rt_transmit.h"
 
 namespace rt {
 
-#define RT_TRANSMIT_THREADS 256u
-#define RT_TRANSMIT_HIT_WORDS 13u
 #define RT_TRANSMIT_RAY_WORDS 11u
-static_assert(sizeof(rt_hit) == RT_TRANSMIT_HIT_WORDS * sizeof(uint32_t), "rt_hit is 13 dwords");
 static_assert(sizeof(rt_ray) == RT_TRANSMIT_RAY_WORDS * sizeof(uint32_t), "rt_ray is 11 dwords");
 
-/* "no hit", as rt_path_advance leaves the vertex of a path that ended */
-__device__ __forceinline__ void store_no_hit(rt_hit *hit) {
-    uint32_t *const preset = reinterpret_cast<uint32_t *>(hit);
-#pragma unroll
-    for (uint32_t k = 0; k < RT_TRANSMIT_HIT_WORDS; ++k) preset[k] = k == 0u ? RT_HIT_NONE : 0u;
-}
-
-/* the listed slot of a lane, or m: the lane has nothing to do */
-__device__ __forceinline__ uint32_t listed_slot(const uint32_t *__restrict__ index, const uint32_t *__restrict__ count, const uint32_t m) {
-    const uint64_t lane = (uint64_t)blockIdx.x * RT_TRANSMIT_THREADS + threadIdx.x;
-    if (lane >= path_listed(index, count, m)) return m;
-    const uint32_t j = index != nullptr ? index[lane] : (uint32_t)lane;
-    return j < m ? j : m; /* an index beyond the slots names nothing, as in rt_cast_rays_indexed */
-}
-
 /* hits is read and, for a path `last` ends, written: not restrict, not const */
-__global__ __launch_bounds__(RT_TRANSMIT_THREADS) void path_branch_kernel(const KernelScene sc, rt_path *__restrict__ paths, const uint32_t m,
+__global__ __launch_bounds__(RT_PATH_THREADS) void path_branch_kernel(const KernelScene sc, rt_path *__restrict__ paths, const uint32_t m,
                                                                           const uint32_t *__restrict__ index, const uint32_t *__restrict__ count, rt_hit *hits,
                                                                           const rt_ray *__restrict__ incoming, const uint32_t seed, const bool last,
                                                                           unsigned char *__restrict__ lobe, unsigned char *__restrict__ transmit,
                                                                           rt_ray *__restrict__ walk_rays, uint32_t *__restrict__ kind, float *__restrict__ travel,
                                                                           uint32_t *__restrict__ casts, unsigned char *__restrict__ walk_flags) {
-    const uint32_t j = listed_slot(index, count, m);
+    const uint32_t j = path_slot(index, count, m);
     if (j >= m) return;
-    uint4 *const record = reinterpret_cast<uint4 *>(paths + j);
-    const uint4 hi = record[1]; /* root, id, bounce, flags */
+    PathTail t = load_path_tail(paths, j);
     bool transmits = false, lobes = false; /* a slot that is not alive: neither */
     uint32_t result = RT_HIT_NONE; /* a slot that does not walk: the state of a finished walk */
     rt_ray inside = no_ray_record();
-    if ((hi.w & RT_PATH_ALIVE) != 0u) {
+    if ((t.flags & RT_PATH_ALIVE) != 0u) {
         const AbiHit h = hit_from_abi(hits + j, sc.n_triangles, sc.n_spheres, sc.n_materials, true);
         float transparency = 0.0f, k = 1.0f;
         if (h.valid) {
@@ -63,9 +44,10 @@ __global__ __launch_bounds__(RT_TRANSMIT_THREADS) void path_branch_kernel(const 
             transparency = mat.transparency;
             k = mat.refraction_index; /* main.rs:354 */
         }
-        transmits = path_transmits(hi.y, hi.z, seed, h.valid, transparency);
+        transmits = path_transmits(t.id, t.bounce, seed, h.valid, transparency);
         if (transmits && last) { /* the path ends here: flags 0, nothing walked, the vertex "no hit" */
-            record[1] = make_uint4(hi.x, hi.y, hi.z, 0u);
+            t.flags = 0u;
+            store_path_tail(paths, j, t);
             store_no_hit(hits + j);
             transmits = false;
         } else if (transmits) {
@@ -85,37 +67,26 @@ __global__ __launch_bounds__(RT_TRANSMIT_THREADS) void path_branch_kernel(const 
 }
 
 /* hits is read (the vertex's material) and, for a path that ends, written: not restrict, not const */
-__global__ __launch_bounds__(RT_TRANSMIT_THREADS) void path_transmit_kernel(const KernelScene sc, rt_path *__restrict__ paths, const uint32_t m,
+__global__ __launch_bounds__(RT_PATH_THREADS) void path_transmit_kernel(const KernelScene sc, rt_path *__restrict__ paths, const uint32_t m,
                                                                             const uint32_t *__restrict__ index, const uint32_t *__restrict__ count, rt_hit *hits,
                                                                             uint32_t *__restrict__ kind, const float *__restrict__ travel,
                                                                             const rt_ray *__restrict__ escape, const PathStep step,
                                                                             rt_ray *__restrict__ next_rays, unsigned char *__restrict__ alive,
                                                                             unsigned char *__restrict__ walk_flags) {
-    const uint32_t j = listed_slot(index, count, m);
+    const uint32_t j = path_slot(index, count, m);
     if (j >= m) return;
     const uint32_t walk = kind[j];
     kind[j] = RT_HIT_NONE; /* stale walk state never walks in a later bounce */
     walk_flags[j] = 0;
-    uint4 *const record = reinterpret_cast<uint4 *>(paths + j);
-    const uint4 lo = record[0], hi = record[1];
-    if ((hi.w & RT_PATH_ALIVE) == 0u) return;
-    rt_path p;
-    p.beta[0] = __uint_as_float(lo.x);
-    p.beta[1] = __uint_as_float(lo.y);
-    p.beta[2] = __uint_as_float(lo.z);
-    p.pdf = __uint_as_float(lo.w);
-    p.root = hi.x;
-    p.id = hi.y;
-    p.bounce = hi.z;
-    p.flags = hi.w;
+    rt_path p = load_path(paths, j);
+    if ((p.flags & RT_PATH_ALIVE) == 0u) return;
 
     const AbiHit h = hit_from_abi(hits + j, sc.n_triangles, sc.n_spheres, sc.n_materials, true);
     float opaque_decay = 0.0f;
     if (h.valid) opaque_decay = material_approx(sc.materials[h.g.obj], h.g.u, h.g.v).opaque_decay;
     const bool lives = path_transmit_record(p, walk, h.valid, opaque_decay, travel[j], step);
 
-    record[0] = make_uint4(__float_as_uint(p.beta[0]), __float_as_uint(p.beta[1]), __float_as_uint(p.beta[2]), __float_as_uint(p.pdf));
-    record[1] = make_uint4(p.root, p.id, p.bounce, p.flags);
+    store_path(paths, j, p);
     alive[j] = lives ? 1 : 0;
     const uint32_t *const from = reinterpret_cast<const uint32_t *>(escape + j);
     uint32_t *const to = reinterpret_cast<uint32_t *>(next_rays + j);
@@ -128,24 +99,20 @@ __global__ __launch_bounds__(RT_TRANSMIT_THREADS) void path_transmit_kernel(cons
 
 /* ---- the C entry points (include/rt_amd.h "transmission queries") ---- */
 
-static bool aligned_16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0u; }
-
 extern "C" {
 
-/* rt_path_advance's checks (hit_sample_args, rt_api_internal.h) on the m slots, then the record's alignment */
+/* rt_path_advance's checks (listed_path_args, rt_api_internal.h) on the m slots, the record's alignment last */
 int rt_path_branch(const rt_scene *scene, rt_path *d_paths, size_t m, const uint32_t *d_index, const uint32_t *d_count, rt_hit *d_hits,
                    const rt_ray *d_incoming, uint32_t seed, int last, unsigned char *d_lobe, unsigned char *d_transmit, rt_ray *d_walk_rays, uint32_t *d_kind,
                    float *d_travel, uint32_t *d_casts, unsigned char *d_walk_flags, void *hip_stream) {
     const char *const who = "rt_path_branch";
     bool done;
-    const int rc = hit_sample_args(who, scene,
-                                   HitSampleArgs(m, d_paths && (d_index == nullptr || d_count != nullptr) && d_hits && d_incoming && d_lobe && d_transmit &&
-                                                        d_walk_rays && d_kind && d_travel && d_casts && d_walk_flags,
-                                                 "path, count (with an index), hit, incoming-ray, lobe, transmit, walk-ray, kind, travel, cast-count or walk-flag"),
-                                   &done);
+    const int rc = listed_path_args(who, scene, d_paths, d_index, d_count,
+                                    HitSampleArgs(m, d_hits && d_incoming && d_lobe && d_transmit && d_walk_rays && d_kind && d_travel && d_casts && d_walk_flags,
+                                                  "path, count (with an index), hit, incoming-ray, lobe, transmit, walk-ray, kind, travel, cast-count or walk-flag"),
+                                    &done);
     if (rc != RT_OK || done) return rc;
-    if (!aligned_16(d_paths)) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": d_paths is not 16-byte aligned");
-    hipLaunchKernelGGL(rt::path_branch_kernel, grid_of(m, RT_TRANSMIT_THREADS), dim3(RT_TRANSMIT_THREADS), 0, static_cast<hipStream_t>(hip_stream), scene->ks,
+    hipLaunchKernelGGL(rt::path_branch_kernel, grid_of(m, RT_PATH_THREADS), dim3(RT_PATH_THREADS), 0, static_cast<hipStream_t>(hip_stream), scene->ks,
                        d_paths, (uint32_t)m, d_index, d_count, d_hits, d_incoming, seed, last != 0, d_lobe, d_transmit, d_walk_rays, d_kind, d_travel, d_casts,
                        d_walk_flags);
     return launched(who);
@@ -157,15 +124,13 @@ int rt_path_transmit(const rt_scene *scene, rt_path *d_paths, size_t m, const ui
                      unsigned char *d_alive, unsigned char *d_walk_flags, void *hip_stream) {
     const char *const who = "rt_path_transmit";
     bool done;
-    const int rc = hit_sample_args(who, scene,
-                                   HitSampleArgs(m, d_paths && (d_index == nullptr || d_count != nullptr) && d_hits && d_kind && d_travel && d_escape &&
-                                                        d_next_rays && d_alive && d_walk_flags,
-                                                 "path, count (with an index), hit, kind, travel, escape-ray, ray, flag or walk-flag")
-                                       .limits(rt::path_limits(RT_HEMISPHERE_SHADING, rr_floor)), &done);
+    const int rc = listed_path_args(who, scene, d_paths, d_index, d_count,
+                                    HitSampleArgs(m, d_hits && d_kind && d_travel && d_escape && d_next_rays && d_alive && d_walk_flags,
+                                                  "path, count (with an index), hit, kind, travel, escape-ray, ray, flag or walk-flag")
+                                        .limits(rt::path_limits(RT_HEMISPHERE_SHADING, rr_floor)), &done);
     if (rc != RT_OK || done) return rc;
-    if (!aligned_16(d_paths)) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": d_paths is not 16-byte aligned");
     const rt::PathStep step = {seed, rr_start, rr_floor, false};
-    hipLaunchKernelGGL(rt::path_transmit_kernel, grid_of(m, RT_TRANSMIT_THREADS), dim3(RT_TRANSMIT_THREADS), 0, static_cast<hipStream_t>(hip_stream), scene->ks,
+    hipLaunchKernelGGL(rt::path_transmit_kernel, grid_of(m, RT_PATH_THREADS), dim3(RT_PATH_THREADS), 0, static_cast<hipStream_t>(hip_stream), scene->ks,
                        d_paths, (uint32_t)m, d_index, d_count, d_hits, d_kind, d_travel, d_escape, step, d_next_rays, d_alive, d_walk_flags);
     return launched(who);
 }

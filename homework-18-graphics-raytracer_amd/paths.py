@@ -76,6 +76,22 @@ def begin(n: int, spp: int, ids=None, out_paths=None, out_radiance=None, device=
     return out_paths, out_radiance
 
 
+def _listed(m, paths, index, count):
+    """the record tensor and the list pair of a listed call, checked: (index, count) as the C call takes them"""
+    _tensor(paths, "paths", "int32", (m, PATH_WORDS))
+    _tensor(index, "index", "int32", (m,), optional=True)  # the call reads up to min(count, M) entries
+    _tensor(count, "count", "int32", (1,), optional=index is None)
+    return _p(index), (_p(count) if index is not None else None)
+
+
+def _asks_out(out_asks, m, dev, stream):
+    """the asks of a connection: slots that are not listed or not alive are not touched, so a new tensor is zeroed here"""
+    if out_asks is None:
+        with _on_stream(stream):
+            out_asks = _new((m,), "uint8", dev).zero_()
+    return _tensor(out_asks, "out_asks", "uint8", (m,))
+
+
 def advance(scene: Scene, paths, hits, incoming, radiance, emitted=None, index=None, count=None, seed: int = 0, normal_kind: int = SHADING,
             rr_start: int = 3, rr_floor: float = 0.05, last: bool = False, out_rays=None, out_alive=None, stream=None):
     """rt_path_advance: one bounce of the listed paths.  ``paths`` (M, 8) int32, ``hits`` (a Hits or its (M, 13) int32 records: the
@@ -92,15 +108,13 @@ def advance(scene: Scene, paths, hits, incoming, radiance, emitted=None, index=N
     ended leaves a "no hit" record.  Slots that are not listed or not alive are not touched in any of them."""
     records = _hit_records(hits)
     m, dev = records.shape[0], records.device
-    _tensor(paths, "paths", "int32", (m, PATH_WORDS))
+    index_p, count_p = _listed(m, paths, index, count)
     _tensor(incoming, "incoming", "int32", (m, 11))
     _tensor(radiance, "radiance", "float32", (m, 3))
     _tensor(emitted, "emitted", "float32", (m, 3), optional=True)
-    _tensor(index, "index", "int32", (m,), optional=True)  # the call reads up to min(count, M) entries
-    _tensor(count, "count", "int32", (1,), optional=index is None)
     out_rays = _out_tensor(out_rays, (m, 11), "int32", dev, "out_rays")
     out_alive = _out_tensor(out_alive, (m,), "uint8", dev, "out_alive")
-    _capi.check(_capi.amd_lib().rt_path_advance(scene._h, _p(paths), m, _p(index), _p(count) if index is not None else None, _p(records), _p(incoming),
+    _capi.check(_capi.amd_lib().rt_path_advance(scene._h, _p(paths), m, index_p, count_p, _p(records), _p(incoming),
                                                 _p(emitted), int(seed) & 0xFFFFFFFF, int(normal_kind), int(rr_start) & 0xFFFFFFFF, float(rr_floor),
                                                 int(bool(last)), _p(radiance), _p(out_rays), _p(out_alive), _stream_ptr(stream)))
     return out_rays, out_alive
@@ -123,13 +137,6 @@ def resolve(radiance, n: int, spp: int, out=None, root=None, stream=None):
 
 # ---- transmission (include/rt_amd.h "transmission queries") ----
 
-def _listed(m, dev, paths, index, count):
-    _tensor(paths, "paths", "int32", (m, PATH_WORDS))
-    _tensor(index, "index", "int32", (m,), optional=True)  # the call reads up to min(count, M) entries
-    _tensor(count, "count", "int32", (1,), optional=index is None)
-    return _p(index), (_p(count) if index is not None else None)
-
-
 def branch(scene: Scene, paths, hits, incoming, index=None, count=None, seed: int = 0, last: bool = False, out_lobe=None, out_transmit=None,
            out_walk_rays=None, out_kind=None, out_travel=None, out_casts=None, out_walk_flags=None, stream=None):
     """rt_path_branch: per listed live path the choice between the vertex's lobes and its glass — it transmits iff the vertex is a hit
@@ -142,7 +149,7 @@ def branch(scene: Scene, paths, hits, incoming, index=None, count=None, seed: in
     listed are not touched."""
     records = _hit_records(hits)
     m, dev = records.shape[0], records.device
-    index_p, count_p = _listed(m, dev, paths, index, count)
+    index_p, count_p = _listed(m, paths, index, count)
     _tensor(incoming, "incoming", "int32", (m, 11))
     out_lobe = _out_tensor(out_lobe, (m,), "uint8", dev, "out_lobe")
     out_transmit = _out_tensor(out_transmit, (m,), "uint8", dev, "out_transmit")
@@ -167,7 +174,7 @@ def transmit(scene: Scene, paths, hits, kind, travel, escape, walk_flags, index=
     and ``walk_flags`` of every listed slot are left HIT_NONE and 0.  Slots that are not listed are not touched."""
     records = _hit_records(hits)
     m, dev = records.shape[0], records.device
-    index_p, count_p = _listed(m, dev, paths, index, count)
+    index_p, count_p = _listed(m, paths, index, count)
     _tensor(kind, "kind", "int32", (m,))
     _tensor(travel, "travel", "float32", (m,))
     _tensor(escape, "escape", "int32", (m, 11))
@@ -201,14 +208,11 @@ def connect(scene: Scene, env: Environment, paths, hits, incoming, index=None, c
     env = _environment(env)
     records = _hit_records(hits)
     m, dev = records.shape[0], records.device
-    index_p, count_p = _listed(m, dev, paths, index, count)
+    index_p, count_p = _listed(m, paths, index, count)
     _tensor(incoming, "incoming", "int32", (m, 11))
     table = _table(env, table, stream)
     out_rays = _out_tensor(out_rays, (m, 11), "int32", dev, "out_rays")
-    if out_asks is None:
-        with _on_stream(stream):
-            out_asks = _new((m,), "uint8", dev).zero_()
-    _tensor(out_asks, "out_asks", "uint8", (m,))
+    out_asks = _asks_out(out_asks, m, dev, stream)
     out_pending = _out_tensor(out_pending, (m, 3), "float32", dev, "out_pending")
     _capi.check(_capi.amd_lib().rt_path_connect(scene._h, C.byref(env.desc), _p(table), _p(paths), m, index_p, count_p, _p(records), _p(incoming),
                                                 int(seed) & 0xFFFFFFFF, int(normal_kind), int(heuristic), int(bool(last)), _p(out_rays), _p(out_asks),
@@ -221,8 +225,8 @@ def settle(paths, asks, pending, radiance, shadow_hits=None, index=None, count=N
     what the cast of connect's rays found; None: nothing occludes) is "no hit" at all; the ask is cleared either way.  To be called after
     advance, so that a vertex's deposit is added before its connection.  ``paths`` is not read: a path advance ended still settles.
     Returns ``radiance``."""
-    m, dev = _tensor(asks, "asks", "uint8", (None,)).shape[0], asks.device
-    index_p, count_p = _listed(m, dev, paths, index, count)
+    m = _tensor(asks, "asks", "uint8", (None,)).shape[0]
+    index_p, count_p = _listed(m, paths, index, count)
     _tensor(shadow_hits, "shadow_hits", "int32", (m, 13), optional=True)
     _tensor(pending, "pending", "float32", (m, 3))
     _tensor(radiance, "radiance", "float32", (m, 3))
@@ -239,7 +243,7 @@ def weigh_escape(env: Environment, paths, hits, incoming, emitted, index=None, c
     env = _environment(env)
     records = _hit_records(hits)
     m, dev = records.shape[0], records.device
-    index_p, count_p = _listed(m, dev, paths, index, count)
+    index_p, count_p = _listed(m, paths, index, count)
     _tensor(incoming, "incoming", "int32", (m, 11))
     _tensor(emitted, "emitted", "float32", (m, 3))
     table = _table(env, table, stream)
@@ -283,16 +287,13 @@ def connect_lights(scene: Scene, paths, hits, incoming, index=None, count=None, 
     ``out_asks`` is zeroed here if not given."""
     records = _hit_records(hits)
     m, dev = records.shape[0], records.device
-    index_p, count_p = _listed(m, dev, paths, index, count)
+    index_p, count_p = _listed(m, paths, index, count)
     _tensor(incoming, "incoming", "int32", (m, 11))
     first, lights = _light_range(scene, light_first, light_count)
     _tensor(radii, "radii", "float32", (lights,), optional=True)
     _tensor(weights, "weights", "float32", (lights,), optional=True)
     out_rays = _out_tensor(out_rays, (m, 11), "int32", dev, "out_rays")
-    if out_asks is None:
-        with _on_stream(stream):
-            out_asks = _new((m,), "uint8", dev).zero_()
-    _tensor(out_asks, "out_asks", "uint8", (m,))
+    out_asks = _asks_out(out_asks, m, dev, stream)
     out_pending = _out_tensor(out_pending, (m, 3), "float32", dev, "out_pending")
     out_reach = _out_tensor(out_reach, (m,), "float32", dev, "out_reach")
     _tensor(out_chosen, "out_chosen", "int32", (m,), optional=True)
@@ -308,8 +309,8 @@ def settle_lights(paths, asks, shadow_rays, reach, pending, radiance, shadow_hit
     hit lies nearer to the ray's origin than ``reach`` — get_shade's rule; the ask is cleared either way.  To be called after advance, so
     that a vertex's deposit is added before its connection.  ``paths`` is not read: a path advance ended still settles.  Returns
     ``radiance``."""
-    m, dev = _tensor(asks, "asks", "uint8", (None,)).shape[0], asks.device
-    index_p, count_p = _listed(m, dev, paths, index, count)
+    m = _tensor(asks, "asks", "uint8", (None,)).shape[0]
+    index_p, count_p = _listed(m, paths, index, count)
     _tensor(shadow_rays, "shadow_rays", "int32", (m, 11))
     _tensor(shadow_hits, "shadow_hits", "int32", (m, 13), optional=True)
     _tensor(reach, "reach", "float32", (m,))
@@ -322,13 +323,39 @@ def settle_lights(paths, asks, shadow_rays, reach, pending, radiance, shadow_hit
 
 # ---- the CPU forms ----
 
-def _host_paths(paths):
+def _host_paths(paths, m=None):
+    """a copy of the records as a PATH_DTYPE array; ``m``: how many there must be"""
     a = np.ascontiguousarray(paths)
     if a.dtype == PATH_DTYPE:
-        return a.reshape(-1).copy()
-    if a.ndim == 2 and a.shape[1] == PATH_WORDS and a.dtype.itemsize == 4:
-        return a.view(PATH_DTYPE).reshape(-1).copy()
-    raise ValueError("paths: expected a PATH_DTYPE array or an (M, 8) array of 4-byte words")
+        a = a.reshape(-1).copy()
+    elif a.ndim == 2 and a.shape[1] == PATH_WORDS and a.dtype.itemsize == 4:
+        a = a.view(PATH_DTYPE).reshape(-1).copy()
+    else:
+        raise ValueError("paths: expected a PATH_DTYPE array or an (M, 8) array of 4-byte words")
+    if m is not None and a.shape[0] != m:
+        raise ValueError(f"paths: expected {m} records")
+    return a
+
+
+def _host_list(index, count, m):
+    """(index, count) as the C forms take them: ``index`` padded to M entries that name nothing, ``count`` one u32"""
+    if index is None:
+        return None, None
+    index = np.ascontiguousarray(index).reshape(-1)
+    given = _host(index, np.uint32, index.shape, "index")[:m]
+    padded = np.full(m, 0xFFFFFFFF, dtype=np.uint32)  # the C form reads up to min(count, M) entries: the rest name nothing
+    padded[:given.shape[0]] = given
+    return padded, np.array([given.shape[0] if count is None else int(count) & 0xFFFFFFFF], dtype=np.uint32)
+
+
+def _host_shadow_hits(shadow_hits, m):
+    """the shadow hits of a settlement as HIT_DTYPE records, or None: nothing occludes"""
+    if shadow_hits is None:
+        return None
+    shadow_hits = _host_records(shadow_hits, HIT_DTYPE, 13, "shadow_hits")
+    if shadow_hits.shape[0] != m:
+        raise ValueError(f"shadow_hits: expected {m} records")
+    return shadow_hits
 
 
 def begin_numpy(n: int, spp: int, ids=None):
@@ -351,23 +378,15 @@ def advance_numpy(surfaces, view, paths, radiance, emitted=None, index=None, cou
     m = surfaces.shape[0]
     view = _host(view, np.float32, (m, 3), "view")
     normals = _host(normals, np.float32, (m, 3), "normals", optional=True)
-    paths = _host_paths(paths)
-    if paths.shape[0] != m:
-        raise ValueError(f"paths: expected {m} records")
+    paths = _host_paths(paths, m)
     radiance = _host(radiance, np.float32, (m, 3), "radiance").copy()
     emitted = _host(emitted, np.float32, (m, 3), "emitted", optional=True)
     dirs = np.zeros((m, 3), dtype=np.float32) if dirs is None else _host(dirs, np.float32, (m, 3), "dirs").copy()
     alive = np.zeros(m, dtype=np.uint8) if alive is None else _host(alive, np.uint8, (m,), "alive").copy()
-    if index is not None:
-        index = np.ascontiguousarray(index).reshape(-1)
-        given = _host(index, np.uint32, index.shape, "index")[:m]
-        index = np.full(m, 0xFFFFFFFF, dtype=np.uint32)  # the C form reads up to min(count, M) entries: the rest name nothing
-        index[:given.shape[0]] = given
-        count = np.array([given.shape[0] if count is None else int(count) & 0xFFFFFFFF], dtype=np.uint32)
-    _capi.check_host(_capi.host_lib().rt_path_advance_cpu(_void(surfaces), _void(normals), _void(view), _void(paths), m, _void(index),
-                                                          _void(count) if index is not None else None, _void(emitted), int(seed) & 0xFFFFFFFF,
-                                                          int(rr_start) & 0xFFFFFFFF, float(rr_floor), int(bool(last)), _void(radiance), _void(dirs),
-                                                          _void(alive)))
+    index, count = _host_list(index, count, m)
+    _capi.check_host(_capi.host_lib().rt_path_advance_cpu(_void(surfaces), _void(normals), _void(view), _void(paths), m, _void(index), _void(count),
+                                                          _void(emitted), int(seed) & 0xFFFFFFFF, int(rr_start) & 0xFFFFFFFF, float(rr_floor),
+                                                          int(bool(last)), _void(radiance), _void(dirs), _void(alive)))
     return paths, radiance, dirs, alive
 
 
@@ -382,17 +401,6 @@ def resolve_numpy(radiance, n: int, spp: int, rgb=None, root=None) -> np.ndarray
         raise ValueError("rgb: expected an (R, 3) float32 array that holds every root's slot")
     _capi.check_host(_capi.host_lib().rt_path_resolve_cpu(_void(radiance), n, spp, _void(root), _void(rgb)))
     return rgb
-
-
-def _host_list(index, count, m):
-    """(index, count) as the C forms take them: ``index`` padded to M entries that name nothing, ``count`` one u32"""
-    if index is None:
-        return None, None
-    index = np.ascontiguousarray(index).reshape(-1)
-    given = _host(index, np.uint32, index.shape, "index")[:m]
-    padded = np.full(m, 0xFFFFFFFF, dtype=np.uint32)  # the C form reads up to min(count, M) entries: the rest name nothing
-    padded[:given.shape[0]] = given
-    return padded, np.array([given.shape[0] if count is None else int(count) & 0xFFFFFFFF], dtype=np.uint32)
 
 
 def _start(a, dtype, shape, name, fill=0):
@@ -430,9 +438,7 @@ def transmit_numpy(surfaces, paths, kind, travel, escape, index=None, count=None
     walk_flags); ``rays``, ``alive`` and ``walk_flags`` as given (zeros if None) where a slot is not touched."""
     surfaces = _host_surfaces(surfaces)
     m = surfaces.shape[0]
-    paths = _host_paths(paths)
-    if paths.shape[0] != m:
-        raise ValueError(f"paths: expected {m} records")
+    paths = _host_paths(paths, m)
     kind = _host(kind, np.uint32, (m,), "kind").copy()
     travel = _host(travel, np.float32, (m,), "travel")
     escape = _host(escape, np.uint32, (m, 11), "escape")
@@ -467,9 +473,7 @@ def connect_numpy(surfaces, view, texels, table, paths, index=None, count=None, 
     normals = _host(normals, np.float32, (m, 3), "normals", optional=True)
     texels, desc = _host_environment(texels, rotation, scale, 0)
     held = _host_table(texels, table)
-    paths = _host_paths(paths)
-    if paths.shape[0] != m:
-        raise ValueError(f"paths: expected {m} records")
+    paths = _host_paths(paths, m)
     dirs, asks, pending = _start(dirs, np.float32, (m, 3), "dirs"), _start(asks, np.uint8, (m,), "asks"), _start(pending, np.float32, (m, 3), "pending")
     index, count = _host_list(index, count, m)
     _capi.check_host(_capi.host_lib().rt_path_connect_cpu(_void(surfaces), _void(normals), _void(view), C.byref(desc), _void(held), _void(paths), m,
@@ -485,10 +489,7 @@ def settle_numpy(asks, pending, radiance, shadow_hits=None, index=None, count=No
     m = asks.shape[0]
     pending = _host(pending, np.float32, (m, 3), "pending")
     radiance = _host(radiance, np.float32, (m, 3), "radiance").copy()
-    if shadow_hits is not None:
-        shadow_hits = _host_records(shadow_hits, HIT_DTYPE, 13, "shadow_hits")
-        if shadow_hits.shape[0] != m:
-            raise ValueError(f"shadow_hits: expected {m} records")
+    shadow_hits = _host_shadow_hits(shadow_hits, m)
     paths = np.zeros(max(m, 1), dtype=PATH_DTYPE)  # not read
     index, count = _host_list(index, count, m)
     _capi.check_host(_capi.host_lib().rt_path_settle_cpu(_void(paths), m, _void(index), _void(count), _void(asks), _void(shadow_hits), _void(pending),
@@ -539,9 +540,7 @@ def connect_lights_numpy(surfaces, positions, view, lights, paths, index=None, c
     radii = _host(radii, np.float32, (n_range,), "radii", optional=True)
     weights = _host(weights, np.float32, (n_range,), "weights", optional=True)
     aux = _host(aux, np.float32, (len(lights), 2), "aux", optional=True)
-    paths = _host_paths(paths)
-    if paths.shape[0] != m:
-        raise ValueError(f"paths: expected {m} records")
+    paths = _host_paths(paths, m)
     dirs, asks, pending = _start(dirs, np.float32, (m, 3), "dirs"), _start(asks, np.uint8, (m,), "asks"), _start(pending, np.float32, (m, 3), "pending")
     reach, chosen = _start(reach, np.float32, (m,), "reach"), _start(chosen, np.uint32, (m,), "chosen", NO_LIGHT)
     index, count = _host_list(index, count, m)
@@ -563,10 +562,7 @@ def settle_lights_numpy(asks, shadow_rays, reach, pending, radiance, shadow_hits
     reach = _host(reach, np.float32, (m,), "reach")
     pending = _host(pending, np.float32, (m, 3), "pending")
     radiance = _host(radiance, np.float32, (m, 3), "radiance").copy()
-    if shadow_hits is not None:
-        shadow_hits = _host_records(shadow_hits, HIT_DTYPE, 13, "shadow_hits")
-        if shadow_hits.shape[0] != m:
-            raise ValueError(f"shadow_hits: expected {m} records")
+    shadow_hits = _host_shadow_hits(shadow_hits, m)
     paths = np.zeros(max(m, 1), dtype=PATH_DTYPE)  # not read
     index, count = _host_list(index, count, m)
     _capi.check_host(_capi.host_lib().rt_path_settle_lights_cpu(_void(paths), m, _void(index), _void(count), _void(asks), _void(shadow_rays),
@@ -575,6 +571,13 @@ def settle_lights_numpy(asks, shadow_rays, reach, pending, radiance, shadow_hits
 
 
 # ---- the loop ----
+
+def _connection_buffers(k, device):
+    """what a sky connection and a light connection both keep for ``k`` paths: (shadow rays, shadow hits, asks — zeroed —, pending, the
+    second index, its count)"""
+    return (_new((k, 11), "int32", device), _new((k, 13), "int32", device), _new((k,), "uint8", device).zero_(), _new((k, 3), "float32", device),
+            _new((k,), "int32", device), _new((1,), "int32", device))
+
 
 class Workspace:
     """The buffers of trace_paths, made once by workspace() so that a caller's loop allocates nothing: ``entries`` paths of room, about
@@ -593,16 +596,13 @@ class Workspace:
         self.light_connections = lc = int(light_connections)
         self.light_chosen = None
         if lc:
-            self.light_shadow_rays, self.light_shadow_hits = _new((lc, 11), "int32", device), _new((lc, 13), "int32", device)
-            self.light_asks, self.light_pending = _new((lc,), "uint8", device).zero_(), _new((lc, 3), "float32", device)
+            (self.light_shadow_rays, self.light_shadow_hits, self.light_asks, self.light_pending, self.light_ask_index,
+             self.light_ask_count) = _connection_buffers(lc, device)
             self.light_reach = _new((lc,), "float32", device)
-            self.light_ask_index, self.light_ask_count = _new((lc,), "int32", device), _new((1,), "int32", device)
             if chosen:
                 self.light_chosen = _new((lc,), "int32", device)
         if connections:
-            self.shadow_rays, self.shadow_hits = _new((connections, 11), "int32", device), _new((connections, 13), "int32", device)
-            self.asks, self.pending = _new((connections,), "uint8", device).zero_(), _new((connections, 3), "float32", device)
-            self.ask_index, self.ask_count = _new((connections,), "int32", device), _new((1,), "int32", device)
+            self.shadow_rays, self.shadow_hits, self.asks, self.pending, self.ask_index, self.ask_count = _connection_buffers(connections, device)
         self.paths, self.radiance = _new((entries, PATH_WORDS), "int32", device), _new((entries, 3), "float32", device)
         self.hits, self.emitted = _new((entries, 13), "int32", device), _new((entries, 3), "float32", device)
         self.rays, self.next_rays = _new((entries, 11), "int32", device), _new((entries, 11), "int32", device)

@@ -124,6 +124,7 @@ CASES = [  # ids, index, count, kind, rr_start, last, emitted, bounce
     dict(index="half", count=0),
     dict(index="half", count=1, ids=True, rr_start=0),
     dict(index="all", count="above", bounce=3, rr_start=2),
+    dict(index="beyond", count="above", ids=True),  # every third entry names a slot >= n, and the padding is read too: they name nothing
 ]
 
 
@@ -157,7 +158,9 @@ def test_the_three_calls_are_their_cpu_forms(ref, n):
         emitted = None if case.get("emitted") is False else rng.random((n, 3)).astype(F32)
         index = count = None
         if case.get("index"):
-            index = rng.permutation(n)[:max(1, n // 2) if case["index"] == "half" else n].astype(np.uint32)
+            index = rng.permutation(n)[:n if case["index"] == "all" else max(1, n // 2)].astype(np.uint32)
+            if case["index"] == "beyond":
+                index[::3] = n + 5 + np.arange(len(index[::3]), dtype=np.uint32)
             count = {"all": len(index), "above": n + 1000}.get(case["count"], case["count"])
         got_paths, got_radiance, got_rays, got_alive, got_hits = run_advance(ref, rows, before, start, emitted, index, count, seed, kind, rr_start, rr_floor, last)
         poison_dirs = np.full((n, 3), 7.0, dtype=F32)
